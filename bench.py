@@ -9,8 +9,13 @@ Algorithmic bytes: 16 B per coefficient per transform (8 read + 8 written; SURVE
 job (all ranks), `roofline` prices the forward transform (its two kernels back to back) against the
 8 TB/s HBM peak, measured with HIP events on the stream the kernels run on.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else: the
+per-direction kernel times and the roofline, the round-trip check, the CPU baseline, the NTT on MOAI's chain, the
+configs[2] key switch and the end-to-end slice (with N > 1 ranks: one encoder layer per GPU).  --dump-outputs DIR writes
+a fixed, seeded sample of the residues the last timed step left in the batch (what a caller of the path receives) as .npy.
 
 Multi-GPU: every rank owns an independent batch (the path shards on the ciphertext index with no
 exchange step); torch.distributed is used only for the barrier and the max-over-ranks
@@ -49,7 +54,13 @@ def main():
     ap.add_argument("--layer-timeout", type=float, default=330.0)
     ap.add_argument("--no-keyswitch", action="store_true", help="skip the configs[2] key-switch region")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (roofline, CPU baseline, MOAI's chain, key switch, "
+                         "end-to-end slice); the --no-* options above select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of what the last timed step computed to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -98,7 +109,7 @@ def main():
         ctx.ntt_inverse(ptr, n_poly, L, stream=stream)
 
     # keep a sample to verify the round trip and parity after the timed region
-    sample_before = data[0, 0, :, :].clone()
+    sample_before = data[0, 0, :, :].clone() if args.full else None
 
     for _ in range(args.warmup):
         step()
@@ -113,23 +124,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = m.shard.max_over_ranks(time.perf_counter() - t0, dist, dev)
 
-    # round trip must be the identity (bit exact)
-    assert torch.equal(data[0, 0, :, :], sample_before), "INTT(NTT(x)) != x"
-
-    # per-direction kernel time with HIP events on the launch stream (outside the timed region)
-    ev = [m.hip.Event() for _ in range(3)]
-    reps = 5
-    fwd_ms, inv_ms = [], []
-    for _ in range(reps):
-        ev[0].record(stream)
-        ctx.ntt_forward(ptr, n_poly, L, stream=stream)
-        ev[1].record(stream)
-        ctx.ntt_inverse(ptr, n_poly, L, stream=stream)
-        ev[2].record(stream)
-        fwd_ms.append(ev[1].elapsed_ms_since(ev[0]))
-        inv_ms.append(ev[2].elapsed_ms_since(ev[1]))
-    fwd = sum(fwd_ms) / reps
-    inv = sum(inv_ms) / reps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, data, np, torch)
 
     coeffs = n_poly * L * N
     bytes_dir = 16.0 * coeffs
@@ -161,7 +157,11 @@ def main():
             "bytes_per_coeff_per_transform": 16,
         },
     }
-    if rank == 0:
+    if args.full:
+        # round trip must be the identity (bit exact), on every rank
+        assert torch.equal(data[0, 0, :, :], sample_before), "INTT(NTT(x)) != x"
+        fwd, inv = direction_ms(m, ctx, ptr, n_poly, stream)
+    if rank == 0 and args.full:
         achieved = bytes_dir / (fwd * 1e-3) / 1e9
         out["roofline"] = {
             # which roof binds is a measured statement (profiles/r03_ntt_pmc_summary.json: the vector ALUs are busy most of the
@@ -207,7 +207,7 @@ def main():
                 out["e2e"] = {"skipped": "end_to_end_slice raised %r" % (e,)}
     # N > 1, the metric's first half: one independent packed batch (256 inputs, its own keys) per GPU -- replicas only, no
     # collective.  Every rank frees its device memory and runs the whole-layer child bound to its own GPU.
-    if world > 1 and not args.no_e2e and not args.no_layer:
+    if world > 1 and args.full and not args.no_e2e and not args.no_layer:
         del data, sample_before
         ctx.close()
         torch.cuda.empty_cache()
@@ -227,6 +227,40 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # residues in --dump-outputs' sample: 2 x 8 MB of float64 halves + 8 MB of indices
+
+
+def dump_outputs(path, data, np, torch):
+    """The batch after the last timed step, sampled at DUMP_SAMPLE positions drawn by a fixed seed: residue_hi32 / residue_lo32
+    are the high and low 32 bits of each 60-bit residue (float64 holds them exactly), index the flat position in the
+    [ciphertext][poly][prime][coefficient] layout.  The step is a forward transform followed by its inverse in place, so a
+    correct step leaves the seeded input: matching dumps show that two builds return the same batch, not that their
+    transforms are right (a step that did nothing, or a forward and an inverse wrong in matching ways, would dump the same;
+    --full checks the round trip and the transforms' parity with the CPU oracle)."""
+    os.makedirs(path, exist_ok=True)
+    flat = data.view(-1)
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=min(DUMP_SAMPLE, flat.numel()), replace=False))
+    vals = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().view(np.uint64)
+    np.save(os.path.join(path, "residue_hi32.npy"), (vals >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "residue_lo32.npy"), (vals & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+
+
+def direction_ms(m, ctx, ptr, n_poly, stream, reps=5):
+    """Per-direction kernel time (ms) with HIP events on the launch stream, outside the timed region."""
+    ev = [m.hip.Event() for _ in range(3)]
+    fwd_ms, inv_ms = [], []
+    for _ in range(reps):
+        ev[0].record(stream)
+        ctx.ntt_forward(ptr, n_poly, L, stream=stream)
+        ev[1].record(stream)
+        ctx.ntt_inverse(ptr, n_poly, L, stream=stream)
+        ev[2].record(stream)
+        fwd_ms.append(ev[1].elapsed_ms_since(ev[0]))
+        inv_ms.append(ev[2].elapsed_ms_since(ev[1]))
+    return sum(fwd_ms) / reps, sum(inv_ms) / reps
 
 
 def batch_of_rank(batch, rank, world, split, shard):

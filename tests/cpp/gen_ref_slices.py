@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Build-time comparator source: cuts the definitions of a few functions out of the reference checkout
-(/root/reference/include/source/bootstrapping/Bootstrapper.cpp and common/func.cpp) into
-tests/cpp/generated/ref_bootstrapper_slices.inc, which is git-ignored and never committed.  The test binaries that
-include it (through tests/cpp/ref_bootstrapper.h) are built in the container that holds the reference and travel to the
-GPU box prebuilt, like test_moai_headers.  Nothing of the reference's text lives in this repository.
+"""Build-time comparator source: cuts the definitions of a few functions out of a reference checkout
+(include/source/bootstrapping/Bootstrapper.cpp and common/func.cpp) into the include named by the second argument
+(oracle/Makefile, target ref_bootstrap: oracle/_ref/generated/, git-ignored, deleted once compiled).  The test binaries
+that include it (through tests/cpp/ref_bootstrapper.h) record the digests tests/golden/bootstrap_ref_digests.txt holds
+(tests/cpp/ref_golden.h).  Nothing of the reference's text lives in this repository.
 
 The sliced routines are the evaluation half of bootstrap_3 that needs no NTL: the two baby-step / giant-step transforms,
 sflinv_full_3 / sfl_full_3, coefftoslot_full_3 / slottocoeff_full_3 and bootstrap_full_3.  They are compiled against the

@@ -1,14 +1,15 @@
 // tests/cpp/ref_bootstrapper.h -- test-side comparator: the reference's OWN source text for the evaluation half of
-// Bootstrapper::bootstrap_3, cut out of the reference checkout at build time (tests/cpp/gen_ref_slices.py ->
-// tests/cpp/generated/ref_bootstrapper_slices.inc, git-ignored, never committed, never shipped to the GPU box as text) and
-// compiled here against the seal:: shim inside namespace refslice.  This header only declares the class those
+// Bootstrapper::bootstrap_3, cut out of a reference checkout at build time (oracle/Makefile, target ref_bootstrap:
+// tests/cpp/gen_ref_slices.py -> oracle/_ref/generated/ref_bootstrapper_slices.inc, git-ignored, never committed, deleted once
+// compiled) and compiled against the seal:: shim inside namespace refslice.  This header only declares the class those
 // definitions belong to -- the members they read (Bootstrapper.h:16-48) -- and supplies the one routine that is not
 // sliced: modraise_inplace writes raw residues through seal::util::iter(Ciphertext) (Bootstrapper.cpp:2973-2988),
 // which a device-resident ciphertext does not offer, so it goes through moai_modraise (checked against the oracle in
 // tests/test_gpu_parity.py::test_modraise).
 //
-// Use: a binary built where the reference checkout exists runs the reference's call sequence, one ciphertext at a time,
-// through the shim's evaluator, and the packed device pipeline is compared with it bit for bit.
+// Use: a binary built where the reference checkout exists (MOAI_REF_SLICES) runs the reference's call sequence, one ciphertext
+// at a time, through the shim's evaluator, compares the packed device pipeline with it bit for bit and prints the digests the
+// in-tree build compares with (tests/cpp/ref_golden.h).
 #pragma once
 #include <cmath>
 #include <complex>

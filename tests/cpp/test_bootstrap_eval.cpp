@@ -1,6 +1,7 @@
 // test_bootstrap_eval.cpp -- seal/moai_bootstrap_eval.h: the evaluation half of Bootstrapper::bootstrap_full_3 on
 // packed ciphertexts.  The reference's Bootstrapper cannot be built here (NTL), so nothing below compares with its
-// output ("parity unpinned" for the constants); what is checked:
+// output ("parity unpinned" for the constants); what is checked (4. directly where the reference's transform routines are
+// built in, MOAI_REF_SLICES, by recorded digests elsewhere: tests/cpp/ref_golden.h):
 //   1. host only (also run by the CPU test suite with --host-only): babycount's choice for MOAI's degree 59, the
 //      shape of the quotient / remainder heap, and that recombining the leaves gives back the polynomial;
 //   2. ModularReducer3::modular_reduction decrypts to the value of the polynomial with its double-angle steps,
@@ -31,7 +32,10 @@ static int g_fail = 0;
         }                                                                  \
     } while (0)
 
+#ifdef MOAI_REF_SLICES
 #include "ref_bootstrapper.h" // the reference's own transform routines, sliced from the checkout at build time
+#endif
+#include "ref_golden.h"
 
 using namespace seal;
 using namespace std;
@@ -125,6 +129,7 @@ int main(int argc, char **argv)
     parms.set_coeff_modulus(CoeffModulus::Create(n, bits));
     parms.set_secret_key_hamming_weight(32);
     SEALContext context(parms, true, sec_level_type::none);
+    refgolden::FixedRandomness fixed(11);
     KeyGenerator keygen(context);
     SecretKey sk = keygen.secret_key();
     PublicKey pk;
@@ -136,12 +141,14 @@ int main(int argc, char **argv)
     moai_fused::boot_rotation_steps_3(logn, logn, steps);
     GaloisKeys gal_keys;
     keygen.create_galois_keys(steps, gal_keys);
+    fixed.release();
     CKKSEncoder encoder(context);
     Encryptor encryptor(context, pk);
     Decryptor decryptor(context, sk);
     Evaluator evaluator(context, encoder);
     const double scale = pow(2.0, 42);
     const int Nh = (int)encoder.slot_count();
+#ifdef MOAI_REF_SLICES
     refslice::Bootstrapper ref(logn, logn, scale, context, encoder, evaluator, gal_keys);
     auto ref_bsgs = [&](Evaluator &, GaloisKeys &, int, Ciphertext &out, Ciphertext &in, int totlen, int basicstep, int coeff_logn,
                         const vector<vector<complex<double>>> &coeff) { ref.bsgs_linear_transform(out, in, totlen, basicstep, coeff_logn, coeff); };
@@ -149,6 +156,7 @@ int main(int argc, char **argv)
                                 const vector<vector<complex<double>>> &coeff) {
         ref.rotated_bsgs_linear_transform(out, in, totlen, basicstep, coeff_logn, coeff);
     };
+#endif
     mt19937_64 rng(11);
     uniform_real_distribution<double> ud(-1.0, 1.0);
 
@@ -261,10 +269,14 @@ int main(int argc, char **argv)
         moai_fused::unpack(packed_out, context, got);
 
         // the reference's sequence on one ciphertext
+#ifdef MOAI_REF_SLICES
         const auto &modulus = context.first_context_data()->parms().coeff_modulus();
         const int bs_inv[3] = { 1 << (logn - p), 1 << (logn - 2 * p), 1 }, bs_fwd[3] = { 1, 1 << p, 1 << (2 * p) };
+#endif
         for (int b = 0; b < B; b++)
         {
+            const string name = "eval.bootstrap_3.ct" + to_string(b);
+#ifdef MOAI_REF_SLICES
             Ciphertext cipher = cts[b];
             const double initial_scale = cipher.scale();
             boot.modraise_inplace(cipher); // moai_modraise has its own parity test against the oracle
@@ -324,6 +336,11 @@ int main(int argc, char **argv)
             CHECK(got[b].parms_id() == want.parms_id());
             CHECK(got[b].scale() == want.scale());
             CHECK(got[b].download() == want.download());
+            refgolden::print_golden(name.c_str(), refgolden::digest(context, want));
+#else
+            CHECK(refgolden::matches_recorded(name, context, got[b]));
+            const Ciphertext &want = got[b];
+#endif
             if (b == 0)
             {
                 CHECK(context.first_context_data()->chain_index() - context.get_context_data(want.parms_id())->chain_index() == 14);

@@ -8,7 +8,8 @@
 //   part 2  N = 2^16, MOAI's exact parameters (36-prime chain, logn = 15): `--full`
 // Both check: chain index after = total - 14 (boot_level, test_full_scheme.hpp:364), output scale = final_scale,
 // max |decoded - message| below the bound stated next to each assertion; calls gathered from concurrent threads give the
-// bits of single calls.
+// bits of single calls; the first of them equals the reference's own bootstrap_full_3 (directly where the reference's
+// routines are built in, MOAI_REF_SLICES, by a recorded digest elsewhere: tests/cpp/ref_golden.h).
 #include <execinfo.h>
 #include <omp.h>
 #include <signal.h>
@@ -21,7 +22,10 @@
 #include <random>
 
 #include "Bootstrapper.h"
+#ifdef MOAI_REF_SLICES
 #include "ref_bootstrapper.h" // the reference's own bootstrap_full_3 and its transforms, sliced from the checkout at build time
+#endif
+#include "ref_golden.h"
 
 static int g_checks = 0, g_fail = 0;
 #define CHECK(cond)                                                \
@@ -68,6 +72,7 @@ static void run(int logN, int remaining_level, int n_threads, int per_thread, bo
     double scale = pow(2.0, logp);
     SEALContext context(parms, true, sec_level_type::none);
 
+    refgolden::FixedRandomness fixed(logN);
     KeyGenerator keygen(context);
     SecretKey secret_key = keygen.secret_key();
     PublicKey public_key;
@@ -93,6 +98,7 @@ static void run(int logN, int remaining_level, int n_threads, int per_thread, bo
     t0 = now_s();
     keygen.create_galois_keys(gal_steps_vector, gal_keys_boot);
     context.sync();
+    fixed.release();
     double t_keys = now_s() - t0;
     bootstrapper.slot_vec.push_back(logn);
     t0 = now_s();
@@ -188,6 +194,8 @@ static void run(int logN, int remaining_level, int n_threads, int per_thread, bo
         }
         // the reference's own source text for bootstrap_full_3 (its transforms, coefficient-to-slot and slot-to-coefficient
         // steps; tests/cpp/ref_bootstrapper.h), one ciphertext through the shim's evaluator with the same constants: same bits
+        const string golden_name = "real.logN" + to_string(logN) + ".bootstrap_full_3";
+#ifdef MOAI_REF_SLICES
         {
             refslice::Bootstrapper ref(logn, logN - 1, scale, context, encoder, evaluator, gal_keys_boot);
             moai_fused::BootDiagonals3 d;
@@ -206,7 +214,11 @@ static void run(int logN, int remaining_level, int n_threads, int per_thread, bo
             printf("  the reference's call sequence on one ciphertext: %.2f s\n", now_s() - t0);
             CHECK(want.parms_id() == alone[0].parms_id() && want.scale() == alone[0].scale());
             CHECK(want.download() == alone[0].download());
+            refgolden::print_golden(golden_name.c_str(), refgolden::digest(context, want));
         }
+#else
+        CHECK(refgolden::matches_recorded(golden_name, context, alone[0]));
+#endif
         const auto before = bootstrapper.gather_statistics();
         t0 = now_s();
 #pragma omp parallel num_threads(n_threads)

@@ -44,7 +44,8 @@ def test_moai_headers_compile_unchanged_against_shim(tmp_path):
 def test_cpp_test_binaries_are_built():
     # built by __graft_entry__.build() (make -C tests/cpp); they travel to the GPU box with the snapshot
     assert os.path.exists(os.path.join(CPP, "test_seal_shim"))
-    assert os.path.exists(os.path.join(CPP, "test_moai_headers"))
+    if os.path.isdir(REF):  # it includes MOAI's own headers: built only where they are (tests/cpp/Makefile)
+        assert os.path.exists(os.path.join(CPP, "test_moai_headers"))
     assert os.path.exists(os.path.join(CPP, "test_bootstrap_lt"))
     assert os.path.exists(os.path.join(CPP, "test_bootstrap_eval"))
     assert os.path.exists(os.path.join(CPP, "test_bootstrap_setup"))
