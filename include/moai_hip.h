@@ -304,6 +304,27 @@ int moai_ckks_encode(moai_ctx *ctx, const double *values, int is_complex, size_t
 int moai_ckks_encode_masked(moai_ctx *ctx, const double *constants, const int32_t *mask, size_t mask_size,
                             size_t n_batch, uint64_t *dst, size_t L, const uint32_t *prime_index, double scale,
                             double *max_coeff, void *stream);
+/* ---- decrypt and decode (the client's output path) ---------------------------------------------------------------
+ * moai_decrypt: out[b] = sum_{i < size} ct[b][i] * s^i mod q_r in NTT form, one launch for the batch (s^i formed in
+ * registers).  ct: device [n_batch][size][L][N], size >= 2; sk_ntt: device [L][N], the secret key's rows under the same
+ * primes as the ciphertext's rows (prime_index[0..L), NULL = 0..L-1: the first L rows of a full [k][N] key); out: device
+ * [n_batch][L][N], canonical residues.
+ * moai_ckks_decode: for each of n_batch NTT-form plaintexts [L][N] (plain_ntt, device, never modified): inverse NTT of a
+ * scratch copy, exact CRT composition, the reference's word-by-word conversion to double with 1/scales[b] (sign by
+ * upper_half_threshold, no borrow between words, zero words skipped), forward DWT with root_powers_, and the
+ * matrix_reps_index_map_ gather of all N/2 slots -- bit-identical to the reference's x86-64 build.  scales: HOST array
+ * [n_batch], read during the call.  out: device [n_batch][N/2] doubles (is_complex = 0, real parts) or [n_batch][N/2][2]
+ * (re, im).  Large batches are processed in chunks whose scratch fits the stream's arena or MOAI_DEC_TMP_MB (default
+ * 1024 MiB), whichever is larger.  Errors (before anything is enqueued): MOAI_EINVAL "scale out of bounds" when
+ * scale <= 0 or (int)log2(scale) >= total_coeff_modulus_bit_count (ckks.h:672-677; a non-finite scale too).
+ * Neither call synchronises. */
+/* Decryptor::ckks_decrypt, SEAL/decryptor.cpp:154-187 with dot_product_ct_sk_array :299-381 */
+int moai_decrypt(moai_ctx *ctx, const uint64_t *ct, size_t size, const uint64_t *sk_ntt, uint64_t *out,
+                 size_t n_batch, size_t L, const uint32_t *prime_index, void *stream);
+/* CKKSEncoder::decode_internal, SEAL/ckks.h:644-761 (full slots) */
+int moai_ckks_decode(moai_ctx *ctx, const uint64_t *plain_ntt, size_t n_batch, size_t L,
+                     const uint32_t *prime_index, const double *scales /* host, [n_batch] */,
+                     int is_complex, double *out /* device, [n_batch][N/2] or [n_batch][N/2][2] */, void *stream);
 /* ContextData::total_coeff_modulus_bit_count (SEAL/context.cpp:169-173): significant bits of the product of
  * the L primes; 0 on error. */
 int moai_total_coeff_modulus_bit_count(const moai_ctx *ctx, size_t L, const uint32_t *prime_index);

@@ -141,6 +141,10 @@ struct moai_ctx
     std::vector<double> ckks_inv_roots_host;  // inv_root_powers_ [N] (re, im)
     uint32_t *ckks_src_map = nullptr;         // device, inverse of ckks_index_map
     double *ckks_inv_roots = nullptr;         // device copy
+    // CKKSEncoder::decode (decoder.hip): root_powers_ [N] (re, im) on the device, and per set of rows the constants of the
+    // exact CRT composition (built on first use of that set)
+    double *ckks_roots = nullptr;
+    std::map<std::vector<uint32_t>, uint64_t *> dec_tables;
     // Key layouts (moai_key_trim): a key-switch key registered here is [digits][2][rows][N] with the special prime's row last
     // instead of the reference's [k-1][2][k][N]; unregistered pointers have the reference's layout.
     struct KeyLayout

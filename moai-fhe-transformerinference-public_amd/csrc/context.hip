@@ -621,6 +621,11 @@ extern "C" void moai_ctx_destroy(moai_ctx *c)
     }
     (void)hipFree(c->ckks_src_map);
     (void)hipFree(c->ckks_inv_roots);
+    (void)hipFree(c->ckks_roots);
+    for (auto &kv : c->dec_tables)
+    {
+        (void)hipFree(kv.second);
+    }
     delete static_cast<std::mutex *>(c->mutex);
     delete static_cast<std::mutex *>(c->op_mutex);
     delete c;

@@ -518,6 +518,23 @@ static int ensure_tables(moai_ctx *c)
         c->ckks_inv_roots_host[2] = 0;
         c->ckks_inv_roots_host[3] = -1;
     }
+    // root_powers_[i] = complex_roots_->get_root(reverse_bits(i, logn)) (ckks.cpp:58-62): the decoder's forward DWT
+    std::vector<double> fwd(2 * n, 0.0);
+    if (m >= 8)
+    {
+        ComplexRoots cr((size_t)m);
+        for (size_t i = 1; i < n; i++)
+        {
+            std::complex<double> z = cr.get_root((size_t)reverse_bits((uint32_t)i, logn));
+            fwd[2 * i] = z.real();
+            fwd[2 * i + 1] = z.imag();
+        }
+    }
+    else
+    {
+        fwd[2] = 0;
+        fwd[3] = 1;
+    }
     std::vector<uint32_t> src(n);
     for (size_t i = 0; i < n; i++)
     {
@@ -525,11 +542,15 @@ static int ensure_tables(moai_ctx *c)
     }
     uint32_t *d_src = nullptr;
     double *d_roots = nullptr;
+    double *d_fwd = nullptr;
     MOAI_HIP_CHECK(hipMalloc(&d_src, sizeof(uint32_t) * n));
     MOAI_HIP_CHECK(hipMalloc(&d_roots, sizeof(double) * 2 * n));
+    MOAI_HIP_CHECK(hipMalloc(&d_fwd, sizeof(double) * 2 * n));
     MOAI_HIP_CHECK(hipMemcpy(d_src, src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     MOAI_HIP_CHECK(hipMemcpy(d_roots, c->ckks_inv_roots_host.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    MOAI_HIP_CHECK(hipMemcpy(d_fwd, fwd.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
     c->ckks_src_map = d_src;
+    c->ckks_roots = d_fwd;
     c->ckks_inv_roots = d_roots;
     return MOAI_OK;
 }
@@ -564,6 +585,17 @@ static int product_bit_count(const moai_ctx *c, size_t L, const uint32_t *prime_
         bits++;
     }
     return bits;
+}
+
+// shared with decoder.hip (launch.h)
+int ensure_ckks_tables(moai_ctx *c)
+{
+    return ensure_tables(c);
+}
+
+int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index)
+{
+    return product_bit_count(c, L, prime_index);
 }
 
 template <int R>

@@ -29,4 +29,9 @@ int galois_table(moai_ctx *c, uint32_t elt, hipStream_t s, const uint32_t **out)
 // out [batch][L][N] = the Galois permutation of polynomial 0 of every ciphertext of in [batch][2][L][N]
 int galois_permute_c0(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t batch, size_t L, uint32_t galois_elt, hipStream_t s);
 
+// CKKSEncoder's tables (matrix_reps_index_map_, root_powers_, inv_root_powers_) on the device, built on first use (encoder.hip)
+int ensure_ckks_tables(moai_ctx *c);
+// ContextData::total_coeff_modulus_bit_count of the selected primes; 0 when an index is out of range (encoder.hip)
+int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index);
+
 } // namespace moai

@@ -70,6 +70,8 @@ SYMBOLS = {
     "moai_apply_galois_hoisted": (C.c_int, [vp, vp, C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_int), vp]),
     "moai_ckks_encode": (C.c_int, [vp, vp, C.c_int, sz, sz, vp, sz, C.POINTER(C.c_uint32), C.c_double, vp, vp]),
     "moai_ckks_encode_masked": (C.c_int, [vp, vp, vp, sz, sz, vp, sz, C.POINTER(C.c_uint32), C.c_double, vp, vp]),
+    "moai_decrypt": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_ckks_decode": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_int, vp, vp]),
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
@@ -438,6 +440,32 @@ class Context:
         _check(lib().moai_memcpy_d2h(mx.ctypes.data, mx_ptr, n_batch * 8, stream))
         _check(lib().moai_stream_sync(stream))
         return out, mx
+
+    def decrypt(self, ct, size, sk_ntt, L, n_batch=1, prime_index=None, stream=None):
+        """Decryptor::decrypt for a batch: ct [n_batch][size][L][N] and sk_ntt [L][N] (device buffers or pointers).
+        Returns a DeviceBuffer [n_batch][L][N] holding c_0 + c_1 s + ... in NTT form."""
+        out = DeviceBuffer(max(n_batch, 1) * L * self.n)
+        _check(lib().moai_decrypt(self.h, _ptr(ct), size, _ptr(sk_ntt), out.ptr, n_batch, L,
+                                  self._pidx(prime_index), stream))
+        return out
+
+    def ckks_decode(self, plain, L, scales, n_batch=1, prime_index=None, is_complex=False, stream=None):
+        """CKKSEncoder::decode of n_batch NTT-form plaintexts plain [n_batch][L][N] (device buffer or pointer) at
+        scales (one float, or one per plaintext).  Returns numpy [n_batch][N/2], float64 or complex128."""
+        sc = np.broadcast_to(np.asarray(scales, dtype=np.float64), (n_batch,))
+        sc = np.ascontiguousarray(sc)
+        slots = self.n // 2
+        words = max(n_batch, 1) * slots * (2 if is_complex else 1)
+        out = DeviceBuffer(words)
+        _check(lib().moai_ckks_decode(self.h, _ptr(plain), n_batch, L, self._pidx(prime_index),
+                                      sc.ctypes.data_as(C.POINTER(C.c_double)), 1 if is_complex else 0, out.ptr, stream))
+        host = np.empty(words, dtype=np.float64)
+        _check(lib().moai_memcpy_d2h(host.ctypes.data, out.ptr, words * 8, stream))
+        _check(lib().moai_stream_sync(stream))
+        host = host[: n_batch * slots * (2 if is_complex else 1)]
+        if is_complex:
+            return host.view(np.complex128).reshape(n_batch, slots)
+        return host.reshape(n_batch, slots)
 
     def total_coeff_modulus_bit_count(self, L, prime_index=None):
         r = lib().moai_total_coeff_modulus_bit_count(self.h, L, self._pidx(prime_index))

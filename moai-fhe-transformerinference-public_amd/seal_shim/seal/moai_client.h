@@ -241,33 +241,7 @@ namespace seal
     public:
         CKKSEncoder(const SEALContext &context) : context_(context)
         {
-            const std::size_t n = context_.n();
-            logn_ = context_.logn();
-            slots_ = n >> 1;
-            const std::uint64_t m = static_cast<std::uint64_t>(n) << 1;
-            // SEAL/ckks.cpp:36-50 (generator 5 in this fork)
-            index_map_.resize(n);
-            std::uint64_t gen = 5, pos = 1;
-            for (std::size_t i = 0; i < slots_; i++)
-            {
-                std::uint64_t index1 = (pos - 1) >> 1;
-                std::uint64_t index2 = (m - pos - 1) >> 1;
-                index_map_[i] = util::reverse_bits(static_cast<std::uint32_t>(index1), logn_);
-                index_map_[slots_ + i] = util::reverse_bits(static_cast<std::uint32_t>(index2), logn_);
-                pos = (pos * gen) & (m - 1);
-            }
-            // root_powers_[bitrev(i)] = zeta^i with zeta = exp(2 pi i / 2N); inverse = conjugates
-            root_powers_.resize(n);
-            inv_root_powers_.resize(n);
-            const double pi = 3.14159265358979323846264338327950288;
-            for (std::size_t i = 0; i < n; i++)
-            {
-                double ang = 2.0 * pi * static_cast<double>(i) / static_cast<double>(m);
-                std::complex<double> w(std::cos(ang), std::sin(ang));
-                std::uint32_t r = util::reverse_bits(static_cast<std::uint32_t>(i), logn_);
-                root_powers_[r] = w;
-                inv_root_powers_[r] = std::conj(w);
-            }
+            slots_ = context_.n() >> 1;
         }
 
         std::size_t slot_count() const noexcept
@@ -318,99 +292,52 @@ namespace seal
             encode(value, context_.first_parms_id(), destination);
         }
 
-        // ---- decode (SEAL/ckks.h:644-760) -----------------------------------------------------------
+        // ---- decode (SEAL/ckks.h:644-760): moai_ckks_decode, then N/2 values to the host -------------------
         template <typename T>
         void decode(const Plaintext &plain, std::vector<T> &destination, MemoryPoolHandle = MemoryPoolHandle()) const
         {
+            static_assert(std::is_same<T, double>::value || std::is_same<T, std::complex<double>>::value,
+                          "decode to double or std::complex<double>");
             auto cd = context_.get_context_data(plain.parms_id());
             if (!cd || !plain.is_ntt_form())
             {
                 throw std::invalid_argument("plain is not in NTT form");
             }
+            // ckks.h:672-677
+            if (plain.scale() <= 0 ||
+                (static_cast<int>(std::log2(plain.scale())) >= cd->total_coeff_modulus_bit_count()))
+            {
+                throw std::invalid_argument("scale out of bounds");
+            }
             const std::size_t n = context_.n();
-            const auto &cm = cd->parms().coeff_modulus();
-            const std::size_t L = cm.size();
-            std::vector<std::uint64_t> rns(L * n);
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            void *st = context_.stream();
+            util::DeviceArray rows;
+            const std::uint64_t *src = nullptr;
             if (plain.is_scalar())
             {
                 // constant rows are the NTT of a constant polynomial
-                for (std::size_t r = 0; r < L; r++)
-                {
-                    std::fill(rns.begin() + r * n, rns.begin() + (r + 1) * n, 0);
-                    rns[r * n] = plain.scalar_rows()[r];
-                }
+                rows.resize(L * n, st);
+                util::hip_check(moai_memset_zero(rows.get(), L * n * 8, st));
+                util::hip_check(moai_add_scalar_rows(context_.device(), rows.get(), plain.scalar_rows().data(), rows.get(), 1,
+                                                     L, st));
+                src = rows.get();
             }
             else
             {
-                util::DeviceArray tmp(L * n, context_.stream());
-                util::hip_check(moai_memcpy_d2d(tmp.get(), plain.device_data(), L * n * 8, context_.stream()));
-                util::hip_check(moai_ntt_inverse(context_.device(), tmp.get(), 1, L, nullptr, context_.stream()));
-                util::hip_check(moai_memcpy_d2h(rns.data(), tmp.get(), L * n * 8, context_.stream()));
-                context_.sync();
+                src = plain.device_data(); // materialises a masked plaintext
             }
-            std::vector<std::uint64_t> primes;
-            for (auto &m : cm)
-            {
-                primes.push_back(m.value());
-            }
-            std::vector<double> coeffs(n);
-            compose_centered(rns, primes, n, coeffs);
-            std::vector<std::complex<double>> res(n);
-            const double inv_scale = 1.0 / plain.scale();
-            for (std::size_t i = 0; i < n; i++)
-            {
-                res[i] = std::complex<double>(coeffs[i] * inv_scale, 0.0);
-            }
-            fft_to_rev(res);
+            constexpr bool cplx = std::is_same<T, std::complex<double>>::value;
+            util::DeviceArray out(slots_ * (cplx ? 2 : 1), st);
+            const double scale = plain.scale();
+            util::hip_check(moai_ckks_decode(context_.device(), src, 1, L, nullptr, &scale, cplx ? 1 : 0,
+                                             reinterpret_cast<double *>(out.get()), st));
             destination.resize(slots_);
-            for (std::size_t i = 0; i < slots_; i++)
-            {
-                assign(destination[i], res[index_map_[i]]);
-            }
+            util::hip_check(moai_memcpy_d2h(destination.data(), out.get(), slots_ * sizeof(T), st));
+            context_.sync();
         }
 
     private:
-        static void assign(double &d, const std::complex<double> &c)
-        {
-            d = c.real();
-        }
-        static void assign(std::complex<double> &d, const std::complex<double> &c)
-        {
-            d = c;
-        }
-        static std::complex<double> as_complex(double v)
-        {
-            return { v, 0.0 };
-        }
-        static std::complex<double> as_complex(std::complex<double> v)
-        {
-            return v;
-        }
-
-        // forward DWT, natural in -> bit-reversed out (DWTHandler::transform_to_rev with complex roots)
-        void fft_to_rev(std::vector<std::complex<double>> &v) const
-        {
-            const std::size_t n = v.size();
-            std::size_t gap = n >> 1, m = 1, root = 0;
-            for (; m <= (n >> 1); m <<= 1)
-            {
-                std::size_t offset = 0;
-                for (std::size_t i = 0; i < m; i++)
-                {
-                    const std::complex<double> r = root_powers_[++root];
-                    for (std::size_t j = 0; j < gap; j++)
-                    {
-                        std::complex<double> u = v[offset + j];
-                        std::complex<double> t = v[offset + gap + j] * r;
-                        v[offset + j] = u + t;
-                        v[offset + gap + j] = u - t;
-                    }
-                    offset += gap << 1;
-                }
-                gap >>= 1;
-            }
-        }
-
         static const double *as_doubles(const double *v)
         {
             return v;
@@ -678,95 +605,9 @@ namespace seal
             destination.data_.release();
         }
 
-    public:
-        // centred value of each coefficient mod Q = prod primes, as a double.  Mixed-radix (Garner)
-        // digits avoid multi-precision integers: sign from comparing digits with those of floor(Q/2).
-        static void compose_centered(const std::vector<std::uint64_t> &rns, const std::vector<std::uint64_t> &primes,
-                                     std::size_t n, std::vector<double> &out)
-        {
-            const std::size_t L = primes.size();
-            // inv[i][j] = (q_j)^-1 mod q_i for j < i
-            std::vector<std::vector<std::uint64_t>> inv(L);
-            for (std::size_t i = 0; i < L; i++)
-            {
-                inv[i].resize(i);
-                for (std::size_t j = 0; j < i; j++)
-                {
-                    inv[i][j] = util::powmod(primes[j] % primes[i], primes[i] - 2, primes[i]);
-                }
-            }
-            // mixed-radix digits of floor(Q/2): Q/2 = (Q-1)/2 since Q is odd; digits of Q-1 are q_i - 1;
-            // halving a mixed-radix number digit by digit from the top
-            std::vector<std::uint64_t> half(L);
-            {
-                std::uint64_t carry = 0; // carry in units of "one of digit i+1" = q_i of digit i
-                for (std::size_t ii = L; ii-- > 0;)
-                {
-                    util::u128 cur = static_cast<util::u128>(carry) * primes[ii] + (primes[ii] - 1);
-                    half[ii] = static_cast<std::uint64_t>(cur / 2);
-                    carry = static_cast<std::uint64_t>(cur % 2);
-                }
-            }
-            std::vector<long double> weight(L);
-            weight[0] = 1.0L;
-            for (std::size_t i = 1; i < L; i++)
-            {
-                weight[i] = weight[i - 1] * static_cast<long double>(primes[i - 1]);
-            }
-            std::vector<std::uint64_t> d(L);
-            out.resize(n);
-            for (std::size_t c = 0; c < n; c++)
-            {
-                for (std::size_t i = 0; i < L; i++)
-                {
-                    const std::uint64_t q = primes[i];
-                    std::uint64_t v = rns[i * n + c] % q;
-                    for (std::size_t j = 0; j < i; j++)
-                    {
-                        std::uint64_t dj = d[j] % q;
-                        v = v >= dj ? v - dj : v + q - dj;
-                        v = util::mulmod(v, inv[i][j], q);
-                    }
-                    d[i] = v;
-                }
-                // compare with half from the top digit
-                bool neg = false;
-                for (std::size_t ii = L; ii-- > 0;)
-                {
-                    if (d[ii] != half[ii])
-                    {
-                        neg = d[ii] > half[ii];
-                        break;
-                    }
-                }
-                long double val = 0.0L;
-                if (!neg)
-                {
-                    for (std::size_t ii = L; ii-- > 0;)
-                    {
-                        val += static_cast<long double>(d[ii]) * weight[ii];
-                    }
-                }
-                else
-                {
-                    // Q - x in mixed radix: (q_i - 1 - d_i) per digit, plus one
-                    long double acc = 1.0L;
-                    for (std::size_t ii = L; ii-- > 0;)
-                    {
-                        acc += static_cast<long double>(primes[ii] - 1 - d[ii]) * weight[ii];
-                    }
-                    val = -acc;
-                }
-                out[c] = static_cast<double>(val);
-            }
-        }
-
     private:
         SEALContext context_;
-        int logn_ = 0;
         std::size_t slots_ = 0;
-        std::vector<std::uint32_t> index_map_;
-        std::vector<std::complex<double>> root_powers_, inv_root_powers_;
     };
 
     // =================================================================================================
@@ -1077,7 +918,7 @@ namespace seal
     public:
         Decryptor(const SEALContext &context, const SecretKey &secret_key) : context_(context), sk_(secret_key.ntt_)
         {}
-        // c0 + c1 s + c2 s^2 ... (SEAL/decryptor.cpp:131-205)
+        // c0 + c1 s + c2 s^2 ... (SEAL/decryptor.cpp:131-205), one moai_decrypt launch
         void decrypt(const Ciphertext &encrypted, Plaintext &destination)
         {
             auto cd = context_.get_context_data(encrypted.parms_id());
@@ -1101,23 +942,19 @@ namespace seal
             destination.L_ = L;
             destination.stream_ = context_.stream();
             destination.data_.resize(L * n, context_.stream());
-            std::uint64_t *acc = destination.data_.get();
-            const std::uint64_t *ct = encrypted.device_data();
-            util::DeviceArray spow(L * n, context_.stream()), term(L * n, context_.stream());
-            util::hip_check(moai_memcpy_d2d(acc, ct, L * n * 8, context_.stream()));
-            util::hip_check(moai_memcpy_d2d(spow.get(), sk_->get(), L * n * 8, context_.stream()));
-            for (std::size_t p = 1; p < encrypted.size(); p++)
-            {
-                util::hip_check(moai_dyadic_mul(context_.device(), ct + p * L * n, spow.get(), term.get(), 1, 1, L,
-                                                context_.stream()));
-                util::hip_check(moai_add(context_.device(), acc, term.get(), acc, 1, L, context_.stream()));
-                if (p + 1 < encrypted.size())
-                {
-                    util::hip_check(moai_dyadic_mul(context_.device(), spow.get(), sk_->get(), spow.get(), 1, 1, L,
-                                                    context_.stream()));
-                }
-            }
+            util::hip_check(moai_decrypt(context_.device(), encrypted.device_data(), encrypted.size(), sk_->get(),
+                                         destination.data_.get(), 1, L, nullptr, context_.stream()));
             context_.sync();
+        }
+
+        // the secret key in NTT form over all primes, [k][N] on the device (moai_fused::decrypt_decode)
+        const std::uint64_t *secret_key_device() const
+        {
+            return sk_->get();
+        }
+        const SEALContext &context() const
+        {
+            return context_;
         }
 
     private:

@@ -9,6 +9,9 @@
 // (Q K^T): out[i] = rescale(relinearize( sum_j multiply(X[j], rotate(W[j], i * num_batch)) )).
 #pragma once
 #include <algorithm>
+#include <cmath>
+#include <complex>
+#include <cstring>
 #include <cstdlib>
 #include <functional>
 #include <iostream>
@@ -66,6 +69,100 @@ namespace moai_fused
             util::hip_check(moai_memcpy_d2d(out[b].device_data(), packed.device_data() + b * words, words * 8, context.stream()));
         }
         cts = std::move(out);
+    }
+
+    // ---- client output path -----------------------------------------------------------------------------------
+    // decrypt_decode(): Decryptor::decrypt then CKKSEncoder::decode of every ciphertext, with the same values bit for
+    // bit, for callers that own many ciphertexts (MOAI decrypts all 768 outputs of a layer, test_full_scheme.hpp:1047-1065).
+    // Packed ciphertexts (pack() above) are accepted and contribute batch() entries to `out`, in order.  Ciphertexts are
+    // grouped by level; per group, the members are decrypted (one moai_decrypt per ciphertext, per packed ciphertext
+    // one for all of its members) into one plaintext buffer and decoded by one moai_ckks_decode, then one copy to the
+    // host.  A group's plaintext buffer is bounded (1 GiB): larger groups go in chunks.  Synchronises once per chunk.
+    template <typename T>
+    inline void decrypt_decode(const std::vector<seal::Ciphertext> &cts, const seal::Decryptor &decryptor,
+                               const seal::CKKSEncoder &encoder, std::vector<std::vector<T>> &out)
+    {
+        using namespace seal;
+        static_assert(std::is_same<T, double>::value || std::is_same<T, std::complex<double>>::value,
+                      "decode to double or std::complex<double>");
+        constexpr bool cplx = std::is_same<T, std::complex<double>>::value;
+        const SEALContext &context = decryptor.context();
+        const std::size_t n = context.n(), slots = encoder.slot_count();
+        void *st = context.stream();
+        struct Member
+        {
+            const std::uint64_t *ct;
+            std::size_t size, L, out;
+            double scale;
+        };
+        std::map<std::size_t, std::vector<Member>> groups; // by level
+        std::size_t total = 0;
+        for (const Ciphertext &c : cts)
+        {
+            auto cd = context.get_context_data(c.parms_id());
+            if (!cd || c.size() < 2)
+            {
+                throw std::invalid_argument("encrypted is not valid for encryption parameters");
+            }
+            if (!c.is_ntt_form())
+            {
+                throw std::invalid_argument("encrypted must be in NTT form");
+            }
+            if (c.scale() <= 0 || (static_cast<int>(std::log2(c.scale())) >= cd->total_coeff_modulus_bit_count()))
+            {
+                throw std::invalid_argument("scale out of bounds");
+            }
+            const std::size_t L = c.coeff_modulus_size(), words = c.size() * L * n;
+            const std::uint64_t *base = c.device_data();
+            for (std::size_t b = 0; b < c.batch(); b++)
+            {
+                groups[L].push_back({ base + b * words, c.size(), L, total++, c.scale() });
+            }
+        }
+        out.assign(total, std::vector<T>());
+        const std::size_t per_value = cplx ? 2 : 1;
+        std::vector<double> host;
+        for (auto &kv : groups)
+        {
+            const std::size_t L = kv.first;
+            const std::vector<Member> &m = kv.second;
+            std::size_t chunk = (std::size_t(1) << 30) / (L * n * 8);
+            chunk = chunk < 1 ? 1 : chunk;
+            for (std::size_t m0 = 0; m0 < m.size(); m0 += chunk)
+            {
+                const std::size_t nb = std::min(chunk, m.size() - m0);
+                util::DeviceArray plain(nb * L * n, st), dout(nb * slots * per_value, st);
+                std::vector<double> scales(nb);
+                // runs of consecutive members of one packed ciphertext share a launch
+                for (std::size_t i = 0; i < nb;)
+                {
+                    std::size_t j = i + 1;
+                    while (j < nb && m[m0 + j].size == m[m0 + i].size &&
+                           m[m0 + j].ct == m[m0 + j - 1].ct + m[m0 + i].size * L * n)
+                    {
+                        j++;
+                    }
+                    util::hip_check(moai_decrypt(context.device(), m[m0 + i].ct, m[m0 + i].size, decryptor.secret_key_device(),
+                                                 plain.get() + i * L * n, j - i, L, nullptr, st));
+                    i = j;
+                }
+                for (std::size_t i = 0; i < nb; i++)
+                {
+                    scales[i] = m[m0 + i].scale;
+                }
+                util::hip_check(moai_ckks_decode(context.device(), plain.get(), nb, L, nullptr, scales.data(), cplx ? 1 : 0,
+                                                 reinterpret_cast<double *>(dout.get()), st));
+                host.resize(nb * slots * per_value);
+                util::hip_check(moai_memcpy_d2h(host.data(), dout.get(), host.size() * 8, st));
+                context.sync();
+                for (std::size_t i = 0; i < nb; i++)
+                {
+                    std::vector<T> &o = out[m[m0 + i].out];
+                    o.resize(slots);
+                    std::memcpy(static_cast<void *>(o.data()), host.data() + i * slots * per_value, slots * sizeof(T));
+                }
+            }
+        }
     }
 
     inline std::vector<seal::Ciphertext> ct_pt_matrix_mul_wo_pre(const std::vector<seal::Ciphertext> &enc_X,
