@@ -332,6 +332,67 @@ int moai_total_coeff_modulus_bit_count(const moai_ctx *ctx, size_t L, const uint
  * inv_root_powers_ (host copy, N (re, im) pairs; ckks.cpp:54-71 via util/croots.cpp). */
 int moai_ckks_tables(moai_ctx *ctx, uint32_t *index_map, double *inv_root_powers);
 
+/* ---- client randomness and encryption (the client's input path) --------------------------------------------------
+ * Stream contract.  Generator: ChaCha20, the RFC 8439 block function (20 rounds), state words 0-3 "expand 32-byte k", 4-11
+ * the 32-byte key (little-endian words), 12-13 a 64-bit block counter (low word first), 14-15 a 64-bit nonce (low word first)
+ * -- the layout of the host seal::util::ChaCha20Rng(seed) with seed = key || nonce (8 bytes, little endian).  The stream of
+ * (key, nonce) is the sequence of 64-bit words  W[w] = o[2j] | o[2j+1] << 32  where o[16] is the output of block c = w / 8
+ * (counter c) and j = w % 8.  A sample depends on (key, nonce, coefficient index) only, never on launch geometry.
+ *   uniform mod q_r   row r, coefficient i of an [L][N] draw: (W[2(rN+i)+1] * 2^64 + W[2(rN+i)]) mod q_r, exactly (a Barrett
+ *                     reduction of the 128-bit value with Modulus::const_ratio; statistical distance from uniform < 2^-67)
+ *   ternary           coefficient i: ((3 * W[i]) >> 64) - 1 in {-1, 0, 1}                     (sample_poly_ternary)
+ *   CBD noise         coefficient i: bytes x[0..5] of W[i] (x[0] least significant), x[2] and x[5] masked to 5 bits,
+ *                     popcount(x0) + popcount(x1) + popcount(x2) - popcount(x3) - popcount(x4) - popcount(x5), i.e.
+ *                     popcount(W & 0x1fffff) - popcount((W >> 24) & 0x1fffff): Binomial(42, 1/2) - 21, sigma = 3.24,
+ *                     |e| <= 21  (sample_poly_cbd, SEAL/util/rlwe.cpp:99-135, SEAL 4.1's default noise sampler)
+ *   RNS               a small signed sample v is ONE integer per coefficient, written in every requested row r as
+ *                     v + (v < 0 ? q_r : 0)  (the reference's flag & q)
+ * Samplers: polynomial p of a call uses nonce + p (the range [nonce, nonce + n_poly) must not wrap), out [n_poly][L][N] with
+ * rows under prime_index (NULL = 0..L-1).  Splitting a draw into several calls with the matching nonces gives the same words.
+ *
+ * Compositions use 64-bit nonces  purpose << 56 | sequence  with sequence < 2^56 and the purposes
+ *   1 uniform a (c1 of a symmetric encryption or key digit)   2 ternary u   3 noise e / e0   4 noise e1
+ * Ciphertext (or key digit) b of a call with sequence base `seq` uses sequence seq + b; a call therefore occupies the
+ * sequence range [seq, seq + n_batch) (key generation: [seq, seq + k - 1)), which must lie below 2^56.  Callers hand out
+ * disjoint ranges per key (the seal:: shim's util::DeviceRng).  The key is read from HOST memory during the call.
+ *
+ * moai_encrypt_symmetric: per ciphertext, e = CBD(purpose 3) over the L rows, forward NTT, then one kernel that draws
+ * c1 = a = uniform(purpose 1) over the same rows directly in NTT form and writes c0 = e - a * s (+ plain), c1 = a
+ * (encrypt_zero_symmetric SEAL/util/rlwe.cpp:311-383 with is_ntt_form, then Encryptor::encrypt_symmetric's add_plain).
+ * sk_ntt: [L][N] rows under the same primes as the output (NULL prime_index: the first L rows of a full [k][N] key).
+ * plain: NULL or device [n_batch][L][N] NTT form.  out: device [n_batch][2][L][N].
+ * moai_encrypt_asymmetric: public-key encryption at the data level of L primes (prefix 0..L-1), SEAL/encryptor.cpp:88-173:
+ * with M = L + 1 primes (the previous level; M = L = k at the key level itself) u = ternary(purpose 2), e0 = CBD(3),
+ * e1 = CBD(4) over M rows, forward NTT, c_i = pk_i * u + e_i over pk rows [0, M) (encrypt_zero_asymmetric,
+ * SEAL/util/rlwe.cpp:224-310); below the key level the dropped prime is divided out exactly as moai_rescale does
+ * (divide_and_round_q_last_ntt_inplace); then plain (NULL or [n_batch][L][N]) is added to c0.  pk: device [2][k][N] (the
+ * key-level public key).  out: device [n_batch][2][L][N].
+ * moai_kswitch_keygen: the k-1 digits of a switching key for new_key_ntt [k][N] under sk_ntt [k][N] at the key level: digit J
+ * is the symmetric encryption of zero with sequence seq + J plus (q_{k-1} mod q_J) * new_key[J] in row J of c0
+ * (KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336).  out: device [k-1][2][k][N], the layout every
+ * key-switch entry point above takes.
+ * Large batches are processed in chunks whose scratch fits the stream's arena or 1 GiB, whichever is larger.  Arguments are
+ * validated before anything is enqueued (MOAI_EINVAL with a message: null context / key / argument, "invalid level", a
+ * sequence range beyond 2^56, more than 65535 ciphertexts; MOAI_ELOGIC for k < 2 in key generation).  No call synchronises. */
+/* sample_poly_uniform SEAL/util/rlwe.cpp:137-183 (the stream above instead of rejection sampling) */
+int moai_sample_uniform(moai_ctx *ctx, const uint8_t *key /* host, 32 bytes */, uint64_t nonce, uint64_t *out, size_t n_poly,
+                        size_t L, const uint32_t *prime_index, void *stream);
+/* sample_poly_ternary SEAL/util/rlwe.cpp:14-38 */
+int moai_sample_ternary(moai_ctx *ctx, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                        const uint32_t *prime_index, void *stream);
+/* sample_poly_cbd SEAL/util/rlwe.cpp:99-135 */
+int moai_sample_cbd(moai_ctx *ctx, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                    const uint32_t *prime_index, void *stream);
+/* Encryptor::encrypt_symmetric / encrypt_zero_symmetric, SEAL/encryptor.cpp:88-120 over SEAL/util/rlwe.cpp:311-383 */
+int moai_encrypt_symmetric(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
+                           uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index, void *stream);
+/* Encryptor::encrypt / encrypt_zero with a public key, SEAL/encryptor.cpp:88-173 over SEAL/util/rlwe.cpp:224-310 */
+int moai_encrypt_asymmetric(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const uint64_t *pk, const uint64_t *plain,
+                            uint64_t *out, size_t n_batch, size_t L, void *stream);
+/* KeyGenerator::generate_kswitch_keys for one new key, SEAL/keygenerator.cpp:303-336 */
+int moai_kswitch_keygen(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
+                        uint64_t *out, void *stream);
+
 /* ---- tuning -------------------------------------------------------------------------------------------------------
  * Overrides a performance knob for the whole process (same names as the environment variables read by the
  * library, which it takes precedence over).  Results never depend on these.  Currently:

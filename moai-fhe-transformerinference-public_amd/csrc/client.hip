@@ -1,0 +1,740 @@
+// client.hip -- the client's input path on the device: a counter-based ChaCha20 generator, the samplers built on it
+// (SEAL/util/rlwe.cpp:99-135 sample_poly_cbd, :137-183 sample_poly_uniform, :14-38 sample_poly_ternary), symmetric and
+// public-key encryption (SEAL/util/rlwe.cpp:224-383, SEAL/encryptor.cpp:88-173) and switching-key generation
+// (SEAL/keygenerator.cpp:303-336).  The stream contract (which words of which block feed which coefficient) is specified in
+// include/moai_hip.h, section "client randomness and encryption"; tests/client_sampling.py restates it.
+//
+// Every sample is a function of (key, nonce, coefficient index) only: a thread computes the one ChaCha20 block its
+// coefficients take and nothing depends on the launch geometry.
+//
+//   cl_uniform      : 4 coefficients (one block of 8 words) per thread, (hi * 2^64 + lo) mod q exactly (mod128)
+//   cl_small        : 8 coefficients (one block) per thread, ternary or CBD, written as residues in every requested row
+//   cl_sym_finish   : c1 = uniform a generated in place (NTT form, as SEAL samples it), c0 = e - a s (+ m) (+ (p mod q_J) s' in
+//                     row J of a key digit); c1 is never stored before this kernel
+//   cl_pk_finish    : c_i = pk_i u + e_i over the rows of the previous level, u read once; then the existing rescale divides by
+//                     the dropped prime (divide_and_round_q_last_ntt_inplace) and cl_add_c0 adds the plaintext to c0
+#include <mutex>
+
+#include "launch.h"
+#include "modarith.hip.h"
+
+namespace moai {
+
+struct ChaKey
+{
+    uint32_t w[8];
+};
+
+// purposes of the nonce (nonce = purpose << 56 | sequence), include/moai_hip.h
+constexpr uint64_t CL_UNIFORM = 1, CL_TERNARY = 2, CL_NOISE0 = 3, CL_NOISE1 = 4;
+constexpr uint64_t CL_SEQ_LIMIT = 1ull << 56;
+
+__device__ __forceinline__ uint32_t rotl32(uint32_t v, int c)
+{
+    return (v << c) | (v >> (32 - c)); // one v_alignbit_b32
+}
+
+#define CL_QR(a, b, c, d)                 \
+    x[a] += x[b];                         \
+    x[d] = rotl32(x[d] ^ x[a], 16);       \
+    x[c] += x[d];                         \
+    x[b] = rotl32(x[b] ^ x[c], 12);       \
+    x[a] += x[b];                         \
+    x[d] = rotl32(x[d] ^ x[a], 8);        \
+    x[c] += x[d];                         \
+    x[b] = rotl32(x[b] ^ x[c], 7);
+
+// RFC 8439 block function with a 64-bit counter in state words 12-13 and a 64-bit nonce in 14-15 (the layout of the host
+// seal::util::ChaCha20Rng): out[16] = the block's 32-bit words
+__device__ __forceinline__ void chacha_block(const ChaKey &k, uint64_t nonce, uint64_t ctr, uint32_t out[16])
+{
+    uint32_t s[16] = { 0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, k.w[0], k.w[1], k.w[2], k.w[3], k.w[4], k.w[5], k.w[6],
+                       k.w[7], (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)nonce, (uint32_t)(nonce >> 32) };
+    uint32_t x[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+    {
+        x[i] = s[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++)
+    {
+        CL_QR(0, 4, 8, 12)
+        CL_QR(1, 5, 9, 13)
+        CL_QR(2, 6, 10, 14)
+        CL_QR(3, 7, 11, 15)
+        CL_QR(0, 5, 10, 15)
+        CL_QR(1, 6, 11, 12)
+        CL_QR(2, 7, 8, 13)
+        CL_QR(3, 4, 9, 14)
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+    {
+        out[i] = x[i] + s[i];
+    }
+}
+#undef CL_QR
+
+// (hi * 2^64 + lo) mod q exactly, for ANY 128-bit value.  barrett128's truncated quotient (the low word of lo * cr0 is dropped)
+// is below the true one by less than 3 for inputs up to 2^128: the remainder before its subtraction is below 3q, so a second
+// conditional subtraction makes the result canonical always, not only for the products below q^2 the shared routine serves
+__device__ __forceinline__ uint64_t mod128(uint64_t lo, uint64_t hi, const PrimeConst &pc)
+{
+    return csub(barrett128(lo, hi, pc.q, pc.cr0, pc.cr1), pc.q);
+}
+
+__device__ __forceinline__ uint64_t word64(const uint32_t b[16], int w)
+{
+    return (uint64_t)b[2 * w] | ((uint64_t)b[2 * w + 1] << 32);
+}
+
+// ((3 w) >> 64) - 1 in {-1, 0, 1}
+__device__ __forceinline__ int ternary_of(uint64_t w)
+{
+    return (int)__umul64hi(w, 3ull) - 1;
+}
+
+// SEAL's cbd(): bytes x[0..5] of the word, x[2] and x[5] masked to 5 bits (rlwe.cpp:105-113)
+__device__ __forceinline__ int cbd_of(uint64_t w)
+{
+    const uint32_t lo = (uint32_t)w & 0x1fffffu;
+    const uint32_t hi = (uint32_t)(w >> 24) & 0x1fffffu;
+    return __popc(lo) - __popc(hi);
+}
+
+// ---- raw samplers -----------------------------------------------------------------------------------------------------
+struct UniformArgs
+{
+    ChaKey key;
+    uint64_t nonce;  // polynomial p uses nonce + p
+    uint64_t *out;   // polynomial p at out + p * stride
+    size_t stride;   // words
+    const PrimeConst *pc;
+    RowMap rows;
+    uint32_t L;
+    uint32_t logn;
+};
+
+__global__ __launch_bounds__(256) void cl_uniform(UniformArgs g)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // block index of the stream = (r N + i) / 4
+    if (t >= (g.L << g.logn) >> 2)
+    {
+        return;
+    }
+    const uint32_t p = blockIdx.y;
+    const uint32_t f = t << 2;
+    const uint32_t r = f >> g.logn;
+    const PrimeConst &pc = g.pc[g.rows.idx[r]];
+    uint32_t b[16];
+    chacha_block(g.key, g.nonce + p, t, b);
+    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(g.out + (size_t)p * g.stride + f);
+    ulonglong2 v0, v1;
+    v0.x = mod128(word64(b, 0), word64(b, 1), pc);
+    v0.y = mod128(word64(b, 2), word64(b, 3), pc);
+    v1.x = mod128(word64(b, 4), word64(b, 5), pc);
+    v1.y = mod128(word64(b, 6), word64(b, 7), pc);
+    dst[0] = v0;
+    dst[1] = v1;
+}
+
+struct SmallArgs
+{
+    ChaKey key;
+    uint64_t nonce; // polynomial p uses nonce + p
+    uint64_t *out;  // polynomial p at out + p * stride, rows [L][N]
+    size_t stride;
+    const PrimeConst *pc;
+    RowMap rows;
+    uint32_t L;
+    uint32_t logn;
+};
+
+template <bool CBD>
+__global__ __launch_bounds__(256) void cl_small(SmallArgs g)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // coefficients 8t .. 8t+7
+    if (t >= (1u << g.logn) >> 3)
+    {
+        return;
+    }
+    const uint32_t p = blockIdx.y;
+    uint32_t b[16];
+    chacha_block(g.key, g.nonce + p, t, b);
+    int v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+    {
+        v[j] = CBD ? cbd_of(word64(b, j)) : ternary_of(word64(b, j));
+    }
+    uint64_t *base = g.out + (size_t)p * g.stride + ((size_t)t << 3);
+    for (uint32_t r = 0; r < g.L; r++)
+    {
+        const uint64_t q = g.pc[g.rows.idx[r]].q;
+        ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(base + ((size_t)r << g.logn));
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            ulonglong2 w;
+            // the residue of a small signed integer: v + (v < 0 ? q : 0)  (SEAL's flag & q)
+            w.x = (uint64_t)(int64_t)v[2 * j] + (v[2 * j] < 0 ? q : 0);
+            w.y = (uint64_t)(int64_t)v[2 * j + 1] + (v[2 * j + 1] < 0 ? q : 0);
+            dst[j] = w;
+        }
+    }
+}
+
+// ---- symmetric encryption / key digits --------------------------------------------------------------------------------
+struct SymArgs
+{
+    ChaKey key;
+    uint64_t nonce_a;       // ciphertext b (of this launch) draws a with nonce_a + b
+    const uint64_t *e;      // [nb][L][N] NTT form
+    const uint64_t *sk;     // [L][N]
+    const uint64_t *plain;  // [nb][L][N] or null
+    const uint64_t *newkey; // [L][N] or null: key digit b adds fac[b] * newkey[b] in row b of c0
+    uint64_t *out;          // [nb][2][L][N]
+    uint32_t digit0;        // digit of ciphertext 0 of this launch
+    const PrimeConst *pc;
+    RowMap rows;
+    uint64_t fac[MOAI_MAX_RNS];
+    uint32_t L;
+    uint32_t logn;
+};
+
+__global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= (g.L << g.logn) >> 2)
+    {
+        return;
+    }
+    const uint32_t b = blockIdx.y;
+    const uint32_t f = t << 2;
+    const uint32_t r = f >> g.logn;
+    const size_t LN = (size_t)g.L << g.logn;
+    const PrimeConst &pc = g.pc[g.rows.idx[r]];
+    const uint64_t q = pc.q;
+    uint32_t blk[16];
+    chacha_block(g.key, g.nonce_a + b, t, blk);
+    uint64_t a[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+    {
+        a[j] = mod128(word64(blk, 2 * j), word64(blk, 2 * j + 1), pc);
+    }
+    const ulonglong2 *e2 = reinterpret_cast<const ulonglong2 *>(g.e + b * LN + f);
+    const ulonglong2 *s2 = reinterpret_cast<const ulonglong2 *>(g.sk + f);
+    uint64_t c0[4];
+    {
+        ulonglong2 e01 = e2[0], e23 = e2[1], s01 = s2[0], s23 = s2[1];
+        const uint64_t ev[4] = { e01.x, e01.y, e23.x, e23.y };
+        const uint64_t sv[4] = { s01.x, s01.y, s23.x, s23.y };
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            const uint64_t as = mulmod_barrett(a[j], sv[j], q, pc.cr0, pc.cr1);
+            c0[j] = ev[j] >= as ? ev[j] - as : ev[j] + q - as;
+        }
+    }
+    if (g.plain)
+    {
+        const ulonglong2 *p2 = reinterpret_cast<const ulonglong2 *>(g.plain + b * LN + f);
+        ulonglong2 p01 = p2[0], p23 = p2[1];
+        const uint64_t pv[4] = { p01.x, p01.y, p23.x, p23.y };
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            c0[j] = csub(c0[j] + pv[j], q);
+        }
+    }
+    if (g.newkey && r == g.digit0 + b)
+    {
+        const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(g.newkey + f);
+        ulonglong2 k01 = k2[0], k23 = k2[1];
+        const uint64_t kv[4] = { k01.x, k01.y, k23.x, k23.y };
+        const uint64_t fac = g.fac[r];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            c0[j] = csub(c0[j] + mulmod_barrett(kv[j], fac, q, pc.cr0, pc.cr1), q);
+        }
+    }
+    ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(g.out + 2 * b * LN + f);
+    ulonglong2 *o1 = reinterpret_cast<ulonglong2 *>(g.out + (2 * b + 1) * LN + f);
+    o0[0] = make_ulonglong2(c0[0], c0[1]);
+    o0[1] = make_ulonglong2(c0[2], c0[3]);
+    o1[0] = make_ulonglong2(a[0], a[1]);
+    o1[1] = make_ulonglong2(a[2], a[3]);
+}
+
+// ---- public-key encryption --------------------------------------------------------------------------------------------
+struct PkArgs
+{
+    const uint64_t *u;     // [nb][M][N] NTT form
+    const uint64_t *e;     // [nb][2][M][N] NTT form
+    const uint64_t *pk;    // [2][k][N]: rows [0, M) of each polynomial are read
+    const uint64_t *plain; // [nb][M][N] or null (key level only)
+    uint64_t *out;         // [nb][2][M][N] (may be e)
+    const PrimeConst *pc;
+    size_t pk_poly;        // k N
+    uint32_t M;
+    uint32_t logn;
+};
+
+__global__ __launch_bounds__(256) void cl_pk_finish(PkArgs g)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // coefficient pair 2t, 2t+1 of the rows
+    if (t >= (g.M << g.logn) >> 1)
+    {
+        return;
+    }
+    const uint32_t b = blockIdx.y;
+    const uint32_t f = t << 1;
+    const uint32_t r = f >> g.logn;
+    const size_t MN = (size_t)g.M << g.logn;
+    const PrimeConst &pc = g.pc[r];
+    const uint64_t q = pc.q;
+    const ulonglong2 u = *reinterpret_cast<const ulonglong2 *>(g.u + b * MN + f);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+    {
+        const ulonglong2 pk = *reinterpret_cast<const ulonglong2 *>(g.pk + i * g.pk_poly + f);
+        const ulonglong2 e = *reinterpret_cast<const ulonglong2 *>(g.e + (2 * b + i) * MN + f);
+        ulonglong2 c;
+        c.x = csub(mulmod_barrett(pk.x, u.x, q, pc.cr0, pc.cr1) + e.x, q);
+        c.y = csub(mulmod_barrett(pk.y, u.y, q, pc.cr0, pc.cr1) + e.y, q);
+        if (i == 0 && g.plain)
+        {
+            const ulonglong2 m = *reinterpret_cast<const ulonglong2 *>(g.plain + b * MN + f);
+            c.x = csub(c.x + m.x, q);
+            c.y = csub(c.y + m.y, q);
+        }
+        *reinterpret_cast<ulonglong2 *>(g.out + (2 * b + i) * MN + f) = c;
+    }
+}
+
+// ct[b][0] += plain[b] over L rows (primes 0..L-1)
+__global__ __launch_bounds__(256) void cl_add_c0(uint64_t *ct, const uint64_t *plain, const PrimeConst *pc, uint32_t L, uint32_t logn)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= (L << logn) >> 1)
+    {
+        return;
+    }
+    const uint32_t b = blockIdx.y;
+    const uint32_t f = t << 1;
+    const uint64_t q = pc[f >> logn].q;
+    const size_t LN = (size_t)L << logn;
+    ulonglong2 *c = reinterpret_cast<ulonglong2 *>(ct + 2 * b * LN + f);
+    const ulonglong2 m = *reinterpret_cast<const ulonglong2 *>(plain + b * LN + f);
+    ulonglong2 v = *c;
+    v.x = csub(v.x + m.x, q);
+    v.y = csub(v.y + m.y, q);
+    *c = v;
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+static ChaKey load_key(const uint8_t *key)
+{
+    ChaKey k;
+    for (int i = 0; i < 8; i++)
+    {
+        k.w[i] = (uint32_t)key[4 * i] | ((uint32_t)key[4 * i + 1] << 8) | ((uint32_t)key[4 * i + 2] << 16) |
+                 ((uint32_t)key[4 * i + 3] << 24);
+    }
+    return k;
+}
+
+static dim3 grid_of(size_t threads, size_t y)
+{
+    return dim3((uint32_t)((threads + 255) / 256), (uint32_t)y);
+}
+
+static int launch_small(moai_ctx *c, bool cbd, const ChaKey &key, uint64_t nonce, uint64_t *out, size_t stride, size_t n_poly,
+                        size_t L, const RowMap &rows, hipStream_t s)
+{
+    SmallArgs a;
+    a.key = key;
+    a.nonce = nonce;
+    a.out = out;
+    a.stride = stride;
+    a.pc = c->pc;
+    a.rows = rows;
+    a.L = (uint32_t)L;
+    a.logn = (uint32_t)c->logn;
+    if (cbd)
+    {
+        hipLaunchKernelGGL(cl_small<true>, grid_of(c->n / 8, n_poly), dim3(256), 0, s, a);
+    }
+    else
+    {
+        hipLaunchKernelGGL(cl_small<false>, grid_of(c->n / 8, n_poly), dim3(256), 0, s, a);
+    }
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+// items per chunk: per-item scratch `per` bytes within the stream's arena or 1 GiB, whichever is larger
+static size_t cl_chunk(moai_ctx *c, hipStream_t s, size_t per, size_t n, size_t cap)
+{
+    size_t budget = (size_t)1 << 30;
+    {
+        std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
+        auto it = c->ws.find((void *)s);
+        if (it != c->ws.end() && it->second.bytes > budget)
+        {
+            budget = it->second.bytes;
+        }
+    }
+    size_t cb = budget / per;
+    cb = cb < 1 ? 1 : cb;
+    cb = cb > cap ? cap : cb;
+    return cb < n ? cb : n;
+}
+
+static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, size_t count)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (!key)
+    {
+        return set_error(MOAI_EINVAL, "null key");
+    }
+    if (c->logn < 3)
+    {
+        return set_error(MOAI_ELOGIC, "client sampling needs N >= 8");
+    }
+    if (seq >= CL_SEQ_LIMIT || count > CL_SEQ_LIMIT - seq)
+    {
+        return set_error(MOAI_EINVAL, "nonce range [%llu, +%zu) exceeds 2^56", (unsigned long long)seq, count);
+    }
+    if (count > 65535)
+    {
+        return set_error(MOAI_EINVAL, "at most 65535 ciphertexts per call");
+    }
+    return MOAI_OK;
+}
+
+// symmetric encryptions (newkey == null) or the digits of a switching key: ciphertext b uses sequence seq + b
+static int sym_impl(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk, const uint64_t *plain, const uint64_t *newkey,
+                    uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, hipStream_t s)
+{
+    int rc = enter_device(c);
+    if (rc)
+    {
+        return rc;
+    }
+    const ChaKey k = load_key(key);
+    const size_t n = c->n, LN = L * n;
+    SymArgs a;
+    a.key = k;
+    a.sk = sk;
+    a.newkey = newkey;
+    a.pc = c->pc;
+    a.rows = rows;
+    a.L = (uint32_t)L;
+    a.logn = (uint32_t)c->logn;
+    for (size_t r = 0; r < MOAI_MAX_RNS; r++)
+    {
+        // SEAL/keygenerator.cpp:315-319: the special prime modulo q_J
+        a.fac[r] = r < L ? c->primes[c->k - 1] % c->primes[rows.idx[r]] : 0;
+    }
+    std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
+    const size_t cb = cl_chunk(c, s, LN * sizeof(uint64_t), n_batch, 65535);
+    void *scratch = nullptr;
+    rc = workspace(c, cb * LN * sizeof(uint64_t), s, &scratch);
+    if (rc)
+    {
+        return rc;
+    }
+    uint64_t *e = static_cast<uint64_t *>(scratch);
+    for (size_t b0 = 0; b0 < n_batch; b0 += cb)
+    {
+        const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
+        rc = launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, LN, nb, L, rows, s);
+        if (!rc)
+        {
+            rc = ntt_launch(c, e, nb, L, rows, false, s);
+        }
+        if (rc)
+        {
+            return rc;
+        }
+        a.nonce_a = (CL_UNIFORM << 56) | (seq + b0);
+        a.e = e;
+        a.plain = plain ? plain + b0 * LN : nullptr;
+        a.out = out + b0 * 2 * LN;
+        a.digit0 = (uint32_t)b0;
+        hipLaunchKernelGGL(cl_sym_finish, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+        MOAI_LAUNCH_CHECK();
+    }
+    return MOAI_OK;
+}
+
+} // namespace moai
+
+using namespace moai;
+
+static int sampler_entry(moai_ctx *c, int kind, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                         const uint32_t *prime_index, void *stream)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (!key)
+    {
+        return set_error(MOAI_EINVAL, "null key");
+    }
+    if (c->logn < 3)
+    {
+        return set_error(MOAI_ELOGIC, "client sampling needs N >= 8");
+    }
+    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
+    {
+        return set_error(MOAI_EINVAL, "invalid level");
+    }
+    RowMap rows;
+    int rc = make_rowmap(c, L, prime_index, &rows);
+    if (rc)
+    {
+        return rc;
+    }
+    if (n_poly == 0)
+    {
+        return MOAI_OK;
+    }
+    if (n_poly > 65535)
+    {
+        return set_error(MOAI_EINVAL, "at most 65535 polynomials per call");
+    }
+    if (nonce + (n_poly - 1) < nonce)
+    {
+        return set_error(MOAI_EINVAL, "nonce range wraps around 2^64");
+    }
+    if (!out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    rc = enter_device(c);
+    if (rc)
+    {
+        return rc;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const ChaKey k = load_key(key);
+    const size_t LN = L * c->n;
+    if (kind == 0)
+    {
+        UniformArgs a;
+        a.key = k;
+        a.nonce = nonce;
+        a.out = out;
+        a.stride = LN;
+        a.pc = c->pc;
+        a.rows = rows;
+        a.L = (uint32_t)L;
+        a.logn = (uint32_t)c->logn;
+        hipLaunchKernelGGL(cl_uniform, grid_of(LN / 4, n_poly), dim3(256), 0, s, a);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    }
+    return launch_small(c, kind == 2, k, nonce, out, LN, n_poly, L, rows, s);
+}
+
+extern "C" int moai_sample_uniform(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                                   const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, out);
+    trace_op("sample_uniform", L, n_poly);
+    return sampler_entry(c, 0, key, nonce, out, n_poly, L, prime_index, stream);
+}
+
+extern "C" int moai_sample_ternary(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                                   const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, out);
+    trace_op("sample_ternary", L, n_poly);
+    return sampler_entry(c, 1, key, nonce, out, n_poly, L, prime_index, stream);
+}
+
+extern "C" int moai_sample_cbd(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
+                               const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, out);
+    trace_op("sample_cbd", L, n_poly);
+    return sampler_entry(c, 2, key, nonce, out, n_poly, L, prime_index, stream);
+}
+
+extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
+                                      uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, plain, out);
+    trace_op("encrypt_symmetric", L, n_batch);
+    int rc = check_common(c, key, seq, n_batch);
+    if (rc)
+    {
+        return rc;
+    }
+    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
+    {
+        return set_error(MOAI_EINVAL, "invalid level");
+    }
+    RowMap rows;
+    rc = make_rowmap(c, L, prime_index, &rows);
+    if (rc)
+    {
+        return rc;
+    }
+    if (n_batch == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!sk_ntt || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    return sym_impl(c, key, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, (hipStream_t)stream);
+}
+
+extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
+                                   uint64_t *out, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    trace_op("kswitch_keygen", c->k, c->k - 1);
+    if (c->k < 2)
+    {
+        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
+    }
+    const size_t digits = c->k - 1;
+    int rc = check_common(c, key, seq, digits);
+    if (rc)
+    {
+        return rc;
+    }
+    if (!sk_ntt || !new_key_ntt || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    RowMap rows;
+    rc = make_rowmap(c, c->k, nullptr, &rows);
+    if (rc)
+    {
+        return rc;
+    }
+    return sym_impl(c, key, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, (hipStream_t)stream);
+}
+
+extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *pk, const uint64_t *plain,
+                                       uint64_t *out, size_t n_batch, size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, pk, plain, out);
+    trace_op("encrypt_asymmetric", L, n_batch);
+    int rc = check_common(c, key, seq, n_batch);
+    if (rc)
+    {
+        return rc;
+    }
+    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
+    {
+        return set_error(MOAI_EINVAL, "invalid level");
+    }
+    if (n_batch == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!pk || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    rc = enter_device(c);
+    if (rc)
+    {
+        return rc;
+    }
+    // SEAL/encryptor.cpp:122-162: below the key level, encrypt at the previous level (one more prime) and divide by it
+    const bool divide = L < c->k;
+    const size_t M = divide ? L + 1 : L;
+    const size_t n = c->n, MN = M * n, LN = L * n;
+    RowMap rows;
+    rc = make_rowmap(c, M, nullptr, &rows);
+    if (rc)
+    {
+        return rc;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const ChaKey k = load_key(key);
+    std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
+    // scratch per ciphertext: u, e0, e1 [3][M][N], and the rescale's own workspace [2][M][N] at the head of the arena
+    const size_t per = (divide ? 5 : 3) * MN * sizeof(uint64_t);
+    const size_t cb = cl_chunk(c, s, per, n_batch, 32767);
+    const size_t head = divide ? rescale_ws_bytes(c, M, 2 * cb) : 0;
+    void *wsp = nullptr;
+    rc = workspace(c, head + 3 * cb * MN * sizeof(uint64_t), s, &wsp);
+    if (rc)
+    {
+        return rc;
+    }
+    uint64_t *u = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + head);
+    for (size_t b0 = 0; b0 < n_batch; b0 += cb)
+    {
+        const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
+        // u [nb][M][N] directly followed by e [nb][2][M][N]: laid out by THIS chunk's count, so that the 3 nb polynomials the
+        // transform covers are exactly u and e also when the last chunk is short
+        uint64_t *e = u + nb * MN;
+        rc = launch_small(c, false, k, (CL_TERNARY << 56) | (seq + b0), u, MN, nb, M, rows, s);
+        if (!rc)
+        {
+            rc = launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, 2 * MN, nb, M, rows, s);
+        }
+        if (!rc)
+        {
+            rc = launch_small(c, true, k, (CL_NOISE1 << 56) | (seq + b0), e + MN, 2 * MN, nb, M, rows, s);
+        }
+        if (!rc)
+        {
+            // u and e are adjacent: one transform of 3 nb polynomials
+            rc = ntt_launch(c, u, 3 * nb, M, rows, false, s);
+        }
+        if (rc)
+        {
+            return rc;
+        }
+        PkArgs a;
+        a.u = u;
+        a.e = e;
+        a.pk = pk;
+        a.plain = divide || !plain ? nullptr : plain + b0 * LN;
+        a.out = divide ? e : out + b0 * 2 * LN;
+        a.pc = c->pc;
+        a.pk_poly = c->k * n;
+        a.M = (uint32_t)M;
+        a.logn = (uint32_t)c->logn;
+        hipLaunchKernelGGL(cl_pk_finish, grid_of(MN / 2, nb), dim3(256), 0, s, a);
+        MOAI_LAUNCH_CHECK();
+        if (divide)
+        {
+            // divide_and_round_q_last_ntt_inplace (SEAL/util/rns.cpp:830-901), the rescale's kernels
+            rc = rescale_nolock(c, e, out + b0 * 2 * LN, 2, M, nb, s);
+            if (rc)
+            {
+                return rc;
+            }
+            if (plain)
+            {
+                hipLaunchKernelGGL(cl_add_c0, grid_of(LN / 2, nb), dim3(256), 0, s, out + b0 * 2 * LN, plain + b0 * LN, c->pc,
+                                   (uint32_t)L, (uint32_t)c->logn);
+                MOAI_LAUNCH_CHECK();
+            }
+        }
+    }
+    return MOAI_OK;
+}

@@ -825,8 +825,9 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(uint64_t *rows, Tw s, u
 
 // rescale_to_next (scalars == nullptr) or a scalar plaintext product followed by it, plus an optional addend of the output's
 // shape ([batch * size][L - 1][N]; may be `out` itself) that the last kernel adds to the quotient
+// (locked: the caller already holds the context's op_mutex, see rescale_nolock)
 static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scalars, const uint64_t *addend, uint64_t *out, size_t size,
-                          size_t L, size_t batch, void *stream)
+                          size_t L, size_t batch, void *stream, bool locked = false)
 {
     const size_t P = batch * size;
     int rc = check_level(c, L, P);
@@ -880,7 +881,11 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
     }
     const size_t sz_last = align256(P * row_bytes);
     const size_t sz_u = align256(P * (L - 1) * row_bytes);
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    std::unique_lock<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex), std::defer_lock);
+    if (!locked)
+    {
+        op_lock.lock();
+    }
     void *wsp;
     rc = workspace(c, sz_last + sz_u, s, &wsp);
     if (rc)
@@ -902,6 +907,19 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
     return moddown(c, last, in, (uint32_t)L, u, out, P, L - 1, (uint32_t)(L - 1), addend, (uint32_t)(2 * (L - 1)), addend ? 1 : 0, s, 1, 0,
                    scalars ? sc : nullptr);
 }
+
+namespace moai {
+size_t rescale_ws_bytes(const moai_ctx *c, size_t L, size_t polys)
+{
+    const size_t row_bytes = c->n * sizeof(uint64_t);
+    return align256(polys * row_bytes) + align256(polys * (L - 1) * row_bytes);
+}
+
+int rescale_nolock(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t size, size_t L, size_t batch, hipStream_t s)
+{
+    return rescale_common(c, in, nullptr, nullptr, out, size, L, batch, (void *)s, true);
+}
+} // namespace moai
 
 extern "C" int moai_rescale(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t size, size_t L, size_t batch,
                             void *stream)

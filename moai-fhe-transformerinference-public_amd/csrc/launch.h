@@ -34,4 +34,9 @@ int ensure_ckks_tables(moai_ctx *c);
 // ContextData::total_coeff_modulus_bit_count of the selected primes; 0 when an index is out of range (encoder.hip)
 int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index);
 
+// moai_rescale for a caller that already holds the context's op_mutex (client.hip): it uses the first
+// rescale_ws_bytes(c, L, batch * size) bytes of the stream's arena, the caller's own scratch lies behind them
+size_t rescale_ws_bytes(const moai_ctx *c, size_t L, size_t polys);
+int rescale_nolock(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t size, size_t L, size_t batch, hipStream_t s);
+
 } // namespace moai

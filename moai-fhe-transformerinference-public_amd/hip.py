@@ -72,6 +72,12 @@ SYMBOLS = {
     "moai_ckks_encode_masked": (C.c_int, [vp, vp, vp, sz, sz, vp, sz, C.POINTER(C.c_uint32), C.c_double, vp, vp]),
     "moai_decrypt": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_ckks_decode": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_int, vp, vp]),
+    "moai_sample_uniform": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_sample_ternary": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_sample_cbd": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_encrypt_symmetric": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_encrypt_asymmetric": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, vp]),
+    "moai_kswitch_keygen": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, vp]),
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
@@ -466,6 +472,54 @@ class Context:
         if is_complex:
             return host.view(np.complex128).reshape(n_batch, slots)
         return host.reshape(n_batch, slots)
+
+    # --- client randomness and encryption (include/moai_hip.h, "client randomness and encryption") -----------------
+    @staticmethod
+    def _key(key):
+        if key is None:
+            return None
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("a ChaCha20 key has 32 bytes")
+        return key
+
+    def _sample(self, fn, key, nonce, n_poly, L, prime_index, stream):
+        out = DeviceBuffer(max(n_poly, 1) * L * self.n)
+        _check(fn(self.h, self._key(key), int(nonce), out.ptr, n_poly, L, self._pidx(prime_index), stream))
+        return out
+
+    def sample_uniform(self, key, nonce, n_poly, L, prime_index=None, stream=None):
+        """[n_poly][L][N] uniform residues; polynomial p from the stream (key, nonce + p)."""
+        return self._sample(lib().moai_sample_uniform, key, nonce, n_poly, L, prime_index, stream)
+
+    def sample_ternary(self, key, nonce, n_poly, L, prime_index=None, stream=None):
+        """[n_poly][L][N] residues of one ternary polynomial each."""
+        return self._sample(lib().moai_sample_ternary, key, nonce, n_poly, L, prime_index, stream)
+
+    def sample_cbd(self, key, nonce, n_poly, L, prime_index=None, stream=None):
+        """[n_poly][L][N] residues of one centred-binomial noise polynomial each."""
+        return self._sample(lib().moai_sample_cbd, key, nonce, n_poly, L, prime_index, stream)
+
+    def encrypt_symmetric(self, key, seq, sk_ntt, L, n_batch=1, plain=None, prime_index=None, stream=None):
+        """Encryptor::encrypt_symmetric of n_batch plaintexts [n_batch][L][N] (None: encryptions of zero) under sk_ntt [L][N].
+        Returns a DeviceBuffer [n_batch][2][L][N]."""
+        out = DeviceBuffer(max(n_batch, 1) * 2 * L * self.n)
+        _check(lib().moai_encrypt_symmetric(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(plain), out.ptr, n_batch, L,
+                                            self._pidx(prime_index), stream))
+        return out
+
+    def encrypt_asymmetric(self, key, seq, pk, L, n_batch=1, plain=None, stream=None):
+        """Encryptor::encrypt with the key-level public key pk [2][k][N] at the level of L primes.
+        Returns a DeviceBuffer [n_batch][2][L][N]."""
+        out = DeviceBuffer(max(n_batch, 1) * 2 * L * self.n)
+        _check(lib().moai_encrypt_asymmetric(self.h, self._key(key), int(seq), _ptr(pk), _ptr(plain), out.ptr, n_batch, L, stream))
+        return out
+
+    def kswitch_keygen(self, key, seq, sk_ntt, new_key_ntt, stream=None):
+        """The k-1 digits of the switching key for new_key_ntt [k][N]: a DeviceBuffer [k-1][2][k][N]."""
+        out = DeviceBuffer(max(self.k - 1, 1) * 2 * self.k * self.n)
+        _check(lib().moai_kswitch_keygen(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(new_key_ntt), out.ptr, stream))
+        return out
 
     def total_coeff_modulus_bit_count(self, L, prime_index=None):
         r = lib().moai_total_coeff_modulus_bit_count(self.h, L, self._pidx(prime_index))

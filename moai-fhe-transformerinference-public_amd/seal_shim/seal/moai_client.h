@@ -150,6 +150,41 @@ namespace seal
             return g;
         }
 
+        // Randomness of the device samplers (include/moai_hip.h, "client randomness and encryption"): a 32-byte ChaCha20 key
+        // drawn from the operating system, and an atomic counter that hands out disjoint ranges of nonce sequences, so that
+        // every encryption or key digit drawn with this object uses a stream of its own, whichever thread asks.  Tests and
+        // tools construct it from a fixed key for reproducible output.
+        class DeviceRng
+        {
+        public:
+            DeviceRng()
+            {
+                ChaCha20Rng::os_random(key_, sizeof(key_));
+            }
+            explicit DeviceRng(const unsigned char (&key)[32], std::uint64_t first_sequence = 0) : next_(first_sequence)
+            {
+                std::memcpy(key_, key, sizeof(key_));
+            }
+            const unsigned char *key() const
+            {
+                return key_;
+            }
+            // the first of `count` consecutive sequence numbers nobody else gets
+            std::uint64_t take(std::uint64_t count)
+            {
+                const std::uint64_t first = next_.fetch_add(count);
+                if (first >= (std::uint64_t(1) << 56) || count > (std::uint64_t(1) << 56) - first)
+                {
+                    throw std::logic_error("device randomness exhausted: draw a new key");
+                }
+                return first;
+            }
+
+        private:
+            unsigned char key_[32];
+            std::atomic<std::uint64_t> next_{ 0 };
+        };
+
         // uniform residues [rows][N], row r under primes[r]
         inline void sample_uniform(const std::vector<std::uint64_t> &primes, std::size_t n, std::vector<std::uint64_t> &out)
         {
@@ -647,6 +682,99 @@ namespace seal
         // relinearization key for s^2 (SEAL/keygenerator.cpp:129-168)
         void create_relin_keys(RelinKeys &destination)
         {
+            create_relin_keys_impl(destination, false);
+        }
+        // keys for the given Galois elements (SEAL/keygenerator.cpp:170-235)
+        void create_galois_keys(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination)
+        {
+            create_galois_keys_impl(galois_elts, destination, false);
+        }
+
+        // ---- device key generation (opt-in, moai_fused::create_*; not part of the reference API) ------------------------
+        // The same keys drawn on the device from util::DeviceRng streams: one moai_encrypt_symmetric for the public key and
+        // one moai_kswitch_keygen per switching key (all k-1 digits in one chain of launches).
+        void create_public_key_device(PublicKey &destination) const
+        {
+            destination.ct_.resize(context_, context_.key_parms_id(), 2);
+            util::hip_check(moai_encrypt_symmetric(context_.device(), rng_->key(), rng_->take(1), sk_.ntt_->get(), nullptr,
+                                                   destination.ct_.device_data(), 1, k_, nullptr, context_.stream()));
+            destination.ct_.is_ntt_form() = true;
+            destination.ct_.scale() = 1.0;
+            context_.sync();
+        }
+        void create_relin_keys_device(RelinKeys &destination)
+        {
+            create_relin_keys_impl(destination, true);
+        }
+        void create_galois_keys_device(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination)
+        {
+            create_galois_keys_impl(galois_elts, destination, true);
+        }
+        // the randomness of the device paths (a fresh OS-keyed one by default)
+        void set_device_rng(std::shared_ptr<util::DeviceRng> rng)
+        {
+            if (!rng)
+            {
+                throw std::invalid_argument("rng cannot be null");
+            }
+            rng_ = std::move(rng);
+        }
+        const std::shared_ptr<util::DeviceRng> &device_rng() const
+        {
+            return rng_;
+        }
+        // GaloisTool::get_elts_all (SEAL/util/galois.cpp:106-131): the conjugation and every power-of-two rotation
+        std::vector<std::uint32_t> galois_elts_all() const
+        {
+            std::vector<std::uint32_t> elts;
+            const std::uint64_t m = static_cast<std::uint64_t>(n_) << 1;
+            elts.push_back(static_cast<std::uint32_t>(m - 1));
+            std::uint64_t pos = 5, neg = 0;
+            for (std::uint64_t x = 1; x < m; x += 2)
+            {
+                if (((x * 5) & (m - 1)) == 1)
+                {
+                    neg = x;
+                    break;
+                }
+            }
+            for (int i = 0; i < context_.logn() - 1; i++)
+            {
+                elts.push_back(static_cast<std::uint32_t>(pos));
+                pos = (pos * pos) & (m - 1);
+                elts.push_back(static_cast<std::uint32_t>(neg));
+                neg = (neg * neg) & (m - 1);
+            }
+            return elts;
+        }
+        std::vector<std::uint32_t> galois_elts_from_steps(const std::vector<int> &steps) const
+        {
+            std::vector<std::uint32_t> elts;
+            for (int s : steps)
+            {
+                std::uint32_t e = moai_galois_elt_from_step(context_.device(), s);
+                if (!e)
+                {
+                    throw std::invalid_argument("step count too large");
+                }
+                elts.push_back(e);
+            }
+            return elts;
+        }
+        void create_galois_keys(const std::vector<int> &steps, GaloisKeys &destination)
+        {
+            create_galois_keys(galois_elts_from_steps(steps), destination);
+        }
+        // all power-of-two rotations and the conjugation (GaloisTool::get_elts_all,
+        // SEAL/util/galois.cpp:106-131)
+        void create_galois_keys(GaloisKeys &destination)
+        {
+            create_galois_keys(galois_elts_all(), destination);
+        }
+
+    private:
+        void create_relin_keys_impl(RelinKeys &destination, bool device)
+        {
             if (!context_.using_keyswitching())
             {
                 throw std::logic_error("keyswitching is not supported by the context");
@@ -657,12 +785,11 @@ namespace seal
             destination.keys_.assign(1, nullptr);
             destination.hoist_ = std::make_shared<KSwitchKeys::HoistCache>(); // constants derived from the keys this call replaces
             destination.generation_ = KSwitchKeys::next_generation();
-            destination.keys_[0] = make_kswitch_key(s2.get());
+            destination.keys_[0] = device ? make_kswitch_key_device(s2.get()) : make_kswitch_key(s2.get());
             destination.parms_id_ = context_.key_parms_id();
             context_.sync();
         }
-        // keys for the given Galois elements (SEAL/keygenerator.cpp:170-235)
-        void create_galois_keys(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination)
+        void create_galois_keys_impl(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination, bool device)
         {
             if (!context_.using_keyswitching())
             {
@@ -687,52 +814,19 @@ namespace seal
                 }
                 util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_, elt,
                                                     context_.stream()));
-                destination.keys_[GaloisKeys::get_index(elt)] = make_kswitch_key(rotated.get());
+                destination.keys_[GaloisKeys::get_index(elt)] = device ? make_kswitch_key_device(rotated.get()) : make_kswitch_key(rotated.get());
             }
             destination.parms_id_ = context_.key_parms_id();
             context_.sync();
         }
-        void create_galois_keys(const std::vector<int> &steps, GaloisKeys &destination)
+        // moai_kswitch_keygen: all k-1 digits in one chain of launches
+        std::shared_ptr<util::DeviceArray> make_kswitch_key_device(const std::uint64_t *new_key_ntt) const
         {
-            std::vector<std::uint32_t> elts;
-            for (int s : steps)
-            {
-                std::uint32_t e = moai_galois_elt_from_step(context_.device(), s);
-                if (!e)
-                {
-                    throw std::invalid_argument("step count too large");
-                }
-                elts.push_back(e);
-            }
-            create_galois_keys(elts, destination);
+            auto key = std::make_shared<util::DeviceArray>((k_ - 1) * 2 * k_ * n_, context_.stream());
+            util::hip_check(moai_kswitch_keygen(context_.device(), rng_->key(), rng_->take(k_ - 1), sk_.ntt_->get(), new_key_ntt,
+                                                key->get(), context_.stream()));
+            return key;
         }
-        // all power-of-two rotations and the conjugation (GaloisTool::get_elts_all,
-        // SEAL/util/galois.cpp:106-131)
-        void create_galois_keys(GaloisKeys &destination)
-        {
-            std::vector<std::uint32_t> elts;
-            const std::uint64_t m = static_cast<std::uint64_t>(n_) << 1;
-            elts.push_back(static_cast<std::uint32_t>(m - 1));
-            std::uint64_t pos = 5, neg = 0;
-            for (std::uint64_t x = 1; x < m; x += 2)
-            {
-                if (((x * 5) & (m - 1)) == 1)
-                {
-                    neg = x;
-                    break;
-                }
-            }
-            for (int i = 0; i < context_.logn() - 1; i++)
-            {
-                elts.push_back(static_cast<std::uint32_t>(pos));
-                pos = (pos * pos) & (m - 1);
-                elts.push_back(static_cast<std::uint32_t>(neg));
-                neg = (neg * neg) & (m - 1);
-            }
-            create_galois_keys(elts, destination);
-        }
-
-    private:
         void upload_ntt(const std::vector<std::uint64_t> &rns, util::DeviceArray &dst, std::size_t rows) const
         {
             util::hip_check(moai_memcpy_h2d(dst.get(), rns.data(), rows * n_ * 8, context_.stream()));
@@ -819,6 +913,7 @@ namespace seal
         std::vector<std::uint64_t> primes_;
         std::size_t n_ = 0, k_ = 0;
         SecretKey sk_;
+        std::shared_ptr<util::DeviceRng> rng_ = std::make_shared<util::DeviceRng>();
     };
 
     // =================================================================================================
@@ -829,9 +924,69 @@ namespace seal
     public:
         Encryptor(const SEALContext &context, const PublicKey &public_key) : context_(context), pk_(public_key.data())
         {}
-        Encryptor(const SEALContext &context, const SecretKey &) : context_(context)
+        // symmetric encryption runs on the device (moai_encrypt_symmetric) with util::DeviceRng randomness
+        Encryptor(const SEALContext &context, const SecretKey &secret_key) : context_(context), sk_(secret_key.ntt_)
+        {}
+        Encryptor(const SEALContext &context, const PublicKey &public_key, const SecretKey &secret_key)
+            : context_(context), pk_(public_key.data()), sk_(secret_key.ntt_)
+        {}
+        void set_public_key(const PublicKey &public_key)
         {
-            throw std::logic_error("symmetric Encryptor is not provided");
+            pk_ = public_key.data();
+        }
+        void set_secret_key(const SecretKey &secret_key)
+        {
+            sk_ = secret_key.ntt_;
+        }
+        // Encryptor::encrypt_symmetric (SEAL/encryptor.h:337-372, encryptor.cpp:88-120): one moai_encrypt_symmetric launch chain
+        void encrypt_symmetric(const Plaintext &plain, Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            auto cd = context_.get_context_data(plain.parms_id());
+            if (!cd || !plain.is_ntt_form())
+            {
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            }
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            const std::uint64_t *p = plain.is_scalar() ? nullptr : plain.device_data();
+            encrypt_symmetric_device(plain.parms_id(), p, destination);
+            if (plain.is_scalar())
+            {
+                util::hip_check(moai_add_scalar_rows(context_.device(), destination.device_data(), plain.scalar_rows().data(),
+                                                     destination.device_data(), 1, L, context_.stream()));
+            }
+            destination.scale() = plain.scale();
+            context_.sync();
+        }
+        void encrypt_zero_symmetric(parms_id_type parms_id, Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            encrypt_symmetric_device(parms_id, nullptr, destination);
+            context_.sync();
+        }
+        void encrypt_zero_symmetric(Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            encrypt_zero_symmetric(context_.first_parms_id(), destination);
+        }
+        // ---- for moai_fused (not part of the reference API) ----------------------------------------------------------------
+        // the key-level public key [2][k][N] on the device, null when none is set
+        const std::uint64_t *public_key_device() const
+        {
+            return pk_.size() ? pk_.device_data() : nullptr;
+        }
+        const SEALContext &context() const
+        {
+            return context_;
+        }
+        void set_device_rng(std::shared_ptr<util::DeviceRng> rng)
+        {
+            if (!rng)
+            {
+                throw std::invalid_argument("rng cannot be null");
+            }
+            rng_ = std::move(rng);
+        }
+        const std::shared_ptr<util::DeviceRng> &device_rng() const
+        {
+            return rng_;
         }
         // public-key encryption at the level of `plain` (SEAL/encryptor.cpp encrypt_internal; the
         // reference samples at the key level and divides by the special prime, here the public key is
@@ -863,6 +1018,10 @@ namespace seal
             if (!cd)
             {
                 throw std::invalid_argument("parms_id is not valid for encryption parameters");
+            }
+            if (!pk_.size())
+            {
+                throw std::logic_error("public key is not set");
             }
             const auto &cm = cd->parms().coeff_modulus();
             const std::size_t L = cm.size(), n = context_.n();
@@ -909,8 +1068,29 @@ namespace seal
         }
 
     private:
+        void encrypt_symmetric_device(parms_id_type parms_id, const std::uint64_t *plain, Ciphertext &destination) const
+        {
+            auto cd = context_.get_context_data(parms_id);
+            if (!cd)
+            {
+                throw std::invalid_argument("parms_id is not valid for encryption parameters");
+            }
+            if (!sk_)
+            {
+                throw std::logic_error("secret key is not set");
+            }
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            destination.resize(context_, parms_id, 2);
+            destination.is_ntt_form() = true;
+            destination.scale() = 1.0;
+            util::hip_check(moai_encrypt_symmetric(context_.device(), rng_->key(), rng_->take(1), sk_->get(), plain,
+                                                   destination.device_data(), 1, L, nullptr, context_.stream()));
+        }
+
         SEALContext context_;
         Ciphertext pk_;
+        std::shared_ptr<util::DeviceArray> sk_;
+        std::shared_ptr<util::DeviceRng> rng_ = std::make_shared<util::DeviceRng>();
     };
 
     class Decryptor

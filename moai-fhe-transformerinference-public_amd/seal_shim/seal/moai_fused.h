@@ -760,4 +760,175 @@ namespace moai_fused
         seal_context.sync();
         return output;
     }
+
+    // ---- the client's input path on the device (opt-in; include/moai_hip.h "client randomness and encryption") ---------
+    // Keys drawn on the device from the key generator's util::DeviceRng: ordinary PublicKey / RelinKeys / GaloisKeys (fresh
+    // generation and hoisting cache, as KeyGenerator's own methods give them), so every evaluator path takes them unchanged.
+    inline void create_public_key(seal::KeyGenerator &keygen, seal::PublicKey &destination)
+    {
+        keygen.create_public_key_device(destination);
+    }
+    inline void create_relin_keys(seal::KeyGenerator &keygen, seal::RelinKeys &destination)
+    {
+        keygen.create_relin_keys_device(destination);
+    }
+    inline void create_galois_keys(seal::KeyGenerator &keygen, const std::vector<std::uint32_t> &galois_elts, seal::GaloisKeys &destination)
+    {
+        keygen.create_galois_keys_device(galois_elts, destination);
+    }
+    inline void create_galois_keys(seal::KeyGenerator &keygen, const std::vector<int> &steps, seal::GaloisKeys &destination)
+    {
+        keygen.create_galois_keys_device(keygen.galois_elts_from_steps(steps), destination);
+    }
+    inline void create_galois_keys(seal::KeyGenerator &keygen, seal::GaloisKeys &destination)
+    {
+        keygen.create_galois_keys_device(keygen.galois_elts_all(), destination);
+    }
+
+    namespace detail
+    {
+        // encrypts `count` NTT-form plaintexts [count][L][N] (contiguous, device) at level parms_id into cts[first ..), batched:
+        // SEAL-faithful public-key encryption (moai_encrypt_asymmetric), then one scatter per 64 ciphertexts
+        inline void encrypt_packed(const seal::Encryptor &encryptor, seal::parms_id_type parms_id, const std::uint64_t *plains,
+                                   std::size_t count, double scale, std::vector<seal::Ciphertext> &cts, std::size_t first)
+        {
+            using namespace seal;
+            const SEALContext &context = encryptor.context();
+            const std::uint64_t *pk = encryptor.public_key_device();
+            if (!pk)
+            {
+                throw std::logic_error("public key is not set");
+            }
+            const std::size_t n = context.n();
+            const std::size_t L = context.get_context_data(parms_id)->parms().coeff_modulus().size();
+            void *st = context.stream();
+            util::DeviceArray packed(count * 2 * L * n, st);
+            const auto &rng = encryptor.device_rng();
+            util::hip_check(moai_encrypt_asymmetric(context.device(), rng->key(), rng->take(count), pk, plains, packed.get(), count, L, st));
+            for (std::size_t g = 0; g < count; g += 64)
+            {
+                const std::size_t m = std::min<std::size_t>(64, count - g);
+                std::uint64_t *dst[64];
+                for (std::size_t j = 0; j < m; j++)
+                {
+                    Ciphertext &c = cts[first + g + j];
+                    c.resize(context, parms_id, 2);
+                    c.is_ntt_form() = true;
+                    c.scale() = scale;
+                    dst[j] = c.device_data();
+                }
+                util::hip_check(moai_scatter_blocks(context.device(), packed.get() + g * 2 * L * n, dst, m, 2 * L * n, st));
+            }
+            context.sync();
+        }
+    } // namespace detail
+
+    // Encryptor::encrypt for many plaintexts (SEAL/encryptor.cpp:88-173 with the public key): batched device launches per run
+    // of plaintexts at one level and scale.  Scalar-row plaintexts are refused (std::invalid_argument): encode them as vectors,
+    // or encrypt them with Encryptor::encrypt.
+    inline void encrypt(const seal::Encryptor &encryptor, const std::vector<seal::Plaintext> &plains, std::vector<seal::Ciphertext> &cts)
+    {
+        using namespace seal;
+        const SEALContext &context = encryptor.context();
+        const std::size_t n = context.n();
+        void *st = context.stream();
+        cts.resize(plains.size());
+        for (std::size_t i = 0; i < plains.size();)
+        {
+            const Plaintext &p0 = plains[i];
+            auto cd = context.get_context_data(p0.parms_id());
+            if (!cd || !p0.is_ntt_form())
+            {
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            }
+            if (p0.is_scalar())
+            {
+                throw std::invalid_argument("moai_fused::encrypt takes vector plaintexts");
+            }
+            std::size_t j = i + 1;
+            while (j < plains.size() && j - i < 64 && plains[j].parms_id() == p0.parms_id() && plains[j].scale() == p0.scale() &&
+                   !plains[j].is_scalar() && plains[j].is_ntt_form())
+            {
+                j++;
+            }
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            util::DeviceArray packed((j - i) * L * n, st);
+            const std::uint64_t *src[64];
+            for (std::size_t t = i; t < j; t++)
+            {
+                src[t - i] = plains[t].device_data();
+            }
+            util::hip_check(moai_gather_blocks(context.device(), src, packed.get(), j - i, L * n, st));
+            detail::encrypt_packed(encryptor, p0.parms_id(), packed.get(), j - i, p0.scale(), cts, i);
+            i = j;
+        }
+    }
+
+    // batch_input of MOAI (include/source/matrix_mul/Batch_encode_encrypt.hpp:8-38): column i of the inputs, slot
+    // num_X * k + j = X[j][k][i], encoded at `scale` (moai_ckks_encode, many columns per launch) and encrypted with pk on the
+    // device in batched launches.  Same slot layout and level as the reference; fresh randomness (rng: null = OS-keyed).
+    inline std::vector<seal::Ciphertext> batch_input(const std::vector<std::vector<std::vector<double>>> &X, int num_X, int num_row,
+                                                     int num_col, double scale, const seal::SEALContext &seal_context,
+                                                     const seal::PublicKey &pk,
+                                                     std::shared_ptr<seal::util::DeviceRng> rng = nullptr)
+    {
+        using namespace seal;
+        Encryptor encryptor(seal_context, pk);
+        if (rng)
+        {
+            encryptor.set_device_rng(rng);
+        }
+        const std::size_t n = seal_context.n(), slots = n / 2;
+        const parms_id_type parms_id = seal_context.first_parms_id();
+        auto cd = seal_context.get_context_data(parms_id);
+        const std::size_t L = cd->parms().coeff_modulus().size();
+        if (scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= cd->total_coeff_modulus_bit_count()))
+        {
+            throw std::invalid_argument("scale out of bounds");
+        }
+        if (static_cast<std::size_t>(num_X) * static_cast<std::size_t>(num_row) > slots)
+        {
+            throw std::invalid_argument("values_size is too large");
+        }
+        void *st = seal_context.stream();
+        std::vector<Ciphertext> output(num_col);
+        constexpr std::size_t G = 64;
+        std::vector<double> vals(G * slots);
+        util::DeviceArray dvals(G * slots, st);
+        util::DeviceArray dmax(G, st);
+        util::DeviceArray plains(G * L * n, st);
+        for (int c0 = 0; c0 < num_col; c0 += static_cast<int>(G))
+        {
+            const std::size_t m = std::min<std::size_t>(G, static_cast<std::size_t>(num_col - c0));
+            std::fill(vals.begin(), vals.end(), 0.0);
+            for (std::size_t t = 0; t < m; t++)
+            {
+                double *vec = vals.data() + t * slots;
+                for (int j = 0; j < num_X; ++j)
+                {
+                    for (int k = 0; k < num_row; ++k)
+                    {
+                        vec[num_X * k + j] = X[j][k][c0 + t];
+                    }
+                }
+            }
+            util::hip_check(moai_memcpy_h2d(dvals.get(), vals.data(), m * slots * 8, st));
+            util::hip_check(moai_ckks_encode(seal_context.device(), reinterpret_cast<const double *>(dvals.get()), 0, slots, m,
+                                             plains.get(), L, nullptr, scale, reinterpret_cast<double *>(dmax.get()), st));
+            // ckks.h:527-538 for every column
+            std::vector<double> mx(m);
+            util::hip_check(moai_memcpy_d2h(mx.data(), dmax.get(), m * 8, st));
+            seal_context.sync();
+            for (double v : mx)
+            {
+                const int bits = static_cast<int>(std::ceil(std::log2(std::max<>(v, 1.0)))) + 1;
+                if (!(bits < cd->total_coeff_modulus_bit_count()))
+                {
+                    throw std::invalid_argument("encoded values are too large");
+                }
+            }
+            detail::encrypt_packed(encryptor, parms_id, plains.get(), m, scale, output, static_cast<std::size_t>(c0));
+        }
+        return output;
+    }
 } // namespace moai_fused
