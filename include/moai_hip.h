@@ -317,6 +317,11 @@ int moai_ckks_encode_masked(moai_ctx *ctx, const double *constants, const int32_
  * (re, im).  Large batches are processed in chunks whose scratch fits the stream's arena or MOAI_DEC_TMP_MB (default
  * 1024 MiB), whichever is larger.  Errors (before anything is enqueued): MOAI_EINVAL "scale out of bounds" when
  * scale <= 0 or (int)log2(scale) >= total_coeff_modulus_bit_count (ckks.h:672-677; a non-finite scale too).
+ * moai_ckks_decode_sparse: the same with the reference's sparse_slots_ (ckks.h:703-713, :757-760): after the CRT composition
+ * every coefficient i with i mod (N/2 / sparse_slots) != 0 is zeroed (its double is +0.0), the conversion and the full-length
+ * forward DWT run as above, and the gather returns the first sparse_slots entries.  out: device [n_batch][sparse_slots]
+ * doubles or [n_batch][sparse_slots][2].  sparse_slots == N/2 gives exactly the bits of moai_ckks_decode.  Errors (before
+ * anything is enqueued): MOAI_EINVAL when sparse_slots is not a power of two in [1, N/2], and those of moai_ckks_decode.
  * Neither call synchronises. */
 /* Decryptor::ckks_decrypt, SEAL/decryptor.cpp:154-187 with dot_product_ct_sk_array :299-381 */
 int moai_decrypt(moai_ctx *ctx, const uint64_t *ct, size_t size, const uint64_t *sk_ntt, uint64_t *out,
@@ -325,6 +330,10 @@ int moai_decrypt(moai_ctx *ctx, const uint64_t *ct, size_t size, const uint64_t 
 int moai_ckks_decode(moai_ctx *ctx, const uint64_t *plain_ntt, size_t n_batch, size_t L,
                      const uint32_t *prime_index, const double *scales /* host, [n_batch] */,
                      int is_complex, double *out /* device, [n_batch][N/2] or [n_batch][N/2][2] */, void *stream);
+/* CKKSEncoder::decode_internal with sparse_slots_ != slots_, SEAL/ckks.h:644-761 */
+int moai_ckks_decode_sparse(moai_ctx *ctx, const uint64_t *plain_ntt, size_t n_batch, size_t L,
+                            const uint32_t *prime_index, const double *scales /* host, [n_batch] */, size_t sparse_slots,
+                            int is_complex, double *out /* device, [n_batch][sparse_slots] or [..][2] */, void *stream);
 /* ContextData::total_coeff_modulus_bit_count (SEAL/context.cpp:169-173): significant bits of the product of
  * the L primes; 0 on error. */
 int moai_total_coeff_modulus_bit_count(const moai_ctx *ctx, size_t L, const uint32_t *prime_index);

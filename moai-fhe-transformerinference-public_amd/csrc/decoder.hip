@@ -97,6 +97,7 @@ struct ComposeArgs
     uint32_t L;
     uint32_t W;
     uint32_t logn;
+    uint32_t zero_mask; // sparse decode: coefficients with (p & zero_mask) != 0 are projected away (0 = keep all)
     double inv_scale[DEC_SCALES];
 };
 
@@ -110,6 +111,12 @@ __global__ __launch_bounds__(256) void dec_compose(ComposeArgs g)
         return;
     }
     const uint32_t b = blockIdx.y;
+    if (p & g.zero_mask)
+    {
+        // ckks.h:704-712 zeroes the composed words; the conversion of an all-zero x is +0.0
+        g.out[(size_t)b * n + p] = make_double2(0.0, 0.0);
+        return;
+    }
     const uint64_t *in = g.in + (size_t)b * g.L * n + p;
     uint64_t x[NW];
 #pragma unroll
@@ -271,8 +278,9 @@ struct TailArgs
     const double2 *data;   // [n_batch][N]
     const double2 *roots;  // root_powers_ [N]
     const uint32_t *src;   // [N]: slot whose matrix_reps_index_map_ entry is this position
-    double *out;           // [n_batch][N/2] or [n_batch][N/2][2]
+    double *out;           // [n_batch][out_slots] or [n_batch][out_slots][2]
     uint32_t logn;
+    uint32_t out_slots;    // N/2, or the sparse slot count
     uint32_t first_stage;  // max(logn - 12, 0)
     uint32_t is_complex;
 };
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(256) void dec_fft_tail(TailArgs g)
     __shared__ double re[DEC_TILE];
     __shared__ double im[DEC_TILE];
     const uint32_t n = 1u << g.logn;
-    const uint32_t slots = n >> 1;
+    const uint32_t slots = g.out_slots;
     const uint32_t tile = n < DEC_TILE ? n : DEC_TILE;
     const uint32_t tiles = n / tile;
     const uint32_t b = blockIdx.x / tiles;
@@ -316,7 +324,7 @@ __global__ __launch_bounds__(256) void dec_fft_tail(TailArgs g)
         }
         __syncthreads();
     }
-    // destination[i] = res[matrix_reps_index_map_[i]] for i < slots (ckks.h:757-760), through the inverse map
+    // destination[i] = res[matrix_reps_index_map_[i]] for i < out_slots (ckks.h:757-760), through the inverse map
     for (uint32_t k = tid; k < tile; k += 256)
     {
         const uint32_t slot = g.src[base + k];
@@ -575,16 +583,10 @@ extern "C" int moai_decrypt(moai_ctx *c, const uint64_t *ct, size_t size, const 
     return MOAI_OK;
 }
 
-extern "C" int moai_ckks_decode(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L,
-                                const uint32_t *prime_index, const double *scales, int is_complex, double *out,
-                                void *stream)
+// decode_internal with sparse_slots_ = out_slots (N/2: the full-slot decode); the caller has validated out_slots
+static int ckks_decode_impl(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L, const uint32_t *prime_index,
+                            const double *scales, size_t out_slots, int is_complex, double *out, void *stream)
 {
-    MOAI_AUDIT(stream, plain_ntt, out);
-    trace_op("ckks_decode", L, n_batch);
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
     if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
     {
         return set_error(MOAI_EINVAL, "invalid level");
@@ -655,10 +657,11 @@ extern "C" int moai_ckks_decode(moai_ctx *c, const uint64_t *plain_ntt, size_t n
     a.L = (uint32_t)L;
     a.W = W;
     a.logn = (uint32_t)c->logn;
+    a.zero_mask = (uint32_t)((n >> 1) / out_slots - 1); // sparsity - 1 (ckks.h:705)
     const uint32_t logn = (uint32_t)c->logn;
     const int R = logn > (uint32_t)DEC_TILE_LOG ? (int)logn - DEC_TILE_LOG : 0;
     const uint32_t tile = n < DEC_TILE ? (uint32_t)n : DEC_TILE;
-    const size_t slots = n >> 1;
+    const size_t slots = out_slots;
     for (size_t b0 = 0; b0 < n_batch; b0 += cb)
     {
         const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
@@ -705,10 +708,41 @@ extern "C" int moai_ckks_decode(moai_ctx *c, const uint64_t *plain_ntt, size_t n
         t.src = c->ckks_src_map;
         t.out = out + b0 * slots * (is_complex ? 2 : 1);
         t.logn = logn;
+        t.out_slots = (uint32_t)out_slots;
         t.first_stage = (uint32_t)R;
         t.is_complex = is_complex ? 1u : 0u;
         hipLaunchKernelGGL(dec_fft_tail, dim3((uint32_t)(nb * (n / tile))), dim3(256), 0, s, t);
         MOAI_LAUNCH_CHECK();
     }
     return MOAI_OK;
+}
+
+extern "C" int moai_ckks_decode(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L,
+                                const uint32_t *prime_index, const double *scales, int is_complex, double *out,
+                                void *stream)
+{
+    MOAI_AUDIT(stream, plain_ntt, out);
+    trace_op("ckks_decode", L, n_batch);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    return ckks_decode_impl(c, plain_ntt, n_batch, L, prime_index, scales, c->n >> 1, is_complex, out, stream);
+}
+
+extern "C" int moai_ckks_decode_sparse(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L,
+                                       const uint32_t *prime_index, const double *scales, size_t sparse_slots,
+                                       int is_complex, double *out, void *stream)
+{
+    MOAI_AUDIT(stream, plain_ntt, out);
+    trace_op("ckks_decode_sparse", L, n_batch);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (sparse_slots == 0 || sparse_slots > (c->n >> 1) || (sparse_slots & (sparse_slots - 1)) != 0)
+    {
+        return set_error(MOAI_EINVAL, "sparse_slots must be a power of two in [1, N/2]");
+    }
+    return ckks_decode_impl(c, plain_ntt, n_batch, L, prime_index, scales, sparse_slots, is_complex, out, stream);
 }

@@ -72,6 +72,7 @@ SYMBOLS = {
     "moai_ckks_encode_masked": (C.c_int, [vp, vp, vp, sz, sz, vp, sz, C.POINTER(C.c_uint32), C.c_double, vp, vp]),
     "moai_decrypt": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_ckks_decode": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_int, vp, vp]),
+    "moai_ckks_decode_sparse": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_double), sz, C.c_int, vp, vp]),
     "moai_sample_uniform": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_sample_ternary": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_sample_cbd": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
@@ -465,6 +466,27 @@ class Context:
         out = DeviceBuffer(words)
         _check(lib().moai_ckks_decode(self.h, _ptr(plain), n_batch, L, self._pidx(prime_index),
                                       sc.ctypes.data_as(C.POINTER(C.c_double)), 1 if is_complex else 0, out.ptr, stream))
+        host = np.empty(words, dtype=np.float64)
+        _check(lib().moai_memcpy_d2h(host.ctypes.data, out.ptr, words * 8, stream))
+        _check(lib().moai_stream_sync(stream))
+        host = host[: n_batch * slots * (2 if is_complex else 1)]
+        if is_complex:
+            return host.view(np.complex128).reshape(n_batch, slots)
+        return host.reshape(n_batch, slots)
+
+    def ckks_decode_sparse(self, plain, L, scales, sparse_slots, n_batch=1, prime_index=None, is_complex=False, stream=None):
+        """CKKSEncoder::decode with sparse_slots set: the projection onto the sparse subring, then the first sparse_slots
+        slots.  Returns numpy [n_batch][sparse_slots], float64 or complex128."""
+        sc = np.broadcast_to(np.asarray(scales, dtype=np.float64), (n_batch,))
+        sc = np.ascontiguousarray(sc)
+        slots = int(sparse_slots)
+        if slots < 1:
+            raise ValueError("sparse_slots must be a power of two in [1, N/2]")
+        words = max(n_batch, 1) * slots * (2 if is_complex else 1)
+        out = DeviceBuffer(words)
+        _check(lib().moai_ckks_decode_sparse(self.h, _ptr(plain), n_batch, L, self._pidx(prime_index),
+                                             sc.ctypes.data_as(C.POINTER(C.c_double)), slots, 1 if is_complex else 0,
+                                             out.ptr, stream))
         host = np.empty(words, dtype=np.float64)
         _check(lib().moai_memcpy_d2h(host.ctypes.data, out.ptr, words * 8, stream))
         _check(lib().moai_stream_sync(stream))

@@ -8,9 +8,15 @@
 //   change_logn (:508-520), genorigcoeff/genfftcoeff_3/geninvfftcoeff_3 through generate_LT_coefficient_3 (:1967-1971),
 //   bsgs_linear_transform / rotated_bsgs_linear_transform (:1997-2129), sflinv_full_3 / sfl_full_3 (:2602-2623, :2460-2497),
 //   coefftoslot_full_3 / slottocoeff_full_3 (:2742-2777), modraise_inplace (:2938-2992), bootstrap_full_3 (:3231-3251),
-//   bootstrap_3 / bootstrap_inplace_3 (:3496-3508), set_final_scale.
-// Not provided: the two-level, one-depth, hoisting, "real" and sparse-slot (logn < logNh) variants, which no MOAI
-// driver calls; they throw std::logic_error.
+//   bootstrap_3 / bootstrap_inplace_3 (:3496-3508), set_final_scale,
+//   and the sparse-slot family for 3 <= logn < logNh: the sparse branches of genfftcoeff_3 / geninvfftcoeff_3
+//   (:1298-1414, :1694-1817), bootstrap_sparse_3 (:3143-3229; sub-sum, coefftoslot_3, ONE modular reduction,
+//   slottocoeff_3).  slot_vec may hold several logn values; change_logn picks one.
+// Not provided: the two-level, one-depth, hoisting and "real" variants, which no MOAI driver calls, and the sparse
+// logn = 0 (multiply_vector) branch and logn = 1, 2 (the level-3 split leaves a part of 0 bits); they throw.
+// Keys of a sparse caller: addBootKeys_3 lists every power of two below Nh, which covers the sub-sum's steps n 2^i and
+// slottocoeff_3's rotation by n; addLeftRotKeys_Linear_to_vector_3 (:89-184) lists neither, so a caller that builds
+// its own key list from that routine alone must add the steps 2^i, logn <= i < logNh (as the reference's would).
 //
 // What is different inside:
 //  * no NTL: the modular-reduction polynomial comes from bootstrapping/moai_remez.h, the transform diagonals from
@@ -117,6 +123,7 @@ public:
         final_scale = _final_scale;
         std::lock_guard<std::mutex> g(engine_mu_);
         engine_.reset();
+        sparse_engines_.clear();
     }
 
     // ---- keys ------------------------------------------------------------------------------------------------------
@@ -142,9 +149,7 @@ public:
         std::lock_guard<std::mutex> run(run_mu_); // not while a bootstrap holds a reference to the engine
         logn = new_logn;
         n = (1 << logn);
-        select_slot_index();
-        std::lock_guard<std::mutex> g(engine_mu_);
-        engine_.reset();
+        select_slot_index(); // the engines are built per logn from slot_vec: none depends on the current one
     }
 
     // ---- constants -------------------------------------------------------------------------------------------------
@@ -214,25 +219,46 @@ public:
         std::lock_guard<std::mutex> run(run_mu_);
         engine().bootstrap_3(rtncipher, cipher);
     }
+    // 3 <= logn < logNh; `cipher` is consumed like the reference's
+    void bootstrap_sparse_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        std::lock_guard<std::mutex> run(run_mu_);
+        sparse_engine(logn).bootstrap_3(rtncipher, cipher);
+    }
     void bootstrap_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
         initial_scale = cipher.scale(); // the reference writes this member from every calling thread as well (:3497)
-        if (logn != logNh)
+        const long ln = logn;
+        if (ln != logNh)
         {
-            throw std::logic_error("bootstrap_sparse_3 (logn < logNh) is not provided");
+            check_sparse(ln); // before anything is enqueued
         }
         if (cipher.batch() != 1 || combine_us_ <= 0 || max_pack_ == 1)
         {
-            bootstrap_full_3(rtncipher, cipher);
+            if (ln == logNh)
+            {
+                bootstrap_full_3(rtncipher, cipher);
+            }
+            else
+            {
+                std::lock_guard<std::mutex> run(run_mu_);
+                sparse_engine(ln).bootstrap_3(rtncipher, cipher);
+            }
             return;
         }
-        gather_and_run(rtncipher, cipher);
+        gather_and_run(rtncipher, cipher, ln);
     }
     void bootstrap_inplace_3(Ciphertext &cipher)
     {
         Ciphertext rtncipher;
         bootstrap_3(rtncipher, cipher);
         cipher = rtncipher;
+    }
+    // calls waiting to be gathered into a pack (a caller that must know its call is queued, e.g. before change_logn)
+    std::size_t gather_pending() const
+    {
+        std::lock_guard<std::mutex> g(gather_mu_);
+        return pending_.size();
     }
     // how the calls of this object were grouped so far: {packed runs, ciphertexts}
     std::pair<std::size_t, std::size_t> gather_statistics() const
@@ -249,10 +275,6 @@ public:
     void bootstrap_inplace(Ciphertext &)
     {
         unsupported("bootstrap_inplace");
-    }
-    void bootstrap_sparse_3(Ciphertext &, Ciphertext &)
-    {
-        unsupported("bootstrap_sparse_3");
     }
     void bootstrap_real_3(Ciphertext &, Ciphertext &)
     {
@@ -292,6 +314,13 @@ private:
             throw std::invalid_argument("LT coefficients were not generated for this logn");
         }
     }
+    void check_sparse(long ln) const
+    {
+        if (const char *why = moai_boot::sparse_unsupported_reason(static_cast<int>(ln), static_cast<int>(logNh)))
+        {
+            throw std::invalid_argument(std::string("bootstrap_sparse_3: ") + why);
+        }
+    }
     void generate_sets(bool forward, bool inverse)
     {
         auto size_to = [&](vector<vector<vector<complex<double>>>> &v) { v.resize(slot_vec.size()); };
@@ -305,9 +334,11 @@ private:
         {
             if (slot_vec[u] != logNh)
             {
-                throw std::logic_error("sparse-slot transform coefficients (logn < logNh) are not provided");
+                check_sparse(slot_vec[u]);
             }
-            moai_boot::LevelThreeDiagonals d = moai_boot::level_three_diagonals(static_cast<int>(slot_vec[u]), boundary_K);
+            moai_boot::LevelThreeDiagonals d =
+                slot_vec[u] == logNh ? moai_boot::level_three_diagonals(static_cast<int>(slot_vec[u]), boundary_K)
+                                     : moai_boot::level_three_sparse_diagonals(static_cast<int>(slot_vec[u]), static_cast<int>(logNh), boundary_K);
             if (forward)
             {
                 fftcoeff1[u] = std::move(d.fftcoeff1);
@@ -323,35 +354,76 @@ private:
         }
         std::lock_guard<std::mutex> g(engine_mu_);
         engine_.reset();
+        sparse_engines_.clear();
     }
 
-    // the device pipeline, built on first use from the members above
+    // the sparse pipeline of slot_vec's entry `ln`, built on first use
+    moai_fused::PackedSparseBootstrapper3 &sparse_engine(long ln)
+    {
+        check_sparse(ln);
+        std::lock_guard<std::mutex> g(engine_mu_);
+        auto it = sparse_engines_.find(ln);
+        if (it != sparse_engines_.end())
+        {
+            return *it->second;
+        }
+        const moai_fused::BootDiagonals3 d = diagonals_of(ln);
+        auto e = std::unique_ptr<moai_fused::PackedSparseBootstrapper3>(new moai_fused::PackedSparseBootstrapper3(
+            context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(ln), static_cast<int>(logNh), final_scale, d,
+            mod_reducer->packed_reducer()));
+        return *sparse_engines_.emplace(ln, std::move(e)).first->second;
+    }
+
+    // the full-slot pipeline behind the reference's member-logn entry points (sflinv_full_3 ... bootstrap_full_3)
     moai_fused::PackedBootstrapper3 &engine()
+    {
+        if (logn != logNh)
+        {
+            throw std::logic_error("only logn == logNh is provided");
+        }
+        return full_engine();
+    }
+    // the full-slot pipeline of slot_vec's entry logNh, built on first use; independent of the current logn, so a gathered
+    // full-slot call runs here whatever change_logn did meanwhile
+    moai_fused::PackedBootstrapper3 &full_engine()
     {
         std::lock_guard<std::mutex> g(engine_mu_);
         if (!engine_)
         {
-            if (logn != logNh)
-            {
-                throw std::logic_error("only logn == logNh is provided");
-            }
-            select_slot_index();
-            const std::size_t u = static_cast<std::size_t>(slot_index);
-            if (fftcoeff1.size() <= u || invfftcoeff1.size() <= u || fftcoeff1[u].empty() || invfftcoeff1[u].empty())
-            {
-                throw std::logic_error("generate_LT_coefficient_3() has not run");
-            }
-            moai_fused::BootDiagonals3 d;
-            d.fftcoeff1 = fftcoeff1[u];
-            d.fftcoeff2 = fftcoeff2[u];
-            d.fftcoeff3 = fftcoeff3[u];
-            d.invfftcoeff1 = invfftcoeff1[u];
-            d.invfftcoeff2 = invfftcoeff2[u];
-            d.invfftcoeff3 = invfftcoeff3[u];
-            engine_.reset(new moai_fused::PackedBootstrapper3(context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(logn),
-                                                              static_cast<int>(logNh), final_scale, d, mod_reducer->packed_reducer()));
+            engine_.reset(new moai_fused::PackedBootstrapper3(context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(logNh),
+                                                              static_cast<int>(logNh), final_scale, diagonals_of(logNh),
+                                                              mod_reducer->packed_reducer()));
         }
         return *engine_;
+    }
+    // the six sets of slot_vec's entry `ln` (caller holds engine_mu_)
+    moai_fused::BootDiagonals3 diagonals_of(long ln) const
+    {
+        std::size_t u = slot_vec.size();
+        for (std::size_t i = 0; i < slot_vec.size(); i++)
+        {
+            if (slot_vec[i] == ln)
+            {
+                u = i;
+                break;
+            }
+        }
+        if (u == slot_vec.size())
+        {
+            throw std::invalid_argument("LT coefficients were not generated for this logn");
+        }
+        if (fftcoeff1.size() <= u || invfftcoeff1.size() <= u || fftcoeff1[u].empty() || invfftcoeff1[u].empty())
+        {
+            throw std::logic_error("generate_LT_coefficient_3() has not run");
+        }
+        moai_fused::BootDiagonals3 d;
+        d.fftcoeff1 = fftcoeff1[u];
+        d.fftcoeff2 = fftcoeff2[u];
+        d.fftcoeff3 = fftcoeff3[u];
+        d.invfftcoeff1 = invfftcoeff1[u];
+        d.invfftcoeff2 = invfftcoeff2[u];
+        d.invfftcoeff3 = invfftcoeff3[u];
+        return d;
     }
     moai_fused::BsgsLinearTransform &transform(bool rotated, int totlen, int basicstep, int coeff_logn,
                                                const vector<vector<complex<double>>> &fftcoeff)
@@ -374,15 +446,16 @@ private:
     {
         Ciphertext *out;
         Ciphertext *in;
+        long logn; // the caller's logn: calls with different logn, or sparse and full ones, never share a pack
         bool done = false;
         std::exception_ptr error;
     };
     // Every caller queues its request; the caller at the head of the queue leads ONE packed run (its own request is part
     // of it), the others sleep until their request is done or they reach the head.  All waits end: a leader's wait for
     // company is bounded by the window, and a finished run always wakes the queue.
-    void gather_and_run(Ciphertext &rtncipher, Ciphertext &cipher)
+    void gather_and_run(Ciphertext &rtncipher, Ciphertext &cipher, long ln)
     {
-        Request me{ &rtncipher, &cipher };
+        Request me{ &rtncipher, &cipher, ln };
         std::unique_lock<std::mutex> lk(gather_mu_);
         pending_.push_back(&me);
         gather_cv_.notify_all();
@@ -443,7 +516,7 @@ private:
             std::rethrow_exception(me.error);
         }
     }
-    // members are grouped by (level, scale); each group is one packed run
+    // members are grouped by (logn, level, scale); each group is one packed run
     void run_batch(const std::vector<Request *> &batch)
     {
         std::vector<bool> used(batch.size(), false);
@@ -456,7 +529,7 @@ private:
             std::vector<std::size_t> group;
             for (std::size_t j = i; j < batch.size(); j++)
             {
-                if (!used[j] && batch[j]->in->parms_id() == batch[i]->in->parms_id() && batch[j]->in->scale() == batch[i]->in->scale() &&
+                if (!used[j] && batch[j]->logn == batch[i]->logn && batch[j]->in->parms_id() == batch[i]->in->parms_id() && batch[j]->in->scale() == batch[i]->in->scale() &&
                     batch[j]->in->size() == batch[i]->in->size() && batch[j]->in->is_ntt_form() == batch[i]->in->is_ntt_form())
                 {
                     group.push_back(j);
@@ -467,10 +540,20 @@ private:
             try
             {
                 std::lock_guard<std::mutex> run(run_mu_);
-                auto &e = engine();
+                const long ln = batch[i]->logn;
+                auto boot = [&](Ciphertext &out, Ciphertext &in) {
+                    if (ln == logNh)
+                    {
+                        full_engine().bootstrap_3(out, in);
+                    }
+                    else
+                    {
+                        sparse_engine(ln).bootstrap_3(out, in);
+                    }
+                };
                 if (group.size() == 1)
                 {
-                    e.bootstrap_3(*batch[group[0]]->out, *batch[group[0]]->in);
+                    boot(*batch[group[0]]->out, *batch[group[0]]->in);
                 }
                 else
                 {
@@ -482,7 +565,7 @@ private:
                     }
                     Ciphertext packed = moai_fused::pack(members, context), packed_out;
                     members.clear();
-                    e.bootstrap_3(packed_out, packed);
+                    boot(packed_out, packed);
                     std::vector<Ciphertext> outs;
                     moai_fused::unpack(packed_out, context, outs);
                     for (std::size_t g = 0; g < group.size(); g++)
@@ -512,5 +595,6 @@ private:
     std::size_t max_pack_ = 48;
     std::size_t runs_ = 0, members_ = 0;
     std::unique_ptr<moai_fused::PackedBootstrapper3> engine_;
+    std::map<long, std::unique_ptr<moai_fused::PackedSparseBootstrapper3>> sparse_engines_;
     std::map<std::tuple<const void *, bool, int, int, int>, std::unique_ptr<moai_fused::BsgsLinearTransform>> transforms_;
 };

@@ -25,6 +25,21 @@
 // ((A B)_{a+b}[k] += A_a[k] B_b[k + a]) -- a dynamic-programming form of the same sums: every entry of a merged
 // matrix has exactly one non-zero path through the butterflies, so each value is the same product of the same roots,
 // multiplied in the same (first stage first) order.  Host-only setup code, double precision like the reference's.
+//
+// Sparse slots (logn < logNh, bootstrap_sparse_3; the reference's branches genfftcoeff_3 :1298-1414, geninvfftcoeff_3
+// :1694-1817).  After the sub-sum the slot vector has period n and holds the 2n subring coefficients t as U (t_lo + i t_hi)
+// (zeta = exp(2 pi i / 4n)).  Same splits as the full case; the arrays are
+//   fftcoeff1/2   [2 totlen + 1][2n]: centred, the n-entry diagonal written twice (both halves of a 2n-periodic vector)
+//   fftcoeff3     [2 totlen + 1][2n]: CENTRED (not rotated), second half = i * first half
+//   invfftcoeff1  [totlen + 1][n]   : rotated, scaled by 1 / (boundary_K 2^(logNh - logn)) (undoes the sub-sum's factor)
+//   invfftcoeff2  [2 totlen + 1][n] : centred
+//   invfftcoeff3  [2 totlen + 1][2n]: centred, scaled by 1/2, second half = -i * first half
+// The centred sets hold TRUE offsets: a sparse transform acts on a 2n-periodic vector, where rotating by -h and by n - h
+// differ, so an entry of row k reading column k + d sits at offset d in (-n, n) -- a butterfly path never leaves its block,
+// so 0 <= k + d < n and d is unique (sparse_centred_layout).  Coefficient-to-slot then yields (t_lo, t_hi) / K in 2n real
+// slots; slot-to-coefficient's rotation by n and addition folds i F(t_hi) onto F(t_lo).  The split needs three non-empty
+// parts, so logn >= 3 (logn 1, 2 leave a part of 0 bits; logn 0 is the reference's separate multiply_vector branch, not
+// provided).  tests/cpp_sparse/test_sparse_setup.cpp pins these sets to the definition like the full ones.
 // The reference's own constants cannot be produced here (its Bootstrapper needs NTL), so nothing compares the arrays
 // with its output ("parity unpinned"); they are pinned to the definition instead: tests/cpp/test_bootstrap_setup.cpp
 // checks F P = U against the O(n^2) sum, F^-1 F = identity / (2 K), and the GPU tests that a bootstrapped ciphertext
@@ -35,6 +50,7 @@
 #include <cstddef>
 #include <map>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 namespace moai_boot
@@ -69,6 +85,11 @@ namespace moai_boot
         std::size_t diagonal_count() const
         {
             return d_.size();
+        }
+        // offset (in [0, n)) -> diagonal
+        const std::map<int, std::vector<cplx>> &diagonals() const
+        {
+            return d_;
         }
         // this <- S * this (S acts after this)
         void apply_left(const DiagonalMatrix &S)
@@ -277,6 +298,116 @@ namespace moai_boot
             s.totlen[i] = (1 << s.part[i]) - 1;
         }
         return s;
+    }
+
+    // centred layout with true offsets (see the header): index i holds offset o = (i - totlen) * basicstep, row k taking
+    // the entry of M's diagonal o mod n only where 0 <= k + o < n
+    inline DiagonalSet sparse_centred_layout(const DiagonalMatrix &M, int totlen, int basicstep)
+    {
+        const int n = M.n();
+        if (static_cast<long>(totlen) * basicstep >= n)
+        {
+            throw std::logic_error("sparse centred layout needs totlen * basicstep < n");
+        }
+        // every non-zero entry must land in the layout: its true offset a multiple of basicstep within +-totlen of it
+        for (const auto &kv : M.diagonals())
+        {
+            for (int k = 0; k < n; k++)
+            {
+                const cplx &z = kv.second[static_cast<std::size_t>(k)];
+                if (z.real() == 0.0 && z.imag() == 0.0)
+                {
+                    continue;
+                }
+                const int o = k + kv.first < n ? kv.first : kv.first - n;
+                if (o % basicstep != 0 || o / basicstep > totlen || o / basicstep < -totlen)
+                {
+                    throw std::logic_error("merged transform has diagonals outside its layout");
+                }
+            }
+        }
+        DiagonalSet out(static_cast<std::size_t>(2 * totlen + 1), std::vector<cplx>(static_cast<std::size_t>(n), cplx(0.0, 0.0)));
+        for (int i = 0; i <= 2 * totlen; i++)
+        {
+            const int o = (i - totlen) * basicstep;
+            if (const auto *d = M.find(o))
+            {
+                for (int k = 0; k < n; k++)
+                {
+                    if (k + o >= 0 && k + o < n)
+                    {
+                        out[static_cast<std::size_t>(i)][static_cast<std::size_t>(k)] = (*d)[static_cast<std::size_t>(k)];
+                    }
+                }
+            }
+        }
+        return out;
+    }
+    // every diagonal to length 2n: the second half is factor * the first
+    inline void double_length(DiagonalSet &set, cplx factor)
+    {
+        for (auto &d : set)
+        {
+            const std::size_t n = d.size();
+            d.resize(2 * n);
+            for (std::size_t k = 0; k < n; k++)
+            {
+                d[n + k] = factor * d[k];
+            }
+        }
+    }
+
+    // why a sparse logn has no level-3 bootstrapping (nullptr: it has one)
+    inline const char *sparse_unsupported_reason(int logn, int logNh)
+    {
+        if (logn >= logNh)
+        {
+            return "not a sparse slot count (logn >= logNh)";
+        }
+        if (logn == 0)
+        {
+            return "logn == 0 (the reference's multiply_vector / conjugate / rotate-by-1 branch) is not provided";
+        }
+        if (logn < 3)
+        {
+            return "the level-3 split of logn < 3 leaves a part of 0 bits";
+        }
+        return nullptr;
+    }
+
+    // the six sets of the sparse-slot (3 <= logn < logNh) level-3 bootstrapping, layout in the header
+    inline LevelThreeDiagonals level_three_sparse_diagonals(int logn, int logNh, long boundary_K)
+    {
+        if (const char *why = sparse_unsupported_reason(logn, logNh))
+        {
+            throw std::invalid_argument(std::string("sparse level-3 diagonals: ") + why);
+        }
+        LevelThreeDiagonals out;
+        {
+            const LevelThreeSplit f = forward_split(logn);
+            DiagonalMatrix g1 = merge_stages(logn, 0, f.part[0], special_fft_stage);
+            DiagonalMatrix g2 = merge_stages(logn, f.part[0], f.part[1], special_fft_stage);
+            DiagonalMatrix g3 = merge_stages(logn, f.part[0] + f.part[1], f.part[2], special_fft_stage);
+            out.fftcoeff1 = sparse_centred_layout(g1, f.totlen[0], f.basicstep[0]);
+            out.fftcoeff2 = sparse_centred_layout(g2, f.totlen[1], f.basicstep[1]);
+            out.fftcoeff3 = sparse_centred_layout(g3, f.totlen[2], f.basicstep[2]);
+            double_length(out.fftcoeff1, cplx(1.0, 0.0));
+            double_length(out.fftcoeff2, cplx(1.0, 0.0));
+            double_length(out.fftcoeff3, cplx(0.0, 1.0)); // :1409-1412
+        }
+        {
+            const LevelThreeSplit v = inverse_split(logn);
+            DiagonalMatrix g1 = merge_stages(logn, 0, v.part[0], special_ifft_stage);
+            DiagonalMatrix g2 = merge_stages(logn, v.part[0], v.part[1], special_ifft_stage);
+            DiagonalMatrix g3 = merge_stages(logn, v.part[0] + v.part[1], v.part[2], special_ifft_stage);
+            g1.scale(1.0 / (boundary_K * (1L << (logNh - logn)))); // :1804-1807
+            g3.scale(0.5);                                         // :1809-1814
+            out.invfftcoeff1 = rotated_layout(g1, v.totlen[0], v.basicstep[0]);
+            out.invfftcoeff2 = sparse_centred_layout(g2, v.totlen[1], v.basicstep[1]);
+            out.invfftcoeff3 = sparse_centred_layout(g3, v.totlen[2], v.basicstep[2]);
+            double_length(out.invfftcoeff3, cplx(0.0, -1.0)); // :1812
+        }
+        return out;
     }
 
     inline LevelThreeDiagonals level_three_diagonals(int logn, long boundary_K)

@@ -622,6 +622,31 @@ namespace moai_fused
         std::vector<std::vector<std::complex<double>>> fftcoeff1, fftcoeff2, fftcoeff3;          // slot-to-coefficient
     };
 
+    // Bootstrapper::modraise_inplace (:2938-2992) on a packed ciphertext; it must sit at the lowest level
+    inline void modraise_packed(const seal::SEALContext &context, const seal::Evaluator &evaluator, seal::Ciphertext &cipher)
+    {
+        using namespace seal;
+        if (cipher.size() != 2)
+        {
+            throw std::invalid_argument("Ciphertexts of size 2 are supported only!");
+        }
+        if (cipher.coeff_modulus_size() != 1)
+        {
+            throw std::invalid_argument("Ciphertexts in the lowest level are supported only!");
+        }
+        if (!cipher.is_ntt_form())
+        {
+            evaluator.transform_to_ntt_inplace(cipher); // moai_modraise reads NTT form; the round trip is exact
+        }
+        Ciphertext raised;
+        raised.resize_batch(context, context.first_parms_id(), 2, cipher.batch());
+        util::hip_check(moai_modraise(context.device(), cipher.device_data(), raised.device_data(), raised.coeff_modulus_size(),
+                                      cipher.batch(), context.stream()));
+        raised.is_ntt_form() = true;
+        raised.scale() = cipher.scale();
+        cipher = std::move(raised);
+    }
+
     // Bootstrapper::bootstrap_3 for logn == logNh (bootstrap_full_3) on packed ciphertexts.  Like the reference's
     // Bootstrapper it keeps references to the encoder, evaluator and keys: they must outlive it.
     class PackedBootstrapper3
@@ -660,26 +685,7 @@ namespace moai_fused
         // :2938-2992; the ciphertext must sit at the lowest level
         void modraise_inplace(seal::Ciphertext &cipher) const
         {
-            using namespace seal;
-            if (cipher.size() != 2)
-            {
-                throw std::invalid_argument("Ciphertexts of size 2 are supported only!");
-            }
-            if (cipher.coeff_modulus_size() != 1)
-            {
-                throw std::invalid_argument("Ciphertexts in the lowest level are supported only!");
-            }
-            if (!cipher.is_ntt_form())
-            {
-                evaluator_.transform_to_ntt_inplace(cipher); // moai_modraise reads NTT form; the round trip is exact
-            }
-            Ciphertext raised;
-            raised.resize_batch(context_, context_.first_parms_id(), 2, cipher.batch());
-            util::hip_check(moai_modraise(context_.device(), cipher.device_data(), raised.device_data(), raised.coeff_modulus_size(),
-                                          cipher.batch(), context_.stream()));
-            raised.is_ntt_form() = true;
-            raised.scale() = cipher.scale();
-            cipher = std::move(raised);
+            modraise_packed(context_, evaluator_, cipher);
         }
 
         // :2602-2623
@@ -693,6 +699,7 @@ namespace moai_fused
             inv_[2]->apply(tmpct2, rtncipher, gal_keys_);
             evaluator_.rescale_to_next_inplace(rtncipher);
         }
+
 
         // :2460-2497
         void sfl_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
@@ -814,6 +821,194 @@ namespace moai_fused
         ModularReducer3 mod_reducer_;
         std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
         int fwd_totlen2_ = 0, fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
+        std::map<std::tuple<double, double, double>, std::unique_ptr<BsgsLinearTransform>> fwd3_;
+    };
+    // Bootstrapper::bootstrap_3 for 3 <= logn < logNh (bootstrap_sparse_3, :3143-3229) on packed ciphertexts, with the
+    // sparse diagonal sets of bootstrapping/moai_fft_diagonals.h (2n-entry diagonals replicated to N/2 slots by
+    // BsgsLinearTransform).  The reference marks these routines "not yet"; its op sequence is followed call for call:
+    //   modraise; scale = q_0; sub-sum (rotate by 2^i, add_inplace, i = logn .. logNh-1, at the top level);
+    //   coefftoslot_3 (:2721-2726) = sflinv_3 (:2579-2600) + complex_conjugate + add_reduced_error;
+    //   ONE modular_reduction; slottocoeff_3 (:2728-2733) = sfl_3 (:2419-2458) + rotate_vector(n) + add_reduced_error;
+    //   scale = final_scale.
+    // Keys: the sub-sum's steps 2^i and the rotation by n are powers of two, which addBootKeys_3 (:374-392) lists; the
+    // transforms' steps come from addLeftRotKeys_Linear_to_vector_3 (boot_rotation_steps_3); a step without its own key
+    // is composed from power-of-two keys as rotate_vector does.
+    class PackedSparseBootstrapper3
+    {
+    public:
+        PackedSparseBootstrapper3(const seal::SEALContext &context, const seal::CKKSEncoder &encoder, const seal::Evaluator &evaluator,
+                                  const seal::RelinKeys &relin_keys, const seal::GaloisKeys &gal_keys, int logn, int logNh,
+                                  double final_scale, const BootDiagonals3 &diagonals, const ModularReducer3 &mod_reducer)
+            : context_(context), encoder_(encoder), evaluator_(evaluator), relin_keys_(relin_keys), gal_keys_(gal_keys), logn_(logn),
+              logNh_(logNh), Nh_(1 << logNh), n_(1 << logn), final_scale_(final_scale), fftcoeff3_(diagonals.fftcoeff3),
+              mod_reducer_(mod_reducer)
+        {
+            if (logn >= logNh || logn < 3)
+            {
+                throw std::invalid_argument("bootstrap_sparse_3 needs 3 <= logn < logNh");
+            }
+            // sflinv_3's split, :2580-2590; the third transform reads 2n-entry diagonals (coeff_logn = logn + 1)
+            {
+                int p1 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p1) / 2.0));
+                int p3 = logn - p1 - p2;
+                inv_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1 << (logn - p1), logn, diagonals.invfftcoeff1, true));
+                inv_[1].reset(new BsgsLinearTransform(context, Nh_, (1 << p2) - 1, 1 << (logn - p1 - p2), logn, diagonals.invfftcoeff2, false));
+                inv_[2].reset(new BsgsLinearTransform(context, Nh_, (1 << p3) - 1, 1, logn + 1, diagonals.invfftcoeff3, false));
+            }
+            // sfl_3's split, :2420-2430; all three transforms centred on 2n-entry diagonals
+            {
+                int p3 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p3) / 2.0));
+                int p1 = logn - p3 - p2;
+                fwd_totlen3_ = (1 << p3) - 1;
+                fwd_basicstep3_ = 1 << (p1 + p2);
+                fwd_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1, logn + 1, diagonals.fftcoeff1, false));
+                fwd_[1].reset(new BsgsLinearTransform(context, Nh_, (1 << p2) - 1, 1 << p1, logn + 1, diagonals.fftcoeff2, false));
+            }
+            if (fftcoeff3_.size() != static_cast<std::size_t>(2 * fwd_totlen3_ + 1))
+            {
+                throw std::invalid_argument("fftcoeff3 of a sparse slot count has 2 totlen3 + 1 diagonals");
+            }
+        }
+
+        int logn() const
+        {
+            return logn_;
+        }
+
+        void modraise_inplace(seal::Ciphertext &cipher) const
+        {
+            modraise_packed(context_, evaluator_, cipher);
+        }
+
+        // :3158-3163: cipher += rotate_vector(cipher, 2^i), i = logn .. logNh - 1.  A step with its own key is one key switch
+        // whose last kernel adds into the running sum (moai_apply_galois_acc: the residues of rotate + add_inplace); a step
+        // without one goes through the evaluator.
+        void subsum_inplace(seal::Ciphertext &cipher) const
+        {
+            using namespace seal;
+            if (cipher.size() != 2 || !cipher.is_ntt_form())
+            {
+                throw std::invalid_argument("encrypted must be a size-2 ciphertext in NTT form");
+            }
+            const std::size_t L = cipher.coeff_modulus_size(), B = cipher.batch();
+            const std::size_t words = B * 2 * L * context_.n();
+            void *st = context_.stream();
+            util::DeviceArray src(words, st);
+            std::vector<std::uint32_t> seq;
+            for (int i = logn_; i < logNh_; i++)
+            {
+                seq.clear();
+                detail::rotation_sequence(context_, gal_keys_, 1 << i, seq);
+                if (seq.size() == 1)
+                {
+                    util::hip_check(moai_memcpy_d2d(src.get(), cipher.device_data(), words * 8, st));
+                    util::hip_check(moai_apply_galois_acc(context_.device(), src.get(), cipher.device_data(), L, seq[0],
+                                                          gal_keys_.device_key(GaloisKeys::get_index(seq[0]), L), B, st));
+                }
+                else
+                {
+                    Ciphertext rot;
+                    evaluator_.rotate_vector(cipher, 1 << i, gal_keys_, rot);
+                    evaluator_.add_inplace(cipher, rot);
+                }
+            }
+            context_.sync(); // the staging copy goes out of scope
+        }
+
+        // :2579-2600
+        void sflinv_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            seal::Ciphertext tmpct, tmpct2;
+            inv_[0]->apply(cipher, tmpct, gal_keys_);
+            evaluator_.rescale_to_next_inplace(tmpct);
+            inv_[1]->apply(tmpct, tmpct2, gal_keys_);
+            evaluator_.rescale_to_next_inplace(tmpct2);
+            inv_[2]->apply(tmpct2, rtncipher, gal_keys_);
+            evaluator_.rescale_to_next_inplace(rtncipher);
+        }
+
+        // :2419-2458; the third set is scaled by the running scale and kept per factor, as in sfl_full_3
+        void sfl_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            Ciphertext tmpct, tmpct2;
+            fwd_[0]->apply(cipher, tmpct, gal_keys_);
+            evaluator_.rescale_to_next_inplace(tmpct);
+            fwd_[1]->apply(tmpct, tmpct2, gal_keys_);
+            evaluator_.rescale_to_next_inplace(tmpct2);
+
+            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
+            auto curr_level = context_.get_context_data(tmpct2.parms_id())->chain_index();
+            double mod_zero = static_cast<double>(modulus[0].value());
+            double curr_mod = static_cast<double>(modulus[curr_level].value());
+            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_);
+            auto it = fwd3_.find(key);
+            if (it == fwd3_.end())
+            {
+                std::vector<std::vector<std::complex<double>>> scaled(fftcoeff3_.size());
+                for (std::size_t i = 0; i < fftcoeff3_.size(); i++)
+                {
+                    scaled[i].resize(static_cast<std::size_t>(2 * n_));
+                    for (std::size_t j = 0; j < static_cast<std::size_t>(2 * n_); j++)
+                    {
+                        scaled[i][j] = fftcoeff3_[i].at(j) * curr_mod * mod_zero * final_scale_ / (tmpct2.scale() * tmpct2.scale() * initial_scale_);
+                    }
+                }
+                it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(context_, Nh_, fwd_totlen3_, fwd_basicstep3_,
+                                                                                                    logn_ + 1, scaled, false)))
+                         .first;
+            }
+            it->second->apply(tmpct2, rtncipher, gal_keys_);
+            evaluator_.rescale_to_next_inplace(rtncipher);
+        }
+
+        // :2721-2726
+        void coefftoslot_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            seal::Ciphertext tmpct1, tmpct2;
+            sflinv_3(tmpct1, cipher);
+            evaluator_.complex_conjugate(tmpct1, gal_keys_, tmpct2);
+            evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
+        }
+
+        // :2728-2733
+        void slottocoeff_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            seal::Ciphertext tmpct1, tmpct2;
+            sfl_3(tmpct1, cipher);
+            evaluator_.rotate_vector(tmpct1, n_, gal_keys_, tmpct2);
+            evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
+        }
+
+        // bootstrap_3 (:3496-3502) -> bootstrap_sparse_3 (:3143-3229) for logn > 0; `cipher` is consumed like the reference's
+        void bootstrap_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            initial_scale_ = cipher.scale();
+            modraise_inplace(cipher);
+            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
+            cipher.scale() = static_cast<double>(modulus[0].value());
+            subsum_inplace(cipher);
+            Ciphertext rtn;
+            coefftoslot_3(rtn, cipher);
+            Ciphertext modrtn;
+            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn, rtn);
+            slottocoeff_3(rtncipher, modrtn);
+            rtncipher.scale() = final_scale_;
+        }
+
+    private:
+        seal::SEALContext context_;
+        const seal::CKKSEncoder &encoder_;
+        const seal::Evaluator &evaluator_;
+        const seal::RelinKeys &relin_keys_;
+        const seal::GaloisKeys &gal_keys_;
+        int logn_, logNh_, Nh_, n_;
+        double final_scale_, initial_scale_ = 1;
+        std::vector<std::vector<std::complex<double>>> fftcoeff3_; // rescaled per running scale in sfl_3
+        ModularReducer3 mod_reducer_;
+        std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
+        int fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
         std::map<std::tuple<double, double, double>, std::unique_ptr<BsgsLinearTransform>> fwd3_;
     };
 } // namespace moai_fused

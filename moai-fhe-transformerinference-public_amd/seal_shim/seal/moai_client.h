@@ -277,11 +277,27 @@ namespace seal
         CKKSEncoder(const SEALContext &context) : context_(context)
         {
             slots_ = context_.n() >> 1;
+            // ckks.cpp:29-30 (0 = all slots)
+            sparse_slots_ = context_.first_context_data()->parms().sparse_slots();
+            if (sparse_slots_ == 0)
+            {
+                sparse_slots_ = slots_;
+            }
         }
 
         std::size_t slot_count() const noexcept
         {
             return slots_;
+        }
+        // ckks.h:446-450; decode returns this many values.  The device decoder refuses a count that is not a power of two
+        // in [1, N/2].
+        void set_sparse_slots(std::size_t sparse_slots)
+        {
+            sparse_slots_ = sparse_slots;
+        }
+        std::size_t sparse_slot_count() const noexcept
+        {
+            return sparse_slots_;
         }
 
         // ---- vector encodes (SEAL/ckks.h:457-637) -------------------------------------------------
@@ -327,7 +343,8 @@ namespace seal
             encode(value, context_.first_parms_id(), destination);
         }
 
-        // ---- decode (SEAL/ckks.h:644-760): moai_ckks_decode, then N/2 values to the host -------------------
+        // ---- decode (SEAL/ckks.h:644-760): moai_ckks_decode, then N/2 values to the host; with sparse slots set
+        // (sparse_slots_ != slots_, ckks.h:703-713) moai_ckks_decode_sparse and sparse_slots_ values -----------------
         template <typename T>
         void decode(const Plaintext &plain, std::vector<T> &destination, MemoryPoolHandle = MemoryPoolHandle()) const
         {
@@ -363,12 +380,21 @@ namespace seal
                 src = plain.device_data(); // materialises a masked plaintext
             }
             constexpr bool cplx = std::is_same<T, std::complex<double>>::value;
-            util::DeviceArray out(slots_ * (cplx ? 2 : 1), st);
+            const std::size_t count = sparse_slots_;
+            util::DeviceArray out((count ? count : 1) * (cplx ? 2 : 1), st);
             const double scale = plain.scale();
-            util::hip_check(moai_ckks_decode(context_.device(), src, 1, L, nullptr, &scale, cplx ? 1 : 0,
-                                             reinterpret_cast<double *>(out.get()), st));
-            destination.resize(slots_);
-            util::hip_check(moai_memcpy_d2h(destination.data(), out.get(), slots_ * sizeof(T), st));
+            if (count == slots_)
+            {
+                util::hip_check(moai_ckks_decode(context_.device(), src, 1, L, nullptr, &scale, cplx ? 1 : 0,
+                                                 reinterpret_cast<double *>(out.get()), st));
+            }
+            else
+            {
+                util::hip_check(moai_ckks_decode_sparse(context_.device(), src, 1, L, nullptr, &scale, count, cplx ? 1 : 0,
+                                                        reinterpret_cast<double *>(out.get()), st));
+            }
+            destination.resize(count);
+            util::hip_check(moai_memcpy_d2h(destination.data(), out.get(), count * sizeof(T), st));
             context_.sync();
         }
 
@@ -643,6 +669,7 @@ namespace seal
     private:
         SEALContext context_;
         std::size_t slots_ = 0;
+        std::size_t sparse_slots_ = 0;
     };
 
     // =================================================================================================

@@ -87,7 +87,8 @@ namespace moai_fused
                       "decode to double or std::complex<double>");
         constexpr bool cplx = std::is_same<T, std::complex<double>>::value;
         const SEALContext &context = decryptor.context();
-        const std::size_t n = context.n(), slots = encoder.slot_count();
+        // the encoder's sparse slot count decides what decode returns (CKKSEncoder::decode)
+        const std::size_t n = context.n(), slots = encoder.sparse_slot_count(), full_slots = encoder.slot_count();
         void *st = context.stream();
         struct Member
         {
@@ -150,8 +151,16 @@ namespace moai_fused
                 {
                     scales[i] = m[m0 + i].scale;
                 }
-                util::hip_check(moai_ckks_decode(context.device(), plain.get(), nb, L, nullptr, scales.data(), cplx ? 1 : 0,
-                                                 reinterpret_cast<double *>(dout.get()), st));
+                if (slots == full_slots)
+                {
+                    util::hip_check(moai_ckks_decode(context.device(), plain.get(), nb, L, nullptr, scales.data(), cplx ? 1 : 0,
+                                                     reinterpret_cast<double *>(dout.get()), st));
+                }
+                else
+                {
+                    util::hip_check(moai_ckks_decode_sparse(context.device(), plain.get(), nb, L, nullptr, scales.data(), slots,
+                                                            cplx ? 1 : 0, reinterpret_cast<double *>(dout.get()), st));
+                }
                 host.resize(nb * slots * per_value);
                 util::hip_check(moai_memcpy_d2h(host.data(), dout.get(), host.size() * 8, st));
                 context.sync();
