@@ -131,6 +131,23 @@ int moai_mul_scalar_rows(moai_ctx *ctx, const uint64_t *a, const uint64_t *scala
  * touches polynomial 0 only: Evaluator::add_plain_inplace SEAL/evaluator.cpp:2014-2018). */
 int moai_add_scalar_rows(moai_ctx *ctx, const uint64_t *a, const uint64_t *scalars, uint64_t *out, size_t n_poly,
                          size_t L, void *stream);
+/* Multiplication by the monomial X^(N/2), which is the slot-wise constant i of a CKKS ciphertext, on rows in NTT form:
+ *     out = a + sign * X^(N/2) * b,  sign = +1 or -1;  a == NULL gives the plain product.  out may alias a or b.
+ * The product is negacyclic_multiply_poly_mono_coeffmod (SEAL/util/polyarithsmallmod.h:634-655) composed with
+ * ntt_negacyclic_harvey (SEAL/util/ntt.cpp:408-437): in the transform's output order X^(N/2) is +psi^(N/2) on indices
+ * [0, N/2) and -psi^(N/2) on [N/2, N), so no plaintext is encoded or read.  With a given it is the `multiply_plain` by the
+ * encoded constant i followed by `add` of include/source/bootstrapping/Bootstrapper.cpp:2760-2777.  Canonical residues in and
+ * out, primes of at most 61 bits. */
+int moai_mul_i_add(moai_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n_poly, size_t L, int sign,
+                   void *stream);
+/* Real and imaginary part of a ciphertext r given its conjugate rbar (both [n_poly][L][N], NTT form), up to the factor 2:
+ *     out_re = r + rbar,   out_im = -X^(N/2) * (r - rbar)
+ * in one pass: the `add_inplace_reduced_error(rtn, conj)` that ends bootstrap_full_real_3
+ * (include/source/bootstrapping/Bootstrapper.cpp:3347-3350; Evaluator::add_inplace SEAL/evaluator.cpp:155-240) and its
+ * counterpart for the imaginary part (sub_poly_coeffmod, SEAL/util/polyarithsmallmod.cpp:88-133, then the monomial product
+ * above).  out_re may alias r and out_im may alias rbar; no other overlap. */
+int moai_real_split(moai_ctx *ctx, const uint64_t *r, const uint64_t *rbar, uint64_t *out_re, uint64_t *out_im, size_t n_poly,
+                    size_t L, void *stream);
 
 /* out = base + sum_{t < terms} x[t] (*) scalars[t]   -- the accumulation chain of MOAI's column-packed ct x pt product
  * (include/source/matrix_mul/Ct_pt_matrix_mul.hpp:19-42: Evaluator::multiply_plain by a scalar-encoded plaintext,

@@ -75,6 +75,102 @@ __global__ __launch_bounds__(256) void ew_kernel(EwArgs g)
     }
 }
 
+// Multiplication by the monomial X^(N/2) in NTT form.  The forward transform of X^(N/2) under prime q, in the
+// bit-reversed order ntt_negacyclic_harvey leaves (SEAL/util/ntt.cpp:408-437), is psi^((2 bitrev(j) + 1) N/2) =
+// I_q (-1)^bitrev(j) with I_q = psi^(N/2), I_q^2 = -1: +I_q on indices [0, N/2) and -I_q on [N/2, N).  So the
+// product negacyclic_multiply_poly_mono_coeffmod computes in coefficient form (SEAL/util/polyarithsmallmod.h:634-655)
+// is here one Shoup product by a wave-uniform constant and a sign that depends on the half of the row only: a
+// workgroup's 256-chunk segment lies in one half whenever N/4 >= 256, smaller rows decide per lane.
+struct MonoArgs
+{
+    const uint64_t *a;   // mul_i_add: the addend or nullptr;  real_split: r
+    const uint64_t *b;   // mul_i_add: the factor;             real_split: rbar
+    uint64_t *out;       // mul_i_add: the result;             real_split: out_re
+    uint64_t *out2;      //                                    real_split: out_im
+    const PrimeConst *pc;
+    uint32_t L;
+    uint32_t n2;
+    uint32_t negative;   // mul_i_add: sign == -1
+    Tw iq[MOAI_MAX_RNS]; // per row: I_q = psi^(N/2) (+ Shoup quotient)
+};
+
+// x * (neg ? -I_q : +I_q), canonical.  The Shoup product takes any 64-bit x and is exact for every prime the context accepts
+// (20 .. 61 bits), as in scalar_rows_kernel: no sub-2^52 assumption.
+__device__ __forceinline__ uint64_t mul_iq(uint64_t x, const Tw &s, uint64_t q, bool neg)
+{
+    const uint64_t r = csub(mul_shoup_lazy(x, s.w, s.wq, q), q);
+    return neg && r ? q - r : r;
+}
+
+// out = a + sign X^(N/2) b   (HAS_A = false: out = sign X^(N/2) b)
+template <bool HAS_A>
+__global__ __launch_bounds__(256) void mul_i_add_kernel(MonoArgs g)
+{
+    const uint32_t row = blockIdx.y;
+    const uint32_t prime = row % g.L;
+    const uint64_t q = g.pc[prime].q;
+    const Tw s = g.iq[prime];
+    const uint32_t half = g.n2 >> 1;
+    const bool by_segment = half >= 256u; // uniform: `half` is a power of two
+    const ulonglong2 *a2 = HAS_A ? reinterpret_cast<const ulonglong2 *>(g.a) + (size_t)row * g.n2 : nullptr;
+    const ulonglong2 *b2 = reinterpret_cast<const ulonglong2 *>(g.b) + (size_t)row * g.n2;
+    ulonglong2 *o2 = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)row * g.n2;
+    for (uint32_t seg = blockIdx.x * 256u; seg < g.n2; seg += gridDim.x * 256u)
+    {
+        const uint32_t i = seg + threadIdx.x;
+        if (i >= g.n2)
+        {
+            break;
+        }
+        const bool neg = ((by_segment ? seg : i) >= half) != (g.negative != 0);
+        const ulonglong2 y = b2[i];
+        ulonglong2 r;
+        r.x = mul_iq(y.x, s, q, neg);
+        r.y = mul_iq(y.y, s, q, neg);
+        if (HAS_A)
+        {
+            const ulonglong2 x = a2[i];
+            r.x = csub(x.x + r.x, q);
+            r.y = csub(x.y + r.y, q);
+        }
+        o2[i] = r;
+    }
+}
+
+// out = r + rbar,  out2 = -X^(N/2) (r - rbar): both read before either is written, so out may be r and out2 may be rbar
+__global__ __launch_bounds__(256) void real_split_kernel(MonoArgs g)
+{
+    const uint32_t row = blockIdx.y;
+    const uint32_t prime = row % g.L;
+    const uint64_t q = g.pc[prime].q;
+    const Tw s = g.iq[prime];
+    const uint32_t half = g.n2 >> 1;
+    const bool by_segment = half >= 256u;
+    const ulonglong2 *a2 = reinterpret_cast<const ulonglong2 *>(g.a) + (size_t)row * g.n2;
+    const ulonglong2 *b2 = reinterpret_cast<const ulonglong2 *>(g.b) + (size_t)row * g.n2;
+    ulonglong2 *re2 = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)row * g.n2;
+    ulonglong2 *im2 = reinterpret_cast<ulonglong2 *>(g.out2) + (size_t)row * g.n2;
+    for (uint32_t seg = blockIdx.x * 256u; seg < g.n2; seg += gridDim.x * 256u)
+    {
+        const uint32_t i = seg + threadIdx.x;
+        if (i >= g.n2)
+        {
+            break;
+        }
+        const bool neg = (by_segment ? seg : i) < half; // the factor is -X^(N/2): -I_q on the lower half
+        const ulonglong2 x = a2[i], y = b2[i];
+        ulonglong2 sum, d;
+        sum.x = csub(x.x + y.x, q);
+        sum.y = csub(x.y + y.y, q);
+        d.x = x.x >= y.x ? x.x - y.x : x.x + q - y.x;
+        d.y = x.y >= y.y ? x.y - y.y : x.y + q - y.y;
+        d.x = mul_iq(d.x, s, q, neg);
+        d.y = mul_iq(d.y, s, q, neg);
+        re2[i] = sum;
+        im2[i] = d;
+    }
+}
+
 struct ScalarArgs
 {
     const uint64_t *a;
@@ -1275,6 +1371,113 @@ extern "C" int moai_add_scalar_rows(moai_ctx *c, const uint64_t *a, const uint64
     MOAI_AUDIT(stream, a, scalars, out);
     trace_op("add_scalar_rows", L, n_poly);
     return scalar_rows(c, a, scalars, out, n_poly, L, stream, false);
+}
+
+// I_q = psi^(N/2) per row with its Shoup quotient, from the context's root table (NTTTables::get_root)
+static void mono_constants(const moai_ctx *c, size_t L, Tw *iq)
+{
+    for (size_t r = 0; r < L; r++)
+    {
+        const uint64_t q = c->primes[r];
+        unsigned __int128 w = c->roots[r] % q;
+        for (int s = 0; s + 1 < c->logn; s++) // psi^(2^(logn-1))
+        {
+            w = (w * w) % q;
+        }
+        iq[r].w = (uint64_t)w;
+        iq[r].wq = (uint64_t)((w << 64) / q);
+    }
+}
+
+extern "C" int moai_mul_i_add(moai_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n_poly, size_t L,
+                              int sign, void *stream)
+{
+    MOAI_AUDIT(stream, a, b, out);
+    trace_op("mul_i_add", L, n_poly);
+    int rc = check_rows(c, n_poly, L);
+    if (rc)
+    {
+        return rc;
+    }
+    if (sign != 1 && sign != -1)
+    {
+        return set_error(MOAI_EINVAL, "sign must be +1 or -1");
+    }
+    if (c->logn < 2)
+    {
+        return set_error(MOAI_EINVAL, "mul_i_add needs N >= 4");
+    }
+    if (n_poly == 0 || L == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!b || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    MonoArgs g;
+    g.a = a;
+    g.b = b;
+    g.out = out;
+    g.out2 = nullptr;
+    g.pc = c->pc;
+    g.L = (uint32_t)L;
+    g.n2 = (uint32_t)(c->n >> 1);
+    g.negative = sign < 0 ? 1u : 0u;
+    mono_constants(c, L, g.iq);
+    MOAI_CHECK_GRID_ROWS(n_poly * L);
+    if (a)
+    {
+        hipLaunchKernelGGL(mul_i_add_kernel<true>, row_grid(c, n_poly * L), dim3(256), 0, (hipStream_t)stream, g);
+    }
+    else
+    {
+        hipLaunchKernelGGL(mul_i_add_kernel<false>, row_grid(c, n_poly * L), dim3(256), 0, (hipStream_t)stream, g);
+    }
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+extern "C" int moai_real_split(moai_ctx *c, const uint64_t *r, const uint64_t *rbar, uint64_t *out_re, uint64_t *out_im,
+                               size_t n_poly, size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, r, rbar, out_re, out_im);
+    trace_op("real_split", L, n_poly);
+    int rc = check_rows(c, n_poly, L);
+    if (rc)
+    {
+        return rc;
+    }
+    if (c->logn < 2)
+    {
+        return set_error(MOAI_EINVAL, "real_split needs N >= 4");
+    }
+    if (n_poly == 0 || L == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!r || !rbar || !out_re || !out_im)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    if (out_re == out_im || out_re == rbar || out_im == r)
+    {
+        return set_error(MOAI_EINVAL, "real_split: out_re may alias r and out_im may alias rbar, nothing else");
+    }
+    MonoArgs g;
+    g.a = r;
+    g.b = rbar;
+    g.out = out_re;
+    g.out2 = out_im;
+    g.pc = c->pc;
+    g.L = (uint32_t)L;
+    g.n2 = (uint32_t)(c->n >> 1);
+    g.negative = 0;
+    mono_constants(c, L, g.iq);
+    MOAI_CHECK_GRID_ROWS(n_poly * L);
+    hipLaunchKernelGGL(real_split_kernel, row_grid(c, n_poly * L), dim3(256), 0, (hipStream_t)stream, g);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
 }
 
 static int ct_mul(moai_ctx *c, const uint64_t *x, const uint64_t *y, uint64_t *out, size_t L, size_t batch, void *stream,

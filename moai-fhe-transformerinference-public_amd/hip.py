@@ -45,6 +45,8 @@ SYMBOLS = {
     "moai_dyadic_mul": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_mul_scalar_rows": (C.c_int, [vp, vp, u64p, vp, sz, sz, vp]),
     "moai_add_scalar_rows": (C.c_int, [vp, vp, u64p, vp, sz, sz, vp]),
+    "moai_mul_i_add": (C.c_int, [vp, vp, vp, vp, sz, sz, C.c_int, vp]),
+    "moai_real_split": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, vp]),
     "moai_ct_multiply": (C.c_int, [vp, vp, vp, vp, sz, sz, vp]),
     "moai_ct_square": (C.c_int, [vp, vp, vp, sz, sz, vp]),
     "moai_ct_multiply_general": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, sz, vp]),
@@ -260,6 +262,14 @@ class Context:
     def add_scalar_rows(self, a, scalars, out, n_poly, L, stream=None):
         s = (C.c_uint64 * L)(*[int(x) for x in scalars])
         _check(lib().moai_add_scalar_rows(self.h, _ptr(a), s, _ptr(out), n_poly, L, stream))
+
+    def mul_i_add(self, a, b, out, n_poly, L, sign=1, stream=None):
+        """out = a + sign * X^(N/2) * b on NTT-form rows (a may be None: the plain monomial product)"""
+        _check(lib().moai_mul_i_add(self.h, _ptr(a), _ptr(b), _ptr(out), n_poly, L, int(sign), stream))
+
+    def real_split(self, r, rbar, out_re, out_im, n_poly, L, stream=None):
+        """out_re = r + rbar, out_im = -X^(N/2) * (r - rbar)"""
+        _check(lib().moai_real_split(self.h, _ptr(r), _ptr(rbar), _ptr(out_re), _ptr(out_im), n_poly, L, stream))
 
     def ct_multiply(self, x, y, out, L, batch, stream=None):
         _check(lib().moai_ct_multiply(self.h, _ptr(x), _ptr(y), _ptr(out), L, batch, stream))

@@ -11,8 +11,13 @@
 //   bootstrap_3 / bootstrap_inplace_3 (:3496-3508), set_final_scale,
 //   and the sparse-slot family for 3 <= logn < logNh: the sparse branches of genfftcoeff_3 / geninvfftcoeff_3
 //   (:1298-1414, :1694-1817), bootstrap_sparse_3 (:3143-3229; sub-sum, coefftoslot_3, ONE modular reduction,
-//   slottocoeff_3).  slot_vec may hold several logn values; change_logn picks one.
-// Not provided: the two-level, one-depth, hoisting and "real" variants, which no MOAI driver calls, and the sparse
+//   slottocoeff_3).  slot_vec may hold several logn values; change_logn picks one;
+//   and the "real" variants of both: sfl_full_half_3 / sfl_half_3 (:2539-2577, :2499-2537), slottocoeff_full_half_3 /
+//   slottocoeff_half_3 (:2778-2795, :2735-2740), bootstrap_full_real_3 (:3328-3351), bootstrap_sparse_real_3 (:3253-3326),
+//   bootstrap_real_3 / bootstrap_inplace_real_3 (:3510-3522).
+// Added (no counterpart in the reference): bootstrap_real_pair_3 / bootstrap_real_many_3 and the opt-in `pair_real`, which
+// send TWO real-valued ciphertexts through one bootstrap as a + i b (see `pair_real` below for what the caller promises).
+// Not provided: the two-level, one-depth and hoisting variants, which no MOAI driver calls, and the sparse
 // logn = 0 (multiply_vector) branch and logn = 1, 2 (the level-3 split leaves a part of 0 bits); they throw.
 // Keys of a sparse caller: addBootKeys_3 lists every power of two below Nh, which covers the sub-sum's steps n 2^i and
 // slottocoeff_3's rotation by n; addLeftRotKeys_Linear_to_vector_3 (:89-184) lists neither, so a caller that builds
@@ -89,6 +94,22 @@ public:
 
     ModularReducer *mod_reducer;
 
+    // Opt-in (default false; true when MOAI_BOOT_PAIR_REAL=1 is in the environment at construction): the caller promises that
+    // EVERY ciphertext handed to bootstrap_3 / bootstrap_real_3 of this object encodes real values.  Gathered calls are then
+    // paired in queue order, each pair goes through ONE bootstrap as a + i b (bootstrap_real_pair_3), and an odd one out
+    // goes through the single real sequence.  What changes for the caller:
+    //  * a result depends on its partner: it is no longer bit-identical to a single call, only equal to it within the
+    //    bootstrap's accuracy (tests/cpp_real/test_bootstrap_real_pair.cpp prints single and paired errors side by side);
+    //  * the message the modular reduction sees is a + i b, |a + i b| <= sqrt(2) max(|a|, |b|): its sine approximation's
+    //    cubic error term grows accordingly and carries a little of b into a's result (DESIGN 5.0d has the table);
+    //  * an input that is NOT real leaks its imaginary part into its partner's result.
+    // Measured at N = 2^16 on MOAI's chain, full slots, real messages of magnitude 1.0 (tests/cpp_real/test_bootstrap_real_pair
+    // --full): max |error| 1.33e-5 and 1.38e-5 for the two members of a pair, against 1.16e-5 and 1.05e-5 for the same two
+    // ciphertexts through bootstrap_real_3 alone; at magnitude 0.02: 7.9e-6 / 1.03e-5 paired, 8.6e-6 / 7.7e-6 alone.  That
+    // -- an error of up to about 1.4e-5 at magnitude 1, up to 2.2 x the single call's -- is what a caller accepts by setting it.
+    // With the flag clear nothing about bootstrap_3 changes.
+    bool pair_real = false;
+
     Bootstrapper(long _loge, long _logn, long _logNh, long _L, double _final_scale, long _boundary_K, long _sin_cos_deg,
                  long _scale_factor, long _inverse_deg, SEALContext &_context, KeyGenerator &_keygen, CKKSEncoder &_encoder,
                  Encryptor &_encryptor, Decryptor &_decryptor, Evaluator &_evaluator, RelinKeys &_relin_keys, GaloisKeys &_gal_keys)
@@ -109,6 +130,8 @@ public:
         {
             max_pack_ = 1;
         }
+        e = std::getenv("MOAI_BOOT_PAIR_REAL");
+        pair_real = e && std::atol(e) == 1;
     }
     Bootstrapper(const Bootstrapper &) = delete;
     Bootstrapper &operator=(const Bootstrapper &) = delete;
@@ -207,6 +230,31 @@ public:
         e.initial_scale() = initial_scale;
         e.slottocoeff_full_3(rtncipher, cipher1, cipher2);
     }
+    void sfl_full_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        auto &e = engine();
+        e.initial_scale() = initial_scale;
+        e.sfl_full_half_3(rtncipher, cipher);
+    }
+    void slottocoeff_full_half_3(Ciphertext &rtncipher, Ciphertext &cipher1, Ciphertext &cipher2)
+    {
+        auto &e = engine();
+        e.initial_scale() = initial_scale;
+        e.slottocoeff_full_half_3(rtncipher, cipher1, cipher2);
+    }
+    // the sparse counterparts (3 <= logn < logNh)
+    void sfl_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        auto &e = sparse_engine(logn);
+        e.initial_scale() = initial_scale;
+        e.sfl_half_3(rtncipher, cipher);
+    }
+    void slottocoeff_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        auto &e = sparse_engine(logn);
+        e.initial_scale() = initial_scale;
+        e.slottocoeff_half_3(rtncipher, cipher);
+    }
     void modraise_inplace(Ciphertext &cipher)
     {
         engine().modraise_inplace(cipher);
@@ -246,13 +294,103 @@ public:
             }
             return;
         }
-        gather_and_run(rtncipher, cipher, ln);
+        gather_and_run(rtncipher, cipher, ln, pair_real ? KIND_PAIR : KIND_COMPLEX);
     }
     void bootstrap_inplace_3(Ciphertext &cipher)
     {
         Ciphertext rtncipher;
         bootstrap_3(rtncipher, cipher);
         cipher = rtncipher;
+    }
+
+    // ---- the real variants: the result encodes the real part of the message (:3328-3351, :3253-3326, :3510-3522) -------
+    void bootstrap_full_real_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        std::lock_guard<std::mutex> run(run_mu_);
+        engine().bootstrap_real_3(rtncipher, cipher);
+    }
+    void bootstrap_sparse_real_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        std::lock_guard<std::mutex> run(run_mu_);
+        sparse_engine(logn).bootstrap_real_3(rtncipher, cipher);
+    }
+    // concurrent callers are gathered like bootstrap_3's; real and complex requests never share a pack, and a gathered real
+    // call has the bits of a single real call (unless `pair_real` is set, see there)
+    void bootstrap_real_3(Ciphertext &rtncipher, Ciphertext &cipher)
+    {
+        initial_scale = cipher.scale(); // :3511
+        const long ln = logn;
+        if (ln != logNh)
+        {
+            check_sparse(ln);
+        }
+        if (cipher.batch() != 1 || combine_us_ <= 0 || max_pack_ == 1)
+        {
+            std::lock_guard<std::mutex> run(run_mu_);
+            boot_single(ln, KIND_REAL, rtncipher, cipher);
+            return;
+        }
+        gather_and_run(rtncipher, cipher, ln, pair_real ? KIND_PAIR : KIND_REAL);
+    }
+    void bootstrap_inplace_real_3(Ciphertext &cipher)
+    {
+        Ciphertext rtncipher;
+        bootstrap_real_3(rtncipher, cipher);
+        cipher = rtncipher;
+    }
+    // Two real-valued ciphertexts (single or packed alike, same level and scale) through ONE bootstrap; both inputs are
+    // consumed like bootstrap_3's.  Outputs at final_scale, on the level bootstrap_3 leaves.  See `pair_real` above for
+    // what pairing means for accuracy.
+    void bootstrap_real_pair_3(Ciphertext &rtn_a, Ciphertext &rtn_b, Ciphertext &a, Ciphertext &b)
+    {
+        initial_scale = a.scale();
+        const long ln = logn;
+        if (ln != logNh)
+        {
+            check_sparse(ln);
+        }
+        std::lock_guard<std::mutex> run(run_mu_);
+        boot_pair(ln, rtn_a, rtn_b, a, b);
+    }
+    // in[2j] is paired with in[2j + 1]; the pairs run in packs of at most MOAI_BOOT_MAX_PACK pairs, an odd last member goes
+    // through the single real sequence.  All inputs on one level, with one scale; they are consumed.
+    void bootstrap_real_many_3(vector<Ciphertext> &rtn, vector<Ciphertext> &in)
+    {
+        if (in.empty())
+        {
+            rtn.clear();
+            return;
+        }
+        initial_scale = in[0].scale();
+        const long ln = logn;
+        if (ln != logNh)
+        {
+            check_sparse(ln);
+        }
+        for (auto &c : in)
+        {
+            if (c.batch() != 1 || c.parms_id() != in[0].parms_id() || c.scale() != in[0].scale() || c.size() != in[0].size() ||
+                c.is_ntt_form() != in[0].is_ntt_form())
+            {
+                throw std::invalid_argument("bootstrap_real_many_3: single ciphertexts of one level, size, form and scale");
+            }
+        }
+        std::vector<Ciphertext *> ins, outs;
+        std::vector<Ciphertext> result(in.size());
+        for (std::size_t i = 0; i < in.size(); i++)
+        {
+            ins.push_back(&in[i]);
+            outs.push_back(&result[i]);
+        }
+        std::lock_guard<std::mutex> run(run_mu_);
+        for (std::size_t at = 0; at < in.size(); at += 2 * max_pack_)
+        {
+            const std::size_t cnt = std::min(in.size() - at, 2 * max_pack_);
+            run_paired(ln, ins.data() + at, outs.data() + at, cnt);
+            runs_++;
+            members_ += cnt;
+        }
+        rtn = std::move(result);
     }
     // calls waiting to be gathered into a pack (a caller that must know its call is queued, e.g. before change_logn)
     std::size_t gather_pending() const
@@ -276,10 +414,6 @@ public:
     {
         unsupported("bootstrap_inplace");
     }
-    void bootstrap_real_3(Ciphertext &, Ciphertext &)
-    {
-        unsupported("bootstrap_real_3");
-    }
     void bootstrap_hoisting(Ciphertext &, Ciphertext &)
     {
         unsupported("bootstrap_hoisting");
@@ -296,7 +430,7 @@ public:
 private:
     [[noreturn]] static void unsupported(const char *what)
     {
-        throw std::logic_error(std::string("Bootstrapper::") + what + " is not provided: only the level-3 full-slot family is");
+        throw std::logic_error(std::string("Bootstrapper::") + what + " is not provided: only the level-3 family (bootstrap_3, bootstrap_real_3 and what they call) is");
     }
     void select_slot_index()
     {
@@ -441,21 +575,92 @@ private:
         return *it->second;
     }
 
-    // ---- gathering of concurrent bootstrap_3 calls ------------------------------------------------------------------
+    // ---- one run on the engine of `ln` (caller holds run_mu_) ---------------------------------------------------------
+    enum Kind
+    {
+        KIND_COMPLEX, // bootstrap_3
+        KIND_REAL,    // bootstrap_real_3
+        KIND_PAIR     // either, with `pair_real` set: real by the caller's promise, paired two to a bootstrap
+    };
+    void boot_single(long ln, Kind kind, Ciphertext &out, Ciphertext &in)
+    {
+        if (ln == logNh)
+        {
+            kind == KIND_COMPLEX ? full_engine().bootstrap_3(out, in) : full_engine().bootstrap_real_3(out, in);
+        }
+        else
+        {
+            kind == KIND_COMPLEX ? sparse_engine(ln).bootstrap_3(out, in) : sparse_engine(ln).bootstrap_real_3(out, in);
+        }
+    }
+    void boot_pair(long ln, Ciphertext &out_a, Ciphertext &out_b, Ciphertext &a, Ciphertext &b)
+    {
+        if (ln == logNh)
+        {
+            full_engine().bootstrap_real_pair_3(out_a, out_b, a, b);
+        }
+        else
+        {
+            sparse_engine(ln).bootstrap_real_pair_3(out_a, out_b, a, b);
+        }
+    }
+    // in[2j] with in[2j + 1] as one packed paired run, an odd last member through the single real sequence
+    void run_paired(long ln, Ciphertext *const *in, Ciphertext *const *out, std::size_t count)
+    {
+        const std::size_t pairs = count / 2;
+        if (pairs == 1)
+        {
+            Ciphertext oa, ob;
+            boot_pair(ln, oa, ob, *in[0], *in[1]);
+            *out[0] = std::move(oa);
+            *out[1] = std::move(ob);
+        }
+        else if (pairs > 1)
+        {
+            std::vector<Ciphertext> first, second;
+            first.reserve(pairs);
+            second.reserve(pairs);
+            for (std::size_t j = 0; j < pairs; j++)
+            {
+                first.push_back(*in[2 * j]);
+                second.push_back(*in[2 * j + 1]);
+            }
+            Ciphertext pa = moai_fused::pack(first, context), pb = moai_fused::pack(second, context), oa, ob;
+            first.clear();
+            second.clear();
+            boot_pair(ln, oa, ob, pa, pb);
+            moai_fused::unpack(oa, context, first);
+            moai_fused::unpack(ob, context, second);
+            for (std::size_t j = 0; j < pairs; j++)
+            {
+                *out[2 * j] = std::move(first[j]);
+                *out[2 * j + 1] = std::move(second[j]);
+            }
+        }
+        if (count & 1)
+        {
+            Ciphertext o;
+            boot_single(ln, KIND_REAL, o, *in[count - 1]);
+            *out[count - 1] = std::move(o);
+        }
+    }
+
+    // ---- gathering of concurrent bootstrap_3 / bootstrap_real_3 calls ---------------------------------------------------
     struct Request
     {
         Ciphertext *out;
         Ciphertext *in;
         long logn; // the caller's logn: calls with different logn, or sparse and full ones, never share a pack
+        Kind kind; // nor do calls of different kinds
         bool done = false;
         std::exception_ptr error;
     };
     // Every caller queues its request; the caller at the head of the queue leads ONE packed run (its own request is part
     // of it), the others sleep until their request is done or they reach the head.  All waits end: a leader's wait for
     // company is bounded by the window, and a finished run always wakes the queue.
-    void gather_and_run(Ciphertext &rtncipher, Ciphertext &cipher, long ln)
+    void gather_and_run(Ciphertext &rtncipher, Ciphertext &cipher, long ln, Kind kind)
     {
-        Request me{ &rtncipher, &cipher, ln };
+        Request me{ &rtncipher, &cipher, ln, kind };
         std::unique_lock<std::mutex> lk(gather_mu_);
         pending_.push_back(&me);
         gather_cv_.notify_all();
@@ -469,7 +674,9 @@ private:
             leader_active_ = true;
             // wait for company: until the pack is full, nobody new arrived for a quarter of the window, or the window ends
             const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(combine_us_);
-            while (pending_.size() < max_pack_)
+            // with pairing a pack holds max_pack_ PAIRS
+            const std::size_t max_take = kind == KIND_PAIR ? 2 * max_pack_ : max_pack_;
+            while (pending_.size() < max_take)
             {
                 const std::size_t seen = pending_.size();
                 auto quiet = std::chrono::steady_clock::now() + std::chrono::microseconds(combine_us_ / 4 + 1);
@@ -483,7 +690,7 @@ private:
                     break;
                 }
             }
-            const std::size_t take = pending_.size() < max_pack_ ? pending_.size() : max_pack_;
+            const std::size_t take = pending_.size() < max_take ? pending_.size() : max_take;
             std::vector<Request *> batch(pending_.begin(), pending_.begin() + static_cast<std::ptrdiff_t>(take));
             pending_.erase(pending_.begin(), pending_.begin() + static_cast<std::ptrdiff_t>(take));
             lk.unlock();
@@ -516,7 +723,8 @@ private:
             std::rethrow_exception(me.error);
         }
     }
-    // members are grouped by (logn, level, scale); each group is one packed run
+    // members are grouped by (logn, kind, level, scale); each group is one packed run -- a KIND_PAIR group pairs its members in
+    // queue order first
     void run_batch(const std::vector<Request *> &batch)
     {
         std::vector<bool> used(batch.size(), false);
@@ -529,7 +737,7 @@ private:
             std::vector<std::size_t> group;
             for (std::size_t j = i; j < batch.size(); j++)
             {
-                if (!used[j] && batch[j]->logn == batch[i]->logn && batch[j]->in->parms_id() == batch[i]->in->parms_id() && batch[j]->in->scale() == batch[i]->in->scale() &&
+                if (!used[j] && batch[j]->logn == batch[i]->logn && batch[j]->kind == batch[i]->kind && batch[j]->in->parms_id() == batch[i]->in->parms_id() && batch[j]->in->scale() == batch[i]->in->scale() &&
                     batch[j]->in->size() == batch[i]->in->size() && batch[j]->in->is_ntt_form() == batch[i]->in->is_ntt_form())
                 {
                     group.push_back(j);
@@ -541,17 +749,23 @@ private:
             {
                 std::lock_guard<std::mutex> run(run_mu_);
                 const long ln = batch[i]->logn;
-                auto boot = [&](Ciphertext &out, Ciphertext &in) {
-                    if (ln == logNh)
+                const Kind kind = batch[i]->kind;
+                auto boot = [&](Ciphertext &out, Ciphertext &in) { boot_single(ln, kind == KIND_PAIR ? KIND_REAL : kind, out, in); };
+                if (kind == KIND_PAIR && group.size() > 1)
+                {
+                    // a group may exceed 2 max_pack_ only if a non-pairing leader took it: keep the packs bounded anyway
+                    std::vector<Ciphertext *> ins, outs;
+                    for (std::size_t j : group)
                     {
-                        full_engine().bootstrap_3(out, in);
+                        ins.push_back(batch[j]->in);
+                        outs.push_back(batch[j]->out);
                     }
-                    else
+                    for (std::size_t at = 0; at < ins.size(); at += 2 * max_pack_)
                     {
-                        sparse_engine(ln).bootstrap_3(out, in);
+                        run_paired(ln, ins.data() + at, outs.data() + at, std::min(ins.size() - at, 2 * max_pack_));
                     }
-                };
-                if (group.size() == 1)
+                }
+                else if (group.size() == 1)
                 {
                     boot(*batch[group[0]]->out, *batch[group[0]]->in);
                 }

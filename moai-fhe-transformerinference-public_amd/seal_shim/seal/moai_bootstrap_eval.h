@@ -7,6 +7,8 @@
 //   ::modraise_inplace                    :2938-2992   (moai_modraise)
 //   ::coefftoslot_full_3 / sflinv_full_3  :2742-2759, :2602-2623
 //   ::slottocoeff_full_3 / sfl_full_3     :2760-2777, :2460-2497
+//   ::slottocoeff_full_half_3 / sfl_full_half_3 :2778-2795, :2539-2577; ::bootstrap_full_real_3 :3328-3351
+//   ::slottocoeff_half_3 / sfl_half_3 :2735-2740, :2499-2537; ::bootstrap_sparse_real_3 :3253-3326
 //   ModularReducer::modular_reduction     ModularReducer.cpp:58-78 (the inverse_deg == 1 branch MOAI configures)
 //   Polynomial::generate_poly_heap        common/Polynomial.cpp:168-214, babycount common/func.cpp:120-142
 //   Polynomial::homomorphic_poly_evaluation   common/Polynomial.cpp:255-520
@@ -704,6 +706,17 @@ namespace moai_fused
         // :2460-2497
         void sfl_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
         {
+            sfl_full_impl(rtncipher, cipher, false);
+        }
+        // :2539-2577: sfl_full_3 with the third set's constants halved, for the real variants (the caller adds the conjugate)
+        void sfl_full_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            sfl_full_impl(rtncipher, cipher, true);
+        }
+
+    private:
+        void sfl_full_impl(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half)
+        {
             using namespace seal;
             Ciphertext tmpct, tmpct2;
             fwd_[0]->apply(cipher, tmpct, gal_keys_);
@@ -717,7 +730,7 @@ namespace moai_fused
             double curr_mod = static_cast<double>(modulus[curr_level].value());
             // the third set is rescaled by a factor that depends on the running scale; it is the same for every
             // ciphertext that went through the same pipeline, so the scaled transform is kept per factor
-            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_);
+            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_, half);
             auto it = fwd3_.find(key);
             if (it == fwd3_.end())
             {
@@ -733,9 +746,11 @@ namespace moai_fused
                     scaled[static_cast<std::size_t>(i)].resize(static_cast<std::size_t>(n_));
                     for (int j = 0; j < n_; j++)
                     {
+                        const std::complex<double> numerator =
+                            fftcoeff3_.at(static_cast<std::size_t>(i)).at(static_cast<std::size_t>(j)) * curr_mod * mod_zero * final_scale_;
                         scaled[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)] =
-                            fftcoeff3_.at(static_cast<std::size_t>(i)).at(static_cast<std::size_t>(j)) * curr_mod * mod_zero * final_scale_ /
-                            (tmpct2.scale() * tmpct2.scale() * initial_scale_);
+                            half ? numerator / (2 * tmpct2.scale() * tmpct2.scale() * initial_scale_) // :2569
+                                 : numerator / (tmpct2.scale() * tmpct2.scale() * initial_scale_);    // :2489
                     }
                 }
                 it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(context_, Nh_, fwd_totlen3_, fwd_basicstep3_,
@@ -746,6 +761,7 @@ namespace moai_fused
             evaluator_.rescale_to_next_inplace(rtncipher);
         }
 
+    public:
         // :2742-2759
         void coefftoslot_full_3(seal::Ciphertext &rtncipher1, seal::Ciphertext &rtncipher2, const seal::Ciphertext &cipher)
         {
@@ -787,6 +803,25 @@ namespace moai_fused
             sfl_full_3(rtncipher, tmpct3);
         }
 
+        // :2778-2795
+        void slottocoeff_full_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher1, const seal::Ciphertext &cipher2)
+        {
+            using namespace seal;
+            Ciphertext tmpct1, tmpct3;
+            std::complex<double> iunit(0.0, 1.0);
+            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
+            for (auto &z : tmpvec)
+            {
+                z += iunit;
+            }
+            Plaintext tmpplain;
+            encoder_.encode(tmpvec, 1.0, tmpplain);
+            evaluator_.mod_switch_to_inplace(tmpplain, cipher2.parms_id());
+            evaluator_.multiply_plain(cipher2, tmpplain, tmpct1);
+            evaluator_.add_reduced_error(cipher1, tmpct1, tmpct3);
+            sfl_full_half_3(rtncipher, tmpct3);
+        }
+
         // bootstrap_3 (:3496-3502) -> bootstrap_full_3 (:3231-3251); `cipher` is consumed like the reference's
         void bootstrap_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
         {
@@ -804,6 +839,58 @@ namespace moai_fused
             rtncipher.scale() = final_scale_;
         }
 
+        // bootstrap_real_3 (:3510-3516) -> bootstrap_full_real_3 (:3328-3351): the result encodes the real part of the message
+        void bootstrap_real_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            bootstrap_half(rtncipher, cipher);
+            Ciphertext conjct;
+            evaluator_.complex_conjugate(rtncipher, gal_keys_, conjct);
+            evaluator_.add_inplace_reduced_error(rtncipher, conjct);
+        }
+
+        // Two real ciphertexts through ONE bootstrap: a + i b (moai_fused::pair_real), everything of bootstrap_real_3 up to its
+        // final conjugate-and-add -- which leaves (a + i b) / 2 at final_scale -- and the conjugation shared by both outputs
+        // (moai_fused::split_real).  a and b are consumed.  Each output depends on its partner: the modular reduction's
+        // error grows with |a + i b|, and an input that is not real leaks its imaginary part into the other output.
+        void bootstrap_real_pair_3(seal::Ciphertext &out_a, seal::Ciphertext &out_b, seal::Ciphertext &a, seal::Ciphertext &b)
+        {
+            using namespace seal;
+            if (!a.is_ntt_form() && a.size() == 2)
+            {
+                evaluator_.transform_to_ntt_inplace(a);
+            }
+            if (!b.is_ntt_form() && b.size() == 2)
+            {
+                evaluator_.transform_to_ntt_inplace(b);
+            }
+            Ciphertext c, r;
+            moai_fused::pair_real(context_, a, b, c);
+            a.release();
+            b.release();
+            bootstrap_half(r, c);
+            moai_fused::split_real(context_, r, gal_keys_, out_a, out_b);
+        }
+
+    private:
+        // bootstrap_full_real_3 up to and including `scale = final_scale` (:3328-3346): encodes half the message
+        void bootstrap_half(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            initial_scale_ = cipher.scale();
+            modraise_inplace(cipher);
+            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
+            cipher.scale() = static_cast<double>(modulus[0].value());
+            Ciphertext rtn1, rtn2;
+            coefftoslot_full_3(rtn1, rtn2, cipher);
+            Ciphertext modrtn1, modrtn2;
+            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn1, rtn1);
+            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn2, rtn2);
+            slottocoeff_full_half_3(rtncipher, modrtn1, modrtn2);
+            rtncipher.scale() = final_scale_;
+        }
+
+    public:
         double &initial_scale()
         {
             return initial_scale_;
@@ -821,7 +908,7 @@ namespace moai_fused
         ModularReducer3 mod_reducer_;
         std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
         int fwd_totlen2_ = 0, fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
-        std::map<std::tuple<double, double, double>, std::unique_ptr<BsgsLinearTransform>> fwd3_;
+        std::map<std::tuple<double, double, double, bool>, std::unique_ptr<BsgsLinearTransform>> fwd3_; // last: the halved set
     };
     // Bootstrapper::bootstrap_3 for 3 <= logn < logNh (bootstrap_sparse_3, :3143-3229) on packed ciphertexts, with the
     // sparse diagonal sets of bootstrapping/moai_fft_diagonals.h (2n-entry diagonals replicated to N/2 slots by
@@ -930,6 +1017,17 @@ namespace moai_fused
         // :2419-2458; the third set is scaled by the running scale and kept per factor, as in sfl_full_3
         void sfl_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
         {
+            sfl_impl(rtncipher, cipher, false);
+        }
+        // :2499-2537: sfl_3 with the third set's constants halved
+        void sfl_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            sfl_impl(rtncipher, cipher, true);
+        }
+
+    private:
+        void sfl_impl(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half)
+        {
             using namespace seal;
             Ciphertext tmpct, tmpct2;
             fwd_[0]->apply(cipher, tmpct, gal_keys_);
@@ -941,7 +1039,7 @@ namespace moai_fused
             auto curr_level = context_.get_context_data(tmpct2.parms_id())->chain_index();
             double mod_zero = static_cast<double>(modulus[0].value());
             double curr_mod = static_cast<double>(modulus[curr_level].value());
-            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_);
+            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_, half);
             auto it = fwd3_.find(key);
             if (it == fwd3_.end())
             {
@@ -951,7 +1049,9 @@ namespace moai_fused
                     scaled[i].resize(static_cast<std::size_t>(2 * n_));
                     for (std::size_t j = 0; j < static_cast<std::size_t>(2 * n_); j++)
                     {
-                        scaled[i][j] = fftcoeff3_[i].at(j) * curr_mod * mod_zero * final_scale_ / (tmpct2.scale() * tmpct2.scale() * initial_scale_);
+                        const std::complex<double> numerator = fftcoeff3_[i].at(j) * curr_mod * mod_zero * final_scale_;
+                        scaled[i][j] = half ? numerator / (2 * tmpct2.scale() * tmpct2.scale() * initial_scale_) // :2532
+                                            : numerator / (tmpct2.scale() * tmpct2.scale() * initial_scale_);    // :2452
                     }
                 }
                 it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(context_, Nh_, fwd_totlen3_, fwd_basicstep3_,
@@ -962,6 +1062,7 @@ namespace moai_fused
             evaluator_.rescale_to_next_inplace(rtncipher);
         }
 
+    public:
         // :2721-2726
         void coefftoslot_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
         {
@@ -976,6 +1077,15 @@ namespace moai_fused
         {
             seal::Ciphertext tmpct1, tmpct2;
             sfl_3(tmpct1, cipher);
+            evaluator_.rotate_vector(tmpct1, n_, gal_keys_, tmpct2);
+            evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
+        }
+
+        // :2735-2740
+        void slottocoeff_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        {
+            seal::Ciphertext tmpct1, tmpct2;
+            sfl_half_3(tmpct1, cipher);
             evaluator_.rotate_vector(tmpct1, n_, gal_keys_, tmpct2);
             evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
         }
@@ -997,7 +1107,59 @@ namespace moai_fused
             rtncipher.scale() = final_scale_;
         }
 
+        // bootstrap_real_3 (:3510-3516) -> bootstrap_sparse_real_3 (:3253-3326) for logn > 0
+        void bootstrap_real_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            bootstrap_half(rtncipher, cipher);
+            Ciphertext conjct;
+            evaluator_.complex_conjugate(rtncipher, gal_keys_, conjct);
+            evaluator_.add_inplace_reduced_error(rtncipher, conjct);
+        }
+
+        // two real ciphertexts through one sparse bootstrap: see PackedBootstrapper3::bootstrap_real_pair_3
+        void bootstrap_real_pair_3(seal::Ciphertext &out_a, seal::Ciphertext &out_b, seal::Ciphertext &a, seal::Ciphertext &b)
+        {
+            using namespace seal;
+            if (!a.is_ntt_form() && a.size() == 2)
+            {
+                evaluator_.transform_to_ntt_inplace(a);
+            }
+            if (!b.is_ntt_form() && b.size() == 2)
+            {
+                evaluator_.transform_to_ntt_inplace(b);
+            }
+            Ciphertext c, r;
+            moai_fused::pair_real(context_, a, b, c);
+            a.release();
+            b.release();
+            bootstrap_half(r, c);
+            moai_fused::split_real(context_, r, gal_keys_, out_a, out_b);
+        }
+
+        double &initial_scale()
+        {
+            return initial_scale_;
+        }
+
     private:
+        // bootstrap_sparse_real_3 up to and including `scale = final_scale` (:3253-3322): encodes half the message
+        void bootstrap_half(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            initial_scale_ = cipher.scale();
+            modraise_inplace(cipher);
+            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
+            cipher.scale() = static_cast<double>(modulus[0].value());
+            subsum_inplace(cipher);
+            Ciphertext rtn;
+            coefftoslot_3(rtn, cipher);
+            Ciphertext modrtn;
+            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn, rtn);
+            slottocoeff_half_3(rtncipher, modrtn);
+            rtncipher.scale() = final_scale_;
+        }
+
         seal::SEALContext context_;
         const seal::CKKSEncoder &encoder_;
         const seal::Evaluator &evaluator_;
@@ -1009,6 +1171,6 @@ namespace moai_fused
         ModularReducer3 mod_reducer_;
         std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
         int fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
-        std::map<std::tuple<double, double, double>, std::unique_ptr<BsgsLinearTransform>> fwd3_;
+        std::map<std::tuple<double, double, double, bool>, std::unique_ptr<BsgsLinearTransform>> fwd3_; // last: the halved set
     };
 } // namespace moai_fused

@@ -71,6 +71,90 @@ namespace moai_fused
         cts = std::move(out);
     }
 
+    // ---- two real ciphertexts in one complex one ----------------------------------------------------------------
+    // pair_real(): out = a + i b, the slot-wise constant i being the monomial X^(N/2) -- exact, no level and no scale
+    // consumed.  The same residues as the reference's way to multiply by i (encode(i, 1.0), mod_switch_to, multiply_plain:
+    // include/source/bootstrapping/Bootstrapper.cpp:2760-2777) followed by add, in one pass over a and b (moai_mul_i_add).
+    // a, b (single or packed alike): same level, scale and batch, size 2, NTT form; anything else throws before any work
+    // is enqueued.  `out` may be `a` or `b`.
+    inline void pair_real(const seal::SEALContext &context, const seal::Ciphertext &a, const seal::Ciphertext &b, seal::Ciphertext &out)
+    {
+        using namespace seal;
+        if (a.size() != 2 || b.size() != 2)
+        {
+            throw std::invalid_argument("pair_real: ciphertexts of size 2 only");
+        }
+        if (!a.is_ntt_form() || !b.is_ntt_form())
+        {
+            throw std::invalid_argument("pair_real: ciphertexts must be in NTT form");
+        }
+        if (a.parms_id() != b.parms_id())
+        {
+            throw std::invalid_argument("pair_real: ciphertexts differ in level");
+        }
+        if (a.scale() != b.scale())
+        {
+            throw std::invalid_argument("pair_real: ciphertexts differ in scale");
+        }
+        if (a.batch() != b.batch())
+        {
+            throw std::invalid_argument("pair_real: ciphertexts differ in batch size");
+        }
+        if (!context.get_context_data(a.parms_id()))
+        {
+            throw std::invalid_argument("pair_real: ciphertext is not valid for encryption parameters");
+        }
+        Ciphertext c;
+        c.resize_batch(context, a.parms_id(), 2, a.batch());
+        c.is_ntt_form() = true;
+        c.scale() = a.scale();
+        util::hip_check(moai_mul_i_add(context.device(), a.device_data(), b.device_data(), c.device_data(), 2 * a.batch(),
+                                       a.coeff_modulus_size(), 1, context.stream()));
+        out = std::move(c);
+    }
+    // split_real(): for r = a + i b with real a, b:  out_re = r + conj(r) = 2a,  out_im = -i (r - conj(r)) = 2b.  One key switch
+    // (the conjugation, Galois element 2N - 1 as in Evaluator::complex_conjugate, SEAL/evaluator.h:1428-1450) and one pass
+    // over r and its conjugate (moai_real_split).  Level, scale and form of r.  The outputs may be r itself.
+    inline void split_real(const seal::SEALContext &context, const seal::Ciphertext &r, const seal::GaloisKeys &gal_keys,
+                           seal::Ciphertext &out_re, seal::Ciphertext &out_im)
+    {
+        using namespace seal;
+        if (r.size() != 2 || !r.is_ntt_form())
+        {
+            throw std::invalid_argument("split_real: a size-2 ciphertext in NTT form only");
+        }
+        if (!context.get_context_data(r.parms_id()))
+        {
+            throw std::invalid_argument("split_real: ciphertext is not valid for encryption parameters");
+        }
+        if (gal_keys.parms_id() != context.key_parms_id())
+        {
+            throw std::invalid_argument("galois_keys is not valid for encryption parameters");
+        }
+        const std::uint32_t elt = static_cast<std::uint32_t>(2 * context.n() - 1);
+        if (!gal_keys.has_key(elt))
+        {
+            throw std::invalid_argument("Galois key not present");
+        }
+        if (&out_re == &out_im)
+        {
+            throw std::invalid_argument("split_real: two distinct outputs");
+        }
+        const std::size_t L = r.coeff_modulus_size(), B = r.batch();
+        Ciphertext re, im;
+        re.resize_batch(context, r.parms_id(), 2, B);
+        im.resize_batch(context, r.parms_id(), 2, B);
+        re.is_ntt_form() = im.is_ntt_form() = true;
+        re.scale() = im.scale() = r.scale();
+        const std::uint64_t *src = r.device_data();
+        util::hip_check(moai_apply_galois_to(context.device(), src, im.device_data(), L, elt,
+                                             gal_keys.device_key(GaloisKeys::get_index(elt), L), B, context.stream()));
+        util::hip_check(moai_real_split(context.device(), src, im.device_data(), re.device_data(), im.device_data(), 2 * B, L,
+                                        context.stream()));
+        out_re = std::move(re);
+        out_im = std::move(im);
+    }
+
     // ---- client output path -----------------------------------------------------------------------------------
     // decrypt_decode(): Decryptor::decrypt then CKKSEncoder::decode of every ciphertext, with the same values bit for
     // bit, for callers that own many ciphertexts (MOAI decrypts all 768 outputs of a layer, test_full_scheme.hpp:1047-1065).

@@ -20,6 +20,9 @@
 // (tests/cpp/test_moai_headers.cpp, test_moai_attention.cpp, test_bootstrap_real.cpp).
 // usage: bench_encoder_layer [heads = 12] [bootstrap packs per round = all] [gelu packs = 48] [bootstrap pack size = 48]
 //   smaller numbers make a quick plumbing run: the remaining work is skipped and its results are copies.
+// MOAI_BOOT_PAIR_REAL=1 in the environment: the bootstrapping rounds pair their (real-valued) ciphertexts two to a bootstrap
+//   (Bootstrapper::bootstrap_real_many_3, packs of that many PAIRS) and print per round how far a sample lands from the
+//   unpaired bootstrap; MOAI's softmax_boot pairs its gathered calls through the same opt-in.  Unset: nothing changes.
 #include "seal/seal.h"
 
 #include <omp.h>
@@ -112,7 +115,75 @@ static int run(int argc, char **argv)
     bootstrapper.generate_LT_coefficient_3();
 
     // one bootstrapping round: every ciphertext to the lowest level (:642-646), then bootstrap_3 in packs of boot_B
+    // With MOAI_BOOT_PAIR_REAL=1 (Bootstrapper::pair_real: the layer's activations are real) a round goes through
+    // bootstrap_real_many_3 instead, in packs of boot_B PAIRS, and reports how far the first and the last ciphertext of the round
+    // land from the same two sent through bootstrap_full_3.
+    auto bootstrap_round_paired = [&](vector<Ciphertext> &cts, const char *name) {
+        const int B = boot_B, chunk = 2 * B, chunks = ((int)cts.size() + chunk - 1) / chunk;
+        double t = now_s();
+        vector<Ciphertext> out(cts.size());
+        Ciphertext first_in, last_in;
+        int done = 0;
+        for (int ci = 0; ci < chunks; ci++)
+        {
+            const int at = ci * chunk, cnt = min(chunk, (int)cts.size() - at);
+            if (2 * ci >= boot_packs)
+            {
+                for (int b = 0; b < cnt; b++) out[at + b] = out[b]; // quick run: copies
+                continue;
+            }
+            vector<Ciphertext> part(cts.begin() + at, cts.begin() + at + cnt), res;
+            for (auto &c : part)
+            {
+                while (context.get_context_data(c.parms_id())->chain_index() != 0) evaluator.mod_switch_to_next_inplace(c);
+            }
+            if (ci == 0)
+            {
+                first_in = part[0];
+            }
+            last_in = part[cnt - 1];
+            bootstrapper.bootstrap_real_many_3(res, part);
+            for (int b = 0; b < cnt; b++)
+            {
+                out[at + b] = std::move(res[b]);
+                cts[at + b].release();
+            }
+            done = at + cnt;
+        }
+        context.sync();
+        t = now_s() - t;
+        // outside the timed region: the same two ciphertexts through the unpaired bootstrap
+        Ciphertext ref_packed = moai_fused::pack({ first_in, last_in }, context), ref_out;
+        bootstrapper.bootstrap_full_3(ref_out, ref_packed);
+        vector<Ciphertext> ref;
+        moai_fused::unpack(ref_out, context, ref);
+        double dev = 0, size = 0;
+        const Ciphertext *mine[2] = { &out[0], &out[done - 1] };
+        for (int k = 0; k < 2; k++)
+        {
+            Plaintext pa, pb;
+            decryptor.decrypt(*mine[k], pa);
+            decryptor.decrypt(ref[k], pb);
+            vector<complex<double>> va, vb;
+            encoder.decode(pa, va);
+            encoder.decode(pb, vb);
+            for (size_t i = 0; i < va.size(); i++)
+            {
+                dev = max(dev, abs(va[i] - vb[i]));
+                size = max(size, abs(vb[i]));
+            }
+        }
+        fprintf(stderr, "%-28s %8.2f s   (paired: %d of %d packs of %d pairs; chain index -> %zu; first and last ciphertext against "
+                        "bootstrap_full_3: max deviation %.3e at max |value| %.3f)\n",
+                name, t, min(chunks, (boot_packs + 1) / 2), chunks, B, context.get_context_data(out[0].parms_id())->chain_index(), dev, size);
+        cts = std::move(out);
+        return t;
+    };
     auto bootstrap_round = [&](vector<Ciphertext> &cts, const char *name) {
+        if (bootstrapper.pair_real)
+        {
+            return bootstrap_round_paired(cts, name);
+        }
         const int B = boot_B, packs = (int)cts.size() / B;
         double t = now_s();
         vector<Ciphertext> out(cts.size());
