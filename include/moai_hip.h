@@ -419,6 +419,57 @@ int moai_encrypt_asymmetric(moai_ctx *ctx, const uint8_t *key, uint64_t seq, con
 int moai_kswitch_keygen(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
                         uint64_t *out, void *stream);
 
+/* ---- wire form: seeded objects and bit-packed rows ---------------------------------------------------------------------
+ * What lets a ciphertext or a key leave the process that made it at 38 % of its resident size.  Both reductions are exact.
+ *
+ * Packed rows.  Row r of a polynomial under prime q_r, with b_r the bit length of q_r, is a little-endian bit stream:
+ * coefficient i occupies bits [i b_r, (i + 1) b_r) of the row, bit j of the stream is bit (j mod 64) of 64-bit word j / 64;
+ * every row starts on a word boundary and takes ceil(N b_r / 64) words (nothing is padded for N >= 64; for smaller N the padding
+ * bits are zero).  Rows follow each other in the order of the unpacked layout [n_poly][L][N], rows under prime_index (NULL =
+ * 0..L-1).  The reference has no such form: it leaves compression to zlib / zstd (SEAL/serialization.cpp:224-320).
+ * moai_packed_words: the words of ONE packed polynomial, sum over r of ceil(N b_r / 64); host arithmetic, no launch; 0 on error.
+ * moai_pack_rows: in [n_poly][L][N] (canonical residues; the low b_r bits of a word are stored) -> packed.
+ * moai_unpack_rows: the inverse.  invalid: NULL or a device uint32_t that the kernel sets to non-zero when any unpacked value is
+ * >= q_r (a b_r-bit field can hold one) and otherwise leaves alone -- the residue check of is_data_valid_for where the data is
+ * (SEAL/valcheck.cpp:302-335, "ciphertext data is invalid" SEAL/ciphertext.cpp:302,358).  The caller zeroes it beforehand.
+ * in / out and packed must not overlap and out must be 16-byte aligned (MOAI_EINVAL); b_r from 2 to 61 is supported.
+ *
+ * Seeded objects.  In a symmetric encryption and in every digit of a switching key the second polynomial is the uniform a,
+ * a function of (key, nonce, coefficient index) only (stream contract above), so the wire form carries a seed in its place
+ * (save_seed: SEAL/util/rlwe.cpp:334-385, SEAL/encryptor.cpp:89-248, SEAL/keygenerator.h:321-360).  moai_encrypt_symmetric and
+ * moai_kswitch_keygen draw a and the noise from the SAME key, which therefore must stay secret; the seeded entry points take
+ * TWO keys as the reference does (rlwe.cpp:353-363): the secret noise_key for e (purpose 3) and the public seed for a (purpose 1).
+ * Only seed and the sequence number travel.  With noise_key == seed a seeded call followed by moai_expand_seeded reproduces the
+ * unseeded entry point bit for bit.
+ *   purpose 5  public seed: the seed of the object with sequence seq is the first 32 bytes (words W[0..3], little endian) of
+ *              the stream (noise key, 5 << 56 | seq), computed on the host (seal::util::ChaCha20Rng); ChaCha20 output does not
+ *              reveal its key.  Inside a seeded object sequences start at 0.
+ * moai_encrypt_symmetric_seeded: out_c0 [n_batch][L][N] = c0 exactly as moai_encrypt_symmetric computes it with a from
+ * (seed, 1 << 56 | seq + b) and e from (noise_key, 3 << 56 | seq + b); c1 is not written.
+ * moai_kswitch_keygen_seeded: the same for the k-1 digits of a switching key, out_c0 [k-1][k][N].
+ * moai_expand_seeded: c0 [count][L][N] -> out [count][2][L][N] with out[b][0] = c0[b] and out[b][1] = uniform(seed,
+ * 1 << 56 | seq + b) in NTT form, i.e. what moai_sample_uniform draws there: a ciphertext batch, or with count = k-1 and L = k a
+ * switching key in the layout every key-switch entry point takes (Ciphertext::expand_seed, SEAL/ciphertext.cpp:118-188).  c0 and
+ * out must not overlap.
+ * Validation as above: MOAI_EINVAL with a message before anything is enqueued; no call synchronises. */
+size_t moai_packed_words(const moai_ctx *ctx, size_t L, const uint32_t *prime_index);
+/* the exact counterpart of Serialization::Save's compression step, SEAL/serialization.cpp:224-320 */
+int moai_pack_rows(moai_ctx *ctx, const uint64_t *in, uint64_t *packed, size_t n_poly, size_t L, const uint32_t *prime_index,
+                   void *stream);
+/* Serialization::Load's decompression plus is_data_valid_for, SEAL/serialization.cpp:365-383, SEAL/valcheck.cpp:302-335 */
+int moai_unpack_rows(moai_ctx *ctx, const uint64_t *packed, uint64_t *out, size_t n_poly, size_t L, const uint32_t *prime_index,
+                     uint32_t *invalid /* device, or NULL */, void *stream);
+/* encrypt_zero_symmetric with save_seed, SEAL/util/rlwe.cpp:311-385 under Encryptor::encrypt_symmetric SEAL/encryptor.cpp:89-248 */
+int moai_encrypt_symmetric_seeded(moai_ctx *ctx, const uint8_t *noise_key /* host, 32 bytes */, const uint8_t *seed /* host, 32 bytes */,
+                                  uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain, uint64_t *out_c0, size_t n_batch,
+                                  size_t L, const uint32_t *prime_index, void *stream);
+/* KeyGenerator::generate_one_kswitch_key with save_seed, SEAL/keygenerator.cpp:303-336, SEAL/keygenerator.h:321-360 */
+int moai_kswitch_keygen_seeded(moai_ctx *ctx, const uint8_t *noise_key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
+                               const uint64_t *new_key_ntt, uint64_t *out_c0, void *stream);
+/* Ciphertext::expand_seed, SEAL/ciphertext.cpp:118-188 */
+int moai_expand_seeded(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const uint64_t *c0, uint64_t *out, size_t count, size_t L,
+                       const uint32_t *prime_index, void *stream);
+
 /* ---- tuning -------------------------------------------------------------------------------------------------------
  * Overrides a performance knob for the whole process (same names as the environment variables read by the
  * library, which it takes precedence over).  Results never depend on these.  Currently:

@@ -10,7 +10,9 @@
 //   cl_uniform      : 4 coefficients (one block of 8 words) per thread, (hi * 2^64 + lo) mod q exactly (mod128)
 //   cl_small        : 8 coefficients (one block) per thread, ternary or CBD, written as residues in every requested row
 //   cl_sym_finish   : c1 = uniform a generated in place (NTT form, as SEAL samples it), c0 = e - a s (+ m) (+ (p mod q_J) s' in
-//                     row J of a key digit); c1 is never stored before this kernel
+//                     row J of a key digit); c1 is never stored before this kernel, and in the seeded form (a from a public seed,
+//                     SEAL/util/rlwe.cpp:353-363) not stored at all
+//   cl_expand       : c1 of a seeded object drawn again from its seed beside a copy of c0 (Ciphertext::expand_seed)
 //   cl_pk_finish    : c_i = pk_i u + e_i over the rows of the previous level, u read once; then the existing rescale divides by
 //                     the dropped prime (divide_and_round_q_last_ntt_inplace) and cl_add_c0 adds the plaintext to c0
 #include <mutex>
@@ -188,13 +190,13 @@ __global__ __launch_bounds__(256) void cl_small(SmallArgs g)
 // ---- symmetric encryption / key digits --------------------------------------------------------------------------------
 struct SymArgs
 {
-    ChaKey key;
+    ChaKey key;             // the stream a is drawn from: the caller's one key, or the public seed of a seeded object
     uint64_t nonce_a;       // ciphertext b (of this launch) draws a with nonce_a + b
     const uint64_t *e;      // [nb][L][N] NTT form
     const uint64_t *sk;     // [L][N]
     const uint64_t *plain;  // [nb][L][N] or null
     const uint64_t *newkey; // [L][N] or null: key digit b adds fac[b] * newkey[b] in row b of c0
-    uint64_t *out;          // [nb][2][L][N]
+    uint64_t *out;          // [nb][2][L][N]; seeded form: c0 only, [nb][L][N]
     uint32_t digit0;        // digit of ciphertext 0 of this launch
     const PrimeConst *pc;
     RowMap rows;
@@ -203,6 +205,7 @@ struct SymArgs
     uint32_t logn;
 };
 
+template <bool SEEDED>
 __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
 {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
@@ -261,12 +264,51 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
             c0[j] = csub(c0[j] + mulmod_barrett(kv[j], fac, q, pc.cr0, pc.cr1), q);
         }
     }
-    ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(g.out + 2 * b * LN + f);
-    ulonglong2 *o1 = reinterpret_cast<ulonglong2 *>(g.out + (2 * b + 1) * LN + f);
+    ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(g.out + (SEEDED ? 1 : 2) * b * LN + f);
     o0[0] = make_ulonglong2(c0[0], c0[1]);
     o0[1] = make_ulonglong2(c0[2], c0[3]);
-    o1[0] = make_ulonglong2(a[0], a[1]);
-    o1[1] = make_ulonglong2(a[2], a[3]);
+    if (!SEEDED)
+    {
+        ulonglong2 *o1 = reinterpret_cast<ulonglong2 *>(g.out + (2 * b + 1) * LN + f);
+        o1[0] = make_ulonglong2(a[0], a[1]);
+        o1[1] = make_ulonglong2(a[2], a[3]);
+    }
+}
+
+// ---- seeded objects ---------------------------------------------------------------------------------------------------
+struct ExpandArgs
+{
+    ChaKey seed;
+    uint64_t nonce;     // object b draws c1 with nonce + b
+    const uint64_t *c0; // [count][L][N]
+    uint64_t *out;      // [count][2][L][N]
+    const PrimeConst *pc;
+    RowMap rows;
+    uint32_t L;
+    uint32_t logn;
+};
+
+__global__ __launch_bounds__(256) void cl_expand(ExpandArgs g)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // block index of the stream, as in cl_uniform
+    if (t >= (g.L << g.logn) >> 2)
+    {
+        return;
+    }
+    const uint32_t b = blockIdx.y;
+    const uint32_t f = t << 2;
+    const size_t LN = (size_t)g.L << g.logn;
+    const PrimeConst &pc = g.pc[g.rows.idx[f >> g.logn]];
+    const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(g.c0 + b * LN + f);
+    const ulonglong2 c01 = src[0], c23 = src[1];
+    uint32_t blk[16];
+    chacha_block(g.seed, g.nonce + b, t, blk);
+    ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(g.out + 2 * b * LN + f);
+    ulonglong2 *o1 = reinterpret_cast<ulonglong2 *>(g.out + (2 * b + 1) * LN + f);
+    o0[0] = c01;
+    o0[1] = c23;
+    o1[0] = make_ulonglong2(mod128(word64(blk, 0), word64(blk, 1), pc), mod128(word64(blk, 2), word64(blk, 3), pc));
+    o1[1] = make_ulonglong2(mod128(word64(blk, 4), word64(blk, 5), pc), mod128(word64(blk, 6), word64(blk, 7), pc));
 }
 
 // ---- public-key encryption --------------------------------------------------------------------------------------------
@@ -419,9 +461,10 @@ static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, siz
     return MOAI_OK;
 }
 
-// symmetric encryptions (newkey == null) or the digits of a switching key: ciphertext b uses sequence seq + b
-static int sym_impl(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk, const uint64_t *plain, const uint64_t *newkey,
-                    uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, hipStream_t s)
+// symmetric encryptions (newkey == null) or the digits of a switching key: ciphertext b uses sequence seq + b.  seed == null:
+// a and e from `key`, out [n_batch][2][L][N]; otherwise e from `key`, a from `seed`, and out holds c0 only, [n_batch][L][N]
+static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk, const uint64_t *plain,
+                    const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, hipStream_t s)
 {
     int rc = enter_device(c);
     if (rc)
@@ -431,7 +474,7 @@ static int sym_impl(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_
     const ChaKey k = load_key(key);
     const size_t n = c->n, LN = L * n;
     SymArgs a;
-    a.key = k;
+    a.key = seed ? load_key(seed) : k;
     a.sk = sk;
     a.newkey = newkey;
     a.pc = c->pc;
@@ -467,9 +510,16 @@ static int sym_impl(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_
         a.nonce_a = (CL_UNIFORM << 56) | (seq + b0);
         a.e = e;
         a.plain = plain ? plain + b0 * LN : nullptr;
-        a.out = out + b0 * 2 * LN;
+        a.out = out + b0 * (seed ? 1 : 2) * LN;
         a.digit0 = (uint32_t)b0;
-        hipLaunchKernelGGL(cl_sym_finish, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+        if (seed)
+        {
+            hipLaunchKernelGGL(cl_sym_finish<true>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+        }
+        else
+        {
+            hipLaunchKernelGGL(cl_sym_finish<false>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+        }
         MOAI_LAUNCH_CHECK();
     }
     return MOAI_OK;
@@ -570,11 +620,10 @@ extern "C" int moai_sample_cbd(moai_ctx *c, const uint8_t *key, uint64_t nonce, 
     return sampler_entry(c, 2, key, nonce, out, n_poly, L, prime_index, stream);
 }
 
-extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
-                                      uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index, void *stream)
+static int encrypt_symmetric_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
+                                   const uint64_t *plain, uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index,
+                                   void *stream)
 {
-    MOAI_AUDIT(stream, sk_ntt, plain, out);
-    trace_op("encrypt_symmetric", L, n_batch);
     int rc = check_common(c, key, seq, n_batch);
     if (rc)
     {
@@ -598,18 +647,33 @@ extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t 
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    return sym_impl(c, key, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, (hipStream_t)stream);
 }
 
-extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
-                                   uint64_t *out, void *stream)
+extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
+                                      uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index, void *stream)
 {
-    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out);
-    if (!c)
+    MOAI_AUDIT(stream, sk_ntt, plain, out);
+    trace_op("encrypt_symmetric", L, n_batch);
+    return encrypt_symmetric_entry(c, key, nullptr, seq, sk_ntt, plain, out, n_batch, L, prime_index, stream);
+}
+
+extern "C" int moai_encrypt_symmetric_seeded(moai_ctx *c, const uint8_t *noise_key, const uint8_t *seed, uint64_t seq,
+                                             const uint64_t *sk_ntt, const uint64_t *plain, uint64_t *out_c0, size_t n_batch, size_t L,
+                                             const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, plain, out_c0);
+    trace_op("encrypt_symmetric_seeded", L, n_batch);
+    if (c && noise_key && !seed)
     {
-        return set_error(MOAI_EINVAL, "null context");
+        return set_error(MOAI_EINVAL, "null seed");
     }
-    trace_op("kswitch_keygen", c->k, c->k - 1);
+    return encrypt_symmetric_entry(c, noise_key, seed, seq, sk_ntt, plain, out_c0, n_batch, L, prime_index, stream);
+}
+
+static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
+                                const uint64_t *new_key_ntt, uint64_t *out, void *stream)
+{
     if (c->k < 2)
     {
         return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
@@ -630,7 +694,88 @@ extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq
     {
         return rc;
     }
-    return sym_impl(c, key, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, (hipStream_t)stream);
+}
+
+extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
+                                   uint64_t *out, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    trace_op("kswitch_keygen", c->k, c->k - 1);
+    return kswitch_keygen_entry(c, key, nullptr, seq, sk_ntt, new_key_ntt, out, stream);
+}
+
+extern "C" int moai_kswitch_keygen_seeded(moai_ctx *c, const uint8_t *noise_key, const uint8_t *seed, uint64_t seq,
+                                          const uint64_t *sk_ntt, const uint64_t *new_key_ntt, uint64_t *out_c0, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out_c0);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    trace_op("kswitch_keygen_seeded", c->k, c->k - 1);
+    if (noise_key && !seed)
+    {
+        return set_error(MOAI_EINVAL, "null seed");
+    }
+    return kswitch_keygen_entry(c, noise_key, seed, seq, sk_ntt, new_key_ntt, out_c0, stream);
+}
+
+extern "C" int moai_expand_seeded(moai_ctx *c, const uint8_t *seed, uint64_t seq, const uint64_t *c0, uint64_t *out, size_t count, size_t L,
+                                  const uint32_t *prime_index, void *stream)
+{
+    MOAI_AUDIT(stream, c0, out);
+    trace_op("expand_seeded", L, count);
+    int rc = check_common(c, seed, seq, count);
+    if (rc)
+    {
+        return rc;
+    }
+    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
+    {
+        return set_error(MOAI_EINVAL, "invalid level");
+    }
+    ExpandArgs a;
+    rc = make_rowmap(c, L, prime_index, &a.rows);
+    if (rc)
+    {
+        return rc;
+    }
+    if (count == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!c0 || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t LN = L * c->n;
+    {
+        const uintptr_t x = (uintptr_t)c0, y = (uintptr_t)out;
+        if (x < y + 2 * count * LN * 8 && y < x + count * LN * 8)
+        {
+            return set_error(MOAI_EINVAL, "c0 and out overlap");
+        }
+    }
+    rc = enter_device(c);
+    if (rc)
+    {
+        return rc;
+    }
+    a.seed = load_key(seed);
+    a.nonce = (CL_UNIFORM << 56) | seq;
+    a.c0 = c0;
+    a.out = out;
+    a.pc = c->pc;
+    a.L = (uint32_t)L;
+    a.logn = (uint32_t)c->logn;
+    hipLaunchKernelGGL(cl_expand, grid_of(LN / 4, count), dim3(256), 0, (hipStream_t)stream, a);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
 }
 
 extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *pk, const uint64_t *plain,

@@ -81,6 +81,12 @@ SYMBOLS = {
     "moai_encrypt_symmetric": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_encrypt_asymmetric": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, vp]),
     "moai_kswitch_keygen": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, vp, vp]),
+    "moai_packed_words": (sz, [vp, sz, C.POINTER(C.c_uint32)]),
+    "moai_pack_rows": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_unpack_rows": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
+    "moai_encrypt_symmetric_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_kswitch_keygen_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, vp]),
+    "moai_expand_seeded": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
@@ -551,6 +557,50 @@ class Context:
         """The k-1 digits of the switching key for new_key_ntt [k][N]: a DeviceBuffer [k-1][2][k][N]."""
         out = DeviceBuffer(max(self.k - 1, 1) * 2 * self.k * self.n)
         _check(lib().moai_kswitch_keygen(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(new_key_ntt), out.ptr, stream))
+        return out
+
+    # --- wire form (include/moai_hip.h, "wire form: seeded objects and bit-packed rows") ---------------------------
+    def packed_words(self, L, prime_index=None):
+        """64-bit words of one packed polynomial of L rows"""
+        w = lib().moai_packed_words(self.h, L, self._pidx(prime_index))
+        if w == 0:
+            _check(MOAI_EINVAL)
+        return w
+
+    def pack_rows(self, data, n_poly, L, prime_index=None, stream=None):
+        """[n_poly][L][N] residues -> a DeviceBuffer of n_poly * packed_words(L) words, every row at its prime's bit length"""
+        out = DeviceBuffer(max(n_poly, 1) * self.packed_words(L, prime_index))
+        _check(lib().moai_pack_rows(self.h, _ptr(data), out.ptr, n_poly, L, self._pidx(prime_index), stream))
+        return out
+
+    def unpack_rows(self, packed, n_poly, L, prime_index=None, check=True, stream=None):
+        """the inverse of pack_rows: (DeviceBuffer [n_poly][L][N], invalid); invalid is True when a field held a value >= its
+        row's prime (None with check=False, which hands the library no flag)"""
+        out = DeviceBuffer(max(n_poly, 1) * L * self.n)
+        flag = DeviceBuffer(1) if check else None
+        if check:
+            _check(lib().moai_memset_zero(flag.ptr, 8, stream))
+        _check(lib().moai_unpack_rows(self.h, _ptr(packed), out.ptr, n_poly, L, self._pidx(prime_index), _ptr(flag), stream))
+        return out, (bool(flag.to_numpy(stream=stream)[0]) if check else None)
+
+    def encrypt_symmetric_seeded(self, noise_key, seed, seq, sk_ntt, L, n_batch=1, plain=None, prime_index=None, stream=None):
+        """c0 [n_batch][L][N] of encrypt_symmetric with a drawn from the public `seed` and the noise from `noise_key`"""
+        out = DeviceBuffer(max(n_batch, 1) * L * self.n)
+        _check(lib().moai_encrypt_symmetric_seeded(self.h, self._key(noise_key), self._key(seed), int(seq), _ptr(sk_ntt), _ptr(plain),
+                                                   out.ptr, n_batch, L, self._pidx(prime_index), stream))
+        return out
+
+    def kswitch_keygen_seeded(self, noise_key, seed, seq, sk_ntt, new_key_ntt, stream=None):
+        """c0 [k-1][k][N] of the k-1 digits of the switching key for new_key_ntt"""
+        out = DeviceBuffer(max(self.k - 1, 1) * self.k * self.n)
+        _check(lib().moai_kswitch_keygen_seeded(self.h, self._key(noise_key), self._key(seed), int(seq), _ptr(sk_ntt),
+                                                _ptr(new_key_ntt), out.ptr, stream))
+        return out
+
+    def expand_seeded(self, seed, seq, c0, count, L, prime_index=None, stream=None):
+        """[count][L][N] -> [count][2][L][N] with c1 drawn from (seed, sequence seq + b)"""
+        out = DeviceBuffer(max(count, 1) * 2 * L * self.n)
+        _check(lib().moai_expand_seeded(self.h, self._key(seed), int(seq), _ptr(c0), out.ptr, count, L, self._pidx(prime_index), stream))
         return out
 
     def total_coeff_modulus_bit_count(self, L, prime_index=None):

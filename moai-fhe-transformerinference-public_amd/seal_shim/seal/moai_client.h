@@ -185,6 +185,29 @@ namespace seal
             std::atomic<std::uint64_t> next_{ 0 };
         };
 
+        // The public seed of a seeded object (include/moai_hip.h, purpose 5): the first 32 bytes of the stream
+        // (noise key, 5 << 56 | seq).  ChaCha20 output does not reveal its key, so the seed may travel where the key may not
+        // (the reference draws its public seed from the secret generator the same way, SEAL/util/rlwe.cpp:353-363).
+        inline void public_seed(const unsigned char *noise_key, std::uint64_t seq, std::uint8_t (&seed)[32])
+        {
+            unsigned char init[40];
+            std::memcpy(init, noise_key, 32);
+            const std::uint64_t nonce = (std::uint64_t(5) << 56) | seq;
+            for (int i = 0; i < 8; i++)
+            {
+                init[32 + i] = static_cast<unsigned char>(nonce >> (8 * i));
+            }
+            ChaCha20Rng g(init);
+            for (int w = 0; w < 4; w++)
+            {
+                const std::uint64_t v = g();
+                for (int i = 0; i < 8; i++)
+                {
+                    seed[8 * w + i] = static_cast<std::uint8_t>(v >> (8 * i));
+                }
+            }
+        }
+
         // uniform residues [rows][N], row r under primes[r]
         inline void sample_uniform(const std::vector<std::uint64_t> &primes, std::size_t n, std::vector<std::uint64_t> &out)
         {
@@ -737,6 +760,65 @@ namespace seal
         {
             create_galois_keys_impl(galois_elts, destination, true);
         }
+        // ---- seeded keys for the wire (SEAL/keygenerator.h:92-118, 138-160, 190-300: the overloads without a destination) ----
+        // c0 of every key digit from moai_kswitch_keygen_seeded and the public seed of the key; the uniform halves are drawn
+        // where the key is loaded (moai_expand_seeded).  The key's digits take the sequences [seq, seq + k - 1) of the device
+        // generator for their noise, and the same sequences under the key's own seed for a.
+        Serializable<PublicKey> create_public_key() const
+        {
+            wire::Object o = seeded_object(wire::kind_public_key);
+            o.head = seeded_record(wire::kind_public_key, nullptr);
+            context_.sync();
+            return Serializable<PublicKey>(std::move(o));
+        }
+        Serializable<RelinKeys> create_relin_keys()
+        {
+            require_keyswitching();
+            util::DeviceArray s2(k_ * n_, context_.stream());
+            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
+                                            context_.stream()));
+            wire::Object o = seeded_object(wire::kind_relin_keys);
+            o.indices.push_back(0);
+            o.keys.push_back(seeded_record(wire::kind_kswitch_key, s2.get()));
+            o.head.count = 1;
+            context_.sync();
+            return Serializable<RelinKeys>(std::move(o));
+        }
+        Serializable<GaloisKeys> create_galois_keys(const std::vector<std::uint32_t> &galois_elts)
+        {
+            require_keyswitching();
+            std::vector<std::uint64_t> idx;
+            for (std::uint32_t elt : galois_elts)
+            {
+                if (!(elt & 1) || elt >= 2 * n_)
+                {
+                    throw std::invalid_argument("Galois element is not valid");
+                }
+                idx.push_back(GaloisKeys::get_index(elt));
+            }
+            std::sort(idx.begin(), idx.end());
+            idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+            wire::Object o = seeded_object(wire::kind_galois_keys);
+            util::DeviceArray rotated(k_ * n_, context_.stream());
+            for (std::uint64_t i : idx)
+            {
+                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
+                                                    static_cast<std::uint32_t>(2 * i + 1), context_.stream()));
+                o.indices.push_back(i);
+                o.keys.push_back(seeded_record(wire::kind_kswitch_key, rotated.get()));
+            }
+            o.head.count = static_cast<std::uint32_t>(o.keys.size());
+            context_.sync();
+            return Serializable<GaloisKeys>(std::move(o));
+        }
+        Serializable<GaloisKeys> create_galois_keys(const std::vector<int> &steps)
+        {
+            return create_galois_keys(galois_elts_from_steps(steps));
+        }
+        Serializable<GaloisKeys> create_galois_keys()
+        {
+            return create_galois_keys(galois_elts_all());
+        }
         // the randomness of the device paths (a fresh OS-keyed one by default)
         void set_device_rng(std::shared_ptr<util::DeviceRng> rng)
         {
@@ -800,6 +882,51 @@ namespace seal
         }
 
     private:
+        void require_keyswitching() const
+        {
+            if (!context_.using_keyswitching())
+            {
+                throw std::logic_error("keyswitching is not supported by the context");
+            }
+        }
+        wire::Object seeded_object(std::uint32_t kind) const
+        {
+            wire::Object o;
+            o.dev = context_.device();
+            o.stream = context_.stream();
+            o.is_set = kind != wire::kind_public_key;
+            o.head.kind = kind;
+            o.head.flags = wire::flag_ntt;
+            o.head.L = static_cast<std::uint32_t>(k_);
+            o.head.parms_id = context_.key_parms_id();
+            return o;
+        }
+        // new_key_ntt == null: an encryption of zero at the key level (the public key); otherwise the k-1 digits of a switching key
+        wire::Record seeded_record(std::uint32_t kind, const std::uint64_t *new_key_ntt) const
+        {
+            const std::size_t count = new_key_ntt ? k_ - 1 : 1;
+            wire::Record r;
+            r.kind = kind;
+            r.flags = wire::flag_ntt | wire::flag_seeded;
+            r.count = static_cast<std::uint32_t>(2 * count);
+            r.L = static_cast<std::uint32_t>(k_);
+            r.parms_id = context_.key_parms_id();
+            r.seq = rng_->take(count);
+            util::public_seed(rng_->key(), r.seq, r.seed);
+            r.block = std::make_shared<util::DeviceArray>(count * k_ * n_, context_.stream());
+            if (new_key_ntt)
+            {
+                util::hip_check(moai_kswitch_keygen_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), new_key_ntt,
+                                                           r.block->get(), context_.stream()));
+            }
+            else
+            {
+                util::hip_check(moai_encrypt_symmetric_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), nullptr,
+                                                              r.block->get(), 1, k_, nullptr, context_.stream()));
+            }
+            r.data = r.block->get();
+            return r;
+        }
         void create_relin_keys_impl(RelinKeys &destination, bool device)
         {
             if (!context_.using_keyswitching())
@@ -993,11 +1120,46 @@ namespace seal
         {
             encrypt_zero_symmetric(context_.first_parms_id(), destination);
         }
+        // ---- seeded ciphertexts for the wire (SEAL/encryptor.h:374-404, 430-478: the overloads without a destination) -----
+        // c0 from moai_encrypt_symmetric_seeded and the public seed; c1 is drawn where the ciphertext is loaded
+        Serializable<Ciphertext> encrypt_symmetric(const Plaintext &plain, MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            auto cd = context_.get_context_data(plain.parms_id());
+            if (!cd || !plain.is_ntt_form())
+            {
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            }
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            wire::Object o = seeded_ciphertext(plain.parms_id(), plain.is_scalar() ? nullptr : plain.device_data());
+            if (plain.is_scalar())
+            {
+                util::hip_check(moai_add_scalar_rows(context_.device(), o.head.block->get(), plain.scalar_rows().data(), o.head.block->get(),
+                                                     1, L, context_.stream()));
+            }
+            o.head.scale = plain.scale();
+            context_.sync();
+            return Serializable<Ciphertext>(std::move(o));
+        }
+        Serializable<Ciphertext> encrypt_zero_symmetric(parms_id_type parms_id, MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            wire::Object o = seeded_ciphertext(parms_id, nullptr);
+            context_.sync();
+            return Serializable<Ciphertext>(std::move(o));
+        }
+        Serializable<Ciphertext> encrypt_zero_symmetric(MemoryPoolHandle = MemoryPoolHandle()) const
+        {
+            return encrypt_zero_symmetric(context_.first_parms_id());
+        }
         // ---- for moai_fused (not part of the reference API) ----------------------------------------------------------------
         // the key-level public key [2][k][N] on the device, null when none is set
         const std::uint64_t *public_key_device() const
         {
             return pk_.size() ? pk_.device_data() : nullptr;
+        }
+        // the secret key in NTT form over all primes, [k][N] on the device, null when none is set
+        const std::uint64_t *secret_key_device() const
+        {
+            return sk_ ? sk_->get() : nullptr;
         }
         const SEALContext &context() const
         {
@@ -1095,6 +1257,35 @@ namespace seal
         }
 
     private:
+        wire::Object seeded_ciphertext(parms_id_type parms_id, const std::uint64_t *plain) const
+        {
+            auto cd = context_.get_context_data(parms_id);
+            if (!cd)
+            {
+                throw std::invalid_argument("parms_id is not valid for encryption parameters");
+            }
+            if (!sk_)
+            {
+                throw std::logic_error("secret key is not set");
+            }
+            const std::size_t L = cd->parms().coeff_modulus().size();
+            wire::Object o;
+            o.dev = context_.device();
+            o.stream = context_.stream();
+            wire::Record &r = o.head;
+            r.kind = wire::kind_ciphertext;
+            r.flags = wire::flag_ntt | wire::flag_seeded;
+            r.count = 2;
+            r.L = static_cast<std::uint32_t>(L);
+            r.parms_id = parms_id;
+            r.seq = rng_->take(1);
+            util::public_seed(rng_->key(), r.seq, r.seed);
+            r.block = std::make_shared<util::DeviceArray>(L * context_.n(), context_.stream());
+            util::hip_check(moai_encrypt_symmetric_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_->get(), plain, r.block->get(),
+                                                          1, L, nullptr, context_.stream()));
+            r.data = r.block->get();
+            return o;
+        }
         void encrypt_symmetric_device(parms_id_type parms_id, const std::uint64_t *plain, Ciphertext &destination) const
         {
             auto cd = context_.get_context_data(parms_id);

@@ -1,0 +1,503 @@
+// seal/moai_serialization.h -- the wire form of the seal:: surface: save / load / save_size with SEAL's signatures
+// (SEAL/serialization.h, SEAL/serializable.h) over this library's own format.  Included from seal/seal.h.
+//
+// The format is NOT SEAL's and cannot be: SEAL expands seeds with Blake2xb / Shake256 (SEAL/randomgen.cpp), this library with
+// ChaCha20 (include/moai_hip.h, "Stream contract"); the shim's parms_id is its own hash; SEAL has no packed rows.  DESIGN.md
+// section 5.0e specifies it completely and tests/wire_format.py restates it.  In short, little-endian and 8-byte aligned:
+//
+//   record  = header (120 bytes) + stored x packed polynomial          (moai_pack_rows: every row at its prime's bit length)
+//   header  = magic "MOAIWIRE", u32 version (1), u32 kind, u32 flags (1 seeded, 2 NTT form), u32 polynomial count, u32 N, u32 L,
+//             u64 total bytes, f64 scale, u64 parms_id[4], u64 first sequence, u8 seed[32]
+//   seeded  : the odd polynomials (c1 of a ciphertext, of every key digit) are not stored; polynomial 2 b + 1 is
+//             uniform(seed, 1 << 56 | first sequence + b) (moai_expand_seeded), so stored = count / 2
+//   key set = header (kind 5 / 6 / 7, count = number of keys, total = the whole set) + u64 index[count] + one record of kind 9
+//             (count = 2 (k - 1) polynomials of k rows) per key
+//
+// Everything that touches residues runs on the device: pack + one device-to-host copy on save; one host-to-device copy +
+// unpack (with the residue check of is_data_valid_for folded in) + expand on load.
+#pragma once
+#include <cstddef>
+
+namespace seal
+{
+    namespace wire
+    {
+        constexpr std::uint32_t version = 1;
+        constexpr std::uint32_t kind_ciphertext = 1, kind_plaintext = 2, kind_public_key = 3, kind_secret_key = 4, kind_kswitch_keys = 5,
+                                kind_relin_keys = 6, kind_galois_keys = 7, kind_encryption_parameters = 8, kind_kswitch_key = 9;
+        constexpr std::uint32_t flag_seeded = 1, flag_ntt = 2;
+
+        struct Header
+        {
+            char magic[8];
+            std::uint32_t version, kind, flags, count, n, L;
+            std::uint64_t total;
+            double scale;
+            std::uint64_t parms_id[4];
+            std::uint64_t seq;
+            std::uint8_t seed[32];
+        };
+        static_assert(sizeof(Header) == 120, "the wire header is 120 bytes without padding");
+
+        // one record in memory: `count` polynomials of L rows, of which stored() are on the device at `data`
+        struct Record
+        {
+            std::uint32_t kind = 0, flags = 0, count = 0, L = 0;
+            double scale = 1.0;
+            parms_id_type parms_id = parms_id_zero;
+            std::uint64_t seq = 0;
+            std::uint8_t seed[32] = {};
+            std::shared_ptr<util::DeviceArray> block; // owner of `data`, where the record has one of its own
+            const std::uint64_t *data = nullptr;      // device [stored()][L][N]; after a load: all `count` polynomials
+            std::size_t stored() const
+            {
+                return (flags & flag_seeded) ? count / 2 : count;
+            }
+        };
+        // what save writes and load reads: one record, or a key set
+        struct Object
+        {
+            Record head;
+            bool is_set = false;
+            std::vector<std::uint64_t> indices;
+            std::vector<Record> keys;
+            moai_ctx *dev = nullptr;
+            void *stream = nullptr;
+        };
+
+        inline void check_mode(compr_mode_type m)
+        {
+            if (m != compr_mode_type::none)
+            {
+                throw std::invalid_argument("unsupported compression mode"); // SEAL/serialization.cpp:89,107
+            }
+        }
+
+        // ---- where bytes go and come from -------------------------------------------------------------------------------
+        struct Sink
+        {
+            virtual ~Sink() = default;
+            virtual void put(const void *p, std::size_t bytes) = 0;
+            virtual std::uint8_t *space(std::size_t bytes) = 0; // to be filled by a device-to-host copy, then commit()
+            virtual void commit() = 0;
+        };
+        struct BufferSink : Sink
+        {
+            std::uint8_t *out;
+            std::size_t size, pos = 0;
+            BufferSink(seal_byte *o, std::size_t s) : out(reinterpret_cast<std::uint8_t *>(o)), size(s)
+            {
+                if (!o)
+                {
+                    throw std::invalid_argument("out cannot be null"); // SEAL/serialization.cpp:189-217
+                }
+            }
+            void put(const void *p, std::size_t bytes) override
+            {
+                std::memcpy(space(bytes), p, bytes);
+            }
+            std::uint8_t *space(std::size_t bytes) override
+            {
+                if (bytes > size - pos)
+                {
+                    throw std::invalid_argument("buffer is too small");
+                }
+                pos += bytes;
+                return out + pos - bytes;
+            }
+            void commit() override
+            {}
+        };
+        struct StreamSink : Sink
+        {
+            std::ostream &s;
+            std::vector<std::uint8_t> tmp;
+            explicit StreamSink(std::ostream &o) : s(o)
+            {}
+            void put(const void *p, std::size_t bytes) override
+            {
+                s.write(static_cast<const char *>(p), static_cast<std::streamsize>(bytes));
+                if (!s)
+                {
+                    throw std::runtime_error("I/O error"); // SEAL/serialization.cpp:55-80
+                }
+            }
+            std::uint8_t *space(std::size_t bytes) override
+            {
+                tmp.resize(bytes);
+                return tmp.data();
+            }
+            void commit() override
+            {
+                put(tmp.data(), tmp.size());
+                tmp.clear();
+            }
+        };
+        struct Source
+        {
+            virtual ~Source() = default;
+            virtual const std::uint8_t *view(std::size_t bytes) = 0; // valid until the next call
+            std::size_t consumed = 0;
+        };
+        struct BufferSource : Source
+        {
+            const std::uint8_t *in;
+            std::size_t size;
+            BufferSource(const seal_byte *i, std::size_t s) : in(reinterpret_cast<const std::uint8_t *>(i)), size(s)
+            {
+                if (!i)
+                {
+                    throw std::invalid_argument("in cannot be null");
+                }
+            }
+            const std::uint8_t *view(std::size_t bytes) override
+            {
+                if (bytes > size - consumed)
+                {
+                    throw std::invalid_argument("buffer is too small");
+                }
+                consumed += bytes;
+                return in + consumed - bytes;
+            }
+        };
+        struct StreamSource : Source
+        {
+            std::istream &s;
+            std::vector<std::uint8_t> tmp;
+            explicit StreamSource(std::istream &i) : s(i)
+            {}
+            const std::uint8_t *view(std::size_t bytes) override
+            {
+                // in steps, so that a header that lies about its size cannot make this allocate what the stream never delivers
+                tmp.clear();
+                while (tmp.size() < bytes)
+                {
+                    const std::size_t step = std::min<std::size_t>(bytes - tmp.size(), std::size_t(1) << 26);
+                    const std::size_t at = tmp.size();
+                    tmp.resize(at + step);
+                    s.read(reinterpret_cast<char *>(tmp.data() + at), static_cast<std::streamsize>(step));
+                    if (static_cast<std::size_t>(s.gcount()) != step)
+                    {
+                        throw std::runtime_error("I/O error: input stream ended unexpectedly"); // SEAL/serialization.cpp:71-76
+                    }
+                }
+                consumed += bytes;
+                return tmp.data();
+            }
+        };
+
+        // ---- sizes --------------------------------------------------------------------------------------------------------
+        inline std::size_t packed_words(moai_ctx *dev, std::size_t L)
+        {
+            const std::size_t w = moai_packed_words(dev, L, nullptr);
+            if (!w)
+            {
+                throw std::logic_error(moai_last_error());
+            }
+            return w;
+        }
+        inline std::size_t record_bytes(moai_ctx *dev, const Record &r)
+        {
+            return sizeof(Header) + (r.stored() ? r.stored() * packed_words(dev, r.L) * 8 : 0);
+        }
+        inline std::size_t object_bytes(const Object &o)
+        {
+            if (!o.is_set)
+            {
+                return record_bytes(o.dev, o.head);
+            }
+            std::size_t b = sizeof(Header) + 8 * o.indices.size();
+            for (auto &k : o.keys)
+            {
+                b += record_bytes(o.dev, k);
+            }
+            return b;
+        }
+
+        // ---- save -----------------------------------------------------------------------------------------------------------
+        inline Header make_header(const Record &r, std::size_t n, std::size_t total)
+        {
+            Header h;
+            std::memset(&h, 0, sizeof(h));
+            std::memcpy(h.magic, "MOAIWIRE", 8);
+            h.version = version;
+            h.kind = r.kind;
+            h.flags = r.flags;
+            h.count = r.count;
+            h.n = static_cast<std::uint32_t>(n);
+            h.L = r.L;
+            h.total = total;
+            h.scale = r.scale;
+            std::copy(r.parms_id.begin(), r.parms_id.end(), h.parms_id);
+            h.seq = r.seq;
+            std::memcpy(h.seed, r.seed, 32);
+            return h;
+        }
+        inline void put_record(const Object &o, const Record &r, Sink &sink)
+        {
+            const std::size_t n = moai_ctx_coeff_count(o.dev);
+            const Header h = make_header(r, n, record_bytes(o.dev, r));
+            sink.put(&h, sizeof(h));
+            if (!r.stored())
+            {
+                return;
+            }
+            // the whole record in one moai_pack_rows and one device-to-host copy
+            const std::size_t words = r.stored() * packed_words(o.dev, r.L);
+            util::DeviceArray packed(words, o.stream);
+            util::hip_check(moai_pack_rows(o.dev, r.data, packed.get(), r.stored(), r.L, nullptr, o.stream));
+            std::uint8_t *dst = sink.space(words * 8);
+            util::hip_check(moai_memcpy_d2h(dst, packed.get(), words * 8, o.stream));
+            util::hip_check(moai_stream_sync(o.stream));
+            sink.commit();
+        }
+        inline std::streamoff save_object(const Object &o, Sink &sink)
+        {
+            if (!o.dev)
+            {
+                throw std::logic_error("object is empty or its context is gone");
+            }
+            const std::size_t total = object_bytes(o);
+            if (!o.is_set)
+            {
+                put_record(o, o.head, sink);
+                return static_cast<std::streamoff>(total);
+            }
+            const Header h = make_header(o.head, moai_ctx_coeff_count(o.dev), total);
+            sink.put(&h, sizeof(h));
+            sink.put(o.indices.data(), 8 * o.indices.size());
+            for (auto &k : o.keys)
+            {
+                put_record(o, k, sink);
+            }
+            return static_cast<std::streamoff>(total);
+        }
+
+        // ---- load -----------------------------------------------------------------------------------------------------------
+        // SEAL/serialization.cpp:365-383: anything unknown is an error, never a guess
+        inline Header get_header(Source &src)
+        {
+            Header h;
+            std::memcpy(&h, src.view(sizeof(Header)), sizeof(Header));
+            if (std::memcmp(h.magic, "MOAIWIRE", 8) != 0)
+            {
+                throw std::logic_error("loaded header is invalid: not a moai wire record");
+            }
+            if (h.version != version)
+            {
+                throw std::logic_error("incompatible version");
+            }
+            if (h.kind < 1 || h.kind > 9 || (h.flags & ~(flag_seeded | flag_ntt)) || h.seq >> 56 || h.total < sizeof(Header))
+            {
+                throw std::logic_error("loaded header is invalid");
+            }
+            bool any_seed = h.seq != 0;
+            for (int i = 0; i < 32; i++)
+            {
+                any_seed = any_seed || h.seed[i];
+            }
+            if (!(h.flags & flag_seeded) && any_seed)
+            {
+                throw std::logic_error("loaded header is invalid");
+            }
+            return h;
+        }
+        // the header's claims against the context: N, a parms_id the context knows, the row count of that level
+        inline void check_against(const SEALContext &context, const Header &h, std::uint32_t kind, const char *what)
+        {
+            parms_id_type id = { h.parms_id[0], h.parms_id[1], h.parms_id[2], h.parms_id[3] };
+            auto cd = context.get_context_data(id);
+            if (h.kind != kind || h.n != context.n() || !cd || cd->parms().coeff_modulus().size() != h.L ||
+                ((h.flags & flag_seeded) && (h.count & 1)))
+            {
+                throw std::logic_error(std::string(what) + " data is invalid"); // SEAL/ciphertext.cpp:302,358
+            }
+        }
+        inline Record get_record(const SEALContext &context, Source &src, std::uint32_t kind, const char *what, bool check, std::size_t max_count)
+        {
+            const Header h = get_header(src);
+            check_against(context, h, kind, what);
+            Record r;
+            r.kind = h.kind;
+            r.flags = h.flags;
+            r.count = h.count;
+            r.L = h.L;
+            r.scale = h.scale;
+            r.parms_id = { h.parms_id[0], h.parms_id[1], h.parms_id[2], h.parms_id[3] };
+            r.seq = h.seq;
+            std::memcpy(r.seed, h.seed, 32);
+            if (r.count < 1 || r.count > max_count || h.total != record_bytes(context.device(), r))
+            {
+                throw std::logic_error(std::string(what) + " data is invalid");
+            }
+            moai_ctx *dev = context.device();
+            void *st = context.stream();
+            const std::size_t n = context.n(), stored = r.stored(), LN = r.L * n;
+            const std::size_t words = stored * packed_words(dev, r.L);
+            const std::uint8_t *bytes = src.view(words * 8);
+            util::DeviceArray packed(words, st), flag(1, st);
+            util::hip_check(moai_memcpy_h2d(packed.get(), bytes, words * 8, st));
+            auto out = std::make_shared<util::DeviceArray>(r.count * LN, st);
+            std::uint64_t bad = 0;
+            if (check)
+            {
+                util::hip_check(moai_memset_zero(flag.get(), 8, st));
+            }
+            std::uint32_t *dflag = check ? reinterpret_cast<std::uint32_t *>(flag.get()) : nullptr;
+            if (r.flags & flag_seeded)
+            {
+                util::DeviceArray c0(stored * LN, st);
+                util::hip_check(moai_unpack_rows(dev, packed.get(), c0.get(), stored, r.L, nullptr, dflag, st));
+                util::hip_check(moai_expand_seeded(dev, r.seed, r.seq, c0.get(), out->get(), stored, r.L, nullptr, st));
+            }
+            else
+            {
+                util::hip_check(moai_unpack_rows(dev, packed.get(), out->get(), stored, r.L, nullptr, dflag, st));
+            }
+            if (check)
+            {
+                util::hip_check(moai_memcpy_d2h(&bad, flag.get(), 8, st));
+            }
+            context.sync();
+            if (bad)
+            {
+                throw std::logic_error(std::string(what) + " data is invalid"); // a residue >= its prime
+            }
+            r.block = out;
+            r.data = out->get();
+            return r;
+        }
+        inline Object load_object(const SEALContext &context, Source &src, std::uint32_t kind, const char *what, bool check)
+        {
+            Object o;
+            o.dev = context.device();
+            o.stream = context.stream();
+            const std::size_t k = context.key_context_data()->parms().coeff_modulus().size();
+            if (kind != kind_kswitch_keys && kind != kind_relin_keys && kind != kind_galois_keys)
+            {
+                o.head = get_record(context, src, kind, what, check, kind == kind_ciphertext ? 6 : (kind == kind_public_key ? 2 : 1));
+                return o;
+            }
+            o.is_set = true;
+            const Header h = get_header(src);
+            check_against(context, h, kind, what);
+            parms_id_type id = { h.parms_id[0], h.parms_id[1], h.parms_id[2], h.parms_id[3] };
+            if (id != context.key_parms_id() || h.count > context.n() || (h.flags & flag_seeded) || k < 2)
+            {
+                throw std::logic_error(std::string(what) + " data is invalid");
+            }
+            o.head.kind = h.kind;
+            o.head.flags = h.flags;
+            o.head.count = h.count;
+            o.head.L = h.L;
+            o.head.parms_id = id;
+            o.indices.resize(h.count);
+            if (h.count)
+            {
+                std::memcpy(o.indices.data(), src.view(8 * h.count), 8 * h.count);
+            }
+            for (std::size_t i = 0; i < o.indices.size(); i++)
+            {
+                if (o.indices[i] >= context.n() || (i && o.indices[i] <= o.indices[i - 1]))
+                {
+                    throw std::logic_error(std::string(what) + " data is invalid");
+                }
+            }
+            for (std::size_t i = 0; i < o.indices.size(); i++)
+            {
+                Record r = get_record(context, src, kind_kswitch_key, what, check, 2 * (k - 1));
+                if (r.count != 2 * (k - 1) || r.parms_id != id)
+                {
+                    throw std::logic_error(std::string(what) + " data is invalid");
+                }
+                o.keys.push_back(std::move(r));
+            }
+            if (src.consumed != h.total)
+            {
+                throw std::logic_error(std::string(what) + " data is invalid");
+            }
+            return o;
+        }
+    } // namespace wire
+
+    // SEAL/serializable.h: an object that can only be saved -- what the seeded encryptions and key generators return.  It holds
+    // c0 of every ciphertext or key digit and the public seed; the uniform halves are never produced on this side.
+    template <class T>
+    class Serializable
+    {
+    public:
+        std::streamoff save_size(compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            return static_cast<std::streamoff>(wire::object_bytes(obj_));
+        }
+        std::streamoff save(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            wire::StreamSink s(stream);
+            return wire::save_object(obj_, s);
+        }
+        std::streamoff save(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            wire::BufferSink s(out, size);
+            return wire::save_object(obj_, s);
+        }
+
+    private:
+        friend class Encryptor;
+        friend class KeyGenerator;
+        explicit Serializable(wire::Object o) : obj_(std::move(o))
+        {}
+        wire::Object obj_;
+    };
+
+// save / load with SEAL's signatures (SEAL/ciphertext.h:560-720 and the same block of every other type) over two hooks each
+// type defines in seal/moai_serialization_impl.h: to_wire() settles lazy state and describes the object without changing it,
+// from_wire() validates what is specific to the type and only then replaces *this (a failed load leaves it as it was)
+#define MOAI_WIRE_METHODS(KIND)                                                                                         \
+    std::streamoff save_size(compr_mode_type compr_mode = compr_mode_default) const                                     \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        return static_cast<std::streamoff>(wire::object_bytes(to_wire()));                                              \
+    }                                                                                                                   \
+    std::streamoff save(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const                    \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        wire::StreamSink s(stream);                                                                                     \
+        return wire::save_object(to_wire(), s);                                                                         \
+    }                                                                                                                   \
+    std::streamoff save(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const        \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        wire::BufferSink s(out, size);                                                                                  \
+        return wire::save_object(to_wire(), s);                                                                         \
+    }                                                                                                                   \
+    std::streamoff load(const SEALContext &context, std::istream &stream)                                               \
+    {                                                                                                                   \
+        wire::StreamSource s(stream);                                                                                   \
+        return load_from(context, s, true);                                                                             \
+    }                                                                                                                   \
+    std::streamoff load(const SEALContext &context, const seal_byte *in, std::size_t size)                              \
+    {                                                                                                                   \
+        wire::BufferSource s(in, size);                                                                                 \
+        return load_from(context, s, true);                                                                             \
+    }                                                                                                                   \
+    std::streamoff unsafe_load(const SEALContext &context, std::istream &stream)                                        \
+    {                                                                                                                   \
+        wire::StreamSource s(stream);                                                                                   \
+        return load_from(context, s, false);                                                                            \
+    }                                                                                                                   \
+    std::streamoff unsafe_load(const SEALContext &context, const seal_byte *in, std::size_t size)                       \
+    {                                                                                                                   \
+        wire::BufferSource s(in, size);                                                                                 \
+        return load_from(context, s, false);                                                                            \
+    }                                                                                                                   \
+    wire::Object to_wire() const;                                                                                       \
+    void from_wire(const SEALContext &context, wire::Object &&o);                                                       \
+    std::streamoff load_from(const SEALContext &context, wire::Source &s, bool check)                                   \
+    {                                                                                                                   \
+        from_wire(context, wire::load_object(context, s, KIND, "loaded", check));                                       \
+        return static_cast<std::streamoff>(s.consumed);                                                                 \
+    }
+} // namespace seal

@@ -27,14 +27,17 @@
 #include <array>
 #include <cmath>
 #include <complex>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <istream>
 #include <iterator>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <ostream>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -64,6 +67,17 @@ namespace seal
         tc192 = 192,
         tc256 = 256
     };
+
+    // SEAL/defines.h seal_byte, SEAL/serialization.h:25-40 compr_mode_type.  The wire form (seal/moai_serialization.h) provides
+    // `none` only; the other two are rejected as SEAL built without zlib / zstd does (SEAL/serialization.cpp:89,107)
+    using seal_byte = std::byte;
+    enum class compr_mode_type : std::uint8_t
+    {
+        none = 0,
+        zlib = 1,
+        zstd = 2
+    };
+    constexpr compr_mode_type compr_mode_default = compr_mode_type::none;
 
     // ---- memory pool handles: accepted and ignored (device memory comes from the moai arena) --------
     class MemoryPoolHandle
@@ -583,6 +597,11 @@ namespace seal
             {
                 return words_;
             }
+            // the stream the block is used on (seal/moai_serialization.h finds the device context of a key by it)
+            void *stream() const
+            {
+                return stream_;
+            }
 
         private:
             std::uint64_t *ptr_ = nullptr;
@@ -701,6 +720,26 @@ namespace seal
         {
             static std::mutex m;
             return m;
+        }
+        // stream of a live SEALContext -> its device context.  save() has SEAL's signature, without a context; a key or a
+        // plaintext knows the stream its blocks are used on, and that names the context (seal/moai_serialization.h)
+        inline moai_ctx *stream_device(void *stream, moai_ctx *set = nullptr, bool erase = false)
+        {
+            static std::mutex mu;
+            static std::map<void *, moai_ctx *> by_stream;
+            std::lock_guard<std::mutex> g(mu);
+            if (erase)
+            {
+                by_stream.erase(stream);
+                return nullptr;
+            }
+            if (set)
+            {
+                by_stream[stream] = set;
+                return set;
+            }
+            auto it = by_stream.find(stream);
+            return it == by_stream.end() ? nullptr : it->second;
         }
         // Small host -> device copies whose source must be free again when the call returns (a constant, a few hundred of them):
         // through a per-thread ring of page-locked slots; a slot is reused only after the event recorded behind its last copy
@@ -1088,6 +1127,12 @@ namespace seal
         {
             return sparse_slots_;
         }
+        // ---- wire form (seal/moai_serialization.h; SEAL/encryptionparams.h:383-470) ----------------------------------
+        std::streamoff save_size(compr_mode_type compr_mode = compr_mode_default) const;
+        std::streamoff save(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const;
+        std::streamoff save(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const;
+        std::streamoff load(std::istream &stream);
+        std::streamoff load(const seal_byte *in, std::size_t size);
 
     private:
         scheme_type scheme_;
@@ -1173,6 +1218,7 @@ namespace seal
             util::hip_check(moai_ctx_create(logn, primes.data(), primes.size(), 0, &c));
             impl_->ctx = c;
             util::hip_check(moai_stream_create(&impl_->stream));
+            util::stream_device(impl_->stream, c);
             const std::size_t k = cm.size();
             // chain: key level (k primes), then data levels with k-1 ... 1 primes
             std::shared_ptr<ContextData> prev;
@@ -1302,6 +1348,7 @@ namespace seal
             {
                 if (stream)
                 {
+                    util::stream_device(stream, nullptr, true);
                     moai_stream_sync(stream);
                     moai_stream_destroy(stream);
                 }
@@ -1314,6 +1361,12 @@ namespace seal
         std::shared_ptr<Impl> impl_;
     };
 
+} // namespace seal
+
+#include "seal/moai_serialization.h"
+
+namespace seal
+{
     // =================================================================================================
     // Plaintext / Ciphertext
     // =================================================================================================
@@ -1415,6 +1468,7 @@ namespace seal
         {
             return owed_.v.load(std::memory_order_acquire);
         }
+        MOAI_WIRE_METHODS(wire::kind_plaintext)
 
     private:
         friend class CKKSEncoder;
@@ -1641,12 +1695,14 @@ namespace seal
             util::hip_check(moai_memcpy_h2d(device_data(), h.data(), h.size() * 8, stream_));
             util::hip_check(moai_stream_sync(stream_));
         }
+        MOAI_WIRE_METHODS(wire::kind_ciphertext)
 
     private:
         friend class Evaluator;
         friend class Encryptor;
         friend class Decryptor;
         friend class KeyGenerator;
+        friend class PublicKey;
         // metadata-only change of level / size after the device op produced the new layout
         void set_layout(void *stream, parms_id_type id, std::size_t size, std::size_t L, std::size_t n)
         {
@@ -1835,6 +1891,7 @@ namespace seal
         {
             return parms_id_;
         }
+        MOAI_WIRE_METHODS(wire::kind_secret_key)
 
     private:
         friend class KeyGenerator;
@@ -1855,6 +1912,7 @@ namespace seal
         {
             return ct_;
         }
+        MOAI_WIRE_METHODS(wire::kind_public_key)
 
     private:
         friend class KeyGenerator;
@@ -1964,8 +2022,12 @@ namespace seal
         {
             return generation_;
         }
+        MOAI_WIRE_METHODS(wire::kind_kswitch_keys)
 
     protected:
+        // the object kind on the wire, and the number of key slots of an empty set (GaloisKeys: N, SEAL/galoiskeys.h:48)
+        wire::Object set_to_wire(std::uint32_t kind) const;
+        void set_from_wire(const SEALContext &context, wire::Object &&o, std::size_t min_slots);
         friend class KeyGenerator;
         static std::uint64_t next_generation()
         {
@@ -2007,6 +2069,7 @@ namespace seal
         {
             return device_key(get_index(key_power)) != nullptr;
         }
+        MOAI_WIRE_METHODS(wire::kind_relin_keys)
     };
 
     class GaloisKeys : public KSwitchKeys
@@ -2024,6 +2087,7 @@ namespace seal
         {
             return device_key(get_index(galois_elt)) != nullptr;
         }
+        MOAI_WIRE_METHODS(wire::kind_galois_keys)
     };
     inline void KSwitchKeys::limit_to_chain_index(const SEALContext &context, std::size_t chain_index, bool keep_host_copy)
     {
@@ -2133,4 +2197,5 @@ namespace seal
 
 #include "seal/moai_combiner.h"
 #include "seal/moai_client.h"
+#include "seal/moai_serialization_impl.h"
 #include "seal/moai_evaluator.h"
