@@ -471,10 +471,30 @@ int moai_expand_seeded(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const u
                        const uint32_t *prime_index, void *stream);
 
 /* ---- tuning -------------------------------------------------------------------------------------------------------
- * Overrides a performance knob for the whole process (same names as the environment variables read by the
- * library, which it takes precedence over).  Results never depend on these.  Currently:
- *   MOAI_KS_FP_MIN_ROWS  batch * L from which the key switch uses the FP64 arithmetic modes (default 16) */
+ * moai_set_tuning overrides a performance knob for the whole process; it takes precedence over the environment variable
+ * of the same name, which the library reads once, on its first use of a knob.  moai_reset_tuning drops every override, so
+ * that the environment's value, else the default, applies again.  A name that is not in this list is MOAI_EINVAL.
+ * Results never depend on a knob.  Name, default, meaning:
+ *   MOAI_NTT_FP            1     0: primes below 2^51 stay on the integer units in every transform, key switch and mod-down
+ *   MOAI_NTT_LAZY8         1     0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient
+ *   MOAI_NTT_LDSTW         1     0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS
+ *   MOAI_NTT_CHUNK_MB      0     > 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB
+ *   MOAI_NTT_NAIVE         0     1: one launch per radix-2 stage over global memory (cross-check path)
+ *   MOAI_NTT_COOP          0     1: the single-launch persistent transform (N >= 4096)
+ *   MOAI_NTT_COOP_WPC      4     single-launch transform: workgroups per compute unit
+ *   MOAI_NTT_COOP_DELAY    4     single-launch transform: rows a second pass stays behind the first
+ *   MOAI_NTT_COOP_OCC      4     single-launch transform: occupancy the kernel is compiled for (3 or 4)
+ *   MOAI_KS_FP_MIN_ROWS    16    batch * L from which the key switch uses the FP64 arithmetic modes
+ *   MOAI_KS_TMP_MB         8192  MiB of key-switch digits in flight: sets how many output moduli share a launch
+ *   MOAI_KS_P1_ITEMS       8     1: the key switch's strided pass at N = 2^16 runs one tile per workgroup instead of eight, pipelined
+ *   MOAI_KS_P1_PRE         0     1: the M_FPN strided pass of the key switch takes its twiddles as plain doubles
+ *   MOAI_KS_MAC_PF         1     key residues of the FP64 key-switch MAC: 0 loaded next to their use, 1 at its head, 2 at the digit's head
+ *   MOAI_KS_HOIST_PAIR     4     rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one
+ *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
+ *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
+ *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller */
 int moai_set_tuning(const char *name, long value);
+int moai_reset_tuning(void);
 
 /* ---- hoisted rotations -------------------------------------------------------------------------------------------
  * out[r] = apply_galois(in, galois_elts[r], galois_keys[r]) for r < R -- R calls of Evaluator::rotate_vector /

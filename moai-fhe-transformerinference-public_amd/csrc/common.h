@@ -63,6 +63,17 @@ int set_error(int code, const char *fmt, ...);
 
 #define MOAI_LAUNCH_CHECK() MOAI_HIP_CHECK(hipGetLastError())
 
+// returns a MOAI_* code other than MOAI_OK to the caller
+#define MOAI_TRY(expr)        \
+    do                        \
+    {                         \
+        int _rc = (expr);     \
+        if (_rc)              \
+        {                     \
+            return _rc;       \
+        }                     \
+    } while (0)
+
 // Stream audit (debug; MOAI_STREAM_AUDIT=1 or moai_debug_stream_audit(1)).  A caller that keeps device blocks in a
 // stream-ordered cache (the seal:: shim's util::DevicePool) labels every block with the stream it belongs to
 // (moai_debug_block_label); every entry point that enqueues work then checks that each device pointer it was handed

@@ -6,12 +6,13 @@
 // shared by every level of the modulus chain.
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <atomic>
 #include <mutex>
 #include <thread>
 
-#include "common.h"
+#include "launch.h"
 
 namespace moai {
 
@@ -31,8 +32,51 @@ const char *last_error()
     return g_err;
 }
 
-static std::mutex g_tuning_mu;
-static std::map<std::string, long> g_tuning;
+// ---- tuning knobs (launch.h MOAI_KNOBS) -----------------------------------------------------------------------------
+struct KnobRow
+{
+    const char *name;
+    long dflt;
+    const char *what;
+};
+static const KnobRow g_knob_rows[KNOB_COUNT] = {
+#define MOAI_KNOB_ROW(id, dflt, what) { "MOAI_" #id, dflt, what },
+    MOAI_KNOBS(MOAI_KNOB_ROW)
+#undef MOAI_KNOB_ROW
+};
+
+struct KnobTable
+{
+    long base[KNOB_COUNT];             // the environment's value, else the default
+    std::atomic<long> value[KNOB_COUNT]; // base, or what moai_set_tuning stored
+    KnobTable()
+    {
+        for (int k = 0; k < KNOB_COUNT; ++k)
+        {
+            const char *e = getenv(g_knob_rows[k].name);
+            base[k] = e ? atol(e) : g_knob_rows[k].dflt;
+        }
+        reset();
+    }
+    void reset()
+    {
+        for (int k = 0; k < KNOB_COUNT; ++k)
+        {
+            value[k].store(base[k], std::memory_order_relaxed);
+        }
+    }
+};
+
+static KnobTable &knobs()
+{
+    static KnobTable t; // the environment is read here, once
+    return t;
+}
+
+long tuning(Knob k)
+{
+    return knobs().value[k].load(std::memory_order_relaxed);
+}
 
 static std::atomic<int> g_trace_on{ 0 };
 static std::mutex g_trace_mu;
@@ -114,20 +158,6 @@ int enter_device(const moai_ctx *c)
 {
     MOAI_HIP_CHECK(hipSetDevice(c->device));
     return MOAI_OK;
-}
-
-long tuning(const char *name, long dflt)
-{
-    {
-        std::lock_guard<std::mutex> g(g_tuning_mu);
-        auto it = g_tuning.find(name);
-        if (it != g_tuning.end())
-        {
-            return it->second;
-        }
-    }
-    const char *e = getenv(name);
-    return e ? atol(e) : dflt;
 }
 
 typedef unsigned __int128 u128;
@@ -311,8 +341,20 @@ extern "C" int moai_set_tuning(const char *name, long value)
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    std::lock_guard<std::mutex> g(g_tuning_mu);
-    g_tuning[name] = value;
+    for (int k = 0; k < KNOB_COUNT; ++k)
+    {
+        if (!strcmp(name, g_knob_rows[k].name))
+        {
+            knobs().value[k].store(value, std::memory_order_relaxed);
+            return MOAI_OK;
+        }
+    }
+    return set_error(MOAI_EINVAL, "unknown tuning knob %s", name);
+}
+
+extern "C" int moai_reset_tuning(void)
+{
+    knobs().reset();
     return MOAI_OK;
 }
 

@@ -504,7 +504,7 @@ static void launch_head(double2 *data, const double2 *roots, uint32_t logn, uint
 static size_t dec_chunk(moai_ctx *c, hipStream_t s, size_t L, size_t n_batch)
 {
     const size_t per = c->n * (L * sizeof(uint64_t) + sizeof(double2));
-    long mb = tuning("MOAI_DEC_TMP_MB", 1024);
+    long mb = tuning(K_DEC_TMP_MB);
     size_t budget = (size_t)(mb < 1 ? 1 : mb) << 20;
     {
         std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));

@@ -2037,7 +2037,7 @@ extern "C" int moai_ct_pt_matmul(moai_ctx *c, const uint64_t *x, const uint64_t 
     g.wd = nullptr;
     dim3 grid((g.n2 + 255u) / 256u, (uint32_t)(size * L), (uint32_t)((cols + CG - 1) / CG));
     // exact FP64 sums when every prime of the level is below 2^51 (MOAI_MATMUL_FP=0: the integer kernel)
-    bool fp = tuning("MOAI_MATMUL_FP", 1) != 0;
+    bool fp = tuning(K_MATMUL_FP) != 0;
     for (size_t r = 0; r < L && fp; r++)
     {
         fp = c->primes[r] < (1ull << 51);

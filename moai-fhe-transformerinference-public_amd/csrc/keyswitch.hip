@@ -273,6 +273,15 @@ static inline size_t align256(size_t x)
     return (x + 255) & ~(size_t)255;
 }
 
+// f(LOGN, MODE) over the degrees and arithmetic modes that the key-switch and mod-down kernels are compiled for
+template <class F>
+static int dispatch_ks(int logn, int mode, F &&f)
+{
+    return dispatch_logn(logn, [&](auto LG) {
+        return dispatch<M_GUARD, M_NOGUARD, M_FPN, M_FPR>("key-switch arithmetic mode ", mode, [&](auto MD) { return f(LG, MD); });
+    });
+}
+
 // Shared tail of rescale and key switch: divide rows [0, Lout) of `acc` by the modulus `prime_last`
 // whose NTT-form row is `last_rows` ([P][N], overwritten), rounding to nearest.
 //   acc row (p, i) = acc + (p * acc_stride + i) * N ; out [P][Lout][N]
@@ -286,16 +295,8 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
 {
     RowMap rm;
     uint32_t pl = prime_last;
-    int rc = make_rowmap(c, 1, &pl, &rm);
-    if (rc)
-    {
-        return rc;
-    }
-    rc = ntt_launch(c, last_rows, P, 1, rm, true, s);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, 1, &pl, &rm));
+    MOAI_TRY(ntt_launch(c, last_rows, P, 1, rm, true, s));
     if (c->logn >= 12)
     {
         // fused: the expand rides on the strided pass's loads, the division on the contiguous pass's stores
@@ -304,8 +305,6 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
         a.u = u;
         a.acc = acc;
         a.out = out;
-        a.tw = c->fwd_tw;
-        a.twb = c->fwd_twb;
         a.pc = c->pc;
         a.inv_last = c->inv_qlast + (size_t)prime_last * c->k;
         a.prime_last = prime_last;
@@ -329,19 +328,13 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
         // one pair of launches per arithmetic mode present among the output moduli (ntt_mode); below
         // MOAI_MD_FP_MIN_ROWS rows the extra launches cost more than the FP64 butterflies save (a single
         // ciphertext at MOAI's top level: 162 vs 147 ms per bootstrap; packs of 16: 66.0 vs 67.1 ms)
-        const long fp_min_rows = tuning("MOAI_MD_FP_MIN_ROWS", 256);
-        const bool allow_fp = (long)(P * Lout) >= fp_min_rows;
+        const bool allow_fp = (long)(P * Lout) >= tuning(K_MD_FP_MIN_ROWS);
         for (int mode = M_GUARD; mode <= M_FPR; ++mode)
         {
             a.Lsel = 0;
             for (size_t i = 0; i < Lout; ++i)
             {
-                int m = ntt_mode(c, (uint32_t)i);
-                if (m >= M_FPN && !allow_fp)
-                {
-                    m = noguard_ok(c->primes[i]) ? M_NOGUARD : M_GUARD;
-                }
-                if (m == mode)
+                if (ntt_mode(c, (uint32_t)i, allow_fp) == mode)
                 {
                     a.sel.idx[a.Lsel++] = (uint32_t)i;
                 }
@@ -351,31 +344,14 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
                 continue;
             }
             a.total_work = (uint32_t)(P * a.Lsel * (c->n >> 12));
-            a.tw = mode >= M_FPN ? c->fwd_twf : c->fwd_tw;
-            a.twb = mode >= M_FPN ? c->fwd_twfb : c->fwd_twb;
-#define MOAI_MD_MODE(LG, MD)                                                                         \
-    hipLaunchKernelGGL((moddown_strided<LG, MD>), dim3(a.total_work), dim3(256), 0, s, a);           \
-    hipLaunchKernelGGL((moddown_contig<LG, MD>), dim3(a.total_work), dim3(256), 0, s, a);
-#define MOAI_MD_CASE(LG)                                     \
-    case LG:                                                 \
-        switch (mode)                                        \
-        {                                                    \
-        case M_GUARD: MOAI_MD_MODE(LG, M_GUARD) break;       \
-        case M_NOGUARD: MOAI_MD_MODE(LG, M_NOGUARD) break;   \
-        case M_FPN: MOAI_MD_MODE(LG, M_FPN) break;           \
-        default: MOAI_MD_MODE(LG, M_FPR) break;              \
-        }                                                    \
-        break;
-            switch (c->logn)
-            {
-                MOAI_MD_CASE(12)
-                MOAI_MD_CASE(13)
-                MOAI_MD_CASE(14)
-                MOAI_MD_CASE(15)
-                MOAI_MD_CASE(16)
-            }
-#undef MOAI_MD_CASE
-#undef MOAI_MD_MODE
+            const TwPair t = twiddles(c, mode, false);
+            a.tw = t.tw;
+            a.twb = t.twb;
+            MOAI_TRY(dispatch_ks(c->logn, mode, [&](auto LG, auto MD) {
+                hipLaunchKernelGGL((moddown_strided<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
+                return MOAI_OK;
+            }));
         }
         MOAI_LAUNCH_CHECK();
         return MOAI_OK;
@@ -394,16 +370,8 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
     MOAI_CHECK_GRID_ROWS(P * Lout);
     hipLaunchKernelGGL(expand_last_kernel, rgrid(c, P * Lout), dim3(256), 0, s, e);
     MOAI_LAUNCH_CHECK();
-    rc = make_rowmap(c, Lout, nullptr, &rm);
-    if (rc)
-    {
-        return rc;
-    }
-    rc = ntt_launch(c, u, P, Lout, rm, false, s);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, Lout, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, u, P, Lout, rm, false, s));
     FinalizeArgs f;
     f.acc = acc;
     f.u = u;
@@ -467,16 +435,12 @@ static int key_rows_for(moai_ctx *c, const uint64_t *key, size_t L, uint32_t *ro
     return MOAI_OK;
 }
 
-template <int LOGN>
-static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint64_t *key, uint64_t *acc, size_t L,
-                          size_t batch, const KsGroup &grp, size_t G, uint32_t splits, int mode, const KsTarget &tg, hipStream_t s);
-
 // number of output moduli whose digits are in flight at once: bounded by the scratch budget
 // (MOAI_KS_TMP_MB, default 8192 MiB) so that small batches expose (L+1) x 16 tiles of parallelism in
 // one launch while large batches stay within a few GiB of workspace
 static size_t ks_group_size(const moai_ctx *c, size_t L, size_t batch)
 {
-    long budget_mb = tuning("MOAI_KS_TMP_MB", 8192);
+    long budget_mb = tuning(K_KS_TMP_MB);
     if (budget_mb < 1)
     {
         budget_mb = 1;
@@ -530,22 +494,44 @@ static size_t ks_tmp_rows(const moai_ctx *c, size_t L, size_t batch)
     return fused > plain ? fused : plain;
 }
 
-static size_t switch_key_ws_bytes(const moai_ctx *c, size_t L, size_t batch)
+// workspace of one key switch, byte offsets: t [B][L][N] | ops, the digits in flight and later u [2B][L][N] |
+// acc [splits][B][2][L+1][N] | last [2B][N]
+struct KsLayout
+{
+    uint32_t splits;
+    size_t split_stride; // words from one partial accumulator to the next
+    size_t t, ops, acc, last, total;
+};
+
+static KsLayout ks_layout(const moai_ctx *c, size_t L, size_t batch)
 {
     const size_t row_bytes = c->n * sizeof(uint64_t);
-    return align256(batch * L * row_bytes) + align256(ks_tmp_rows(c, L, batch) * row_bytes) +
-           align256(ks_splits(c, L, batch) * batch * 2 * (L + 1) * row_bytes) + align256(batch * 2 * row_bytes);
+    KsLayout w;
+    w.splits = ks_splits(c, L, batch);
+    w.split_stride = batch * 2 * (L + 1) * c->n;
+    w.t = 0;
+    w.ops = w.t + align256(batch * L * row_bytes);
+    w.acc = w.ops + align256(ks_tmp_rows(c, L, batch) * row_bytes);
+    w.last = w.acc + align256(w.splits * w.split_stride * sizeof(uint64_t));
+    w.total = w.last + align256(batch * 2 * row_bytes);
+    return w;
+}
+
+static size_t switch_key_ws_bytes(const moai_ctx *c, size_t L, size_t batch)
+{
+    return ks_layout(c, L, batch).total;
+}
+
+static inline uint64_t *at_bytes(void *base, size_t offset)
+{
+    return reinterpret_cast<uint64_t *>(static_cast<char *>(base) + offset);
 }
 
 // which arithmetic the fused kernels use for output modulus `prime` (keyswitch_kernels.hip.h): the forward
 // transform's mode, with the integer no-guard form only when the lazy digit may also enter the MAC unreduced
 static int ks_mode(const moai_ctx *c, uint32_t prime, size_t L, bool allow_fp)
 {
-    int m = ntt_mode(c, prime);
-    if (m >= M_FPN && !allow_fp)
-    {
-        m = noguard_ok(c->primes[prime]) ? M_NOGUARD : M_GUARD;
-    }
+    const int m = ntt_mode(c, prime, allow_fp);
     if (m != M_NOGUARD)
     {
         return m;
@@ -556,15 +542,66 @@ static int ks_mode(const moai_ctx *c, uint32_t prime, size_t L, bool allow_fp)
     return lim < ((~(unsigned __int128)0) / (36 * (unsigned __int128)(L ? L : 1))) ? M_NOGUARD : M_GUARD;
 }
 
+// The launches of a key switch at L data primes: the output moduli (slot I = L stands for the special prime) ordered by
+// arithmetic mode, cut into groups of at most ks_group_size() moduli of one mode.  The unused entries of a KsGroup repeat its
+// first member.  Every mode is one more pair of launches: a few ciphertexts at a low level are launch-bound and stay on the
+// single integer group (measured: FP64 pays from about 16 digit rows per call, MOAI_KS_FP_MIN_ROWS).
+struct KsPlanGroup
+{
+    KsGroup grp;
+    size_t g; // members
+    int mode;
+};
+
+static std::vector<KsPlanGroup> ks_plan(const moai_ctx *c, size_t L, size_t batch)
+{
+    const size_t G = ks_group_size(c, L, batch);
+    const bool allow_fp = (long)(batch * L) >= tuning(K_KS_FP_MIN_ROWS);
+    const auto prime_of = [&](size_t Iidx) { return (uint32_t)(Iidx == L ? c->k - 1 : Iidx); };
+    std::vector<uint32_t> order;
+    std::vector<int> order_mode;
+    for (int mode = M_FPR; mode >= M_GUARD; --mode)
+    {
+        for (size_t Iidx = 0; Iidx <= L; ++Iidx)
+        {
+            if (ks_mode(c, prime_of(Iidx), L, allow_fp) == mode)
+            {
+                order.push_back((uint32_t)Iidx);
+                order_mode.push_back(mode);
+            }
+        }
+    }
+    std::vector<KsPlanGroup> plan;
+    for (size_t o0 = 0; o0 < order.size();)
+    {
+        KsPlanGroup pg;
+        pg.mode = order_mode[o0];
+        pg.g = 0;
+        while (o0 + pg.g < order.size() && pg.g < G && order_mode[o0 + pg.g] == pg.mode)
+        {
+            ++pg.g;
+        }
+        for (size_t i = 0; i < MOAI_MAX_RNS; ++i)
+        {
+            const size_t Iidx = order[o0 + (i < pg.g ? i : 0)];
+            pg.grp.prime[i] = prime_of(Iidx);
+            pg.grp.slot[i] = (uint32_t)Iidx;
+        }
+        plan.push_back(pg);
+        o0 += pg.g;
+    }
+    return plan;
+}
+
 template <int LOGN, int MODE>
-static int ks_fused_group_mode(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint64_t *key, uint64_t *acc, size_t L,
-                               size_t batch, const KsGroup &grp, size_t G, uint32_t splits, const KsTarget &tg, hipStream_t s)
+static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint64_t *key, uint64_t *acc, size_t L, size_t batch,
+                          const KsGroup &grp, size_t G, uint32_t splits, const KsTarget &tg, hipStream_t s)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
     KsP1Args p1;
     p1.t = t;
     p1.tmp = tmp;
-    p1.tw = MODE >= M_FPN ? c->fwd_twf : c->fwd_tw;
+    p1.tw = twiddles(c, MODE, false).tw;
     p1.pc = c->pc;
     p1.grp = grp;
     p1.L = (uint32_t)L;
@@ -574,11 +611,11 @@ static int ks_fused_group_mode(moai_ctx *c, const uint64_t *t, uint64_t *tmp, co
     // N = 2^16, FP64 modes, enough work to fill the chip that way: eight tiles per workgroup, software-pipelined
     // (fwd_strided_tiles; MOAI_KS_P1_ITEMS=1: one tile per workgroup)
     constexpr int P1_ITEMS = (LOGN == 16 && MODE >= M_FPN) ? 8 : 1;
-    if (P1_ITEMS > 1 && p1.total_work >= 8u * 2048u && tuning("MOAI_KS_P1_ITEMS", 8) > 1)
+    if (P1_ITEMS > 1 && p1.total_work >= 8u * 2048u && tuning(K_KS_P1_ITEMS) > 1)
     {
         hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE, false, P1_ITEMS>), dim3(p1.total_work / P1_ITEMS), dim3(256), 0, s, p1);
     }
-    else if (MODE == M_FPN && tuning("MOAI_KS_P1_PRE", 0))
+    else if (MODE == M_FPN && tuning(K_KS_P1_PRE))
     {
         hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE, MODE == M_FPN>), dim3(p1.total_work), dim3(256), 0, s, p1);
     }
@@ -594,7 +631,7 @@ static int ks_fused_group_mode(moai_ctx *c, const uint64_t *t, uint64_t *tmp, co
     p2.tgt_off = tg.off_rows;
     p2.key = key;
     p2.acc = acc;
-    p2.tw = MODE >= M_FPN ? c->fwd_twf : c->fwd_tw;
+    p2.tw = p1.tw;
     p2.tw1 = c->fwd_twf1;
     p2.pc = c->pc;
     p2.grp = grp;
@@ -609,7 +646,7 @@ static int ks_fused_group_mode(moai_ctx *c, const uint64_t *t, uint64_t *tmp, co
     // where the MAC fetches its key residues (keyswitch_kernels.hip.h): all eight loads at the head of the MAC by default --
     // same box, same hour, l = 35 / 15, batch 64: 0.572 / 0.134 ms per ciphertext with the compiler's placement (0), 0.532 / 0.121
     // with 1, 0.547 / 0.124 with 2 (profiles/r03_b_ks_kernel_variants_ab.txt)
-    const long pf = MODE >= M_FPN ? tuning("MOAI_KS_MAC_PF", 1) : 0;
+    const long pf = MODE >= M_FPN ? tuning(K_KS_MAC_PF) : 0;
     if (pf == 1)
     {
         hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 1 : 0)>), dim3(p2.total_work), dim3(256), 0, s, p2);
@@ -624,19 +661,6 @@ static int ks_fused_group_mode(moai_ctx *c, const uint64_t *t, uint64_t *tmp, co
     }
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
-}
-
-template <int LOGN>
-static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint64_t *key, uint64_t *acc, size_t L,
-                          size_t batch, const KsGroup &grp, size_t G, uint32_t splits, int mode, const KsTarget &tg, hipStream_t s)
-{
-    switch (mode)
-    {
-    case M_FPN: return ks_fused_group_mode<LOGN, M_FPN>(c, t, tmp, key, acc, L, batch, grp, G, splits, tg, s);
-    case M_FPR: return ks_fused_group_mode<LOGN, M_FPR>(c, t, tmp, key, acc, L, batch, grp, G, splits, tg, s);
-    case M_NOGUARD: return ks_fused_group_mode<LOGN, M_NOGUARD>(c, t, tmp, key, acc, L, batch, grp, G, splits, tg, s);
-    default: return ks_fused_group_mode<LOGN, M_GUARD>(c, t, tmp, key, acc, L, batch, grp, G, splits, tg, s);
-    }
 }
 
 // target row block of ciphertext b starts at target + (b * target_stride_rows + target_off_rows) * N.
@@ -657,108 +681,33 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
         return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
     }
     uint32_t key_rows = 0;
-    {
-        const int krc = key_rows_for(c, key, L, &key_rows);
-        if (krc)
-        {
-            return krc;
-        }
-    }
-    const size_t row_bytes = n * sizeof(uint64_t);
-    const size_t sz_t = align256(batch * L * row_bytes);
-    const size_t sz_ops = align256(ks_tmp_rows(c, L, batch) * row_bytes); // digits in flight; later u [2B][L][N]
-    const uint32_t splits = ks_splits(c, L, batch);
-    const size_t split_stride = batch * 2 * (L + 1) * n; // words
-    const size_t sz_acc = align256(splits * split_stride * sizeof(uint64_t));
-    uint64_t *t = static_cast<uint64_t *>(wsp);
-    uint64_t *ops = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + sz_t);
-    uint64_t *acc = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + sz_t + sz_ops);
-    uint64_t *last = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + sz_t + sz_ops + sz_acc);
+    MOAI_TRY(key_rows_for(c, key, L, &key_rows));
+    const KsLayout w = ks_layout(c, L, batch);
+    uint64_t *t = at_bytes(wsp, w.t), *ops = at_bytes(wsp, w.ops), *acc = at_bytes(wsp, w.acc), *last = at_bytes(wsp, w.last);
     const uint32_t n2 = (uint32_t)(n >> 1);
 
     // 1. t = INTT(target)      (evaluator.cpp:2804-2812)
     RowMap rm;
-    int rc = make_rowmap(c, L, nullptr, &rm);
-    if (rc)
-    {
-        return rc;
-    }
-    rc = ntt_launch(c, t, batch, L, rm, true, s, target, target_stride_rows, target_off_rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, target, target_stride_rows, target_off_rows));
     // 2. inner products per output modulus    (evaluator.cpp:2817-2911)
     if (c->logn >= 12)
     {
         // fused: "mod q_I" rides on the strided pass's loads, the key MAC on the contiguous pass
-        const size_t G = ks_group_size(c, L, batch);
-        if (batch * G * L * (n >> 11) > 0x7fffffffull)
+        if (batch * ks_group_size(c, L, batch) * L * (n >> 11) > 0x7fffffffull)
         {
             return set_error(MOAI_EINVAL, "batch too large for one launch");
         }
-        // output moduli (I = L stands for the special prime) ordered by arithmetic mode; a launch covers up to
-        // G of them, all of one mode
-        // every mode is one more pair of launches: a few ciphertexts at a low level are launch-bound and stay
-        // on the single integer group (measured: FP64 pays from about 16 digit rows per call)
-        const bool allow_fp = (long)(batch * L) >= tuning("MOAI_KS_FP_MIN_ROWS", 16);
         KsTarget tg;
         tg.ptr = target;
         tg.stride_rows = (uint32_t)target_stride_rows;
         tg.off_rows = (uint32_t)target_off_rows;
         tg.key_rows = key_rows;
-        std::vector<uint32_t> order;
-        std::vector<int> order_mode;
-        for (int mode = M_FPR; mode >= M_GUARD; --mode)
+        for (const KsPlanGroup &pg : ks_plan(c, L, batch))
         {
-            for (size_t Iidx = 0; Iidx <= L; ++Iidx)
-            {
-                const uint32_t prime = (uint32_t)(Iidx == L ? k - 1 : Iidx);
-                if (ks_mode(c, prime, L, allow_fp) == mode)
-                {
-                    order.push_back((uint32_t)Iidx);
-                    order_mode.push_back(mode);
-                }
-            }
-        }
-        for (size_t o0 = 0; o0 < order.size();)
-        {
-            const int mode = order_mode[o0];
-            size_t g = 0;
-            while (o0 + g < order.size() && g < G && order_mode[o0 + g] == mode)
-            {
-                ++g;
-            }
-            KsGroup grp;
-            for (size_t i = 0; i < MOAI_MAX_RNS; ++i)
-            {
-                size_t Iidx = order[o0 + (i < g ? i : 0)];
-                grp.prime[i] = (uint32_t)(Iidx == L ? k - 1 : Iidx);
-                grp.slot[i] = (uint32_t)Iidx;
-            }
-            switch (c->logn)
-            {
-            case 12:
-                rc = ks_fused_group<12>(c, t, ops, key, acc, L, batch, grp, g, splits, mode, tg, s);
-                break;
-            case 13:
-                rc = ks_fused_group<13>(c, t, ops, key, acc, L, batch, grp, g, splits, mode, tg, s);
-                break;
-            case 14:
-                rc = ks_fused_group<14>(c, t, ops, key, acc, L, batch, grp, g, splits, mode, tg, s);
-                break;
-            case 15:
-                rc = ks_fused_group<15>(c, t, ops, key, acc, L, batch, grp, g, splits, mode, tg, s);
-                break;
-            default:
-                rc = ks_fused_group<16>(c, t, ops, key, acc, L, batch, grp, g, splits, mode, tg, s);
-                break;
-            }
-            if (rc)
-            {
-                return rc;
-            }
-            o0 += g;
+            MOAI_TRY(dispatch_ks(c->logn, pg.mode, [&](auto LG, auto MD) {
+                return ks_fused_group<decltype(LG)::value, decltype(MD)::value>(c, t, ops, key, acc, L, batch, pg.grp, pg.g, w.splits, tg, s);
+            }));
         }
     }
     else
@@ -774,11 +723,7 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
             {
                 rm.idx[r] = (uint32_t)prime;
             }
-            rc = ntt_launch(c, ops, batch, L, rm, false, s);
-            if (rc)
-            {
-                return rc;
-            }
+            MOAI_TRY(ntt_launch(c, ops, batch, L, rm, false, s));
             MacArgs m;
             m.ops = ops;
             m.key = key;
@@ -797,11 +742,11 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
     }
     // 3. mod-down by the special prime, accumulated into ct   (evaluator.cpp:2913-3018)
     MOAI_CHECK_GRID_ROWS(batch * 2);
-    hipLaunchKernelGGL(sum_rows_kernel, rgrid(c, batch * 2), dim3(256), 0, s, acc, last, (uint32_t)(L + 1), (uint32_t)L, splits,
-                       split_stride, c->pc, (uint32_t)(k - 1), n2);
+    hipLaunchKernelGGL(sum_rows_kernel, rgrid(c, batch * 2), dim3(256), 0, s, acc, last, (uint32_t)(L + 1), (uint32_t)L, w.splits,
+                       w.split_stride, c->pc, (uint32_t)(k - 1), n2);
     MOAI_LAUNCH_CHECK();
-    return moddown(c, last, acc, (uint32_t)(L + 1), ops, ct, batch * 2, L, (uint32_t)(k - 1), addend, (uint32_t)addend_bstride, add_mode, s, splits,
-                   split_stride, nullptr, addend2);
+    return moddown(c, last, acc, (uint32_t)(L + 1), ops, ct, batch * 2, L, (uint32_t)(k - 1), addend, (uint32_t)addend_bstride, add_mode, s,
+                   w.splits, w.split_stride, nullptr, addend2);
 }
 
 } // namespace moai
@@ -854,11 +799,7 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
     {
         // small transforms take the two separate steps
         void *tmp = nullptr;
-        rc = moai_malloc(&tmp, P * L * row_bytes);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(moai_malloc(&tmp, P * L * row_bytes));
         rc = moai_mul_scalar_rows(c, in, scalars, static_cast<uint64_t *>(tmp), P, L, stream);
         if (!rc)
         {
@@ -887,11 +828,7 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
         op_lock.lock();
     }
     void *wsp;
-    rc = workspace(c, sz_last + sz_u, s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, sz_last + sz_u, s, &wsp));
     uint64_t *last = static_cast<uint64_t *>(wsp);
     uint64_t *u = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + sz_last);
     MOAI_CHECK_GRID_ROWS(P);
@@ -970,11 +907,7 @@ extern "C" int moai_switch_key(moai_ctx *c, uint64_t *ct, const uint64_t *target
 {
     MOAI_AUDIT(stream, ct, target, key);
     trace_op("switch_key", L, batch);
-    int rc = check_level(c, L, batch * 2);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, batch * 2));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -985,11 +918,7 @@ extern "C" int moai_switch_key(moai_ctx *c, uint64_t *ct, const uint64_t *target
     }
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
-    rc = workspace(c, switch_key_ws_bytes(c, L, batch), (hipStream_t)stream, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, switch_key_ws_bytes(c, L, batch), (hipStream_t)stream, &wsp));
     return switch_key_impl(c, ct, target, L, 0, key, L, batch, wsp, (hipStream_t)stream, ct, 2 * L, 1);
 }
 
@@ -998,11 +927,7 @@ extern "C" int moai_relinearize(moai_ctx *c, const uint64_t *ct3, const uint64_t
 {
     MOAI_AUDIT(stream, ct3, relin_key, out);
     trace_op("relinearize", L, batch);
-    int rc = check_level(c, L, batch * 3);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, batch * 3));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1014,14 +939,25 @@ extern "C" int moai_relinearize(moai_ctx *c, const uint64_t *ct3, const uint64_t
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
-    rc = workspace(c, switch_key_ws_bytes(c, L, batch), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, switch_key_ws_bytes(c, L, batch), s, &wsp));
     // out = (c0, c1) + switch_key(c2, relin_keys[0])      (evaluator.cpp:1383-1392): c0 and c1 are read from ct3 by
     // the last kernel of the key switch, no copy first
     return switch_key_impl(c, out, ct3, 3 * L, 2 * L, relin_key, L, batch, wsp, s, ct3, 3 * L, 1);
+}
+
+// out = (galois(in0), 0) + switch_key(galois(in1)) [+ sum]      (evaluator.cpp:2631-2654): both summands are added by the
+// last kernel of the key switch, so `out` is written once and may be `in` (or `sum`)
+static int apply_galois_impl(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, uint32_t galois_elt, const uint64_t *galois_key,
+                             size_t batch, void *stream, const uint64_t *sum)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sz_tmp = align256(batch * 2 * L * c->n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    void *wsp;
+    MOAI_TRY(workspace(c, sz_tmp + switch_key_ws_bytes(c, L, batch), s, &wsp));
+    uint64_t *tmp = static_cast<uint64_t *>(wsp); // galois(in), both polynomials
+    MOAI_TRY(moai_galois_permute(c, in, tmp, batch * 2, L, galois_elt, stream));
+    return switch_key_impl(c, out, tmp, 2 * L, L, galois_key, L, batch, static_cast<char *>(wsp) + sz_tmp, s, tmp, 2 * L, 2, sum);
 }
 
 extern "C" int moai_apply_galois_to(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, uint32_t galois_elt,
@@ -1029,11 +965,7 @@ extern "C" int moai_apply_galois_to(moai_ctx *c, const uint64_t *in, uint64_t *o
 {
     MOAI_AUDIT(stream, in, out, galois_key);
     trace_op("apply_galois_to", L, batch);
-    int rc = check_level(c, L, batch * 2);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, batch * 2));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1042,26 +974,7 @@ extern "C" int moai_apply_galois_to(moai_ctx *c, const uint64_t *in, uint64_t *o
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t row_bytes = c->n * sizeof(uint64_t);
-    const size_t sz_tmp = align256(batch * 2 * L * row_bytes);
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
-    void *wsp;
-    rc = workspace(c, sz_tmp + switch_key_ws_bytes(c, L, batch), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
-    uint64_t *tmp = static_cast<uint64_t *>(wsp);
-    void *ks_ws = static_cast<char *>(wsp) + sz_tmp;
-    // tmp = galois(in) for both polynomials; out = (tmp0, 0) + switch_key(tmp1)  (evaluator.cpp:2631-2654): tmp0 is
-    // added by the last kernel of the key switch, so `out` is written once and may be `in`
-    rc = moai_galois_permute(c, in, tmp, batch * 2, L, galois_elt, stream);
-    if (rc)
-    {
-        return rc;
-    }
-    return switch_key_impl(c, out, tmp, 2 * L, L, galois_key, L, batch, ks_ws, s, tmp, 2 * L, 2);
+    return apply_galois_impl(c, in, out, L, galois_elt, galois_key, batch, stream, nullptr);
 }
 
 extern "C" int moai_apply_galois(moai_ctx *c, uint64_t *ct, size_t L, uint32_t galois_elt, const uint64_t *galois_key,
@@ -1076,11 +989,7 @@ extern "C" int moai_apply_galois_acc(moai_ctx *c, const uint64_t *in, uint64_t *
 {
     MOAI_AUDIT(stream, in, acc, galois_key);
     trace_op("apply_galois_to", L, batch); // the same key switch; the addition that follows it is what is saved
-    int rc = check_level(c, L, batch * 2);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, batch * 2));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1089,25 +998,7 @@ extern "C" int moai_apply_galois_acc(moai_ctx *c, const uint64_t *in, uint64_t *
     {
         return set_error(MOAI_EINVAL, "null argument, or the sum is the input");
     }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t row_bytes = c->n * sizeof(uint64_t);
-    const size_t sz_tmp = align256(batch * 2 * L * row_bytes);
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
-    void *wsp;
-    rc = workspace(c, sz_tmp + switch_key_ws_bytes(c, L, batch), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
-    uint64_t *tmp = static_cast<uint64_t *>(wsp);
-    void *ks_ws = static_cast<char *>(wsp) + sz_tmp;
-    rc = moai_galois_permute(c, in, tmp, batch * 2, L, galois_elt, stream);
-    if (rc)
-    {
-        return rc;
-    }
-    // acc = acc + (tmp0, 0) + switch_key(tmp1): both summands are added by the key switch's last kernel
-    return switch_key_impl(c, acc, tmp, 2 * L, L, galois_key, L, batch, ks_ws, s, tmp, 2 * L, 2, acc);
+    return apply_galois_impl(c, in, acc, L, galois_elt, galois_key, batch, stream, acc);
 }
 
 extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L_out, size_t batch, void *stream)
@@ -1115,11 +1006,7 @@ extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, siz
     MOAI_AUDIT(stream, in, out);
     trace_op("modraise", L_out, batch);
     const size_t P = batch * 2;
-    int rc = check_level(c, L_out, P);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L_out, P));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1132,24 +1019,12 @@ extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, siz
     const size_t row_bytes = c->n * sizeof(uint64_t);
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
-    rc = workspace(c, align256(P * row_bytes), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, align256(P * row_bytes), s, &wsp));
     uint64_t *src = static_cast<uint64_t *>(wsp);
     MOAI_HIP_CHECK(hipMemcpyAsync(src, in, P * row_bytes, hipMemcpyDeviceToDevice, s));
     RowMap rm;
-    rc = make_rowmap(c, 1, nullptr, &rm);
-    if (rc)
-    {
-        return rc;
-    }
-    rc = ntt_launch(c, src, P, 1, rm, true, s);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, 1, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, src, P, 1, rm, true, s));
     RaiseArgs g;
     g.src = src;
     g.out = out;
@@ -1159,34 +1034,25 @@ extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, siz
     MOAI_CHECK_GRID_ROWS(P * L_out);
     hipLaunchKernelGGL(modraise_kernel, rgrid(c, P * L_out), dim3(256), 0, s, g);
     MOAI_LAUNCH_CHECK();
-    rc = make_rowmap(c, L_out, nullptr, &rm);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, L_out, nullptr, &rm));
     return ntt_launch(c, out, P, L_out, rm, false, s);
 }
 
 // ---- hoisted rotations (keyswitch_kernels.hip.h explains the identity) --------------------------------------------
 namespace moai {
 
-template <int LOGN>
-static void hoist_contig_finish(moai_ctx *c, uint64_t *tmp, size_t L, size_t batch, const KsGroup &grp, size_t G, int mode, hipStream_t s)
+template <int LOGN, int MODE>
+static void hoist_contig_finish(moai_ctx *c, uint64_t *tmp, size_t L, size_t batch, const KsGroup &grp, size_t G, hipStream_t s)
 {
     // the strided pass left [B][G][L][N] in the mode's lazy form: the plain contiguous pass finishes every row of group
     // member g under that member's prime and leaves canonical residues
     constexpr uint32_t tpr = 1u << (LOGN - 12);
+    const TwPair t = twiddles(c, MODE, false);
     for (size_t g = 0; g < G; ++g)
     {
-        NttArgs a;
-        memset(&a, 0, sizeof(a));
-        a.data = tmp;
-        a.tw = mode >= M_FPN ? c->fwd_twf : c->fwd_tw;
-        a.twb = mode >= M_FPN ? c->fwd_twfb : c->fwd_twb;
-        a.pc = c->pc;
-        a.L = (uint32_t)(G * L);
-        a.n_poly = (uint32_t)batch;
-        a.lds_twiddles = tuning("MOAI_NTT_LDSTW", 1) ? 1u : 0u;
+        NttArgs a = ntt_args(c, tmp, batch, G * L, RowMap{}, false);
+        a.tw = t.tw;
+        a.twb = t.twb;
         a.Lsel = 0;
         for (size_t J = 0; J < L; ++J)
         {
@@ -1198,48 +1064,48 @@ static void hoist_contig_finish(moai_ctx *c, uint64_t *tmp, size_t L, size_t bat
             a.selp.idx[a.Lsel++] = grp.prime[g];
         }
         a.total_work = a.n_poly * a.Lsel * tpr;
-        switch (mode)
-        {
-        case M_FPN: hipLaunchKernelGGL((ntt_fwd_contig<LOGN, M_FPN>), dim3(a.total_work), dim3(256), 0, s, a); break;
-        case M_FPR: hipLaunchKernelGGL((ntt_fwd_contig<LOGN, M_FPR>), dim3(a.total_work), dim3(256), 0, s, a); break;
-        case M_NOGUARD: hipLaunchKernelGGL((ntt_fwd_contig<LOGN, M_NOGUARD>), dim3(a.total_work), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((ntt_fwd_contig<LOGN, M_GUARD>), dim3(a.total_work), dim3(256), 0, s, a); break;
-        }
+        hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
     }
 }
 
-template <int LOGN>
+// what the rotations of one hoisted call share (one entry per rotation)
+struct HoistRotations
+{
+    size_t R;
+    const uint32_t *const *tables, *const *itables;
+    const uint64_t *const *keys;
+    const uint32_t *key_rows;
+    const uint64_t *const *corrs;
+    uint64_t *acc; // rotation r accumulates at acc + r * acc_stride_words
+    size_t acc_stride_words;
+};
+
+template <int LOGN, int MODE>
 static int hoist_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint64_t *in, size_t L, size_t batch, const KsGroup &grp,
-                       size_t G, int mode, const uint32_t *const *tables, const uint32_t *const *itables, const uint64_t *const *keys,
-                       const uint32_t *key_rows, const uint64_t *const *corrs, uint64_t *acc, size_t acc_stride_words, size_t R, hipStream_t s)
+                       size_t G, const HoistRotations &rot, hipStream_t s)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
+    constexpr bool FP = MODE >= M_FPN;
     KsP1Args p1;
     p1.t = t;
     p1.tmp = tmp;
-    p1.tw = mode >= M_FPN ? c->fwd_twf : c->fwd_tw;
+    p1.tw = twiddles(c, MODE, false).tw;
     p1.tw1 = c->fwd_twf1;
     p1.pc = c->pc;
     p1.grp = grp;
     p1.L = (uint32_t)L;
     p1.G = (uint32_t)G;
     p1.total_work = (uint32_t)(batch * G * L * TPR);
-    switch (mode)
-    {
-    case M_FPN: hipLaunchKernelGGL((ks_fwd_strided<LOGN, M_FPN>), dim3(p1.total_work), dim3(256), 0, s, p1); break;
-    case M_FPR: hipLaunchKernelGGL((ks_fwd_strided<LOGN, M_FPR>), dim3(p1.total_work), dim3(256), 0, s, p1); break;
-    case M_NOGUARD: hipLaunchKernelGGL((ks_fwd_strided<LOGN, M_NOGUARD>), dim3(p1.total_work), dim3(256), 0, s, p1); break;
-    default: hipLaunchKernelGGL((ks_fwd_strided<LOGN, M_GUARD>), dim3(p1.total_work), dim3(256), 0, s, p1); break;
-    }
+    hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE>), dim3(p1.total_work), dim3(256), 0, s, p1);
     MOAI_LAUNCH_CHECK();
-    hoist_contig_finish<LOGN>(c, tmp, L, batch, grp, G, mode, s);
+    hoist_contig_finish<LOGN, MODE>(c, tmp, L, batch, grp, G, s);
     MOAI_LAUNCH_CHECK();
     // FP64 modes: four or two rotations per pass over the digits (ks_hoisted_mac2); MOAI_KS_HOIST_PAIR=0 keeps one per pass,
     // 2 at most two
-    const long pair = (mode == M_FPN || mode == M_FPR) ? tuning("MOAI_KS_HOIST_PAIR", 4) : 0;
-    for (size_t r = 0; r < R; ++r)
+    const long pair = FP ? tuning(K_KS_HOIST_PAIR) : 0;
+    for (size_t r = 0; r < rot.R; ++r)
     {
-        const size_t nr = pair >= 4 && r + 3 < R ? 4 : (pair >= 1 && r + 1 < R ? 2 : 1);
+        const size_t nr = pair >= 4 && r + 3 < rot.R ? 4 : (pair >= 1 && r + 1 < rot.R ? 2 : 1);
         if (nr > 1)
         {
             HoistMac2Args m2;
@@ -1248,11 +1114,11 @@ static int hoist_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint
             for (size_t h = 0; h < 4; ++h)
             {
                 const size_t rr = r + (h < nr ? h : 0);
-                m2.itable[h] = itables[rr];
-                m2.key[h] = keys[rr];
-                m2.krows[h] = key_rows[rr];
-                m2.corr[h] = corrs[rr];
-                m2.acc[h] = acc + rr * acc_stride_words;
+                m2.itable[h] = rot.itables[rr];
+                m2.key[h] = rot.keys[rr];
+                m2.krows[h] = rot.key_rows[rr];
+                m2.corr[h] = rot.corrs[rr];
+                m2.acc[h] = rot.acc + rr * rot.acc_stride_words;
             }
             m2.pc = c->pc;
             m2.grp = grp;
@@ -1261,54 +1127,55 @@ static int hoist_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint
             m2.k = (uint32_t)c->k;
             m2.B = (uint32_t)batch;
             m2.total_work = (uint32_t)(batch * G * TPR * 2);
-            if (mode == M_FPN && nr == 4)
-            {
-                hipLaunchKernelGGL((ks_hoisted_mac2<LOGN, false, 4>), dim3(m2.total_work), dim3(256), 0, s, m2);
-            }
-            else if (mode == M_FPN)
-            {
-                hipLaunchKernelGGL((ks_hoisted_mac2<LOGN, false, 2>), dim3(m2.total_work), dim3(256), 0, s, m2);
-            }
-            else if (nr == 4)
-            {
-                hipLaunchKernelGGL((ks_hoisted_mac2<LOGN, true, 4>), dim3(m2.total_work), dim3(256), 0, s, m2);
-            }
-            else
-            {
-                hipLaunchKernelGGL((ks_hoisted_mac2<LOGN, true, 2>), dim3(m2.total_work), dim3(256), 0, s, m2);
-            }
+            MOAI_TRY((dispatch<2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
+                hipLaunchKernelGGL((ks_hoisted_mac2<LOGN, MODE == M_FPR, decltype(NR)::value>), dim3(m2.total_work), dim3(256), 0, s, m2);
+                return MOAI_OK;
+            })));
             r += nr - 1;
             continue;
         }
         HoistMacArgs m;
         m.dig = tmp;
         m.ct = in;
-        m.table = tables[r];
-        m.key = keys[r];
-        m.corr = corrs[r];
-        m.acc = acc + r * acc_stride_words;
+        m.table = rot.tables[r];
+        m.key = rot.keys[r];
+        m.corr = rot.corrs[r];
+        m.acc = rot.acc + r * rot.acc_stride_words;
         m.pc = c->pc;
         m.grp = grp;
         m.L = (uint32_t)L;
         m.G = (uint32_t)G;
-        m.k = key_rows[r];
+        m.k = rot.key_rows[r];
         m.B = (uint32_t)batch;
         m.total_work = (uint32_t)(batch * G * TPR * 2);
-        if (mode == M_FPN)
-        {
-            hipLaunchKernelGGL((ks_hoisted_mac<LOGN, true, false>), dim3(m.total_work), dim3(256), 0, s, m);
-        }
-        else if (mode == M_FPR)
-        {
-            hipLaunchKernelGGL((ks_hoisted_mac<LOGN, true, true>), dim3(m.total_work), dim3(256), 0, s, m);
-        }
-        else
-        {
-            hipLaunchKernelGGL((ks_hoisted_mac<LOGN, false, false>), dim3(m.total_work), dim3(256), 0, s, m);
-        }
+        hipLaunchKernelGGL((ks_hoisted_mac<LOGN, FP, MODE == M_FPR>), dim3(m.total_work), dim3(256), 0, s, m);
     }
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
+}
+
+// workspace of one hoisted call of R rotations, byte offsets: flag | t [B][L][N] | tmp [B][G][L][N] | acc [R][B][2][L+1][N] |
+// last [2B][N] | u [2B][L][N] | c0 [B][L][N]
+struct HoistLayout
+{
+    size_t acc_stride_words;
+    size_t flag, t, tmp, acc, last, u, c0, total;
+};
+
+static HoistLayout hoist_layout(const moai_ctx *c, size_t L, size_t batch, size_t R)
+{
+    const size_t row_bytes = c->n * sizeof(uint64_t);
+    HoistLayout w;
+    w.acc_stride_words = batch * 2 * (L + 1) * c->n;
+    w.flag = 0;
+    w.t = 256;
+    w.tmp = w.t + align256(batch * L * row_bytes);
+    w.acc = w.tmp + align256(batch * ks_group_size(c, L, batch) * L * row_bytes);
+    w.last = w.acc + align256(R * w.acc_stride_words * sizeof(uint64_t));
+    w.u = w.last + align256(batch * 2 * row_bytes);
+    w.c0 = w.u + align256(2 * batch * L * row_bytes);
+    w.total = w.c0 + align256(batch * L * row_bytes);
+    return w;
 }
 
 } // namespace moai
@@ -1318,11 +1185,7 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
 {
     MOAI_AUDIT(stream, galois_key, correction);
     trace_op("hoist_correction", L, 1);
-    int rc = check_level(c, L, 2);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, 2));
     if (!galois_key || !correction)
     {
         return set_error(MOAI_EINVAL, "null argument");
@@ -1336,20 +1199,12 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
         return set_error(MOAI_EINVAL, "Galois element is not valid");
     }
     uint32_t key_rows = 0;
-    rc = key_rows_for(c, galois_key, L, &key_rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(key_rows_for(c, galois_key, L, &key_rows));
     hipStream_t s = (hipStream_t)stream;
     const size_t row_bytes = c->n * sizeof(uint64_t);
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
-    rc = workspace(c, align256((L + 1) * row_bytes), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, align256((L + 1) * row_bytes), s, &wsp));
     uint64_t *mask = static_cast<uint64_t *>(wsp);
     hipLaunchKernelGGL(galois_sign_mask_kernel, dim3((uint32_t)((c->n + 255) / 256)), dim3(256), 0, s, mask, (uint32_t)c->logn, galois_elt,
                        (uint32_t)(L + 1));
@@ -1361,16 +1216,8 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
     }
     pidx[L] = (uint32_t)(c->k - 1);
     RowMap rm;
-    rc = make_rowmap(c, L + 1, pidx.data(), &rm);
-    if (rc)
-    {
-        return rc;
-    }
-    rc = ntt_launch(c, mask, 1, L + 1, rm, false, s);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, L + 1, pidx.data(), &rm));
+    MOAI_TRY(ntt_launch(c, mask, 1, L + 1, rm, false, s));
     HoistCorrArgs g;
     g.key = galois_key;
     g.mask = mask;
@@ -1422,11 +1269,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
     {
         *used_fallback = 0;
     }
-    int rc = check_level(c, L, batch * 2);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_level(c, L, batch * 2));
     if (batch == 0 || R == 0)
     {
         return MOAI_OK;
@@ -1452,11 +1295,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         {
             return set_error(MOAI_EINVAL, "null key, correction or output (an output must not be the input)");
         }
-        rc = galois_table(c, galois_elts[r], s, &tables[r]);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(galois_table(c, galois_elts[r], s, &tables[r]));
         // the inverse permutation is the table of the inverse element (mod 2N, by Newton's iteration on an odd number)
         const uint32_t two_n_mask = (uint32_t)(2 * n - 1);
         uint32_t inv = galois_elts[r];
@@ -1464,61 +1303,28 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         {
             inv = (inv * (2u - galois_elts[r] * inv)) & two_n_mask;
         }
-        rc = galois_table(c, inv, s, &itables[r]);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(galois_table(c, inv, s, &itables[r]));
     }
     std::vector<uint32_t> key_rows(R);
     for (size_t r = 0; r < R; ++r)
     {
-        rc = key_rows_for(c, galois_keys[r], L, &key_rows[r]);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(key_rows_for(c, galois_keys[r], L, &key_rows[r]));
     }
     bool fallback = c->logn < 12;
     if (!fallback)
     {
-        const size_t row_bytes = n * sizeof(uint64_t);
-        const size_t G = ks_group_size(c, L, batch);
-        const size_t sz_t = align256(batch * L * row_bytes);
-        const size_t sz_tmp = align256(batch * G * L * row_bytes);
-        const size_t acc_stride_words = batch * 2 * (L + 1) * n;
-        const size_t sz_acc = align256(R * acc_stride_words * sizeof(uint64_t));
-        const size_t sz_last = align256(batch * 2 * row_bytes);
-        const size_t sz_u = align256(2 * batch * L * row_bytes);
-        const size_t sz_c0 = align256(batch * L * row_bytes);
+        const HoistLayout w = hoist_layout(c, L, batch, R);
         std::unique_lock<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
         void *wsp;
-        rc = workspace(c, 256 + sz_t + sz_tmp + sz_acc + sz_last + sz_u + sz_c0, s, &wsp);
-        if (rc)
-        {
-            return rc;
-        }
-        char *base = static_cast<char *>(wsp);
-        uint32_t *flag = reinterpret_cast<uint32_t *>(base);
-        uint64_t *t = reinterpret_cast<uint64_t *>(base + 256);
-        uint64_t *tmp = reinterpret_cast<uint64_t *>(base + 256 + sz_t);
-        uint64_t *acc = reinterpret_cast<uint64_t *>(base + 256 + sz_t + sz_tmp);
-        uint64_t *last = reinterpret_cast<uint64_t *>(base + 256 + sz_t + sz_tmp + sz_acc);
-        uint64_t *u = reinterpret_cast<uint64_t *>(base + 256 + sz_t + sz_tmp + sz_acc + sz_last);
-        uint64_t *pc0 = reinterpret_cast<uint64_t *>(base + 256 + sz_t + sz_tmp + sz_acc + sz_last + sz_u);
+        MOAI_TRY(workspace(c, w.total, s, &wsp));
+        uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
+        uint64_t *t = at_bytes(wsp, w.t), *tmp = at_bytes(wsp, w.tmp), *acc = at_bytes(wsp, w.acc), *last = at_bytes(wsp, w.last);
+        uint64_t *u = at_bytes(wsp, w.u), *pc0 = at_bytes(wsp, w.c0);
         const uint32_t n2 = (uint32_t)(n >> 1);
         // t = INTT(c1), UNPERMUTED: once for all rotations
         RowMap rm;
-        rc = make_rowmap(c, L, nullptr, &rm);
-        if (rc)
-        {
-            return rc;
-        }
-        rc = ntt_launch(c, t, batch, L, rm, true, s, in, 2 * L, L);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+        MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, in, 2 * L, L));
         MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(any_zero_kernel, dim3(1024), dim3(256), 0, s, t, batch * L * n / 2, flag);
         MOAI_LAUNCH_CHECK();
@@ -1531,69 +1337,24 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         }
         else
         {
-            const bool allow_fp = (long)(batch * L) >= tuning("MOAI_KS_FP_MIN_ROWS", 16);
-            std::vector<uint32_t> order;
-            std::vector<int> order_mode;
-            for (int mode = M_FPR; mode >= M_GUARD; --mode)
+            const HoistRotations rot = { R, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, w.acc_stride_words };
+            for (const KsPlanGroup &pg : ks_plan(c, L, batch))
             {
-                for (size_t Iidx = 0; Iidx <= L; ++Iidx)
-                {
-                    const uint32_t prime = (uint32_t)(Iidx == L ? k - 1 : Iidx);
-                    if (ks_mode(c, prime, L, allow_fp) == mode)
-                    {
-                        order.push_back((uint32_t)Iidx);
-                        order_mode.push_back(mode);
-                    }
-                }
-            }
-            for (size_t o0 = 0; o0 < order.size();)
-            {
-                const int mode = order_mode[o0];
-                size_t g = 0;
-                while (o0 + g < order.size() && g < G && order_mode[o0 + g] == mode)
-                {
-                    ++g;
-                }
-                KsGroup grp;
-                for (size_t i = 0; i < MOAI_MAX_RNS; ++i)
-                {
-                    size_t Iidx = order[o0 + (i < g ? i : 0)];
-                    grp.prime[i] = (uint32_t)(Iidx == L ? k - 1 : Iidx);
-                    grp.slot[i] = (uint32_t)Iidx;
-                }
-                switch (c->logn)
-                {
-                case 12: rc = hoist_group<12>(c, t, tmp, in, L, batch, grp, g, mode, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, acc_stride_words, R, s); break;
-                case 13: rc = hoist_group<13>(c, t, tmp, in, L, batch, grp, g, mode, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, acc_stride_words, R, s); break;
-                case 14: rc = hoist_group<14>(c, t, tmp, in, L, batch, grp, g, mode, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, acc_stride_words, R, s); break;
-                case 15: rc = hoist_group<15>(c, t, tmp, in, L, batch, grp, g, mode, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, acc_stride_words, R, s); break;
-                default: rc = hoist_group<16>(c, t, tmp, in, L, batch, grp, g, mode, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, acc_stride_words, R, s); break;
-                }
-                if (rc)
-                {
-                    return rc;
-                }
-                o0 += g;
+                MOAI_TRY(dispatch_ks(c->logn, pg.mode, [&](auto LG, auto MD) {
+                    return hoist_group<decltype(LG)::value, decltype(MD)::value>(c, t, tmp, in, L, batch, pg.grp, pg.g, rot, s);
+                }));
             }
             // per rotation: the permuted c0 is the addend, then the shared mod-down tail (evaluator.cpp:2913-3018)
             for (size_t r = 0; r < R; ++r)
             {
-                uint64_t *acc_r = acc + r * acc_stride_words;
+                uint64_t *acc_r = acc + r * w.acc_stride_words;
                 // pc0 [B][L][N] = perm(c0 of in): the addend of the even polynomials (add_mode 2, ciphertexts L rows apart)
-                rc = galois_permute_c0(c, in, pc0, batch, L, galois_elts[r], s);
-                if (rc)
-                {
-                    return rc;
-                }
+                MOAI_TRY(galois_permute_c0(c, in, pc0, batch, L, galois_elts[r], s));
                 MOAI_CHECK_GRID_ROWS(batch * 2);
                 hipLaunchKernelGGL(sum_rows_kernel, rgrid(c, batch * 2), dim3(256), 0, s, acc_r, last, (uint32_t)(L + 1), (uint32_t)L, 1u,
                                    (size_t)0, c->pc, (uint32_t)(k - 1), n2);
                 MOAI_LAUNCH_CHECK();
-                rc = moddown(c, last, acc_r, (uint32_t)(L + 1), u, outs[r], batch * 2, L, (uint32_t)(k - 1), pc0, (uint32_t)L, 2, s);
-                if (rc)
-                {
-                    return rc;
-                }
+                MOAI_TRY(moddown(c, last, acc_r, (uint32_t)(L + 1), u, outs[r], batch * 2, L, (uint32_t)(k - 1), pc0, (uint32_t)L, 2, s));
             }
             return MOAI_OK;
         }
@@ -1605,11 +1366,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
     }
     for (size_t r = 0; r < R; ++r)
     {
-        rc = moai_apply_galois_to(c, in, outs[r], L, galois_elts[r], galois_keys[r], batch, stream);
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(moai_apply_galois_to(c, in, outs[r], L, galois_elts[r], galois_keys[r], batch, stream));
     }
     return MOAI_OK;
 }
@@ -1632,11 +1389,7 @@ extern "C" int moai_key_trim(moai_ctx *c, const uint64_t *full_key, size_t level
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    int rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
     const size_t k = c->k, n = c->n;
     if (k < 2 || levels < 1 || levels > k - 1)
     {

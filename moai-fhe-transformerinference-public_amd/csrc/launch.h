@@ -1,11 +1,61 @@
 // launch.h -- host-side entry points shared between the translation units of the library.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace moai {
 
-// a tuning knob: the value set through moai_set_tuning, else the environment variable of that name, else dflt
-long tuning(const char *name, long dflt);
+// Every tuning knob of the library: X(id, default, what it does).  The environment variable and the moai_set_tuning name
+// of a knob is "MOAI_" #id.  Knobs change speed or memory use, never results.  (MOAI_STREAM_AUDIT is a debug switch with
+// a path of its own, common.h; the seal:: shim's MOAI_SHIM_* / MOAI_BOOT_* / MOAI_POOL_* switches live in the shim.)
+#define MOAI_KNOBS(X)                                                                                                          \
+    X(NTT_FP, 1, "0: primes below 2^51 stay on the integer units in every transform, key switch and mod-down")                \
+    X(NTT_LAZY8, 1, "0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient")       \
+    X(NTT_LDSTW, 1, "0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS")      \
+    X(NTT_CHUNK_MB, 0, "> 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB")          \
+    X(NTT_NAIVE, 0, "1: one launch per radix-2 stage over global memory (cross-check path)")                                   \
+    X(NTT_COOP, 0, "1: the single-launch persistent transform (N >= 4096)")                                                    \
+    X(NTT_COOP_WPC, 4, "single-launch transform: workgroups per compute unit")                                                 \
+    X(NTT_COOP_DELAY, 4, "single-launch transform: rows a second pass stays behind the first")                                 \
+    X(NTT_COOP_OCC, 4, "single-launch transform: occupancy the kernel is compiled for (3 or 4)")                               \
+    X(KS_FP_MIN_ROWS, 16, "batch * L from which the key switch uses the FP64 arithmetic modes")                                \
+    X(KS_TMP_MB, 8192, "MiB of key-switch digits in flight: sets how many output moduli share a launch")                       \
+    X(KS_P1_ITEMS, 8, "1: the key switch's strided pass at N = 2^16 runs one tile per workgroup instead of eight, pipelined")  \
+    X(KS_P1_PRE, 0, "1: the M_FPN strided pass of the key switch takes its twiddles as plain doubles")                         \
+    X(KS_MAC_PF, 1, "key residues of the FP64 key-switch MAC: 0 loaded next to their use, 1 at its head, 2 at the digit's head") \
+    X(KS_HOIST_PAIR, 4, "rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one")                         \
+    X(MD_FP_MIN_ROWS, 256, "polynomials * L from which mod-down and rescale use the FP64 arithmetic modes")                    \
+    X(MATMUL_FP, 1, "0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel")                                      \
+    X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")
+
+enum Knob
+{
+#define MOAI_KNOB_ID(id, dflt, what) K_##id,
+    MOAI_KNOBS(MOAI_KNOB_ID)
+#undef MOAI_KNOB_ID
+    KNOB_COUNT
+};
+// a knob's value: what moai_set_tuning stored, else the environment variable (read once, on first use), else the default.
+// One relaxed atomic load.
+long tuning(Knob k);
+
+// Calls f(std::integral_constant<int, V>) for the V among Vs that equals v and returns what f returns; a v outside the list is
+// MOAI_ELOGIC "unsupported <what><v>", never a default case.  Every call site names the values it has kernels for, so no other
+// instantiation can appear.
+template <int... Vs, class F>
+int dispatch(const char *what, int v, F &&f)
+{
+    int rc = MOAI_OK;
+    const bool found = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return found ? rc : set_error(MOAI_ELOGIC, "unsupported %s%d", what, v);
+}
+// the tiled kernels exist for N = 2^12 .. 2^16
+template <class F>
+int dispatch_logn(int logn, F &&f)
+{
+    return dispatch<12, 13, 14, 15, 16>("poly_modulus_degree 2^", logn, f);
+}
 // operation census for the end-to-end bench (moai_op_trace): counts `units` (polynomials, ciphertexts or products, as the
 // entry point's own batch argument counts them) per (entry point, level); a relaxed atomic load when it is off
 void trace_op(const char *name, size_t L, size_t units);
@@ -13,8 +63,18 @@ bool noguard_ok(uint64_t q);
 // makes the context's device current for the calling thread (contexts of several devices may live in one process);
 // every operation entry point calls it before it allocates or launches
 int enter_device(const moai_ctx *c);
-// arithmetic mode (modarith.hip.h M_*) of the forward transform under a context prime
-int ntt_mode(const moai_ctx *c, uint32_t prime);
+// arithmetic mode (modarith.hip.h M_*) of a transform under a context prime: FP64 (M_FPN / M_FPR) below 2^51 unless MOAI_NTT_FP=0
+// or the caller does not allow it, else integer with (M_GUARD) or without (M_NOGUARD) per-stage guards
+int ntt_mode(const moai_ctx *c, uint32_t prime, bool allow_fp = true);
+// the twiddle tables of a mode: tw in natural order, twb in the contiguous pass's per-thread order
+struct TwPair
+{
+    const Tw *tw, *twb;
+};
+TwPair twiddles(const moai_ctx *c, int mode, bool inverse);
+// kernel arguments of a transform of data [n_poly][L][N] with every row selected and no grid size yet (ntt_kernels.hip.h)
+struct NttArgs;
+NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse);
 int make_rowmap(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap *out);
 // src (inverse only): polynomial p's row r is read from src row p * src_stride_rows + src_off_rows + r, the result lands in
 // `data` [n_poly][L][N] -- the inverse transform of a slice of a larger layout without copying the slice first

@@ -1,28 +1,63 @@
 // ntt.hip -- launchers of the negacyclic NTT kernels (C ABI: moai_ntt_forward / moai_ntt_inverse).
-#include <cstdlib>
-
 #include "ntt_kernels.hip.h"
 #include "launch.h"
 
 namespace moai {
 
-int ntt_mode(const moai_ctx *c, uint32_t prime);
-
-static bool naive_requested()
+// 36 q < 2^64: forward butterflies may skip the per-stage guard (modarith.hip.h ct_bfly_noguard)
+bool noguard_ok(uint64_t q)
 {
-    static int v = -1;
-    if (v < 0)
-    {
-        const char *e = getenv("MOAI_NTT_NAIVE");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
+    return q < (~0ull) / 36;
 }
 
-static long env_long(const char *name, long dflt)
+int ntt_mode(const moai_ctx *c, uint32_t prime, bool allow_fp)
 {
-    const char *e = getenv(name);
-    return e ? atol(e) : dflt;
+    const int m = (int)c->pc_host[prime].fp_mode;
+    if (allow_fp && m && tuning(K_NTT_FP))
+    {
+        return m;
+    }
+    return noguard_ok(c->primes[prime]) ? M_NOGUARD : M_GUARD;
+}
+
+TwPair twiddles(const moai_ctx *c, int mode, bool inverse)
+{
+    if (mode >= M_FPN)
+    {
+        return inverse ? TwPair{ c->inv_twf, c->inv_twfb } : TwPair{ c->fwd_twf, c->fwd_twfb };
+    }
+    return inverse ? TwPair{ c->inv_tw, c->inv_twb } : TwPair{ c->fwd_tw, c->fwd_twb };
+}
+
+NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse)
+{
+    NttArgs a;
+    const TwPair t = twiddles(c, M_GUARD, inverse);
+    a.data = data;
+    a.tw = t.tw;
+    a.twb = t.twb;
+    a.pc = c->pc;
+    a.rows = rows;
+    for (size_t r = 0; r < MOAI_MAX_RNS; ++r)
+    {
+        a.sel.idx[r] = (uint32_t)(r < L ? r : 0);
+        a.selp.idx[r] = rows.idx[r < L ? r : 0];
+    }
+    a.Lsel = (uint32_t)L;
+    a.L = (uint32_t)L;
+    a.n_poly = (uint32_t)n_poly;
+    a.total_work = 0;
+    a.src = nullptr;
+    a.src_stride = a.src_off = 0;
+    a.lds_twiddles = tuning(K_NTT_LDSTW) ? 1u : 0u;
+    return a;
+}
+
+// integer primes below 2^60 take the butterflies with the approximate Shoup quotient (M_LAZY8), the others the exact
+// ones; same residues either way (modarith.hip.h)
+static bool lazy8_ok(const moai_ctx *c, uint32_t prime)
+{
+    return tuning(K_NTT_LAZY8) && c->primes[prime] < (1ull << 60);
 }
 
 template <int LOGN, int MODE>
@@ -30,11 +65,9 @@ static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
 {
     constexpr uint32_t tpr = 1u << (LOGN - 12);
     a.total_work = a.n_poly * a.Lsel * tpr;
-    if (MODE >= M_FPN)
-    {
-        a.tw = c->fwd_twf;
-        a.twb = c->fwd_twfb;
-    }
+    const TwPair t = twiddles(c, MODE, false);
+    a.tw = t.tw;
+    a.twb = t.twb;
     // (the software-pipelined strided pass of the key switch, fwd_strided_tiles, does not pay here: measured in round 3 on 256 x 2
     // polynomials, 11.25 against 11.37 ms with the bench's 60-bit primes and 7.77 against 7.40 ms -- slower -- with MOAI's FP64
     // rows.  An in-place transform reads as much as it writes and has no cached operand; five resident workgroups of one tile
@@ -43,57 +76,40 @@ static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
     hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
 }
 
-// forward transform: the rows are split by the arithmetic their prime allows (ntt_mode) and every class
-// gets its own pair of launches
+// forward transform: the rows are split by the arithmetic their prime allows and every class gets its own pair of launches.
+// The plain transform has no M_GUARD kernels: ntt_mode's integer primes with guards take M_LAZY8 below 2^60, else the guard
+// of every second stage (M_GUARD2).
 template <int LOGN>
-static void launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
+static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    for (int mode = M_GUARD; mode <= M_FPR; ++mode)
+    for (int mode : { M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR })
     {
         NttArgs a = base;
         a.Lsel = 0;
         for (uint32_t r = 0; r < a.L; ++r)
         {
-            if (ntt_mode(c, a.rows.idx[r]) == mode)
+            const uint32_t prime = a.rows.idx[r];
+            int m = ntt_mode(c, prime);
+            if (m == M_GUARD)
             {
-                a.selp.idx[a.Lsel] = a.rows.idx[r];
-                a.sel.idx[a.Lsel++] = (uint32_t)r;
+                m = lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD2;
+            }
+            if (m == mode)
+            {
+                a.selp.idx[a.Lsel] = prime;
+                a.sel.idx[a.Lsel++] = r;
             }
         }
         if (a.Lsel == 0)
         {
             continue;
         }
-        switch (mode)
-        {
-        case M_GUARD:
-        {
-            // integer primes: below 2^60 the butterfly with the approximate Shoup quotient (M_LAZY8), else the exact one with a
-            // guard every second stage (M_GUARD2); same residues either way (modarith.hip.h).  One launch pair per class.
-            static const long lazy8 = env_long("MOAI_NTT_LAZY8", 1);
-            NttArgs lo = a, hi = a;
-            lo.Lsel = hi.Lsel = 0;
-            for (uint32_t i = 0; i < a.Lsel; ++i)
-            {
-                NttArgs &dst = (lazy8 && c->primes[a.selp.idx[i]] < (1ull << 60)) ? lo : hi;
-                dst.selp.idx[dst.Lsel] = a.selp.idx[i];
-                dst.sel.idx[dst.Lsel++] = a.sel.idx[i];
-            }
-            if (lo.Lsel)
-            {
-                launch_fwd_mode<LOGN, M_LAZY8>(c, lo, s);
-            }
-            if (hi.Lsel)
-            {
-                launch_fwd_mode<LOGN, M_GUARD2>(c, hi, s);
-            }
-            break;
-        }
-        case M_NOGUARD: launch_fwd_mode<LOGN, M_NOGUARD>(c, a, s); break;
-        case M_FPN: launch_fwd_mode<LOGN, M_FPN>(c, a, s); break;
-        default: launch_fwd_mode<LOGN, M_FPR>(c, a, s); break;
-        }
+        MOAI_TRY((dispatch<M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR>("forward transform mode ", mode, [&](auto MD) {
+            launch_fwd_mode<LOGN, decltype(MD)::value>(c, a, s);
+            return MOAI_OK;
+        })));
     }
+    return MOAI_OK;
 }
 
 // inverse transform: rows of primes below 2^51 run in exact FP64 arithmetic like the forward transform (FPN / FPR, modarith.hip.h
@@ -115,19 +131,19 @@ static void launch_inv_class(NttArgs a, hipStream_t s)
 template <int LOGN>
 static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    static const long lazy8 = env_long("MOAI_NTT_LAZY8", 1);
     NttArgs cls[4] = { base, base, base, base }; // exact, lazy8, FPN, FPR
     for (NttArgs &a : cls)
     {
         a.Lsel = 0;
     }
-    cls[2].tw = cls[3].tw = c->inv_twf;
-    cls[2].twb = cls[3].twb = c->inv_twfb;
+    const TwPair fp = twiddles(c, M_FPN, true);
+    cls[2].tw = cls[3].tw = fp.tw;
+    cls[2].twb = cls[3].twb = fp.twb;
     for (uint32_t r = 0; r < base.L; ++r)
     {
         const uint32_t prime = base.rows.idx[r];
         const int m = ntt_mode(c, prime);
-        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : ((lazy8 && c->primes[prime] < (1ull << 60)) ? cls[1] : cls[0]));
+        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (lazy8_ok(c, prime) ? cls[1] : cls[0]));
         dst.selp.idx[dst.Lsel] = prime;
         dst.sel.idx[dst.Lsel++] = r;
     }
@@ -137,37 +153,16 @@ static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
     launch_inv_class<LOGN, 3>(cls[3], s);
 }
 
-} // namespace moai
-namespace moai {
-// 36 q < 2^64: forward butterflies may skip the per-stage guard (modarith.hip.h ct_bfly_noguard)
-bool noguard_ok(uint64_t q)
-{
-    return q < (~0ull) / 36;
-}
-
-// the arithmetic mode of the forward transform under context prime `prime` (modarith.hip.h M_*):
-// FP64 below 2^51 (MOAI_NTT_FP=0 keeps everything on the integer units), else integer with or without guards
-int ntt_mode(const moai_ctx *c, uint32_t prime)
-{
-    static const long fp = env_long("MOAI_NTT_FP", 1);
-    const int m = (int)c->pc_host[prime].fp_mode;
-    if (fp && m)
-    {
-        return m;
-    }
-    return noguard_ok(c->primes[prime]) ? M_NOGUARD : M_GUARD;
-}
-
 // single-launch transform (ntt_coop); its queue state lives in a per-stream arena
 static size_t coop_grid(const moai_ctx *c)
 {
-    static const long wpc = env_long("MOAI_NTT_COOP_WPC", 4);
+    const long wpc = tuning(K_NTT_COOP_WPC);
     return (size_t)c->num_cu * (size_t)(wpc > 0 ? wpc : 4);
 }
 
 static uint32_t coop_delay()
 {
-    static const long d = env_long("MOAI_NTT_COOP_DELAY", 4);
+    const long d = tuning(K_NTT_COOP_DELAY);
     return (uint32_t)(d > 0 ? d : 1);
 }
 
@@ -181,10 +176,8 @@ static size_t coop_state_bytes(const moai_ctx *c, size_t rows)
     return sizeof(CoopState) + sizeof(uint32_t) * (rows + 8 * coop_steps_cap(c, rows));
 }
 
-template <int LOGN>
 static int launch_coop(moai_ctx *c, const NttArgs &base, bool inverse, void *state_mem, hipStream_t s)
 {
-    static const long occ = env_long("MOAI_NTT_COOP_OCC", 4);
     NttArgs a = base;
     const uint32_t rows = a.n_poly * a.L;
     const uint32_t grid = (uint32_t)coop_grid(c);
@@ -197,28 +190,15 @@ static int launch_coop(moai_ctx *c, const NttArgs &base, bool inverse, void *sta
     ca.rowmap = ca.done + rows;
     MOAI_HIP_CHECK(hipMemsetAsync(state_mem, 0, coop_state_bytes(c, rows), s));
     a.total_work = grid;
-    if (occ == 3)
-    {
-        if (inverse)
-        {
-            hipLaunchKernelGGL((ntt_coop<LOGN, true, 3>), dim3(grid), dim3(256), 0, s, a, ca);
-        }
-        else
-        {
-            hipLaunchKernelGGL((ntt_coop<LOGN, false, 3>), dim3(grid), dim3(256), 0, s, a, ca);
-        }
-    }
-    else
-    {
-        if (inverse)
-        {
-            hipLaunchKernelGGL((ntt_coop<LOGN, true, 4>), dim3(grid), dim3(256), 0, s, a, ca);
-        }
-        else
-        {
-            hipLaunchKernelGGL((ntt_coop<LOGN, false, 4>), dim3(grid), dim3(256), 0, s, a, ca);
-        }
-    }
+    MOAI_TRY(dispatch_logn(c->logn, [&](auto LG) {
+        return dispatch<3, 4>("ntt_coop occupancy ", tuning(K_NTT_COOP_OCC) == 3 ? 3 : 4, [&](auto OCC) {
+            return dispatch<0, 1>("direction ", inverse, [&](auto INV) {
+                hipLaunchKernelGGL((ntt_coop<decltype(LG)::value, decltype(INV)::value != 0, decltype(OCC)::value>), dim3(grid), dim3(256), 0,
+                                   s, a, ca);
+                return MOAI_OK;
+            });
+        });
+    }));
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }
@@ -243,30 +223,12 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
     {
         return set_error(MOAI_EINVAL, "batch too large for one launch");
     }
-    NttArgs a;
-    a.data = data;
-    a.tw = inverse ? c->inv_tw : c->fwd_tw;
-    a.twb = inverse ? c->inv_twb : c->fwd_twb;
-    a.pc = c->pc;
-    a.rows = rows;
-    for (size_t r = 0; r < MOAI_MAX_RNS; ++r)
-    {
-        a.sel.idx[r] = (uint32_t)(r < L ? r : 0);
-        a.selp.idx[r] = rows.idx[r < L ? r : 0];
-    }
-    a.Lsel = (uint32_t)L;
-    a.L = (uint32_t)L;
-    a.n_poly = (uint32_t)n_poly;
-    a.total_work = 0;
-    a.src = nullptr;
-    a.src_stride = a.src_off = 0;
-    static const long ldstw = env_long("MOAI_NTT_LDSTW", 1);
-    a.lds_twiddles = ldstw ? 1u : 0u;
+    NttArgs a = ntt_args(c, data, n_poly, L, rows, inverse);
     const int logn = c->logn;
-    static const long coop_on = env_long("MOAI_NTT_COOP", 0);
+    const bool naive = tuning(K_NTT_NAIVE) != 0, coop = tuning(K_NTT_COOP) != 0;
     if (src)
     {
-        if (naive_requested() || logn <= 11 || coop_on)
+        if (naive || logn <= 11 || coop)
         {
             // the paths that transform in place: bring the slice over first
             const size_t row_bytes = c->n * sizeof(uint64_t);
@@ -280,7 +242,7 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
             a.src_off = (uint32_t)src_off_rows;
         }
     }
-    if (naive_requested() && logn >= 1)
+    if (naive && logn >= 1)
     {
         uint32_t bx = (uint32_t)(((c->n >> 1) + 255) / 256);
         dim3 grid(bx, (uint32_t)(n_poly * L));
@@ -315,69 +277,29 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
         MOAI_LAUNCH_CHECK();
         return MOAI_OK;
     }
+    if (coop)
     {
         // opt-in (MOAI_NTT_COOP=1): one persistent launch per transform, the two passes meeting in L2.
         // Measured on MI355X (round 1): no faster than two launches -- L2 is write-through, so only the
         // second-pass reads could be saved, and keeping enough rows in flight to avoid dependency stalls
         // overflows the 4 MiB L2.
-        static const long coop = env_long("MOAI_NTT_COOP", 0);
-        if (coop)
-        {
-            void *st = nullptr;
-            int rc = reserve_for_stream(c, (void *)((uintptr_t)s ^ 1u), coop_state_bytes(c, n_poly * L), &st, false);
-            if (rc)
-            {
-                return rc;
-            }
-            switch (logn)
-            {
-            case 12:
-                return launch_coop<12>(c, a, inverse, st, s);
-            case 13:
-                return launch_coop<13>(c, a, inverse, st, s);
-            case 14:
-                return launch_coop<14>(c, a, inverse, st, s);
-            case 15:
-                return launch_coop<15>(c, a, inverse, st, s);
-            case 16:
-                return launch_coop<16>(c, a, inverse, st, s);
-            default:
-                return set_error(MOAI_ELOGIC, "unsupported poly_modulus_degree 2^%d", logn);
-            }
-        }
+        void *st = nullptr;
+        MOAI_TRY(reserve_for_stream(c, (void *)((uintptr_t)s ^ 1u), coop_state_bytes(c, n_poly * L), &st, false));
+        return launch_coop(c, a, inverse, st, s);
     }
     // The two passes of one transform exchange the whole polynomial through memory.  Launching them
     // per chunk of polynomials that fits the 256 MiB Infinity Cache lets the second pass read what
-    // the first one just wrote from the cache instead of HBM (MOAI_NTT_CHUNK_MB=0 disables).
+    // the first one just wrote from the cache instead of HBM (MOAI_NTT_CHUNK_MB, 0 = one chunk).
     size_t chunk = n_poly;
+    const long chunk_mb = tuning(K_NTT_CHUNK_MB);
+    if (chunk_mb > 0)
     {
-        static long chunk_mb = -1;
-        if (chunk_mb < 0)
+        chunk = ((size_t)chunk_mb << 20) / (L * c->n * sizeof(uint64_t));
+        if (chunk < 1)
         {
-            const char *e = getenv("MOAI_NTT_CHUNK_MB");
-            chunk_mb = e ? atol(e) : 0;
-        }
-        if (chunk_mb > 0)
-        {
-            size_t per_poly = L * c->n * sizeof(uint64_t);
-            chunk = ((size_t)chunk_mb << 20) / per_poly;
-            if (chunk < 1)
-            {
-                chunk = 1;
-            }
+            chunk = 1;
         }
     }
-#define MOAI_NTT_CASE(LG)               \
-    case LG:                            \
-        if (inverse)                    \
-        {                               \
-            launch_inv<LG>(c, a, s);    \
-        }                               \
-        else                            \
-        {                               \
-            launch_fwd<LG>(c, a, s);    \
-        }                               \
-        break;
     for (size_t p0 = 0; p0 < n_poly; p0 += chunk)
     {
         a.data = data + p0 * L * c->n;
@@ -386,18 +308,15 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
             a.src = src + p0 * src_stride_rows * c->n;
         }
         a.n_poly = (uint32_t)(n_poly - p0 < chunk ? n_poly - p0 : chunk);
-        switch (logn)
-        {
-            MOAI_NTT_CASE(12)
-            MOAI_NTT_CASE(13)
-            MOAI_NTT_CASE(14)
-            MOAI_NTT_CASE(15)
-            MOAI_NTT_CASE(16)
-        default:
-            return set_error(MOAI_ELOGIC, "unsupported poly_modulus_degree 2^%d", logn);
-        }
+        MOAI_TRY(dispatch_logn(logn, [&](auto LG) {
+            if (inverse)
+            {
+                launch_inv<decltype(LG)::value>(c, a, s);
+                return MOAI_OK;
+            }
+            return launch_fwd<decltype(LG)::value>(c, a, s);
+        }));
     }
-#undef MOAI_NTT_CASE
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }

@@ -90,6 +90,7 @@ SYMBOLS = {
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
+    "moai_reset_tuning": (C.c_int, []),
     "moai_mem_info": (C.c_int, [C.POINTER(sz), C.POINTER(sz)]),
     "moai_op_trace": (C.c_int, [C.c_int]),
     "moai_op_trace_dump": (C.c_size_t, [C.c_char_p, C.c_size_t]),
@@ -621,6 +622,11 @@ class Context:
 
 def set_tuning(name, value):
     _check(lib().moai_set_tuning(name.encode(), int(value)))
+
+
+def reset_tuning():
+    """drop every set_tuning override: the environment's value, else the default, applies again"""
+    _check(lib().moai_reset_tuning())
 
 
 def op_trace(enable):

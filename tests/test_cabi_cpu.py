@@ -44,6 +44,32 @@ def test_ctx_create_validates_before_gpu(moai):
     assert h.value is None
 
 
+def test_tuning_knobs_are_checked_by_name(moai):
+    """moai_set_tuning knows its knobs: a mistyped name is refused and named in the message instead of being ignored."""
+    L = moai.hip.lib()
+    assert L.moai_set_tuning(None, 1) == -1
+    assert L.moai_set_tuning(b"MOAI_KS_TMP_MBS", 1) == -1
+    assert b"MOAI_KS_TMP_MBS" in L.moai_last_error()
+    assert L.moai_set_tuning(b"MOAI_KS_TMP_MB", 1) == 0
+    assert L.moai_reset_tuning() == 0
+    with pytest.raises(moai.MoaiError, match="MOAI_NO_SUCH_KNOB"):
+        moai.hip.set_tuning("MOAI_NO_SUCH_KNOB", 0)
+    moai.hip.reset_tuning()
+
+
+def test_knob_lists_match_the_table():
+    """the knob lists of include/moai_hip.h and INTEGRATION.md are written by hand from the table in csrc/launch.h"""
+    table = open(os.path.join(ROOT, "moai-fhe-transformerinference-public_amd", "csrc", "launch.h")).read()
+    rows = re.findall(r'^\s*X\((\w+), (-?\d+), "', table, re.M)
+    assert len(rows) >= 18
+    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
+    listed = re.findall(r"^ \*   MOAI_(\w+)\s+(-?\d+) ", hdr, re.M)
+    assert listed == rows
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name, _ in rows:
+        assert "`MOAI_%s`" % name in doc, name
+
+
 def test_no_product_dependency_on_oracle():
     """The product path may never import, link or call the oracle (and has no CPU fallback)."""
     pkg = os.path.join(ROOT, "moai-fhe-transformerinference-public_amd")

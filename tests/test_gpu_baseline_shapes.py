@@ -72,10 +72,7 @@ def set_arith(moai, arith):
 
 
 def reset_tuning(moai):
-    moai.hip.set_tuning("MOAI_KS_FP_MIN_ROWS", 16)
-    moai.hip.set_tuning("MOAI_MD_FP_MIN_ROWS", 256)
-    moai.hip.set_tuning("MOAI_KS_TMP_MB", 8192)
-    moai.hip.set_tuning("MOAI_KS_P1_ITEMS", 8)
+    moai.hip.reset_tuning()
 
 
 @pytest.mark.parametrize("L", [35, 15])

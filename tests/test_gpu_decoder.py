@@ -182,7 +182,7 @@ def test_decode_in_chunks(moai):
     try:
         chunked = moai.Context(logn, primes).ckks_decode(d, L, 2.0**40, n_batch=B)
     finally:
-        moai.hip.set_tuning("MOAI_DEC_TMP_MB", 1024)
+        moai.hip.reset_tuning()
     full = moai.Context(logn, primes).ckks_decode(d, L, 2.0**40, n_batch=B)
     assert (_bits(full) == _bits(chunked)).all()
     for b in (0, B - 1):

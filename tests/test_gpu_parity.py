@@ -23,8 +23,7 @@ def ks_arith(request, moai):
     moai.hip.set_tuning("MOAI_KS_FP_MIN_ROWS", 0 if request.param == "fp64" else 1 << 40)
     moai.hip.set_tuning("MOAI_MD_FP_MIN_ROWS", 0 if request.param == "fp64" else 1 << 40)  # the mod-down tail and rescale
     yield request.param
-    moai.hip.set_tuning("MOAI_KS_FP_MIN_ROWS", 16)
-    moai.hip.set_tuning("MOAI_MD_FP_MIN_ROWS", 256)
+    moai.hip.reset_tuning()
 
 
 @pytest.fixture(scope="module")
@@ -772,7 +771,7 @@ def test_ct_pt_matmul_matches_multiply_plain_loop(moai, bits, rows, cols):
         ctx.ct_pt_matmul(dx, dw, dout, rows, cols, 2, L)
         assert (dout.to_numpy((cols, 2, L, n)) == got).all()
     finally:
-        moai.hip.set_tuning("MOAI_MATMUL_FP", 1)
+        moai.hip.reset_tuning()
     for c in (0, cols // 2, cols - 1):
         acc = np.zeros((2, L, n), dtype=np.uint64)
         for j in range(rows):
@@ -898,8 +897,7 @@ def test_fp64_modes_at_their_size_limits(moai):
             for b in range(3):
                 assert (got[b] == octx.rescale(x[b], 2, L)).all(), (L, b)
     finally:
-        moai.hip.set_tuning("MOAI_KS_FP_MIN_ROWS", 16)
-        moai.hip.set_tuning("MOAI_MD_FP_MIN_ROWS", 256)
+        moai.hip.reset_tuning()
 
 
 @pytest.mark.parametrize("logn,bits,L,B", [(12, [51, 46, 46, 51, 58], 4, 3), (12, [60, 46, 51, 61], 3, 2), (13, [46, 46, 51, 58], 2, 1)])
@@ -928,14 +926,6 @@ def test_hoisted_rotations_equal_separate_rotations(moai, logn, bits, L, B, ks_a
         for b in range(B):
             assert (got[r, b] == octx.apply_galois(ct[b], L, e, kk).reshape(2, L, n)).all(), (r, b)
     assert (dct.to_numpy(ct.shape) == ct).all()  # the input is left alone
-    # the FP64 modes take four (or two) rotations per pass over the digits; two at most, and one per pass: the same bits
-    try:
-        for per_pass in (2, 0):
-            moai.hip.set_tuning("MOAI_KS_HOIST_PAIR", per_pass)
-            assert not ctx.apply_galois_hoisted(dct, dout, L, elts, dkeys, corrs, B)
-            assert (dout.to_numpy((len(steps), B, 2, L, n)) == got).all(), per_pass
-    finally:
-        moai.hip.set_tuning("MOAI_KS_HOIST_PAIR", 4)
     # a transparent-looking input: c1 = NTT(polynomial with zero coefficients) -> the identity does not hold -> fallback
     ct0 = ct.copy()
     sparse = np.zeros((1, L, n), dtype=np.uint64)
@@ -943,9 +933,86 @@ def test_hoisted_rotations_equal_separate_rotations(moai, logn, bits, L, B, ks_a
     ct0[0, 1] = octx.ntt(sparse, L)[0]
     dct0 = up(moai, ct0)
     assert ctx.apply_galois_hoisted(dct0, dout, L, elts, dkeys, corrs, B)
-    got = dout.to_numpy((len(steps), B, 2, L, n))
+    got0 = dout.to_numpy((len(steps), B, 2, L, n))
     for r, (e, kk) in enumerate(zip(elts, keys)):
-        assert (got[r, 0] == octx.apply_galois(ct0[0], L, e, kk).reshape(2, L, n)).all(), r
+        assert (got0[r, 0] == octx.apply_galois(ct0[0], L, e, kk).reshape(2, L, n)).all(), r
+    # the FP64 modes take four (or two) rotations per pass over the digits; two at most, and one per pass: the same bits
+    # (last in the test: reset_tuning drops the arithmetic that ks_arith chose as well)
+    try:
+        for per_pass in (2, 0):
+            moai.hip.set_tuning("MOAI_KS_HOIST_PAIR", per_pass)
+            assert not ctx.apply_galois_hoisted(dct, dout, L, elts, dkeys, corrs, B)
+            assert (dout.to_numpy((len(steps), B, 2, L, n)) == got).all(), per_pass
+    finally:
+        moai.hip.reset_tuning()
+
+
+def test_key_switch_plan_cut_into_groups(moai, ks_arith):
+    """switch_key and apply_galois_hoisted launch from one plan (ks_plan): the output moduli ordered by arithmetic mode and
+    cut into groups that fit MOAI_KS_TMP_MB.  N = 2^12, L = 4, batch 3: one output modulus needs 3 * 4 * 4096 * 8 = 393 216
+    bytes of digits, so 1 MiB holds G = 2 of the 5.  With the FP64 modes that is one M_FPR group {51 bit}, two M_FPN groups
+    {46, 46} and {46}, one integer group {special prime}; on the integer units 2 + 2 + 1 of one mode: a cut inside a mode and
+    a mode change at a group border.  Both paths against the oracle bit for bit, then again with all 5 in one group."""
+    logn, L, B = 12, 4, 3
+    n = 1 << logn
+    primes = O.coeff_modulus_create(n, [46, 46, 46, 51, 58])
+    octx, ctx = O.Context(logn, primes), moai.Context(logn, primes)
+    k = len(primes)
+    rng = np.random.default_rng(412)
+    key = O.uniform_rns(rng, primes, (k - 1, 2), n)
+    ct = O.uniform_rns(rng, primes[:L], (B, 2), n)
+    tgt = O.uniform_rns(rng, primes[:L], (B,), n)
+    want_sk = [octx.switch_key(ct[b], tgt[b], key, L).reshape(2, L, n) for b in range(B)]
+    steps = [1, -2, 0]  # 0 = conjugation
+    elts = [ctx.galois_elt_from_step(s) if s else 2 * n - 1 for s in steps]
+    keys = [O.uniform_rns(rng, primes, (k - 1, 2), n) for _ in steps]
+    want_rot = [[octx.apply_galois(ct[b], L, e, kk).reshape(2, L, n) for b in range(B)] for e, kk in zip(elts, keys)]
+    dkey, dt, dsrc = up(moai, key), up(moai, tgt), up(moai, ct)
+    dkeys = [up(moai, kk) for kk in keys]
+    corrs = [ctx.hoist_correction(dk, e, L) for dk, e in zip(dkeys, elts)]
+    dout = moai.DeviceBuffer(len(steps) * B * 2 * L * n)
+
+    def check(what):
+        dct = up(moai, ct)
+        ctx.switch_key(dct, dt, dkey, L, B)
+        got = dct.to_numpy(ct.shape)
+        for b in range(B):
+            assert (got[b] == want_sk[b]).all(), (what, "switch_key", b)
+        assert not ctx.apply_galois_hoisted(dsrc, dout, L, elts, dkeys, corrs, B)  # no fallback: the hoisted kernels ran
+        got = dout.to_numpy((len(steps), B, 2, L, n))
+        for r in range(len(steps)):
+            for b in range(B):
+                assert (got[r, b] == want_rot[r][b]).all(), (what, "hoisted", r, b)
+
+    moai.hip.set_tuning("MOAI_KS_TMP_MB", 1)
+    try:
+        check("G = 2")
+    finally:
+        moai.hip.reset_tuning()
+    check("G = 5")
+
+
+def test_ntt_knobs_through_set_tuning(moai):
+    """the transform's knobs are reached by set_tuning in the running process: with the FP64 rows on the integer units, with
+    the exact integer butterflies, and with the twiddles from memory, forward and inverse equal the oracle"""
+    logn, npoly = 12, 5
+    n = 1 << logn
+    primes = O.coeff_modulus_create(n, [60, 51, 46])
+    octx, ctx = O.Context(logn, primes), moai.Context(logn, primes)
+    L = len(primes)
+    x = O.uniform_rns(np.random.default_rng(9), primes, (npoly,), n)
+    fwd, inv = octx.ntt(x, L), octx.ntt(x, L, inverse=True)
+    for knob in ("MOAI_NTT_FP", "MOAI_NTT_LAZY8", "MOAI_NTT_LDSTW"):
+        moai.hip.set_tuning(knob, 0)
+        try:
+            d = up(moai, x)
+            ctx.ntt_forward(d, npoly, L)
+            assert (d.to_numpy(x.shape) == fwd).all(), knob
+            d = up(moai, x)
+            ctx.ntt_inverse(d, npoly, L)
+            assert (d.to_numpy(x.shape) == inv).all(), knob
+        finally:
+            moai.hip.reset_tuning()
 
 
 @pytest.mark.gpu
