@@ -254,6 +254,7 @@ int moai_mod_drop(moai_ctx *ctx, const uint64_t *in, uint64_t *out, size_t size,
 /* ---- Galois automorphism and key switching -----------------------------------------------------------
  * GaloisTool::apply_galois_ntt SEAL/util/galois.cpp:192-218 with the table of :18-51:
  * out[p][r][i] = in[p][r][table[i]].  galois_elt odd, < 2N.  out must not alias in.
+ * One row per workgroup row like every elementwise entry point: n_poly * L above 65535 is MOAI_EINVAL.
  */
 int moai_galois_permute(moai_ctx *ctx, const uint64_t *in, uint64_t *out, size_t n_poly, size_t L,
                         uint32_t galois_elt, void *stream);

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
         for (int j = 0; j < 4; j++)
         {
             const uint64_t as = mulmod_barrett(a[j], sv[j], q, pc.cr0, pc.cr1);
-            c0[j] = ev[j] >= as ? ev[j] - as : ev[j] + q - as;
+            c0[j] = submod(ev[j], as, q);
         }
     }
     if (g.plain)

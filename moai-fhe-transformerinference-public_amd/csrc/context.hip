@@ -732,6 +732,14 @@ int reserve_for_stream_locked(moai_ctx *c, moai_ctx::Arena &a, size_t bytes)
     }
     return MOAI_OK;
 }
+
+int workspace(moai_ctx *c, size_t bytes, hipStream_t s, void **out)
+{
+    // per-stream arena; a first-time or larger request reallocates with headroom (max of 1.25 x the request and
+    // 1.5 x the old size), which synchronises the device and therefore must not happen under stream capture
+    // (moai_ctx_reserve[_stream] sizes the arena beforehand)
+    return reserve_for_stream(c, (void *)s, bytes ? bytes : 256, out, true);
+}
 } // namespace moai
 
 extern "C" int moai_ctx_reserve(moai_ctx *c, size_t bytes)

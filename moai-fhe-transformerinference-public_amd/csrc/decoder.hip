@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void dec_compose(ComposeArgs g)
         }
         acc = csub(acc, q);
         const uint64_t a = in[(size_t)i * n];
-        const uint64_t d = a >= acc ? a - acc : a + q - acc;
+        const uint64_t d = submod(a, acc, q);
         const Tw ip = g.invp[i];
         const uint64_t v = csub(mul_shoup_lazy(d, ip.w, ip.wq, q), q);
         // x += v * P_i  (the sum is below P_{i+1}: the carry out of word nw - 1 lands in word nw, which is zero)

@@ -181,14 +181,6 @@ struct MacArgs
     uint32_t n2;
 };
 
-__device__ __forceinline__ void mac128(uint64_t &lo, uint64_t &hi, uint64_t a, uint64_t b)
-{
-    uint64_t pl = a * b;
-    uint64_t ph = mulhi64(a, b);
-    lo += pl;
-    hi += ph + (lo < pl ? 1 : 0);
-}
-
 // acc[b][K][slot] = sum_J ops[b][J] (*) key[J][K][prime]  mod q      (evaluator.cpp:2858-2910)
 // blockIdx.y = b
 __global__ __launch_bounds__(256) void keyswitch_mac_kernel(MacArgs g)
@@ -1295,7 +1287,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         {
             return set_error(MOAI_EINVAL, "null key, correction or output (an output must not be the input)");
         }
-        MOAI_TRY(galois_table(c, galois_elts[r], s, &tables[r]));
+        MOAI_TRY(galois_table(c, galois_elts[r], &tables[r]));
         // the inverse permutation is the table of the inverse element (mod 2N, by Newton's iteration on an odd number)
         const uint32_t two_n_mask = (uint32_t)(2 * n - 1);
         uint32_t inv = galois_elts[r];
@@ -1303,7 +1295,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         {
             inv = (inv * (2u - galois_elts[r] * inv)) & two_n_mask;
         }
-        MOAI_TRY(galois_table(c, inv, s, &itables[r]));
+        MOAI_TRY(galois_table(c, inv, &itables[r]));
     }
     std::vector<uint32_t> key_rows(R);
     for (size_t r = 0; r < R; ++r)

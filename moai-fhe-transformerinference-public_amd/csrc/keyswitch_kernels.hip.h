@@ -140,14 +140,6 @@ struct KsP2Args
     uint32_t total_work;
 };
 
-__device__ __forceinline__ void mac128r(uint64_t &lo, uint64_t &hi, uint64_t a, uint64_t b)
-{
-    uint64_t pl = a * b;
-    uint64_t ph = mulhi64(a, b);
-    lo += pl;
-    hi += ph + (lo < pl ? 1 : 0);
-}
-
 // ---- contiguous pass + key MAC, 8 coefficients per thread --------------------------------------------------------
 // With the NTT kernels' 16 coefficients per thread the 2 x 16 128-bit accumulators need 250 VGPRs (two waves
 // per SIMD; measured 6-12 % slower).  Here a workgroup owns a 2048-coefficient tile (8 blocks of 256): radix-8 /
@@ -485,10 +477,10 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
                 }
                 ulonglong2 ka = k0[c];
                 ulonglong2 kb = k1[c];
-                mac128r(lo0[2 * c], hi0[2 * c], vx, ka.x);
-                mac128r(lo0[2 * c + 1], hi0[2 * c + 1], vy, ka.y);
-                mac128r(lo1[2 * c], hi1[2 * c], vx, kb.x);
-                mac128r(lo1[2 * c + 1], hi1[2 * c + 1], vy, kb.y);
+                mac128(lo0[2 * c], hi0[2 * c], vx, ka.x);
+                mac128(lo0[2 * c + 1], hi0[2 * c + 1], vy, ka.y);
+                mac128(lo1[2 * c], hi1[2 * c], vx, kb.x);
+                mac128(lo1[2 * c + 1], hi1[2 * c + 1], vy, kb.y);
             }
         }
         // no barrier here: the next digit writes buffer A, whose readers all passed the second barrier above,
@@ -572,8 +564,8 @@ __global__ __launch_bounds__(256) void ks_hoist_correction_kernel(HoistCorrArgs 
             const uint64_t delta = barrett64(g.pc[J].q, q, cr1);
             const ulonglong2 kv =
                 (reinterpret_cast<const ulonglong2 *>(g.key) + ((size_t)(J * 2 + K) * g.krows + (slot == g.L ? g.krows - 1 : slot)) * g.n2)[j];
-            mac128r(lx, hx, kv.x, delta);
-            mac128r(ly, hy, kv.y, delta);
+            mac128(lx, hx, kv.x, delta);
+            mac128(ly, hy, kv.y, delta);
         }
         const ulonglong2 m = mk[j];
         ulonglong2 r;
@@ -706,8 +698,8 @@ __global__ __launch_bounds__(256, 4) void ks_hoisted_mac(HoistMacArgs a)
 #pragma unroll
             for (int e = 0; e < 8; ++e)
             {
-                mac128r(lo0[e], hi0[e], xs[e], kas[e]);
-                mac128r(lo1[e], hi1[e], xs[e], kbs[e]);
+                mac128(lo0[e], hi0[e], xs[e], kas[e]);
+                mac128(lo1[e], hi1[e], xs[e], kbs[e]);
             }
         }
     }

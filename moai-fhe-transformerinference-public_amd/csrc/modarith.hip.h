@@ -58,6 +58,80 @@ __device__ __forceinline__ uint64_t barrett64(uint64_t x, uint64_t q, uint64_t c
     return csub(x - t * q, q);
 }
 
+// x - y mod q for canonical x, y
+__device__ __forceinline__ uint64_t submod(uint64_t x, uint64_t y, uint64_t q)
+{
+    return x >= y ? x - y : x + q - y;
+}
+
+// (hi:lo) += a * b, modulo 2^128
+__device__ __forceinline__ void mac128(uint64_t &lo, uint64_t &hi, uint64_t a, uint64_t b)
+{
+    uint64_t pl = a * b;
+    uint64_t ph = mulhi64(a, b);
+    lo += pl;
+    hi += ph + (lo < pl ? 1 : 0);
+}
+
+// ---- lane pairs: the two coefficients of one 16-byte access, canonical in and out ------------------------------------
+__device__ __forceinline__ ulonglong2 add2(ulonglong2 x, ulonglong2 y, uint64_t q)
+{
+    return make_ulonglong2(csub(x.x + y.x, q), csub(x.y + y.y, q));
+}
+__device__ __forceinline__ ulonglong2 sub2(ulonglong2 x, ulonglong2 y, uint64_t q)
+{
+    return make_ulonglong2(submod(x.x, y.x, q), submod(x.y, y.y, q));
+}
+__device__ __forceinline__ ulonglong2 neg2(ulonglong2 x, uint64_t q)
+{
+    return make_ulonglong2(x.x ? q - x.x : 0, x.y ? q - x.y : 0);
+}
+__device__ __forceinline__ ulonglong2 mulmod2(ulonglong2 x, ulonglong2 y, uint64_t q, uint64_t cr0, uint64_t cr1)
+{
+    return make_ulonglong2(mulmod_barrett(x.x, y.x, q, cr0, cr1), mulmod_barrett(x.y, y.y, q, cr0, cr1));
+}
+// acc + x * y, each lane's product added and reduced before the other lane's
+__device__ __forceinline__ ulonglong2 addmul2(ulonglong2 acc, ulonglong2 x, ulonglong2 y, uint64_t q, uint64_t cr0, uint64_t cr1)
+{
+    return make_ulonglong2(csub(acc.x + mulmod_barrett(x.x, y.x, q, cr0, cr1), q), csub(acc.y + mulmod_barrett(x.y, y.y, q, cr0, cr1), q));
+}
+
+// ---- the 128-bit sums of a lane pair -----------------------------------------------------------------------------------
+// Products of residues are accumulated without reduction (mac2) and brought back below q with one Barrett step (fold2 /
+// reduce2); the canonical residues of a sum do not depend on when the reductions happen.  moai_ctx_create accepts primes
+// below 2^61 only, so a product of two residues is below 2^122 and 63 of them on top of a folded sum or a base below 2^61
+// stay below 2^128 (and far inside barrett128's range).  When to fold is the caller's business: every kernel states its
+// own period and why it fits.
+// The accumulator is four words (lx, hx: the x lane's low and high word; ly, hy: the y lane's) that the kernel declares,
+// zeroed, as plain locals or as elements of plain arrays, and that these functions take by reference.  Not a struct on
+// purpose: words that sit in a struct, or whose addresses pass through one, are allocated to registers differently once
+// they are indexed in an unrolled loop (ct_pt_matmul_kernel: 150 instead of 166 VGPRs), and this layer is meant to compile
+// to exactly what the hand-written sums did.
+__device__ __forceinline__ void seed2(uint64_t &lx, uint64_t &hx, uint64_t &ly, uint64_t &hy, ulonglong2 base)
+{
+    lx = base.x;
+    ly = base.y;
+    hx = hy = 0;
+}
+__device__ __forceinline__ void mac2(uint64_t &lx, uint64_t &hx, uint64_t &ly, uint64_t &hy, ulonglong2 a, ulonglong2 b)
+{
+    mac128(lx, hx, a.x, b.x);
+    mac128(ly, hy, a.y, b.y);
+}
+__device__ __forceinline__ void mac2(uint64_t &lx, uint64_t &hx, uint64_t &ly, uint64_t &hy, ulonglong2 a, uint64_t s)
+{
+    mac128(lx, hx, a.x, s);
+    mac128(ly, hy, a.y, s);
+}
+__device__ __forceinline__ ulonglong2 reduce2(uint64_t lx, uint64_t hx, uint64_t ly, uint64_t hy, uint64_t q, uint64_t cr0, uint64_t cr1)
+{
+    return make_ulonglong2(barrett128(lx, hx, q, cr0, cr1), barrett128(ly, hy, q, cr0, cr1));
+}
+__device__ __forceinline__ void fold2(uint64_t &lx, uint64_t &hx, uint64_t &ly, uint64_t &hy, uint64_t q, uint64_t cr0, uint64_t cr1)
+{
+    seed2(lx, hx, ly, hy, reduce2(lx, hx, ly, hy, q, cr0, cr1));
+}
+
 // Cooley-Tukey butterfly, Harvey lazy form: x, y in [0, 4q) -> [0, 4q)   (SEAL/util/ntt.h:30-61,
 // dwthandler.h:110-163)
 __device__ __forceinline__ void ct_bfly(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t q, uint64_t q2)

@@ -1266,3 +1266,132 @@ def test_gather_and_scatter_blocks_copy_every_word(moai, n_blocks, words):
         ctx.gather_blocks(blocks[:1] * 65, packed, 2)
     with pytest.raises(Exception):
         ctx.gather_blocks(blocks[:1], packed, 3)
+
+
+# ---- lazy 128-bit sums at their worst case: every residue q - 1 under 61-bit primes ------------------------------------------------
+# A sum of T products of residues that are all q - 1 is T (q - 1)^2, the largest value T terms can reach; the expected residues are
+# that closed form in Python integers.  Term counts sit at and one past each kernel's fold period and at its per-launch limit: a
+# kernel that folds one term late wraps 128 bits on exactly these inputs and on no random ones.
+@pytest.fixture(scope="module")
+def worst61(moai):
+    logn = 10
+    n = 1 << logn
+    primes = O.coeff_modulus_create(n, [61, 61, 60])
+    row = np.array([q - 1 for q in primes], dtype=np.uint64)[:, None] * np.ones(n, dtype=np.uint64)  # [L][N]
+
+    def full(*lead, L=len(primes)):
+        return np.ascontiguousarray(np.broadcast_to(row[:L], tuple(lead) + (L, n)))
+
+    def want(products, base, L=len(primes)):
+        """(base ? q - 1 : 0) + products (q - 1)^2 mod q per row, as [L][N]"""
+        vals = [((q - 1 if base else 0) + products * (q - 1) * (q - 1)) % q for q in primes[:L]]
+        return np.array(vals, dtype=np.uint64)[:, None] * np.ones(n, dtype=np.uint64)
+
+    return n, primes, moai.Context(logn, primes), full, want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("terms", [16, 17])
+def test_pointer_sums_hold_all_q_minus_1_operands(moai, worst61, terms):
+    """moai_scalar_dot, moai_vector_dot and moai_ct_dot_ptrs (sixteen terms per launch) on a base of q - 1"""
+    n, primes, ctx, full, want = worst61
+    L = len(primes)
+    ct = up(moai, full(2))
+    xs = [ct] * terms
+    sc = np.array([[q - 1 for q in primes]] * terms, dtype=np.uint64)
+    acc = up(moai, full(2))
+    ctx.scalar_dot(xs, sc, acc, acc, 2, L)
+    assert (acc.to_numpy((2, L, n)) == want(terms, True)[None]).all()
+    acc = up(moai, full(2))
+    ctx.vector_dot(xs, up(moai, full(terms)), acc, acc, 2, L)
+    assert (acc.to_numpy((2, L, n)) == want(terms, True)[None]).all()
+    acc = up(moai, full(3))
+    ctx.ct_dot_ptrs(xs, xs, acc, acc, L)
+    got = acc.to_numpy((3, L, n))
+    for k, products in enumerate((terms, 2 * terms, terms)):  # (x0 y0, x0 y1 + x1 y0, x1 y1)
+        assert (got[k] == want(products, True)).all(), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [16, 17, 32])
+def test_ct_dot_holds_all_q_minus_1_operands(moai, worst61, count):
+    """moai_ct_dot folds every sixteen terms: 32 products in the middle component"""
+    n, primes, ctx, full, want = worst61
+    L = len(primes)
+    x = up(moai, full(count, 2))
+    out = moai.DeviceBuffer(3 * L * n)
+    ctx.ct_dot(x, x, out, count, L)
+    got = out.to_numpy((3, L, n))
+    for k, products in enumerate((count, 2 * count, count)):
+        assert (got[k] == want(products, False)).all(), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_poly", [1, 5])  # one polynomial per thread; four per thread with a short last group
+@pytest.mark.parametrize("terms", [32, 33, 64])
+def test_ct_pt_dot_holds_all_q_minus_1_operands(moai, worst61, terms, n_poly):
+    """moai_ct_pt_dot and moai_ct_pt_dot2 fold every 32 terms and take at most 64; the second sum runs over the leading 33 terms (all
+    32 where there are no more)"""
+    n, primes, ctx, full, want = worst61
+    L = len(primes)
+    x, p = up(moai, full(n_poly)), up(moai, full(1))
+    zeros = [0] * terms
+    out, out2 = moai.DeviceBuffer(n_poly * L * n), moai.DeviceBuffer(n_poly * L * n)
+    ctx.ct_pt_dot(x, p, out, zeros, zeros, n_poly, L)
+    assert (out.to_numpy((n_poly, L, n)) == want(terms, False)[None]).all()
+    terms2 = min(33, terms)
+    out = moai.DeviceBuffer(n_poly * L * n)
+    ctx.ct_pt_dot2(x, p, out, out2, zeros, zeros, zeros[:terms2], n_poly, L)
+    assert (out.to_numpy((n_poly, L, n)) == want(terms, False)[None]).all()
+    assert (out2.to_numpy((n_poly, L, n)) == want(terms2, False)[None]).all()
+
+
+@pytest.mark.gpu
+def test_ct_pt_dot_rows_holds_all_q_minus_1_operands(moai, worst61):
+    """moai_ct_pt_dot_rows cuts the rows into min(8192 / blocks, rows, 64) slices and folds every 32 rows since the last fold: with
+    64 * 33 rows of 2^10 coefficients (4 blocks, so 64 slices) every slice sums 33 rows"""
+    n, primes, ctx, full, want = worst61
+    L, rows = 2, 64 * 33
+    x, p = up(moai, full(rows, 1, L=L)), up(moai, full(rows, L=L))
+    o1, o2 = moai.DeviceBuffer(L * n), moai.DeviceBuffer(L * n)
+    ctx.ct_pt_dot_rows(x, p, None, o1, None, rows, 1, L)
+    assert (o1.to_numpy((L, n)) == want(rows, False, L)).all()
+    o1 = moai.DeviceBuffer(L * n)
+    ctx.ct_pt_dot_rows(x, p, p, o1, o2, rows, 1, L)  # two sums in one pass
+    assert (o1.to_numpy((L, n)) == want(rows, False, L)).all()
+    assert (o2.to_numpy((L, n)) == want(rows, False, L)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", [32, 33, 64])
+def test_ct_pt_matmul_integer_kernel_holds_all_q_minus_1_operands(moai, worst61, rows):
+    """moai_ct_pt_matmul's integer kernel folds every 32 rows; 17 columns are one full group of sixteen and a group of one"""
+    n, primes, ctx, full, want = worst61
+    L, cols = len(primes), 17
+    x = up(moai, full(rows, 2))
+    w = up(moai, np.ascontiguousarray(np.broadcast_to(np.array([q - 1 for q in primes], dtype=np.uint64)[:, None, None], (L, rows, cols))))
+    out = moai.DeviceBuffer(cols * 2 * L * n)
+    moai.hip.set_tuning("MOAI_MATMUL_FP", 0)
+    try:
+        ctx.ct_pt_matmul(x, w, out, rows, cols, 2, L)
+    finally:
+        moai.hip.reset_tuning()
+    assert (out.to_numpy((cols, 2, L, n)) == want(rows, False)[None, None]).all()
+
+
+@pytest.mark.gpu
+def test_galois_permute_row_limit(moai):
+    """a row-per-block launch takes at most 65535 rows: moai_galois_permute permutes that many and refuses one more like its siblings"""
+    logn = 4
+    n = 1 << logn
+    primes = O.coeff_modulus_create(n, [40])
+    ctx = moai.Context(logn, primes)
+    rng = np.random.default_rng(65535)
+    x = rng.integers(0, primes[0], size=(65536, 1, n), dtype=np.uint64)
+    dx, do = up(moai, x), moai.DeviceBuffer(x.size)
+    elt = ctx.galois_elt_from_step(1)
+    with pytest.raises(moai.MoaiError, match=r"rows \(limit 65535\)"):
+        ctx.galois_permute(dx, do, 65536, 1, elt)
+    ctx.galois_permute(dx, do, 65535, 1, elt)
+    tab = O.galois_table_ntt(logn, elt)
+    assert (do.to_numpy((65535, 1, n), words=65535 * n) == x[:65535][:, :, tab]).all()
