@@ -65,6 +65,8 @@ size_t moai_ctx_coeff_count(const moai_ctx *ctx);
 size_t moai_ctx_prime_count(const moai_ctx *ctx);
 /* psi = minimal primitive 2N-th root of prime i (NTTTables::get_root) */
 uint64_t moai_ctx_root(const moai_ctx *ctx, size_t prime);
+/* prime i of the context as moai_ctx_create received it; 0 when i is out of range */
+uint64_t moai_ctx_prime(const moai_ctx *ctx, size_t prime);
 
 /* ---- memory / streams (the device arena behind seal::DynArray / MemoryPool, SEAL/dynarray.h) -- */
 int moai_malloc(void **dptr, size_t bytes);
@@ -470,6 +472,37 @@ int moai_kswitch_keygen_seeded(moai_ctx *ctx, const uint8_t *noise_key, const ui
 /* Ciphertext::expand_seed, SEAL/ciphertext.cpp:118-188 */
 int moai_expand_seeded(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const uint64_t *c0, uint64_t *out, size_t count, size_t L,
                        const uint32_t *prime_index, void *stream);
+
+/* ---- SEAL's own format: the generator of seeded objects ------------------------------------------------------------------
+ * A SEAL client ships symmetric ciphertexts and switching keys seeded: one polynomial of data and a 64-byte seed from which
+ * Ciphertext::expand_seed redraws the other with SEAL's default generator, Blake2xb in counter mode (buffer c of 4096 bytes is a
+ * hash of (seed, c) alone).  These entry points are that generator and the sampler on top of it, bit for bit; the byte format
+ * itself is host work (seal_shim/seal/moai_seal_format.h).  Shake256-seeded objects are not supported.
+ * moai_seal_prng_bytes: out (device, n_blocks * 4096 bytes, 16-byte aligned) = buffers first_block .. first_block + n_blocks - 1
+ * of Blake2xbPRNG(seed).
+ * moai_seal_sample_uniform: for every b < count, out + b * stride_words as [L][N] (rows under prime_index, NULL = 0..L-1) is
+ * what sample_poly_uniform writes from a fresh Blake2xbPRNG(seeds[b]): the first L N little-endian words of the stream are the
+ * candidates in row-major order; in row j a word is accepted iff it is below (2^64 - 1) - ((2^64 - 1) mod q_j) - 1 and then
+ * reduced mod q_j; a rejected word is replaced by the next unread word of the same stream until one is accepted, rejections
+ * served in order of row, then coefficient.  With stride_words = 2 L N and out pointing at polynomial 1 this fills c1 of a
+ * batch of ciphertexts or of the digits of a switching key; no word outside the count targets is touched.  stride_words >= L N,
+ * and even when count > 1; out 16-byte aligned; count >= 1.
+ * rejected: NULL, or two device uint32_t that the caller zeroes: [0] is incremented by the number of stream words rejected,
+ * [1] is set to 1 when a polynomial's replacements ran over the bound of 2 L N + 512 tail words (no loop on the device is
+ * unbounded); the words not yet replaced then stay 2^64 - 1, which moai_check_residues reports.
+ * moai_check_residues: sets *invalid (device, zeroed by the caller) to non-zero when a residue of data [n_poly][L][N] is >= its
+ * prime, and otherwise leaves it alone: the flag of moai_unpack_rows for rows that arrive unpacked.
+ * Validation as above: MOAI_EINVAL with a message before anything is enqueued; no call synchronises. */
+/* Blake2xbPRNG::refill_buffer, SEAL/randomgen.cpp:201-211 over blake2xb, SEAL/util/blake2xb.c:32-181 */
+int moai_seal_prng_bytes(moai_ctx *ctx, const uint8_t *seed /* host, 64 bytes */, uint64_t first_block, uint64_t n_blocks, void *out,
+                         void *stream);
+/* sample_poly_uniform, SEAL/util/rlwe.cpp:137-166, with a generator per polynomial as in Ciphertext::expand_seed,
+ * SEAL/ciphertext.cpp:118-151 */
+int moai_seal_sample_uniform(moai_ctx *ctx, const uint8_t *seeds /* host, [count][64] */, uint64_t *out, size_t stride_words, size_t count,
+                             size_t L, const uint32_t *prime_index, uint32_t *rejected /* device [2], or NULL */, void *stream);
+/* is_data_valid_for's residue check, SEAL/valcheck.cpp:302-335 */
+int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index, uint32_t *invalid,
+                        void *stream);
 
 /* ---- tuning -------------------------------------------------------------------------------------------------------
  * moai_set_tuning overrides a performance knob for the whole process; it takes precedence over the environment variable

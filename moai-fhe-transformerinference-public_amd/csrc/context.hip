@@ -776,6 +776,11 @@ extern "C" uint64_t moai_ctx_root(const moai_ctx *c, size_t prime)
     return (c && prime < c->k) ? c->roots[prime] : 0;
 }
 
+extern "C" uint64_t moai_ctx_prime(const moai_ctx *c, size_t prime)
+{
+    return (c && prime < c->k) ? c->primes[prime] : 0;
+}
+
 // ---- memory / stream plumbing ---------------------------------------------------------------------
 extern "C" int moai_malloc(void **dptr, size_t bytes)
 {

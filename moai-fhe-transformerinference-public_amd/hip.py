@@ -28,6 +28,7 @@ SYMBOLS = {
     "moai_ctx_coeff_count": (sz, [vp]),
     "moai_ctx_prime_count": (sz, [vp]),
     "moai_ctx_root": (C.c_uint64, [vp, sz]),
+    "moai_ctx_prime": (C.c_uint64, [vp, sz]),
     "moai_malloc": (C.c_int, [C.POINTER(vp), sz]),
     "moai_free": (C.c_int, [vp]),
     "moai_memcpy_h2d": (C.c_int, [vp, vp, sz, vp]),
@@ -87,6 +88,9 @@ SYMBOLS = {
     "moai_encrypt_symmetric_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_kswitch_keygen_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, vp]),
     "moai_expand_seeded": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
+    "moai_seal_prng_bytes": (C.c_int, [vp, C.c_char_p, C.c_uint64, C.c_uint64, vp, vp]),
+    "moai_seal_sample_uniform": (C.c_int, [vp, C.c_char_p, vp, sz, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
+    "moai_check_residues": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
@@ -603,6 +607,42 @@ class Context:
         out = DeviceBuffer(max(count, 1) * 2 * L * self.n)
         _check(lib().moai_expand_seeded(self.h, self._key(seed), int(seq), _ptr(c0), out.ptr, count, L, self._pidx(prime_index), stream))
         return out
+
+    # --- SEAL's own format (include/moai_hip.h, "SEAL's own format: the generator of seeded objects") --------------
+    def seal_prng_bytes(self, seed, first_block, n_blocks, stream=None):
+        """buffers first_block .. first_block + n_blocks - 1 (4096 bytes each) of SEAL's Blake2xbPRNG(seed), as bytes"""
+        seed = bytes(seed)
+        if len(seed) != 64:
+            raise ValueError("a SEAL generator seed has 64 bytes")
+        out = DeviceBuffer(max(n_blocks, 1) * 512)
+        _check(lib().moai_seal_prng_bytes(self.h, seed, int(first_block), int(n_blocks), out.ptr, stream))
+        return out.to_numpy(stream=stream, words=n_blocks * 512).astype("<u8").tobytes()
+
+    def seal_sample_uniform(self, seeds, L, out=None, stride_words=None, prime_index=None, count_rejected=True, stream=None):
+        """sample_poly_uniform from a fresh Blake2xbPRNG per seed (64 bytes each): polynomial b lands at out + b * stride_words
+        as [L][N] (a new DeviceBuffer [count][L][N] when out is None).  Returns (DeviceBuffer or None, rejected, overflow):
+        the stream words rejected and whether a tail ran over its bound (None, None with count_rejected=False)."""
+        seeds = [bytes(s) for s in seeds]
+        if any(len(s) != 64 for s in seeds):
+            raise ValueError("a SEAL generator seed has 64 bytes")
+        stride_words = L * self.n if stride_words is None else stride_words
+        made = DeviceBuffer(max(len(seeds), 1) * stride_words) if out is None else None
+        flag = DeviceBuffer(1) if count_rejected else None
+        if count_rejected:
+            _check(lib().moai_memset_zero(flag.ptr, 8, stream))
+        _check(lib().moai_seal_sample_uniform(self.h, b"".join(seeds), _ptr(made if out is None else out), stride_words, len(seeds), L,
+                                              self._pidx(prime_index), _ptr(flag), stream))
+        if not count_rejected:
+            return made, None, None
+        word = int(flag.to_numpy(stream=stream)[0])
+        return made, word & 0xFFFFFFFF, bool(word >> 32)
+
+    def check_residues(self, data, n_poly, L, prime_index=None, stream=None):
+        """True when a residue of data [n_poly][L][N] is >= its row's prime"""
+        flag = DeviceBuffer(1)
+        _check(lib().moai_memset_zero(flag.ptr, 8, stream))
+        _check(lib().moai_check_residues(self.h, _ptr(data), n_poly, L, self._pidx(prime_index), flag.ptr, stream))
+        return bool(flag.to_numpy(stream=stream)[0])
 
     def total_coeff_modulus_bit_count(self, L, prime_index=None):
         r = lib().moai_total_coeff_modulus_bit_count(self.h, L, self._pidx(prime_index))

@@ -1,9 +1,11 @@
 // seal/moai_serialization.h -- the wire form of the seal:: surface: save / load / save_size with SEAL's signatures
 // (SEAL/serialization.h, SEAL/serializable.h) over this library's own format.  Included from seal/seal.h.
 //
-// The format is NOT SEAL's and cannot be: SEAL expands seeds with Blake2xb / Shake256 (SEAL/randomgen.cpp), this library with
-// ChaCha20 (include/moai_hip.h, "Stream contract"); the shim's parms_id is its own hash; SEAL has no packed rows.  DESIGN.md
-// section 5.0e specifies it completely and tests/wire_format.py restates it.  In short, little-endian and 8-byte aligned:
+// save writes this library's own format, which is smaller than SEAL's: seeds are expanded with ChaCha20 (include/moai_hip.h,
+// "Stream contract") where SEAL uses Blake2xb / Shake256 (SEAL/randomgen.cpp), the parms_id is the shim's own hash, and rows
+// are bit-packed, which SEAL's format cannot express.  SEAL's own byte format is the other one this surface speaks
+// (seal/moai_seal_format.h): load recognises either from its first byte, and save_seal / save_size_seal write SEAL's.  DESIGN.md
+// section 5.0e specifies this format completely and tests/wire_format.py restates it.  In short, little-endian and 8-byte aligned:
 //
 //   record  = header (120 bytes) + stored x packed polynomial          (moai_pack_rows: every row at its prime's bit length)
 //   header  = magic "MOAIWIRE", u32 version (1), u32 kind, u32 flags (1 seeded, 2 NTT form), u32 polynomial count, u32 N, u32 L,
@@ -137,6 +139,8 @@ namespace seal
         {
             virtual ~Source() = default;
             virtual const std::uint8_t *view(std::size_t bytes) = 0; // valid until the next call
+            virtual int peek() = 0;                                   // the next byte without consuming it, -1 at the end
+            virtual bool stable() const = 0;                          // a view stays valid after the next call
             std::size_t consumed = 0;
         };
         struct BufferSource : Source
@@ -158,6 +162,14 @@ namespace seal
                 }
                 consumed += bytes;
                 return in + consumed - bytes;
+            }
+            int peek() override
+            {
+                return consumed < size ? in[consumed] : -1;
+            }
+            bool stable() const override
+            {
+                return true;
             }
         };
         struct StreamSource : Source
@@ -183,6 +195,15 @@ namespace seal
                 }
                 consumed += bytes;
                 return tmp.data();
+            }
+            int peek() override
+            {
+                const auto c = s.peek();
+                return c == std::istream::traits_type::eof() ? -1 : static_cast<int>(static_cast<unsigned char>(c));
+            }
+            bool stable() const override
+            {
+                return false;
             }
         };
 
@@ -420,6 +441,15 @@ namespace seal
         }
     } // namespace wire
 
+    namespace sealfmt
+    {
+        // seal/moai_seal_format.h: SEAL 4.1's own byte format, compression mode none
+        constexpr int first_byte = 0x5E; // of SEALHeader::magic 0xA15E; this library's own format starts with 'M'
+        inline std::size_t object_bytes(const wire::Object &o);
+        inline std::streamoff save_object(const wire::Object &o, wire::Sink &sink);
+        inline wire::Object load_object(const SEALContext &context, wire::Source &src, std::uint32_t kind, bool check);
+    } // namespace sealfmt
+
     // SEAL/serializable.h: an object that can only be saved -- what the seeded encryptions and key generators return.  It holds
     // c0 of every ciphertext or key digit and the public seed; the uniform halves are never produced on this side.
     template <class T>
@@ -443,6 +473,24 @@ namespace seal
             wire::BufferSink s(out, size);
             return wire::save_object(obj_, s);
         }
+        // SEAL's own format, unseeded: SEAL cannot expand a seed of this side (ChaCha20), so the object is expanded first
+        std::streamoff save_size_seal(compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            return static_cast<std::streamoff>(sealfmt::object_bytes(obj_));
+        }
+        std::streamoff save_seal(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            wire::StreamSink s(stream);
+            return sealfmt::save_object(obj_, s);
+        }
+        std::streamoff save_seal(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const
+        {
+            wire::check_mode(compr_mode);
+            wire::BufferSink s(out, size);
+            return sealfmt::save_object(obj_, s);
+        }
 
     private:
         friend class Encryptor;
@@ -454,8 +502,26 @@ namespace seal
 
 // save / load with SEAL's signatures (SEAL/ciphertext.h:560-720 and the same block of every other type) over two hooks each
 // type defines in seal/moai_serialization_impl.h: to_wire() settles lazy state and describes the object without changing it,
-// from_wire() validates what is specific to the type and only then replaces *this (a failed load leaves it as it was)
+// from_wire() validates what is specific to the type and only then replaces *this (a failed load leaves it as it was).
+// save_seal / save_size_seal write SEAL's own format (seal/moai_seal_format.h), and load takes either format.
 #define MOAI_WIRE_METHODS(KIND)                                                                                         \
+    std::streamoff save_size_seal(compr_mode_type compr_mode = compr_mode_default) const                                \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        return static_cast<std::streamoff>(sealfmt::object_bytes(to_wire()));                                           \
+    }                                                                                                                   \
+    std::streamoff save_seal(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const               \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        wire::StreamSink s(stream);                                                                                     \
+        return sealfmt::save_object(to_wire(), s);                                                                      \
+    }                                                                                                                   \
+    std::streamoff save_seal(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const   \
+    {                                                                                                                   \
+        wire::check_mode(compr_mode);                                                                                   \
+        wire::BufferSink s(out, size);                                                                                  \
+        return sealfmt::save_object(to_wire(), s);                                                                      \
+    }                                                                                                                   \
     std::streamoff save_size(compr_mode_type compr_mode = compr_mode_default) const                                     \
     {                                                                                                                   \
         wire::check_mode(compr_mode);                                                                                   \
@@ -497,7 +563,8 @@ namespace seal
     void from_wire(const SEALContext &context, wire::Object &&o);                                                       \
     std::streamoff load_from(const SEALContext &context, wire::Source &s, bool check)                                   \
     {                                                                                                                   \
-        from_wire(context, wire::load_object(context, s, KIND, "loaded", check));                                       \
+        from_wire(context, s.peek() == sealfmt::first_byte ? sealfmt::load_object(context, s, KIND, check)              \
+                                                           : wire::load_object(context, s, KIND, "loaded", check));     \
         return static_cast<std::streamoff>(s.consumed);                                                                 \
     }
 } // namespace seal

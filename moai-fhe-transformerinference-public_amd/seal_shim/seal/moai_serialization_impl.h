@@ -285,9 +285,47 @@ namespace seal
         sink.put(buf.data(), buf.size());
         return static_cast<std::streamoff>(buf.size());
     }
+    // SEAL's own format: u8 scheme, u64 N, u64 L, L + 1 Modulus objects (the fork's hamming weight and sparse slots do not travel)
+    inline std::streamoff EncryptionParameters::save_size_seal(compr_mode_type compr_mode) const
+    {
+        wire::check_mode(compr_mode);
+        return static_cast<std::streamoff>(sealfmt::parms_bytes(coeff_modulus_.size()));
+    }
+    inline std::streamoff EncryptionParameters::save_seal(seal_byte *out, std::size_t size, compr_mode_type compr_mode) const
+    {
+        wire::check_mode(compr_mode);
+        wire::BufferSink sink(out, size);
+        sealfmt::put_parms(scheme_, poly_modulus_degree_, coeff_modulus_, sink);
+        return save_size_seal();
+    }
+    inline std::streamoff EncryptionParameters::save_seal(std::ostream &stream, compr_mode_type compr_mode) const
+    {
+        wire::check_mode(compr_mode);
+        wire::StreamSink sink(stream);
+        sealfmt::put_parms(scheme_, poly_modulus_degree_, coeff_modulus_, sink);
+        return save_size_seal();
+    }
+    inline std::streamoff EncryptionParameters::load_seal(wire::Source &src)
+    {
+        const sealfmt::Parms p = sealfmt::get_parms(src);
+        EncryptionParameters fresh(static_cast<scheme_type>(p.scheme)); // throws for a scheme this build does not provide
+        fresh.set_poly_modulus_degree(p.n);
+        std::vector<Modulus> cm;
+        for (auto q : p.primes)
+        {
+            cm.emplace_back(q);
+        }
+        fresh.set_coeff_modulus(cm);
+        *this = fresh;
+        return static_cast<std::streamoff>(src.consumed);
+    }
     inline std::streamoff EncryptionParameters::load(const seal_byte *in, std::size_t size)
     {
         wire::BufferSource src(in, size);
+        if (src.peek() == sealfmt::first_byte)
+        {
+            return load_seal(src);
+        }
         const wire::Header h = wire::get_header(src);
         if (h.kind != wire::kind_encryption_parameters || h.count || h.flags || h.L < 1 || h.L > 256 ||
             h.total != sizeof(wire::Header) + 8 * (3 + std::size_t(h.L)))
@@ -312,6 +350,10 @@ namespace seal
     inline std::streamoff EncryptionParameters::load(std::istream &stream)
     {
         wire::StreamSource src(stream);
+        if (src.peek() == sealfmt::first_byte)
+        {
+            return load_seal(src);
+        }
         std::vector<seal_byte> buf(sizeof(wire::Header));
         std::memcpy(buf.data(), src.view(sizeof(wire::Header)), sizeof(wire::Header));
         wire::Header h;

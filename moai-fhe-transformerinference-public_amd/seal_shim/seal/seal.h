@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "moai_hip.h"
+#include "seal/util/blake2b.h"
 
 namespace seal
 {
@@ -1060,6 +1061,11 @@ namespace seal
         }
     } // namespace util
 
+    namespace wire
+    {
+        struct Source;
+    }
+
     class EncryptionParameters
     {
     public:
@@ -1133,8 +1139,13 @@ namespace seal
         std::streamoff save(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const;
         std::streamoff load(std::istream &stream);
         std::streamoff load(const seal_byte *in, std::size_t size);
+        // SEAL's own format (seal/moai_seal_format.h; SEAL/encryptionparams.cpp:15-110); load takes either
+        std::streamoff save_size_seal(compr_mode_type compr_mode = compr_mode_default) const;
+        std::streamoff save_seal(std::ostream &stream, compr_mode_type compr_mode = compr_mode_default) const;
+        std::streamoff save_seal(seal_byte *out, std::size_t size, compr_mode_type compr_mode = compr_mode_default) const;
 
     private:
+        std::streamoff load_seal(wire::Source &src);
         scheme_type scheme_;
         std::size_t poly_modulus_degree_ = 0;
         std::vector<Modulus> coeff_modulus_;
@@ -1160,6 +1171,12 @@ namespace seal
             {
                 return parms_id_;
             }
+            // what Microsoft SEAL calls this level (SEAL/encryptionparams.cpp:124-158): the parms_id inside objects in SEAL's
+            // own format (seal/moai_seal_format.h); parms_id() above stays the shim's own and is what the wire form carries
+            const parms_id_type &seal_parms_id() const noexcept
+            {
+                return seal_parms_id_;
+            }
             std::size_t chain_index() const noexcept
             {
                 return chain_index_;
@@ -1181,6 +1198,7 @@ namespace seal
             friend class SEALContext;
             EncryptionParameters parms_;
             parms_id_type parms_id_ = parms_id_zero;
+            parms_id_type seal_parms_id_ = parms_id_zero;
             std::size_t chain_index_ = 0;
             int total_bits_ = 0;
             std::weak_ptr<const ContextData> prev_;
@@ -1250,7 +1268,9 @@ namespace seal
                     cd->prev_ = prev;
                     prev->next_ = cd;
                 }
+                cd->seal_parms_id_ = util::seal_parms_id(n, std::vector<std::uint64_t>(primes.begin(), primes.begin() + static_cast<std::ptrdiff_t>(count)));
                 impl_->by_id[cd->parms_id_] = cd;
+                impl_->by_seal_id[cd->seal_parms_id_] = cd;
                 impl_->by_count[count] = cd;
                 if (lvl == 0)
                 {
@@ -1273,6 +1293,12 @@ namespace seal
         {
             auto it = impl_->by_id.find(id);
             return it == impl_->by_id.end() ? nullptr : it->second;
+        }
+        // the level SEAL's parms_id names, or null
+        std::shared_ptr<const ContextData> get_context_data_seal(const parms_id_type &seal_id) const
+        {
+            auto it = impl_->by_seal_id.find(seal_id);
+            return it == impl_->by_seal_id.end() ? nullptr : it->second;
         }
         std::shared_ptr<const ContextData> key_context_data() const
         {
@@ -1341,7 +1367,7 @@ namespace seal
             void *stream = nullptr;
             int logn = 0;
             std::size_t n = 0;
-            std::map<parms_id_type, std::shared_ptr<ContextData>> by_id;
+            std::map<parms_id_type, std::shared_ptr<ContextData>> by_id, by_seal_id;
             std::map<std::size_t, std::shared_ptr<ContextData>> by_count;
             std::shared_ptr<ContextData> key, first, last;
             ~Impl()
@@ -1364,6 +1390,7 @@ namespace seal
 } // namespace seal
 
 #include "seal/moai_serialization.h"
+#include "seal/moai_seal_format.h"
 
 namespace seal
 {
