@@ -406,36 +406,15 @@ static int launch_small(moai_ctx *c, bool cbd, const ChaKey &key, uint64_t nonce
     a.rows = rows;
     a.L = (uint32_t)L;
     a.logn = (uint32_t)c->logn;
-    if (cbd)
-    {
-        hipLaunchKernelGGL(cl_small<true>, grid_of(c->n / 8, n_poly), dim3(256), 0, s, a);
-    }
-    else
-    {
-        hipLaunchKernelGGL(cl_small<false>, grid_of(c->n / 8, n_poly), dim3(256), 0, s, a);
-    }
+    hipLaunchKernelGGL(cbd ? cl_small<true> : cl_small<false>, grid_of(c->n / 8, n_poly), dim3(256), 0, s, a);
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }
 
-// items per chunk: per-item scratch `per` bytes within the stream's arena or 1 GiB, whichever is larger
-static size_t cl_chunk(moai_ctx *c, hipStream_t s, size_t per, size_t n, size_t cap)
-{
-    size_t budget = (size_t)1 << 30;
-    {
-        std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
-        auto it = c->ws.find((void *)s);
-        if (it != c->ws.end() && it->second.bytes > budget)
-        {
-            budget = it->second.bytes;
-        }
-    }
-    size_t cb = budget / per;
-    cb = cb < 1 ? 1 : cb;
-    cb = cb > cap ? cap : cb;
-    return cb < n ? cb : n;
-}
+// items per chunk (launch.h chunk_items): within the stream's arena or 1 GiB, whichever is larger
+constexpr size_t CL_CHUNK_FLOOR = (size_t)1 << 30;
 
+// what every entry point checks first; the samplers, which take a raw nonce, pass seq = count = 0
 static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, size_t count)
 {
     if (!c)
@@ -466,11 +445,7 @@ static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, siz
 static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk, const uint64_t *plain,
                     const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, hipStream_t s)
 {
-    int rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
     const ChaKey k = load_key(key);
     const size_t n = c->n, LN = L * n;
     SymArgs a;
@@ -487,42 +462,22 @@ static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64
         a.fac[r] = r < L ? c->primes[c->k - 1] % c->primes[rows.idx[r]] : 0;
     }
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
-    const size_t cb = cl_chunk(c, s, LN * sizeof(uint64_t), n_batch, 65535);
+    const size_t cb = chunk_items(c, s, LN * sizeof(uint64_t), n_batch, 65535, CL_CHUNK_FLOOR);
     void *scratch = nullptr;
-    rc = workspace(c, cb * LN * sizeof(uint64_t), s, &scratch);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, cb * LN * sizeof(uint64_t), s, &scratch));
     uint64_t *e = static_cast<uint64_t *>(scratch);
-    for (size_t b0 = 0; b0 < n_batch; b0 += cb)
-    {
-        const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
-        rc = launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, LN, nb, L, rows, s);
-        if (!rc)
-        {
-            rc = ntt_launch(c, e, nb, L, rows, false, s);
-        }
-        if (rc)
-        {
-            return rc;
-        }
+    return for_chunks(n_batch, cb, [&](size_t b0, size_t nb) {
+        MOAI_TRY(launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, LN, nb, L, rows, s));
+        MOAI_TRY(ntt_launch(c, e, nb, L, rows, false, s));
         a.nonce_a = (CL_UNIFORM << 56) | (seq + b0);
         a.e = e;
         a.plain = plain ? plain + b0 * LN : nullptr;
         a.out = out + b0 * (seed ? 1 : 2) * LN;
         a.digit0 = (uint32_t)b0;
-        if (seed)
-        {
-            hipLaunchKernelGGL(cl_sym_finish<true>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
-        }
-        else
-        {
-            hipLaunchKernelGGL(cl_sym_finish<false>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
-        }
+        hipLaunchKernelGGL(seed ? cl_sym_finish<true> : cl_sym_finish<false>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
         MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }
 
 } // namespace moai
@@ -532,28 +487,9 @@ using namespace moai;
 static int sampler_entry(moai_ctx *c, int kind, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
                          const uint32_t *prime_index, void *stream)
 {
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (!key)
-    {
-        return set_error(MOAI_EINVAL, "null key");
-    }
-    if (c->logn < 3)
-    {
-        return set_error(MOAI_ELOGIC, "client sampling needs N >= 8");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    MOAI_TRY(check_common(c, key, 0, 0));
     RowMap rows;
-    int rc = make_rowmap(c, L, prime_index, &rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(rows_entry(c, L, prime_index, &rows));
     if (n_poly == 0)
     {
         return MOAI_OK;
@@ -570,11 +506,7 @@ static int sampler_entry(moai_ctx *c, int kind, const uint8_t *key, uint64_t non
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
     hipStream_t s = (hipStream_t)stream;
     const ChaKey k = load_key(key);
     const size_t LN = L * c->n;
@@ -596,49 +528,27 @@ static int sampler_entry(moai_ctx *c, int kind, const uint8_t *key, uint64_t non
     return launch_small(c, kind == 2, k, nonce, out, LN, n_poly, L, rows, s);
 }
 
-extern "C" int moai_sample_uniform(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
-                                   const uint32_t *prime_index, void *stream)
-{
-    MOAI_AUDIT(stream, out);
-    trace_op("sample_uniform", L, n_poly);
-    return sampler_entry(c, 0, key, nonce, out, n_poly, L, prime_index, stream);
-}
-
-extern "C" int moai_sample_ternary(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
-                                   const uint32_t *prime_index, void *stream)
-{
-    MOAI_AUDIT(stream, out);
-    trace_op("sample_ternary", L, n_poly);
-    return sampler_entry(c, 1, key, nonce, out, n_poly, L, prime_index, stream);
-}
-
-extern "C" int moai_sample_cbd(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,
-                               const uint32_t *prime_index, void *stream)
-{
-    MOAI_AUDIT(stream, out);
-    trace_op("sample_cbd", L, n_poly);
-    return sampler_entry(c, 2, key, nonce, out, n_poly, L, prime_index, stream);
-}
+// the three samplers: kind 0 uniform, 1 ternary, 2 centred binomial
+#define MOAI_SAMPLER(name, kind)                                                                                                  \
+    extern "C" int moai_sample_##name(moai_ctx *c, const uint8_t *key, uint64_t nonce, uint64_t *out, size_t n_poly, size_t L,   \
+                                      const uint32_t *prime_index, void *stream)                                                 \
+    {                                                                                                                             \
+        MOAI_AUDIT(stream, out);                                                                                                  \
+        trace_op("sample_" #name, L, n_poly);                                                                                     \
+        return sampler_entry(c, kind, key, nonce, out, n_poly, L, prime_index, stream);                                           \
+    }
+MOAI_SAMPLER(uniform, 0)
+MOAI_SAMPLER(ternary, 1)
+MOAI_SAMPLER(cbd, 2)
+#undef MOAI_SAMPLER
 
 static int encrypt_symmetric_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
                                    const uint64_t *plain, uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index,
                                    void *stream)
 {
-    int rc = check_common(c, key, seq, n_batch);
-    if (rc)
-    {
-        return rc;
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    MOAI_TRY(check_common(c, key, seq, n_batch));
     RowMap rows;
-    rc = make_rowmap(c, L, prime_index, &rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(rows_entry(c, L, prime_index, &rows));
     if (n_batch == 0)
     {
         return MOAI_OK;
@@ -679,21 +589,13 @@ static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *
         return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
     }
     const size_t digits = c->k - 1;
-    int rc = check_common(c, key, seq, digits);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(check_common(c, key, seq, digits));
     if (!sk_ntt || !new_key_ntt || !out)
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
     RowMap rows;
-    rc = make_rowmap(c, c->k, nullptr, &rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, c->k, nullptr, &rows));
     return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, (hipStream_t)stream);
 }
 
@@ -730,21 +632,9 @@ extern "C" int moai_expand_seeded(moai_ctx *c, const uint8_t *seed, uint64_t seq
 {
     MOAI_AUDIT(stream, c0, out);
     trace_op("expand_seeded", L, count);
-    int rc = check_common(c, seed, seq, count);
-    if (rc)
-    {
-        return rc;
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    MOAI_TRY(check_common(c, seed, seq, count));
     ExpandArgs a;
-    rc = make_rowmap(c, L, prime_index, &a.rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(rows_entry(c, L, prime_index, &a.rows));
     if (count == 0)
     {
         return MOAI_OK;
@@ -754,18 +644,11 @@ extern "C" int moai_expand_seeded(moai_ctx *c, const uint8_t *seed, uint64_t seq
         return set_error(MOAI_EINVAL, "null argument");
     }
     const size_t LN = L * c->n;
+    if (overlap(c0, count * LN * 8, out, 2 * count * LN * 8))
     {
-        const uintptr_t x = (uintptr_t)c0, y = (uintptr_t)out;
-        if (x < y + 2 * count * LN * 8 && y < x + count * LN * 8)
-        {
-            return set_error(MOAI_EINVAL, "c0 and out overlap");
-        }
+        return set_error(MOAI_EINVAL, "c0 and out overlap");
     }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
     a.seed = load_key(seed);
     a.nonce = (CL_UNIFORM << 56) | seq;
     a.c0 = c0;
@@ -783,15 +666,9 @@ extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t
 {
     MOAI_AUDIT(stream, pk, plain, out);
     trace_op("encrypt_asymmetric", L, n_batch);
-    int rc = check_common(c, key, seq, n_batch);
-    if (rc)
-    {
-        return rc;
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    MOAI_TRY(check_common(c, key, seq, n_batch));
+    RowMap rows;
+    MOAI_TRY(rows_entry(c, L, nullptr, &rows));
     if (n_batch == 0)
     {
         return MOAI_OK;
@@ -800,59 +677,31 @@ extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
     // SEAL/encryptor.cpp:122-162: below the key level, encrypt at the previous level (one more prime) and divide by it
     const bool divide = L < c->k;
     const size_t M = divide ? L + 1 : L;
     const size_t n = c->n, MN = M * n, LN = L * n;
-    RowMap rows;
-    rc = make_rowmap(c, M, nullptr, &rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(make_rowmap(c, M, nullptr, &rows));
     hipStream_t s = (hipStream_t)stream;
     const ChaKey k = load_key(key);
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
     // scratch per ciphertext: u, e0, e1 [3][M][N], and the rescale's own workspace [2][M][N] at the head of the arena
     const size_t per = (divide ? 5 : 3) * MN * sizeof(uint64_t);
-    const size_t cb = cl_chunk(c, s, per, n_batch, 32767);
+    const size_t cb = chunk_items(c, s, per, n_batch, 32767, CL_CHUNK_FLOOR);
     const size_t head = divide ? rescale_ws_bytes(c, M, 2 * cb) : 0;
     void *wsp = nullptr;
-    rc = workspace(c, head + 3 * cb * MN * sizeof(uint64_t), s, &wsp);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, head + 3 * cb * MN * sizeof(uint64_t), s, &wsp));
     uint64_t *u = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + head);
-    for (size_t b0 = 0; b0 < n_batch; b0 += cb)
-    {
-        const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
+    return for_chunks(n_batch, cb, [&](size_t b0, size_t nb) {
         // u [nb][M][N] directly followed by e [nb][2][M][N]: laid out by THIS chunk's count, so that the 3 nb polynomials the
         // transform covers are exactly u and e also when the last chunk is short
         uint64_t *e = u + nb * MN;
-        rc = launch_small(c, false, k, (CL_TERNARY << 56) | (seq + b0), u, MN, nb, M, rows, s);
-        if (!rc)
-        {
-            rc = launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, 2 * MN, nb, M, rows, s);
-        }
-        if (!rc)
-        {
-            rc = launch_small(c, true, k, (CL_NOISE1 << 56) | (seq + b0), e + MN, 2 * MN, nb, M, rows, s);
-        }
-        if (!rc)
-        {
-            // u and e are adjacent: one transform of 3 nb polynomials
-            rc = ntt_launch(c, u, 3 * nb, M, rows, false, s);
-        }
-        if (rc)
-        {
-            return rc;
-        }
+        MOAI_TRY(launch_small(c, false, k, (CL_TERNARY << 56) | (seq + b0), u, MN, nb, M, rows, s));
+        MOAI_TRY(launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, 2 * MN, nb, M, rows, s));
+        MOAI_TRY(launch_small(c, true, k, (CL_NOISE1 << 56) | (seq + b0), e + MN, 2 * MN, nb, M, rows, s));
+        // u and e are adjacent: one transform of 3 nb polynomials
+        MOAI_TRY(ntt_launch(c, u, 3 * nb, M, rows, false, s));
         PkArgs a;
         a.u = u;
         a.e = e;
@@ -868,11 +717,7 @@ extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t
         if (divide)
         {
             // divide_and_round_q_last_ntt_inplace (SEAL/util/rns.cpp:830-901), the rescale's kernels
-            rc = rescale_nolock(c, e, out + b0 * 2 * LN, 2, M, nb, s);
-            if (rc)
-            {
-                return rc;
-            }
+            MOAI_TRY(rescale_nolock(c, e, out + b0 * 2 * LN, 2, M, nb, s));
             if (plain)
             {
                 hipLaunchKernelGGL(cl_add_c0, grid_of(LN / 2, nb), dim3(256), 0, s, out + b0 * 2 * LN, plain + b0 * LN, c->pc,
@@ -880,6 +725,6 @@ extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t
                 MOAI_LAUNCH_CHECK();
             }
         }
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <thread>
 
+#include "hostmath.h"
 #include "launch.h"
 
 namespace moai {
@@ -160,29 +161,6 @@ int enter_device(const moai_ctx *c)
     return MOAI_OK;
 }
 
-typedef unsigned __int128 u128;
-
-static inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q)
-{
-    return (uint64_t)(((u128)a * b) % q);
-}
-
-static uint64_t powmod(uint64_t a, uint64_t e, uint64_t q)
-{
-    uint64_t r = 1;
-    a %= q;
-    while (e)
-    {
-        if (e & 1)
-        {
-            r = mulmod(r, a, q);
-        }
-        a = mulmod(a, a, q);
-        e >>= 1;
-    }
-    return r;
-}
-
 static bool is_prime_u64(uint64_t n)
 {
     static const uint64_t bases[] = { 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37 };
@@ -233,11 +211,6 @@ static bool is_prime_u64(uint64_t n)
     return true;
 }
 
-static inline uint32_t bitrev(uint32_t x, int bits)
-{
-    return bits ? (__builtin_bitreverse32(x) >> (32 - bits)) : 0;
-}
-
 // The smallest primitive 2N-th root of unity mod q: the value the reference's
 // try_minimal_primitive_root converges to (SEAL/util/numth.cpp:386-413).
 static bool minimal_primitive_root(uint64_t two_n, uint64_t q, uint64_t *out)
@@ -274,14 +247,6 @@ static bool minimal_primitive_root(uint64_t two_n, uint64_t q, uint64_t *out)
     }
     *out = best;
     return true;
-}
-
-static inline Tw make_tw(uint64_t w, uint64_t q)
-{
-    Tw t;
-    t.w = w;
-    t.wq = (uint64_t)((((u128)w) << 64) / q);
-    return t;
 }
 
 static void build_prime(int logn, uint64_t q, uint64_t psi, Tw *fwd, Tw *inv, PrimeConst *pc)
@@ -739,6 +704,23 @@ int workspace(moai_ctx *c, size_t bytes, hipStream_t s, void **out)
     // 1.5 x the old size), which synchronises the device and therefore must not happen under stream capture
     // (moai_ctx_reserve[_stream] sizes the arena beforehand)
     return reserve_for_stream(c, (void *)s, bytes ? bytes : 256, out, true);
+}
+
+size_t chunk_items(moai_ctx *c, hipStream_t s, size_t per_bytes, size_t n, size_t cap, size_t floor_bytes)
+{
+    size_t budget = floor_bytes;
+    {
+        std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
+        auto it = c->ws.find((void *)s);
+        if (it != c->ws.end() && it->second.bytes > budget)
+        {
+            budget = it->second.bytes;
+        }
+    }
+    size_t cb = budget / per_bytes;
+    cb = cb < 1 ? 1 : cb;
+    cb = cb > cap ? cap : cb;
+    return cb < n ? cb : n;
 }
 } // namespace moai
 

@@ -4,7 +4,7 @@
 // Decrypt is exact integer arithmetic: one launch for a batch, out = sum_i c_i * s^i mod q with the powers of s formed in
 // registers.
 //
-// Decode, per chunk of plaintexts (the scratch is bounded, see dec_chunk):
+// Decode, per chunk of plaintexts (the scratch is bounded, see chunk_items in ckks_decode_impl):
 //   moai_ntt_inverse  : on a scratch copy of the rows (the caller's input is never modified; the reference copies too)
 //   dec_compose<NW>   : exact CRT composition of every coefficient into the words of x in [0, Q), then the reference's
 //                       word-by-word conversion to double (ckks.h:713-753), one coefficient per thread
@@ -29,9 +29,11 @@
 // DWT.  Every butterfly is  u + y*r, u - y*r  with the complex product as four separately rounded products and two sums
 // (std::complex<double> operator* on finite values; the file is compiled with -ffp-contract=off), so any parallel schedule
 // gives the reference's bits.
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 
+#include "hostmath.h"
 #include "launch.h"
 #include "modarith.hip.h"
 
@@ -345,179 +347,94 @@ __global__ __launch_bounds__(256) void dec_fft_tail(TailArgs g)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static uint64_t mulmod_host(uint64_t a, uint64_t b, uint64_t q)
+// the composition constants of one set of rows, one block of 64-bit words: offsets of the parts in ComposeArgs order
+struct DecLayout
 {
-    return (uint64_t)((unsigned __int128)a * b % q);
-}
-
-static uint64_t powmod_host(uint64_t a, uint64_t e, uint64_t q)
-{
-    uint64_t r = 1 % q;
-    a %= q;
-    while (e)
+    size_t pw, invp, P, nw, q, Q, T, words;
+    DecLayout(size_t L, size_t W)
+        : pw(0), invp(pw + 2 * L * W), P(invp + 2 * L), nw(P + L * W), q(nw + L), Q(q + L), T(Q + W), words(T + W)
     {
-        if (e & 1)
-        {
-            r = mulmod_host(r, a, q);
-        }
-        a = mulmod_host(a, a, q);
-        e >>= 1;
     }
-    return r;
-}
-
-static Tw shoup(uint64_t w, uint64_t q)
-{
-    Tw t;
-    t.w = w;
-    t.wq = (uint64_t)(((unsigned __int128)w << 64) / q);
-    return t;
-}
-
-// words of a little-endian multi-word integer without its leading zero words (at least one)
-static uint32_t sig_words(const std::vector<uint64_t> &a)
-{
-    uint32_t w = (uint32_t)a.size();
-    while (w > 1 && a[w - 1] == 0)
-    {
-        w--;
-    }
-    return w;
-}
-
-// the composition constants of one set of rows (layout in ComposeArgs order); W = significant words of Q
-struct DecTable
-{
-    const uint64_t *base = nullptr;
-    uint32_t W = 0;
 };
 
-static int dec_table(moai_ctx *c, const RowMap &rows, size_t L, DecTable *out)
+// fills the table pointers, L and W (the words of Q) of `a`, building the block on first use of the set of rows
+static int dec_table(moai_ctx *c, const RowMap &rows, size_t L, ComposeArgs *a)
 {
     std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
     std::vector<uint32_t> key(rows.idx, rows.idx + L);
-    // the product words: W = words of Q
-    std::vector<uint64_t> prod(L + 1, 0);
-    prod[0] = 1;
+    // P[i] = q_0 ... q_{i-1}, prod = Q
+    std::vector<uint64_t> prod(1, 1);
     std::vector<std::vector<uint64_t>> P(L);
     for (size_t i = 0; i < L; i++)
     {
         P[i] = prod;
-        const uint64_t q = c->primes[rows.idx[i]];
-        unsigned __int128 carry = 0;
-        for (size_t w = 0; w <= L; w++)
-        {
-            unsigned __int128 t = (unsigned __int128)prod[w] * q + carry;
-            prod[w] = (uint64_t)t;
-            carry = t >> 64;
-        }
+        mul_word(prod, c->primes[rows.idx[i]]);
     }
-    const uint32_t W = sig_words(prod);
+    const size_t W = prod.size();
+    const DecLayout lay(L, W);
     auto it = c->dec_tables.find(key);
-    if (it != c->dec_tables.end())
+    const uint64_t *base = it != c->dec_tables.end() ? it->second : nullptr;
+    if (!base)
     {
-        out->base = it->second;
-        out->W = W;
-        return MOAI_OK;
-    }
-    // [L][W] Tw pw | [L] Tw invp | [L][W] P | [L] nw | [L] q | [W] Q | [W] T
-    std::vector<uint64_t> h(2 * L * W + 2 * L + L * W + L + L + W + W, 0);
-    uint64_t *pw = h.data();
-    uint64_t *invp = pw + 2 * L * W;
-    uint64_t *Pw = invp + 2 * L;
-    uint64_t *nw = Pw + L * W;
-    uint64_t *qv = nw + L;
-    uint64_t *Qw = qv + L;
-    uint64_t *Tw_ = Qw + W;
-    for (size_t i = 0; i < L; i++)
-    {
-        const uint64_t q = c->primes[rows.idx[i]];
-        const uint64_t two64 = (uint64_t)(((unsigned __int128)1 << 64) % q);
-        uint64_t pwr = 1 % q;
+        std::vector<uint64_t> h(lay.words, 0);
+        for (size_t i = 0; i < L; i++)
+        {
+            const uint64_t q = c->primes[rows.idx[i]];
+            const uint64_t two64 = (uint64_t)(((u128)1 << 64) % q);
+            uint64_t pwr = 1;
+            for (size_t w = 0; w < W; w++)
+            {
+                const Tw t = make_tw(pwr, q);
+                h[lay.pw + 2 * (i * W + w)] = t.w;
+                h[lay.pw + 2 * (i * W + w) + 1] = t.wq;
+                pwr = mulmod(pwr, two64, q);
+            }
+            // P_i mod q_i, then its inverse (q_i is prime and coprime to the others)
+            uint64_t pm = 0;
+            for (size_t w = P[i].size(); w-- > 0;)
+            {
+                pm = (uint64_t)((((u128)pm << 64) | P[i][w]) % q);
+            }
+            if (pm == 0)
+            {
+                return set_error(MOAI_EINVAL, "prime_index repeats a prime");
+            }
+            const Tw ip = make_tw(powmod(pm, q - 2, q), q);
+            h[lay.invp + 2 * i] = ip.w;
+            h[lay.invp + 2 * i + 1] = ip.wq;
+            std::copy(P[i].begin(), P[i].end(), h.begin() + lay.P + i * W);
+            h[lay.nw + i] = P[i].size();
+            h[lay.q + i] = q;
+        }
+        // upper_half_threshold = (Q + 1) >> 1 (SEAL/context.cpp:376-382); Q is odd so Q + 1 does not carry out of W words
+        std::copy(prod.begin(), prod.end(), h.begin() + lay.Q);
         for (size_t w = 0; w < W; w++)
         {
-            const Tw t = shoup(pwr, q);
-            pw[2 * (i * W + w)] = t.w;
-            pw[2 * (i * W + w) + 1] = t.wq;
-            pwr = mulmod_host(pwr, two64, q);
+            if (++prod[w] != 0)
+            {
+                break;
+            }
         }
-        // P_i mod q_i, then its inverse (q_i is prime and coprime to the others)
-        uint64_t pm = 0;
-        for (size_t w = P[i].size(); w-- > 0;)
-        {
-            pm = (uint64_t)((((unsigned __int128)pm << 64) | P[i][w]) % q);
-        }
-        if (pm == 0)
-        {
-            return set_error(MOAI_EINVAL, "prime_index repeats a prime");
-        }
-        const Tw ip = shoup(powmod_host(pm, q - 2, q), q);
-        invp[2 * i] = ip.w;
-        invp[2 * i + 1] = ip.wq;
         for (size_t w = 0; w < W; w++)
         {
-            Pw[i * W + w] = P[i][w];
+            h[lay.T + w] = (prod[w] >> 1) | (w + 1 < W ? prod[w + 1] << 63 : 0);
         }
-        nw[i] = sig_words(P[i]);
-        qv[i] = q;
+        uint64_t *d = nullptr;
+        MOAI_HIP_CHECK(hipMalloc(&d, h.size() * 8));
+        MOAI_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+        c->dec_tables[key] = d;
+        base = d;
     }
-    // upper_half_threshold = (Q + 1) >> 1 (SEAL/context.cpp:376-382); Q is odd so Q + 1 does not carry out of W words
-    std::vector<uint64_t> t(prod.begin(), prod.begin() + W);
-    for (size_t w = 0; w < W; w++)
-    {
-        Qw[w] = t[w];
-    }
-    for (size_t w = 0; w < W; w++)
-    {
-        if (++t[w] != 0)
-        {
-            break;
-        }
-    }
-    for (size_t w = 0; w < W; w++)
-    {
-        Tw_[w] = (t[w] >> 1) | (w + 1 < W ? t[w + 1] << 63 : 0);
-    }
-    uint64_t *d = nullptr;
-    MOAI_HIP_CHECK(hipMalloc(&d, h.size() * 8));
-    MOAI_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    c->dec_tables[key] = d;
-    out->base = d;
-    out->W = W;
+    a->pw = reinterpret_cast<const Tw *>(base + lay.pw);
+    a->invp = reinterpret_cast<const Tw *>(base + lay.invp);
+    a->P = base + lay.P;
+    a->nw = base + lay.nw;
+    a->q = base + lay.q;
+    a->Q = base + lay.Q;
+    a->T = base + lay.T;
+    a->L = (uint32_t)L;
+    a->W = (uint32_t)W;
     return MOAI_OK;
-}
-
-template <int NW>
-static void launch_compose(const ComposeArgs &a, dim3 grid, hipStream_t s)
-{
-    hipLaunchKernelGGL(dec_compose<NW>, grid, dim3(256), 0, s, a);
-}
-
-template <int R>
-static void launch_head(double2 *data, const double2 *roots, uint32_t logn, uint32_t nb, hipStream_t s)
-{
-    hipLaunchKernelGGL(dec_fft_head<R>, dim3(DEC_TILE / 256, nb), dim3(256), 0, s, data, roots, logn);
-}
-
-// plaintexts per chunk: the scratch of one is its L rows plus N complex doubles; the budget is the stream's arena when that
-// is larger (moai_ctx_reserve), else MOAI_DEC_TMP_MB (default 1024 MiB)
-static size_t dec_chunk(moai_ctx *c, hipStream_t s, size_t L, size_t n_batch)
-{
-    const size_t per = c->n * (L * sizeof(uint64_t) + sizeof(double2));
-    long mb = tuning(K_DEC_TMP_MB);
-    size_t budget = (size_t)(mb < 1 ? 1 : mb) << 20;
-    {
-        std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
-        auto it = c->ws.find((void *)s);
-        if (it != c->ws.end() && it->second.bytes > budget)
-        {
-            budget = it->second.bytes;
-        }
-    }
-    size_t cb = budget / per;
-    cb = cb < 1 ? 1 : cb;
-    cb = cb > 65535 ? 65535 : cb;
-    return cb < n_batch ? cb : n_batch;
 }
 
 } // namespace moai
@@ -529,14 +446,8 @@ extern "C" int moai_decrypt(moai_ctx *c, const uint64_t *ct, size_t size, const 
 {
     MOAI_AUDIT(stream, ct, sk_ntt, out);
     trace_op("decrypt", L, n_batch);
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    DecryptArgs g;
+    MOAI_TRY(rows_entry(c, L, prime_index, &g.rows));
     if (size < 2)
     {
         return set_error(MOAI_EINVAL, "encrypted is not valid for encryption parameters");
@@ -544,12 +455,6 @@ extern "C" int moai_decrypt(moai_ctx *c, const uint64_t *ct, size_t size, const 
     if (size > 0xffffu)
     {
         return set_error(MOAI_EINVAL, "ciphertext size too large");
-    }
-    RowMap rows;
-    int rc = make_rowmap(c, L, prime_index, &rows);
-    if (rc)
-    {
-        return rc;
     }
     if (n_batch == 0)
     {
@@ -563,17 +468,11 @@ extern "C" int moai_decrypt(moai_ctx *c, const uint64_t *ct, size_t size, const 
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
-    DecryptArgs g;
+    MOAI_TRY(enter_device(c));
     g.ct = ct;
     g.sk = sk_ntt;
     g.out = out;
     g.pc = c->pc;
-    g.rows = rows;
     g.size = (uint32_t)size;
     g.L = (uint32_t)L;
     g.logn = (uint32_t)c->logn;
@@ -587,19 +486,11 @@ extern "C" int moai_decrypt(moai_ctx *c, const uint64_t *ct, size_t size, const 
 static int ckks_decode_impl(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L, const uint32_t *prime_index,
                             const double *scales, size_t out_slots, int is_complex, double *out, void *stream)
 {
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    RowMap rows;
+    MOAI_TRY(rows_entry(c, L, prime_index, &rows));
     if (c->logn < 3 || c->logn > DEC_TILE_LOG + 4)
     {
         return set_error(MOAI_ELOGIC, "decoder supports 8 <= N <= 2^16");
-    }
-    RowMap rows;
-    int rc = make_rowmap(c, L, prime_index, &rows);
-    if (rc)
-    {
-        return rc;
     }
     if (n_batch == 0)
     {
@@ -619,63 +510,35 @@ static int ckks_decode_impl(moai_ctx *c, const uint64_t *plain_ntt, size_t n_bat
             return set_error(MOAI_EINVAL, "scale out of bounds");
         }
     }
-    rc = enter_device(c);
-    if (!rc)
-    {
-        rc = ensure_ckks_tables(c);
-    }
-    DecTable tab;
-    if (!rc)
-    {
-        rc = dec_table(c, rows, L, &tab);
-    }
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
+    MOAI_TRY(ensure_ckks_tables(c));
+    ComposeArgs a;
+    MOAI_TRY(dec_table(c, rows, L, &a));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
-    const size_t n = c->n;
-    const size_t cb = dec_chunk(c, s, L, n_batch);
+    // plaintexts per chunk: the scratch of one is its L rows plus N complex doubles; the budget is the stream's arena when that
+    // is larger (moai_ctx_reserve), else MOAI_DEC_TMP_MB (default 1024 MiB)
+    const size_t n = c->n, per = n * (L * sizeof(uint64_t) + sizeof(double2));
+    const size_t cb = chunk_items(c, s, per, n_batch, 65535, (size_t)std::max(1l, tuning(K_DEC_TMP_MB)) << 20);
     void *scratch = nullptr;
-    rc = workspace(c, cb * n * (L * sizeof(uint64_t) + sizeof(double2)), s, &scratch);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, cb * per, s, &scratch));
     uint64_t *rows_tmp = static_cast<uint64_t *>(scratch);
     double2 *vals = reinterpret_cast<double2 *>(rows_tmp + cb * L * n);
-    const uint32_t W = tab.W;
-    ComposeArgs a;
-    a.pw = reinterpret_cast<const Tw *>(tab.base);
-    a.invp = reinterpret_cast<const Tw *>(tab.base + 2 * L * W);
-    a.P = tab.base + 2 * L * W + 2 * L;
-    a.nw = a.P + L * W;
-    a.q = a.nw + L;
-    a.Q = a.q + L;
-    a.T = a.Q + W;
-    a.L = (uint32_t)L;
-    a.W = W;
     a.logn = (uint32_t)c->logn;
     a.zero_mask = (uint32_t)((n >> 1) / out_slots - 1); // sparsity - 1 (ckks.h:705)
+    int NW = 1; // the words of Q rounded up to a power of two
+    while (NW < (int)a.W)
+    {
+        NW <<= 1;
+    }
     const uint32_t logn = (uint32_t)c->logn;
     const int R = logn > (uint32_t)DEC_TILE_LOG ? (int)logn - DEC_TILE_LOG : 0;
     const uint32_t tile = n < DEC_TILE ? (uint32_t)n : DEC_TILE;
     const size_t slots = out_slots;
-    for (size_t b0 = 0; b0 < n_batch; b0 += cb)
-    {
-        const size_t nb = n_batch - b0 < cb ? n_batch - b0 : cb;
+    return for_chunks(n_batch, cb, [&](size_t b0, size_t nb) {
         // SEAL copies the plaintext before inverse_ntt_negacyclic_harvey (ckks.h:689-697)
-        rc = ntt_launch(c, rows_tmp, nb, L, rows, true, s, plain_ntt + b0 * L * n, L, 0);
-        if (rc)
-        {
-            return rc;
-        }
-        a.in = rows_tmp;
-        a.out = vals;
-        for (size_t g0 = 0; g0 < nb; g0 += DEC_SCALES)
-        {
-            const size_t gn = nb - g0 < DEC_SCALES ? nb - g0 : DEC_SCALES;
+        MOAI_TRY(ntt_launch(c, rows_tmp, nb, L, rows, true, s, plain_ntt + b0 * L * n, L, 0));
+        MOAI_TRY(for_chunks(nb, DEC_SCALES, [&](size_t g0, size_t gn) {
             a.in = rows_tmp + g0 * L * n;
             a.out = vals + g0 * n;
             for (size_t j = 0; j < gn; j++)
@@ -683,25 +546,21 @@ static int ckks_decode_impl(moai_ctx *c, const uint64_t *plain_ntt, size_t n_bat
                 a.inv_scale[j] = double(1.0) / scales[b0 + g0 + j];
             }
             dim3 grid((uint32_t)((n + 255) / 256), (uint32_t)gn);
-            if (W <= 1) launch_compose<1>(a, grid, s);
-            else if (W <= 2) launch_compose<2>(a, grid, s);
-            else if (W <= 4) launch_compose<4>(a, grid, s);
-            else if (W <= 8) launch_compose<8>(a, grid, s);
-            else if (W <= 16) launch_compose<16>(a, grid, s);
-            else if (W <= 32) launch_compose<32>(a, grid, s);
-            else launch_compose<64>(a, grid, s);
-            MOAI_LAUNCH_CHECK();
-        }
+            return dispatch<1, 2, 4, 8, 16, 32, 64>("composition words ", NW, [&](auto nw) {
+                hipLaunchKernelGGL(dec_compose<decltype(nw)::value>, grid, dim3(256), 0, s, a);
+                MOAI_LAUNCH_CHECK();
+                return MOAI_OK;
+            });
+        }));
         const double2 *roots = reinterpret_cast<const double2 *>(c->ckks_roots);
-        switch (R)
+        if (R > 0)
         {
-        case 0: break;
-        case 1: launch_head<1>(vals, roots, logn, (uint32_t)nb, s); break;
-        case 2: launch_head<2>(vals, roots, logn, (uint32_t)nb, s); break;
-        case 3: launch_head<3>(vals, roots, logn, (uint32_t)nb, s); break;
-        default: launch_head<4>(vals, roots, logn, (uint32_t)nb, s); break;
+            MOAI_TRY((dispatch<1, 2, 3, 4>("decoder head stages ", R, [&](auto r) {
+                hipLaunchKernelGGL(dec_fft_head<decltype(r)::value>, dim3(DEC_TILE / 256, (uint32_t)nb), dim3(256), 0, s, vals, roots, logn);
+                MOAI_LAUNCH_CHECK();
+                return MOAI_OK;
+            })));
         }
-        MOAI_LAUNCH_CHECK();
         TailArgs t;
         t.data = vals;
         t.roots = roots;
@@ -713,8 +572,8 @@ static int ckks_decode_impl(moai_ctx *c, const uint64_t *plain_ntt, size_t n_bat
         t.is_complex = is_complex ? 1u : 0u;
         hipLaunchKernelGGL(dec_fft_tail, dim3((uint32_t)(nb * (n / tile))), dim3(256), 0, s, t);
         MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }
 
 extern "C" int moai_ckks_decode(moai_ctx *c, const uint64_t *plain_ntt, size_t n_batch, size_t L,

@@ -6,8 +6,8 @@
 // 16-byte accesses, one RNS prime per block row (blockIdx.y = polynomial row), so the per-prime
 // constants are wave-uniform scalars.
 //
-// Layout of this file: the kernels, the host helpers every entry point shares (check_rows, fill_rows, launch_rows,
-// for_term_chunks), then the entry points by family.  A new fused sum is a kernel of its own that accumulates each lane
+// Layout of this file: the kernels, the host helpers every entry point shares (check_rows, fill_rows, launch_rows;
+// for_term_chunks is launch.h's), then the entry points by family.  A new fused sum is a kernel of its own that accumulates each lane
 // pair with mac2 / fold2 / reduce2 (modarith.hip.h), an args struct that fill_rows fills, and one launch_rows call.
 #include <algorithm>
 #include <mutex>
@@ -913,20 +913,6 @@ static int launch_rows(Kernel kernel, const moai_ctx *c, size_t rows, void *stre
     MOAI_CHECK_GRID_ROWS(rows);
     hipLaunchKernelGGL(kernel, row_grid(c, rows), dim3(256), 0, (hipStream_t)stream, args...);
     MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
-}
-
-// f(t0, cnt) for consecutive chunks of at most `per` of `terms` terms; no terms at all is one empty chunk (out = base)
-template <class F>
-static int for_term_chunks(size_t terms, size_t per, F &&f)
-{
-    size_t t0 = 0;
-    do
-    {
-        const size_t cnt = std::min(per, terms - t0);
-        MOAI_TRY(f(t0, cnt));
-        t0 += cnt;
-    } while (t0 < terms);
     return MOAI_OK;
 }
 

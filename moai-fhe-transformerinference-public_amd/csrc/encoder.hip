@@ -16,6 +16,7 @@
 #include <complex>
 #include <mutex>
 
+#include "hostmath.h"
 #include "launch.h"
 #include "modarith.hip.h"
 
@@ -425,16 +426,6 @@ __global__ __launch_bounds__(256) void ckks_fft_finish(EncArgs g)
 }
 
 // ---- host side: tables exactly as CKKSEncoder's constructor builds them (SEAL/ckks.cpp:13-76) ------------
-static uint32_t reverse_bits(uint32_t x, int bits)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < bits; i++)
-    {
-        r = (r << 1) | ((x >> i) & 1u);
-    }
-    return r;
-}
-
 namespace {
 // util::ComplexRoots (SEAL/util/croots.cpp:18-75): an eighth of the circle from std::polar, the rest by
 // exact symmetries
@@ -480,7 +471,7 @@ struct ComplexRoots
 };
 } // namespace
 
-static int ensure_tables(moai_ctx *c)
+int ensure_ckks_tables(moai_ctx *c)
 {
     std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
     if (c->ckks_inv_roots)
@@ -497,41 +488,32 @@ static int ensure_tables(moai_ctx *c)
     {
         uint64_t index1 = (pos - 1) >> 1;
         uint64_t index2 = (m - pos - 1) >> 1;
-        c->ckks_index_map[i] = reverse_bits((uint32_t)index1, logn);
-        c->ckks_index_map[slots | i] = reverse_bits((uint32_t)index2, logn);
+        c->ckks_index_map[i] = bitrev((uint32_t)index1, logn);
+        c->ckks_index_map[slots | i] = bitrev((uint32_t)index2, logn);
         pos *= gen;
         pos &= (m - 1);
     }
+    // inv_root_powers_, and for the decoder's forward DWT root_powers_[i] = complex_roots_->get_root(reverse_bits(i, logn))
+    // (ckks.cpp:58-62), from one table of roots
     c->ckks_inv_roots_host.assign(2 * n, 0.0);
-    if (m >= 8)
-    {
-        ComplexRoots cr((size_t)m);
-        for (size_t i = 1; i < n; i++)
-        {
-            std::complex<double> z = std::conj(cr.get_root((size_t)reverse_bits((uint32_t)(i - 1), logn) + 1));
-            c->ckks_inv_roots_host[2 * i] = z.real();
-            c->ckks_inv_roots_host[2 * i + 1] = z.imag();
-        }
-    }
-    else
-    {
-        c->ckks_inv_roots_host[2] = 0;
-        c->ckks_inv_roots_host[3] = -1;
-    }
-    // root_powers_[i] = complex_roots_->get_root(reverse_bits(i, logn)) (ckks.cpp:58-62): the decoder's forward DWT
     std::vector<double> fwd(2 * n, 0.0);
     if (m >= 8)
     {
         ComplexRoots cr((size_t)m);
         for (size_t i = 1; i < n; i++)
         {
-            std::complex<double> z = cr.get_root((size_t)reverse_bits((uint32_t)i, logn));
-            fwd[2 * i] = z.real();
-            fwd[2 * i + 1] = z.imag();
+            const std::complex<double> zi = std::conj(cr.get_root((size_t)bitrev((uint32_t)(i - 1), logn) + 1));
+            const std::complex<double> zf = cr.get_root((size_t)bitrev((uint32_t)i, logn));
+            c->ckks_inv_roots_host[2 * i] = zi.real();
+            c->ckks_inv_roots_host[2 * i + 1] = zi.imag();
+            fwd[2 * i] = zf.real();
+            fwd[2 * i + 1] = zf.imag();
         }
     }
     else
     {
+        c->ckks_inv_roots_host[2] = 0;
+        c->ckks_inv_roots_host[3] = -1;
         fwd[2] = 0;
         fwd[3] = 1;
     }
@@ -555,53 +537,16 @@ static int ensure_tables(moai_ctx *c)
     return MOAI_OK;
 }
 
-// significant bits of the product of the selected primes (schoolbook multi-word product)
-static int product_bit_count(const moai_ctx *c, size_t L, const uint32_t *prime_index)
+int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index)
 {
-    std::vector<uint64_t> acc(1, 1);
-    for (size_t j = 0; j < L; j++)
+    for (size_t j = 0; prime_index && j < L; j++)
     {
-        size_t idx = prime_index ? prime_index[j] : j;
-        if (idx >= c->k)
+        if (prime_index[j] >= c->k)
         {
             return 0;
         }
-        const uint64_t q = c->primes[idx];
-        unsigned __int128 carry = 0;
-        for (size_t w = 0; w < acc.size(); w++)
-        {
-            unsigned __int128 t = (unsigned __int128)acc[w] * q + carry;
-            acc[w] = (uint64_t)t;
-            carry = t >> 64;
-        }
-        if (carry)
-        {
-            acc.push_back((uint64_t)carry);
-        }
     }
-    int bits = 64 * (int)(acc.size() - 1);
-    for (uint64_t top = acc.back(); top; top >>= 1)
-    {
-        bits++;
-    }
-    return bits;
-}
-
-// shared with decoder.hip (launch.h)
-int ensure_ckks_tables(moai_ctx *c)
-{
-    return ensure_tables(c);
-}
-
-int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index)
-{
-    return product_bit_count(c, L, prime_index);
-}
-
-template <int R>
-static void launch_finish(const EncArgs &g, dim3 grid, hipStream_t s)
-{
-    hipLaunchKernelGGL(ckks_fft_finish<R>, grid, dim3(256), 0, s, g);
+    return bit_length(prime_product(c, prime_index, L));
 }
 
 } // namespace moai
@@ -615,7 +560,7 @@ extern "C" int moai_total_coeff_modulus_bit_count(const moai_ctx *c, size_t L, c
         set_error(MOAI_EINVAL, "invalid level");
         return 0;
     }
-    return product_bit_count(c, L, prime_index);
+    return total_coeff_bits(c, L, prime_index);
 }
 
 extern "C" int moai_ckks_tables(moai_ctx *c, uint32_t *index_map, double *inv_root_powers)
@@ -624,11 +569,7 @@ extern "C" int moai_ckks_tables(moai_ctx *c, uint32_t *index_map, double *inv_ro
     {
         return set_error(MOAI_EINVAL, "null context");
     }
-    int rc = ensure_tables(c);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(ensure_ckks_tables(c));
     if (index_map)
     {
         std::copy(c->ckks_index_map.begin(), c->ckks_index_map.end(), index_map);
@@ -644,14 +585,8 @@ static int encode_impl(moai_ctx *c, const double *values, const int32_t *mask, i
                        size_t n_batch, uint64_t *dst, size_t L, const uint32_t *prime_index, double scale,
                        double *max_coeff, void *stream)
 {
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
+    RowMap rows;
+    MOAI_TRY(rows_entry(c, L, prime_index, &rows));
     if (c->logn < 3 || c->logn > ENC_TILE_LOG + 4)
     {
         return set_error(MOAI_ELOGIC, "encoder supports 8 <= N <= 2^16");
@@ -664,14 +599,8 @@ static int encode_impl(moai_ctx *c, const double *values, const int32_t *mask, i
     {
         return set_error(MOAI_EINVAL, "values cannot be null");
     }
-    RowMap rows;
-    int rc = make_rowmap(c, L, prime_index, &rows);
-    if (rc)
-    {
-        return rc;
-    }
     // ckks.h:493-497
-    const int total_bits = product_bit_count(c, L, prime_index);
+    const int total_bits = total_coeff_bits(c, L, prime_index);
     if (scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= total_bits))
     {
         return set_error(MOAI_EINVAL, "scale out of bounds");
@@ -688,23 +617,12 @@ static int encode_impl(moai_ctx *c, const double *values, const int32_t *mask, i
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    rc = enter_device(c);
-    if (!rc)
-    {
-        rc = ensure_tables(c);
-    }
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(enter_device(c));
+    MOAI_TRY(ensure_ckks_tables(c));
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
     void *scratch = nullptr;
-    rc = workspace(c, n_batch * c->n * sizeof(double2), s, &scratch);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(workspace(c, n_batch * c->n * sizeof(double2), s, &scratch));
     if (max_coeff)
     {
         MOAI_HIP_CHECK(hipMemsetAsync(max_coeff, 0, sizeof(double) * n_batch, s));
@@ -727,26 +645,16 @@ static int encode_impl(moai_ctx *c, const double *values, const int32_t *mask, i
 
     const uint32_t tile = c->n < ENC_TILE ? (uint32_t)c->n : ENC_TILE;
     const uint32_t tiles = (uint32_t)(c->n / tile);
-    if (c->logn >= ENC_TILE_LOG)
-    {
-        hipLaunchKernelGGL(ckks_fft_contig16, dim3((uint32_t)(n_batch * tiles)), dim3(256), 0, s, g);
-    }
-    else
-    {
-        hipLaunchKernelGGL(ckks_fft_contig, dim3((uint32_t)(n_batch * tiles)), dim3(256), 0, s, g);
-    }
+    hipLaunchKernelGGL(c->logn >= ENC_TILE_LOG ? ckks_fft_contig16 : ckks_fft_contig, dim3((uint32_t)(n_batch * tiles)), dim3(256), 0, s,
+                       g);
     MOAI_LAUNCH_CHECK();
     const int R = c->logn > ENC_TILE_LOG ? c->logn - ENC_TILE_LOG : 0;
     dim3 grid((tile + 255) / 256, (uint32_t)((L + ENC_ROWS_PER_BLOCK - 1) / ENC_ROWS_PER_BLOCK), (uint32_t)n_batch);
-    switch (R)
-    {
-    case 0: launch_finish<0>(g, grid, s); break;
-    case 1: launch_finish<1>(g, grid, s); break;
-    case 2: launch_finish<2>(g, grid, s); break;
-    case 3: launch_finish<3>(g, grid, s); break;
-    default: launch_finish<4>(g, grid, s); break;
-    }
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY((dispatch<0, 1, 2, 3, 4>("encoder strided stages ", R, [&](auto r) {
+        hipLaunchKernelGGL(ckks_fft_finish<decltype(r)::value>, grid, dim3(256), 0, s, g);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    })));
     // ckks.h:631-634: ntt_negacyclic_harvey on every row
     return ntt_launch(c, dst, n_batch, L, rows, false, s);
 }

@@ -56,6 +56,28 @@ int dispatch_logn(int logn, F &&f)
 {
     return dispatch<12, 13, 14, 15, 16>("poly_modulus_degree 2^", logn, f);
 }
+// f(x0, cnt) for consecutive chunks of at most `per` of n items, until one returns a code other than MOAI_OK
+template <class F>
+int for_chunks(size_t n, size_t per, F &&f)
+{
+    for (size_t x0 = 0; x0 < n; x0 += per)
+    {
+        MOAI_TRY(f(x0, n - x0 < per ? n - x0 : per));
+    }
+    return MOAI_OK;
+}
+// the same over the terms of a sum, where no terms at all is one empty chunk (out = base)
+template <class F>
+int for_term_chunks(size_t terms, size_t per, F &&f)
+{
+    return terms ? for_chunks(terms, per, f) : f(0, 0);
+}
+// whether the byte ranges [a, a + a_bytes) and [b, b + b_bytes) intersect
+inline bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
 // operation census for the end-to-end bench (moai_op_trace): counts `units` (polynomials, ciphertexts or products, as the
 // entry point's own batch argument counts them) per (entry point, level); a relaxed atomic load when it is off
 void trace_op(const char *name, size_t L, size_t units);
@@ -76,12 +98,18 @@ TwPair twiddles(const moai_ctx *c, int mode, bool inverse);
 struct NttArgs;
 NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse);
 int make_rowmap(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap *out);
+// the head of an entry point that takes a level and a row selection: "null context", "invalid level" unless 1 <= L <= k, then
+// make_rowmap
+int rows_entry(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap *out);
 // src (inverse only): polynomial p's row r is read from src row p * src_stride_rows + src_off_rows + r, the result lands in
 // `data` [n_poly][L][N] -- the inverse transform of a slice of a larger layout without copying the slice first
 int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse,
                hipStream_t s, const uint64_t *src = nullptr, size_t src_stride_rows = 0, size_t src_off_rows = 0);
 // returns the context workspace grown to at least `bytes` (grows only outside stream capture)
 int workspace(moai_ctx *c, size_t bytes, hipStream_t s, void **out);
+// items per chunk of a batch of n whose items need per_bytes of scratch each: as many as fit the stream's arena, or floor_bytes
+// when the arena is smaller or absent; at least 1, at most cap and n.  The caller holds op_mutex and sizes workspace() with it.
+size_t chunk_items(moai_ctx *c, hipStream_t s, size_t per_bytes, size_t n, size_t cap, size_t floor_bytes);
 // headroom: allocate max(1.25 x bytes, 1.5 x the current size) when the arena has to grow
 int reserve_for_stream(moai_ctx *c, void *stream, size_t bytes, void **out, bool headroom);
 // device pointer to the Galois permutation table of `elt` (built on first use, on the NULL stream, and complete on return)
@@ -89,9 +117,11 @@ int galois_table(moai_ctx *c, uint32_t elt, const uint32_t **out);
 // out [batch][L][N] = the Galois permutation of polynomial 0 of every ciphertext of in [batch][2][L][N]
 int galois_permute_c0(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t batch, size_t L, uint32_t galois_elt, hipStream_t s);
 
-// CKKSEncoder's tables (matrix_reps_index_map_, root_powers_, inv_root_powers_) on the device, built on first use (encoder.hip)
+// CKKSEncoder's tables (matrix_reps_index_map_, root_powers_, inv_root_powers_) on the device, built on first use under
+// c->mutex (encoder.hip)
 int ensure_ckks_tables(moai_ctx *c);
-// ContextData::total_coeff_modulus_bit_count of the selected primes; 0 when an index is out of range (encoder.hip)
+// ContextData::total_coeff_modulus_bit_count of the selected primes; 0, and no error set, when an index is out of range
+// (encoder.hip)
 int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index);
 
 // moai_rescale for a caller that already holds the context's op_mutex (client.hip): it uses the first

@@ -343,6 +343,19 @@ int make_rowmap(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap
     return MOAI_OK;
 }
 
+int rows_entry(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap *out)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
+    {
+        return set_error(MOAI_EINVAL, "invalid level");
+    }
+    return make_rowmap(c, L, prime_index, out);
+}
+
 } // namespace moai
 
 using namespace moai;

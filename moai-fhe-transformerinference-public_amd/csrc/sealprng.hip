@@ -470,16 +470,8 @@ extern "C" int moai_seal_sample_uniform(moai_ctx *c, const uint8_t *seeds, uint6
 {
     MOAI_AUDIT(stream, out, rejected);
     trace_op("seal_sample_uniform", L, count);
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
     SealArgs a = {};
-    MOAI_TRY(make_rowmap(c, L, prime_index, &a.rows));
+    MOAI_TRY(rows_entry(c, L, prime_index, &a.rows));
     if (!seeds)
     {
         return set_error(MOAI_EINVAL, "null seed");
@@ -515,28 +507,19 @@ extern "C" int moai_seal_sample_uniform(moai_ctx *c, const uint8_t *seeds, uint6
     a.L = (uint32_t)L;
     a.logn = (uint32_t)c->logn;
     const uint32_t blocks = (uint32_t)((a.nbuf + 4 * SEAL_WAVE_BUFS - 1) / (4 * SEAL_WAVE_BUFS));
-    for (size_t p0 = 0; p0 < count; p0 += SEAL_SEEDS)
-    {
-        const uint32_t np = (uint32_t)(count - p0 < SEAL_SEEDS ? count - p0 : SEAL_SEEDS);
-        for (uint32_t p = 0; p < np; p++)
+    return for_chunks(count, SEAL_SEEDS, [&](size_t p0, size_t np) {
+        for (size_t p = 0; p < np; p++)
         {
             key_state(seeds + (p0 + p) * 64, a.h1[p]);
         }
         a.out = out + p0 * stride_words;
         a.cnt = static_cast<uint32_t *>(ws) + p0 * L;
-        if (c->logn >= 9)
-        {
-            hipLaunchKernelGGL(seal_fill<FILL_WIDE>, dim3(blocks, np), dim3(256), 0, s, a);
-        }
-        else
-        {
-            hipLaunchKernelGGL(seal_fill<FILL_NARROW>, dim3(blocks, np), dim3(256), 0, s, a);
-        }
+        hipLaunchKernelGGL(c->logn >= 9 ? seal_fill<FILL_WIDE> : seal_fill<FILL_NARROW>, dim3(blocks, (uint32_t)np), dim3(256), 0, s, a);
         MOAI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(seal_fixup, dim3(np), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(seal_fixup, dim3((uint32_t)np), dim3(64), 0, s, a);
         MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }
 
 extern "C" int moai_check_residues(moai_ctx *c, const uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index,
@@ -544,16 +527,8 @@ extern "C" int moai_check_residues(moai_ctx *c, const uint64_t *data, size_t n_p
 {
     MOAI_AUDIT(stream, data, invalid);
     trace_op("check_residues", L, n_poly);
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
     CheckArgs a;
-    MOAI_TRY(make_rowmap(c, L, prime_index, &a.rows));
+    MOAI_TRY(rows_entry(c, L, prime_index, &a.rows));
     if (n_poly == 0)
     {
         return MOAI_OK;
@@ -571,12 +546,11 @@ extern "C" int moai_check_residues(moai_ctx *c, const uint64_t *data, size_t n_p
     a.pc = c->pc;
     a.L = (uint32_t)L;
     a.logn = (uint32_t)c->logn;
-    for (size_t p0 = 0; p0 < n_poly; p0 += 65535)
-    {
-        const size_t np = n_poly - p0 < 65535 ? n_poly - p0 : 65535;
+    // gridDim.z holds at most 65535 polynomials
+    return for_chunks(n_poly, 65535, [&](size_t p0, size_t np) {
         a.data = data + p0 * L * c->n;
         hipLaunchKernelGGL(seal_check, dim3((uint32_t)((c->n + 255) / 256), (uint32_t)L, (uint32_t)np), dim3(256), 0, (hipStream_t)stream, a);
         MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }

@@ -9,6 +9,8 @@
 //
 // Both are streaming kernels: gridDim.y is the row of the polynomial, gridDim.z the polynomial, so that the field width, the
 // row's offset in the packed polynomial and its modulus are uniform over a workgroup and live in scalar registers.
+#include <algorithm>
+
 #include "launch.h"
 
 namespace moai {
@@ -116,19 +118,7 @@ static size_t row_words(const moai_ctx *c, uint32_t prime)
 
 static int wire_args(const moai_ctx *c, size_t L, const uint32_t *prime_index, WireArgs *a)
 {
-    if (!c)
-    {
-        return set_error(MOAI_EINVAL, "null context");
-    }
-    if (L == 0 || L > c->k || L > MOAI_MAX_RNS)
-    {
-        return set_error(MOAI_EINVAL, "invalid level");
-    }
-    int rc = make_rowmap(c, L, prime_index, &a->rows);
-    if (rc)
-    {
-        return rc;
-    }
+    MOAI_TRY(rows_entry(c, L, prime_index, &a->rows));
     size_t off = 0;
     for (size_t r = 0; r < MOAI_MAX_RNS; r++)
     {
@@ -147,10 +137,53 @@ static int wire_args(const moai_ctx *c, size_t L, const uint32_t *prime_index, W
     return MOAI_OK;
 }
 
-static bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+// what pack and unpack share: validation, then one launch of `kernel` per 65535 polynomials (gridDim.z), `grid_x` workgroups
+// per row.  rows [n_poly][L][N] and packed [n_poly][poly_words] are the two blocks: pack reads the first and writes the second,
+// unpack the reverse (the one that is read is the caller's const block).
+template <class Kernel>
+static int wire_launch(Kernel kernel, bool unpack, moai_ctx *c, uint64_t *rows, uint64_t *packed, size_t n_poly, size_t L,
+                       const uint32_t *prime_index, uint32_t *invalid, void *stream)
 {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
+    WireArgs a;
+    MOAI_TRY(wire_args(c, L, prime_index, &a));
+    if (n_poly == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!rows || !packed)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    if (n_poly > ((size_t)1 << 40))
+    {
+        return set_error(MOAI_EINVAL, "too many polynomials");
+    }
+    if (unpack && ((uintptr_t)rows & 15))
+    {
+        return set_error(MOAI_EINVAL, "out must be 16-byte aligned");
+    }
+    const size_t row_words = L * c->n;
+    if (overlap(rows, n_poly * row_words * 8, packed, n_poly * a.poly_words * 8))
+    {
+        return set_error(MOAI_EINVAL, unpack ? "packed and out overlap" : "in and packed overlap");
+    }
+    MOAI_TRY(enter_device(c));
+    a.invalid = invalid;
+    uint32_t grid_x = (uint32_t)((c->n / 2 + 255) / 256);
+    if (!unpack)
+    {
+        // one thread per packed word of the widest row
+        const uint32_t widest = *std::max_element(a.words, a.words + L);
+        grid_x = (widest + 255) / 256;
+    }
+    return for_chunks(n_poly, 65535, [&](size_t p0, size_t np) {
+        uint64_t *r = rows + p0 * row_words, *p = packed + p0 * a.poly_words;
+        a.src = unpack ? p : r;
+        a.dst = unpack ? r : p;
+        hipLaunchKernelGGL(kernel, dim3(grid_x, (uint32_t)L, (uint32_t)np), dim3(256), 0, (hipStream_t)stream, a);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
 }
 
 } // namespace moai
@@ -172,48 +205,7 @@ extern "C" int moai_pack_rows(moai_ctx *c, const uint64_t *in, uint64_t *packed,
 {
     MOAI_AUDIT(stream, in, packed);
     trace_op("pack_rows", L, n_poly);
-    WireArgs a;
-    int rc = wire_args(c, L, prime_index, &a);
-    if (rc)
-    {
-        return rc;
-    }
-    if (n_poly == 0)
-    {
-        return MOAI_OK;
-    }
-    if (!in || !packed)
-    {
-        return set_error(MOAI_EINVAL, "null argument");
-    }
-    if (n_poly > ((size_t)1 << 40))
-    {
-        return set_error(MOAI_EINVAL, "too many polynomials");
-    }
-    if (overlap(in, n_poly * L * c->n * 8, packed, n_poly * a.poly_words * 8))
-    {
-        return set_error(MOAI_EINVAL, "in and packed overlap");
-    }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
-    uint32_t widest = 0;
-    for (size_t r = 0; r < L; r++)
-    {
-        widest = a.words[r] > widest ? a.words[r] : widest;
-    }
-    // gridDim.z holds at most 65535 polynomials
-    for (size_t p0 = 0; p0 < n_poly; p0 += 65535)
-    {
-        const size_t np = n_poly - p0 < 65535 ? n_poly - p0 : 65535;
-        a.src = in + p0 * L * c->n;
-        a.dst = packed + p0 * a.poly_words;
-        hipLaunchKernelGGL(wire_pack, dim3((widest + 255) / 256, (uint32_t)L, (uint32_t)np), dim3(256), 0, (hipStream_t)stream, a);
-        MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+    return wire_launch(wire_pack, false, c, const_cast<uint64_t *>(in), packed, n_poly, L, prime_index, nullptr, stream);
 }
 
 extern "C" int moai_unpack_rows(moai_ctx *c, const uint64_t *packed, uint64_t *out, size_t n_poly, size_t L, const uint32_t *prime_index,
@@ -221,46 +213,5 @@ extern "C" int moai_unpack_rows(moai_ctx *c, const uint64_t *packed, uint64_t *o
 {
     MOAI_AUDIT(stream, packed, out, invalid);
     trace_op("unpack_rows", L, n_poly);
-    WireArgs a;
-    int rc = wire_args(c, L, prime_index, &a);
-    if (rc)
-    {
-        return rc;
-    }
-    if (n_poly == 0)
-    {
-        return MOAI_OK;
-    }
-    if (!packed || !out)
-    {
-        return set_error(MOAI_EINVAL, "null argument");
-    }
-    if (n_poly > ((size_t)1 << 40))
-    {
-        return set_error(MOAI_EINVAL, "too many polynomials");
-    }
-    if ((uintptr_t)out & 15)
-    {
-        return set_error(MOAI_EINVAL, "out must be 16-byte aligned");
-    }
-    if (overlap(out, n_poly * L * c->n * 8, packed, n_poly * a.poly_words * 8))
-    {
-        return set_error(MOAI_EINVAL, "packed and out overlap");
-    }
-    rc = enter_device(c);
-    if (rc)
-    {
-        return rc;
-    }
-    a.invalid = invalid;
-    for (size_t p0 = 0; p0 < n_poly; p0 += 65535)
-    {
-        const size_t np = n_poly - p0 < 65535 ? n_poly - p0 : 65535;
-        a.src = packed + p0 * a.poly_words;
-        a.dst = out + p0 * L * c->n;
-        hipLaunchKernelGGL(wire_unpack, dim3((uint32_t)((c->n / 2 + 255) / 256), (uint32_t)L, (uint32_t)np), dim3(256), 0,
-                           (hipStream_t)stream, a);
-        MOAI_LAUNCH_CHECK();
-    }
-    return MOAI_OK;
+    return wire_launch(wire_unpack, true, c, out, const_cast<uint64_t *>(packed), n_poly, L, prime_index, invalid, stream);
 }

@@ -189,6 +189,34 @@ def test_decode_in_chunks(moai):
         assert_same(full[b], SD.decode(octx, enc, plain[b], L, 2.0**40))
 
 
+def test_decode_chunks_and_scale_groups(moai):
+    """N = 4096, L = 3: a plaintext needs 4096 * (3 * 8 + 16) = 163840 bytes of scratch.  At MOAI_DEC_TMP_MB = 1 six fit a chunk,
+    so 346 plaintexts are 57 chunks of 6 and one of 4; at 24 MiB 153 fit, so they are chunks of 153, 153 and 40, and a chunk of
+    153 is two compose launches of 128 (DEC_SCALES, the scales that travel in one launch) and 25.  Every plaintext has its own
+    scale, so one that met another's, or another chunk's rows, decodes to other bits."""
+    logn = 12
+    n = 1 << logn
+    primes, octx, enc = _setup(logn, [51, 46, 46, 58])
+    rng = np.random.default_rng(346)
+    B, L = 2 * 153 + 40, 3
+    plain = O.uniform_rns(rng, primes[:L], (B,), n)
+    scales = [2.0**30 * (1 + b / 1024) for b in range(B)]
+    d = moai.DeviceBuffer.from_numpy(plain)
+    # a fresh context each: a stream arena that already holds the whole batch sets the budget instead
+    runs = {}
+    for mb in (1, 24):
+        moai.hip.set_tuning("MOAI_DEC_TMP_MB", mb)
+        try:
+            runs[mb] = moai.Context(logn, primes).ckks_decode(d, L, scales, n_batch=B)
+        finally:
+            moai.hip.reset_tuning()
+    full = moai.Context(logn, primes).ckks_decode(d, L, scales, n_batch=B)
+    assert (_bits(full) == _bits(runs[1])).all() and (_bits(full) == _bits(runs[24])).all()
+    # both sides of every chunk and group boundary of the three runs
+    for b in (0, 5, 6, 127, 128, 152, 153, 255, 256, 280, 281, 305, 306, 341, 342, B - 1):
+        assert_same(full[b], SD.decode(octx, enc, plain[b], L, scales[b]))
+
+
 def test_argument_errors(moai):
     logn = 10
     n = 1 << logn

@@ -204,3 +204,42 @@ def test_argument_errors(moai):
         ctx.check_residues(None, 1, 3)
     # nothing was enqueued: the buffer still holds zeros
     assert not d.to_numpy().any()
+
+
+def test_argument_table(moai):
+    """one fault per row: the return code and the text of moai_last_error().  Nothing is launched on a failing row."""
+    logn, n = 10, 1 << 10
+    primes = O.coeff_modulus_create(n, [51, 46, 58])
+    ctx = moai.Context(logn, primes)
+    lib = moai.hip.lib()
+    EINVAL = moai.hip.MOAI_EINVAL
+    d = moai.DeviceBuffer.from_numpy(np.zeros((2, 2, 3, n), dtype=np.uint64))
+    flag = moai.DeviceBuffer.from_numpy(np.zeros(1, dtype=np.uint64))
+    seeds = _seed(1) + _seed(2)
+    h = ctx.h
+    table = [
+        (lib.moai_seal_prng_bytes, (h, None, 0, 1, d.ptr, None), EINVAL, b"null seed"),
+        (lib.moai_seal_prng_bytes, (h, seeds, 0, 1, d.ptr + 8, None), EINVAL, b"out must be 16-byte aligned"),
+        (lib.moai_seal_prng_bytes, (h, seeds, 2**64 - 1, 2, d.ptr, None), EINVAL, b"block range wraps around 2^64"),
+        (lib.moai_seal_prng_bytes, (h, seeds, 0, 2**36 + 1, d.ptr, None), EINVAL, b"too many blocks"),
+        (lib.moai_seal_prng_bytes, (h, seeds, 0, 0, None, None), 0, None),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 4 * n, 1, 4, None, None, None), EINVAL, b"invalid level"),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 3 * n, 1, 0, None, None, None), EINVAL, b"invalid level"),
+        (lib.moai_seal_sample_uniform, (h, None, d.ptr, 3 * n, 1, 3, None, None, None), EINVAL, b"null seed"),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 3 * n, 0, 3, None, None, None), EINVAL, b"count must be between 1 and 2^24"),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 3 * n, 2**24 + 1, 3, None, None, None), EINVAL,
+         b"count must be between 1 and 2^24"),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 3 * n - 2, 2, 3, None, None, None), EINVAL,
+         b"stride is smaller than a polynomial"),
+        (lib.moai_seal_sample_uniform, (h, seeds, d.ptr, 3 * n + 1, 2, 3, None, None, None), EINVAL, b"out must be 16-byte aligned"),
+        (lib.moai_check_residues, (h, d.ptr, 1, 4, None, flag.ptr, None), EINVAL, b"invalid level"),
+        (lib.moai_check_residues, (h, d.ptr, 1, 0, None, flag.ptr, None), EINVAL, b"invalid level"),
+        (lib.moai_check_residues, (h, d.ptr, 1, 3, None, None, None), EINVAL, b"null argument"),
+        (lib.moai_check_residues, (h, None, 0, 3, None, None, None), 0, None),
+        (lib.moai_total_coeff_modulus_bit_count, (h, 4, None), 0, b"invalid level"),
+        (lib.moai_total_coeff_modulus_bit_count, (h, 0, None), 0, b"invalid level"),
+    ]
+    for fn, args, rc, text in table:
+        assert fn(*args) == rc, (fn.__name__, args[1:])
+        assert text is None or lib.moai_last_error() == text, (fn.__name__, args[1:], lib.moai_last_error())
+    assert not d.to_numpy().any() and not flag.to_numpy().any()

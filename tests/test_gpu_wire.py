@@ -135,6 +135,33 @@ def test_validity_flag(moai, logn, bits):
             assert none is None
 
 
+def test_pack_unpack_past_one_launch(moai):
+    """65535 + 2 polynomials: a launch holds 65535 (gridDim.z), so the second one starts from advanced pointers.  N = 16 with a
+    30-bit and a 31-bit prime (rows of 8 words each, so the row offset matters): the round trip is bit-exact, the packed words
+    on both sides of the boundary are the comparator's, and a residue equal to its prime past the boundary is reported"""
+    logn, bits = 4, [30, 31]
+    primes, _, ctx = _setup(moai, logn, bits)
+    n, L, n_poly = 1 << logn, 2, 65535 + 2
+    assert sorted(int(q).bit_length() for q in primes) == bits
+    polys = O.uniform_rns(np.random.default_rng(65537), primes, (n_poly,), n)
+    pw = WF.packed_words(n, primes)
+    d = moai.DeviceBuffer.from_numpy(polys)
+    packed = ctx.pack_rows(d, n_poly, L)
+    words = packed.to_numpy().reshape(n_poly, pw)
+    for p in (0, 65534, 65535, 65536):
+        assert (words[p] == WF.pack_rows(polys[p:p + 1], primes)).all(), p
+    back, invalid = ctx.unpack_rows(packed, n_poly, L)
+    assert invalid is False and (back.to_numpy((n_poly, L, n)) == polys).all()
+    assert ctx.check_residues(d, n_poly, L) is False
+    bad = polys.copy()
+    bad[65536, 1, 3] = primes[1]
+    bad_words = words.copy()
+    bad_words[65536] = WF.pack_rows(bad[65536:], primes)
+    out, invalid = ctx.unpack_rows(moai.DeviceBuffer.from_numpy(bad_words), n_poly, L)
+    assert invalid is True and (out.to_numpy((n_poly, L, n)) == bad).all()
+    assert ctx.check_residues(moai.DeviceBuffer.from_numpy(bad), n_poly, L) is True
+
+
 def _sym_c0(octx, noise_key, seed, seq, sk_ntt, L, rows=None):
     """(c0, a) of a symmetric encryption of zero: e from (noise_key, purpose 3), a from (seed, purpose 1)"""
     n, primes = octx.n, octx.primes[:L]
@@ -304,4 +331,33 @@ def test_argument_errors(moai):
     assert lib.moai_expand_seeded(ctx.h, SEED, 0, d.ptr, d.ptr + 8 * 2 * n, 1, 3, None, None) == EINVAL
     assert b"overlap" in lib.moai_last_error()
     # nothing was enqueued: the buffers still hold zeros
+    assert not d.to_numpy().any() and not e.to_numpy().any()
+
+
+def test_argument_table(moai):
+    """one fault per row: the return code and the text of moai_last_error().  Nothing is launched on a failing row."""
+    logn = 10
+    n = 1 << logn
+    primes = O.coeff_modulus_create(n, [51, 46, 58])
+    ctx = moai.Context(logn, primes)
+    d = moai.DeviceBuffer.from_numpy(np.zeros((4, 2, 3, n), dtype=np.uint64))
+    e = moai.DeviceBuffer.from_numpy(np.zeros((4, 2, 3, n), dtype=np.uint64))
+    lib = moai.hip.lib()
+    EINVAL = moai.hip.MOAI_EINVAL
+    h = ctx.h
+    pw8 = 8 * ctx.packed_words(3)
+    table = [
+        # in [2][3][N] before packed, and packed [2][pw] before in
+        (lib.moai_pack_rows, (h, d.ptr, d.ptr + 8 * n, 2, 3, None, None), EINVAL, b"in and packed overlap"),
+        (lib.moai_pack_rows, (h, d.ptr + pw8, d.ptr, 2, 3, None, None), EINVAL, b"in and packed overlap"),
+        (lib.moai_unpack_rows, (h, d.ptr + 16 * n, d.ptr, 2, 3, None, None, None), EINVAL, b"packed and out overlap"),
+        (lib.moai_unpack_rows, (h, d.ptr, d.ptr + pw8, 2, 3, None, None, None), EINVAL, b"packed and out overlap"),
+        (lib.moai_unpack_rows, (h, d.ptr, e.ptr + 8, 1, 3, None, None, None), EINVAL, b"out must be 16-byte aligned"),
+        (lib.moai_pack_rows, (h, d.ptr, e.ptr, 2**40 + 1, 3, None, None), EINVAL, b"too many polynomials"),
+        (lib.moai_unpack_rows, (h, d.ptr, e.ptr, 2**40 + 1, 3, None, None, None), EINVAL, b"too many polynomials"),
+        (lib.moai_expand_seeded, (h, SEED, 0, d.ptr, d.ptr + 8 * 2 * n, 1, 3, None, None), EINVAL, b"c0 and out overlap"),
+        (lib.moai_expand_seeded, (h, SEED, 0, d.ptr + 8 * 3 * n, d.ptr, 1, 3, None, None), EINVAL, b"c0 and out overlap"),
+    ]
+    for fn, args, rc, text in table:
+        assert fn(*args) == rc and text in lib.moai_last_error(), (fn.__name__, args[1:], lib.moai_last_error())
     assert not d.to_numpy().any() and not e.to_numpy().any()
