@@ -26,8 +26,11 @@
 // What is different inside:
 //  * no NTL: the modular-reduction polynomial comes from bootstrapping/moai_remez.h, the transform diagonals from
 //    bootstrapping/moai_fft_diagonals.h (both re-derived; see those files for what pins them);
-//  * the evaluation runs on the device through seal/moai_bootstrap_eval.h (PackedBootstrapper3): the evaluator calls of the
-//    reference's routines in their order, with the plaintext diagonals encoded once per (level, scale) and cached;
+//  * the evaluation runs on the device through seal/moai_bootstrap_eval.h: ONE engine class, PackedBootstrapper3, for full
+//    and sparse slots alike, one instance per logn of slot_vec built on first use (engine_for) and dropped, with the cached
+//    transforms of bsgs_linear_transform, whenever the sets or final_scale change (reset_engines).  It issues the evaluator
+//    calls of the reference's routines in their order, with the plaintext diagonals encoded once per (level, scale) and
+//    cached, and holds no per-call state: the forwards with the reference's names pass the member initial_scale along;
 //  * bootstrap_3 is what MOAI calls from its OpenMP loops, one ciphertext per call (include/test/test_full_scheme.hpp:
 //    654-660).  Concurrent callers are gathered into ONE packed run (leader / followers, bounded waits): every ciphertext
 //    gets exactly the result of its own call -- the packed kernels compute each member independently, bit-identical to
@@ -144,9 +147,7 @@ public:
     {
         std::lock_guard<std::mutex> run(run_mu_); // not while a bootstrap holds a reference to the engine
         final_scale = _final_scale;
-        std::lock_guard<std::mutex> g(engine_mu_);
-        engine_.reset();
-        sparse_engines_.clear();
+        reset_engines();
     }
 
     // ---- keys ------------------------------------------------------------------------------------------------------
@@ -210,15 +211,15 @@ public:
     {
         transform(true, totlen, basicstep, coeff_logn, fftcoeff).apply(cipher, rtncipher, gal_keys);
     }
+    // the reference's names for the stages, on the current logn; those that rescale the third forward set read the member
+    // initial_scale, as the reference's do
     void sflinv_full_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        engine().sflinv_full_3(rtncipher, cipher);
+        engine().sflinv(rtncipher, cipher);
     }
     void sfl_full_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        auto &e = engine();
-        e.initial_scale() = initial_scale;
-        e.sfl_full_3(rtncipher, cipher);
+        engine().sfl(rtncipher, cipher, false, initial_scale);
     }
     void coefftoslot_full_3(Ciphertext &rtncipher1, Ciphertext &rtncipher2, Ciphertext &cipher)
     {
@@ -226,34 +227,24 @@ public:
     }
     void slottocoeff_full_3(Ciphertext &rtncipher, Ciphertext &cipher1, Ciphertext &cipher2)
     {
-        auto &e = engine();
-        e.initial_scale() = initial_scale;
-        e.slottocoeff_full_3(rtncipher, cipher1, cipher2);
+        engine().slottocoeff_full_3(rtncipher, cipher1, cipher2, false, initial_scale);
     }
     void sfl_full_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        auto &e = engine();
-        e.initial_scale() = initial_scale;
-        e.sfl_full_half_3(rtncipher, cipher);
+        engine().sfl(rtncipher, cipher, true, initial_scale);
     }
     void slottocoeff_full_half_3(Ciphertext &rtncipher, Ciphertext &cipher1, Ciphertext &cipher2)
     {
-        auto &e = engine();
-        e.initial_scale() = initial_scale;
-        e.slottocoeff_full_half_3(rtncipher, cipher1, cipher2);
+        engine().slottocoeff_full_3(rtncipher, cipher1, cipher2, true, initial_scale);
     }
     // the sparse counterparts (3 <= logn < logNh)
     void sfl_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        auto &e = sparse_engine(logn);
-        e.initial_scale() = initial_scale;
-        e.sfl_half_3(rtncipher, cipher);
+        sparse_engine().sfl(rtncipher, cipher, true, initial_scale);
     }
     void slottocoeff_half_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        auto &e = sparse_engine(logn);
-        e.initial_scale() = initial_scale;
-        e.slottocoeff_half_3(rtncipher, cipher);
+        sparse_engine().slottocoeff_3(rtncipher, cipher, true, initial_scale);
     }
     void modraise_inplace(Ciphertext &cipher)
     {
@@ -271,27 +262,15 @@ public:
     void bootstrap_sparse_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
         std::lock_guard<std::mutex> run(run_mu_);
-        sparse_engine(logn).bootstrap_3(rtncipher, cipher);
+        sparse_engine().bootstrap_3(rtncipher, cipher);
     }
     void bootstrap_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        initial_scale = cipher.scale(); // the reference writes this member from every calling thread as well (:3497)
-        const long ln = logn;
-        if (ln != logNh)
-        {
-            check_sparse(ln); // before anything is enqueued
-        }
+        const long ln = enter(cipher);
         if (cipher.batch() != 1 || combine_us_ <= 0 || max_pack_ == 1)
         {
-            if (ln == logNh)
-            {
-                bootstrap_full_3(rtncipher, cipher);
-            }
-            else
-            {
-                std::lock_guard<std::mutex> run(run_mu_);
-                sparse_engine(ln).bootstrap_3(rtncipher, cipher);
-            }
+            std::lock_guard<std::mutex> run(run_mu_);
+            boot_single(ln, KIND_COMPLEX, rtncipher, cipher);
             return;
         }
         gather_and_run(rtncipher, cipher, ln, pair_real ? KIND_PAIR : KIND_COMPLEX);
@@ -312,18 +291,13 @@ public:
     void bootstrap_sparse_real_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
         std::lock_guard<std::mutex> run(run_mu_);
-        sparse_engine(logn).bootstrap_real_3(rtncipher, cipher);
+        sparse_engine().bootstrap_real_3(rtncipher, cipher);
     }
     // concurrent callers are gathered like bootstrap_3's; real and complex requests never share a pack, and a gathered real
     // call has the bits of a single real call (unless `pair_real` is set, see there)
     void bootstrap_real_3(Ciphertext &rtncipher, Ciphertext &cipher)
     {
-        initial_scale = cipher.scale(); // :3511
-        const long ln = logn;
-        if (ln != logNh)
-        {
-            check_sparse(ln);
-        }
+        const long ln = enter(cipher);
         if (cipher.batch() != 1 || combine_us_ <= 0 || max_pack_ == 1)
         {
             std::lock_guard<std::mutex> run(run_mu_);
@@ -343,14 +317,9 @@ public:
     // what pairing means for accuracy.
     void bootstrap_real_pair_3(Ciphertext &rtn_a, Ciphertext &rtn_b, Ciphertext &a, Ciphertext &b)
     {
-        initial_scale = a.scale();
-        const long ln = logn;
-        if (ln != logNh)
-        {
-            check_sparse(ln);
-        }
+        const long ln = enter(a);
         std::lock_guard<std::mutex> run(run_mu_);
-        boot_pair(ln, rtn_a, rtn_b, a, b);
+        engine_for(ln).bootstrap_real_pair_3(rtn_a, rtn_b, a, b);
     }
     // in[2j] is paired with in[2j + 1]; the pairs run in packs of at most MOAI_BOOT_MAX_PACK pairs, an odd last member goes
     // through the single real sequence.  All inputs on one level, with one scale; they are consumed.
@@ -361,12 +330,7 @@ public:
             rtn.clear();
             return;
         }
-        initial_scale = in[0].scale();
-        const long ln = logn;
-        if (ln != logNh)
-        {
-            check_sparse(ln);
-        }
+        const long ln = enter(in[0]);
         for (auto &c : in)
         {
             if (c.batch() != 1 || c.parms_id() != in[0].parms_id() || c.scale() != in[0].scale() || c.size() != in[0].size() ||
@@ -486,28 +450,47 @@ private:
                 invfftcoeff3[u] = std::move(d.invfftcoeff3);
             }
         }
-        std::lock_guard<std::mutex> g(engine_mu_);
-        engine_.reset();
-        sparse_engines_.clear();
+        reset_engines();
     }
-
-    // the sparse pipeline of slot_vec's entry `ln`, built on first use
-    moai_fused::PackedSparseBootstrapper3 &sparse_engine(long ln)
+    // The engines hold copies of the sets and final_scale; the transforms behind bsgs_linear_transform are keyed by the
+    // ADDRESS of a set, whose contents generate_sets replaces: both go when either input changes.
+    void reset_engines()
     {
-        check_sparse(ln);
         std::lock_guard<std::mutex> g(engine_mu_);
-        auto it = sparse_engines_.find(ln);
-        if (it != sparse_engines_.end())
+        engines_.clear();
+        transforms_.clear();
+    }
+    // what every bootstrap entry point does first: the reference writes the member initial_scale from every calling thread
+    // as well (:3497, :3511), and a sparse logn without a level-3 bootstrapping is refused before anything is enqueued.
+    // Returns the logn of this call.
+    long enter(const Ciphertext &cipher)
+    {
+        initial_scale = cipher.scale();
+        const long ln = logn;
+        if (ln != logNh)
         {
-            return *it->second;
+            check_sparse(ln);
         }
-        const moai_fused::BootDiagonals3 d = diagonals_of(ln);
-        auto e = std::unique_ptr<moai_fused::PackedSparseBootstrapper3>(new moai_fused::PackedSparseBootstrapper3(
-            context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(ln), static_cast<int>(logNh), final_scale, d,
-            mod_reducer->packed_reducer()));
-        return *sparse_engines_.emplace(ln, std::move(e)).first->second;
+        return ln;
     }
 
+    // The pipeline of slot_vec's entry `ln`, full slots (ln == logNh) or sparse, built on first use.  Independent of the
+    // current logn, so a gathered call runs on the engine of its own logn whatever change_logn did meanwhile.
+    moai_fused::PackedBootstrapper3 &engine_for(long ln)
+    {
+        if (ln != logNh)
+        {
+            check_sparse(ln);
+        }
+        std::lock_guard<std::mutex> g(engine_mu_);
+        auto &e = engines_[ln];
+        if (!e)
+        {
+            e.reset(new moai_fused::PackedBootstrapper3(context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(ln),
+                                                        static_cast<int>(logNh), final_scale, diagonals_of(ln), mod_reducer->packed_reducer()));
+        }
+        return *e;
+    }
     // the full-slot pipeline behind the reference's member-logn entry points (sflinv_full_3 ... bootstrap_full_3)
     moai_fused::PackedBootstrapper3 &engine()
     {
@@ -515,20 +498,13 @@ private:
         {
             throw std::logic_error("only logn == logNh is provided");
         }
-        return full_engine();
+        return engine_for(logNh);
     }
-    // the full-slot pipeline of slot_vec's entry logNh, built on first use; independent of the current logn, so a gathered
-    // full-slot call runs here whatever change_logn did meanwhile
-    moai_fused::PackedBootstrapper3 &full_engine()
+    // its counterpart behind the sparse names (bootstrap_sparse_3, sfl_half_3, ...)
+    moai_fused::PackedBootstrapper3 &sparse_engine()
     {
-        std::lock_guard<std::mutex> g(engine_mu_);
-        if (!engine_)
-        {
-            engine_.reset(new moai_fused::PackedBootstrapper3(context, encoder, evaluator, relin_keys, gal_keys, static_cast<int>(logNh),
-                                                              static_cast<int>(logNh), final_scale, diagonals_of(logNh),
-                                                              mod_reducer->packed_reducer()));
-        }
-        return *engine_;
+        check_sparse(logn);
+        return engine_for(logn);
     }
     // the six sets of slot_vec's entry `ln` (caller holds engine_mu_)
     moai_fused::BootDiagonals3 diagonals_of(long ln) const
@@ -550,14 +526,7 @@ private:
         {
             throw std::logic_error("generate_LT_coefficient_3() has not run");
         }
-        moai_fused::BootDiagonals3 d;
-        d.fftcoeff1 = fftcoeff1[u];
-        d.fftcoeff2 = fftcoeff2[u];
-        d.fftcoeff3 = fftcoeff3[u];
-        d.invfftcoeff1 = invfftcoeff1[u];
-        d.invfftcoeff2 = invfftcoeff2[u];
-        d.invfftcoeff3 = invfftcoeff3[u];
-        return d;
+        return { fftcoeff1[u], fftcoeff2[u], fftcoeff3[u], invfftcoeff1[u], invfftcoeff2[u], invfftcoeff3[u] };
     }
     moai_fused::BsgsLinearTransform &transform(bool rotated, int totlen, int basicstep, int coeff_logn,
                                                const vector<vector<complex<double>>> &fftcoeff)
@@ -584,25 +553,8 @@ private:
     };
     void boot_single(long ln, Kind kind, Ciphertext &out, Ciphertext &in)
     {
-        if (ln == logNh)
-        {
-            kind == KIND_COMPLEX ? full_engine().bootstrap_3(out, in) : full_engine().bootstrap_real_3(out, in);
-        }
-        else
-        {
-            kind == KIND_COMPLEX ? sparse_engine(ln).bootstrap_3(out, in) : sparse_engine(ln).bootstrap_real_3(out, in);
-        }
-    }
-    void boot_pair(long ln, Ciphertext &out_a, Ciphertext &out_b, Ciphertext &a, Ciphertext &b)
-    {
-        if (ln == logNh)
-        {
-            full_engine().bootstrap_real_pair_3(out_a, out_b, a, b);
-        }
-        else
-        {
-            sparse_engine(ln).bootstrap_real_pair_3(out_a, out_b, a, b);
-        }
+        auto &e = engine_for(ln);
+        kind == KIND_COMPLEX ? e.bootstrap_3(out, in) : e.bootstrap_real_3(out, in);
     }
     // in[2j] with in[2j + 1] as one packed paired run, an odd last member through the single real sequence
     void run_paired(long ln, Ciphertext *const *in, Ciphertext *const *out, std::size_t count)
@@ -611,7 +563,7 @@ private:
         if (pairs == 1)
         {
             Ciphertext oa, ob;
-            boot_pair(ln, oa, ob, *in[0], *in[1]);
+            engine_for(ln).bootstrap_real_pair_3(oa, ob, *in[0], *in[1]);
             *out[0] = std::move(oa);
             *out[1] = std::move(ob);
         }
@@ -628,7 +580,7 @@ private:
             Ciphertext pa = moai_fused::pack(first, context), pb = moai_fused::pack(second, context), oa, ob;
             first.clear();
             second.clear();
-            boot_pair(ln, oa, ob, pa, pb);
+            engine_for(ln).bootstrap_real_pair_3(oa, ob, pa, pb);
             moai_fused::unpack(oa, context, first);
             moai_fused::unpack(ob, context, second);
             for (std::size_t j = 0; j < pairs; j++)
@@ -808,7 +760,6 @@ private:
     long combine_us_ = 2000;
     std::size_t max_pack_ = 48;
     std::size_t runs_ = 0, members_ = 0;
-    std::unique_ptr<moai_fused::PackedBootstrapper3> engine_;
-    std::map<long, std::unique_ptr<moai_fused::PackedSparseBootstrapper3>> sparse_engines_;
+    std::map<long, std::unique_ptr<moai_fused::PackedBootstrapper3>> engines_; // by logn, full (logNh) and sparse alike
     std::map<std::tuple<const void *, bool, int, int, int>, std::unique_ptr<moai_fused::BsgsLinearTransform>> transforms_;
 };

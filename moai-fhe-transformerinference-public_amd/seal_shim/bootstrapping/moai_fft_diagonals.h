@@ -53,9 +53,10 @@
 #include <string>
 #include <vector>
 
+#include "../seal/moai_level_three.h" // LevelThreeSplit, forward_split / inverse_split, DiagonalSet, LevelThreeDiagonals
+
 namespace moai_boot
 {
-    using cplx = std::complex<double>;
 
     // (M x)[k] = sum over stored offsets d of diag[d][k] * x[(k + d) mod n]; offsets are kept in [0, n)
     class DiagonalMatrix
@@ -213,8 +214,6 @@ namespace moai_boot
         return M;
     }
 
-    using DiagonalSet = std::vector<std::vector<cplx>>;
-
     // index i holds the diagonal of offset (i - totlen) * basicstep, i = 0 .. 2 totlen
     inline DiagonalSet centred_layout(const DiagonalMatrix &M, int totlen, int basicstep)
     {
@@ -252,52 +251,6 @@ namespace moai_boot
             throw std::logic_error("merged transform has diagonals outside its layout");
         }
         return out;
-    }
-
-    // the six sets of the full-slot (logn == logNh) level-3 bootstrapping
-    struct LevelThreeDiagonals
-    {
-        DiagonalSet fftcoeff1, fftcoeff2, fftcoeff3;          // slot-to-coefficient, applied 1, 2, 3
-        DiagonalSet invfftcoeff1, invfftcoeff2, invfftcoeff3; // coefficient-to-slot, applied 1, 2, 3
-    };
-
-    struct LevelThreeSplit
-    {
-        int part[3];      // stages per group, in order of application
-        int totlen[3];
-        int basicstep[3];
-    };
-    // genfftcoeff_3's split (Bootstrapper.cpp:1159-1170): the LAST group gets floor(logn / 3) stages
-    inline LevelThreeSplit forward_split(int logn)
-    {
-        LevelThreeSplit s;
-        s.part[2] = static_cast<int>(std::floor(logn / 3.0));
-        s.part[1] = static_cast<int>(std::floor((logn - s.part[2]) / 2.0));
-        s.part[0] = logn - s.part[2] - s.part[1];
-        s.basicstep[0] = 1;
-        s.basicstep[1] = 1 << s.part[0];
-        s.basicstep[2] = 1 << (s.part[0] + s.part[1]);
-        for (int i = 0; i < 3; i++)
-        {
-            s.totlen[i] = (1 << s.part[i]) - 1;
-        }
-        return s;
-    }
-    // geninvfftcoeff_3's split (:1567-1578): the FIRST group gets floor(logn / 3) stages
-    inline LevelThreeSplit inverse_split(int logn)
-    {
-        LevelThreeSplit s;
-        s.part[0] = static_cast<int>(std::floor(logn / 3.0));
-        s.part[1] = static_cast<int>(std::floor((logn - s.part[0]) / 2.0));
-        s.part[2] = logn - s.part[0] - s.part[1];
-        s.basicstep[0] = 1 << (logn - s.part[0]);
-        s.basicstep[1] = 1 << (logn - s.part[0] - s.part[1]);
-        s.basicstep[2] = 1;
-        for (int i = 0; i < 3; i++)
-        {
-            s.totlen[i] = (1 << s.part[i]) - 1;
-        }
-        return s;
     }
 
     // centred layout with true offsets (see the header): index i holds offset o = (i - totlen) * basicstep, row k taking
@@ -375,68 +328,61 @@ namespace moai_boot
         return nullptr;
     }
 
-    // the six sets of the sparse-slot (3 <= logn < logNh) level-3 bootstrapping, layout in the header
+    // The six sets for n = 2^logn slots: full slots (logNh == logn) or sparse slots (logn < logNh), layouts in the header.
+    // The two kinds merge the same six stage groups; they differ in the layout of the centred sets, in the factor of the
+    // first inverse group and in which sets are doubled to 2n entries.
+    inline LevelThreeDiagonals level_three_sets(int logn, int logNh, long boundary_K)
+    {
+        const bool sparse = logn != logNh;
+        const auto centred = sparse ? sparse_centred_layout : centred_layout;
+        const LevelThreeSplit f = forward_split(logn), v = inverse_split(logn);
+        LevelThreeDiagonals out;
+        {
+            DiagonalMatrix g1 = merge_stages(logn, 0, f.part[0], special_fft_stage);
+            DiagonalMatrix g2 = merge_stages(logn, f.part[0], f.part[1], special_fft_stage);
+            DiagonalMatrix g3 = merge_stages(logn, f.part[0] + f.part[1], f.part[2], special_fft_stage);
+            out.fftcoeff1 = centred(g1, f.totlen[0], f.basicstep[0]);
+            out.fftcoeff2 = centred(g2, f.totlen[1], f.basicstep[1]);
+            out.fftcoeff3 = sparse ? sparse_centred_layout(g3, f.totlen[2], f.basicstep[2]) : rotated_layout(g3, f.totlen[2], f.basicstep[2]);
+        }
+        {
+            DiagonalMatrix g1 = merge_stages(logn, 0, v.part[0], special_ifft_stage);
+            DiagonalMatrix g2 = merge_stages(logn, v.part[0], v.part[1], special_ifft_stage);
+            DiagonalMatrix g3 = merge_stages(logn, v.part[0] + v.part[1], v.part[2], special_ifft_stage);
+            // :1684-1687; sparse :1804-1807, which also undoes the sub-sum's factor
+            g1.scale(sparse ? 1.0 / (boundary_K * (1L << (logNh - logn))) : 1.0 / boundary_K);
+            g3.scale(0.5); // :1689-1692, :1809-1814
+            out.invfftcoeff1 = rotated_layout(g1, v.totlen[0], v.basicstep[0]);
+            out.invfftcoeff2 = centred(g2, v.totlen[1], v.basicstep[1]);
+            out.invfftcoeff3 = centred(g3, v.totlen[2], v.basicstep[2]);
+        }
+        if (sparse)
+        {
+            double_length(out.fftcoeff1, cplx(1.0, 0.0));
+            double_length(out.fftcoeff2, cplx(1.0, 0.0));
+            double_length(out.fftcoeff3, cplx(0.0, 1.0));     // :1409-1412
+            double_length(out.invfftcoeff3, cplx(0.0, -1.0)); // :1812
+        }
+        return out;
+    }
+
+    // sparse slots, 3 <= logn < logNh
     inline LevelThreeDiagonals level_three_sparse_diagonals(int logn, int logNh, long boundary_K)
     {
         if (const char *why = sparse_unsupported_reason(logn, logNh))
         {
             throw std::invalid_argument(std::string("sparse level-3 diagonals: ") + why);
         }
-        LevelThreeDiagonals out;
-        {
-            const LevelThreeSplit f = forward_split(logn);
-            DiagonalMatrix g1 = merge_stages(logn, 0, f.part[0], special_fft_stage);
-            DiagonalMatrix g2 = merge_stages(logn, f.part[0], f.part[1], special_fft_stage);
-            DiagonalMatrix g3 = merge_stages(logn, f.part[0] + f.part[1], f.part[2], special_fft_stage);
-            out.fftcoeff1 = sparse_centred_layout(g1, f.totlen[0], f.basicstep[0]);
-            out.fftcoeff2 = sparse_centred_layout(g2, f.totlen[1], f.basicstep[1]);
-            out.fftcoeff3 = sparse_centred_layout(g3, f.totlen[2], f.basicstep[2]);
-            double_length(out.fftcoeff1, cplx(1.0, 0.0));
-            double_length(out.fftcoeff2, cplx(1.0, 0.0));
-            double_length(out.fftcoeff3, cplx(0.0, 1.0)); // :1409-1412
-        }
-        {
-            const LevelThreeSplit v = inverse_split(logn);
-            DiagonalMatrix g1 = merge_stages(logn, 0, v.part[0], special_ifft_stage);
-            DiagonalMatrix g2 = merge_stages(logn, v.part[0], v.part[1], special_ifft_stage);
-            DiagonalMatrix g3 = merge_stages(logn, v.part[0] + v.part[1], v.part[2], special_ifft_stage);
-            g1.scale(1.0 / (boundary_K * (1L << (logNh - logn)))); // :1804-1807
-            g3.scale(0.5);                                         // :1809-1814
-            out.invfftcoeff1 = rotated_layout(g1, v.totlen[0], v.basicstep[0]);
-            out.invfftcoeff2 = sparse_centred_layout(g2, v.totlen[1], v.basicstep[1]);
-            out.invfftcoeff3 = sparse_centred_layout(g3, v.totlen[2], v.basicstep[2]);
-            double_length(out.invfftcoeff3, cplx(0.0, -1.0)); // :1812
-        }
-        return out;
+        return level_three_sets(logn, logNh, boundary_K);
     }
 
+    // full slots, logn == logNh
     inline LevelThreeDiagonals level_three_diagonals(int logn, long boundary_K)
     {
         if (logn < 3)
         {
             throw std::invalid_argument("the level-3 split needs at least three stages");
         }
-        LevelThreeDiagonals out;
-        {
-            const LevelThreeSplit f = forward_split(logn);
-            DiagonalMatrix g1 = merge_stages(logn, 0, f.part[0], special_fft_stage);
-            DiagonalMatrix g2 = merge_stages(logn, f.part[0], f.part[1], special_fft_stage);
-            DiagonalMatrix g3 = merge_stages(logn, f.part[0] + f.part[1], f.part[2], special_fft_stage);
-            out.fftcoeff1 = centred_layout(g1, f.totlen[0], f.basicstep[0]);
-            out.fftcoeff2 = centred_layout(g2, f.totlen[1], f.basicstep[1]);
-            out.fftcoeff3 = rotated_layout(g3, f.totlen[2], f.basicstep[2]);
-        }
-        {
-            const LevelThreeSplit v = inverse_split(logn);
-            DiagonalMatrix g1 = merge_stages(logn, 0, v.part[0], special_ifft_stage);
-            DiagonalMatrix g2 = merge_stages(logn, v.part[0], v.part[1], special_ifft_stage);
-            DiagonalMatrix g3 = merge_stages(logn, v.part[0] + v.part[1], v.part[2], special_ifft_stage);
-            g1.scale(1.0 / boundary_K); // :1684-1687
-            g3.scale(0.5);              // :1689-1692
-            out.invfftcoeff1 = rotated_layout(g1, v.totlen[0], v.basicstep[0]);
-            out.invfftcoeff2 = centred_layout(g2, v.totlen[1], v.basicstep[1]);
-            out.invfftcoeff3 = centred_layout(g3, v.totlen[2], v.basicstep[2]);
-        }
-        return out;
+        return level_three_sets(logn, logn, boundary_K);
     }
 } // namespace moai_boot

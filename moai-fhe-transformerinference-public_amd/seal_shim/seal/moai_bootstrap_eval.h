@@ -1,12 +1,16 @@
-// seal/moai_bootstrap_eval.h -- the evaluation half of MOAI's bootstrapping (Bootstrapper::bootstrap_full_3)
+// seal/moai_bootstrap_eval.h -- the evaluation half of MOAI's bootstrapping (Bootstrapper::bootstrap_3, bootstrap_real_3)
 // on PACKED ciphertexts: modulus raise, coefficient-to-slot, the modular reduction's
-// Chebyshev polynomial in baby-step / giant-step form with its double-angle steps, slot-to-coefficient.
+// Chebyshev polynomial in baby-step / giant-step form with its double-angle steps, slot-to-coefficient.  ONE engine,
+// PackedBootstrapper3(logn, logNh), serves full slots (logn == logNh) and sparse slots (3 <= logn < logNh), complex, real
+// and paired; the level-3 split and the struct of the six diagonal sets it shares with the setup code are in
+// seal/moai_level_three.h.
 //
 // What it follows, call for call:
 //   Bootstrapper::bootstrap_full_3        include/source/bootstrapping/Bootstrapper.cpp:3231-3251
+//   ::bootstrap_sparse_3                  :3143-3229 (sub-sum, coefftoslot_3 :2721-2726, slottocoeff_3 :2728-2733)
 //   ::modraise_inplace                    :2938-2992   (moai_modraise)
-//   ::coefftoslot_full_3 / sflinv_full_3  :2742-2759, :2602-2623
-//   ::slottocoeff_full_3 / sfl_full_3     :2760-2777, :2460-2497
+//   ::coefftoslot_full_3 / sflinv_full_3  :2742-2759, :2602-2623; sflinv_3 :2579-2600
+//   ::slottocoeff_full_3 / sfl_full_3     :2760-2777, :2460-2497; sfl_3 :2419-2458
 //   ::slottocoeff_full_half_3 / sfl_full_half_3 :2778-2795, :2539-2577; ::bootstrap_full_real_3 :3328-3351
 //   ::slottocoeff_half_3 / sfl_half_3 :2735-2740, :2499-2537; ::bootstrap_sparse_real_3 :3253-3326
 //   ModularReducer::modular_reduction     ModularReducer.cpp:58-78 (the inverse_deg == 1 branch MOAI configures)
@@ -35,6 +39,7 @@
 #include <vector>
 
 #include "seal/moai_bootstrap_lt.h"
+#include "seal/moai_level_three.h"
 #include "seal/seal.h"
 
 namespace moai_fused
@@ -556,11 +561,8 @@ namespace moai_fused
     inline void boot_rotation_steps_3(int logn, int logNh, std::vector<int> &gal_steps_vector)
     {
         const int Nh = 1 << logNh;
-        int div_part1 = static_cast<int>(std::floor(logn / 3.0));
-        int div_part2 = static_cast<int>(std::floor((logn - div_part1) / 2.0));
-        int div_part3 = logn - div_part1 - div_part2;
-        int totlen[3] = { (1 << div_part1) - 1, (1 << div_part2) - 1, (1 << div_part3) - 1 };
-        int basicstep[3] = { 1 << (logn - div_part1), 1 << (logn - div_part1 - div_part2), 1 };
+        const moai_boot::LevelThreeSplit split = moai_boot::inverse_split(logn);
+        const int *totlen = split.totlen, *basicstep = split.basicstep;
         int gs1_e = 0;
         int gs[3] = { giantstep(totlen[0] + 1), giantstep(2 * totlen[1] + 1), giantstep(2 * totlen[2] + 1) };
         if (logn != logNh)
@@ -615,14 +617,8 @@ namespace moai_fused
         giants(2);
     }
 
-    // The diagonals of the six transforms, in the reference's layout (Bootstrapper.h: fftcoeff1..3 and
-    // invfftcoeff1..3 of one slot index): 2 totlen + 1 diagonals for a plain transform, the first
-    // totlen + 1 are used by a rotated one.
-    struct BootDiagonals3
-    {
-        std::vector<std::vector<std::complex<double>>> invfftcoeff1, invfftcoeff2, invfftcoeff3; // coefficient-to-slot
-        std::vector<std::vector<std::complex<double>>> fftcoeff1, fftcoeff2, fftcoeff3;          // slot-to-coefficient
-    };
+    // the six diagonal sets of one slot count (seal/moai_level_three.h), under the name this namespace has always used
+    using BootDiagonals3 = moai_boot::LevelThreeDiagonals;
 
     // Bootstrapper::modraise_inplace (:2938-2992) on a packed ciphertext; it must sit at the lowest level
     inline void modraise_packed(const seal::SEALContext &context, const seal::Evaluator &evaluator, seal::Ciphertext &cipher)
@@ -649,8 +645,20 @@ namespace moai_fused
         cipher = std::move(raised);
     }
 
-    // Bootstrapper::bootstrap_3 for logn == logNh (bootstrap_full_3) on packed ciphertexts.  Like the reference's
-    // Bootstrapper it keeps references to the encoder, evaluator and keys: they must outlive it.
+    // Bootstrapper::bootstrap_3 / bootstrap_real_3 on packed ciphertexts, for n = 2^logn slots of Nh = 2^logNh:
+    //   full slots (logn == logNh; bootstrap_full_3 :3231-3251, bootstrap_full_real_3 :3328-3351):
+    //     modraise; scale = q_0; coefftoslot_full_3; TWO modular reductions; slottocoeff_full_3; scale = final_scale
+    //   sparse slots (3 <= logn < logNh; bootstrap_sparse_3 :3143-3229, bootstrap_sparse_real_3 :3253-3326; the reference
+    //   marks these "not yet", its op sequence is followed call for call), with the sparse sets of
+    //   bootstrapping/moai_fft_diagonals.h (2n-entry diagonals, replicated to N/2 slots by BsgsLinearTransform):
+    //     modraise; scale = q_0; sub-sum; coefftoslot_3; ONE modular reduction; slottocoeff_3; scale = final_scale
+    // The two kinds share the three inverse and three forward transforms; what differs between them is the table in the
+    // constructor and the stages that exist for one kind only, which throw std::logic_error on the other.
+    // Keys of the sparse kind: the sub-sum's steps 2^i and the rotation by n are powers of two, which addBootKeys_3 (:374-392)
+    // lists; the transforms' steps come from boot_rotation_steps_3; a step without its own key is composed from
+    // power-of-two keys as rotate_vector does.
+    // Like the reference's Bootstrapper it keeps references to the encoder, evaluator and keys: they must outlive it.  It
+    // holds no per-call state: the scale a ciphertext came in with is an argument of the stages that need it.
     class PackedBootstrapper3
     {
     public:
@@ -658,30 +666,43 @@ namespace moai_fused
                             const seal::RelinKeys &relin_keys, const seal::GaloisKeys &gal_keys, int logn, int logNh,
                             double final_scale, const BootDiagonals3 &diagonals, const ModularReducer3 &mod_reducer)
             : context_(context), encoder_(encoder), evaluator_(evaluator), relin_keys_(relin_keys), gal_keys_(gal_keys), logn_(logn),
-              Nh_(1 << logNh), n_(1 << logn), final_scale_(final_scale), fftcoeff3_(diagonals.fftcoeff3), mod_reducer_(mod_reducer)
+              logNh_(logNh), Nh_(1 << logNh), n_(1 << logn), sparse_(logn < logNh), final_scale_(final_scale),
+              fftcoeff3_(diagonals.fftcoeff3), mod_reducer_(mod_reducer)
         {
-            if (logn != logNh)
+            if (logn > logNh || logn < 3)
             {
-                throw std::invalid_argument("bootstrap_full_3 is the logn == logNh case");
+                throw std::invalid_argument("bootstrap_3 needs 3 <= logn <= logNh");
             }
-            // sflinv_full_3's split, Bootstrapper.cpp:2603-2613
+            fwd_split_ = moai_boot::forward_split(logn);
+            const moai_boot::LevelThreeSplit v = moai_boot::inverse_split(logn), &f = fwd_split_;
+            // Sparse: the last inverse and all forward transforms read 2n-entry diagonals (coeff_logn = logn + 1), and the
+            // third forward set is centred, 2 totlen + 1 diagonals.  Full: the third forward set is rotated and the reference
+            // fills totlen + 1 diagonals of n entries.
+            kind_ = sparse_ ? Kind{ { logn, logn, logn + 1 }, logn + 1, false, 2 * f.totlen[2] + 1, 2 * n_ }
+                            : Kind{ { logn, logn, logn }, logn, true, f.totlen[2] + 1, n_ };
+            if (sparse_ && fftcoeff3_.size() != static_cast<std::size_t>(kind_.fwd3_count))
             {
-                int p1 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p1) / 2.0));
-                int p3 = logn - p1 - p2;
-                inv_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1 << (logn - p1), logn, diagonals.invfftcoeff1, true));
-                inv_[1].reset(new BsgsLinearTransform(context, Nh_, (1 << p2) - 1, 1 << (logn - p1 - p2), logn, diagonals.invfftcoeff2, false));
-                inv_[2].reset(new BsgsLinearTransform(context, Nh_, (1 << p3) - 1, 1, logn, diagonals.invfftcoeff3, false));
+                throw std::invalid_argument("fftcoeff3 of a sparse slot count has 2 totlen3 + 1 diagonals");
             }
-            // sfl_full_3's split, :2461-2471
+            const moai_boot::DiagonalSet *inv_sets[3] = { &diagonals.invfftcoeff1, &diagonals.invfftcoeff2, &diagonals.invfftcoeff3 };
+            const moai_boot::DiagonalSet *fwd_sets[2] = { &diagonals.fftcoeff1, &diagonals.fftcoeff2 };
+            for (int i = 0; i < 3; i++) // the first inverse transform is the rotated one
             {
-                int p3 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p3) / 2.0));
-                int p1 = logn - p3 - p2;
-                fwd_totlen2_ = (1 << p2) - 1;
-                fwd_totlen3_ = (1 << p3) - 1;
-                fwd_basicstep3_ = 1 << (p1 + p2);
-                fwd_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1, logn, diagonals.fftcoeff1, false));
-                fwd_[1].reset(new BsgsLinearTransform(context, Nh_, fwd_totlen2_, 1 << p1, logn, diagonals.fftcoeff2, false));
+                inv_[i].reset(new BsgsLinearTransform(context, Nh_, v.totlen[i], v.basicstep[i], kind_.inv_coeff_logn[i], *inv_sets[i], i == 0));
             }
+            for (int i = 0; i < 2; i++)
+            {
+                fwd_[i].reset(new BsgsLinearTransform(context, Nh_, f.totlen[i], f.basicstep[i], kind_.fwd_coeff_logn, *fwd_sets[i], false));
+            }
+        }
+
+        int logn() const
+        {
+            return logn_;
+        }
+        bool sparse() const
+        {
+            return sparse_;
         }
 
         // :2938-2992; the ciphertext must sit at the lowest level
@@ -690,289 +711,13 @@ namespace moai_fused
             modraise_packed(context_, evaluator_, cipher);
         }
 
-        // :2602-2623
-        void sflinv_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            seal::Ciphertext tmpct, tmpct2;
-            inv_[0]->apply(cipher, tmpct, gal_keys_);
-            evaluator_.rescale_to_next_inplace(tmpct);
-            inv_[1]->apply(tmpct, tmpct2, gal_keys_);
-            evaluator_.rescale_to_next_inplace(tmpct2);
-            inv_[2]->apply(tmpct2, rtncipher, gal_keys_);
-            evaluator_.rescale_to_next_inplace(rtncipher);
-        }
-
-
-        // :2460-2497
-        void sfl_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            sfl_full_impl(rtncipher, cipher, false);
-        }
-        // :2539-2577: sfl_full_3 with the third set's constants halved, for the real variants (the caller adds the conjugate)
-        void sfl_full_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            sfl_full_impl(rtncipher, cipher, true);
-        }
-
-    private:
-        void sfl_full_impl(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half)
-        {
-            using namespace seal;
-            Ciphertext tmpct, tmpct2;
-            fwd_[0]->apply(cipher, tmpct, gal_keys_);
-            evaluator_.rescale_to_next_inplace(tmpct);
-            fwd_[1]->apply(tmpct, tmpct2, gal_keys_);
-            evaluator_.rescale_to_next_inplace(tmpct2);
-
-            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
-            auto curr_level = context_.get_context_data(tmpct2.parms_id())->chain_index();
-            double mod_zero = static_cast<double>(modulus[0].value());
-            double curr_mod = static_cast<double>(modulus[curr_level].value());
-            // the third set is rescaled by a factor that depends on the running scale; it is the same for every
-            // ciphertext that went through the same pipeline, so the scaled transform is kept per factor
-            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_, half);
-            auto it = fwd3_.find(key);
-            if (it == fwd3_.end())
-            {
-                // the reference fills totlen2 + 1 entries of an array of 2 totlen3 + 1 and the rotated transform reads
-                // totlen3 + 1 of them: defined only when the last two parts of the split are equal (logn = 15: 5 + 5 + 5)
-                if (fwd_totlen2_ != fwd_totlen3_)
-                {
-                    throw std::invalid_argument("sfl_full_3 is undefined in the reference for this logn");
-                }
-                std::vector<std::vector<std::complex<double>>> scaled(static_cast<std::size_t>(fwd_totlen3_ + 1));
-                for (int i = 0; i < fwd_totlen2_ + 1; i++)
-                {
-                    scaled[static_cast<std::size_t>(i)].resize(static_cast<std::size_t>(n_));
-                    for (int j = 0; j < n_; j++)
-                    {
-                        const std::complex<double> numerator =
-                            fftcoeff3_.at(static_cast<std::size_t>(i)).at(static_cast<std::size_t>(j)) * curr_mod * mod_zero * final_scale_;
-                        scaled[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)] =
-                            half ? numerator / (2 * tmpct2.scale() * tmpct2.scale() * initial_scale_) // :2569
-                                 : numerator / (tmpct2.scale() * tmpct2.scale() * initial_scale_);    // :2489
-                    }
-                }
-                it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(context_, Nh_, fwd_totlen3_, fwd_basicstep3_,
-                                                                                                    logn_, scaled, true)))
-                         .first;
-            }
-            it->second->apply(tmpct2, rtncipher, gal_keys_);
-            evaluator_.rescale_to_next_inplace(rtncipher);
-        }
-
-    public:
-        // :2742-2759
-        void coefftoslot_full_3(seal::Ciphertext &rtncipher1, seal::Ciphertext &rtncipher2, const seal::Ciphertext &cipher)
-        {
-            using namespace seal;
-            Ciphertext tmpct1, tmpct2, tmpct3, tmpct4;
-            sflinv_full_3(tmpct1, cipher);
-            std::complex<double> iunit(0.0, 1.0);
-            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
-            for (auto &z : tmpvec)
-            {
-                z -= iunit;
-            }
-            Plaintext tmpplain;
-            encoder_.encode(tmpvec, 1.0, tmpplain);
-            evaluator_.mod_switch_to_inplace(tmpplain, tmpct1.parms_id());
-            evaluator_.multiply_plain(tmpct1, tmpplain, tmpct2);
-            evaluator_.complex_conjugate(tmpct2, gal_keys_, tmpct3);
-            evaluator_.complex_conjugate(tmpct1, gal_keys_, tmpct4);
-            evaluator_.add_reduced_error(tmpct1, tmpct4, rtncipher1);
-            evaluator_.add_reduced_error(tmpct2, tmpct3, rtncipher2);
-        }
-
-        // :2760-2777
-        void slottocoeff_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher1, const seal::Ciphertext &cipher2)
-        {
-            using namespace seal;
-            Ciphertext tmpct1, tmpct3;
-            std::complex<double> iunit(0.0, 1.0);
-            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
-            for (auto &z : tmpvec)
-            {
-                z += iunit;
-            }
-            Plaintext tmpplain;
-            encoder_.encode(tmpvec, 1.0, tmpplain);
-            evaluator_.mod_switch_to_inplace(tmpplain, cipher2.parms_id());
-            evaluator_.multiply_plain(cipher2, tmpplain, tmpct1);
-            evaluator_.add_reduced_error(cipher1, tmpct1, tmpct3);
-            sfl_full_3(rtncipher, tmpct3);
-        }
-
-        // :2778-2795
-        void slottocoeff_full_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher1, const seal::Ciphertext &cipher2)
-        {
-            using namespace seal;
-            Ciphertext tmpct1, tmpct3;
-            std::complex<double> iunit(0.0, 1.0);
-            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
-            for (auto &z : tmpvec)
-            {
-                z += iunit;
-            }
-            Plaintext tmpplain;
-            encoder_.encode(tmpvec, 1.0, tmpplain);
-            evaluator_.mod_switch_to_inplace(tmpplain, cipher2.parms_id());
-            evaluator_.multiply_plain(cipher2, tmpplain, tmpct1);
-            evaluator_.add_reduced_error(cipher1, tmpct1, tmpct3);
-            sfl_full_half_3(rtncipher, tmpct3);
-        }
-
-        // bootstrap_3 (:3496-3502) -> bootstrap_full_3 (:3231-3251); `cipher` is consumed like the reference's
-        void bootstrap_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
-        {
-            using namespace seal;
-            initial_scale_ = cipher.scale();
-            modraise_inplace(cipher);
-            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
-            cipher.scale() = static_cast<double>(modulus[0].value());
-            Ciphertext rtn1, rtn2;
-            coefftoslot_full_3(rtn1, rtn2, cipher);
-            Ciphertext modrtn1, modrtn2;
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn1, rtn1);
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn2, rtn2);
-            slottocoeff_full_3(rtncipher, modrtn1, modrtn2);
-            rtncipher.scale() = final_scale_;
-        }
-
-        // bootstrap_real_3 (:3510-3516) -> bootstrap_full_real_3 (:3328-3351): the result encodes the real part of the message
-        void bootstrap_real_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
-        {
-            using namespace seal;
-            bootstrap_half(rtncipher, cipher);
-            Ciphertext conjct;
-            evaluator_.complex_conjugate(rtncipher, gal_keys_, conjct);
-            evaluator_.add_inplace_reduced_error(rtncipher, conjct);
-        }
-
-        // Two real ciphertexts through ONE bootstrap: a + i b (moai_fused::pair_real), everything of bootstrap_real_3 up to its
-        // final conjugate-and-add -- which leaves (a + i b) / 2 at final_scale -- and the conjugation shared by both outputs
-        // (moai_fused::split_real).  a and b are consumed.  Each output depends on its partner: the modular reduction's
-        // error grows with |a + i b|, and an input that is not real leaks its imaginary part into the other output.
-        void bootstrap_real_pair_3(seal::Ciphertext &out_a, seal::Ciphertext &out_b, seal::Ciphertext &a, seal::Ciphertext &b)
-        {
-            using namespace seal;
-            if (!a.is_ntt_form() && a.size() == 2)
-            {
-                evaluator_.transform_to_ntt_inplace(a);
-            }
-            if (!b.is_ntt_form() && b.size() == 2)
-            {
-                evaluator_.transform_to_ntt_inplace(b);
-            }
-            Ciphertext c, r;
-            moai_fused::pair_real(context_, a, b, c);
-            a.release();
-            b.release();
-            bootstrap_half(r, c);
-            moai_fused::split_real(context_, r, gal_keys_, out_a, out_b);
-        }
-
-    private:
-        // bootstrap_full_real_3 up to and including `scale = final_scale` (:3328-3346): encodes half the message
-        void bootstrap_half(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
-        {
-            using namespace seal;
-            initial_scale_ = cipher.scale();
-            modraise_inplace(cipher);
-            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
-            cipher.scale() = static_cast<double>(modulus[0].value());
-            Ciphertext rtn1, rtn2;
-            coefftoslot_full_3(rtn1, rtn2, cipher);
-            Ciphertext modrtn1, modrtn2;
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn1, rtn1);
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn2, rtn2);
-            slottocoeff_full_half_3(rtncipher, modrtn1, modrtn2);
-            rtncipher.scale() = final_scale_;
-        }
-
-    public:
-        double &initial_scale()
-        {
-            return initial_scale_;
-        }
-
-    private:
-        seal::SEALContext context_;
-        const seal::CKKSEncoder &encoder_;
-        const seal::Evaluator &evaluator_;
-        const seal::RelinKeys &relin_keys_;
-        const seal::GaloisKeys &gal_keys_;
-        int logn_, Nh_, n_;
-        double final_scale_, initial_scale_ = 1;
-        std::vector<std::vector<std::complex<double>>> fftcoeff3_; // rescaled per running scale in sfl_full_3; the other sets live in their transforms
-        ModularReducer3 mod_reducer_;
-        std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
-        int fwd_totlen2_ = 0, fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
-        std::map<std::tuple<double, double, double, bool>, std::unique_ptr<BsgsLinearTransform>> fwd3_; // last: the halved set
-    };
-    // Bootstrapper::bootstrap_3 for 3 <= logn < logNh (bootstrap_sparse_3, :3143-3229) on packed ciphertexts, with the
-    // sparse diagonal sets of bootstrapping/moai_fft_diagonals.h (2n-entry diagonals replicated to N/2 slots by
-    // BsgsLinearTransform).  The reference marks these routines "not yet"; its op sequence is followed call for call:
-    //   modraise; scale = q_0; sub-sum (rotate by 2^i, add_inplace, i = logn .. logNh-1, at the top level);
-    //   coefftoslot_3 (:2721-2726) = sflinv_3 (:2579-2600) + complex_conjugate + add_reduced_error;
-    //   ONE modular_reduction; slottocoeff_3 (:2728-2733) = sfl_3 (:2419-2458) + rotate_vector(n) + add_reduced_error;
-    //   scale = final_scale.
-    // Keys: the sub-sum's steps 2^i and the rotation by n are powers of two, which addBootKeys_3 (:374-392) lists; the
-    // transforms' steps come from addLeftRotKeys_Linear_to_vector_3 (boot_rotation_steps_3); a step without its own key
-    // is composed from power-of-two keys as rotate_vector does.
-    class PackedSparseBootstrapper3
-    {
-    public:
-        PackedSparseBootstrapper3(const seal::SEALContext &context, const seal::CKKSEncoder &encoder, const seal::Evaluator &evaluator,
-                                  const seal::RelinKeys &relin_keys, const seal::GaloisKeys &gal_keys, int logn, int logNh,
-                                  double final_scale, const BootDiagonals3 &diagonals, const ModularReducer3 &mod_reducer)
-            : context_(context), encoder_(encoder), evaluator_(evaluator), relin_keys_(relin_keys), gal_keys_(gal_keys), logn_(logn),
-              logNh_(logNh), Nh_(1 << logNh), n_(1 << logn), final_scale_(final_scale), fftcoeff3_(diagonals.fftcoeff3),
-              mod_reducer_(mod_reducer)
-        {
-            if (logn >= logNh || logn < 3)
-            {
-                throw std::invalid_argument("bootstrap_sparse_3 needs 3 <= logn < logNh");
-            }
-            // sflinv_3's split, :2580-2590; the third transform reads 2n-entry diagonals (coeff_logn = logn + 1)
-            {
-                int p1 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p1) / 2.0));
-                int p3 = logn - p1 - p2;
-                inv_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1 << (logn - p1), logn, diagonals.invfftcoeff1, true));
-                inv_[1].reset(new BsgsLinearTransform(context, Nh_, (1 << p2) - 1, 1 << (logn - p1 - p2), logn, diagonals.invfftcoeff2, false));
-                inv_[2].reset(new BsgsLinearTransform(context, Nh_, (1 << p3) - 1, 1, logn + 1, diagonals.invfftcoeff3, false));
-            }
-            // sfl_3's split, :2420-2430; all three transforms centred on 2n-entry diagonals
-            {
-                int p3 = static_cast<int>(std::floor(logn / 3.0)), p2 = static_cast<int>(std::floor((logn - p3) / 2.0));
-                int p1 = logn - p3 - p2;
-                fwd_totlen3_ = (1 << p3) - 1;
-                fwd_basicstep3_ = 1 << (p1 + p2);
-                fwd_[0].reset(new BsgsLinearTransform(context, Nh_, (1 << p1) - 1, 1, logn + 1, diagonals.fftcoeff1, false));
-                fwd_[1].reset(new BsgsLinearTransform(context, Nh_, (1 << p2) - 1, 1 << p1, logn + 1, diagonals.fftcoeff2, false));
-            }
-            if (fftcoeff3_.size() != static_cast<std::size_t>(2 * fwd_totlen3_ + 1))
-            {
-                throw std::invalid_argument("fftcoeff3 of a sparse slot count has 2 totlen3 + 1 diagonals");
-            }
-        }
-
-        int logn() const
-        {
-            return logn_;
-        }
-
-        void modraise_inplace(seal::Ciphertext &cipher) const
-        {
-            modraise_packed(context_, evaluator_, cipher);
-        }
-
-        // :3158-3163: cipher += rotate_vector(cipher, 2^i), i = logn .. logNh - 1.  A step with its own key is one key switch
-        // whose last kernel adds into the running sum (moai_apply_galois_acc: the residues of rotate + add_inplace); a step
-        // without one goes through the evaluator.
+        // sparse only, :3158-3163: cipher += rotate_vector(cipher, 2^i), i = logn .. logNh - 1.  A step with its own key is one
+        // key switch whose last kernel adds into the running sum (moai_apply_galois_acc: the residues of rotate + add_inplace);
+        // a step without one goes through the evaluator.
         void subsum_inplace(seal::Ciphertext &cipher) const
         {
             using namespace seal;
+            require_kind(true, "subsum_inplace");
             if (cipher.size() != 2 || !cipher.is_ntt_form())
             {
                 throw std::invalid_argument("encrypted must be a size-2 ciphertext in NTT form");
@@ -1002,8 +747,8 @@ namespace moai_fused
             context_.sync(); // the staging copy goes out of scope
         }
 
-        // :2579-2600
-        void sflinv_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        // sflinv_full_3 :2602-2623, sflinv_3 :2579-2600
+        void sflinv(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
         {
             seal::Ciphertext tmpct, tmpct2;
             inv_[0]->apply(cipher, tmpct, gal_keys_);
@@ -1014,19 +759,10 @@ namespace moai_fused
             evaluator_.rescale_to_next_inplace(rtncipher);
         }
 
-        // :2419-2458; the third set is scaled by the running scale and kept per factor, as in sfl_full_3
-        void sfl_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            sfl_impl(rtncipher, cipher, false);
-        }
-        // :2499-2537: sfl_3 with the third set's constants halved
-        void sfl_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            sfl_impl(rtncipher, cipher, true);
-        }
-
-    private:
-        void sfl_impl(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half)
+        // sfl_full_3 :2460-2497, sfl_3 :2419-2458; `half`: the third set's constants halved, for the real variants whose caller
+        // adds the conjugate (sfl_full_half_3 :2539-2577, sfl_half_3 :2499-2537).  `initial_scale`: the scale the ciphertext had
+        // when it entered the bootstrap.
+        void sfl(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half, double initial_scale)
         {
             using namespace seal;
             Ciphertext tmpct, tmpct2;
@@ -1039,85 +775,118 @@ namespace moai_fused
             auto curr_level = context_.get_context_data(tmpct2.parms_id())->chain_index();
             double mod_zero = static_cast<double>(modulus[0].value());
             double curr_mod = static_cast<double>(modulus[curr_level].value());
-            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale_, half);
+            // the third set is rescaled by a factor that depends on the running scale; it is the same for every
+            // ciphertext that went through the same pipeline, so the scaled transform is kept per factor
+            auto key = std::make_tuple(curr_mod, tmpct2.scale(), initial_scale, half);
             auto it = fwd3_.find(key);
             if (it == fwd3_.end())
             {
-                std::vector<std::vector<std::complex<double>>> scaled(fftcoeff3_.size());
-                for (std::size_t i = 0; i < fftcoeff3_.size(); i++)
+                // full slots: the reference fills totlen2 + 1 entries of an array of 2 totlen3 + 1 and the rotated transform reads
+                // totlen3 + 1 of them: defined only when the last two parts of the split are equal (logn = 15: 5 + 5 + 5)
+                if (!sparse_ && fwd_split_.totlen[1] != fwd_split_.totlen[2])
                 {
-                    scaled[i].resize(static_cast<std::size_t>(2 * n_));
-                    for (std::size_t j = 0; j < static_cast<std::size_t>(2 * n_); j++)
+                    throw std::invalid_argument("sfl_full_3 is undefined in the reference for this logn");
+                }
+                moai_boot::DiagonalSet scaled(static_cast<std::size_t>(kind_.fwd3_count));
+                for (std::size_t i = 0; i < scaled.size(); i++)
+                {
+                    scaled[i].resize(static_cast<std::size_t>(kind_.fwd3_length));
+                    for (std::size_t j = 0; j < scaled[i].size(); j++)
                     {
-                        const std::complex<double> numerator = fftcoeff3_[i].at(j) * curr_mod * mod_zero * final_scale_;
-                        scaled[i][j] = half ? numerator / (2 * tmpct2.scale() * tmpct2.scale() * initial_scale_) // :2532
-                                            : numerator / (tmpct2.scale() * tmpct2.scale() * initial_scale_);    // :2452
+                        const std::complex<double> numerator = fftcoeff3_.at(i).at(j) * curr_mod * mod_zero * final_scale_;
+                        scaled[i][j] = half ? numerator / (2 * tmpct2.scale() * tmpct2.scale() * initial_scale) // :2569, :2532
+                                            : numerator / (tmpct2.scale() * tmpct2.scale() * initial_scale);    // :2489, :2452
                     }
                 }
-                it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(context_, Nh_, fwd_totlen3_, fwd_basicstep3_,
-                                                                                                    logn_ + 1, scaled, false)))
+                it = fwd3_.emplace(key, std::unique_ptr<BsgsLinearTransform>(new BsgsLinearTransform(
+                                            context_, Nh_, fwd_split_.totlen[2], fwd_split_.basicstep[2], kind_.fwd_coeff_logn, scaled, kind_.fwd3_rotated)))
                          .first;
             }
             it->second->apply(tmpct2, rtncipher, gal_keys_);
             evaluator_.rescale_to_next_inplace(rtncipher);
         }
 
-    public:
-        // :2721-2726
+        // full only, :2742-2759
+        void coefftoslot_full_3(seal::Ciphertext &rtncipher1, seal::Ciphertext &rtncipher2, const seal::Ciphertext &cipher)
+        {
+            using namespace seal;
+            require_kind(false, "coefftoslot_full_3");
+            Ciphertext tmpct1, tmpct2, tmpct3, tmpct4;
+            sflinv(tmpct1, cipher);
+            std::complex<double> iunit(0.0, 1.0);
+            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
+            for (auto &z : tmpvec)
+            {
+                z -= iunit;
+            }
+            Plaintext tmpplain;
+            encoder_.encode(tmpvec, 1.0, tmpplain);
+            evaluator_.mod_switch_to_inplace(tmpplain, tmpct1.parms_id());
+            evaluator_.multiply_plain(tmpct1, tmpplain, tmpct2);
+            evaluator_.complex_conjugate(tmpct2, gal_keys_, tmpct3);
+            evaluator_.complex_conjugate(tmpct1, gal_keys_, tmpct4);
+            evaluator_.add_reduced_error(tmpct1, tmpct4, rtncipher1);
+            evaluator_.add_reduced_error(tmpct2, tmpct3, rtncipher2);
+        }
+        // sparse only, :2721-2726
         void coefftoslot_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
         {
+            require_kind(true, "coefftoslot_3");
             seal::Ciphertext tmpct1, tmpct2;
-            sflinv_3(tmpct1, cipher);
+            sflinv(tmpct1, cipher);
             evaluator_.complex_conjugate(tmpct1, gal_keys_, tmpct2);
             evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
         }
 
-        // :2728-2733
-        void slottocoeff_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
+        // full only, :2760-2777; `half`: slottocoeff_full_half_3 :2778-2795
+        void slottocoeff_full_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher1, const seal::Ciphertext &cipher2, bool half,
+                                double initial_scale)
         {
+            using namespace seal;
+            require_kind(false, "slottocoeff_full_3");
+            Ciphertext tmpct1, tmpct3;
+            std::complex<double> iunit(0.0, 1.0);
+            std::vector<std::complex<double>> tmpvec(static_cast<std::size_t>(Nh_), 0);
+            for (auto &z : tmpvec)
+            {
+                z += iunit;
+            }
+            Plaintext tmpplain;
+            encoder_.encode(tmpvec, 1.0, tmpplain);
+            evaluator_.mod_switch_to_inplace(tmpplain, cipher2.parms_id());
+            evaluator_.multiply_plain(cipher2, tmpplain, tmpct1);
+            evaluator_.add_reduced_error(cipher1, tmpct1, tmpct3);
+            sfl(rtncipher, tmpct3, half, initial_scale);
+        }
+        // sparse only, :2728-2733; `half`: slottocoeff_half_3 :2735-2740
+        void slottocoeff_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher, bool half, double initial_scale)
+        {
+            require_kind(true, "slottocoeff_3");
             seal::Ciphertext tmpct1, tmpct2;
-            sfl_3(tmpct1, cipher);
+            sfl(tmpct1, cipher, half, initial_scale);
             evaluator_.rotate_vector(tmpct1, n_, gal_keys_, tmpct2);
             evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
         }
 
-        // :2735-2740
-        void slottocoeff_half_3(seal::Ciphertext &rtncipher, const seal::Ciphertext &cipher)
-        {
-            seal::Ciphertext tmpct1, tmpct2;
-            sfl_half_3(tmpct1, cipher);
-            evaluator_.rotate_vector(tmpct1, n_, gal_keys_, tmpct2);
-            evaluator_.add_reduced_error(tmpct1, tmpct2, rtncipher);
-        }
-
-        // bootstrap_3 (:3496-3502) -> bootstrap_sparse_3 (:3143-3229) for logn > 0; `cipher` is consumed like the reference's
+        // bootstrap_3 (:3496-3502); `cipher` is consumed like the reference's
         void bootstrap_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
         {
-            using namespace seal;
-            initial_scale_ = cipher.scale();
-            modraise_inplace(cipher);
-            const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
-            cipher.scale() = static_cast<double>(modulus[0].value());
-            subsum_inplace(cipher);
-            Ciphertext rtn;
-            coefftoslot_3(rtn, cipher);
-            Ciphertext modrtn;
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn, rtn);
-            slottocoeff_3(rtncipher, modrtn);
-            rtncipher.scale() = final_scale_;
+            run(rtncipher, cipher, false);
         }
 
-        // bootstrap_real_3 (:3510-3516) -> bootstrap_sparse_real_3 (:3253-3326) for logn > 0
+        // bootstrap_real_3 (:3510-3516): the result encodes the real part of the message
         void bootstrap_real_3(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
         {
-            using namespace seal;
-            bootstrap_half(rtncipher, cipher);
-            Ciphertext conjct;
+            run(rtncipher, cipher, true);
+            seal::Ciphertext conjct;
             evaluator_.complex_conjugate(rtncipher, gal_keys_, conjct);
             evaluator_.add_inplace_reduced_error(rtncipher, conjct);
         }
 
-        // two real ciphertexts through one sparse bootstrap: see PackedBootstrapper3::bootstrap_real_pair_3
+        // Two real ciphertexts through ONE bootstrap: a + i b (moai_fused::pair_real), everything of bootstrap_real_3 up to its
+        // final conjugate-and-add -- which leaves (a + i b) / 2 at final_scale -- and the conjugation shared by both outputs
+        // (moai_fused::split_real).  a and b are consumed.  Each output depends on its partner: the modular reduction's
+        // error grows with |a + i b|, and an input that is not real leaks its imaginary part into the other output.
         void bootstrap_real_pair_3(seal::Ciphertext &out_a, seal::Ciphertext &out_b, seal::Ciphertext &a, seal::Ciphertext &b)
         {
             using namespace seal;
@@ -1133,30 +902,52 @@ namespace moai_fused
             moai_fused::pair_real(context_, a, b, c);
             a.release();
             b.release();
-            bootstrap_half(r, c);
+            run(r, c, true);
             moai_fused::split_real(context_, r, gal_keys_, out_a, out_b);
         }
 
-        double &initial_scale()
-        {
-            return initial_scale_;
-        }
-
     private:
-        // bootstrap_sparse_real_3 up to and including `scale = final_scale` (:3253-3322): encodes half the message
-        void bootstrap_half(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher)
+        // what differs between the transforms of the two kinds
+        struct Kind
+        {
+            int inv_coeff_logn[3], fwd_coeff_logn; // per inverse transform; of all three forward ones
+            bool fwd3_rotated;                     // the third forward set: rotated or centred,
+            int fwd3_count, fwd3_length;           // its diagonals and their length
+        };
+        void require_kind(bool sparse, const char *what) const
+        {
+            if (sparse_ != sparse)
+            {
+                throw std::logic_error(std::string(what) + (sparse ? " is a sparse-slot stage (logn < logNh)" : " is a full-slot stage (logn == logNh)"));
+            }
+        }
+        // the whole pipeline up to and including `scale = final_scale`; with `half` the result encodes half the message
+        // (the real variants up to their conjugate-and-add: :3328-3346, :3253-3322)
+        void run(seal::Ciphertext &rtncipher, seal::Ciphertext &cipher, bool half)
         {
             using namespace seal;
-            initial_scale_ = cipher.scale();
+            const double initial_scale = cipher.scale();
             modraise_inplace(cipher);
             const auto &modulus = context_.first_context_data()->parms().coeff_modulus();
             cipher.scale() = static_cast<double>(modulus[0].value());
-            subsum_inplace(cipher);
-            Ciphertext rtn;
-            coefftoslot_3(rtn, cipher);
-            Ciphertext modrtn;
-            mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn, rtn);
-            slottocoeff_half_3(rtncipher, modrtn);
+            if (sparse_)
+            {
+                subsum_inplace(cipher);
+                Ciphertext rtn;
+                coefftoslot_3(rtn, cipher);
+                Ciphertext modrtn;
+                mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn, rtn);
+                slottocoeff_3(rtncipher, modrtn, half, initial_scale);
+            }
+            else
+            {
+                Ciphertext rtn1, rtn2;
+                coefftoslot_full_3(rtn1, rtn2, cipher);
+                Ciphertext modrtn1, modrtn2;
+                mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn1, rtn1);
+                mod_reducer_.modular_reduction(evaluator_, relin_keys_, modrtn2, rtn2);
+                slottocoeff_full_3(rtncipher, modrtn1, modrtn2, half, initial_scale);
+            }
             rtncipher.scale() = final_scale_;
         }
 
@@ -1166,11 +957,14 @@ namespace moai_fused
         const seal::RelinKeys &relin_keys_;
         const seal::GaloisKeys &gal_keys_;
         int logn_, logNh_, Nh_, n_;
-        double final_scale_, initial_scale_ = 1;
-        std::vector<std::vector<std::complex<double>>> fftcoeff3_; // rescaled per running scale in sfl_3
+        bool sparse_;
+        double final_scale_;
+        moai_boot::DiagonalSet fftcoeff3_; // rescaled per running scale in sfl; the other sets live in their transforms
         ModularReducer3 mod_reducer_;
+        moai_boot::LevelThreeSplit fwd_split_;
+        Kind kind_;
         std::unique_ptr<BsgsLinearTransform> inv_[3], fwd_[2];
-        int fwd_totlen3_ = 0, fwd_basicstep3_ = 1;
-        std::map<std::tuple<double, double, double, bool>, std::unique_ptr<BsgsLinearTransform>> fwd3_; // last: the halved set
+        // the scaled third forward transform by (level's prime, running scale, initial scale, halved)
+        std::map<std::tuple<double, double, double, bool>, std::unique_ptr<BsgsLinearTransform>> fwd3_;
     };
 } // namespace moai_fused

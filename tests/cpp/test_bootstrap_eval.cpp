@@ -371,9 +371,27 @@ int main(int argc, char **argv)
             CHECK(throws([&] { boot.modraise_inplace(top); })); // not at the lowest level
             Ciphertext out;
             CHECK(throws([&] { boot.bootstrap_3(out, top); }));
-            CHECK(throws([&] {
-                moai_fused::PackedBootstrapper3 sparse(context, encoder, evaluator, relin_keys, gal_keys, logn - 1, logn, final_scale, dg, reducer);
-            })); // the sparse-slot driver (bootstrap_sparse_3) is not provided
+            auto construct = [&](int ln, int lNh) {
+                moai_fused::PackedBootstrapper3 other(context, encoder, evaluator, relin_keys, gal_keys, ln, lNh, final_scale, dg, reducer);
+            };
+            CHECK(throws([&] { construct(logn - 1, logn); })); // a sparse slot count, but dg's third forward set has the full-slot shape
+            CHECK(throws([&] { construct(logn + 1, logn); })); // more slots than the ring has
+            CHECK(throws([&] { construct(2, logn); }));        // the level-3 split of logn < 3 leaves a part of 0 bits
+            // stages of the sparse kind on the full-slot engine
+            auto logic = [&](auto &&f) {
+                try
+                {
+                    f();
+                }
+                catch (const std::logic_error &e)
+                {
+                    return dynamic_cast<const std::invalid_argument *>(&e) == nullptr;
+                }
+                return false;
+            };
+            CHECK(logic([&] { boot.subsum_inplace(top); }));
+            CHECK(logic([&] { boot.coefftoslot_3(out, top); }));
+            CHECK(logic([&] { boot.slottocoeff_3(out, top, false, scale); }));
             CHECK(throws([&] { ChebyshevHeap bad(vector<double>{ 1.0 }); }));
         }
         // a second pack reuses every cached diagonal set, including the rescaled third one

@@ -30,63 +30,11 @@
 #include <thread>
 
 #include "Bootstrapper.h"
-#include "ref_golden.h"
+#include "boot_fixture.h"
 
-static int g_checks = 0, g_fail = 0;
-#define CHECK(cond)                                                \
-    do                                                             \
-    {                                                              \
-        g_checks++;                                                \
-        if (!(cond))                                               \
-        {                                                          \
-            g_fail++;                                              \
-            printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-        }                                                          \
-    } while (0)
-
-static double now_s()
+struct Keys : Setup
 {
-    return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-struct Setup
-{
-    int logN, remaining_level, total_level;
-    double scale;
-    EncryptionParameters parms{ scheme_type::ckks };
-    unique_ptr<SEALContext> context;
-    unique_ptr<KeyGenerator> keygen;
-    RelinKeys relin_keys;
-    GaloisKeys gal_keys;
-    unique_ptr<Encryptor> encryptor;
-    unique_ptr<Decryptor> decryptor;
-    unique_ptr<CKKSEncoder> encoder;
-    unique_ptr<Evaluator> evaluator;
-    Setup(int logN_, int remaining) : logN(logN_), remaining_level(remaining)
-    {
-        // include/test/test_full_scheme.hpp:345-378
-        const int logp = 46, logq = 51, log_special_prime = 58, boot_level = 14;
-        total_level = remaining_level + boot_level;
-        vector<int> bits{ logq };
-        for (int i = 0; i < remaining_level; i++) bits.push_back(logp);
-        for (int i = 0; i < boot_level; i++) bits.push_back(logq);
-        bits.push_back(log_special_prime);
-        const size_t N = size_t(1) << logN;
-        parms.set_poly_modulus_degree(N);
-        parms.set_coeff_modulus(CoeffModulus::Create(N, bits));
-        parms.set_secret_key_hamming_weight(192);
-        scale = pow(2.0, logp);
-        context.reset(new SEALContext(parms, true, sec_level_type::none));
-        refgolden::FixedRandomness fixed(logN);
-        keygen.reset(new KeyGenerator(*context));
-        PublicKey pk;
-        keygen->create_public_key(pk);
-        keygen->create_relin_keys(relin_keys);
-        encryptor.reset(new Encryptor(*context, pk));
-        decryptor.reset(new Decryptor(*context, keygen->secret_key()));
-        encoder.reset(new CKKSEncoder(*context));
-        evaluator.reset(new Evaluator(*context, *encoder));
-    }
+    using Setup::Setup;
     // n REAL values replicated to N/2 slots, encrypted; moved to the lowest level (test_full_scheme.hpp:642-646) unless `top`
     void fresh(mt19937_64 &rng, size_t n, double magnitude, vector<complex<double>> &msg, Ciphertext &ct, bool top = false,
                double at_scale = 0)
@@ -134,19 +82,6 @@ struct Setup
     }
 };
 
-static bool throws(const std::function<void()> &f, const char *needle = nullptr)
-{
-    try
-    {
-        f();
-    }
-    catch (const std::exception &e)
-    {
-        return !needle || strstr(e.what(), needle) != nullptr;
-    }
-    return false;
-}
-
 // ---- operation census (moai_op_trace): (entry point, level) -> units
 typedef map<pair<string, int>, long> Census;
 static Census census_stop()
@@ -193,7 +128,7 @@ static vector<complex<double>> clear_transform(const vector<complex<double>> &x,
 
 static void run(int logN, int remaining, const vector<long> &logns, long pair_sparse_logn, int n_threads)
 {
-    Setup s(logN, remaining);
+    Keys s(logN, remaining);
     const long logNh = logN - 1;
     const size_t Nh = size_t(1) << logNh;
     const long boundary_K = 25, deg = 59, scale_factor = 2, inverse_deg = 1, loge = 10;
@@ -220,6 +155,7 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
     const size_t top = s.context->first_context_data()->chain_index();
     mt19937_64 rng(logN * 1000 + 7);
     const double bound = 2e-5; // what the complex case meets at both sizes (tests/cpp/test_bootstrap_real.cpp, test_bootstrap_sparse.cpp)
+    const string own = "own.real.logN" + to_string(logN); // recorded digests, tests/golden/bootstrap_ref_digests.txt
     auto check_shape = [&](const Ciphertext &out) {
         CHECK(s.chain_index(out) == top - 14);
         CHECK(out.scale() == s.scale);
@@ -258,6 +194,7 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
                log2(out.scale()), err, dt);
         check_shape(out);
         CHECK(err < bound);
+        check_recorded(s, own + ".logn" + to_string(ln) + ".bootstrap_real_3", out);
         // the named variants give the same bits, and bootstrap_inplace_real_3 too
         Ciphertext again = keep, out2;
         if (ln == logNh)
@@ -299,6 +236,7 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
         // the scale bookkeeping `factor` relies on
         CHECK(fabs(full.scale() / (s2 * s2 / curr_mod) - 1) < 1e-9 && half.scale() == full.scale());
         CHECK(s.chain_index(full) == top - 3 && half.parms_id() == full.parms_id());
+        check_recorded(s, own + ".slottocoeff_full_half_3", half);
         // clear-text transform of the decrypted input c1 + i c2
         const vector<complex<double>> d1 = s.decode(c1), d2 = s.decode(c2);
         vector<complex<double>> x(Nh);
@@ -369,7 +307,7 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
     {
         double ea, eb, single_a, single_b;
     };
-    auto pair_run = [&](long ln, double magnitude, bool with_single) {
+    auto pair_run = [&](long ln, double magnitude, bool with_single, bool recorded = false) {
         boot.change_logn(ln);
         const size_t n = size_t(1) << ln;
         vector<complex<double>> ma, mb;
@@ -388,6 +326,11 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
         boot.bootstrap_real_pair_3(oa, ob, a, b);
         check_shape(oa);
         check_shape(ob);
+        if (recorded)
+        {
+            check_recorded(s, own + ".logn" + to_string(ln) + ".bootstrap_real_pair_3.a", oa);
+            check_recorded(s, own + ".logn" + to_string(ln) + ".bootstrap_real_pair_3.b", ob);
+        }
         r.ea = s.error(oa, ma);
         r.eb = s.error(ob, mb);
         return r;
@@ -396,7 +339,7 @@ static void run(int logN, int remaining, const vector<long> &logns, long pair_sp
         printf("4: bootstrap_real_pair_3\n");
         for (long ln : { logNh, pair_sparse_logn })
         {
-            const PairRun r = pair_run(ln, 0.02, false);
+            const PairRun r = pair_run(ln, 0.02, false, true); // the first pair of each logn is pinned
             printf("  logn %ld, |a|, |b| <= 0.02: max |error| a %.2e, b %.2e (imaginary parts of the outputs included)\n", ln, r.ea, r.eb);
             CHECK(r.ea < bound);
             CHECK(r.eb < bound);

@@ -8,7 +8,9 @@
 //   --full   N = 2^16, MOAI's 36-prime chain, logn = 12
 // Checks per logn: decrypt(bootstrap_3(ct)) decoded with sparse_slots = n is the message (bound next to the assertion); the
 // full-slot decode of the output has period n; chain index top - 14 and scale final_scale as in the full case; concurrent
-// calls gathered into a pack give the bits of single calls; calls with different logn are never packed together.
+// calls gathered into a pack give the bits of single calls; calls with different logn are never packed together; the
+// output of each first call has the recorded bits (tests/golden/bootstrap_ref_digests.txt, "own." entries); regenerated
+// sets are not served from transforms cached for the old ones.
 #include <omp.h>
 
 #include <chrono>
@@ -19,67 +21,11 @@
 #include <thread>
 
 #include "Bootstrapper.h"
-#include "ref_golden.h"
+#include "boot_fixture.h"
 
-static int g_checks = 0, g_fail = 0;
-#define CHECK(cond)                                                \
-    do                                                             \
-    {                                                              \
-        g_checks++;                                                \
-        if (!(cond))                                               \
-        {                                                          \
-            g_fail++;                                              \
-            printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-        }                                                          \
-    } while (0)
-
-static double now_s()
+struct Keys : Setup
 {
-    return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-struct Setup
-{
-    int logN, remaining_level, total_level;
-    double scale;
-    EncryptionParameters parms{ scheme_type::ckks };
-    unique_ptr<SEALContext> context;
-    unique_ptr<KeyGenerator> keygen;
-    RelinKeys relin_keys;
-    GaloisKeys gal_keys;
-    unique_ptr<Encryptor> encryptor;
-    unique_ptr<Decryptor> decryptor;
-    unique_ptr<CKKSEncoder> encoder;
-    unique_ptr<Evaluator> evaluator;
-    Setup(int logN_, int remaining, size_t sparse_slots = 0) : logN(logN_), remaining_level(remaining)
-    {
-        // include/test/test_full_scheme.hpp:345-378
-        const int logp = 46, logq = 51, log_special_prime = 58, boot_level = 14;
-        total_level = remaining_level + boot_level;
-        vector<int> bits{ logq };
-        for (int i = 0; i < remaining_level; i++) bits.push_back(logp);
-        for (int i = 0; i < boot_level; i++) bits.push_back(logq);
-        bits.push_back(log_special_prime);
-        const size_t N = size_t(1) << logN;
-        parms.set_poly_modulus_degree(N);
-        parms.set_coeff_modulus(CoeffModulus::Create(N, bits));
-        parms.set_secret_key_hamming_weight(192);
-        if (sparse_slots)
-        {
-            parms.set_sparse_slots(sparse_slots);
-        }
-        scale = pow(2.0, logp);
-        context.reset(new SEALContext(parms, true, sec_level_type::none));
-        refgolden::FixedRandomness fixed(logN);
-        keygen.reset(new KeyGenerator(*context));
-        PublicKey pk;
-        keygen->create_public_key(pk);
-        keygen->create_relin_keys(relin_keys);
-        encryptor.reset(new Encryptor(*context, pk));
-        decryptor.reset(new Decryptor(*context, keygen->secret_key()));
-        encoder.reset(new CKKSEncoder(*context));
-        evaluator.reset(new Evaluator(*context, *encoder));
-    }
+    using Setup::Setup;
     // n values replicated to N/2 slots, encrypted and moved to the lowest level (test_full_scheme.hpp:642-646)
     void fresh(mt19937_64 &rng, size_t n, double magnitude, vector<complex<double>> &msg, Ciphertext &ct)
     {
@@ -95,26 +41,13 @@ struct Setup
     }
 };
 
-static bool throws(const std::function<void()> &f, const char *needle = nullptr)
-{
-    try
-    {
-        f();
-    }
-    catch (const std::exception &e)
-    {
-        return !needle || strstr(e.what(), needle) != nullptr;
-    }
-    return false;
-}
-
 static void run_decode()
 {
     const size_t n = 64;
-    Setup s(11, 2, n);
+    Keys s(11, 2, n);
     CKKSEncoder &sparse_enc = *s.encoder; // built from parms with sparse_slots = n (ckks.cpp:29-30)
     CHECK(sparse_enc.sparse_slot_count() == n && sparse_enc.slot_count() == 1024);
-    Setup f(11, 2);
+    Keys f(11, 2);
     CHECK(f.encoder->sparse_slot_count() == 1024);
     mt19937_64 rng(5);
     vector<complex<double>> msg;
@@ -153,7 +86,7 @@ static void run_decode()
 
 static void run_boot(int logN, int remaining, const vector<long> &logns, int n_threads, double bound)
 {
-    Setup s(logN, remaining);
+    Keys s(logN, remaining);
     const long logNh = logN - 1;
     const long boundary_K = 25, deg = 59, scale_factor = 2, inverse_deg = 1, loge = 10;
     Bootstrapper boot(loge, logns[0], logNh, s.total_level, s.scale, boundary_K, deg, scale_factor, inverse_deg, *s.context, *s.keygen,
@@ -224,6 +157,7 @@ static void run_boot(int logN, int remaining, const vector<long> &logns, int n_t
         }
         CHECK(out2.download() == out.download());
         single[ln] = { keep, out };
+        check_recorded(s, "own.sparse.logN" + to_string(logN) + ".logn" + to_string(ln) + ".bootstrap_3", out);
     }
     // concurrent calls at one logn are gathered into packs, bit-identical to single calls
     {
@@ -292,6 +226,31 @@ static void run_boot(int logN, int remaining, const vector<long> &logns, int n_t
     if (single.count(logNh) && logns.size() > 1)
     {
         together(logNh, logns[0]); // the full call first: its pack runs after change_logn made the member logn sparse
+    }
+    // Regenerating the sets drops the transforms bsgs_linear_transform caches by the ADDRESS of a set: with another
+    // boundary_K the first inverse set holds other values at the same address, and the transform must follow them.
+    if (single.count(logNh))
+    {
+        boot.change_logn(logNh);
+        const auto v = moai_boot::inverse_split((int)logNh);
+        vector<complex<double>> slots(s.encoder->slot_count());
+        for (size_t i = 0; i < slots.size(); i++) slots[i] = { 0.01 * (double)(i % 7), -0.02 };
+        Plaintext p;
+        s.encoder->encode(slots, s.scale, p);
+        Ciphertext x, with_k, with_2k, with_k_again;
+        s.encryptor->encrypt(p, x);
+        auto apply = [&](Ciphertext &out) {
+            boot.rotated_bsgs_linear_transform(out, x, v.totlen[0], v.basicstep[0], (int)logNh, boot.invfftcoeff1[boot.slot_index]);
+        };
+        apply(with_k);
+        boot.boundary_K *= 2;
+        boot.generate_LT_coefficient_3();
+        apply(with_2k);
+        boot.boundary_K /= 2;
+        boot.generate_LT_coefficient_3();
+        apply(with_k_again);
+        CHECK(with_2k.download() != with_k.download());
+        CHECK(with_k_again.download() == with_k.download());
     }
     // refusals before anything is enqueued
     {
