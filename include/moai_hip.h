@@ -511,6 +511,7 @@ int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size
  * Results never depend on a knob.  Name, default, meaning:
  *   MOAI_NTT_FP            1     0: primes below 2^51 stay on the integer units in every transform, key switch and mod-down
  *   MOAI_NTT_LAZY8         1     0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient
+ *   MOAI_NTT_LAZY16        1     0: those primes keep values below 8q with a guard in every stage instead of below 16q with fewer (M_LAZY8)
  *   MOAI_NTT_LDSTW         1     0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS
  *   MOAI_NTT_CHUNK_MB      0     > 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB
  *   MOAI_NTT_NAIVE         0     1: one launch per radix-2 stage over global memory (cross-check path)

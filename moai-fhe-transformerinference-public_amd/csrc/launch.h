@@ -12,6 +12,7 @@ namespace moai {
 #define MOAI_KNOBS(X)                                                                                                          \
     X(NTT_FP, 1, "0: primes below 2^51 stay on the integer units in every transform, key switch and mod-down")                \
     X(NTT_LAZY8, 1, "0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient")       \
+    X(NTT_LAZY16, 1, "0: those primes keep values below 8q with a guard in every stage instead of below 16q with fewer (M_LAZY8)") \
     X(NTT_LDSTW, 1, "0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS")      \
     X(NTT_CHUNK_MB, 0, "> 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB")          \
     X(NTT_NAIVE, 0, "1: one launch per radix-2 stage over global memory (cross-check path)")                                   \

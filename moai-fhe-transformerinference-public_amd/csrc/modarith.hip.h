@@ -168,6 +168,7 @@ __device__ __forceinline__ void ct_bfly_noguard(uint64_t &x, uint64_t &y, uint64
 // patterns of (double q, double RN(1/q)).
 enum
 {
+    M_LAZY16 = -3, // integer, q < 2^60: M_LAZY8's product, values below 16q, a guard where the bound needs one (lazy16_fwd / lazy16_inv)
     M_LAZY8 = -2,  // integer, q < 2^60: approximate Shoup quotient, values below 8q, see ct_bfly_lazy8; plain forward NTT
     M_GUARD2 = -1, // integer, any q < 2^61: the guard of every SECOND stage only (values below 8q), plain forward NTT
     M_GUARD = 0,   // integer, reference discipline [0,4q)
@@ -343,6 +344,142 @@ __device__ __forceinline__ void gs_bfly_last_lazy8(uint64_t &x, uint64_t &y, con
     x = mul_shoup_approx(u + v, ninv.w, ninv.wq, nq);
     y = mul_shoup_approx(u - (v + n4q), ninv_w1.w, ninv_w1.wq, nq);
 }
+// ---- M_LAZY16: M_LAZY8 with a guard only where the bound needs one (q < 2^60) ------------------------------------------
+// M_LAZY8 keeps values below 8q (4q in the inverse) only so that csub_sign can test bit 63.  The approximate product accepts any
+// 64-bit operand and 16q < 2^64, so with a guard that tests the CARRY of x + (2^64 - m) values may grow to 16q, and a stage whose
+// input bound allows it runs without a guard.  Which stages those are is decided at compile time by the two bound trackers below;
+// the kernels static_assert what the trackers prove (no value of 16q or more, the bound one pass hands to the other, the bound
+// the existing final subtractions expect).  Bounds are multiples of q, exclusive.  Same residues as every other mode.
+__device__ __forceinline__ uint64_t csub_carry(uint64_t x, uint64_t neg_m)
+{
+    // x - m if x >= m else x, for any x and 0 < m < 2^64, given 2^64 - m: the sum wraps exactly when x >= m
+    const uint64_t d = x + neg_m;
+    return d < x ? d : x;
+}
+// Forward: u + v and u + 4q - v are below bound(u) + 4q.  Stages [first, first + count) of a 2^logn transform from bound b0: a
+// stage goes unguarded iff its input bound + 4q <= 16q, else x takes one conditional subtraction of 8q (below 16q -> below 8q);
+// the transform's last stage brings x below 4q (8q, then 4q), so that its outputs are below 8q.  Bit s of g8 / g4: stage s
+// subtracts 8q / 4q conditionally.
+struct Lazy16Fwd
+{
+    uint32_t g8, g4;
+    int end;  // bound of the outputs of the last stage run
+    int peak; // largest bound met
+};
+constexpr Lazy16Fwd lazy16_fwd(int logn, int first, int count, int b0)
+{
+    Lazy16Fwd r{ 0, 0, b0, b0 };
+    int b = b0;
+    for (int s = first; s < first + count; ++s)
+    {
+        int u = b;
+        if (s == logn - 1)
+        {
+            if (u > 8)
+            {
+                r.g8 |= 1u << s;
+                u = u - 8 > 8 ? u - 8 : 8;
+            }
+            if (u > 4)
+            {
+                r.g4 |= 1u << s;
+                u = u - 4 > 4 ? u - 4 : 4;
+            }
+        }
+        else if (b + 4 > 16)
+        {
+            r.g8 |= 1u << s;
+            u = b - 8 > 8 ? b - 8 : 8;
+        }
+        b = u + 4;
+        r.peak = b > r.peak ? b : r.peak;
+    }
+    r.end = b;
+    return r;
+}
+// what the strided pass (stages 0 .. logn-9, from inputs below 8q like M_LAZY8's) hands to the contiguous pass
+constexpr int lazy16_fwd_handover(int logn)
+{
+    return (logn & 1) ? 12 : 16;
+}
+// G: bit 0 = x takes a conditional subtraction of 8q, bit 1 = (then) of 4q; nq = 2^64 - q, n4q = 2^64 - 4q
+template <int G>
+__device__ __forceinline__ void ct_bfly_lazy16(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t nq, uint64_t n4q)
+{
+    uint64_t u = x;
+    if (G & 1)
+    {
+        u = csub_carry(u, n4q << 1);
+    }
+    if (G & 2)
+    {
+        u = csub_carry(u, n4q);
+    }
+    const uint64_t v = mul_shoup_approx(y, w, wq, nq);
+    x = u + v;
+    y = u - (v + n4q);
+}
+// Inverse: the sum u + v doubles the bound, the difference goes through the product and comes out below 4q.  Two sums of 16q
+// would not fit 64 bits, so a sum is brought back below 8q at once; what the range buys is that a butterfly whose two inputs are
+// both PRODUCTS (below 4q: sum below 8q) needs no guard.  Inside one radix-16 register block that is known per register: after a
+// stage of distance h the registers with bit h set hold products, and the next stage (distance 2h) pairs registers that agree in
+// bit h.  One block of `count` stages from inputs below bin q: bit i of xk = the butterflies of stage i that are not known to
+// take two products (all of stage 0) have inputs up to 8q -- guard the sum with 8q, form the difference as u - v + 8q; otherwise
+// inputs below 4q, no guard, u - v + 4q.  The transform's last stage (`last`) multiplies both outputs and guards nothing.
+struct Lazy16Inv
+{
+    uint32_t xk;
+    int out;  // bound of the block's outputs
+    int peak; // largest bound met, sums before their guard included
+};
+constexpr Lazy16Inv lazy16_inv(int count, int bin, bool last)
+{
+    Lazy16Inv r{ 0, bin, bin };
+    int bx = bin;
+    for (int i = 0; i < count; ++i)
+    {
+        const bool fin = last && i == count - 1;
+        const int sum = 2 * bx;
+        if (bx > 4)
+        {
+            r.xk |= 1u << i;
+            r.peak = bx > 8 ? 99 : r.peak; // u - v + 8q needs v below 8q
+        }
+        r.peak = sum > r.peak ? sum : r.peak;
+        const int xout = fin ? 4 : (sum > 8 ? (sum - 8 > 8 ? sum - 8 : 8) : sum);
+        const int pout = (i > 0 && !fin) ? 8 : 4; // sums of two products; the products themselves
+        bx = xout > pout ? xout : pout;
+    }
+    r.out = bx;
+    return r;
+}
+// what the contiguous pass (two blocks of four stages, inputs below 4q like M_LAZY8's) hands to the strided pass
+constexpr int lazy16_inv_handover()
+{
+    return 8;
+}
+// K: 1 = inputs below 8q, sum guarded; 0 = inputs below 4q
+template <int K>
+__device__ __forceinline__ void gs_bfly_lazy16(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t nq, uint64_t n4q)
+{
+    const uint64_t u = x, v = y;
+    x = K ? csub_carry(u + v, n4q << 1) : u + v;
+    y = mul_shoup_approx(u - (v + (K ? n4q << 1 : n4q)), w, wq, nq);
+}
+template <int K>
+__device__ __forceinline__ void gs_bfly_last_lazy16(uint64_t &x, uint64_t &y, const Tw &ninv, const Tw &ninv_w1, uint64_t nq, uint64_t n4q)
+{
+    const uint64_t u = x, v = y;
+    x = mul_shoup_approx(u + v, ninv.w, ninv.wq, nq);
+    y = mul_shoup_approx(u - (v + (K ? n4q << 1 : n4q)), ninv_w1.w, ninv_w1.wq, nq);
+}
+// the kind of the butterfly on registers (j, j + half) in stage i of a block with schedule xk; a constant once the caller's loops
+// are unrolled
+__device__ __forceinline__ int lazy16_inv_kind(uint32_t xk, int i, int j, int half)
+{
+    return (i > 0 && (j & (half >> 1))) ? 0 : (int)((xk >> i) & 1u);
+}
+
 template <bool LZ>
 __device__ __forceinline__ void gs_bfly_sel(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t a, uint64_t b);
 

@@ -59,6 +59,11 @@ static bool lazy8_ok(const moai_ctx *c, uint32_t prime)
 {
     return tuning(K_NTT_LAZY8) && c->primes[prime] < (1ull << 60);
 }
+// the same rows keep values below 16q and guard only where the bound needs it (M_LAZY16) unless MOAI_NTT_LAZY16=0
+static bool lazy16_ok(const moai_ctx *c, uint32_t prime)
+{
+    return lazy8_ok(c, prime) && tuning(K_NTT_LAZY16);
+}
 
 template <int LOGN, int MODE>
 static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
@@ -73,16 +78,31 @@ static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
     // rows.  An in-place transform reads as much as it writes and has no cached operand; five resident workgroups of one tile
     // each keep more of that traffic in flight than four pipelined ones.)
     hipLaunchKernelGGL((ntt_fwd_strided<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
-    hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+    if constexpr (MODE == M_LAZY16)
+    {
+        // where the first four stages' twiddles come from is compiled into this mode's contiguous pass
+        if (a.lds_twiddles)
+        {
+            hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE, 1>), dim3(a.total_work), dim3(256), 0, s, a);
+        }
+        else
+        {
+            hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE, 0>), dim3(a.total_work), dim3(256), 0, s, a);
+        }
+    }
+    else
+    {
+        hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+    }
 }
 
 // forward transform: the rows are split by the arithmetic their prime allows and every class gets its own pair of launches.
-// The plain transform has no M_GUARD kernels: ntt_mode's integer primes with guards take M_LAZY8 below 2^60, else the guard
-// of every second stage (M_GUARD2).
+// The plain transform has no M_GUARD kernels: ntt_mode's integer primes with guards take M_LAZY16 (or M_LAZY8) below 2^60, else
+// the guard of every second stage (M_GUARD2).
 template <int LOGN>
 static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    for (int mode : { M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR })
+    for (int mode : { M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR })
     {
         NttArgs a = base;
         a.Lsel = 0;
@@ -92,7 +112,7 @@ static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
             int m = ntt_mode(c, prime);
             if (m == M_GUARD)
             {
-                m = lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD2;
+                m = lazy16_ok(c, prime) ? M_LAZY16 : (lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD2);
             }
             if (m == mode)
             {
@@ -104,7 +124,7 @@ static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
         {
             continue;
         }
-        MOAI_TRY((dispatch<M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR>("forward transform mode ", mode, [&](auto MD) {
+        MOAI_TRY((dispatch<M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR>("forward transform mode ", mode, [&](auto MD) {
             launch_fwd_mode<LOGN, decltype(MD)::value>(c, a, s);
             return MOAI_OK;
         })));
@@ -114,7 +134,7 @@ static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 
 // inverse transform: rows of primes below 2^51 run in exact FP64 arithmetic like the forward transform (FPN / FPR, modarith.hip.h
 // gs_bfly_fp; MOAI_NTT_FP=0 keeps them on the integer units), rows of primes below 2^60 take the integer butterflies with the
-// approximate Shoup quotient (M_LAZY8), the others the exact ones; one pair of launches per class, same residues
+// approximate Shoup quotient (M_LAZY16, or M_LAZY8), the others the exact ones; one pair of launches per class, same residues
 template <int LOGN, int IM>
 static void launch_inv_class(NttArgs a, hipStream_t s)
 {
@@ -131,7 +151,7 @@ static void launch_inv_class(NttArgs a, hipStream_t s)
 template <int LOGN>
 static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    NttArgs cls[4] = { base, base, base, base }; // exact, lazy8, FPN, FPR
+    NttArgs cls[5] = { base, base, base, base, base }; // exact, lazy8, FPN, FPR, lazy16
     for (NttArgs &a : cls)
     {
         a.Lsel = 0;
@@ -143,7 +163,7 @@ static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
     {
         const uint32_t prime = base.rows.idx[r];
         const int m = ntt_mode(c, prime);
-        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (lazy8_ok(c, prime) ? cls[1] : cls[0]));
+        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (lazy16_ok(c, prime) ? cls[4] : (lazy8_ok(c, prime) ? cls[1] : cls[0])));
         dst.selp.idx[dst.Lsel] = prime;
         dst.sel.idx[dst.Lsel++] = r;
     }
@@ -151,6 +171,7 @@ static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
     launch_inv_class<LOGN, 1>(cls[1], s);
     launch_inv_class<LOGN, 2>(cls[2], s);
     launch_inv_class<LOGN, 3>(cls[3], s);
+    launch_inv_class<LOGN, IM_LAZY16>(cls[4], s);
 }
 
 // single-launch transform (ntt_coop); its queue state lives in a per-stream arena

@@ -17,6 +17,7 @@
 //
 // Lazy ranges: forward keeps values in [0,4q) between stages, inverse in [0,2q), like the
 // reference; the pass that finishes a transform writes canonical residues.
+// (M_LAZY8: below 8q / 4q; M_LAZY16: below 16q with the guards its bound trackers ask for, modarith.hip.h.)
 #pragma once
 #include "modarith.hip.h"
 
@@ -91,16 +92,24 @@ struct NttArgs
     uint32_t lds_twiddles; // forward contiguous pass: the first four stages' twiddles through LDS (MOAI_NTT_LDSTW=0: global loads)
 };
 
+// the modes whose butterflies take (2^64 - q, 2^64 - 4q)
+constexpr bool mode_lazy(int mode)
+{
+    return mode == M_LAZY8 || mode == M_LAZY16;
+}
+// inverse passes: IM = 0 exact integer, 1 M_LAZY8, 2 / 3 FP64 (FPN / FPR), IM_LAZY16 = M_LAZY16
+constexpr int IM_LAZY16 = -1;
+
 // (q, q2) arguments of a tile function under MODE: the integer pair, or the bit patterns of (double q, 1/q)
 template <int MODE>
 __device__ __forceinline__ uint64_t mode_q(const PrimeConst &pc)
 {
-    return MODE >= M_FPN ? pc.qd : (MODE == M_LAZY8 ? pc.nq : pc.q);
+    return MODE >= M_FPN ? pc.qd : (mode_lazy(MODE) ? pc.nq : pc.q);
 }
 template <int MODE>
 __device__ __forceinline__ uint64_t mode_q2(const PrimeConst &pc)
 {
-    return MODE >= M_FPN ? pc.qinv : (MODE == M_LAZY8 ? pc.n4q : pc.q2);
+    return MODE >= M_FPN ? pc.qinv : (mode_lazy(MODE) ? pc.n4q : pc.q2);
 }
 
 // =====================================================================================================
@@ -158,10 +167,38 @@ struct LoadBarrettFp
 
 
 // the unrolled stage loops of the tiles carry the stage number in a loop variable; M_GUARD2 needs it as a constant
-template <int MODE>
+// (M_LAZY16 also needs LOGN: its schedule counts stages from the head of the transform)
+template <int MODE, int LOGN = 0>
 __device__ __forceinline__ void ct_bfly_stage(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t q, uint64_t q2, int stages_left)
 {
-    if (MODE == M_GUARD2)
+    if constexpr (MODE == M_LAZY16) // (if constexpr: the other modes pass no LOGN, and LOGN = 0 has no schedule to evaluate)
+    {
+        constexpr int R1 = LOGN - 8;
+        constexpr Lazy16Fwd p1 = lazy16_fwd(LOGN, 0, R1, 8), p2 = lazy16_fwd(LOGN, R1, 8, lazy16_fwd_handover(LOGN));
+        static_assert(p1.peak <= 16 && p2.peak <= 16, "a value of 16q or more");
+        static_assert(p1.end == lazy16_fwd_handover(LOGN), "the contiguous pass starts from another bound");
+        static_assert(p2.end <= 8, "the final subtractions expect values below 8q");
+        constexpr uint32_t g8 = p1.g8 | p2.g8, g4 = p1.g4 | p2.g4;
+        const int s = LOGN - 1 - stages_left;
+        const int g = (int)((g8 >> s) & 1u) | ((int)((g4 >> s) & 1u) << 1);
+        if (g == 0)
+        {
+            ct_bfly_lazy16<0>(x, y, w, wq, q, q2);
+        }
+        else if (g == 1)
+        {
+            ct_bfly_lazy16<1>(x, y, w, wq, q, q2);
+        }
+        else if (g == 2)
+        {
+            ct_bfly_lazy16<2>(x, y, w, wq, q, q2);
+        }
+        else
+        {
+            ct_bfly_lazy16<3>(x, y, w, wq, q, q2);
+        }
+    }
+    else if (MODE == M_GUARD2)
     {
         if (stages_left & 1)
         {
@@ -234,7 +271,7 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
             if (!(j & half) MOAI_DIAG_STAGE_OK(u))
             {
                 const uint32_t ti = (1u << u) + (uint32_t)(j >> (4 - u));
-                ct_bfly_stage<MODE>(x[j], x[j + half], twa[ti].w, twa[ti].wq, q, q2, LOGN - 1 - u);
+                ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], twa[ti].w, twa[ti].wq, q, q2, LOGN - 1 - u);
             }
         }
     }
@@ -290,7 +327,7 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
                     {
                         uint32_t t_ = (th << 4) | (uint32_t)j;
                         Tw t = LDSTW ? ldstw[(1u << s) + (t_ >> (R1 - s))] : tw[(1u << s) + (t_ >> (R1 - s))];
-                        ct_bfly_stage<MODE>(x[j], x[j + half], t.w, t.wq, q, q2, LOGN - 1 - s);
+                        ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], t.w, t.wq, q, q2, LOGN - 1 - s);
                     }
                 }
             }
@@ -394,11 +431,11 @@ __device__ __forceinline__ void fwd_strided_tiles(const uint64_t *inp, uint64_t 
 // five waves per SIMD (96 VGPRs) where the body fits; the modes whose body does not (12, 8 and 14 spilled registers
 // under that cap) run faster at four: M_GUARD2 12.17 -> 11.90 ms per batch transform, FP64 / unguarded rows 2-3 %
 template <int LOGN, int MODE = M_GUARD>
-__global__ __launch_bounds__(256, (MODE == M_GUARD2 || MODE == M_LAZY8 || MODE == M_FPR || MODE == M_NOGUARD) ? 4 : 5) void ntt_fwd_strided(NttArgs a)
+__global__ __launch_bounds__(256, (MODE == M_GUARD2 || mode_lazy(MODE) || MODE == M_FPR || MODE == M_NOGUARD) ? 4 : 5) void ntt_fwd_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
     // the modes that run four workgroups per CU anyway take phase B's twiddles through LDS at N = 2^16 (4 KiB more)
-    constexpr bool LDSTW = LOGN == 16 && (MODE == M_GUARD2 || MODE == M_LAZY8 || MODE == M_FPR || MODE == M_NOGUARD);
+    constexpr bool LDSTW = LOGN == 16 && (MODE == M_GUARD2 || mode_lazy(MODE) || MODE == M_FPR || MODE == M_NOGUARD);
     __shared__ uint64_t lds[4096 + (LDSTW ? 512 : 0)];
     const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
     const uint32_t tile = w % TPR;
@@ -449,7 +486,10 @@ struct StoreTile
 // block's sixteen threads.  Every wave fetches the sixty of its own four blocks with ONE load per lane and reads them back from LDS
 // (broadcast reads, no s_barrier: the blocks of a wave are its own), instead of fifteen 16-byte global loads per thread issued one
 // or two ahead of the butterflies that use them.
-template <int LOGN, int MODE = M_GUARD, class StoreOp = StoreTile>
+// TWL: -1 = `ldstw` decides at run time (the reads are then generic loads: every wait for one drains LDS and memory alike);
+// 0 = memory; 1 = LDS, known at compile time: the reads are ds_read_b128, and the copy's load is issued with the tile's own
+// sixteen and waited for only where it is written to LDS, instead of costing one round trip in front of every tile.
+template <int LOGN, int MODE = M_GUARD, class StoreOp = StoreTile, int TWL = -1>
 __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
                                                 const Tw *__restrict__ twb, uint64_t cr1, StoreOp store, Tw *ldstw = nullptr)
@@ -462,10 +502,22 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
     const uint32_t blk = (tile << 4) + b;
     const Tw *__restrict__ twbt = twb + (size_t)tile * (15 * 256);
 
-    if (ldstw)
+    const bool use_lds = TWL < 0 ? ldstw != nullptr : TWL == 1;
+    Tw fill;
+    uint32_t fill_slot = 0;
+    if (use_lds)
     {
         const uint32_t lane = tid & 63u;
-        if (lane < 60u)
+        if (TWL == 1)
+        {
+            // lanes 60..63 repeat lane 59's load, so that it is issued without a branch, and store nothing
+            const uint32_t l = lane < 59u ? lane : 59u;
+            const uint32_t bb = ((tid >> 6) << 2) + l / 15u, i = l % 15u;
+            const uint32_t u = i == 0 ? 0u : (i < 3 ? 1u : (i < 7 ? 2u : 3u)), k = i - ((1u << u) - 1u);
+            fill = tw[(1u << (R1 + u)) + (((tile << 4) + bb) << u) + k];
+            fill_slot = bb * 15u + i;
+        }
+        else if (lane < 60u)
         {
             const uint32_t bb = ((tid >> 6) << 2) + lane / 15u, i = lane % 15u;       // block of this wave, slot 2^u - 1 + k
             const uint32_t u = i == 0 ? 0u : (i < 3 ? 1u : (i < 7 ? 2u : 3u)), k = i - ((1u << u) - 1u);
@@ -478,8 +530,12 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
     {
         x[j] = base[(b << 8) | ((uint32_t)j << 4) | tl];
     }
-    if (ldstw)
+    if (use_lds)
     {
+        if (TWL == 1 && (tid & 63u) < 60u)
+        {
+            ldstw[fill_slot] = fill;
+        }
         lds_wave_sync();
     }
 #pragma unroll
@@ -491,9 +547,9 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
         {
             if (!(j & half))
             {
-                Tw t = ldstw ? ldstw[b * 15u + ((1u << u) - 1u) + (uint32_t)(j >> (4 - u))]
-                             : tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(j >> (4 - u))];
-                ct_bfly_stage<MODE>(x[j], x[j + half], t.w, t.wq, q, q2, 7 - u);
+                Tw t = use_lds ? ldstw[b * 15u + ((1u << u) - 1u) + (uint32_t)(j >> (4 - u))]
+                               : tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(j >> (4 - u))];
+                ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], t.w, t.wq, q, q2, 7 - u);
             }
         }
     }
@@ -523,7 +579,7 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
             {
                 // slot = 2^(u-4) - 1 + (j >> (8-u)); consecutive threads read consecutive entries
                 Tw t = twbt[(((1u << (u - 4)) - 1u + (uint32_t)(j >> (8 - u))) << 8) + tid];
-                ct_bfly_stage<MODE>(x[j], x[j + half], t.w, t.wq, q, q2, 7 - u);
+                ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], t.w, t.wq, q, q2, 7 - u);
             }
         }
     }
@@ -542,7 +598,7 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
             v.x = barrett64(x[2 * c], q, cr1);
             v.y = barrett64(x[2 * c + 1], q, cr1);
         }
-        else if (MODE == M_LAZY8)
+        else if (mode_lazy(MODE))
         {
             // values below 8q; (q, q2) = (2^64 - q, 2^64 - 4q), and 2^64 - 2q = (2^64 - 4q) / 2 + 2^63
             const uint64_t n2q = (q2 >> 1) | 0x8000000000000000ull;
@@ -594,7 +650,8 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
     fwd_contig_tile<LOGN, MODE, StoreTile>(rowp, tile, tw, q, q2, lds2, tid, twb, cr1, st, ldstw);
 }
 
-template <int LOGN, int MODE = M_GUARD>
+// TWL (fwd_contig_tile): -1 = NttArgs::lds_twiddles decides at run time, 0 / 1 = compiled in (M_LAZY16)
+template <int LOGN, int MODE = M_GUARD, int TWL = -1>
 __global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -606,9 +663,12 @@ __global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
     const uint32_t r = __builtin_amdgcn_readfirstlane(a.sel.idx[rest / TPR]);
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[rest / TPR]);
     const PrimeConst &pc = a.pc[prime];
-    fwd_contig_tile<LOGN, MODE>(a.data + (((size_t)pol * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN),
-                                mode_q<MODE>(pc), mode_q2<MODE>(pc), lds2, threadIdx.x,
-                                a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), pc.cr1, a.lds_twiddles ? reinterpret_cast<Tw *>(lds2 + 2048) : nullptr);
+    uint64_t *rowp = a.data + (((size_t)pol * a.L + r) << LOGN);
+    StoreTile st;
+    st.out = reinterpret_cast<ulonglong2 *>(rowp + ((size_t)tile << 12));
+    fwd_contig_tile<LOGN, MODE, StoreTile, TWL>(rowp, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc), lds2, threadIdx.x,
+                                                a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), pc.cr1, st,
+                                                (TWL < 0 ? a.lds_twiddles != 0 : TWL == 1) ? reinterpret_cast<Tw *>(lds2 + 2048) : nullptr);
 }
 
 // =====================================================================================================
@@ -617,6 +677,28 @@ __global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
 // LZ: the M_LAZY8 butterflies (modarith.hip.h), with (q, q2) = (2^64 - q, 2^64 - 4q); values below 4q instead of 2q
 // IM: 0 exact integer butterflies, 1 M_LAZY8, 2 / 3 exact FP64 (FPN / FPR, modarith.hip.h gs_bfly_fp: canonical integers in,
 // doubles out to the strided pass; tw / twb = the FP64 inverse tables, (q, q2) = the bit patterns of (double q, 1/q))
+// one butterfly of an inverse tile on registers (j, j + half): stage i of a register block whose M_LAZY16 schedule is xk
+template <int IM>
+__device__ __forceinline__ void gs_bfly_tile(uint64_t (&x)[16], int j, int half, uint64_t w, uint64_t wq, uint64_t q, uint64_t q2, const bool redsum,
+                                             uint32_t xk, int i)
+{
+    if (IM == IM_LAZY16)
+    {
+        if (lazy16_inv_kind(xk, i, j, half))
+        {
+            gs_bfly_lazy16<1>(x[j], x[j + half], w, wq, q, q2);
+        }
+        else
+        {
+            gs_bfly_lazy16<0>(x[j], x[j + half], w, wq, q, q2);
+        }
+    }
+    else
+    {
+        gs_bfly_im<IM>(x[j], x[j + half], w, wq, q, q2, redsum);
+    }
+}
+
 template <int LOGN, int IM = 0>
 __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
@@ -629,6 +711,10 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
     const uint32_t tl = tid & 15u;
     const uint32_t blk = (tile << 4) + b;
     const Tw *__restrict__ twbt = twb + (size_t)tile * (15 * 256);
+    // M_LAZY16: two register blocks of four stages from inputs below 4q
+    constexpr Lazy16Inv z1 = lazy16_inv(4, 4, false), z2 = lazy16_inv(4, z1.out, false);
+    static_assert(z1.peak <= 16 && z2.peak <= 16, "a value of 16q or more");
+    static_assert(z2.out == lazy16_inv_handover(), "the strided pass starts from another bound");
 
     // the per-thread twiddles of the first four stages do not depend on the data: fetch them while the tile is
     // staged through LDS instead of one by one behind the barrier (-3.7 % on the inverse transform; the same
@@ -685,7 +771,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
             if (!(j & half))
             {
                 Tw t = tb[(1 << (u - 4)) - 1 + (j >> (8 - u))];
-                gs_bfly_im<IM>(x[j], x[j + half], t.w, t.wq, q, q2, (u & 3) == 0); // FPN: sums folded in every fourth stage
+                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z1.xk, 7 - u); // FPN: sums folded in every fourth stage
             }
         }
     }
@@ -715,7 +801,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
             {
                 Tw t = ldstw ? ldstw[b * 15u + ((1u << u) - 1u) + (uint32_t)(j >> (4 - u))]
                              : tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(j >> (4 - u))];
-                gs_bfly_im<IM>(x[j], x[j + half], t.w, t.wq, q, q2, (u & 3) == 0); // FPN: sums folded in every fourth stage
+                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z2.xk, 3 - u); // FPN: sums folded in every fourth stage
             }
         }
     }
@@ -739,8 +825,9 @@ __global__ __launch_bounds__(256) void ntt_inv_contig(NttArgs a)
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[rest / TPR]);
     const PrimeConst &pc = a.pc[prime];
     const uint64_t *srcp = a.src ? a.src + (((size_t)pol * a.src_stride + a.src_off + r) << LOGN) : nullptr;
+    constexpr bool LZ = IM == 1 || IM == IM_LAZY16;
     inv_contig_tile<LOGN, IM>(a.data + (((size_t)pol * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN),
-                              IM >= 2 ? pc.qd : (IM == 1 ? pc.nq : pc.q), IM >= 2 ? pc.qinv : (IM == 1 ? pc.n4q : pc.q2), lds2, threadIdx.x,
+                              IM >= 2 ? pc.qd : (LZ ? pc.nq : pc.q), IM >= 2 ? pc.qinv : (LZ ? pc.n4q : pc.q2), lds2, threadIdx.x,
                               a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), srcp);
 }
 
@@ -751,7 +838,7 @@ template <int LOGN, int IM = 0>
 __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                  const PrimeConst *pc, uint64_t *lds, const uint32_t tid)
 {
-    constexpr bool LZ = (IM == 1);
+    constexpr bool LZ = (IM == 1 || IM == IM_LAZY16);
     constexpr int R1 = LOGN - 8;
     constexpr int RB = R1 - 4;
     constexpr int GB = 12 - R1;
@@ -759,10 +846,14 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
     const uint64_t q = IM >= 2 ? pc->qd : (LZ ? pc->nq : pc->q);
     const uint64_t q2 = IM >= 2 ? pc->qinv : (LZ ? pc->n4q : pc->q2);
     uint64_t *__restrict__ row = rowp + tile * G;
+    // M_LAZY16: phase B's RB stages from what the contiguous pass hands over, then phase A's four, the transform's last among them
+    constexpr Lazy16Inv zb = lazy16_inv(RB, lazy16_inv_handover(), false), za = lazy16_inv(4, zb.out, true);
+    static_assert(zb.peak <= 16 && za.peak <= 16, "a value of 16q or more");
+    static_assert(za.out <= 4, "the final subtractions expect values below 4q");
 
     // LDSTW (M_LAZY8 at N = 2^16: four workgroups per CU either way): phase B's twiddles -- entries 16..255 of the table, shared by
     // the sixteen threads of a group -- through a copy in LDS (`lds` + 4096 words), as in the forward strided pass
-    constexpr bool LDSTW = LOGN == 16 && IM == 1;
+    constexpr bool LDSTW = LOGN == 16 && LZ;
     Tw *ldstw = reinterpret_cast<Tw *>(lds + 4096);
     uint64_t x[16];
     if (RB > 0)
@@ -794,7 +885,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
                 {
                     uint32_t t_ = (th << 4) | (uint32_t)j;
                     Tw t = LDSTW ? ldstw[(1u << s) + (t_ >> (R1 - s))] : tw[(1u << s) + (t_ >> (R1 - s))];
-                    gs_bfly_im<IM>(x[j], x[j + half], t.w, t.wq, q, q2, ((R1 - 1 - s) & 3) == 3); // stage number in this pass
+                    gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, ((R1 - 1 - s) & 3) == 3, zb.xk, R1 - 1 - s); // stage number in this pass
                 }
             }
         }
@@ -829,7 +920,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
             if (!(j & half))
             {
                 Tw t = tw[(1u << u) + (uint32_t)(j >> (4 - u))];
-                gs_bfly_im<IM>(x[j], x[j + half], t.w, t.wq, q, q2, ((RB + 3 - u) & 3) == 3);
+                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, ((RB + 3 - u) & 3) == 3, za.xk, 3 - u);
             }
         }
     }
@@ -839,7 +930,18 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
 #pragma unroll
         for (int j = 0; j < 8; ++j)
         {
-            if (IM >= 2)
+            if (IM == IM_LAZY16)
+            {
+                if (lazy16_inv_kind(za.xk, 3, j, 8))
+                {
+                    gs_bfly_last_lazy16<1>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
+                }
+                else
+                {
+                    gs_bfly_last_lazy16<0>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
+                }
+            }
+            else if (IM >= 2)
             {
                 gs_bfly_last_fp<IM == 3>(x[j], x[j + 8], fp_from_u64(ninv.w), fp_from_u64(ninv_w1.w), u2d(q), u2d(q2));
             }
@@ -864,10 +966,10 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
 }
 
 template <int LOGN, int IM = 0>
-__global__ __launch_bounds__(256, IM == 1 ? 4 : 5) void ntt_inv_strided(NttArgs a)
+__global__ __launch_bounds__(256, (IM == 1 || IM == IM_LAZY16) ? 4 : 5) void ntt_inv_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
-    __shared__ uint64_t lds[4096 + ((LOGN == 16 && IM == 1) ? 512 : 0)]; // the exchange buffer (+ phase B's twiddles, inv_strided_tile)
+    __shared__ uint64_t lds[4096 + ((LOGN == 16 && (IM == 1 || IM == IM_LAZY16)) ? 512 : 0)]; // the exchange buffer (+ phase B's twiddles, inv_strided_tile)
     const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
     const uint32_t tile = w % TPR;
     const uint32_t srow = w / TPR; // over n_poly * Lsel selected rows
