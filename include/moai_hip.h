@@ -565,6 +565,42 @@ size_t moai_key_words(const moai_ctx *ctx, size_t levels);
 int moai_key_trim(moai_ctx *ctx, const uint64_t *full_key, size_t levels, uint64_t *trimmed, void *stream);
 int moai_key_forget(moai_ctx *ctx, const uint64_t *key);
 
+/* ---- keys limited to a chain index ----------------------------------------------------------------------------------
+ * The key that is BORN in moai_key_trim's layout: a client that knows a key is only used at l <= levels data primes
+ * generates, ships and loads exactly the digits J < levels and the rows {0 .. levels-1, k-1} that switch_key_inplace reads
+ * there (SEAL/evaluator.cpp:2818, 2831), never the full key of KeyGenerator::generate_one_kswitch_key
+ * (SEAL/keygenerator.cpp:303-336).  1 <= levels <= k-1; the layout is [levels][2][levels+1][N] with the special prime's row
+ * last, moai_key_words(ctx, levels) words.
+ * Contract: every word equals the corresponding word of moai_key_trim(moai_kswitch_keygen(same key, same seq, ...), levels)
+ * (the seeded forms: of moai_kswitch_keygen_seeded + moai_expand_seeded + trim).  Digit J draws its noise from (noise key,
+ * 3 << 56 | seq + J) and its uniform half from (key or seed, 1 << 56 | seq + J), and coefficient i of the row under prime
+ * index p takes the stream words 2(pN + i), 2(pN + i) + 1: the position of the FULL k-row draw, not of the compact one (the
+ * entry points with a prime_index keep their compact positions).  The call occupies the sequence range [seq, seq + levels);
+ * with levels == k-1 the output is word for word the full key.  sk_ntt and new_key_ntt stay full [k][N] keys.
+ * moai_kswitch_keygen_limited: out [levels][2][levels+1][N]; records the layout of `out` in the context as moai_key_trim does,
+ * so every key-switch entry point accepts it for l <= levels (MOAI_ERANGE above); moai_key_forget before the block is freed
+ * or reused.
+ * moai_kswitch_keygen_limited_seeded: out_c0 [levels][levels+1][N], a from the public seed, e from noise_key; nothing is
+ * recorded.
+ * moai_expand_seeded_limited: c0 [levels][levels+1][N] -> out [levels][2][levels+1][N], a usable limited key; records the
+ * layout of `out`.  c0 and out must not overlap.
+ * moai_key_register: records the trimmed layout for a block [levels][2][levels+1][N] that arrived unseeded from elsewhere.
+ * MOAI_EINVAL for a null pointer, for levels outside 1 .. k-1, and for an address already recorded with another layout.
+ * Validation as above (null context / key / seed / argument, levels out of range, a sequence range beyond 2^56; MOAI_ELOGIC for
+ * k < 2) before anything is enqueued; no call synchronises; large keys are generated in chunks as moai_kswitch_keygen's are. */
+/* KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336, cut to what SEAL/evaluator.cpp:2818,2831 read */
+int moai_kswitch_keygen_limited(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
+                                size_t levels, uint64_t *out, void *stream);
+/* the same with save_seed, SEAL/keygenerator.cpp:303-336, SEAL/keygenerator.h:321-360; rows of SEAL/evaluator.cpp:2818,2831 */
+int moai_kswitch_keygen_limited_seeded(moai_ctx *ctx, const uint8_t *noise_key, const uint8_t *seed, uint64_t seq,
+                                       const uint64_t *sk_ntt, const uint64_t *new_key_ntt, size_t levels, uint64_t *out_c0,
+                                       void *stream);
+/* Ciphertext::expand_seed, SEAL/ciphertext.cpp:118-188, over the rows of SEAL/evaluator.cpp:2818,2831 */
+int moai_expand_seeded_limited(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const uint64_t *c0, size_t levels, uint64_t *out,
+                               void *stream);
+/* the layout record of moai_key_trim for a block filled elsewhere (SEAL/evaluator.cpp:2818,2831) */
+int moai_key_register(moai_ctx *ctx, const uint64_t *key, size_t levels);
+
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is

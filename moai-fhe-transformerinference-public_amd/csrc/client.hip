@@ -13,6 +13,9 @@
 //                     row J of a key digit); c1 is never stored before this kernel, and in the seeded form (a from a public seed,
 //                     SEAL/util/rlwe.cpp:353-363) not stored at all
 //   cl_expand       : c1 of a seeded object drawn again from its seed beside a copy of c0 (Ciphertext::expand_seed)
+//   FULLPOS (both)  : the rows are a selection {0 .. levels-1, k-1} of a key digit's k rows that keeps the FULL draw's stream
+//                     positions (row r under prime p takes the words of row p), and sk / newkey stay full [k][N] keys read at
+//                     row p: a level-limited key is word for word the trim of the full one (moai_kswitch_keygen_limited)
 //   cl_pk_finish    : c_i = pk_i u + e_i over the rows of the previous level, u read once; then the existing rescale divides by
 //                     the dropped prime (divide_and_round_q_last_ntt_inplace) and cl_add_c0 adds the plaintext to c0
 #include <mutex>
@@ -193,9 +196,9 @@ struct SymArgs
     ChaKey key;             // the stream a is drawn from: the caller's one key, or the public seed of a seeded object
     uint64_t nonce_a;       // ciphertext b (of this launch) draws a with nonce_a + b
     const uint64_t *e;      // [nb][L][N] NTT form
-    const uint64_t *sk;     // [L][N]
+    const uint64_t *sk;     // [L][N]; FULLPOS: [k][N], row r read at its prime's index
     const uint64_t *plain;  // [nb][L][N] or null
-    const uint64_t *newkey; // [L][N] or null: key digit b adds fac[b] * newkey[b] in row b of c0
+    const uint64_t *newkey; // [L][N] ([k][N] with FULLPOS) or null: key digit b adds fac[b] * newkey[b] in row b of c0
     uint64_t *out;          // [nb][2][L][N]; seeded form: c0 only, [nb][L][N]
     uint32_t digit0;        // digit of ciphertext 0 of this launch
     const PrimeConst *pc;
@@ -205,7 +208,7 @@ struct SymArgs
     uint32_t logn;
 };
 
-template <bool SEEDED>
+template <bool SEEDED, bool FULLPOS>
 __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
 {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
@@ -217,10 +220,13 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
     const uint32_t f = t << 2;
     const uint32_t r = f >> g.logn;
     const size_t LN = (size_t)g.L << g.logn;
-    const PrimeConst &pc = g.pc[g.rows.idx[r]];
+    const uint32_t p = g.rows.idx[r];
+    const PrimeConst &pc = g.pc[p];
     const uint64_t q = pc.q;
+    // coefficient offset of this thread in the full [k][N] layout (sk, newkey and the stream position), else the compact one
+    const uint32_t ff = FULLPOS ? (p << g.logn) + (f & ((1u << g.logn) - 1)) : f;
     uint32_t blk[16];
-    chacha_block(g.key, g.nonce_a + b, t, blk);
+    chacha_block(g.key, g.nonce_a + b, ff >> 2, blk);
     uint64_t a[4];
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -228,7 +234,7 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
         a[j] = mod128(word64(blk, 2 * j), word64(blk, 2 * j + 1), pc);
     }
     const ulonglong2 *e2 = reinterpret_cast<const ulonglong2 *>(g.e + b * LN + f);
-    const ulonglong2 *s2 = reinterpret_cast<const ulonglong2 *>(g.sk + f);
+    const ulonglong2 *s2 = reinterpret_cast<const ulonglong2 *>(g.sk + ff);
     uint64_t c0[4];
     {
         ulonglong2 e01 = e2[0], e23 = e2[1], s01 = s2[0], s23 = s2[1];
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
     }
     if (g.newkey && r == g.digit0 + b)
     {
-        const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(g.newkey + f);
+        const ulonglong2 *k2 = reinterpret_cast<const ulonglong2 *>(g.newkey + ff);
         ulonglong2 k01 = k2[0], k23 = k2[1];
         const uint64_t kv[4] = { k01.x, k01.y, k23.x, k23.y };
         const uint64_t fac = g.fac[r];
@@ -288,9 +294,10 @@ struct ExpandArgs
     uint32_t logn;
 };
 
+template <bool FULLPOS>
 __global__ __launch_bounds__(256) void cl_expand(ExpandArgs g)
 {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // block index of the stream, as in cl_uniform
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x; // block index of the stream, as in cl_uniform (FULLPOS: see cl_sym_finish)
     if (t >= (g.L << g.logn) >> 2)
     {
         return;
@@ -298,11 +305,13 @@ __global__ __launch_bounds__(256) void cl_expand(ExpandArgs g)
     const uint32_t b = blockIdx.y;
     const uint32_t f = t << 2;
     const size_t LN = (size_t)g.L << g.logn;
-    const PrimeConst &pc = g.pc[g.rows.idx[f >> g.logn]];
+    const uint32_t p = g.rows.idx[f >> g.logn];
+    const PrimeConst &pc = g.pc[p];
+    const uint32_t tpos = FULLPOS ? ((p << g.logn) + (f & ((1u << g.logn) - 1))) >> 2 : t;
     const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(g.c0 + b * LN + f);
     const ulonglong2 c01 = src[0], c23 = src[1];
     uint32_t blk[16];
-    chacha_block(g.seed, g.nonce + b, t, blk);
+    chacha_block(g.seed, g.nonce + b, tpos, blk);
     ulonglong2 *o0 = reinterpret_cast<ulonglong2 *>(g.out + 2 * b * LN + f);
     ulonglong2 *o1 = reinterpret_cast<ulonglong2 *>(g.out + (2 * b + 1) * LN + f);
     o0[0] = c01;
@@ -441,9 +450,10 @@ static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, siz
 }
 
 // symmetric encryptions (newkey == null) or the digits of a switching key: ciphertext b uses sequence seq + b.  seed == null:
-// a and e from `key`, out [n_batch][2][L][N]; otherwise e from `key`, a from `seed`, and out holds c0 only, [n_batch][L][N]
+// a and e from `key`, out [n_batch][2][L][N]; otherwise e from `key`, a from `seed`, and out holds c0 only, [n_batch][L][N].
+// fullpos: sk and newkey are full [k][N] keys and a keeps the stream positions of the full k-row draw (cl_sym_finish FULLPOS)
 static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk, const uint64_t *plain,
-                    const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, hipStream_t s)
+                    const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, bool fullpos, hipStream_t s)
 {
     MOAI_TRY(enter_device(c));
     const ChaKey k = load_key(key);
@@ -474,7 +484,9 @@ static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64
         a.plain = plain ? plain + b0 * LN : nullptr;
         a.out = out + b0 * (seed ? 1 : 2) * LN;
         a.digit0 = (uint32_t)b0;
-        hipLaunchKernelGGL(seed ? cl_sym_finish<true> : cl_sym_finish<false>, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+        auto *kernel = fullpos ? (seed ? cl_sym_finish<true, true> : cl_sym_finish<false, true>)
+                               : (seed ? cl_sym_finish<true, false> : cl_sym_finish<false, false>);
+        hipLaunchKernelGGL(kernel, grid_of(LN / 4, nb), dim3(256), 0, s, a);
         MOAI_LAUNCH_CHECK();
         return MOAI_OK;
     });
@@ -557,7 +569,7 @@ static int encrypt_symmetric_entry(moai_ctx *c, const uint8_t *key, const uint8_
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    return sym_impl(c, key, seed, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, false, (hipStream_t)stream);
 }
 
 extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
@@ -596,7 +608,7 @@ static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *
     }
     RowMap rows;
     MOAI_TRY(make_rowmap(c, c->k, nullptr, &rows));
-    return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, false, (hipStream_t)stream);
 }
 
 extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
@@ -656,8 +668,112 @@ extern "C" int moai_expand_seeded(moai_ctx *c, const uint8_t *seed, uint64_t seq
     a.pc = c->pc;
     a.L = (uint32_t)L;
     a.logn = (uint32_t)c->logn;
-    hipLaunchKernelGGL(cl_expand, grid_of(LN / 4, count), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(cl_expand<false>, grid_of(LN / 4, count), dim3(256), 0, (hipStream_t)stream, a);
     MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+// ---- keys limited to a chain index (born in moai_key_trim's layout) -------------------------------------------------------------
+// the rows of a key limited to `levels` data primes, {0 .. levels-1, k-1}, after the checks every limited entry point shares
+static int limited_rows(const moai_ctx *c, size_t levels, RowMap *rows)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (c->k < 2)
+    {
+        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
+    }
+    if (levels < 1 || levels > c->k - 1)
+    {
+        return set_error(MOAI_EINVAL, "levels must lie in 1 .. %zu", c->k - 1);
+    }
+    uint32_t idx[MOAI_MAX_RNS];
+    for (size_t r = 0; r < levels; r++)
+    {
+        idx[r] = (uint32_t)r;
+    }
+    idx[levels] = (uint32_t)(c->k - 1);
+    return make_rowmap(c, levels + 1, idx, rows);
+}
+
+static int kswitch_keygen_limited_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
+                                        const uint64_t *new_key_ntt, size_t levels, uint64_t *out, bool record, void *stream)
+{
+    RowMap rows;
+    MOAI_TRY(limited_rows(c, levels, &rows));
+    MOAI_TRY(check_common(c, key, seq, levels));
+    if (!sk_ntt || !new_key_ntt || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    if (record)
+    {
+        MOAI_TRY(moai_key_register(c, out, levels));
+    }
+    const int rc = sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, levels, levels + 1, rows, true, (hipStream_t)stream);
+    if (rc && record)
+    {
+        moai_key_forget(c, out);
+    }
+    return rc;
+}
+
+extern "C" int moai_kswitch_keygen_limited(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt,
+                                           const uint64_t *new_key_ntt, size_t levels, uint64_t *out, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out);
+    trace_op("kswitch_keygen_limited", levels + 1, levels);
+    return kswitch_keygen_limited_entry(c, key, nullptr, seq, sk_ntt, new_key_ntt, levels, out, true, stream);
+}
+
+extern "C" int moai_kswitch_keygen_limited_seeded(moai_ctx *c, const uint8_t *noise_key, const uint8_t *seed, uint64_t seq,
+                                                  const uint64_t *sk_ntt, const uint64_t *new_key_ntt, size_t levels, uint64_t *out_c0,
+                                                  void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out_c0);
+    trace_op("kswitch_keygen_limited_seeded", levels + 1, levels);
+    if (c && noise_key && !seed)
+    {
+        return set_error(MOAI_EINVAL, "null seed");
+    }
+    return kswitch_keygen_limited_entry(c, noise_key, seed, seq, sk_ntt, new_key_ntt, levels, out_c0, false, stream);
+}
+
+extern "C" int moai_expand_seeded_limited(moai_ctx *c, const uint8_t *seed, uint64_t seq, const uint64_t *c0, size_t levels, uint64_t *out,
+                                          void *stream)
+{
+    MOAI_AUDIT(stream, c0, out);
+    trace_op("expand_seeded_limited", levels + 1, levels);
+    ExpandArgs a;
+    MOAI_TRY(limited_rows(c, levels, &a.rows));
+    MOAI_TRY(check_common(c, seed, seq, levels));
+    if (!c0 || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t L = levels + 1, LN = L * c->n;
+    if (overlap(c0, levels * LN * 8, out, 2 * levels * LN * 8))
+    {
+        return set_error(MOAI_EINVAL, "c0 and out overlap");
+    }
+    MOAI_TRY(enter_device(c));
+    MOAI_TRY(moai_key_register(c, out, levels));
+    a.seed = load_key(seed);
+    a.nonce = (CL_UNIFORM << 56) | seq;
+    a.c0 = c0;
+    a.out = out;
+    a.pc = c->pc;
+    a.L = (uint32_t)L;
+    a.logn = (uint32_t)c->logn;
+    hipLaunchKernelGGL(cl_expand<true>, grid_of(LN / 4, levels), dim3(256), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+    {
+        moai_key_forget(c, out);
+        return set_error(MOAI_EHIP, "cl_expand launch failed: %s", hipGetErrorString(e));
+    }
     return MOAI_OK;
 }
 

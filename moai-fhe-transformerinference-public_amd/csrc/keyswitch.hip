@@ -1411,6 +1411,27 @@ extern "C" int moai_key_trim(moai_ctx *c, const uint64_t *full_key, size_t level
     return MOAI_OK;
 }
 
+extern "C" int moai_key_register(moai_ctx *c, const uint64_t *key, size_t levels)
+{
+    if (!c || !key)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t k = c->k;
+    if (k < 2 || levels < 1 || levels > k - 1)
+    {
+        return set_error(MOAI_EINVAL, "levels must lie in 1 .. %zu", k < 2 ? (size_t)0 : k - 1);
+    }
+    std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
+    auto it = c->key_layouts.find(key);
+    if (it != c->key_layouts.end() && (it->second.digits != levels || it->second.rows != levels + 1))
+    {
+        return set_error(MOAI_EINVAL, "the address is recorded as a key of %u levels; moai_key_forget it first", it->second.digits);
+    }
+    c->key_layouts[key] = moai_ctx::KeyLayout{ (uint32_t)levels, (uint32_t)(levels + 1) };
+    return MOAI_OK;
+}
+
 extern "C" int moai_key_forget(moai_ctx *c, const uint64_t *key)
 {
     if (!c)

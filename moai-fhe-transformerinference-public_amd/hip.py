@@ -106,6 +106,10 @@ SYMBOLS = {
     "moai_key_words": (sz, [vp, sz]),
     "moai_key_trim": (C.c_int, [vp, vp, sz, vp, vp]),
     "moai_key_forget": (C.c_int, [vp, vp]),
+    "moai_kswitch_keygen_limited": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, vp, vp]),
+    "moai_kswitch_keygen_limited_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, sz, vp, vp]),
+    "moai_expand_seeded_limited": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, sz, vp, vp]),
+    "moai_key_register": (C.c_int, [vp, vp, sz]),
     "moai_debug_stream_audit": (C.c_int, [C.c_int]),
     "moai_debug_block_label": (None, [vp, sz, vp, C.c_int]),
     "moai_debug_stream_audit_counts": (None, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
@@ -198,6 +202,20 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class KeyBuffer(DeviceBuffer):
+    """A DeviceBuffer holding a key whose trimmed layout the context has recorded (moai_key_register and the entry points that
+    record): the record is dropped (moai_key_forget) before the block goes back to the allocator."""
+
+    def __init__(self, ctx, n_words):
+        super().__init__(n_words)
+        self._ctx = ctx
+
+    def free(self):
+        if self.ptr and getattr(self._ctx, "h", None):
+            lib().moai_key_forget(self._ctx.h, self.ptr)
+        super().free()
 
 
 def _ptr(x):
@@ -396,6 +414,36 @@ class Context:
 
     def key_forget(self, key):
         _check(lib().moai_key_forget(self.h, _ptr(key)))
+
+    def key_register(self, key, levels):
+        """record the trimmed layout [levels][2][levels+1][N] for a block filled elsewhere (moai_key_register); key_forget before
+        the block is freed or reused"""
+        _check(lib().moai_key_register(self.h, _ptr(key), levels))
+
+    def _key_buffer(self, levels):
+        words = lib().moai_key_words(self.h, levels) if 1 <= levels <= self.k - 1 else 0
+        return KeyBuffer(self, max(words, 2))  # out-of-range levels: the library reports them
+
+    def kswitch_keygen_limited(self, key, seq, sk_ntt, new_key_ntt, levels, stream=None):
+        """The switching key for new_key_ntt [k][N] limited to `levels` data primes: a KeyBuffer [levels][2][levels+1][N] whose
+        layout the context knows, word for word key_trim(kswitch_keygen(key, seq, ...), levels)"""
+        out = self._key_buffer(levels)
+        _check(lib().moai_kswitch_keygen_limited(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(new_key_ntt), levels, out.ptr,
+                                                 stream))
+        return out
+
+    def kswitch_keygen_limited_seeded(self, noise_key, seed, seq, sk_ntt, new_key_ntt, levels, stream=None):
+        """c0 [levels][levels+1][N] of the limited switching key (nothing is recorded)"""
+        out = DeviceBuffer(max(levels * (levels + 1), 1) * self.n)
+        _check(lib().moai_kswitch_keygen_limited_seeded(self.h, self._key(noise_key), self._key(seed), int(seq), _ptr(sk_ntt),
+                                                        _ptr(new_key_ntt), levels, out.ptr, stream))
+        return out
+
+    def expand_seeded_limited(self, seed, seq, c0, levels, stream=None):
+        """c0 [levels][levels+1][N] -> a usable limited key, a KeyBuffer [levels][2][levels+1][N] whose layout the context knows"""
+        out = self._key_buffer(levels)
+        _check(lib().moai_expand_seeded_limited(self.h, self._key(seed), int(seq), _ptr(c0), levels, out.ptr, stream))
+        return out
 
     def hoist_correction(self, key, elt, L, stream=None):
         """the per-(key, level) constant of the hoisted rotations: DeviceBuffer [2][L+1][N]"""

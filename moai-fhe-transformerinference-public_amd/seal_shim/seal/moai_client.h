@@ -704,12 +704,7 @@ namespace seal
         KeyGenerator(const SEALContext &context) : context_(context)
         {
             const auto &kp = context_.key_context_data()->parms();
-            for (auto &m : kp.coeff_modulus())
-            {
-                primes_.push_back(m.value());
-            }
-            n_ = context_.n();
-            k_ = primes_.size();
+            set_parms();
             std::vector<std::int64_t> s;
             util::sample_ternary(n_, kp.secret_key_hamming_weight(), s);
             std::vector<std::uint64_t> rns;
@@ -717,6 +712,16 @@ namespace seal
             sk_.ntt_ = std::make_shared<util::DeviceArray>(k_ * n_, context_.stream());
             upload_ntt(rns, *sk_.ntt_, k_);
             sk_.parms_id_ = context_.key_parms_id();
+        }
+        // a generator for an existing secret key (SEAL/keygenerator.h, the second constructor; SEAL/keygenerator.cpp:31-45)
+        KeyGenerator(const SEALContext &context, const SecretKey &secret_key) : context_(context)
+        {
+            set_parms();
+            if (!secret_key.ntt_ || secret_key.parms_id() != context_.key_parms_id() || secret_key.ntt_->size() != k_ * n_)
+            {
+                throw std::invalid_argument("secret key is not valid for encryption parameters");
+            }
+            sk_ = secret_key;
         }
         const SecretKey &secret_key() const
         {
@@ -819,6 +824,72 @@ namespace seal
         {
             return create_galois_keys(galois_elts_all());
         }
+        // ---- keys limited to a chain index (not part of the reference API; include/moai_hip.h, "keys limited to a chain index") ----
+        // A key that is only used at chain index <= c is generated, shipped and loaded as the digits J < c + 1 and the rows
+        // {0 .. c, special prime} a switch reads there (SEAL/evaluator.cpp:2818, 2831): (c+1)(c+2) / ((k-1) k) of the key.
+        // c >= k-2 gives a full key.  Every key, limited or not, reserves k-1 sequences of the device generator, so a generator
+        // with a fixed secret key and a fixed DeviceRng(key, first_sequence) produces, key for key, the trim of what it would
+        // have produced in full.  chain_indices: one entry per element, or a single entry for all.
+        Serializable<RelinKeys> create_relin_keys_limited(std::size_t chain_index)
+        {
+            require_keyswitching();
+            util::DeviceArray s2(k_ * n_, context_.stream());
+            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
+                                            context_.stream()));
+            wire::Object o = seeded_object(wire::kind_relin_keys);
+            o.indices.push_back(0);
+            o.keys.push_back(seeded_key_record(s2.get(), levels_of(chain_index)));
+            o.head.count = 1;
+            context_.sync();
+            return Serializable<RelinKeys>(std::move(o));
+        }
+        Serializable<GaloisKeys> create_galois_keys_limited(const std::vector<std::uint32_t> &galois_elts,
+                                                            const std::vector<std::size_t> &chain_indices)
+        {
+            require_keyswitching();
+            // slot -> levels, in the order of the slots as create_galois_keys writes them; the first mention of an element counts
+            std::vector<std::pair<std::uint64_t, std::size_t>> slots = limited_slots(galois_elts, chain_indices);
+            std::stable_sort(slots.begin(), slots.end(), [](const std::pair<std::uint64_t, std::size_t> &a,
+                                                            const std::pair<std::uint64_t, std::size_t> &b) { return a.first < b.first; });
+            wire::Object o = seeded_object(wire::kind_galois_keys);
+            util::DeviceArray rotated(k_ * n_, context_.stream());
+            for (auto &sl : slots)
+            {
+                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
+                                                    static_cast<std::uint32_t>(2 * sl.first + 1), context_.stream()));
+                o.indices.push_back(sl.first);
+                o.keys.push_back(seeded_key_record(rotated.get(), sl.second));
+            }
+            o.head.count = static_cast<std::uint32_t>(o.keys.size());
+            context_.sync();
+            return Serializable<GaloisKeys>(std::move(o));
+        }
+        // the same into a destination, drawn on the device like moai_fused::create_*_keys (a and e from the generator's one key)
+        void create_relin_keys_limited_device(std::size_t chain_index, RelinKeys &destination)
+        {
+            require_keyswitching();
+            util::DeviceArray s2(k_ * n_, context_.stream());
+            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
+                                            context_.stream()));
+            reset_set(destination, 1);
+            put_key_device(destination, 0, s2.get(), levels_of(chain_index));
+            context_.sync();
+        }
+        void create_galois_keys_limited_device(const std::vector<std::uint32_t> &galois_elts, const std::vector<std::size_t> &chain_indices,
+                                               GaloisKeys &destination)
+        {
+            require_keyswitching();
+            const std::vector<std::pair<std::uint64_t, std::size_t>> slots = limited_slots(galois_elts, chain_indices);
+            reset_set(destination, n_);
+            util::DeviceArray rotated(k_ * n_, context_.stream());
+            for (auto &sl : slots)
+            {
+                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
+                                                    static_cast<std::uint32_t>(2 * sl.first + 1), context_.stream()));
+                put_key_device(destination, sl.first, rotated.get(), sl.second);
+            }
+            context_.sync();
+        }
         // the randomness of the device paths (a fresh OS-keyed one by default)
         void set_device_rng(std::shared_ptr<util::DeviceRng> rng)
         {
@@ -882,12 +953,98 @@ namespace seal
         }
 
     private:
+        void set_parms()
+        {
+            for (auto &m : context_.key_context_data()->parms().coeff_modulus())
+            {
+                primes_.push_back(m.value());
+            }
+            n_ = context_.n();
+            k_ = primes_.size();
+        }
         void require_keyswitching() const
         {
             if (!context_.using_keyswitching())
             {
                 throw std::logic_error("keyswitching is not supported by the context");
             }
+        }
+        // data primes of a key limited to chain index c: c + 1, and the full k-1 from c = k-2 on
+        std::size_t levels_of(std::size_t chain_index) const
+        {
+            return chain_index >= k_ - 2 ? k_ - 1 : chain_index + 1;
+        }
+        // (slot, levels) per distinct Galois element, in the order given
+        std::vector<std::pair<std::uint64_t, std::size_t>> limited_slots(const std::vector<std::uint32_t> &galois_elts,
+                                                                         const std::vector<std::size_t> &chain_indices) const
+        {
+            if (chain_indices.size() != 1 && chain_indices.size() != galois_elts.size())
+            {
+                throw std::invalid_argument("chain_indices must hold one entry, or one per Galois element");
+            }
+            std::vector<std::pair<std::uint64_t, std::size_t>> slots;
+            for (std::size_t i = 0; i < galois_elts.size(); i++)
+            {
+                const std::uint32_t elt = galois_elts[i];
+                if (!(elt & 1) || elt >= 2 * n_)
+                {
+                    throw std::invalid_argument("Galois element is not valid");
+                }
+                const std::uint64_t slot = GaloisKeys::get_index(elt);
+                bool seen = false;
+                for (auto &s : slots)
+                {
+                    seen = seen || s.first == slot;
+                }
+                if (!seen)
+                {
+                    slots.emplace_back(slot, levels_of(chain_indices[chain_indices.size() == 1 ? 0 : i]));
+                }
+            }
+            return slots;
+        }
+        // c0 of a key's digits: the whole key (record kind 9) at levels == k-1, otherwise the limited one (kind 10)
+        wire::Record seeded_key_record(const std::uint64_t *new_key_ntt, std::size_t levels) const
+        {
+            if (levels == k_ - 1)
+            {
+                return seeded_record(wire::kind_kswitch_key, new_key_ntt);
+            }
+            wire::Record r;
+            r.kind = wire::kind_kswitch_key_limited;
+            r.flags = wire::flag_ntt | wire::flag_seeded;
+            r.count = static_cast<std::uint32_t>(2 * levels);
+            r.L = static_cast<std::uint32_t>(levels + 1);
+            r.parms_id = context_.key_parms_id();
+            r.seq = rng_->take(k_ - 1);
+            util::public_seed(rng_->key(), r.seq, r.seed);
+            r.block = std::make_shared<util::DeviceArray>(levels * (levels + 1) * n_, context_.stream());
+            util::hip_check(moai_kswitch_keygen_limited_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), new_key_ntt,
+                                                               levels, r.block->get(), context_.stream()));
+            r.data = r.block->get();
+            return r;
+        }
+        // an empty set of `slots` slots with caches and residency of its own
+        void reset_set(KSwitchKeys &destination, std::size_t slots) const
+        {
+            destination.keys_.assign(slots, nullptr);
+            destination.hoist_ = std::make_shared<KSwitchKeys::HoistCache>();
+            destination.res_.reset();
+            destination.generation_ = KSwitchKeys::next_generation();
+            destination.parms_id_ = context_.key_parms_id();
+        }
+        void put_key_device(KSwitchKeys &destination, std::size_t slot, const std::uint64_t *new_key_ntt, std::size_t levels) const
+        {
+            if (levels == k_ - 1)
+            {
+                destination.keys_[slot] = make_kswitch_key_device(new_key_ntt);
+                return;
+            }
+            auto key = wire::limited_key_block(context_, levels);
+            util::hip_check(moai_kswitch_keygen_limited(context_.device(), rng_->key(), rng_->take(k_ - 1), sk_.ntt_->get(), new_key_ntt, levels,
+                                                        key->get(), context_.stream()));
+            destination.keys_[slot] = key;
+            destination.mark_born_limited(context_, slot, levels);
         }
         wire::Object seeded_object(std::uint32_t kind) const
         {

@@ -869,6 +869,16 @@ namespace moai_fused
     {
         keygen.create_galois_keys_device(galois_elts, destination);
     }
+    // keys limited to a chain index, drawn on the device in the trimmed layout (KeyGenerator::create_*_keys_limited)
+    inline void create_relin_keys_limited(seal::KeyGenerator &keygen, std::size_t chain_index, seal::RelinKeys &destination)
+    {
+        keygen.create_relin_keys_limited_device(chain_index, destination);
+    }
+    inline void create_galois_keys_limited(seal::KeyGenerator &keygen, const std::vector<std::uint32_t> &galois_elts,
+                                           const std::vector<std::size_t> &chain_indices, seal::GaloisKeys &destination)
+    {
+        keygen.create_galois_keys_limited_device(galois_elts, chain_indices, destination);
+    }
     inline void create_galois_keys(seal::KeyGenerator &keygen, const std::vector<int> &steps, seal::GaloisKeys &destination)
     {
         keygen.create_galois_keys_device(keygen.galois_elts_from_steps(steps), destination);

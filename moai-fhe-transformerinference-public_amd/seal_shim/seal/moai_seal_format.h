@@ -132,6 +132,13 @@ namespace seal
             {
                 return sealfmt::record_bytes(o, o.head);
             }
+            for (auto &r : o.keys)
+            {
+                if (r.kind == wire::kind_kswitch_key_limited)
+                {
+                    throw std::logic_error("a key limited to a chain index has no form in SEAL's format: save it in this library's own");
+                }
+            }
             const std::size_t n = moai_ctx_coeff_count(o.dev), k = o.head.L;
             const std::size_t digit = header_bytes + ct_member_bytes + dyn_bytes(2 * k * n);
             return header_bytes + 32 + 8 + 8 * slots(o) + o.keys.size() * (k - 1) * digit;

@@ -13,7 +13,10 @@
 //   seeded  : the odd polynomials (c1 of a ciphertext, of every key digit) are not stored; polynomial 2 b + 1 is
 //             uniform(seed, 1 << 56 | first sequence + b) (moai_expand_seeded), so stored = count / 2
 //   key set = header (kind 5 / 6 / 7, count = number of keys, total = the whole set) + u64 index[count] + one record of kind 9
-//             (count = 2 (k - 1) polynomials of k rows) per key
+//             (count = 2 (k - 1) polynomials of k rows) per key, or of kind 10 for a key limited to a chain index
+//   kind 10 = a limited switching key (include/moai_hip.h, "keys limited to a chain index"): count = 2 levels polynomials,
+//             L = levels + 1 rows packed under the primes {0 .. levels-1, k-1}, parms_id of the key level; seeded: the odd
+//             polynomials are moai_expand_seeded_limited of the seed (stream positions of the full k-row draw)
 //
 // Everything that touches residues runs on the device: pack + one device-to-host copy on save; one host-to-device copy +
 // unpack (with the residue check of is_data_valid_for folded in) + expand on load.
@@ -26,7 +29,8 @@ namespace seal
     {
         constexpr std::uint32_t version = 1;
         constexpr std::uint32_t kind_ciphertext = 1, kind_plaintext = 2, kind_public_key = 3, kind_secret_key = 4, kind_kswitch_keys = 5,
-                                kind_relin_keys = 6, kind_galois_keys = 7, kind_encryption_parameters = 8, kind_kswitch_key = 9;
+                                kind_relin_keys = 6, kind_galois_keys = 7, kind_encryption_parameters = 8, kind_kswitch_key = 9,
+                                kind_kswitch_key_limited = 10;
         constexpr std::uint32_t flag_seeded = 1, flag_ntt = 2;
 
         struct Header
@@ -208,9 +212,23 @@ namespace seal
         };
 
         // ---- sizes --------------------------------------------------------------------------------------------------------
-        inline std::size_t packed_words(moai_ctx *dev, std::size_t L)
+        // the primes a record's rows sit under: empty (0 .. L-1), or {0 .. L-2, k-1} for a limited switching key
+        inline std::vector<std::uint32_t> record_rows(moai_ctx *dev, std::uint32_t kind, std::size_t L)
         {
-            const std::size_t w = moai_packed_words(dev, L, nullptr);
+            std::vector<std::uint32_t> idx;
+            if (kind == kind_kswitch_key_limited && L >= 2)
+            {
+                for (std::size_t r = 0; r + 1 < L; r++)
+                {
+                    idx.push_back(static_cast<std::uint32_t>(r));
+                }
+                idx.push_back(static_cast<std::uint32_t>(moai_ctx_prime_count(dev) - 1));
+            }
+            return idx;
+        }
+        inline std::size_t packed_words(moai_ctx *dev, std::size_t L, const std::vector<std::uint32_t> &rows = {})
+        {
+            const std::size_t w = moai_packed_words(dev, L, rows.empty() ? nullptr : rows.data());
             if (!w)
             {
                 throw std::logic_error(moai_last_error());
@@ -219,7 +237,7 @@ namespace seal
         }
         inline std::size_t record_bytes(moai_ctx *dev, const Record &r)
         {
-            return sizeof(Header) + (r.stored() ? r.stored() * packed_words(dev, r.L) * 8 : 0);
+            return sizeof(Header) + (r.stored() ? r.stored() * packed_words(dev, r.L, record_rows(dev, r.kind, r.L)) * 8 : 0);
         }
         inline std::size_t object_bytes(const Object &o)
         {
@@ -264,9 +282,10 @@ namespace seal
                 return;
             }
             // the whole record in one moai_pack_rows and one device-to-host copy
-            const std::size_t words = r.stored() * packed_words(o.dev, r.L);
+            const std::vector<std::uint32_t> rows = record_rows(o.dev, r.kind, r.L);
+            const std::size_t words = r.stored() * packed_words(o.dev, r.L, rows);
             util::DeviceArray packed(words, o.stream);
-            util::hip_check(moai_pack_rows(o.dev, r.data, packed.get(), r.stored(), r.L, nullptr, o.stream));
+            util::hip_check(moai_pack_rows(o.dev, r.data, packed.get(), r.stored(), r.L, rows.empty() ? nullptr : rows.data(), o.stream));
             std::uint8_t *dst = sink.space(words * 8);
             util::hip_check(moai_memcpy_d2h(dst, packed.get(), words * 8, o.stream));
             util::hip_check(moai_stream_sync(o.stream));
@@ -308,7 +327,7 @@ namespace seal
             {
                 throw std::logic_error("incompatible version");
             }
-            if (h.kind < 1 || h.kind > 9 || (h.flags & ~(flag_seeded | flag_ntt)) || h.seq >> 56 || h.total < sizeof(Header))
+            if (h.kind < 1 || h.kind > kind_kswitch_key_limited || (h.flags & ~(flag_seeded | flag_ntt)) || h.seq >> 56 || h.total < sizeof(Header))
             {
                 throw std::logic_error("loaded header is invalid");
             }
@@ -334,10 +353,41 @@ namespace seal
                 throw std::logic_error(std::string(what) + " data is invalid"); // SEAL/ciphertext.cpp:302,358
             }
         }
+        // a limited switching key inside a key set: N, the key level's parms_id, 1 <= levels <= k-1 with L = levels + 1 rows and
+        // 2 levels polynomials
+        inline void check_limited(const SEALContext &context, const Header &h, const char *what)
+        {
+            const std::size_t k = context.key_context_data()->parms().coeff_modulus().size();
+            parms_id_type id = { h.parms_id[0], h.parms_id[1], h.parms_id[2], h.parms_id[3] };
+            if (h.n != context.n() || id != context.key_parms_id() || k < 2 || h.L < 2 || h.L > k || h.count != 2 * (std::size_t(h.L) - 1))
+            {
+                throw std::logic_error(std::string(what) + " data is invalid");
+            }
+        }
+        // a block [levels][2][levels+1][N] whose trimmed layout the library keeps by its address (moai_key_register and the entry
+        // points that record): the record is dropped before the block goes back to the pool
+        inline std::shared_ptr<util::DeviceArray> limited_key_block(const SEALContext &context, std::size_t levels)
+        {
+            std::shared_ptr<SEALContext> keep(new SEALContext(context));
+            return std::shared_ptr<util::DeviceArray>(new util::DeviceArray(moai_key_words(context.device(), levels), context.stream()),
+                                                      [keep](util::DeviceArray *p) {
+                                                          moai_key_forget(keep->device(), p->get());
+                                                          delete p;
+                                                      });
+        }
         inline Record get_record(const SEALContext &context, Source &src, std::uint32_t kind, const char *what, bool check, std::size_t max_count)
         {
             const Header h = get_header(src);
-            check_against(context, h, kind, what);
+            // where a whole switching key is expected, one limited to a chain index may stand
+            const bool limited = kind == kind_kswitch_key && h.kind == kind_kswitch_key_limited;
+            if (limited)
+            {
+                check_limited(context, h, what);
+            }
+            else
+            {
+                check_against(context, h, kind, what);
+            }
             Record r;
             r.kind = h.kind;
             r.flags = h.flags;
@@ -354,11 +404,13 @@ namespace seal
             moai_ctx *dev = context.device();
             void *st = context.stream();
             const std::size_t n = context.n(), stored = r.stored(), LN = r.L * n;
-            const std::size_t words = stored * packed_words(dev, r.L);
+            const std::vector<std::uint32_t> rows = record_rows(dev, r.kind, r.L);
+            const std::uint32_t *pidx = rows.empty() ? nullptr : rows.data();
+            const std::size_t words = stored * packed_words(dev, r.L, rows);
             const std::uint8_t *bytes = src.view(words * 8);
             util::DeviceArray packed(words, st), flag(1, st);
             util::hip_check(moai_memcpy_h2d(packed.get(), bytes, words * 8, st));
-            auto out = std::make_shared<util::DeviceArray>(r.count * LN, st);
+            auto out = limited ? limited_key_block(context, r.L - 1) : std::make_shared<util::DeviceArray>(r.count * LN, st);
             std::uint64_t bad = 0;
             if (check)
             {
@@ -368,12 +420,23 @@ namespace seal
             if (r.flags & flag_seeded)
             {
                 util::DeviceArray c0(stored * LN, st);
-                util::hip_check(moai_unpack_rows(dev, packed.get(), c0.get(), stored, r.L, nullptr, dflag, st));
-                util::hip_check(moai_expand_seeded(dev, r.seed, r.seq, c0.get(), out->get(), stored, r.L, nullptr, st));
+                util::hip_check(moai_unpack_rows(dev, packed.get(), c0.get(), stored, r.L, pidx, dflag, st));
+                if (limited)
+                {
+                    util::hip_check(moai_expand_seeded_limited(dev, r.seed, r.seq, c0.get(), r.L - 1, out->get(), st));
+                }
+                else
+                {
+                    util::hip_check(moai_expand_seeded(dev, r.seed, r.seq, c0.get(), out->get(), stored, r.L, nullptr, st));
+                }
             }
             else
             {
-                util::hip_check(moai_unpack_rows(dev, packed.get(), out->get(), stored, r.L, nullptr, dflag, st));
+                util::hip_check(moai_unpack_rows(dev, packed.get(), out->get(), stored, r.L, pidx, dflag, st));
+                if (limited)
+                {
+                    util::hip_check(moai_key_register(dev, out->get(), r.L - 1));
+                }
             }
             if (check)
             {
@@ -427,7 +490,7 @@ namespace seal
             for (std::size_t i = 0; i < o.indices.size(); i++)
             {
                 Record r = get_record(context, src, kind_kswitch_key, what, check, 2 * (k - 1));
-                if (r.count != 2 * (k - 1) || r.parms_id != id)
+                if (r.count != 2 * (r.kind == kind_kswitch_key_limited ? std::size_t(r.L) - 1 : k - 1) || r.parms_id != id)
                 {
                     throw std::logic_error(std::string(what) + " data is invalid");
                 }

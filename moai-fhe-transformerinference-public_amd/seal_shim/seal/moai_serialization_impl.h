@@ -155,12 +155,18 @@ namespace seal
             {
                 continue;
             }
-            // the full key: a key trimmed by limit_to_chain_index is saved from the copy that came back, or from its parked host copy
+            // the full key: a key trimmed by limit_to_chain_index is saved from the copy that came back, or from its parked host copy;
+            // a key born limited is saved as it is (record kind 10)
             std::shared_ptr<util::DeviceArray> full = keys_[i];
+            std::size_t born = 0;
             if (res_)
             {
                 std::lock_guard<std::mutex> g(res_->mu);
-                if (i < res_->levels.size() && res_->levels[i])
+                if (i < res_->born.size() && res_->born[i])
+                {
+                    born = res_->levels[i];
+                }
+                else if (i < res_->levels.size() && res_->levels[i])
                 {
                     if (i < res_->regrown.size() && res_->regrown[i])
                     {
@@ -190,10 +196,10 @@ namespace seal
             }
             const std::size_t k = moai_ctx_prime_count(o.dev);
             wire::Record r;
-            r.kind = wire::kind_kswitch_key;
+            r.kind = born ? wire::kind_kswitch_key_limited : wire::kind_kswitch_key;
             r.flags = wire::flag_ntt;
-            r.count = static_cast<std::uint32_t>(2 * (k - 1));
-            r.L = static_cast<std::uint32_t>(k);
+            r.count = static_cast<std::uint32_t>(2 * (born ? born : k - 1));
+            r.L = static_cast<std::uint32_t>(born ? born + 1 : k);
             r.parms_id = parms_id_;
             r.block = full;
             r.data = full->get();
@@ -211,10 +217,11 @@ namespace seal
         o.head.parms_id = parms_id_;
         return o;
     }
-    inline void KSwitchKeys::set_from_wire(const SEALContext &, wire::Object &&o, std::size_t min_slots)
+    inline void KSwitchKeys::set_from_wire(const SEALContext &context, wire::Object &&o, std::size_t min_slots)
     {
-        // an ordinary key set: whole keys in the reference's layout, constants of hoisted rotations yet to be derived, and a
-        // generation of its own, so that nothing cached with the keys this object held before is mistaken for these
+        // whole keys in the reference's layout and keys born limited (record kind 10: trimmed blocks the library knows),
+        // constants of hoisted rotations yet to be derived, and a generation of its own, so that nothing cached with the keys
+        // this object held before is mistaken for these
         std::vector<std::shared_ptr<util::DeviceArray>> keys(std::max<std::size_t>(min_slots, o.indices.empty() ? 0 : o.indices.back() + 1));
         for (std::size_t i = 0; i < o.indices.size(); i++)
         {
@@ -224,6 +231,13 @@ namespace seal
         parms_id_ = o.head.parms_id;
         hoist_ = std::make_shared<HoistCache>();
         res_.reset();
+        for (std::size_t i = 0; i < o.indices.size(); i++)
+        {
+            if (o.keys[i].kind == wire::kind_kswitch_key_limited)
+            {
+                mark_born_limited(context, o.indices[i], o.keys[i].L - 1);
+            }
+        }
         generation_ = next_generation();
     }
     inline wire::Object KSwitchKeys::to_wire() const

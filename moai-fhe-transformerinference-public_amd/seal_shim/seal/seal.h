@@ -2025,6 +2025,31 @@ namespace seal
             }
             return b;
         }
+        // the data primes the key in slot `index` is limited to: 0 = none (a whole key, or no key), otherwise `levels` -- for a
+        // key born limited (KeyGenerator::create_*_keys_limited, or loaded from record kind 10) and, until it has come back
+        // whole, for one trimmed by limit_to_chain_index
+        std::size_t limited_levels(std::size_t index) const
+        {
+            if (!res_ || index >= keys_.size() || !keys_[index])
+            {
+                return 0;
+            }
+            std::lock_guard<std::mutex> g(res_->mu);
+            if (index < res_->regrown.size() && res_->regrown[index])
+            {
+                return 0;
+            }
+            return index < res_->levels.size() ? res_->levels[index] : 0;
+        }
+        bool born_limited(std::size_t index) const
+        {
+            if (!res_)
+            {
+                return false;
+            }
+            std::lock_guard<std::mutex> g(res_->mu);
+            return index < res_->born.size() && res_->born[index];
+        }
         // how many trimmed keys had to come back whole so far
         std::size_t regrown_count() const
         {
@@ -2055,6 +2080,22 @@ namespace seal
         // the object kind on the wire, and the number of key slots of an empty set (GaloisKeys: N, SEAL/galoiskeys.h:48)
         wire::Object set_to_wire(std::uint32_t kind) const;
         void set_from_wire(const SEALContext &context, wire::Object &&o, std::size_t min_slots);
+        // keys_[index] is a trimmed block of `levels` data primes with no full key behind it
+        void mark_born_limited(const SEALContext &context, std::size_t index, std::size_t levels)
+        {
+            if (!res_)
+            {
+                res_ = std::make_shared<Residency>();
+                res_->context.reset(new SEALContext(context));
+            }
+            std::lock_guard<std::mutex> g(res_->mu);
+            res_->levels.resize(keys_.size(), 0);
+            res_->host.resize(keys_.size());
+            res_->regrown.resize(keys_.size());
+            res_->born.resize(keys_.size(), 0);
+            res_->levels[index] = levels;
+            res_->born[index] = 1;
+        }
         friend class KeyGenerator;
         static std::uint64_t next_generation()
         {
@@ -2077,6 +2118,7 @@ namespace seal
             std::vector<std::size_t> levels;                             // data primes a trimmed key serves (0 = not trimmed)
             std::vector<std::shared_ptr<std::vector<std::uint64_t>>> host; // the full key, parked
             std::vector<std::shared_ptr<util::DeviceArray>> regrown;     // the full key, back on the device
+            std::vector<char> born;                                      // the key was born limited: there is no full key
         };
         std::shared_ptr<Residency> res_;
     };
@@ -2134,6 +2176,7 @@ namespace seal
         res_->levels.resize(keys_.size(), 0);
         res_->host.resize(keys_.size());
         res_->regrown.resize(keys_.size());
+        res_->born.resize(keys_.size(), 0);
         const std::size_t full_words = (k - 1) * 2 * k * n;
         for (std::size_t i = 0; i < keys_.size(); i++)
         {
@@ -2157,12 +2200,7 @@ namespace seal
                 res_->host[i] = h;
             }
             // the library keeps the layout of the trimmed block by its address: forget it before the block goes back to the pool
-            std::shared_ptr<SEALContext> keep(new SEALContext(context));
-            std::shared_ptr<util::DeviceArray> t(new util::DeviceArray(moai_key_words(context.device(), levels), context.stream()),
-                                                 [keep](util::DeviceArray *p) {
-                                                     moai_key_forget(keep->device(), p->get());
-                                                     delete p;
-                                                 });
+            std::shared_ptr<util::DeviceArray> t = wire::limited_key_block(context, levels);
             util::hip_check(moai_key_trim(context.device(), keys_[i]->get(), levels, t->get(), context.stream()));
             context.sync(); // the full block is released behind the copy
             keys_[i] = t;
