@@ -97,6 +97,14 @@ int moai_stream_sync(void *stream);
  * inverse:  bit-reversed in -> natural out, scaled by N^-1, canonical
  *           (inverse_ntt_negacyclic_harvey, SEAL/util/ntt.cpp:453-475;
  *           Evaluator::transform_from_ntt_inplace SEAL/evaluator.cpp:2516-2561)
+ *           Input range: every row accepts [0, 2q), what the reference's lazy inverse accepts (dwthandler.h:226-250).
+ *           Per class of row (moai_arith_mode, MOAI_MODE_OF_NTT_INVERSE), N >= 4096, the kernels accept no more than
+ *             FPN, FPR        any value below 2^52 (the load converts with an exact 52-bit trick, csrc/modarith.hip.h
+ *                             fp_from_u52, which drops bits 52 and up; FPN folds it to |.| <= q/2 at once, FPR in its
+ *                             first butterfly, whose sum of two inputs stays below 2^53) -- at least [0, 2q) as q < 2^51
+ *             LAZY16, LAZY8   [0, 4q)
+ *             GUARD           [0, 2q)
+ *           Every internal caller (key switch, mod-down / rescale, hoisted rotations, mod-raise, decode) passes canonical rows.
  */
 int moai_ntt_forward(moai_ctx *ctx, uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index,
                      void *stream);
@@ -530,6 +538,30 @@ int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
+/* Which arithmetic a context prime takes (read-only; no launch, no stream; no counterpart in the reference, whose arithmetic
+ * is the same for every modulus).  Every mode computes the same residues; each is exact only below a size limit on the prime,
+ * and tests use this query to know which limit a row exercises.  *mode receives the code the launcher itself would pick NOW,
+ * the tuning knobs included (the launchers and this query call the same host functions):
+ *   MOAI_MODE_OF_KEY_SWITCH  the fused key-switch kernels for output modulus `prime` at L data primes and `rows` = batch
+ *                            ciphertexts (MOAI_KS_FP_MIN_ROWS, MOAI_NTT_FP): GUARD, NOGUARD, FPN or FPR
+ *   MOAI_MODE_OF_MOD_DOWN    mod-down and rescale for output modulus `prime` with `rows` = polynomials * kept primes
+ *                            (MOAI_MD_FP_MIN_ROWS, MOAI_NTT_FP; L is ignored): GUARD, NOGUARD, FPN or FPR
+ *   MOAI_MODE_OF_NTT_FORWARD moai_ntt_forward's tiled kernels (N >= 4096; L, rows ignored): LAZY16, LAZY8, GUARD2, NOGUARD, FPN, FPR
+ *   MOAI_MODE_OF_NTT_INVERSE moai_ntt_inverse's tiled kernels: LAZY16, LAZY8, GUARD (the exact integer butterflies), FPN or FPR
+ * Limits: FPN 33 q < 2^52; FPR q < 2^51; NOGUARD 36 q < 2^64 and, in the key switch, 36 q^2 L < 2^128; LAZY16 / LAZY8 q < 2^60;
+ * GUARD / GUARD2 any q < 2^61.  MOAI_EINVAL for a null argument or an unknown `op`, MOAI_ERANGE for prime >= k. */
+#define MOAI_MODE_LAZY16 (-3)
+#define MOAI_MODE_LAZY8 (-2)
+#define MOAI_MODE_GUARD2 (-1)
+#define MOAI_MODE_GUARD 0
+#define MOAI_MODE_NOGUARD 1
+#define MOAI_MODE_FPN 2
+#define MOAI_MODE_FPR 3
+#define MOAI_MODE_OF_KEY_SWITCH 0
+#define MOAI_MODE_OF_MOD_DOWN 1
+#define MOAI_MODE_OF_NTT_FORWARD 2
+#define MOAI_MODE_OF_NTT_INVERSE 3
+int moai_arith_mode(const moai_ctx *ctx, size_t prime, int op, size_t L, size_t rows, int *mode);
 
 /* ---- hoisted rotations -------------------------------------------------------------------------------------------
  * out[r] = apply_galois(in, galois_elts[r], galois_keys[r]) for r < R -- R calls of Evaluator::rotate_vector /

@@ -274,6 +274,14 @@ static int dispatch_ks(int logn, int mode, F &&f)
     });
 }
 
+// whether mod-down and rescale of `rows` = polynomials * kept primes may use the FP64 arithmetic modes: below
+// MOAI_MD_FP_MIN_ROWS rows the extra launches cost more than the FP64 butterflies save (a single
+// ciphertext at MOAI's top level: 162 vs 147 ms per bootstrap; packs of 16: 66.0 vs 67.1 ms)
+static bool md_allow_fp(size_t rows)
+{
+    return (long)rows >= tuning(K_MD_FP_MIN_ROWS);
+}
+
 // Shared tail of rescale and key switch: divide rows [0, Lout) of `acc` by the modulus `prime_last`
 // whose NTT-form row is `last_rows` ([P][N], overwritten), rounding to nearest.
 //   acc row (p, i) = acc + (p * acc_stride + i) * N ; out [P][Lout][N]
@@ -317,10 +325,8 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
         }
         a.acc_splits = acc_splits;
         a.acc_split_stride = acc_split_stride;
-        // one pair of launches per arithmetic mode present among the output moduli (ntt_mode); below
-        // MOAI_MD_FP_MIN_ROWS rows the extra launches cost more than the FP64 butterflies save (a single
-        // ciphertext at MOAI's top level: 162 vs 147 ms per bootstrap; packs of 16: 66.0 vs 67.1 ms)
-        const bool allow_fp = (long)(P * Lout) >= tuning(K_MD_FP_MIN_ROWS);
+        // one pair of launches per arithmetic mode present among the output moduli (ntt_mode, md_allow_fp)
+        const bool allow_fp = md_allow_fp(P * Lout);
         for (int mode = M_GUARD; mode <= M_FPR; ++mode)
         {
             a.Lsel = 0;
@@ -534,6 +540,12 @@ static int ks_mode(const moai_ctx *c, uint32_t prime, size_t L, bool allow_fp)
     return lim < ((~(unsigned __int128)0) / (36 * (unsigned __int128)(L ? L : 1))) ? M_NOGUARD : M_GUARD;
 }
 
+// a few ciphertexts at a low level are launch-bound and stay on the integer modes (MOAI_KS_FP_MIN_ROWS, ks_plan)
+static bool ks_allow_fp(size_t L, size_t batch)
+{
+    return (long)(batch * L) >= tuning(K_KS_FP_MIN_ROWS);
+}
+
 // The launches of a key switch at L data primes: the output moduli (slot I = L stands for the special prime) ordered by
 // arithmetic mode, cut into groups of at most ks_group_size() moduli of one mode.  The unused entries of a KsGroup repeat its
 // first member.  Every mode is one more pair of launches: a few ciphertexts at a low level are launch-bound and stay on the
@@ -548,7 +560,7 @@ struct KsPlanGroup
 static std::vector<KsPlanGroup> ks_plan(const moai_ctx *c, size_t L, size_t batch)
 {
     const size_t G = ks_group_size(c, L, batch);
-    const bool allow_fp = (long)(batch * L) >= tuning(K_KS_FP_MIN_ROWS);
+    const bool allow_fp = ks_allow_fp(L, batch);
     const auto prime_of = [&](size_t Iidx) { return (uint32_t)(Iidx == L ? c->k - 1 : Iidx); };
     std::vector<uint32_t> order;
     std::vector<int> order_mode;
@@ -744,6 +756,43 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
 } // namespace moai
 
 using namespace moai;
+
+// the header's codes are the enum of modarith.hip.h
+static_assert(MOAI_MODE_LAZY16 == moai::M_LAZY16 && MOAI_MODE_LAZY8 == moai::M_LAZY8 && MOAI_MODE_GUARD2 == moai::M_GUARD2 &&
+                  MOAI_MODE_GUARD == moai::M_GUARD && MOAI_MODE_NOGUARD == moai::M_NOGUARD && MOAI_MODE_FPN == moai::M_FPN &&
+                  MOAI_MODE_FPR == moai::M_FPR,
+              "include/moai_hip.h and modarith.hip.h disagree");
+
+// read-only: the mode the launchers would pick now (ks_plan, moddown, launch_fwd, launch_inv call the same functions)
+extern "C" int moai_arith_mode(const moai_ctx *c, size_t prime, int op, size_t L, size_t rows, int *mode)
+{
+    if (!c || !mode)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    if (prime >= c->k)
+    {
+        return set_error(MOAI_ERANGE, "prime index %zu out of range (k = %zu)", prime, c->k);
+    }
+    const uint32_t p = (uint32_t)prime;
+    switch (op)
+    {
+    case MOAI_MODE_OF_KEY_SWITCH:
+        *mode = ks_mode(c, p, L, ks_allow_fp(L, rows));
+        return MOAI_OK;
+    case MOAI_MODE_OF_MOD_DOWN:
+        *mode = ntt_mode(c, p, md_allow_fp(rows));
+        return MOAI_OK;
+    case MOAI_MODE_OF_NTT_FORWARD:
+        *mode = fwd_class(c, p);
+        return MOAI_OK;
+    case MOAI_MODE_OF_NTT_INVERSE:
+        *mode = inv_class(c, p);
+        return MOAI_OK;
+    default:
+        return set_error(MOAI_EINVAL, "unknown operation %d", op);
+    }
+}
 
 namespace moai {
 // rows[r][:] = rows[r][:] * s mod q, canonical   (the dropped row of a fused scalar product + rescale)

@@ -386,15 +386,17 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
             }
         }
         } // !direct
-        // FP64 modes: when the sixteen running sums are folded back to |.| <= q/2.  Every product is below 0.88 q (fp_mulmod_q with
-        // a balanced digit), so M_FPR (2^53 / q > 4) may add three of them to a folded sum, M_FPN (q < 2^52 / 25) sixteen
+        // FP64 modes: when the sixteen running sums are folded back to |.| <= q/2.  With a balanced digit (M_FPR folds it first; a
+        // copied digit is canonical) every product is below 0.88 q, so M_FPR (2^53 / q > 4) may add three of them to a folded sum.
+        // M_FPN (33 q < 2^52, context.hip build_prime) takes the digit as the butterflies left it, its products are below 2.5 q
+        // (bounds below), and it adds sixteen
         const bool fold = MODE == M_FPR ? ((J - j0) % 3u == 2u) : (((J - j0) & 15u) == 15u);
         if (MODE >= M_FPN && PF != 0)
         {
             // the same products and sums as below, in the same order per accumulator: the same bits.
             // The digit value enters the products as the butterflies left it in M_FPN (below 33q < 2^52: the quotient estimate of
             // fp_mulmod_q is then off by at most 2, the product below 2.5 q, h - c q = r - l still an integer below 2^50, and
-            // sixteen of them on a folded sum stay below 40.5 q < 2^53 = 50 q at least) and folded to |v| <= q/2 in M_FPR
+            // sixteen of them on a folded sum stay below 40.5 q < 2^53 = 66 q at least) and folded to |v| <= q/2 in M_FPR
             // (2^53 is only 4q there).  A copied digit (canonical, below q) needs no folding in either mode.
             const double qd = u2d(bq1), qinv = u2d(bq2);
             if (PF == 1)

@@ -173,7 +173,7 @@ enum
     M_GUARD2 = -1, // integer, any q < 2^61: the guard of every SECOND stage only (values below 8q), plain forward NTT
     M_GUARD = 0,   // integer, reference discipline [0,4q)
     M_NOGUARD = 1, // integer, 36 q < 2^64
-    M_FPN = 2,     // FP64, q < 2^52 / 25: sixteen stages need no intermediate reduction
+    M_FPN = 2,     // FP64, 33 q < 2^52 (context.hip build_prime): sixteen stages need no intermediate reduction
     M_FPR = 3      // FP64, q < 2^51: the untouched operand of every butterfly is reduced first
 };
 
@@ -549,9 +549,14 @@ __device__ __forceinline__ void gs_bfly_sel<true>(uint64_t &x, uint64_t &y, uint
 // Gentleman-Sande butterfly on doubles holding integers: x' = u + v, y' = (u - v) w mod q with the product reduced at once
 // (fp_mulmod: exact for |u - v| < 2^52).  The sums double from stage to stage, the products come out below 1.5 q:
 //   FPR  (q < 2^51, 2^53 > 4q): sum and difference are reduced in every butterfly (inputs below q, outputs below 0.75 q);
-//   FPN  (q < 2^52 / 25): `redsum` reduces the sum in every FOURTH stage of a pass -- from q/2 (the load folds the input) or from
-//        the ~1.2 q of a product the sums stay below 10q, the differences below 19q (below 2^52, as 25q is) -- and the last stage of the transform
-//        multiplies both outputs by N^-1 (gs_bfly_last_fp).
+//   FPN  (33 q < 2^52, context.hip build_prime): `redsum` reduces the sum in every FOURTH stage of a pass, and the last stage of the
+//        transform multiplies both outputs by N^-1 (gs_bfly_last_fp).  Worst case, counted stage by stage with B the bound on a
+//        butterfly's inputs: sum and difference are below 2B, the product below 1.5 q, so B' = max(2B, 1.5 q), or 1.5 q after a
+//        `redsum` stage (the folded sum is at most q/2).  The load folds to B = q/2; a block of four stages from there sees
+//        differences of q, 3q, 6q, 12q and ends at 1.5 q, every later block sees 3q, 6q, 12q, 24q: that is the second register block
+//        of the contiguous pass and every full block of the strided pass, at every degree (the strided pass of N = 2^(12 + r)
+//        counts its r + 4 stages from zero, so its last, unfolded stage multiplies sums and differences of at most 24q by N^-1).
+//        No operand of a product exceeds 24 q < 33 q < 2^52, no sum before its fold 24 q < 2^53.
 // Same exact integers as the integer butterflies, canonical at the end (fp_to_canonical): the reference's residues.
 template <bool FPR>
 __device__ __forceinline__ void gs_bfly_fp(uint64_t &xb, uint64_t &yb, uint64_t wb, uint64_t wqb, uint64_t qb, uint64_t qinvb, const bool redsum)

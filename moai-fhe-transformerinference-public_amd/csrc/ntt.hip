@@ -29,6 +29,42 @@ TwPair twiddles(const moai_ctx *c, int mode, bool inverse)
     return inverse ? TwPair{ c->inv_tw, c->inv_twb } : TwPair{ c->fwd_tw, c->fwd_twb };
 }
 
+// integer primes below 2^60 take the butterflies with the approximate Shoup quotient (M_LAZY8), the others the exact
+// ones; same residues either way (modarith.hip.h)
+static bool lazy8_ok(const moai_ctx *c, uint32_t prime)
+{
+    return tuning(K_NTT_LAZY8) && c->primes[prime] < (1ull << 60);
+}
+// the same rows keep values below 16q and guard only where the bound needs it (M_LAZY16) unless MOAI_NTT_LAZY16=0
+static bool lazy16_ok(const moai_ctx *c, uint32_t prime)
+{
+    return lazy8_ok(c, prime) && tuning(K_NTT_LAZY16);
+}
+
+// The plain transform has no M_GUARD kernels: ntt_mode's integer primes with guards take M_LAZY16 (or M_LAZY8) below 2^60, else
+// the guard of every second stage (M_GUARD2).
+int fwd_class(const moai_ctx *c, uint32_t prime)
+{
+    const int m = ntt_mode(c, prime);
+    if (m != M_GUARD)
+    {
+        return m;
+    }
+    return lazy16_ok(c, prime) ? M_LAZY16 : (lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD2);
+}
+
+// inverse: FP64 below 2^51 like the forward transform, the approximate Shoup quotient below 2^60 (the inverse has no butterflies
+// without guards, so ntt_mode's M_NOGUARD rows take it too), else the exact integer butterflies (M_GUARD)
+int inv_class(const moai_ctx *c, uint32_t prime)
+{
+    const int m = ntt_mode(c, prime);
+    if (m >= M_FPN)
+    {
+        return m;
+    }
+    return lazy16_ok(c, prime) ? M_LAZY16 : (lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD);
+}
+
 NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse)
 {
     NttArgs a;
@@ -51,18 +87,6 @@ NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, con
     a.src_stride = a.src_off = 0;
     a.lds_twiddles = tuning(K_NTT_LDSTW) ? 1u : 0u;
     return a;
-}
-
-// integer primes below 2^60 take the butterflies with the approximate Shoup quotient (M_LAZY8), the others the exact
-// ones; same residues either way (modarith.hip.h)
-static bool lazy8_ok(const moai_ctx *c, uint32_t prime)
-{
-    return tuning(K_NTT_LAZY8) && c->primes[prime] < (1ull << 60);
-}
-// the same rows keep values below 16q and guard only where the bound needs it (M_LAZY16) unless MOAI_NTT_LAZY16=0
-static bool lazy16_ok(const moai_ctx *c, uint32_t prime)
-{
-    return lazy8_ok(c, prime) && tuning(K_NTT_LAZY16);
 }
 
 template <int LOGN, int MODE>
@@ -96,9 +120,8 @@ static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
     }
 }
 
-// forward transform: the rows are split by the arithmetic their prime allows and every class gets its own pair of launches.
-// The plain transform has no M_GUARD kernels: ntt_mode's integer primes with guards take M_LAZY16 (or M_LAZY8) below 2^60, else
-// the guard of every second stage (M_GUARD2).
+// forward transform: the rows are split by the arithmetic their prime allows (fwd_class) and every class gets its own pair of
+// launches
 template <int LOGN>
 static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
@@ -109,12 +132,7 @@ static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
         for (uint32_t r = 0; r < a.L; ++r)
         {
             const uint32_t prime = a.rows.idx[r];
-            int m = ntt_mode(c, prime);
-            if (m == M_GUARD)
-            {
-                m = lazy16_ok(c, prime) ? M_LAZY16 : (lazy8_ok(c, prime) ? M_LAZY8 : M_GUARD2);
-            }
-            if (m == mode)
+            if (fwd_class(c, prime) == mode)
             {
                 a.selp.idx[a.Lsel] = prime;
                 a.sel.idx[a.Lsel++] = r;
@@ -162,8 +180,8 @@ static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
     for (uint32_t r = 0; r < base.L; ++r)
     {
         const uint32_t prime = base.rows.idx[r];
-        const int m = ntt_mode(c, prime);
-        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (lazy16_ok(c, prime) ? cls[4] : (lazy8_ok(c, prime) ? cls[1] : cls[0])));
+        const int m = inv_class(c, prime);
+        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (m == M_LAZY16 ? cls[4] : (m == M_LAZY8 ? cls[1] : cls[0])));
         dst.selp.idx[dst.Lsel] = prime;
         dst.sel.idx[dst.Lsel++] = r;
     }

@@ -95,6 +95,7 @@ SYMBOLS = {
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
     "moai_reset_tuning": (C.c_int, []),
+    "moai_arith_mode": (C.c_int, [vp, sz, C.c_int, sz, sz, C.POINTER(C.c_int)]),
     "moai_mem_info": (C.c_int, [C.POINTER(sz), C.POINTER(sz)]),
     "moai_op_trace": (C.c_int, [C.c_int]),
     "moai_op_trace_dump": (C.c_size_t, [C.c_char_p, C.c_size_t]),
@@ -125,6 +126,9 @@ SYMBOLS = {
 
 
 MOAI_EINVAL = -1  # include/moai_hip.h
+# moai_arith_mode: the arithmetic modes and the operations it answers for (include/moai_hip.h)
+MODE_LAZY16, MODE_LAZY8, MODE_GUARD2, MODE_GUARD, MODE_NOGUARD, MODE_FPN, MODE_FPR = -3, -2, -1, 0, 1, 2, 3
+MODE_OF_KEY_SWITCH, MODE_OF_MOD_DOWN, MODE_OF_NTT_FORWARD, MODE_OF_NTT_INVERSE = 0, 1, 2, 3
 
 
 class MoaiError(RuntimeError):
@@ -703,6 +707,14 @@ class Context:
         roots = np.empty((self.n, 2), dtype=np.float64)
         _check(lib().moai_ckks_tables(self.h, idx.ctypes.data, roots.ctypes.data))
         return idx, roots
+
+    def arith_mode(self, prime, op, L=0, rows=0):
+        """the arithmetic mode (MODE_*) that operation `op` (MODE_OF_*) takes now for context prime `prime`: the key switch at L
+        data primes and rows = batch ciphertexts, mod-down / rescale with rows = polynomials * kept primes, or the plain
+        forward / inverse transform (moai_arith_mode; no launch)"""
+        m = C.c_int(0)
+        _check(lib().moai_arith_mode(self.h, int(prime), int(op), int(L), int(rows), C.byref(m)))
+        return m.value
 
     def sync(self, stream=None):
         _check(lib().moai_stream_sync(stream))
