@@ -521,7 +521,11 @@ int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size
  *   MOAI_NTT_LAZY8         1     0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient
  *   MOAI_NTT_LAZY16        1     0: those primes keep values below 8q with a guard in every stage instead of below 16q with fewer (M_LAZY8)
  *   MOAI_NTT_LDSTW         1     0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS
- *   MOAI_NTT_CHUNK_MB      0     > 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB
+ *   MOAI_NTT_CHUNK_MB      88    > 0: launch the two passes of a transform per chunk of whole polynomials of at most this many MiB
+ *   MOAI_NTT_CHUNK_KB      0     KiB added to MOAI_NTT_CHUNK_MB: chunks of rings whose polynomials are smaller than a MiB
+ *   MOAI_NTT_PIPE          2     1..3: deal those chunks to this many side streams, so that a chunk's second pass runs beside the next one's first; 0: one stream
+ *   MOAI_NTT_PIPE_MIN      32    chunks per side stream below which a transform stays on the caller's stream
+ *   MOAI_NTT_PIPE_INNER    0     1: the transforms inside key switch, mod-down, encode and decode take the MOAI_NTT_PIPE schedule too
  *   MOAI_NTT_NAIVE         0     1: one launch per radix-2 stage over global memory (cross-check path)
  *   MOAI_NTT_COOP          0     1: the single-launch persistent transform (N >= 4096)
  *   MOAI_NTT_COOP_WPC      4     single-launch transform: workgroups per compute unit
@@ -538,6 +542,14 @@ int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
+/* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of
+ * chunk_bytes (MOAI_NTT_CHUNK_MB and _KB, in bytes) and k side streams (MOAI_NTT_PIPE): the number of chunks the busiest side
+ * stream gets, or 0 when the transform stays on the caller's stream -- k < 1, no chunk size, fewer than two chunks, or fewer than
+ * min_chunks (MOAI_NTT_PIPE_MIN) for the busiest stream.  Chunks are whole polynomials, at least one; at most three side streams, and no more than there are chunks, are used.  The side streams
+ * belong to the context (one set per caller's stream, destroyed with it); the caller's stream forks to them and joins them through
+ * events, so the transform stays ordered on the caller's stream like any other call.  A stream that is being captured keeps the
+ * single-stream form.  Read-only host arithmetic: no context, no launch.  No counterpart in the reference. */
+size_t moai_ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes, long k, long min_chunks);
 /* Which arithmetic a context prime takes (read-only; no launch, no stream; no counterpart in the reference, whose arithmetic
  * is the same for every modulus).  Every mode computes the same residues; each is exact only below a size limit on the prime,
  * and tests use this query to know which limit a row exercises.  *mode receives the code the launcher itself would pick NOW,

@@ -50,6 +50,10 @@ struct RowMap
 
 int set_error(int code, const char *fmt, ...);
 
+// side streams of the transform's chunk schedule: with the caller's stream they make the four hardware queues a process opens
+// by default
+constexpr int NTT_PIPE_MAX = 3;
+
 #define MOAI_HIP_CHECK(expr)                                                                   \
     do                                                                                         \
     {                                                                                          \
@@ -145,6 +149,16 @@ struct moai_ctx
         size_t bytes = 0;
     };
     std::map<void *, Arena> ws;
+    // side streams of the two-pass transform's pipelined chunk schedule (ntt.hip ntt_launch), one set per caller's stream like
+    // the arenas, made on the first transform that takes the schedule (context.hip ntt_pipe) and destroyed with the context
+    struct NttPipe
+    {
+        hipStream_t side[moai::NTT_PIPE_MAX] = {};
+        hipEvent_t fork = nullptr, join[moai::NTT_PIPE_MAX] = {};
+        bool ready = false, failed = false; // failed: a stream or an event could not be created; the caller stays on one stream
+        void *mu = nullptr;                 // std::mutex: one schedule at a time is enqueued through these events
+    };
+    std::map<void *, NttPipe> ntt_pipes;
     // Galois permutation tables, built lazily per element (galois.cpp:18-51)
     std::vector<uint32_t *> galois_tables; // [N] entries index (elt-1)>>1, device pointers
     // CKKSEncoder tables (SEAL/ckks.cpp:13-76), built on the first moai_ckks_encode

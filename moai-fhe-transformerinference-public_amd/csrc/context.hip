@@ -619,6 +619,26 @@ extern "C" void moai_ctx_destroy(moai_ctx *c)
     {
         (void)hipFree(kv.second.ptr);
     }
+    for (auto &kv : c->ntt_pipes)
+    {
+        // (hipStreamDestroy waits for what the stream still holds)
+        for (int i = 0; i < NTT_PIPE_MAX; ++i)
+        {
+            if (kv.second.side[i])
+            {
+                (void)hipStreamDestroy(kv.second.side[i]);
+            }
+            if (kv.second.join[i])
+            {
+                (void)hipEventDestroy(kv.second.join[i]);
+            }
+        }
+        if (kv.second.fork)
+        {
+            (void)hipEventDestroy(kv.second.fork);
+        }
+        delete static_cast<std::mutex *>(kv.second.mu);
+    }
     for (uint32_t *t : c->galois_tables)
     {
         if (t)
@@ -704,6 +724,33 @@ int workspace(moai_ctx *c, size_t bytes, hipStream_t s, void **out)
     // 1.5 x the old size), which synchronises the device and therefore must not happen under stream capture
     // (moai_ctx_reserve[_stream] sizes the arena beforehand)
     return reserve_for_stream(c, (void *)s, bytes ? bytes : 256, out, true);
+}
+
+moai_ctx::NttPipe *ntt_pipe(moai_ctx *c, hipStream_t s)
+{
+    std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
+    moai_ctx::NttPipe &p = c->ntt_pipes[(void *)s]; // (std::map: the address stays valid while other streams are added)
+    if (!p.ready && !p.failed)
+    {
+        bool ok = hipEventCreateWithFlags(&p.fork, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; ok && i < NTT_PIPE_MAX; ++i)
+        {
+            ok = hipStreamCreateWithFlags(&p.side[i], hipStreamNonBlocking) == hipSuccess &&
+                 hipEventCreateWithFlags(&p.join[i], hipEventDisableTiming) == hipSuccess;
+        }
+        if (ok)
+        {
+            p.mu = new std::mutex();
+            p.ready = true;
+        }
+        else
+        {
+            // what was made stays until moai_ctx_destroy; the failure is not the caller's, whose transform runs on its own stream
+            (void)hipGetLastError();
+            p.failed = true;
+        }
+    }
+    return p.ready ? &p : nullptr;
 }
 
 size_t chunk_items(moai_ctx *c, hipStream_t s, size_t per_bytes, size_t n, size_t cap, size_t floor_bytes)

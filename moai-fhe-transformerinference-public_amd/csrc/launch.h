@@ -14,7 +14,11 @@ namespace moai {
     X(NTT_LAZY8, 1, "0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient")       \
     X(NTT_LAZY16, 1, "0: those primes keep values below 8q with a guard in every stage instead of below 16q with fewer (M_LAZY8)") \
     X(NTT_LDSTW, 1, "0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS")      \
-    X(NTT_CHUNK_MB, 0, "> 0: launch the two passes of a transform per chunk of polynomials of at most this many MiB")          \
+    X(NTT_CHUNK_MB, 88, "> 0: launch the two passes of a transform per chunk of whole polynomials of at most this many MiB")    \
+    X(NTT_CHUNK_KB, 0, "KiB added to MOAI_NTT_CHUNK_MB: chunks of rings whose polynomials are smaller than a MiB")             \
+    X(NTT_PIPE, 2, "1..3: deal those chunks to this many side streams, so that a chunk's second pass runs beside the next one's first; 0: one stream") \
+    X(NTT_PIPE_MIN, 32, "chunks per side stream below which a transform stays on the caller's stream")                         \
+    X(NTT_PIPE_INNER, 0, "1: the transforms inside key switch, mod-down, encode and decode take the MOAI_NTT_PIPE schedule too") \
     X(NTT_NAIVE, 0, "1: one launch per radix-2 stage over global memory (cross-check path)")                                   \
     X(NTT_COOP, 0, "1: the single-launch persistent transform (N >= 4096)")                                                    \
     X(NTT_COOP_WPC, 4, "single-launch transform: workgroups per compute unit")                                                 \
@@ -109,8 +113,19 @@ int make_rowmap(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap
 int rows_entry(const moai_ctx *c, size_t L, const uint32_t *prime_index, RowMap *out);
 // src (inverse only): polynomial p's row r is read from src row p * src_stride_rows + src_off_rows + r, the result lands in
 // `data` [n_poly][L][N] -- the inverse transform of a slice of a larger layout without copying the slice first
+// entry: the call is moai_ntt_forward's or moai_ntt_inverse's own; the others take the side streams of MOAI_NTT_PIPE only under
+// MOAI_NTT_PIPE_INNER
 int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse,
-               hipStream_t s, const uint64_t *src = nullptr, size_t src_stride_rows = 0, size_t src_off_rows = 0);
+               hipStream_t s, const uint64_t *src = nullptr, size_t src_stride_rows = 0, size_t src_off_rows = 0, bool entry = false);
+// The chunk schedule of a two-pass transform of n_poly polynomials of L rows of n coefficients, with chunks of chunk_bytes
+// (rounded down to whole polynomials, at least one) dealt round-robin to k side streams: the number of chunks the busiest
+// stream gets, or 0 for the caller's stream alone -- k < 1, no chunk size, fewer than two chunks (no second pass has a first
+// pass to run beside), or fewer than min_chunks for the busiest stream.  More streams than NTT_PIPE_MAX or than chunks are not
+// used.  Pure host arithmetic.
+size_t ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes, long k, long min_chunks, size_t *chunk_polys = nullptr,
+                     int *streams = nullptr);
+// the side streams and events of caller's stream s, made on first use; nullptr when they could not be made (remembered)
+moai_ctx::NttPipe *ntt_pipe(moai_ctx *c, hipStream_t s);
 // returns the context workspace grown to at least `bytes` (grows only outside stream capture)
 int workspace(moai_ctx *c, size_t bytes, hipStream_t s, void **out);
 // items per chunk of a batch of n whose items need per_bytes of scratch each: as many as fit the stream's arena, or floor_bytes

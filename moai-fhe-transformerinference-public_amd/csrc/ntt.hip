@@ -1,4 +1,6 @@
 // ntt.hip -- launchers of the negacyclic NTT kernels (C ABI: moai_ntt_forward / moai_ntt_inverse).
+#include <mutex>
+
 #include "ntt_kernels.hip.h"
 #include "launch.h"
 
@@ -242,9 +244,44 @@ static int launch_coop(moai_ctx *c, const NttArgs &base, bool inverse, void *sta
     return MOAI_OK;
 }
 
+size_t ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes, long k, long min_chunks, size_t *chunk_polys, int *streams)
+{
+    size_t chunk = n_poly, per_stream = 0;
+    int nk = 0;
+    if (n_poly && L && n && chunk_bytes)
+    {
+        // (a polynomial too large for size_t is larger than any chunk)
+        const size_t poly_bytes = L > (~(size_t)0) / sizeof(uint64_t) / n ? ~(size_t)0 : L * n * sizeof(uint64_t);
+        chunk = chunk_bytes / poly_bytes;
+        chunk = chunk < 1 ? 1 : (chunk > n_poly ? n_poly : chunk);
+    }
+    const size_t chunks = chunk ? (n_poly + chunk - 1) / chunk : 0;
+    if (k >= 1 && chunks >= 2)
+    {
+        nk = k > NTT_PIPE_MAX ? NTT_PIPE_MAX : (int)k;
+        nk = (size_t)nk > chunks ? (int)chunks : nk;
+        per_stream = (chunks + (size_t)nk - 1) / (size_t)nk;
+        if (min_chunks > 0 && per_stream < (size_t)min_chunks)
+        {
+            // the fork and the join cost a small batch more than the overlap gives back (profiles/ntt_pipe_sweep.txt)
+            nk = 0;
+            per_stream = 0;
+        }
+    }
+    if (chunk_polys)
+    {
+        *chunk_polys = chunk;
+    }
+    if (streams)
+    {
+        *streams = nk;
+    }
+    return per_stream;
+}
+
 // data [n_poly][L][N]; rows maps row -> prime.  Returns a MOAI_* code.
 int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMap &rows, bool inverse, hipStream_t s,
-               const uint64_t *src, size_t src_stride_rows, size_t src_off_rows)
+               const uint64_t *src, size_t src_stride_rows, size_t src_off_rows, bool entry)
 {
     if (n_poly == 0 || L == 0)
     {
@@ -326,36 +363,80 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
         MOAI_TRY(reserve_for_stream(c, (void *)((uintptr_t)s ^ 1u), coop_state_bytes(c, n_poly * L), &st, false));
         return launch_coop(c, a, inverse, st, s);
     }
-    // The two passes of one transform exchange the whole polynomial through memory.  Launching them
-    // per chunk of polynomials that fits the 256 MiB Infinity Cache lets the second pass read what
-    // the first one just wrote from the cache instead of HBM (MOAI_NTT_CHUNK_MB, 0 = one chunk).
+    // The two passes of one transform exchange the whole polynomial through memory.  Launched per chunk of polynomials
+    // (MOAI_NTT_CHUNK_MB [+ _KB], 0 = one chunk), the second pass can read from the 256 MiB Infinity Cache what the first one just
+    // wrote.  On one stream that gains nothing: every launch of a chunk ends in a tail that leaves the chip part empty, and the
+    // round-2 sweep broke even down to 88 MiB and lost below (profiles/r02_g_ntt_subbatch_experiment.txt).  MOAI_NTT_PIPE = K
+    // deals the chunks round-robin to K side streams instead: stream order keeps a chunk's second pass behind its first, chunks
+    // are independent, so chunk i's second pass runs beside chunk i+1's first and fills its tail (profiles/ntt_pipe_sweep.txt).
+    // The caller's stream forks to the side streams through one event and joins them through one event each.
     size_t chunk = n_poly;
-    const long chunk_mb = tuning(K_NTT_CHUNK_MB);
-    if (chunk_mb > 0)
+    int nk = 0;
+    const long chunk_mb = tuning(K_NTT_CHUNK_MB), chunk_kb = tuning(K_NTT_CHUNK_KB);
+    const size_t chunk_bytes = ((size_t)(chunk_mb > 0 ? chunk_mb : 0) << 20) + ((size_t)(chunk_kb > 0 ? chunk_kb : 0) << 10);
+    const long want = tuning(K_NTT_PIPE);
+    ntt_pipe_plan(n_poly, L, c->n, chunk_bytes, want > 0 && (entry || tuning(K_NTT_PIPE_INNER)) ? want : 0, tuning(K_NTT_PIPE_MIN), &chunk,
+                  &nk);
+    moai_ctx::NttPipe *pipe = nullptr;
+    if (nk > 0)
     {
-        chunk = ((size_t)chunk_mb << 20) / (L * c->n * sizeof(uint64_t));
-        if (chunk < 1)
+        // a capture must not acquire parallel branches: a capturing stream keeps the single-stream loop
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess)
         {
-            chunk = 1;
+            (void)hipGetLastError();
+        }
+        else if (cap == hipStreamCaptureStatusNone)
+        {
+            pipe = ntt_pipe(c, s);
         }
     }
-    for (size_t p0 = 0; p0 < n_poly; p0 += chunk)
+    std::unique_lock<std::mutex> pipe_lock;
+    if (want > 0 && !pipe)
     {
+        // the chunks are there for the side streams: a call that takes none (the library's own transforms, a capture, a small
+        // batch) is one pair of launches.  MOAI_NTT_PIPE=0 keeps the chunk loop on the caller's stream.
+        chunk = n_poly;
+    }
+    if (pipe)
+    {
+        pipe_lock = std::unique_lock<std::mutex>(*static_cast<std::mutex *>(pipe->mu));
+        MOAI_HIP_CHECK(hipEventRecord(pipe->fork, s));
+        for (int i = 0; i < nk; ++i)
+        {
+            MOAI_HIP_CHECK(hipStreamWaitEvent(pipe->side[i], pipe->fork, 0));
+        }
+    }
+    int rc = MOAI_OK;
+    size_t ci = 0;
+    for (size_t p0 = 0; p0 < n_poly && rc == MOAI_OK; p0 += chunk, ++ci)
+    {
+        const hipStream_t cs = pipe ? pipe->side[ci % (size_t)nk] : s;
         a.data = data + p0 * L * c->n;
         if (a.src)
         {
             a.src = src + p0 * src_stride_rows * c->n;
         }
         a.n_poly = (uint32_t)(n_poly - p0 < chunk ? n_poly - p0 : chunk);
-        MOAI_TRY(dispatch_logn(logn, [&](auto LG) {
+        rc = dispatch_logn(logn, [&](auto LG) {
             if (inverse)
             {
-                launch_inv<decltype(LG)::value>(c, a, s);
+                launch_inv<decltype(LG)::value>(c, a, cs);
                 return MOAI_OK;
             }
-            return launch_fwd<decltype(LG)::value>(c, a, s);
-        }));
+            return launch_fwd<decltype(LG)::value>(c, a, cs);
+        });
     }
+    if (pipe)
+    {
+        // (also after an error: the caller's stream never leaves a side stream behind)
+        for (int i = 0; i < nk; ++i)
+        {
+            MOAI_HIP_CHECK(hipEventRecord(pipe->join[i], pipe->side[i]));
+            MOAI_HIP_CHECK(hipStreamWaitEvent(s, pipe->join[i], 0));
+        }
+    }
+    MOAI_TRY(rc);
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }
@@ -416,7 +497,12 @@ static int ntt_entry(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const
     {
         return rc;
     }
-    return ntt_launch(c, data, n_poly, L, rows, inverse, (hipStream_t)stream);
+    return ntt_launch(c, data, n_poly, L, rows, inverse, (hipStream_t)stream, nullptr, 0, 0, true);
+}
+
+extern "C" size_t moai_ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes, long k, long min_chunks)
+{
+    return ntt_pipe_plan(n_poly, L, n, chunk_bytes, k, min_chunks);
 }
 
 extern "C" int moai_ntt_forward(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index,

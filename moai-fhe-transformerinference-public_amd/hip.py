@@ -95,6 +95,7 @@ SYMBOLS = {
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
     "moai_set_tuning": (C.c_int, [C.c_char_p, C.c_long]),
     "moai_reset_tuning": (C.c_int, []),
+    "moai_ntt_pipe_plan": (sz, [sz, sz, sz, sz, C.c_long, C.c_long]),
     "moai_arith_mode": (C.c_int, [vp, sz, C.c_int, sz, sz, C.POINTER(C.c_int)]),
     "moai_mem_info": (C.c_int, [C.POINTER(sz), C.POINTER(sz)]),
     "moai_op_trace": (C.c_int, [C.c_int]),
@@ -722,6 +723,11 @@ class Context:
 
 def set_tuning(name, value):
     _check(lib().moai_set_tuning(name.encode(), int(value)))
+
+
+def ntt_pipe_plan(n_poly, L, n, chunk_bytes, k, min_chunks=1):
+    """chunks on the busiest side stream of the transform's chunk schedule, 0: the caller's stream alone (moai_ntt_pipe_plan)"""
+    return int(lib().moai_ntt_pipe_plan(n_poly, L, n, chunk_bytes, k, min_chunks))
 
 
 def reset_tuning():
