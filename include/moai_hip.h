@@ -408,7 +408,7 @@ int moai_ckks_tables(moai_ctx *ctx, uint32_t *index_map, double *inv_root_powers
  * is the symmetric encryption of zero with sequence seq + J plus (q_{k-1} mod q_J) * new_key[J] in row J of c0
  * (KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336).  out: device [k-1][2][k][N], the layout every
  * key-switch entry point above takes.
- * Large batches are processed in chunks whose scratch fits the stream's arena or 1 GiB, whichever is larger.  Arguments are
+ * Large batches are processed in chunks whose scratch fits the stream's arena or 1 GiB (MOAI_CLIENT_TMP_KB), whichever is larger.  Arguments are
  * validated before anything is enqueued (MOAI_EINVAL with a message: null context / key / argument, "invalid level", a
  * sequence range beyond 2^56, more than 65535 ciphertexts; MOAI_ELOGIC for k < 2 in key generation).  No call synchronises. */
 /* sample_poly_uniform SEAL/util/rlwe.cpp:137-183 (the stream above instead of rejection sampling) */
@@ -455,6 +455,9 @@ int moai_kswitch_keygen(moai_ctx *ctx, const uint8_t *key, uint64_t seq, const u
  *   purpose 5  public seed: the seed of the object with sequence seq is the first 32 bytes (words W[0..3], little endian) of
  *              the stream (noise key, 5 << 56 | seq), computed on the host (seal::util::ChaCha20Rng); ChaCha20 output does not
  *              reveal its key.  Inside a seeded object sequences start at 0.
+ *   purpose 6  SEAL seed: the 64-byte Blake2xb seed of the object (ciphertext or key digit) with sequence seq is words W[0..7],
+ *              little endian, of the stream (noise key, 6 << 56 | seq), computed on the host as purpose 5 is; it feeds the
+ *              SEAL-seeded entry points of the next section, whose objects SEAL itself expands.
  * moai_encrypt_symmetric_seeded: out_c0 [n_batch][L][N] = c0 exactly as moai_encrypt_symmetric computes it with a from
  * (seed, 1 << 56 | seq + b) and e from (noise_key, 3 << 56 | seq + b); c1 is not written.
  * moai_kswitch_keygen_seeded: the same for the k-1 digits of a switching key, out_c0 [k-1][k][N].
@@ -485,7 +488,9 @@ int moai_expand_seeded(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const u
  * A SEAL client ships symmetric ciphertexts and switching keys seeded: one polynomial of data and a 64-byte seed from which
  * Ciphertext::expand_seed redraws the other with SEAL's default generator, Blake2xb in counter mode (buffer c of 4096 bytes is a
  * hash of (seed, c) alone).  These entry points are that generator and the sampler on top of it, bit for bit; the byte format
- * itself is host work (seal_shim/seal/moai_seal_format.h).  Shake256-seeded objects are not supported.
+ * itself is host work (seal_shim/seal/moai_seal_format.h).  Shake256-seeded objects are not supported.  The same generator
+ * serves the other direction: moai_encrypt_symmetric_seal_seeded and moai_kswitch_keygen_seal_seeded make objects whose uniform
+ * half IS the expansion of a SEAL seed, so that what leaves this side seeded is what SEAL's own load expands.
  * moai_seal_prng_bytes: out (device, n_blocks * 4096 bytes, 16-byte aligned) = buffers first_block .. first_block + n_blocks - 1
  * of Blake2xbPRNG(seed).
  * moai_seal_sample_uniform: for every b < count, out + b * stride_words as [L][N] (rows under prime_index, NULL = 0..L-1) is
@@ -500,7 +505,18 @@ int moai_expand_seeded(moai_ctx *ctx, const uint8_t *seed, uint64_t seq, const u
  * unbounded); the words not yet replaced then stay 2^64 - 1, which moai_check_residues reports.
  * moai_check_residues: sets *invalid (device, zeroed by the caller) to non-zero when a residue of data [n_poly][L][N] is >= its
  * prime, and otherwise leaves it alone: the flag of moai_unpack_rows for rows that arrive unpacked.
- * Validation as above: MOAI_EINVAL with a message before anything is enqueued; no call synchronises. */
+ * moai_encrypt_symmetric_seal_seeded: moai_encrypt_symmetric_seeded with a from SEAL's generator instead of ChaCha20: for
+ * ciphertext b, a_b is exactly what moai_seal_sample_uniform writes for seeds[b] over the same rows (NTT form, as SEAL samples
+ * it), e_b is the CBD draw of (noise_key, 3 << 56 | seq + b), word for word the noise of the ChaCha20-seeded call, and
+ * out_c0[b] = NTT(e_b) - a_b * s (+ plain_b); c1 is never written.  One 64-byte seed per ciphertext, as Ciphertext::expand_seed
+ * takes one generator per ciphertext (callers draw them under purpose 6 of the stream contract, or anywhere else).
+ * moai_kswitch_keygen_seal_seeded: the same for the k-1 digits of a switching key, digit J from seeds[J] and sequence seq + J
+ * plus (q_{k-1} mod q_J) * new_key[J] in row J; out_c0 [k-1][k][N].
+ * Both expand a into scratch [chunk][L][N] beside the noise with the sampler's own kernels on the caller's stream and read it
+ * back in the kernel that writes c0; a chunk's scratch is 2 L N words and L counters per ciphertext or digit, within the
+ * stream's arena or 1 GiB as for the other client calls.  rejected: as in moai_seal_sample_uniform, the overflow word included.
+ * Validation as above: MOAI_EINVAL with a message before anything is enqueued (a null seeds pointer is "null seed"); no call
+ * synchronises. */
 /* Blake2xbPRNG::refill_buffer, SEAL/randomgen.cpp:201-211 over blake2xb, SEAL/util/blake2xb.c:32-181 */
 int moai_seal_prng_bytes(moai_ctx *ctx, const uint8_t *seed /* host, 64 bytes */, uint64_t first_block, uint64_t n_blocks, void *out,
                          void *stream);
@@ -511,6 +527,16 @@ int moai_seal_sample_uniform(moai_ctx *ctx, const uint8_t *seeds /* host, [count
 /* is_data_valid_for's residue check, SEAL/valcheck.cpp:302-335 */
 int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index, uint32_t *invalid,
                         void *stream);
+/* encrypt_zero_symmetric with save_seed, SEAL/util/rlwe.cpp:311-385, a from Ciphertext::expand_seed's generator,
+ * SEAL/ciphertext.cpp:118-151 */
+int moai_encrypt_symmetric_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key /* host, 32 bytes */,
+                                       const uint8_t *seeds /* host, [n_batch][64] */, uint64_t seq, const uint64_t *sk_ntt,
+                                       const uint64_t *plain, uint64_t *out_c0, size_t n_batch, size_t L, const uint32_t *prime_index,
+                                       uint32_t *rejected /* device [2], or NULL */, void *stream);
+/* KeyGenerator::generate_one_kswitch_key with save_seed, SEAL/keygenerator.cpp:303-336: one 64-byte seed per digit */
+int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, const uint8_t *seeds /* host, [k-1][64] */, uint64_t seq,
+                                    const uint64_t *sk_ntt, const uint64_t *new_key_ntt, uint64_t *out_c0 /* [k-1][k][N] */,
+                                    uint32_t *rejected, void *stream);
 
 /* ---- tuning -------------------------------------------------------------------------------------------------------
  * moai_set_tuning overrides a performance knob for the whole process; it takes precedence over the environment variable
@@ -539,7 +565,8 @@ int moai_check_residues(moai_ctx *ctx, const uint64_t *data, size_t n_poly, size
  *   MOAI_KS_HOIST_PAIR     4     rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one
  *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
- *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller */
+ *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
+ *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
 /* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of

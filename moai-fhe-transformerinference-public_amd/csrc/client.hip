@@ -12,12 +12,15 @@
 //   cl_sym_finish   : c1 = uniform a generated in place (NTT form, as SEAL samples it), c0 = e - a s (+ m) (+ (p mod q_J) s' in
 //                     row J of a key digit); c1 is never stored before this kernel, and in the seeded form (a from a public seed,
 //                     SEAL/util/rlwe.cpp:353-363) not stored at all
+//                     A_MEM: a is not drawn but read from scratch [nb][L][N] that sealprng.hip's fill and fix-up kernels have
+//                     just written on the same stream from a SEAL seed per ciphertext (the SEAL-seeded entry points)
 //   cl_expand       : c1 of a seeded object drawn again from its seed beside a copy of c0 (Ciphertext::expand_seed)
 //   FULLPOS (both)  : the rows are a selection {0 .. levels-1, k-1} of a key digit's k rows that keeps the FULL draw's stream
 //                     positions (row r under prime p takes the words of row p), and sk / newkey stay full [k][N] keys read at
 //                     row p: a level-limited key is word for word the trim of the full one (moai_kswitch_keygen_limited)
 //   cl_pk_finish    : c_i = pk_i u + e_i over the rows of the previous level, u read once; then the existing rescale divides by
 //                     the dropped prime (divide_and_round_q_last_ntt_inplace) and cl_add_c0 adds the plaintext to c0
+#include <algorithm>
 #include <mutex>
 
 #include "launch.h"
@@ -33,6 +36,14 @@ struct ChaKey
 // purposes of the nonce (nonce = purpose << 56 | sequence), include/moai_hip.h
 constexpr uint64_t CL_UNIFORM = 1, CL_TERNARY = 2, CL_NOISE0 = 3, CL_NOISE1 = 4;
 constexpr uint64_t CL_SEQ_LIMIT = 1ull << 56;
+// (purposes 5 and 6, the public ChaCha20 seed and the SEAL seed of a seeded object, are drawn on the host by the seal:: shim)
+
+// where cl_sym_finish takes a from
+enum
+{
+    A_CHACHA, // drawn in the kernel from (key, nonce_a + b)
+    A_MEM     // read from SymArgs::a
+};
 
 __device__ __forceinline__ uint32_t rotl32(uint32_t v, int c)
 {
@@ -195,6 +206,7 @@ struct SymArgs
 {
     ChaKey key;             // the stream a is drawn from: the caller's one key, or the public seed of a seeded object
     uint64_t nonce_a;       // ciphertext b (of this launch) draws a with nonce_a + b
+    const uint64_t *a;      // A_MEM: [nb][L][N] NTT form, a of ciphertext b instead of the draw
     const uint64_t *e;      // [nb][L][N] NTT form
     const uint64_t *sk;     // [L][N]; FULLPOS: [k][N], row r read at its prime's index
     const uint64_t *plain;  // [nb][L][N] or null
@@ -208,7 +220,7 @@ struct SymArgs
     uint32_t logn;
 };
 
-template <bool SEEDED, bool FULLPOS>
+template <int A_SRC, bool SEEDED, bool FULLPOS>
 __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
 {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
@@ -225,13 +237,25 @@ __global__ __launch_bounds__(256) void cl_sym_finish(SymArgs g)
     const uint64_t q = pc.q;
     // coefficient offset of this thread in the full [k][N] layout (sk, newkey and the stream position), else the compact one
     const uint32_t ff = FULLPOS ? (p << g.logn) + (f & ((1u << g.logn) - 1)) : f;
-    uint32_t blk[16];
-    chacha_block(g.key, g.nonce_a + b, ff >> 2, blk);
     uint64_t a[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++)
+    if (A_SRC == A_MEM)
     {
-        a[j] = mod128(word64(blk, 2 * j), word64(blk, 2 * j + 1), pc);
+        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2 *>(g.a + b * LN + f);
+        const ulonglong2 a01 = a2[0], a23 = a2[1];
+        a[0] = a01.x;
+        a[1] = a01.y;
+        a[2] = a23.x;
+        a[3] = a23.y;
+    }
+    else
+    {
+        uint32_t blk[16];
+        chacha_block(g.key, g.nonce_a + b, ff >> 2, blk);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            a[j] = mod128(word64(blk, 2 * j), word64(blk, 2 * j + 1), pc);
+        }
     }
     const ulonglong2 *e2 = reinterpret_cast<const ulonglong2 *>(g.e + b * LN + f);
     const ulonglong2 *s2 = reinterpret_cast<const ulonglong2 *>(g.sk + ff);
@@ -420,8 +444,11 @@ static int launch_small(moai_ctx *c, bool cbd, const ChaKey &key, uint64_t nonce
     return MOAI_OK;
 }
 
-// items per chunk (launch.h chunk_items): within the stream's arena or 1 GiB, whichever is larger
-constexpr size_t CL_CHUNK_FLOOR = (size_t)1 << 30;
+// items per chunk (launch.h chunk_items): within the stream's arena or MOAI_CLIENT_TMP_KB (1 GiB), whichever is larger
+static size_t chunk_floor()
+{
+    return (size_t)std::max(1l, tuning(K_CLIENT_TMP_KB)) << 10;
+}
 
 // what every entry point checks first; the samplers, which take a raw nonce, pass seq = count = 0
 static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, size_t count)
@@ -452,14 +479,19 @@ static int check_common(const moai_ctx *c, const uint8_t *key, uint64_t seq, siz
 // symmetric encryptions (newkey == null) or the digits of a switching key: ciphertext b uses sequence seq + b.  seed == null:
 // a and e from `key`, out [n_batch][2][L][N]; otherwise e from `key`, a from `seed`, and out holds c0 only, [n_batch][L][N].
 // fullpos: sk and newkey are full [k][N] keys and a keeps the stream positions of the full k-row draw (cl_sym_finish FULLPOS)
+// seal_seeds (with seed == null, never with fullpos): host [n_batch][64]; a of ciphertext b is SEAL's sample_poly_uniform of
+// seal_seeds[b], expanded per chunk into scratch beside e, out holds c0 only, and `rejected` is moai_seal_sample_uniform's
 static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk, const uint64_t *plain,
-                    const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, bool fullpos, hipStream_t s)
+                    const uint64_t *newkey, uint64_t *out, size_t n_batch, size_t L, const RowMap &rows, bool fullpos, hipStream_t s,
+                    const uint8_t *seal_seeds = nullptr, uint32_t *rejected = nullptr)
 {
     MOAI_TRY(enter_device(c));
     const ChaKey k = load_key(key);
     const size_t n = c->n, LN = L * n;
+    const bool c0_only = seed || seal_seeds;
     SymArgs a;
     a.key = seed ? load_key(seed) : k;
+    a.a = nullptr;
     a.sk = sk;
     a.newkey = newkey;
     a.pc = c->pc;
@@ -472,23 +504,39 @@ static int sym_impl(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64
         a.fac[r] = r < L ? c->primes[c->k - 1] % c->primes[rows.idx[r]] : 0;
     }
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
-    const size_t cb = chunk_items(c, s, LN * sizeof(uint64_t), n_batch, 65535, CL_CHUNK_FLOOR);
+    // scratch per ciphertext: e [L][N]; from SEAL seeds also a [L][N] and the sampler's mark counts [L]
+    const size_t per = seal_seeds ? 2 * LN * sizeof(uint64_t) + L * sizeof(uint32_t) : LN * sizeof(uint64_t);
+    const size_t cb = chunk_items(c, s, per, n_batch, 65535, chunk_floor());
     void *scratch = nullptr;
-    MOAI_TRY(workspace(c, cb * LN * sizeof(uint64_t), s, &scratch));
+    MOAI_TRY(workspace(c, cb * per, s, &scratch));
     uint64_t *e = static_cast<uint64_t *>(scratch);
+    uint64_t *a_mem = e + cb * LN;
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(a_mem + cb * LN);
     return for_chunks(n_batch, cb, [&](size_t b0, size_t nb) {
+        if (seal_seeds)
+        {
+            MOAI_TRY(seal_uniform_launch(c, seal_seeds + b0 * 64, a_mem, LN, nb, L, rows, cnt, rejected, s));
+            a.a = a_mem;
+        }
         MOAI_TRY(launch_small(c, true, k, (CL_NOISE0 << 56) | (seq + b0), e, LN, nb, L, rows, s));
         MOAI_TRY(ntt_launch(c, e, nb, L, rows, false, s));
         a.nonce_a = (CL_UNIFORM << 56) | (seq + b0);
         a.e = e;
         a.plain = plain ? plain + b0 * LN : nullptr;
-        a.out = out + b0 * (seed ? 1 : 2) * LN;
+        a.out = out + b0 * (c0_only ? 1 : 2) * LN;
         a.digit0 = (uint32_t)b0;
-        auto *kernel = fullpos ? (seed ? cl_sym_finish<true, true> : cl_sym_finish<false, true>)
-                               : (seed ? cl_sym_finish<true, false> : cl_sym_finish<false, false>);
-        hipLaunchKernelGGL(kernel, grid_of(LN / 4, nb), dim3(256), 0, s, a);
-        MOAI_LAUNCH_CHECK();
-        return MOAI_OK;
+        return dispatch<A_CHACHA, A_MEM>("source of a ", seal_seeds ? A_MEM : A_CHACHA, [&](auto src) {
+            constexpr int SRC = decltype(src)::value;
+            void (*kernel)(SymArgs) = cl_sym_finish<SRC, true, false>; // a from memory exists in this form only
+            if constexpr (SRC == A_CHACHA)
+            {
+                kernel = fullpos ? (seed ? cl_sym_finish<SRC, true, true> : cl_sym_finish<SRC, false, true>)
+                                 : (seed ? cl_sym_finish<SRC, true, false> : cl_sym_finish<SRC, false, false>);
+            }
+            hipLaunchKernelGGL(kernel, grid_of(LN / 4, nb), dim3(256), 0, s, a);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        });
     });
 }
 
@@ -556,7 +604,7 @@ MOAI_SAMPLER(cbd, 2)
 
 static int encrypt_symmetric_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
                                    const uint64_t *plain, uint64_t *out, size_t n_batch, size_t L, const uint32_t *prime_index,
-                                   void *stream)
+                                   void *stream, const uint8_t *seal_seeds = nullptr, uint32_t *rejected = nullptr)
 {
     MOAI_TRY(check_common(c, key, seq, n_batch));
     RowMap rows;
@@ -569,7 +617,7 @@ static int encrypt_symmetric_entry(moai_ctx *c, const uint8_t *key, const uint8_
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    return sym_impl(c, key, seed, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, false, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, plain, nullptr, out, n_batch, L, rows, false, (hipStream_t)stream, seal_seeds, rejected);
 }
 
 extern "C" int moai_encrypt_symmetric(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *plain,
@@ -594,7 +642,8 @@ extern "C" int moai_encrypt_symmetric_seeded(moai_ctx *c, const uint8_t *noise_k
 }
 
 static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
-                                const uint64_t *new_key_ntt, uint64_t *out, void *stream)
+                                const uint64_t *new_key_ntt, uint64_t *out, void *stream, const uint8_t *seal_seeds = nullptr,
+                                uint32_t *rejected = nullptr)
 {
     if (c->k < 2)
     {
@@ -608,7 +657,8 @@ static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *
     }
     RowMap rows;
     MOAI_TRY(make_rowmap(c, c->k, nullptr, &rows));
-    return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, false, (hipStream_t)stream);
+    return sym_impl(c, key, seed, seq, sk_ntt, nullptr, new_key_ntt, out, digits, c->k, rows, false, (hipStream_t)stream, seal_seeds,
+                    rejected);
 }
 
 extern "C" int moai_kswitch_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
@@ -637,6 +687,36 @@ extern "C" int moai_kswitch_keygen_seeded(moai_ctx *c, const uint8_t *noise_key,
         return set_error(MOAI_EINVAL, "null seed");
     }
     return kswitch_keygen_entry(c, noise_key, seed, seq, sk_ntt, new_key_ntt, out_c0, stream);
+}
+
+extern "C" int moai_encrypt_symmetric_seal_seeded(moai_ctx *c, const uint8_t *noise_key, const uint8_t *seeds, uint64_t seq,
+                                                  const uint64_t *sk_ntt, const uint64_t *plain, uint64_t *out_c0, size_t n_batch, size_t L,
+                                                  const uint32_t *prime_index, uint32_t *rejected, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, plain, out_c0, rejected);
+    trace_op("encrypt_symmetric_seal_seeded", L, n_batch);
+    if (c && noise_key && !seeds)
+    {
+        return set_error(MOAI_EINVAL, "null seed");
+    }
+    return encrypt_symmetric_entry(c, noise_key, nullptr, seq, sk_ntt, plain, out_c0, n_batch, L, prime_index, stream, seeds, rejected);
+}
+
+extern "C" int moai_kswitch_keygen_seal_seeded(moai_ctx *c, const uint8_t *noise_key, const uint8_t *seeds, uint64_t seq,
+                                               const uint64_t *sk_ntt, const uint64_t *new_key_ntt, uint64_t *out_c0, uint32_t *rejected,
+                                               void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out_c0, rejected);
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    trace_op("kswitch_keygen_seal_seeded", c->k, c->k - 1);
+    if (noise_key && !seeds)
+    {
+        return set_error(MOAI_EINVAL, "null seed");
+    }
+    return kswitch_keygen_entry(c, noise_key, nullptr, seq, sk_ntt, new_key_ntt, out_c0, stream, seeds, rejected);
 }
 
 extern "C" int moai_expand_seeded(moai_ctx *c, const uint8_t *seed, uint64_t seq, const uint64_t *c0, uint64_t *out, size_t count, size_t L,
@@ -804,7 +884,7 @@ extern "C" int moai_encrypt_asymmetric(moai_ctx *c, const uint8_t *key, uint64_t
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
     // scratch per ciphertext: u, e0, e1 [3][M][N], and the rescale's own workspace [2][M][N] at the head of the arena
     const size_t per = (divide ? 5 : 3) * MN * sizeof(uint64_t);
-    const size_t cb = chunk_items(c, s, per, n_batch, 32767, CL_CHUNK_FLOOR);
+    const size_t cb = chunk_items(c, s, per, n_batch, 32767, chunk_floor());
     const size_t head = divide ? rescale_ws_bytes(c, M, 2 * cb) : 0;
     void *wsp = nullptr;
     MOAI_TRY(workspace(c, head + 3 * cb * MN * sizeof(uint64_t), s, &wsp));

@@ -32,7 +32,8 @@ namespace moai {
     X(KS_HOIST_PAIR, 4, "rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one")                         \
     X(MD_FP_MIN_ROWS, 256, "polynomials * L from which mod-down and rescale use the FP64 arithmetic modes")                    \
     X(MATMUL_FP, 1, "0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel")                                      \
-    X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")
+    X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")                     \
+    X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller")
 
 enum Knob
 {
@@ -149,5 +150,11 @@ int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index);
 // rescale_ws_bytes(c, L, batch * size) bytes of the stream's arena, the caller's own scratch lies behind them
 size_t rescale_ws_bytes(const moai_ctx *c, size_t L, size_t polys);
 int rescale_nolock(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t size, size_t L, size_t batch, hipStream_t s);
+
+// moai_seal_sample_uniform for a caller that has validated its arguments and holds op_mutex (client.hip's SEAL-seeded entry
+// points): polynomial b of `count` lands at out + b * stride_words; cnt is device scratch [count][L] that the call zeroes itself
+// (sealprng.hip)
+int seal_uniform_launch(moai_ctx *c, const uint8_t *seeds, uint64_t *out, size_t stride_words, size_t count, size_t L,
+                        const RowMap &rows, uint32_t *cnt, uint32_t *rejected, hipStream_t s);
 
 } // namespace moai

@@ -417,6 +417,36 @@ static void key_state(const uint8_t *seed, uint64_t h[8])
     b2_compress(h, m, 128, false);
 }
 
+// moai_seal_sample_uniform after its checks, for a caller that holds op_mutex and owns the scratch (launch.h)
+int seal_uniform_launch(moai_ctx *c, const uint8_t *seeds, uint64_t *out, size_t stride_words, size_t count, size_t L,
+                        const RowMap &rows, uint32_t *cnt, uint32_t *rejected, hipStream_t s)
+{
+    const size_t LN = L * c->n;
+    MOAI_HIP_CHECK(hipMemsetAsync(cnt, 0, count * L * sizeof(uint32_t), s));
+    SealArgs a = {};
+    a.rows = rows;
+    a.stride = stride_words;
+    a.rejected = rejected;
+    a.pc = c->pc;
+    a.nbuf = (LN + SEAL_BUF_WORDS - 1) / SEAL_BUF_WORDS;
+    a.L = (uint32_t)L;
+    a.logn = (uint32_t)c->logn;
+    const uint32_t blocks = (uint32_t)((a.nbuf + 4 * SEAL_WAVE_BUFS - 1) / (4 * SEAL_WAVE_BUFS));
+    return for_chunks(count, SEAL_SEEDS, [&](size_t p0, size_t np) {
+        for (size_t p = 0; p < np; p++)
+        {
+            key_state(seeds + (p0 + p) * 64, a.h1[p]);
+        }
+        a.out = out + p0 * stride_words;
+        a.cnt = cnt + p0 * L;
+        hipLaunchKernelGGL(c->logn >= 9 ? seal_fill<FILL_WIDE> : seal_fill<FILL_NARROW>, dim3(blocks, (uint32_t)np), dim3(256), 0, s, a);
+        MOAI_LAUNCH_CHECK();
+        hipLaunchKernelGGL(seal_fixup, dim3((uint32_t)np), dim3(64), 0, s, a);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
+}
+
 } // namespace moai
 
 using namespace moai;
@@ -470,8 +500,8 @@ extern "C" int moai_seal_sample_uniform(moai_ctx *c, const uint8_t *seeds, uint6
 {
     MOAI_AUDIT(stream, out, rejected);
     trace_op("seal_sample_uniform", L, count);
-    SealArgs a = {};
-    MOAI_TRY(rows_entry(c, L, prime_index, &a.rows));
+    RowMap rows;
+    MOAI_TRY(rows_entry(c, L, prime_index, &rows));
     if (!seeds)
     {
         return set_error(MOAI_EINVAL, "null seed");
@@ -497,29 +527,8 @@ extern "C" int moai_seal_sample_uniform(moai_ctx *c, const uint8_t *seeds, uint6
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> op(*static_cast<std::mutex *>(c->op_mutex));
     void *ws = nullptr;
-    const size_t cnt_words = count * L;
-    MOAI_TRY(workspace(c, cnt_words * sizeof(uint32_t), s, &ws));
-    MOAI_HIP_CHECK(hipMemsetAsync(ws, 0, cnt_words * sizeof(uint32_t), s));
-    a.stride = stride_words;
-    a.rejected = rejected;
-    a.pc = c->pc;
-    a.nbuf = (LN + SEAL_BUF_WORDS - 1) / SEAL_BUF_WORDS;
-    a.L = (uint32_t)L;
-    a.logn = (uint32_t)c->logn;
-    const uint32_t blocks = (uint32_t)((a.nbuf + 4 * SEAL_WAVE_BUFS - 1) / (4 * SEAL_WAVE_BUFS));
-    return for_chunks(count, SEAL_SEEDS, [&](size_t p0, size_t np) {
-        for (size_t p = 0; p < np; p++)
-        {
-            key_state(seeds + (p0 + p) * 64, a.h1[p]);
-        }
-        a.out = out + p0 * stride_words;
-        a.cnt = static_cast<uint32_t *>(ws) + p0 * L;
-        hipLaunchKernelGGL(c->logn >= 9 ? seal_fill<FILL_WIDE> : seal_fill<FILL_NARROW>, dim3(blocks, (uint32_t)np), dim3(256), 0, s, a);
-        MOAI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(seal_fixup, dim3((uint32_t)np), dim3(64), 0, s, a);
-        MOAI_LAUNCH_CHECK();
-        return MOAI_OK;
-    });
+    MOAI_TRY(workspace(c, count * L * sizeof(uint32_t), s, &ws));
+    return seal_uniform_launch(c, seeds, out, stride_words, count, L, rows, static_cast<uint32_t *>(ws), rejected, s);
 }
 
 extern "C" int moai_check_residues(moai_ctx *c, const uint64_t *data, size_t n_poly, size_t L, const uint32_t *prime_index,

@@ -90,6 +90,8 @@ SYMBOLS = {
     "moai_expand_seeded": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp]),
     "moai_seal_prng_bytes": (C.c_int, [vp, C.c_char_p, C.c_uint64, C.c_uint64, vp, vp]),
     "moai_seal_sample_uniform": (C.c_int, [vp, C.c_char_p, vp, sz, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
+    "moai_encrypt_symmetric_seal_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
+    "moai_kswitch_keygen_seal_seeded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint64, vp, vp, vp, vp, vp]),
     "moai_check_residues": (C.c_int, [vp, vp, sz, sz, C.POINTER(C.c_uint32), vp, vp]),
     "moai_total_coeff_modulus_bit_count": (C.c_int, [vp, sz, C.POINTER(C.c_uint32)]),
     "moai_ckks_tables": (C.c_int, [vp, vp, vp]),
@@ -680,15 +682,54 @@ class Context:
             raise ValueError("a SEAL generator seed has 64 bytes")
         stride_words = L * self.n if stride_words is None else stride_words
         made = DeviceBuffer(max(len(seeds), 1) * stride_words) if out is None else None
+        flag = self._rejected_flag(count_rejected, stream)
+        _check(lib().moai_seal_sample_uniform(self.h, b"".join(seeds), _ptr(made if out is None else out), stride_words, len(seeds), L,
+                                              self._pidx(prime_index), _ptr(flag), stream))
+        return (made,) + self._rejected_words(flag, stream)
+
+    @staticmethod
+    def _rejected_flag(count_rejected, stream):
+        """a zeroed device uint32_t[2] for a `rejected` argument, or None"""
         flag = DeviceBuffer(1) if count_rejected else None
         if count_rejected:
             _check(lib().moai_memset_zero(flag.ptr, 8, stream))
-        _check(lib().moai_seal_sample_uniform(self.h, b"".join(seeds), _ptr(made if out is None else out), stride_words, len(seeds), L,
-                                              self._pidx(prime_index), _ptr(flag), stream))
-        if not count_rejected:
-            return made, None, None
+        return flag
+
+    @staticmethod
+    def _rejected_words(flag, stream):
+        """(rejected stream words, whether a tail ran over its bound), (None, None) without a flag"""
+        if flag is None:
+            return None, None
         word = int(flag.to_numpy(stream=stream)[0])
-        return made, word & 0xFFFFFFFF, bool(word >> 32)
+        return word & 0xFFFFFFFF, bool(word >> 32)
+
+    @staticmethod
+    def _seal_seeds(seeds, count):
+        seeds = [bytes(s) for s in seeds]
+        if len(seeds) != count or any(len(s) != 64 for s in seeds):
+            raise ValueError("%d SEAL generator seeds of 64 bytes each are needed" % count)
+        return b"".join(seeds)
+
+    def encrypt_symmetric_seal_seeded(self, noise_key, seeds, seq, sk_ntt, L, plain=None, prime_index=None, count_rejected=True,
+                                      stream=None):
+        """c0 [len(seeds)][L][N] of encrypt_symmetric with a of ciphertext b = SEAL's sample_poly_uniform of seeds[b] (64 bytes
+        each) and the noise from `noise_key`.  Returns (DeviceBuffer, rejected, overflow) as seal_sample_uniform does."""
+        n_batch = len(seeds)
+        out = DeviceBuffer(max(n_batch, 1) * L * self.n)
+        flag = self._rejected_flag(count_rejected, stream)
+        _check(lib().moai_encrypt_symmetric_seal_seeded(self.h, self._key(noise_key), self._seal_seeds(seeds, n_batch), int(seq),
+                                                        _ptr(sk_ntt), _ptr(plain), out.ptr, n_batch, L, self._pidx(prime_index),
+                                                        _ptr(flag), stream))
+        return (out,) + self._rejected_words(flag, stream)
+
+    def kswitch_keygen_seal_seeded(self, noise_key, seeds, seq, sk_ntt, new_key_ntt, count_rejected=True, stream=None):
+        """c0 [k-1][k][N] of the k-1 digits of the switching key for new_key_ntt, a of digit J from the SEAL seed seeds[J].
+        Returns (DeviceBuffer, rejected, overflow)."""
+        out = DeviceBuffer(max(self.k - 1, 1) * self.k * self.n)
+        flag = self._rejected_flag(count_rejected, stream)
+        _check(lib().moai_kswitch_keygen_seal_seeded(self.h, self._key(noise_key), self._seal_seeds(seeds, self.k - 1), int(seq),
+                                                     _ptr(sk_ntt), _ptr(new_key_ntt), out.ptr, _ptr(flag), stream))
+        return (out,) + self._rejected_words(flag, stream)
 
     def check_residues(self, data, n_poly, L, prime_index=None, stream=None):
         """True when a residue of data [n_poly][L][N] is >= its row's prime"""

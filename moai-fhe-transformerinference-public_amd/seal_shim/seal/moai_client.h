@@ -150,6 +150,15 @@ namespace seal
             return g;
         }
 
+        // Which generator the public half of a seeded object (a Serializable<T>) is the expansion of: this library's ChaCha20
+        // stream (the default, and the only kind its own wire format carries seeded), or SEAL's Blake2xbPRNG under a 64-byte seed
+        // per ciphertext or key digit, which save_seal then writes seeded as SEAL itself would (SEAL/ciphertext.cpp:190-381)
+        enum class seed_kind
+        {
+            chacha20,
+            seal_blake2xb
+        };
+
         // Randomness of the device samplers (include/moai_hip.h, "client randomness and encryption"): a 32-byte ChaCha20 key
         // drawn from the operating system, and an atomic counter that hands out disjoint ranges of nonce sequences, so that
         // every encryption or key digit drawn with this object uses a stream of its own, whichever thread asks.  Tests and
@@ -179,33 +188,68 @@ namespace seal
                 }
                 return first;
             }
+            // opt-in: the calls without a destination (Encryptor::encrypt_symmetric(plain), KeyGenerator::create_*_keys())
+            // return objects seeded for SEAL.  Noise and sequence numbers are what they are under the default.
+            void set_seed_kind(seed_kind kind)
+            {
+                kind_.store(kind);
+            }
+            seed_kind get_seed_kind() const
+            {
+                return kind_.load();
+            }
 
         private:
             unsigned char key_[32];
             std::atomic<std::uint64_t> next_{ 0 };
+            std::atomic<seed_kind> kind_{ seed_kind::chacha20 };
         };
+
+        // the first `words` 64-bit words, little endian, of the stream (noise key, purpose << 56 | seq)
+        inline void stream_head(const unsigned char *noise_key, std::uint64_t purpose, std::uint64_t seq, std::uint8_t *out, int words)
+        {
+            unsigned char init[40];
+            std::memcpy(init, noise_key, 32);
+            const std::uint64_t nonce = (purpose << 56) | seq;
+            for (int i = 0; i < 8; i++)
+            {
+                init[32 + i] = static_cast<unsigned char>(nonce >> (8 * i));
+            }
+            ChaCha20Rng g(init);
+            for (int w = 0; w < words; w++)
+            {
+                const std::uint64_t v = g();
+                for (int i = 0; i < 8; i++)
+                {
+                    out[8 * w + i] = static_cast<std::uint8_t>(v >> (8 * i));
+                }
+            }
+        }
 
         // The public seed of a seeded object (include/moai_hip.h, purpose 5): the first 32 bytes of the stream
         // (noise key, 5 << 56 | seq).  ChaCha20 output does not reveal its key, so the seed may travel where the key may not
         // (the reference draws its public seed from the secret generator the same way, SEAL/util/rlwe.cpp:353-363).
         inline void public_seed(const unsigned char *noise_key, std::uint64_t seq, std::uint8_t (&seed)[32])
         {
-            unsigned char init[40];
-            std::memcpy(init, noise_key, 32);
-            const std::uint64_t nonce = (std::uint64_t(5) << 56) | seq;
-            for (int i = 0; i < 8; i++)
+            stream_head(noise_key, 5, seq, seed, 4);
+        }
+        // The SEAL seeds of `count` consecutive objects (include/moai_hip.h, purpose 6): for the ciphertext or key digit with
+        // sequence seq + b the 64 bytes W[0..7] of the stream (noise key, 6 << 56 | seq + b)
+        inline std::vector<std::uint8_t> seal_seeds(const unsigned char *noise_key, std::uint64_t seq, std::size_t count)
+        {
+            std::vector<std::uint8_t> seeds(64 * count);
+            for (std::size_t b = 0; b < count; b++)
             {
-                init[32 + i] = static_cast<unsigned char>(nonce >> (8 * i));
+                stream_head(noise_key, 6, seq + b, seeds.data() + 64 * b, 8);
             }
-            ChaCha20Rng g(init);
-            for (int w = 0; w < 4; w++)
-            {
-                const std::uint64_t v = g();
-                for (int i = 0; i < 8; i++)
-                {
-                    seed[8 * w + i] = static_cast<std::uint8_t>(v >> (8 * i));
-                }
-            }
+            return seeds;
+        }
+        // a zeroed device uint32_t[2] for moai_seal_sample_uniform's `rejected`
+        inline std::shared_ptr<DeviceArray> seal_flags(void *stream)
+        {
+            auto f = std::make_shared<DeviceArray>(1, stream);
+            hip_check(moai_memset_zero(f->get(), 8, stream));
+            return f;
         }
 
         // uniform residues [rows][N], row r under primes[r]
@@ -290,6 +334,7 @@ namespace seal
             }
         }
     } // namespace util
+    using util::seed_kind;
 
     // =================================================================================================
     // CKKSEncoder  (SEAL/ckks.{h,cpp})
@@ -1006,6 +1051,10 @@ namespace seal
         // c0 of a key's digits: the whole key (record kind 9) at levels == k-1, otherwise the limited one (kind 10)
         wire::Record seeded_key_record(const std::uint64_t *new_key_ntt, std::size_t levels) const
         {
+            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
+            {
+                throw std::logic_error("a key limited to a chain index has no form in SEAL's format: generate it under seed_kind::chacha20");
+            }
             if (levels == k_ - 1)
             {
                 return seeded_record(wire::kind_kswitch_key, new_key_ntt);
@@ -1068,9 +1117,30 @@ namespace seal
             r.count = static_cast<std::uint32_t>(2 * count);
             r.L = static_cast<std::uint32_t>(k_);
             r.parms_id = context_.key_parms_id();
+            r.block = std::make_shared<util::DeviceArray>(count * k_ * n_, context_.stream());
+            r.data = r.block->get();
+            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
+            {
+                // the same sequences for the noise; a of digit J from the SEAL seed of sequence seq + J
+                const std::uint64_t seq = rng_->take(count);
+                r.seal_seeds = util::seal_seeds(rng_->key(), seq, count);
+                r.seal_flags = util::seal_flags(context_.stream());
+                std::uint32_t *rejected = reinterpret_cast<std::uint32_t *>(r.seal_flags->get());
+                if (new_key_ntt)
+                {
+                    util::hip_check(moai_kswitch_keygen_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq, sk_.ntt_->get(),
+                                                                    new_key_ntt, r.block->get(), rejected, context_.stream()));
+                }
+                else
+                {
+                    util::hip_check(moai_encrypt_symmetric_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq,
+                                                                       sk_.ntt_->get(), nullptr, r.block->get(), 1, k_, nullptr, rejected,
+                                                                       context_.stream()));
+                }
+                return r;
+            }
             r.seq = rng_->take(count);
             util::public_seed(rng_->key(), r.seq, r.seed);
-            r.block = std::make_shared<util::DeviceArray>(count * k_ * n_, context_.stream());
             if (new_key_ntt)
             {
                 util::hip_check(moai_kswitch_keygen_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), new_key_ntt,
@@ -1435,9 +1505,20 @@ namespace seal
             r.count = 2;
             r.L = static_cast<std::uint32_t>(L);
             r.parms_id = parms_id;
+            r.block = std::make_shared<util::DeviceArray>(L * context_.n(), context_.stream());
+            r.data = r.block->get();
+            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
+            {
+                const std::uint64_t seq = rng_->take(1);
+                r.seal_seeds = util::seal_seeds(rng_->key(), seq, 1);
+                r.seal_flags = util::seal_flags(context_.stream());
+                util::hip_check(moai_encrypt_symmetric_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq, sk_->get(), plain,
+                                                                   r.block->get(), 1, L, nullptr,
+                                                                   reinterpret_cast<std::uint32_t *>(r.seal_flags->get()), context_.stream()));
+                return o;
+            }
             r.seq = rng_->take(1);
             util::public_seed(rng_->key(), r.seq, r.seed);
-            r.block = std::make_shared<util::DeviceArray>(L * context_.n(), context_.stream());
             util::hip_check(moai_encrypt_symmetric_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_->get(), plain, r.block->get(),
                                                           1, L, nullptr, context_.stream()));
             r.data = r.block->get();

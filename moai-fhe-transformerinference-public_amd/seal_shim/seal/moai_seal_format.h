@@ -19,7 +19,9 @@
 // seeded halves of a ciphertext or of a whole switching key come from ONE moai_seal_sample_uniform (Blake2xb on the device); the
 // residue check (moai_check_residues) and the expansion's overflow word come back in one 16-byte copy.  A header that names zlib
 // or zstd is rejected as SEAL built without them rejects it, Shake256 seeds with SEAL's "unsupported prng_type".
-// Save: unseeded; what is seeded on this side (ChaCha20, which SEAL cannot expand) is expanded first.
+// Save: an object seeded with SEAL's own generator on this side (util::seed_kind::seal_blake2xb, wire::Record::seal_seeds) is
+// written seeded, polynomial 0 and UniformRandomGeneratorInfo with type byte 1 per ciphertext or key digit, as SEAL's save_seed
+// route writes it; what is seeded with ChaCha20, which SEAL cannot expand, is expanded first and written in full.
 #pragma once
 
 namespace seal
@@ -109,9 +111,18 @@ namespace seal
         }
 
         // ---- sizes --------------------------------------------------------------------------------------------------------
+        // a seeded Ciphertext / PublicKey: polynomial 0 and the generator's info (SEAL/ciphertext.cpp:190-247)
+        inline std::size_t seeded_ct_bytes(std::size_t LN)
+        {
+            return header_bytes + ct_member_bytes + dyn_bytes(LN) + prng_info_bytes;
+        }
         inline std::size_t record_bytes(const wire::Object &o, const wire::Record &r)
         {
             const std::size_t LN = r.L * moai_ctx_coeff_count(o.dev);
+            if (r.seal_seeded())
+            {
+                return r.stored() * seeded_ct_bytes(LN);
+            }
             return header_bytes + (is_plain(r.kind) ? pt_member_bytes + dyn_bytes(LN) : ct_member_bytes + dyn_bytes(r.count * LN));
         }
         inline std::size_t slots(const wire::Object &o)
@@ -141,7 +152,12 @@ namespace seal
             }
             const std::size_t n = moai_ctx_coeff_count(o.dev), k = o.head.L;
             const std::size_t digit = header_bytes + ct_member_bytes + dyn_bytes(2 * k * n);
-            return header_bytes + 32 + 8 + 8 * slots(o) + o.keys.size() * (k - 1) * digit;
+            std::size_t bytes = header_bytes + 32 + 8 + 8 * slots(o);
+            for (auto &r : o.keys)
+            {
+                bytes += (k - 1) * (r.seal_seeded() ? seeded_ct_bytes(k * n) : digit);
+            }
+            return bytes;
         }
 
         // ---- save ---------------------------------------------------------------------------------------------------------
@@ -156,12 +172,13 @@ namespace seal
             util::hip_check(moai_stream_sync(o.stream));
             sink.commit();
         }
-        // one Ciphertext / PublicKey: `polys` polynomials of L rows at dev_words
+        // one Ciphertext / PublicKey: `polys` polynomials of L rows at dev_words; seal_seed: polynomial 0 alone is there and stored,
+        // followed by UniformRandomGeneratorInfo { blake2xb, the 64 bytes }
         inline void put_ct(const wire::Object &o, const std::uint64_t *dev_words, std::size_t polys, std::size_t L, bool ntt, double scale,
-                           wire::Sink &sink)
+                           wire::Sink &sink, const std::uint8_t *seal_seed = nullptr)
         {
-            const std::size_t n = moai_ctx_coeff_count(o.dev);
-            const Header h = make_seal_header(header_bytes + ct_member_bytes + dyn_bytes(polys * L * n));
+            const std::size_t n = moai_ctx_coeff_count(o.dev), stored = seal_seed ? 1 : polys;
+            const Header h = make_seal_header(seal_seed ? seeded_ct_bytes(L * n) : header_bytes + ct_member_bytes + dyn_bytes(polys * L * n));
             sink.put(&h, sizeof(h));
             const parms_id_type id = id_of(o.dev, L);
             const std::uint8_t ntt_byte = ntt ? 1 : 0;
@@ -171,11 +188,32 @@ namespace seal
             sink.put(f, 24);
             sink.put(&scale, 8);
             sink.put(&correction, 8);
-            put_data(o, dev_words, polys * L * n, sink);
+            put_data(o, dev_words, stored * L * n, sink);
+            if (seal_seed)
+            {
+                const Header info = make_seal_header(prng_info_bytes);
+                const std::uint8_t type = 1; // prng_type::blake2xb
+                sink.put(&info, sizeof(info));
+                sink.put(&type, 1);
+                sink.put(seal_seed, 64);
+            }
         }
         inline void put_record(const wire::Object &o, const wire::Record &r, wire::Sink &sink)
         {
             const std::size_t n = moai_ctx_coeff_count(o.dev), LN = r.L * n;
+            if (r.seal_seeded())
+            {
+                // seeded with SEAL's generator: every ciphertext or key digit goes out as polynomial 0 and its seed
+                const wire::SealOverflow overflow(o, r);
+                for (std::size_t j = 0; j < r.stored(); j++)
+                {
+                    const bool key = r.kind == wire::kind_kswitch_key;
+                    put_ct(o, r.data + j * LN, 2, r.L, key || (r.flags & wire::flag_ntt) != 0, key ? 1.0 : r.scale, sink,
+                           r.seal_seeds.data() + 64 * j);
+                    overflow.settle(); // put_ct has synchronised
+                }
+                return;
+            }
             // seeded on this side: ChaCha20, which SEAL cannot expand
             const std::uint64_t *data = r.data;
             util::DeviceArray full;

@@ -18,6 +18,9 @@
 //             L = levels + 1 rows packed under the primes {0 .. levels-1, k-1}, parms_id of the key level; seeded: the odd
 //             polynomials are moai_expand_seeded_limited of the seed (stream positions of the full k-row draw)
 //
+//   SEAL seeds : an object made under util::seed_kind::seal_blake2xb (Record::seal_seeds) has no seeded form here.  save expands
+//             it first (moai_seal_sample_uniform) and writes the unseeded record; save_seal writes SEAL's seeded layout.
+//
 // Everything that touches residues runs on the device: pack + one device-to-host copy on save; one host-to-device copy +
 // unpack (with the residue check of is_data_valid_for folded in) + expand on load.
 #pragma once
@@ -53,11 +56,20 @@ namespace seal
             parms_id_type parms_id = parms_id_zero;
             std::uint64_t seq = 0;
             std::uint8_t seed[32] = {};
+            // seeded for SEAL instead (util::seed_kind::seal_blake2xb): 64 bytes per stored polynomial b, of which polynomial
+            // 2 b + 1 is sample_poly_uniform; seq and seed stay zero.  seal_flags: the device uint32_t[2] the generating call
+            // counted its rejections into (moai_seal_sample_uniform's `rejected`), read back when the object is saved
+            std::vector<std::uint8_t> seal_seeds;
+            std::shared_ptr<util::DeviceArray> seal_flags;
             std::shared_ptr<util::DeviceArray> block; // owner of `data`, where the record has one of its own
             const std::uint64_t *data = nullptr;      // device [stored()][L][N]; after a load: all `count` polynomials
             std::size_t stored() const
             {
                 return (flags & flag_seeded) ? count / 2 : count;
+            }
+            bool seal_seeded() const
+            {
+                return !seal_seeds.empty();
             }
         };
         // what save writes and load reads: one record, or a key set
@@ -237,7 +249,8 @@ namespace seal
         }
         inline std::size_t record_bytes(moai_ctx *dev, const Record &r)
         {
-            return sizeof(Header) + (r.stored() ? r.stored() * packed_words(dev, r.L, record_rows(dev, r.kind, r.L)) * 8 : 0);
+            const std::size_t polys = r.seal_seeded() ? r.count : r.stored(); // SEAL seeds are expanded on the way out
+            return sizeof(Header) + (polys ? polys * packed_words(dev, r.L, record_rows(dev, r.kind, r.L)) * 8 : 0);
         }
         inline std::size_t object_bytes(const Object &o)
         {
@@ -272,9 +285,51 @@ namespace seal
             std::memcpy(h.seed, r.seed, 32);
             return h;
         }
-        inline void put_record(const Object &o, const Record &r, Sink &sink)
+        // what the generating call left in a SEAL-seeded record's overflow word, enqueued before a synchronisation and judged
+        // after it: a seed whose replacements ran over their bound (what the loader's expansion raises for such a seed)
+        struct SealOverflow
+        {
+            std::uint32_t f[2] = { 0, 0 };
+            SealOverflow(const Object &o, const Record &r)
+            {
+                if (r.seal_seeded() && r.seal_flags)
+                {
+                    util::hip_check(moai_memcpy_d2h(f, r.seal_flags->get(), 8, o.stream));
+                }
+            }
+            void settle() const
+            {
+                if (f[1])
+                {
+                    throw std::logic_error("ciphertext data is invalid");
+                }
+            }
+        };
+        // all `count` polynomials of a SEAL-seeded record: c0 copied, the uniform halves from moai_seal_sample_uniform
+        inline void expand_seal_seeded(const Object &o, const Record &r, util::DeviceArray &full)
+        {
+            const std::size_t LN = r.L * moai_ctx_coeff_count(o.dev);
+            full.resize(r.count * LN, o.stream);
+            for (std::size_t b = 0; b < r.stored(); b++)
+            {
+                util::hip_check(moai_memcpy_d2d(full.get() + 2 * b * LN, r.data + b * LN, LN * 8, o.stream));
+            }
+            util::hip_check(moai_seal_sample_uniform(o.dev, r.seal_seeds.data(), full.get() + LN, 2 * LN, r.stored(), r.L, nullptr, nullptr,
+                                                     o.stream));
+        }
+        inline void put_record(const Object &o, const Record &r0, Sink &sink)
         {
             const std::size_t n = moai_ctx_coeff_count(o.dev);
+            Record r = r0;
+            util::DeviceArray full;
+            const SealOverflow overflow(o, r0);
+            if (r0.seal_seeded())
+            {
+                expand_seal_seeded(o, r0, full);
+                r.flags &= ~flag_seeded;
+                r.seal_seeds.clear();
+                r.data = full.get();
+            }
             const Header h = make_header(r, n, record_bytes(o.dev, r));
             sink.put(&h, sizeof(h));
             if (!r.stored())
@@ -289,6 +344,7 @@ namespace seal
             std::uint8_t *dst = sink.space(words * 8);
             util::hip_check(moai_memcpy_d2h(dst, packed.get(), words * 8, o.stream));
             util::hip_check(moai_stream_sync(o.stream));
+            overflow.settle();
             sink.commit();
         }
         inline std::streamoff save_object(const Object &o, Sink &sink)
@@ -514,7 +570,8 @@ namespace seal
     } // namespace sealfmt
 
     // SEAL/serializable.h: an object that can only be saved -- what the seeded encryptions and key generators return.  It holds
-    // c0 of every ciphertext or key digit and the public seed; the uniform halves are never produced on this side.
+    // c0 of every ciphertext or key digit and the public seed (ChaCha20: one per object; SEAL's Blake2xb: one per ciphertext or
+    // digit); the uniform halves are not kept on this side.
     template <class T>
     class Serializable
     {
@@ -536,7 +593,8 @@ namespace seal
             wire::BufferSink s(out, size);
             return wire::save_object(obj_, s);
         }
-        // SEAL's own format, unseeded: SEAL cannot expand a seed of this side (ChaCha20), so the object is expanded first
+        // SEAL's own format: seeded as SEAL writes it when the object was made under util::seed_kind::seal_blake2xb; otherwise
+        // unseeded, because SEAL cannot expand a ChaCha20 seed, so the object is expanded first
         std::streamoff save_size_seal(compr_mode_type compr_mode = compr_mode_default) const
         {
             wire::check_mode(compr_mode);
