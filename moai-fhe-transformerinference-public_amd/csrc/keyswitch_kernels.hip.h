@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
     const PrimeConst *pc = a.pc + prime;
     const uint64_t *in = a.t + (((size_t)b * a.L + J) << LOGN);
     uint64_t *out = a.tmp + ((((size_t)b * a.G + g) * a.L + J) << LOGN);
-    if (MODE >= M_FPN)
+    if (mode_fp(MODE))
     {
         // FP64 modes: the conversion to a double reduces modulo q_I on the way; a digit of 53 bits and more
         // (its own prime is an integer-mode one) takes an integer Barrett step first.  Workgroup-uniform.
@@ -79,11 +79,11 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
             op.qinv = pc->qinv;
             if constexpr (ITEMS > 1)
             {
-                fwd_strided_tiles<LOGN, LoadBarrettFp, MODE, ITEMS>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->qd, pc->qinv, lds, threadIdx.x, op);
+                fwd_strided_tiles<LOGN, LoadBarrettFp, MODE, ITEMS>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op);
             }
             else
             {
-                fwd_strided_tile<LOGN, LoadBarrettFp, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->qd, pc->qinv, lds, threadIdx.x, op,
+                fwd_strided_tile<LOGN, LoadBarrettFp, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op,
                                                                  PRE ? a.tw1 + ((size_t)prime << LOGN) : nullptr);
             }
         }
@@ -94,11 +94,11 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
             op.qinv = pc->qinv;
             if constexpr (ITEMS > 1)
             {
-                fwd_strided_tiles<LOGN, LoadFp52, MODE, ITEMS>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->qd, pc->qinv, lds, threadIdx.x, op);
+                fwd_strided_tiles<LOGN, LoadFp52, MODE, ITEMS>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op);
             }
             else
             {
-                fwd_strided_tile<LOGN, LoadFp52, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->qd, pc->qinv, lds, threadIdx.x, op,
+                fwd_strided_tile<LOGN, LoadFp52, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op,
                                                             PRE ? a.tw1 + ((size_t)prime << LOGN) : nullptr);
             }
         }
@@ -110,11 +110,11 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
         LoadBarrett op;
         op.q = pc->q;
         op.cr1 = pc->cr1;
-        fwd_strided_tile<LOGN, LoadBarrett, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->q, pc->q2, lds, threadIdx.x, op);
+        fwd_strided_tile<LOGN, LoadBarrett, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op);
     }
     else
     {
-        fwd_strided_tile<LOGN, LoadIdentity, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), pc->q, pc->q2, lds, threadIdx.x);
+        fwd_strided_tile<LOGN, LoadIdentity, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x);
     }
 }
 
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
     __shared__ ulonglong2 lds_b2[1024];
     // FP64 modes: the seven twiddles of stages 0..2 per 256-block ([block][8] doubles) -- the same for every digit of the loop
     // and for the block's 32 threads: fetched once per workgroup, read from LDS in every iteration instead of seven global loads
-    constexpr bool TW012 = MODE >= M_FPN;
+    constexpr bool TW012 = mode_fp(MODE);
     __shared__ double lds_tw[TW012 ? 64 : 1];
     uint64_t *lds_a = reinterpret_cast<uint64_t *>(lds_a2);
     uint64_t *lds_b = reinterpret_cast<uint64_t *>(lds_b2);
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
     // depend on the prime, the tile and the thread only) -- 26 registers instead of 13 loads behind the two LDS
     // barriers of every iteration
     double twr[13];
-    if (MODE >= M_FPN)
+    if (mode_fp(MODE))
     {
         const uint32_t b = tid0 >> 5, r = tid0 & 31u, hi3 = r >> 2;
         const uint32_t blk = (tile << 3) + b;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
         const ulonglong2 *__restrict__ k1 =
             reinterpret_cast<const ulonglong2 *>(a.key + (((size_t)(J * 2 + 1) * a.k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
         ulonglong2 kpa[4], kpb[4];
-        if (MODE >= M_FPN && PF == 2)
+        if (mode_fp(MODE) && PF == 2)
         {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -283,8 +283,8 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
             {
                 ulonglong2 v = trow[c];
                 // FP64 modes: as doubles, like the values the butterflies leave (canonical below q: nothing to fold)
-                x[2 * c] = MODE >= M_FPN ? d2u(fp_from_u52(v.x)) : v.x;
-                x[2 * c + 1] = MODE >= M_FPN ? d2u(fp_from_u52(v.y)) : v.y;
+                x[2 * c] = mode_fp(MODE) ? d2u(fp_from_u52(v.x)) : v.x;
+                x[2 * c + 1] = mode_fp(MODE) ? d2u(fp_from_u52(v.y)) : v.y;
             }
         }
         else
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
             {
                 if (!(j & half))
                 {
-                    if (MODE >= M_FPN)
+                    if (mode_fp(MODE))
                     {
                         ct_bfly_fp1_sel(x[j], x[j + half], lds_tw[(b << 3) + ((1u << u) - 1u) + (uint32_t)(j >> (3 - u))], u2d(bq1), u2d(bq2),
                                         MODE == M_FPR && !(u & 1));
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
                 if (!(j & half))
                 {
                     uint32_t t_ = (hi3 << 5) | ((uint32_t)j << 2) | lo2;
-                    if (MODE >= M_FPN)
+                    if (mode_fp(MODE))
                     {
                         ct_bfly_fp1_sel(x[j], x[j + half], twr[(u == 3) ? 0 : (u == 4) ? 1 + (j >> 2) : 3 + (j >> 1)], u2d(bq1), u2d(bq2), MODE == M_FPR && !(u & 1));
                     }
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
                 if (!(j & half))
                 {
                     uint32_t t_ = (r << 3) | (uint32_t)j;
-                    if (MODE >= M_FPN)
+                    if (mode_fp(MODE))
                     {
                         ct_bfly_fp1_sel(x[j], x[j + half], twr[(u == 6) ? 7 + (j >> 2) : 9 + (j >> 1)], u2d(bq1), u2d(bq2), MODE == M_FPR && !(u & 1));
                     }
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
         // M_FPN (33 q < 2^52, context.hip build_prime) takes the digit as the butterflies left it, its products are below 2.5 q
         // (bounds below), and it adds sixteen
         const bool fold = MODE == M_FPR ? ((J - j0) % 3u == 2u) : (((J - j0) & 15u) == 15u);
-        if (MODE >= M_FPN && PF != 0)
+        if (mode_fp(MODE) && PF != 0)
         {
             // the same products and sums as below, in the same order per accumulator: the same bits.
             // The digit value enters the products as the butterflies left it in M_FPN (below 33q < 2^52: the quotient estimate of
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
                 lo1[2 * c + 1] = d2u(sm[4 * c + 3]);
             }
         }
-        else if (MODE >= M_FPN)
+        else if (mode_fp(MODE))
         {
             // FP64 modes: the MAC stays on the FP64 pipe as well (fp_mulmod_q with the key residue canonical, below 2^51; the
             // digit folded to |v| <= q/2 first in M_FPR, as it comes in M_FPN -- bounds above), each product is reduced
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
     for (int c = 0; c < 4; ++c)
     {
         ulonglong2 r0, r1;
-        if (MODE >= M_FPN)
+        if (mode_fp(MODE))
         {
             const double qd = u2d(bq1), qinv = u2d(bq2);
             r0.x = fp_to_canonical(u2d(lo0[2 * c]), qd, qinv);
@@ -1011,7 +1011,8 @@ __global__ __launch_bounds__(256, 4) void moddown_strided(ModDownArgs a)
     const uint64_t fix = pc->q - barrett64(half, pc->q, pc->cr1);
     const uint64_t *in = a.last + ((size_t)p << LOGN);
     uint64_t *outp = a.u + (((size_t)p * a.Lout + i) << LOGN);
-    if (MODE >= M_FPN)
+    const uint64_t bq1 = mode_q<MODE>(*pc), bq2 = mode_q2<MODE>(*pc); // the butterflies' (q, q2) under MODE
+    if (mode_fp(MODE))
     {
         LoadExpandLastFp op;
         op.ql = ql;
@@ -1021,7 +1022,7 @@ __global__ __launch_bounds__(256, 4) void moddown_strided(ModDownArgs a)
         op.fix = fix;
         op.qd = pc->qd;
         op.qinv = pc->qinv;
-        fwd_strided_tile<LOGN, LoadExpandLastFp, MODE>(in, outp, tile, a.tw + ((size_t)i << LOGN), pc->qd, pc->qinv, lds, threadIdx.x, op);
+        fwd_strided_tile<LOGN, LoadExpandLastFp, MODE>(in, outp, tile, a.tw + ((size_t)i << LOGN), bq1, bq2, lds, threadIdx.x, op);
     }
     else
     {
@@ -1031,7 +1032,7 @@ __global__ __launch_bounds__(256, 4) void moddown_strided(ModDownArgs a)
         op.q = pc->q;
         op.cr1 = pc->cr1;
         op.fix = fix;
-        fwd_strided_tile<LOGN, LoadExpandLast, MODE>(in, outp, tile, a.tw + ((size_t)i << LOGN), pc->q, pc->q2, lds, threadIdx.x, op);
+        fwd_strided_tile<LOGN, LoadExpandLast, MODE>(in, outp, tile, a.tw + ((size_t)i << LOGN), bq1, bq2, lds, threadIdx.x, op);
     }
 }
 

@@ -96,7 +96,7 @@ int enter_device(const moai_ctx *c);
 int ntt_mode(const moai_ctx *c, uint32_t prime, bool allow_fp = true);
 // the kernel class of the plain tiled transform for a row under a context prime (ntt.hip launch_fwd / launch_inv):
 // forward M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN or M_FPR; inverse M_LAZY16, M_LAZY8, M_GUARD (the exact integer
-// butterflies), M_FPN or M_FPR
+// butterflies), M_FPN or M_FPR.  In both directions the class is the MODE the kernels are instantiated with.
 int fwd_class(const moai_ctx *c, uint32_t prime);
 int inv_class(const moai_ctx *c, uint32_t prime);
 // the twiddle tables of a mode: tw in natural order, twb in the contiguous pass's per-thread order

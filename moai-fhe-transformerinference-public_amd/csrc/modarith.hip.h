@@ -176,6 +176,16 @@ enum
     M_FPN = 2,     // FP64, 33 q < 2^52 (context.hip build_prime): sixteen stages need no intermediate reduction
     M_FPR = 3      // FP64, q < 2^51: the untouched operand of every butterfly is reduced first
 };
+// the modes whose butterflies take (2^64 - q, 2^64 - 4q)
+constexpr bool mode_lazy(int mode)
+{
+    return mode == M_LAZY8 || mode == M_LAZY16;
+}
+// the modes whose butterflies take the bit patterns of (double q, 1/q) and work on doubles
+constexpr bool mode_fp(int mode)
+{
+    return mode == M_FPN || mode == M_FPR;
+}
 
 __device__ __forceinline__ double u2d(uint64_t b)
 {
@@ -480,9 +490,6 @@ __device__ __forceinline__ int lazy16_inv_kind(uint32_t xk, int i, int j, int ha
     return (i > 0 && (j & (half >> 1))) ? 0 : (int)((xk >> i) & 1u);
 }
 
-template <bool LZ>
-__device__ __forceinline__ void gs_bfly_sel(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t a, uint64_t b);
-
 // STAGES_LEFT = number of stages after this one (compile-time in the unrolled tiles): M_GUARD2 guards the stages
 // with an even number left, so the last stage of a transform is guarded and hands over values below 6q
 template <int MODE, int STAGES_LEFT = 0>
@@ -533,18 +540,6 @@ __device__ __forceinline__ void gs_bfly_last(uint64_t &x, uint64_t &y, const Tw 
     y = mul_shoup_lazy(u + q2 - v, ninv_w1.w, ninv_w1.wq, q);
 }
 
-// (a, b) = (q, 2q) for the exact butterflies, (2^64 - q, 2^64 - 4q) for the M_LAZY8 ones
-template <>
-__device__ __forceinline__ void gs_bfly_sel<false>(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t a, uint64_t b)
-{
-    gs_bfly(x, y, w, wq, a, b);
-}
-template <>
-__device__ __forceinline__ void gs_bfly_sel<true>(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t a, uint64_t b)
-{
-    gs_bfly_lazy8(x, y, w, wq, a, b);
-}
-
 // ---- inverse transform in exact FP64 arithmetic (primes below 2^51; the scheme of the forward M_FPN / M_FPR modes) ----------
 // Gentleman-Sande butterfly on doubles holding integers: x' = u + v, y' = (u - v) w mod q with the product reduced at once
 // (fp_mulmod: exact for |u - v| < 2^52).  The sums double from stage to stage, the products come out below 1.5 q:
@@ -590,17 +585,41 @@ __device__ __forceinline__ void gs_bfly_last_fp(uint64_t &xb, uint64_t &yb, doub
     xb = d2u(fp_mulmod_q(s, ninv, q, qi));
     yb = d2u(fp_mulmod_q(d, ninv_w1, q, qi));
 }
-// IM: 0 exact integer [0, 2q), 1 M_LAZY8, 2 FPN, 3 FPR; (a, b) = the mode's two constants
-template <int IM>
-__device__ __forceinline__ void gs_bfly_im(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t a, uint64_t b, const bool redsum)
+// The inverse butterfly of MODE with (q, q2) = the mode's two constants (ntt_kernels.hip.h mode_q / mode_q2); redsum: M_FPN's fold
+// of the sum.  M_LAZY16 chooses between its two per butterfly (ntt_kernels.hip.h gs_bfly_tile); M_GUARD2 and M_NOGUARD have none.
+template <int MODE>
+__device__ __forceinline__ void gs_bfly_t(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t q, uint64_t q2, const bool redsum)
 {
-    if (IM >= 2)
+    static_assert(MODE == M_GUARD || MODE == M_LAZY8 || mode_fp(MODE), "no inverse butterfly of this mode");
+    if (MODE == M_LAZY8)
     {
-        gs_bfly_fp<IM == 3>(x, y, w, wq, a, b, redsum);
+        gs_bfly_lazy8(x, y, w, wq, q, q2);
+    }
+    else if (mode_fp(MODE))
+    {
+        gs_bfly_fp<MODE == M_FPR>(x, y, w, wq, q, q2, redsum);
     }
     else
     {
-        gs_bfly_sel<IM == 1>(x, y, w, wq, a, b);
+        gs_bfly(x, y, w, wq, q, q2);
+    }
+}
+// the same for the last stage of the transform, N^-1 folded in
+template <int MODE>
+__device__ __forceinline__ void gs_bfly_last_t(uint64_t &x, uint64_t &y, const Tw &ninv, const Tw &ninv_w1, uint64_t q, uint64_t q2)
+{
+    static_assert(MODE == M_GUARD || MODE == M_LAZY8 || mode_fp(MODE), "no inverse butterfly of this mode");
+    if (MODE == M_LAZY8)
+    {
+        gs_bfly_last_lazy8(x, y, ninv, ninv_w1, q, q2);
+    }
+    else if (mode_fp(MODE))
+    {
+        gs_bfly_last_fp<MODE == M_FPR>(x, y, fp_from_u64(ninv.w), fp_from_u64(ninv_w1.w), u2d(q), u2d(q2));
+    }
+    else
+    {
+        gs_bfly_last(x, y, ninv, ninv_w1, q, q2);
     }
 }
 

@@ -24,7 +24,7 @@ int ntt_mode(const moai_ctx *c, uint32_t prime, bool allow_fp)
 
 TwPair twiddles(const moai_ctx *c, int mode, bool inverse)
 {
-    if (mode >= M_FPN)
+    if (mode_fp(mode))
     {
         return inverse ? TwPair{ c->inv_twf, c->inv_twfb } : TwPair{ c->fwd_twf, c->fwd_twfb };
     }
@@ -60,7 +60,7 @@ int fwd_class(const moai_ctx *c, uint32_t prime)
 int inv_class(const moai_ctx *c, uint32_t prime)
 {
     const int m = ntt_mode(c, prime);
-    if (m >= M_FPN)
+    if (mode_fp(m))
     {
         return m;
     }
@@ -91,14 +91,10 @@ NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, con
     return a;
 }
 
+// the forward pair of launches of one class; `a` selects its rows and carries its tables and grid size
 template <int LOGN, int MODE>
-static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
+static void launch_fwd_mode(const NttArgs &a, hipStream_t s)
 {
-    constexpr uint32_t tpr = 1u << (LOGN - 12);
-    a.total_work = a.n_poly * a.Lsel * tpr;
-    const TwPair t = twiddles(c, MODE, false);
-    a.tw = t.tw;
-    a.twb = t.twb;
     // (the software-pipelined strided pass of the key switch, fwd_strided_tiles, does not pay here: measured in round 3 on 256 x 2
     // polynomials, 11.25 against 11.37 ms with the bench's 60-bit primes and 7.77 against 7.40 ms -- slower -- with MOAI's FP64
     // rows.  An in-place transform reads as much as it writes and has no cached operand; five resident workgroups of one tile
@@ -122,76 +118,69 @@ static void launch_fwd_mode(const moai_ctx *c, NttArgs a, hipStream_t s)
     }
 }
 
-// forward transform: the rows are split by the arithmetic their prime allows (fwd_class) and every class gets its own pair of
-// launches
-template <int LOGN>
-static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
+// a.sel / a.selp / a.Lsel = the rows of `a` (and their primes) whose class -- fwd_class or inv_class -- is `mode`
+static void select_class(const moai_ctx *c, int (*row_class)(const moai_ctx *, uint32_t), int mode, NttArgs &a)
 {
-    for (int mode : { M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR })
+    a.Lsel = 0;
+    for (uint32_t r = 0; r < a.L; ++r)
+    {
+        const uint32_t prime = a.rows.idx[r];
+        if (row_class(c, prime) == mode)
+        {
+            a.selp.idx[a.Lsel] = prime;
+            a.sel.idx[a.Lsel++] = r;
+        }
+    }
+}
+
+// The rows are split by the arithmetic their prime allows and every class that has rows gets its own pair of launches, in the
+// order of MODES, with the tables of its mode.
+template <int LOGN, bool INV, int... MODES>
+static int launch_classes(const moai_ctx *c, const NttArgs &base, hipStream_t s)
+{
+    for (int mode : { MODES... })
     {
         NttArgs a = base;
-        a.Lsel = 0;
-        for (uint32_t r = 0; r < a.L; ++r)
-        {
-            const uint32_t prime = a.rows.idx[r];
-            if (fwd_class(c, prime) == mode)
-            {
-                a.selp.idx[a.Lsel] = prime;
-                a.sel.idx[a.Lsel++] = r;
-            }
-        }
+        select_class(c, INV ? inv_class : fwd_class, mode, a);
         if (a.Lsel == 0)
         {
             continue;
         }
-        MOAI_TRY((dispatch<M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR>("forward transform mode ", mode, [&](auto MD) {
-            launch_fwd_mode<LOGN, decltype(MD)::value>(c, a, s);
+        const TwPair t = twiddles(c, mode, INV);
+        a.tw = t.tw;
+        a.twb = t.twb;
+        a.total_work = a.n_poly * a.Lsel * (1u << (LOGN - 12));
+        MOAI_TRY((dispatch<MODES...>(INV ? "inverse transform mode " : "forward transform mode ", mode, [&](auto MD) {
+            constexpr int MODE = decltype(MD)::value;
+            if constexpr (INV)
+            {
+                hipLaunchKernelGGL((ntt_inv_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+                hipLaunchKernelGGL((ntt_inv_strided<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+            }
+            else
+            {
+                launch_fwd_mode<LOGN, MODE>(a, s);
+            }
             return MOAI_OK;
         })));
     }
     return MOAI_OK;
 }
 
-// inverse transform: rows of primes below 2^51 run in exact FP64 arithmetic like the forward transform (FPN / FPR, modarith.hip.h
-// gs_bfly_fp; MOAI_NTT_FP=0 keeps them on the integer units), rows of primes below 2^60 take the integer butterflies with the
-// approximate Shoup quotient (M_LAZY16, or M_LAZY8), the others the exact ones; one pair of launches per class, same residues
-template <int LOGN, int IM>
-static void launch_inv_class(NttArgs a, hipStream_t s)
+// forward transform: the classes of fwd_class
+template <int LOGN>
+static int launch_fwd(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    constexpr uint32_t tpr = 1u << (LOGN - 12);
-    if (!a.Lsel)
-    {
-        return;
-    }
-    a.total_work = a.n_poly * a.Lsel * tpr;
-    hipLaunchKernelGGL((ntt_inv_contig<LOGN, IM>), dim3(a.total_work), dim3(256), 0, s, a);
-    hipLaunchKernelGGL((ntt_inv_strided<LOGN, IM>), dim3(a.total_work), dim3(256), 0, s, a);
+    return launch_classes<LOGN, false, M_LAZY16, M_LAZY8, M_GUARD2, M_NOGUARD, M_FPN, M_FPR>(c, base, s);
 }
 
+// inverse transform, the classes of inv_class: rows of primes below 2^51 run in exact FP64 arithmetic like the forward transform
+// (M_FPN / M_FPR, modarith.hip.h gs_bfly_fp; MOAI_NTT_FP=0 keeps them on the integer units), rows of primes below 2^60 take the
+// integer butterflies with the approximate Shoup quotient (M_LAZY16, or M_LAZY8), the others the exact ones (M_GUARD); same residues
 template <int LOGN>
-static void launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
+static int launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
 {
-    NttArgs cls[5] = { base, base, base, base, base }; // exact, lazy8, FPN, FPR, lazy16
-    for (NttArgs &a : cls)
-    {
-        a.Lsel = 0;
-    }
-    const TwPair fp = twiddles(c, M_FPN, true);
-    cls[2].tw = cls[3].tw = fp.tw;
-    cls[2].twb = cls[3].twb = fp.twb;
-    for (uint32_t r = 0; r < base.L; ++r)
-    {
-        const uint32_t prime = base.rows.idx[r];
-        const int m = inv_class(c, prime);
-        NttArgs &dst = m == M_FPN ? cls[2] : (m == M_FPR ? cls[3] : (m == M_LAZY16 ? cls[4] : (m == M_LAZY8 ? cls[1] : cls[0])));
-        dst.selp.idx[dst.Lsel] = prime;
-        dst.sel.idx[dst.Lsel++] = r;
-    }
-    launch_inv_class<LOGN, 0>(cls[0], s);
-    launch_inv_class<LOGN, 1>(cls[1], s);
-    launch_inv_class<LOGN, 2>(cls[2], s);
-    launch_inv_class<LOGN, 3>(cls[3], s);
-    launch_inv_class<LOGN, IM_LAZY16>(cls[4], s);
+    return launch_classes<LOGN, true, M_GUARD, M_LAZY8, M_FPN, M_FPR, M_LAZY16>(c, base, s);
 }
 
 // single-launch transform (ntt_coop); its queue state lives in a per-stream arena
@@ -419,12 +408,7 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
         }
         a.n_poly = (uint32_t)(n_poly - p0 < chunk ? n_poly - p0 : chunk);
         rc = dispatch_logn(logn, [&](auto LG) {
-            if (inverse)
-            {
-                launch_inv<decltype(LG)::value>(c, a, cs);
-                return MOAI_OK;
-            }
-            return launch_fwd<decltype(LG)::value>(c, a, cs);
+            return inverse ? launch_inv<decltype(LG)::value>(c, a, cs) : launch_fwd<decltype(LG)::value>(c, a, cs);
         });
     }
     if (pipe)

@@ -92,24 +92,17 @@ struct NttArgs
     uint32_t lds_twiddles; // forward contiguous pass: the first four stages' twiddles through LDS (MOAI_NTT_LDSTW=0: global loads)
 };
 
-// the modes whose butterflies take (2^64 - q, 2^64 - 4q)
-constexpr bool mode_lazy(int mode)
-{
-    return mode == M_LAZY8 || mode == M_LAZY16;
-}
-// inverse passes: IM = 0 exact integer, 1 M_LAZY8, 2 / 3 FP64 (FPN / FPR), IM_LAZY16 = M_LAZY16
-constexpr int IM_LAZY16 = -1;
-
-// (q, q2) arguments of a tile function under MODE: the integer pair, or the bit patterns of (double q, 1/q)
+// (q, q2) arguments of a tile function under MODE, forward or inverse: the integer pair (q, 2q), its lazy form
+// (2^64 - q, 2^64 - 4q), or the bit patterns of (double q, 1/q)
 template <int MODE>
 __device__ __forceinline__ uint64_t mode_q(const PrimeConst &pc)
 {
-    return MODE >= M_FPN ? pc.qd : (mode_lazy(MODE) ? pc.nq : pc.q);
+    return mode_fp(MODE) ? pc.qd : (mode_lazy(MODE) ? pc.nq : pc.q);
 }
 template <int MODE>
 __device__ __forceinline__ uint64_t mode_q2(const PrimeConst &pc)
 {
-    return MODE >= M_FPN ? pc.qinv : (mode_lazy(MODE) ? pc.n4q : pc.q2);
+    return mode_fp(MODE) ? pc.qinv : (mode_lazy(MODE) ? pc.n4q : pc.q2);
 }
 
 // =====================================================================================================
@@ -430,12 +423,16 @@ __device__ __forceinline__ void fwd_strided_tiles(const uint64_t *inp, uint64_t 
 
 // five waves per SIMD (96 VGPRs) where the body fits; the modes whose body does not (12, 8 and 14 spilled registers
 // under that cap) run faster at four: M_GUARD2 12.17 -> 11.90 ms per batch transform, FP64 / unguarded rows 2-3 %
+constexpr bool fwd_strided_occ4(int mode)
+{
+    return mode == M_GUARD2 || mode_lazy(mode) || mode == M_FPR || mode == M_NOGUARD;
+}
 template <int LOGN, int MODE = M_GUARD>
-__global__ __launch_bounds__(256, (MODE == M_GUARD2 || mode_lazy(MODE) || MODE == M_FPR || MODE == M_NOGUARD) ? 4 : 5) void ntt_fwd_strided(NttArgs a)
+__global__ __launch_bounds__(256, fwd_strided_occ4(MODE) ? 4 : 5) void ntt_fwd_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
     // the modes that run four workgroups per CU anyway take phase B's twiddles through LDS at N = 2^16 (4 KiB more)
-    constexpr bool LDSTW = LOGN == 16 && (MODE == M_GUARD2 || mode_lazy(MODE) || MODE == M_FPR || MODE == M_NOGUARD);
+    constexpr bool LDSTW = LOGN == 16 && fwd_strided_occ4(MODE);
     __shared__ uint64_t lds[4096 + (LDSTW ? 512 : 0)];
     const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
     const uint32_t tile = w % TPR;
@@ -447,17 +444,17 @@ __global__ __launch_bounds__(256, (MODE == M_GUARD2 || mode_lazy(MODE) || MODE =
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[si]);
     const PrimeConst &pc = a.pc[prime];
     uint64_t *rowp = a.data + ((size_t)((srow / a.Lsel) * a.L + r) << LOGN);
-    if (MODE >= M_FPN)
+    const uint64_t q = mode_q<MODE>(pc), q2 = mode_q2<MODE>(pc);
+    if (mode_fp(MODE))
     {
         LoadFp op;
         op.qd = pc.qd;
         op.qinv = pc.qinv;
-        fwd_strided_tile<LOGN, LoadFp, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), pc.qd, pc.qinv, lds, threadIdx.x, op);
+        fwd_strided_tile<LOGN, LoadFp, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x, op);
     }
     else
     {
-        fwd_strided_tile<LOGN, LoadIdentity, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc),
-                                                                 lds, threadIdx.x);
+        fwd_strided_tile<LOGN, LoadIdentity, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x);
     }
 }
 
@@ -588,7 +585,7 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
     for (int c = 0; c < 8; ++c)
     {
         ulonglong2 v;
-        if (MODE >= M_FPN)
+        if (mode_fp(MODE))
         {
             v.x = fp_to_canonical(u2d(x[2 * c]), u2d(q), u2d(q2));
             v.y = fp_to_canonical(u2d(x[2 * c + 1]), u2d(q), u2d(q2));
@@ -674,15 +671,15 @@ __global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
 // =====================================================================================================
 // inverse, contiguous pass: stages LOGN-1 .. LOGN-8 (gap 1 .. 128); lazy [0,2q) out
 // =====================================================================================================
-// LZ: the M_LAZY8 butterflies (modarith.hip.h), with (q, q2) = (2^64 - q, 2^64 - 4q); values below 4q instead of 2q
-// IM: 0 exact integer butterflies, 1 M_LAZY8, 2 / 3 exact FP64 (FPN / FPR, modarith.hip.h gs_bfly_fp: canonical integers in,
-// doubles out to the strided pass; tw / twb = the FP64 inverse tables, (q, q2) = the bit patterns of (double q, 1/q))
+// MODE: M_GUARD the exact integer butterflies; M_LAZY8 / M_LAZY16 (modarith.hip.h) with (q, q2) = (2^64 - q, 2^64 - 4q), values below
+// 4q instead of 2q; M_FPN / M_FPR exact FP64 (modarith.hip.h gs_bfly_fp: canonical integers in, doubles out to the strided pass;
+// tw / twb = the FP64 inverse tables, (q, q2) = the bit patterns of (double q, 1/q)).  M_GUARD2 and M_NOGUARD are forward only.
 // one butterfly of an inverse tile on registers (j, j + half): stage i of a register block whose M_LAZY16 schedule is xk
-template <int IM>
+template <int MODE>
 __device__ __forceinline__ void gs_bfly_tile(uint64_t (&x)[16], int j, int half, uint64_t w, uint64_t wq, uint64_t q, uint64_t q2, const bool redsum,
                                              uint32_t xk, int i)
 {
-    if (IM == IM_LAZY16)
+    if constexpr (MODE == M_LAZY16)
     {
         if (lazy16_inv_kind(xk, i, j, half))
         {
@@ -695,15 +692,16 @@ __device__ __forceinline__ void gs_bfly_tile(uint64_t (&x)[16], int j, int half,
     }
     else
     {
-        gs_bfly_im<IM>(x[j], x[j + half], w, wq, q, q2, redsum);
+        gs_bfly_t<MODE>(x[j], x[j + half], w, wq, q, q2, redsum);
     }
 }
 
-template <int LOGN, int IM = 0>
+template <int LOGN, int MODE = M_GUARD>
 __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
                                                 const Tw *__restrict__ twb, const uint64_t *srcp = nullptr, Tw *ldstw = nullptr)
 {
+    static_assert(MODE != M_GUARD2 && MODE != M_NOGUARD, "M_GUARD2 and M_NOGUARD have no inverse butterflies");
     constexpr int R1 = LOGN - 8;
     uint64_t *lds = reinterpret_cast<uint64_t *>(lds2);
     uint64_t *base = rowp + ((size_t)tile << 12);
@@ -758,8 +756,8 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
         ulonglong2 v = lds2[(myrow << 3) | ((uint32_t)c ^ (myrow & 7u))];
         // FP64 modes: any input below 2^52 (canonical or lazy, like the integer butterflies accept); FPN folds it to |.| <= q/2
         // here -- its schedule of sum reductions counts from there --, FPR folds in every butterfly anyway
-        x[2 * c] = IM == 2 ? d2u(fp_red(fp_from_u52(v.x), u2d(q), u2d(q2))) : (IM == 3 ? d2u(fp_from_u52(v.x)) : v.x);
-        x[2 * c + 1] = IM == 2 ? d2u(fp_red(fp_from_u52(v.y), u2d(q), u2d(q2))) : (IM == 3 ? d2u(fp_from_u52(v.y)) : v.y);
+        x[2 * c] = MODE == M_FPN ? d2u(fp_red(fp_from_u52(v.x), u2d(q), u2d(q2))) : (MODE == M_FPR ? d2u(fp_from_u52(v.x)) : v.x);
+        x[2 * c + 1] = MODE == M_FPN ? d2u(fp_red(fp_from_u52(v.y), u2d(q), u2d(q2))) : (MODE == M_FPR ? d2u(fp_from_u52(v.y)) : v.y);
     }
 #pragma unroll
     for (int u = 7; u >= 4; --u)
@@ -771,7 +769,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
             if (!(j & half))
             {
                 Tw t = tb[(1 << (u - 4)) - 1 + (j >> (8 - u))];
-                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z1.xk, 7 - u); // FPN: sums folded in every fourth stage
+                gs_bfly_tile<MODE>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z1.xk, 7 - u); // FPN: sums folded in every fourth stage
             }
         }
     }
@@ -801,7 +799,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
             {
                 Tw t = ldstw ? ldstw[b * 15u + ((1u << u) - 1u) + (uint32_t)(j >> (4 - u))]
                              : tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(j >> (4 - u))];
-                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z2.xk, 3 - u); // FPN: sums folded in every fourth stage
+                gs_bfly_tile<MODE>(x, j, half, t.w, t.wq, q, q2, (u & 3) == 0, z2.xk, 3 - u); // FPN: sums folded in every fourth stage
             }
         }
     }
@@ -812,7 +810,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
     }
 }
 
-template <int LOGN, int IM = 0>
+template <int LOGN, int MODE = M_GUARD>
 __global__ __launch_bounds__(256) void ntt_inv_contig(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -825,35 +823,38 @@ __global__ __launch_bounds__(256) void ntt_inv_contig(NttArgs a)
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[rest / TPR]);
     const PrimeConst &pc = a.pc[prime];
     const uint64_t *srcp = a.src ? a.src + (((size_t)pol * a.src_stride + a.src_off + r) << LOGN) : nullptr;
-    constexpr bool LZ = IM == 1 || IM == IM_LAZY16;
-    inv_contig_tile<LOGN, IM>(a.data + (((size_t)pol * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN),
-                              IM >= 2 ? pc.qd : (LZ ? pc.nq : pc.q), IM >= 2 ? pc.qinv : (LZ ? pc.n4q : pc.q2), lds2, threadIdx.x,
-                              a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), srcp);
+    inv_contig_tile<LOGN, MODE>(a.data + (((size_t)pol * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc),
+                                mode_q2<MODE>(pc), lds2, threadIdx.x, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), srcp);
 }
 
 // =====================================================================================================
 // inverse, strided pass: stages LOGN-9 .. 0, N^-1 folded into stage 0; writes canonical
 // =====================================================================================================
-template <int LOGN, int IM = 0>
+// the lazy modes' pass is compiled for four workgroups per CU, the others for five; at N = 2^16 the former take phase B's twiddles
+// through LDS (inv_strided_tile)
+constexpr bool inv_strided_occ4(int mode)
+{
+    return mode_lazy(mode);
+}
+template <int LOGN, int MODE = M_GUARD>
 __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                  const PrimeConst *pc, uint64_t *lds, const uint32_t tid)
 {
-    constexpr bool LZ = (IM == 1 || IM == IM_LAZY16);
+    static_assert(MODE != M_GUARD2 && MODE != M_NOGUARD, "M_GUARD2 and M_NOGUARD have no inverse butterflies");
     constexpr int R1 = LOGN - 8;
     constexpr int RB = R1 - 4;
     constexpr int GB = 12 - R1;
     constexpr uint32_t G = 1u << GB;
-    const uint64_t q = IM >= 2 ? pc->qd : (LZ ? pc->nq : pc->q);
-    const uint64_t q2 = IM >= 2 ? pc->qinv : (LZ ? pc->n4q : pc->q2);
+    const uint64_t q = mode_q<MODE>(*pc), q2 = mode_q2<MODE>(*pc);
     uint64_t *__restrict__ row = rowp + tile * G;
     // M_LAZY16: phase B's RB stages from what the contiguous pass hands over, then phase A's four, the transform's last among them
     constexpr Lazy16Inv zb = lazy16_inv(RB, lazy16_inv_handover(), false), za = lazy16_inv(4, zb.out, true);
     static_assert(zb.peak <= 16 && za.peak <= 16, "a value of 16q or more");
     static_assert(za.out <= 4, "the final subtractions expect values below 4q");
 
-    // LDSTW (M_LAZY8 at N = 2^16: four workgroups per CU either way): phase B's twiddles -- entries 16..255 of the table, shared by
+    // LDSTW (the lazy modes at N = 2^16: four workgroups per CU either way): phase B's twiddles -- entries 16..255 of the table, shared by
     // the sixteen threads of a group -- through a copy in LDS (`lds` + 4096 words), as in the forward strided pass
-    constexpr bool LDSTW = LOGN == 16 && LZ;
+    constexpr bool LDSTW = LOGN == 16 && inv_strided_occ4(MODE);
     Tw *ldstw = reinterpret_cast<Tw *>(lds + 4096);
     uint64_t x[16];
     if (RB > 0)
@@ -885,7 +886,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
                 {
                     uint32_t t_ = (th << 4) | (uint32_t)j;
                     Tw t = LDSTW ? ldstw[(1u << s) + (t_ >> (R1 - s))] : tw[(1u << s) + (t_ >> (R1 - s))];
-                    gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, ((R1 - 1 - s) & 3) == 3, zb.xk, R1 - 1 - s); // stage number in this pass
+                    gs_bfly_tile<MODE>(x, j, half, t.w, t.wq, q, q2, ((R1 - 1 - s) & 3) == 3, zb.xk, R1 - 1 - s); // stage number in this pass
                 }
             }
         }
@@ -920,7 +921,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
             if (!(j & half))
             {
                 Tw t = tw[(1u << u) + (uint32_t)(j >> (4 - u))];
-                gs_bfly_tile<IM>(x, j, half, t.w, t.wq, q, q2, ((RB + 3 - u) & 3) == 3, za.xk, 3 - u);
+                gs_bfly_tile<MODE>(x, j, half, t.w, t.wq, q, q2, ((RB + 3 - u) & 3) == 3, za.xk, 3 - u);
             }
         }
     }
@@ -930,7 +931,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
 #pragma unroll
         for (int j = 0; j < 8; ++j)
         {
-            if (IM == IM_LAZY16)
+            if constexpr (MODE == M_LAZY16)
             {
                 if (lazy16_inv_kind(za.xk, 3, j, 8))
                 {
@@ -941,17 +942,9 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
                     gs_bfly_last_lazy16<0>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
                 }
             }
-            else if (IM >= 2)
-            {
-                gs_bfly_last_fp<IM == 3>(x[j], x[j + 8], fp_from_u64(ninv.w), fp_from_u64(ninv_w1.w), u2d(q), u2d(q2));
-            }
-            else if (LZ)
-            {
-                gs_bfly_last_lazy8(x[j], x[j + 8], ninv, ninv_w1, q, q2);
-            }
             else
             {
-                gs_bfly_last(x[j], x[j + 8], ninv, ninv_w1, q, q2);
+                gs_bfly_last_t<MODE>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
             }
         }
     }
@@ -959,24 +952,24 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
     for (int j = 0; j < 16; ++j)
     {
         uint32_t e = (uint32_t)j * 256u + tid;
-        // exact: below 2q; LZ: below 4q, with 2^64 - 2q = (2^64 - 4q) / 2 + 2^63
-        row[((e >> GB) << 8) + (e & (G - 1))] = IM >= 2 ? fp_to_canonical(u2d(x[j]), u2d(q), u2d(q2))
-                                                        : (LZ ? csub_sign(csub_sign(x[j], (q2 >> 1) | 0x8000000000000000ull), q) : csub(x[j], q));
+        // exact: below 2q; lazy: below 4q, with 2^64 - 2q = (2^64 - 4q) / 2 + 2^63
+        row[((e >> GB) << 8) + (e & (G - 1))] = mode_fp(MODE) ? fp_to_canonical(u2d(x[j]), u2d(q), u2d(q2))
+                                                              : (mode_lazy(MODE) ? csub_sign(csub_sign(x[j], (q2 >> 1) | 0x8000000000000000ull), q) : csub(x[j], q));
     }
 }
 
-template <int LOGN, int IM = 0>
-__global__ __launch_bounds__(256, (IM == 1 || IM == IM_LAZY16) ? 4 : 5) void ntt_inv_strided(NttArgs a)
+template <int LOGN, int MODE = M_GUARD>
+__global__ __launch_bounds__(256, inv_strided_occ4(MODE) ? 4 : 5) void ntt_inv_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
-    __shared__ uint64_t lds[4096 + ((LOGN == 16 && (IM == 1 || IM == IM_LAZY16)) ? 512 : 0)]; // the exchange buffer (+ phase B's twiddles, inv_strided_tile)
+    __shared__ uint64_t lds[4096 + ((LOGN == 16 && inv_strided_occ4(MODE)) ? 512 : 0)]; // the exchange buffer (+ phase B's twiddles, inv_strided_tile)
     const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
     const uint32_t tile = w % TPR;
     const uint32_t srow = w / TPR; // over n_poly * Lsel selected rows
     const uint32_t si = srow % a.Lsel;
     const uint32_t r = __builtin_amdgcn_readfirstlane(a.sel.idx[si]);
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[si]);
-    inv_strided_tile<LOGN, IM>(a.data + ((size_t)((srow / a.Lsel) * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN), a.pc + prime, lds,
+    inv_strided_tile<LOGN, MODE>(a.data + ((size_t)((srow / a.Lsel) * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN), a.pc + prime, lds,
                                threadIdx.x);
 }
 

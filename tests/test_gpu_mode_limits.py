@@ -66,7 +66,7 @@ def release_device_contexts():
         entry[3].close()
     for entry in _long.values():
         entry["ctx"].close()
-    for cache in (_ctxs, _long, _ntt, _ks, _rs, _hoist):
+    for cache in (_ctxs, _long, _ntt, _mixed, _ks, _rs, _hoist):
         cache.clear()
 
 
@@ -218,6 +218,62 @@ def test_ntt_at_the_limits(moai, logn, fp):
             d.upload(lazy)
             ctx.ntt_inverse(d, 2, K)
             assert (d.to_numpy(x.shape) == c["inv"][p]).all(), "inverse from the top of its input range, " + pname
+            d.free()
+    finally:
+        H.reset_tuning()
+
+
+# A row selection in which the classes interleave and row r is not prime r: what the launcher's partition of the rows by class
+# has to get right (which rows, which primes, which tables per class) and the identity map of the tests above does not force.
+# Under the defaults no two neighbouring rows share both their forward and their inverse class.
+MIXED_ROWS = ("g60", "fpn_hi", "g61", "fpr_hi", "ng_hi", "small", "g_lo", "fpr_lo", "int_lo")
+# (2^12: a grid of n_poly * rows of a class workgroups, with 3 polynomials no multiple of 8 and with 8 polynomials one -- the two
+# arms of the kernels' work-id map; 2^16: the degree with the twiddle copies in LDS and the larger inverse LDS array)
+MIXED_SHAPES = [(12, 3), (12, 8), (16, 1)]
+MIXED_KNOBS = {"fp": {"MOAI_NTT_FP": 1}, "int": {"MOAI_NTT_FP": 0}, "lazy8": {"MOAI_NTT_LAZY16": 0}}
+_mixed = {}
+
+
+def mixed_case(logn):
+    """prime index per row, inputs [pattern][8 or 1][9][N] (polynomial j: the patterns j coefficients on) and the oracle's forward
+    transform under that row selection; once per degree, the 3-polynomial case takes the first three"""
+    if logn not in _mixed:
+        n, npoly = 1 << logn, max(p for l, p in MIXED_SHAPES if l == logn)
+        primes = ML.ordered(logn, "g61_last")
+        pidx = [ML.ORDERS["g61_last"].index(name) for name in MIXED_ROWS]
+        assert sorted(pidx) == list(range(K)) and pidx != list(range(K))
+        pat = ML.pattern_rows([primes[i] for i in pidx], n, np.random.default_rng(5250 + logn))
+        x = np.stack([np.roll(pat, j, axis=-1) for j in range(npoly)], axis=1)
+        fwd = O.Context(logn, primes).ntt(x.reshape(-1, K, n), K, prime_index=pidx).reshape(x.shape)
+        for v in (x, fwd):
+            v.setflags(write=False)
+        _mixed[logn] = (pidx, x, fwd)
+    return _mixed[logn]
+
+
+@pytest.mark.parametrize("logn,npoly,knobs", [(l, p, k) for l, p in MIXED_SHAPES for k in MIXED_KNOBS])
+def test_ntt_interleaved_classes_and_permuted_primes(moai, logn, npoly, knobs):
+    H = moai.hip
+    pidx, x, fwd = mixed_case(logn)
+    _, names, _, ctx = contexts(moai, logn, "g61_last")
+    for knob, v in MIXED_KNOBS[knobs].items():
+        H.set_tuning(knob, v)
+    try:
+        col = 1 if knobs == "int" else 0
+        want = [[H.MODE_LAZY8 if knobs == "lazy8" and table[name][col] == "LAZY16" else code(moai, table[name][col]) for name in MIXED_ROWS]
+                for table in (FWD_CLASS, INV_CLASS)]
+        got = [[ctx.arith_mode(i, of) for i in pidx] for of in (H.MODE_OF_NTT_FORWARD, H.MODE_OF_NTT_INVERSE)]
+        assert got == want
+        if knobs == "fp":
+            assert all((got[0][r], got[1][r]) != (got[0][r + 1], got[1][r + 1]) for r in range(K - 1)), "neighbours of one class pair"
+            assert len(set(got[0])) == 5 and len(set(got[1])) == 4  # every class but the one MOAI_NTT_LAZY16=0 brings
+        for p, pname in enumerate(ML.PATTERNS):
+            xp = x[p, :npoly]
+            d = up(moai, xp)
+            ctx.ntt_forward(d, npoly, K, prime_index=pidx)
+            assert (d.to_numpy(xp.shape) == fwd[p, :npoly]).all(), "forward, " + pname
+            ctx.ntt_inverse(d, npoly, K, prime_index=pidx)
+            assert (d.to_numpy(xp.shape) == xp).all(), "round trip, " + pname
             d.free()
     finally:
         H.reset_tuning()
