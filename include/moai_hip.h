@@ -300,6 +300,25 @@ int moai_apply_galois_to(moai_ctx *ctx, const uint64_t *in, uint64_t *out, size_
  * in, acc: [batch][2][L][N], distinct.  Same residues as moai_apply_galois_to followed by moai_add. */
 int moai_apply_galois_acc(moai_ctx *ctx, const uint64_t *in, uint64_t *acc, size_t L, uint32_t galois_elt,
                           const uint64_t *galois_key, size_t batch, void *stream);
+/* Key switches on a LIST of single ciphertexts, each in its own block with its own Galois element and key:
+ * outs[i] = [sums[i] +] apply_galois(ins[i], galois_elts[i], galois_keys[i]), i < n -- n calls of moai_apply_galois_to /
+ * moai_apply_galois_acc (Evaluator::apply_galois_inplace, SEAL/evaluator.cpp:2563-2665, switch_key_inplace :2724-3020) in one
+ * chain of launches, bit-identical to them.  What the differently rotated ciphertexts of MOAI's OpenMP loops
+ * (include/source/matrix_mul/Ct_ct_matrix_mul.hpp:22-31, 84-102, 142-149) need to share launches: the batch forms above take
+ * one contiguous block and one key.  The members' keys may have different layouts (whole, moai_key_trim'med or born limited).
+ *   ins / outs / galois_keys / sums: HOST arrays of n device pointers, each member [2][L][N]; sums may be NULL, and so may
+ *   any sums[i].  outs[i] may be ins[i] or sums[i]; otherwise no output may overlap any member's input, output or sum.
+ * Any n: 64 members per pass.  Nothing is enqueued when an argument is refused: MOAI_EINVAL for a null list or member, an even
+ * element or one >= 2N, or an overlap; MOAI_ERANGE, naming the member, for a key limited below L.  n == 0 is MOAI_OK.  The
+ * call does not synchronise.  moai_op_trace counts it as n units of "apply_galois_to". */
+int moai_apply_galois_ptrs(moai_ctx *ctx, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *galois_elts,
+                           const uint64_t *const *galois_keys, const uint64_t *const *sums, size_t n, void *stream);
+/* outs[i] = relinearize(ct3s[i]) with one key: n calls of moai_relinearize(..., batch 1) (Evaluator::relinearize_internal,
+ * SEAL/evaluator.cpp:1345-1400) in one chain of launches, bit-identical to them.  ct3s / outs: HOST arrays of n device
+ * pointers, ct3s[i] [3][L][N], outs[i] [2][L][N]; no output may overlap any member's input or output.  Errors, n and tracing
+ * ("relinearize") as above. */
+int moai_relinearize_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *relin_key, size_t L,
+                          size_t n, void *stream);
 
 /* ---- MOAI-owned integer kernel ---------------------------------------------------------------------------
  * Bootstrapper::modraise_inplace include/source/bootstrapping/Bootstrapper.cpp:2938-2992:

@@ -48,6 +48,20 @@ struct RowMap
     uint32_t idx[MOAI_MAX_RNS];
 };
 
+// The per-member operands of a key switch on a list of ciphertexts (moai_apply_galois_ptrs, moai_relinearize_ptrs): one record per
+// pass of at most KS_LIST_MAX members, in device memory, written on the call's stream.  The list kernels index it with the member
+// their workgroup serves, which is uniform: scalar loads, once per workgroup.
+constexpr size_t KS_LIST_MAX = 64;
+struct KsList
+{
+    const uint64_t *ins[KS_LIST_MAX];    // the member's input block
+    uint64_t *outs[KS_LIST_MAX];         // [2][L][N] result
+    const uint64_t *sums[KS_LIST_MAX];   // [2][L][N] added to the result, or null
+    const uint64_t *keys[KS_LIST_MAX];   // [digits][2][key_rows][N]
+    const uint32_t *tables[KS_LIST_MAX]; // galois_table of the member's element
+    uint32_t key_rows[KS_LIST_MAX];      // rows per key polynomial in the member's key layout (key_rows_for)
+};
+
 int set_error(int code, const char *fmt, ...);
 
 // side streams of the transform's chunk schedule: with the caller's stream they make the four hardware queues a process opens

@@ -843,10 +843,24 @@ __global__ __launch_bounds__(256) void drop_rows_kernel(const uint64_t *in, uint
 // out[row][i] = in[row][table[i]]   (apply_galois_ntt, SEAL/util/galois.cpp:192-218)
 // source row of output row r: (r / L) * src_poly_rows + r % L -- src_poly_rows = L for a dense copy, 2 L to take the first
 // polynomial of every size-2 ciphertext only
-__global__ __launch_bounds__(256) void galois_gather_kernel(const uint64_t *in, uint64_t *out, const uint32_t *table,
-                                                            uint32_t n, uint32_t L, uint32_t src_poly_rows)
+// LIST: the rows come from separate blocks, each with its own element.  Output rows [b * L, (b + 1) * L) are rows
+// src_poly_rows .. src_poly_rows + L - 1 of in->ins[b], permuted by in->tables[b]; `in` is the list and `table` is not used.  This is both
+// the gather into the key switch's contiguous scratch and the permutation, in one pass.
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void galois_gather_kernel(std::conditional_t<LIST, const KsList *, const uint64_t *> in, uint64_t *out,
+                                                            const uint32_t *table, uint32_t n, uint32_t L, uint32_t src_poly_rows)
 {
-    const uint64_t *s = in + ((size_t)(blockIdx.y / L) * src_poly_rows + blockIdx.y % L) * n;
+    const uint64_t *s;
+    if constexpr (LIST)
+    {
+        const uint32_t b = blockIdx.y / L; // uniform: the two list entries arrive through scalar loads
+        s = in->ins[b] + ((size_t)src_poly_rows + blockIdx.y % L) * n;
+        table = in->tables[b];
+    }
+    else
+    {
+        s = in + ((size_t)(blockIdx.y / L) * src_poly_rows + blockIdx.y % L) * n;
+    }
     uint64_t *d = out + (size_t)blockIdx.y * n;
     for (uint32_t i = (blockIdx.x * 256u + threadIdx.x) * 2u; i < n; i += gridDim.x * 512u)
     {
@@ -970,8 +984,18 @@ static int galois_gather(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t 
         return MOAI_OK;
     }
     MOAI_CHECK_GRID_ROWS(rows);
-    hipLaunchKernelGGL(galois_gather_kernel, dim3((uint32_t)((c->n + 511) / 512), (uint32_t)rows), dim3(256), 0, s, in, out, table,
+    hipLaunchKernelGGL(galois_gather_kernel<false>, dim3((uint32_t)((c->n + 511) / 512), (uint32_t)rows), dim3(256), 0, s, in, out, table,
                        (uint32_t)c->n, (uint32_t)L, (uint32_t)src_poly_rows);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+int galois_gather_list(moai_ctx *c, const KsList *lst, uint64_t *out, size_t members, size_t rows_per_member, size_t src_off_rows,
+                       hipStream_t s)
+{
+    MOAI_CHECK_GRID_ROWS(members * rows_per_member);
+    hipLaunchKernelGGL(galois_gather_kernel<true>, dim3((uint32_t)((c->n + 511) / 512), (uint32_t)(members * rows_per_member)), dim3(256), 0,
+                       s, lst, out, (const uint32_t *)nullptr, (uint32_t)c->n, (uint32_t)rows_per_member, (uint32_t)src_off_rows);
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }

@@ -17,6 +17,7 @@
 // The loop over I is outermost so that the 2*L key rows of modulus I are read once per batch.
 #include <mutex>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -119,8 +120,15 @@ struct FinalizeArgs
     int add_mode;
 };
 
+struct FinalizeListArgs : FinalizeArgs
+{
+    const KsList *lst; // see moddown_contig
+};
+
 // (acc_i - u_i) * q_last^-1 mod q_i      (rns.cpp:892-897 / evaluator.cpp:3012-3017)
-__global__ __launch_bounds__(256) void moddown_finalize_kernel(FinalizeArgs g)
+// LIST: outputs, second addends and (add_mode 1) first addends per ciphertext p / 2, as in moddown_contig
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void moddown_finalize_kernel(std::conditional_t<LIST, FinalizeListArgs, FinalizeArgs> g)
 {
     const uint32_t p = blockIdx.y / g.Lout;
     const uint32_t i = blockIdx.y % g.Lout;
@@ -129,21 +137,41 @@ __global__ __launch_bounds__(256) void moddown_finalize_kernel(FinalizeArgs g)
     const ulonglong2 *a = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)p * g.acc_stride + i) * g.n2;
     const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.u) + (size_t)blockIdx.y * g.n2;
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * g.n2;
+    const ulonglong2 *add = nullptr, *add2 = nullptr;
+    if constexpr (LIST)
+    {
+        const size_t row = ((size_t)(p & 1u) * g.Lout + i) * g.n2; // inside the member's [2][Lout][N]
+        o = reinterpret_cast<ulonglong2 *>(g.lst->outs[p >> 1]) + row;
+        if (g.lst->sums[p >> 1])
+        {
+            add2 = reinterpret_cast<const ulonglong2 *>(g.lst->sums[p >> 1]) + row;
+        }
+        if (g.add_mode == 1)
+        {
+            add = reinterpret_cast<const ulonglong2 *>(g.lst->ins[p >> 1]) + row;
+        }
+    }
     for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
     {
         ulonglong2 x = a[j], y = u[j], r;
         r.x = csub(mul_shoup_lazy(x.x + q - y.x, inv.w, inv.wq, q), q);
         r.y = csub(mul_shoup_lazy(x.y + q - y.y, inv.w, inv.wq, q), q);
-        if (g.add_mode == 1 || (g.add_mode == 2 && !(p & 1u)))
+        if (LIST && add)
+        {
+            ulonglong2 c = add[j];
+            r.x = csub(r.x + c.x, q);
+            r.y = csub(r.y + c.y, q);
+        }
+        else if (g.add_mode == 1 || (g.add_mode == 2 && !(p & 1u)))
         {
             ulonglong2 c = (reinterpret_cast<const ulonglong2 *>(g.addend) +
                             ((size_t)(p >> 1) * g.addend_bstride + (size_t)(p & 1u) * g.Lout + i) * g.n2)[j];
             r.x = csub(r.x + c.x, q);
             r.y = csub(r.y + c.y, q);
         }
-        if (g.addend2)
+        if (LIST ? add2 != nullptr : g.addend2 != nullptr)
         {
-            ulonglong2 c = (reinterpret_cast<const ulonglong2 *>(g.addend2) + (size_t)blockIdx.y * g.n2)[j];
+            ulonglong2 c = LIST ? add2[j] : (reinterpret_cast<const ulonglong2 *>(g.addend2) + (size_t)blockIdx.y * g.n2)[j];
             r.x = csub(r.x + c.x, q);
             r.y = csub(r.y + c.y, q);
         }
@@ -181,9 +209,15 @@ struct MacArgs
     uint32_t n2;
 };
 
+struct MacListArgs : MacArgs
+{
+    const KsList *lst; // ciphertext b's key is lst->keys[b] with lst->key_rows[b] rows (key, k and krow unused)
+};
+
 // acc[b][K][slot] = sum_J ops[b][J] (*) key[J][K][prime]  mod q      (evaluator.cpp:2858-2910)
 // blockIdx.y = b
-__global__ __launch_bounds__(256) void keyswitch_mac_kernel(MacArgs g)
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void keyswitch_mac_kernel(std::conditional_t<LIST, MacListArgs, MacArgs> g)
 {
     const PrimeConst *pc = g.pc + g.prime;
     const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
@@ -191,6 +225,14 @@ __global__ __launch_bounds__(256) void keyswitch_mac_kernel(MacArgs g)
     const size_t n2 = g.n2;
     const ulonglong2 *ops = reinterpret_cast<const ulonglong2 *>(g.ops) + (size_t)b * g.L * n2;
     const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key);
+    uint32_t list_k = 0;
+    if constexpr (LIST)
+    {
+        key = reinterpret_cast<const ulonglong2 *>(g.lst->keys[b]);
+        list_k = g.lst->key_rows[b];
+    }
+    const uint32_t key_k = LIST ? list_k : g.k;
+    const uint32_t krow = LIST ? (g.slot == g.L ? list_k - 1 : g.prime) : g.krow;
     ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (g.L + 1) + g.slot) * n2;
     ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (g.L + 1) + g.slot) * n2;
     for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
@@ -199,8 +241,8 @@ __global__ __launch_bounds__(256) void keyswitch_mac_kernel(MacArgs g)
         for (uint32_t J = 0; J < g.L; ++J)
         {
             ulonglong2 o = ops[(size_t)J * n2 + j];
-            ulonglong2 k0 = key[((size_t)(J * 2 + 0) * g.k + g.krow) * n2 + j];
-            ulonglong2 k1 = key[((size_t)(J * 2 + 1) * g.k + g.krow) * n2 + j];
+            ulonglong2 k0 = key[((size_t)(J * 2 + 0) * key_k + krow) * n2 + j];
+            ulonglong2 k1 = key[((size_t)(J * 2 + 1) * key_k + krow) * n2 + j];
             mac128(l0x, h0x, o.x, k0.x);
             mac128(l0y, h0y, o.y, k0.y);
             mac128(l1x, h1x, o.x, k1.x);
@@ -288,10 +330,12 @@ static bool md_allow_fp(size_t rows)
 // scratch: u [P][Lout][N]
 //   addend / addend_bstride / add_mode: what is added to the quotient (ModDownArgs); add_mode 0 for rescale
 //   addend2: a second summand with the output's layout (may be `out`), or null
+//   lst (device memory, key switch only): polynomials 2b and 2b + 1 go to lst->outs[b] plus lst->sums[b], and add_mode 1 reads
+//   lst->ins[b]; out and addend2 are null then (the LIST kernels)
 static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32_t acc_stride, uint64_t *u,
                    uint64_t *out, size_t P, size_t Lout, uint32_t prime_last, const uint64_t *addend, uint32_t addend_bstride,
                    int add_mode, hipStream_t s, uint32_t acc_splits = 1, size_t acc_split_stride = 0, const Tw *scal = nullptr,
-                   const uint64_t *addend2 = nullptr)
+                   const uint64_t *addend2 = nullptr, const KsList *lst = nullptr)
 {
     RowMap rm;
     uint32_t pl = prime_last;
@@ -347,7 +391,17 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
             a.twb = t.twb;
             MOAI_TRY(dispatch_ks(c->logn, mode, [&](auto LG, auto MD) {
                 hipLaunchKernelGGL((moddown_strided<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
-                hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
+                if (lst)
+                {
+                    ModDownListArgs al;
+                    static_cast<ModDownArgs &>(al) = a;
+                    al.lst = lst;
+                    hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value, true>), dim3(a.total_work), dim3(256), 0, s, al);
+                }
+                else
+                {
+                    hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
+                }
                 return MOAI_OK;
             }));
         }
@@ -384,7 +438,17 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
     f.addend_bstride = addend_bstride;
     f.add_mode = add_mode;
     MOAI_CHECK_GRID_ROWS(P * Lout);
-    hipLaunchKernelGGL(moddown_finalize_kernel, rgrid(c, P * Lout), dim3(256), 0, s, f);
+    if (lst)
+    {
+        FinalizeListArgs fl;
+        static_cast<FinalizeArgs &>(fl) = f;
+        fl.lst = lst;
+        hipLaunchKernelGGL(moddown_finalize_kernel<true>, rgrid(c, P * Lout), dim3(256), 0, s, fl);
+    }
+    else
+    {
+        hipLaunchKernelGGL(moddown_finalize_kernel<false>, rgrid(c, P * Lout), dim3(256), 0, s, f);
+    }
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
 }
@@ -411,11 +475,13 @@ struct KsTarget
     const uint64_t *ptr; // NTT-form target rows
     uint32_t stride_rows, off_rows;
     uint32_t key_rows;   // rows per key polynomial in the key's layout (key_rows_for)
+    const KsList *lst;   // or null: every ciphertext its own key and layout (device memory; key and key_rows unused)
 };
 
 // rows per key polynomial of `key` (k for the reference's layout, levels + 1 for a key moai_key_trim produced), after checking
 // that the key holds what a switch at L data primes reads: digits J < L and rows {0 .. L-1, special} (SEAL/evaluator.cpp:2818,2831)
-static int key_rows_for(moai_ctx *c, const uint64_t *key, size_t L, uint32_t *rows)
+// member >= 0: the key is that member's of a list, and the message says so
+static int key_rows_for(moai_ctx *c, const uint64_t *key, size_t L, uint32_t *rows, long member = -1)
 {
     std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
     auto it = c->key_layouts.find(key);
@@ -423,6 +489,11 @@ static int key_rows_for(moai_ctx *c, const uint64_t *key, size_t L, uint32_t *ro
     {
         *rows = (uint32_t)c->k;
         return MOAI_OK;
+    }
+    if ((L > it->second.digits || L + 1 > it->second.rows) && member >= 0)
+    {
+        return set_error(MOAI_ERANGE, "member %ld: the key was trimmed to %u levels and cannot switch a ciphertext of %zu data primes", member,
+                         it->second.digits, L);
     }
     if (L > it->second.digits || L + 1 > it->second.rows)
     {
@@ -651,7 +722,26 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
     // same box, same hour, l = 35 / 15, batch 64: 0.572 / 0.134 ms per ciphertext with the compiler's placement (0), 0.532 / 0.121
     // with 1, 0.547 / 0.124 with 2 (profiles/r03_b_ks_kernel_variants_ab.txt)
     const long pf = MODE >= M_FPN ? tuning(K_KS_MAC_PF) : 0;
-    if (pf == 1)
+    if (tg.lst)
+    {
+        // every ciphertext its own key: the same three placements
+        KsP2ListArgs pl;
+        static_cast<KsP2Args &>(pl) = p2;
+        pl.lst = tg.lst;
+        if (pf == 1)
+        {
+            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 1 : 0), true>), dim3(p2.total_work), dim3(256), 0, s, pl);
+        }
+        else if (pf == 2)
+        {
+            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 2 : 0), true>), dim3(p2.total_work), dim3(256), 0, s, pl);
+        }
+        else
+        {
+            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, 0, true>), dim3(p2.total_work), dim3(256), 0, s, pl);
+        }
+    }
+    else if (pf == 1)
     {
         hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 1 : 0)>), dim3(p2.total_work), dim3(256), 0, s, p2);
     }
@@ -670,9 +760,12 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
 // target row block of ciphertext b starts at target + (b * target_stride_rows + target_off_rows) * N.
 // wsp: switch_key_ws_bytes() bytes of scratch.
 // ct [batch][2][L][N] = addend (add_mode, ModDownArgs) + key switch of `target`; ct may be the addend itself
+// lst (device memory; its keys validated by the caller): ciphertext b is switched with lst->keys[b] and its result goes to
+// lst->outs[b] (+ lst->sums[b]); ct, key and addend2 are null then, and add_mode 1 adds lst->ins[b] (moddown)
 static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, size_t target_stride_rows,
                            size_t target_off_rows, const uint64_t *key, size_t L, size_t batch, void *wsp,
-                           hipStream_t s, const uint64_t *addend, size_t addend_bstride, int add_mode, const uint64_t *addend2 = nullptr)
+                           hipStream_t s, const uint64_t *addend, size_t addend_bstride, int add_mode, const uint64_t *addend2 = nullptr,
+                           const KsList *lst = nullptr)
 {
     const size_t n = c->n;
     const size_t k = c->k;
@@ -685,7 +778,10 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
         return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
     }
     uint32_t key_rows = 0;
-    MOAI_TRY(key_rows_for(c, key, L, &key_rows));
+    if (!lst)
+    {
+        MOAI_TRY(key_rows_for(c, key, L, &key_rows));
+    }
     const KsLayout w = ks_layout(c, L, batch);
     uint64_t *t = at_bytes(wsp, w.t), *ops = at_bytes(wsp, w.ops), *acc = at_bytes(wsp, w.acc), *last = at_bytes(wsp, w.last);
     const uint32_t n2 = (uint32_t)(n >> 1);
@@ -707,6 +803,7 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
         tg.stride_rows = (uint32_t)target_stride_rows;
         tg.off_rows = (uint32_t)target_off_rows;
         tg.key_rows = key_rows;
+        tg.lst = lst;
         for (const KsPlanGroup &pg : ks_plan(c, L, batch))
         {
             MOAI_TRY(dispatch_ks(c->logn, pg.mode, [&](auto LG, auto MD) {
@@ -740,7 +837,17 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
             m.slot = (uint32_t)Iidx;
             m.n2 = n2;
             MOAI_CHECK_GRID_ROWS(batch);
-            hipLaunchKernelGGL(keyswitch_mac_kernel, rgrid(c, batch), dim3(256), 0, s, m);
+            if (lst)
+            {
+                MacListArgs ml;
+                static_cast<MacArgs &>(ml) = m;
+                ml.lst = lst;
+                hipLaunchKernelGGL(keyswitch_mac_kernel<true>, rgrid(c, batch), dim3(256), 0, s, ml);
+            }
+            else
+            {
+                hipLaunchKernelGGL(keyswitch_mac_kernel<false>, rgrid(c, batch), dim3(256), 0, s, m);
+            }
             MOAI_LAUNCH_CHECK();
         }
     }
@@ -750,7 +857,7 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
                        w.split_stride, c->pc, (uint32_t)(k - 1), n2);
     MOAI_LAUNCH_CHECK();
     return moddown(c, last, acc, (uint32_t)(L + 1), ops, ct, batch * 2, L, (uint32_t)(k - 1), addend, (uint32_t)addend_bstride, add_mode, s,
-                   w.splits, w.split_stride, nullptr, addend2);
+                   w.splits, w.split_stride, nullptr, addend2, lst);
 }
 
 } // namespace moai
@@ -1040,6 +1147,192 @@ extern "C" int moai_apply_galois_acc(moai_ctx *c, const uint64_t *in, uint64_t *
         return set_error(MOAI_EINVAL, "null argument, or the sum is the input");
     }
     return apply_galois_impl(c, in, acc, L, galois_elt, galois_key, batch, stream, acc);
+}
+
+// ---- key switches on a list of ciphertexts, each with its own key and element ----------------------------------------------
+namespace moai {
+
+// one pass's list goes to device memory on the call's stream: the record travels as a kernel argument and thread i stores
+// entry i (no host-to-device copy, which would read pageable memory after the call has returned)
+__global__ __launch_bounds__(64) void ks_list_write_kernel(KsList h, KsList *d)
+{
+    const uint32_t i = threadIdx.x;
+    d->ins[i] = h.ins[i];
+    d->outs[i] = h.outs[i];
+    d->sums[i] = h.sums[i];
+    d->keys[i] = h.keys[i];
+    d->tables[i] = h.tables[i];
+    d->key_rows[i] = h.key_rows[i];
+}
+
+// What the two list entry points share.  relin: member i is [3][L][N], its third polynomial is switched with `one_key` and the
+// first two are added (moai_relinearize); else member i is [2][L][N] and gets apply_galois by elts[i] with keys[i], plus sums[i].
+// Everything is validated before anything is enqueued; then at most KS_LIST_MAX members per pass: the list, one gather that
+// also permutes (galois_gather_kernel<true>) into the contiguous scratch, and the key switch with the LIST kernels.
+static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *elts,
+                        const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n, bool relin, void *stream)
+{
+    if (n == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!ins || !outs || (relin ? !one_key : (!elts || !keys)))
+    {
+        return set_error(MOAI_EINVAL, "null list");
+    }
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (!ins[i] || !outs[i] || (!relin && !keys[i]))
+        {
+            return set_error(MOAI_EINVAL, "member %zu: null pointer", i);
+        }
+        if (!relin && !(elts[i] & 1u))
+        {
+            return set_error(MOAI_EINVAL, "member %zu: Galois element is not valid", i);
+        }
+    }
+    const size_t nb = n < KS_LIST_MAX ? n : KS_LIST_MAX; // members per pass
+    MOAI_TRY(check_level(c, L, nb * (relin ? 3 : 2)));
+    if (c->k < 2)
+    {
+        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
+    }
+    if (L > c->k - 1)
+    {
+        return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
+    }
+    const size_t rn = L * c->n, in_bytes = (relin ? 3 : 2) * rn * sizeof(uint64_t), out_bytes = 2 * rn * sizeof(uint64_t);
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (!relin && elts[i] >= 2 * c->n)
+        {
+            return set_error(MOAI_EINVAL, "member %zu: Galois element is not valid", i);
+        }
+        // a member's own blocks: the output may be the input or the sum exactly (apply_galois), never a part of them
+        const uint64_t *sum = sums ? sums[i] : nullptr;
+        if (outs[i] != ins[i] ? overlap(outs[i], out_bytes, ins[i], in_bytes) : relin)
+        {
+            return set_error(MOAI_EINVAL, "member %zu: the output overlaps the input", i);
+        }
+        if (sum && outs[i] != sum && overlap(outs[i], out_bytes, sum, out_bytes))
+        {
+            return set_error(MOAI_EINVAL, "member %zu: the output overlaps the sum", i);
+        }
+        if (sum && sum == ins[i])
+        {
+            return set_error(MOAI_EINVAL, "member %zu: the sum is the input", i); // as moai_apply_galois_acc
+        }
+    }
+    // another member's blocks: passes and workgroups run in no order that a caller could rely on.  Every block sorted by its
+    // start; a block that overlaps an output starts less than the longest block before the output's end, so each output looks at
+    // the few blocks in that window: n log n, not n^2, for the lists a caller may pass (any n).
+    {
+        struct Block
+        {
+            uintptr_t at;
+            size_t bytes, member;
+        };
+        std::vector<Block> blocks;
+        blocks.reserve(3 * n);
+        for (size_t i = 0; i < n; ++i)
+        {
+            blocks.push_back({ (uintptr_t)ins[i], in_bytes, i });
+            blocks.push_back({ (uintptr_t)outs[i], out_bytes, i });
+            if (sums && sums[i])
+            {
+                blocks.push_back({ (uintptr_t)sums[i], out_bytes, i });
+            }
+        }
+        std::sort(blocks.begin(), blocks.end(), [](const Block &x, const Block &y) { return x.at < y.at; });
+        for (size_t i = 0; i < n; ++i)
+        {
+            const uintptr_t lo = (uintptr_t)outs[i], hi = lo + out_bytes;
+            auto it = std::lower_bound(blocks.begin(), blocks.end(), lo > in_bytes ? lo - in_bytes : 0,
+                                       [](const Block &x, uintptr_t v) { return x.at < v; });
+            for (; it != blocks.end() && it->at < hi; ++it)
+            {
+                if (it->member != i && it->at + it->bytes > lo)
+                {
+                    return set_error(MOAI_EINVAL, "member %zu: the output overlaps a block of member %zu", i, it->member);
+                }
+            }
+        }
+    }
+    std::vector<uint32_t> key_rows(n);
+    if (relin)
+    {
+        MOAI_TRY(key_rows_for(c, one_key, L, &key_rows[0]));
+        std::fill(key_rows.begin(), key_rows.end(), key_rows[0]);
+    }
+    for (size_t i = 0; !relin && i < n; ++i)
+    {
+        MOAI_TRY(key_rows_for(c, keys[i], L, &key_rows[i], (long)i));
+    }
+    std::vector<const uint32_t *> tables(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        // relinearize: element 1, the identity permutation -- the gather then only collects the third polynomials
+        MOAI_TRY(galois_table(c, relin ? 1u : elts[i], &tables[i]));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t rows_tmp = relin ? L : 2 * L; // rows per member of the gathered target
+    const size_t sz_list = align256(sizeof(KsList)), sz_tmp = align256(nb * rows_tmp * c->n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    void *wsp;
+    MOAI_TRY(workspace(c, sz_list + sz_tmp + switch_key_ws_bytes(c, L, nb), s, &wsp));
+    KsList *dlist = static_cast<KsList *>(wsp);
+    uint64_t *tmp = at_bytes(wsp, sz_list);
+    return for_chunks(n, KS_LIST_MAX, [&](size_t m0, size_t cnt) {
+        KsList h;
+        for (size_t e = 0; e < KS_LIST_MAX; ++e)
+        {
+            const size_t i = m0 + (e < cnt ? e : 0); // the unused entries repeat the pass's first member
+            h.ins[e] = ins[i];
+            h.outs[e] = outs[i];
+            h.sums[e] = sums ? sums[i] : nullptr;
+            h.keys[e] = relin ? one_key : keys[i];
+            h.tables[e] = tables[i];
+            h.key_rows[e] = key_rows[i];
+        }
+        hipLaunchKernelGGL(ks_list_write_kernel, dim3(1), dim3((uint32_t)KS_LIST_MAX), 0, s, h, dlist);
+        MOAI_LAUNCH_CHECK();
+        if (relin)
+        {
+            // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch_key(c2)   (evaluator.cpp:1383-1392)
+            MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
+            return switch_key_impl(c, nullptr, tmp, L, 0, nullptr, L, cnt, static_cast<char *>(wsp) + sz_list + sz_tmp, s, nullptr, 0, 1,
+                                   nullptr, dlist);
+        }
+        // tmp [cnt][2][L][N] = galois(ins); out = (galois(in0), 0) + switch_key(galois(in1)) [+ sum]   (evaluator.cpp:2631-2654)
+        MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, 2 * L, 0, s));
+        return switch_key_impl(c, nullptr, tmp, 2 * L, L, nullptr, L, cnt, static_cast<char *>(wsp) + sz_list + sz_tmp, s, tmp, 2 * L, 2,
+                               nullptr, dlist);
+    });
+}
+
+} // namespace moai
+
+extern "C" int moai_apply_galois_ptrs(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *galois_elts,
+                                      const uint64_t *const *galois_keys, const uint64_t *const *sums, size_t n, void *stream)
+{
+    for (size_t i = 0; ins && outs && galois_keys && i < n; ++i)
+    {
+        MOAI_AUDIT(stream, ins[i], outs[i], galois_keys[i], sums ? sums[i] : nullptr);
+    }
+    trace_op("apply_galois_to", L, n); // the calls it replaces
+    return ks_ptrs_impl(c, ins, outs, L, galois_elts, galois_keys, nullptr, sums, n, false, stream);
+}
+
+extern "C" int moai_relinearize_ptrs(moai_ctx *c, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *relin_key, size_t L,
+                                     size_t n, void *stream)
+{
+    MOAI_AUDIT(stream, relin_key);
+    for (size_t i = 0; ct3s && outs && i < n; ++i)
+    {
+        MOAI_AUDIT(stream, ct3s[i], outs[i]);
+    }
+    trace_op("relinearize", L, n);
+    return ks_ptrs_impl(c, ct3s, outs, L, nullptr, nullptr, relin_key, nullptr, n, true, stream);
 }
 
 extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L_out, size_t batch, void *stream)

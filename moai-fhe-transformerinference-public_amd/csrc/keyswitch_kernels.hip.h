@@ -10,6 +10,8 @@
 // shared by the batch through L2) instead of 56 B + key for the unfused sequence
 // reduce -> NTT -> NTT -> MAC.
 #pragma once
+#include <type_traits>
+
 #include "ntt_kernels.hip.h"
 
 namespace moai {
@@ -140,6 +142,12 @@ struct KsP2Args
     uint32_t total_work;
 };
 
+// the LIST instantiations take one more argument; the others keep the argument block they always had
+struct KsP2ListArgs : KsP2Args
+{
+    const KsList *lst; // ciphertext b's key is lst->keys[b] with lst->key_rows[b] rows (key and k unused)
+};
+
 // ---- contiguous pass + key MAC, 8 coefficients per thread --------------------------------------------------------
 // With the NTT kernels' 16 coefficients per thread the 2 x 16 128-bit accumulators need 250 VGPRs (two waves
 // per SIMD; measured 6-12 % slower).  Here a workgroup owns a 2048-coefficient tile (8 blocks of 256): radix-8 /
@@ -171,8 +179,11 @@ __device__ __forceinline__ uint32_t phys8_b(uint32_t e)
 // twiddles of stages 0..2 in LDS, no global load at the head of an iteration: bit-identical, 0.496 against 0.502 ms per key switch
 // at l = 35 and 0.120 against 0.118 at l = 15 -- noise.  The wait for the key residues at the head of the MAC also waits for the
 // copy issued before them (vector memory operations complete in order), and the kernel's idle fifth is not this round trip.)
-template <int LOGN, int MODE, int PF = 0>
-__global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
+// LIST: every ciphertext of the batch has its own key and key layout (KsList).  The ciphertext index is uniform over the workgroup,
+// so the key's address and row count are two scalar loads at the head of the workgroup and live in SGPRs like the kernel
+// arguments they replace: the loop over the digits is the same code.
+template <int LOGN, int MODE, int PF = 0, bool LIST = false>
+__global__ __launch_bounds__(256, 4) void ks_contig_mac8(std::conditional_t<LIST, KsP2ListArgs, KsP2Args> a)
 {
     constexpr int R1 = LOGN - 8;
     constexpr uint32_t TPR8 = 1u << (LOGN - 11);
@@ -202,6 +213,13 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
     const Tw *__restrict__ tw = a.tw + ((size_t)prime << LOGN);
     const double *__restrict__ tw1 = a.tw1 + ((size_t)prime << LOGN);
     const uint32_t tid0 = threadIdx.x;
+    const uint64_t *list_key = nullptr;
+    uint32_t list_k = 0;
+    if constexpr (LIST)
+    {
+        list_key = a.lst->keys[bq];
+        list_k = a.lst->key_rows[bq];
+    }
 
     uint64_t lo0[8], hi0[8], lo1[8], hi1[8];
 #pragma unroll
@@ -258,11 +276,13 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(KsP2Args a)
         const uint64_t *__restrict__ base = dig + ((size_t)J << LOGN);
         uint64_t x[8];
         const bool direct = (slot == J); // workgroup-uniform
-        const uint32_t krow = slot == a.L ? a.k - 1 : prime; // the special prime's row is the last one of the key's layout
+        const uint64_t *key = LIST ? list_key : a.key;
+        const uint32_t key_k = LIST ? list_k : a.k;
+        const uint32_t krow = slot == a.L ? key_k - 1 : prime; // the special prime's row is the last one of the key's layout
         const ulonglong2 *__restrict__ k0 =
-            reinterpret_cast<const ulonglong2 *>(a.key + (((size_t)(J * 2 + 0) * a.k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
+            reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 0) * key_k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
         const ulonglong2 *__restrict__ k1 =
-            reinterpret_cast<const ulonglong2 *>(a.key + (((size_t)(J * 2 + 1) * a.k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
+            reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 1) * key_k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
         ulonglong2 kpa[4], kpb[4];
         if (mode_fp(MODE) && PF == 2)
         {
@@ -993,6 +1013,18 @@ struct ModDownArgs
     Tw scal[MOAI_MAX_RNS];
 };
 
+struct ModDownListArgs : ModDownArgs
+{
+    const KsList *lst; // LIST instantiations of moddown_contig: see there
+};
+
+// the same store under a name of its own: the LIST kernels then instantiate their own fwd_contig_tile, and the one the existing
+// kernels inline keeps its single caller (with two callers the compiler simplifies it before inlining, and the existing kernels'
+// instruction streams change)
+struct StoreModDownList : StoreModDown
+{
+};
+
 // (one tile per workgroup: the software-pipelined form of the key switch's strided pass, fwd_strided_tiles, measured the same here --
 // 313 against 308 us per launch at pack 48 -- this pass is bound by its load operation's arithmetic)
 template <int LOGN, int MODE>
@@ -1036,8 +1068,13 @@ __global__ __launch_bounds__(256, 4) void moddown_strided(ModDownArgs a)
     }
 }
 
-template <int LOGN, int MODE>
-__global__ __launch_bounds__(256) void moddown_contig(ModDownArgs a)
+// LIST (key switch only, polynomials 2b and 2b + 1 belong to ciphertext b): the result goes to lst->outs[b] instead of `out`, the
+// second addend is lst->sums[b] where that is not null, and with add_mode 1 the first addend is the matching row of lst->ins[b]
+// (relinearize: c0 and c1 of the member's own block; add_mode 2 keeps reading the permuted c0 from the contiguous `addend`).  A
+// thread reads the chunks it adds before it writes the same chunks, so outs[b] may be sums[b] or ins[b].  b is uniform over the
+// workgroup: three scalar loads.
+template <int LOGN, int MODE, bool LIST = false>
+__global__ __launch_bounds__(256) void moddown_contig(std::conditional_t<LIST, ModDownListArgs, ModDownArgs> a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
     // (the first four stages' twiddles through LDS, as in ntt_fwd_contig, measured slower here -- 756 against 716-739 us per launch:
@@ -1050,7 +1087,8 @@ __global__ __launch_bounds__(256) void moddown_contig(ModDownArgs a)
     const uint32_t tile = w % TPR;
     const uint32_t i = __builtin_amdgcn_readfirstlane(a.sel.idx[w / TPR]);
     const PrimeConst &pc = a.pc[i];
-    StoreModDown st;
+    using Store = std::conditional_t<LIST, StoreModDownList, StoreModDown>;
+    Store st;
     st.acc = reinterpret_cast<const ulonglong2 *>(a.acc + (((size_t)p * a.acc_stride + i) << LOGN)) + ((size_t)tile << 11);
     st.out = reinterpret_cast<ulonglong2 *>(a.out + (((size_t)p * a.Lout + i) << LOGN)) + ((size_t)tile << 11);
     st.q = pc.q;
@@ -1062,12 +1100,24 @@ __global__ __launch_bounds__(256) void moddown_contig(ModDownArgs a)
                  ((size_t)tile << 11);
     }
     st.add2 = a.addend2 ? reinterpret_cast<const ulonglong2 *>(a.addend2 + (((size_t)p * a.Lout + i) << LOGN)) + ((size_t)tile << 11) : nullptr;
+    if constexpr (LIST)
+    {
+        const uint32_t b = p >> 1;
+        const size_t row = ((size_t)(p & 1u) * a.Lout + i) << LOGN; // inside the member's [2][Lout][N]
+        st.out = reinterpret_cast<ulonglong2 *>(a.lst->outs[b] + row) + ((size_t)tile << 11);
+        const uint64_t *sum = a.lst->sums[b];
+        st.add2 = sum ? reinterpret_cast<const ulonglong2 *>(sum + row) + ((size_t)tile << 11) : nullptr;
+        if (a.add_mode == 1)
+        {
+            st.add = reinterpret_cast<const ulonglong2 *>(a.lst->ins[b] + row) + ((size_t)tile << 11);
+        }
+    }
     st.splits = a.acc_splits;
     st.split_stride = a.acc_split_stride >> 1;
     st.use_sc = a.has_scal;
     st.sc = a.scal[i];
     // the tile hands the store canonical integers in every mode
-    fwd_contig_tile<LOGN, MODE, StoreModDown>(a.u + (((size_t)p * a.Lout + i) << LOGN), tile, a.tw + ((size_t)i << LOGN), mode_q<MODE>(pc),
+    fwd_contig_tile<LOGN, MODE, Store>(a.u + (((size_t)p * a.Lout + i) << LOGN), tile, a.tw + ((size_t)i << LOGN), mode_q<MODE>(pc),
                                               mode_q2<MODE>(pc), lds2, threadIdx.x, a.twb + (size_t)i * ((size_t)TPR * 15 * 256), pc.cr1,
                                               st);
 }

@@ -138,6 +138,10 @@ int reserve_for_stream(moai_ctx *c, void *stream, size_t bytes, void **out, bool
 int galois_table(moai_ctx *c, uint32_t elt, const uint32_t **out);
 // out [batch][L][N] = the Galois permutation of polynomial 0 of every ciphertext of in [batch][2][L][N]
 int galois_permute_c0(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t batch, size_t L, uint32_t galois_elt, hipStream_t s);
+// out [members][rows_per_member][N]: rows src_off_rows .. src_off_rows + rows_per_member - 1 of lst->ins[b], permuted by
+// lst->tables[b]; lst is a device pointer (common.h KsList)
+int galois_gather_list(moai_ctx *c, const KsList *lst, uint64_t *out, size_t members, size_t rows_per_member, size_t src_off_rows,
+                       hipStream_t s);
 
 // CKKSEncoder's tables (matrix_reps_index_map_, root_powers_, inv_root_powers_) on the device, built on first use under
 // c->mutex (encoder.hip)

@@ -105,6 +105,8 @@ SYMBOLS = {
     "moai_scalar_dot": (C.c_int, [vp, C.POINTER(vp), u64p, sz, vp, vp, sz, sz, vp]),
     "moai_vector_dot": (C.c_int, [vp, C.POINTER(vp), vp, sz, vp, vp, sz, sz, vp]),
     "moai_ct_dot_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, vp, vp, sz, vp]),
+    "moai_apply_galois_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
+    "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -398,6 +400,24 @@ class Context:
         ax = (vp * T)(*[_ptr(x) for x in xs])
         ay = (vp * T)(*[_ptr(y) for y in ys])
         _check(lib().moai_ct_dot_ptrs(self.h, ax, ay, T, _ptr(base), _ptr(out), L, stream))
+
+    def apply_galois_ptrs(self, ins, outs, L, elts, keys, sums=None, stream=None):
+        """outs[i] = [sums[i] +] apply_galois(ins[i], elts[i], keys[i]) for single ciphertexts [2][L][N] in separate buffers, in
+        one chain of launches; sums: None, or a list whose entries may be None"""
+        n = len(ins)
+        ai = (vp * n)(*[_ptr(x) for x in ins])
+        ao = (vp * n)(*[_ptr(x) for x in outs])
+        e = (C.c_uint32 * n)(*[int(x) for x in elts])
+        ak = (vp * n)(*[_ptr(x) for x in keys])
+        asum = None if sums is None else (vp * n)(*[_ptr(x) for x in sums])
+        _check(lib().moai_apply_galois_ptrs(self.h, ai, ao, L, e, ak, asum, n, stream))
+
+    def relinearize_ptrs(self, ct3s, outs, key, L, stream=None):
+        """outs[i] [2][L][N] = relinearize(ct3s[i] [3][L][N]) with one key, in one chain of launches"""
+        n = len(ct3s)
+        ai = (vp * n)(*[_ptr(x) for x in ct3s])
+        ao = (vp * n)(*[_ptr(x) for x in outs])
+        _check(lib().moai_relinearize_ptrs(self.h, ai, ao, _ptr(key), L, n, stream))
 
     def gather_blocks(self, blocks, packed, words, stream=None):
         """packed[i] = blocks[i] (`words` 64-bit words each) in one launch"""

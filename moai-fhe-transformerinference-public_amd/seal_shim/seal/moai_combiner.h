@@ -7,11 +7,15 @@
 // (1.06 ms at l = 35 against 0.62 ms per ciphertext in a batch; 0.35 against 0.15 ms at l = 15).  Calls that
 // arrive within a short window with the same operation, level and key are therefore executed as ONE batched call:
 // the first caller becomes the group's leader, waits up to `window` for the number of threads recently seen
-// calling (never when only one thread is calling), then gathers the members' ciphertexts into one buffer, issues
-// the batched call and scatters the results; the other members block until that is enqueued.  Every ciphertext
-// gets exactly the operation it asked for, so results do not change; only the grouping of launches does.
-// All waits are bounded; a leader that keeps waiting in vain stops waiting for a while.
+// calling (never when only one thread is calling), then issues one call on the list of the members' own blocks
+// (moai_apply_galois_ptrs / moai_relinearize_ptrs: no gather or scatter copies); the other members block until
+// that is enqueued.  Every ciphertext gets exactly the operation it asked for, so results do not change; only the
+// grouping of launches does.  A group holds at most max_batch() members: a caller that finds the open group full
+// leads a new one.  All waits are bounded; a leader that keeps waiting in vain stops waiting for a while.
 // MOAI_SHIM_COMBINE_US sets the window in microseconds (default 500, 0 turns combining off).
+// With MOAI_SHIM_COMBINE_ANY_KEY=1 (seal.h util::combine_any_key) the evaluator leaves the Galois element and the key
+// out of a rotation's group key: concurrent rotations of one level then meet whatever their step, each member with
+// the element and key its Request carries.
 #pragma once
 #include <array>
 #include <atomic>
@@ -38,6 +42,8 @@ namespace seal
             {
                 const std::uint64_t *in;
                 std::uint64_t *out;
+                std::uint32_t elt = 0;              // the member's own Galois element and key: what a leader passes per
+                const std::uint64_t *key = nullptr; // member when the group key does not fix them
             };
             // operation kind, level (RNS rows), Galois element or 0, key pointer, device context
             using Key = std::tuple<int, std::size_t, std::uint32_t, const void *, const void *>;
@@ -59,9 +65,9 @@ namespace seal
                 note_caller(now);
                 std::unique_lock<std::mutex> lk(mu_);
                 auto it = open_.find(key);
-                if (it != open_.end())
+                if (it != open_.end() && it->second->reqs.size() < max_batch_)
                 {
-                    // join the open group
+                    // join the open group (a full one is left to its leader: this caller leads the next)
                     std::shared_ptr<Group> g = it->second;
                     g->reqs.push_back(r);
                     if (g->reqs.size() >= g->target)
@@ -83,11 +89,17 @@ namespace seal
                 const bool wait = g->target > 1 && now >= cooldown_until_;
                 if (wait)
                 {
-                    open_[key] = g;
+                    open_[key] = g; // (in the place of a full group, if there is one)
                     g->cv_leader.wait_for(lk, std::chrono::microseconds(window_us_), [&] { return g->reqs.size() >= g->target; });
-                    open_.erase(key);
+                    auto mine = open_.find(key);
+                    if (mine != open_.end() && mine->second == g)
+                    {
+                        open_.erase(mine);
+                    }
                 }
                 std::vector<Request> reqs = g->reqs; // closed: nobody can find the group any more
+                std::size_t &largest = largest_[std::get<0>(key)];
+                largest = reqs.size() > largest ? reqs.size() : largest;
                 if (wait)
                 {
                     if (reqs.size() == 1)
@@ -122,6 +134,26 @@ namespace seal
                 if (err)
                 {
                     std::rethrow_exception(err);
+                }
+            }
+
+            std::size_t max_batch() const
+            {
+                return max_batch_;
+            }
+            // the largest group executed so far for an operation kind (the first field of Key): whether callers have met
+            std::size_t largest_group(int kind)
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                auto it = largest_.find(kind);
+                return it == largest_.end() ? 0 : it->second;
+            }
+            // a combiner of its own for a test or a tool: the window in microseconds and the group cap
+            explicit OpCombiner(long window_us, std::size_t max_batch = 64) : window_us_(window_us), max_batch_(max_batch ? max_batch : 1)
+            {
+                for (auto &t : seen_)
+                {
+                    t.store(0);
                 }
             }
 
@@ -167,6 +199,7 @@ namespace seal
             std::size_t max_batch_ = 64;
             std::mutex mu_;
             std::map<Key, std::shared_ptr<Group>> open_;
+            std::map<int, std::size_t> largest_;
             std::array<std::atomic<std::int64_t>, 257> seen_;
             int misses_ = 0;
             std::int64_t cooldown_until_ = 0;

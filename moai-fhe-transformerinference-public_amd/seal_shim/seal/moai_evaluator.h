@@ -280,7 +280,6 @@ namespace seal
             if (encrypted.batch() == 1 && comb.enabled())
             {
                 const std::uint64_t *key = relin_keys.device_key(0, L);
-                const std::size_t rn = L * encrypted.poly_modulus_degree();
                 comb.submit(util::OpCombiner::Key(1, L, 0, key, dev()), { encrypted.device_data(), out.device_data() },
                             [&](const std::vector<util::OpCombiner::Request> &reqs) {
                                 if (reqs.size() == 1)
@@ -288,10 +287,15 @@ namespace seal
                                     hip(moai_relinearize(dev(), reqs[0].in, key, reqs[0].out, L, 1, st()));
                                     return;
                                 }
-                                util::DeviceArray tin(reqs.size() * 3 * rn, st()), tout(reqs.size() * 2 * rn, st());
-                                gather_requests(dev(), reqs, tin.get(), 3 * rn, st());
-                                hip(moai_relinearize(dev(), tin.get(), key, tout.get(), L, reqs.size(), st()));
-                                scatter_requests(dev(), reqs, tout.get(), 2 * rn, st());
+                                // one call on the members' own blocks
+                                std::vector<const std::uint64_t *> ins(reqs.size());
+                                std::vector<std::uint64_t *> outs(reqs.size());
+                                for (std::size_t i = 0; i < reqs.size(); i++)
+                                {
+                                    ins[i] = reqs[i].in;
+                                    outs[i] = reqs[i].out;
+                                }
+                                hip(moai_relinearize_ptrs(dev(), ins.data(), outs.data(), key, L, reqs.size(), st()));
                             });
             }
             else
@@ -907,26 +911,34 @@ namespace seal
             }
         }
 
-        // the members' blocks <-> one packed array, one launch each way (moai_gather_blocks / moai_scatter_blocks)
-        static void gather_requests(moai_ctx *d, const std::vector<util::OpCombiner::Request> &reqs, std::uint64_t *packed, std::size_t words,
-                                    void *stream)
+        // A single-ciphertext rotation through the call combiner: concurrent callers with the same level -- and, unless
+        // MOAI_SHIM_COMBINE_ANY_KEY=1, the same element and key -- share one moai_apply_galois_ptrs call on their own blocks.  A
+        // group of one is the single call it always was.
+        static void combined_rotation(moai_ctx *d, const std::uint64_t *in, std::uint64_t *out, std::size_t L, std::uint32_t elt,
+                                      const std::uint64_t *key, void *stream)
         {
-            const std::uint64_t *ptrs[64];
-            for (std::size_t i = 0; i < reqs.size(); i++)
-            {
-                ptrs[i] = reqs[i].in;
-            }
-            util::hip_check(moai_gather_blocks(d, ptrs, packed, reqs.size(), words, stream));
-        }
-        static void scatter_requests(moai_ctx *d, const std::vector<util::OpCombiner::Request> &reqs, const std::uint64_t *packed, std::size_t words,
-                                     void *stream)
-        {
-            std::uint64_t *ptrs[64];
-            for (std::size_t i = 0; i < reqs.size(); i++)
-            {
-                ptrs[i] = reqs[i].out;
-            }
-            util::hip_check(moai_scatter_blocks(d, packed, ptrs, reqs.size(), words, stream));
+            util::OpCombiner &comb = util::OpCombiner::instance();
+            const bool any = util::combine_any_key();
+            comb.submit(util::OpCombiner::Key(0, L, any ? 0 : elt, any ? nullptr : key, d), { in, out, elt, key },
+                        [&](const std::vector<util::OpCombiner::Request> &reqs) {
+                            if (reqs.size() == 1)
+                            {
+                                util::hip_check(moai_apply_galois_to(d, reqs[0].in, reqs[0].out, L, reqs[0].elt, reqs[0].key, 1, stream));
+                                return;
+                            }
+                            const std::size_t m = reqs.size();
+                            std::vector<const std::uint64_t *> ins(m), keys(m);
+                            std::vector<std::uint64_t *> outs(m);
+                            std::vector<std::uint32_t> elts(m);
+                            for (std::size_t i = 0; i < m; i++)
+                            {
+                                ins[i] = reqs[i].in;
+                                outs[i] = reqs[i].out;
+                                elts[i] = reqs[i].elt;
+                                keys[i] = reqs[i].key;
+                            }
+                            util::hip_check(moai_apply_galois_ptrs(d, ins.data(), outs.data(), L, elts.data(), keys.data(), nullptr, m, stream));
+                        });
         }
         // SEAL/evaluator.cpp:155-240 / :263-350
         // a deferred rotation that is made alone goes through the call combiner, like an eager one
@@ -935,24 +947,12 @@ namespace seal
             static const bool once = [] {
                 util::single_rotation_hook() = [](moai_ctx *d, const std::uint64_t *in, std::uint64_t *out, std::size_t L, std::uint32_t elt,
                                                   const std::uint64_t *key, void *stream) {
-                    util::OpCombiner &comb = util::OpCombiner::instance();
-                    if (!comb.enabled())
+                    if (!util::OpCombiner::instance().enabled())
                     {
                         util::hip_check(moai_apply_galois_to(d, in, out, L, elt, key, 1, stream));
                         return;
                     }
-                    const std::size_t words = 2 * L * moai_ctx_coeff_count(d);
-                    comb.submit(util::OpCombiner::Key(0, L, elt, key, d), { in, out }, [&](const std::vector<util::OpCombiner::Request> &reqs) {
-                        if (reqs.size() == 1)
-                        {
-                            util::hip_check(moai_apply_galois_to(d, reqs[0].in, reqs[0].out, L, elt, key, 1, stream));
-                            return;
-                        }
-                        util::DeviceArray tmp(reqs.size() * words, stream);
-                        gather_requests(d, reqs, tmp.get(), words, stream);
-                        util::hip_check(moai_apply_galois(d, tmp.get(), L, elt, key, reqs.size(), stream));
-                        scatter_requests(d, reqs, tmp.get(), words, stream);
-                    });
+                    combined_rotation(d, in, out, L, elt, key, stream);
                 };
                 return true;
             }();
@@ -1289,20 +1289,8 @@ namespace seal
             util::OpCombiner &comb = util::OpCombiner::instance();
             if (src.batch() == 1 && comb.enabled())
             {
-                // concurrent callers with the same element, level and key share one batched key switch
-                const std::size_t words = 2 * L * src.poly_modulus_degree();
-                comb.submit(util::OpCombiner::Key(0, L, galois_elt, key, dev()), { in_ptr, out_ptr },
-                            [&](const std::vector<util::OpCombiner::Request> &reqs) {
-                                if (reqs.size() == 1)
-                                {
-                                    hip(moai_apply_galois_to(dev(), reqs[0].in, reqs[0].out, L, galois_elt, key, 1, st()));
-                                    return;
-                                }
-                                util::DeviceArray tmp(reqs.size() * words, st());
-                                gather_requests(dev(), reqs, tmp.get(), words, st());
-                                hip(moai_apply_galois(dev(), tmp.get(), L, galois_elt, key, reqs.size(), st()));
-                                scatter_requests(dev(), reqs, tmp.get(), words, st());
-                            });
+                // concurrent callers with the same element, level and key share one key switch
+                combined_rotation(dev(), in_ptr, out_ptr, L, galois_elt, key, st());
                 return;
             }
             if (in_ptr == out_ptr)

@@ -814,6 +814,18 @@ namespace seal
             static std::function<void(moai_ctx *, const std::uint64_t *, std::uint64_t *, std::size_t, std::uint32_t, const std::uint64_t *, void *)> h;
             return h;
         }
+        // MOAI_SHIM_COMBINE_ANY_KEY=1 (read once): single-ciphertext rotations of one level share a key switch whatever their step
+        // -- the pending rotations of one thread (rot_resolve) and the concurrent callers of the call combiner (moai_combiner.h)
+        // -- through moai_apply_galois_ptrs, where every member has its own element and key.  Off by default: the grouping, and with
+        // it the sequence of launches, stays as it was.  The results are the same bits either way.
+        inline bool combine_any_key()
+        {
+            static const bool on = [] {
+                const char *e = std::getenv("MOAI_SHIM_COMBINE_ANY_KEY");
+                return e && e[0] == '1';
+            }();
+            return on;
+        }
         inline std::vector<std::weak_ptr<RotState>> &rot_registry()
         {
             static thread_local std::vector<std::weak_ptr<RotState>> r;
@@ -843,11 +855,13 @@ namespace seal
         {
             std::unique_lock<std::mutex> mine(me->mu);
             RotationCache &cache = RotationCache::instance();
+            const bool any_key = combine_any_key();
             while (!me->elts.empty())
             {
                 const std::uint32_t e = me->elts.front();
                 const DeviceArray *key = me->keys.front().get();
-                // peers: pending rotations registered by this thread with the same next step
+                // peers: pending rotations registered by this thread with the same next step (any_key: of the same level, whatever
+                // their next step and key)
                 std::vector<std::shared_ptr<RotState>> group{ me };
                 std::vector<std::unique_lock<std::mutex>> held;
                 for (auto &w : rot_registry())
@@ -858,8 +872,8 @@ namespace seal
                         continue;
                     }
                     std::unique_lock<std::mutex> lk(p->mu, std::try_to_lock);
-                    if (lk.owns_lock() && !p->elts.empty() && p->elts.front() == e && p->keys.front().get() == key && p->L == me->L && p->dev == me->dev &&
-                        p->n == me->n)
+                    if (lk.owns_lock() && !p->elts.empty() && (any_key || (p->elts.front() == e && p->keys.front().get() == key)) && p->L == me->L &&
+                        p->dev == me->dev && p->n == me->n)
                     {
                         group.push_back(p);
                         held.push_back(std::move(lk));
@@ -873,7 +887,7 @@ namespace seal
                 for (std::size_t i = 0; i < group.size(); i++)
                 {
                     RotState &g = *group[i];
-                    ckeys[i] = RotationCache::Key(g.src.get(), e, g.key_ids.front().first, g.key_ids.front().second, g.L);
+                    ckeys[i] = RotationCache::Key(g.src.get(), g.elts.front(), g.key_ids.front().first, g.key_ids.front().second, g.L);
                     next[i] = cache.enabled() ? cache.find(ckeys[i]) : nullptr;
                     if (!next[i])
                     {
@@ -886,13 +900,31 @@ namespace seal
                     auto out = std::make_shared<DeviceArray>(words, g.stream);
                     if (single_rotation_hook())
                     {
-                        single_rotation_hook()(g.dev, g.src->get(), out->get(), g.L, e, key->get(), g.stream);
+                        single_rotation_hook()(g.dev, g.src->get(), out->get(), g.L, g.elts.front(), g.keys.front()->get(), g.stream);
                     }
                     else
                     {
-                        hip_check(moai_apply_galois_to(g.dev, g.src->get(), out->get(), g.L, e, key->get(), 1, g.stream));
+                        hip_check(moai_apply_galois_to(g.dev, g.src->get(), out->get(), g.L, g.elts.front(), g.keys.front()->get(), 1, g.stream));
                     }
                     next[todo[0]] = out;
+                }
+                else if (todo.size() > 1 && any_key)
+                {
+                    // one call on the members' own blocks, each with its own element and key: no copies into a packed block
+                    const std::size_t m = todo.size();
+                    std::vector<const std::uint64_t *> ins(m), kptr(m);
+                    std::vector<std::uint64_t *> outs(m);
+                    std::vector<std::uint32_t> elts(m);
+                    for (std::size_t t = 0; t < m; t++)
+                    {
+                        RotState &g = *group[todo[t]];
+                        next[todo[t]] = std::make_shared<DeviceArray>(words, g.stream);
+                        ins[t] = g.src->get();
+                        outs[t] = next[todo[t]]->get();
+                        elts[t] = g.elts.front();
+                        kptr[t] = g.keys.front()->get();
+                    }
+                    hip_check(moai_apply_galois_ptrs(me->dev, ins.data(), outs.data(), me->L, elts.data(), kptr.data(), nullptr, m, me->stream));
                 }
                 else if (todo.size() > 1)
                 {
