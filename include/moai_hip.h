@@ -585,7 +585,8 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
- *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller */
+ *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
+ *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
 /* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of
@@ -690,6 +691,55 @@ int moai_expand_seeded_limited(moai_ctx *ctx, const uint8_t *seed, uint64_t seq,
                                void *stream);
 /* the layout record of moai_key_trim for a block filled elsewhere (SEAL/evaluator.cpp:2818,2831) */
 int moai_key_register(moai_ctx *ctx, const uint64_t *key, size_t levels);
+
+/* ---- hybrid key switching: alpha special primes, digits of alpha primes ---------------------------------------------------
+ * Evaluator::switch_key_inplace decomposes per RNS prime and has one special prime: at l data primes l^2 + 3l + 2 transforms
+ * and a key of l digits.  The hybrid form groups alpha primes into a digit and takes the last alpha primes of the context as
+ * the special modulus; SEAL's switch is exactly its alpha = 1 case (same key layout, same mod-up, same rounding mod-down), and
+ * at alpha = 1 every entry point below is bit for bit its counterpart above.  For alpha > 1 the results differ from the
+ * reference in noise only, and are bit for bit the integer restatement tests/hybrid_ref.py.  Opt-in: nothing else uses it.
+ *
+ * All values are canonical residues.  Context primes m_0 .. m_{k-1}, 1 <= alpha < k (and alpha <= 16):
+ *   special primes  p_t = m_{k-alpha+t}, t < alpha;  P their product;  h = floor(P / 2)
+ *   data primes     q_i = m_i, i < Lmax = k - alpha
+ *   digits at L     R_j = { r : j alpha <= r < min((j+1) alpha, L) }, j < beta(L) = ceil(L / alpha);  D_j = prod_{r in R_j} q_r
+ * Key for s' under s: [beta(Lmax)][2][k][N] at the key level.  Digit j is a symmetric encryption of zero over all k rows with
+ * noise and uniform half from sequence seq + j of the stream contract above (as moai_kswitch_keygen), plus (P mod q_r) s'[r] in
+ * row r of c0 for every r of the top-level digit j.  A switch at L reads digits j < beta(L), rows {0 .. L-1} and {k-alpha .. k-1}.
+ * Switch of target c [L][N] (NTT form) into ct [2][L][N]:
+ *   1. c_r = INTT(c[r]), r < L
+ *   2. mod-up, per digit j: y_r = c_r [(D_j / q_r)^-1]_{q_r} mod q_r for r in R_j; for every row m among q_i (i < L, i not in R_j)
+ *      and p_t:  chat_j mod m = (sum_{r in R_j} y_r ((D_j / q_r) mod m)) mod m;  for m = q_r, r in R_j, chat_j is the NTT-form row
+ *      c[r] as it is
+ *   3. forward NTT of the converted rows
+ *   4. acc[p][row] = sum_j chat_j[row] (*) key[j][p][row] mod m_row, p in {0, 1}
+ *   5. mod-down with rounding, per p: x_t = INTT(acc[p][p_t]);  y_t = ((x_t + h mod p_t) mod p_t) [(P / p_t)^-1]_{p_t} mod p_t;
+ *      conv_i = ((sum_t y_t ((P / p_t) mod q_i)) - (h mod q_i)) mod q_i;  ct[p][i] += (acc[p][i] - NTT(conv_i)) [P^-1]_{q_i} mod q_i
+ * Noise: with keys from moai_hybrid_keygen (|e| <= 21) the output satisfies d0 + d1 s = c s' + E (mod Q_L) with
+ *   |E| <= beta(L) N alpha 21 D_max / P + (alpha - 1/2)(1 + |s|_1),  D_max the largest D_j at that level;
+ * P >= D_max keeps the first term small (a precondition of use, not checked: SEAL does not impose it at alpha = 1).
+ * Shapes and aliasing follow moai_switch_key, moai_relinearize and moai_apply_galois.  Nothing is enqueued when an argument is
+ * refused: MOAI_EINVAL with a message for a null context or pointer, alpha = 0, alpha >= k or alpha > 16, L = 0 or
+ * L > k - alpha, an even Galois element or one >= 2N, a sequence range beyond 2^56.  batch = 0 is MOAI_OK.  Scratch per
+ * ciphertext is beta (L + alpha) + 4L + 4 alpha rows of N words (2L more for apply_galois) from the stream's workspace; a batch
+ * runs in chunks that fit MOAI_HYBRID_TMP_KB.  The first call at a new (L, alpha) builds that pair's constants with a blocking
+ * copy, as the first use of a Galois element builds its table; otherwise no call synchronises.  moai_op_trace counts the calls
+ * as "switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid" and "hybrid_keygen". */
+/* beta(L) = ceil(L / alpha), the digits SEAL/evaluator.cpp:2724-3020 would loop over at alpha = 1; 0 and the error set when refused */
+size_t moai_hybrid_digits(const moai_ctx *ctx, size_t alpha, size_t L);
+/* KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336, with digits of alpha primes and P for the special prime */
+int moai_hybrid_keygen(moai_ctx *ctx, const uint8_t *key /* host, 32 */, uint64_t seq, const uint64_t *sk_ntt /* [k][N] */,
+                       const uint64_t *new_key_ntt /* [k][N], rows < k-alpha read */, size_t alpha,
+                       uint64_t *out /* [beta(k-alpha)][2][k][N] */, void *stream);
+/* Evaluator::switch_key_inplace, SEAL/evaluator.cpp:2724-3020, in the hybrid form; ct [batch][2][L][N] in place, target [batch][L][N] */
+int moai_switch_key_hybrid(moai_ctx *ctx, uint64_t *ct, const uint64_t *target, const uint64_t *key, size_t L, size_t alpha,
+                           size_t batch, void *stream);
+/* Evaluator::relinearize_internal over the hybrid switch (SEAL/evaluator.cpp:2724-3020): ct3 [batch][3][L][N] -> out [batch][2][L][N] */
+int moai_relinearize_hybrid(moai_ctx *ctx, const uint64_t *ct3, const uint64_t *key, uint64_t *out, size_t L, size_t alpha,
+                            size_t batch, void *stream);
+/* Evaluator::apply_galois_inplace over the hybrid switch (SEAL/evaluator.cpp:2724-3020): ct [batch][2][L][N] in place */
+int moai_apply_galois_hybrid(moai_ctx *ctx, uint64_t *ct, size_t L, size_t alpha, uint32_t galois_elt, const uint64_t *key,
+                             size_t batch, void *stream);
 
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be

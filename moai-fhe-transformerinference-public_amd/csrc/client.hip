@@ -641,6 +641,14 @@ extern "C" int moai_encrypt_symmetric_seeded(moai_ctx *c, const uint8_t *noise_k
     return encrypt_symmetric_entry(c, noise_key, seed, seq, sk_ntt, plain, out_c0, n_batch, L, prime_index, stream);
 }
 
+namespace moai {
+int encrypt_zero_key_level(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, uint64_t *out, size_t n_batch,
+                           hipStream_t s)
+{
+    return encrypt_symmetric_entry(c, key, nullptr, seq, sk_ntt, nullptr, out, n_batch, c ? c->k : 0, nullptr, (void *)s);
+}
+} // namespace moai
+
 static int kswitch_keygen_entry(moai_ctx *c, const uint8_t *key, const uint8_t *seed, uint64_t seq, const uint64_t *sk_ntt,
                                 const uint64_t *new_key_ntt, uint64_t *out, void *stream, const uint8_t *seal_seeds = nullptr,
                                 uint32_t *rejected = nullptr)

@@ -191,6 +191,8 @@ struct moai_ctx
         uint32_t digits, rows;
     };
     std::map<const void *, KeyLayout> key_layouts;
+    // constants of the hybrid key switch (hybrid.hip HyTable), one device block per (L, alpha), built on first use under op_mutex
+    std::map<std::pair<size_t, size_t>, void *> hybrid_tables;
     void *mutex = nullptr;
     // serialises the enqueue of multi-kernel operations that share a stream's workspace arena: callers
     // on different host threads may target the same stream (MOAI's OpenMP loops do)

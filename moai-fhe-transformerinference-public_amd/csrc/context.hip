@@ -653,6 +653,10 @@ extern "C" void moai_ctx_destroy(moai_ctx *c)
     {
         (void)hipFree(kv.second);
     }
+    for (auto &kv : c->hybrid_tables)
+    {
+        (void)hipFree(kv.second);
+    }
     delete static_cast<std::mutex *>(c->mutex);
     delete static_cast<std::mutex *>(c->op_mutex);
     delete c;

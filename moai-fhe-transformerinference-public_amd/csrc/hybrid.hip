@@ -1,0 +1,689 @@
+// hybrid.hip -- hybrid key switching: alpha special primes, digits of alpha data primes.
+//
+// Reference: Evaluator::switch_key_inplace (SEAL/evaluator.cpp:2724-3020) and KeyGenerator::generate_one_kswitch_key
+// (SEAL/keygenerator.cpp:303-336) are exactly the alpha = 1 case of what is computed here; include/moai_hip.h, section
+// "hybrid key switching", states the algorithm for any alpha and tests/hybrid_ref.py restates it in integers.
+//
+// Context primes m_0 .. m_{k-1}: special p_t = m_{k-alpha+t}, P their product; data q_i = m_i, i < k - alpha.  At L data primes
+// digit j < beta = ceil(L / alpha) is the rows R_j = [j alpha, min((j+1) alpha, L)), D_j their product.
+//
+// Structure on the device, unfused, per chunk of the batch (scratch per ciphertext: hy_rows_per_ct rows of N words):
+//   t        = INTT(target)                                                     [B][L][N]
+//   ext_j    = hy_convert_kernel: digit j from base R_j to every other row      [B][L - |R_j| + alpha][N], then forward NTT
+//              (rows of R_j are not converted: the MAC reads the target's own NTT-form rows)
+//   acc      = hy_mac_kernel: sum_j ext_j (*) key[j][p][row], 128-bit sums      [B][2][L + alpha][N]
+//   x        = INTT(special rows of acc)                                        [2B][alpha][N]
+//   conv     = hy_convert_kernel: base {p_t} -> {q_i} with the rounding terms   [2B][L][N], then forward NTT
+//   out      = hy_finalize_kernel: addend + (acc - conv) P^-1
+// Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
+// that the context owns.
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "hostmath.h"
+#include "launch.h"
+#include "modarith.hip.h"
+
+namespace moai {
+
+// a digit's source rows are held in registers by the conversion kernel; the constants are products of at most this many residues
+constexpr uint32_t HY_MAX_ALPHA = 16;
+
+// One fast base conversion: sources r < nsrc under context primes src_prime[r], targets t < ntgt under tgt_prime[t]:
+//   y_r = ((x_r + src_pre[r]) mod s_r) * src_inv[r] mod s_r,   out_t = ((sum_r y_r w[t][r]) - tgt_post[t]) mod m_t
+// mod-up of digit j: src_pre = tgt_post = 0, src_inv = (D_j / q_r)^-1, w = (D_j / q_r) mod m_t
+// mod-down:          src_pre = floor(P / 2) mod p_t, tgt_post = floor(P / 2) mod q_i, src_inv = (P / p_t)^-1, w = (P / p_t) mod q_i
+struct alignas(16) HyConv
+{
+    uint32_t nsrc, ntgt, pad[2];
+    uint32_t src_prime[HY_MAX_ALPHA];
+    uint32_t tgt_prime[MOAI_MAX_RNS];
+    Tw src_inv[HY_MAX_ALPHA];
+    uint64_t src_pre[HY_MAX_ALPHA];
+    uint64_t tgt_post[MOAI_MAX_RNS];
+    uint64_t w[MOAI_MAX_RNS][HY_MAX_ALPHA];
+};
+
+// the constants of a switch at (L, alpha): conv[j], j < beta, are the mod-ups and conv[beta] is the mod-down
+struct alignas(16) HyTable
+{
+    Tw pinv[MOAI_MAX_RNS]; // P^-1 mod q_i
+    HyConv conv[1];
+};
+
+// (hi * 2^64 + lo) mod q for ANY 128-bit value: barrett128's quotient is short of the true one by at most 2 there, so one more
+// conditional subtraction makes the residue canonical (a source residue is below ITS prime, which may be far above the target's)
+__device__ __forceinline__ uint64_t hy_mod128(uint64_t lo, uint64_t hi, uint64_t q, uint64_t cr0, uint64_t cr1)
+{
+    return csub(barrett128(lo, hi, q, cr0, cr1), q);
+}
+
+struct HyConvArgs
+{
+    const uint64_t *src; // polynomial b's source row r at row b * src_stride + src_off + r, coefficient form, canonical
+    uint64_t *dst;       // [B][ntgt][N], canonical
+    const HyConv *cv;
+    const PrimeConst *pc;
+    uint32_t src_stride, src_off;
+    uint32_t n2;
+};
+
+// blockIdx.y = polynomial.  A thread reads the nsrc <= AMAX source residues of its two coefficients once, scales them, and walks
+// the target rows: per target nsrc 128-bit multiply-adds (at most 16 products below 2^122) and one reduction.  The constants are
+// indexed by uniform values: scalar loads.
+template <int AMAX>
+__global__ __launch_bounds__(256) void hy_convert_kernel(HyConvArgs g)
+{
+    const HyConv &cv = *g.cv;
+    const uint32_t ns = cv.nsrc, nt = cv.ntgt;
+    const size_t n2 = g.n2;
+    const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(g.src) + ((size_t)blockIdx.y * g.src_stride + g.src_off) * n2;
+    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(g.dst) + (size_t)blockIdx.y * nt * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    {
+        ulonglong2 y[AMAX];
+#pragma unroll
+        for (int r = 0; r < AMAX; ++r)
+        {
+            y[r] = make_ulonglong2(0, 0);
+            if ((uint32_t)r < ns)
+            {
+                const uint64_t q = g.pc[cv.src_prime[r]].q, pre = cv.src_pre[r];
+                const Tw inv = cv.src_inv[r];
+                const ulonglong2 v = s[(size_t)r * n2 + j];
+                y[r].x = csub(mul_shoup_lazy(csub(v.x + pre, q), inv.w, inv.wq, q), q);
+                y[r].y = csub(mul_shoup_lazy(csub(v.y + pre, q), inv.w, inv.wq, q), q);
+            }
+        }
+        for (uint32_t t = 0; t < nt; ++t)
+        {
+            const PrimeConst *pc = g.pc + cv.tgt_prime[t];
+            const uint64_t m = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, post = cv.tgt_post[t];
+            uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
+#pragma unroll
+            for (int r = 0; r < AMAX; ++r)
+            {
+                if ((uint32_t)r < ns)
+                {
+                    mac2(lx, hx, ly, hy, y[r], cv.w[t][r]);
+                }
+            }
+            ulonglong2 o;
+            o.x = submod(hy_mod128(lx, hx, m, cr0, cr1), post, m);
+            o.y = submod(hy_mod128(ly, hy, m, cr0, cr1), post, m);
+            d[(size_t)t * n2 + j] = o;
+        }
+    }
+}
+
+struct HyMacArgs
+{
+    const uint64_t *ext;   // digit j's converted rows at ext + j * B * L * N: [B][L - |R_j| + alpha][N], NTT form
+    const uint64_t *tgt;   // ciphertext b's NTT-form target row r at row b * tgt_stride + tgt_off + r
+    const uint64_t *key;   // [beta(k - alpha)][2][k][N]
+    uint64_t *acc;         // [B][2][L + alpha][N]
+    const PrimeConst *pc;
+    uint32_t tgt_stride, tgt_off;
+    uint32_t L, alpha, beta, k;
+    uint32_t n2;
+};
+
+// acc[b][p][row] = sum_{j < beta} digit_j[row] (*) key[j][p][row]; blockIdx.x = b (the workgroups that read the same key words
+// are dispatched together), blockIdx.z = row.  At most 63 products below 2^122 per sum: no fold before the one reduction.
+__global__ __launch_bounds__(256) void hy_mac_kernel(HyMacArgs g)
+{
+    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
+    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
+    const PrimeConst *pc = g.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = g.n2;
+    const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
+    const ulonglong2 *tgt = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)b * g.tgt_stride + g.tgt_off) * n2;
+    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + (size_t)prime * n2;
+    ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (g.L + g.alpha) + row) * n2;
+    ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (g.L + g.alpha) + row) * n2;
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < g.n2; x += gridDim.y * 256u)
+    {
+        uint64_t l0x = 0, h0x = 0, l0y = 0, h0y = 0, l1x = 0, h1x = 0, l1y = 0, h1y = 0;
+        for (uint32_t j = 0; j < g.beta; ++j)
+        {
+            const uint32_t lo = j * g.alpha, hi = min(lo + g.alpha, g.L), nr = hi - lo;
+            const ulonglong2 *op;
+            if (row >= lo && row < hi)
+            {
+                op = tgt + (size_t)row * n2; // the digit under one of its own primes is the target's row as it is
+            }
+            else
+            {
+                const uint32_t pos = row < lo ? row : row - nr;
+                op = ext + ((size_t)j * B * g.L + (size_t)b * (g.L - nr + g.alpha) + pos) * n2;
+            }
+            const ulonglong2 o = op[x];
+            const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * g.k * n2 + x];
+            const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * g.k * n2 + x];
+            mac2(l0x, h0x, l0y, h0y, o, k0);
+            mac2(l1x, h1x, l1y, h1y, o, k1);
+        }
+        acc0[x] = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
+        acc1[x] = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
+    }
+}
+
+struct HyFinalArgs
+{
+    const uint64_t *acc;  // [2B][L + alpha][N]
+    const uint64_t *conv; // [2B][L][N], NTT form
+    uint64_t *out;        // [2B][L][N]
+    const Tw *pinv;
+    const PrimeConst *pc;
+    const uint64_t *addend; // polynomial p of ciphertext b at row b * addend_bstride + p * L
+    uint32_t addend_bstride;
+    int add_mode;           // 1: both polynomials get their addend, 2: polynomial 0 only
+    uint32_t L, alpha;
+    uint32_t n2;
+};
+
+// out = addend + (acc - conv) * P^-1 mod q_i; blockIdx.y = (b, p, i)
+__global__ __launch_bounds__(256) void hy_finalize_kernel(HyFinalArgs g)
+{
+    const uint32_t pp = blockIdx.y / g.L, i = blockIdx.y % g.L;
+    const uint64_t q = g.pc[i].q;
+    const Tw inv = g.pinv[i];
+    const size_t n2 = g.n2;
+    const ulonglong2 *a = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)pp * (g.L + g.alpha) + i) * n2;
+    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.conv) + (size_t)blockIdx.y * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
+    const bool add = g.add_mode == 1 || !(pp & 1u);
+    const ulonglong2 *ad =
+        reinterpret_cast<const ulonglong2 *>(g.addend) + ((size_t)(pp >> 1) * g.addend_bstride + (size_t)(pp & 1u) * g.L + i) * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    {
+        const ulonglong2 x = a[j], y = u[j];
+        ulonglong2 r;
+        r.x = csub(mul_shoup_lazy(x.x + q - y.x, inv.w, inv.wq, q), q);
+        r.y = csub(mul_shoup_lazy(x.y + q - y.y, inv.w, inv.wq, q), q);
+        if (add)
+        {
+            r = add2(r, ad[j], q);
+        }
+        o[j] = r;
+    }
+}
+
+struct HyKeyAddArgs
+{
+    uint64_t *key;          // [beta][2][k][N]
+    const uint64_t *newkey; // [k][N], rows < k - alpha read
+    const PrimeConst *pc;
+    uint64_t fac[MOAI_MAX_RNS]; // P mod q_r
+    uint32_t alpha, k;
+    uint32_t n2;
+};
+
+// row r of c0 of digit r / alpha += (P mod q_r) * newkey[r]      (keygenerator.cpp:315-333 with P for the special prime)
+__global__ __launch_bounds__(256) void hy_key_add_kernel(HyKeyAddArgs g)
+{
+    const uint32_t r = blockIdx.y;
+    const PrimeConst *pc = g.pc + r;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, fac = g.fac[r];
+    const size_t n2 = g.n2;
+    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(g.key) + ((size_t)(r / g.alpha) * 2 * g.k + r) * n2;
+    const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(g.newkey) + (size_t)r * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    {
+        const ulonglong2 v = s[j];
+        ulonglong2 c = d[j];
+        c.x = csub(c.x + mulmod_barrett(v.x, fac, q, cr0, cr1), q);
+        c.y = csub(c.y + mulmod_barrett(v.y, fac, q, cr0, cr1), q);
+        d[j] = c;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+static inline size_t hy_beta(size_t L, size_t alpha)
+{
+    return (L + alpha - 1) / alpha;
+}
+
+static inline size_t hy_align(size_t x)
+{
+    return (x + 255) & ~(size_t)255;
+}
+
+static inline dim3 hy_grid(const moai_ctx *c, size_t rows)
+{
+    const uint32_t bx = (uint32_t)(((c->n >> 1) + 255) / 256);
+    return dim3(bx ? bx : 1, (uint32_t)rows);
+}
+
+// product of the context primes idx[0..cnt) except idx[skip], modulo m
+static uint64_t hy_prod_mod(const moai_ctx *c, const uint32_t *idx, size_t cnt, size_t skip, uint64_t m)
+{
+    uint64_t r = 1 % m;
+    for (size_t i = 0; i < cnt; ++i)
+    {
+        if (i != skip)
+        {
+            r = mulmod(r, c->primes[idx[i]] % m, m);
+        }
+    }
+    return r;
+}
+
+static uint64_t hy_invmod(uint64_t a, uint64_t q)
+{
+    return powmod(a, q - 2, q);
+}
+
+// floor(P / 2) mod m from P mod m (P odd)
+static uint64_t hy_half_mod(uint64_t p_mod_m, uint64_t m)
+{
+    return mulmod((p_mod_m + m - 1) % m, hy_invmod(2, m), m);
+}
+
+// the device block of constants for (L, alpha); the caller holds op_mutex.  Built on first use with a blocking copy from a host
+// buffer that lives until the copy has returned.
+static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
+{
+    const auto key = std::make_pair(L, alpha);
+    auto it = c->hybrid_tables.find(key);
+    if (it != c->hybrid_tables.end())
+    {
+        *out = static_cast<const HyTable *>(it->second);
+        return MOAI_OK;
+    }
+    const size_t k = c->k, beta = hy_beta(L, alpha);
+    const size_t bytes = sizeof(HyTable) + beta * sizeof(HyConv);
+    std::vector<unsigned char> host(bytes, 0);
+    HyTable *t = reinterpret_cast<HyTable *>(host.data());
+    HyConv *convs = reinterpret_cast<HyConv *>(host.data() + offsetof(HyTable, conv));
+    uint32_t special[HY_MAX_ALPHA];
+    for (size_t s = 0; s < alpha; ++s)
+    {
+        special[s] = (uint32_t)(k - alpha + s);
+    }
+    for (size_t i = 0; i < L; ++i)
+    {
+        const uint64_t q = c->primes[i];
+        t->pinv[i] = make_tw(hy_invmod(hy_prod_mod(c, special, alpha, alpha, q), q), q);
+    }
+    for (size_t j = 0; j < beta; ++j)
+    {
+        HyConv &cv = convs[j];
+        const size_t lo = j * alpha, hi = std::min(lo + alpha, L);
+        cv.nsrc = (uint32_t)(hi - lo);
+        for (size_t r = 0; r < cv.nsrc; ++r)
+        {
+            cv.src_prime[r] = (uint32_t)(lo + r);
+        }
+        for (size_t r = 0; r < cv.nsrc; ++r)
+        {
+            const uint64_t q = c->primes[lo + r];
+            cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, cv.src_prime, cv.nsrc, r, q), q), q);
+        }
+        cv.ntgt = 0;
+        for (size_t row = 0; row < L + alpha; ++row)
+        {
+            if (row >= lo && row < hi)
+            {
+                continue;
+            }
+            const uint32_t prime = (uint32_t)(row < L ? row : k - alpha + (row - L));
+            const uint32_t tg = cv.ntgt++;
+            cv.tgt_prime[tg] = prime;
+            for (size_t r = 0; r < cv.nsrc; ++r)
+            {
+                cv.w[tg][r] = hy_prod_mod(c, cv.src_prime, cv.nsrc, r, c->primes[prime]);
+            }
+        }
+    }
+    {
+        HyConv &cv = convs[beta];
+        cv.nsrc = (uint32_t)alpha;
+        cv.ntgt = (uint32_t)L;
+        for (size_t s = 0; s < alpha; ++s)
+        {
+            const uint64_t p = c->primes[special[s]];
+            cv.src_prime[s] = special[s];
+            cv.src_inv[s] = make_tw(hy_invmod(hy_prod_mod(c, special, alpha, s, p), p), p);
+            cv.src_pre[s] = hy_half_mod(0, p);
+        }
+        for (size_t i = 0; i < L; ++i)
+        {
+            const uint64_t q = c->primes[i];
+            cv.tgt_prime[i] = (uint32_t)i;
+            cv.tgt_post[i] = hy_half_mod(hy_prod_mod(c, special, alpha, alpha, q), q);
+            for (size_t s = 0; s < alpha; ++s)
+            {
+                cv.w[i][s] = hy_prod_mod(c, special, alpha, s, q);
+            }
+        }
+    }
+    void *dev = nullptr;
+    MOAI_HIP_CHECK(hipMalloc(&dev, bytes));
+    hipError_t e = hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipFree(dev);
+        return set_error(MOAI_EHIP, "hybrid key-switch constants: %s", hipGetErrorString(e));
+    }
+    c->hybrid_tables[key] = dev;
+    *out = static_cast<const HyTable *>(dev);
+    return MOAI_OK;
+}
+
+static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_t src_off, uint64_t *dst, const HyConv *cv, size_t nsrc,
+                      size_t polys, hipStream_t s)
+{
+    HyConvArgs a;
+    a.src = src;
+    a.dst = dst;
+    a.cv = cv;
+    a.pc = c->pc;
+    a.src_stride = (uint32_t)src_stride;
+    a.src_off = (uint32_t)src_off;
+    a.n2 = (uint32_t)(c->n >> 1);
+    MOAI_CHECK_GRID_ROWS(polys);
+    // the smallest instantiation that holds the digit: its registers are the unrolled source rows
+    const int amax = nsrc <= 1 ? 1 : nsrc <= 2 ? 2 : nsrc <= 4 ? 4 : nsrc <= 8 ? 8 : 16;
+    MOAI_TRY((dispatch<1, 2, 4, 8, 16>("digit size ", amax, [&](auto A) {
+        hipLaunchKernelGGL(hy_convert_kernel<decltype(A)::value>, hy_grid(c, polys), dim3(256), 0, s, a);
+        return MOAI_OK;
+    })));
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+// rows of N words of scratch per ciphertext: t, the converted digits, acc, the special rows, conv (and the permuted input of
+// apply_galois)
+static size_t hy_rows_per_ct(size_t L, size_t alpha, bool galois)
+{
+    const size_t beta = hy_beta(L, alpha);
+    return (galois ? 2 * L : 0) + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * alpha + 2 * L;
+}
+
+struct HyLayout
+{
+    size_t gal, t, ext, acc, x, conv, total; // byte offsets
+};
+
+static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, bool galois)
+{
+    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
+    HyLayout w;
+    w.gal = 0;
+    w.t = w.gal + hy_align(galois ? cb * 2 * L * row : 0);
+    w.ext = w.t + hy_align(cb * L * row);
+    w.acc = w.ext + hy_align(cb * (beta * (L + alpha) - L) * row);
+    w.x = w.acc + hy_align(cb * 2 * (L + alpha) * row);
+    w.conv = w.x + hy_align(cb * 2 * alpha * row);
+    w.total = w.conv + hy_align(cb * 2 * L * row);
+    return w;
+}
+
+// ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one
+static size_t hy_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, bool galois)
+{
+    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
+    const size_t per = hy_rows_per_ct(L, alpha, galois) * c->n * sizeof(uint64_t);
+    size_t cb = budget / per;
+    cb = cb < 1 ? 1 : cb;
+    // row-per-workgroup launches: 2 * cb * (L + alpha) rows in gridDim.y
+    const size_t cap = 65535 / (2 * (L + alpha));
+    cb = cb > cap ? cap : cb;
+    return cb < batch ? cb : batch;
+}
+
+static inline uint64_t *hy_at(void *base, size_t offset)
+{
+    return reinterpret_cast<uint64_t *>(static_cast<char *>(base) + offset);
+}
+
+// one chunk of B ciphertexts: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + the switch of the target rows
+// (ciphertext b's row r at target row b * tgt_stride + tgt_off + r)
+static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const uint64_t *target, size_t tgt_stride, size_t tgt_off,
+                           const uint64_t *key, size_t L, size_t alpha, size_t B, void *wsp, const HyLayout &w, const uint64_t *addend,
+                           size_t addend_bstride, int add_mode, hipStream_t s)
+{
+    const size_t n = c->n, k = c->k, beta = hy_beta(L, alpha);
+    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
+    const HyConv *cvs = tab->conv; // device address arithmetic only
+    RowMap rm;
+    // 1. t = INTT(target)
+    MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, t, B, L, rm, true, s, target, tgt_stride, tgt_off));
+    // 2., 3. mod-up of every digit and the forward transform of the converted rows
+    for (size_t j = 0; j < beta; ++j)
+    {
+        const size_t lo = j * alpha, hi = std::min(lo + alpha, L), nr = hi - lo, cr = L - nr + alpha;
+        uint64_t *ext_j = ext + j * B * L * n;
+        MOAI_TRY(hy_convert(c, t, L, lo, ext_j, cvs + j, nr, B, s));
+        size_t tg = 0;
+        for (size_t row = 0; row < L + alpha; ++row)
+        {
+            if (row < lo || row >= hi)
+            {
+                rm.idx[tg++] = (uint32_t)(row < L ? row : k - alpha + (row - L));
+            }
+        }
+        MOAI_TRY(ntt_launch(c, ext_j, B, cr, rm, false, s));
+    }
+    // 4. the inner products with the key
+    {
+        HyMacArgs m;
+        m.ext = ext;
+        m.tgt = target;
+        m.key = key;
+        m.acc = acc;
+        m.pc = c->pc;
+        m.tgt_stride = (uint32_t)tgt_stride;
+        m.tgt_off = (uint32_t)tgt_off;
+        m.L = (uint32_t)L;
+        m.alpha = (uint32_t)alpha;
+        m.beta = (uint32_t)beta;
+        m.k = (uint32_t)k;
+        m.n2 = (uint32_t)(n >> 1);
+        const dim3 g1 = hy_grid(c, 1);
+        hipLaunchKernelGGL(hy_mac_kernel, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
+        MOAI_LAUNCH_CHECK();
+    }
+    // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
+    for (size_t r = 0; r < alpha; ++r)
+    {
+        rm.idx[r] = (uint32_t)(k - alpha + r);
+    }
+    MOAI_TRY(ntt_launch(c, x, 2 * B, alpha, rm, true, s, acc, L + alpha, L));
+    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, cvs + beta, alpha, 2 * B, s));
+    MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, conv, 2 * B, L, rm, false, s));
+    HyFinalArgs f;
+    f.acc = acc;
+    f.conv = conv;
+    f.out = out;
+    f.pinv = tab->pinv;
+    f.pc = c->pc;
+    f.addend = addend;
+    f.addend_bstride = (uint32_t)addend_bstride;
+    f.add_mode = add_mode;
+    f.L = (uint32_t)L;
+    f.alpha = (uint32_t)alpha;
+    f.n2 = (uint32_t)(n >> 1);
+    MOAI_CHECK_GRID_ROWS(2 * B * L);
+    hipLaunchKernelGGL(hy_finalize_kernel, hy_grid(c, 2 * B * L), dim3(256), 0, s, f);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+// what every hybrid entry point refuses, in the order the header gives: first what needs no context
+static int hy_check(const moai_ctx *c, size_t alpha, size_t L, bool level)
+{
+    if (alpha == 0)
+    {
+        return set_error(MOAI_EINVAL, "alpha = 0: a digit holds at least one prime");
+    }
+    if (level && L == 0)
+    {
+        return set_error(MOAI_EINVAL, "L = 0 out of range");
+    }
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (alpha >= c->k)
+    {
+        return set_error(MOAI_EINVAL, "alpha = %zu leaves no data prime in a context of %zu primes", alpha, c->k);
+    }
+    if (alpha > HY_MAX_ALPHA)
+    {
+        return set_error(MOAI_EINVAL, "alpha = %zu: digits of more than %u primes are not supported", alpha, HY_MAX_ALPHA);
+    }
+    if (level && L > c->k - alpha)
+    {
+        return set_error(MOAI_EINVAL, "L = %zu out of range: %zu data primes with alpha = %zu", L, c->k - alpha, alpha);
+    }
+    return MOAI_OK;
+}
+
+enum
+{
+    HY_SWITCH,
+    HY_RELIN,
+    HY_GALOIS
+};
+
+// the three switches: validated, then chunk by chunk on the stream's workspace
+//   HY_SWITCH  io = ct [batch][2][L][N] in place, in = target [batch][L][N]
+//   HY_RELIN   in = ct3 [batch][3][L][N], io = out [batch][2][L][N]
+//   HY_GALOIS  io = ct [batch][2][L][N] in place
+static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, const uint64_t *key, size_t L, size_t alpha, uint32_t elt,
+                    size_t batch, void *stream)
+{
+    if (kind == HY_GALOIS && !(elt & 1u))
+    {
+        return set_error(MOAI_EINVAL, "Galois element is not valid");
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (kind == HY_GALOIS && elt >= 2 * c->n)
+    {
+        return set_error(MOAI_EINVAL, "Galois element is not valid");
+    }
+    if (batch == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!io || !key || (kind != HY_GALOIS && !in) || (kind == HY_RELIN && in == io))
+    {
+        return set_error(MOAI_EINVAL, kind == HY_RELIN ? "bad pointers" : "null argument");
+    }
+    MOAI_TRY(enter_device(c));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = c->n;
+    const uint32_t *table = nullptr;
+    if (kind == HY_GALOIS)
+    {
+        MOAI_TRY(galois_table(c, elt, &table)); // built before the first launch of the call
+    }
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    const size_t cb = hy_chunk(c, L, alpha, batch, kind == HY_GALOIS);
+    const HyLayout w = hy_layout(c, L, alpha, cb, kind == HY_GALOIS);
+    void *wsp;
+    MOAI_TRY(workspace(c, w.total, s, &wsp));
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        switch (kind)
+        {
+        case HY_SWITCH:
+            // ct += switch(target)
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, in + b0 * L * n, L, 0, key, L, alpha, B, wsp, w, io + b0 * 2 * L * n, 2 * L, 1,
+                                   s);
+        case HY_RELIN:
+            // out = (c0, c1) + switch(c2)      (evaluator.cpp:1383-1392)
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, in + b0 * 3 * L * n, 3 * L, 2 * L, key, L, alpha, B, wsp, w,
+                                   in + b0 * 3 * L * n, 3 * L, 1, s);
+        default:
+        {
+            // ct = (galois(c0), 0) + switch(galois(c1))      (evaluator.cpp:2631-2654)
+            uint64_t *tmp = hy_at(wsp, w.gal);
+            MOAI_TRY(moai_galois_permute(c, io + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, tmp, 2 * L, L, key, L, alpha, B, wsp, w, tmp, 2 * L, 2, s);
+        }
+        }
+    });
+}
+
+} // namespace moai
+
+using namespace moai;
+
+extern "C" size_t moai_hybrid_digits(const moai_ctx *c, size_t alpha, size_t L)
+{
+    if (hy_check(c, alpha, L, true))
+    {
+        return 0;
+    }
+    return hy_beta(L, alpha);
+}
+
+extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,
+                                  size_t alpha, uint64_t *out, void *stream)
+{
+    MOAI_AUDIT(stream, sk_ntt, new_key_ntt, out);
+    MOAI_TRY(hy_check(c, alpha, 0, false));
+    const size_t k = c->k, Lmax = k - alpha, digits = hy_beta(Lmax, alpha);
+    trace_op("hybrid_keygen", k, digits);
+    if (!key)
+    {
+        return set_error(MOAI_EINVAL, "null key");
+    }
+    if (!sk_ntt || !new_key_ntt || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    // digit j = Enc_s(0) over all k rows with sequence seq + j (validates the sequence range before it enqueues)
+    MOAI_TRY(encrypt_zero_key_level(c, key, seq, sk_ntt, out, digits, (hipStream_t)stream));
+    HyKeyAddArgs a;
+    a.key = out;
+    a.newkey = new_key_ntt;
+    a.pc = c->pc;
+    a.alpha = (uint32_t)alpha;
+    a.k = (uint32_t)k;
+    a.n2 = (uint32_t)(c->n >> 1);
+    uint32_t special[HY_MAX_ALPHA];
+    for (size_t s = 0; s < alpha; ++s)
+    {
+        special[s] = (uint32_t)(k - alpha + s);
+    }
+    for (size_t r = 0; r < MOAI_MAX_RNS; ++r)
+    {
+        a.fac[r] = r < Lmax ? hy_prod_mod(c, special, alpha, alpha, c->primes[r]) : 0;
+    }
+    hipLaunchKernelGGL(hy_key_add_kernel, hy_grid(c, Lmax), dim3(256), 0, (hipStream_t)stream, a);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+extern "C" int moai_switch_key_hybrid(moai_ctx *c, uint64_t *ct, const uint64_t *target, const uint64_t *key, size_t L, size_t alpha,
+                                      size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, ct, target, key);
+    trace_op("switch_key_hybrid", L, batch);
+    return hy_entry(c, HY_SWITCH, ct, target, key, L, alpha, 1, batch, stream);
+}
+
+extern "C" int moai_relinearize_hybrid(moai_ctx *c, const uint64_t *ct3, const uint64_t *key, uint64_t *out, size_t L, size_t alpha,
+                                       size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, ct3, key, out);
+    trace_op("relinearize_hybrid", L, batch);
+    return hy_entry(c, HY_RELIN, out, ct3, key, L, alpha, 1, batch, stream);
+}
+
+extern "C" int moai_apply_galois_hybrid(moai_ctx *c, uint64_t *ct, size_t L, size_t alpha, uint32_t galois_elt, const uint64_t *key,
+                                        size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, ct, key);
+    trace_op("apply_galois_hybrid", L, batch);
+    return hy_entry(c, HY_GALOIS, ct, nullptr, key, L, alpha, galois_elt, batch, stream);
+}

@@ -33,7 +33,8 @@ namespace moai {
     X(MD_FP_MIN_ROWS, 256, "polynomials * L from which mod-down and rescale use the FP64 arithmetic modes")                    \
     X(MATMUL_FP, 1, "0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel")                                      \
     X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")                     \
-    X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller")
+    X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller") \
+    X(HYBRID_TMP_KB, 16777216, "KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight")
 
 enum Knob
 {
@@ -154,6 +155,11 @@ int total_coeff_bits(const moai_ctx *c, size_t L, const uint32_t *prime_index);
 // rescale_ws_bytes(c, L, batch * size) bytes of the stream's arena, the caller's own scratch lies behind them
 size_t rescale_ws_bytes(const moai_ctx *c, size_t L, size_t polys);
 int rescale_nolock(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t size, size_t L, size_t batch, hipStream_t s);
+
+// moai_encrypt_symmetric of n_batch zeros over all k rows for another translation unit (hybrid.hip's key digits): the same
+// validation and stream positions, not traced; takes op_mutex itself
+int encrypt_zero_key_level(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, uint64_t *out, size_t n_batch,
+                           hipStream_t s);
 
 // moai_seal_sample_uniform for a caller that has validated its arguments and holds op_mutex (client.hip's SEAL-seeded entry
 // points): polynomial b of `count` lands at out + b * stride_words; cnt is device scratch [count][L] that the call zeroes itself

@@ -107,6 +107,11 @@ SYMBOLS = {
     "moai_ct_dot_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, vp, vp, sz, vp]),
     "moai_apply_galois_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
     "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
+    "moai_hybrid_digits": (sz, [vp, sz, sz]),
+    "moai_hybrid_keygen": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, vp, vp]),
+    "moai_switch_key_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
+    "moai_relinearize_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
+    "moai_apply_galois_hybrid": (C.c_int, [vp, vp, sz, sz, C.c_uint32, vp, sz, vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -378,6 +383,23 @@ class Context:
     def apply_galois(self, ct, L, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois(self.h, _ptr(ct), L, int(elt), _ptr(key), batch, stream))
 
+    # hybrid key switching (include/moai_hip.h, "hybrid key switching"): alpha special primes, digits of alpha primes
+    def hybrid_digits(self, alpha, L):
+        """beta(L) = ceil(L / alpha) for a level of L <= k - alpha data primes"""
+        d = lib().moai_hybrid_digits(self.h, alpha, L)
+        if d == 0:
+            _check(MOAI_EINVAL)
+        return int(d)
+
+    def switch_key_hybrid(self, ct, target, key, L, alpha, batch, stream=None):
+        _check(lib().moai_switch_key_hybrid(self.h, _ptr(ct), _ptr(target), _ptr(key), L, alpha, batch, stream))
+
+    def relinearize_hybrid(self, ct3, key, out, L, alpha, batch, stream=None):
+        _check(lib().moai_relinearize_hybrid(self.h, _ptr(ct3), _ptr(key), _ptr(out), L, alpha, batch, stream))
+
+    def apply_galois_hybrid(self, ct, L, alpha, elt, key, batch, stream=None):
+        _check(lib().moai_apply_galois_hybrid(self.h, _ptr(ct), L, alpha, int(elt), _ptr(key), batch, stream))
+
     def apply_galois_to(self, src, dst, L, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois_to(self.h, _ptr(src), _ptr(dst), L, int(elt), _ptr(key), batch, stream))
 
@@ -637,6 +659,13 @@ class Context:
         """The k-1 digits of the switching key for new_key_ntt [k][N]: a DeviceBuffer [k-1][2][k][N]."""
         out = DeviceBuffer(max(self.k - 1, 1) * 2 * self.k * self.n)
         _check(lib().moai_kswitch_keygen(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(new_key_ntt), out.ptr, stream))
+        return out
+
+    def hybrid_keygen(self, key, seq, sk_ntt, new_key_ntt, alpha, stream=None):
+        """The beta(k - alpha) digits of the hybrid switching key for new_key_ntt [k][N]: a DeviceBuffer [beta][2][k][N]."""
+        digits = self.hybrid_digits(alpha, self.k - alpha)
+        out = DeviceBuffer(digits * 2 * self.k * self.n)
+        _check(lib().moai_hybrid_keygen(self.h, self._key(key), int(seq), _ptr(sk_ntt), _ptr(new_key_ntt), alpha, out.ptr, stream))
         return out
 
     # --- wire form (include/moai_hip.h, "wire form: seeded objects and bit-packed rows") ---------------------------
