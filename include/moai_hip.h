@@ -586,7 +586,8 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
  *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
- *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight */
+ *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight
+ *   MOAI_HYBRID_HOIST_NR   4     rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1 */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
 /* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of
@@ -740,6 +741,49 @@ int moai_relinearize_hybrid(moai_ctx *ctx, const uint64_t *ct3, const uint64_t *
 /* Evaluator::apply_galois_inplace over the hybrid switch (SEAL/evaluator.cpp:2724-3020): ct [batch][2][L][N] in place */
 int moai_apply_galois_hybrid(moai_ctx *ctx, uint64_t *ct, size_t L, size_t alpha, uint32_t galois_elt, const uint64_t *key,
                              size_t batch, void *stream);
+
+/* ---- hoisted rotations over the hybrid key switch ------------------------------------------------------------------------------
+ * R rotations of the SAME ciphertext, each with its own key (the baby steps of MOAI's bootstrapping transforms, include/source/
+ * bootstrapping/Bootstrapper.cpp:2017-2022, 2082-2088), with steps 1-3 above -- INTT, mod-up, forward transforms: L +
+ * beta (L + alpha) - L of the 2 alpha + 2 L + beta (L + alpha) transforms of a switch -- done ONCE per ciphertext, as
+ * moai_apply_galois_hoisted does for the reference's switch.  Bit-identical to the R separate moai_apply_galois_hybrid calls.
+ * With sigma the automorphism, mask_sigma[i] = 1 where sigma negates the coefficient that lands on i, t = INTT(c1), n_j = |R_j|:
+ * a separate call converts sigma(t), whose residues are q_r - t_r under the mask (t_r != 0), so its scaled residues are
+ * q_r - y_r, and since sum_{r in R_j} q_r (D_j / q_r) = n_j D_j, for every row m outside R_j
+ *     modup_j(sigma(t)) = sigma(chat_j) + n_j (D_j mod m) mask_sigma   (mod m)
+ * as long as no coefficient of t is zero in any row; on the rows of R_j the digit is the permuted row of c1 and D_j mod q_r = 0.
+ * NTT_m is linear and turns sigma into the index permutation apply_galois_ntt uses (SEAL/util/galois.cpp:192-218), so
+ *     acc_r[p][row]  = sum_j perm_r(NTT(chat_j)[row]) (*) key_r[j][p][row] + corr_r[p][row]
+ *     corr_r[p][row] = NTT_row(mask_r) (*) sum_{j < beta(L)} (n_j D_j mod m_row) key_r[j][p][row]      (mod m_row)
+ * is congruent to the separate call's sum: the canonical accumulators are the same bits, and step 5 is unchanged.  At alpha = 1
+ * this is moai_hoist_correction / moai_apply_galois_hoisted word for word (csrc/keyswitch_kernels.hip.h has that derivation).
+ *   in, outs[r]  [batch][2][L][N]; no output may overlap the input or another output.  keys[r] in moai_hybrid_keygen's layout
+ *   [beta(k-alpha)][2][k][N].  corrections[r] [2][L+alpha][N] from moai_hybrid_hoist_correction for the same (key, galois_elt, L,
+ *   alpha).  outs / keys / corrections: host arrays of R device pointers; any R.
+ * The identity needs INTT(c1) free of zero coefficients.  The call checks that on the device per batch chunk and makes the R
+ * separate rotations of a chunk itself where it fails (*used_fallback = 1, same bits).  It therefore SYNCHRONISES the stream once
+ * per batch chunk -- once when the batch fits the scratch budget -- and cannot run under HIP-graph stream capture (the
+ * synchronisation fails there with MOAI_EHIP, as in moai_apply_galois_hoisted).
+ * Scratch from the stream's workspace, in rows of N words, for cb ciphertexts per chunk and G rotations in flight:
+ *     cb beta (L + alpha)  +  cb G (2 (L + alpha) + 2 alpha + 2 L + L)      (t and the digits; acc, special rows, conv, permuted c0)
+ * plus one 256-byte block for the flag.  cb is the largest count for which cb ciphertexts with one rotation in flight fit
+ * MOAI_HYBRID_TMP_KB, G the largest for which G rotations fit beside them; at least one of each, at most batch and R, and
+ * 2 cb G (L + alpha) <= 65535.  A ciphertext is decomposed once however many groups its rotations take, MOAI_HYBRID_HOIST_NR
+ * rotations share a pass of the MAC over the digits, and results depend on neither.
+ * Nothing is enqueued and nothing written when an argument is refused: MOAI_EINVAL with a message for what the hybrid entry
+ * points above refuse, a null array or a null entry in one, an even Galois element or one >= 2N, an output that overlaps the
+ * input or another output.  batch = 0 and R = 0 are MOAI_OK.  moai_op_trace counts "hybrid_hoist_correction" (1) and
+ * "apply_galois_hybrid_hoisted" (batch R) at L. */
+/* corr [2][L+alpha][N]: rows 0..L-1 under q_0..q_{L-1}, rows L..L+alpha-1 under p_0..p_{alpha-1}; per (key, galois_elt, L, alpha);
+ * the mod-up of SEAL/evaluator.cpp:2724-3020 applied to a permuted polynomial, less the permuted mod-up */
+int moai_hybrid_hoist_correction(moai_ctx *ctx, const uint64_t *key, uint32_t galois_elt, size_t L, size_t alpha,
+                                 uint64_t *correction, void *stream);
+/* outs[r] = moai_apply_galois_hybrid(copy of in, L, alpha, galois_elts[r], keys[r]) for r < R, bit for bit, with ONE
+ * INTT + mod-up + forward transform of the digits per ciphertext (SEAL/evaluator.cpp:2724-3020 shared by R rotations) */
+int moai_apply_galois_hybrid_hoisted(moai_ctx *ctx, const uint64_t *in, uint64_t *const *outs, size_t L, size_t alpha,
+                                     const uint32_t *galois_elts, const uint64_t *const *keys,
+                                     const uint64_t *const *corrections, size_t R, size_t batch, int *used_fallback,
+                                     void *stream);
 
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be

@@ -15,6 +15,9 @@
 //   x        = INTT(special rows of acc)                                        [2B][alpha][N]
 //   conv     = hy_convert_kernel: base {p_t} -> {q_i} with the rounding terms   [2B][L][N], then forward NTT
 //   out      = hy_finalize_kernel: addend + (acc - conv) P^-1
+// Hoisted rotations (R automorphisms of one ciphertext, each with its own key) run t, ext_j and their forward transforms ONCE on
+// the unpermuted c1 and replace the MAC by hy_hoisted_mac_kernel, which reads the digits through each rotation's permutation
+// table and adds that rotation's correction (hy_hoist_correction_kernel; the header states the identity).
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 #include <algorithm>
@@ -45,12 +48,19 @@ struct alignas(16) HyConv
     uint64_t w[MOAI_MAX_RNS][HY_MAX_ALPHA];
 };
 
-// the constants of a switch at (L, alpha): conv[j], j < beta, are the mod-ups and conv[beta] is the mod-down
+// the constants of a switch at (L, alpha): conv[j], j < beta, are the mod-ups and conv[beta] is the mod-down; behind them lie the
+// multipliers of the hoisted rotations' correction, [beta][L + alpha] words: |R_j| D_j mod m_row (hy_hoist_mult)
 struct alignas(16) HyTable
 {
     Tw pinv[MOAI_MAX_RNS]; // P^-1 mod q_i
     HyConv conv[1];
 };
+
+// device address arithmetic only
+static inline const uint64_t *hy_hoist_mult(const HyTable *tab, size_t beta)
+{
+    return reinterpret_cast<const uint64_t *>(tab->conv + beta + 1);
+}
 
 // (hi * 2^64 + lo) mod q for ANY 128-bit value: barrett128's quotient is short of the true one by at most 2 there, so one more
 // conditional subtraction makes the residue canonical (a source residue is below ITS prime, which may be far above the target's)
@@ -167,6 +177,132 @@ __global__ __launch_bounds__(256) void hy_mac_kernel(HyMacArgs g)
         }
         acc0[x] = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
         acc1[x] = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
+    }
+}
+
+struct HyCorrArgs
+{
+    const uint64_t *key;  // [beta(k - alpha)][2][k][N]
+    const uint64_t *mask; // [L + alpha][N]: NTT of the rotation's sign mask under each row's prime
+    const uint64_t *mult; // [beta][L + alpha]: |R_j| D_j mod m_row
+    uint64_t *out;        // [2][L + alpha][N]
+    const PrimeConst *pc;
+    uint32_t L, alpha, beta, k;
+    uint32_t n2;
+};
+
+// out[p][row] = mask[row] (*) sum_{j < beta} mult[j][row] key[j][p][row]; blockIdx.y = p * (L + alpha) + row.  At most 63 products
+// below 2^122.  A multiplier of zero (the rows of R_j itself, D_j mod q_r = 0) is skipped: the branch is uniform.
+__global__ __launch_bounds__(256) void hy_hoist_correction_kernel(HyCorrArgs g)
+{
+    const uint32_t rows = g.L + g.alpha, p = blockIdx.y / rows, row = blockIdx.y % rows;
+    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
+    const PrimeConst *pc = g.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = g.n2;
+    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + ((size_t)p * g.k + prime) * n2;
+    const ulonglong2 *mk = reinterpret_cast<const ulonglong2 *>(g.mask) + (size_t)row * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < g.n2; x += gridDim.x * 256u)
+    {
+        uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
+        for (uint32_t j = 0; j < g.beta; ++j)
+        {
+            const uint64_t f = g.mult[j * rows + row];
+            if (f)
+            {
+                mac2(lx, hx, ly, hy, key[(size_t)j * 2 * g.k * n2 + x], f);
+            }
+        }
+        o[x] = mulmod2(reduce2(lx, hx, ly, hy, q, cr0, cr1), mk[x], q, cr0, cr1);
+    }
+}
+
+constexpr int HY_HOIST_MAX_NR = 4;
+
+struct HyHoistMacArgs
+{
+    const uint64_t *ext; // as HyMacArgs: the digits of the UNPERMUTED c1
+    const uint64_t *in;  // the unpermuted input [B][2][L][N]: its c1 row r is the digit under prime r
+    const uint32_t *table[HY_HOIST_MAX_NR]; // per rotation: its NTT-form index permutation (galois_table), out[i] = in[table[i]]
+    const uint64_t *key[HY_HOIST_MAX_NR];   // its key [beta(k - alpha)][2][k][N]
+    const uint64_t *corr[HY_HOIST_MAX_NR];  // its correction [2][L + alpha][N]
+    uint64_t *acc[HY_HOIST_MAX_NR];         // its accumulators [B][2][L + alpha][N]
+    const PrimeConst *pc;
+    uint32_t L, alpha, beta, k;
+    uint32_t n2;
+};
+
+// acc_r[b][p][row] = sum_{j < beta} digit_j[row][table_r] (*) key_r[j][p][row] + corr_r[p][row] for NR rotations in one pass over
+// the digits; grid as hy_mac_kernel (blockIdx.x = b, blockIdx.z = row).  A thread owns two neighbouring OUTPUT positions: the key,
+// the correction and the accumulators are read and written in order, two words per lane, and only the digit is gathered (beta of
+// the 3 beta + 4 words per output).  Per digit every load of every rotation is issued before the arithmetic.  Sums as in
+// hy_mac_kernel: at most 63 products below 2^122, one reduction, then the canonical add of the correction.
+template <int NR>
+__global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
+{
+    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
+    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
+    const PrimeConst *pc = g.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = g.n2;
+    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * g.L + row) * 2 * n2; // read only where row < L
+    const size_t acc_row = ((size_t)b * 2 * (g.L + g.alpha) + row) * n2, acc_poly = (size_t)(g.L + g.alpha) * n2;
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < g.n2; x += gridDim.y * 256u)
+    {
+        uint2 src[NR];
+        uint64_t l0x[NR], h0x[NR], l0y[NR], h0y[NR], l1x[NR], h1x[NR], l1y[NR], h1y[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            src[r] = reinterpret_cast<const uint2 *>(g.table[r])[x];
+            l0x[r] = h0x[r] = l0y[r] = h0y[r] = l1x[r] = h1x[r] = l1y[r] = h1y[r] = 0;
+        }
+        for (uint32_t j = 0; j < g.beta; ++j)
+        {
+            const uint32_t lo = j * g.alpha, hi = min(lo + g.alpha, g.L), nr = hi - lo;
+            const uint64_t *op;
+            if (row >= lo && row < hi)
+            {
+                op = own; // the digit under one of its own primes is the input's c1 row, read through the same permutation
+            }
+            else
+            {
+                const uint32_t pos = row < lo ? row : row - nr;
+                op = g.ext + ((size_t)j * B * g.L + (size_t)b * (g.L - nr + g.alpha) + pos) * 2 * n2;
+            }
+            const size_t koff = ((size_t)j * 2 * g.k + prime) * n2 + x;
+            ulonglong2 o[NR], k0[NR], k1[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+            {
+                const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[r]);
+                o[r] = make_ulonglong2(op[src[r].x], op[src[r].y]);
+                k0[r] = key[koff];
+                k1[r] = key[koff + (size_t)g.k * n2];
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+            {
+                mac2(l0x[r], h0x[r], l0y[r], h0y[r], o[r], k0[r]);
+                mac2(l1x[r], h1x[r], l1y[r], h1y[r], o[r], k1[r]);
+            }
+        }
+        ulonglong2 c0[NR], c1[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            const ulonglong2 *corr = reinterpret_cast<const ulonglong2 *>(g.corr[r]) + (size_t)row * n2 + x;
+            c0[r] = corr[0];
+            c1[r] = corr[acc_poly];
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            ulonglong2 *acc = reinterpret_cast<ulonglong2 *>(g.acc[r]) + acc_row + x;
+            acc[0] = add2(reduce2(l0x[r], h0x[r], l0y[r], h0y[r], q, cr0, cr1), c0[r], q);
+            acc[acc_poly] = add2(reduce2(l1x[r], h1x[r], l1y[r], h1y[r], q, cr0, cr1), c1[r], q);
+        }
     }
 }
 
@@ -294,7 +430,8 @@ static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
         return MOAI_OK;
     }
     const size_t k = c->k, beta = hy_beta(L, alpha);
-    const size_t bytes = sizeof(HyTable) + beta * sizeof(HyConv);
+    const size_t conv_bytes = offsetof(HyTable, conv) + (beta + 1) * sizeof(HyConv);
+    const size_t bytes = conv_bytes + beta * (L + alpha) * sizeof(uint64_t);
     std::vector<unsigned char> host(bytes, 0);
     HyTable *t = reinterpret_cast<HyTable *>(host.data());
     HyConv *convs = reinterpret_cast<HyConv *>(host.data() + offsetof(HyTable, conv));
@@ -358,6 +495,17 @@ static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
             {
                 cv.w[i][s] = hy_prod_mod(c, special, alpha, s, q);
             }
+        }
+    }
+    // the hoisted rotations' correction: sum_{r in R_j} q_r (D_j / q_r) = |R_j| D_j, modulo every row's prime (0 on the rows of R_j)
+    uint64_t *mult = reinterpret_cast<uint64_t *>(host.data() + conv_bytes);
+    for (size_t j = 0; j < beta; ++j)
+    {
+        const HyConv &cv = convs[j];
+        for (size_t row = 0; row < L + alpha; ++row)
+        {
+            const uint64_t m = c->primes[row < L ? row : k - alpha + (row - L)];
+            mult[j * (L + alpha) + row] = mulmod(cv.nsrc % m, hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, m), m);
         }
     }
     void *dev = nullptr;
@@ -440,14 +588,12 @@ static inline uint64_t *hy_at(void *base, size_t offset)
     return reinterpret_cast<uint64_t *>(static_cast<char *>(base) + offset);
 }
 
-// one chunk of B ciphertexts: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + the switch of the target rows
-// (ciphertext b's row r at target row b * tgt_stride + tgt_off + r)
-static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const uint64_t *target, size_t tgt_stride, size_t tgt_off,
-                           const uint64_t *key, size_t L, size_t alpha, size_t B, void *wsp, const HyLayout &w, const uint64_t *addend,
-                           size_t addend_bstride, int add_mode, hipStream_t s)
+// steps 1-3 for B ciphertexts: t [B][L][N] = INTT of the target rows (ciphertext b's row r at target row b * tgt_stride + tgt_off
+// + r), ext = the converted rows of every digit in NTT form (HyMacArgs::ext)
+static int hy_decompose(moai_ctx *c, const HyTable *tab, const uint64_t *target, size_t tgt_stride, size_t tgt_off, size_t L, size_t alpha,
+                        size_t B, uint64_t *t, uint64_t *ext, hipStream_t s)
 {
     const size_t n = c->n, k = c->k, beta = hy_beta(L, alpha);
-    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
     const HyConv *cvs = tab->conv; // device address arithmetic only
     RowMap rm;
     // 1. t = INTT(target)
@@ -469,34 +615,31 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
         }
         MOAI_TRY(ntt_launch(c, ext_j, B, cr, rm, false, s));
     }
-    // 4. the inner products with the key
-    {
-        HyMacArgs m;
-        m.ext = ext;
-        m.tgt = target;
-        m.key = key;
-        m.acc = acc;
-        m.pc = c->pc;
-        m.tgt_stride = (uint32_t)tgt_stride;
-        m.tgt_off = (uint32_t)tgt_off;
-        m.L = (uint32_t)L;
-        m.alpha = (uint32_t)alpha;
-        m.beta = (uint32_t)beta;
-        m.k = (uint32_t)k;
-        m.n2 = (uint32_t)(n >> 1);
-        const dim3 g1 = hy_grid(c, 1);
-        hipLaunchKernelGGL(hy_mac_kernel, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
-        MOAI_LAUNCH_CHECK();
-    }
-    // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
+    return MOAI_OK;
+}
+
+// step 5 up to the last kernel, for the accumulators [B][2][L + alpha][N] of B switches: x [2B][alpha][N] = INTT(special rows),
+// conv [2B][L][N] = NTT(base conversion with the rounding terms)
+static int hy_mod_down(moai_ctx *c, const HyTable *tab, const uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
+                       hipStream_t s)
+{
+    const size_t k = c->k, beta = hy_beta(L, alpha);
+    RowMap rm{};
     for (size_t r = 0; r < alpha; ++r)
     {
         rm.idx[r] = (uint32_t)(k - alpha + r);
     }
     MOAI_TRY(ntt_launch(c, x, 2 * B, alpha, rm, true, s, acc, L + alpha, L));
-    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, cvs + beta, alpha, 2 * B, s));
+    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + beta, alpha, 2 * B, s));
     MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
-    MOAI_TRY(ntt_launch(c, conv, 2 * B, L, rm, false, s));
+    return ntt_launch(c, conv, 2 * B, L, rm, false, s);
+}
+
+// the last kernel of step 5: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + (acc - conv) / P
+static int hy_finalize(moai_ctx *c, const HyTable *tab, const uint64_t *acc, const uint64_t *conv, uint64_t *out, size_t L, size_t alpha,
+                       size_t B, const uint64_t *addend, size_t addend_bstride, int add_mode, hipStream_t s)
+{
+    const size_t n = c->n;
     HyFinalArgs f;
     f.acc = acc;
     f.conv = conv;
@@ -513,6 +656,39 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
     hipLaunchKernelGGL(hy_finalize_kernel, hy_grid(c, 2 * B * L), dim3(256), 0, s, f);
     MOAI_LAUNCH_CHECK();
     return MOAI_OK;
+}
+
+// one chunk of B ciphertexts: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + the switch of the target rows
+// (ciphertext b's row r at target row b * tgt_stride + tgt_off + r)
+static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const uint64_t *target, size_t tgt_stride, size_t tgt_off,
+                           const uint64_t *key, size_t L, size_t alpha, size_t B, void *wsp, const HyLayout &w, const uint64_t *addend,
+                           size_t addend_bstride, int add_mode, hipStream_t s)
+{
+    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
+    // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
+    MOAI_TRY(hy_decompose(c, tab, target, tgt_stride, tgt_off, L, alpha, B, t, ext, s));
+    // 4. the inner products with the key
+    {
+        HyMacArgs m;
+        m.ext = ext;
+        m.tgt = target;
+        m.key = key;
+        m.acc = acc;
+        m.pc = c->pc;
+        m.tgt_stride = (uint32_t)tgt_stride;
+        m.tgt_off = (uint32_t)tgt_off;
+        m.L = (uint32_t)L;
+        m.alpha = (uint32_t)alpha;
+        m.beta = (uint32_t)hy_beta(L, alpha);
+        m.k = (uint32_t)c->k;
+        m.n2 = (uint32_t)(c->n >> 1);
+        const dim3 g1 = hy_grid(c, 1);
+        hipLaunchKernelGGL(hy_mac_kernel, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
+        MOAI_LAUNCH_CHECK();
+    }
+    // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
+    MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, B, s));
+    return hy_finalize(c, tab, acc, conv, out, L, alpha, B, addend, addend_bstride, add_mode, s);
 }
 
 // what every hybrid entry point refuses, in the order the header gives: first what needs no context
@@ -613,6 +789,182 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
     });
 }
 
+// ---- hoisted rotations ------------------------------------------------------------------------------------------------------
+// rows of N words of scratch: per ciphertext t and the converted digits, per (rotation in flight, ciphertext) acc, the special
+// rows, conv and the permuted c0
+static inline size_t hy_hoist_shared_rows(size_t L, size_t alpha)
+{
+    return hy_beta(L, alpha) * (L + alpha);
+}
+
+static inline size_t hy_hoist_rotation_rows(size_t L, size_t alpha)
+{
+    return 2 * (L + alpha) + 2 * alpha + 2 * L + L;
+}
+
+struct HyHoistLayout
+{
+    size_t flag, t, ext, acc, x, conv, c0, total; // byte offsets
+};
+
+static HyHoistLayout hy_hoist_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
+{
+    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
+    HyHoistLayout w;
+    w.flag = 0;
+    w.t = 256;
+    w.ext = w.t + hy_align(cb * L * row);
+    w.acc = w.ext + hy_align(cb * (beta * (L + alpha) - L) * row);
+    w.x = w.acc + hy_align(G * cb * 2 * (L + alpha) * row);
+    w.conv = w.x + hy_align(G * cb * 2 * alpha * row);
+    w.c0 = w.conv + hy_align(G * cb * 2 * L * row);
+    w.total = w.c0 + hy_align(G * cb * L * row);
+    return w;
+}
+
+// ciphertexts per chunk (*cb) and rotations in flight (*G) under MOAI_HYBRID_TMP_KB: as many ciphertexts as fit with one rotation
+// in flight, then as many rotations as fit beside them; at least one of each, and no row-per-workgroup grid above 65535 (the
+// mod-down runs over 2 * cb * G polynomials of at most L + alpha rows)
+static void hy_hoist_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t R, size_t *cb_out, size_t *G_out)
+{
+    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
+    const size_t shared = hy_hoist_shared_rows(L, alpha) * row, rot = hy_hoist_rotation_rows(L, alpha) * row;
+    const size_t cap = 65535 / (2 * (L + alpha));
+    size_t cb = budget / (shared + rot);
+    cb = cb < 1 ? 1 : cb;
+    cb = cb > cap ? cap : cb;
+    cb = cb < batch ? cb : batch;
+    size_t G = budget / cb > shared ? (budget / cb - shared) / rot : 0;
+    G = G < 1 ? 1 : G;
+    G = G > cap / cb ? cap / cb : G;
+    *cb_out = cb;
+    *G_out = G < R ? G : R;
+}
+
+static int hy_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t elt, size_t L, size_t alpha, uint64_t *correction, hipStream_t s)
+{
+    const size_t rows = L + alpha, beta = hy_beta(L, alpha);
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    void *wsp;
+    MOAI_TRY(workspace(c, hy_align(rows * c->n * sizeof(uint64_t)), s, &wsp));
+    uint64_t *mask = static_cast<uint64_t *>(wsp);
+    // the sign mask under every row's prime, then its forward transform
+    MOAI_TRY(galois_sign_mask(c, mask, elt, rows, s));
+    RowMap rm{};
+    for (size_t row = 0; row < rows; ++row)
+    {
+        rm.idx[row] = (uint32_t)(row < L ? row : c->k - alpha + (row - L));
+    }
+    MOAI_TRY(ntt_launch(c, mask, 1, rows, rm, false, s));
+    HyCorrArgs g;
+    g.key = key;
+    g.mask = mask;
+    g.mult = hy_hoist_mult(tab, beta);
+    g.out = correction;
+    g.pc = c->pc;
+    g.L = (uint32_t)L;
+    g.alpha = (uint32_t)alpha;
+    g.beta = (uint32_t)beta;
+    g.k = (uint32_t)c->k;
+    g.n2 = (uint32_t)(c->n >> 1);
+    hipLaunchKernelGGL(hy_hoist_correction_kernel, hy_grid(c, 2 * rows), dim3(256), 0, s, g);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+struct HyHoistRotations
+{
+    size_t R;
+    const uint32_t *elts;
+    const uint32_t *const *tables;
+    const uint64_t *const *keys, *const *corrs;
+    uint64_t *const *outs;
+};
+
+// the hoisted MAC for rotations [r0, r0 + g) of one chunk, MOAI_HYBRID_HOIST_NR of them per pass over the digits; rotation r0 + h
+// accumulates at acc + h * B * 2 * (L + alpha) * N
+static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, const HyHoistRotations &rot, size_t r0, size_t g,
+                          uint64_t *acc, size_t L, size_t alpha, size_t B, hipStream_t s)
+{
+    const long per_pass = tuning(K_HYBRID_HOIST_NR);
+    const dim3 g1 = hy_grid(c, 1);
+    for (size_t r = 0; r < g;)
+    {
+        const size_t nr = per_pass >= 4 && r + 3 < g ? 4 : (per_pass >= 2 && r + 1 < g ? 2 : 1);
+        HyHoistMacArgs m;
+        m.ext = ext;
+        m.in = in;
+        for (size_t h = 0; h < (size_t)HY_HOIST_MAX_NR; ++h)
+        {
+            const size_t rr = r + (h < nr ? h : 0);
+            m.table[h] = rot.tables[r0 + rr];
+            m.key[h] = rot.keys[r0 + rr];
+            m.corr[h] = rot.corrs[r0 + rr];
+            m.acc[h] = acc + rr * B * 2 * (L + alpha) * c->n;
+        }
+        m.pc = c->pc;
+        m.L = (uint32_t)L;
+        m.alpha = (uint32_t)alpha;
+        m.beta = (uint32_t)hy_beta(L, alpha);
+        m.k = (uint32_t)c->k;
+        m.n2 = (uint32_t)(c->n >> 1);
+        MOAI_TRY((dispatch<1, 2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
+            hipLaunchKernelGGL(hy_hoisted_mac_kernel<decltype(NR)::value>, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
+            return MOAI_OK;
+        })));
+        MOAI_LAUNCH_CHECK();
+        r += nr;
+    }
+    return MOAI_OK;
+}
+
+// one chunk of B ciphertexts at `in` [B][2][L][N]; rotation r's result goes to rot.outs[r] + out_off.  *fallback is set when
+// INTT(c1) holds a zero coefficient: nothing but the scratch has been written then, and the caller makes the separate calls.
+static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyHoistRotations &rot, size_t L, size_t alpha, size_t B,
+                              size_t cb, size_t G, bool *fallback, hipStream_t s)
+{
+    const size_t n = c->n;
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    const HyHoistLayout w = hy_hoist_layout(c, L, alpha, cb, G);
+    void *wsp;
+    MOAI_TRY(workspace(c, w.total, s, &wsp));
+    uint32_t *flag = reinterpret_cast<uint32_t *>(hy_at(wsp, w.flag));
+    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
+    uint64_t *pc0 = hy_at(wsp, w.c0);
+    // steps 1-3 on the UNPERMUTED c1, once for all rotations
+    MOAI_TRY(hy_decompose(c, tab, in, 2 * L, L, L, alpha, B, t, ext, s));
+    MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
+    MOAI_TRY(any_zero(t, B * L * n, flag, s));
+    uint32_t host_flag = 0;
+    MOAI_HIP_CHECK(hipMemcpyAsync(&host_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    MOAI_HIP_CHECK(hipStreamSynchronize(s));
+    *fallback = host_flag != 0; // a zero coefficient: the identity does not hold for it
+    if (*fallback)
+    {
+        return MOAI_OK;
+    }
+    return for_chunks(rot.R, G, [&](size_t r0, size_t g) {
+        MOAI_TRY(hy_hoisted_mac(c, ext, in, rot, r0, g, acc, L, alpha, B, s));
+        // pc0 [g][B][L][N] = perm_r(c0): the addend of the even polynomials (add_mode 2, ciphertexts L rows apart)
+        for (size_t r = 0; r < g; ++r)
+        {
+            MOAI_TRY(galois_permute_c0(c, in, pc0 + r * B * L * n, B, L, rot.elts[r0 + r], s));
+        }
+        // steps 5 over (rotation, ciphertext) pairs
+        MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, g * B, s));
+        for (size_t r = 0; r < g; ++r)
+        {
+            MOAI_TRY(hy_finalize(c, tab, acc + r * B * 2 * (L + alpha) * n, conv + r * B * 2 * L * n, rot.outs[r0 + r] + out_off, L, alpha, B,
+                                 pc0 + r * B * L * n, L, 2, s));
+        }
+        return MOAI_OK;
+    });
+}
+
 } // namespace moai
 
 using namespace moai;
@@ -686,4 +1038,103 @@ extern "C" int moai_apply_galois_hybrid(moai_ctx *c, uint64_t *ct, size_t L, siz
     MOAI_AUDIT(stream, ct, key);
     trace_op("apply_galois_hybrid", L, batch);
     return hy_entry(c, HY_GALOIS, ct, nullptr, key, L, alpha, galois_elt, batch, stream);
+}
+
+extern "C" int moai_hybrid_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t galois_elt, size_t L, size_t alpha,
+                                            uint64_t *correction, void *stream)
+{
+    MOAI_AUDIT(stream, key, correction);
+    trace_op("hybrid_hoist_correction", L, 1);
+    if (!(galois_elt & 1u))
+    {
+        return set_error(MOAI_EINVAL, "Galois element is not valid");
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (galois_elt >= 2 * c->n)
+    {
+        return set_error(MOAI_EINVAL, "Galois element is not valid");
+    }
+    if (!key || !correction)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    MOAI_TRY(enter_device(c));
+    return hy_hoist_correction(c, key, galois_elt, L, alpha, correction, (hipStream_t)stream);
+}
+
+extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in, uint64_t *const *outs, size_t L, size_t alpha,
+                                                const uint32_t *galois_elts, const uint64_t *const *keys,
+                                                const uint64_t *const *corrections, size_t R, size_t batch, int *used_fallback, void *stream)
+{
+    MOAI_AUDIT(stream, in);
+    for (size_t r = 0; outs && keys && corrections && r < R; ++r)
+    {
+        MOAI_AUDIT(stream, outs[r], keys[r], corrections[r]);
+    }
+    trace_op("apply_galois_hybrid_hoisted", L, batch * R);
+    if (used_fallback)
+    {
+        *used_fallback = 0;
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (batch == 0 || R == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!in || !outs || !galois_elts || !keys || !corrections)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t n = c->n, ct_bytes = batch * 2 * L * n * sizeof(uint64_t);
+    for (size_t r = 0; r < R; ++r)
+    {
+        if (!keys[r] || !corrections[r] || !outs[r])
+        {
+            return set_error(MOAI_EINVAL, "null key, correction or output");
+        }
+        if (!(galois_elts[r] & 1u) || galois_elts[r] >= 2 * n)
+        {
+            return set_error(MOAI_EINVAL, "Galois element is not valid");
+        }
+        if (overlap(outs[r], ct_bytes, in, ct_bytes))
+        {
+            return set_error(MOAI_EINVAL, "an output must not alias the input");
+        }
+        for (size_t q = 0; q < r; ++q)
+        {
+            if (overlap(outs[r], ct_bytes, outs[q], ct_bytes))
+            {
+                return set_error(MOAI_EINVAL, "an output must not alias another output");
+            }
+        }
+    }
+    MOAI_TRY(enter_device(c));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<const uint32_t *> tables(R);
+    for (size_t r = 0; r < R; ++r)
+    {
+        MOAI_TRY(galois_table(c, galois_elts[r], &tables[r])); // built before the first launch of the call
+    }
+    const HyHoistRotations rot = { R, galois_elts, tables.data(), keys, corrections, outs };
+    size_t cb, G;
+    hy_hoist_chunk(c, L, alpha, batch, R, &cb, &G);
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        const size_t off = b0 * 2 * L * n;
+        bool fallback = false;
+        MOAI_TRY(hy_hoist_chunk_run(c, in + off, off, rot, L, alpha, B, cb, G, &fallback, s));
+        if (fallback)
+        {
+            // the separate rotations of this chunk, each on a copy of the input (they take the lock and the workspace themselves)
+            if (used_fallback)
+            {
+                *used_fallback = 1;
+            }
+            for (size_t r = 0; r < R; ++r)
+            {
+                MOAI_HIP_CHECK(hipMemcpyAsync(outs[r] + off, in + off, B * 2 * L * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+                MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, nullptr, keys[r], L, alpha, galois_elts[r], B, stream));
+            }
+        }
+        return MOAI_OK;
+    });
 }

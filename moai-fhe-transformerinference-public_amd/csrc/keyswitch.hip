@@ -1397,6 +1397,10 @@ static void hoist_contig_finish(moai_ctx *c, uint64_t *tmp, size_t L, size_t bat
             a.sel.idx[a.Lsel] = (uint32_t)(g * L + J);
             a.selp.idx[a.Lsel++] = grp.prime[g];
         }
+        if (a.Lsel == 0)
+        {
+            continue; // L = 1: the only digit of a data prime's member is the one read from the ciphertext
+        }
         a.total_work = a.n_poly * a.Lsel * tpr;
         hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
     }
@@ -1512,6 +1516,21 @@ static HoistLayout hoist_layout(const moai_ctx *c, size_t L, size_t batch, size_
     return w;
 }
 
+int galois_sign_mask(moai_ctx *c, uint64_t *mask, uint32_t galois_elt, size_t copies, hipStream_t s)
+{
+    hipLaunchKernelGGL(galois_sign_mask_kernel, dim3((uint32_t)((c->n + 255) / 256)), dim3(256), 0, s, mask, (uint32_t)c->logn, galois_elt,
+                       (uint32_t)copies);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+int any_zero(const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s)
+{
+    hipLaunchKernelGGL(any_zero_kernel, dim3(1024), dim3(256), 0, s, v, words / 2, flag);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
 } // namespace moai
 
 extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, uint32_t galois_elt, size_t L, uint64_t *correction,
@@ -1540,9 +1559,7 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
     void *wsp;
     MOAI_TRY(workspace(c, align256((L + 1) * row_bytes), s, &wsp));
     uint64_t *mask = static_cast<uint64_t *>(wsp);
-    hipLaunchKernelGGL(galois_sign_mask_kernel, dim3((uint32_t)((c->n + 255) / 256)), dim3(256), 0, s, mask, (uint32_t)c->logn, galois_elt,
-                       (uint32_t)(L + 1));
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY(galois_sign_mask(c, mask, galois_elt, L + 1, s));
     std::vector<uint32_t> pidx(L + 1);
     for (size_t i = 0; i < L; ++i)
     {
@@ -1660,8 +1677,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
         MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, in, 2 * L, L));
         MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(any_zero_kernel, dim3(1024), dim3(256), 0, s, t, batch * L * n / 2, flag);
-        MOAI_LAUNCH_CHECK();
+        MOAI_TRY(any_zero(t, batch * L * n, flag, s));
         uint32_t host_flag = 0;
         MOAI_HIP_CHECK(hipMemcpyAsync(&host_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         MOAI_HIP_CHECK(hipStreamSynchronize(s));

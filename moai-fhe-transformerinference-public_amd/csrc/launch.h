@@ -34,7 +34,8 @@ namespace moai {
     X(MATMUL_FP, 1, "0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel")                                      \
     X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")                     \
     X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller") \
-    X(HYBRID_TMP_KB, 16777216, "KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight")
+    X(HYBRID_TMP_KB, 16777216, "KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight") \
+    X(HYBRID_HOIST_NR, 4, "rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1")
 
 enum Knob
 {
@@ -139,6 +140,11 @@ int reserve_for_stream(moai_ctx *c, void *stream, size_t bytes, void **out, bool
 int galois_table(moai_ctx *c, uint32_t elt, const uint32_t **out);
 // out [batch][L][N] = the Galois permutation of polynomial 0 of every ciphertext of in [batch][2][L][N]
 int galois_permute_c0(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t batch, size_t L, uint32_t galois_elt, hipStream_t s);
+// the hoisted rotations' kernels of keyswitch_kernels.hip.h for another translation unit (hybrid.hip):
+// mask [copies][N], every copy = 1 where x -> x^elt negates the coefficient that lands there (galois_sign_mask_kernel)
+int galois_sign_mask(moai_ctx *c, uint64_t *mask, uint32_t galois_elt, size_t copies, hipStream_t s);
+// *flag |= 1 when one of the `words` (an even number) words at v is zero (any_zero_kernel); the caller clears the flag
+int any_zero(const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s);
 // out [members][rows_per_member][N]: rows src_off_rows .. src_off_rows + rows_per_member - 1 of lst->ins[b], permuted by
 // lst->tables[b]; lst is a device pointer (common.h KsList)
 int galois_gather_list(moai_ctx *c, const KsList *lst, uint64_t *out, size_t members, size_t rows_per_member, size_t src_off_rows,

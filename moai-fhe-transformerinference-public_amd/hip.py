@@ -112,6 +112,8 @@ SYMBOLS = {
     "moai_switch_key_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_relinearize_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_apply_galois_hybrid": (C.c_int, [vp, vp, sz, sz, C.c_uint32, vp, sz, vp]),
+    "moai_hybrid_hoist_correction": (C.c_int, [vp, vp, C.c_uint32, sz, sz, vp, vp]),
+    "moai_apply_galois_hybrid_hoisted": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_int), vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -399,6 +401,29 @@ class Context:
 
     def apply_galois_hybrid(self, ct, L, alpha, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois_hybrid(self.h, _ptr(ct), L, alpha, int(elt), _ptr(key), batch, stream))
+
+    def hybrid_hoist_correction(self, key, elt, L, alpha, stream=None):
+        """the per-(key, element, level) constant of the hoisted hybrid rotations: DeviceBuffer [2][L+alpha][N]"""
+        out = DeviceBuffer(2 * (L + alpha) * self.n)
+        _check(lib().moai_hybrid_hoist_correction(self.h, _ptr(key), int(elt), L, alpha, _ptr(out), stream))
+        return out
+
+    def apply_galois_hybrid_hoisted(self, src, dst, L, alpha, elts, keys, corrections, batch, stream=None):
+        """dst[r] = apply_galois_hybrid(copy of src, elts[r], keys[r]) for every r with one digit decomposition (dst: one buffer
+        [R][batch][2][L][N] or a list of R buffers); returns True when the library had to fall back to separate calls (a zero
+        coefficient in INTT(c1))"""
+        R = len(elts)
+        if isinstance(dst, (list, tuple)):
+            op = (vp * R)(*[_ptr(d) for d in dst])
+        else:
+            words = batch * 2 * L * self.n * 8
+            op = (vp * R)(*[_ptr(dst) + r * words for r in range(R)])
+        e = (C.c_uint32 * R)(*[int(x) for x in elts])
+        kp = (vp * R)(*[_ptr(k) for k in keys])
+        cp = (vp * R)(*[_ptr(k) for k in corrections])
+        fb = C.c_int(0)
+        _check(lib().moai_apply_galois_hybrid_hoisted(self.h, _ptr(src), op, L, alpha, e, kp, cp, R, batch, C.byref(fb), stream))
+        return bool(fb.value)
 
     def apply_galois_to(self, src, dst, L, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois_to(self.h, _ptr(src), _ptr(dst), L, int(elt), _ptr(key), batch, stream))
