@@ -36,8 +36,12 @@ struct alignas(16) PrimeConst
     uint64_t fp_mode;  // 0: integer only; M_FPN or M_FPR
     uint64_t nq;       // 2^64 - q     } M_LAZY8 (modarith.hip.h): stored, not derived on the device, so that the compiler
     uint64_t n4q;      // 2^64 - 4 q   } keeps  t * (-q)  a multiply-add chain instead of a 64-bit subtract
-    uint64_t pad[3];
+    uint64_t qh;       // (q - 1) / N: N^-1 = -qh mod q, the last inverse stage's N^-1 by shift (ntt_finish.h)
+    uint32_t red_m;    // floor(2^(32 + red_s) / q)  } the one-step final reduction of the lazy modes
+    uint32_t red_s;    // max(bits(q) - 20, 0)       } (ntt_finish.h final_quotient_step)
+    uint64_t pad[1];
 };
+static_assert(sizeof(PrimeConst) == 128, "one 128-byte record per prime");
 
 // Row -> context-prime map passed by value to kernels (rows of one RNS polynomial).
 struct RowMap

@@ -14,6 +14,7 @@
 
 #include "hostmath.h"
 #include "launch.h"
+#include "ntt_finish.h"
 
 namespace moai {
 
@@ -268,6 +269,9 @@ static void build_prime(int logn, uint64_t q, uint64_t psi, Tw *fwd, Tw *inv, Pr
     pc->q2 = q << 1;
     pc->nq = 0 - q;
     pc->n4q = 0 - (q << 2);
+    pc->qh = ninv_shift_qh(q, logn);
+    pc->red_s = final_step_shift(q);
+    pc->red_m = final_step_mult(q, pc->red_s);
     {
         // floor(2^128 / q)
         u128 hi = ((u128)1 << 64);

@@ -3,6 +3,7 @@
 // canonical residues equal the reference's (SEAL/util/uintarithsmallmod.h:167-326).
 #pragma once
 #include "common.h"
+#include "ntt_finish.h"
 
 namespace moai {
 
@@ -310,13 +311,14 @@ __device__ __forceinline__ void ct_bfly_guard2(uint64_t &x, uint64_t &y, uint64_
 //    high word, with n = 2^64 - q read from the per-prime record (no subtract);
 //  * every stage guards  u = x - 4q if x >= 4q  by adding 2^64 - 4q and testing the sign (values stay below 8q < 2^63), so
 //    x' = u + r < 8q and y' = u + 4q - r in (0, 8q): the same residues as the reference's [0, 4q) discipline.
-// The pass that finishes the transform reduces below q with three such conditional subtractions.
+// The pass that finishes the transform reduces below q with one quotient step and one such conditional subtraction (ntt_finish.h).
 __device__ __forceinline__ uint64_t csub_sign(uint64_t x, uint64_t neg_m)
 {
     // x - m if x >= m else x, for x < 2^63 and m <= 2^62, given 2^64 - m
     uint64_t d = x + neg_m;
     return (int64_t)d < 0 ? x : d;
 }
+// (the result's two words are put together by pack64, ntt_finish.h: as a shift and an OR the high word's sum is widened to 64 bits)
 __device__ __forceinline__ uint64_t mul_shoup_approx(uint64_t y, uint64_t w, uint64_t wq, uint64_t nq)
 {
     const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32);
@@ -329,7 +331,7 @@ __device__ __forceinline__ uint64_t mul_shoup_approx(uint64_t y, uint64_t w, uin
     uint64_t p = (uint64_t)y0 * w0;
     p += (uint64_t)t0 * n0;
     const uint32_t hi = (uint32_t)(p >> 32) + y0 * w1 + y1 * w0 + t0 * n1 + t1 * n0;
-    return ((uint64_t)hi << 32) | (uint32_t)p;
+    return pack64((uint32_t)p, hi);
 }
 // x, y below 8q -> below 8q; nq = 2^64 - q, n4q = 2^64 - 4q
 __device__ __forceinline__ void ct_bfly_lazy8(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t nq, uint64_t n4q)
@@ -348,10 +350,13 @@ __device__ __forceinline__ void gs_bfly_lazy8(uint64_t &x, uint64_t &y, uint64_t
     x = csub_sign(u + v, n4q);
     y = mul_shoup_approx(u - (v + n4q), w, wq, nq);
 }
-__device__ __forceinline__ void gs_bfly_last_lazy8(uint64_t &x, uint64_t &y, const Tw &ninv, const Tw &ninv_w1, uint64_t nq, uint64_t n4q)
+// (tiled kernels, LOGN >= 12: the sum, below 8q, takes N^-1 by shift and comes out below 2q; qh = (q - 1) / N)
+template <int LOGN>
+__device__ __forceinline__ void gs_bfly_last_lazy8(uint64_t &x, uint64_t &y, uint64_t qh, const Tw &ninv_w1, uint64_t nq, uint64_t n4q)
 {
+    static_assert(LOGN >= 12, "N^-1 by shift returns less than 2q from logn = 12 on");
     const uint64_t u = x, v = y;
-    x = mul_shoup_approx(u + v, ninv.w, ninv.wq, nq);
+    x = ninv_by_shift(u + v, qh, LOGN);
     y = mul_shoup_approx(u - (v + n4q), ninv_w1.w, ninv_w1.wq, nq);
 }
 // ---- M_LAZY16: M_LAZY8 with a guard only where the bound needs one (q < 2^60) ------------------------------------------
@@ -368,17 +373,17 @@ __device__ __forceinline__ uint64_t csub_carry(uint64_t x, uint64_t neg_m)
 }
 // Forward: u + v and u + 4q - v are below bound(u) + 4q.  Stages [first, first + count) of a 2^logn transform from bound b0: a
 // stage goes unguarded iff its input bound + 4q <= 16q, else x takes one conditional subtraction of 8q (below 16q -> below 8q);
-// the transform's last stage brings x below 4q (8q, then 4q), so that its outputs are below 8q.  Bit s of g8 / g4: stage s
-// subtracts 8q / 4q conditionally.
+// the transform's last stage brings x below 8q whatever its input bound, so that its outputs are below 12q: the one-step final
+// reduction (ntt_finish.h final_quotient_step) accepts 16q.  Bit s of g8: stage s subtracts 8q conditionally.
 struct Lazy16Fwd
 {
-    uint32_t g8, g4;
+    uint32_t g8;
     int end;  // bound of the outputs of the last stage run
     int peak; // largest bound met
 };
 constexpr Lazy16Fwd lazy16_fwd(int logn, int first, int count, int b0)
 {
-    Lazy16Fwd r{ 0, 0, b0, b0 };
+    Lazy16Fwd r{ 0, b0, b0 };
     int b = b0;
     for (int s = first; s < first + count; ++s)
     {
@@ -389,11 +394,6 @@ constexpr Lazy16Fwd lazy16_fwd(int logn, int first, int count, int b0)
             {
                 r.g8 |= 1u << s;
                 u = u - 8 > 8 ? u - 8 : 8;
-            }
-            if (u > 4)
-            {
-                r.g4 |= 1u << s;
-                u = u - 4 > 4 ? u - 4 : 4;
             }
         }
         else if (b + 4 > 16)
@@ -412,18 +412,14 @@ constexpr int lazy16_fwd_handover(int logn)
 {
     return (logn & 1) ? 12 : 16;
 }
-// G: bit 0 = x takes a conditional subtraction of 8q, bit 1 = (then) of 4q; nq = 2^64 - q, n4q = 2^64 - 4q
-template <int G>
+// G: x takes a conditional subtraction of 8q; nq = 2^64 - q, n4q = 2^64 - 4q
+template <bool G>
 __device__ __forceinline__ void ct_bfly_lazy16(uint64_t &x, uint64_t &y, uint64_t w, uint64_t wq, uint64_t nq, uint64_t n4q)
 {
     uint64_t u = x;
-    if (G & 1)
+    if (G)
     {
         u = csub_carry(u, n4q << 1);
-    }
-    if (G & 2)
-    {
-        u = csub_carry(u, n4q);
     }
     const uint64_t v = mul_shoup_approx(y, w, wq, nq);
     x = u + v;
@@ -435,16 +431,19 @@ __device__ __forceinline__ void ct_bfly_lazy16(uint64_t &x, uint64_t &y, uint64_
 // stage of distance h the registers with bit h set hold products, and the next stage (distance 2h) pairs registers that agree in
 // bit h.  One block of `count` stages from inputs below bin q: bit i of xk = the butterflies of stage i that are not known to
 // take two products (all of stage 0) have inputs up to 8q -- guard the sum with 8q, form the difference as u - v + 8q; otherwise
-// inputs below 4q, no guard, u - v + 4q.  The transform's last stage (`last`) multiplies both outputs and guards nothing.
+// inputs below 4q, no guard, u - v + 4q.  The transform's last stage (`last`) guards nothing: its difference goes through the
+// product with N^-1 w_1 (below 4q), its sum -- below 16q, as `peak` proves -- through N^-1 by shift (ntt_finish.h ninv_by_shift:
+// below 2q), so the two halves of its outputs end with different bounds, `out` and `xlast`.
 struct Lazy16Inv
 {
     uint32_t xk;
-    int out;  // bound of the block's outputs
-    int peak; // largest bound met, sums before their guard included
+    int out;   // bound of the block's outputs
+    int peak;  // largest bound met, sums before their guard included
+    int xlast; // `last`: bound of the sums times N^-1
 };
 constexpr Lazy16Inv lazy16_inv(int count, int bin, bool last)
 {
-    Lazy16Inv r{ 0, bin, bin };
+    Lazy16Inv r{ 0, bin, bin, 0 };
     int bx = bin;
     for (int i = 0; i < count; ++i)
     {
@@ -456,7 +455,12 @@ constexpr Lazy16Inv lazy16_inv(int count, int bin, bool last)
             r.peak = bx > 8 ? 99 : r.peak; // u - v + 8q needs v below 8q
         }
         r.peak = sum > r.peak ? sum : r.peak;
-        const int xout = fin ? 4 : (sum > 8 ? (sum - 8 > 8 ? sum - 8 : 8) : sum);
+        if (fin)
+        {
+            r.peak = sum > NINV_SHIFT_IN ? 99 : r.peak;
+            r.xlast = NINV_SHIFT_OUT;
+        }
+        const int xout = fin ? NINV_SHIFT_OUT : (sum > 8 ? (sum - 8 > 8 ? sum - 8 : 8) : sum);
         const int pout = (i > 0 && !fin) ? 8 : 4; // sums of two products; the products themselves
         bx = xout > pout ? xout : pout;
     }
@@ -476,11 +480,12 @@ __device__ __forceinline__ void gs_bfly_lazy16(uint64_t &x, uint64_t &y, uint64_
     x = K ? csub_carry(u + v, n4q << 1) : u + v;
     y = mul_shoup_approx(u - (v + (K ? n4q << 1 : n4q)), w, wq, nq);
 }
-template <int K>
-__device__ __forceinline__ void gs_bfly_last_lazy16(uint64_t &x, uint64_t &y, const Tw &ninv, const Tw &ninv_w1, uint64_t nq, uint64_t n4q)
+template <int K, int LOGN>
+__device__ __forceinline__ void gs_bfly_last_lazy16(uint64_t &x, uint64_t &y, uint64_t qh, const Tw &ninv_w1, uint64_t nq, uint64_t n4q)
 {
+    static_assert(LOGN >= 12, "N^-1 by shift returns less than 2q from logn = 12 on");
     const uint64_t u = x, v = y;
-    x = mul_shoup_approx(u + v, ninv.w, ninv.wq, nq);
+    x = ninv_by_shift(u + v, qh, LOGN); // (lazy16_inv: the sum is below 16q)
     y = mul_shoup_approx(u - (v + (K ? n4q << 1 : n4q)), ninv_w1.w, ninv_w1.wq, nq);
 }
 // the kind of the butterfly on registers (j, j + half) in stage i of a block with schedule xk; a constant once the caller's loops
@@ -604,16 +609,12 @@ __device__ __forceinline__ void gs_bfly_t(uint64_t &x, uint64_t &y, uint64_t w, 
         gs_bfly(x, y, w, wq, q, q2);
     }
 }
-// the same for the last stage of the transform, N^-1 folded in
+// the same for the last stage of the transform, N^-1 folded in (the lazy modes have their own: gs_bfly_last_lazy8 / _lazy16)
 template <int MODE>
 __device__ __forceinline__ void gs_bfly_last_t(uint64_t &x, uint64_t &y, const Tw &ninv, const Tw &ninv_w1, uint64_t q, uint64_t q2)
 {
-    static_assert(MODE == M_GUARD || MODE == M_LAZY8 || mode_fp(MODE), "no inverse butterfly of this mode");
-    if (MODE == M_LAZY8)
-    {
-        gs_bfly_last_lazy8(x, y, ninv, ninv_w1, q, q2);
-    }
-    else if (mode_fp(MODE))
+    static_assert(MODE == M_GUARD || mode_fp(MODE), "no inverse butterfly of this mode");
+    if (mode_fp(MODE))
     {
         gs_bfly_last_fp<MODE == M_FPR>(x, y, fp_from_u64(ninv.w), fp_from_u64(ninv_w1.w), u2d(q), u2d(q2));
     }

@@ -104,6 +104,19 @@ __device__ __forceinline__ uint64_t mode_q2(const PrimeConst &pc)
 {
     return mode_fp(MODE) ? pc.qinv : (mode_lazy(MODE) ? pc.n4q : pc.q2);
 }
+// the `cr1` argument of fwd_contig_tile, the constant of the pass's final reduction: M_NOGUARD's Barrett word, or the lazy modes'
+// quotient step (ntt_finish.h), red_m in the low and red_s in the high word
+template <int MODE>
+__device__ __forceinline__ uint64_t mode_fin(const PrimeConst &pc)
+{
+    return mode_lazy(MODE) ? ((uint64_t)pc.red_s << 32) | pc.red_m : pc.cr1;
+}
+// the end of a lazy transform: a value below 16q to its canonical residue; nq = 2^64 - q, fin = mode_fin
+__device__ __forceinline__ uint64_t lazy_final(uint64_t z, uint64_t nq, uint64_t fin)
+{
+    static_assert(FINAL_STEP_OUT == 2, "one conditional subtraction follows the quotient step");
+    return csub_sign(final_quotient_step(z, (uint32_t)(fin >> 32), (uint32_t)fin, nq), nq);
+}
 
 // =====================================================================================================
 // forward, strided pass: stages 0 .. LOGN-9
@@ -170,25 +183,16 @@ __device__ __forceinline__ void ct_bfly_stage(uint64_t &x, uint64_t &y, uint64_t
         constexpr Lazy16Fwd p1 = lazy16_fwd(LOGN, 0, R1, 8), p2 = lazy16_fwd(LOGN, R1, 8, lazy16_fwd_handover(LOGN));
         static_assert(p1.peak <= 16 && p2.peak <= 16, "a value of 16q or more");
         static_assert(p1.end == lazy16_fwd_handover(LOGN), "the contiguous pass starts from another bound");
-        static_assert(p2.end <= 8, "the final subtractions expect values below 8q");
-        constexpr uint32_t g8 = p1.g8 | p2.g8, g4 = p1.g4 | p2.g4;
+        static_assert(p2.end <= FINAL_STEP_IN, "the final reduction expects values below 16q");
+        constexpr uint32_t g8 = p1.g8 | p2.g8;
         const int s = LOGN - 1 - stages_left;
-        const int g = (int)((g8 >> s) & 1u) | ((int)((g4 >> s) & 1u) << 1);
-        if (g == 0)
+        if ((g8 >> s) & 1u)
         {
-            ct_bfly_lazy16<0>(x, y, w, wq, q, q2);
-        }
-        else if (g == 1)
-        {
-            ct_bfly_lazy16<1>(x, y, w, wq, q, q2);
-        }
-        else if (g == 2)
-        {
-            ct_bfly_lazy16<2>(x, y, w, wq, q, q2);
+            ct_bfly_lazy16<true>(x, y, w, wq, q, q2);
         }
         else
         {
-            ct_bfly_lazy16<3>(x, y, w, wq, q, q2);
+            ct_bfly_lazy16<false>(x, y, w, wq, q, q2);
         }
     }
     else if (MODE == M_GUARD2)
@@ -597,10 +601,11 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
         }
         else if (mode_lazy(MODE))
         {
-            // values below 8q; (q, q2) = (2^64 - q, 2^64 - 4q), and 2^64 - 2q = (2^64 - 4q) / 2 + 2^63
-            const uint64_t n2q = (q2 >> 1) | 0x8000000000000000ull;
-            v.x = csub_sign(csub_sign(csub_sign(x[2 * c], q2), n2q), q);
-            v.y = csub_sign(csub_sign(csub_sign(x[2 * c + 1], q2), n2q), q);
+            // values below 8q (M_LAZY8) or 12q (M_LAZY16, ct_bfly_stage); `q` carries 2^64 - q, `cr1` mode_fin.  One quotient step and one
+            // conditional subtraction, 10 vector instructions, where three conditional subtractions (from 8q) take 12 -- and the
+            // last stage of M_LAZY16 keeps the guard that brought its outputs below 8q for them
+            v.x = lazy_final(x[2 * c], q, cr1);
+            v.y = lazy_final(x[2 * c + 1], q, cr1);
         }
         else if (MODE == M_GUARD2)
         {
@@ -642,14 +647,17 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
                                                 const Tw *__restrict__ twb, uint64_t cr1 = 0, Tw *ldstw = nullptr)
 {
+    static_assert(!mode_lazy(MODE), "the lazy modes' final reduction needs mode_fin, not a default");
     StoreTile st;
     st.out = reinterpret_cast<ulonglong2 *>(rowp + ((size_t)tile << 12));
     fwd_contig_tile<LOGN, MODE, StoreTile>(rowp, tile, tw, q, q2, lds2, tid, twb, cr1, st, ldstw);
 }
 
 // TWL (fwd_contig_tile): -1 = NttArgs::lds_twiddles decides at run time, 0 / 1 = compiled in (M_LAZY16)
+// (36.6 KiB of LDS admit four workgroups per CU, and every mode's body fits the 128 registers that go with them; said here so that
+// the allocator does not settle for 129 and three)
 template <int LOGN, int MODE = M_GUARD, int TWL = -1>
-__global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
+__global__ __launch_bounds__(256, 4) void ntt_fwd_contig(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
     __shared__ ulonglong2 lds2[2048 + 240]; // the tile, and the first four stages' twiddles (fwd_contig_tile, ldstw)
@@ -664,7 +672,7 @@ __global__ __launch_bounds__(256) void ntt_fwd_contig(NttArgs a)
     StoreTile st;
     st.out = reinterpret_cast<ulonglong2 *>(rowp + ((size_t)tile << 12));
     fwd_contig_tile<LOGN, MODE, StoreTile, TWL>(rowp, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc), lds2, threadIdx.x,
-                                                a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), pc.cr1, st,
+                                                a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), mode_fin<MODE>(pc), st,
                                                 (TWL < 0 ? a.lds_twiddles != 0 : TWL == 1) ? reinterpret_cast<Tw *>(lds2 + 2048) : nullptr);
 }
 
@@ -850,7 +858,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
     // M_LAZY16: phase B's RB stages from what the contiguous pass hands over, then phase A's four, the transform's last among them
     constexpr Lazy16Inv zb = lazy16_inv(RB, lazy16_inv_handover(), false), za = lazy16_inv(4, zb.out, true);
     static_assert(zb.peak <= 16 && za.peak <= 16, "a value of 16q or more");
-    static_assert(za.out <= 4, "the final subtractions expect values below 4q");
+    static_assert(za.out <= 4 && za.xlast <= 2, "the final subtractions expect products below 4q and the sums times N^-1 below 2q");
 
     // LDSTW (the lazy modes at N = 2^16: four workgroups per CU either way): phase B's twiddles -- entries 16..255 of the table, shared by
     // the sixteen threads of a group -- through a copy in LDS (`lds` + 4096 words), as in the forward strided pass
@@ -928,6 +936,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
     {
         const Tw ninv = pc->ninv;
         const Tw ninv_w1 = pc->ninv_w1;
+        const uint64_t qh = pc->qh;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
         {
@@ -935,12 +944,16 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
             {
                 if (lazy16_inv_kind(za.xk, 3, j, 8))
                 {
-                    gs_bfly_last_lazy16<1>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
+                    gs_bfly_last_lazy16<1, LOGN>(x[j], x[j + 8], qh, ninv_w1, q, q2);
                 }
                 else
                 {
-                    gs_bfly_last_lazy16<0>(x[j], x[j + 8], ninv, ninv_w1, q, q2);
+                    gs_bfly_last_lazy16<0, LOGN>(x[j], x[j + 8], qh, ninv_w1, q, q2);
                 }
+            }
+            else if constexpr (MODE == M_LAZY8)
+            {
+                gs_bfly_last_lazy8<LOGN>(x[j], x[j + 8], qh, ninv_w1, q, q2);
             }
             else
             {
@@ -952,9 +965,23 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
     for (int j = 0; j < 16; ++j)
     {
         uint32_t e = (uint32_t)j * 256u + tid;
-        // exact: below 2q; lazy: below 4q, with 2^64 - 2q = (2^64 - 4q) / 2 + 2^63
-        row[((e >> GB) << 8) + (e & (G - 1))] = mode_fp(MODE) ? fp_to_canonical(u2d(x[j]), u2d(q), u2d(q2))
-                                                              : (mode_lazy(MODE) ? csub_sign(csub_sign(x[j], (q2 >> 1) | 0x8000000000000000ull), q) : csub(x[j], q));
+        uint64_t v;
+        if (mode_fp(MODE))
+        {
+            v = fp_to_canonical(u2d(x[j]), u2d(q), u2d(q2));
+        }
+        else if (mode_lazy(MODE))
+        {
+            // registers 0..7 hold the last stage's sums times N^-1, below 2q: one conditional subtraction; registers 8..15 its
+            // products, below 4q: two, with 2^64 - 2q = (2^64 - 4q) / 2 + 2^63.  (The quotient step of the forward pass would take
+            // 10 vector instructions where these chains take 4 and 8.)
+            v = j < 8 ? csub_sign(x[j], q) : csub_sign(csub_sign(x[j], (q2 >> 1) | 0x8000000000000000ull), q);
+        }
+        else
+        {
+            v = csub(x[j], q); // below 2q
+        }
+        row[((e >> GB) << 8) + (e & (G - 1))] = v;
     }
 }
 
