@@ -6,8 +6,8 @@
 // 16-byte accesses, one RNS prime per block row (blockIdx.y = polynomial row), so the per-prime
 // constants are wave-uniform scalars.
 //
-// Layout of this file: the kernels, the host helpers every entry point shares (check_rows, fill_rows, launch_rows;
-// for_term_chunks is launch.h's), then the entry points by family.  A new fused sum is a kernel of its own that accumulates each lane
+// Layout of this file: the kernels, the host helpers every entry point shares (check_rows; fill_rows and launch_rows
+// are rowlaunch.h's, for_term_chunks is launch.h's), then the entry points by family.  A new fused sum is a kernel of its own that accumulates each lane
 // pair with mac2 / fold2 / reduce2 (modarith.hip.h), an args struct that fill_rows fills, and one launch_rows call.
 #include <algorithm>
 #include <mutex>
@@ -887,12 +887,6 @@ __global__ void galois_table_kernel(uint32_t *table, int logn, uint32_t elt)
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------------------------
-static inline dim3 row_grid(const moai_ctx *c, size_t rows)
-{
-    const uint32_t n2 = (uint32_t)(c->n >> 1);
-    return dim3(std::max(1u, (n2 + 255u) / 256u), (uint32_t)rows);
-}
-
 static int check_rows(const moai_ctx *c, size_t n_poly, size_t L)
 {
     if (!c)
@@ -908,26 +902,6 @@ static int check_rows(const moai_ctx *c, size_t n_poly, size_t L)
         return set_error(MOAI_EINVAL, "batch too large for one launch");
     }
     return enter_device(c);
-}
-
-// the three fields every args struct describes its rows with
-template <class Args>
-static void fill_rows(Args &g, const moai_ctx *c, size_t L)
-{
-    g.pc = c->pc;
-    g.L = (uint32_t)L;
-    g.n2 = (uint32_t)(c->n >> 1);
-}
-
-// `kernel` over `rows` block rows (blockIdx.y) of 256-thread workgroups that cover a row of N / 2 chunks.  A kernel that a
-// bool selects is passed as  flag ? kernel<true> : kernel<false>.
-template <class Kernel, class... Args>
-static int launch_rows(Kernel kernel, const moai_ctx *c, size_t rows, void *stream, const Args &...args)
-{
-    MOAI_CHECK_GRID_ROWS(rows);
-    hipLaunchKernelGGL(kernel, row_grid(c, rows), dim3(256), 0, (hipStream_t)stream, args...);
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
 }
 
 // the fields the pointer-array sums share, for the chunk of `cnt` terms from t0: every chunk after the first adds onto `out`
@@ -951,12 +925,18 @@ static int check_term(const uint64_t *p, const uint64_t *out, const char *what)
     return p && p != out ? MOAI_OK : set_error(MOAI_EINVAL, "%s", what);
 }
 
-int galois_table(moai_ctx *c, uint32_t elt, const uint32_t **out)
+int galois_elt_check(const moai_ctx *c, uint32_t elt)
 {
-    if (!(elt & 1u) || elt >= 2 * c->n)
+    if (!(elt & 1u) || (c && elt >= 2 * c->n))
     {
         return set_error(MOAI_EINVAL, "Galois element is not valid");
     }
+    return MOAI_OK;
+}
+
+int galois_table(moai_ctx *c, uint32_t elt, const uint32_t **out)
+{
+    MOAI_TRY(galois_elt_check(c, elt));
     std::lock_guard<std::mutex> g(*static_cast<std::mutex *>(c->mutex));
     size_t idx = (elt - 1) >> 1; // GaloisTool::GetIndexFromElt, SEAL/util/galois.h
     if (!c->galois_tables[idx])

@@ -14,7 +14,7 @@
 //   acc      = hy_mac_kernel: sum_j ext_j (*) key[j][p][row], 128-bit sums      [B][2][L + alpha][N]
 //   x        = INTT(special rows of acc)                                        [2B][alpha][N]
 //   conv     = hy_convert_kernel: base {p_t} -> {q_i} with the rounding terms   [2B][L][N], then forward NTT
-//   out      = hy_finalize_kernel: addend + (acc - conv) P^-1
+//   out      = moddown_finalize (keyswitch.hip, the unfused mod-down's last kernel): addend + (acc - conv) P^-1
 // Hoisted rotations (R automorphisms of one ciphertext, each with its own key) run t, ext_j and their forward transforms ONCE on
 // the unpermuted c1 and replace the MAC by hy_hoisted_mac_kernel, which reads the digits through each rotation's permutation
 // table and adds that rotation's correction (hy_hoist_correction_kernel; the header states the identity).
@@ -127,51 +127,64 @@ __global__ __launch_bounds__(256) void hy_convert_kernel(HyConvArgs g)
     }
 }
 
+// what every kernel below knows of a switch at (L, alpha); hy_dims fills it
+struct HyDims
+{
+    const PrimeConst *pc;
+    uint32_t L, alpha, beta, k;
+    uint32_t n2;
+};
+
+// The operand of digit j under the prime of `row`, for ciphertext b of B, at L data primes in digits of alpha: `own` where the row is
+// one of the digit's own primes (the ciphertext's NTT-form row as it is), else the digit's converted row in ext (HyMacArgs::ext, as
+// rows of row_elems elements of T)
+template <class T>
+__device__ __forceinline__ const T *hy_digit_operand(const T *own, const T *ext, size_t row_elems, uint32_t L, uint32_t alpha, uint32_t B,
+                                                     uint32_t b, uint32_t row, uint32_t j)
+{
+    const uint32_t lo = j * alpha, hi = min(lo + alpha, L), nr = hi - lo;
+    if (row >= lo && row < hi)
+    {
+        return own;
+    }
+    const uint32_t pos = row < lo ? row : row - nr;
+    return ext + ((size_t)j * B * L + (size_t)b * (L - nr + alpha) + pos) * row_elems;
+}
+
 struct HyMacArgs
 {
     const uint64_t *ext;   // digit j's converted rows at ext + j * B * L * N: [B][L - |R_j| + alpha][N], NTT form
     const uint64_t *tgt;   // ciphertext b's NTT-form target row r at row b * tgt_stride + tgt_off + r
     const uint64_t *key;   // [beta(k - alpha)][2][k][N]
     uint64_t *acc;         // [B][2][L + alpha][N]
-    const PrimeConst *pc;
     uint32_t tgt_stride, tgt_off;
-    uint32_t L, alpha, beta, k;
-    uint32_t n2;
+    HyDims d;
 };
 
 // acc[b][p][row] = sum_{j < beta} digit_j[row] (*) key[j][p][row]; blockIdx.x = b (the workgroups that read the same key words
 // are dispatched together), blockIdx.z = row.  At most 63 products below 2^122 per sum: no fold before the one reduction.
 __global__ __launch_bounds__(256) void hy_mac_kernel(HyMacArgs g)
 {
+    const HyDims &d = g.d;
     const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
-    const PrimeConst *pc = g.pc + prime;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
     const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = g.n2;
+    const size_t n2 = d.n2;
     const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
     const ulonglong2 *tgt = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)b * g.tgt_stride + g.tgt_off) * n2;
     const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + (size_t)prime * n2;
-    ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (g.L + g.alpha) + row) * n2;
-    ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (g.L + g.alpha) + row) * n2;
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < g.n2; x += gridDim.y * 256u)
+    ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (d.L + d.alpha) + row) * n2;
+    ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (d.L + d.alpha) + row) * n2;
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
     {
         uint64_t l0x = 0, h0x = 0, l0y = 0, h0y = 0, l1x = 0, h1x = 0, l1y = 0, h1y = 0;
-        for (uint32_t j = 0; j < g.beta; ++j)
+        for (uint32_t j = 0; j < d.beta; ++j)
         {
-            const uint32_t lo = j * g.alpha, hi = min(lo + g.alpha, g.L), nr = hi - lo;
-            const ulonglong2 *op;
-            if (row >= lo && row < hi)
-            {
-                op = tgt + (size_t)row * n2; // the digit under one of its own primes is the target's row as it is
-            }
-            else
-            {
-                const uint32_t pos = row < lo ? row : row - nr;
-                op = ext + ((size_t)j * B * g.L + (size_t)b * (g.L - nr + g.alpha) + pos) * n2;
-            }
+            const ulonglong2 *op = hy_digit_operand(tgt + (size_t)row * n2, ext, n2, d.L, d.alpha, B, b, row, j);
             const ulonglong2 o = op[x];
-            const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * g.k * n2 + x];
-            const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * g.k * n2 + x];
+            const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * d.k * n2 + x];
+            const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * d.k * n2 + x];
             mac2(l0x, h0x, l0y, h0y, o, k0);
             mac2(l1x, h1x, l1y, h1y, o, k1);
         }
@@ -186,32 +199,31 @@ struct HyCorrArgs
     const uint64_t *mask; // [L + alpha][N]: NTT of the rotation's sign mask under each row's prime
     const uint64_t *mult; // [beta][L + alpha]: |R_j| D_j mod m_row
     uint64_t *out;        // [2][L + alpha][N]
-    const PrimeConst *pc;
-    uint32_t L, alpha, beta, k;
-    uint32_t n2;
+    HyDims d;
 };
 
 // out[p][row] = mask[row] (*) sum_{j < beta} mult[j][row] key[j][p][row]; blockIdx.y = p * (L + alpha) + row.  At most 63 products
 // below 2^122.  A multiplier of zero (the rows of R_j itself, D_j mod q_r = 0) is skipped: the branch is uniform.
 __global__ __launch_bounds__(256) void hy_hoist_correction_kernel(HyCorrArgs g)
 {
-    const uint32_t rows = g.L + g.alpha, p = blockIdx.y / rows, row = blockIdx.y % rows;
-    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
-    const PrimeConst *pc = g.pc + prime;
+    const HyDims &d = g.d;
+    const uint32_t rows = d.L + d.alpha, p = blockIdx.y / rows, row = blockIdx.y % rows;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
     const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = g.n2;
-    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + ((size_t)p * g.k + prime) * n2;
+    const size_t n2 = d.n2;
+    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + ((size_t)p * d.k + prime) * n2;
     const ulonglong2 *mk = reinterpret_cast<const ulonglong2 *>(g.mask) + (size_t)row * n2;
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
-    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < g.n2; x += gridDim.x * 256u)
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
     {
         uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
-        for (uint32_t j = 0; j < g.beta; ++j)
+        for (uint32_t j = 0; j < d.beta; ++j)
         {
             const uint64_t f = g.mult[j * rows + row];
             if (f)
             {
-                mac2(lx, hx, ly, hy, key[(size_t)j * 2 * g.k * n2 + x], f);
+                mac2(lx, hx, ly, hy, key[(size_t)j * 2 * d.k * n2 + x], f);
             }
         }
         o[x] = mulmod2(reduce2(lx, hx, ly, hy, q, cr0, cr1), mk[x], q, cr0, cr1);
@@ -228,9 +240,7 @@ struct HyHoistMacArgs
     const uint64_t *key[HY_HOIST_MAX_NR];   // its key [beta(k - alpha)][2][k][N]
     const uint64_t *corr[HY_HOIST_MAX_NR];  // its correction [2][L + alpha][N]
     uint64_t *acc[HY_HOIST_MAX_NR];         // its accumulators [B][2][L + alpha][N]
-    const PrimeConst *pc;
-    uint32_t L, alpha, beta, k;
-    uint32_t n2;
+    HyDims d;
 };
 
 // acc_r[b][p][row] = sum_{j < beta} digit_j[row][table_r] (*) key_r[j][p][row] + corr_r[p][row] for NR rotations in one pass over
@@ -241,14 +251,15 @@ struct HyHoistMacArgs
 template <int NR>
 __global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
 {
+    const HyDims &d = g.d;
     const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = row < g.L ? row : g.k - g.alpha + (row - g.L);
-    const PrimeConst *pc = g.pc + prime;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
     const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = g.n2;
-    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * g.L + row) * 2 * n2; // read only where row < L
-    const size_t acc_row = ((size_t)b * 2 * (g.L + g.alpha) + row) * n2, acc_poly = (size_t)(g.L + g.alpha) * n2;
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < g.n2; x += gridDim.y * 256u)
+    const size_t n2 = d.n2;
+    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * d.L + row) * 2 * n2; // read only where row < L
+    const size_t acc_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, acc_poly = (size_t)(d.L + d.alpha) * n2;
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
     {
         uint2 src[NR];
         uint64_t l0x[NR], h0x[NR], l0y[NR], h0y[NR], l1x[NR], h1x[NR], l1y[NR], h1y[NR];
@@ -258,20 +269,11 @@ __global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
             src[r] = reinterpret_cast<const uint2 *>(g.table[r])[x];
             l0x[r] = h0x[r] = l0y[r] = h0y[r] = l1x[r] = h1x[r] = l1y[r] = h1y[r] = 0;
         }
-        for (uint32_t j = 0; j < g.beta; ++j)
+        for (uint32_t j = 0; j < d.beta; ++j)
         {
-            const uint32_t lo = j * g.alpha, hi = min(lo + g.alpha, g.L), nr = hi - lo;
-            const uint64_t *op;
-            if (row >= lo && row < hi)
-            {
-                op = own; // the digit under one of its own primes is the input's c1 row, read through the same permutation
-            }
-            else
-            {
-                const uint32_t pos = row < lo ? row : row - nr;
-                op = g.ext + ((size_t)j * B * g.L + (size_t)b * (g.L - nr + g.alpha) + pos) * 2 * n2;
-            }
-            const size_t koff = ((size_t)j * 2 * g.k + prime) * n2 + x;
+            // the digit under one of its own primes is the input's c1 row, read through the same permutation
+            const uint64_t *op = hy_digit_operand(own, g.ext, 2 * n2, d.L, d.alpha, B, b, row, j);
+            const size_t koff = ((size_t)j * 2 * d.k + prime) * n2 + x;
             ulonglong2 o[NR], k0[NR], k1[NR];
 #pragma unroll
             for (int r = 0; r < NR; ++r)
@@ -279,7 +281,7 @@ __global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
                 const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[r]);
                 o[r] = make_ulonglong2(op[src[r].x], op[src[r].y]);
                 k0[r] = key[koff];
-                k1[r] = key[koff + (size_t)g.k * n2];
+                k1[r] = key[koff + (size_t)d.k * n2];
             }
 #pragma unroll
             for (int r = 0; r < NR; ++r)
@@ -306,73 +308,30 @@ __global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
     }
 }
 
-struct HyFinalArgs
-{
-    const uint64_t *acc;  // [2B][L + alpha][N]
-    const uint64_t *conv; // [2B][L][N], NTT form
-    uint64_t *out;        // [2B][L][N]
-    const Tw *pinv;
-    const PrimeConst *pc;
-    const uint64_t *addend; // polynomial p of ciphertext b at row b * addend_bstride + p * L
-    uint32_t addend_bstride;
-    int add_mode;           // 1: both polynomials get their addend, 2: polynomial 0 only
-    uint32_t L, alpha;
-    uint32_t n2;
-};
-
-// out = addend + (acc - conv) * P^-1 mod q_i; blockIdx.y = (b, p, i)
-__global__ __launch_bounds__(256) void hy_finalize_kernel(HyFinalArgs g)
-{
-    const uint32_t pp = blockIdx.y / g.L, i = blockIdx.y % g.L;
-    const uint64_t q = g.pc[i].q;
-    const Tw inv = g.pinv[i];
-    const size_t n2 = g.n2;
-    const ulonglong2 *a = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)pp * (g.L + g.alpha) + i) * n2;
-    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.conv) + (size_t)blockIdx.y * n2;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
-    const bool add = g.add_mode == 1 || !(pp & 1u);
-    const ulonglong2 *ad =
-        reinterpret_cast<const ulonglong2 *>(g.addend) + ((size_t)(pp >> 1) * g.addend_bstride + (size_t)(pp & 1u) * g.L + i) * n2;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
-    {
-        const ulonglong2 x = a[j], y = u[j];
-        ulonglong2 r;
-        r.x = csub(mul_shoup_lazy(x.x + q - y.x, inv.w, inv.wq, q), q);
-        r.y = csub(mul_shoup_lazy(x.y + q - y.y, inv.w, inv.wq, q), q);
-        if (add)
-        {
-            r = add2(r, ad[j], q);
-        }
-        o[j] = r;
-    }
-}
-
 struct HyKeyAddArgs
 {
     uint64_t *key;          // [beta][2][k][N]
     const uint64_t *newkey; // [k][N], rows < k - alpha read
-    const PrimeConst *pc;
     uint64_t fac[MOAI_MAX_RNS]; // P mod q_r
-    uint32_t alpha, k;
-    uint32_t n2;
+    HyDims d;                   // at L = k - alpha
 };
 
 // row r of c0 of digit r / alpha += (P mod q_r) * newkey[r]      (keygenerator.cpp:315-333 with P for the special prime)
 __global__ __launch_bounds__(256) void hy_key_add_kernel(HyKeyAddArgs g)
 {
     const uint32_t r = blockIdx.y;
-    const PrimeConst *pc = g.pc + r;
+    const PrimeConst *pc = g.d.pc + r;
     const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, fac = g.fac[r];
-    const size_t n2 = g.n2;
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(g.key) + ((size_t)(r / g.alpha) * 2 * g.k + r) * n2;
+    const size_t n2 = g.d.n2;
+    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(g.key) + ((size_t)(r / g.d.alpha) * 2 * g.d.k + r) * n2;
     const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(g.newkey) + (size_t)r * n2;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.d.n2; j += gridDim.x * 256u)
     {
         const ulonglong2 v = s[j];
-        ulonglong2 c = d[j];
+        ulonglong2 c = dst[j];
         c.x = csub(c.x + mulmod_barrett(v.x, fac, q, cr0, cr1), q);
         c.y = csub(c.y + mulmod_barrett(v.y, fac, q, cr0, cr1), q);
-        d[j] = c;
+        dst[j] = c;
     }
 }
 
@@ -382,15 +341,14 @@ static inline size_t hy_beta(size_t L, size_t alpha)
     return (L + alpha - 1) / alpha;
 }
 
-static inline size_t hy_align(size_t x)
+static HyDims hy_dims(const moai_ctx *c, size_t L, size_t alpha)
 {
-    return (x + 255) & ~(size_t)255;
-}
-
-static inline dim3 hy_grid(const moai_ctx *c, size_t rows)
-{
-    const uint32_t bx = (uint32_t)(((c->n >> 1) + 255) / 256);
-    return dim3(bx ? bx : 1, (uint32_t)rows);
+    HyDims d;
+    d.alpha = (uint32_t)alpha;
+    d.beta = (uint32_t)hy_beta(L, alpha);
+    d.k = (uint32_t)c->k;
+    fill_rows(d, c, L);
+    return d;
 }
 
 // product of the context primes idx[0..cnt) except idx[skip], modulo m
@@ -466,7 +424,7 @@ static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
             {
                 continue;
             }
-            const uint32_t prime = (uint32_t)(row < L ? row : k - alpha + (row - L));
+            const uint32_t prime = (uint32_t)hy_row_prime(row, L, alpha, k);
             const uint32_t tg = cv.ntgt++;
             cv.tgt_prime[tg] = prime;
             for (size_t r = 0; r < cv.nsrc; ++r)
@@ -504,7 +462,7 @@ static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
         const HyConv &cv = convs[j];
         for (size_t row = 0; row < L + alpha; ++row)
         {
-            const uint64_t m = c->primes[row < L ? row : k - alpha + (row - L)];
+            const uint64_t m = c->primes[hy_row_prime(row, L, alpha, k)];
             mult[j * (L + alpha) + row] = mulmod(cv.nsrc % m, hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, m), m);
         }
     }
@@ -532,15 +490,10 @@ static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_
     a.src_stride = (uint32_t)src_stride;
     a.src_off = (uint32_t)src_off;
     a.n2 = (uint32_t)(c->n >> 1);
-    MOAI_CHECK_GRID_ROWS(polys);
     // the smallest instantiation that holds the digit: its registers are the unrolled source rows
     const int amax = nsrc <= 1 ? 1 : nsrc <= 2 ? 2 : nsrc <= 4 ? 4 : nsrc <= 8 ? 8 : 16;
-    MOAI_TRY((dispatch<1, 2, 4, 8, 16>("digit size ", amax, [&](auto A) {
-        hipLaunchKernelGGL(hy_convert_kernel<decltype(A)::value>, hy_grid(c, polys), dim3(256), 0, s, a);
-        return MOAI_OK;
-    })));
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    return dispatch<1, 2, 4, 8, 16>("digit size ", amax,
+                                    [&](auto A) { return launch_rows(hy_convert_kernel<decltype(A)::value>, c, polys, s, a); });
 }
 
 // rows of N words of scratch per ciphertext: t, the converted digits, acc, the special rows, conv (and the permuted input of
@@ -561,12 +514,12 @@ static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, 
     const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
     HyLayout w;
     w.gal = 0;
-    w.t = w.gal + hy_align(galois ? cb * 2 * L * row : 0);
-    w.ext = w.t + hy_align(cb * L * row);
-    w.acc = w.ext + hy_align(cb * (beta * (L + alpha) - L) * row);
-    w.x = w.acc + hy_align(cb * 2 * (L + alpha) * row);
-    w.conv = w.x + hy_align(cb * 2 * alpha * row);
-    w.total = w.conv + hy_align(cb * 2 * L * row);
+    w.t = w.gal + align256(galois ? cb * 2 * L * row : 0);
+    w.ext = w.t + align256(cb * L * row);
+    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
+    w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
+    w.conv = w.x + align256(cb * 2 * alpha * row);
+    w.total = w.conv + align256(cb * 2 * L * row);
     return w;
 }
 
@@ -583,36 +536,24 @@ static size_t hy_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, 
     return cb < batch ? cb : batch;
 }
 
-static inline uint64_t *hy_at(void *base, size_t offset)
+// steps 1-3 for B ciphertexts: t [B][L][N] = INTT of the target rows tg, ext = the converted rows of every digit in NTT form
+// (HyMacArgs::ext)
+static int hy_decompose(moai_ctx *c, const HyTable *tab, const KsTarget &tg, size_t L, size_t alpha, size_t B, uint64_t *t, uint64_t *ext,
+                        hipStream_t s)
 {
-    return reinterpret_cast<uint64_t *>(static_cast<char *>(base) + offset);
-}
-
-// steps 1-3 for B ciphertexts: t [B][L][N] = INTT of the target rows (ciphertext b's row r at target row b * tgt_stride + tgt_off
-// + r), ext = the converted rows of every digit in NTT form (HyMacArgs::ext)
-static int hy_decompose(moai_ctx *c, const HyTable *tab, const uint64_t *target, size_t tgt_stride, size_t tgt_off, size_t L, size_t alpha,
-                        size_t B, uint64_t *t, uint64_t *ext, hipStream_t s)
-{
-    const size_t n = c->n, k = c->k, beta = hy_beta(L, alpha);
+    const size_t n = c->n, beta = hy_beta(L, alpha);
     const HyConv *cvs = tab->conv; // device address arithmetic only
     RowMap rm;
     // 1. t = INTT(target)
     MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
-    MOAI_TRY(ntt_launch(c, t, B, L, rm, true, s, target, tgt_stride, tgt_off));
-    // 2., 3. mod-up of every digit and the forward transform of the converted rows
+    MOAI_TRY(ntt_launch(c, t, B, L, rm, true, s, tg.ptr, tg.stride_rows, tg.off_rows));
+    // 2., 3. mod-up of every digit and the forward transform of the converted rows: all rows but the digit's own
     for (size_t j = 0; j < beta; ++j)
     {
-        const size_t lo = j * alpha, hi = std::min(lo + alpha, L), nr = hi - lo, cr = L - nr + alpha;
+        const size_t lo = j * alpha, hi = std::min(lo + alpha, L);
         uint64_t *ext_j = ext + j * B * L * n;
-        MOAI_TRY(hy_convert(c, t, L, lo, ext_j, cvs + j, nr, B, s));
-        size_t tg = 0;
-        for (size_t row = 0; row < L + alpha; ++row)
-        {
-            if (row < lo || row >= hi)
-            {
-                rm.idx[tg++] = (uint32_t)(row < L ? row : k - alpha + (row - L));
-            }
-        }
+        MOAI_TRY(hy_convert(c, t, L, lo, ext_j, cvs + j, hi - lo, B, s));
+        const size_t cr = hy_rowmap(c, L, alpha, lo, hi, &rm);
         MOAI_TRY(ntt_launch(c, ext_j, B, cr, rm, false, s));
     }
     return MOAI_OK;
@@ -623,72 +564,46 @@ static int hy_decompose(moai_ctx *c, const HyTable *tab, const uint64_t *target,
 static int hy_mod_down(moai_ctx *c, const HyTable *tab, const uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
                        hipStream_t s)
 {
-    const size_t k = c->k, beta = hy_beta(L, alpha);
     RowMap rm{};
-    for (size_t r = 0; r < alpha; ++r)
-    {
-        rm.idx[r] = (uint32_t)(k - alpha + r);
-    }
+    hy_rowmap(c, L, alpha, 0, L, &rm); // the special rows
     MOAI_TRY(ntt_launch(c, x, 2 * B, alpha, rm, true, s, acc, L + alpha, L));
-    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + beta, alpha, 2 * B, s));
+    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + hy_beta(L, alpha), alpha, 2 * B, s));
     MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
     return ntt_launch(c, conv, 2 * B, L, rm, false, s);
 }
 
-// the last kernel of step 5: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + (acc - conv) / P
-static int hy_finalize(moai_ctx *c, const HyTable *tab, const uint64_t *acc, const uint64_t *conv, uint64_t *out, size_t L, size_t alpha,
-                       size_t B, const uint64_t *addend, size_t addend_bstride, int add_mode, hipStream_t s)
+// the hy_mac_kernel / hy_hoisted_mac_kernel grid: blockIdx.x = ciphertext, .y covers a row, .z = row of L + alpha
+static int hy_mac_grid(const moai_ctx *c, size_t B, size_t rows, dim3 *grid)
 {
-    const size_t n = c->n;
-    HyFinalArgs f;
-    f.acc = acc;
-    f.conv = conv;
-    f.out = out;
-    f.pinv = tab->pinv;
-    f.pc = c->pc;
-    f.addend = addend;
-    f.addend_bstride = (uint32_t)addend_bstride;
-    f.add_mode = add_mode;
-    f.L = (uint32_t)L;
-    f.alpha = (uint32_t)alpha;
-    f.n2 = (uint32_t)(n >> 1);
-    MOAI_CHECK_GRID_ROWS(2 * B * L);
-    hipLaunchKernelGGL(hy_finalize_kernel, hy_grid(c, 2 * B * L), dim3(256), 0, s, f);
-    MOAI_LAUNCH_CHECK();
+    MOAI_CHECK_GRID_ROWS(rows);
+    *grid = dim3((uint32_t)B, row_grid(c, 1).x, (uint32_t)rows);
     return MOAI_OK;
 }
 
-// one chunk of B ciphertexts: out [B][2][L][N] = addend (add_mode, HyFinalArgs) + the switch of the target rows
-// (ciphertext b's row r at target row b * tgt_stride + tgt_off + r)
-static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const uint64_t *target, size_t tgt_stride, size_t tgt_off,
-                           const uint64_t *key, size_t L, size_t alpha, size_t B, void *wsp, const HyLayout &w, const uint64_t *addend,
-                           size_t addend_bstride, int add_mode, hipStream_t s)
+// one chunk of B ciphertexts: out [B][2][L][N] = add (KsAddend) + the switch of the target rows tg
+static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
+                           size_t B, void *wsp, const HyLayout &w, const KsAddend &add, hipStream_t s)
 {
-    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
+    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
+    uint64_t *conv = at_bytes(wsp, w.conv);
     // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
-    MOAI_TRY(hy_decompose(c, tab, target, tgt_stride, tgt_off, L, alpha, B, t, ext, s));
+    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, t, ext, s));
     // 4. the inner products with the key
-    {
-        HyMacArgs m;
-        m.ext = ext;
-        m.tgt = target;
-        m.key = key;
-        m.acc = acc;
-        m.pc = c->pc;
-        m.tgt_stride = (uint32_t)tgt_stride;
-        m.tgt_off = (uint32_t)tgt_off;
-        m.L = (uint32_t)L;
-        m.alpha = (uint32_t)alpha;
-        m.beta = (uint32_t)hy_beta(L, alpha);
-        m.k = (uint32_t)c->k;
-        m.n2 = (uint32_t)(c->n >> 1);
-        const dim3 g1 = hy_grid(c, 1);
-        hipLaunchKernelGGL(hy_mac_kernel, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
-        MOAI_LAUNCH_CHECK();
-    }
+    HyMacArgs m;
+    m.ext = ext;
+    m.tgt = tg.ptr;
+    m.key = key;
+    m.acc = acc;
+    m.tgt_stride = (uint32_t)tg.stride_rows;
+    m.tgt_off = (uint32_t)tg.off_rows;
+    m.d = hy_dims(c, L, alpha);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
+    MOAI_LAUNCH_CHECK();
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
     MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, B, s));
-    return hy_finalize(c, tab, acc, conv, out, L, alpha, B, addend, addend_bstride, add_mode, s);
+    return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, nullptr, s);
 }
 
 // what every hybrid entry point refuses, in the order the header gives: first what needs no context
@@ -735,15 +650,10 @@ enum
 static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, const uint64_t *key, size_t L, size_t alpha, uint32_t elt,
                     size_t batch, void *stream)
 {
-    if (kind == HY_GALOIS && !(elt & 1u))
-    {
-        return set_error(MOAI_EINVAL, "Galois element is not valid");
-    }
+    // every kind but HY_GALOIS comes with element 1; an even element is refused before the context is looked at
+    MOAI_TRY(galois_elt_check(nullptr, elt));
     MOAI_TRY(hy_check(c, alpha, L, true));
-    if (kind == HY_GALOIS && elt >= 2 * c->n)
-    {
-        return set_error(MOAI_EINVAL, "Galois element is not valid");
-    }
+    MOAI_TRY(galois_elt_check(c, elt));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -772,18 +682,18 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
         {
         case HY_SWITCH:
             // ct += switch(target)
-            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, in + b0 * L * n, L, 0, key, L, alpha, B, wsp, w, io + b0 * 2 * L * n, 2 * L, 1,
-                                   s);
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { in + b0 * L * n, L, 0 }, key, L, alpha, B, wsp, w,
+                                   { io + b0 * 2 * L * n, 2 * L, 1 }, s);
         case HY_RELIN:
             // out = (c0, c1) + switch(c2)      (evaluator.cpp:1383-1392)
-            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, in + b0 * 3 * L * n, 3 * L, 2 * L, key, L, alpha, B, wsp, w,
-                                   in + b0 * 3 * L * n, 3 * L, 1, s);
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { in + b0 * 3 * L * n, 3 * L, 2 * L }, key, L, alpha, B, wsp, w,
+                                   { in + b0 * 3 * L * n, 3 * L, 1 }, s);
         default:
         {
             // ct = (galois(c0), 0) + switch(galois(c1))      (evaluator.cpp:2631-2654)
-            uint64_t *tmp = hy_at(wsp, w.gal);
+            uint64_t *tmp = at_bytes(wsp, w.gal);
             MOAI_TRY(moai_galois_permute(c, io + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
-            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, tmp, 2 * L, L, key, L, alpha, B, wsp, w, tmp, 2 * L, 2, s);
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { tmp, 2 * L, L }, key, L, alpha, B, wsp, w, { tmp, 2 * L, 2 }, s);
         }
         }
     });
@@ -813,12 +723,12 @@ static HyHoistLayout hy_hoist_layout(const moai_ctx *c, size_t L, size_t alpha, 
     HyHoistLayout w;
     w.flag = 0;
     w.t = 256;
-    w.ext = w.t + hy_align(cb * L * row);
-    w.acc = w.ext + hy_align(cb * (beta * (L + alpha) - L) * row);
-    w.x = w.acc + hy_align(G * cb * 2 * (L + alpha) * row);
-    w.conv = w.x + hy_align(G * cb * 2 * alpha * row);
-    w.c0 = w.conv + hy_align(G * cb * 2 * L * row);
-    w.total = w.c0 + hy_align(G * cb * L * row);
+    w.ext = w.t + align256(cb * L * row);
+    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
+    w.x = w.acc + align256(G * cb * 2 * (L + alpha) * row);
+    w.conv = w.x + align256(G * cb * 2 * alpha * row);
+    w.c0 = w.conv + align256(G * cb * 2 * L * row);
+    w.total = w.c0 + align256(G * cb * L * row);
     return w;
 }
 
@@ -848,30 +758,20 @@ static int hy_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t elt, s
     const HyTable *tab;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
     void *wsp;
-    MOAI_TRY(workspace(c, hy_align(rows * c->n * sizeof(uint64_t)), s, &wsp));
+    MOAI_TRY(workspace(c, align256(rows * c->n * sizeof(uint64_t)), s, &wsp));
     uint64_t *mask = static_cast<uint64_t *>(wsp);
     // the sign mask under every row's prime, then its forward transform
     MOAI_TRY(galois_sign_mask(c, mask, elt, rows, s));
     RowMap rm{};
-    for (size_t row = 0; row < rows; ++row)
-    {
-        rm.idx[row] = (uint32_t)(row < L ? row : c->k - alpha + (row - L));
-    }
+    hy_rowmap(c, L, alpha, 0, 0, &rm);
     MOAI_TRY(ntt_launch(c, mask, 1, rows, rm, false, s));
     HyCorrArgs g;
     g.key = key;
     g.mask = mask;
     g.mult = hy_hoist_mult(tab, beta);
     g.out = correction;
-    g.pc = c->pc;
-    g.L = (uint32_t)L;
-    g.alpha = (uint32_t)alpha;
-    g.beta = (uint32_t)beta;
-    g.k = (uint32_t)c->k;
-    g.n2 = (uint32_t)(c->n >> 1);
-    hipLaunchKernelGGL(hy_hoist_correction_kernel, hy_grid(c, 2 * rows), dim3(256), 0, s, g);
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    g.d = hy_dims(c, L, alpha);
+    return launch_rows(hy_hoist_correction_kernel, c, 2 * rows, s, g);
 }
 
 struct HyHoistRotations
@@ -889,7 +789,8 @@ static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, 
                           uint64_t *acc, size_t L, size_t alpha, size_t B, hipStream_t s)
 {
     const long per_pass = tuning(K_HYBRID_HOIST_NR);
-    const dim3 g1 = hy_grid(c, 1);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
     for (size_t r = 0; r < g;)
     {
         const size_t nr = per_pass >= 4 && r + 3 < g ? 4 : (per_pass >= 2 && r + 1 < g ? 2 : 1);
@@ -904,14 +805,9 @@ static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, 
             m.corr[h] = rot.corrs[r0 + rr];
             m.acc[h] = acc + rr * B * 2 * (L + alpha) * c->n;
         }
-        m.pc = c->pc;
-        m.L = (uint32_t)L;
-        m.alpha = (uint32_t)alpha;
-        m.beta = (uint32_t)hy_beta(L, alpha);
-        m.k = (uint32_t)c->k;
-        m.n2 = (uint32_t)(c->n >> 1);
+        m.d = hy_dims(c, L, alpha);
         MOAI_TRY((dispatch<1, 2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
-            hipLaunchKernelGGL(hy_hoisted_mac_kernel<decltype(NR)::value>, dim3((uint32_t)B, g1.x, (uint32_t)(L + alpha)), dim3(256), 0, s, m);
+            hipLaunchKernelGGL(hy_hoisted_mac_kernel<decltype(NR)::value>, grid, dim3(256), 0, s, m);
             return MOAI_OK;
         })));
         MOAI_LAUNCH_CHECK();
@@ -932,17 +828,12 @@ static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, c
     const HyHoistLayout w = hy_hoist_layout(c, L, alpha, cb, G);
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
-    uint32_t *flag = reinterpret_cast<uint32_t *>(hy_at(wsp, w.flag));
-    uint64_t *t = hy_at(wsp, w.t), *ext = hy_at(wsp, w.ext), *acc = hy_at(wsp, w.acc), *x = hy_at(wsp, w.x), *conv = hy_at(wsp, w.conv);
-    uint64_t *pc0 = hy_at(wsp, w.c0);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
+    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
+    uint64_t *conv = at_bytes(wsp, w.conv), *pc0 = at_bytes(wsp, w.c0);
     // steps 1-3 on the UNPERMUTED c1, once for all rotations
-    MOAI_TRY(hy_decompose(c, tab, in, 2 * L, L, L, alpha, B, t, ext, s));
-    MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
-    MOAI_TRY(any_zero(t, B * L * n, flag, s));
-    uint32_t host_flag = 0;
-    MOAI_HIP_CHECK(hipMemcpyAsync(&host_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    MOAI_HIP_CHECK(hipStreamSynchronize(s));
-    *fallback = host_flag != 0; // a zero coefficient: the identity does not hold for it
+    MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, t, ext, s));
+    MOAI_TRY(probe_any_zero(c, t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
     if (*fallback)
     {
         return MOAI_OK;
@@ -958,8 +849,8 @@ static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, c
         MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, g * B, s));
         for (size_t r = 0; r < g; ++r)
         {
-            MOAI_TRY(hy_finalize(c, tab, acc + r * B * 2 * (L + alpha) * n, conv + r * B * 2 * L * n, rot.outs[r0 + r] + out_off, L, alpha, B,
-                                 pc0 + r * B * L * n, L, 2, s));
+            MOAI_TRY(moddown_finalize(c, acc + r * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + r * B * 2 * L * n,
+                                      rot.outs[r0 + r] + out_off, 2 * B, L, tab->pinv, { pc0 + r * B * L * n, L, 2 }, nullptr, s));
         }
         return MOAI_OK;
     });
@@ -998,10 +889,7 @@ extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq,
     HyKeyAddArgs a;
     a.key = out;
     a.newkey = new_key_ntt;
-    a.pc = c->pc;
-    a.alpha = (uint32_t)alpha;
-    a.k = (uint32_t)k;
-    a.n2 = (uint32_t)(c->n >> 1);
+    a.d = hy_dims(c, Lmax, alpha);
     uint32_t special[HY_MAX_ALPHA];
     for (size_t s = 0; s < alpha; ++s)
     {
@@ -1011,9 +899,7 @@ extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq,
     {
         a.fac[r] = r < Lmax ? hy_prod_mod(c, special, alpha, alpha, c->primes[r]) : 0;
     }
-    hipLaunchKernelGGL(hy_key_add_kernel, hy_grid(c, Lmax), dim3(256), 0, (hipStream_t)stream, a);
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    return launch_rows(hy_key_add_kernel, c, Lmax, stream, a);
 }
 
 extern "C" int moai_switch_key_hybrid(moai_ctx *c, uint64_t *ct, const uint64_t *target, const uint64_t *key, size_t L, size_t alpha,
@@ -1045,15 +931,9 @@ extern "C" int moai_hybrid_hoist_correction(moai_ctx *c, const uint64_t *key, ui
 {
     MOAI_AUDIT(stream, key, correction);
     trace_op("hybrid_hoist_correction", L, 1);
-    if (!(galois_elt & 1u))
-    {
-        return set_error(MOAI_EINVAL, "Galois element is not valid");
-    }
+    MOAI_TRY(galois_elt_check(nullptr, galois_elt)); // oddness first: it needs no context
     MOAI_TRY(hy_check(c, alpha, L, true));
-    if (galois_elt >= 2 * c->n)
-    {
-        return set_error(MOAI_EINVAL, "Galois element is not valid");
-    }
+    MOAI_TRY(galois_elt_check(c, galois_elt));
     if (!key || !correction)
     {
         return set_error(MOAI_EINVAL, "null argument");
@@ -1092,10 +972,7 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
         {
             return set_error(MOAI_EINVAL, "null key, correction or output");
         }
-        if (!(galois_elts[r] & 1u) || galois_elts[r] >= 2 * n)
-        {
-            return set_error(MOAI_EINVAL, "Galois element is not valid");
-        }
+        MOAI_TRY(galois_elt_check(c, galois_elts[r]));
         if (overlap(outs[r], ct_bytes, in, ct_bytes))
         {
             return set_error(MOAI_EINVAL, "an output must not alias the input");

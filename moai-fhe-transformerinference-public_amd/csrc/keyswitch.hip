@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "hostmath.h"
 #include "launch.h"
 #include <vector>
 
@@ -130,50 +131,48 @@ struct FinalizeListArgs : FinalizeArgs
 template <bool LIST = false>
 __global__ __launch_bounds__(256) void moddown_finalize_kernel(std::conditional_t<LIST, FinalizeListArgs, FinalizeArgs> g)
 {
-    const uint32_t p = blockIdx.y / g.Lout;
-    const uint32_t i = blockIdx.y % g.Lout;
+    const uint32_t p = blockIdx.y / g.Lout, i = blockIdx.y % g.Lout;
     const uint64_t q = g.pc[i].q;
     const Tw inv = g.inv_last[i];
-    const ulonglong2 *a = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)p * g.acc_stride + i) * g.n2;
-    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.u) + (size_t)blockIdx.y * g.n2;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * g.n2;
-    const ulonglong2 *add = nullptr, *add2 = nullptr;
+    const size_t n2 = g.n2;
+    const ulonglong2 *a = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)p * g.acc_stride + i) * n2;
+    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.u) + (size_t)blockIdx.y * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
+    const size_t row = ((size_t)(p & 1u) * g.Lout + i) * n2; // inside a ciphertext's [2][Lout][N]
+    const ulonglong2 *ad = nullptr, *ad2 = nullptr;          // null: nothing to add (uniform over the workgroup)
+    if (g.add_mode == 1 || (g.add_mode == 2 && !(p & 1u)))
+    {
+        ad = reinterpret_cast<const ulonglong2 *>(g.addend) + (size_t)(p >> 1) * g.addend_bstride * n2 + row;
+    }
     if constexpr (LIST)
     {
-        const size_t row = ((size_t)(p & 1u) * g.Lout + i) * g.n2; // inside the member's [2][Lout][N]
         o = reinterpret_cast<ulonglong2 *>(g.lst->outs[p >> 1]) + row;
         if (g.lst->sums[p >> 1])
         {
-            add2 = reinterpret_cast<const ulonglong2 *>(g.lst->sums[p >> 1]) + row;
+            ad2 = reinterpret_cast<const ulonglong2 *>(g.lst->sums[p >> 1]) + row;
         }
         if (g.add_mode == 1)
         {
-            add = reinterpret_cast<const ulonglong2 *>(g.lst->ins[p >> 1]) + row;
+            ad = reinterpret_cast<const ulonglong2 *>(g.lst->ins[p >> 1]) + row;
         }
+    }
+    else if (g.addend2)
+    {
+        ad2 = reinterpret_cast<const ulonglong2 *>(g.addend2) + (size_t)blockIdx.y * n2;
     }
     for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
     {
-        ulonglong2 x = a[j], y = u[j], r;
+        const ulonglong2 x = a[j], y = u[j];
+        ulonglong2 r;
         r.x = csub(mul_shoup_lazy(x.x + q - y.x, inv.w, inv.wq, q), q);
         r.y = csub(mul_shoup_lazy(x.y + q - y.y, inv.w, inv.wq, q), q);
-        if (LIST && add)
+        if (ad)
         {
-            ulonglong2 c = add[j];
-            r.x = csub(r.x + c.x, q);
-            r.y = csub(r.y + c.y, q);
+            r = add2(r, ad[j], q);
         }
-        else if (g.add_mode == 1 || (g.add_mode == 2 && !(p & 1u)))
+        if (ad2)
         {
-            ulonglong2 c = (reinterpret_cast<const ulonglong2 *>(g.addend) +
-                            ((size_t)(p >> 1) * g.addend_bstride + (size_t)(p & 1u) * g.Lout + i) * g.n2)[j];
-            r.x = csub(r.x + c.x, q);
-            r.y = csub(r.y + c.y, q);
-        }
-        if (LIST ? add2 != nullptr : g.addend2 != nullptr)
-        {
-            ulonglong2 c = LIST ? add2[j] : (reinterpret_cast<const ulonglong2 *>(g.addend2) + (size_t)blockIdx.y * g.n2)[j];
-            r.x = csub(r.x + c.x, q);
-            r.y = csub(r.y + c.y, q);
+            r = add2(r, ad2[j], q);
         }
         o[j] = r;
     }
@@ -295,18 +294,6 @@ __global__ __launch_bounds__(256) void modraise_kernel(RaiseArgs g)
     }
 }
 
-static inline dim3 rgrid(const moai_ctx *c, size_t rows)
-{
-    uint32_t n2 = (uint32_t)(c->n >> 1);
-    uint32_t bx = (n2 + 255u) / 256u;
-    return dim3(bx ? bx : 1, (uint32_t)rows);
-}
-
-static inline size_t align256(size_t x)
-{
-    return (x + 255) & ~(size_t)255;
-}
-
 // f(LOGN, MODE) over the degrees and arithmetic modes that the key-switch and mod-down kernels are compiled for
 template <class F>
 static int dispatch_ks(int logn, int mode, F &&f)
@@ -328,15 +315,14 @@ static bool md_allow_fp(size_t rows)
 // whose NTT-form row is `last_rows` ([P][N], overwritten), rounding to nearest.
 //   acc row (p, i) = acc + (p * acc_stride + i) * N ; out [P][Lout][N]
 // scratch: u [P][Lout][N]
-//   addend / addend_bstride / add_mode: what is added to the quotient (ModDownArgs); add_mode 0 for rescale
-//   addend2: a second summand with the output's layout (may be `out`), or null
-//   lst (device memory, key switch only): polynomials 2b and 2b + 1 go to lst->outs[b] plus lst->sums[b], and add_mode 1 reads
-//   lst->ins[b]; out and addend2 are null then (the LIST kernels)
-static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32_t acc_stride, uint64_t *u,
-                   uint64_t *out, size_t P, size_t Lout, uint32_t prime_last, const uint64_t *addend, uint32_t addend_bstride,
-                   int add_mode, hipStream_t s, uint32_t acc_splits = 1, size_t acc_split_stride = 0, const Tw *scal = nullptr,
-                   const uint64_t *addend2 = nullptr, const KsList *lst = nullptr)
+//   add: what is added to the quotient (KsAddend); nothing for a plain rescale
+//   lst (device memory, key switch only): polynomials 2b and 2b + 1 go to lst->outs[b] plus lst->sums[b], and add.mode 1 reads
+//   lst->ins[b]; out and add.second are null then (the LIST kernels)
+static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32_t acc_stride, uint64_t *u, uint64_t *out, size_t P,
+                   size_t Lout, uint32_t prime_last, const KsAddend &add, hipStream_t s, uint32_t acc_splits = 1,
+                   size_t acc_split_stride = 0, const Tw *scal = nullptr, const KsList *lst = nullptr)
 {
+    const Tw *inv_last = c->inv_qlast + (size_t)prime_last * c->k;
     RowMap rm;
     uint32_t pl = prime_last;
     MOAI_TRY(make_rowmap(c, 1, &pl, &rm));
@@ -350,15 +336,15 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
         a.acc = acc;
         a.out = out;
         a.pc = c->pc;
-        a.inv_last = c->inv_qlast + (size_t)prime_last * c->k;
+        a.inv_last = inv_last;
         a.prime_last = prime_last;
         a.acc_stride = acc_stride;
         a.Lout = (uint32_t)Lout;
         a.P = (uint32_t)P;
-        a.addend = addend;
-        a.addend2 = addend2;
-        a.addend_bstride = addend_bstride;
-        a.add_mode = add_mode;
+        a.addend = add.ptr;
+        a.addend2 = add.second;
+        a.addend_bstride = (uint32_t)add.bstride;
+        a.add_mode = add.mode;
         a.has_scal = scal ? 1 : 0;
         if (scal)
         {
@@ -391,18 +377,11 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
             a.twb = t.twb;
             MOAI_TRY(dispatch_ks(c->logn, mode, [&](auto LG, auto MD) {
                 hipLaunchKernelGGL((moddown_strided<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
-                if (lst)
-                {
-                    ModDownListArgs al;
-                    static_cast<ModDownArgs &>(al) = a;
-                    al.lst = lst;
-                    hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value, true>), dim3(a.total_work), dim3(256), 0, s, al);
-                }
-                else
-                {
-                    hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value>), dim3(a.total_work), dim3(256), 0, s, a);
-                }
-                return MOAI_OK;
+                return plain_or_list<ModDownListArgs>(a, lst, [&](const auto &args, auto LIST) {
+                    hipLaunchKernelGGL((moddown_contig<decltype(LG)::value, decltype(MD)::value, decltype(LIST)::value>), dim3(a.total_work),
+                                       dim3(256), 0, s, args);
+                    return MOAI_OK;
+                });
             }));
         }
         MOAI_LAUNCH_CHECK();
@@ -419,38 +398,32 @@ static int moddown(moai_ctx *c, uint64_t *last_rows, const uint64_t *acc, uint32
     e.prime_last = prime_last;
     e.Lout = (uint32_t)Lout;
     e.n2 = (uint32_t)(c->n >> 1);
-    MOAI_CHECK_GRID_ROWS(P * Lout);
-    hipLaunchKernelGGL(expand_last_kernel, rgrid(c, P * Lout), dim3(256), 0, s, e);
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY(launch_rows(expand_last_kernel, c, P * Lout, s, e));
     MOAI_TRY(make_rowmap(c, Lout, nullptr, &rm));
     MOAI_TRY(ntt_launch(c, u, P, Lout, rm, false, s));
+    return moddown_finalize(c, acc, acc_stride, u, out, P, Lout, inv_last, add, lst, s);
+}
+
+// the last kernel of the unfused mod-down (launch.h): the tail above and the hybrid key switch's base conversion (hybrid.hip)
+int moddown_finalize(moai_ctx *c, const uint64_t *acc, uint32_t acc_stride, const uint64_t *u, uint64_t *out, size_t P, size_t Lout,
+                     const Tw *inv, const KsAddend &add, const KsList *lst, hipStream_t s)
+{
     FinalizeArgs f;
     f.acc = acc;
     f.u = u;
     f.out = out;
     f.pc = c->pc;
-    f.inv_last = c->inv_qlast + (size_t)prime_last * c->k;
+    f.inv_last = inv;
     f.acc_stride = acc_stride;
     f.Lout = (uint32_t)Lout;
     f.n2 = (uint32_t)(c->n >> 1);
-    f.addend = addend;
-    f.addend2 = addend2;
-    f.addend_bstride = addend_bstride;
-    f.add_mode = add_mode;
-    MOAI_CHECK_GRID_ROWS(P * Lout);
-    if (lst)
-    {
-        FinalizeListArgs fl;
-        static_cast<FinalizeArgs &>(fl) = f;
-        fl.lst = lst;
-        hipLaunchKernelGGL(moddown_finalize_kernel<true>, rgrid(c, P * Lout), dim3(256), 0, s, fl);
-    }
-    else
-    {
-        hipLaunchKernelGGL(moddown_finalize_kernel<false>, rgrid(c, P * Lout), dim3(256), 0, s, f);
-    }
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    f.addend = add.ptr;
+    f.addend2 = add.second;
+    f.addend_bstride = (uint32_t)add.bstride;
+    f.add_mode = add.mode;
+    return plain_or_list<FinalizeListArgs>(f, lst, [&](const auto &args, auto LIST) {
+        return launch_rows(moddown_finalize_kernel<decltype(LIST)::value>, c, P * Lout, s, args);
+    });
 }
 
 static int check_level(const moai_ctx *c, size_t L, size_t polys)
@@ -470,13 +443,19 @@ static int check_level(const moai_ctx *c, size_t L, size_t polys)
     return enter_device(c);
 }
 
-struct KsTarget
+// what a key switch at L data primes needs of the context: a special prime, and L of the other k - 1
+static int check_switch_level(const moai_ctx *c, size_t L)
 {
-    const uint64_t *ptr; // NTT-form target rows
-    uint32_t stride_rows, off_rows;
-    uint32_t key_rows;   // rows per key polynomial in the key's layout (key_rows_for)
-    const KsList *lst;   // or null: every ciphertext its own key and layout (device memory; key and key_rows unused)
-};
+    if (c->k < 2)
+    {
+        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
+    }
+    if (L > c->k - 1)
+    {
+        return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
+    }
+    return MOAI_OK;
+}
 
 // rows per key polynomial of `key` (k for the reference's layout, levels + 1 for a key moai_key_trim produced), after checking
 // that the key holds what a switch at L data primes reads: digits J < L and rows {0 .. L-1, special} (SEAL/evaluator.cpp:2818,2831)
@@ -591,11 +570,6 @@ static size_t switch_key_ws_bytes(const moai_ctx *c, size_t L, size_t batch)
     return ks_layout(c, L, batch).total;
 }
 
-static inline uint64_t *at_bytes(void *base, size_t offset)
-{
-    return reinterpret_cast<uint64_t *>(static_cast<char *>(base) + offset);
-}
-
 // which arithmetic the fused kernels use for output modulus `prime` (keyswitch_kernels.hip.h): the forward
 // transform's mode, with the integer no-guard form only when the lazy digit may also enter the MAC unreduced
 static int ks_mode(const moai_ctx *c, uint32_t prime, size_t L, bool allow_fp)
@@ -702,8 +676,8 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
     KsP2Args p2;
     p2.tmp = tmp;
     p2.tgt = tg.ptr;
-    p2.tgt_stride = tg.stride_rows;
-    p2.tgt_off = tg.off_rows;
+    p2.tgt_stride = (uint32_t)tg.stride_rows;
+    p2.tgt_off = (uint32_t)tg.off_rows;
     p2.key = key;
     p2.acc = acc;
     p2.tw = p1.tw;
@@ -721,66 +695,31 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
     // where the MAC fetches its key residues (keyswitch_kernels.hip.h): all eight loads at the head of the MAC by default --
     // same box, same hour, l = 35 / 15, batch 64: 0.572 / 0.134 ms per ciphertext with the compiler's placement (0), 0.532 / 0.121
     // with 1, 0.547 / 0.124 with 2 (profiles/r03_b_ks_kernel_variants_ab.txt)
+    // The integer modes have the PF = 0 kernels only; a value other than 1 or 2 is 0.
     const long pf = MODE >= M_FPN ? tuning(K_KS_MAC_PF) : 0;
-    if (tg.lst)
-    {
-        // every ciphertext its own key: the same three placements
-        KsP2ListArgs pl;
-        static_cast<KsP2Args &>(pl) = p2;
-        pl.lst = tg.lst;
-        if (pf == 1)
-        {
-            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 1 : 0), true>), dim3(p2.total_work), dim3(256), 0, s, pl);
-        }
-        else if (pf == 2)
-        {
-            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 2 : 0), true>), dim3(p2.total_work), dim3(256), 0, s, pl);
-        }
-        else
-        {
-            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, 0, true>), dim3(p2.total_work), dim3(256), 0, s, pl);
-        }
-    }
-    else if (pf == 1)
-    {
-        hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 1 : 0)>), dim3(p2.total_work), dim3(256), 0, s, p2);
-    }
-    else if (pf == 2)
-    {
-        hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? 2 : 0)>), dim3(p2.total_work), dim3(256), 0, s, p2);
-    }
-    else
-    {
-        hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE>), dim3(p2.total_work), dim3(256), 0, s, p2);
-    }
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    return dispatch<0, 1, 2>("key residue placement ", pf == 1 || pf == 2 ? (int)pf : 0, [&](auto PF) {
+        return plain_or_list<KsP2ListArgs>(p2, tg.lst, [&](const auto &args, auto LIST) {
+            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? decltype(PF)::value : 0), decltype(LIST)::value>),
+                               dim3(p2.total_work), dim3(256), 0, s, args);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        });
+    });
 }
 
-// target row block of ciphertext b starts at target + (b * target_stride_rows + target_off_rows) * N.
 // wsp: switch_key_ws_bytes() bytes of scratch.
-// ct [batch][2][L][N] = addend (add_mode, ModDownArgs) + key switch of `target`; ct may be the addend itself
-// lst (device memory; its keys validated by the caller): ciphertext b is switched with lst->keys[b] and its result goes to
-// lst->outs[b] (+ lst->sums[b]); ct, key and addend2 are null then, and add_mode 1 adds lst->ins[b] (moddown)
-static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, size_t target_stride_rows,
-                           size_t target_off_rows, const uint64_t *key, size_t L, size_t batch, void *wsp,
-                           hipStream_t s, const uint64_t *addend, size_t addend_bstride, int add_mode, const uint64_t *addend2 = nullptr,
-                           const KsList *lst = nullptr)
+// ct [batch][2][L][N] = add (KsAddend) + key switch of the target rows tg; ct may be the addend itself
+// tg.lst (device memory; its keys validated by the caller): ciphertext b is switched with lst->keys[b] and its result goes to
+// lst->outs[b] (+ lst->sums[b]); ct, key and add.second are null then, and add.mode 1 adds lst->ins[b] (moddown)
+static int switch_key_impl(moai_ctx *c, uint64_t *ct, KsTarget tg, const uint64_t *key, size_t L, size_t batch, void *wsp, hipStream_t s,
+                           const KsAddend &add)
 {
     const size_t n = c->n;
     const size_t k = c->k;
-    if (k < 2)
+    MOAI_TRY(check_switch_level(c, L));
+    if (!tg.lst)
     {
-        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
-    }
-    if (L > k - 1)
-    {
-        return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
-    }
-    uint32_t key_rows = 0;
-    if (!lst)
-    {
-        MOAI_TRY(key_rows_for(c, key, L, &key_rows));
+        MOAI_TRY(key_rows_for(c, key, L, &tg.key_rows));
     }
     const KsLayout w = ks_layout(c, L, batch);
     uint64_t *t = at_bytes(wsp, w.t), *ops = at_bytes(wsp, w.ops), *acc = at_bytes(wsp, w.acc), *last = at_bytes(wsp, w.last);
@@ -789,7 +728,7 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
     // 1. t = INTT(target)      (evaluator.cpp:2804-2812)
     RowMap rm;
     MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
-    MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, target, target_stride_rows, target_off_rows));
+    MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, tg.ptr, tg.stride_rows, tg.off_rows));
     // 2. inner products per output modulus    (evaluator.cpp:2817-2911)
     if (c->logn >= 12)
     {
@@ -798,12 +737,6 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
         {
             return set_error(MOAI_EINVAL, "batch too large for one launch");
         }
-        KsTarget tg;
-        tg.ptr = target;
-        tg.stride_rows = (uint32_t)target_stride_rows;
-        tg.off_rows = (uint32_t)target_off_rows;
-        tg.key_rows = key_rows;
-        tg.lst = lst;
         for (const KsPlanGroup &pg : ks_plan(c, L, batch))
         {
             MOAI_TRY(dispatch_ks(c->logn, pg.mode, [&](auto LG, auto MD) {
@@ -817,9 +750,7 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
         for (size_t Iidx = 0; Iidx <= L; ++Iidx)
         {
             const uint32_t prime = (uint32_t)(Iidx == L ? k - 1 : Iidx);
-            MOAI_CHECK_GRID_ROWS(batch * L);
-            hipLaunchKernelGGL(reduce_rows_kernel, rgrid(c, batch * L), dim3(256), 0, s, t, ops, c->pc, prime, n2);
-            MOAI_LAUNCH_CHECK();
+            MOAI_TRY(launch_rows(reduce_rows_kernel, c, batch * L, s, t, ops, c->pc, prime, n2));
             for (size_t r = 0; r < L; ++r)
             {
                 rm.idx[r] = (uint32_t)prime;
@@ -831,33 +762,21 @@ static int switch_key_impl(moai_ctx *c, uint64_t *ct, const uint64_t *target, si
             m.acc = acc;
             m.pc = c->pc;
             m.L = (uint32_t)L;
-            m.k = key_rows;
-            m.krow = Iidx == L ? key_rows - 1 : prime;
+            m.k = tg.key_rows;
+            m.krow = Iidx == L ? tg.key_rows - 1 : prime;
             m.prime = prime;
             m.slot = (uint32_t)Iidx;
             m.n2 = n2;
-            MOAI_CHECK_GRID_ROWS(batch);
-            if (lst)
-            {
-                MacListArgs ml;
-                static_cast<MacArgs &>(ml) = m;
-                ml.lst = lst;
-                hipLaunchKernelGGL(keyswitch_mac_kernel<true>, rgrid(c, batch), dim3(256), 0, s, ml);
-            }
-            else
-            {
-                hipLaunchKernelGGL(keyswitch_mac_kernel<false>, rgrid(c, batch), dim3(256), 0, s, m);
-            }
-            MOAI_LAUNCH_CHECK();
+            MOAI_TRY(plain_or_list<MacListArgs>(m, tg.lst, [&](const auto &args, auto LIST) {
+                return launch_rows(keyswitch_mac_kernel<decltype(LIST)::value>, c, batch, s, args);
+            }));
         }
     }
     // 3. mod-down by the special prime, accumulated into ct   (evaluator.cpp:2913-3018)
-    MOAI_CHECK_GRID_ROWS(batch * 2);
-    hipLaunchKernelGGL(sum_rows_kernel, rgrid(c, batch * 2), dim3(256), 0, s, acc, last, (uint32_t)(L + 1), (uint32_t)L, w.splits,
-                       w.split_stride, c->pc, (uint32_t)(k - 1), n2);
-    MOAI_LAUNCH_CHECK();
-    return moddown(c, last, acc, (uint32_t)(L + 1), ops, ct, batch * 2, L, (uint32_t)(k - 1), addend, (uint32_t)addend_bstride, add_mode, s,
-                   w.splits, w.split_stride, nullptr, addend2, lst);
+    MOAI_TRY(launch_rows(sum_rows_kernel, c, batch * 2, s, acc, last, (uint32_t)(L + 1), (uint32_t)L, w.splits, w.split_stride, c->pc,
+                         (uint32_t)(k - 1), n2));
+    return moddown(c, last, acc, (uint32_t)(L + 1), ops, ct, batch * 2, L, (uint32_t)(k - 1), add, s, w.splits, w.split_stride, nullptr,
+                   tg.lst);
 }
 
 } // namespace moai
@@ -962,10 +881,7 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
     {
         for (size_t r = 0; r < L; r++)
         {
-            const uint64_t q = c->primes[r];
-            const uint64_t v = scalars[r] % q; // barrett_reduce_64, polyarithsmallmod.h:209-217
-            sc[r].w = v;
-            sc[r].wq = (uint64_t)((((unsigned __int128)v) << 64) / q);
+            sc[r] = make_tw(scalars[r] % c->primes[r], c->primes[r]); // barrett_reduce_64, polyarithsmallmod.h:209-217
         }
     }
     const size_t sz_last = align256(P * row_bytes);
@@ -978,18 +894,15 @@ static int rescale_common(moai_ctx *c, const uint64_t *in, const uint64_t *scala
     void *wsp;
     MOAI_TRY(workspace(c, sz_last + sz_u, s, &wsp));
     uint64_t *last = static_cast<uint64_t *>(wsp);
-    uint64_t *u = reinterpret_cast<uint64_t *>(static_cast<char *>(wsp) + sz_last);
-    MOAI_CHECK_GRID_ROWS(P);
-    hipLaunchKernelGGL(copy_rows_kernel, rgrid(c, P), dim3(256), 0, s, in, last, 1u, (uint32_t)L, (uint32_t)(L - 1), NO_ZERO,
-                       (uint32_t)(c->n >> 1));
+    uint64_t *u = at_bytes(wsp, sz_last);
+    MOAI_TRY(launch_rows(copy_rows_kernel, c, P, s, in, last, 1u, (uint32_t)L, (uint32_t)(L - 1), NO_ZERO, (uint32_t)(c->n >> 1)));
     if (scalars)
     {
-        hipLaunchKernelGGL(scale_rows_kernel, rgrid(c, P), dim3(256), 0, s, last, sc[L - 1], c->primes[L - 1], (uint32_t)(c->n >> 1));
+        MOAI_TRY(launch_rows(scale_rows_kernel, c, P, s, last, sc[L - 1], c->primes[L - 1], (uint32_t)(c->n >> 1)));
     }
-    MOAI_LAUNCH_CHECK();
     // the addend has the output's layout: polynomial p starts (L - 1) rows after polynomial p - 1 (ModDownArgs: pairs of
     // polynomials 2 (L - 1) rows apart)
-    return moddown(c, last, in, (uint32_t)L, u, out, P, L - 1, (uint32_t)(L - 1), addend, (uint32_t)(2 * (L - 1)), addend ? 1 : 0, s, 1, 0,
+    return moddown(c, last, in, (uint32_t)L, u, out, P, L - 1, (uint32_t)(L - 1), { addend, 2 * (L - 1), addend ? 1 : 0 }, s, 1, 0,
                    scalars ? sc : nullptr);
 }
 
@@ -1067,7 +980,7 @@ extern "C" int moai_switch_key(moai_ctx *c, uint64_t *ct, const uint64_t *target
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
     MOAI_TRY(workspace(c, switch_key_ws_bytes(c, L, batch), (hipStream_t)stream, &wsp));
-    return switch_key_impl(c, ct, target, L, 0, key, L, batch, wsp, (hipStream_t)stream, ct, 2 * L, 1);
+    return switch_key_impl(c, ct, { target, L, 0 }, key, L, batch, wsp, (hipStream_t)stream, { ct, 2 * L, 1 });
 }
 
 extern "C" int moai_relinearize(moai_ctx *c, const uint64_t *ct3, const uint64_t *relin_key, uint64_t *out, size_t L,
@@ -1090,7 +1003,7 @@ extern "C" int moai_relinearize(moai_ctx *c, const uint64_t *ct3, const uint64_t
     MOAI_TRY(workspace(c, switch_key_ws_bytes(c, L, batch), s, &wsp));
     // out = (c0, c1) + switch_key(c2, relin_keys[0])      (evaluator.cpp:1383-1392): c0 and c1 are read from ct3 by
     // the last kernel of the key switch, no copy first
-    return switch_key_impl(c, out, ct3, 3 * L, 2 * L, relin_key, L, batch, wsp, s, ct3, 3 * L, 1);
+    return switch_key_impl(c, out, { ct3, 3 * L, 2 * L }, relin_key, L, batch, wsp, s, { ct3, 3 * L, 1 });
 }
 
 // out = (galois(in0), 0) + switch_key(galois(in1)) [+ sum]      (evaluator.cpp:2631-2654): both summands are added by the
@@ -1105,7 +1018,7 @@ static int apply_galois_impl(moai_ctx *c, const uint64_t *in, uint64_t *out, siz
     MOAI_TRY(workspace(c, sz_tmp + switch_key_ws_bytes(c, L, batch), s, &wsp));
     uint64_t *tmp = static_cast<uint64_t *>(wsp); // galois(in), both polynomials
     MOAI_TRY(moai_galois_permute(c, in, tmp, batch * 2, L, galois_elt, stream));
-    return switch_key_impl(c, out, tmp, 2 * L, L, galois_key, L, batch, static_cast<char *>(wsp) + sz_tmp, s, tmp, 2 * L, 2, sum);
+    return switch_key_impl(c, out, { tmp, 2 * L, L }, galois_key, L, batch, at_bytes(wsp, sz_tmp), s, { tmp, 2 * L, 2, sum });
 }
 
 extern "C" int moai_apply_galois_to(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, uint32_t galois_elt,
@@ -1193,14 +1106,7 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
     }
     const size_t nb = n < KS_LIST_MAX ? n : KS_LIST_MAX; // members per pass
     MOAI_TRY(check_level(c, L, nb * (relin ? 3 : 2)));
-    if (c->k < 2)
-    {
-        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
-    }
-    if (L > c->k - 1)
-    {
-        return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
-    }
+    MOAI_TRY(check_switch_level(c, L));
     const size_t rn = L * c->n, in_bytes = (relin ? 3 : 2) * rn * sizeof(uint64_t), out_bytes = 2 * rn * sizeof(uint64_t);
     for (size_t i = 0; i < n; ++i)
     {
@@ -1300,13 +1206,11 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
         {
             // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch_key(c2)   (evaluator.cpp:1383-1392)
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
-            return switch_key_impl(c, nullptr, tmp, L, 0, nullptr, L, cnt, static_cast<char *>(wsp) + sz_list + sz_tmp, s, nullptr, 0, 1,
-                                   nullptr, dlist);
+            return switch_key_impl(c, nullptr, { tmp, L, 0, dlist }, nullptr, L, cnt, at_bytes(wsp, sz_list + sz_tmp), s, { nullptr, 0, 1 });
         }
         // tmp [cnt][2][L][N] = galois(ins); out = (galois(in0), 0) + switch_key(galois(in1)) [+ sum]   (evaluator.cpp:2631-2654)
         MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, 2 * L, 0, s));
-        return switch_key_impl(c, nullptr, tmp, 2 * L, L, nullptr, L, cnt, static_cast<char *>(wsp) + sz_list + sz_tmp, s, tmp, 2 * L, 2,
-                               nullptr, dlist);
+        return switch_key_impl(c, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, cnt, at_bytes(wsp, sz_list + sz_tmp), s, { tmp, 2 * L, 2 });
     });
 }
 
@@ -1365,9 +1269,7 @@ extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, siz
     g.pc = c->pc;
     g.Lout = (uint32_t)L_out;
     g.n2 = (uint32_t)(c->n >> 1);
-    MOAI_CHECK_GRID_ROWS(P * L_out);
-    hipLaunchKernelGGL(modraise_kernel, rgrid(c, P * L_out), dim3(256), 0, s, g);
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY(launch_rows(modraise_kernel, c, P * L_out, s, g));
     MOAI_TRY(make_rowmap(c, L_out, nullptr, &rm));
     return ntt_launch(c, out, P, L_out, rm, false, s);
 }
@@ -1524,10 +1426,16 @@ int galois_sign_mask(moai_ctx *c, uint64_t *mask, uint32_t galois_elt, size_t co
     return MOAI_OK;
 }
 
-int any_zero(const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s)
+int probe_any_zero(moai_ctx *c, const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s, bool *found)
 {
+    (void)c;
+    MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
     hipLaunchKernelGGL(any_zero_kernel, dim3(1024), dim3(256), 0, s, v, words / 2, flag);
     MOAI_LAUNCH_CHECK();
+    uint32_t host_flag = 0;
+    MOAI_HIP_CHECK(hipMemcpyAsync(&host_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    MOAI_HIP_CHECK(hipStreamSynchronize(s));
+    *found = host_flag != 0;
     return MOAI_OK;
 }
 
@@ -1547,10 +1455,7 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
     {
         return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
     }
-    if (!(galois_elt & 1u) || galois_elt >= 2 * c->n)
-    {
-        return set_error(MOAI_EINVAL, "Galois element is not valid");
-    }
+    MOAI_TRY(galois_elt_check(c, galois_elt));
     uint32_t key_rows = 0;
     MOAI_TRY(key_rows_for(c, galois_key, L, &key_rows));
     hipStream_t s = (hipStream_t)stream;
@@ -1578,10 +1483,7 @@ extern "C" int moai_hoist_correction(moai_ctx *c, const uint64_t *galois_key, ui
     g.k = (uint32_t)c->k;
     g.krows = key_rows;
     g.n2 = (uint32_t)(c->n >> 1);
-    MOAI_CHECK_GRID_ROWS(2 * (L + 1));
-    hipLaunchKernelGGL(ks_hoist_correction_kernel, rgrid(c, 2 * (L + 1)), dim3(256), 0, s, g);
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
+    return launch_rows(ks_hoist_correction_kernel, c, 2 * (L + 1), s, g);
 }
 
 extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64_t *const *outs, size_t L, const uint32_t *galois_elts,
@@ -1630,14 +1532,7 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         return set_error(MOAI_EINVAL, "null argument");
     }
     const size_t n = c->n, k = c->k;
-    if (k < 2)
-    {
-        return set_error(MOAI_ELOGIC, "keyswitching is not supported by the context");
-    }
-    if (L > k - 1)
-    {
-        return set_error(MOAI_EINVAL, "L exceeds the key's decomposition size");
-    }
+    MOAI_TRY(check_switch_level(c, L));
     hipStream_t s = (hipStream_t)stream;
     std::vector<const uint32_t *> tables(R), itables(R);
     for (size_t r = 0; r < R; ++r)
@@ -1676,16 +1571,8 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
         RowMap rm;
         MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
         MOAI_TRY(ntt_launch(c, t, batch, L, rm, true, s, in, 2 * L, L));
-        MOAI_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
-        MOAI_TRY(any_zero(t, batch * L * n, flag, s));
-        uint32_t host_flag = 0;
-        MOAI_HIP_CHECK(hipMemcpyAsync(&host_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        MOAI_HIP_CHECK(hipStreamSynchronize(s));
-        if (host_flag)
-        {
-            fallback = true; // a zero coefficient: the identity above does not hold for it
-        }
-        else
+        MOAI_TRY(probe_any_zero(c, t, batch * L * n, flag, s, &fallback)); // a zero coefficient: the identity above does not hold for it
+        if (!fallback)
         {
             const HoistRotations rot = { R, tables.data(), itables.data(), galois_keys, key_rows.data(), corrections, acc, w.acc_stride_words };
             for (const KsPlanGroup &pg : ks_plan(c, L, batch))
@@ -1700,11 +1587,9 @@ extern "C" int moai_apply_galois_hoisted(moai_ctx *c, const uint64_t *in, uint64
                 uint64_t *acc_r = acc + r * w.acc_stride_words;
                 // pc0 [B][L][N] = perm(c0 of in): the addend of the even polynomials (add_mode 2, ciphertexts L rows apart)
                 MOAI_TRY(galois_permute_c0(c, in, pc0, batch, L, galois_elts[r], s));
-                MOAI_CHECK_GRID_ROWS(batch * 2);
-                hipLaunchKernelGGL(sum_rows_kernel, rgrid(c, batch * 2), dim3(256), 0, s, acc_r, last, (uint32_t)(L + 1), (uint32_t)L, 1u,
-                                   (size_t)0, c->pc, (uint32_t)(k - 1), n2);
-                MOAI_LAUNCH_CHECK();
-                MOAI_TRY(moddown(c, last, acc_r, (uint32_t)(L + 1), u, outs[r], batch * 2, L, (uint32_t)(k - 1), pc0, (uint32_t)L, 2, s));
+                MOAI_TRY(launch_rows(sum_rows_kernel, c, batch * 2, s, acc_r, last, (uint32_t)(L + 1), (uint32_t)L, 1u, (size_t)0, c->pc,
+                                     (uint32_t)(k - 1), n2));
+                MOAI_TRY(moddown(c, last, acc_r, (uint32_t)(L + 1), u, outs[r], batch * 2, L, (uint32_t)(k - 1), { pc0, L, 2 }, s));
             }
             return MOAI_OK;
         }

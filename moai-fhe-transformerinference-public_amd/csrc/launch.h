@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rowlaunch.h"
 
 namespace moai {
 
@@ -143,8 +144,17 @@ int galois_permute_c0(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t bat
 // the hoisted rotations' kernels of keyswitch_kernels.hip.h for another translation unit (hybrid.hip):
 // mask [copies][N], every copy = 1 where x -> x^elt negates the coefficient that lands there (galois_sign_mask_kernel)
 int galois_sign_mask(moai_ctx *c, uint64_t *mask, uint32_t galois_elt, size_t copies, hipStream_t s);
-// *flag |= 1 when one of the `words` (an even number) words at v is zero (any_zero_kernel); the caller clears the flag
-int any_zero(const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s);
+// *found = one of the `words` (an even number) words at v is zero (any_zero_kernel): clears the device word `flag`, runs the
+// kernel, copies the word back and synchronizes the stream
+int probe_any_zero(moai_ctx *c, const uint64_t *v, size_t words, uint32_t *flag, hipStream_t s, bool *found);
+// MOAI_EINVAL "Galois element is not valid" unless elt is odd and below 2N; with a null context only the oddness, which needs
+// none, is tested (the entry points that refuse an even element before they look at the context)
+int galois_elt_check(const moai_ctx *c, uint32_t elt);
+// the last kernel of the unfused mod-down (moddown_finalize_kernel), for keyswitch.hip's small rings and for hybrid.hip:
+// out [P][Lout][N] = addend + (acc - u) * inv[i] mod q_i with acc's row (p, i) at acc + (p * acc_stride + i) * N, u [P][Lout][N] in
+// NTT form and inv[i] the Shoup pair of the divisor's inverse mod q_i (device memory); lst as in moddown
+int moddown_finalize(moai_ctx *c, const uint64_t *acc, uint32_t acc_stride, const uint64_t *u, uint64_t *out, size_t P, size_t Lout,
+                     const Tw *inv, const KsAddend &add, const KsList *lst, hipStream_t s);
 // out [members][rows_per_member][N]: rows src_off_rows .. src_off_rows + rows_per_member - 1 of lst->ins[b], permuted by
 // lst->tables[b]; lst is a device pointer (common.h KsList)
 int galois_gather_list(moai_ctx *c, const KsList *lst, uint64_t *out, size_t members, size_t rows_per_member, size_t src_off_rows,

@@ -309,8 +309,7 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
     }
     if (naive && logn >= 1)
     {
-        uint32_t bx = (uint32_t)(((c->n >> 1) + 255) / 256);
-        dim3 grid(bx, (uint32_t)(n_poly * L));
+        const dim3 grid = row_grid(c, n_poly * L);
         if (!inverse)
         {
             for (int st = 0; st < logn; ++st)
