@@ -122,6 +122,91 @@ def long_chain(logn, k):
     return primes[:k], names[:k]
 
 
+# ---- the written contract of the plain transforms: the arithmetic class of every chain prime ----------------------------------
+# plain forward transform: (MOAI_NTT_FP=1, MOAI_NTT_FP=0)
+FWD_CLASS = {
+    "fpn_hi": ("FPN", "NOGUARD"), "fpr_lo": ("FPR", "NOGUARD"), "fpr_hi": ("FPR", "NOGUARD"), "int_lo": ("NOGUARD", "NOGUARD"),
+    "ng_hi": ("NOGUARD", "NOGUARD"), "g_lo": ("LAZY16", "LAZY16"), "g60": ("LAZY16", "LAZY16"), "g61": ("GUARD2", "GUARD2"),
+    "small": ("FPN", "NOGUARD"),
+}
+# plain inverse transform: GUARD = the exact integer butterflies
+INV_CLASS = {
+    "fpn_hi": ("FPN", "LAZY16"), "fpr_lo": ("FPR", "LAZY16"), "fpr_hi": ("FPR", "LAZY16"), "int_lo": ("LAZY16", "LAZY16"),
+    "ng_hi": ("LAZY16", "LAZY16"), "g_lo": ("LAZY16", "LAZY16"), "g60": ("LAZY16", "LAZY16"), "g61": ("GUARD", "GUARD"),
+    "small": ("FPN", "LAZY16"),
+}
+
+
+# ---- chains for the hybrid key switch (alpha special primes, digits of alpha data primes) ------------------------------------
+# name: (data primes, special primes); 'x-' is the next prime = 1 (mod 2N) below the limit prime x, as in long_chain
+HYBRID_CHAINS = {
+    # P above every digit's product; the classes of the data rows interleave
+    "special_large": (("fpn_hi", "g_lo", "fpr_hi", "ng_hi", "small", "fpr_lo", "int_lo"), ("g60", "g61", "ng_hi-")),
+    # P far below D_max (the header's P >= D_max is a precondition of use, not of bit-exactness): the mod-down's inverse
+    # transform runs on FP64 rows, its conversion goes from small sources to 61-bit targets, the mod-up from 61-bit sources to
+    # the prime just above 2^40
+    "special_small": (("g61", "fpn_hi", "g60", "fpr_lo", "g_lo", "int_lo", "ng_hi"), ("fpr_hi", "small", "fpn_hi-")),
+}
+WIDE_ALPHAS = (2, 4, 8, 16)
+
+
+def primes_below(logn, q, count):
+    """the next `count` primes = 1 (mod 2N) below q, descending"""
+    m = 2 << logn
+    out = []
+    for _ in range(count):
+        q = prime_at_most(logn, q - m)
+        out.append(q)
+    return out
+
+
+def hybrid_chain(logn, which, alpha=None):
+    """(primes, names, alpha): the data primes, then the alpha special primes; all distinct.  names[i] is the chain() name of prime i,
+    or the name of the limit prime it was found below with a '-' suffix.
+        special_large, special_small   HYBRID_CHAINS, alpha = 3
+        wide (alpha in WIDE_ALPHAS)    data: g61 and the next alpha - 1 primes below it (digit 0, all 61-bit), then small as a last
+                                       digit of one prime; special: the next alpha primes below those
+        long63                         alpha = 1; data: g61 and the 62 next primes below it; special: the next one (k = 64, the
+                                       library's MOAI_MAX_RNS, and 63 digits at L = 63)"""
+    c = chain(logn)
+    if which in HYBRID_CHAINS:
+        assert alpha in (None, 3)
+        names = list(HYBRID_CHAINS[which][0] + HYBRID_CHAINS[which][1])
+        primes = [primes_below(logn, c[x[:-1]], 1)[0] if x.endswith("-") else c[x] for x in names]
+        alpha = 3
+    elif which == "wide":
+        assert alpha in WIDE_ALPHAS
+        run = primes_below(logn, c["g61"], 2 * alpha - 1)
+        primes = [c["g61"]] + run[:alpha - 1] + [c["small"]] + run[alpha - 1:]
+        names = ["g61"] + ["g61-"] * (alpha - 1) + ["small"] + ["g61-"] * alpha
+    elif which == "long63":
+        assert alpha in (None, 1)
+        alpha = 1
+        primes = [c["g61"]] + primes_below(logn, c["g61"], 63)
+        names = ["g61"] + ["g61-"] * 63
+    else:
+        raise ValueError(which)
+    assert len(set(primes)) == len(primes) == len(names)
+    return primes, names, alpha
+
+
+def worst_coeff(primes, L, alpha, n):
+    """uint64 [L][n], coefficient form: row r of digit j (rows R_j = [j alpha, min((j + 1) alpha, L)), D_j their product) holds
+    c_r = (q_r - 1) (D_j / q_r) mod q_r in every coefficient.  The scaled residue y_r = c_r (D_j / q_r)^-1 mod q_r that the fast base
+    conversion multiplies its weights with is then q_r - 1, the largest there is, in every row of every digit; and no coefficient is
+    zero (both factors are units), so the hoisted rotations do not fall back."""
+    out = np.empty((L, n), dtype=np.uint64)
+    for lo in range(0, L, alpha):
+        rows = range(lo, min(lo + alpha, L))
+        for r in rows:
+            q, rest = primes[r], 1
+            for s in rows:
+                if s != r:
+                    rest = rest * primes[s] % q
+            out[r, :] = (q - 1) * rest % q
+    return out
+
+
 def largest_noguard_L(q):
     """the largest L with 36 q^2 L < 2^128 (the key switch's 128-bit lazy MAC, csrc/keyswitch.hip ks_mode)"""
     return ((1 << 128) - 1) // (36 * q * q)

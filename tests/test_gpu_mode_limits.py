@@ -15,6 +15,7 @@ import pytest
 
 import mode_limits as ML
 import oracle as O
+from mode_limits import FWD_CLASS, INV_CLASS  # the plain forward and inverse transforms
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +30,6 @@ KS_CLASS = {
     "fpn_hi": ("FPN", "NOGUARD"), "fpr_lo": ("FPR", "NOGUARD"), "fpr_hi": ("FPR", "NOGUARD"), "int_lo": ("NOGUARD", "NOGUARD"),
     "ng_hi": ("NOGUARD", "NOGUARD"), "g_lo": ("GUARD", "GUARD"), "g60": ("GUARD", "GUARD"), "g61": ("GUARD", "GUARD"),
     "small": ("FPN", "NOGUARD"),
-}
-# plain forward transform: (MOAI_NTT_FP=1, MOAI_NTT_FP=0)
-FWD_CLASS = {
-    "fpn_hi": ("FPN", "NOGUARD"), "fpr_lo": ("FPR", "NOGUARD"), "fpr_hi": ("FPR", "NOGUARD"), "int_lo": ("NOGUARD", "NOGUARD"),
-    "ng_hi": ("NOGUARD", "NOGUARD"), "g_lo": ("LAZY16", "LAZY16"), "g60": ("LAZY16", "LAZY16"), "g61": ("GUARD2", "GUARD2"),
-    "small": ("FPN", "NOGUARD"),
-}
-# plain inverse transform: GUARD = the exact integer butterflies
-INV_CLASS = {
-    "fpn_hi": ("FPN", "LAZY16"), "fpr_lo": ("FPR", "LAZY16"), "fpr_hi": ("FPR", "LAZY16"), "int_lo": ("LAZY16", "LAZY16"),
-    "ng_hi": ("LAZY16", "LAZY16"), "g_lo": ("LAZY16", "LAZY16"), "g60": ("LAZY16", "LAZY16"), "g61": ("GUARD", "GUARD"),
-    "small": ("FPN", "LAZY16"),
 }
 
 
