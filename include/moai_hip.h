@@ -785,6 +785,62 @@ int moai_apply_galois_hybrid_hoisted(moai_ctx *ctx, const uint64_t *in, uint64_t
                                      const uint64_t *const *corrections, size_t R, size_t batch, int *used_fallback,
                                      void *stream);
 
+/* ---- plaintext-weighted sums of hoisted rotations, one mod-down per sum ---------------------------------------------------------
+ * The inner sum of a baby-step / giant-step linear transform over hybrid keys: n_out outputs, each sum_r p_{g,r} (*) rot_r(ct) over
+ * the same R rotations of ONE ciphertext.  A hybrid switch keeps its sum in the extended basis Q P until step 5, so the plaintext
+ * products and the sum over r are taken THERE and one mod-down per output replaces one per rotation: no accumulator of a
+ * rotation and no rotated ciphertext reaches memory.
+ *   in [batch][2][L][N], NTT form;  outs[g] [batch][2][L][N], g < n_out;  rotation r < R: Galois element e_r, keys[r] in
+ *   moai_hybrid_keygen's layout, corrections[r] from moai_hybrid_hoist_correction for the same (key, element, L, alpha);
+ *   plains[g R + r]: p_{g,r}, [L+alpha][N] words in NTT form, rows 0..L-1 under q_i and rows L..L+alpha-1 under p_t (the row order of
+ *   a correction; moai_ckks_encode with prime_index = {0..L-1, k-alpha..k-1}), shared by the batch, or NULL: the term is absent.
+ * Per ciphertext (c0, c1) and output g, with steps 1-5 of "hybrid key switching" above, all residues canonical:
+ *   A_r    (e_r != 1)  [2][L+alpha]: the accumulator of steps 1-4 for the target perm_r(c1) with keys[r], what a separate
+ *          moai_apply_galois_hybrid forms before its step 5;  U_r[i] = perm_r(c0)[i], i < L
+ *   S_g[p][row]  = sum_{r : e_r != 1, p_{g,r} present} p_{g,r}[row] (*) A_r[p][row]  mod m_row
+ *   D_g          = step 5 of S_g: D_g[p][i] = (S_g[p][i] - NTT(conv_i(S_g[p]))) [P^-1]_{q_i}, the rounding terms as there; D_g = 0
+ *                  and no step 5 when output g has no present term with e_r != 1
+ *   out_g[0][i]  = D_g[0][i] + sum_{r : e_r != 1} p_{g,r}[i] (*) U_r[i] + sum_{r : e_r = 1} p_{g,r}[i] (*) c0[i]  mod q_i
+ *   out_g[1][i]  = D_g[1][i] + sum_{r : e_r = 1} p_{g,r}[i] (*) c1[i]  mod q_i
+ * e_r = 1 is the zeroth baby step, a plain product: its key and correction are not read and may be NULL.  Keys, corrections and
+ * plaintexts may repeat.  The result is bit for bit the integer restatement tests/hybrid_dot_ref.py.  It is NOT the sum of the
+ * separately switched rotations, whose roundings happen once each: it differs from that sum in noise only.
+ * Noise: with keys from moai_hybrid_keygen for sigma_r(s) -> s,  out_g[0] + out_g[1] s = sum_r p_{g,r} sigma_r(c0 + c1 s) + E.
+ * Before step 5, S_g[0] + S_g[1] s = P sum_r p_{g,r} sigma_r(c1) sigma_r(s) + sum_r p_{g,r} e'_r over Q_L P, where e'_r = sum_j
+ * chat_{j,r} e_{j,r} is the key noise of rotation r, |e'_r| <= beta(L) N alpha 21 D_max as in the single switch (|chat_j| <=
+ * alpha D_max, |e| <= 21, N coefficients per product).  A product p e' of polynomials has coefficients of at most |p|_1 |e'|_inf,
+ * |p|_1 the sum of the absolute centred coefficients of the encoded integer polynomial, so the key noise of S_g is at most
+ * (sum_r |p_{g,r}|_1) beta(L) N alpha 21 D_max, and step 5 divides it by P.  Step 5 itself rounds each of the two polynomials
+ * once: its fast base conversion is off by at most alpha - 1 multiples of P besides the 1/2 of the rounding, (alpha - 1/2) on
+ * d0 and (alpha - 1/2) |s|_1 through d1 s.  The products added after step 5 are exact.  Hence
+ *   |E| <= (sum_{r : e_r != 1} |p_{g,r}|_1) beta(L) N alpha 21 D_max / P + (alpha - 1/2)(1 + |s|_1):
+ * the single switch's first term scaled by the plaintexts, and ONE mod-down's rounding however many rotations are summed.
+ * Hoisted as moai_apply_galois_hybrid_hoisted: steps 1-3 run once per ciphertext on the unpermuted c1, every rotation reads the
+ * digits through its permutation table and adds its correction, and the kernel weights the accumulators it holds in registers
+ * into S_g and the addend of every output in flight, MOAI_HYBRID_HOIST_NR rotations per pass; S_g and the addend travel between
+ * passes as canonical residues.  The identity needs INTT(c1) free of zero coefficients: the call checks that on the device per
+ * batch chunk, and a chunk where it fails takes every rotation through the unhoisted steps 1-4 on the permuted input instead
+ * (*used_fallback = 1, same bits).  It therefore SYNCHRONISES the stream once per batch chunk and cannot run under HIP-graph stream
+ * capture (MOAI_EHIP there), as moai_apply_galois_hybrid_hoisted.
+ * Scratch from the stream's workspace, in rows of N words, for cb ciphertexts per chunk and G outputs in flight:
+ *     cb (beta (L + alpha) + 2 L + 2 (L + alpha))  +  cb G (2 (L + alpha) + 2 alpha + 2 L + 2 L)
+ * (t and the digits, the unhoisted route's permuted input and accumulators; S, special rows, conv, addend) plus one 256-byte block
+ * for the flag: nothing grows with R.  cb is the largest count for which cb ciphertexts with one output in flight fit
+ * MOAI_HYBRID_TMP_KB, G the largest for which G outputs fit beside them; at least one of each, at most batch and n_out, G <= 16 and
+ * 2 cb G (L + alpha) <= 65535.  Outputs beyond G repeat the MAC over the digits, not the decomposition.  Results depend on neither
+ * the budget nor MOAI_HYBRID_HOIST_NR.
+ * Nothing is enqueued and nothing written when an argument is refused: MOAI_EINVAL with a message for what the hybrid entry
+ * points above refuse, a null array, a null key or correction where e_r != 1, a null output, an even Galois element or one >= 2N,
+ * an output that overlaps the input or another output, an output with no present term.  batch = 0 and n_out = 0 are MOAI_OK.
+ * moai_op_trace counts "hybrid_rotate_pt_dot" (batch n_out) at L. */
+/* outs[g] = sum_r plains[g R + r] (*) rotate(in, galois_elts[r]) with ONE mod-down per output: the rotate_vector / multiply_plain /
+ * add_inplace loops of MOAI's bsgs_linear_transform (include/source/bootstrapping/Bootstrapper.cpp:2017-2042, 2082-2108) over the
+ * hybrid form of SEAL/evaluator.cpp:2724-3020 */
+int moai_hybrid_rotate_pt_dot(moai_ctx *ctx, const uint64_t *in, uint64_t *const *outs, size_t n_out, size_t L, size_t alpha,
+                              const uint32_t *galois_elts, const uint64_t *const *keys, const uint64_t *const *corrections, size_t R,
+                              const uint64_t *const *plains /* host array [n_out * R], entry g * R + r, NULL = absent */, size_t batch,
+                              int *used_fallback, void *stream);
+
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is

@@ -308,6 +308,223 @@ __global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
     }
 }
 
+// ---- plaintext-weighted sums of rotations (moai_hybrid_rotate_pt_dot) ---------------------------------------------------------
+// outputs in flight per launch: their plaintext pointers travel as kernel arguments
+constexpr int HY_DOT_MAX_NG = 16;
+
+struct HyDotOutputs
+{
+    uint64_t *S;     // output h's extended-basis sums at S + h * B * 2 * (L + alpha) * N: [B][2][L + alpha][N], canonical
+    uint64_t *add;   // its addend at add + h * B * 2 * L * N: [B][2][L][N], canonical, always read-modified-written
+    uint32_t ng;     // outputs of this launch
+    uint32_t seeded; // bit h: S of output h already holds a sum; clear: this launch's products start it
+    const uint64_t *plain[HY_DOT_MAX_NG][HY_HOIST_MAX_NR]; // p_{g,r} [L + alpha][N] of output h and rotation r of the pass; null: absent
+};
+
+// hy_hoisted_mac_kernel's sums for one thread at output chunk x, kept in registers: a0[r], a1[r] = the canonical acc_r[b][0][row] and
+// acc_r[b][1][row], correction included, and src[r] = the two source positions of rotation r.  The same loads in the same order and
+// the same bound (at most 63 products below 2^122, one reduction, the canonical add of the correction); that kernel keeps its own
+// copy of the loop so that its code is what it was.
+template <int NR>
+__device__ __forceinline__ void hy_hoisted_sums(const HyHoistMacArgs &g, uint32_t b, uint32_t B, uint32_t row, uint32_t prime, uint32_t x,
+                                                uint2 (&src)[NR], ulonglong2 (&a0)[NR], ulonglong2 (&a1)[NR])
+{
+    const HyDims &d = g.d;
+    const PrimeConst *pc = d.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = d.n2;
+    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * d.L + row) * 2 * n2; // read only where row < L
+    const size_t acc_poly = (size_t)(d.L + d.alpha) * n2;
+    uint64_t l0x[NR], h0x[NR], l0y[NR], h0y[NR], l1x[NR], h1x[NR], l1y[NR], h1y[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+    {
+        src[r] = reinterpret_cast<const uint2 *>(g.table[r])[x];
+        l0x[r] = h0x[r] = l0y[r] = h0y[r] = l1x[r] = h1x[r] = l1y[r] = h1y[r] = 0;
+    }
+    for (uint32_t j = 0; j < d.beta; ++j)
+    {
+        // the digit under one of its own primes is the input's c1 row, read through the same permutation
+        const uint64_t *op = hy_digit_operand(own, g.ext, 2 * n2, d.L, d.alpha, B, b, row, j);
+        const size_t koff = ((size_t)j * 2 * d.k + prime) * n2 + x;
+        ulonglong2 o[NR], k0[NR], k1[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[r]);
+            o[r] = make_ulonglong2(op[src[r].x], op[src[r].y]);
+            k0[r] = key[koff];
+            k1[r] = key[koff + (size_t)d.k * n2];
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            mac2(l0x[r], h0x[r], l0y[r], h0y[r], o[r], k0[r]);
+            mac2(l1x[r], h1x[r], l1y[r], h1y[r], o[r], k1[r]);
+        }
+    }
+    ulonglong2 c0[NR], c1[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+    {
+        const ulonglong2 *corr = reinterpret_cast<const ulonglong2 *>(g.corr[r]) + (size_t)row * n2 + x;
+        c0[r] = corr[0];
+        c1[r] = corr[acc_poly];
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+    {
+        a0[r] = add2(reduce2(l0x[r], h0x[r], l0y[r], h0y[r], q, cr0, cr1), c0[r], q);
+        a1[r] = add2(reduce2(l1x[r], h1x[r], l1y[r], h1y[r], q, cr0, cr1), c1[r], q);
+    }
+}
+
+// S_h[b][p][row] += sum_r plain[h][r][row] (*) acc_r[b][p][row] and, on the data rows, add_h[b][0][row] += sum_r plain[h][r][row] (*)
+// perm_r(c0)[row], for the NR rotations of one pass of hy_hoisted_sums and every output in flight: the accumulators of a rotation
+// never leave the registers.  Grid as hy_hoisted_mac_kernel.  A rotation's sums and its gathered c0 are formed once and reused by
+// every output; the plaintext, S and the addend are read and written in order.  Every 128-bit sum here is one canonical residue
+// (below 2^61) plus at most NR <= 4 products below 2^122, below 2^125: no fold, one reduction, and the stored value is canonical
+// again, so the sum over any number of rotations is carried across passes as residues.  An absent term (a null pointer, uniform)
+// multiplies by zero; an output with no term in the pass is skipped, and one whose S no pass has written yet starts from zero.
+template <int NR>
+__global__ __launch_bounds__(256) void hy_hoisted_dot_kernel(HyHoistMacArgs g, HyDotOutputs o)
+{
+    const HyDims &d = g.d;
+    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = d.n2;
+    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
+    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
+    const bool data = row < d.L;
+    const uint64_t *c0 = g.in + ((size_t)(b * 2) * d.L + row) * 2 * n2; // read only on the data rows
+    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2;
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
+    {
+        uint2 src[NR];
+        ulonglong2 a0[NR], a1[NR], u[NR];
+        hy_hoisted_sums<NR>(g, b, B, row, prime, x, src, a0, a1);
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+        {
+            u[r] = data ? make_ulonglong2(c0[src[r].x], c0[src[r].y]) : make_ulonglong2(0, 0);
+        }
+        for (uint32_t h = 0; h < o.ng; ++h)
+        {
+            ulonglong2 p[NR];
+            bool any = false;
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+            {
+                p[r] = make_ulonglong2(0, 0);
+                if (o.plain[h][r])
+                {
+                    p[r] = reinterpret_cast<const ulonglong2 *>(o.plain[h][r])[(size_t)row * n2 + x];
+                    any = true;
+                }
+            }
+            if (!any)
+            {
+                continue;
+            }
+            // every load of this output before its arithmetic; an absent term multiplies by zero
+            ulonglong2 *S = reinterpret_cast<ulonglong2 *>(o.S) + h * s_out + s_row + x;
+            ulonglong2 *ad = reinterpret_cast<ulonglong2 *>(o.add) + h * add_out + add_row + x; // touched only on the data rows
+            const bool seeded = (o.seeded >> h) & 1u;
+            const ulonglong2 zero = make_ulonglong2(0, 0);
+            const ulonglong2 s0 = seeded ? S[0] : zero, s1 = seeded ? S[s_poly] : zero, ad0 = data ? ad[0] : zero;
+            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y, lux, hux, luy, huy;
+            seed2(l0x, h0x, l0y, h0y, s0);
+            seed2(l1x, h1x, l1y, h1y, s1);
+            seed2(lux, hux, luy, huy, ad0);
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+            {
+                mac2(l0x, h0x, l0y, h0y, a0[r], p[r]);
+                mac2(l1x, h1x, l1y, h1y, a1[r], p[r]);
+                mac2(lux, hux, luy, huy, u[r], p[r]);
+            }
+            S[0] = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
+            S[s_poly] = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
+            if (data)
+            {
+                ad[0] = reduce2(lux, hux, luy, huy, q, cr0, cr1);
+            }
+        }
+    }
+}
+
+struct HyDotTermArgs
+{
+    const uint64_t *A; // the term's accumulators [B][2][L + alpha][N], canonical; null: an identity term, which has none
+    const uint64_t *u; // ciphertext b's rows at u + b * 2 * L * N, [2][L][N]: the permuted input of a rotation, the input itself for
+                       // an identity term
+    HyDims d;
+};
+
+// One term r of the sums, for every output in flight (plain[h][0] = p_{h,r}, null: absent); blockIdx.x = b, .z = row.
+//   a rotation (A set, rows of L + alpha):  S_h[b][p][row] += plain (*) A[b][p][row];  add_h[b][0][row] += plain (*) u[b][0][row] on data rows
+//   an identity term (A null, rows of L):   add_h[b][p][row] += plain (*) u[b][p][row], p in {0, 1}
+// The unhoisted route of a chunk and the identity terms.  addmul2: every product is reduced and added canonically, no 128-bit sum.
+__global__ __launch_bounds__(256) void hy_dot_term_kernel(HyDotTermArgs g, HyDotOutputs o)
+{
+    const HyDims &d = g.d;
+    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = d.n2;
+    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
+    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
+    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2, add_poly = (size_t)d.L * n2; // the layout of u and of an addend
+    const bool data = row < d.L;
+    const ulonglong2 *A = reinterpret_cast<const ulonglong2 *>(g.A), *u = reinterpret_cast<const ulonglong2 *>(g.u);
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
+    {
+        ulonglong2 a0, a1, u0, u1;
+        a0 = a1 = u0 = u1 = make_ulonglong2(0, 0);
+        if (A)
+        {
+            a0 = A[s_row + x];
+            a1 = A[s_row + s_poly + x];
+        }
+        if (data)
+        {
+            u0 = u[add_row + x];
+            if (!A)
+            {
+                u1 = u[add_row + add_poly + x];
+            }
+        }
+        for (uint32_t h = 0; h < o.ng; ++h)
+        {
+            if (!o.plain[h][0])
+            {
+                continue;
+            }
+            const ulonglong2 p = reinterpret_cast<const ulonglong2 *>(o.plain[h][0])[(size_t)row * n2 + x];
+            if (A)
+            {
+                ulonglong2 *S = reinterpret_cast<ulonglong2 *>(o.S) + h * s_out + s_row + x;
+                const bool seeded = (o.seeded >> h) & 1u;
+                const ulonglong2 zero = make_ulonglong2(0, 0);
+                S[0] = addmul2(seeded ? S[0] : zero, a0, p, q, cr0, cr1);
+                S[s_poly] = addmul2(seeded ? S[s_poly] : zero, a1, p, q, cr0, cr1);
+            }
+            if (data)
+            {
+                ulonglong2 *ad = reinterpret_cast<ulonglong2 *>(o.add) + h * add_out + add_row + x;
+                ad[0] = addmul2(ad[0], u0, p, q, cr0, cr1);
+                if (!A)
+                {
+                    ad[add_poly] = addmul2(ad[add_poly], u1, p, q, cr0, cr1);
+                }
+            }
+        }
+    }
+}
+
 struct HyKeyAddArgs
 {
     uint64_t *key;          // [beta][2][k][N]
@@ -856,6 +1073,232 @@ static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, c
     });
 }
 
+// ---- plaintext-weighted sums of hoisted rotations -------------------------------------------------------------------------------
+// rows of N words of scratch: per ciphertext t, the converted digits and the unhoisted route's permuted input and accumulators; per
+// (output in flight, ciphertext) the sums S, the special rows, conv and the addend.  Nothing grows with R.
+static inline size_t hy_dot_shared_rows(size_t L, size_t alpha)
+{
+    return hy_beta(L, alpha) * (L + alpha) + 2 * L + 2 * (L + alpha);
+}
+
+static inline size_t hy_dot_output_rows(size_t L, size_t alpha)
+{
+    return 2 * (L + alpha) + 2 * alpha + 2 * L + 2 * L;
+}
+
+struct HyDotLayout
+{
+    size_t flag, t, ext, gal, acc, S, x, conv, add, total; // byte offsets
+};
+
+static HyDotLayout hy_dot_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
+{
+    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
+    HyDotLayout w;
+    w.flag = 0;
+    w.t = 256;
+    w.ext = w.t + align256(cb * L * row);
+    w.gal = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
+    w.acc = w.gal + align256(cb * 2 * L * row);
+    w.S = w.acc + align256(cb * 2 * (L + alpha) * row);
+    w.x = w.S + align256(G * cb * 2 * (L + alpha) * row);
+    w.conv = w.x + align256(G * cb * 2 * alpha * row);
+    w.add = w.conv + align256(G * cb * 2 * L * row);
+    w.total = w.add + align256(G * cb * 2 * L * row);
+    return w;
+}
+
+// ciphertexts per chunk (*cb) and outputs in flight (*G) under MOAI_HYBRID_TMP_KB, as hy_hoist_chunk sizes ciphertexts and rotations:
+// at least one of each, G at most HY_DOT_MAX_NG, and no row-per-workgroup grid above 65535 (the mod-down runs over 2 * cb * G
+// polynomials of at most L + alpha rows)
+static void hy_dot_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t n_out, size_t *cb_out, size_t *G_out)
+{
+    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
+    const size_t shared = hy_dot_shared_rows(L, alpha) * row, out = hy_dot_output_rows(L, alpha) * row;
+    const size_t cap = 65535 / (2 * (L + alpha));
+    size_t cb = budget / (shared + out);
+    cb = cb < 1 ? 1 : cb;
+    cb = cb > cap ? cap : cb;
+    cb = cb < batch ? cb : batch;
+    size_t G = budget / cb > shared ? (budget / cb - shared) / out : 0;
+    G = G < 1 ? 1 : G;
+    G = G > cap / cb ? cap / cb : G;
+    G = G > (size_t)HY_DOT_MAX_NG ? (size_t)HY_DOT_MAX_NG : G;
+    *cb_out = cb;
+    *G_out = G < n_out ? G : n_out;
+}
+
+struct HyDotTerms
+{
+    size_t R, n_out;
+    const uint32_t *elts;
+    const uint32_t *const *tables; // null where the element is 1
+    const uint64_t *const *keys, *const *corrs, *const *plains; // plains[g * R + r]
+    uint64_t *const *outs;
+};
+
+// whether rotation r carries a term of one of the outputs gs[0 .. ng)
+static bool hy_dot_used(const HyDotTerms &tm, const size_t *gs, size_t ng, size_t r)
+{
+    for (size_t h = 0; h < ng; ++h)
+    {
+        if (tm.plains[gs[h] * tm.R + r])
+        {
+            return true;
+        }
+    }
+    return false;
+}
+
+// column `slot` of o.plain = the plaintexts of rotation r for the outputs gs[0 .. ng); returns the outputs that have one as bits
+static uint32_t hy_dot_column(HyDotOutputs &o, const HyDotTerms &tm, const size_t *gs, size_t ng, size_t r, size_t slot)
+{
+    uint32_t present = 0;
+    for (size_t h = 0; h < ng; ++h)
+    {
+        o.plain[h][slot] = tm.plains[gs[h] * tm.R + r];
+        present |= o.plain[h][slot] ? 1u << h : 0u;
+    }
+    return present;
+}
+
+// one term through hy_dot_term_kernel: rows of L + alpha with accumulators A, rows of L without
+static int hy_dot_term(moai_ctx *c, const uint64_t *A, const uint64_t *u, HyDotOutputs &o, const HyDotTerms &tm, const size_t *gs, size_t ng,
+                       size_t r, size_t L, size_t alpha, size_t B, hipStream_t s)
+{
+    const uint32_t present = hy_dot_column(o, tm, gs, ng, r, 0);
+    HyDotTermArgs a;
+    a.A = A;
+    a.u = u;
+    a.d = hy_dims(c, L, alpha);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, A ? L + alpha : L, &grid));
+    hipLaunchKernelGGL(hy_dot_term_kernel, grid, dim3(256), 0, s, a, o);
+    MOAI_LAUNCH_CHECK();
+    o.seeded |= A ? present : 0u;
+    return MOAI_OK;
+}
+
+// one chunk of B ciphertexts at `in` [B][2][L][N]; output g's result goes to tm.outs[g] + out_off.  sw: the outputs with a term whose
+// element is not 1, G of them in flight; the others (idn) are sums of plain products.  *fallback is set when INTT(c1) holds a zero
+// coefficient: the chunk then takes every rotation through the unhoisted steps 1-4 on the permuted input, to the same bits.
+static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyDotTerms &tm, const std::vector<size_t> &sw,
+                            const std::vector<size_t> &idn, size_t L, size_t alpha, size_t B, size_t cb, size_t G, bool *fallback,
+                            hipStream_t s)
+{
+    const size_t n = c->n, ct_words = B * 2 * L * n;
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    const HyDotLayout w = hy_dot_layout(c, L, alpha, cb, G);
+    void *wsp;
+    MOAI_TRY(workspace(c, w.total, s, &wsp));
+    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
+    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *gal = at_bytes(wsp, w.gal), *acc = at_bytes(wsp, w.acc);
+    uint64_t *S = at_bytes(wsp, w.S), *x = at_bytes(wsp, w.x), *conv = at_bytes(wsp, w.conv), *add = at_bytes(wsp, w.add);
+    const long per_pass = tuning(K_HYBRID_HOIST_NR);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    if (!sw.empty())
+    {
+        // steps 1-3 on the UNPERMUTED c1, once for all rotations and outputs
+        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, t, ext, s));
+        MOAI_TRY(probe_any_zero(c, t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
+    }
+    MOAI_TRY(for_chunks(sw.size(), G, [&](size_t g0, size_t ng) {
+        const size_t *gs = sw.data() + g0;
+        HyDotOutputs o{};
+        o.S = S;
+        o.add = add;
+        o.ng = (uint32_t)ng;
+        MOAI_HIP_CHECK(hipMemsetAsync(add, 0, ng * ct_words * sizeof(uint64_t), s));
+        std::vector<size_t> rot, ident; // the terms these outputs have
+        for (size_t r = 0; r < tm.R; ++r)
+        {
+            if (hy_dot_used(tm, gs, ng, r))
+            {
+                (tm.elts[r] == 1 ? ident : rot).push_back(r);
+            }
+        }
+        if (!*fallback)
+        {
+            // the hoisted MAC, MOAI_HYBRID_HOIST_NR rotations per pass over the digits, weighted into S and the addend
+            for (size_t i = 0; i < rot.size();)
+            {
+                const size_t left = rot.size() - i, nr = per_pass >= 4 && left >= 4 ? 4 : (per_pass >= 2 && left >= 2 ? 2 : 1);
+                HyHoistMacArgs m{};
+                m.ext = ext;
+                m.in = in;
+                uint32_t present = 0;
+                for (size_t h = 0; h < nr; ++h)
+                {
+                    const size_t r = rot[i + h];
+                    m.table[h] = tm.tables[r];
+                    m.key[h] = tm.keys[r];
+                    m.corr[h] = tm.corrs[r];
+                    present |= hy_dot_column(o, tm, gs, ng, r, h);
+                }
+                m.d = hy_dims(c, L, alpha);
+                MOAI_TRY((dispatch<1, 2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
+                    hipLaunchKernelGGL(hy_hoisted_dot_kernel<decltype(NR)::value>, grid, dim3(256), 0, s, m, o);
+                    return MOAI_OK;
+                })));
+                MOAI_LAUNCH_CHECK();
+                o.seeded |= present;
+                i += nr;
+            }
+        }
+        else
+        {
+            // per rotation: permute, steps 1-4 into one scratch accumulator, then its products
+            for (size_t r : rot)
+            {
+                MOAI_TRY(moai_galois_permute(c, in, gal, B * 2, L, tm.elts[r], s));
+                MOAI_TRY(hy_decompose(c, tab, { gal, 2 * L, L }, L, alpha, B, t, ext, s));
+                HyMacArgs m;
+                m.ext = ext;
+                m.tgt = gal;
+                m.key = tm.keys[r];
+                m.acc = acc;
+                m.tgt_stride = (uint32_t)(2 * L);
+                m.tgt_off = (uint32_t)L;
+                m.d = hy_dims(c, L, alpha);
+                hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
+                MOAI_LAUNCH_CHECK();
+                MOAI_TRY(hy_dot_term(c, acc, gal, o, tm, gs, ng, r, L, alpha, B, s));
+            }
+        }
+        for (size_t r : ident)
+        {
+            MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, gs, ng, r, L, alpha, B, s));
+        }
+        // step 5 once per output, over (output, ciphertext) pairs
+        MOAI_TRY(hy_mod_down(c, tab, S, x, conv, L, alpha, ng * B, s));
+        for (size_t h = 0; h < ng; ++h)
+        {
+            MOAI_TRY(moddown_finalize(c, S + h * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + h * ct_words, tm.outs[gs[h]] + out_off,
+                                      2 * B, L, tab->pinv, { add + h * ct_words, 2 * L, 1 }, nullptr, s));
+        }
+        return MOAI_OK;
+    }));
+    // outputs of identity terms only: no step 5, the sum is formed in the output itself
+    for (size_t g : idn)
+    {
+        HyDotOutputs o{};
+        o.add = tm.outs[g] + out_off;
+        o.ng = 1;
+        MOAI_HIP_CHECK(hipMemsetAsync(o.add, 0, ct_words * sizeof(uint64_t), s));
+        for (size_t r = 0; r < tm.R; ++r)
+        {
+            if (tm.plains[g * tm.R + r])
+            {
+                MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, &g, 1, r, L, alpha, B, s));
+            }
+        }
+    }
+    return MOAI_OK;
+}
+
 } // namespace moai
 
 using namespace moai;
@@ -1011,6 +1454,100 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
                 MOAI_HIP_CHECK(hipMemcpyAsync(outs[r] + off, in + off, B * 2 * L * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
                 MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, nullptr, keys[r], L, alpha, galois_elts[r], B, stream));
             }
+        }
+        return MOAI_OK;
+    });
+}
+
+extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64_t *const *outs, size_t n_out, size_t L, size_t alpha,
+                                         const uint32_t *galois_elts, const uint64_t *const *keys, const uint64_t *const *corrections,
+                                         size_t R, const uint64_t *const *plains, size_t batch, int *used_fallback, void *stream)
+{
+    MOAI_AUDIT(stream, in);
+    for (size_t g = 0; outs && g < n_out; ++g)
+    {
+        MOAI_AUDIT(stream, outs[g]);
+    }
+    trace_op("hybrid_rotate_pt_dot", L, batch * n_out);
+    if (used_fallback)
+    {
+        *used_fallback = 0;
+    }
+    for (size_t r = 0; galois_elts && r < R; ++r)
+    {
+        MOAI_TRY(galois_elt_check(nullptr, galois_elts[r])); // oddness first: it needs no context
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (batch == 0 || n_out == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!in || !outs || !plains || (R && (!galois_elts || !keys || !corrections)))
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t n = c->n, ct_bytes = batch * 2 * L * n * sizeof(uint64_t);
+    for (size_t r = 0; r < R; ++r)
+    {
+        MOAI_TRY(galois_elt_check(c, galois_elts[r]));
+        if (galois_elts[r] != 1 && (!keys[r] || !corrections[r]))
+        {
+            return set_error(MOAI_EINVAL, "null key or correction of rotation %zu", r);
+        }
+    }
+    std::vector<size_t> sw, idn; // outputs with and without a term that is switched
+    for (size_t g = 0; g < n_out; ++g)
+    {
+        if (!outs[g])
+        {
+            return set_error(MOAI_EINVAL, "null output");
+        }
+        if (overlap(outs[g], ct_bytes, in, ct_bytes))
+        {
+            return set_error(MOAI_EINVAL, "an output must not alias the input");
+        }
+        for (size_t q = 0; q < g; ++q)
+        {
+            if (overlap(outs[g], ct_bytes, outs[q], ct_bytes))
+            {
+                return set_error(MOAI_EINVAL, "an output must not alias another output");
+            }
+        }
+        bool any = false, switched = false;
+        for (size_t r = 0; r < R; ++r)
+        {
+            if (plains[g * R + r])
+            {
+                any = true;
+                switched = switched || galois_elts[r] != 1;
+            }
+        }
+        if (!any)
+        {
+            return set_error(MOAI_EINVAL, "output %zu has no term", g);
+        }
+        (switched ? sw : idn).push_back(g);
+    }
+    MOAI_TRY(enter_device(c));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<const uint32_t *> tables(R, nullptr);
+    for (size_t r = 0; r < R; ++r)
+    {
+        if (galois_elts[r] != 1)
+        {
+            MOAI_TRY(galois_table(c, galois_elts[r], &tables[r])); // built before the first launch of the call
+        }
+    }
+    const HyDotTerms tm = { R, n_out, galois_elts, tables.data(), keys, corrections, plains, outs };
+    size_t cb, G;
+    hy_dot_chunk(c, L, alpha, batch, std::max<size_t>(sw.size(), 1), &cb, &G);
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        const size_t off = b0 * 2 * L * n;
+        bool fallback = false;
+        MOAI_TRY(hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, cb, G, &fallback, s));
+        if (fallback && used_fallback)
+        {
+            *used_fallback = 1;
         }
         return MOAI_OK;
     });

@@ -114,6 +114,7 @@ SYMBOLS = {
     "moai_apply_galois_hybrid": (C.c_int, [vp, vp, sz, sz, C.c_uint32, vp, sz, vp]),
     "moai_hybrid_hoist_correction": (C.c_int, [vp, vp, C.c_uint32, sz, sz, vp, vp]),
     "moai_apply_galois_hybrid_hoisted": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_int), vp]),
+    "moai_hybrid_rotate_pt_dot": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -423,6 +424,25 @@ class Context:
         cp = (vp * R)(*[_ptr(k) for k in corrections])
         fb = C.c_int(0)
         _check(lib().moai_apply_galois_hybrid_hoisted(self.h, _ptr(src), op, L, alpha, e, kp, cp, R, batch, C.byref(fb), stream))
+        return bool(fb.value)
+
+    def hybrid_rotate_pt_dot(self, src, dsts, L, alpha, elts, keys, corrections, plains, batch, stream=None):
+        """dsts[g] = sum_r plains[g][r] (*) rotation elts[r] of src, summed in the extended basis with one mod-down per output
+        (dsts: one buffer [n_out][batch][2][L][N] or a list of n_out buffers; plains: n_out lists of R buffers [L+alpha][N] or None
+        for an absent term; keys[r] and corrections[r] may be None where elts[r] is 1); returns True when a chunk took the
+        unhoisted route (a zero coefficient in INTT(c1))"""
+        R, n_out = len(elts), len(plains)
+        if isinstance(dsts, (list, tuple)):
+            op = (vp * n_out)(*[_ptr(d) for d in dsts])
+        else:
+            words = batch * 2 * L * self.n * 8
+            op = (vp * n_out)(*[_ptr(dsts) + g * words for g in range(n_out)])
+        e = (C.c_uint32 * R)(*[int(x) for x in elts])
+        kp = (vp * R)(*[_ptr(k) for k in keys])
+        cp = (vp * R)(*[_ptr(k) for k in corrections])
+        pp = (vp * (n_out * R))(*[_ptr(p) for row in plains for p in row])
+        fb = C.c_int(0)
+        _check(lib().moai_hybrid_rotate_pt_dot(self.h, _ptr(src), op, n_out, L, alpha, e, kp, cp, R, pp, batch, C.byref(fb), stream))
         return bool(fb.value)
 
     def apply_galois_to(self, src, dst, L, elt, key, batch, stream=None):
