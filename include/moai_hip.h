@@ -841,6 +841,68 @@ int moai_hybrid_rotate_pt_dot(moai_ctx *ctx, const uint64_t *in, uint64_t *const
                               const uint64_t *const *plains /* host array [n_out * R], entry g * R + r, NULL = absent */, size_t batch,
                               int *used_fallback, void *stream);
 
+/* ---- giant steps summed in the extended basis: a whole BSGS linear transform with n_giant + 2 polynomial mod-downs -----------------
+ * The second half of the double-hoisted baby-step / giant-step transform over hybrid keys.  The inner sums of the section above stay
+ * in the extended basis Q P; each giant step takes ONE polynomial of its inner sum (c1) down to Q to feed its own key switch, whose
+ * accumulator is again kept over Q P; everything is summed there and ONE step 5 of both polynomials ends the call.  No inner sum, no
+ * rotated inner sum and no accumulator of a giant step is rounded or written out on its own.
+ *   in, out [batch][2][L][N], NTT form;  baby step r < R: element e_r, baby_keys[r], baby_corrections[r] and plains[g R + r] exactly
+ *   the operands of the section above with n_out = n_giant;  giant step g < n_giant: Galois element E_g and giant_keys[g], an ordinary
+ *   hybrid Galois key for sigma_{E_g}(s) -> s in moai_hybrid_keygen's layout (what moai_apply_galois_hybrid takes; no correction).
+ *   An element 1 on either side reads no key (and no correction): the entries may be NULL there.
+ * Per ciphertext, all residues canonical, with S_g [2][L+alpha] and the addend a_g [2][L] (a_g[p][i] = out_g[p][i] - D_g[p][i]) of
+ * the section above for output g, and Pq_i = P mod q_i:
+ *   T_g    the inner sum lifted into Q P, nothing rounded: T_g[p][i] = S_g[p][i] + Pq_i a_g[p][i] mod q_i on the data rows i < L,
+ *          T_g[p][row] = S_g[p][row] on the special rows (S_g = 0 where output g has no term with e_r != 1)
+ *   c1'_g  [L] = out_g[1] of the section above, bit for bit: step 5 of S_g[1] plus a_g[1], and a_g[1] alone without a step 5 where
+ *          output g has no term with e_r != 1.  The only mod-down a giant step takes, of one polynomial.
+ *   E_g != 1:  B_g [2][L+alpha] = the accumulator of steps 1-4 for the target perm_{E_g}(c1'_g) with giant_keys[g];
+ *              Z[0][row] += B_g[0][row] + perm_{E_g}(T_g[0])[row] over all L + alpha rows,  Z[1][row] += B_g[1][row]
+ *   E_g = 1:   Z[p][row] += T_g[p][row]
+ *   out = step 5 of Z, both polynomials, no addend.
+ * Lifting is exact ((T[i] - conv_i) P^-1 = (S[i] - conv_i) P^-1 + a[i] mod q_i, the special rows untouched), so one giant step of
+ * element 1 is the section above with one output, bit for bit; and R = 1, e_0 = 1, the all-ones plaintext and one giant step E with
+ * key K is moai_apply_galois_hybrid on a copy of the input, bit for bit (c1' = c1 because no step 5 runs, Z = B + perm(P c0)).
+ * Everything else differs from the composition of those calls in noise only.  The result is bit for bit the integer restatement
+ * tests/hybrid_bsgs_ref.py.
+ * Noise: with keys for sigma(s) -> s,  out[0] + out[1] s = sum_g sigma_{E_g}(sum_r p_{g,r} sigma_{e_r}(c0 + c1 s)) + E.  Write M_g for
+ * the inner sum's message.  By the section above T_g[0] + T_g[1] s = P M_g + eps_g over Q_L P with |eps_g| <= l_g u P, where l_g =
+ * sum_{r : e_r != 1} |p_{g,r}|_1 and u = beta(L) N alpha 21 D_max / P is the single switch's key-noise term.  The one-polynomial
+ * mod-down gives T_g[1] = P c1'_g + rho_g with |rho_g| <= (alpha - 1/2) P (the fast base conversion is off by at most alpha - 1
+ * multiples of P besides the 1/2 of the rounding; rho_g = 0 where no step 5 runs).  The giant switch gives B_g[0] + B_g[1] s = P
+ * sigma_E(c1'_g) sigma_E(s) + eps'_g with |eps'_g| <= u P, so giant step g adds
+ *   B_g[0] + sigma_E(T_g[0]) + B_g[1] s = P sigma_E(M_g) + sigma_E(eps_g) - sigma_E(rho_g s) + eps'_g,   |rho_g s| <= (alpha - 1/2) P |s|_1,
+ * and a giant step of element 1 adds P M_g + eps_g.  The final step 5 divides the sum by P and rounds both polynomials once.  Hence
+ *   |E| <= (alpha - 1/2)(1 + |s|_1) + sum_g [ l_g u + [E_g != 1] (u + (alpha - 1/2) |s|_1) ].
+ * On the device the inner stage is that of the section above up to its step 5 (one decomposition of the unpermuted c1 per ciphertext,
+ * the zero probe and its unhoisted route, MOAI_HYBRID_HOIST_NR rotations per pass), for the giant steps of a group at a time.  Then
+ * one kernel takes S_g[1] and a_g[1] to c1'_g and writes it permuted by E_g, steps 1-3 run over all (giant step, ciphertext) pairs of
+ * the group at once, and one MAC kernel sums the giant steps' digit-key products, the gathered T_g[0] and the terms of element 1 into
+ * Z, which it reads (after the first group) and writes once per group.  The giant stage is not hoisted and needs no zero probe:
+ * *used_fallback and the one synchronisation per batch chunk are the inner stage's, and the call cannot run under HIP-graph stream
+ * capture (MOAI_EHIP there).
+ * Scratch from the stream's workspace, in rows of N words, for cb ciphertexts per chunk and G giant steps in flight:
+ *     cb (beta (L + alpha) + 2 L + 2 (L + alpha)  +  2 (L + alpha) + 2 alpha + 2 L)
+ *   + cb G (2 (L + alpha) + 2 L  +  alpha + L  +  L + beta (L + alpha))
+ * (the inner stage's shared rows; Z with the special rows and conv of its step 5; per giant step S and the addend; the special rows
+ * and conv of c1'; the permuted c1' with its t and digits) plus one 256-byte block for the flag: nothing grows with R.  A group of giant
+ * steps repeats the inner stage's MAC over the baby steps it uses and a batch chunk repeats nothing, so the giant steps come first:
+ * G = min(n_giant, 16) when one ciphertext with G giant steps in flight fits MOAI_HYBRID_TMP_KB, and cb is then the largest count that
+ * fits with them; else cb = 1 and G is the largest count that fits beside one ciphertext, at least one.  cb <= batch (the chunks of
+ * a batch are evened out) and 2 cb G (L + alpha) <= 65535.  Results depend on neither the budget nor MOAI_HYBRID_HOIST_NR.
+ * Nothing is enqueued and nothing written when an argument is refused: MOAI_EINVAL with a message for everything the section above
+ * refuses, a null giant array, a null giant key where E_g != 1, an even giant element or one >= 2N, out null or overlapping in, a
+ * giant step with no present term, R = 0 or n_giant = 0.  batch = 0 is MOAI_OK.
+ * moai_op_trace counts "hybrid_bsgs_dot" (batch) at L and none of the calls it replaces. */
+/* out = sum_g rotate( sum_r plains[g R + r] (*) rotate(in, baby_elts[r]), giant_elts[g] ), everything summed in the extended basis:
+ * the whole of MOAI's bsgs_linear_transform / rotated_bsgs_linear_transform (include/source/bootstrapping/Bootstrapper.cpp:1997-2062,
+ * 2064-2129) over the hybrid form of SEAL/evaluator.cpp:2724-3020 */
+int moai_hybrid_bsgs_dot(moai_ctx *ctx, const uint64_t *in, uint64_t *out /* [batch][2][L][N] */, size_t L, size_t alpha,
+                         const uint32_t *baby_elts, const uint64_t *const *baby_keys, const uint64_t *const *baby_corrections, size_t R,
+                         const uint32_t *giant_elts, const uint64_t *const *giant_keys, size_t n_giant,
+                         const uint64_t *const *plains /* host array [n_giant * R], entry g * R + r, NULL = absent */, size_t batch,
+                         int *used_fallback, void *stream);
+
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is

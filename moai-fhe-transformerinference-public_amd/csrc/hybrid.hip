@@ -18,6 +18,10 @@
 // Hoisted rotations (R automorphisms of one ciphertext, each with its own key) run t, ext_j and their forward transforms ONCE on
 // the unpermuted c1 and replace the MAC by hy_hoisted_mac_kernel, which reads the digits through each rotation's permutation
 // table and adds that rotation's correction (hy_hoist_correction_kernel; the header states the identity).
+// Plaintext-weighted sums of hoisted rotations keep S_g and an addend per output in the extended basis (hy_hoisted_dot_kernel) and
+// take one step 5 per sum; a whole baby-step / giant-step transform (moai_hybrid_bsgs_dot) stops that inner stage before its step 5,
+// takes only c1 of every inner sum down (hy_c1_moddown_permute_kernel), and sums the giant steps' digit-key products and the lifted
+// inner sums into one accumulator Z over Q P (hy_bsgs_mac_kernel) that takes the one final step 5.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 #include <algorithm>
@@ -522,6 +526,153 @@ __global__ __launch_bounds__(256) void hy_dot_term_kernel(HyDotTermArgs g, HyDot
                 }
             }
         }
+    }
+}
+
+// ---- giant steps summed in the extended basis (moai_hybrid_bsgs_dot) ------------------------------------------------------------
+struct HyC1Args
+{
+    const uint64_t *S;    // [ng][B][2][L + alpha][N]: polynomial 1 of pair (h, b) is read where h < n_md
+    const uint64_t *conv; // [n_md * B][L][N], NTT form: the base conversion of the special rows of S[.][.][1]
+    const uint64_t *add;  // [ng][B][2][L][N]: the addends, polynomial 1 read
+    uint64_t *tgt;        // [n_rot * B][L][N]
+    const uint32_t *table[HY_DOT_MAX_NG]; // giant step h's index permutation, h < n_rot
+    const Tw *pinv;       // P^-1 mod q_i
+    uint32_t n_md, B;
+    HyDims d;
+};
+
+// The one-polynomial form of the mod-down's last kernel, with the giant step's permutation applied as it writes: for pair (h, b),
+//   c1'[i] = add[h][b][1][i] + (S[h][b][1][i] - conv[h B + b][i]) P^-1 mod q_i   where h < n_md (moddown_finalize_kernel's arithmetic),
+//   c1'[i] = add[h][b][1][i]                                                    otherwise (an inner sum without a switched term),
+// and tgt[h B + b][i][x] = c1'[i][table_h[x]].  blockIdx.y = (h B + b) L + i.  The target is written in order, two words per lane;
+// the two or three sources are gathered.
+__global__ __launch_bounds__(256) void hy_c1_moddown_permute_kernel(HyC1Args g)
+{
+    const HyDims &d = g.d;
+    const uint32_t pair = blockIdx.y / d.L, i = blockIdx.y % d.L, h = pair / g.B;
+    const uint64_t q = d.pc[i].q;
+    const Tw inv = g.pinv[i];
+    const size_t n = 2 * (size_t)d.n2;
+    const uint64_t *S = g.S + ((size_t)(pair * 2 + 1) * (d.L + d.alpha) + i) * n;
+    const uint64_t *u = g.conv + ((size_t)pair * d.L + i) * n;
+    const uint64_t *ad = g.add + ((size_t)(pair * 2 + 1) * d.L + i) * n;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.tgt) + (size_t)blockIdx.y * d.n2;
+    const uint2 *table = reinterpret_cast<const uint2 *>(g.table[h]);
+    const bool md = h < g.n_md;
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
+    {
+        const uint2 src = table[x];
+        ulonglong2 r = make_ulonglong2(ad[src.x], ad[src.y]);
+        if (md)
+        {
+            ulonglong2 v;
+            v.x = csub(mul_shoup_lazy(S[src.x] + q - u[src.x], inv.w, inv.wq, q), q);
+            v.y = csub(mul_shoup_lazy(S[src.y] + q - u[src.y], inv.w, inv.wq, q), q);
+            r = add2(v, r, q);
+        }
+        o[x] = r;
+    }
+}
+
+struct HyBsgsMacArgs
+{
+    const uint64_t *ext; // as HyMacArgs for the n_rot * B targets: digit j at ext + j * n_rot * B * L * N
+    const uint64_t *tgt; // [n_rot * B][L][N]: perm_{E_h}(c1'_h) of pair (h, b) at row block h * B + b
+    const uint64_t *S;   // [ng][B][2][L + alpha][N], canonical (zero where the inner sum has no switched term)
+    const uint64_t *add; // [ng][B][2][L][N], canonical
+    uint64_t *Z;         // [B][2][L + alpha][N]
+    const uint32_t *table[HY_DOT_MAX_NG]; // giant step h < n_rot: its index permutation
+    const uint64_t *key[HY_DOT_MAX_NG];   // and its key [beta(k - alpha)][2][k][N]
+    uint64_t fac[MOAI_MAX_RNS];           // P mod q_i
+    uint32_t n_rot, ng;  // giant steps h < n_rot have E_h != 1, n_rot <= h < ng have E_h = 1
+    uint32_t zseeded;    // Z holds the sum of the earlier groups; clear: this launch starts it
+    HyDims d;
+};
+
+// Z[b][p][row] (+)= sum_{h < ng} contribution of giant step h, for the giant steps of one group; grid as hy_mac_kernel (blockIdx.x =
+// b, blockIdx.z = row).  With T_h = S_h + (P mod q_row) a_h on the data rows and T_h = S_h on the special rows (the inner sum lifted
+// into Q P, nothing rounded):
+//   h < n_rot (E_h != 1):  Z[0] += sum_j digit_{h,j}[row] (*) key_h[j][0][row] + T_h[0][row][table_h],   Z[1] += sum_j digit_{h,j}[row]
+//                          (*) key_h[j][1][row], the digits those of perm_{E_h}(c1'_h) (steps 1-3 on tgt)
+//   h >= n_rot (E_h = 1):  Z[p] += T_h[p][row]
+// A thread owns two neighbouring output positions; the digits, the keys and Z are read in order and only T_h[0] of a rotated giant
+// step is gathered.  No B_h and no permuted T_h[0] reaches memory, and Z is read (after the first group) and written once.
+// 128-bit sums: the running sums z0, z1 are canonical residues (below 2^61).  Per giant step a sum is seeded with one of them and
+// takes the beta <= 63 products below 2^122 of the digits: below 2^61 + 63 2^122 < 2^128, one reduction.  The lifted term is then
+// one canonical residue (z + S, added canonically) plus ONE product below 2^122, reduced again.  Every giant step leaves canonical
+// residues behind, so the sum over any number of giant steps and groups is carried as residues and cannot overflow.
+__global__ __launch_bounds__(256) void hy_bsgs_mac_kernel(HyBsgsMacArgs g)
+{
+    const HyDims &d = g.d;
+    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
+    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
+    const PrimeConst *pc = d.pc + prime;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = d.n2;
+    const bool data = row < d.L;
+    const uint64_t fac = data ? g.fac[row] : 0;
+    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
+    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
+    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2, add_poly = (size_t)d.L * n2; // touched only on the data rows
+    const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
+    const ulonglong2 *S = reinterpret_cast<const ulonglong2 *>(g.S), *ad = reinterpret_cast<const ulonglong2 *>(g.add);
+    ulonglong2 *Z = reinterpret_cast<ulonglong2 *>(g.Z) + s_row;
+    const ulonglong2 zero = make_ulonglong2(0, 0);
+    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
+    {
+        ulonglong2 z0 = zero, z1 = zero;
+        if (g.zseeded)
+        {
+            z0 = Z[x];
+            z1 = Z[s_poly + x];
+        }
+        for (uint32_t h = 0; h < g.n_rot; ++h)
+        {
+            const uint32_t pair = h * B + b;
+            // the lifted inner sum's polynomial 0, gathered: its loads are issued before the digit loop
+            const uint2 src = reinterpret_cast<const uint2 *>(g.table[h])[x];
+            const uint64_t *Sh = g.S + 2 * (h * s_out + s_row), *ah = g.add + 2 * (h * add_out + add_row);
+            const ulonglong2 t0 = make_ulonglong2(Sh[src.x], Sh[src.y]);
+            const ulonglong2 a0 = data ? make_ulonglong2(ah[src.x], ah[src.y]) : zero;
+            const ulonglong2 *own = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)pair * d.L + row) * n2; // read where row < L
+            const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[h]) + (size_t)prime * n2;
+            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y;
+            seed2(l0x, h0x, l0y, h0y, z0);
+            seed2(l1x, h1x, l1y, h1y, z1);
+            for (uint32_t j = 0; j < d.beta; ++j)
+            {
+                const ulonglong2 *op = hy_digit_operand(own, ext, n2, d.L, d.alpha, g.n_rot * B, pair, row, j);
+                const ulonglong2 o = op[x];
+                const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * d.k * n2 + x];
+                const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * d.k * n2 + x];
+                mac2(l0x, h0x, l0y, h0y, o, k0);
+                mac2(l1x, h1x, l1y, h1y, o, k1);
+            }
+            z1 = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
+            seed2(l0x, h0x, l0y, h0y, add2(reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1), t0, q));
+            mac2(l0x, h0x, l0y, h0y, a0, fac);
+            z0 = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
+        }
+        for (uint32_t h = g.n_rot; h < g.ng; ++h)
+        {
+            const ulonglong2 t0 = S[h * s_out + s_row + x], t1 = S[h * s_out + s_row + s_poly + x];
+            ulonglong2 a0 = zero, a1 = zero;
+            if (data)
+            {
+                a0 = ad[h * add_out + add_row + x];
+                a1 = ad[h * add_out + add_row + add_poly + x];
+            }
+            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y;
+            seed2(l0x, h0x, l0y, h0y, add2(z0, t0, q));
+            seed2(l1x, h1x, l1y, h1y, add2(z1, t1, q));
+            mac2(l0x, h0x, l0y, h0y, a0, fac);
+            mac2(l1x, h1x, l1y, h1y, a1, fac);
+            z0 = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
+            z1 = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
+        }
+        Z[x] = z0;
+        Z[s_poly + x] = z1;
     }
 }
 
@@ -1179,6 +1330,88 @@ static int hy_dot_term(moai_ctx *c, const uint64_t *A, const uint64_t *u, HyDotO
     return MOAI_OK;
 }
 
+// the scratch of the inner stage of a chunk: t and the digits of the unpermuted c1, and the unhoisted route's permuted input and
+// accumulators
+struct HyDotScratch
+{
+    uint64_t *t, *ext, *gal, *acc;
+};
+
+// The inner stage for the outputs gs[0 .. ng) of one chunk of B ciphertexts at `in`, up to its step 5: o.S and o.add (o.ng = ng)
+// receive S_g and the addend a_g of every output, and o.seeded tells which outputs have a switched term (the S of the others is
+// not written).  sc.t / sc.ext hold the digits of the unpermuted c1 unless `fallback`, which takes every rotation through the
+// unhoisted steps 1-4 on the permuted input, to the same bits.  Shared by moai_hybrid_rotate_pt_dot and moai_hybrid_bsgs_dot.
+static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, const HyDotTerms &tm, const size_t *gs, size_t ng,
+                        HyDotOutputs &o, const HyDotScratch &sc, size_t L, size_t alpha, size_t B, bool fallback, hipStream_t s)
+{
+    const size_t ct_words = B * 2 * L * c->n;
+    const long per_pass = tuning(K_HYBRID_HOIST_NR);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    MOAI_HIP_CHECK(hipMemsetAsync(o.add, 0, ng * ct_words * sizeof(uint64_t), s));
+    std::vector<size_t> rot, ident; // the terms these outputs have
+    for (size_t r = 0; r < tm.R; ++r)
+    {
+        if (hy_dot_used(tm, gs, ng, r))
+        {
+            (tm.elts[r] == 1 ? ident : rot).push_back(r);
+        }
+    }
+    if (!fallback)
+    {
+        // the hoisted MAC, MOAI_HYBRID_HOIST_NR rotations per pass over the digits, weighted into S and the addend
+        for (size_t i = 0; i < rot.size();)
+        {
+            const size_t left = rot.size() - i, nr = per_pass >= 4 && left >= 4 ? 4 : (per_pass >= 2 && left >= 2 ? 2 : 1);
+            HyHoistMacArgs m{};
+            m.ext = sc.ext;
+            m.in = in;
+            uint32_t present = 0;
+            for (size_t h = 0; h < nr; ++h)
+            {
+                const size_t r = rot[i + h];
+                m.table[h] = tm.tables[r];
+                m.key[h] = tm.keys[r];
+                m.corr[h] = tm.corrs[r];
+                present |= hy_dot_column(o, tm, gs, ng, r, h);
+            }
+            m.d = hy_dims(c, L, alpha);
+            MOAI_TRY((dispatch<1, 2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
+                hipLaunchKernelGGL(hy_hoisted_dot_kernel<decltype(NR)::value>, grid, dim3(256), 0, s, m, o);
+                return MOAI_OK;
+            })));
+            MOAI_LAUNCH_CHECK();
+            o.seeded |= present;
+            i += nr;
+        }
+    }
+    else
+    {
+        // per rotation: permute, steps 1-4 into one scratch accumulator, then its products
+        for (size_t r : rot)
+        {
+            MOAI_TRY(moai_galois_permute(c, in, sc.gal, B * 2, L, tm.elts[r], s));
+            MOAI_TRY(hy_decompose(c, tab, { sc.gal, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
+            HyMacArgs m;
+            m.ext = sc.ext;
+            m.tgt = sc.gal;
+            m.key = tm.keys[r];
+            m.acc = sc.acc;
+            m.tgt_stride = (uint32_t)(2 * L);
+            m.tgt_off = (uint32_t)L;
+            m.d = hy_dims(c, L, alpha);
+            hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
+            MOAI_LAUNCH_CHECK();
+            MOAI_TRY(hy_dot_term(c, sc.acc, sc.gal, o, tm, gs, ng, r, L, alpha, B, s));
+        }
+    }
+    for (size_t r : ident)
+    {
+        MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, gs, ng, r, L, alpha, B, s));
+    }
+    return MOAI_OK;
+}
+
 // one chunk of B ciphertexts at `in` [B][2][L][N]; output g's result goes to tm.outs[g] + out_off.  sw: the outputs with a term whose
 // element is not 1, G of them in flight; the others (idn) are sums of plain products.  *fallback is set when INTT(c1) holds a zero
 // coefficient: the chunk then takes every rotation through the unhoisted steps 1-4 on the permuted input, to the same bits.
@@ -1194,16 +1427,13 @@ static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, con
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
     uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
-    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *gal = at_bytes(wsp, w.gal), *acc = at_bytes(wsp, w.acc);
+    const HyDotScratch sc = { at_bytes(wsp, w.t), at_bytes(wsp, w.ext), at_bytes(wsp, w.gal), at_bytes(wsp, w.acc) };
     uint64_t *S = at_bytes(wsp, w.S), *x = at_bytes(wsp, w.x), *conv = at_bytes(wsp, w.conv), *add = at_bytes(wsp, w.add);
-    const long per_pass = tuning(K_HYBRID_HOIST_NR);
-    dim3 grid;
-    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
     if (!sw.empty())
     {
         // steps 1-3 on the UNPERMUTED c1, once for all rotations and outputs
-        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, t, ext, s));
-        MOAI_TRY(probe_any_zero(c, t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
+        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
+        MOAI_TRY(probe_any_zero(c, sc.t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
     }
     MOAI_TRY(for_chunks(sw.size(), G, [&](size_t g0, size_t ng) {
         const size_t *gs = sw.data() + g0;
@@ -1211,67 +1441,7 @@ static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, con
         o.S = S;
         o.add = add;
         o.ng = (uint32_t)ng;
-        MOAI_HIP_CHECK(hipMemsetAsync(add, 0, ng * ct_words * sizeof(uint64_t), s));
-        std::vector<size_t> rot, ident; // the terms these outputs have
-        for (size_t r = 0; r < tm.R; ++r)
-        {
-            if (hy_dot_used(tm, gs, ng, r))
-            {
-                (tm.elts[r] == 1 ? ident : rot).push_back(r);
-            }
-        }
-        if (!*fallback)
-        {
-            // the hoisted MAC, MOAI_HYBRID_HOIST_NR rotations per pass over the digits, weighted into S and the addend
-            for (size_t i = 0; i < rot.size();)
-            {
-                const size_t left = rot.size() - i, nr = per_pass >= 4 && left >= 4 ? 4 : (per_pass >= 2 && left >= 2 ? 2 : 1);
-                HyHoistMacArgs m{};
-                m.ext = ext;
-                m.in = in;
-                uint32_t present = 0;
-                for (size_t h = 0; h < nr; ++h)
-                {
-                    const size_t r = rot[i + h];
-                    m.table[h] = tm.tables[r];
-                    m.key[h] = tm.keys[r];
-                    m.corr[h] = tm.corrs[r];
-                    present |= hy_dot_column(o, tm, gs, ng, r, h);
-                }
-                m.d = hy_dims(c, L, alpha);
-                MOAI_TRY((dispatch<1, 2, 4>("rotations per pass ", (int)nr, [&](auto NR) {
-                    hipLaunchKernelGGL(hy_hoisted_dot_kernel<decltype(NR)::value>, grid, dim3(256), 0, s, m, o);
-                    return MOAI_OK;
-                })));
-                MOAI_LAUNCH_CHECK();
-                o.seeded |= present;
-                i += nr;
-            }
-        }
-        else
-        {
-            // per rotation: permute, steps 1-4 into one scratch accumulator, then its products
-            for (size_t r : rot)
-            {
-                MOAI_TRY(moai_galois_permute(c, in, gal, B * 2, L, tm.elts[r], s));
-                MOAI_TRY(hy_decompose(c, tab, { gal, 2 * L, L }, L, alpha, B, t, ext, s));
-                HyMacArgs m;
-                m.ext = ext;
-                m.tgt = gal;
-                m.key = tm.keys[r];
-                m.acc = acc;
-                m.tgt_stride = (uint32_t)(2 * L);
-                m.tgt_off = (uint32_t)L;
-                m.d = hy_dims(c, L, alpha);
-                hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
-                MOAI_LAUNCH_CHECK();
-                MOAI_TRY(hy_dot_term(c, acc, gal, o, tm, gs, ng, r, L, alpha, B, s));
-            }
-        }
-        for (size_t r : ident)
-        {
-            MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, gs, ng, r, L, alpha, B, s));
-        }
+        MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs, ng, o, sc, L, alpha, B, *fallback, s));
         // step 5 once per output, over (output, ciphertext) pairs
         MOAI_TRY(hy_mod_down(c, tab, S, x, conv, L, alpha, ng * B, s));
         for (size_t h = 0; h < ng; ++h)
@@ -1297,6 +1467,194 @@ static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, con
         }
     }
     return MOAI_OK;
+}
+
+// ---- giant steps summed in the extended basis --------------------------------------------------------------------------------------
+// rows of N words of scratch: per ciphertext the inner stage's shared rows, the sum Z and the special rows and conv of its step 5; per
+// (giant step in flight, ciphertext) S and the addend, the special rows and conv of c1', the permuted c1' and its t and digits
+static inline size_t hy_bsgs_shared_rows(size_t L, size_t alpha)
+{
+    return hy_dot_shared_rows(L, alpha) + 2 * (L + alpha) + 2 * alpha + 2 * L;
+}
+
+static inline size_t hy_bsgs_giant_rows(size_t L, size_t alpha)
+{
+    return 2 * (L + alpha) + 2 * L + alpha + L + L + hy_beta(L, alpha) * (L + alpha);
+}
+
+struct HyBsgsLayout
+{
+    size_t flag, t, ext, gal, acc, Z, zx, zconv, S, add, x, conv, tgt, t2, ext2, total; // byte offsets
+};
+
+static HyBsgsLayout hy_bsgs_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
+{
+    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
+    HyBsgsLayout w;
+    w.flag = 0;
+    w.t = 256;
+    w.ext = w.t + align256(cb * L * row);
+    w.gal = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
+    w.acc = w.gal + align256(cb * 2 * L * row);
+    w.Z = w.acc + align256(cb * 2 * (L + alpha) * row);
+    w.zx = w.Z + align256(cb * 2 * (L + alpha) * row);
+    w.zconv = w.zx + align256(cb * 2 * alpha * row);
+    w.S = w.zconv + align256(cb * 2 * L * row);
+    w.add = w.S + align256(G * cb * 2 * (L + alpha) * row);
+    w.x = w.add + align256(G * cb * 2 * L * row);
+    w.conv = w.x + align256(G * cb * alpha * row);
+    w.tgt = w.conv + align256(G * cb * L * row);
+    w.t2 = w.tgt + align256(G * cb * L * row);
+    w.ext2 = w.t2 + align256(G * cb * L * row);
+    w.total = w.ext2 + align256(G * cb * (beta * (L + alpha) - L) * row);
+    return w;
+}
+
+// ciphertexts per chunk (*cb) and giant steps in flight (*G) under MOAI_HYBRID_TMP_KB.  A group of giant steps repeats the inner
+// stage's MAC over every baby step it uses while a batch chunk repeats nothing, so the giant steps come first: all of them (at most
+// HY_DOT_MAX_NG) are in flight when one ciphertext fits beside them, and cb is the largest count that fits with them; else one
+// ciphertext per chunk with as many giant steps as fit, at least one.  No row-per-workgroup grid above 65535 (the transforms run over
+// cb * G polynomials of at most 2 (L + alpha) rows), and the chunks of a batch are evened out.
+static void hy_bsgs_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t n_giant, size_t *cb_out, size_t *G_out)
+{
+    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
+    const size_t shared = hy_bsgs_shared_rows(L, alpha) * row, giant = hy_bsgs_giant_rows(L, alpha) * row;
+    const size_t cap = 65535 / (2 * (L + alpha));
+    size_t G = std::min(std::min(n_giant, (size_t)HY_DOT_MAX_NG), cap);
+    size_t cb = budget / (shared + G * giant);
+    if (cb < 1)
+    {
+        cb = 1;
+        G = budget > shared ? (budget - shared) / giant : 0;
+        G = G < 1 ? 1 : G;
+    }
+    cb = cb > cap / G ? cap / G : cb;
+    cb = cb < batch ? cb : batch;
+    const size_t chunks = (batch + cb - 1) / cb;
+    *cb_out = (batch + chunks - 1) / chunks;
+    *G_out = G;
+}
+
+struct HyBsgsGiants
+{
+    size_t n;
+    const uint32_t *elts;
+    const uint32_t *const *tables; // null where the element is 1
+    const uint64_t *const *keys;
+    const std::vector<char> *switched; // giant step g's inner sum has a term whose baby element is not 1
+};
+
+// one chunk of B ciphertexts at `in` [B][2][L][N] into out [B][2][L][N]; tm holds the baby terms with one output per giant step
+// (tm.outs unused), G giant steps in flight.  *fallback as in hy_dot_chunk_run: the inner stage's zero probe.
+static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, const HyDotTerms &tm, const HyBsgsGiants &gi, bool any_switched,
+                             size_t L, size_t alpha, size_t B, size_t cb, size_t G, bool *fallback, hipStream_t s)
+{
+    const size_t n = c->n, s_words = B * 2 * (L + alpha) * n;
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    const HyBsgsLayout w = hy_bsgs_layout(c, L, alpha, cb, G);
+    void *wsp;
+    MOAI_TRY(workspace(c, w.total, s, &wsp));
+    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
+    const HyDotScratch sc = { at_bytes(wsp, w.t), at_bytes(wsp, w.ext), at_bytes(wsp, w.gal), at_bytes(wsp, w.acc) };
+    uint64_t *Z = at_bytes(wsp, w.Z), *zx = at_bytes(wsp, w.zx), *zconv = at_bytes(wsp, w.zconv);
+    uint64_t *S = at_bytes(wsp, w.S), *add = at_bytes(wsp, w.add), *x = at_bytes(wsp, w.x), *conv = at_bytes(wsp, w.conv);
+    uint64_t *tgt = at_bytes(wsp, w.tgt), *t2 = at_bytes(wsp, w.t2), *ext2 = at_bytes(wsp, w.ext2);
+    if (any_switched)
+    {
+        // steps 1-3 on the UNPERMUTED c1, once for all baby steps and giant steps
+        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
+        MOAI_TRY(probe_any_zero(c, sc.t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
+    }
+    HyBsgsMacArgs m{};
+    m.ext = ext2;
+    m.tgt = tgt;
+    m.S = S;
+    m.add = add;
+    m.Z = Z;
+    m.d = hy_dims(c, L, alpha);
+    uint32_t special[HY_MAX_ALPHA];
+    for (size_t t = 0; t < alpha; ++t)
+    {
+        special[t] = (uint32_t)(c->k - alpha + t);
+    }
+    for (size_t i = 0; i < L; ++i)
+    {
+        m.fac[i] = hy_prod_mod(c, special, alpha, alpha, c->primes[i]);
+    }
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    MOAI_TRY(for_chunks(gi.n, G, [&](size_t g0, size_t ng) {
+        // the group's giant steps in the order the kernels index them: rotated ones whose c1' takes a mod-down, rotated ones whose
+        // inner sum has no switched term, then those of element 1 (a sum of canonical residues does not depend on the order)
+        std::vector<size_t> gs;
+        size_t n_md = 0, n_rot = 0;
+        for (int cls = 0; cls < 3; ++cls)
+        {
+            for (size_t g = g0; g < g0 + ng; ++g)
+            {
+                const int is = gi.elts[g] == 1 ? 2 : ((*gi.switched)[g] ? 0 : 1);
+                if (is == cls)
+                {
+                    gs.push_back(g);
+                }
+            }
+            n_md = cls == 0 ? gs.size() : n_md;
+            n_rot = cls == 1 ? gs.size() : n_rot;
+        }
+        HyDotOutputs o{};
+        o.S = S;
+        o.add = add;
+        o.ng = (uint32_t)ng;
+        MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs.data(), ng, o, sc, L, alpha, B, *fallback, s));
+        for (size_t h = 0; h < ng; ++h)
+        {
+            if (!((o.seeded >> h) & 1u))
+            {
+                MOAI_HIP_CHECK(hipMemsetAsync(S + h * s_words, 0, s_words * sizeof(uint64_t), s)); // no switched term: S_g = 0
+            }
+        }
+        if (n_rot)
+        {
+            if (n_md)
+            {
+                // step 5 of S_g[1] alone: the special rows of polynomial 1 of every (giant step, ciphertext) pair
+                RowMap rm{};
+                hy_rowmap(c, L, alpha, 0, L, &rm);
+                MOAI_TRY(ntt_launch(c, x, n_md * B, alpha, rm, true, s, S, 2 * (L + alpha), (L + alpha) + L));
+                MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + hy_beta(L, alpha), alpha, n_md * B, s));
+                MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+                MOAI_TRY(ntt_launch(c, conv, n_md * B, L, rm, false, s));
+            }
+            // tgt = perm_{E_g}(c1'_g), then steps 1-3 on all (giant step, ciphertext) pairs at once
+            HyC1Args a{};
+            a.S = S;
+            a.conv = conv;
+            a.add = add;
+            a.tgt = tgt;
+            a.pinv = tab->pinv;
+            a.n_md = (uint32_t)n_md;
+            a.B = (uint32_t)B;
+            a.d = m.d;
+            for (size_t h = 0; h < n_rot; ++h)
+            {
+                a.table[h] = m.table[h] = gi.tables[gs[h]];
+                m.key[h] = gi.keys[gs[h]];
+            }
+            MOAI_TRY(launch_rows(hy_c1_moddown_permute_kernel, c, n_rot * B * L, s, a));
+            MOAI_TRY(hy_decompose(c, tab, { tgt, L, 0 }, L, alpha, n_rot * B, t2, ext2, s));
+        }
+        m.n_rot = (uint32_t)n_rot;
+        m.ng = (uint32_t)ng;
+        m.zseeded = g0 ? 1u : 0u;
+        hipLaunchKernelGGL(hy_bsgs_mac_kernel, grid, dim3(256), 0, s, m);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    }));
+    // the one final step 5, both polynomials, no addend
+    MOAI_TRY(hy_mod_down(c, tab, Z, zx, zconv, L, alpha, B, s));
+    return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
 }
 
 } // namespace moai
@@ -1545,6 +1903,108 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
         const size_t off = b0 * 2 * L * n;
         bool fallback = false;
         MOAI_TRY(hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, cb, G, &fallback, s));
+        if (fallback && used_fallback)
+        {
+            *used_fallback = 1;
+        }
+        return MOAI_OK;
+    });
+}
+
+extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, size_t alpha, const uint32_t *baby_elts,
+                                    const uint64_t *const *baby_keys, const uint64_t *const *baby_corrections, size_t R,
+                                    const uint32_t *giant_elts, const uint64_t *const *giant_keys, size_t n_giant,
+                                    const uint64_t *const *plains, size_t batch, int *used_fallback, void *stream)
+{
+    MOAI_AUDIT(stream, in, out);
+    trace_op("hybrid_bsgs_dot", L, batch);
+    if (used_fallback)
+    {
+        *used_fallback = 0;
+    }
+    for (size_t r = 0; baby_elts && r < R; ++r)
+    {
+        MOAI_TRY(galois_elt_check(nullptr, baby_elts[r])); // oddness first: it needs no context
+    }
+    for (size_t g = 0; giant_elts && g < n_giant; ++g)
+    {
+        MOAI_TRY(galois_elt_check(nullptr, giant_elts[g]));
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (batch == 0)
+    {
+        return MOAI_OK;
+    }
+    if (R == 0 || n_giant == 0)
+    {
+        return set_error(MOAI_EINVAL, "R = %zu baby steps and %zu giant steps: a sum needs at least one of each", R, n_giant);
+    }
+    if (!in || !out || !plains || !baby_elts || !baby_keys || !baby_corrections || !giant_elts || !giant_keys)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t n = c->n, ct_bytes = batch * 2 * L * n * sizeof(uint64_t);
+    if (overlap(out, ct_bytes, in, ct_bytes))
+    {
+        return set_error(MOAI_EINVAL, "the output must not alias the input");
+    }
+    for (size_t r = 0; r < R; ++r)
+    {
+        MOAI_TRY(galois_elt_check(c, baby_elts[r]));
+        if (baby_elts[r] != 1 && (!baby_keys[r] || !baby_corrections[r]))
+        {
+            return set_error(MOAI_EINVAL, "null key or correction of baby step %zu", r);
+        }
+    }
+    std::vector<char> switched(n_giant, 0); // giant step g's inner sum has a term that is switched
+    bool any_switched = false;
+    for (size_t g = 0; g < n_giant; ++g)
+    {
+        MOAI_TRY(galois_elt_check(c, giant_elts[g]));
+        if (giant_elts[g] != 1 && !giant_keys[g])
+        {
+            return set_error(MOAI_EINVAL, "null key of giant step %zu", g);
+        }
+        bool any = false;
+        for (size_t r = 0; r < R; ++r)
+        {
+            if (plains[g * R + r])
+            {
+                any = true;
+                switched[g] = switched[g] || baby_elts[r] != 1;
+            }
+        }
+        if (!any)
+        {
+            return set_error(MOAI_EINVAL, "giant step %zu has no term", g);
+        }
+        any_switched = any_switched || switched[g];
+    }
+    MOAI_TRY(enter_device(c));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<const uint32_t *> baby_tables(R, nullptr), giant_tables(n_giant, nullptr);
+    for (size_t r = 0; r < R; ++r)
+    {
+        if (baby_elts[r] != 1)
+        {
+            MOAI_TRY(galois_table(c, baby_elts[r], &baby_tables[r])); // built before the first launch of the call
+        }
+    }
+    for (size_t g = 0; g < n_giant; ++g)
+    {
+        if (giant_elts[g] != 1)
+        {
+            MOAI_TRY(galois_table(c, giant_elts[g], &giant_tables[g]));
+        }
+    }
+    const HyDotTerms tm = { R, n_giant, baby_elts, baby_tables.data(), baby_keys, baby_corrections, plains, nullptr };
+    const HyBsgsGiants gi = { n_giant, giant_elts, giant_tables.data(), giant_keys, &switched };
+    size_t cb, G;
+    hy_bsgs_chunk(c, L, alpha, batch, n_giant, &cb, &G);
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        const size_t off = b0 * 2 * L * n;
+        bool fallback = false;
+        MOAI_TRY(hy_bsgs_chunk_run(c, in + off, out + off, tm, gi, any_switched, L, alpha, B, cb, G, &fallback, s));
         if (fallback && used_fallback)
         {
             *used_fallback = 1;

@@ -115,6 +115,7 @@ SYMBOLS = {
     "moai_hybrid_hoist_correction": (C.c_int, [vp, vp, C.c_uint32, sz, sz, vp, vp]),
     "moai_apply_galois_hybrid_hoisted": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_int), vp]),
     "moai_hybrid_rotate_pt_dot": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
+    "moai_hybrid_bsgs_dot": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -443,6 +444,23 @@ class Context:
         pp = (vp * (n_out * R))(*[_ptr(p) for row in plains for p in row])
         fb = C.c_int(0)
         _check(lib().moai_hybrid_rotate_pt_dot(self.h, _ptr(src), op, n_out, L, alpha, e, kp, cp, R, pp, batch, C.byref(fb), stream))
+        return bool(fb.value)
+
+    def hybrid_bsgs_dot(self, src, dst, L, alpha, baby_elts, baby_keys, baby_corrections, giant_elts, giant_keys, plains, batch,
+                        stream=None):
+        """dst = sum_g rotation giant_elts[g] of (sum_r plains[g][r] (*) rotation baby_elts[r] of src), everything summed in the
+        extended basis with one final mod-down (dst [batch][2][L][N]; plains: n_giant lists of R buffers [L+alpha][N] or None for an
+        absent term; keys and corrections may be None where the element is 1); returns True when a chunk's inner stage took the
+        unhoisted route (a zero coefficient in INTT(c1))"""
+        R, ng = len(baby_elts), len(giant_elts)
+        e = (C.c_uint32 * R)(*[int(x) for x in baby_elts])
+        kp = (vp * R)(*[_ptr(k) for k in baby_keys])
+        cp = (vp * R)(*[_ptr(k) for k in baby_corrections])
+        ge = (C.c_uint32 * ng)(*[int(x) for x in giant_elts])
+        gk = (vp * ng)(*[_ptr(k) for k in giant_keys])
+        pp = (vp * (ng * R))(*[_ptr(p) for row in plains for p in row])
+        fb = C.c_int(0)
+        _check(lib().moai_hybrid_bsgs_dot(self.h, _ptr(src), _ptr(dst), L, alpha, e, kp, cp, R, ge, gk, ng, pp, batch, C.byref(fb), stream))
         return bool(fb.value)
 
     def apply_galois_to(self, src, dst, L, elt, key, batch, stream=None):
