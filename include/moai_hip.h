@@ -903,6 +903,58 @@ int moai_hybrid_bsgs_dot(moai_ctx *ctx, const uint64_t *in, uint64_t *out /* [ba
                          const uint64_t *const *plains /* host array [n_giant * R], entry g * R + r, NULL = absent */, size_t batch,
                          int *used_fallback, void *stream);
 
+/* ---- hybrid relinearize + rescale: one mod-down by P and the last prime ---------------------------------------------------------------
+ * multiply -> relinearize -> rescale over hybrid keys is moai_relinearize_hybrid (a mod-down by P: per polynomial alpha inverse and L
+ * forward transforms) directly followed by moai_rescale (a divide-and-round by q_{L-1}: 1 inverse and L - 1 forward transforms, one
+ * more pass over the ciphertext).  Both divide by a product of primes of the basis and round, so the calls below take ONE mod-down
+ * by W = P q_{L-1} from the basis Q_L P straight to Q_{L-1}: 2L transforms fewer per ciphertext (305 -> 235 at L = 35, alpha = 12;
+ * 138 -> 108 at L = 15) and one elementwise pass over [2][L][N] less.  Opt-in like the rest of the hybrid sections; every other
+ * entry point keeps its bits.  `key` is a relinearization key (s^2 under s) in moai_hybrid_keygen's layout: no new key material.
+ *
+ * Definition of moai_relinearize_rescale_hybrid.  All residues canonical; notation and steps 1-4 are those of "hybrid key switching".
+ * Per ciphertext (c_0, c_1, c_2), steps 1-4 on the target c_2 give acc[p][row] over the L data rows and the alpha special rows.
+ * W = P q_{L-1}, H = floor(W / 2); the source base is S = {q_{L-1}, p_0, .., p_{alpha-1}}, alpha + 1 primes.  For p in {0, 1}:
+ *   lift     Z_p[i] = (acc[p][i] + (P mod q_i) c_p[i]) mod q_i for i < L;  Z_p[p_t] = acc[p][p_t]
+ *   inverse  x_m = INTT(Z_p[m]) for m in S (in the accumulator's row order [L data rows][alpha special rows] the contiguous rows
+ *            L-1 .. L+alpha-1)
+ *   scale    y_m = ((x_m + H mod m) mod m) [(W / m)^-1]_m mod m
+ *   convert  conv_i = ((sum_{m in S} y_m ((W / m) mod q_i)) - (H mod q_i)) mod q_i for i < L - 1, then forward NTT
+ *   finish   out[p][i] = (Z_p[i] - conv_i) [W^-1]_{q_i} mod q_i for i < L - 1
+ * (the device finishes with c_p[i] [q_{L-1}^-1]_{q_i} + (acc[p][i] - conv_i) [W^-1]_{q_i}, which is the same residue, so only row
+ * L - 1 is lifted before the inverse transform).  The result is bit for bit the integer restatement tests/hybrid_rescale_ref.py.
+ * As an integer, coefficientwise, out_p = floor((Z_p + H) / W) - u'_p, where the integer u'_p in [0, alpha] is the overflow of the
+ * fast conversion of alpha + 1 residues.  Three consequences:
+ *   Not the composition's bits.  The call is NOT bit-equal to moai_rescale(moai_relinearize_hybrid(ct3)).  In coefficient form each
+ *     coefficient of (out - composition) mod Q_{L-1}, centred, lies in [-(alpha + 1), +1]: the composition is round(X) + {-1, 0, 1}
+ *     because its own overflow u is divided by q_{L-1}, the merged form is round(X) - u'.
+ *   Noise.  With keys from moai_hybrid_keygen the centred value of q_{L-1} (out_0 + out_1 s) - (c_0 + c_1 s + c_2 s^2) mod Q_L is
+ *     at most  beta(L) N alpha 21 D_max / P  +  q_{L-1} (alpha + 1/2)(1 + |s|_1)  in absolute value.  After the division by q_{L-1} the
+ *     rounding term is (alpha + 1/2)(1 + |s|_1) where the composition's is about 1/2 (1 + |s|_1): the merged call buys its saved
+ *     transforms with up to alpha more units of rounding per coefficient, the size of what every hybrid rotation already adds at the
+ *     ciphertext's scale.
+ *   Preconditions.  L >= 2 (a prime must be left to rescale to) and alpha + 1 <= 16 (the conversion holds its sources in registers).
+ * moai_multiply_relin_rescale_hybrid is bit for bit moai_ct_multiply (moai_ct_square where y == x) followed by the call above; the
+ * three-polynomial product lives only in the chunk's scratch, 3L more rows per ciphertext, and never reaches caller memory.
+ *   ct3 [batch][3][L][N];  x, y [batch][2][L][N], y may be x;  out [batch][2][L-1][N];  inputs are never written.
+ * Nothing is enqueued and nothing written when an argument is refused: MOAI_EINVAL with a message for everything the hybrid entry
+ * points refuse, in their order (alpha = 0, L = 0, then L = 1 and alpha = 16, all answered before the context is touched; then a null
+ * context, alpha >= k, alpha > 16, L > k - alpha), a null pointer, `out` overlapping an input or the key.  batch = 0 is MOAI_OK.
+ * Scratch per ciphertext is beta (L + alpha) + 2 (L + alpha) + 2 (alpha + 1) + 2 (L - 1) rows of N words (3L more with the product)
+ * from the stream's workspace; a batch runs in chunks that fit MOAI_HYBRID_TMP_KB and results do not depend on the budget.  The
+ * first call at a new (L, alpha) builds that pair's constants with a blocking copy; otherwise neither call synchronises.
+ * moai_op_trace counts "relinearize_rescale_hybrid" (batch) and "multiply_relin_rescale_hybrid" (batch) at L, and none of the calls
+ * they replace. */
+/* Evaluator::relinearize_internal over the hybrid switch (SEAL/evaluator.cpp:2724-3020) merged with Evaluator::rescale_to_next
+ * (SEAL/evaluator.cpp:1682-1720 -> mod_switch_scale_to_next :1402-1481 -> RNSTool::divide_and_round_q_last_ntt_inplace
+ * SEAL/util/rns.cpp:830-901): one mod-down by P q_{L-1} */
+int moai_relinearize_rescale_hybrid(moai_ctx *ctx, const uint64_t *ct3 /* [batch][3][L][N] */, const uint64_t *key,
+                                    uint64_t *out /* [batch][2][L-1][N] */, size_t L, size_t alpha, size_t batch, void *stream);
+/* Evaluator::multiply (SEAL/evaluator.cpp:770-909; :1223-1282 where y == x), then the hybrid form of relinearize
+ * (SEAL/evaluator.cpp:2724-3020) merged with rescale_to_next (SEAL/evaluator.cpp:1682-1720, :1402-1481, SEAL/util/rns.cpp:830-901) */
+int moai_multiply_relin_rescale_hybrid(moai_ctx *ctx, const uint64_t *x, const uint64_t *y /* [batch][2][L][N], y may be x */,
+                                       const uint64_t *key, uint64_t *out /* [batch][2][L-1][N] */, size_t L, size_t alpha,
+                                       size_t batch, void *stream);
+
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is

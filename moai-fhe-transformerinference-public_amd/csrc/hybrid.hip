@@ -22,6 +22,10 @@
 // take one step 5 per sum; a whole baby-step / giant-step transform (moai_hybrid_bsgs_dot) stops that inner stage before its step 5,
 // takes only c1 of every inner sum down (hy_c1_moddown_permute_kernel), and sums the giant steps' digit-key products and the lifted
 // inner sums into one accumulator Z over Q P (hy_bsgs_mac_kernel) that takes the one final step 5.
+// Relinearize + rescale (moai_relinearize_rescale_hybrid) replaces step 5 and the rescale behind it by ONE mod-down by W = P q_{L-1}:
+// row L - 1 of the accumulator is lifted by (P mod q_{L-1}) c_p (hy_lift_last_row_kernel), rows L-1 .. L+alpha-1 are the conversion's
+// alpha + 1 sources, and hy_rescale_finalize_kernel carries the two multipliers W^-1 and q_{L-1}^-1; moai_multiply_relin_rescale_hybrid
+// forms the three-polynomial product in the chunk's scratch first (hy_ct_product_kernel).
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 #include <algorithm>
@@ -700,6 +704,111 @@ __global__ __launch_bounds__(256) void hy_key_add_kernel(HyKeyAddArgs g)
         c.x = csub(c.x + mulmod_barrett(v.x, fac, q, cr0, cr1), q);
         c.y = csub(c.y + mulmod_barrett(v.y, fac, q, cr0, cr1), q);
         dst[j] = c;
+    }
+}
+
+// ---- relinearize + rescale: one mod-down by W = P q_{L-1} (moai_relinearize_rescale_hybrid) ---------------------------------------
+// the constants of the merged mod-down at (L, alpha), a sibling of HyTable in the context's map of device blocks: sources
+// S = {q_{L-1}, p_0 .. p_{alpha-1}}, targets q_i, i < L - 1
+struct alignas(16) HyRescaleTable
+{
+    Tw winv[MOAI_MAX_RNS]; // W^-1 mod q_i
+    Tw qinv[MOAI_MAX_RNS]; // q_{L-1}^-1 mod q_i
+    HyConv conv;           // src_pre = floor(W / 2) mod m, tgt_post = floor(W / 2) mod q_i, src_inv = (W / m)^-1, w = (W / m) mod q_i
+};
+
+struct HyProductArgs
+{
+    const uint64_t *x, *y; // [B][2][L][N], y may be x
+    uint64_t *out;         // [B][3][L][N]
+    const PrimeConst *pc;
+    uint32_t L, n2;
+};
+
+// out[b] = (x0 y0, x0 y1 + x1 y0, x1 y1) under q_i; blockIdx.y = b * L + i.  The canonical residues of moai_ct_multiply, and of
+// moai_ct_square where y is x (x0 x1 + x1 x0 = 2 x0 x1).  The middle sum is two products below 2^122: below 2^123, one reduction.
+__global__ __launch_bounds__(256) void hy_ct_product_kernel(HyProductArgs g)
+{
+    const uint32_t b = blockIdx.y / g.L, i = blockIdx.y % g.L;
+    const PrimeConst *pc = g.pc + i;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = g.n2;
+    const ulonglong2 *x0 = reinterpret_cast<const ulonglong2 *>(g.x) + ((size_t)(b * 2) * g.L + i) * n2, *x1 = x0 + (size_t)g.L * n2;
+    const ulonglong2 *y0 = reinterpret_cast<const ulonglong2 *>(g.y) + ((size_t)(b * 2) * g.L + i) * n2, *y1 = y0 + (size_t)g.L * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + ((size_t)(b * 3) * g.L + i) * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    {
+        const ulonglong2 a0 = x0[j], a1 = x1[j], b0 = y0[j], b1 = y1[j];
+        uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
+        mac2(lx, hx, ly, hy, a0, b1);
+        mac2(lx, hx, ly, hy, a1, b0);
+        o[j] = mulmod2(a0, b0, q, cr0, cr1);
+        o[(size_t)g.L * n2 + j] = reduce2(lx, hx, ly, hy, q, cr0, cr1);
+        o[2 * (size_t)g.L * n2 + j] = mulmod2(a1, b1, q, cr0, cr1);
+    }
+}
+
+struct HyLiftArgs
+{
+    uint64_t *acc;       // [B][2][L + alpha][N]: row L - 1 of both polynomials is lifted in place
+    const uint64_t *ct3; // [B][3][L][N]: row L - 1 of c_0 and c_1 read
+    uint64_t plast;      // P mod q_{L-1}
+    HyDims d;
+};
+
+// Z_p[L-1] = acc[p][L-1] + (P mod q_{L-1}) c_p[L-1]: the one data row among the merged mod-down's sources; blockIdx.y = b * 2 + p.
+// The sum is one canonical residue (below 2^61) plus one product below 2^122: one reduction.
+__global__ __launch_bounds__(256) void hy_lift_last_row_kernel(HyLiftArgs g)
+{
+    const HyDims &d = g.d;
+    const uint32_t b = blockIdx.y >> 1, p = blockIdx.y & 1u, last = d.L - 1;
+    const PrimeConst *pc = d.pc + last;
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t n2 = d.n2;
+    ulonglong2 *acc = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)blockIdx.y * (d.L + d.alpha) + last) * n2;
+    const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + last) * n2;
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
+    {
+        uint64_t lx, hx, ly, hy;
+        seed2(lx, hx, ly, hy, acc[x]);
+        mac2(lx, hx, ly, hy, cp[x], g.plast);
+        acc[x] = reduce2(lx, hx, ly, hy, q, cr0, cr1);
+    }
+}
+
+struct HyRescaleFinalArgs
+{
+    const uint64_t *acc;  // [B][2][L + alpha][N]
+    const uint64_t *conv; // [2B][L - 1][N], NTT form
+    const uint64_t *ct3;  // [B][3][L][N]: c_0 and c_1 read
+    uint64_t *out;        // [B][2][L - 1][N]
+    const Tw *winv, *qinv;
+    HyDims d;
+};
+
+// out[b][p][i] = c_p[i] [q_{L-1}^-1]_{q_i} + (acc[p][i] - conv_i) [W^-1]_{q_i} mod q_i, i < L - 1: the finish of the merged mod-down
+// with the lift (P mod q_i) c_p[i] W^-1 = c_p[i] q_{L-1}^-1 taken on its own multiplier.  blockIdx.y = (b * 2 + p) (L - 1) + i.  No
+// 128-bit sum: two Shoup products made canonical and one canonical add.
+__global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(HyRescaleFinalArgs g)
+{
+    const HyDims &d = g.d;
+    const uint32_t lo = d.L - 1, poly = blockIdx.y / lo, i = blockIdx.y % lo, b = poly >> 1, p = poly & 1u;
+    const uint64_t q = d.pc[i].q;
+    const Tw wi = g.winv[i], qi = g.qinv[i];
+    const size_t n2 = d.n2;
+    const ulonglong2 *acc = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)poly * (d.L + d.alpha) + i) * n2;
+    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.conv) + (size_t)blockIdx.y * n2;
+    const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + i) * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
+    {
+        const ulonglong2 a = acc[x], v = u[x], c = cp[x];
+        ulonglong2 r, t;
+        r.x = csub(mul_shoup_lazy(a.x + q - v.x, wi.w, wi.wq, q), q);
+        r.y = csub(mul_shoup_lazy(a.y + q - v.y, wi.w, wi.wq, q), q);
+        t.x = csub(mul_shoup_lazy(c.x, qi.w, qi.wq, q), q);
+        t.y = csub(mul_shoup_lazy(c.y, qi.w, qi.wq, q), q);
+        o[x] = add2(r, t, q);
     }
 }
 
@@ -1657,6 +1766,212 @@ static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, con
     return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
 }
 
+// ---- relinearize + rescale --------------------------------------------------------------------------------------------------------
+// the merged mod-down's constants share the context's map with hy_table's blocks: the same (L, alpha) with this bit in alpha
+constexpr size_t HY_RESCALE_KEY = (size_t)1 << 32;
+
+// the device block of the merged mod-down's constants for (L, alpha), L >= 2 and alpha + 1 <= HY_MAX_ALPHA; the caller holds
+// op_mutex.  Built on first use with a blocking copy, as hy_table.
+static int hy_rescale_table(moai_ctx *c, size_t L, size_t alpha, const HyRescaleTable **out)
+{
+    const auto key = std::make_pair(L, alpha | HY_RESCALE_KEY);
+    auto it = c->hybrid_tables.find(key);
+    if (it != c->hybrid_tables.end())
+    {
+        *out = static_cast<const HyRescaleTable *>(it->second);
+        return MOAI_OK;
+    }
+    std::vector<unsigned char> host(sizeof(HyRescaleTable), 0);
+    HyRescaleTable *t = reinterpret_cast<HyRescaleTable *>(host.data());
+    HyConv &cv = t->conv;
+    const size_t k = c->k, last = L - 1;
+    cv.nsrc = (uint32_t)(alpha + 1);
+    cv.ntgt = (uint32_t)last;
+    cv.src_prime[0] = (uint32_t)last;
+    for (size_t s = 0; s < alpha; ++s)
+    {
+        cv.src_prime[1 + s] = (uint32_t)(k - alpha + s);
+    }
+    for (size_t r = 0; r < cv.nsrc; ++r)
+    {
+        const uint64_t m = c->primes[cv.src_prime[r]];
+        cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, cv.src_prime, cv.nsrc, r, m), m), m);
+        cv.src_pre[r] = hy_half_mod(0, m);
+    }
+    for (size_t i = 0; i < last; ++i)
+    {
+        const uint64_t q = c->primes[i];
+        const uint64_t w_mod_q = hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, q);
+        cv.tgt_prime[i] = (uint32_t)i;
+        cv.tgt_post[i] = hy_half_mod(w_mod_q, q);
+        for (size_t r = 0; r < cv.nsrc; ++r)
+        {
+            cv.w[i][r] = hy_prod_mod(c, cv.src_prime, cv.nsrc, r, q);
+        }
+        t->winv[i] = make_tw(hy_invmod(w_mod_q, q), q);
+        t->qinv[i] = make_tw(hy_invmod(c->primes[last] % q, q), q);
+    }
+    void *dev = nullptr;
+    MOAI_HIP_CHECK(hipMalloc(&dev, host.size()));
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        (void)hipFree(dev);
+        return set_error(MOAI_EHIP, "hybrid relinearize-rescale constants: %s", hipGetErrorString(e));
+    }
+    c->hybrid_tables[key] = dev;
+    *out = static_cast<const HyRescaleTable *>(dev);
+    return MOAI_OK;
+}
+
+// rows of N words of scratch per ciphertext: t, the converted digits, acc, the alpha + 1 source rows of the merged mod-down, conv
+// over L - 1 rows (and the three-polynomial product of moai_multiply_relin_rescale_hybrid)
+static size_t hy_rescale_rows_per_ct(size_t L, size_t alpha, bool product)
+{
+    const size_t beta = hy_beta(L, alpha);
+    return (product ? 3 * L : 0) + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * (alpha + 1) + 2 * (L - 1);
+}
+
+struct HyRescaleLayout
+{
+    size_t prod, t, ext, acc, x, conv, total; // byte offsets
+};
+
+static HyRescaleLayout hy_rescale_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, bool product)
+{
+    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
+    HyRescaleLayout w;
+    w.prod = 0;
+    w.t = w.prod + align256(product ? cb * 3 * L * row : 0);
+    w.ext = w.t + align256(cb * L * row);
+    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
+    w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
+    w.conv = w.x + align256(cb * 2 * (alpha + 1) * row);
+    w.total = w.conv + align256(cb * 2 * (L - 1) * row);
+    return w;
+}
+
+// ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one; no row-per-workgroup grid above 65535 (the widest runs
+// over 3 * cb * L rows with the product, 2 * cb * (L + alpha) without)
+static size_t hy_rescale_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, bool product)
+{
+    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
+    const size_t per = hy_rescale_rows_per_ct(L, alpha, product) * c->n * sizeof(uint64_t);
+    size_t cb = budget / per;
+    cb = cb < 1 ? 1 : cb;
+    const size_t cap = 65535 / std::max(2 * (L + alpha), 3 * L);
+    cb = cb > cap ? cap : cb;
+    return cb < batch ? cb : batch;
+}
+
+// one chunk of B ciphertexts: out [B][2][L - 1][N] = the merged mod-down of (c0, c1) + switch(c2) for ct3 [B][3][L][N]
+static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescaleTable *rt, const uint64_t *ct3, const uint64_t *key,
+                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyRescaleLayout &w, hipStream_t s)
+{
+    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
+    uint64_t *conv = at_bytes(wsp, w.conv);
+    // steps 1-4 on c2, as every switch
+    MOAI_TRY(hy_decompose(c, tab, { ct3, 3 * L, 2 * L }, L, alpha, B, t, ext, s));
+    HyMacArgs m;
+    m.ext = ext;
+    m.tgt = ct3;
+    m.key = key;
+    m.acc = acc;
+    m.tgt_stride = (uint32_t)(3 * L);
+    m.tgt_off = (uint32_t)(2 * L);
+    m.d = hy_dims(c, L, alpha);
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
+    MOAI_LAUNCH_CHECK();
+    // the lift of the one data row among the sources (the rows below it take theirs in the last kernel)
+    HyLiftArgs lf;
+    lf.acc = acc;
+    lf.ct3 = ct3;
+    lf.d = m.d;
+    uint32_t special[HY_MAX_ALPHA];
+    for (size_t sp = 0; sp < alpha; ++sp)
+    {
+        special[sp] = (uint32_t)(c->k - alpha + sp);
+    }
+    lf.plast = hy_prod_mod(c, special, alpha, alpha, c->primes[L - 1]);
+    MOAI_TRY(launch_rows(hy_lift_last_row_kernel, c, 2 * B, s, lf));
+    // the merged mod-down: x = INTT(rows L-1 .. L+alpha-1 of acc, contiguous), conv = NTT(base conversion with W's rounding terms)
+    RowMap rm{};
+    hy_rowmap(c, L, alpha, 0, L - 1, &rm);
+    MOAI_TRY(ntt_launch(c, x, 2 * B, alpha + 1, rm, true, s, acc, L + alpha, L - 1));
+    MOAI_TRY(hy_convert(c, x, alpha + 1, 0, conv, &rt->conv, alpha + 1, 2 * B, s));
+    MOAI_TRY(make_rowmap(c, L - 1, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, conv, 2 * B, L - 1, rm, false, s));
+    HyRescaleFinalArgs f;
+    f.acc = acc;
+    f.conv = conv;
+    f.ct3 = ct3;
+    f.out = out;
+    f.winv = rt->winv; // device address arithmetic only
+    f.qinv = rt->qinv;
+    f.d = m.d;
+    return launch_rows(hy_rescale_finalize_kernel, c, 2 * B * (L - 1), s, f);
+}
+
+// the two entry points: validated, then chunk by chunk on the stream's workspace
+//   y null:  x = ct3 [batch][3][L][N]
+//   y set:   x, y [batch][2][L][N] (y may be x); their product lives in the chunk's workspace
+static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, bool product, const uint64_t *key, uint64_t *out, size_t L,
+                            size_t alpha, size_t batch, void *stream)
+{
+    // what needs no context first, in hy_check's order: alpha = 0 and L = 0 are its own
+    if (alpha != 0 && L == 1)
+    {
+        return set_error(MOAI_EINVAL, "L = 1: no prime left to rescale to");
+    }
+    if (alpha == HY_MAX_ALPHA && L != 0)
+    {
+        return set_error(MOAI_EINVAL, "alpha = %zu: the merged mod-down converts alpha + 1 residues, at most %u", alpha, HY_MAX_ALPHA);
+    }
+    MOAI_TRY(hy_check(c, alpha, L, true));
+    if (batch == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!x || (product && !y) || !key || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    const size_t n = c->n, row = n * sizeof(uint64_t);
+    const size_t out_bytes = batch * 2 * (L - 1) * row, in_bytes = batch * (product ? 2 : 3) * L * row;
+    const size_t key_bytes = hy_beta(c->k - alpha, alpha) * 2 * c->k * row;
+    if (overlap(out, out_bytes, x, in_bytes) || (product && overlap(out, out_bytes, y, in_bytes)) || overlap(out, out_bytes, key, key_bytes))
+    {
+        return set_error(MOAI_EINVAL, "the output must not overlap an input");
+    }
+    MOAI_TRY(enter_device(c));
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    const HyRescaleTable *rt;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
+    const size_t cb = hy_rescale_chunk(c, L, alpha, batch, product);
+    const HyRescaleLayout w = hy_rescale_layout(c, L, alpha, cb, product);
+    void *wsp;
+    MOAI_TRY(workspace(c, w.total, s, &wsp));
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        const uint64_t *ct3 = x + b0 * 3 * L * n;
+        if (product)
+        {
+            HyProductArgs g;
+            g.x = x + b0 * 2 * L * n;
+            g.y = y + b0 * 2 * L * n;
+            g.out = at_bytes(wsp, w.prod);
+            fill_rows(g, c, L);
+            MOAI_TRY(launch_rows(hy_ct_product_kernel, c, B * L, s, g));
+            ct3 = g.out;
+        }
+        return hy_rescale_chunk_run(c, tab, rt, ct3, key, out + b0 * 2 * (L - 1) * n, L, alpha, B, wsp, w, s);
+    });
+}
+
 } // namespace moai
 
 using namespace moai;
@@ -2011,4 +2326,20 @@ extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *o
         }
         return MOAI_OK;
     });
+}
+
+extern "C" int moai_relinearize_rescale_hybrid(moai_ctx *c, const uint64_t *ct3, const uint64_t *key, uint64_t *out, size_t L, size_t alpha,
+                                               size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, ct3, key, out);
+    trace_op("relinearize_rescale_hybrid", L, batch);
+    return hy_rescale_entry(c, ct3, nullptr, false, key, out, L, alpha, batch, stream);
+}
+
+extern "C" int moai_multiply_relin_rescale_hybrid(moai_ctx *c, const uint64_t *x, const uint64_t *y, const uint64_t *key, uint64_t *out,
+                                                  size_t L, size_t alpha, size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, x, y, key, out);
+    trace_op("multiply_relin_rescale_hybrid", L, batch);
+    return hy_rescale_entry(c, x, y, true, key, out, L, alpha, batch, stream);
 }

@@ -116,6 +116,8 @@ SYMBOLS = {
     "moai_apply_galois_hybrid_hoisted": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_int), vp]),
     "moai_hybrid_rotate_pt_dot": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
     "moai_hybrid_bsgs_dot": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
+    "moai_relinearize_rescale_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
+    "moai_multiply_relin_rescale_hybrid": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -400,6 +402,15 @@ class Context:
 
     def relinearize_hybrid(self, ct3, key, out, L, alpha, batch, stream=None):
         _check(lib().moai_relinearize_hybrid(self.h, _ptr(ct3), _ptr(key), _ptr(out), L, alpha, batch, stream))
+
+    def relinearize_rescale_hybrid(self, ct3, key, out, L, alpha, batch, stream=None):
+        """out [batch][2][L-1][N] = relinearize_hybrid + rescale of ct3 [batch][3][L][N] with ONE mod-down by P q_{L-1} (its own
+        documented rounding, not the composition's bits)"""
+        _check(lib().moai_relinearize_rescale_hybrid(self.h, _ptr(ct3), _ptr(key), _ptr(out), L, alpha, batch, stream))
+
+    def multiply_relin_rescale_hybrid(self, x, y, key, out, L, alpha, batch, stream=None):
+        """ct_multiply (ct_square where y is x) followed by relinearize_rescale_hybrid; the product stays in scratch"""
+        _check(lib().moai_multiply_relin_rescale_hybrid(self.h, _ptr(x), _ptr(y), _ptr(key), _ptr(out), L, alpha, batch, stream))
 
     def apply_galois_hybrid(self, ct, L, alpha, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois_hybrid(self.h, _ptr(ct), L, alpha, int(elt), _ptr(key), batch, stream))
