@@ -955,6 +955,65 @@ int moai_multiply_relin_rescale_hybrid(moai_ctx *ctx, const uint64_t *x, const u
                                        const uint64_t *key, uint64_t *out /* [batch][2][L-1][N] */, size_t L, size_t alpha,
                                        size_t batch, void *stream);
 
+/* ---- hybrid key switches on a list of ciphertexts, each with its own key and element ---------------------------------------------------
+ * What "Key switches on a LIST of single ciphertexts" (moai_apply_galois_ptrs, moai_relinearize_ptrs) is to the SEAL-style switch,
+ * for hybrid keys: every hybrid entry point above takes ONE contiguous block [batch][..], one key and one Galois element, while the
+ * differently rotated ciphertexts of MOAI's OpenMP loops (include/source/matrix_mul/Ct_ct_matrix_mul.hpp:22-31, 84-102, 142-149) sit
+ * each in its own block with its own element and key.  The list forms are the n single calls at batch 1 in one chain of launches,
+ * and the out-of-place and accumulating rotations are the same last kernel with an output pointer and a second addend.  All five
+ * are bit for bit the calls they stand for: no restatement changes (tests/hybrid_ref.py, tests/hybrid_rescale_ref.py), and at
+ * alpha = 1 moai_apply_galois_hybrid_ptrs and moai_relinearize_hybrid_ptrs are bit for bit moai_apply_galois_ptrs and
+ * moai_relinearize_ptrs.  Opt-in like the rest of the hybrid sections; every other entry point keeps its bits.
+ *   Keys: moai_hybrid_keygen's whole layout [beta(k-alpha)][2][k][N] only.
+ *   Lists (ins / ct3s / outs / keys / sums / galois_elts): HOST arrays of n entries, read before the call returns; the pointer lists
+ *     reach the device as kernel arguments, never through a host-to-device copy.  sums may be NULL, and so may any sums[i].
+ *   Aliasing, as moai_apply_galois_ptrs: outs[i] may be ins[i] or sums[i] exactly; it may never be a part of ins[i] or sums[i], and
+ *     never touch a block of another member; sums[i] may not be ins[i].  For the two relinearize forms the output may not be the
+ *     input.  An output block of moai_relinearize_rescale_hybrid_ptrs is 2 (L - 1) N words.  Inputs, sums that are not outputs, and
+ *     keys are only read.
+ *   Refusals: everything is validated before anything is enqueued and nothing is written on refusal; MOAI_EINVAL, in this order:
+ *     n == 0 is MOAI_OK whatever else is passed; "null list"; "member i: null pointer" or "member i: Galois element is not valid"
+ *     (an even element); then what the hybrid entry points refuse, in their order and words (alpha = 0, L = 0, null context,
+ *     alpha >= k, alpha > 16, L > k - alpha; the rescale form also L = 1 and alpha = 16, where moai_relinearize_rescale_hybrid
+ *     answers them); then "member i: ..." for an element >= 2N and for the overlaps.  moai_apply_galois_hybrid_to / _acc refuse
+ *     what moai_apply_galois_hybrid does, in its order, then a null pointer, `in` == `acc`, and any overlap of `out` with `in` (or
+ *     of `acc` with `in`) other than out == in.
+ *   Passes: a pass takes min(64, the chunk MOAI_HYBRID_TMP_KB allows) members, at least one.  Scratch per member, in rows of N
+ *     words from the stream's workspace: the rotation beta (L + alpha) + 4L + 4 alpha + 2L (the permuted member; the same as a
+ *     ciphertext of moai_apply_galois_hybrid), moai_relinearize_hybrid_ptrs beta (L + alpha) + 4L + 4 alpha + L (the gathered third
+ *     polynomial), moai_relinearize_rescale_hybrid_ptrs beta (L + alpha) + 2 (L + alpha) + 2 (alpha + 1) + 2 (L - 1) + L; beta =
+ *     ceil(L / alpha).  Results depend on neither the budget nor n.
+ *   No call synchronises beyond the first-use builds of "hybrid key switching" (the constants of a new (L, alpha), the table of a
+ *     new Galois element).  moai_op_trace counts the calls they replace: "apply_galois_hybrid", "relinearize_hybrid" and
+ *     "relinearize_rescale_hybrid", n (or batch) units at L. */
+/* Evaluator::apply_galois (SEAL/evaluator.cpp:2563-2665 with a `destination`, SEAL/evaluator.h:1093-1101) over the hybrid switch
+ * (SEAL/evaluator.cpp:2724-3020): moai_apply_galois_hybrid on a copy of `in`, without the copy.  in, out [batch][2][L][N]; out may be
+ * in, and moai_apply_galois_hybrid is this call with out == in. */
+int moai_apply_galois_hybrid_to(moai_ctx *ctx, const uint64_t *in, uint64_t *out, size_t L, size_t alpha, uint32_t galois_elt,
+                                const uint64_t *key, size_t batch, void *stream);
+/* acc = add_inplace(acc, apply_galois(in)) (SEAL/evaluator.cpp:2563-2665 over the hybrid switch SEAL/evaluator.cpp:2724-3020), as
+ * moai_apply_galois_acc: the bits of moai_apply_galois_hybrid_to followed by moai_add, canonical residues; the addition rides on the
+ * last kernel's second addend.  in, acc [batch][2][L][N], distinct. */
+int moai_apply_galois_hybrid_acc(moai_ctx *ctx, const uint64_t *in, uint64_t *acc, size_t L, size_t alpha, uint32_t galois_elt,
+                                 const uint64_t *key, size_t batch, void *stream);
+/* outs[i] = [sums[i] +] moai_apply_galois_hybrid(copy of ins[i], galois_elts[i], keys[i]), i < n: n calls of
+ * moai_apply_galois_hybrid_to / _acc at batch 1 (Evaluator::apply_galois_inplace, SEAL/evaluator.cpp:2563-2665, over the hybrid
+ * switch SEAL/evaluator.cpp:2724-3020) in one chain of launches per pass.  Each member [2][L][N]. */
+int moai_apply_galois_hybrid_ptrs(moai_ctx *ctx, const uint64_t *const *ins, uint64_t *const *outs, size_t L, size_t alpha,
+                                  const uint32_t *galois_elts, const uint64_t *const *keys,
+                                  const uint64_t *const *sums /* NULL, or entries may be NULL */, size_t n, void *stream);
+/* outs[i] = moai_relinearize_hybrid(ct3s[i]) with one key: n calls at batch 1 (Evaluator::relinearize_internal,
+ * SEAL/evaluator.cpp:1345-1400, over the hybrid switch SEAL/evaluator.cpp:2724-3020) in one chain of launches per pass.  ct3s[i]
+ * [3][L][N], outs[i] [2][L][N]. */
+int moai_relinearize_hybrid_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *key, size_t L,
+                                 size_t alpha, size_t n, void *stream);
+/* outs[i] = moai_relinearize_rescale_hybrid(ct3s[i]) with one key: n calls at batch 1 (Evaluator::relinearize_internal,
+ * SEAL/evaluator.cpp:1345-1400, over the hybrid switch SEAL/evaluator.cpp:2724-3020, merged with Evaluator::rescale_to_next,
+ * SEAL/evaluator.cpp:1682-1720) in one chain of launches per pass; that call's documented rounding carries over unchanged.  ct3s[i]
+ * [3][L][N], outs[i] [2][L-1][N]; L >= 2. */
+int moai_relinearize_rescale_hybrid_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uint64_t *const *outs /* [2][L-1][N] */,
+                                         const uint64_t *key, size_t L, size_t alpha, size_t n, void *stream);
+
 /* ---- stream audit (debug) ----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is

@@ -26,6 +26,10 @@
 // row L - 1 of the accumulator is lifted by (P mod q_{L-1}) c_p (hy_lift_last_row_kernel), rows L-1 .. L+alpha-1 are the conversion's
 // alpha + 1 sources, and hy_rescale_finalize_kernel carries the two multipliers W^-1 and q_{L-1}^-1; moai_multiply_relin_rescale_hybrid
 // forms the three-polynomial product in the chunk's scratch first (hy_ct_product_kernel).
+// The list forms (moai_apply_galois_hybrid_ptrs, moai_relinearize_hybrid_ptrs, moai_relinearize_rescale_hybrid_ptrs) gather a pass of
+// single ciphertexts, each in its own block, into that same scratch (galois_gather_list) and run the chain above on it; the kernels
+// that read a member's key or touch a caller's block (hy_mac_kernel, moddown_finalize, hy_lift_last_row_kernel,
+// hy_rescale_finalize_kernel) have a LIST instantiation that takes those pointers from the pass's KsList record.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 #include <algorithm>
@@ -169,9 +173,17 @@ struct HyMacArgs
     HyDims d;
 };
 
+struct HyMacListArgs : HyMacArgs
+{
+    const KsList *lst; // ciphertext b's key is lst->keys[b], in the same whole layout (key unused)
+};
+
 // acc[b][p][row] = sum_{j < beta} digit_j[row] (*) key[j][p][row]; blockIdx.x = b (the workgroups that read the same key words
 // are dispatched together), blockIdx.z = row.  At most 63 products below 2^122 per sum: no fold before the one reduction.
-__global__ __launch_bounds__(256) void hy_mac_kernel(HyMacArgs g)
+// LIST: every ciphertext of the batch has its own key (KsList).  The ciphertext index is uniform over the workgroup, so the list
+// entry arrives through a scalar load; the digits and the accumulators stay in the pass's contiguous scratch.
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void hy_mac_kernel(std::conditional_t<LIST, HyMacListArgs, HyMacArgs> g)
 {
     const HyDims &d = g.d;
     const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
@@ -182,6 +194,10 @@ __global__ __launch_bounds__(256) void hy_mac_kernel(HyMacArgs g)
     const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
     const ulonglong2 *tgt = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)b * g.tgt_stride + g.tgt_off) * n2;
     const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + (size_t)prime * n2;
+    if constexpr (LIST)
+    {
+        key = reinterpret_cast<const ulonglong2 *>(g.lst->keys[b]) + (size_t)prime * n2;
+    }
     ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (d.L + d.alpha) + row) * n2;
     ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (d.L + d.alpha) + row) * n2;
     for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
@@ -756,9 +772,16 @@ struct HyLiftArgs
     HyDims d;
 };
 
+struct HyLiftListArgs : HyLiftArgs
+{
+    const KsList *lst; // ciphertext b's [3][L][N] block is lst->ins[b] (ct3 unused)
+};
+
 // Z_p[L-1] = acc[p][L-1] + (P mod q_{L-1}) c_p[L-1]: the one data row among the merged mod-down's sources; blockIdx.y = b * 2 + p.
 // The sum is one canonical residue (below 2^61) plus one product below 2^122: one reduction.
-__global__ __launch_bounds__(256) void hy_lift_last_row_kernel(HyLiftArgs g)
+// LIST: c_p is read from the member's own block; b is uniform over the workgroup (a scalar load of the list entry).
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void hy_lift_last_row_kernel(std::conditional_t<LIST, HyLiftListArgs, HyLiftArgs> g)
 {
     const HyDims &d = g.d;
     const uint32_t b = blockIdx.y >> 1, p = blockIdx.y & 1u, last = d.L - 1;
@@ -767,6 +790,10 @@ __global__ __launch_bounds__(256) void hy_lift_last_row_kernel(HyLiftArgs g)
     const size_t n2 = d.n2;
     ulonglong2 *acc = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)blockIdx.y * (d.L + d.alpha) + last) * n2;
     const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + last) * n2;
+    if constexpr (LIST)
+    {
+        cp = reinterpret_cast<const ulonglong2 *>(g.lst->ins[b]) + ((size_t)p * d.L + last) * n2;
+    }
     for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
     {
         uint64_t lx, hx, ly, hy;
@@ -786,10 +813,17 @@ struct HyRescaleFinalArgs
     HyDims d;
 };
 
+struct HyRescaleFinalListArgs : HyRescaleFinalArgs
+{
+    const KsList *lst; // ciphertext b's [3][L][N] block is lst->ins[b] and its [2][L - 1][N] result lst->outs[b] (ct3 and out unused)
+};
+
 // out[b][p][i] = c_p[i] [q_{L-1}^-1]_{q_i} + (acc[p][i] - conv_i) [W^-1]_{q_i} mod q_i, i < L - 1: the finish of the merged mod-down
 // with the lift (P mod q_i) c_p[i] W^-1 = c_p[i] q_{L-1}^-1 taken on its own multiplier.  blockIdx.y = (b * 2 + p) (L - 1) + i.  No
 // 128-bit sum: two Shoup products made canonical and one canonical add.
-__global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(HyRescaleFinalArgs g)
+// LIST: c_p and the output per member, as hy_lift_last_row_kernel.
+template <bool LIST = false>
+__global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(std::conditional_t<LIST, HyRescaleFinalListArgs, HyRescaleFinalArgs> g)
 {
     const HyDims &d = g.d;
     const uint32_t lo = d.L - 1, poly = blockIdx.y / lo, i = blockIdx.y % lo, b = poly >> 1, p = poly & 1u;
@@ -800,6 +834,11 @@ __global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(HyRescaleFinal
     const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.conv) + (size_t)blockIdx.y * n2;
     const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + i) * n2;
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
+    if constexpr (LIST)
+    {
+        cp = reinterpret_cast<const ulonglong2 *>(g.lst->ins[b]) + ((size_t)p * d.L + i) * n2;
+        o = reinterpret_cast<ulonglong2 *>(g.lst->outs[b]) + ((size_t)p * lo + i) * n2;
+    }
     for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
     {
         const ulonglong2 a = acc[x], v = u[x], c = cp[x];
@@ -973,12 +1012,12 @@ static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_
                                     [&](auto A) { return launch_rows(hy_convert_kernel<decltype(A)::value>, c, polys, s, a); });
 }
 
-// rows of N words of scratch per ciphertext: t, the converted digits, acc, the special rows, conv (and the permuted input of
-// apply_galois)
-static size_t hy_rows_per_ct(size_t L, size_t alpha, bool galois)
+// rows of N words of scratch per ciphertext: t, the converted digits, acc, the special rows, conv, and gal_rows rows of gathered
+// input (2 L: the permuted input of apply_galois; L: the third polynomial of a member of the relinearize list; 0 otherwise)
+static size_t hy_rows_per_ct(size_t L, size_t alpha, size_t gal_rows)
 {
     const size_t beta = hy_beta(L, alpha);
-    return (galois ? 2 * L : 0) + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * alpha + 2 * L;
+    return gal_rows + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * alpha + 2 * L;
 }
 
 struct HyLayout
@@ -986,12 +1025,12 @@ struct HyLayout
     size_t gal, t, ext, acc, x, conv, total; // byte offsets
 };
 
-static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, bool galois)
+static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t gal_rows)
 {
     const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
     HyLayout w;
     w.gal = 0;
-    w.t = w.gal + align256(galois ? cb * 2 * L * row : 0);
+    w.t = w.gal + align256(cb * gal_rows * row);
     w.ext = w.t + align256(cb * L * row);
     w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
     w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
@@ -1001,10 +1040,10 @@ static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, 
 }
 
 // ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one
-static size_t hy_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, bool galois)
+static size_t hy_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t gal_rows)
 {
     const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
-    const size_t per = hy_rows_per_ct(L, alpha, galois) * c->n * sizeof(uint64_t);
+    const size_t per = hy_rows_per_ct(L, alpha, gal_rows) * c->n * sizeof(uint64_t);
     size_t cb = budget / per;
     cb = cb < 1 ? 1 : cb;
     // row-per-workgroup launches: 2 * cb * (L + alpha) rows in gridDim.y
@@ -1057,7 +1096,21 @@ static int hy_mac_grid(const moai_ctx *c, size_t B, size_t rows, dim3 *grid)
     return MOAI_OK;
 }
 
-// one chunk of B ciphertexts: out [B][2][L][N] = add (KsAddend) + the switch of the target rows tg
+// step 4 for B ciphertexts with the key m.key or, with a list, member b's own
+static int hy_mac(moai_ctx *c, const HyMacArgs &m, size_t B, const KsList *lst, hipStream_t s)
+{
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, m.d.L + m.d.alpha, &grid));
+    return plain_or_list<HyMacListArgs>(m, lst, [&](const auto &args, auto LIST) {
+        hipLaunchKernelGGL(hy_mac_kernel<decltype(LIST)::value>, grid, dim3(256), 0, s, args);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
+}
+
+// one chunk of B ciphertexts: out [B][2][L][N] = add (KsAddend) + the switch of the target rows tg.  With tg.lst (a device record,
+// common.h KsList) ciphertext b's key is lst->keys[b] and the last kernel writes lst->outs[b], adds lst->sums[b] and, for add.mode 1,
+// reads the addend from lst->ins[b]; key and out are not used
 static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
                            size_t B, void *wsp, const HyLayout &w, const KsAddend &add, hipStream_t s)
 {
@@ -1074,13 +1127,10 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
     m.tgt_stride = (uint32_t)tg.stride_rows;
     m.tgt_off = (uint32_t)tg.off_rows;
     m.d = hy_dims(c, L, alpha);
-    dim3 grid;
-    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
-    hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY(hy_mac(c, m, B, tg.lst, s));
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
     MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, B, s));
-    return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, nullptr, s);
+    return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, tg.lst, s);
 }
 
 // what every hybrid entry point refuses, in the order the header gives: first what needs no context
@@ -1123,9 +1173,10 @@ enum
 // the three switches: validated, then chunk by chunk on the stream's workspace
 //   HY_SWITCH  io = ct [batch][2][L][N] in place, in = target [batch][L][N]
 //   HY_RELIN   in = ct3 [batch][3][L][N], io = out [batch][2][L][N]
-//   HY_GALOIS  io = ct [batch][2][L][N] in place
+//   HY_GALOIS  in [batch][2][L][N], io = out [batch][2][L][N], which may be in itself; sum: null, or [batch][2][L][N] added by the last
+//              kernel (it may be io, never in)
 static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, const uint64_t *key, size_t L, size_t alpha, uint32_t elt,
-                    size_t batch, void *stream)
+                    size_t batch, void *stream, const uint64_t *sum = nullptr)
 {
     // every kind but HY_GALOIS comes with element 1; an even element is refused before the context is looked at
     MOAI_TRY(galois_elt_check(nullptr, elt));
@@ -1135,13 +1186,25 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
     {
         return MOAI_OK;
     }
-    if (!io || !key || (kind != HY_GALOIS && !in) || (kind == HY_RELIN && in == io))
+    if (!io || !key || !in || (kind == HY_RELIN && in == io))
     {
         return set_error(MOAI_EINVAL, kind == HY_RELIN ? "bad pointers" : "null argument");
     }
+    const size_t n = c->n;
+    if (kind == HY_GALOIS)
+    {
+        const size_t bytes = batch * 2 * L * n * sizeof(uint64_t);
+        if (sum && sum == in)
+        {
+            return set_error(MOAI_EINVAL, "null argument, or the sum is the input"); // as moai_apply_galois_acc
+        }
+        if ((io != in && overlap(io, bytes, in, bytes)) || (sum && sum != io && overlap(io, bytes, sum, bytes)))
+        {
+            return set_error(MOAI_EINVAL, "the output overlaps an input");
+        }
+    }
     MOAI_TRY(enter_device(c));
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = c->n;
     const uint32_t *table = nullptr;
     if (kind == HY_GALOIS)
     {
@@ -1150,8 +1213,9 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     const HyTable *tab;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
-    const size_t cb = hy_chunk(c, L, alpha, batch, kind == HY_GALOIS);
-    const HyLayout w = hy_layout(c, L, alpha, cb, kind == HY_GALOIS);
+    const size_t gal_rows = kind == HY_GALOIS ? 2 * L : 0;
+    const size_t cb = hy_chunk(c, L, alpha, batch, gal_rows);
+    const HyLayout w = hy_layout(c, L, alpha, cb, gal_rows);
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
     return for_chunks(batch, cb, [&](size_t b0, size_t B) {
@@ -1167,10 +1231,12 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
                                    { in + b0 * 3 * L * n, 3 * L, 1 }, s);
         default:
         {
-            // ct = (galois(c0), 0) + switch(galois(c1))      (evaluator.cpp:2631-2654)
+            // out = (galois(in0), 0) + switch(galois(in1)) [+ sum]      (evaluator.cpp:2631-2654): both summands are added by the last
+            // kernel, so a chunk of out is written once, after the chunk of in has been permuted into the scratch
             uint64_t *tmp = at_bytes(wsp, w.gal);
-            MOAI_TRY(moai_galois_permute(c, io + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
-            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { tmp, 2 * L, L }, key, L, alpha, B, wsp, w, { tmp, 2 * L, 2 }, s);
+            MOAI_TRY(moai_galois_permute(c, in + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
+            return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { tmp, 2 * L, L }, key, L, alpha, B, wsp, w,
+                                   { tmp, 2 * L, 2, sum ? sum + b0 * 2 * L * n : nullptr }, s);
         }
         }
     });
@@ -1509,7 +1575,7 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
             m.tgt_stride = (uint32_t)(2 * L);
             m.tgt_off = (uint32_t)L;
             m.d = hy_dims(c, L, alpha);
-            hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
+            hipLaunchKernelGGL(hy_mac_kernel<false>, grid, dim3(256), 0, s, m);
             MOAI_LAUNCH_CHECK();
             MOAI_TRY(hy_dot_term(c, sc.acc, sc.gal, o, tm, gs, ng, r, L, alpha, B, s));
         }
@@ -1825,11 +1891,12 @@ static int hy_rescale_table(moai_ctx *c, size_t L, size_t alpha, const HyRescale
 }
 
 // rows of N words of scratch per ciphertext: t, the converted digits, acc, the alpha + 1 source rows of the merged mod-down, conv
-// over L - 1 rows (and the three-polynomial product of moai_multiply_relin_rescale_hybrid)
-static size_t hy_rescale_rows_per_ct(size_t L, size_t alpha, bool product)
+// over L - 1 rows, and head_rows rows in front of them (3 L: the three-polynomial product of moai_multiply_relin_rescale_hybrid;
+// L: the gathered third polynomial of a member of the list form; 0 otherwise)
+static size_t hy_rescale_rows_per_ct(size_t L, size_t alpha, size_t head_rows)
 {
     const size_t beta = hy_beta(L, alpha);
-    return (product ? 3 * L : 0) + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * (alpha + 1) + 2 * (L - 1);
+    return head_rows + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * (alpha + 1) + 2 * (L - 1);
 }
 
 struct HyRescaleLayout
@@ -1837,12 +1904,12 @@ struct HyRescaleLayout
     size_t prod, t, ext, acc, x, conv, total; // byte offsets
 };
 
-static HyRescaleLayout hy_rescale_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, bool product)
+static HyRescaleLayout hy_rescale_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t head_rows)
 {
     const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
     HyRescaleLayout w;
     w.prod = 0;
-    w.t = w.prod + align256(product ? cb * 3 * L * row : 0);
+    w.t = w.prod + align256(cb * head_rows * row);
     w.ext = w.t + align256(cb * L * row);
     w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
     w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
@@ -1853,10 +1920,10 @@ static HyRescaleLayout hy_rescale_layout(const moai_ctx *c, size_t L, size_t alp
 
 // ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one; no row-per-workgroup grid above 65535 (the widest runs
 // over 3 * cb * L rows with the product, 2 * cb * (L + alpha) without)
-static size_t hy_rescale_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, bool product)
+static size_t hy_rescale_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t head_rows)
 {
     const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
-    const size_t per = hy_rescale_rows_per_ct(L, alpha, product) * c->n * sizeof(uint64_t);
+    const size_t per = hy_rescale_rows_per_ct(L, alpha, head_rows) * c->n * sizeof(uint64_t);
     size_t cb = budget / per;
     cb = cb < 1 ? 1 : cb;
     const size_t cap = 65535 / std::max(2 * (L + alpha), 3 * L);
@@ -1864,26 +1931,27 @@ static size_t hy_rescale_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t
     return cb < batch ? cb : batch;
 }
 
-// one chunk of B ciphertexts: out [B][2][L - 1][N] = the merged mod-down of (c0, c1) + switch(c2) for ct3 [B][3][L][N]
+// one chunk of B ciphertexts: out [B][2][L - 1][N] = the merged mod-down of (c0, c1) + switch(c2) for ct3 [B][3][L][N].  With lst (a
+// device record, common.h KsList) c2 [B][L][N] has been gathered to w.gal, c0 and c1 are read from lst->ins[b], the key is
+// lst->keys[b] and the result goes to lst->outs[b]; ct3, key and out are not used
 static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescaleTable *rt, const uint64_t *ct3, const uint64_t *key,
-                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyRescaleLayout &w, hipStream_t s)
+                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyRescaleLayout &w, hipStream_t s,
+                                const KsList *lst = nullptr)
 {
     uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
     uint64_t *conv = at_bytes(wsp, w.conv);
     // steps 1-4 on c2, as every switch
-    MOAI_TRY(hy_decompose(c, tab, { ct3, 3 * L, 2 * L }, L, alpha, B, t, ext, s));
+    const KsTarget tg = lst ? KsTarget{ at_bytes(wsp, w.prod), L, 0 } : KsTarget{ ct3, 3 * L, 2 * L };
+    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, t, ext, s));
     HyMacArgs m;
     m.ext = ext;
-    m.tgt = ct3;
+    m.tgt = tg.ptr;
     m.key = key;
     m.acc = acc;
-    m.tgt_stride = (uint32_t)(3 * L);
-    m.tgt_off = (uint32_t)(2 * L);
+    m.tgt_stride = (uint32_t)tg.stride_rows;
+    m.tgt_off = (uint32_t)tg.off_rows;
     m.d = hy_dims(c, L, alpha);
-    dim3 grid;
-    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
-    hipLaunchKernelGGL(hy_mac_kernel, grid, dim3(256), 0, s, m);
-    MOAI_LAUNCH_CHECK();
+    MOAI_TRY(hy_mac(c, m, B, lst, s));
     // the lift of the one data row among the sources (the rows below it take theirs in the last kernel)
     HyLiftArgs lf;
     lf.acc = acc;
@@ -1895,7 +1963,9 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
         special[sp] = (uint32_t)(c->k - alpha + sp);
     }
     lf.plast = hy_prod_mod(c, special, alpha, alpha, c->primes[L - 1]);
-    MOAI_TRY(launch_rows(hy_lift_last_row_kernel, c, 2 * B, s, lf));
+    MOAI_TRY(plain_or_list<HyLiftListArgs>(lf, lst, [&](const auto &args, auto LIST) {
+        return launch_rows(hy_lift_last_row_kernel<decltype(LIST)::value>, c, 2 * B, s, args);
+    }));
     // the merged mod-down: x = INTT(rows L-1 .. L+alpha-1 of acc, contiguous), conv = NTT(base conversion with W's rounding terms)
     RowMap rm{};
     hy_rowmap(c, L, alpha, 0, L - 1, &rm);
@@ -1911,16 +1981,14 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
     f.winv = rt->winv; // device address arithmetic only
     f.qinv = rt->qinv;
     f.d = m.d;
-    return launch_rows(hy_rescale_finalize_kernel, c, 2 * B * (L - 1), s, f);
+    return plain_or_list<HyRescaleFinalListArgs>(f, lst, [&](const auto &args, auto LIST) {
+        return launch_rows(hy_rescale_finalize_kernel<decltype(LIST)::value>, c, 2 * B * (L - 1), s, args);
+    });
 }
 
-// the two entry points: validated, then chunk by chunk on the stream's workspace
-//   y null:  x = ct3 [batch][3][L][N]
-//   y set:   x, y [batch][2][L][N] (y may be x); their product lives in the chunk's workspace
-static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, bool product, const uint64_t *key, uint64_t *out, size_t L,
-                            size_t alpha, size_t batch, void *stream)
+// what the merged forms refuse: what needs no context first, in hy_check's order (alpha = 0 and L = 0 are its own)
+static int hy_rescale_check(const moai_ctx *c, size_t alpha, size_t L)
 {
-    // what needs no context first, in hy_check's order: alpha = 0 and L = 0 are its own
     if (alpha != 0 && L == 1)
     {
         return set_error(MOAI_EINVAL, "L = 1: no prime left to rescale to");
@@ -1929,7 +1997,16 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
     {
         return set_error(MOAI_EINVAL, "alpha = %zu: the merged mod-down converts alpha + 1 residues, at most %u", alpha, HY_MAX_ALPHA);
     }
-    MOAI_TRY(hy_check(c, alpha, L, true));
+    return hy_check(c, alpha, L, true);
+}
+
+// the two entry points: validated, then chunk by chunk on the stream's workspace
+//   y null:  x = ct3 [batch][3][L][N]
+//   y set:   x, y [batch][2][L][N] (y may be x); their product lives in the chunk's workspace
+static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, bool product, const uint64_t *key, uint64_t *out, size_t L,
+                            size_t alpha, size_t batch, void *stream)
+{
+    MOAI_TRY(hy_rescale_check(c, alpha, L));
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1952,8 +2029,8 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
     const HyRescaleTable *rt;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
     MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
-    const size_t cb = hy_rescale_chunk(c, L, alpha, batch, product);
-    const HyRescaleLayout w = hy_rescale_layout(c, L, alpha, cb, product);
+    const size_t cb = hy_rescale_chunk(c, L, alpha, batch, product ? 3 * L : 0);
+    const HyRescaleLayout w = hy_rescale_layout(c, L, alpha, cb, product ? 3 * L : 0);
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
     return for_chunks(batch, cb, [&](size_t b0, size_t B) {
@@ -1969,6 +2046,100 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
             ct3 = g.out;
         }
         return hy_rescale_chunk_run(c, tab, rt, ct3, key, out + b0 * 2 * (L - 1) * n, L, alpha, B, wsp, w, s);
+    });
+}
+
+// ---- the switches on a list of ciphertexts, each in its own block (and, for the rotation, with its own key and element) ------------
+enum
+{
+    HY_LIST_GALOIS,
+    HY_LIST_RELIN,
+    HY_LIST_RESCALE
+};
+
+// What the three list entry points share; the n single calls at batch 1 in one chain of launches per pass.
+//   HY_LIST_GALOIS   member i is [2][L][N] and gets apply_galois by elts[i] with keys[i], plus sums[i]; outs[i] [2][L][N]
+//   HY_LIST_RELIN    member i is [3][L][N]; outs[i] [2][L][N] = (c0, c1) + switch(c2) with one_key
+//   HY_LIST_RESCALE  the same through the merged mod-down; outs[i] [2][L - 1][N]
+// Everything is validated before anything is enqueued (the context-free part and the overlaps are keyswitch.hip's own checks).  A
+// pass takes min(KS_LIST_MAX, the chunk MOAI_HYBRID_TMP_KB allows) members: its record goes to the device as a kernel argument,
+// galois_gather_list permutes the members (or, with the identity table, collects their third polynomials) into the chunk's
+// contiguous scratch, steps 1-3 and the mod-down's transforms run on that scratch as they do for a batch, and the MAC and the last
+// kernels take the member's key, addends and output from the record.
+static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint64_t *const *outs, size_t L, size_t alpha,
+                        const uint32_t *elts, const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n,
+                        void *stream)
+{
+    const bool relin = kind != HY_LIST_GALOIS, rescale = kind == HY_LIST_RESCALE;
+    if (n == 0)
+    {
+        return MOAI_OK;
+    }
+    MOAI_TRY(ks_list_check_members(ins, outs, elts, keys, one_key, n, relin));
+    MOAI_TRY(rescale ? hy_rescale_check(c, alpha, L) : hy_check(c, alpha, L, true));
+    const size_t row = c->n * sizeof(uint64_t), Lout = rescale ? L - 1 : L;
+    MOAI_TRY(ks_list_check_blocks(c, ins, outs, elts, sums, n, (relin ? 3 : 2) * L * row, 2 * Lout * row, relin));
+    MOAI_TRY(enter_device(c));
+    std::vector<const uint32_t *> tables(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        // relinearize: element 1, the identity permutation -- the gather then only collects the third polynomials
+        MOAI_TRY(galois_table(c, relin ? 1u : elts[i], &tables[i]));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    const HyRescaleTable *rt = nullptr;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    if (rescale)
+    {
+        MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
+    }
+    const size_t gal_rows = relin ? L : 2 * L; // rows per member of the gathered target
+    const size_t nb = std::min(KS_LIST_MAX, rescale ? hy_rescale_chunk(c, L, alpha, n, gal_rows) : hy_chunk(c, L, alpha, n, gal_rows));
+    HyLayout w{};
+    HyRescaleLayout wr{};
+    if (rescale)
+    {
+        wr = hy_rescale_layout(c, L, alpha, nb, gal_rows);
+    }
+    else
+    {
+        w = hy_layout(c, L, alpha, nb, gal_rows);
+    }
+    const size_t sz_list = align256(sizeof(KsList));
+    void *wsp;
+    MOAI_TRY(workspace(c, sz_list + (rescale ? wr.total : w.total), s, &wsp));
+    KsList *dlist = static_cast<KsList *>(wsp);
+    void *chunk = at_bytes(wsp, sz_list);
+    return for_chunks(n, nb, [&](size_t m0, size_t cnt) {
+        KsList h;
+        for (size_t e = 0; e < KS_LIST_MAX; ++e)
+        {
+            const size_t i = m0 + (e < cnt ? e : 0); // the unused entries repeat the pass's first member
+            h.ins[e] = ins[i];
+            h.outs[e] = outs[i];
+            h.sums[e] = sums ? sums[i] : nullptr;
+            h.keys[e] = relin ? one_key : keys[i];
+            h.tables[e] = tables[i];
+            h.key_rows[e] = (uint32_t)c->k; // the whole layout
+        }
+        MOAI_TRY(ks_list_write(h, dlist, s));
+        uint64_t *tmp = at_bytes(chunk, rescale ? wr.prod : w.gal);
+        switch (kind)
+        {
+        case HY_LIST_GALOIS:
+            // tmp [cnt][2][L][N] = galois(ins); out = (galois(in0), 0) + switch(galois(in1)) [+ sum]   (evaluator.cpp:2631-2654)
+            MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, 2 * L, 0, s));
+            return hy_switch_chunk(c, tab, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, alpha, cnt, chunk, w, { tmp, 2 * L, 2 }, s);
+        case HY_LIST_RELIN:
+            // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch(c2)   (evaluator.cpp:1383-1392)
+            MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
+            return hy_switch_chunk(c, tab, nullptr, { tmp, L, 0, dlist }, nullptr, L, alpha, cnt, chunk, w, { nullptr, 0, 1 }, s);
+        default:
+            MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
+            return hy_rescale_chunk_run(c, tab, rt, nullptr, nullptr, nullptr, L, alpha, cnt, chunk, wr, s, dlist);
+        }
     });
 }
 
@@ -2039,7 +2210,47 @@ extern "C" int moai_apply_galois_hybrid(moai_ctx *c, uint64_t *ct, size_t L, siz
 {
     MOAI_AUDIT(stream, ct, key);
     trace_op("apply_galois_hybrid", L, batch);
-    return hy_entry(c, HY_GALOIS, ct, nullptr, key, L, alpha, galois_elt, batch, stream);
+    return hy_entry(c, HY_GALOIS, ct, ct, key, L, alpha, galois_elt, batch, stream);
+}
+
+extern "C" int moai_apply_galois_hybrid_to(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, size_t alpha, uint32_t galois_elt,
+                                           const uint64_t *key, size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, in, out, key);
+    trace_op("apply_galois_hybrid", L, batch);
+    return hy_entry(c, HY_GALOIS, out, in, key, L, alpha, galois_elt, batch, stream);
+}
+
+extern "C" int moai_apply_galois_hybrid_acc(moai_ctx *c, const uint64_t *in, uint64_t *acc, size_t L, size_t alpha, uint32_t galois_elt,
+                                            const uint64_t *key, size_t batch, void *stream)
+{
+    MOAI_AUDIT(stream, in, acc, key);
+    trace_op("apply_galois_hybrid", L, batch); // the same switch; the addition that follows it is what is saved
+    return hy_entry(c, HY_GALOIS, acc, in, key, L, alpha, galois_elt, batch, stream, acc);
+}
+
+extern "C" int moai_apply_galois_hybrid_ptrs(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, size_t alpha,
+                                             const uint32_t *galois_elts, const uint64_t *const *keys, const uint64_t *const *sums, size_t n,
+                                             void *stream)
+{
+    for (size_t i = 0; ins && outs && keys && i < n; ++i)
+    {
+        MOAI_AUDIT(stream, ins[i], outs[i], keys[i], sums ? sums[i] : nullptr);
+    }
+    trace_op("apply_galois_hybrid", L, n); // the calls it replaces
+    return hy_ptrs_impl(c, HY_LIST_GALOIS, ins, outs, L, alpha, galois_elts, keys, nullptr, sums, n, stream);
+}
+
+extern "C" int moai_relinearize_hybrid_ptrs(moai_ctx *c, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *key, size_t L,
+                                            size_t alpha, size_t n, void *stream)
+{
+    MOAI_AUDIT(stream, key);
+    for (size_t i = 0; ct3s && outs && i < n; ++i)
+    {
+        MOAI_AUDIT(stream, ct3s[i], outs[i]);
+    }
+    trace_op("relinearize_hybrid", L, n);
+    return hy_ptrs_impl(c, HY_LIST_RELIN, ct3s, outs, L, alpha, nullptr, nullptr, key, nullptr, n, stream);
 }
 
 extern "C" int moai_hybrid_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t galois_elt, size_t L, size_t alpha,
@@ -2125,7 +2336,7 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
             for (size_t r = 0; r < R; ++r)
             {
                 MOAI_HIP_CHECK(hipMemcpyAsync(outs[r] + off, in + off, B * 2 * L * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-                MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, nullptr, keys[r], L, alpha, galois_elts[r], B, stream));
+                MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, outs[r] + off, keys[r], L, alpha, galois_elts[r], B, stream));
             }
         }
         return MOAI_OK;
@@ -2334,6 +2545,18 @@ extern "C" int moai_relinearize_rescale_hybrid(moai_ctx *c, const uint64_t *ct3,
     MOAI_AUDIT(stream, ct3, key, out);
     trace_op("relinearize_rescale_hybrid", L, batch);
     return hy_rescale_entry(c, ct3, nullptr, false, key, out, L, alpha, batch, stream);
+}
+
+extern "C" int moai_relinearize_rescale_hybrid_ptrs(moai_ctx *c, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *key,
+                                                    size_t L, size_t alpha, size_t n, void *stream)
+{
+    MOAI_AUDIT(stream, key);
+    for (size_t i = 0; ct3s && outs && i < n; ++i)
+    {
+        MOAI_AUDIT(stream, ct3s[i], outs[i]);
+    }
+    trace_op("relinearize_rescale_hybrid", L, n);
+    return hy_ptrs_impl(c, HY_LIST_RESCALE, ct3s, outs, L, alpha, nullptr, nullptr, key, nullptr, n, stream);
 }
 
 extern "C" int moai_multiply_relin_rescale_hybrid(moai_ctx *c, const uint64_t *x, const uint64_t *y, const uint64_t *key, uint64_t *out,

@@ -1078,17 +1078,17 @@ __global__ __launch_bounds__(64) void ks_list_write_kernel(KsList h, KsList *d)
     d->key_rows[i] = h.key_rows[i];
 }
 
-// What the two list entry points share.  relin: member i is [3][L][N], its third polynomial is switched with `one_key` and the
-// first two are added (moai_relinearize); else member i is [2][L][N] and gets apply_galois by elts[i] with keys[i], plus sums[i].
-// Everything is validated before anything is enqueued; then at most KS_LIST_MAX members per pass: the list, one gather that
-// also permutes (galois_gather_kernel<true>) into the contiguous scratch, and the key switch with the LIST kernels.
-static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *elts,
-                        const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n, bool relin, void *stream)
+// the three steps of a list call that hybrid.hip's list forms share with the two below (launch.h)
+int ks_list_write(const KsList &h, KsList *d, hipStream_t s)
 {
-    if (n == 0)
-    {
-        return MOAI_OK;
-    }
+    hipLaunchKernelGGL(ks_list_write_kernel, dim3(1), dim3((uint32_t)KS_LIST_MAX), 0, s, h, d);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+int ks_list_check_members(const uint64_t *const *ins, uint64_t *const *outs, const uint32_t *elts, const uint64_t *const *keys,
+                          const uint64_t *one_key, size_t n, bool relin)
+{
     if (!ins || !outs || (relin ? !one_key : (!elts || !keys)))
     {
         return set_error(MOAI_EINVAL, "null list");
@@ -1104,10 +1104,12 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
             return set_error(MOAI_EINVAL, "member %zu: Galois element is not valid", i);
         }
     }
-    const size_t nb = n < KS_LIST_MAX ? n : KS_LIST_MAX; // members per pass
-    MOAI_TRY(check_level(c, L, nb * (relin ? 3 : 2)));
-    MOAI_TRY(check_switch_level(c, L));
-    const size_t rn = L * c->n, in_bytes = (relin ? 3 : 2) * rn * sizeof(uint64_t), out_bytes = 2 * rn * sizeof(uint64_t);
+    return MOAI_OK;
+}
+
+int ks_list_check_blocks(const moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, const uint32_t *elts,
+                         const uint64_t *const *sums, size_t n, size_t in_bytes, size_t out_bytes, bool relin)
+{
     for (size_t i = 0; i < n; ++i)
     {
         if (!relin && elts[i] >= 2 * c->n)
@@ -1132,38 +1134,56 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
     // another member's blocks: passes and workgroups run in no order that a caller could rely on.  Every block sorted by its
     // start; a block that overlaps an output starts less than the longest block before the output's end, so each output looks at
     // the few blocks in that window: n log n, not n^2, for the lists a caller may pass (any n).
+    struct Block
     {
-        struct Block
+        uintptr_t at;
+        size_t bytes, member;
+    };
+    std::vector<Block> blocks;
+    blocks.reserve(3 * n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        blocks.push_back({ (uintptr_t)ins[i], in_bytes, i });
+        blocks.push_back({ (uintptr_t)outs[i], out_bytes, i });
+        if (sums && sums[i])
         {
-            uintptr_t at;
-            size_t bytes, member;
-        };
-        std::vector<Block> blocks;
-        blocks.reserve(3 * n);
-        for (size_t i = 0; i < n; ++i)
-        {
-            blocks.push_back({ (uintptr_t)ins[i], in_bytes, i });
-            blocks.push_back({ (uintptr_t)outs[i], out_bytes, i });
-            if (sums && sums[i])
-            {
-                blocks.push_back({ (uintptr_t)sums[i], out_bytes, i });
-            }
+            blocks.push_back({ (uintptr_t)sums[i], out_bytes, i });
         }
-        std::sort(blocks.begin(), blocks.end(), [](const Block &x, const Block &y) { return x.at < y.at; });
-        for (size_t i = 0; i < n; ++i)
+    }
+    std::sort(blocks.begin(), blocks.end(), [](const Block &x, const Block &y) { return x.at < y.at; });
+    for (size_t i = 0; i < n; ++i)
+    {
+        const uintptr_t lo = (uintptr_t)outs[i], hi = lo + out_bytes;
+        auto it = std::lower_bound(blocks.begin(), blocks.end(), lo > in_bytes ? lo - in_bytes : 0,
+                                   [](const Block &x, uintptr_t v) { return x.at < v; });
+        for (; it != blocks.end() && it->at < hi; ++it)
         {
-            const uintptr_t lo = (uintptr_t)outs[i], hi = lo + out_bytes;
-            auto it = std::lower_bound(blocks.begin(), blocks.end(), lo > in_bytes ? lo - in_bytes : 0,
-                                       [](const Block &x, uintptr_t v) { return x.at < v; });
-            for (; it != blocks.end() && it->at < hi; ++it)
+            if (it->member != i && it->at + it->bytes > lo)
             {
-                if (it->member != i && it->at + it->bytes > lo)
-                {
-                    return set_error(MOAI_EINVAL, "member %zu: the output overlaps a block of member %zu", i, it->member);
-                }
+                return set_error(MOAI_EINVAL, "member %zu: the output overlaps a block of member %zu", i, it->member);
             }
         }
     }
+    return MOAI_OK;
+}
+
+// What the two list entry points share.  relin: member i is [3][L][N], its third polynomial is switched with `one_key` and the
+// first two are added (moai_relinearize); else member i is [2][L][N] and gets apply_galois by elts[i] with keys[i], plus sums[i].
+// Everything is validated before anything is enqueued; then at most KS_LIST_MAX members per pass: the list, one gather that
+// also permutes (galois_gather_kernel<true>) into the contiguous scratch, and the key switch with the LIST kernels.
+static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *elts,
+                        const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n, bool relin, void *stream)
+{
+    if (n == 0)
+    {
+        return MOAI_OK;
+    }
+    MOAI_TRY(ks_list_check_members(ins, outs, elts, keys, one_key, n, relin));
+    const size_t nb = n < KS_LIST_MAX ? n : KS_LIST_MAX; // members per pass
+    MOAI_TRY(check_level(c, L, nb * (relin ? 3 : 2)));
+    MOAI_TRY(check_switch_level(c, L));
+    const size_t rn = L * c->n, in_bytes = (relin ? 3 : 2) * rn * sizeof(uint64_t), out_bytes = 2 * rn * sizeof(uint64_t);
+    MOAI_TRY(ks_list_check_blocks(c, ins, outs, elts, sums, n, in_bytes, out_bytes, relin));
     std::vector<uint32_t> key_rows(n);
     if (relin)
     {
@@ -1200,8 +1220,7 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
             h.tables[e] = tables[i];
             h.key_rows[e] = key_rows[i];
         }
-        hipLaunchKernelGGL(ks_list_write_kernel, dim3(1), dim3((uint32_t)KS_LIST_MAX), 0, s, h, dlist);
-        MOAI_LAUNCH_CHECK();
+        MOAI_TRY(ks_list_write(h, dlist, s));
         if (relin)
         {
             // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch_key(c2)   (evaluator.cpp:1383-1392)

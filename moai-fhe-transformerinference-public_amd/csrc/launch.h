@@ -159,6 +159,18 @@ int moddown_finalize(moai_ctx *c, const uint64_t *acc, uint32_t acc_stride, cons
 // lst->tables[b]; lst is a device pointer (common.h KsList)
 int galois_gather_list(moai_ctx *c, const KsList *lst, uint64_t *out, size_t members, size_t rows_per_member, size_t src_off_rows,
                        hipStream_t s);
+// What the list forms of the key switches (moai_apply_galois_ptrs, moai_relinearize_ptrs and their hybrid counterparts) share
+// (keyswitch.hip).  ks_list_write: one pass's record h goes to the device record d on stream s as a kernel argument
+// (ks_list_write_kernel), never through a host-to-device copy.  ks_list_check_members: what needs no context -- "null list", then
+// per member "member i: null pointer" and an even element; relin: one key for all, no elements.  ks_list_check_blocks: what needs the
+// ring -- an element of 2N or more, then the overlaps: a member's output may be its input (not with relin) or its sum exactly, never a
+// part of them, and never touches a block of another member; a member's input is in_bytes long, its output and its sum out_bytes
+// (in_bytes >= out_bytes).
+int ks_list_write(const KsList &h, KsList *d, hipStream_t s);
+int ks_list_check_members(const uint64_t *const *ins, uint64_t *const *outs, const uint32_t *elts, const uint64_t *const *keys,
+                          const uint64_t *one_key, size_t n, bool relin);
+int ks_list_check_blocks(const moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, const uint32_t *elts,
+                         const uint64_t *const *sums, size_t n, size_t in_bytes, size_t out_bytes, bool relin);
 
 // CKKSEncoder's tables (matrix_reps_index_map_, root_powers_, inv_root_powers_) on the device, built on first use under
 // c->mutex (encoder.hip)

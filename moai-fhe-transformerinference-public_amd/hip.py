@@ -118,6 +118,11 @@ SYMBOLS = {
     "moai_hybrid_bsgs_dot": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_int), vp]),
     "moai_relinearize_rescale_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_multiply_relin_rescale_hybrid": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+    "moai_apply_galois_hybrid_to": (C.c_int, [vp, vp, vp, sz, sz, C.c_uint32, vp, sz, vp]),
+    "moai_apply_galois_hybrid_acc": (C.c_int, [vp, vp, vp, sz, sz, C.c_uint32, vp, sz, vp]),
+    "moai_apply_galois_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
+    "moai_relinearize_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, sz, vp]),
+    "moai_relinearize_rescale_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, sz, vp]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -414,6 +419,40 @@ class Context:
 
     def apply_galois_hybrid(self, ct, L, alpha, elt, key, batch, stream=None):
         _check(lib().moai_apply_galois_hybrid(self.h, _ptr(ct), L, alpha, int(elt), _ptr(key), batch, stream))
+
+    # hybrid key switches on a list of ciphertexts (include/moai_hip.h, "hybrid key switches on a list of ciphertexts")
+    def apply_galois_hybrid_to(self, src, dst, L, alpha, elt, key, batch, stream=None):
+        """dst = apply_galois_hybrid(copy of src); dst may be src"""
+        _check(lib().moai_apply_galois_hybrid_to(self.h, _ptr(src), _ptr(dst), L, alpha, int(elt), _ptr(key), batch, stream))
+
+    def apply_galois_hybrid_acc(self, src, acc, L, alpha, elt, key, batch, stream=None):
+        """acc += apply_galois_hybrid(copy of src): the addition rides on the switch's last kernel"""
+        _check(lib().moai_apply_galois_hybrid_acc(self.h, _ptr(src), _ptr(acc), L, alpha, int(elt), _ptr(key), batch, stream))
+
+    def apply_galois_hybrid_ptrs(self, ins, outs, L, alpha, elts, keys, sums=None, stream=None):
+        """outs[i] = [sums[i] +] apply_galois_hybrid(copy of ins[i], elts[i], keys[i]) for single ciphertexts [2][L][N] in separate
+        buffers, in one chain of launches; sums: None, or a list whose entries may be None"""
+        n = len(ins)
+        ai = (vp * n)(*[_ptr(x) for x in ins])
+        ao = (vp * n)(*[_ptr(x) for x in outs])
+        e = (C.c_uint32 * n)(*[int(x) for x in elts])
+        ak = (vp * n)(*[_ptr(x) for x in keys])
+        asum = None if sums is None else (vp * n)(*[_ptr(x) for x in sums])
+        _check(lib().moai_apply_galois_hybrid_ptrs(self.h, ai, ao, L, alpha, e, ak, asum, n, stream))
+
+    def relinearize_hybrid_ptrs(self, ct3s, outs, key, L, alpha, stream=None):
+        """outs[i] [2][L][N] = relinearize_hybrid(ct3s[i] [3][L][N]) with one key, in one chain of launches"""
+        n = len(ct3s)
+        ai = (vp * n)(*[_ptr(x) for x in ct3s])
+        ao = (vp * n)(*[_ptr(x) for x in outs])
+        _check(lib().moai_relinearize_hybrid_ptrs(self.h, ai, ao, _ptr(key), L, alpha, n, stream))
+
+    def relinearize_rescale_hybrid_ptrs(self, ct3s, outs, key, L, alpha, stream=None):
+        """outs[i] [2][L-1][N] = relinearize_rescale_hybrid(ct3s[i] [3][L][N]) with one key, in one chain of launches"""
+        n = len(ct3s)
+        ai = (vp * n)(*[_ptr(x) for x in ct3s])
+        ao = (vp * n)(*[_ptr(x) for x in outs])
+        _check(lib().moai_relinearize_rescale_hybrid_ptrs(self.h, ai, ao, _ptr(key), L, alpha, n, stream))
 
     def hybrid_hoist_correction(self, key, elt, L, alpha, stream=None):
         """the per-(key, element, level) constant of the hoisted hybrid rotations: DeviceBuffer [2][L+alpha][N]"""
