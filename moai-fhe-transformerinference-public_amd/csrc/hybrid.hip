@@ -7,7 +7,7 @@
 // Context primes m_0 .. m_{k-1}: special p_t = m_{k-alpha+t}, P their product; data q_i = m_i, i < k - alpha.  At L data primes
 // digit j < beta = ceil(L / alpha) is the rows R_j = [j alpha, min((j+1) alpha, L)), D_j their product.
 //
-// Structure on the device, unfused, per chunk of the batch (scratch per ciphertext: hy_rows_per_ct rows of N words):
+// Structure on the device, unfused, per chunk of the batch (scratch per ciphertext: the rows of hy_plan_switch, N words each):
 //   t        = INTT(target)                                                     [B][L][N]
 //   ext_j    = hy_convert_kernel: digit j from base R_j to every other row      [B][L - |R_j| + alpha][N], then forward NTT
 //              (rows of R_j are not converted: the MAC reads the target's own NTT-form rows)
@@ -32,6 +32,12 @@
 // hy_rescale_finalize_kernel) have a LIST instantiation that takes those pointers from the pass's KsList record.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
+//
+// Files: the argument structs, the constant blocks and every kernel are in hybrid_kernels.hip.h; this file is the host code.  The
+// scratch of a chunk is planned by hybrid_scratch.h (host only, no context, no device): each call family (switch, hoisted, pt-dot,
+// bsgs, rescale) states its regions once -- a name, a row count, held per ciphertext or per (group, ciphertext) pair -- and from that
+// one statement a HyPlan takes the row totals that size a chunk under MOAI_HYBRID_TMP_KB, the 256-aligned offsets and the total.
+// Three sizing policies: ciphertexts only; ciphertexts, then groups beside them; groups first with the chunks evened out.
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -40,823 +46,12 @@
 #include "launch.h"
 #include "modarith.hip.h"
 
+#include "hybrid_kernels.hip.h"
+#include "hybrid_scratch.h"
+
 namespace moai {
 
-// a digit's source rows are held in registers by the conversion kernel; the constants are products of at most this many residues
-constexpr uint32_t HY_MAX_ALPHA = 16;
-
-// One fast base conversion: sources r < nsrc under context primes src_prime[r], targets t < ntgt under tgt_prime[t]:
-//   y_r = ((x_r + src_pre[r]) mod s_r) * src_inv[r] mod s_r,   out_t = ((sum_r y_r w[t][r]) - tgt_post[t]) mod m_t
-// mod-up of digit j: src_pre = tgt_post = 0, src_inv = (D_j / q_r)^-1, w = (D_j / q_r) mod m_t
-// mod-down:          src_pre = floor(P / 2) mod p_t, tgt_post = floor(P / 2) mod q_i, src_inv = (P / p_t)^-1, w = (P / p_t) mod q_i
-struct alignas(16) HyConv
-{
-    uint32_t nsrc, ntgt, pad[2];
-    uint32_t src_prime[HY_MAX_ALPHA];
-    uint32_t tgt_prime[MOAI_MAX_RNS];
-    Tw src_inv[HY_MAX_ALPHA];
-    uint64_t src_pre[HY_MAX_ALPHA];
-    uint64_t tgt_post[MOAI_MAX_RNS];
-    uint64_t w[MOAI_MAX_RNS][HY_MAX_ALPHA];
-};
-
-// the constants of a switch at (L, alpha): conv[j], j < beta, are the mod-ups and conv[beta] is the mod-down; behind them lie the
-// multipliers of the hoisted rotations' correction, [beta][L + alpha] words: |R_j| D_j mod m_row (hy_hoist_mult)
-struct alignas(16) HyTable
-{
-    Tw pinv[MOAI_MAX_RNS]; // P^-1 mod q_i
-    HyConv conv[1];
-};
-
-// device address arithmetic only
-static inline const uint64_t *hy_hoist_mult(const HyTable *tab, size_t beta)
-{
-    return reinterpret_cast<const uint64_t *>(tab->conv + beta + 1);
-}
-
-// (hi * 2^64 + lo) mod q for ANY 128-bit value: barrett128's quotient is short of the true one by at most 2 there, so one more
-// conditional subtraction makes the residue canonical (a source residue is below ITS prime, which may be far above the target's)
-__device__ __forceinline__ uint64_t hy_mod128(uint64_t lo, uint64_t hi, uint64_t q, uint64_t cr0, uint64_t cr1)
-{
-    return csub(barrett128(lo, hi, q, cr0, cr1), q);
-}
-
-struct HyConvArgs
-{
-    const uint64_t *src; // polynomial b's source row r at row b * src_stride + src_off + r, coefficient form, canonical
-    uint64_t *dst;       // [B][ntgt][N], canonical
-    const HyConv *cv;
-    const PrimeConst *pc;
-    uint32_t src_stride, src_off;
-    uint32_t n2;
-};
-
-// blockIdx.y = polynomial.  A thread reads the nsrc <= AMAX source residues of its two coefficients once, scales them, and walks
-// the target rows: per target nsrc 128-bit multiply-adds (at most 16 products below 2^122) and one reduction.  The constants are
-// indexed by uniform values: scalar loads.
-template <int AMAX>
-__global__ __launch_bounds__(256) void hy_convert_kernel(HyConvArgs g)
-{
-    const HyConv &cv = *g.cv;
-    const uint32_t ns = cv.nsrc, nt = cv.ntgt;
-    const size_t n2 = g.n2;
-    const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(g.src) + ((size_t)blockIdx.y * g.src_stride + g.src_off) * n2;
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(g.dst) + (size_t)blockIdx.y * nt * n2;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
-    {
-        ulonglong2 y[AMAX];
-#pragma unroll
-        for (int r = 0; r < AMAX; ++r)
-        {
-            y[r] = make_ulonglong2(0, 0);
-            if ((uint32_t)r < ns)
-            {
-                const uint64_t q = g.pc[cv.src_prime[r]].q, pre = cv.src_pre[r];
-                const Tw inv = cv.src_inv[r];
-                const ulonglong2 v = s[(size_t)r * n2 + j];
-                y[r].x = csub(mul_shoup_lazy(csub(v.x + pre, q), inv.w, inv.wq, q), q);
-                y[r].y = csub(mul_shoup_lazy(csub(v.y + pre, q), inv.w, inv.wq, q), q);
-            }
-        }
-        for (uint32_t t = 0; t < nt; ++t)
-        {
-            const PrimeConst *pc = g.pc + cv.tgt_prime[t];
-            const uint64_t m = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, post = cv.tgt_post[t];
-            uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
-#pragma unroll
-            for (int r = 0; r < AMAX; ++r)
-            {
-                if ((uint32_t)r < ns)
-                {
-                    mac2(lx, hx, ly, hy, y[r], cv.w[t][r]);
-                }
-            }
-            ulonglong2 o;
-            o.x = submod(hy_mod128(lx, hx, m, cr0, cr1), post, m);
-            o.y = submod(hy_mod128(ly, hy, m, cr0, cr1), post, m);
-            d[(size_t)t * n2 + j] = o;
-        }
-    }
-}
-
-// what every kernel below knows of a switch at (L, alpha); hy_dims fills it
-struct HyDims
-{
-    const PrimeConst *pc;
-    uint32_t L, alpha, beta, k;
-    uint32_t n2;
-};
-
-// The operand of digit j under the prime of `row`, for ciphertext b of B, at L data primes in digits of alpha: `own` where the row is
-// one of the digit's own primes (the ciphertext's NTT-form row as it is), else the digit's converted row in ext (HyMacArgs::ext, as
-// rows of row_elems elements of T)
-template <class T>
-__device__ __forceinline__ const T *hy_digit_operand(const T *own, const T *ext, size_t row_elems, uint32_t L, uint32_t alpha, uint32_t B,
-                                                     uint32_t b, uint32_t row, uint32_t j)
-{
-    const uint32_t lo = j * alpha, hi = min(lo + alpha, L), nr = hi - lo;
-    if (row >= lo && row < hi)
-    {
-        return own;
-    }
-    const uint32_t pos = row < lo ? row : row - nr;
-    return ext + ((size_t)j * B * L + (size_t)b * (L - nr + alpha) + pos) * row_elems;
-}
-
-struct HyMacArgs
-{
-    const uint64_t *ext;   // digit j's converted rows at ext + j * B * L * N: [B][L - |R_j| + alpha][N], NTT form
-    const uint64_t *tgt;   // ciphertext b's NTT-form target row r at row b * tgt_stride + tgt_off + r
-    const uint64_t *key;   // [beta(k - alpha)][2][k][N]
-    uint64_t *acc;         // [B][2][L + alpha][N]
-    uint32_t tgt_stride, tgt_off;
-    HyDims d;
-};
-
-struct HyMacListArgs : HyMacArgs
-{
-    const KsList *lst; // ciphertext b's key is lst->keys[b], in the same whole layout (key unused)
-};
-
-// acc[b][p][row] = sum_{j < beta} digit_j[row] (*) key[j][p][row]; blockIdx.x = b (the workgroups that read the same key words
-// are dispatched together), blockIdx.z = row.  At most 63 products below 2^122 per sum: no fold before the one reduction.
-// LIST: every ciphertext of the batch has its own key (KsList).  The ciphertext index is uniform over the workgroup, so the list
-// entry arrives through a scalar load; the digits and the accumulators stay in the pass's contiguous scratch.
-template <bool LIST = false>
-__global__ __launch_bounds__(256) void hy_mac_kernel(std::conditional_t<LIST, HyMacListArgs, HyMacArgs> g)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
-    const ulonglong2 *tgt = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)b * g.tgt_stride + g.tgt_off) * n2;
-    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + (size_t)prime * n2;
-    if constexpr (LIST)
-    {
-        key = reinterpret_cast<const ulonglong2 *>(g.lst->keys[b]) + (size_t)prime * n2;
-    }
-    ulonglong2 *acc0 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 0) * (d.L + d.alpha) + row) * n2;
-    ulonglong2 *acc1 = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)(b * 2 + 1) * (d.L + d.alpha) + row) * n2;
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
-    {
-        uint64_t l0x = 0, h0x = 0, l0y = 0, h0y = 0, l1x = 0, h1x = 0, l1y = 0, h1y = 0;
-        for (uint32_t j = 0; j < d.beta; ++j)
-        {
-            const ulonglong2 *op = hy_digit_operand(tgt + (size_t)row * n2, ext, n2, d.L, d.alpha, B, b, row, j);
-            const ulonglong2 o = op[x];
-            const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * d.k * n2 + x];
-            const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * d.k * n2 + x];
-            mac2(l0x, h0x, l0y, h0y, o, k0);
-            mac2(l1x, h1x, l1y, h1y, o, k1);
-        }
-        acc0[x] = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
-        acc1[x] = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
-    }
-}
-
-struct HyCorrArgs
-{
-    const uint64_t *key;  // [beta(k - alpha)][2][k][N]
-    const uint64_t *mask; // [L + alpha][N]: NTT of the rotation's sign mask under each row's prime
-    const uint64_t *mult; // [beta][L + alpha]: |R_j| D_j mod m_row
-    uint64_t *out;        // [2][L + alpha][N]
-    HyDims d;
-};
-
-// out[p][row] = mask[row] (*) sum_{j < beta} mult[j][row] key[j][p][row]; blockIdx.y = p * (L + alpha) + row.  At most 63 products
-// below 2^122.  A multiplier of zero (the rows of R_j itself, D_j mod q_r = 0) is skipped: the branch is uniform.
-__global__ __launch_bounds__(256) void hy_hoist_correction_kernel(HyCorrArgs g)
-{
-    const HyDims &d = g.d;
-    const uint32_t rows = d.L + d.alpha, p = blockIdx.y / rows, row = blockIdx.y % rows;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key) + ((size_t)p * d.k + prime) * n2;
-    const ulonglong2 *mk = reinterpret_cast<const ulonglong2 *>(g.mask) + (size_t)row * n2;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
-    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
-    {
-        uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
-        for (uint32_t j = 0; j < d.beta; ++j)
-        {
-            const uint64_t f = g.mult[j * rows + row];
-            if (f)
-            {
-                mac2(lx, hx, ly, hy, key[(size_t)j * 2 * d.k * n2 + x], f);
-            }
-        }
-        o[x] = mulmod2(reduce2(lx, hx, ly, hy, q, cr0, cr1), mk[x], q, cr0, cr1);
-    }
-}
-
-constexpr int HY_HOIST_MAX_NR = 4;
-
-struct HyHoistMacArgs
-{
-    const uint64_t *ext; // as HyMacArgs: the digits of the UNPERMUTED c1
-    const uint64_t *in;  // the unpermuted input [B][2][L][N]: its c1 row r is the digit under prime r
-    const uint32_t *table[HY_HOIST_MAX_NR]; // per rotation: its NTT-form index permutation (galois_table), out[i] = in[table[i]]
-    const uint64_t *key[HY_HOIST_MAX_NR];   // its key [beta(k - alpha)][2][k][N]
-    const uint64_t *corr[HY_HOIST_MAX_NR];  // its correction [2][L + alpha][N]
-    uint64_t *acc[HY_HOIST_MAX_NR];         // its accumulators [B][2][L + alpha][N]
-    HyDims d;
-};
-
-// acc_r[b][p][row] = sum_{j < beta} digit_j[row][table_r] (*) key_r[j][p][row] + corr_r[p][row] for NR rotations in one pass over
-// the digits; grid as hy_mac_kernel (blockIdx.x = b, blockIdx.z = row).  A thread owns two neighbouring OUTPUT positions: the key,
-// the correction and the accumulators are read and written in order, two words per lane, and only the digit is gathered (beta of
-// the 3 beta + 4 words per output).  Per digit every load of every rotation is issued before the arithmetic.  Sums as in
-// hy_mac_kernel: at most 63 products below 2^122, one reduction, then the canonical add of the correction.
-template <int NR>
-__global__ __launch_bounds__(256) void hy_hoisted_mac_kernel(HyHoistMacArgs g)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * d.L + row) * 2 * n2; // read only where row < L
-    const size_t acc_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, acc_poly = (size_t)(d.L + d.alpha) * n2;
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
-    {
-        uint2 src[NR];
-        uint64_t l0x[NR], h0x[NR], l0y[NR], h0y[NR], l1x[NR], h1x[NR], l1y[NR], h1y[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            src[r] = reinterpret_cast<const uint2 *>(g.table[r])[x];
-            l0x[r] = h0x[r] = l0y[r] = h0y[r] = l1x[r] = h1x[r] = l1y[r] = h1y[r] = 0;
-        }
-        for (uint32_t j = 0; j < d.beta; ++j)
-        {
-            // the digit under one of its own primes is the input's c1 row, read through the same permutation
-            const uint64_t *op = hy_digit_operand(own, g.ext, 2 * n2, d.L, d.alpha, B, b, row, j);
-            const size_t koff = ((size_t)j * 2 * d.k + prime) * n2 + x;
-            ulonglong2 o[NR], k0[NR], k1[NR];
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-            {
-                const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[r]);
-                o[r] = make_ulonglong2(op[src[r].x], op[src[r].y]);
-                k0[r] = key[koff];
-                k1[r] = key[koff + (size_t)d.k * n2];
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-            {
-                mac2(l0x[r], h0x[r], l0y[r], h0y[r], o[r], k0[r]);
-                mac2(l1x[r], h1x[r], l1y[r], h1y[r], o[r], k1[r]);
-            }
-        }
-        ulonglong2 c0[NR], c1[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            const ulonglong2 *corr = reinterpret_cast<const ulonglong2 *>(g.corr[r]) + (size_t)row * n2 + x;
-            c0[r] = corr[0];
-            c1[r] = corr[acc_poly];
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            ulonglong2 *acc = reinterpret_cast<ulonglong2 *>(g.acc[r]) + acc_row + x;
-            acc[0] = add2(reduce2(l0x[r], h0x[r], l0y[r], h0y[r], q, cr0, cr1), c0[r], q);
-            acc[acc_poly] = add2(reduce2(l1x[r], h1x[r], l1y[r], h1y[r], q, cr0, cr1), c1[r], q);
-        }
-    }
-}
-
-// ---- plaintext-weighted sums of rotations (moai_hybrid_rotate_pt_dot) ---------------------------------------------------------
-// outputs in flight per launch: their plaintext pointers travel as kernel arguments
-constexpr int HY_DOT_MAX_NG = 16;
-
-struct HyDotOutputs
-{
-    uint64_t *S;     // output h's extended-basis sums at S + h * B * 2 * (L + alpha) * N: [B][2][L + alpha][N], canonical
-    uint64_t *add;   // its addend at add + h * B * 2 * L * N: [B][2][L][N], canonical, always read-modified-written
-    uint32_t ng;     // outputs of this launch
-    uint32_t seeded; // bit h: S of output h already holds a sum; clear: this launch's products start it
-    const uint64_t *plain[HY_DOT_MAX_NG][HY_HOIST_MAX_NR]; // p_{g,r} [L + alpha][N] of output h and rotation r of the pass; null: absent
-};
-
-// hy_hoisted_mac_kernel's sums for one thread at output chunk x, kept in registers: a0[r], a1[r] = the canonical acc_r[b][0][row] and
-// acc_r[b][1][row], correction included, and src[r] = the two source positions of rotation r.  The same loads in the same order and
-// the same bound (at most 63 products below 2^122, one reduction, the canonical add of the correction); that kernel keeps its own
-// copy of the loop so that its code is what it was.
-template <int NR>
-__device__ __forceinline__ void hy_hoisted_sums(const HyHoistMacArgs &g, uint32_t b, uint32_t B, uint32_t row, uint32_t prime, uint32_t x,
-                                                uint2 (&src)[NR], ulonglong2 (&a0)[NR], ulonglong2 (&a1)[NR])
-{
-    const HyDims &d = g.d;
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const uint64_t *own = g.in + ((size_t)(b * 2 + 1) * d.L + row) * 2 * n2; // read only where row < L
-    const size_t acc_poly = (size_t)(d.L + d.alpha) * n2;
-    uint64_t l0x[NR], h0x[NR], l0y[NR], h0y[NR], l1x[NR], h1x[NR], l1y[NR], h1y[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-    {
-        src[r] = reinterpret_cast<const uint2 *>(g.table[r])[x];
-        l0x[r] = h0x[r] = l0y[r] = h0y[r] = l1x[r] = h1x[r] = l1y[r] = h1y[r] = 0;
-    }
-    for (uint32_t j = 0; j < d.beta; ++j)
-    {
-        // the digit under one of its own primes is the input's c1 row, read through the same permutation
-        const uint64_t *op = hy_digit_operand(own, g.ext, 2 * n2, d.L, d.alpha, B, b, row, j);
-        const size_t koff = ((size_t)j * 2 * d.k + prime) * n2 + x;
-        ulonglong2 o[NR], k0[NR], k1[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[r]);
-            o[r] = make_ulonglong2(op[src[r].x], op[src[r].y]);
-            k0[r] = key[koff];
-            k1[r] = key[koff + (size_t)d.k * n2];
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            mac2(l0x[r], h0x[r], l0y[r], h0y[r], o[r], k0[r]);
-            mac2(l1x[r], h1x[r], l1y[r], h1y[r], o[r], k1[r]);
-        }
-    }
-    ulonglong2 c0[NR], c1[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-    {
-        const ulonglong2 *corr = reinterpret_cast<const ulonglong2 *>(g.corr[r]) + (size_t)row * n2 + x;
-        c0[r] = corr[0];
-        c1[r] = corr[acc_poly];
-    }
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-    {
-        a0[r] = add2(reduce2(l0x[r], h0x[r], l0y[r], h0y[r], q, cr0, cr1), c0[r], q);
-        a1[r] = add2(reduce2(l1x[r], h1x[r], l1y[r], h1y[r], q, cr0, cr1), c1[r], q);
-    }
-}
-
-// S_h[b][p][row] += sum_r plain[h][r][row] (*) acc_r[b][p][row] and, on the data rows, add_h[b][0][row] += sum_r plain[h][r][row] (*)
-// perm_r(c0)[row], for the NR rotations of one pass of hy_hoisted_sums and every output in flight: the accumulators of a rotation
-// never leave the registers.  Grid as hy_hoisted_mac_kernel.  A rotation's sums and its gathered c0 are formed once and reused by
-// every output; the plaintext, S and the addend are read and written in order.  Every 128-bit sum here is one canonical residue
-// (below 2^61) plus at most NR <= 4 products below 2^122, below 2^125: no fold, one reduction, and the stored value is canonical
-// again, so the sum over any number of rotations is carried across passes as residues.  An absent term (a null pointer, uniform)
-// multiplies by zero; an output with no term in the pass is skipped, and one whose S no pass has written yet starts from zero.
-template <int NR>
-__global__ __launch_bounds__(256) void hy_hoisted_dot_kernel(HyHoistMacArgs g, HyDotOutputs o)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
-    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
-    const bool data = row < d.L;
-    const uint64_t *c0 = g.in + ((size_t)(b * 2) * d.L + row) * 2 * n2; // read only on the data rows
-    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2;
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
-    {
-        uint2 src[NR];
-        ulonglong2 a0[NR], a1[NR], u[NR];
-        hy_hoisted_sums<NR>(g, b, B, row, prime, x, src, a0, a1);
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-        {
-            u[r] = data ? make_ulonglong2(c0[src[r].x], c0[src[r].y]) : make_ulonglong2(0, 0);
-        }
-        for (uint32_t h = 0; h < o.ng; ++h)
-        {
-            ulonglong2 p[NR];
-            bool any = false;
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-            {
-                p[r] = make_ulonglong2(0, 0);
-                if (o.plain[h][r])
-                {
-                    p[r] = reinterpret_cast<const ulonglong2 *>(o.plain[h][r])[(size_t)row * n2 + x];
-                    any = true;
-                }
-            }
-            if (!any)
-            {
-                continue;
-            }
-            // every load of this output before its arithmetic; an absent term multiplies by zero
-            ulonglong2 *S = reinterpret_cast<ulonglong2 *>(o.S) + h * s_out + s_row + x;
-            ulonglong2 *ad = reinterpret_cast<ulonglong2 *>(o.add) + h * add_out + add_row + x; // touched only on the data rows
-            const bool seeded = (o.seeded >> h) & 1u;
-            const ulonglong2 zero = make_ulonglong2(0, 0);
-            const ulonglong2 s0 = seeded ? S[0] : zero, s1 = seeded ? S[s_poly] : zero, ad0 = data ? ad[0] : zero;
-            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y, lux, hux, luy, huy;
-            seed2(l0x, h0x, l0y, h0y, s0);
-            seed2(l1x, h1x, l1y, h1y, s1);
-            seed2(lux, hux, luy, huy, ad0);
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-            {
-                mac2(l0x, h0x, l0y, h0y, a0[r], p[r]);
-                mac2(l1x, h1x, l1y, h1y, a1[r], p[r]);
-                mac2(lux, hux, luy, huy, u[r], p[r]);
-            }
-            S[0] = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
-            S[s_poly] = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
-            if (data)
-            {
-                ad[0] = reduce2(lux, hux, luy, huy, q, cr0, cr1);
-            }
-        }
-    }
-}
-
-struct HyDotTermArgs
-{
-    const uint64_t *A; // the term's accumulators [B][2][L + alpha][N], canonical; null: an identity term, which has none
-    const uint64_t *u; // ciphertext b's rows at u + b * 2 * L * N, [2][L][N]: the permuted input of a rotation, the input itself for
-                       // an identity term
-    HyDims d;
-};
-
-// One term r of the sums, for every output in flight (plain[h][0] = p_{h,r}, null: absent); blockIdx.x = b, .z = row.
-//   a rotation (A set, rows of L + alpha):  S_h[b][p][row] += plain (*) A[b][p][row];  add_h[b][0][row] += plain (*) u[b][0][row] on data rows
-//   an identity term (A null, rows of L):   add_h[b][p][row] += plain (*) u[b][p][row], p in {0, 1}
-// The unhoisted route of a chunk and the identity terms.  addmul2: every product is reduced and added canonically, no 128-bit sum.
-__global__ __launch_bounds__(256) void hy_dot_term_kernel(HyDotTermArgs g, HyDotOutputs o)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
-    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
-    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2, add_poly = (size_t)d.L * n2; // the layout of u and of an addend
-    const bool data = row < d.L;
-    const ulonglong2 *A = reinterpret_cast<const ulonglong2 *>(g.A), *u = reinterpret_cast<const ulonglong2 *>(g.u);
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
-    {
-        ulonglong2 a0, a1, u0, u1;
-        a0 = a1 = u0 = u1 = make_ulonglong2(0, 0);
-        if (A)
-        {
-            a0 = A[s_row + x];
-            a1 = A[s_row + s_poly + x];
-        }
-        if (data)
-        {
-            u0 = u[add_row + x];
-            if (!A)
-            {
-                u1 = u[add_row + add_poly + x];
-            }
-        }
-        for (uint32_t h = 0; h < o.ng; ++h)
-        {
-            if (!o.plain[h][0])
-            {
-                continue;
-            }
-            const ulonglong2 p = reinterpret_cast<const ulonglong2 *>(o.plain[h][0])[(size_t)row * n2 + x];
-            if (A)
-            {
-                ulonglong2 *S = reinterpret_cast<ulonglong2 *>(o.S) + h * s_out + s_row + x;
-                const bool seeded = (o.seeded >> h) & 1u;
-                const ulonglong2 zero = make_ulonglong2(0, 0);
-                S[0] = addmul2(seeded ? S[0] : zero, a0, p, q, cr0, cr1);
-                S[s_poly] = addmul2(seeded ? S[s_poly] : zero, a1, p, q, cr0, cr1);
-            }
-            if (data)
-            {
-                ulonglong2 *ad = reinterpret_cast<ulonglong2 *>(o.add) + h * add_out + add_row + x;
-                ad[0] = addmul2(ad[0], u0, p, q, cr0, cr1);
-                if (!A)
-                {
-                    ad[add_poly] = addmul2(ad[add_poly], u1, p, q, cr0, cr1);
-                }
-            }
-        }
-    }
-}
-
-// ---- giant steps summed in the extended basis (moai_hybrid_bsgs_dot) ------------------------------------------------------------
-struct HyC1Args
-{
-    const uint64_t *S;    // [ng][B][2][L + alpha][N]: polynomial 1 of pair (h, b) is read where h < n_md
-    const uint64_t *conv; // [n_md * B][L][N], NTT form: the base conversion of the special rows of S[.][.][1]
-    const uint64_t *add;  // [ng][B][2][L][N]: the addends, polynomial 1 read
-    uint64_t *tgt;        // [n_rot * B][L][N]
-    const uint32_t *table[HY_DOT_MAX_NG]; // giant step h's index permutation, h < n_rot
-    const Tw *pinv;       // P^-1 mod q_i
-    uint32_t n_md, B;
-    HyDims d;
-};
-
-// The one-polynomial form of the mod-down's last kernel, with the giant step's permutation applied as it writes: for pair (h, b),
-//   c1'[i] = add[h][b][1][i] + (S[h][b][1][i] - conv[h B + b][i]) P^-1 mod q_i   where h < n_md (moddown_finalize_kernel's arithmetic),
-//   c1'[i] = add[h][b][1][i]                                                    otherwise (an inner sum without a switched term),
-// and tgt[h B + b][i][x] = c1'[i][table_h[x]].  blockIdx.y = (h B + b) L + i.  The target is written in order, two words per lane;
-// the two or three sources are gathered.
-__global__ __launch_bounds__(256) void hy_c1_moddown_permute_kernel(HyC1Args g)
-{
-    const HyDims &d = g.d;
-    const uint32_t pair = blockIdx.y / d.L, i = blockIdx.y % d.L, h = pair / g.B;
-    const uint64_t q = d.pc[i].q;
-    const Tw inv = g.pinv[i];
-    const size_t n = 2 * (size_t)d.n2;
-    const uint64_t *S = g.S + ((size_t)(pair * 2 + 1) * (d.L + d.alpha) + i) * n;
-    const uint64_t *u = g.conv + ((size_t)pair * d.L + i) * n;
-    const uint64_t *ad = g.add + ((size_t)(pair * 2 + 1) * d.L + i) * n;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.tgt) + (size_t)blockIdx.y * d.n2;
-    const uint2 *table = reinterpret_cast<const uint2 *>(g.table[h]);
-    const bool md = h < g.n_md;
-    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
-    {
-        const uint2 src = table[x];
-        ulonglong2 r = make_ulonglong2(ad[src.x], ad[src.y]);
-        if (md)
-        {
-            ulonglong2 v;
-            v.x = csub(mul_shoup_lazy(S[src.x] + q - u[src.x], inv.w, inv.wq, q), q);
-            v.y = csub(mul_shoup_lazy(S[src.y] + q - u[src.y], inv.w, inv.wq, q), q);
-            r = add2(v, r, q);
-        }
-        o[x] = r;
-    }
-}
-
-struct HyBsgsMacArgs
-{
-    const uint64_t *ext; // as HyMacArgs for the n_rot * B targets: digit j at ext + j * n_rot * B * L * N
-    const uint64_t *tgt; // [n_rot * B][L][N]: perm_{E_h}(c1'_h) of pair (h, b) at row block h * B + b
-    const uint64_t *S;   // [ng][B][2][L + alpha][N], canonical (zero where the inner sum has no switched term)
-    const uint64_t *add; // [ng][B][2][L][N], canonical
-    uint64_t *Z;         // [B][2][L + alpha][N]
-    const uint32_t *table[HY_DOT_MAX_NG]; // giant step h < n_rot: its index permutation
-    const uint64_t *key[HY_DOT_MAX_NG];   // and its key [beta(k - alpha)][2][k][N]
-    uint64_t fac[MOAI_MAX_RNS];           // P mod q_i
-    uint32_t n_rot, ng;  // giant steps h < n_rot have E_h != 1, n_rot <= h < ng have E_h = 1
-    uint32_t zseeded;    // Z holds the sum of the earlier groups; clear: this launch starts it
-    HyDims d;
-};
-
-// Z[b][p][row] (+)= sum_{h < ng} contribution of giant step h, for the giant steps of one group; grid as hy_mac_kernel (blockIdx.x =
-// b, blockIdx.z = row).  With T_h = S_h + (P mod q_row) a_h on the data rows and T_h = S_h on the special rows (the inner sum lifted
-// into Q P, nothing rounded):
-//   h < n_rot (E_h != 1):  Z[0] += sum_j digit_{h,j}[row] (*) key_h[j][0][row] + T_h[0][row][table_h],   Z[1] += sum_j digit_{h,j}[row]
-//                          (*) key_h[j][1][row], the digits those of perm_{E_h}(c1'_h) (steps 1-3 on tgt)
-//   h >= n_rot (E_h = 1):  Z[p] += T_h[p][row]
-// A thread owns two neighbouring output positions; the digits, the keys and Z are read in order and only T_h[0] of a rotated giant
-// step is gathered.  No B_h and no permuted T_h[0] reaches memory, and Z is read (after the first group) and written once.
-// 128-bit sums: the running sums z0, z1 are canonical residues (below 2^61).  Per giant step a sum is seeded with one of them and
-// takes the beta <= 63 products below 2^122 of the digits: below 2^61 + 63 2^122 < 2^128, one reduction.  The lifted term is then
-// one canonical residue (z + S, added canonically) plus ONE product below 2^122, reduced again.  Every giant step leaves canonical
-// residues behind, so the sum over any number of giant steps and groups is carried as residues and cannot overflow.
-__global__ __launch_bounds__(256) void hy_bsgs_mac_kernel(HyBsgsMacArgs g)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.x, B = gridDim.x, row = blockIdx.z;
-    const uint32_t prime = hy_row_prime(row, d.L, d.alpha, d.k);
-    const PrimeConst *pc = d.pc + prime;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    const bool data = row < d.L;
-    const uint64_t fac = data ? g.fac[row] : 0;
-    const size_t s_row = ((size_t)b * 2 * (d.L + d.alpha) + row) * n2, s_poly = (size_t)(d.L + d.alpha) * n2;
-    const size_t s_out = (size_t)B * 2 * s_poly, add_out = (size_t)B * 2 * d.L * n2;
-    const size_t add_row = ((size_t)b * 2 * d.L + row) * n2, add_poly = (size_t)d.L * n2; // touched only on the data rows
-    const ulonglong2 *ext = reinterpret_cast<const ulonglong2 *>(g.ext);
-    const ulonglong2 *S = reinterpret_cast<const ulonglong2 *>(g.S), *ad = reinterpret_cast<const ulonglong2 *>(g.add);
-    ulonglong2 *Z = reinterpret_cast<ulonglong2 *>(g.Z) + s_row;
-    const ulonglong2 zero = make_ulonglong2(0, 0);
-    for (uint32_t x = blockIdx.y * 256u + threadIdx.x; x < d.n2; x += gridDim.y * 256u)
-    {
-        ulonglong2 z0 = zero, z1 = zero;
-        if (g.zseeded)
-        {
-            z0 = Z[x];
-            z1 = Z[s_poly + x];
-        }
-        for (uint32_t h = 0; h < g.n_rot; ++h)
-        {
-            const uint32_t pair = h * B + b;
-            // the lifted inner sum's polynomial 0, gathered: its loads are issued before the digit loop
-            const uint2 src = reinterpret_cast<const uint2 *>(g.table[h])[x];
-            const uint64_t *Sh = g.S + 2 * (h * s_out + s_row), *ah = g.add + 2 * (h * add_out + add_row);
-            const ulonglong2 t0 = make_ulonglong2(Sh[src.x], Sh[src.y]);
-            const ulonglong2 a0 = data ? make_ulonglong2(ah[src.x], ah[src.y]) : zero;
-            const ulonglong2 *own = reinterpret_cast<const ulonglong2 *>(g.tgt) + ((size_t)pair * d.L + row) * n2; // read where row < L
-            const ulonglong2 *key = reinterpret_cast<const ulonglong2 *>(g.key[h]) + (size_t)prime * n2;
-            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y;
-            seed2(l0x, h0x, l0y, h0y, z0);
-            seed2(l1x, h1x, l1y, h1y, z1);
-            for (uint32_t j = 0; j < d.beta; ++j)
-            {
-                const ulonglong2 *op = hy_digit_operand(own, ext, n2, d.L, d.alpha, g.n_rot * B, pair, row, j);
-                const ulonglong2 o = op[x];
-                const ulonglong2 k0 = key[(size_t)(j * 2 + 0) * d.k * n2 + x];
-                const ulonglong2 k1 = key[(size_t)(j * 2 + 1) * d.k * n2 + x];
-                mac2(l0x, h0x, l0y, h0y, o, k0);
-                mac2(l1x, h1x, l1y, h1y, o, k1);
-            }
-            z1 = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
-            seed2(l0x, h0x, l0y, h0y, add2(reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1), t0, q));
-            mac2(l0x, h0x, l0y, h0y, a0, fac);
-            z0 = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
-        }
-        for (uint32_t h = g.n_rot; h < g.ng; ++h)
-        {
-            const ulonglong2 t0 = S[h * s_out + s_row + x], t1 = S[h * s_out + s_row + s_poly + x];
-            ulonglong2 a0 = zero, a1 = zero;
-            if (data)
-            {
-                a0 = ad[h * add_out + add_row + x];
-                a1 = ad[h * add_out + add_row + add_poly + x];
-            }
-            uint64_t l0x, h0x, l0y, h0y, l1x, h1x, l1y, h1y;
-            seed2(l0x, h0x, l0y, h0y, add2(z0, t0, q));
-            seed2(l1x, h1x, l1y, h1y, add2(z1, t1, q));
-            mac2(l0x, h0x, l0y, h0y, a0, fac);
-            mac2(l1x, h1x, l1y, h1y, a1, fac);
-            z0 = reduce2(l0x, h0x, l0y, h0y, q, cr0, cr1);
-            z1 = reduce2(l1x, h1x, l1y, h1y, q, cr0, cr1);
-        }
-        Z[x] = z0;
-        Z[s_poly + x] = z1;
-    }
-}
-
-struct HyKeyAddArgs
-{
-    uint64_t *key;          // [beta][2][k][N]
-    const uint64_t *newkey; // [k][N], rows < k - alpha read
-    uint64_t fac[MOAI_MAX_RNS]; // P mod q_r
-    HyDims d;                   // at L = k - alpha
-};
-
-// row r of c0 of digit r / alpha += (P mod q_r) * newkey[r]      (keygenerator.cpp:315-333 with P for the special prime)
-__global__ __launch_bounds__(256) void hy_key_add_kernel(HyKeyAddArgs g)
-{
-    const uint32_t r = blockIdx.y;
-    const PrimeConst *pc = g.d.pc + r;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, fac = g.fac[r];
-    const size_t n2 = g.d.n2;
-    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(g.key) + ((size_t)(r / g.d.alpha) * 2 * g.d.k + r) * n2;
-    const ulonglong2 *s = reinterpret_cast<const ulonglong2 *>(g.newkey) + (size_t)r * n2;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.d.n2; j += gridDim.x * 256u)
-    {
-        const ulonglong2 v = s[j];
-        ulonglong2 c = dst[j];
-        c.x = csub(c.x + mulmod_barrett(v.x, fac, q, cr0, cr1), q);
-        c.y = csub(c.y + mulmod_barrett(v.y, fac, q, cr0, cr1), q);
-        dst[j] = c;
-    }
-}
-
-// ---- relinearize + rescale: one mod-down by W = P q_{L-1} (moai_relinearize_rescale_hybrid) ---------------------------------------
-// the constants of the merged mod-down at (L, alpha), a sibling of HyTable in the context's map of device blocks: sources
-// S = {q_{L-1}, p_0 .. p_{alpha-1}}, targets q_i, i < L - 1
-struct alignas(16) HyRescaleTable
-{
-    Tw winv[MOAI_MAX_RNS]; // W^-1 mod q_i
-    Tw qinv[MOAI_MAX_RNS]; // q_{L-1}^-1 mod q_i
-    HyConv conv;           // src_pre = floor(W / 2) mod m, tgt_post = floor(W / 2) mod q_i, src_inv = (W / m)^-1, w = (W / m) mod q_i
-};
-
-struct HyProductArgs
-{
-    const uint64_t *x, *y; // [B][2][L][N], y may be x
-    uint64_t *out;         // [B][3][L][N]
-    const PrimeConst *pc;
-    uint32_t L, n2;
-};
-
-// out[b] = (x0 y0, x0 y1 + x1 y0, x1 y1) under q_i; blockIdx.y = b * L + i.  The canonical residues of moai_ct_multiply, and of
-// moai_ct_square where y is x (x0 x1 + x1 x0 = 2 x0 x1).  The middle sum is two products below 2^122: below 2^123, one reduction.
-__global__ __launch_bounds__(256) void hy_ct_product_kernel(HyProductArgs g)
-{
-    const uint32_t b = blockIdx.y / g.L, i = blockIdx.y % g.L;
-    const PrimeConst *pc = g.pc + i;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = g.n2;
-    const ulonglong2 *x0 = reinterpret_cast<const ulonglong2 *>(g.x) + ((size_t)(b * 2) * g.L + i) * n2, *x1 = x0 + (size_t)g.L * n2;
-    const ulonglong2 *y0 = reinterpret_cast<const ulonglong2 *>(g.y) + ((size_t)(b * 2) * g.L + i) * n2, *y1 = y0 + (size_t)g.L * n2;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + ((size_t)(b * 3) * g.L + i) * n2;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
-    {
-        const ulonglong2 a0 = x0[j], a1 = x1[j], b0 = y0[j], b1 = y1[j];
-        uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
-        mac2(lx, hx, ly, hy, a0, b1);
-        mac2(lx, hx, ly, hy, a1, b0);
-        o[j] = mulmod2(a0, b0, q, cr0, cr1);
-        o[(size_t)g.L * n2 + j] = reduce2(lx, hx, ly, hy, q, cr0, cr1);
-        o[2 * (size_t)g.L * n2 + j] = mulmod2(a1, b1, q, cr0, cr1);
-    }
-}
-
-struct HyLiftArgs
-{
-    uint64_t *acc;       // [B][2][L + alpha][N]: row L - 1 of both polynomials is lifted in place
-    const uint64_t *ct3; // [B][3][L][N]: row L - 1 of c_0 and c_1 read
-    uint64_t plast;      // P mod q_{L-1}
-    HyDims d;
-};
-
-struct HyLiftListArgs : HyLiftArgs
-{
-    const KsList *lst; // ciphertext b's [3][L][N] block is lst->ins[b] (ct3 unused)
-};
-
-// Z_p[L-1] = acc[p][L-1] + (P mod q_{L-1}) c_p[L-1]: the one data row among the merged mod-down's sources; blockIdx.y = b * 2 + p.
-// The sum is one canonical residue (below 2^61) plus one product below 2^122: one reduction.
-// LIST: c_p is read from the member's own block; b is uniform over the workgroup (a scalar load of the list entry).
-template <bool LIST = false>
-__global__ __launch_bounds__(256) void hy_lift_last_row_kernel(std::conditional_t<LIST, HyLiftListArgs, HyLiftArgs> g)
-{
-    const HyDims &d = g.d;
-    const uint32_t b = blockIdx.y >> 1, p = blockIdx.y & 1u, last = d.L - 1;
-    const PrimeConst *pc = d.pc + last;
-    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
-    const size_t n2 = d.n2;
-    ulonglong2 *acc = reinterpret_cast<ulonglong2 *>(g.acc) + ((size_t)blockIdx.y * (d.L + d.alpha) + last) * n2;
-    const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + last) * n2;
-    if constexpr (LIST)
-    {
-        cp = reinterpret_cast<const ulonglong2 *>(g.lst->ins[b]) + ((size_t)p * d.L + last) * n2;
-    }
-    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
-    {
-        uint64_t lx, hx, ly, hy;
-        seed2(lx, hx, ly, hy, acc[x]);
-        mac2(lx, hx, ly, hy, cp[x], g.plast);
-        acc[x] = reduce2(lx, hx, ly, hy, q, cr0, cr1);
-    }
-}
-
-struct HyRescaleFinalArgs
-{
-    const uint64_t *acc;  // [B][2][L + alpha][N]
-    const uint64_t *conv; // [2B][L - 1][N], NTT form
-    const uint64_t *ct3;  // [B][3][L][N]: c_0 and c_1 read
-    uint64_t *out;        // [B][2][L - 1][N]
-    const Tw *winv, *qinv;
-    HyDims d;
-};
-
-struct HyRescaleFinalListArgs : HyRescaleFinalArgs
-{
-    const KsList *lst; // ciphertext b's [3][L][N] block is lst->ins[b] and its [2][L - 1][N] result lst->outs[b] (ct3 and out unused)
-};
-
-// out[b][p][i] = c_p[i] [q_{L-1}^-1]_{q_i} + (acc[p][i] - conv_i) [W^-1]_{q_i} mod q_i, i < L - 1: the finish of the merged mod-down
-// with the lift (P mod q_i) c_p[i] W^-1 = c_p[i] q_{L-1}^-1 taken on its own multiplier.  blockIdx.y = (b * 2 + p) (L - 1) + i.  No
-// 128-bit sum: two Shoup products made canonical and one canonical add.
-// LIST: c_p and the output per member, as hy_lift_last_row_kernel.
-template <bool LIST = false>
-__global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(std::conditional_t<LIST, HyRescaleFinalListArgs, HyRescaleFinalArgs> g)
-{
-    const HyDims &d = g.d;
-    const uint32_t lo = d.L - 1, poly = blockIdx.y / lo, i = blockIdx.y % lo, b = poly >> 1, p = poly & 1u;
-    const uint64_t q = d.pc[i].q;
-    const Tw wi = g.winv[i], qi = g.qinv[i];
-    const size_t n2 = d.n2;
-    const ulonglong2 *acc = reinterpret_cast<const ulonglong2 *>(g.acc) + ((size_t)poly * (d.L + d.alpha) + i) * n2;
-    const ulonglong2 *u = reinterpret_cast<const ulonglong2 *>(g.conv) + (size_t)blockIdx.y * n2;
-    const ulonglong2 *cp = reinterpret_cast<const ulonglong2 *>(g.ct3) + ((size_t)(b * 3 + p) * d.L + i) * n2;
-    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(g.out) + (size_t)blockIdx.y * n2;
-    if constexpr (LIST)
-    {
-        cp = reinterpret_cast<const ulonglong2 *>(g.lst->ins[b]) + ((size_t)p * d.L + i) * n2;
-        o = reinterpret_cast<ulonglong2 *>(g.lst->outs[b]) + ((size_t)p * lo + i) * n2;
-    }
-    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
-    {
-        const ulonglong2 a = acc[x], v = u[x], c = cp[x];
-        ulonglong2 r, t;
-        r.x = csub(mul_shoup_lazy(a.x + q - v.x, wi.w, wi.wq, q), q);
-        r.y = csub(mul_shoup_lazy(a.y + q - v.y, wi.w, wi.wq, q), q);
-        t.x = csub(mul_shoup_lazy(c.x, qi.w, qi.wq, q), q);
-        t.y = csub(mul_shoup_lazy(c.y, qi.w, qi.wq, q), q);
-        o[x] = add2(r, t, q);
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static inline size_t hy_beta(size_t L, size_t alpha)
-{
-    return (L + alpha - 1) / alpha;
-}
-
 static HyDims hy_dims(const moai_ctx *c, size_t L, size_t alpha)
 {
     HyDims d;
@@ -865,6 +60,17 @@ static HyDims hy_dims(const moai_ctx *c, size_t L, size_t alpha)
     d.k = (uint32_t)c->k;
     fill_rows(d, c, L);
     return d;
+}
+
+// the bytes of scratch a chunk may take (MOAI_HYBRID_TMP_KB), for the plans of hybrid_scratch.h
+static size_t hy_budget()
+{
+    return (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
+}
+
+static uint64_t *hy_at(void *wsp, const HyPlan &p, HyRegion r)
+{
+    return at_bytes(wsp, p.off[r]);
 }
 
 // product of the context primes idx[0..cnt) except idx[skip], modulo m
@@ -881,6 +87,17 @@ static uint64_t hy_prod_mod(const moai_ctx *c, const uint32_t *idx, size_t cnt, 
     return r;
 }
 
+// P mod m, P the product of the alpha special primes
+static uint64_t hy_p_mod(const moai_ctx *c, size_t alpha, uint64_t m)
+{
+    uint64_t r = 1 % m;
+    for (size_t s = 0; s < alpha; ++s)
+    {
+        r = mulmod(r, c->primes[c->k - alpha + s] % m, m);
+    }
+    return r;
+}
+
 static uint64_t hy_invmod(uint64_t a, uint64_t q)
 {
     return powmod(a, q - 2, q);
@@ -892,107 +109,114 @@ static uint64_t hy_half_mod(uint64_t p_mod_m, uint64_t m)
     return mulmod((p_mod_m + m - 1) % m, hy_invmod(2, m), m);
 }
 
-// the device block of constants for (L, alpha); the caller holds op_mutex.  Built on first use with a blocking copy from a host
-// buffer that lives until the copy has returned.
+// cv = the mod-down by W, the product of the context primes src[0 .. nsrc), to the data primes 0 .. ntgt-1, with the rounding terms
+// of floor(W / 2) (HyConv states the formulas)
+static void hy_moddown_conv(const moai_ctx *c, HyConv &cv, const uint32_t *src, size_t nsrc, size_t ntgt)
+{
+    cv.nsrc = (uint32_t)nsrc;
+    cv.ntgt = (uint32_t)ntgt;
+    for (size_t r = 0; r < nsrc; ++r)
+    {
+        const uint64_t m = c->primes[src[r]];
+        cv.src_prime[r] = src[r];
+        cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, src, nsrc, r, m), m), m);
+        cv.src_pre[r] = hy_half_mod(0, m);
+    }
+    for (size_t i = 0; i < ntgt; ++i)
+    {
+        const uint64_t q = c->primes[i];
+        cv.tgt_prime[i] = (uint32_t)i;
+        cv.tgt_post[i] = hy_half_mod(hy_prod_mod(c, src, nsrc, nsrc, q), q);
+        for (size_t r = 0; r < nsrc; ++r)
+        {
+            cv.w[i][r] = hy_prod_mod(c, src, nsrc, r, q);
+        }
+    }
+}
+
+// The device block of constants the context caches under `key`; the caller holds op_mutex.  Built on first use: fill(host) writes the
+// zeroed block of `bytes`, which goes over with a blocking copy from a host buffer that lives until the copy has returned.
+template <class T, class Fill>
+static int hy_cached_table(moai_ctx *c, std::pair<size_t, size_t> key, size_t bytes, const char *what, const T **out, Fill &&fill)
+{
+    auto it = c->hybrid_tables.find(key);
+    if (it == c->hybrid_tables.end())
+    {
+        std::vector<unsigned char> host(bytes, 0);
+        fill(host.data());
+        void *dev = nullptr;
+        MOAI_HIP_CHECK(hipMalloc(&dev, bytes));
+        hipError_t e = hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+        {
+            (void)hipFree(dev);
+            return set_error(MOAI_EHIP, "hybrid %s constants: %s", what, hipGetErrorString(e));
+        }
+        it = c->hybrid_tables.emplace(key, dev).first;
+    }
+    *out = static_cast<const T *>(it->second);
+    return MOAI_OK;
+}
+
+// the constants for (L, alpha)
 static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
 {
-    const auto key = std::make_pair(L, alpha);
-    auto it = c->hybrid_tables.find(key);
-    if (it != c->hybrid_tables.end())
-    {
-        *out = static_cast<const HyTable *>(it->second);
-        return MOAI_OK;
-    }
     const size_t k = c->k, beta = hy_beta(L, alpha);
     const size_t conv_bytes = offsetof(HyTable, conv) + (beta + 1) * sizeof(HyConv);
     const size_t bytes = conv_bytes + beta * (L + alpha) * sizeof(uint64_t);
-    std::vector<unsigned char> host(bytes, 0);
-    HyTable *t = reinterpret_cast<HyTable *>(host.data());
-    HyConv *convs = reinterpret_cast<HyConv *>(host.data() + offsetof(HyTable, conv));
-    uint32_t special[HY_MAX_ALPHA];
-    for (size_t s = 0; s < alpha; ++s)
-    {
-        special[s] = (uint32_t)(k - alpha + s);
-    }
-    for (size_t i = 0; i < L; ++i)
-    {
-        const uint64_t q = c->primes[i];
-        t->pinv[i] = make_tw(hy_invmod(hy_prod_mod(c, special, alpha, alpha, q), q), q);
-    }
-    for (size_t j = 0; j < beta; ++j)
-    {
-        HyConv &cv = convs[j];
-        const size_t lo = j * alpha, hi = std::min(lo + alpha, L);
-        cv.nsrc = (uint32_t)(hi - lo);
-        for (size_t r = 0; r < cv.nsrc; ++r)
-        {
-            cv.src_prime[r] = (uint32_t)(lo + r);
-        }
-        for (size_t r = 0; r < cv.nsrc; ++r)
-        {
-            const uint64_t q = c->primes[lo + r];
-            cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, cv.src_prime, cv.nsrc, r, q), q), q);
-        }
-        cv.ntgt = 0;
-        for (size_t row = 0; row < L + alpha; ++row)
-        {
-            if (row >= lo && row < hi)
-            {
-                continue;
-            }
-            const uint32_t prime = (uint32_t)hy_row_prime(row, L, alpha, k);
-            const uint32_t tg = cv.ntgt++;
-            cv.tgt_prime[tg] = prime;
-            for (size_t r = 0; r < cv.nsrc; ++r)
-            {
-                cv.w[tg][r] = hy_prod_mod(c, cv.src_prime, cv.nsrc, r, c->primes[prime]);
-            }
-        }
-    }
-    {
-        HyConv &cv = convs[beta];
-        cv.nsrc = (uint32_t)alpha;
-        cv.ntgt = (uint32_t)L;
-        for (size_t s = 0; s < alpha; ++s)
-        {
-            const uint64_t p = c->primes[special[s]];
-            cv.src_prime[s] = special[s];
-            cv.src_inv[s] = make_tw(hy_invmod(hy_prod_mod(c, special, alpha, s, p), p), p);
-            cv.src_pre[s] = hy_half_mod(0, p);
-        }
+    return hy_cached_table(c, std::make_pair(L, alpha), bytes, "key-switch", out, [&](unsigned char *host) {
+        HyTable *t = reinterpret_cast<HyTable *>(host);
+        HyConv *convs = reinterpret_cast<HyConv *>(host + offsetof(HyTable, conv));
         for (size_t i = 0; i < L; ++i)
         {
             const uint64_t q = c->primes[i];
-            cv.tgt_prime[i] = (uint32_t)i;
-            cv.tgt_post[i] = hy_half_mod(hy_prod_mod(c, special, alpha, alpha, q), q);
-            for (size_t s = 0; s < alpha; ++s)
+            t->pinv[i] = make_tw(hy_invmod(hy_p_mod(c, alpha, q), q), q);
+        }
+        for (size_t j = 0; j < beta; ++j)
+        {
+            HyConv &cv = convs[j];
+            const size_t lo = j * alpha, hi = std::min(lo + alpha, L);
+            cv.nsrc = (uint32_t)(hi - lo);
+            for (size_t r = 0; r < cv.nsrc; ++r)
             {
-                cv.w[i][s] = hy_prod_mod(c, special, alpha, s, q);
+                cv.src_prime[r] = (uint32_t)(lo + r);
+            }
+            for (size_t r = 0; r < cv.nsrc; ++r)
+            {
+                const uint64_t q = c->primes[lo + r];
+                cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, cv.src_prime, cv.nsrc, r, q), q), q);
+            }
+            cv.ntgt = 0;
+            for (size_t row = 0; row < L + alpha; ++row)
+            {
+                if (row >= lo && row < hi)
+                {
+                    continue;
+                }
+                const uint32_t prime = (uint32_t)hy_row_prime(row, L, alpha, k);
+                const uint32_t tg = cv.ntgt++;
+                cv.tgt_prime[tg] = prime;
+                for (size_t r = 0; r < cv.nsrc; ++r)
+                {
+                    cv.w[tg][r] = hy_prod_mod(c, cv.src_prime, cv.nsrc, r, c->primes[prime]);
+                }
             }
         }
-    }
-    // the hoisted rotations' correction: sum_{r in R_j} q_r (D_j / q_r) = |R_j| D_j, modulo every row's prime (0 on the rows of R_j)
-    uint64_t *mult = reinterpret_cast<uint64_t *>(host.data() + conv_bytes);
-    for (size_t j = 0; j < beta; ++j)
-    {
-        const HyConv &cv = convs[j];
-        for (size_t row = 0; row < L + alpha; ++row)
+        RowMap special{};
+        hy_rowmap(c, L, alpha, 0, L, &special);
+        hy_moddown_conv(c, convs[beta], special.idx, alpha, L);
+        // the hoisted rotations' correction: sum_{r in R_j} q_r (D_j / q_r) = |R_j| D_j, modulo every row's prime (0 on the rows of R_j)
+        uint64_t *mult = reinterpret_cast<uint64_t *>(host + conv_bytes);
+        for (size_t j = 0; j < beta; ++j)
         {
-            const uint64_t m = c->primes[hy_row_prime(row, L, alpha, k)];
-            mult[j * (L + alpha) + row] = mulmod(cv.nsrc % m, hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, m), m);
+            const HyConv &cv = convs[j];
+            for (size_t row = 0; row < L + alpha; ++row)
+            {
+                const uint64_t m = c->primes[hy_row_prime(row, L, alpha, k)];
+                mult[j * (L + alpha) + row] = mulmod(cv.nsrc % m, hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, m), m);
+            }
         }
-    }
-    void *dev = nullptr;
-    MOAI_HIP_CHECK(hipMalloc(&dev, bytes));
-    hipError_t e = hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipFree(dev);
-        return set_error(MOAI_EHIP, "hybrid key-switch constants: %s", hipGetErrorString(e));
-    }
-    c->hybrid_tables[key] = dev;
-    *out = static_cast<const HyTable *>(dev);
-    return MOAI_OK;
+    });
 }
 
 static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_t src_off, uint64_t *dst, const HyConv *cv, size_t nsrc,
@@ -1010,46 +234,6 @@ static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_
     const int amax = nsrc <= 1 ? 1 : nsrc <= 2 ? 2 : nsrc <= 4 ? 4 : nsrc <= 8 ? 8 : 16;
     return dispatch<1, 2, 4, 8, 16>("digit size ", amax,
                                     [&](auto A) { return launch_rows(hy_convert_kernel<decltype(A)::value>, c, polys, s, a); });
-}
-
-// rows of N words of scratch per ciphertext: t, the converted digits, acc, the special rows, conv, and gal_rows rows of gathered
-// input (2 L: the permuted input of apply_galois; L: the third polynomial of a member of the relinearize list; 0 otherwise)
-static size_t hy_rows_per_ct(size_t L, size_t alpha, size_t gal_rows)
-{
-    const size_t beta = hy_beta(L, alpha);
-    return gal_rows + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * alpha + 2 * L;
-}
-
-struct HyLayout
-{
-    size_t gal, t, ext, acc, x, conv, total; // byte offsets
-};
-
-static HyLayout hy_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t gal_rows)
-{
-    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
-    HyLayout w;
-    w.gal = 0;
-    w.t = w.gal + align256(cb * gal_rows * row);
-    w.ext = w.t + align256(cb * L * row);
-    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
-    w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
-    w.conv = w.x + align256(cb * 2 * alpha * row);
-    w.total = w.conv + align256(cb * 2 * L * row);
-    return w;
-}
-
-// ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one
-static size_t hy_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t gal_rows)
-{
-    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
-    const size_t per = hy_rows_per_ct(L, alpha, gal_rows) * c->n * sizeof(uint64_t);
-    size_t cb = budget / per;
-    cb = cb < 1 ? 1 : cb;
-    // row-per-workgroup launches: 2 * cb * (L + alpha) rows in gridDim.y
-    const size_t cap = 65535 / (2 * (L + alpha));
-    cb = cb > cap ? cap : cb;
-    return cb < batch ? cb : batch;
 }
 
 // steps 1-3 for B ciphertexts: t [B][L][N] = INTT of the target rows tg, ext = the converted rows of every digit in NTT form
@@ -1075,17 +259,26 @@ static int hy_decompose(moai_ctx *c, const HyTable *tab, const KsTarget &tg, siz
     return MOAI_OK;
 }
 
-// step 5 up to the last kernel, for the accumulators [B][2][L + alpha][N] of B switches: x [2B][alpha][N] = INTT(special rows),
-// conv [2B][L][N] = NTT(base conversion with the rounding terms)
-static int hy_mod_down(moai_ctx *c, const HyTable *tab, const uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
-                       hipStream_t s)
+// A mod-down up to its last kernel, for `polys` polynomials whose nsrc source rows -- the last nsrc of a switch's L + alpha -- are
+// rows off .. off + nsrc - 1 of every `stride` rows at src: x [polys][nsrc][N] = INTT(those rows), conv [polys][ntgt][N] = NTT(cv's
+// base conversion with the rounding terms), ntgt = L + alpha - nsrc
+static int hy_mod_down(moai_ctx *c, const HyConv *cv, const uint64_t *src, size_t stride, size_t off, size_t nsrc, size_t ntgt, size_t polys,
+                       uint64_t *x, uint64_t *conv, size_t L, size_t alpha, hipStream_t s)
 {
     RowMap rm{};
-    hy_rowmap(c, L, alpha, 0, L, &rm); // the special rows
-    MOAI_TRY(ntt_launch(c, x, 2 * B, alpha, rm, true, s, acc, L + alpha, L));
-    MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + hy_beta(L, alpha), alpha, 2 * B, s));
-    MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
-    return ntt_launch(c, conv, 2 * B, L, rm, false, s);
+    hy_rowmap(c, L, alpha, 0, ntgt, &rm);
+    MOAI_TRY(ntt_launch(c, x, polys, nsrc, rm, true, s, src, stride, off));
+    MOAI_TRY(hy_convert(c, x, nsrc, 0, conv, cv, nsrc, polys, s));
+    MOAI_TRY(make_rowmap(c, ntgt, nullptr, &rm));
+    return ntt_launch(c, conv, polys, ntgt, rm, false, s);
+}
+
+// step 5 up to the last kernel, for the accumulators [B][2][L + alpha][N] of B switches: x [2B][alpha][N] = INTT(special rows),
+// conv [2B][L][N]
+static int hy_step5(moai_ctx *c, const HyTable *tab, const uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
+                    hipStream_t s)
+{
+    return hy_mod_down(c, tab->conv + hy_beta(L, alpha), acc, L + alpha, L, alpha, L, 2 * B, x, conv, L, alpha, s);
 }
 
 // the hy_mac_kernel / hy_hoisted_mac_kernel grid: blockIdx.x = ciphertext, .y covers a row, .z = row of L + alpha
@@ -1096,29 +289,11 @@ static int hy_mac_grid(const moai_ctx *c, size_t B, size_t rows, dim3 *grid)
     return MOAI_OK;
 }
 
-// step 4 for B ciphertexts with the key m.key or, with a list, member b's own
-static int hy_mac(moai_ctx *c, const HyMacArgs &m, size_t B, const KsList *lst, hipStream_t s)
+// step 4 for B ciphertexts: acc = the inner products of the digits of the target rows tg (ext, and the target's own rows) with `key`
+// or, with tg.lst, member b's own
+static int hy_mac(moai_ctx *c, const KsTarget &tg, const uint64_t *ext, const uint64_t *key, uint64_t *acc, size_t L, size_t alpha, size_t B,
+                  hipStream_t s)
 {
-    dim3 grid;
-    MOAI_TRY(hy_mac_grid(c, B, m.d.L + m.d.alpha, &grid));
-    return plain_or_list<HyMacListArgs>(m, lst, [&](const auto &args, auto LIST) {
-        hipLaunchKernelGGL(hy_mac_kernel<decltype(LIST)::value>, grid, dim3(256), 0, s, args);
-        MOAI_LAUNCH_CHECK();
-        return MOAI_OK;
-    });
-}
-
-// one chunk of B ciphertexts: out [B][2][L][N] = add (KsAddend) + the switch of the target rows tg.  With tg.lst (a device record,
-// common.h KsList) ciphertext b's key is lst->keys[b] and the last kernel writes lst->outs[b], adds lst->sums[b] and, for add.mode 1,
-// reads the addend from lst->ins[b]; key and out are not used
-static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
-                           size_t B, void *wsp, const HyLayout &w, const KsAddend &add, hipStream_t s)
-{
-    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
-    uint64_t *conv = at_bytes(wsp, w.conv);
-    // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
-    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, t, ext, s));
-    // 4. the inner products with the key
     HyMacArgs m;
     m.ext = ext;
     m.tgt = tg.ptr;
@@ -1127,9 +302,35 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
     m.tgt_stride = (uint32_t)tg.stride_rows;
     m.tgt_off = (uint32_t)tg.off_rows;
     m.d = hy_dims(c, L, alpha);
-    MOAI_TRY(hy_mac(c, m, B, tg.lst, s));
+    dim3 grid;
+    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+    return plain_or_list<HyMacListArgs>(m, tg.lst, [&](const auto &args, auto LIST) {
+        hipLaunchKernelGGL(hy_mac_kernel<decltype(LIST)::value>, grid, dim3(256), 0, s, args);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
+}
+
+// rotations of the next pass of a hoisted MAC over the digits when `left` are left: MOAI_HYBRID_HOIST_NR of them, 4, 2 or 1
+static size_t hy_pass_size(size_t left)
+{
+    const long per_pass = tuning(K_HYBRID_HOIST_NR);
+    return per_pass >= 4 && left >= 4 ? 4 : (per_pass >= 2 && left >= 2 ? 2 : 1);
+}
+
+// one chunk of B ciphertexts: out [B][2][L][N] = add (KsAddend) + the switch of the target rows tg.  With tg.lst (a device record,
+// common.h KsList) ciphertext b's key is lst->keys[b] and the last kernel writes lst->outs[b], adds lst->sums[b] and, for add.mode 1,
+// reads the addend from lst->ins[b]; key and out are not used
+static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
+                           size_t B, void *wsp, const HyPlan &w, const KsAddend &add, hipStream_t s)
+{
+    uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
+    // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
+    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, hy_at(wsp, w, HY_T), ext, s));
+    // 4. the inner products with the key
+    MOAI_TRY(hy_mac(c, tg, ext, key, acc, L, alpha, B, s));
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
-    MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, B, s));
+    MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, w, HY_X), conv, L, alpha, B, s));
     return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, tg.lst, s);
 }
 
@@ -1213,12 +414,11 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     const HyTable *tab;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
-    const size_t gal_rows = kind == HY_GALOIS ? 2 * L : 0;
-    const size_t cb = hy_chunk(c, L, alpha, batch, gal_rows);
-    const HyLayout w = hy_layout(c, L, alpha, cb, gal_rows);
+    // 2 L rows in front: the permuted input of apply_galois
+    const HyPlan w = hy_plan_switch(n, L, alpha, batch, kind == HY_GALOIS ? 2 * L : 0, hy_budget());
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
-    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+    return for_chunks(batch, w.cb, [&](size_t b0, size_t B) {
         switch (kind)
         {
         case HY_SWITCH:
@@ -1233,7 +433,7 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
         {
             // out = (galois(in0), 0) + switch(galois(in1)) [+ sum]      (evaluator.cpp:2631-2654): both summands are added by the last
             // kernel, so a chunk of out is written once, after the chunk of in has been permuted into the scratch
-            uint64_t *tmp = at_bytes(wsp, w.gal);
+            uint64_t *tmp = hy_at(wsp, w, HY_HEAD);
             MOAI_TRY(moai_galois_permute(c, in + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
             return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { tmp, 2 * L, L }, key, L, alpha, B, wsp, w,
                                    { tmp, 2 * L, 2, sum ? sum + b0 * 2 * L * n : nullptr }, s);
@@ -1243,57 +443,6 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
 }
 
 // ---- hoisted rotations ------------------------------------------------------------------------------------------------------
-// rows of N words of scratch: per ciphertext t and the converted digits, per (rotation in flight, ciphertext) acc, the special
-// rows, conv and the permuted c0
-static inline size_t hy_hoist_shared_rows(size_t L, size_t alpha)
-{
-    return hy_beta(L, alpha) * (L + alpha);
-}
-
-static inline size_t hy_hoist_rotation_rows(size_t L, size_t alpha)
-{
-    return 2 * (L + alpha) + 2 * alpha + 2 * L + L;
-}
-
-struct HyHoistLayout
-{
-    size_t flag, t, ext, acc, x, conv, c0, total; // byte offsets
-};
-
-static HyHoistLayout hy_hoist_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
-{
-    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
-    HyHoistLayout w;
-    w.flag = 0;
-    w.t = 256;
-    w.ext = w.t + align256(cb * L * row);
-    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
-    w.x = w.acc + align256(G * cb * 2 * (L + alpha) * row);
-    w.conv = w.x + align256(G * cb * 2 * alpha * row);
-    w.c0 = w.conv + align256(G * cb * 2 * L * row);
-    w.total = w.c0 + align256(G * cb * L * row);
-    return w;
-}
-
-// ciphertexts per chunk (*cb) and rotations in flight (*G) under MOAI_HYBRID_TMP_KB: as many ciphertexts as fit with one rotation
-// in flight, then as many rotations as fit beside them; at least one of each, and no row-per-workgroup grid above 65535 (the
-// mod-down runs over 2 * cb * G polynomials of at most L + alpha rows)
-static void hy_hoist_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t R, size_t *cb_out, size_t *G_out)
-{
-    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
-    const size_t shared = hy_hoist_shared_rows(L, alpha) * row, rot = hy_hoist_rotation_rows(L, alpha) * row;
-    const size_t cap = 65535 / (2 * (L + alpha));
-    size_t cb = budget / (shared + rot);
-    cb = cb < 1 ? 1 : cb;
-    cb = cb > cap ? cap : cb;
-    cb = cb < batch ? cb : batch;
-    size_t G = budget / cb > shared ? (budget / cb - shared) / rot : 0;
-    G = G < 1 ? 1 : G;
-    G = G > cap / cb ? cap / cb : G;
-    *cb_out = cb;
-    *G_out = G < R ? G : R;
-}
-
 static int hy_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t elt, size_t L, size_t alpha, uint64_t *correction, hipStream_t s)
 {
     const size_t rows = L + alpha, beta = hy_beta(L, alpha);
@@ -1317,6 +466,29 @@ static int hy_hoist_correction(moai_ctx *c, const uint64_t *key, uint32_t elt, s
     return launch_rows(hy_hoist_correction_kernel, c, 2 * rows, s, g);
 }
 
+// What a chunk of the three hoisted families (their plans keep the probe's flag in front) begins with, under the lock it holds to the
+// chunk's end -- per chunk, because a fallback re-enters hy_entry, which takes the lock itself: the constants, the workspace of plan p
+// and, with `decompose`, steps 1-3 on the UNPERMUTED c1 of the B ciphertexts at `in` [B][2][L][N], once for everything that reads the
+// digits, and the zero probe: *fallback is set when INTT(c1) holds a zero coefficient, for which the identity does not hold.  Then
+// body(tab, wsp).
+template <class F>
+static int hy_hoisted_chunk(moai_ctx *c, const HyPlan &p, const uint64_t *in, size_t L, size_t alpha, size_t B, bool decompose,
+                            bool *fallback, hipStream_t s, F &&body)
+{
+    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+    const HyTable *tab;
+    MOAI_TRY(hy_table(c, L, alpha, &tab));
+    void *wsp;
+    MOAI_TRY(workspace(c, p.total, s, &wsp));
+    if (decompose)
+    {
+        uint64_t *t = hy_at(wsp, p, HY_T);
+        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, t, hy_at(wsp, p, HY_EXT), s));
+        MOAI_TRY(probe_any_zero(c, t, B * L * c->n, static_cast<uint32_t *>(wsp), s, fallback));
+    }
+    return body(tab, wsp);
+}
+
 struct HyHoistRotations
 {
     size_t R;
@@ -1331,12 +503,11 @@ struct HyHoistRotations
 static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, const HyHoistRotations &rot, size_t r0, size_t g,
                           uint64_t *acc, size_t L, size_t alpha, size_t B, hipStream_t s)
 {
-    const long per_pass = tuning(K_HYBRID_HOIST_NR);
     dim3 grid;
     MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
     for (size_t r = 0; r < g;)
     {
-        const size_t nr = per_pass >= 4 && r + 3 < g ? 4 : (per_pass >= 2 && r + 1 < g ? 2 : 1);
+        const size_t nr = hy_pass_size(g - r);
         HyHoistMacArgs m;
         m.ext = ext;
         m.in = in;
@@ -1359,101 +530,38 @@ static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, 
     return MOAI_OK;
 }
 
-// one chunk of B ciphertexts at `in` [B][2][L][N]; rotation r's result goes to rot.outs[r] + out_off.  *fallback is set when
-// INTT(c1) holds a zero coefficient: nothing but the scratch has been written then, and the caller makes the separate calls.
+// one chunk of B ciphertexts at `in` [B][2][L][N] on plan p; rotation r's result goes to rot.outs[r] + out_off.  *fallback is set
+// when INTT(c1) holds a zero coefficient: nothing but the scratch has been written then, and the caller makes the separate calls.
 static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyHoistRotations &rot, size_t L, size_t alpha, size_t B,
-                              size_t cb, size_t G, bool *fallback, hipStream_t s)
+                              const HyPlan &p, bool *fallback, hipStream_t s)
 {
     const size_t n = c->n;
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
-    const HyTable *tab;
-    MOAI_TRY(hy_table(c, L, alpha, &tab));
-    const HyHoistLayout w = hy_hoist_layout(c, L, alpha, cb, G);
-    void *wsp;
-    MOAI_TRY(workspace(c, w.total, s, &wsp));
-    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
-    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
-    uint64_t *conv = at_bytes(wsp, w.conv), *pc0 = at_bytes(wsp, w.c0);
-    // steps 1-3 on the UNPERMUTED c1, once for all rotations
-    MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, t, ext, s));
-    MOAI_TRY(probe_any_zero(c, t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
-    if (*fallback)
-    {
-        return MOAI_OK;
-    }
-    return for_chunks(rot.R, G, [&](size_t r0, size_t g) {
-        MOAI_TRY(hy_hoisted_mac(c, ext, in, rot, r0, g, acc, L, alpha, B, s));
-        // pc0 [g][B][L][N] = perm_r(c0): the addend of the even polynomials (add_mode 2, ciphertexts L rows apart)
-        for (size_t r = 0; r < g; ++r)
+    return hy_hoisted_chunk(c, p, in, L, alpha, B, true, fallback, s, [&](const HyTable *tab, void *wsp) -> int {
+        if (*fallback)
         {
-            MOAI_TRY(galois_permute_c0(c, in, pc0 + r * B * L * n, B, L, rot.elts[r0 + r], s));
+            return MOAI_OK;
         }
-        // steps 5 over (rotation, ciphertext) pairs
-        MOAI_TRY(hy_mod_down(c, tab, acc, x, conv, L, alpha, g * B, s));
-        for (size_t r = 0; r < g; ++r)
-        {
-            MOAI_TRY(moddown_finalize(c, acc + r * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + r * B * 2 * L * n,
-                                      rot.outs[r0 + r] + out_off, 2 * B, L, tab->pinv, { pc0 + r * B * L * n, L, 2 }, nullptr, s));
-        }
-        return MOAI_OK;
+        uint64_t *acc = hy_at(wsp, p, HY_ACC), *conv = hy_at(wsp, p, HY_CONV), *pc0 = hy_at(wsp, p, HY_C0);
+        return for_chunks(rot.R, p.G, [&](size_t r0, size_t g) {
+            MOAI_TRY(hy_hoisted_mac(c, hy_at(wsp, p, HY_EXT), in, rot, r0, g, acc, L, alpha, B, s));
+            // pc0 [g][B][L][N] = perm_r(c0): the addend of the even polynomials (add_mode 2, ciphertexts L rows apart)
+            for (size_t r = 0; r < g; ++r)
+            {
+                MOAI_TRY(galois_permute_c0(c, in, pc0 + r * B * L * n, B, L, rot.elts[r0 + r], s));
+            }
+            // steps 5 over (rotation, ciphertext) pairs
+            MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, p, HY_X), conv, L, alpha, g * B, s));
+            for (size_t r = 0; r < g; ++r)
+            {
+                MOAI_TRY(moddown_finalize(c, acc + r * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + r * B * 2 * L * n,
+                                          rot.outs[r0 + r] + out_off, 2 * B, L, tab->pinv, { pc0 + r * B * L * n, L, 2 }, nullptr, s));
+            }
+            return MOAI_OK;
+        });
     });
 }
 
 // ---- plaintext-weighted sums of hoisted rotations -------------------------------------------------------------------------------
-// rows of N words of scratch: per ciphertext t, the converted digits and the unhoisted route's permuted input and accumulators; per
-// (output in flight, ciphertext) the sums S, the special rows, conv and the addend.  Nothing grows with R.
-static inline size_t hy_dot_shared_rows(size_t L, size_t alpha)
-{
-    return hy_beta(L, alpha) * (L + alpha) + 2 * L + 2 * (L + alpha);
-}
-
-static inline size_t hy_dot_output_rows(size_t L, size_t alpha)
-{
-    return 2 * (L + alpha) + 2 * alpha + 2 * L + 2 * L;
-}
-
-struct HyDotLayout
-{
-    size_t flag, t, ext, gal, acc, S, x, conv, add, total; // byte offsets
-};
-
-static HyDotLayout hy_dot_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
-{
-    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
-    HyDotLayout w;
-    w.flag = 0;
-    w.t = 256;
-    w.ext = w.t + align256(cb * L * row);
-    w.gal = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
-    w.acc = w.gal + align256(cb * 2 * L * row);
-    w.S = w.acc + align256(cb * 2 * (L + alpha) * row);
-    w.x = w.S + align256(G * cb * 2 * (L + alpha) * row);
-    w.conv = w.x + align256(G * cb * 2 * alpha * row);
-    w.add = w.conv + align256(G * cb * 2 * L * row);
-    w.total = w.add + align256(G * cb * 2 * L * row);
-    return w;
-}
-
-// ciphertexts per chunk (*cb) and outputs in flight (*G) under MOAI_HYBRID_TMP_KB, as hy_hoist_chunk sizes ciphertexts and rotations:
-// at least one of each, G at most HY_DOT_MAX_NG, and no row-per-workgroup grid above 65535 (the mod-down runs over 2 * cb * G
-// polynomials of at most L + alpha rows)
-static void hy_dot_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t n_out, size_t *cb_out, size_t *G_out)
-{
-    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
-    const size_t shared = hy_dot_shared_rows(L, alpha) * row, out = hy_dot_output_rows(L, alpha) * row;
-    const size_t cap = 65535 / (2 * (L + alpha));
-    size_t cb = budget / (shared + out);
-    cb = cb < 1 ? 1 : cb;
-    cb = cb > cap ? cap : cb;
-    cb = cb < batch ? cb : batch;
-    size_t G = budget / cb > shared ? (budget / cb - shared) / out : 0;
-    G = G < 1 ? 1 : G;
-    G = G > cap / cb ? cap / cb : G;
-    G = G > (size_t)HY_DOT_MAX_NG ? (size_t)HY_DOT_MAX_NG : G;
-    *cb_out = cb;
-    *G_out = G < n_out ? G : n_out;
-}
-
 struct HyDotTerms
 {
     size_t R, n_out;
@@ -1512,6 +620,11 @@ struct HyDotScratch
     uint64_t *t, *ext, *gal, *acc;
 };
 
+static HyDotScratch hy_dot_scratch(void *wsp, const HyPlan &p)
+{
+    return { hy_at(wsp, p, HY_T), hy_at(wsp, p, HY_EXT), hy_at(wsp, p, HY_GAL), hy_at(wsp, p, HY_ACC) };
+}
+
 // The inner stage for the outputs gs[0 .. ng) of one chunk of B ciphertexts at `in`, up to its step 5: o.S and o.add (o.ng = ng)
 // receive S_g and the addend a_g of every output, and o.seeded tells which outputs have a switched term (the S of the others is
 // not written).  sc.t / sc.ext hold the digits of the unpermuted c1 unless `fallback`, which takes every rotation through the
@@ -1520,7 +633,6 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
                         HyDotOutputs &o, const HyDotScratch &sc, size_t L, size_t alpha, size_t B, bool fallback, hipStream_t s)
 {
     const size_t ct_words = B * 2 * L * c->n;
-    const long per_pass = tuning(K_HYBRID_HOIST_NR);
     dim3 grid;
     MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
     MOAI_HIP_CHECK(hipMemsetAsync(o.add, 0, ng * ct_words * sizeof(uint64_t), s));
@@ -1537,7 +649,7 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
         // the hoisted MAC, MOAI_HYBRID_HOIST_NR rotations per pass over the digits, weighted into S and the addend
         for (size_t i = 0; i < rot.size();)
         {
-            const size_t left = rot.size() - i, nr = per_pass >= 4 && left >= 4 ? 4 : (per_pass >= 2 && left >= 2 ? 2 : 1);
+            const size_t nr = hy_pass_size(rot.size() - i);
             HyHoistMacArgs m{};
             m.ext = sc.ext;
             m.in = in;
@@ -1563,20 +675,12 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
     else
     {
         // per rotation: permute, steps 1-4 into one scratch accumulator, then its products
+        const KsTarget tg = { sc.gal, 2 * L, L };
         for (size_t r : rot)
         {
             MOAI_TRY(moai_galois_permute(c, in, sc.gal, B * 2, L, tm.elts[r], s));
-            MOAI_TRY(hy_decompose(c, tab, { sc.gal, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
-            HyMacArgs m;
-            m.ext = sc.ext;
-            m.tgt = sc.gal;
-            m.key = tm.keys[r];
-            m.acc = sc.acc;
-            m.tgt_stride = (uint32_t)(2 * L);
-            m.tgt_off = (uint32_t)L;
-            m.d = hy_dims(c, L, alpha);
-            hipLaunchKernelGGL(hy_mac_kernel<false>, grid, dim3(256), 0, s, m);
-            MOAI_LAUNCH_CHECK();
+            MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, sc.t, sc.ext, s));
+            MOAI_TRY(hy_mac(c, tg, sc.ext, tm.keys[r], sc.acc, L, alpha, B, s));
             MOAI_TRY(hy_dot_term(c, sc.acc, sc.gal, o, tm, gs, ng, r, L, alpha, B, s));
         }
     }
@@ -1587,129 +691,54 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
     return MOAI_OK;
 }
 
-// one chunk of B ciphertexts at `in` [B][2][L][N]; output g's result goes to tm.outs[g] + out_off.  sw: the outputs with a term whose
-// element is not 1, G of them in flight; the others (idn) are sums of plain products.  *fallback is set when INTT(c1) holds a zero
-// coefficient: the chunk then takes every rotation through the unhoisted steps 1-4 on the permuted input, to the same bits.
+// one chunk of B ciphertexts at `in` [B][2][L][N] on plan p; output g's result goes to tm.outs[g] + out_off.  sw: the outputs with a
+// term whose element is not 1, p.G of them in flight; the others (idn) are sums of plain products.  *fallback is set when INTT(c1)
+// holds a zero coefficient: the chunk then takes every rotation through the unhoisted steps 1-4 on the permuted input, to the same
+// bits.
 static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyDotTerms &tm, const std::vector<size_t> &sw,
-                            const std::vector<size_t> &idn, size_t L, size_t alpha, size_t B, size_t cb, size_t G, bool *fallback,
-                            hipStream_t s)
+                            const std::vector<size_t> &idn, size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, hipStream_t s)
 {
     const size_t n = c->n, ct_words = B * 2 * L * n;
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
-    const HyTable *tab;
-    MOAI_TRY(hy_table(c, L, alpha, &tab));
-    const HyDotLayout w = hy_dot_layout(c, L, alpha, cb, G);
-    void *wsp;
-    MOAI_TRY(workspace(c, w.total, s, &wsp));
-    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
-    const HyDotScratch sc = { at_bytes(wsp, w.t), at_bytes(wsp, w.ext), at_bytes(wsp, w.gal), at_bytes(wsp, w.acc) };
-    uint64_t *S = at_bytes(wsp, w.S), *x = at_bytes(wsp, w.x), *conv = at_bytes(wsp, w.conv), *add = at_bytes(wsp, w.add);
-    if (!sw.empty())
-    {
-        // steps 1-3 on the UNPERMUTED c1, once for all rotations and outputs
-        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
-        MOAI_TRY(probe_any_zero(c, sc.t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
-    }
-    MOAI_TRY(for_chunks(sw.size(), G, [&](size_t g0, size_t ng) {
-        const size_t *gs = sw.data() + g0;
-        HyDotOutputs o{};
-        o.S = S;
-        o.add = add;
-        o.ng = (uint32_t)ng;
-        MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs, ng, o, sc, L, alpha, B, *fallback, s));
-        // step 5 once per output, over (output, ciphertext) pairs
-        MOAI_TRY(hy_mod_down(c, tab, S, x, conv, L, alpha, ng * B, s));
-        for (size_t h = 0; h < ng; ++h)
-        {
-            MOAI_TRY(moddown_finalize(c, S + h * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + h * ct_words, tm.outs[gs[h]] + out_off,
-                                      2 * B, L, tab->pinv, { add + h * ct_words, 2 * L, 1 }, nullptr, s));
-        }
-        return MOAI_OK;
-    }));
-    // outputs of identity terms only: no step 5, the sum is formed in the output itself
-    for (size_t g : idn)
-    {
-        HyDotOutputs o{};
-        o.add = tm.outs[g] + out_off;
-        o.ng = 1;
-        MOAI_HIP_CHECK(hipMemsetAsync(o.add, 0, ct_words * sizeof(uint64_t), s));
-        for (size_t r = 0; r < tm.R; ++r)
-        {
-            if (tm.plains[g * tm.R + r])
+    // steps 1-3 and the probe only where an output has a switched term
+    return hy_hoisted_chunk(c, p, in, L, alpha, B, !sw.empty(), fallback, s, [&](const HyTable *tab, void *wsp) -> int {
+        const HyDotScratch sc = hy_dot_scratch(wsp, p);
+        uint64_t *S = hy_at(wsp, p, HY_S), *conv = hy_at(wsp, p, HY_CONV), *add = hy_at(wsp, p, HY_ADD);
+        MOAI_TRY(for_chunks(sw.size(), p.G, [&](size_t g0, size_t ng) {
+            const size_t *gs = sw.data() + g0;
+            HyDotOutputs o{};
+            o.S = S;
+            o.add = add;
+            o.ng = (uint32_t)ng;
+            MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs, ng, o, sc, L, alpha, B, *fallback, s));
+            // step 5 once per output, over (output, ciphertext) pairs
+            MOAI_TRY(hy_step5(c, tab, S, hy_at(wsp, p, HY_X), conv, L, alpha, ng * B, s));
+            for (size_t h = 0; h < ng; ++h)
             {
-                MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, &g, 1, r, L, alpha, B, s));
+                MOAI_TRY(moddown_finalize(c, S + h * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + h * ct_words,
+                                          tm.outs[gs[h]] + out_off, 2 * B, L, tab->pinv, { add + h * ct_words, 2 * L, 1 }, nullptr, s));
+            }
+            return MOAI_OK;
+        }));
+        // outputs of identity terms only: no step 5, the sum is formed in the output itself
+        for (size_t g : idn)
+        {
+            HyDotOutputs o{};
+            o.add = tm.outs[g] + out_off;
+            o.ng = 1;
+            MOAI_HIP_CHECK(hipMemsetAsync(o.add, 0, ct_words * sizeof(uint64_t), s));
+            for (size_t r = 0; r < tm.R; ++r)
+            {
+                if (tm.plains[g * tm.R + r])
+                {
+                    MOAI_TRY(hy_dot_term(c, nullptr, in, o, tm, &g, 1, r, L, alpha, B, s));
+                }
             }
         }
-    }
-    return MOAI_OK;
+        return MOAI_OK;
+    });
 }
 
 // ---- giant steps summed in the extended basis --------------------------------------------------------------------------------------
-// rows of N words of scratch: per ciphertext the inner stage's shared rows, the sum Z and the special rows and conv of its step 5; per
-// (giant step in flight, ciphertext) S and the addend, the special rows and conv of c1', the permuted c1' and its t and digits
-static inline size_t hy_bsgs_shared_rows(size_t L, size_t alpha)
-{
-    return hy_dot_shared_rows(L, alpha) + 2 * (L + alpha) + 2 * alpha + 2 * L;
-}
-
-static inline size_t hy_bsgs_giant_rows(size_t L, size_t alpha)
-{
-    return 2 * (L + alpha) + 2 * L + alpha + L + L + hy_beta(L, alpha) * (L + alpha);
-}
-
-struct HyBsgsLayout
-{
-    size_t flag, t, ext, gal, acc, Z, zx, zconv, S, add, x, conv, tgt, t2, ext2, total; // byte offsets
-};
-
-static HyBsgsLayout hy_bsgs_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t G)
-{
-    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
-    HyBsgsLayout w;
-    w.flag = 0;
-    w.t = 256;
-    w.ext = w.t + align256(cb * L * row);
-    w.gal = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
-    w.acc = w.gal + align256(cb * 2 * L * row);
-    w.Z = w.acc + align256(cb * 2 * (L + alpha) * row);
-    w.zx = w.Z + align256(cb * 2 * (L + alpha) * row);
-    w.zconv = w.zx + align256(cb * 2 * alpha * row);
-    w.S = w.zconv + align256(cb * 2 * L * row);
-    w.add = w.S + align256(G * cb * 2 * (L + alpha) * row);
-    w.x = w.add + align256(G * cb * 2 * L * row);
-    w.conv = w.x + align256(G * cb * alpha * row);
-    w.tgt = w.conv + align256(G * cb * L * row);
-    w.t2 = w.tgt + align256(G * cb * L * row);
-    w.ext2 = w.t2 + align256(G * cb * L * row);
-    w.total = w.ext2 + align256(G * cb * (beta * (L + alpha) - L) * row);
-    return w;
-}
-
-// ciphertexts per chunk (*cb) and giant steps in flight (*G) under MOAI_HYBRID_TMP_KB.  A group of giant steps repeats the inner
-// stage's MAC over every baby step it uses while a batch chunk repeats nothing, so the giant steps come first: all of them (at most
-// HY_DOT_MAX_NG) are in flight when one ciphertext fits beside them, and cb is the largest count that fits with them; else one
-// ciphertext per chunk with as many giant steps as fit, at least one.  No row-per-workgroup grid above 65535 (the transforms run over
-// cb * G polynomials of at most 2 (L + alpha) rows), and the chunks of a batch are evened out.
-static void hy_bsgs_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t n_giant, size_t *cb_out, size_t *G_out)
-{
-    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10, row = c->n * sizeof(uint64_t);
-    const size_t shared = hy_bsgs_shared_rows(L, alpha) * row, giant = hy_bsgs_giant_rows(L, alpha) * row;
-    const size_t cap = 65535 / (2 * (L + alpha));
-    size_t G = std::min(std::min(n_giant, (size_t)HY_DOT_MAX_NG), cap);
-    size_t cb = budget / (shared + G * giant);
-    if (cb < 1)
-    {
-        cb = 1;
-        G = budget > shared ? (budget - shared) / giant : 0;
-        G = G < 1 ? 1 : G;
-    }
-    cb = cb > cap / G ? cap / G : cb;
-    cb = cb < batch ? cb : batch;
-    const size_t chunks = (batch + cb - 1) / cb;
-    *cb_out = (batch + chunks - 1) / chunks;
-    *G_out = G;
-}
-
 struct HyBsgsGiants
 {
     size_t n;
@@ -1719,260 +748,145 @@ struct HyBsgsGiants
     const std::vector<char> *switched; // giant step g's inner sum has a term whose baby element is not 1
 };
 
-// one chunk of B ciphertexts at `in` [B][2][L][N] into out [B][2][L][N]; tm holds the baby terms with one output per giant step
-// (tm.outs unused), G giant steps in flight.  *fallback as in hy_dot_chunk_run: the inner stage's zero probe.
+// one chunk of B ciphertexts at `in` [B][2][L][N] into out [B][2][L][N] on plan p; tm holds the baby terms with one output per giant
+// step (tm.outs unused), p.G giant steps in flight.  *fallback as in hy_dot_chunk_run: the inner stage's zero probe.
 static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, const HyDotTerms &tm, const HyBsgsGiants &gi, bool any_switched,
-                             size_t L, size_t alpha, size_t B, size_t cb, size_t G, bool *fallback, hipStream_t s)
+                             size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, hipStream_t s)
 {
     const size_t n = c->n, s_words = B * 2 * (L + alpha) * n;
-    std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
-    const HyTable *tab;
-    MOAI_TRY(hy_table(c, L, alpha, &tab));
-    const HyBsgsLayout w = hy_bsgs_layout(c, L, alpha, cb, G);
-    void *wsp;
-    MOAI_TRY(workspace(c, w.total, s, &wsp));
-    uint32_t *flag = reinterpret_cast<uint32_t *>(at_bytes(wsp, w.flag));
-    const HyDotScratch sc = { at_bytes(wsp, w.t), at_bytes(wsp, w.ext), at_bytes(wsp, w.gal), at_bytes(wsp, w.acc) };
-    uint64_t *Z = at_bytes(wsp, w.Z), *zx = at_bytes(wsp, w.zx), *zconv = at_bytes(wsp, w.zconv);
-    uint64_t *S = at_bytes(wsp, w.S), *add = at_bytes(wsp, w.add), *x = at_bytes(wsp, w.x), *conv = at_bytes(wsp, w.conv);
-    uint64_t *tgt = at_bytes(wsp, w.tgt), *t2 = at_bytes(wsp, w.t2), *ext2 = at_bytes(wsp, w.ext2);
-    if (any_switched)
-    {
-        // steps 1-3 on the UNPERMUTED c1, once for all baby steps and giant steps
-        MOAI_TRY(hy_decompose(c, tab, { in, 2 * L, L }, L, alpha, B, sc.t, sc.ext, s));
-        MOAI_TRY(probe_any_zero(c, sc.t, B * L * n, flag, s, fallback)); // a zero coefficient: the identity does not hold for it
-    }
-    HyBsgsMacArgs m{};
-    m.ext = ext2;
-    m.tgt = tgt;
-    m.S = S;
-    m.add = add;
-    m.Z = Z;
-    m.d = hy_dims(c, L, alpha);
-    uint32_t special[HY_MAX_ALPHA];
-    for (size_t t = 0; t < alpha; ++t)
-    {
-        special[t] = (uint32_t)(c->k - alpha + t);
-    }
-    for (size_t i = 0; i < L; ++i)
-    {
-        m.fac[i] = hy_prod_mod(c, special, alpha, alpha, c->primes[i]);
-    }
-    dim3 grid;
-    MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
-    MOAI_TRY(for_chunks(gi.n, G, [&](size_t g0, size_t ng) {
-        // the group's giant steps in the order the kernels index them: rotated ones whose c1' takes a mod-down, rotated ones whose
-        // inner sum has no switched term, then those of element 1 (a sum of canonical residues does not depend on the order)
-        std::vector<size_t> gs;
-        size_t n_md = 0, n_rot = 0;
-        for (int cls = 0; cls < 3; ++cls)
+    return hy_hoisted_chunk(c, p, in, L, alpha, B, any_switched, fallback, s, [&](const HyTable *tab, void *wsp) -> int {
+        const HyDotScratch sc = hy_dot_scratch(wsp, p);
+        uint64_t *Z = hy_at(wsp, p, HY_Z), *zconv = hy_at(wsp, p, HY_ZCONV);
+        uint64_t *S = hy_at(wsp, p, HY_S), *add = hy_at(wsp, p, HY_ADD), *x = hy_at(wsp, p, HY_X), *conv = hy_at(wsp, p, HY_CONV);
+        uint64_t *tgt = hy_at(wsp, p, HY_TGT), *ext2 = hy_at(wsp, p, HY_EXT2);
+        HyBsgsMacArgs m{};
+        m.ext = ext2;
+        m.tgt = tgt;
+        m.S = S;
+        m.add = add;
+        m.Z = Z;
+        m.d = hy_dims(c, L, alpha);
+        for (size_t i = 0; i < L; ++i)
         {
-            for (size_t g = g0; g < g0 + ng; ++g)
+            m.fac[i] = hy_p_mod(c, alpha, c->primes[i]);
+        }
+        dim3 grid;
+        MOAI_TRY(hy_mac_grid(c, B, L + alpha, &grid));
+        MOAI_TRY(for_chunks(gi.n, p.G, [&](size_t g0, size_t ng) {
+            // the group's giant steps in the order the kernels index them: rotated ones whose c1' takes a mod-down, rotated ones whose
+            // inner sum has no switched term, then those of element 1 (a sum of canonical residues does not depend on the order)
+            std::vector<size_t> gs;
+            size_t n_md = 0, n_rot = 0;
+            for (int cls = 0; cls < 3; ++cls)
             {
-                const int is = gi.elts[g] == 1 ? 2 : ((*gi.switched)[g] ? 0 : 1);
-                if (is == cls)
+                for (size_t g = g0; g < g0 + ng; ++g)
                 {
-                    gs.push_back(g);
+                    const int is = gi.elts[g] == 1 ? 2 : ((*gi.switched)[g] ? 0 : 1);
+                    if (is == cls)
+                    {
+                        gs.push_back(g);
+                    }
+                }
+                n_md = cls == 0 ? gs.size() : n_md;
+                n_rot = cls == 1 ? gs.size() : n_rot;
+            }
+            HyDotOutputs o{};
+            o.S = S;
+            o.add = add;
+            o.ng = (uint32_t)ng;
+            MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs.data(), ng, o, sc, L, alpha, B, *fallback, s));
+            for (size_t h = 0; h < ng; ++h)
+            {
+                if (!((o.seeded >> h) & 1u))
+                {
+                    MOAI_HIP_CHECK(hipMemsetAsync(S + h * s_words, 0, s_words * sizeof(uint64_t), s)); // no switched term: S_g = 0
                 }
             }
-            n_md = cls == 0 ? gs.size() : n_md;
-            n_rot = cls == 1 ? gs.size() : n_rot;
-        }
-        HyDotOutputs o{};
-        o.S = S;
-        o.add = add;
-        o.ng = (uint32_t)ng;
-        MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs.data(), ng, o, sc, L, alpha, B, *fallback, s));
-        for (size_t h = 0; h < ng; ++h)
-        {
-            if (!((o.seeded >> h) & 1u))
+            if (n_rot)
             {
-                MOAI_HIP_CHECK(hipMemsetAsync(S + h * s_words, 0, s_words * sizeof(uint64_t), s)); // no switched term: S_g = 0
+                if (n_md)
+                {
+                    // step 5 of S_g[1] alone: the special rows of polynomial 1 of every (giant step, ciphertext) pair
+                    MOAI_TRY(hy_mod_down(c, tab->conv + hy_beta(L, alpha), S, 2 * (L + alpha), (L + alpha) + L, alpha, L, n_md * B, x, conv,
+                                         L, alpha, s));
+                }
+                // tgt = perm_{E_g}(c1'_g), then steps 1-3 on all (giant step, ciphertext) pairs at once
+                HyC1Args a{};
+                a.S = S;
+                a.conv = conv;
+                a.add = add;
+                a.tgt = tgt;
+                a.pinv = tab->pinv;
+                a.n_md = (uint32_t)n_md;
+                a.B = (uint32_t)B;
+                a.d = m.d;
+                for (size_t h = 0; h < n_rot; ++h)
+                {
+                    a.table[h] = m.table[h] = gi.tables[gs[h]];
+                    m.key[h] = gi.keys[gs[h]];
+                }
+                MOAI_TRY(launch_rows(hy_c1_moddown_permute_kernel, c, n_rot * B * L, s, a));
+                MOAI_TRY(hy_decompose(c, tab, { tgt, L, 0 }, L, alpha, n_rot * B, hy_at(wsp, p, HY_T2), ext2, s));
             }
-        }
-        if (n_rot)
-        {
-            if (n_md)
-            {
-                // step 5 of S_g[1] alone: the special rows of polynomial 1 of every (giant step, ciphertext) pair
-                RowMap rm{};
-                hy_rowmap(c, L, alpha, 0, L, &rm);
-                MOAI_TRY(ntt_launch(c, x, n_md * B, alpha, rm, true, s, S, 2 * (L + alpha), (L + alpha) + L));
-                MOAI_TRY(hy_convert(c, x, alpha, 0, conv, tab->conv + hy_beta(L, alpha), alpha, n_md * B, s));
-                MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
-                MOAI_TRY(ntt_launch(c, conv, n_md * B, L, rm, false, s));
-            }
-            // tgt = perm_{E_g}(c1'_g), then steps 1-3 on all (giant step, ciphertext) pairs at once
-            HyC1Args a{};
-            a.S = S;
-            a.conv = conv;
-            a.add = add;
-            a.tgt = tgt;
-            a.pinv = tab->pinv;
-            a.n_md = (uint32_t)n_md;
-            a.B = (uint32_t)B;
-            a.d = m.d;
-            for (size_t h = 0; h < n_rot; ++h)
-            {
-                a.table[h] = m.table[h] = gi.tables[gs[h]];
-                m.key[h] = gi.keys[gs[h]];
-            }
-            MOAI_TRY(launch_rows(hy_c1_moddown_permute_kernel, c, n_rot * B * L, s, a));
-            MOAI_TRY(hy_decompose(c, tab, { tgt, L, 0 }, L, alpha, n_rot * B, t2, ext2, s));
-        }
-        m.n_rot = (uint32_t)n_rot;
-        m.ng = (uint32_t)ng;
-        m.zseeded = g0 ? 1u : 0u;
-        hipLaunchKernelGGL(hy_bsgs_mac_kernel, grid, dim3(256), 0, s, m);
-        MOAI_LAUNCH_CHECK();
-        return MOAI_OK;
-    }));
-    // the one final step 5, both polynomials, no addend
-    MOAI_TRY(hy_mod_down(c, tab, Z, zx, zconv, L, alpha, B, s));
-    return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
+            m.n_rot = (uint32_t)n_rot;
+            m.ng = (uint32_t)ng;
+            m.zseeded = g0 ? 1u : 0u;
+            hipLaunchKernelGGL(hy_bsgs_mac_kernel, grid, dim3(256), 0, s, m);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        }));
+        // the one final step 5, both polynomials, no addend
+        MOAI_TRY(hy_step5(c, tab, Z, hy_at(wsp, p, HY_ZX), zconv, L, alpha, B, s));
+        return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
+    });
 }
 
 // ---- relinearize + rescale --------------------------------------------------------------------------------------------------------
 // the merged mod-down's constants share the context's map with hy_table's blocks: the same (L, alpha) with this bit in alpha
 constexpr size_t HY_RESCALE_KEY = (size_t)1 << 32;
 
-// the device block of the merged mod-down's constants for (L, alpha), L >= 2 and alpha + 1 <= HY_MAX_ALPHA; the caller holds
-// op_mutex.  Built on first use with a blocking copy, as hy_table.
+// the constants of the merged mod-down for (L, alpha), L >= 2 and alpha + 1 <= HY_MAX_ALPHA
 static int hy_rescale_table(moai_ctx *c, size_t L, size_t alpha, const HyRescaleTable **out)
 {
     const auto key = std::make_pair(L, alpha | HY_RESCALE_KEY);
-    auto it = c->hybrid_tables.find(key);
-    if (it != c->hybrid_tables.end())
-    {
-        *out = static_cast<const HyRescaleTable *>(it->second);
-        return MOAI_OK;
-    }
-    std::vector<unsigned char> host(sizeof(HyRescaleTable), 0);
-    HyRescaleTable *t = reinterpret_cast<HyRescaleTable *>(host.data());
-    HyConv &cv = t->conv;
-    const size_t k = c->k, last = L - 1;
-    cv.nsrc = (uint32_t)(alpha + 1);
-    cv.ntgt = (uint32_t)last;
-    cv.src_prime[0] = (uint32_t)last;
-    for (size_t s = 0; s < alpha; ++s)
-    {
-        cv.src_prime[1 + s] = (uint32_t)(k - alpha + s);
-    }
-    for (size_t r = 0; r < cv.nsrc; ++r)
-    {
-        const uint64_t m = c->primes[cv.src_prime[r]];
-        cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, cv.src_prime, cv.nsrc, r, m), m), m);
-        cv.src_pre[r] = hy_half_mod(0, m);
-    }
-    for (size_t i = 0; i < last; ++i)
-    {
-        const uint64_t q = c->primes[i];
-        const uint64_t w_mod_q = hy_prod_mod(c, cv.src_prime, cv.nsrc, cv.nsrc, q);
-        cv.tgt_prime[i] = (uint32_t)i;
-        cv.tgt_post[i] = hy_half_mod(w_mod_q, q);
-        for (size_t r = 0; r < cv.nsrc; ++r)
+    return hy_cached_table(c, key, sizeof(HyRescaleTable), "relinearize-rescale", out, [&](unsigned char *host) {
+        HyRescaleTable *t = reinterpret_cast<HyRescaleTable *>(host);
+        const size_t last = L - 1;
+        RowMap src{}; // q_{L-1}, then the special primes: W is their product
+        const size_t nsrc = hy_rowmap(c, L, alpha, 0, last, &src);
+        hy_moddown_conv(c, t->conv, src.idx, nsrc, last);
+        for (size_t i = 0; i < last; ++i)
         {
-            cv.w[i][r] = hy_prod_mod(c, cv.src_prime, cv.nsrc, r, q);
+            const uint64_t q = c->primes[i];
+            t->winv[i] = make_tw(hy_invmod(hy_prod_mod(c, src.idx, nsrc, nsrc, q), q), q);
+            t->qinv[i] = make_tw(hy_invmod(c->primes[last] % q, q), q);
         }
-        t->winv[i] = make_tw(hy_invmod(w_mod_q, q), q);
-        t->qinv[i] = make_tw(hy_invmod(c->primes[last] % q, q), q);
-    }
-    void *dev = nullptr;
-    MOAI_HIP_CHECK(hipMalloc(&dev, host.size()));
-    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        (void)hipFree(dev);
-        return set_error(MOAI_EHIP, "hybrid relinearize-rescale constants: %s", hipGetErrorString(e));
-    }
-    c->hybrid_tables[key] = dev;
-    *out = static_cast<const HyRescaleTable *>(dev);
-    return MOAI_OK;
-}
-
-// rows of N words of scratch per ciphertext: t, the converted digits, acc, the alpha + 1 source rows of the merged mod-down, conv
-// over L - 1 rows, and head_rows rows in front of them (3 L: the three-polynomial product of moai_multiply_relin_rescale_hybrid;
-// L: the gathered third polynomial of a member of the list form; 0 otherwise)
-static size_t hy_rescale_rows_per_ct(size_t L, size_t alpha, size_t head_rows)
-{
-    const size_t beta = hy_beta(L, alpha);
-    return head_rows + L + (beta * (L + alpha) - L) + 2 * (L + alpha) + 2 * (alpha + 1) + 2 * (L - 1);
-}
-
-struct HyRescaleLayout
-{
-    size_t prod, t, ext, acc, x, conv, total; // byte offsets
-};
-
-static HyRescaleLayout hy_rescale_layout(const moai_ctx *c, size_t L, size_t alpha, size_t cb, size_t head_rows)
-{
-    const size_t row = c->n * sizeof(uint64_t), beta = hy_beta(L, alpha);
-    HyRescaleLayout w;
-    w.prod = 0;
-    w.t = w.prod + align256(cb * head_rows * row);
-    w.ext = w.t + align256(cb * L * row);
-    w.acc = w.ext + align256(cb * (beta * (L + alpha) - L) * row);
-    w.x = w.acc + align256(cb * 2 * (L + alpha) * row);
-    w.conv = w.x + align256(cb * 2 * (alpha + 1) * row);
-    w.total = w.conv + align256(cb * 2 * (L - 1) * row);
-    return w;
-}
-
-// ciphertexts per chunk: as many as MOAI_HYBRID_TMP_KB holds, at least one; no row-per-workgroup grid above 65535 (the widest runs
-// over 3 * cb * L rows with the product, 2 * cb * (L + alpha) without)
-static size_t hy_rescale_chunk(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t head_rows)
-{
-    const size_t budget = (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
-    const size_t per = hy_rescale_rows_per_ct(L, alpha, head_rows) * c->n * sizeof(uint64_t);
-    size_t cb = budget / per;
-    cb = cb < 1 ? 1 : cb;
-    const size_t cap = 65535 / std::max(2 * (L + alpha), 3 * L);
-    cb = cb > cap ? cap : cb;
-    return cb < batch ? cb : batch;
+    });
 }
 
 // one chunk of B ciphertexts: out [B][2][L - 1][N] = the merged mod-down of (c0, c1) + switch(c2) for ct3 [B][3][L][N].  With lst (a
-// device record, common.h KsList) c2 [B][L][N] has been gathered to w.gal, c0 and c1 are read from lst->ins[b], the key is
+// device record, common.h KsList) c2 [B][L][N] has been gathered to the plan's head, c0 and c1 are read from lst->ins[b], the key is
 // lst->keys[b] and the result goes to lst->outs[b]; ct3, key and out are not used
 static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescaleTable *rt, const uint64_t *ct3, const uint64_t *key,
-                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyRescaleLayout &w, hipStream_t s,
+                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyPlan &w, hipStream_t s,
                                 const KsList *lst = nullptr)
 {
-    uint64_t *t = at_bytes(wsp, w.t), *ext = at_bytes(wsp, w.ext), *acc = at_bytes(wsp, w.acc), *x = at_bytes(wsp, w.x);
-    uint64_t *conv = at_bytes(wsp, w.conv);
+    uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
     // steps 1-4 on c2, as every switch
-    const KsTarget tg = lst ? KsTarget{ at_bytes(wsp, w.prod), L, 0 } : KsTarget{ ct3, 3 * L, 2 * L };
-    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, t, ext, s));
-    HyMacArgs m;
-    m.ext = ext;
-    m.tgt = tg.ptr;
-    m.key = key;
-    m.acc = acc;
-    m.tgt_stride = (uint32_t)tg.stride_rows;
-    m.tgt_off = (uint32_t)tg.off_rows;
-    m.d = hy_dims(c, L, alpha);
-    MOAI_TRY(hy_mac(c, m, B, lst, s));
+    const KsTarget tg = lst ? KsTarget{ hy_at(wsp, w, HY_HEAD), L, 0, lst } : KsTarget{ ct3, 3 * L, 2 * L };
+    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, hy_at(wsp, w, HY_T), ext, s));
+    MOAI_TRY(hy_mac(c, tg, ext, key, acc, L, alpha, B, s));
     // the lift of the one data row among the sources (the rows below it take theirs in the last kernel)
     HyLiftArgs lf;
     lf.acc = acc;
     lf.ct3 = ct3;
-    lf.d = m.d;
-    uint32_t special[HY_MAX_ALPHA];
-    for (size_t sp = 0; sp < alpha; ++sp)
-    {
-        special[sp] = (uint32_t)(c->k - alpha + sp);
-    }
-    lf.plast = hy_prod_mod(c, special, alpha, alpha, c->primes[L - 1]);
+    lf.d = hy_dims(c, L, alpha);
+    lf.plast = hy_p_mod(c, alpha, c->primes[L - 1]);
     MOAI_TRY(plain_or_list<HyLiftListArgs>(lf, lst, [&](const auto &args, auto LIST) {
         return launch_rows(hy_lift_last_row_kernel<decltype(LIST)::value>, c, 2 * B, s, args);
     }));
     // the merged mod-down: x = INTT(rows L-1 .. L+alpha-1 of acc, contiguous), conv = NTT(base conversion with W's rounding terms)
-    RowMap rm{};
-    hy_rowmap(c, L, alpha, 0, L - 1, &rm);
-    MOAI_TRY(ntt_launch(c, x, 2 * B, alpha + 1, rm, true, s, acc, L + alpha, L - 1));
-    MOAI_TRY(hy_convert(c, x, alpha + 1, 0, conv, &rt->conv, alpha + 1, 2 * B, s));
-    MOAI_TRY(make_rowmap(c, L - 1, nullptr, &rm));
-    MOAI_TRY(ntt_launch(c, conv, 2 * B, L - 1, rm, false, s));
+    MOAI_TRY(hy_mod_down(c, &rt->conv, acc, L + alpha, L - 1, alpha + 1, L - 1, 2 * B, hy_at(wsp, w, HY_X), conv, L, alpha, s));
     HyRescaleFinalArgs f;
     f.acc = acc;
     f.conv = conv;
@@ -1980,7 +894,7 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
     f.out = out;
     f.winv = rt->winv; // device address arithmetic only
     f.qinv = rt->qinv;
-    f.d = m.d;
+    f.d = lf.d;
     return plain_or_list<HyRescaleFinalListArgs>(f, lst, [&](const auto &args, auto LIST) {
         return launch_rows(hy_rescale_finalize_kernel<decltype(LIST)::value>, c, 2 * B * (L - 1), s, args);
     });
@@ -2029,18 +943,18 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
     const HyRescaleTable *rt;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
     MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
-    const size_t cb = hy_rescale_chunk(c, L, alpha, batch, product ? 3 * L : 0);
-    const HyRescaleLayout w = hy_rescale_layout(c, L, alpha, cb, product ? 3 * L : 0);
+    // 3 L rows in front: the three-polynomial product
+    const HyPlan w = hy_plan_rescale(n, L, alpha, batch, product ? 3 * L : 0, hy_budget());
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
-    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+    return for_chunks(batch, w.cb, [&](size_t b0, size_t B) {
         const uint64_t *ct3 = x + b0 * 3 * L * n;
         if (product)
         {
             HyProductArgs g;
             g.x = x + b0 * 2 * L * n;
             g.y = y + b0 * 2 * L * n;
-            g.out = at_bytes(wsp, w.prod);
+            g.out = hy_at(wsp, w, HY_HEAD);
             fill_rows(g, c, L);
             MOAI_TRY(launch_rows(hy_ct_product_kernel, c, B * L, s, g));
             ct3 = g.out;
@@ -2063,9 +977,9 @@ enum
 //   HY_LIST_RESCALE  the same through the merged mod-down; outs[i] [2][L - 1][N]
 // Everything is validated before anything is enqueued (the context-free part and the overlaps are keyswitch.hip's own checks).  A
 // pass takes min(KS_LIST_MAX, the chunk MOAI_HYBRID_TMP_KB allows) members: its record goes to the device as a kernel argument,
-// galois_gather_list permutes the members (or, with the identity table, collects their third polynomials) into the chunk's
-// contiguous scratch, steps 1-3 and the mod-down's transforms run on that scratch as they do for a batch, and the MAC and the last
-// kernels take the member's key, addends and output from the record.
+// galois_gather_list permutes the members (or, with the identity table, collects their third polynomials) into the head of the
+// chunk's contiguous scratch, steps 1-3 and the mod-down's transforms run on that scratch as they do for a batch, and the MAC and the
+// last kernels take the member's key, addends and output from the record.
 static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint64_t *const *outs, size_t L, size_t alpha,
                         const uint32_t *elts, const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n,
                         void *stream)
@@ -2096,23 +1010,14 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
         MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
     }
     const size_t gal_rows = relin ? L : 2 * L; // rows per member of the gathered target
-    const size_t nb = std::min(KS_LIST_MAX, rescale ? hy_rescale_chunk(c, L, alpha, n, gal_rows) : hy_chunk(c, L, alpha, n, gal_rows));
-    HyLayout w{};
-    HyRescaleLayout wr{};
-    if (rescale)
-    {
-        wr = hy_rescale_layout(c, L, alpha, nb, gal_rows);
-    }
-    else
-    {
-        w = hy_layout(c, L, alpha, nb, gal_rows);
-    }
+    const HyPlan w = rescale ? hy_plan_rescale(c->n, L, alpha, n, gal_rows, hy_budget(), KS_LIST_MAX)
+                             : hy_plan_switch(c->n, L, alpha, n, gal_rows, hy_budget(), KS_LIST_MAX);
     const size_t sz_list = align256(sizeof(KsList));
     void *wsp;
-    MOAI_TRY(workspace(c, sz_list + (rescale ? wr.total : w.total), s, &wsp));
+    MOAI_TRY(workspace(c, sz_list + w.total, s, &wsp));
     KsList *dlist = static_cast<KsList *>(wsp);
     void *chunk = at_bytes(wsp, sz_list);
-    return for_chunks(n, nb, [&](size_t m0, size_t cnt) {
+    return for_chunks(n, w.cb, [&](size_t m0, size_t cnt) {
         KsList h;
         for (size_t e = 0; e < KS_LIST_MAX; ++e)
         {
@@ -2125,7 +1030,7 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
             h.key_rows[e] = (uint32_t)c->k; // the whole layout
         }
         MOAI_TRY(ks_list_write(h, dlist, s));
-        uint64_t *tmp = at_bytes(chunk, rescale ? wr.prod : w.gal);
+        uint64_t *tmp = hy_at(chunk, w, HY_HEAD);
         switch (kind)
         {
         case HY_LIST_GALOIS:
@@ -2138,9 +1043,93 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
             return hy_switch_chunk(c, tab, nullptr, { tmp, L, 0, dlist }, nullptr, L, alpha, cnt, chunk, w, { nullptr, 0, 1 }, s);
         default:
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
-            return hy_rescale_chunk_run(c, tab, rt, nullptr, nullptr, nullptr, L, alpha, cnt, chunk, wr, s, dlist);
+            return hy_rescale_chunk_run(c, tab, rt, nullptr, nullptr, nullptr, L, alpha, cnt, chunk, w, s, dlist);
         }
     });
+}
+
+// ---- what the entry points of the hoisted families share ------------------------------------------------------------------------------
+// an even element is refused before the context is looked at: oddness needs none
+static int hy_odd_check(const uint32_t *elts, size_t n)
+{
+    for (size_t r = 0; elts && r < n; ++r)
+    {
+        MOAI_TRY(galois_elt_check(nullptr, elts[r]));
+    }
+    return MOAI_OK;
+}
+
+// output i of outs, ct_bytes long, against the input and the outputs before it
+static int hy_output_alias_check(uint64_t *const *outs, size_t i, const uint64_t *in, size_t ct_bytes)
+{
+    if (overlap(outs[i], ct_bytes, in, ct_bytes))
+    {
+        return set_error(MOAI_EINVAL, "an output must not alias the input");
+    }
+    for (size_t q = 0; q < i; ++q)
+    {
+        if (overlap(outs[i], ct_bytes, outs[q], ct_bytes))
+        {
+            return set_error(MOAI_EINVAL, "an output must not alias another output");
+        }
+    }
+    return MOAI_OK;
+}
+
+// (*tables)[r] = the permutation table of elts[r], built before the first launch of the call; with skip_identity null where the
+// element is 1
+static int hy_galois_tables(moai_ctx *c, const uint32_t *elts, size_t n, bool skip_identity, std::vector<const uint32_t *> *tables)
+{
+    tables->assign(n, nullptr);
+    for (size_t r = 0; r < n; ++r)
+    {
+        if (!skip_identity || elts[r] != 1)
+        {
+            MOAI_TRY(galois_table(c, elts[r], &(*tables)[r]));
+        }
+    }
+    return MOAI_OK;
+}
+
+// the terms plains[g * R + r], r < R, of sum g: whether it has any, and whether one of them is switched (its element is not 1)
+static void hy_term_census(const uint64_t *const *plains, size_t g, size_t R, const uint32_t *elts, bool *any, bool *switched)
+{
+    *any = *switched = false;
+    for (size_t r = 0; r < R; ++r)
+    {
+        if (plains[g * R + r])
+        {
+            *any = true;
+            *switched = *switched || elts[r] != 1;
+        }
+    }
+}
+
+// run(off, B, &fallback) for every chunk of at most cb of the batch's ciphertexts of ct_words words each, off the chunk's word offset;
+// a chunk that reports a fallback sets *used_fallback (where given) and then runs on_fallback(off, B)
+template <class Run, class OnFallback>
+static int hy_batch_chunks(size_t batch, size_t cb, size_t ct_words, int *used_fallback, Run &&run, OnFallback &&on_fallback)
+{
+    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
+        const size_t off = b0 * ct_words;
+        bool fallback = false;
+        MOAI_TRY(run(off, B, &fallback));
+        if (fallback)
+        {
+            if (used_fallback)
+            {
+                *used_fallback = 1;
+            }
+            MOAI_TRY(on_fallback(off, B));
+        }
+        return MOAI_OK;
+    });
+}
+
+template <class Run>
+static int hy_batch_chunks(size_t batch, size_t cb, size_t ct_words, int *used_fallback, Run &&run)
+{
+    return hy_batch_chunks(batch, cb, ct_words, used_fallback, run, [](size_t, size_t) { return MOAI_OK; });
 }
 
 } // namespace moai
@@ -2177,14 +1166,9 @@ extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq,
     a.key = out;
     a.newkey = new_key_ntt;
     a.d = hy_dims(c, Lmax, alpha);
-    uint32_t special[HY_MAX_ALPHA];
-    for (size_t s = 0; s < alpha; ++s)
-    {
-        special[s] = (uint32_t)(k - alpha + s);
-    }
     for (size_t r = 0; r < MOAI_MAX_RNS; ++r)
     {
-        a.fac[r] = r < Lmax ? hy_prod_mod(c, special, alpha, alpha, c->primes[r]) : 0;
+        a.fac[r] = r < Lmax ? hy_p_mod(c, alpha, c->primes[r]) : 0;
     }
     return launch_rows(hy_key_add_kernel, c, Lmax, stream, a);
 }
@@ -2300,47 +1284,26 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
             return set_error(MOAI_EINVAL, "null key, correction or output");
         }
         MOAI_TRY(galois_elt_check(c, galois_elts[r]));
-        if (overlap(outs[r], ct_bytes, in, ct_bytes))
-        {
-            return set_error(MOAI_EINVAL, "an output must not alias the input");
-        }
-        for (size_t q = 0; q < r; ++q)
-        {
-            if (overlap(outs[r], ct_bytes, outs[q], ct_bytes))
-            {
-                return set_error(MOAI_EINVAL, "an output must not alias another output");
-            }
-        }
+        MOAI_TRY(hy_output_alias_check(outs, r, in, ct_bytes));
     }
     MOAI_TRY(enter_device(c));
     hipStream_t s = (hipStream_t)stream;
-    std::vector<const uint32_t *> tables(R);
-    for (size_t r = 0; r < R; ++r)
-    {
-        MOAI_TRY(galois_table(c, galois_elts[r], &tables[r])); // built before the first launch of the call
-    }
+    std::vector<const uint32_t *> tables;
+    MOAI_TRY(hy_galois_tables(c, galois_elts, R, false, &tables));
     const HyHoistRotations rot = { R, galois_elts, tables.data(), keys, corrections, outs };
-    size_t cb, G;
-    hy_hoist_chunk(c, L, alpha, batch, R, &cb, &G);
-    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
-        const size_t off = b0 * 2 * L * n;
-        bool fallback = false;
-        MOAI_TRY(hy_hoist_chunk_run(c, in + off, off, rot, L, alpha, B, cb, G, &fallback, s));
-        if (fallback)
-        {
+    const HyPlan p = hy_plan_hoisted(n, L, alpha, batch, R, hy_budget());
+    return hy_batch_chunks(
+        batch, p.cb, 2 * L * n, used_fallback,
+        [&](size_t off, size_t B, bool *fallback) { return hy_hoist_chunk_run(c, in + off, off, rot, L, alpha, B, p, fallback, s); },
+        [&](size_t off, size_t B) {
             // the separate rotations of this chunk, each on a copy of the input (they take the lock and the workspace themselves)
-            if (used_fallback)
-            {
-                *used_fallback = 1;
-            }
             for (size_t r = 0; r < R; ++r)
             {
                 MOAI_HIP_CHECK(hipMemcpyAsync(outs[r] + off, in + off, B * 2 * L * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
                 MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, outs[r] + off, keys[r], L, alpha, galois_elts[r], B, stream));
             }
-        }
-        return MOAI_OK;
-    });
+            return MOAI_OK;
+        });
 }
 
 extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64_t *const *outs, size_t n_out, size_t L, size_t alpha,
@@ -2357,10 +1320,7 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
     {
         *used_fallback = 0;
     }
-    for (size_t r = 0; galois_elts && r < R; ++r)
-    {
-        MOAI_TRY(galois_elt_check(nullptr, galois_elts[r])); // oddness first: it needs no context
-    }
+    MOAI_TRY(hy_odd_check(galois_elts, R));
     MOAI_TRY(hy_check(c, alpha, L, true));
     if (batch == 0 || n_out == 0)
     {
@@ -2386,26 +1346,9 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
         {
             return set_error(MOAI_EINVAL, "null output");
         }
-        if (overlap(outs[g], ct_bytes, in, ct_bytes))
-        {
-            return set_error(MOAI_EINVAL, "an output must not alias the input");
-        }
-        for (size_t q = 0; q < g; ++q)
-        {
-            if (overlap(outs[g], ct_bytes, outs[q], ct_bytes))
-            {
-                return set_error(MOAI_EINVAL, "an output must not alias another output");
-            }
-        }
-        bool any = false, switched = false;
-        for (size_t r = 0; r < R; ++r)
-        {
-            if (plains[g * R + r])
-            {
-                any = true;
-                switched = switched || galois_elts[r] != 1;
-            }
-        }
+        MOAI_TRY(hy_output_alias_check(outs, g, in, ct_bytes));
+        bool any, switched;
+        hy_term_census(plains, g, R, galois_elts, &any, &switched);
         if (!any)
         {
             return set_error(MOAI_EINVAL, "output %zu has no term", g);
@@ -2414,26 +1357,12 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
     }
     MOAI_TRY(enter_device(c));
     hipStream_t s = (hipStream_t)stream;
-    std::vector<const uint32_t *> tables(R, nullptr);
-    for (size_t r = 0; r < R; ++r)
-    {
-        if (galois_elts[r] != 1)
-        {
-            MOAI_TRY(galois_table(c, galois_elts[r], &tables[r])); // built before the first launch of the call
-        }
-    }
+    std::vector<const uint32_t *> tables;
+    MOAI_TRY(hy_galois_tables(c, galois_elts, R, true, &tables));
     const HyDotTerms tm = { R, n_out, galois_elts, tables.data(), keys, corrections, plains, outs };
-    size_t cb, G;
-    hy_dot_chunk(c, L, alpha, batch, std::max<size_t>(sw.size(), 1), &cb, &G);
-    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
-        const size_t off = b0 * 2 * L * n;
-        bool fallback = false;
-        MOAI_TRY(hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, cb, G, &fallback, s));
-        if (fallback && used_fallback)
-        {
-            *used_fallback = 1;
-        }
-        return MOAI_OK;
+    const HyPlan p = hy_plan_dot(n, L, alpha, batch, std::max<size_t>(sw.size(), 1), HY_DOT_MAX_NG, hy_budget());
+    return hy_batch_chunks(batch, p.cb, 2 * L * n, used_fallback, [&](size_t off, size_t B, bool *fallback) {
+        return hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, p, fallback, s);
     });
 }
 
@@ -2448,14 +1377,8 @@ extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *o
     {
         *used_fallback = 0;
     }
-    for (size_t r = 0; baby_elts && r < R; ++r)
-    {
-        MOAI_TRY(galois_elt_check(nullptr, baby_elts[r])); // oddness first: it needs no context
-    }
-    for (size_t g = 0; giant_elts && g < n_giant; ++g)
-    {
-        MOAI_TRY(galois_elt_check(nullptr, giant_elts[g]));
-    }
+    MOAI_TRY(hy_odd_check(baby_elts, R));
+    MOAI_TRY(hy_odd_check(giant_elts, n_giant));
     MOAI_TRY(hy_check(c, alpha, L, true));
     if (batch == 0)
     {
@@ -2491,51 +1414,25 @@ extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *o
         {
             return set_error(MOAI_EINVAL, "null key of giant step %zu", g);
         }
-        bool any = false;
-        for (size_t r = 0; r < R; ++r)
-        {
-            if (plains[g * R + r])
-            {
-                any = true;
-                switched[g] = switched[g] || baby_elts[r] != 1;
-            }
-        }
+        bool any, sw;
+        hy_term_census(plains, g, R, baby_elts, &any, &sw);
         if (!any)
         {
             return set_error(MOAI_EINVAL, "giant step %zu has no term", g);
         }
-        any_switched = any_switched || switched[g];
+        switched[g] = sw;
+        any_switched = any_switched || sw;
     }
     MOAI_TRY(enter_device(c));
     hipStream_t s = (hipStream_t)stream;
-    std::vector<const uint32_t *> baby_tables(R, nullptr), giant_tables(n_giant, nullptr);
-    for (size_t r = 0; r < R; ++r)
-    {
-        if (baby_elts[r] != 1)
-        {
-            MOAI_TRY(galois_table(c, baby_elts[r], &baby_tables[r])); // built before the first launch of the call
-        }
-    }
-    for (size_t g = 0; g < n_giant; ++g)
-    {
-        if (giant_elts[g] != 1)
-        {
-            MOAI_TRY(galois_table(c, giant_elts[g], &giant_tables[g]));
-        }
-    }
+    std::vector<const uint32_t *> baby_tables, giant_tables;
+    MOAI_TRY(hy_galois_tables(c, baby_elts, R, true, &baby_tables));
+    MOAI_TRY(hy_galois_tables(c, giant_elts, n_giant, true, &giant_tables));
     const HyDotTerms tm = { R, n_giant, baby_elts, baby_tables.data(), baby_keys, baby_corrections, plains, nullptr };
     const HyBsgsGiants gi = { n_giant, giant_elts, giant_tables.data(), giant_keys, &switched };
-    size_t cb, G;
-    hy_bsgs_chunk(c, L, alpha, batch, n_giant, &cb, &G);
-    return for_chunks(batch, cb, [&](size_t b0, size_t B) {
-        const size_t off = b0 * 2 * L * n;
-        bool fallback = false;
-        MOAI_TRY(hy_bsgs_chunk_run(c, in + off, out + off, tm, gi, any_switched, L, alpha, B, cb, G, &fallback, s));
-        if (fallback && used_fallback)
-        {
-            *used_fallback = 1;
-        }
-        return MOAI_OK;
+    const HyPlan p = hy_plan_bsgs(n, L, alpha, batch, n_giant, HY_DOT_MAX_NG, hy_budget());
+    return hy_batch_chunks(batch, p.cb, 2 * L * n, used_fallback, [&](size_t off, size_t B, bool *fallback) {
+        return hy_bsgs_chunk_run(c, in + off, out + off, tm, gi, any_switched, L, alpha, B, p, fallback, s);
     });
 }
 
