@@ -609,7 +609,9 @@ size_t moai_ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes,
  *   MOAI_MODE_OF_NTT_FORWARD moai_ntt_forward's tiled kernels (N >= 4096; L, rows ignored): LAZY16, LAZY8, GUARD2, NOGUARD, FPN, FPR
  *   MOAI_MODE_OF_NTT_INVERSE moai_ntt_inverse's tiled kernels: LAZY16, LAZY8, GUARD (the exact integer butterflies), FPN or FPR
  * Limits: FPN 33 q < 2^52; FPR q < 2^51; NOGUARD 36 q < 2^64 and, in the key switch, 36 q^2 L < 2^128; LAZY16 / LAZY8 q < 2^60;
- * GUARD / GUARD2 any q < 2^61.  MOAI_EINVAL for a null argument or an unknown `op`, MOAI_ERANGE for prime >= k. */
+ * GUARD / GUARD2 any q < 2^61.  MOAI_EINVAL for a null argument or an unknown `op`, MOAI_ERANGE for prime >= k.
+ * The degrees below N = 4096 have no arithmetic modes: one set of integer kernels (Harvey butterflies, a 128-bit key-switch sum
+ * that needs L q^2 < 2^128) serves every prime below 2^61 there, and the answer of this query says nothing about them. */
 #define MOAI_MODE_LAZY16 (-3)
 #define MOAI_MODE_LAZY8 (-2)
 #define MOAI_MODE_GUARD2 (-1)
@@ -631,7 +633,8 @@ int moai_arith_mode(const moai_ctx *ctx, size_t prime, int op, size_t L, size_t 
  * calls: the digit of a permuted polynomial is the permuted digit plus (q_J mod q_I) times the rotation's sign mask, and
  * that second term is the per-(key, level) constant moai_hoist_correction computes once (csrc/keyswitch_kernels.hip.h
  * has the derivation).  The identity needs INTT(c1) free of zero coefficients; the call checks that on the device and
- * otherwise makes the R separate calls itself (*used_fallback = 1).
+ * otherwise makes the R separate calls itself (*used_fallback = 1).  Below N = 4096 there is no hoisted kernel: the call
+ * always makes the R separate calls and reports *used_fallback = 1.
  *   in, outs[r]  [batch][2][L][N] (no output may alias the input)   correction [2][L+1][N] (rows 0..L-1 under primes
  *   0..L-1, row L under the special prime), computed for the same (key, galois_elt, L).  outs / galois_keys /
  *   corrections: host arrays of R device pointers.

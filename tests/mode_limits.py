@@ -7,6 +7,12 @@ Limits (each is what the code tests, in the same integer arithmetic):
     M_NOGUARD  q < floor((2^64 - 1) / 36)            csrc/ntt.hip noguard_ok; key switch: also 36 q^2 L < 2^128 (ks_mode)
     M_LAZY*    q < 2^60                              csrc/ntt.hip lazy8_ok (plain transforms only)
     M_GUARD*   q < 2^61
+and, outside the modes, the fold period of the FP64 matrix product (csrc/elementwise.hip ct_pt_matmul_fp_kernel):
+    every 16 rows   q < floor(2^52 / 25), every row otherwise (the kernel itself is taken when every prime is below 2^51)
+
+Every search below works at any degree: chain(), ordered() and long_chain() hold for logn 1 .. 16 and give primes of the same bit
+lengths (47, 47, 51, 52, 59, 59, 60, 61, 41) at each of them; the degrees below 2^12 have no arithmetic modes, the limits are the
+same numbers there.
 """
 import numpy as np
 
@@ -14,6 +20,7 @@ FPN_LIMIT = ((1 << 52) - 1) // 33  # largest q with 33 q < 2^52 (33 does not div
 FPR_LIMIT = 1 << 51                # q < 2^51
 NOGUARD_LIMIT = ((1 << 64) - 1) // 36  # q < this
 LAZY_LIMIT = 1 << 60               # q < 2^60
+MATMUL_FOLD_LIMIT = (1 << 52) // 25  # q < this: ct_pt_matmul_fp_kernel folds its sums every 16 rows, else every row
 
 # the names of chain(), in the order of their definition
 NAMES = ("fpn_hi", "fpr_lo", "fpr_hi", "int_lo", "ng_hi", "g_lo", "g60", "g61", "small")
@@ -95,6 +102,18 @@ def ordered(logn, order):
     """the nine primes in one of ORDERS"""
     c = chain(logn)
     return [c[name] for name in ORDERS[order]]
+
+
+_matmul_chains = {}
+
+
+def matmul_chain(logn):
+    """chain(logn) and the two primes on either side of the FP64 matrix product's fold limit (NAMES and ORDERS do not know them):
+    mm_hi the largest below MATMUL_FOLD_LIMIT, mm_lo the smallest at or above it"""
+    if logn not in _matmul_chains:
+        _matmul_chains[logn] = dict(chain(logn), mm_hi=prime_at_most(logn, MATMUL_FOLD_LIMIT - 1),
+                                    mm_lo=prime_at_least(logn, MATMUL_FOLD_LIMIT))
+    return dict(_matmul_chains[logn])
 
 
 def long_chain(logn, k):
@@ -236,3 +255,78 @@ def pattern_rows(primes, n, rng):
 def rounding_row(q, n):
     """the coefficients of a dropped row around the rounding boundary of divide-and-round: 0, q-1, q/2, q/2 +- 1, 1"""
     return np.resize(np.array([0, q - 1, q // 2, q // 2 + 1, q // 2 - 1, 1], dtype=np.uint64), n)
+
+
+# ---- element-wise kernels ------------------------------------------------------------------------------------------------------
+def pair_values(q):
+    """the residues whose sums, differences and products sit on the boundaries of the conditional subtractions and of Barrett's
+    quotient estimate"""
+    return (0, 1, q - 1, q // 2, q // 2 + 1)
+
+
+def pair_patterns(q, n, rng):
+    """(a, b), uint64 [n] each: the 25 ordered pairs of pair_values(q) in coefficients 0 .. 24 (a walks the five values with period 5,
+    b with period 25), uniform residues below q from coefficient 25 on.  For n < 25 only the first n pairs fit: a row of a smaller
+    degree does not hold all of them (pair_rows starts every row elsewhere in the cycle, so that the pairs of short rows differ)."""
+    v = np.array(pair_values(q), dtype=np.uint64)
+    a = rng.integers(0, q, size=n, dtype=np.uint64)
+    b = rng.integers(0, q, size=n, dtype=np.uint64)
+    m = min(n, 25)
+    i = np.arange(m)
+    a[:m] = v[i % 5]
+    b[:m] = v[i // 5]
+    return a, b
+
+
+def pair_rows(primes, n_poly, n, rng):
+    """(a, b) uint64 [n_poly][len(primes)][n]: pair_patterns per row.  Polynomial p and row r start 5 (p + r) + p pairs into the cycle
+    of 25 (both operands alike, so the pairs stay pairs): a short row (n < 25) then holds other pairs in every row and
+    polynomial, and the nine rows of a polynomial hold all 25 between them from n = 8 on"""
+    a = np.empty((n_poly, len(primes), n), dtype=np.uint64)
+    b = np.empty_like(a)
+    for p in range(n_poly):
+        for r, q in enumerate(primes):
+            x, y = pair_patterns(q, max(n, 32), rng)
+            s = -(5 * (p + r) + p) % 25
+            x[:25], y[:25] = np.roll(x[:25], s), np.roll(y[:25], s)
+            a[p, r], b[p, r] = x[:n], y[:n]
+    return a, b
+
+
+def matmul_worst(q, rows, cols, n, rng):
+    """(x, w, w_neg) for one prime of ct_pt_matmul: x uint64 [rows][n], w and w_neg uint64 [rows][cols].
+    x: h = (q - 1) / 2 in the even coefficients and h + 1 in the odd ones, in every row: +h and -h in the balanced representation
+    the FP64 kernel works in.  w[j][c] = 2 m + 1 with a fresh m < 2^16 per (j, c), so x w = m q + (h - m): the residue of every
+    product is within 2^16 of q / 2, with one sign for all rows of a coefficient (+ in the even, - in the odd ones), and the real
+    quotient (m + 1/2 - (m + 1/2) / q) is within 2^-30 of a half-integer, where the kernel's estimate rint(h qinv) may go either
+    way.  w_neg = q - w: the same with the signs exchanged."""
+    h = (q - 1) // 2
+    x = np.empty((rows, n), dtype=np.uint64)
+    x[:, 0::2] = h
+    x[:, 1::2] = h + 1
+    w = rng.integers(0, 1 << 16, size=(rows, cols), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    return x, w, np.uint64(q) - w
+
+
+def _shift_mod(v, bits, q):
+    """v 2^bits mod q for uint64 v below q < 2^52, twelve bits at a time (v 2^12 < 2^64)"""
+    q = np.uint64(q)
+    while bits:
+        s = min(bits, 12)
+        v = (v << np.uint64(s)) % q
+        bits -= s
+    return v
+
+
+def matmul_mod(x, w, q):
+    """sum_j x[j] w[j][c] mod q as uint64 [cols][...] for x uint64 [rows][...] and w uint64 [rows][cols], both below q < 2^52, at
+    most 2^12 rows; exact integer arithmetic: operands split at bit 26, the four sums of partial products stay below 2^64
+    (tests/test_elementwise_limits_cpu.py pins it against Python integers)"""
+    assert q < 1 << 52 and x.shape[0] == w.shape[0] <= 1 << 12
+    lo = np.uint64((1 << 26) - 1)
+    xs = x.reshape(x.shape[0], -1)
+    x0, x1, w0, w1 = xs & lo, xs >> np.uint64(26), w & lo, w >> np.uint64(26)
+    qq = np.uint64(q)
+    s00, s01, s10, s11 = (np.tensordot(b, a, axes=(0, 0)) % qq for a, b in ((x0, w0), (x0, w1), (x1, w0), (x1, w1)))
+    out = (s00 + _shift_mod((s01 + s10) % qq, 26, q) + _shift_mod(s11, 52, q)) % qq
+    return out.reshape((w.shape[1],) + x.shape[1:])
