@@ -100,10 +100,7 @@ def _bsgs_dot(octx, ct, L, alpha, baby_elts, baby_keys, giant_elts, giant_keys, 
 def noise_bound(octx, L, alpha, s_l1, giant_elts, plain_l1_sums):
     """the header's bound: (alpha - 1/2)(1 + |s|_1) + sum_g [ l_g u + [E_g != 1](u + (alpha - 1/2)|s|_1) ] with u = beta N alpha 21
     D_max / P and l_g = plain_l1_sums[g], the sum of |p_{g,r}|_1 over the present terms with e_r != 1"""
-    primes, k = octx.primes, octx.k
-    P = HR._prod(primes[k - alpha:])
-    d_max = max(HR._prod(primes[r] for r in HR.digit_rows(j, L, alpha)) for j in range(HR.beta(L, alpha)))
-    u = HR.beta(L, alpha) * octx.n * alpha * 21 * d_max / P
+    u = HR.approx_u(octx, L, alpha)
     bound = (alpha - 0.5) * (1 + s_l1)
     for E, l1 in zip(giant_elts, plain_l1_sums):
         bound += l1 * u + ((u + (alpha - 0.5) * s_l1) if E != 1 else 0)

@@ -81,10 +81,7 @@ def encode_plain(octx, coeffs, L, alpha):
 def noise_bound(octx, L, alpha, s_l1, plain_l1_sum):
     """the header's bound: (sum_r |p_{g,r}|_1) beta N alpha 21 D_max / P + (alpha - 1/2)(1 + |s|_1), the sum over the terms with
     e_r != 1"""
-    primes, k = octx.primes, octx.k
-    P = HR._prod(primes[k - alpha:])
-    d_max = max(HR._prod(primes[r] for r in HR.digit_rows(j, L, alpha)) for j in range(HR.beta(L, alpha)))
-    return plain_l1_sum * HR.beta(L, alpha) * octx.n * alpha * 21 * d_max / P + (alpha - 0.5) * (1 + s_l1)
+    return HR.approx_u(octx, L, alpha, times=plain_l1_sum) + (alpha - 0.5) * (1 + s_l1)
 
 
 def dot_error(octx, out, ct, s_ntt, L, elts, plains_g):

@@ -127,12 +127,18 @@ def apply_galois(octx, ct, L, elt, key, alpha):
     return switch_key(octx, base, perm[1], key, L, alpha)
 
 
-def noise_bound(octx, L, alpha, s_l1):
-    """B of the header: |d0 + d1 s - c s'| <= beta N alpha 21 D_max / P + (alpha - 1/2)(1 + |s|_1)"""
+def approx_u(octx, L, alpha, times=1):
+    """the approximation term of every hybrid noise bound, u = beta N alpha 21 D_max / P; `times` u for an integer `times`, with the
+    one division last, so that it is rounded once"""
     primes, k = octx.primes, octx.k
     P = _prod(primes[k - alpha:])
     d_max = max(_prod(primes[r] for r in digit_rows(j, L, alpha)) for j in range(beta(L, alpha)))
-    return beta(L, alpha) * octx.n * alpha * 21 * d_max / P + (alpha - 0.5) * (1 + s_l1)
+    return times * beta(L, alpha) * octx.n * alpha * 21 * d_max / P
+
+
+def noise_bound(octx, L, alpha, s_l1):
+    """B of the header: |d0 + d1 s - c s'| <= beta N alpha 21 D_max / P + (alpha - 1/2)(1 + |s|_1)"""
+    return approx_u(octx, L, alpha) + (alpha - 0.5) * (1 + s_l1)
 
 
 def switch_error(octx, d, c, s_ntt, s_new_ntt, L):

@@ -5,7 +5,7 @@ module (exact CRT, the oracle's rescale, the noise inequality); tests/test_gpu_h
 CPU only."""
 import numpy as np
 
-from hybrid_ref import _obj, _prod, _u64, beta, digit_rows, mod_up, special_rows
+from hybrid_ref import _obj, _prod, _u64, approx_u, beta, mod_up, special_rows
 
 
 def accumulate(octx, target, key, L, alpha):
@@ -109,10 +109,7 @@ def centred(x, M):
 
 def noise_bound(octx, L, alpha, s_l1):
     """the header's bound on |q_{L-1} (out0 + out1 s) - (c0 + c1 s + c2 s^2)|: beta N alpha 21 D_max / P + q_{L-1} (alpha + 1/2)(1 + |s|_1)"""
-    primes, k = octx.primes, octx.k
-    P = _prod(primes[k - alpha:])
-    d_max = max(_prod(primes[r] for r in digit_rows(j, L, alpha)) for j in range(beta(L, alpha)))
-    return beta(L, alpha) * octx.n * alpha * 21 * d_max / P + primes[L - 1] * (alpha + 0.5) * (1 + s_l1)
+    return approx_u(octx, L, alpha) + octx.primes[L - 1] * (alpha + 0.5) * (1 + s_l1)
 
 
 def rescale_error(octx, out, ct3, s_ntt, L):

@@ -5,11 +5,10 @@ moai_relinearize_rescale_hybrid_ptrs):
 (b) each header comment sits on its declaration and cites the reference lines of the function it stands for;
 (c) the refusals that need no device arrive in the documented order, with a null context and pointers that are never dereferenced."""
 import ctypes as C
-import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL = 0, -1
+from hybrid_kit import EINVAL, OK, exported, header, header_comment
+
 # name -> (the Context method, what its comment cites besides switch_key_inplace)
 NAMES = {
     "moai_apply_galois_hybrid_to": ("apply_galois_hybrid_to", ["SEAL/evaluator.cpp:2563-2665"]),
@@ -20,18 +19,11 @@ NAMES = {
 }
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "moai_hip.h")).read()
-
-
 def test_symbols_exported_declared_and_bound(moai):
-    L = C.CDLL(moai.lib_path())
+    exported(moai, NAMES, [method for method, _ in NAMES.values()])
     hdr = header()
-    for name, (method, _) in NAMES.items():
-        assert hasattr(L, name), name
-        assert name in moai.hip.SYMBOLS, name
+    for name in NAMES:
         assert re.search(r"^int " + name + r"\(", hdr, re.M), name
-        assert callable(getattr(moai.Context, method)), method
 
 
 def test_section_follows_relinearize_rescale():
@@ -43,11 +35,8 @@ def test_section_follows_relinearize_rescale():
 
 
 def test_header_comments_cite_reference_lines():
-    hdr = header()
     for name, (_, cites) in NAMES.items():
-        at = hdr.index("int " + name + "(")
-        comment = hdr[hdr.rindex("/*", 0, at):at]
-        assert comment.rstrip().endswith("*/"), name  # the comment sits directly on the declaration
+        comment = header_comment(name)
         assert re.search(r"SEAL/evaluator\.cpp:\d+-\d+", comment), name
         assert "SEAL/evaluator.cpp:2724-3020" in comment, name  # switch_key_inplace
         for cite in cites:

@@ -27,73 +27,13 @@ import hybrid_bsgs_ref as HB
 import hybrid_ref as HR
 import mode_limits as ML
 import oracle as O
+from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, PATTERN, Env, cached, traced, tuned, unit_plain
+from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL = 0, -1
-IDENT = "identity"
 BABY = [IDENT, 1, 3, -2, 64, 0]  # 0 = conjugation (Galois element 2N - 1)
 GIANT = [IDENT, 4, -8]
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-
-
-class Env:
-    def __init__(self, moai, logn, data_bits=None, special_bits=None, primes=None, alpha=None):
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits) if primes is None else alpha
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits)) if primes is None else list(primes)
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
-
-    def random_key(self, rng):
-        return O.uniform_rns(rng, self.primes, (self.digits, 2), self.n)
-
-    def elts(self, steps):
-        return [1 if s == IDENT else (self.ctx.galois_elt_from_step(s) if s else 2 * self.n - 1) for s in steps]
-
-    def rows(self, L):
-        """the primes of a plaintext's L + alpha rows"""
-        return [self.primes[i] for i in list(range(L)) + list(range(self.k - self.alpha, self.k))]
-
-    def random_input(self, rng, L, B):
-        """[B][2][L][N] with no zero coefficient in any INTT(c1)"""
-        ct = O.uniform_rns(rng, self.primes[:L], (B, 2), self.n)
-        for b in range(B):
-            assert self.octx.ntt(ct[b, 1], L, inverse=True).all(), b
-        return ct
-
-
-@pytest.fixture(scope="module")
-def env_small1(moai):
-    return Env(moai, 10, [60, 60], [60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled1(moai):
-    return Env(moai, 12, [51, 46, 46], [58])
-
-
-@pytest.fixture(scope="module")
-def env_small2(moai):
-    return Env(moai, 10, [40, 41, 42, 43, 44], [60, 60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled3(moai):
-    return Env(moai, 12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])
-
-
-def up(moai, a):
-    return moai.DeviceBuffer.from_numpy(a)
-
-
-def cached(cache, key, make):
-    if key not in cache:
-        cache[key] = make()
-    return cache[key]
 
 
 def default_absent(baby, giant):
@@ -106,7 +46,7 @@ def default_absent(baby, giant):
 class Case:
     """one call: the operands on the device, and the restatement's output computed once (want=False: not at all)"""
 
-    def __init__(self, moai, e, L, baby=BABY, giant=GIANT, B=None, seed=0, ct=None, plain=None, shared_key=False, want=True):
+    def __init__(self, e, L, baby=BABY, giant=GIANT, B=None, seed=0, ct=None, plain=None, shared_key=False, want=True):
         B = (3 if e.logn == 10 else 2) if B is None else B
         self.e, self.L, self.B, self.R, self.ng = e, L, B, len(baby), len(giant)
         rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed + 5)
@@ -115,10 +55,10 @@ class Case:
         self.bkeys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.baby]
         self.gkeys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.giant]
         dk = {}
-        self.dbkeys = [None if k is None else cached(dk, id(k), lambda: up(moai, k)) for k in self.bkeys]
-        self.dgkeys = [None if k is None else cached(dk, id(k), lambda: up(moai, k)) for k in self.gkeys]
+        self.dbkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.bkeys]
+        self.dgkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.gkeys]
         self.ct = e.random_input(rng, L, B) if ct is None else ct(rng)
-        self.dct = up(moai, self.ct)
+        self.dct = e.up(self.ct)
         dc = {}
         self.corrs = [None if k is None else cached(dc, (id(k), elt), lambda: e.ctx.hybrid_hoist_correction(k, elt, L, e.alpha))
                       for k, elt in zip(self.dbkeys, self.baby)]
@@ -126,111 +66,107 @@ class Case:
         new_plain = plain or (lambda: O.uniform_rns(rng, e.rows(L), (), e.n))
         self.plains = [[None if (g, r) in absent else new_plain() for r in range(self.R)] for g in range(self.ng)]
         dp = {}
-        self.dplains = [[None if p is None else cached(dp, id(p), lambda: up(moai, p)) for p in row] for row in self.plains]
+        self.dplains = [[None if p is None else cached(dp, id(p), lambda: e.up(p)) for p in row] for row in self.plains]
         self.shape = (B, 2, L, e.n)
         if want:
             self.want = np.stack([HB.bsgs_dot(e.octx, self.ct[b], L, e.alpha, self.baby, self.bkeys, self.giant, self.gkeys, self.plains)
                                   for b in range(B)])
 
-    def run(self, moai):
+    def run(self):
         """(fallback flag, output [B][2][L][N]) from an output buffer filled with a pattern"""
-        out = up(moai, np.full(int(np.prod(self.shape)), 0xABCD, dtype=np.uint64))
+        out = self.e.filled(self.shape, PATTERN)
         fb = self.e.ctx.hybrid_bsgs_dot(self.dct, out, self.L, self.e.alpha, self.baby, self.dbkeys, self.corrs, self.giant, self.dgkeys,
                                         self.dplains, self.B)
         got = out.to_numpy(self.shape)
         assert (self.dct.to_numpy(self.ct.shape) == self.ct).all()  # the input is left alone
         return fb, got
 
-    def check(self, moai):
-        fb, got = self.run(moai)
+    def check(self):
+        fb, got = self.run()
         assert not fb
         assert (got == self.want).all()
 
 
 @pytest.fixture(scope="module")
-def case_tiled3(moai, env_tiled3):
+def case_tiled3(env_tiled3):
     """the default case at alpha = 3, L = 7, shared by the tests of the knobs"""
-    return Case(moai, env_tiled3, 7)
+    return Case(env_tiled3, 7)
 
 
 # ---- 1. alpha = 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [3, 1])
-def test_alpha_1_tiled_transform(moai, env_tiled1, L):
-    Case(moai, env_tiled1, L).check(moai)
+def test_alpha_1_tiled_transform(env_tiled1, L):
+    Case(env_tiled1, L).check()
 
 
-def test_alpha_1_small_transform(moai, env_small1):
-    Case(moai, env_small1, 2).check(moai)
+def test_alpha_1_small_transform(env_small1):
+    Case(env_small1, 2).check()
 
 
 # ---- 2. alpha > 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [5, 3, 1])
-def test_alpha_2_small_transform(moai, env_small2, L):
-    Case(moai, env_small2, L).check(moai)
+def test_alpha_2_small_transform(env_small2, L):
+    Case(env_small2, L).check()
 
 
-def test_alpha_3_tiled_transform_full_digits(moai, case_tiled3):
-    case_tiled3.check(moai)
+def test_alpha_3_tiled_transform_full_digits(case_tiled3):
+    case_tiled3.check()
 
 
-def test_alpha_3_tiled_transform_partial_digit(moai, env_tiled3):
-    Case(moai, env_tiled3, 4).check(moai)
+def test_alpha_3_tiled_transform_partial_digit(env_tiled3):
+    Case(env_tiled3, 4).check()
 
 
 # ---- 3. wide digits -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("alpha", [6, 12])
 def test_wide_digits(moai, alpha):
     e = Env(moai, 10, [40] * (alpha + 1), [50] * alpha)
-    Case(moai, e, alpha + 1, baby=[1, 0], giant=[IDENT, 4], B=1).check(moai)
-    e.ctx.close()
+    Case(e, alpha + 1, baby=[1, 0], giant=[IDENT, 4], B=1).check()
+    e.close()
 
 
 # ---- 4. the two identities against the device's own calls -----------------------------------------------------------------------
 @pytest.mark.parametrize("L", [5, 3])
-def test_one_giant_step_of_element_1_is_hybrid_rotate_pt_dot(moai, env_small2, L):
+def test_one_giant_step_of_element_1_is_hybrid_rotate_pt_dot(env_small2, L):
     e = env_small2
-    c = Case(moai, e, L, giant=[IDENT], want=False)
-    out = up(moai, np.zeros(int(np.prod(c.shape)), dtype=np.uint64))
+    c = Case(e, L, giant=[IDENT], want=False)
+    out = e.filled(c.shape, 0)
     fb = e.ctx.hybrid_rotate_pt_dot(c.dct, [out], L, e.alpha, c.baby, c.dbkeys, c.corrs, c.dplains, c.B)
     assert not fb
-    fb, got = c.run(moai)
+    fb, got = c.run()
     assert not fb
     assert (got == out.to_numpy(c.shape)).all()
 
 
-def unit_plain(e, L):
-    return lambda: np.ones((L + e.alpha, e.n), dtype=np.uint64)
-
-
-def check_unit_giant_step(moai, e, L, B):
-    c = Case(moai, e, L, baby=[IDENT], giant=[3], B=B, plain=unit_plain(e, L), want=False)
-    d = up(moai, c.ct)
+def check_unit_giant_step(e, L, B):
+    c = Case(e, L, baby=[IDENT], giant=[3], B=B, plain=unit_plain(e, L), want=False)
+    d = e.up(c.ct)
     e.ctx.apply_galois_hybrid(d, L, e.alpha, c.giant[0], c.dgkeys[0], B)
-    fb, got = c.run(moai)
+    fb, got = c.run()
     assert not fb
     assert (got == d.to_numpy(c.shape)).all()
 
 
-def test_a_unit_plaintext_giant_step_is_apply_galois_hybrid(moai, env_small2):
+def test_a_unit_plaintext_giant_step_is_apply_galois_hybrid(env_small2):
     for L in (5, 3):
-        check_unit_giant_step(moai, env_small2, L, 3)
+        check_unit_giant_step(env_small2, L, 3)
 
 
 def test_a_unit_plaintext_giant_step_at_moais_parameters(moai):
     """N = 2^16, MOAI's 35 data primes plus twelve 60-bit special primes, L = 35: three digits, two of 12 primes and one of 11"""
     e = Env(moai, 16, MOAI_DATA_BITS, [60] * 12)
-    check_unit_giant_step(moai, e, 35, 1)
-    e.ctx.close()
+    check_unit_giant_step(e, 35, 1)
+    e.close()
 
 
 def test_degree_65536_equals_the_restatement(moai):
     e = Env(moai, 16, [51, 46, 46], [60, 60])
-    Case(moai, e, 3, baby=[IDENT, 1], giant=[IDENT, 4], B=1).check(moai)
-    e.ctx.close()
+    Case(e, 3, baby=[IDENT, 1], giant=[IDENT, 4], B=1).check()
+    e.close()
 
 
 # ---- 5. fallback ----------------------------------------------------------------------------------------------------------------
-def test_a_zero_coefficient_sets_the_flag_and_gives_the_same_bits(moai, env_small2):
+def test_a_zero_coefficient_sets_the_flag_and_gives_the_same_bits(env_small2):
     e, L = env_small2, 5
 
     def with_sparse_c1(rng):
@@ -240,8 +176,8 @@ def test_a_zero_coefficient_sets_the_flag_and_gives_the_same_bits(moai, env_smal
         ct[0, 1] = e.octx.ntt(sparse, L)[0]
         return ct
 
-    c = Case(moai, e, L, ct=with_sparse_c1)
-    fb, got = c.run(moai)
+    c = Case(e, L, ct=with_sparse_c1)
+    fb, got = c.run()
     assert fb
     assert (got == c.want).all()
 
@@ -249,13 +185,11 @@ def test_a_zero_coefficient_sets_the_flag_and_gives_the_same_bits(moai, env_smal
 # ---- 6. every instantiation -----------------------------------------------------------------------------------------------------
 def test_rotations_per_pass_do_not_change_the_bits(moai, case_tiled3):
     c = case_tiled3
-    try:
+    with tuned(moai):
         for per_pass in (4, 2, 1):
             moai.hip.set_tuning("MOAI_HYBRID_HOIST_NR", per_pass)
-            fb, got = c.run(moai)
+            fb, got = c.run()
             assert not fb and (got == c.want).all(), per_pass
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 7. chunking ----------------------------------------------------------------------------------------------------------------
@@ -273,13 +207,11 @@ def test_chunks_and_giant_groups_give_the_unchunked_result(moai, case_tiled3):
     giant, row_kib = 2 * (L + e.alpha) + 2 * L + e.alpha + L + L + beta * (L + e.alpha), e.n * 8 // 1024
     budgets = [(shared + 3 * giant) * row_kib, (shared + 2 * giant) * row_kib, (shared + giant) * row_kib, 1]
     assert budgets == [347 * 32, 266 * 32, 185 * 32, 1]
-    try:
+    with tuned(moai):
         for kb in budgets:
             moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
-            fb, got = c.run(moai)
+            fb, got = c.run()
             assert not fb and (got == c.want).all(), kb
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 8. more than 63 terms ------------------------------------------------------------------------------------------------------
@@ -292,8 +224,8 @@ def test_65_giant_steps_of_full_size_plaintexts_sum_exactly(moai):
     e = Env(moai, 10, primes=primes, alpha=1)
     top = np.stack([np.full(e.n, q - 1, dtype=np.uint64) for q in e.rows(1)])
     giant = [[1, 3, -2, 5, 0][g % 5] for g in range(65)]
-    Case(moai, e, 1, baby=[IDENT], giant=giant, B=1, plain=lambda: top, shared_key=True).check(moai)
-    e.ctx.close()
+    Case(e, 1, baby=[IDENT], giant=giant, B=1, plain=lambda: top, shared_key=True).check()
+    e.close()
 
 
 # ---- 9. refusals ----------------------------------------------------------------------------------------------------------------
@@ -302,8 +234,8 @@ def test_every_refusal_is_einval_and_leaves_the_output_alone(moai, env_small2):
     L, B, R, G = e.lmax, 2, 2, 2
     lib = moai.hip.lib()
     words = B * 2 * L * n
-    fill = np.full(words, 7, dtype=np.uint64)
-    out, src = up(moai, fill), up(moai, np.full(words, 5, dtype=np.uint64))
+    fill = np.full(words, FILL, dtype=np.uint64)
+    out, src = e.up(fill), e.filled(words, 5)
     dkey, dcorr = moai.DeviceBuffer(e.digits * 2 * k * n), moai.DeviceBuffer(2 * (L + alpha) * n)
     dplain = moai.DeviceBuffer((L + alpha) * n)
     h, s, o, ky, co, pl = e.ctx.h, src.ptr, out.ptr, dkey.ptr, dcorr.ptr, dplain.ptr
@@ -372,13 +304,10 @@ def test_every_refusal_is_einval_and_leaves_the_output_alone(moai, env_small2):
 # ---- 10. op trace ---------------------------------------------------------------------------------------------------------------
 def test_op_trace_counts(moai, env_small2):
     e, L = env_small2, 3
-    c = Case(moai, e, L, baby=[IDENT, 1], giant=[IDENT, 4], B=3, seed=9, want=False)
-    moai.hip.op_trace(True)
-    try:
-        c.run(moai)
-    finally:
-        moai.hip.op_trace(False)
-    counts = moai.hip.op_trace_counts()
+    c = Case(e, L, baby=[IDENT, 1], giant=[IDENT, 4], B=3, seed=9, want=False)
+    with traced(moai) as trace:
+        c.run()
+    counts = trace()
     assert counts.get(("hybrid_bsgs_dot", L)) == 3
     assert ("hybrid_rotate_pt_dot", L) not in counts
     assert ("apply_galois_hybrid", L) not in counts

@@ -21,91 +21,41 @@ import pytest
 
 import hybrid_hoist_ref as HH
 import hybrid_ref as HR
-import oracle as O
+from hybrid_kit import EINVAL, FILL, MOAI_DATA_BITS, OK, PATTERN, Env, traced, tuned
+from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL = 0, -1
 STEPS = [1, 3, -2, 64, 0]  # 0 = conjugation (Galois element 2N - 1)
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-
-
-class Env:
-    def __init__(self, moai, logn, data_bits, special_bits):
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits)
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits))
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
-
-    def random_key(self, rng):
-        return O.uniform_rns(rng, self.primes, (self.digits, 2), self.n)
-
-    def elts(self, steps):
-        return [self.ctx.galois_elt_from_step(s) if s else 2 * self.n - 1 for s in steps]
-
-    def random_input(self, rng, L, B):
-        """[B][2][L][N] with no zero coefficient in any INTT(c1)"""
-        ct = O.uniform_rns(rng, self.primes[:L], (B, 2), self.n)
-        for b in range(B):
-            assert self.octx.ntt(ct[b, 1], L, inverse=True).all(), b
-        return ct
-
-
-@pytest.fixture(scope="module")
-def env_small1(moai):
-    return Env(moai, 10, [60, 60], [60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled1(moai):
-    return Env(moai, 12, [51, 46, 46], [58])
-
-
-@pytest.fixture(scope="module")
-def env_small2(moai):
-    return Env(moai, 10, [40, 41, 42, 43, 44], [60, 60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled3(moai):
-    return Env(moai, 12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])
-
-
-def up(moai, a):
-    return moai.DeviceBuffer.from_numpy(a)
 
 
 class Case:
     """R rotations of one batch: the operands on the device, and the R separate moai_apply_galois_hybrid calls computed once"""
 
-    def __init__(self, moai, e, L, steps=STEPS, B=3, seed=0, ct=None):
+    def __init__(self, e, L, steps=STEPS, B=3, seed=0, ct=None):
         self.e, self.L, self.B, self.R = e, L, B, len(steps)
         rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed)
         self.elts = e.elts(steps)
         self.keys = [e.random_key(rng) for _ in steps]
-        self.dkeys = [up(moai, k) for k in self.keys]
+        self.dkeys = [e.up(k) for k in self.keys]
         self.ct = e.random_input(rng, L, B) if ct is None else ct(rng)
-        self.dct = up(moai, self.ct)
+        self.dct = e.up(self.ct)
         self.corrs = [e.ctx.hybrid_hoist_correction(dk, elt, L, e.alpha) for dk, elt in zip(self.dkeys, self.elts)]
         self.shape = (self.R, B, 2, L, e.n)
         self.want = np.empty(self.shape, dtype=np.uint64)
         for r in range(self.R):
-            d = up(moai, self.ct)
+            d = e.up(self.ct)
             e.ctx.apply_galois_hybrid(d, L, e.alpha, self.elts[r], self.dkeys[r], B)
             self.want[r] = d.to_numpy(self.shape[1:])
 
-    def hoisted(self, moai):
+    def hoisted(self):
         """(fallback flag, outputs [R][B][2][L][N]) from output buffers filled with a pattern"""
-        out = up(moai, np.full(int(np.prod(self.shape)), 0xABCD, dtype=np.uint64))
+        out = self.e.filled(self.shape, PATTERN)
         fb = self.e.ctx.apply_galois_hybrid_hoisted(self.dct, out, self.L, self.e.alpha, self.elts, self.dkeys, self.corrs, self.B)
         return fb, out.to_numpy(self.shape)
 
-    def check(self, moai):
-        fb, got = self.hoisted(moai)
+    def check(self):
+        fb, got = self.hoisted()
         assert not fb
         for r in range(self.R):
             assert (got[r] == self.want[r]).all(), r
@@ -122,34 +72,34 @@ class Case:
 @pytest.mark.parametrize("L", [3, 1])
 def test_alpha_1_equals_the_existing_hoisted_entry_points(moai, env_tiled1, L):
     e = env_tiled1
-    c = Case(moai, e, L)
-    c.check(moai)
+    c = Case(e, L)
+    c.check()
     old_corrs = [e.ctx.hoist_correction(dk, elt, L) for dk, elt in zip(c.dkeys, c.elts)]
     for r in range(c.R):
         assert (c.corrs[r].to_numpy() == old_corrs[r].to_numpy()).all(), r
     out = moai.DeviceBuffer(int(np.prod(c.shape)))
     assert not e.ctx.apply_galois_hoisted(c.dct, out, L, c.elts, c.dkeys, old_corrs, c.B)
-    assert (out.to_numpy(c.shape) == c.hoisted(moai)[1]).all()
+    assert (out.to_numpy(c.shape) == c.hoisted()[1]).all()
 
 
-def test_alpha_1_small_transform_equals_separate_calls(moai, env_small1):
-    c = Case(moai, env_small1, env_small1.lmax)
-    c.check(moai)
+def test_alpha_1_small_transform_equals_separate_calls(env_small1):
+    c = Case(env_small1, env_small1.lmax)
+    c.check()
     c.check_corrections()
 
 
 # ---- 2. alpha > 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [5, 3, 1])
-def test_alpha_2_small_transform_equals_separate_calls(moai, env_small2, L):
-    c = Case(moai, env_small2, L)
-    c.check(moai)
+def test_alpha_2_small_transform_equals_separate_calls(env_small2, L):
+    c = Case(env_small2, L)
+    c.check()
     c.check_corrections()
 
 
 @pytest.mark.parametrize("L", [7, 4])
-def test_alpha_3_tiled_transform_equals_separate_calls(moai, env_tiled3, L):
-    c = Case(moai, env_tiled3, L)
-    c.check(moai)
+def test_alpha_3_tiled_transform_equals_separate_calls(env_tiled3, L):
+    c = Case(env_tiled3, L)
+    c.check()
     c.check_corrections()
 
 
@@ -157,12 +107,12 @@ def test_alpha_3_tiled_transform_equals_separate_calls(moai, env_tiled3, L):
 @pytest.mark.parametrize("alpha", [6, 12])
 def test_wide_digits_equal_separate_calls(moai, alpha):
     e = Env(moai, 10, [40] * (alpha + 1), [50] * alpha)
-    Case(moai, e, alpha + 1, steps=[1, 0], B=1).check(moai)
-    e.ctx.close()
+    Case(e, alpha + 1, steps=[1, 0], B=1).check()
+    e.close()
 
 
 # ---- 4. fallback ----------------------------------------------------------------------------------------------------------------
-def test_a_zero_coefficient_takes_the_fallback_and_the_same_bits(moai, env_small2):
+def test_a_zero_coefficient_takes_the_fallback_and_the_same_bits(env_small2):
     e, L = env_small2, 5
 
     def with_sparse_c1(rng):
@@ -172,8 +122,8 @@ def test_a_zero_coefficient_takes_the_fallback_and_the_same_bits(moai, env_small
         ct[0, 1] = e.octx.ntt(sparse, L)[0]
         return ct
 
-    c = Case(moai, e, L, ct=with_sparse_c1)
-    fb, got = c.hoisted(moai)
+    c = Case(e, L, ct=with_sparse_c1)
+    fb, got = c.hoisted()
     assert fb
     assert (got == c.want).all()
     assert (c.dct.to_numpy(c.ct.shape) == c.ct).all()
@@ -181,14 +131,12 @@ def test_a_zero_coefficient_takes_the_fallback_and_the_same_bits(moai, env_small
 
 # ---- 5. every instantiation -----------------------------------------------------------------------------------------------------
 def test_rotations_per_pass_do_not_change_the_bits(moai, env_tiled3):
-    c = Case(moai, env_tiled3, 7, seed=5)
-    try:
+    c = Case(env_tiled3, 7, seed=5)
+    with tuned(moai):
         for per_pass in (4, 2, 1):
             moai.hip.set_tuning("MOAI_HYBRID_HOIST_NR", per_pass)
-            fb, got = c.hoisted(moai)
+            fb, got = c.hoisted()
             assert not fb and (got == c.want).all(), per_pass
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 6. chunking ----------------------------------------------------------------------------------------------------------------
@@ -197,26 +145,24 @@ def test_chunks_and_groups_give_the_unchunked_result(moai, env_tiled3):
     rows.  154 rows hold two ciphertexts with one rotation in flight (chunks of 2, 2, 1; five groups each), 124 rows one ciphertext
     with two rotations (five chunks; groups of 2, 2, 1), and 1 KiB is the floor of one and one."""
     e, L, B = env_tiled3, 7, 5
-    c = Case(moai, e, L, B=B, seed=6)
+    c = Case(e, L, B=B, seed=6)
     shared, per_rotation, row_kib = HR.beta(L, e.alpha) * (L + e.alpha), 5 * L + 4 * e.alpha, e.n * 8 // 1024
     budgets = [2 * (shared + per_rotation) * row_kib, (shared + 2 * per_rotation) * row_kib, 1]
     assert budgets == [154 * 32, 124 * 32, 1]
-    c.check(moai)  # unchunked
-    try:
+    c.check()  # unchunked
+    with tuned(moai):
         for kb in budgets:
             moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
-            fb, got = c.hoisted(moai)
+            fb, got = c.hoisted()
             assert not fb and (got == c.want).all(), kb
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 7. MOAI's parameters -------------------------------------------------------------------------------------------------------
 def test_moais_parameters_equal_separate_calls(moai):
     """N = 2^16, MOAI's 35 data primes plus twelve 60-bit special primes, L = 35: three digits, two of 12 primes and one of 11"""
     e = Env(moai, 16, MOAI_DATA_BITS, [60] * 12)
-    Case(moai, e, 35, steps=[1, 0], B=1).check(moai)
-    e.ctx.close()
+    Case(e, 35, steps=[1, 0], B=1).check()
+    e.close()
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------
@@ -225,10 +171,10 @@ def test_every_refusal_is_einval_and_leaves_the_outputs_alone(moai, env_small2):
     L, B, R = e.lmax, 2, 2
     lib = moai.hip.lib()
     words = B * 2 * L * n
-    fill = np.full(R * words, 7, dtype=np.uint64)
-    out, src = up(moai, fill), up(moai, np.full(words, 5, dtype=np.uint64))
+    fill = np.full(R * words, FILL, dtype=np.uint64)
+    out, src = e.up(fill), e.filled(words, 5)
     corr_fill = np.full(2 * (L + alpha) * n, 9, dtype=np.uint64)
-    dkey, dcorr = moai.DeviceBuffer(e.digits * 2 * k * n), up(moai, corr_fill)
+    dkey, dcorr = moai.DeviceBuffer(e.digits * 2 * k * n), e.up(corr_fill)
     h, s, ky, co = e.ctx.h, src.ptr, dkey.ptr, dcorr.ptr
     vp = C.c_void_p
 
@@ -293,14 +239,11 @@ def test_every_refusal_is_einval_and_leaves_the_outputs_alone(moai, env_small2):
 # ---- 9. op trace ----------------------------------------------------------------------------------------------------------------
 def test_op_trace_counts(moai, env_small2):
     e, L = env_small2, 3
-    c = Case(moai, e, L, steps=[1, 0], B=3, seed=9)
-    moai.hip.op_trace(True)
-    try:
+    c = Case(e, L, steps=[1, 0], B=3, seed=9)
+    with traced(moai) as trace:
         e.ctx.hybrid_hoist_correction(c.dkeys[0], c.elts[0], L, e.alpha)
-        c.hoisted(moai)
-    finally:
-        moai.hip.op_trace(False)
-    counts = moai.hip.op_trace_counts()
+        c.hoisted()
+    counts = trace()
     assert counts.get(("hybrid_hoist_correction", L)) == 1
     assert counts.get(("apply_galois_hybrid_hoisted", L)) == 3 * 2
     assert ("apply_galois_hybrid", L) not in counts

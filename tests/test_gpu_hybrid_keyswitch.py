@@ -17,55 +17,12 @@ import pytest
 
 import hybrid_ref as HR
 import oracle as O
+from hybrid_kit import EINVAL, FILL, MOAI_DATA_BITS, Env, traced, tuned
+from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 KEY = bytes(range(1, 33))
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-
-
-class Env:
-    def __init__(self, moai, logn, data_bits, special_bits):
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits)
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits))
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
-
-    def random_key(self, rng):
-        return O.uniform_rns(rng, self.primes, (self.digits, 2), self.n)
-
-    def edge_targets(self, L):
-        top = np.stack([np.full(self.n, q - 1, dtype=np.uint64) for q in self.primes[:L]])
-        return top, np.zeros_like(top)
-
-
-@pytest.fixture(scope="module")
-def env_small1(moai):
-    return Env(moai, 10, [60, 60], [60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled1(moai):
-    return Env(moai, 12, [51, 46, 46], [58])
-
-
-@pytest.fixture(scope="module")
-def env_small2(moai):
-    return Env(moai, 10, [40, 41, 42, 43, 44], [60, 60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled3(moai):
-    return Env(moai, 12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])
-
-
-def up(moai, a):
-    return moai.DeviceBuffer.from_numpy(a)
 
 
 # ---- 1. alpha = 1 is the existing path ---------------------------------------------------------------------------------------
@@ -75,39 +32,36 @@ def test_alpha_1_equals_the_existing_entry_points(moai, env_small1, env_tiled1, 
     e = env_small1 if which == "small" else env_tiled1
     L, B, n = (e.lmax if level == "top" else 1), 3, e.n
     rng = np.random.default_rng(e.logn * 10 + L)
-    dkey = up(moai, e.random_key(rng))
+    dkey = e.up(e.random_key(rng))
     ct = O.uniform_rns(rng, e.primes[:L], (B, 2), n)
     target = O.uniform_rns(rng, e.primes[:L], (B,), n)
     target[1], target[2] = e.edge_targets(L)
     ct3 = O.uniform_rns(rng, e.primes[:L], (B, 3), n)
     elt = e.ctx.galois_elt_from_step(1)
-    dt = up(moai, target)
-    moai.hip.op_trace(True)
-    try:
+    dt = e.up(target)
+    with traced(moai) as trace:
         # switch_key
-        a, b = up(moai, ct), up(moai, ct)
+        a, b = e.up(ct), e.up(ct)
         e.ctx.switch_key(a, dt, dkey, L, B)
         e.ctx.switch_key_hybrid(b, dt, dkey, L, 1, B)
         assert (a.to_numpy() == b.to_numpy()).all()
         # relinearize
-        d3, a, b = up(moai, ct3), moai.DeviceBuffer(B * 2 * L * n), moai.DeviceBuffer(B * 2 * L * n)
+        d3, a, b = e.up(ct3), moai.DeviceBuffer(B * 2 * L * n), moai.DeviceBuffer(B * 2 * L * n)
         e.ctx.relinearize(d3, dkey, a, L, B)
         e.ctx.relinearize_hybrid(d3, dkey, b, L, 1, B)
         assert (a.to_numpy() == b.to_numpy()).all()
         # apply_galois
-        a, b = up(moai, ct), up(moai, ct)
+        a, b = e.up(ct), e.up(ct)
         e.ctx.apply_galois(a, L, elt, dkey, B)
         e.ctx.apply_galois_hybrid(b, L, 1, elt, dkey, B)
         assert (a.to_numpy() == b.to_numpy()).all()
-    finally:
-        moai.hip.op_trace(False)
-    counts = moai.hip.op_trace_counts()
+    counts = trace()
     for name in ("switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid"):
         assert counts.get((name, L)) == B, name
 
 
 @pytest.mark.parametrize("which", ["small", "tiled"])
-def test_alpha_1_keygen_equals_kswitch_keygen(moai, env_small1, env_tiled1, which):
+def test_alpha_1_keygen_equals_kswitch_keygen(env_small1, env_tiled1, which):
     e = env_small1 if which == "small" else env_tiled1
     sk = e.ctx.sample_ternary(KEY, 1 << 40, 1, e.k)
     new = e.ctx.sample_ternary(KEY, 2 << 40, 1, e.k)
@@ -120,15 +74,15 @@ def test_alpha_1_keygen_equals_kswitch_keygen(moai, env_small1, env_tiled1, whic
 
 
 # ---- 2. alpha > 1 against the restatement ------------------------------------------------------------------------------------
-def against_restatement(moai, e, L):
+def against_restatement(e, L):
     rng = np.random.default_rng(e.logn * 100 + L)
     key = e.random_key(rng)
     B, n = 4, e.n  # two random ciphertexts, one target with every row m - 1, one zero
     ct = O.uniform_rns(rng, e.primes[:L], (B, 2), n)
     target = O.uniform_rns(rng, e.primes[:L], (B,), n)
     target[2], target[3] = e.edge_targets(L)
-    dct = up(moai, ct)
-    e.ctx.switch_key_hybrid(dct, up(moai, target), up(moai, key), L, e.alpha, B)
+    dct = e.up(ct)
+    e.ctx.switch_key_hybrid(dct, e.up(target), e.up(key), L, e.alpha, B)
     got = dct.to_numpy((B, 2, L, n))
     assert e.ctx.hybrid_digits(e.alpha, L) == HR.beta(L, e.alpha)
     for b in range(B):
@@ -136,13 +90,13 @@ def against_restatement(moai, e, L):
 
 
 @pytest.mark.parametrize("L", [5, 3, 1])
-def test_alpha_2_small_transform_against_the_restatement(moai, env_small2, L):
-    against_restatement(moai, env_small2, L)
+def test_alpha_2_small_transform_against_the_restatement(env_small2, L):
+    against_restatement(env_small2, L)
 
 
 @pytest.mark.parametrize("L", [7, 4])
-def test_alpha_3_tiled_transform_against_the_restatement(moai, env_tiled3, L):
-    against_restatement(moai, env_tiled3, L)
+def test_alpha_3_tiled_transform_against_the_restatement(env_tiled3, L):
+    against_restatement(env_tiled3, L)
 
 
 @pytest.mark.parametrize("alpha", [6, 12])
@@ -150,24 +104,24 @@ def test_wide_digits_against_the_restatement(moai, alpha):
     """digits of 6 and 12 primes take the conversion kernel's instantiations for up to 8 and up to 16 source rows; alpha + 1 data
     primes leave a last digit of one prime"""
     e = Env(moai, 10, [40] * (alpha + 1), [50] * alpha)
-    against_restatement(moai, e, alpha + 1)
-    against_restatement(moai, e, alpha)
-    e.ctx.close()
+    against_restatement(e, alpha + 1)
+    against_restatement(e, alpha)
+    e.close()
 
 
 def test_relinearize_and_galois_against_the_restatement(moai, env_small2):
     e, L, n = env_small2, 3, env_small2.n
     rng = np.random.default_rng(33)
     key = e.random_key(rng)
-    dkey = up(moai, key)
+    dkey = e.up(key)
     ct3 = O.uniform_rns(rng, e.primes[:L], (2, 3), n)
     out = moai.DeviceBuffer(2 * 2 * L * n)
-    e.ctx.relinearize_hybrid(up(moai, ct3), dkey, out, L, e.alpha, 2)
+    e.ctx.relinearize_hybrid(e.up(ct3), dkey, out, L, e.alpha, 2)
     got = out.to_numpy((2, 2, L, n))
     for b in range(2):
         assert (got[b] == HR.relinearize(e.octx, ct3[b], key, L, e.alpha)).all(), b
     elt = e.ctx.galois_elt_from_step(3)
-    dct = up(moai, ct3[:, :2])
+    dct = e.up(ct3[:, :2])
     e.ctx.apply_galois_hybrid(dct, L, e.alpha, elt, dkey, 2)
     got = dct.to_numpy((2, 2, L, n))
     for b in range(2):
@@ -175,12 +129,12 @@ def test_relinearize_and_galois_against_the_restatement(moai, env_small2):
 
 
 @pytest.mark.parametrize("which", ["small", "tiled"])
-def test_keygen_against_the_restatement(moai, env_small2, env_tiled3, which):
+def test_keygen_against_the_restatement(env_small2, env_tiled3, which):
     e = env_small2 if which == "small" else env_tiled3
     rng = np.random.default_rng(7)
     sk = O.uniform_rns(rng, e.primes, (), e.n)  # any residues: the digit formula does not care that a key is small
     new = O.uniform_rns(rng, e.primes, (), e.n)
-    got = e.ctx.hybrid_keygen(KEY, 41, up(moai, sk), up(moai, new), e.alpha).to_numpy((e.digits, 2, e.k, e.n))
+    got = e.ctx.hybrid_keygen(KEY, 41, e.up(sk), e.up(new), e.alpha).to_numpy((e.digits, 2, e.k, e.n))
     assert (got == HR.keygen(e.octx, KEY, 41, sk, new, e.alpha)).all()
 
 
@@ -197,7 +151,7 @@ def switch_errors(moai, e, levels, B=2):
     out = []
     for L in levels:
         rng = np.random.default_rng(L)
-        c = up(moai, O.uniform_rns(rng, e.primes[:L], (B,), n))
+        c = e.up(O.uniform_rns(rng, e.primes[:L], (B,), n))
         d = moai.DeviceBuffer(B * 2 * L * n)
         moai.hip._check(moai.hip.lib().moai_memset_zero(d.ptr, d.n_words * 8, None))
         ctx.switch_key_hybrid(d, c, key, L, e.alpha, B)
@@ -233,7 +187,7 @@ def test_it_is_a_key_switch_at_moais_parameters(moai):
     """N = 2^16, MOAI's 35 data primes plus 12 60-bit special primes (a key of 0.15 GB), L = 35 and 15"""
     e = Env(moai, 16, MOAI_DATA_BITS, [60] * 12)
     check_errors(switch_errors(moai, e, (35, 15)))
-    e.ctx.close()
+    e.close()
 
 
 # ---- 4. chunking -------------------------------------------------------------------------------------------------------------
@@ -242,22 +196,20 @@ def test_chunks_of_two_give_the_unchunked_result(moai, env_tiled3):
     hold two switches (chunks of 2, 2, 1) and one rotation (five chunks), 6000 KiB two of either"""
     e, L, B, n = env_tiled3, 7, 5, env_tiled3.n
     rng = np.random.default_rng(4)
-    dkey = up(moai, e.random_key(rng))
+    dkey = e.up(e.random_key(rng))
     ct = O.uniform_rns(rng, e.primes[:L], (B, 2), n)
-    dt = up(moai, O.uniform_rns(rng, e.primes[:L], (B,), n))
+    dt = e.up(O.uniform_rns(rng, e.primes[:L], (B,), n))
     elt = e.ctx.galois_elt_from_step(2)
     got = {}
-    try:
+    with tuned(moai):
         for kb in (None, 5000, 6000):
             moai.hip.reset_tuning()
             if kb:
                 moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
-            a, b = up(moai, ct), up(moai, ct)
+            a, b = e.up(ct), e.up(ct)
             e.ctx.switch_key_hybrid(a, dt, dkey, L, e.alpha, B)
             e.ctx.apply_galois_hybrid(b, L, e.alpha, elt, dkey, B)
             got[kb] = (a.to_numpy(), b.to_numpy())
-    finally:
-        moai.hip.reset_tuning()
     for kb in (5000, 6000):
         assert (got[kb][0] == got[None][0]).all() and (got[kb][1] == got[None][1]).all(), kb
 
@@ -267,8 +219,8 @@ def test_every_refusal_is_einval_and_leaves_the_outputs_alone(moai, env_small2):
     e, n, k, alpha = env_small2, env_small2.n, env_small2.k, env_small2.alpha
     L = e.lmax
     lib = moai.hip.lib()
-    fill = np.full(2 * 2 * L * n, 7, dtype=np.uint64)
-    out, src = up(moai, fill), up(moai, np.full(2 * 3 * L * n, 5, dtype=np.uint64))
+    fill = np.full(2 * 2 * L * n, FILL, dtype=np.uint64)
+    out, src = e.up(fill), e.filled(2 * 3 * L * n, 5)
     dkey = moai.DeviceBuffer(e.digits * 2 * k * n)
     odd = 3
     h, o, s, ky = e.ctx.h, out.ptr, src.ptr, dkey.ptr

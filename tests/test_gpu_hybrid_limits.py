@@ -25,9 +25,11 @@ import numpy as np
 import pytest
 
 import hybrid_hoist_ref as HH
+import hybrid_kit
 import hybrid_ref as HR
 import mode_limits as ML
 import oracle as O
+from hybrid_kit import PATTERN, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -38,18 +40,14 @@ SEAL_KEY = bytes(range(1, 33))
 Q_HALVES = ML.PATTERNS[3]
 
 
-class Env:
+class Env(hybrid_kit.Env):
     """one chain at one degree: the oracle's and the device's context, the two keys on host and device"""
 
     def __init__(self, moai, logn, which, alpha):
-        self.logn, self.n, self.which = logn, 1 << logn, which
-        self.primes, self.names, self.alpha = ML.hybrid_chain(logn, which, alpha)
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.digits = HR.beta(self.lmax, self.alpha)
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self._keys, self._dkeys, self.cases = {}, {}, {}
+        primes, self.names, alpha = ML.hybrid_chain(logn, which, alpha)
+        super().__init__(moai, logn, primes=primes, alpha=alpha)
+        self.which = which
+        self._keys, self._dkeys = {}, {}
 
     def key(self, kind):
         if kind not in self._keys:
@@ -63,18 +61,15 @@ class Env:
             self._keys[kind] = key
         return self._keys[kind]
 
-    def dkey(self, moai, kind):
+    def dkey(self, kind):
         if kind not in self._dkeys:
-            self._dkeys[kind] = up(moai, self.key(kind))
+            self._dkeys[kind] = self.up(self.key(kind))
         return self._dkeys[kind]
-
-    def elts(self, steps):
-        return [O.galois_elt_from_step(self.logn, s) if s else 2 * self.n - 1 for s in steps]
 
     def close(self):
         for b in self._dkeys.values():
             b.free()
-        self.ctx.close()
+        super().close()
 
 
 _envs = {}
@@ -93,10 +88,6 @@ def env(moai, logn, which, alpha=None):
     if (logn, which, alpha) not in _envs:
         _envs[(logn, which, alpha)] = Env(moai, logn, which, alpha)
     return _envs[(logn, which, alpha)]
-
-
-def up(moai, a):
-    return moai.DeviceBuffer.from_numpy(a)
 
 
 def code(moai, name):
@@ -123,10 +114,8 @@ def assert_modes(moai, e, fp=1, lazy16=1):
 @pytest.mark.parametrize("which", CHAINS)
 def test_special_rows_take_the_intended_inverse_class(moai, which):
     """the mod-down inverts the special rows: exact integer and lazy butterflies on special_large, FP64 ones on special_small"""
-    try:
+    with tuned(moai):
         inv = [c[1] for c in assert_modes(moai, env(moai, 12, which))]
-    finally:
-        moai.hip.reset_tuning()
     assert inv == (["LAZY16", "GUARD", "LAZY16"] if which == "special_large" else ["FPR", "FPN", "FPN"])
 
 
@@ -134,7 +123,7 @@ def test_special_rows_take_the_intended_inverse_class(moai, which):
 def switch_inputs(e, L):
     """names, ct [B][2][L][N] (random addends) and tgt [B][L][N] (NTT form of the coefficient patterns).  2^10 and 2^12: worst_coeff
     and every pattern of ML.PATTERNS; above: worst_coeff, q/2 and q/2+1, random."""
-    if ("in", L) not in e.cases:
+    if ("in", L) not in e.cache:
         rng = np.random.default_rng(7200 + 100 * e.logn + L)
         pat = ML.pattern_rows(e.primes[:L], e.n, rng)
         worst = ML.worst_coeff(e.primes, L, e.alpha, e.n)
@@ -146,40 +135,40 @@ def switch_inputs(e, L):
         ct = O.uniform_rns(rng, e.primes[:L], (len(names), 2), e.n)
         for a in (tgt, ct):
             a.setflags(write=False)
-        e.cases[("in", L)] = (names, ct, tgt)
-    return e.cases[("in", L)]
+        e.cache[("in", L)] = (names, ct, tgt)
+    return e.cache[("in", L)]
 
 
 def switch_ref(e, L, kind, b):
     """HR.switch_key of ciphertext b of switch_inputs with key `kind`"""
-    if ("sk", L, kind, b) not in e.cases:
+    if ("sk", L, kind, b) not in e.cache:
         _, ct, tgt = switch_inputs(e, L)
         ref = HR.switch_key(e.octx, ct[b], tgt[b], e.key(kind), L, e.alpha)
         ref.setflags(write=False)
-        e.cases[("sk", L, kind, b)] = ref
-    return e.cases[("sk", L, kind, b)]
+        e.cache[("sk", L, kind, b)] = ref
+    return e.cache[("sk", L, kind, b)]
 
 
 def galois_case(e, L, kind, step, B):
     """the first B ciphertexts of switch_inputs with c1 placed so that the rotation's permutation brings the target back, and
     HR.apply_galois"""
     names, ct, tgt = switch_inputs(e, L)
-    if ("ag", L, kind, step, B) not in e.cases:
+    if ("ag", L, kind, step, B) not in e.cache:
         elt = e.elts([step])[0]
         table = O.galois_table_ntt(e.logn, elt)
         ctg = ct[:B].copy()
         ctg[:, 1][..., table] = tgt[:B]
         ref = np.stack([HR.apply_galois(e.octx, ctg[b], L, elt, e.key(kind), e.alpha) for b in range(B)])
-        e.cases[("ag", L, kind, step, B)] = (elt, ctg, ref)
-    return (names[:B],) + e.cases[("ag", L, kind, step, B)]
+        e.cache[("ag", L, kind, step, B)] = (elt, ctg, ref)
+    return (names[:B],) + e.cache[("ag", L, kind, step, B)]
 
 
-def check_switch(moai, e, L, kind, picks=None):
+def check_switch(e, L, kind, picks=None):
     """switch_key_hybrid on the ciphertexts `picks` of switch_inputs (all of them by default) in one batch"""
     names, ct, tgt = switch_inputs(e, L)
     picks = list(range(len(names))) if picks is None else list(picks)
-    d, dt = up(moai, ct[picks]), up(moai, tgt[picks])
-    e.ctx.switch_key_hybrid(d, dt, e.dkey(moai, kind), L, e.alpha, len(picks))
+    d, dt = e.up(ct[picks]), e.up(tgt[picks])
+    e.ctx.switch_key_hybrid(d, dt, e.dkey(kind), L, e.alpha, len(picks))
     got = d.to_numpy((len(picks), 2, L, e.n))
     d.free()
     dt.free()
@@ -197,12 +186,10 @@ SWITCH_SHAPES = [(logn, 7) for logn in (10, 12, 13, 14, 15, 16)] + [(logn, L) fo
 def test_switch_at_the_limits(moai, which, logn, L, kind):
     """L = 7: digits of 3, 3, 1 primes; 4: a partial last digit; 3: one full digit and no other data row; 1: one digit of one prime"""
     e = env(moai, logn, which)
-    try:
+    with tuned(moai):
         assert_modes(moai, e)
         assert e.ctx.hybrid_digits(e.alpha, L) == HR.beta(L, e.alpha)
-        check_switch(moai, e, L, kind)
-    finally:
-        moai.hip.reset_tuning()
+        check_switch(e, L, kind)
 
 
 # ---- c. the other entry points --------------------------------------------------------------------------------------------------
@@ -214,10 +201,10 @@ def test_relinearize_at_the_limits(moai, which, L, kind):
     e = env(moai, 12, which)
     names, ct, tgt = switch_inputs(e, L)
     B = len(names)
-    d3, out = up(moai, np.concatenate([ct, tgt[:, None]], axis=1)), moai.DeviceBuffer(B * 2 * L * e.n)
+    d3, out = e.up(np.concatenate([ct, tgt[:, None]], axis=1)), moai.DeviceBuffer(B * 2 * L * e.n)
     try:
         assert_modes(moai, e)
-        e.ctx.relinearize_hybrid(d3, e.dkey(moai, kind), out, L, e.alpha, B)
+        e.ctx.relinearize_hybrid(d3, e.dkey(kind), out, L, e.alpha, B)
         got = out.to_numpy((B, 2, L, e.n))
     finally:
         moai.hip.reset_tuning()
@@ -234,10 +221,10 @@ def test_relinearize_at_the_limits(moai, which, L, kind):
 def test_apply_galois_at_the_limits(moai, which, L, kind, step):
     e = env(moai, 12, which)
     names, elt, ctg, ref = galois_case(e, L, kind, step, 3)  # worst_coeff, all q-1, all 0
-    d = up(moai, ctg)
+    d = e.up(ctg)
     try:
         assert_modes(moai, e)
-        e.ctx.apply_galois_hybrid(d, L, e.alpha, elt, e.dkey(moai, kind), len(names))
+        e.ctx.apply_galois_hybrid(d, L, e.alpha, elt, e.dkey(kind), len(names))
         got = d.to_numpy(ref.shape)
     finally:
         moai.hip.reset_tuning()
@@ -253,7 +240,7 @@ def test_keygen_at_the_limits(moai, which):
     e = env(moai, 12, which)
     sk = O.uniform_rns(np.random.default_rng(7300), e.primes, (), e.n)
     new = np.stack([np.full(e.n, m - 1, dtype=np.uint64) for m in e.primes])
-    dsk, dnew = up(moai, sk), up(moai, new)
+    dsk, dnew = e.up(sk), e.up(new)
     got = e.ctx.hybrid_keygen(SEAL_KEY, 41, dsk, dnew, e.alpha)
     try:
         assert (got.to_numpy((e.digits, 2, e.k, e.n)) == HR.keygen(e.octx, SEAL_KEY, 41, sk, new, e.alpha)).all()
@@ -265,14 +252,14 @@ def test_keygen_at_the_limits(moai, which):
 # ---- d. wide digits at 61 bits ----------------------------------------------------------------------------------------------------
 def short_case(e, L):
     """two ciphertexts per key: targets worst_coeff and random; HR.switch_key per key"""
-    if ("short", L) not in e.cases:
+    if ("short", L) not in e.cache:
         rng = np.random.default_rng(7400 + 100 * e.logn + L)
         coeff = [ML.worst_coeff(e.primes, L, e.alpha, e.n), O.uniform_rns(rng, e.primes[:L], (), e.n)]
         tgt = np.stack([e.octx.ntt(cf, L) for cf in coeff])
         ct = O.uniform_rns(rng, e.primes[:L], (2, 2), e.n)
         refs = {kind: np.stack([HR.switch_key(e.octx, ct[b], tgt[b], e.key(kind), L, e.alpha) for b in range(2)]) for kind in KEYS}
-        e.cases[("short", L)] = (ct, tgt, refs)
-    return e.cases[("short", L)]
+        e.cache[("short", L)] = (ct, tgt, refs)
+    return e.cache[("short", L)]
 
 
 @pytest.mark.parametrize("full", [False, True])
@@ -284,17 +271,15 @@ def test_wide_digits_at_61_bits(moai, alpha, logn, full):
     e = env(moai, logn, "wide", alpha)
     L = alpha if full else alpha + 1
     ct, tgt, refs = short_case(e, L)
-    try:
+    with tuned(moai):
         assert_modes(moai, e)
         for kind in KEYS:
-            d, dt = up(moai, ct), up(moai, tgt)
-            e.ctx.switch_key_hybrid(d, dt, e.dkey(moai, kind), L, alpha, 2)
+            d, dt = e.up(ct), e.up(tgt)
+            e.ctx.switch_key_hybrid(d, dt, e.dkey(kind), L, alpha, 2)
             got = d.to_numpy(ct.shape)
             d.free()
             dt.free()
             assert (got == refs[kind]).all(), kind
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- e. 63 digits -----------------------------------------------------------------------------------------------------------------
@@ -304,14 +289,14 @@ L63 = 63
 def long_inputs(e):
     """c1 in NTT form [3][63][N]: worst_coeff, random (both free of zero coefficients), and every row all q - 1, whose digits make
     every product of the MAC's first row (q_j - 1) (m - 1)"""
-    if "long" not in e.cases:
+    if "long" not in e.cache:
         rng = np.random.default_rng(7500)
         coeff = [ML.worst_coeff(e.primes, L63, 1, e.n), O.uniform_rns(rng, e.primes[:L63], (), e.n)]
         assert coeff[1].all()
         top = np.stack([np.full(e.n, q - 1, dtype=np.uint64) for q in e.primes[:L63]])
         tgt = np.stack([e.octx.ntt(cf, L63) for cf in coeff] + [top])
-        e.cases["long"] = (tgt, O.uniform_rns(rng, e.primes[:L63], (3, 2), e.n))
-    return e.cases["long"]
+        e.cache["long"] = (tgt, O.uniform_rns(rng, e.primes[:L63], (3, 2), e.n))
+    return e.cache["long"]
 
 
 @pytest.mark.parametrize("kind,b", [("max", 0), ("rnd", 1), ("max", 2)])
@@ -320,8 +305,8 @@ def test_63_digits_switch(moai, kind, b):
     e = env(moai, 10, "long63")
     assert e.k == 64 and e.ctx.hybrid_digits(1, L63) == 63
     tgt, ct = long_inputs(e)
-    d, dt = up(moai, ct[b]), up(moai, tgt[b])
-    e.ctx.switch_key_hybrid(d, dt, e.dkey(moai, kind), L63, 1, 1)
+    d, dt = e.up(ct[b]), e.up(tgt[b])
+    e.ctx.switch_key_hybrid(d, dt, e.dkey(kind), L63, 1, 1)
     got = d.to_numpy((2, L63, e.n))
     d.free()
     dt.free()
@@ -346,10 +331,10 @@ def check_hoisted(moai, e, L, ct, elts, kinds, per_pass):
     for b in range(B):
         assert e.octx.ntt(ct[b, 1], L, inverse=True).all(), b  # zero-free by construction
     keys = [e.key(kind) for kind in kinds]
-    dkeys = [e.dkey(moai, kind) for kind in kinds]
+    dkeys = [e.dkey(kind) for kind in kinds]
     want = np.stack([HH.apply_galois_hoisted(e.octx, ct[b], L, elts, keys, e.alpha) for b in range(B)], axis=1)  # [R][B][2][L][N]
     corrs = [e.ctx.hybrid_hoist_correction(dk, elt, L, e.alpha) for dk, elt in zip(dkeys, elts)]
-    dct, dout = up(moai, ct), moai.DeviceBuffer(R * B * 2 * L * e.n)
+    dct, dout = e.up(ct), moai.DeviceBuffer(R * B * 2 * L * e.n)
     try:
         seen = {}
         for r in range(R):
@@ -359,7 +344,7 @@ def check_hoisted(moai, e, L, ct, elts, kinds, per_pass):
             assert (corrs[r].to_numpy(ref.shape) == ref).all(), ("correction", r)
         for nr in per_pass:
             moai.hip.set_tuning("MOAI_HYBRID_HOIST_NR", nr)
-            dout.upload(np.full(R * B * 2 * L * e.n, 0xABCD, dtype=np.uint64))
+            dout.upload(np.full(R * B * 2 * L * e.n, PATTERN, dtype=np.uint64))
             assert not e.ctx.apply_galois_hybrid_hoisted(dct, dout, L, e.alpha, elts, dkeys, corrs, B), "fallback taken"
             got = dout.to_numpy(want.shape)
             for r in range(R):
@@ -426,16 +411,12 @@ def test_schedules_give_the_restatements_bits(moai, schedule):
     e, L, B, kind = env(moai, 12, "special_small"), 7, 5, "rnd"
     names, elt, ctg, ref = galois_case(e, L, kind, 2, B)
     knobs = SCHEDULES[schedule]
-    try:
-        for knob, v in knobs.items():
-            moai.hip.set_tuning(knob, v)
+    with tuned(moai, **knobs):
         assert_modes(moai, e, fp=knobs.get("MOAI_NTT_FP", 1), lazy16=knobs.get("MOAI_NTT_LAZY16", 1))
-        check_switch(moai, e, L, kind, picks=range(B))
-        d = up(moai, ctg)
-        e.ctx.apply_galois_hybrid(d, L, e.alpha, elt, e.dkey(moai, kind), B)
+        check_switch(e, L, kind, picks=range(B))
+        d = e.up(ctg)
+        e.ctx.apply_galois_hybrid(d, L, e.alpha, elt, e.dkey(kind), B)
         got = d.to_numpy(ref.shape)
         d.free()
         for b in range(B):
             assert (got[b] == ref[b]).all(), ("apply_galois_hybrid", names[b])
-    finally:
-        moai.hip.reset_tuning()

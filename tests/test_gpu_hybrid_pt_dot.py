@@ -25,72 +25,12 @@ import hybrid_dot_ref as HD
 import hybrid_ref as HR
 import mode_limits as ML
 import oracle as O
+from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, PATTERN, Env, cached, traced, tuned, unit_plain
+from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL = 0, -1
-IDENT = "identity"
 STEPS = [1, 3, -2, 64, 0, IDENT]  # 0 = conjugation (Galois element 2N - 1)
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-
-
-class Env:
-    def __init__(self, moai, logn, data_bits=None, special_bits=None, primes=None, alpha=None):
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits) if primes is None else alpha
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits)) if primes is None else list(primes)
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
-
-    def random_key(self, rng):
-        return O.uniform_rns(rng, self.primes, (self.digits, 2), self.n)
-
-    def elts(self, steps):
-        return [1 if s == IDENT else (self.ctx.galois_elt_from_step(s) if s else 2 * self.n - 1) for s in steps]
-
-    def rows(self, L):
-        """the primes of a plaintext's L + alpha rows"""
-        return [self.primes[i] for i in list(range(L)) + list(range(self.k - self.alpha, self.k))]
-
-    def random_input(self, rng, L, B):
-        """[B][2][L][N] with no zero coefficient in any INTT(c1)"""
-        ct = O.uniform_rns(rng, self.primes[:L], (B, 2), self.n)
-        for b in range(B):
-            assert self.octx.ntt(ct[b, 1], L, inverse=True).all(), b
-        return ct
-
-
-@pytest.fixture(scope="module")
-def env_small1(moai):
-    return Env(moai, 10, [60, 60], [60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled1(moai):
-    return Env(moai, 12, [51, 46, 46], [58])
-
-
-@pytest.fixture(scope="module")
-def env_small2(moai):
-    return Env(moai, 10, [40, 41, 42, 43, 44], [60, 60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled3(moai):
-    return Env(moai, 12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])
-
-
-def up(moai, a):
-    return moai.DeviceBuffer.from_numpy(a)
-
-
-def cached(cache, key, make):
-    if key not in cache:
-        cache[key] = make()
-    return cache[key]
 
 
 def default_absent(steps, n_out):
@@ -103,16 +43,16 @@ def default_absent(steps, n_out):
 class Case:
     """one call: the operands on the device, and the restatement's outputs computed once (want=False: not at all)"""
 
-    def __init__(self, moai, e, L, steps=STEPS, B=3, n_out=3, seed=0, ct=None, plain=None, shared_key=False, want=True):
+    def __init__(self, e, L, steps=STEPS, B=3, n_out=3, seed=0, ct=None, plain=None, shared_key=False, want=True):
         self.e, self.L, self.B, self.R, self.n_out = e, L, B, len(steps), n_out
         rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed)
         self.elts = e.elts(steps)
         one_key = e.random_key(rng) if shared_key else None
         self.keys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.elts]
         dk = {}
-        self.dkeys = [None if k is None else cached(dk, id(k), lambda: up(moai, k)) for k in self.keys]
+        self.dkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.keys]
         self.ct = e.random_input(rng, L, B) if ct is None else ct(rng)
-        self.dct = up(moai, self.ct)
+        self.dct = e.up(self.ct)
         dc = {}
         self.corrs = [None if k is None else cached(dc, (id(k), elt), lambda: e.ctx.hybrid_hoist_correction(k, elt, L, e.alpha))
                       for k, elt in zip(self.dkeys, self.elts)]
@@ -120,100 +60,96 @@ class Case:
         new_plain = plain or (lambda: O.uniform_rns(rng, e.rows(L), (), e.n))
         self.plains = [[None if (g, r) in absent else new_plain() for r in range(self.R)] for g in range(n_out)]
         dp = {}
-        self.dplains = [[None if p is None else cached(dp, id(p), lambda: up(moai, p)) for p in row] for row in self.plains]
+        self.dplains = [[None if p is None else cached(dp, id(p), lambda: e.up(p)) for p in row] for row in self.plains]
         self.shape = (n_out, B, 2, L, e.n)
         if want:
             self.want = np.empty(self.shape, dtype=np.uint64)
             for b in range(B):
                 self.want[:, b] = HD.rotate_pt_dot(e.octx, self.ct[b], L, e.alpha, self.elts, self.keys, self.plains)
 
-    def run(self, moai):
+    def run(self):
         """(fallback flag, outputs [n_out][B][2][L][N]) from output buffers filled with a pattern"""
-        out = up(moai, np.full(int(np.prod(self.shape)), 0xABCD, dtype=np.uint64))
+        out = self.e.filled(self.shape, PATTERN)
         fb = self.e.ctx.hybrid_rotate_pt_dot(self.dct, out, self.L, self.e.alpha, self.elts, self.dkeys, self.corrs, self.dplains, self.B)
         got = out.to_numpy(self.shape)
         assert (self.dct.to_numpy(self.ct.shape) == self.ct).all()  # the input is left alone
         return fb, got
 
-    def check(self, moai):
-        fb, got = self.run(moai)
+    def check(self):
+        fb, got = self.run()
         assert not fb
         for g in range(self.n_out):
             assert (got[g] == self.want[g]).all(), g
 
 
 @pytest.fixture(scope="module")
-def case_tiled3(moai, env_tiled3):
+def case_tiled3(env_tiled3):
     """the default case at alpha = 3, L = 7, shared by the tests of the knobs"""
-    return Case(moai, env_tiled3, 7)
+    return Case(env_tiled3, 7)
 
 
 # ---- 1. alpha = 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [3, 1])
-def test_alpha_1_tiled_transform(moai, env_tiled1, L):
-    Case(moai, env_tiled1, L).check(moai)
+def test_alpha_1_tiled_transform(env_tiled1, L):
+    Case(env_tiled1, L).check()
 
 
-def test_alpha_1_small_transform(moai, env_small1):
-    Case(moai, env_small1, 2).check(moai)
+def test_alpha_1_small_transform(env_small1):
+    Case(env_small1, 2).check()
 
 
 # ---- 2. alpha > 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L", [5, 3, 1])
-def test_alpha_2_small_transform(moai, env_small2, L):
-    Case(moai, env_small2, L).check(moai)
+def test_alpha_2_small_transform(env_small2, L):
+    Case(env_small2, L).check()
 
 
-def test_alpha_3_tiled_transform_full_digits(moai, case_tiled3):
-    case_tiled3.check(moai)
+def test_alpha_3_tiled_transform_full_digits(case_tiled3):
+    case_tiled3.check()
 
 
-def test_alpha_3_tiled_transform_partial_digit(moai, env_tiled3):
-    Case(moai, env_tiled3, 4).check(moai)
+def test_alpha_3_tiled_transform_partial_digit(env_tiled3):
+    Case(env_tiled3, 4).check()
 
 
 # ---- 3. wide digits -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("alpha", [6, 12])
 def test_wide_digits(moai, alpha):
     e = Env(moai, 10, [40] * (alpha + 1), [50] * alpha)
-    Case(moai, e, alpha + 1, steps=[1, 0], B=1, n_out=1).check(moai)
-    e.ctx.close()
+    Case(e, alpha + 1, steps=[1, 0], B=1, n_out=1).check()
+    e.close()
 
 
 # ---- 4. the unit plaintext is the separate rotation -----------------------------------------------------------------------------
-def unit_plain(e, L):
-    return lambda: np.ones((L + e.alpha, e.n), dtype=np.uint64)
-
-
-def check_unit_rotation(moai, e, L, B):
-    c = Case(moai, e, L, steps=[3], B=B, n_out=1, plain=unit_plain(e, L), want=False)
-    d = up(moai, c.ct)
+def check_unit_rotation(e, L, B):
+    c = Case(e, L, steps=[3], B=B, n_out=1, plain=unit_plain(e, L), want=False)
+    d = e.up(c.ct)
     e.ctx.apply_galois_hybrid(d, L, e.alpha, c.elts[0], c.dkeys[0], B)
-    fb, got = c.run(moai)
+    fb, got = c.run()
     assert not fb
     assert (got[0] == d.to_numpy(c.shape[1:])).all()
 
 
-def test_one_rotation_with_the_unit_plaintext_is_apply_galois_hybrid(moai, env_small2):
+def test_one_rotation_with_the_unit_plaintext_is_apply_galois_hybrid(env_small2):
     for L in (5, 3):
-        check_unit_rotation(moai, env_small2, L, 3)
+        check_unit_rotation(env_small2, L, 3)
 
 
 def test_one_rotation_with_the_unit_plaintext_at_moais_parameters(moai):
     """N = 2^16, MOAI's 35 data primes plus twelve 60-bit special primes, L = 35: three digits, two of 12 primes and one of 11"""
     e = Env(moai, 16, MOAI_DATA_BITS, [60] * 12)
-    check_unit_rotation(moai, e, 35, 1)
-    e.ctx.close()
+    check_unit_rotation(e, 35, 1)
+    e.close()
 
 
 def test_degree_65536_equals_the_restatement(moai):
     e = Env(moai, 16, [51, 46, 46], [60, 60])
-    Case(moai, e, 3, steps=[1, 0, IDENT], B=1, n_out=2).check(moai)
-    e.ctx.close()
+    Case(e, 3, steps=[1, 0, IDENT], B=1, n_out=2).check()
+    e.close()
 
 
 # ---- 5. fallback ----------------------------------------------------------------------------------------------------------------
-def test_a_zero_coefficient_takes_the_unhoisted_route_and_the_same_bits(moai, env_small2):
+def test_a_zero_coefficient_takes_the_unhoisted_route_and_the_same_bits(env_small2):
     e, L = env_small2, 5
 
     def with_sparse_c1(rng):
@@ -223,8 +159,8 @@ def test_a_zero_coefficient_takes_the_unhoisted_route_and_the_same_bits(moai, en
         ct[0, 1] = e.octx.ntt(sparse, L)[0]
         return ct
 
-    c = Case(moai, e, L, ct=with_sparse_c1)
-    fb, got = c.run(moai)
+    c = Case(e, L, ct=with_sparse_c1)
+    fb, got = c.run()
     assert fb
     assert (got == c.want).all()
 
@@ -232,13 +168,11 @@ def test_a_zero_coefficient_takes_the_unhoisted_route_and_the_same_bits(moai, en
 # ---- 6. every instantiation -----------------------------------------------------------------------------------------------------
 def test_rotations_per_pass_do_not_change_the_bits(moai, case_tiled3):
     c = case_tiled3
-    try:
+    with tuned(moai):
         for per_pass in (4, 2, 1):
             moai.hip.set_tuning("MOAI_HYBRID_HOIST_NR", per_pass)
-            fb, got = c.run(moai)
+            fb, got = c.run()
             assert not fb and (got == c.want).all(), per_pass
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 7. chunking ----------------------------------------------------------------------------------------------------------------
@@ -252,13 +186,11 @@ def test_chunks_and_output_groups_give_the_unchunked_result(moai, case_tiled3):
     per_output, row_kib = 6 * L + 4 * e.alpha, e.n * 8 // 1024
     budgets = [2 * (shared + per_output) * row_kib, (shared + 2 * per_output) * row_kib, 1]
     assert budgets == [236 * 32, 172 * 32, 1]
-    try:
+    with tuned(moai):
         for kb in budgets:
             moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
-            fb, got = c.run(moai)
+            fb, got = c.run()
             assert not fb and (got == c.want).all(), kb
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 8. more than 63 terms ------------------------------------------------------------------------------------------------------
@@ -271,8 +203,8 @@ def test_65_rotations_of_full_size_plaintexts_sum_exactly(moai):
     e = Env(moai, 10, primes=primes, alpha=1)
     top = np.stack([np.full(e.n, q - 1, dtype=np.uint64) for q in e.rows(1)])
     steps = [[1, 3, -2, 5, 0][r % 5] for r in range(65)]
-    Case(moai, e, 1, steps=steps, B=1, n_out=1, plain=lambda: top, shared_key=True).check(moai)
-    e.ctx.close()
+    Case(e, 1, steps=steps, B=1, n_out=1, plain=lambda: top, shared_key=True).check()
+    e.close()
 
 
 # ---- 9. refusals ----------------------------------------------------------------------------------------------------------------
@@ -281,8 +213,8 @@ def test_every_refusal_is_einval_and_leaves_the_outputs_alone(moai, env_small2):
     L, B, R, G = e.lmax, 2, 2, 2
     lib = moai.hip.lib()
     words = B * 2 * L * n
-    fill = np.full(G * words, 7, dtype=np.uint64)
-    out, src = up(moai, fill), up(moai, np.full(words, 5, dtype=np.uint64))
+    fill = np.full(G * words, FILL, dtype=np.uint64)
+    out, src = e.up(fill), e.filled(words, 5)
     dkey, dcorr = moai.DeviceBuffer(e.digits * 2 * k * n), moai.DeviceBuffer(2 * (L + alpha) * n)
     dplain = moai.DeviceBuffer((L + alpha) * n)
     h, s, ky, co, pl = e.ctx.h, src.ptr, dkey.ptr, dcorr.ptr, dplain.ptr
@@ -344,13 +276,10 @@ def test_every_refusal_is_einval_and_leaves_the_outputs_alone(moai, env_small2):
 # ---- 10. op trace ---------------------------------------------------------------------------------------------------------------
 def test_op_trace_counts(moai, env_small2):
     e, L = env_small2, 3
-    c = Case(moai, e, L, steps=[1, IDENT], B=3, n_out=2, seed=9, want=False)
-    moai.hip.op_trace(True)
-    try:
-        c.run(moai)
-    finally:
-        moai.hip.op_trace(False)
-    counts = moai.hip.op_trace_counts()
+    c = Case(e, L, steps=[1, IDENT], B=3, n_out=2, seed=9, want=False)
+    with traced(moai) as trace:
+        c.run()
+    counts = trace()
     assert counts.get(("hybrid_rotate_pt_dot", L)) == 3 * 2
     assert ("apply_galois_hybrid", L) not in counts
     assert ("apply_galois_hybrid_hoisted", L) not in counts

@@ -18,46 +18,28 @@ computed once per shape and shared."""
 import numpy as np
 import pytest
 
+import hybrid_kit
 import hybrid_ref as HR
 import hybrid_rescale_ref as RR
 import oracle as O
+from hybrid_kit import EINVAL, ENVS, FILL, MOAI_DATA_BITS, traced, tuned
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
-FILL = 7
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-ENVS = {"small1": (10, [60, 60], [60]), "tiled1": (12, [51, 46, 46], [58]), "small2": (10, [40, 41, 42, 43, 44], [60, 60]),
-        "tiled3": (12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])}
 
+class Env(hybrid_kit.Env):
+    """with n_keys uniform keys on host and device, and the elements of two rotations and the conjugation"""
 
-class Env:
     def __init__(self, moai, logn, data_bits, special_bits, n_keys=3, oracle=True):
-        self.moai = moai
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits)
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits))
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes) if oracle else None
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
+        super().__init__(moai, logn, data_bits, special_bits, oracle=oracle)
         rng = np.random.default_rng(1000 + logn + self.k)
-        self.keys = [O.uniform_rns(rng, self.primes, (self.digits, 2), self.n) for _ in range(n_keys)]
-        self.dkeys = [moai.DeviceBuffer.from_numpy(key) for key in self.keys]
-        # two rotations and the conjugation
-        self.elts = [self.ctx.galois_elt_from_step(1), self.ctx.galois_elt_from_step(3), 2 * self.n - 1]
+        self.keys = [self.random_key(rng) for _ in range(n_keys)]
+        self.dkeys = [self.up(key) for key in self.keys]
+        self.elements = self.elts([1, 3, 0])
 
-    def up(self, a):
-        return self.moai.DeviceBuffer.from_numpy(a)
-
-    def filled(self, L, polys=2):
-        return self.up(np.full((polys, L, self.n), FILL, dtype=np.uint64))
-
-    def edges(self, L, polys):
-        top = np.stack([np.full(self.n, q - 1, dtype=np.uint64) for q in self.primes[:L]])
-        top = np.stack([top] * polys)
-        return top, np.zeros_like(top)
+    def out_block(self, L):
+        """an output of two polynomials, filled with the pattern"""
+        return self.filled((2, L, self.n), FILL)
 
     def members(self, rng, L, n):
         """n members (ciphertext, element, key index): keys and elements come round, so member 3 repeats member 0's key and element;
@@ -65,7 +47,7 @@ class Env:
         cts = O.uniform_rns(rng, self.primes[:L], (n, 2), self.n)
         if n >= 3:
             cts[1], cts[2] = self.edges(L, 2)
-        return [(cts[i], self.elts[i % 3], i % len(self.keys)) for i in range(n)]
+        return [(cts[i], self.elements[i % 3], i % len(self.keys)) for i in range(n)]
 
     def ct3s(self, rng, L, n):
         c = O.uniform_rns(rng, self.primes[:L], (n, 3), self.n)
@@ -98,7 +80,7 @@ def unchanged(bufs, hosts):
 def run_galois_ptrs(e, L, members, sums=None):
     """the list call on fresh blocks with pattern-filled outputs; the inputs and keys are compared afterwards"""
     d_in = [e.up(ct) for ct, _, _ in members]
-    d_out = [e.filled(L) for _ in members]
+    d_out = [e.out_block(L) for _ in members]
     e.ctx.apply_galois_hybrid_ptrs(d_in, d_out, L, e.alpha, [m[1] for m in members], [e.dkeys[m[2]] for m in members], sums)
     got = [d.to_numpy((2, L, e.n)) for d in d_out]
     unchanged(d_in, [m[0] for m in members])
@@ -117,7 +99,7 @@ def single_galois(e, L, members):
 def run_relin_ptrs(e, L, ct3, rescale):
     Lout = L - 1 if rescale else L
     d_in = [e.up(c) for c in ct3]
-    d_out = [e.filled(Lout) for _ in ct3]
+    d_out = [e.out_block(Lout) for _ in ct3]
     call = e.ctx.relinearize_rescale_hybrid_ptrs if rescale else e.ctx.relinearize_hybrid_ptrs
     call(d_in, d_out, e.dkeys[0], L, e.alpha)
     got = [d.to_numpy((2, Lout, e.n)) for d in d_out]
@@ -130,7 +112,7 @@ def single_relin(e, L, ct3, rescale):
     call = e.ctx.relinearize_rescale_hybrid if rescale else e.ctx.relinearize_hybrid
     out = []
     for c in ct3:
-        d = e.filled(Lout)
+        d = e.out_block(Lout)
         call(e.up(c), e.dkeys[0], d, L, e.alpha, 1)
         out.append(d.to_numpy((2, Lout, e.n)))
     return out
@@ -151,12 +133,12 @@ def test_alpha_1_equals_the_seal_style_list_calls(env, which, level):
     rng = np.random.default_rng(e.logn * 10 + L)
     members = e.members(rng, L, n)
     elts, keys = [m[1] for m in members], [e.dkeys[m[2]] for m in members]
-    assert sorted(elts) == sorted(e.elts) and len(set(m[2] for m in members)) == 3
+    assert sorted(elts) == sorted(e.elements) and len(set(m[2] for m in members)) == 3
     addends = O.uniform_rns(rng, e.primes[:L], (n, 2), e.n)
     for with_sums in (False, True):
         d_in = [e.up(m[0]) for m in members]
         sums = [e.up(addends[0]), None, e.up(addends[2])] if with_sums else None
-        a, b = [e.filled(L) for _ in members], [e.filled(L) for _ in members]
+        a, b = [e.out_block(L) for _ in members], [e.out_block(L) for _ in members]
         e.ctx.apply_galois_ptrs(d_in, a, L, elts, keys, sums)
         e.ctx.apply_galois_hybrid_ptrs(d_in, b, L, 1, elts, keys, sums)
         same([d.to_numpy((2, L, e.n)) for d in b], [d.to_numpy((2, L, e.n)) for d in a], "sums %s" % with_sums)
@@ -165,7 +147,7 @@ def test_alpha_1_equals_the_seal_style_list_calls(env, which, level):
             unchanged([sums[0], sums[2]], [addends[0], addends[2]])
     ct3 = e.ct3s(rng, L, n)
     d_in = [e.up(c) for c in ct3]
-    a, b = [e.filled(L) for _ in ct3], [e.filled(L) for _ in ct3]
+    a, b = [e.out_block(L) for _ in ct3], [e.out_block(L) for _ in ct3]
     e.ctx.relinearize_ptrs(d_in, a, e.dkeys[1], L)
     e.ctx.relinearize_hybrid_ptrs(d_in, b, e.dkeys[1], L, 1)
     same([d.to_numpy((2, L, e.n)) for d in b], [d.to_numpy((2, L, e.n)) for d in a], "relinearize")
@@ -242,7 +224,7 @@ def test_sums_and_in_place_members(env):
             e.ctx.apply_galois_hybrid_acc(e.up(ct), acc, L, e.alpha, elt, e.dkeys[ki], 1)
             single.append(acc.to_numpy((2, L, e.n)))
         elif i == 0:
-            d = e.filled(L)
+            d = e.out_block(L)
             e.ctx.apply_galois_hybrid_to(e.up(ct), d, L, e.alpha, elt, e.dkeys[ki], 1)
             single.append(d.to_numpy((2, L, e.n)))
         else:
@@ -255,7 +237,7 @@ def test_sums_and_in_place_members(env):
         assert (single[i] == (plain[i] + addends[i]) % q).all(), i  # _acc is the switch followed by moai_add's canonical sum
     d_in = [e.up(m[0]) for m in members]
     d_sum = [None, e.up(addends[1]), e.up(addends[2]), None]
-    d_out = [e.filled(L), e.filled(L), d_sum[2], d_in[3]]
+    d_out = [e.out_block(L), e.out_block(L), d_sum[2], d_in[3]]
     e.ctx.apply_galois_hybrid_ptrs(d_in, d_out, L, e.alpha, [m[1] for m in members], [e.dkeys[m[2]] for m in members], d_sum)
     same([d.to_numpy((2, L, e.n)) for d in d_out], single, "singles")
     unchanged([d_sum[1]], [addends[1]])  # a sum that is not an output is only read
@@ -270,7 +252,7 @@ def test_to_and_acc_at_batch_3(moai, env, which, L):
     rng = np.random.default_rng(44 + L)
     ct = O.uniform_rns(rng, e.primes[:L], (B, 2), e.n)
     base = O.uniform_rns(rng, e.primes[:L], (B, 2), e.n)
-    elt, dkey = e.elts[1], e.dkeys[2]
+    elt, dkey = e.elements[1], e.dkeys[2]
     per = (HR.beta(L, e.alpha) * (L + e.alpha) + 4 * L + 4 * e.alpha + 2 * L) * e.n * 8
     two = 2 * per + per // 2 >> 10  # KiB that hold two ciphertexts of the batch, not three
     assert (two << 10) // per == 2
@@ -280,12 +262,12 @@ def test_to_and_acc_at_batch_3(moai, env, which, L):
     summed = e.moai.DeviceBuffer(B * 2 * L * e.n)
     e.ctx.add(e.up(want), e.up(base), summed, B * 2, L)
     summed = summed.to_numpy((B, 2, L, e.n))
-    try:
+    with tuned(moai):
         for kb in (None, two):
             moai.hip.reset_tuning()
             if kb:
                 moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
-            src, dst = e.up(ct), e.up(np.full((B, 2, L, e.n), FILL, dtype=np.uint64))
+            src, dst = e.up(ct), e.filled((B, 2, L, e.n), FILL)
             e.ctx.apply_galois_hybrid_to(src, dst, L, e.alpha, elt, dkey, B)
             assert (dst.to_numpy((B, 2, L, e.n)) == want).all(), kb
             unchanged([src], [ct])
@@ -295,8 +277,6 @@ def test_to_and_acc_at_batch_3(moai, env, which, L):
             e.ctx.apply_galois_hybrid_acc(src, acc, L, e.alpha, elt, dkey, B)
             assert (acc.to_numpy((B, 2, L, e.n)) == summed).all(), kb
             unchanged([src], [ct])
-    finally:
-        moai.hip.reset_tuning()
     e.keys_unchanged()
 
 
@@ -309,14 +289,12 @@ def test_seventy_members_take_two_passes(moai, env):
     ct3 = e.ct3s(np.random.default_rng(71), L, n)
     relin = run_relin_ptrs(e, L, ct3, False)
     same(relin, [HR.relinearize(e.octx, c, e.keys[0], L, e.alpha) for c in ct3], "restatement")
-    try:
+    with tuned(moai):
         # a budget of 33 members: three passes of 33, 33 and 4
         per = (HR.beta(L, e.alpha) * (L + e.alpha) + 4 * L + 4 * e.alpha + 2 * L) * e.n * 8
         moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", 33 * per + 1023 >> 10)
         assert ((33 * per + 1023 >> 10) << 10) // per == 33
         same(run_galois_ptrs(e, L, members), got, "budget of 33")
-    finally:
-        moai.hip.reset_tuning()
     e.keys_unchanged()
 
 
@@ -334,14 +312,12 @@ def test_a_budget_of_two_members_gives_the_default_budgets_bits(moai, env):
     members = e.members(np.random.default_rng(55), L, n)
     ct3 = e.ct3s(np.random.default_rng(56), L, n)
     got = {}
-    try:
+    with tuned(moai):
         for budget in (None, kb):
             moai.hip.reset_tuning()
             if budget:
                 moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", budget)
             got[budget] = (run_galois_ptrs(e, L, members), run_relin_ptrs(e, L, ct3, False), run_relin_ptrs(e, L, ct3, True))
-    finally:
-        moai.hip.reset_tuning()
     for x, y in zip(got[kb], got[None]):
         same(x, y, "budget")
     same(got[None][0], single_galois(e, L, members), "singles")
@@ -361,7 +337,7 @@ def test_wide_digits_against_the_singles(moai, alpha):
     for rescale in (False, True):
         same(run_relin_ptrs(e, L, ct3, rescale), single_relin(e, L, ct3, rescale), "relin, rescale %s" % rescale)
     e.keys_unchanged()
-    e.ctx.close()
+    e.close()
 
 
 def test_n65536_at_moais_parameters_once(moai):
@@ -370,12 +346,12 @@ def test_n65536_at_moais_parameters_once(moai):
     L = 15
     rng = np.random.default_rng(16)
     cts = O.uniform_rns(rng, e.primes[:L], (2, 2), e.n)
-    members = [(cts[0], e.elts[0], 0), (cts[1], e.elts[2], 1)]
+    members = [(cts[0], e.elements[0], 0), (cts[1], e.elements[2], 1)]
     same(run_galois_ptrs(e, L, members), single_galois(e, L, members), "galois")
     ct3 = e.ct3s(rng, L, 2)
     same(run_relin_ptrs(e, L, ct3, True), single_relin(e, L, ct3, True), "rescale")
     e.keys_unchanged()
-    e.ctx.close()
+    e.close()
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------------
@@ -475,7 +451,7 @@ def test_every_refusal_is_einval_names_the_member_and_writes_nothing(moai, env):
     assert lib.moai_relinearize_rescale_hybrid_ptrs(None, None, None, None, 1, 16, 0, None) == 0
     check(galois(L=0), "L = 0")  # nothing above wrote anything
     # an output block of the rescale form is 2 (L - 1) N words: three outputs packed at that stride are no overlap, one word less is
-    packed = e.up(np.full(3 * 2 * (L - 1) * N + 8, FILL, dtype=np.uint64))
+    packed = e.filled(3 * 2 * (L - 1) * N + 8, FILL)
     step = 2 * (L - 1) * N * 8
     check(relin(True, outs=[packed.ptr, packed.ptr + step - 8, packed.ptr + 2 * step]), "the output overlaps a block of member")
     e.ctx.relinearize_rescale_hybrid_ptrs(d_ct3, [packed.ptr + i * step for i in range(3)], e.dkeys[0], L, a)
@@ -483,7 +459,7 @@ def test_every_refusal_is_einval_names_the_member_and_writes_nothing(moai, env):
     same(list(got[:3 * 2 * (L - 1) * N].reshape(3, 2, L - 1, N)), single_relin(e, L, ct3, True), "packed outputs")
     assert (got[3 * 2 * (L - 1) * N:] == FILL).all()
     e.keys_unchanged()
-    wide.ctx.close()
+    wide.close()
 
 
 # ---- 9. the census --------------------------------------------------------------------------------------------------------------------
@@ -492,16 +468,13 @@ def test_op_trace_counts_the_calls_they_replace(moai, env):
     members = e.members(np.random.default_rng(3), L, 5)
     ct3 = e.ct3s(np.random.default_rng(4), L, 4)
     batch = e.up(np.stack([m[0] for m in members[:3]]))
-    moai.hip.op_trace(True)
-    try:
+    with traced(moai) as trace:
         run_galois_ptrs(e, L, members)                                                 # 5
-        e.ctx.apply_galois_hybrid_to(batch, e.filled(3 * L), L, e.alpha, e.elts[0], e.dkeys[0], 3)  # 3
-        e.ctx.apply_galois_hybrid_acc(batch, e.filled(3 * L), L, e.alpha, e.elts[0], e.dkeys[0], 3)  # 3
+        e.ctx.apply_galois_hybrid_to(batch, e.out_block(3 * L), L, e.alpha, e.elements[0], e.dkeys[0], 3)  # 3
+        e.ctx.apply_galois_hybrid_acc(batch, e.out_block(3 * L), L, e.alpha, e.elements[0], e.dkeys[0], 3)  # 3
         run_relin_ptrs(e, L, ct3, False)                                               # 4
         run_relin_ptrs(e, L, ct3[:2], True)                                            # 2
-    finally:
-        moai.hip.op_trace(False)
-    counts = moai.hip.op_trace_counts()
+    counts = trace()
     assert counts.get(("apply_galois_hybrid", L)) == 11
     assert counts.get(("relinearize_hybrid", L)) == 4
     assert counts.get(("relinearize_rescale_hybrid", L)) == 2

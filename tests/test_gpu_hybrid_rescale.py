@@ -22,65 +22,17 @@ import hybrid_ref as HR
 import hybrid_rescale_ref as RR
 import mode_limits as ML
 import oracle as O
+from hybrid_kit import EINVAL, FILL, MOAI_DATA_BITS, OK, PATTERN, Env, cached, traced, tuned
+from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL = 0, -1
-MOAI_DATA_BITS = [51] + [46] * 20 + [51] * 14  # MOAI's 35 data primes
-PATTERN = 0xABCD
-
-
-class Env:
-    def __init__(self, moai, logn, data_bits=None, special_bits=None, primes=None, alpha=None):
-        self.logn, self.n = logn, 1 << logn
-        self.alpha = len(special_bits) if primes is None else alpha
-        self.primes = O.coeff_modulus_create(self.n, list(data_bits) + list(special_bits)) if primes is None else list(primes)
-        self.k = len(self.primes)
-        self.lmax = self.k - self.alpha
-        self.octx = O.Context(logn, self.primes)
-        self.ctx = moai.Context(logn, self.primes)
-        self.digits = HR.beta(self.lmax, self.alpha)
-        self._key = None
-
-    def key(self):
-        """one uniform key per environment, (host, device), made once"""
-        if self._key is None:
-            k = O.uniform_rns(np.random.default_rng(self.logn * 100 + self.alpha), self.primes, (self.digits, 2), self.n)
-            self._key = k, up(k)
-        return self._key
-
-
-DeviceBuffer = None  # the package's DeviceBuffer, bound from the moai fixture before any test of the module runs
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _device_buffer(moai):
-    global DeviceBuffer
-    DeviceBuffer = moai.DeviceBuffer
-
-
-def up(a):
-    return DeviceBuffer.from_numpy(a)
-
-
-@pytest.fixture(scope="module")
-def env_small1(moai):
-    return Env(moai, 10, [60, 60], [60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled1(moai):
-    return Env(moai, 12, [51, 46, 46], [58])
-
-
-@pytest.fixture(scope="module")
-def env_small2(moai):
-    return Env(moai, 10, [40, 41, 42, 43, 44], [60, 60])
-
-
-@pytest.fixture(scope="module")
-def env_tiled3(moai):
-    return Env(moai, 12, [51, 46, 46, 46, 51, 46, 51], [58, 60, 60])
+def key_of(e):
+    """one uniform key per environment, (host, device), made once"""
+    def make():
+        k = O.uniform_rns(np.random.default_rng(e.logn * 100 + e.alpha), e.primes, (e.digits, 2), e.n)
+        return k, e.up(k)
+    return cached(e.cache, "key", make)
 
 
 def default_batch(e):
@@ -95,15 +47,15 @@ class Case:
         self.B = B = default_batch(e) if B is None else B
         rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed + 3)
         self.ct3 = O.uniform_rns(rng, e.primes[:L], (B, 3), e.n) if ct3 is None else ct3
-        self.dct3 = up(self.ct3)
-        self.key, self.dkey = e.key() if key is None else (key, up(key))
+        self.dct3 = e.up(self.ct3)
+        self.key, self.dkey = key_of(e) if key is None else (key, e.up(key))
         self.shape = (B, 2, L - 1, e.n)
         if want:
             self.want = np.stack([RR.relinearize_rescale(e.octx, self.ct3[b], self.key, L, e.alpha) for b in range(B)])
 
     def run(self):
         """the output [B][2][L-1][N], from a buffer filled with a pattern"""
-        out = up(np.full(int(np.prod(self.shape)), PATTERN, dtype=np.uint64))
+        out = self.e.filled(self.shape, PATTERN)
         self.e.ctx.relinearize_rescale_hybrid(self.dct3, self.dkey, out, self.L, self.e.alpha, self.B)
         got = out.to_numpy(self.shape)
         assert (self.dct3.to_numpy(self.ct3.shape) == self.ct3).all()  # the inputs are left alone
@@ -114,14 +66,9 @@ class Case:
         assert (self.run() == self.want).all()
 
 
-_cases = {}
-
-
 def case(e, L):
     """the default case of an environment at L, shared by the tests that run at the shapes of 2 and 3"""
-    if (id(e), L) not in _cases:
-        _cases[id(e), L] = Case(e, L)
-    return _cases[id(e), L]
+    return cached(e.cache, ("case", L), lambda: Case(e, L))
 
 
 # ---- 1. alpha = 1 ---------------------------------------------------------------------------------------------------------------
@@ -151,7 +98,7 @@ def test_wide_digits(moai, alpha):
     """alpha = 8: nine sources, which only the 16-source instantiation of the conversion holds"""
     e = Env(moai, 10, [40] * (alpha + 1), [50] * alpha)
     Case(e, alpha + 1, B=1).check()
-    e.ctx.close()
+    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -185,7 +132,7 @@ def test_sources_far_from_the_targets(moai, which, logn):
     primes, _, alpha = ML.hybrid_chain(logn, which)
     e = Env(moai, logn, primes=primes, alpha=alpha)
     Case(e, e.lmax, B=1).check()
-    e.ctx.close()
+    e.close()
 
 
 # ---- 5. against the device's own composition --------------------------------------------------------------------------------------
@@ -193,10 +140,10 @@ def check_distance_to_the_composition(e, c, got):
     """got - rescale(relinearize_hybrid(ct3)), per output row in coefficient form: the residue of one integer d in [-(alpha + 1), 1],
     the same in every row"""
     ctx, L, B, n = e.ctx, c.L, c.B, e.n
-    relin, comp = DeviceBuffer(B * 2 * L * n), DeviceBuffer(B * 2 * (L - 1) * n)
+    relin, comp = e.moai.DeviceBuffer(B * 2 * L * n), e.moai.DeviceBuffer(B * 2 * (L - 1) * n)
     ctx.relinearize_hybrid(c.dct3, c.dkey, relin, L, e.alpha, B)
     ctx.rescale(relin, comp, 2, L, B)
-    diff, dgot = DeviceBuffer(B * 2 * (L - 1) * n), up(got)
+    diff, dgot = e.moai.DeviceBuffer(B * 2 * (L - 1) * n), e.up(got)
     ctx.sub(dgot, comp, diff, B * 2, L - 1)
     ctx.ntt_inverse(diff, B * 2, L - 1)
     r = diff.to_numpy(c.shape)
@@ -225,7 +172,7 @@ def test_distance_to_the_composition_at_moais_parameters(moai):
     for L in (35, 15):
         c = Case(e, L, B=2, want=False)
         check_distance_to_the_composition(e, c, c.run())
-    e.ctx.close()
+    e.close()
 
 
 # ---- 6. the product in scratch ------------------------------------------------------------------------------------------------------
@@ -233,14 +180,14 @@ def check_multiply(e, L, B):
     ctx, n = e.ctx, e.n
     rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + 77)
     x, y = O.uniform_rns(rng, e.primes[:L], (B, 2), n), O.uniform_rns(rng, e.primes[:L], (B, 2), n)
-    dx, dy = up(x), up(y)
-    _, dkey = e.key()
+    dx, dy = e.up(x), e.up(y)
+    _, dkey = key_of(e)
     shape = (B, 2, L - 1, n)
     for other, dother, product in ((y, dy, lambda t: ctx.ct_multiply(dx, dy, t, L, B)), (x, dx, lambda t: ctx.ct_square(dx, t, L, B))):
-        ct3, want = DeviceBuffer(B * 3 * L * n), DeviceBuffer(int(np.prod(shape)))
+        ct3, want = e.moai.DeviceBuffer(B * 3 * L * n), e.moai.DeviceBuffer(int(np.prod(shape)))
         product(ct3)
         ctx.relinearize_rescale_hybrid(ct3, dkey, want, L, e.alpha, B)
-        out = up(np.full(int(np.prod(shape)), PATTERN, dtype=np.uint64))
+        out = e.filled(shape, PATTERN)
         ctx.multiply_relin_rescale_hybrid(dx, dother, dkey, out, L, e.alpha, B)
         assert (out.to_numpy(shape) == want.to_numpy(shape)).all()
         assert (dx.to_numpy(x.shape) == x).all() and (dother.to_numpy(other.shape) == other).all()  # the inputs are left alone
@@ -260,9 +207,9 @@ def test_multiply_equals_the_restatement(env_small2):
     e, L = env_small2, 4
     rng = np.random.default_rng(11)
     x, y = O.uniform_rns(rng, e.primes[:L], (1, 2), e.n), O.uniform_rns(rng, e.primes[:L], (1, 2), e.n)
-    key, dkey = e.key()
-    out = DeviceBuffer(2 * (L - 1) * e.n)
-    e.ctx.multiply_relin_rescale_hybrid(up(x), up(y), dkey, out, L, e.alpha, 1)
+    key, dkey = key_of(e)
+    out = e.moai.DeviceBuffer(2 * (L - 1) * e.n)
+    e.ctx.multiply_relin_rescale_hybrid(e.up(x), e.up(y), dkey, out, L, e.alpha, 1)
     assert (out.to_numpy((2, L - 1, e.n)) == RR.multiply_relin_rescale(e.octx, x[0], y[0], key, L, e.alpha)).all()
 
 
@@ -275,19 +222,17 @@ def test_a_budget_of_one_ciphertext_gives_the_same_bits(moai, env_small2):
     assert c.B == 3
     rows = HR.beta(L, e.alpha) * (L + e.alpha) + 2 * (L + e.alpha) + 2 * (e.alpha + 1) + 2 * (L - 1)
     assert rows == 49
-    x = up(c.ct3[:, :2].copy())
-    _, dkey = e.key()
-    unchunked = DeviceBuffer(int(np.prod(c.shape)))
+    x = e.up(c.ct3[:, :2].copy())
+    _, dkey = key_of(e)
+    unchunked = moai.DeviceBuffer(int(np.prod(c.shape)))
     e.ctx.multiply_relin_rescale_hybrid(x, x, dkey, unchunked, L, e.alpha, c.B)
-    try:
+    with tuned(moai):
         for kb in (rows * e.n * 8 // 1024, (rows + 3 * L) * e.n * 8 // 1024, 1):
             moai.hip.set_tuning("MOAI_HYBRID_TMP_KB", kb)
             assert (c.run() == c.want).all(), kb
-            out = DeviceBuffer(int(np.prod(c.shape)))
+            out = moai.DeviceBuffer(int(np.prod(c.shape)))
             e.ctx.multiply_relin_rescale_hybrid(x, x, dkey, out, L, e.alpha, c.B)
             assert (out.to_numpy() == unchunked.to_numpy()).all(), kb
-    finally:
-        moai.hip.reset_tuning()
 
 
 # ---- 8. refusals ------------------------------------------------------------------------------------------------------------------
@@ -295,10 +240,10 @@ def test_every_refusal_is_einval_and_leaves_everything_alone(moai, env_small2):
     e, n, k, alpha = env_small2, env_small2.n, env_small2.k, env_small2.alpha
     L, B = e.lmax, 2
     lib = moai.hip.lib()
-    fill = np.full(B * 2 * (L - 1) * n, 7, dtype=np.uint64)
-    out = up(fill)
-    src = up(np.full(B * 3 * L * n, 5, dtype=np.uint64))  # ct3; x and y are its first B * 2 * L * N words
-    dkey = up(np.full(e.digits * 2 * k * n, 3, dtype=np.uint64))
+    fill = np.full(B * 2 * (L - 1) * n, FILL, dtype=np.uint64)
+    out = e.up(fill)
+    src = e.filled(B * 3 * L * n, 5)  # ct3; x and y are its first B * 2 * L * N words
+    dkey = e.filled(e.digits * 2 * k * n, 3)
     h, s, o, ky = e.ctx.h, src.ptr, out.ptr, dkey.ptr
 
     def rr(ctx=h, ct3=s, key=ky, out=o, L=L, alpha=alpha, batch=B):
@@ -345,18 +290,14 @@ def test_every_refusal_is_einval_and_leaves_everything_alone(moai, env_small2):
 def test_op_trace_counts(moai, env_small2):
     e, L = env_small2, 3
     c = case(e, L)
-    x = up(c.ct3[:, :2].copy())
-    out = DeviceBuffer(int(np.prod(c.shape)))
-    moai.hip.op_trace(True)
-    try:
+    x = e.up(c.ct3[:, :2].copy())
+    out = moai.DeviceBuffer(int(np.prod(c.shape)))
+    with traced(moai) as trace:
         c.run()
-        counts1 = moai.hip.op_trace_counts()
-        moai.hip.op_trace(False)
-        moai.hip.op_trace(True)
+        counts1 = trace()
+    with traced(moai) as trace:
         e.ctx.multiply_relin_rescale_hybrid(x, x, c.dkey, out, L, e.alpha, c.B)
-    finally:
-        moai.hip.op_trace(False)
-    counts2 = moai.hip.op_trace_counts()
+    counts2 = trace()
     assert counts1.get(("relinearize_rescale_hybrid", L)) == c.B
     assert counts2.get(("multiply_relin_rescale_hybrid", L)) == c.B
     for counts in (counts1, counts2):

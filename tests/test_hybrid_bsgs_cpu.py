@@ -8,7 +8,6 @@
 (c) the symbol is exported, declared and bound, its comment cites reference lines, and the refusals that need no context are
     answered before the device is touched."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -18,10 +17,8 @@ import hybrid_bsgs_ref as HB
 import hybrid_dot_ref as HD
 import hybrid_ref as HR
 import oracle as O
-from test_hybrid_pt_dot_cpu import KEY, NOISE_CASES, UNIT_CASES, elt_of, secret
+from hybrid_kit import EINVAL, KEY, NOISE_CASES, UNIT_CASES, elt_of, exported, header_comment, secret
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
 NAME = "moai_hybrid_bsgs_dot"
 
 
@@ -67,7 +64,7 @@ def test_decryption_error_is_within_the_bound(data, special, L, steps, bits):
     bits = max(bits, 16)  # 16 to 20 bits on every chain
     primes = O.coeff_modulus_create(1 << logn, data + special)
     octx = O.Context(logn, primes)
-    s, sk = secret(octx, 1)
+    s, sk = secret(octx, KEY, 1)
     rng = np.random.default_rng(2000 * alpha + 10 * L)
     baby = [1, elt_of(logn, 1), elt_of(logn, 2), elt_of(logn, 3)]
     giant = [1, elt_of(logn, 4), elt_of(logn, -8), elt_of(logn, 0)]
@@ -92,18 +89,11 @@ def test_decryption_error_is_within_the_bound(data, special, L, steps, bits):
 
 # ---- (c) the C ABI --------------------------------------------------------------------------------------------------------------
 def test_symbol_exported_declared_and_bound(moai):
-    L = C.CDLL(moai.lib_path())
-    assert hasattr(L, NAME)
-    assert NAME in moai.hip.SYMBOLS
-    assert callable(moai.Context.hybrid_bsgs_dot)
+    exported(moai, [NAME], ["hybrid_bsgs_dot"])
 
 
 def test_header_comment_cites_reference_lines():
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
-    at = hdr.index(" " + NAME + "(")
-    at = hdr.rindex("\n", 0, at) + 1  # the start of the declaration's line
-    comment = hdr[hdr.rindex("/*", 0, at):at]
-    assert comment.rstrip().endswith("*/")  # the comment sits directly on the declaration
+    comment = header_comment(NAME)
     assert re.search(r"Bootstrapper\.cpp:1997-2062", comment)
     assert re.search(r"SEAL/evaluator\.cpp:2724-3020", comment)
 

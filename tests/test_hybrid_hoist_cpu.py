@@ -6,7 +6,6 @@ switch").
 (b) the two symbols are exported and bound, their comments cite reference lines, and the refusals that need no context are answered
     before the device is touched."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -15,9 +14,8 @@ import pytest
 import hybrid_hoist_ref as HH
 import hybrid_ref as HR
 import oracle as O
+from hybrid_kit import EINVAL, exported, header, header_comment
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
 NAMES = ("moai_hybrid_hoist_correction", "moai_apply_galois_hybrid_hoisted")
 
 # (logn, data bits, special bits, L, steps); step 0 is the conjugation
@@ -59,23 +57,13 @@ def test_sign_mask_marks_the_negated_coefficients():
 
 # ---- (b) the C ABI --------------------------------------------------------------------------------------------------------------
 def test_symbols_exported_and_declared(moai):
-    L = C.CDLL(moai.lib_path())
-    for name in NAMES:
-        assert hasattr(L, name), name
-        assert name in moai.hip.SYMBOLS, name
-    for method in ("hybrid_hoist_correction", "apply_galois_hybrid_hoisted"):
-        assert callable(getattr(moai.Context, method)), method
+    exported(moai, NAMES, ("hybrid_hoist_correction", "apply_galois_hybrid_hoisted"))
 
 
 def test_header_comments_cite_reference_lines():
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
     for name in NAMES:
-        at = hdr.index(" " + name + "(")
-        at = hdr.rindex("\n", 0, at) + 1  # the start of the declaration's line
-        comment = hdr[hdr.rindex("/*", 0, at):at]
-        assert comment.rstrip().endswith("*/"), name  # the comment sits directly on the declaration
-        assert re.search(r"SEAL/evaluator\.cpp:2724-3020", comment), name
-    assert "MOAI_HYBRID_HOIST_NR" in hdr
+        assert re.search(r"SEAL/evaluator\.cpp:2724-3020", header_comment(name)), name
+    assert "MOAI_HYBRID_HOIST_NR" in header()
 
 
 def test_arguments_refused_without_a_device(moai):

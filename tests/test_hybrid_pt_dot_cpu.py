@@ -6,38 +6,20 @@
 (c) the symbol is exported and bound, its comment cites reference lines, and the refusals that need no context are answered before
     the device is touched."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import client_sampling as CS
 import hybrid_dot_ref as HD
 import hybrid_ref as HR
 import oracle as O
+from hybrid_kit import EINVAL, KEY, NOISE_CASES, UNIT_CASES, elt_of, exported, header_comment, secret
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -1
 NAME = "moai_hybrid_rotate_pt_dot"
-KEY = bytes(range(32))
-
-
-def secret(octx, seq):
-    """a ternary secret: (coefficients, NTT form over all k primes)"""
-    s = CS.ternary(KEY, CS.nonce(CS.TERNARY, seq), octx.n)
-    return s, octx.ntt(CS.to_rns(s, octx.primes), octx.k)
-
-
-def elt_of(logn, step):
-    return O.galois_elt_from_step(logn, step) if step else 2 * (1 << logn) - 1
 
 
 # ---- (a) one rotation with p = 1 is the separate rotation ----------------------------------------------------------------------
-# (data bits, special bits, levels)
-UNIT_CASES = [([30, 31, 32], [40], (3, 1)), ([30, 31, 32, 33, 34], [40, 41], (5, 3, 1)), ([30, 31, 32, 33], [40, 41, 42], (4, 2))]
-
-
 @pytest.mark.parametrize("data,special,levels", UNIT_CASES)
 def test_one_rotation_with_the_unit_plaintext_is_apply_galois(data, special, levels):
     logn, alpha = 5, len(special)
@@ -58,21 +40,12 @@ def test_one_rotation_with_the_unit_plaintext_is_apply_galois(data, special, lev
 
 
 # ---- (b) the noise bound ----------------------------------------------------------------------------------------------------------
-# (data bits, special bits, L, steps (0 = conjugation), bits of the plaintext coefficients)
-NOISE_CASES = [
-    ([40, 41, 42, 43, 44], [60, 60], 5, [1, 3, -2, 5, 0], 20),
-    ([40, 41, 42, 43, 44], [60, 60], 3, [1, 3, -2, 5, 0], 20),
-    ([40, 41, 42, 43, 44], [60, 60], 1, [1, 0], 10),
-    ([36] * 7, [58, 60, 60], 7, [1, 2, 3, 4, 5, -1, -2, 0], 16),
-]
-
-
 @pytest.mark.parametrize("data,special,L,steps,bits", NOISE_CASES)
 def test_decryption_error_is_within_the_bound(data, special, L, steps, bits):
     logn, alpha = 6, len(special)
     primes = O.coeff_modulus_create(1 << logn, data + special)
     octx = O.Context(logn, primes)
-    s, sk = secret(octx, 1)
+    s, sk = secret(octx, KEY, 1)
     rng = np.random.default_rng(1000 * alpha + 10 * L + len(steps))
     elts = [elt_of(logn, st) for st in steps]
     keys = [HR.keygen(octx, KEY, 100 * (r + 1), sk, sk[:, O.galois_table_ntt(logn, elt)], alpha) for r, elt in enumerate(elts)]
@@ -92,18 +65,11 @@ def test_decryption_error_is_within_the_bound(data, special, L, steps, bits):
 
 # ---- (c) the C ABI --------------------------------------------------------------------------------------------------------------
 def test_symbol_exported_and_declared(moai):
-    L = C.CDLL(moai.lib_path())
-    assert hasattr(L, NAME)
-    assert NAME in moai.hip.SYMBOLS
-    assert callable(moai.Context.hybrid_rotate_pt_dot)
+    exported(moai, [NAME], ["hybrid_rotate_pt_dot"])
 
 
 def test_header_comment_cites_reference_lines():
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
-    at = hdr.index(" " + NAME + "(")
-    at = hdr.rindex("\n", 0, at) + 1  # the start of the declaration's line
-    comment = hdr[hdr.rindex("/*", 0, at):at]
-    assert comment.rstrip().endswith("*/")  # the comment sits directly on the declaration
+    comment = header_comment(NAME)
     assert re.search(r"Bootstrapper\.cpp:2017-2042, 2082-2108", comment)
     assert re.search(r"SEAL/evaluator\.cpp:2724-3020", comment)
 

@@ -5,8 +5,6 @@
     within the header's bound B;
 (c) the five symbols are exported and bound, their comments cite reference lines, and the refusals that need no context are
     answered before the device is touched."""
-import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -15,17 +13,9 @@ import pytest
 import client_sampling as CS
 import hybrid_ref as HR
 import oracle as O
+from hybrid_kit import EINVAL, KEY, exported, header_comment, secret
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL = 0, -1
 NAMES = ("moai_hybrid_digits", "moai_hybrid_keygen", "moai_switch_key_hybrid", "moai_relinearize_hybrid", "moai_apply_galois_hybrid")
-KEY = bytes(range(32))
-
-
-def secret(octx, seq):
-    """a ternary secret: (coefficients, NTT form over all k primes)"""
-    s = CS.ternary(KEY, CS.nonce(CS.TERNARY, seq), octx.n)
-    return s, octx.ntt(CS.to_rns(s, octx.primes), octx.k)
 
 
 # ---- (a) alpha = 1 is the reference -----------------------------------------------------------------------------------------
@@ -63,8 +53,8 @@ def test_alpha_1_relinearize_and_galois_are_the_oracles(env1, level):
 
 def test_alpha_1_key_is_client_samplings(env1):
     octx, _, _ = env1
-    _, sk = secret(octx, 1)
-    _, new = secret(octx, 2)
+    _, sk = secret(octx, KEY, 1)
+    _, new = secret(octx, KEY, 2)
     want = np.stack([CS.kswitch_digit(octx, KEY, 77, sk, new, J) for J in range(octx.k - 1)])
     assert (HR.keygen(octx, KEY, 77, sk, new, 1) == want).all()
 
@@ -80,8 +70,8 @@ def test_decryption_error_is_within_the_bound(alpha, data, special, levels):
     logn = 6
     primes = O.coeff_modulus_create(1 << logn, data + special)
     octx = O.Context(logn, primes)
-    s, sk = secret(octx, 1)
-    _, new = secret(octx, 2)
+    s, sk = secret(octx, KEY, 1)
+    _, new = secret(octx, KEY, 2)
     key = HR.keygen(octx, KEY, 5, sk, new, alpha)
     assert key.shape == (HR.beta(len(data), alpha), 2, octx.k, octx.n)
     rng = np.random.default_rng(alpha)
@@ -97,22 +87,12 @@ def test_decryption_error_is_within_the_bound(alpha, data, special, levels):
 
 # ---- (c) the C ABI --------------------------------------------------------------------------------------------------------------
 def test_symbols_exported_and_declared(moai):
-    L = C.CDLL(moai.lib_path())
-    for name in NAMES:
-        assert hasattr(L, name), name
-        assert name in moai.hip.SYMBOLS, name
-    for method in ("hybrid_digits", "hybrid_keygen", "switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid"):
-        assert callable(getattr(moai.Context, method)), method
+    exported(moai, NAMES, ("hybrid_digits", "hybrid_keygen", "switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid"))
 
 
 def test_header_comments_cite_reference_lines():
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
     for name in NAMES:
-        at = hdr.index(" " + name + "(")
-        at = hdr.rindex("\n", 0, at) + 1  # the start of the declaration's line
-        comment = hdr[hdr.rindex("/*", 0, at):at]
-        assert comment.rstrip().endswith("*/"), name  # the comment sits directly on the declaration
-        assert re.search(r"SEAL/(evaluator\.cpp:2724-3020|keygenerator\.cpp:303-336)", comment), name
+        assert re.search(r"SEAL/(evaluator\.cpp:2724-3020|keygenerator\.cpp:303-336)", header_comment(name)), name
 
 
 def test_arguments_refused_without_a_device(moai):

@@ -7,22 +7,17 @@ restatement tests/hybrid_rescale_ref.py, at N = 2^6 with real keys for s^2 from 
 (d) both symbols are exported, declared and bound, their comments cite the reference lines, and the refusals that need no context
     are answered before the device is touched.
 Cases of (a)-(c): alpha in {1, 2, 3} with full and partial last digits, L down to 2, and alpha = 15 with seventeen 30-bit data primes."""
-import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-import client_sampling as CS
 import hybrid_ref as HR
 import hybrid_rescale_ref as RR
 import oracle as O
+from hybrid_kit import EINVAL, KEY, exported, header, header_comment, secret
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL = 0, -1
 NAMES = ("moai_relinearize_rescale_hybrid", "moai_multiply_relin_rescale_hybrid")
-KEY = bytes(range(32))
 LOGN = 6
 
 # (alpha, data bits, special bits, levels): a full last digit, a partial one, q_{L-1} alone in the last digit, and L = 2
@@ -39,8 +34,7 @@ def env(ci):
     if ci not in _env:
         alpha, data, special, _ = CASES[ci]
         octx = O.Context(LOGN, O.coeff_modulus_create(1 << LOGN, data + special))
-        s = CS.ternary(KEY, CS.nonce(CS.TERNARY, 1), octx.n)
-        sk = octx.ntt(CS.to_rns(s, octx.primes), octx.k)
+        s, sk = secret(octx, KEY, 1)
         s2 = np.stack([HR._u64(HR._obj(sk[r]) * HR._obj(sk[r]) % q) for r, q in enumerate(octx.primes)])
         _env[ci] = octx, s, sk, HR.keygen(octx, KEY, 5, sk, s2, alpha)
     return _env[ci]
@@ -120,22 +114,15 @@ def test_product_is_the_oracles_multiply_and_square():
 
 # ---- (d) the C ABI ------------------------------------------------------------------------------------------------------------------
 def test_symbols_exported_and_declared(moai):
-    L = C.CDLL(moai.lib_path())
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
+    exported(moai, NAMES, ("relinearize_rescale_hybrid", "multiply_relin_rescale_hybrid"))
+    hdr = header()
     for name in NAMES:
-        assert hasattr(L, name), name
-        assert name in moai.hip.SYMBOLS, name
         assert re.search(r"^int " + name + r"\(", hdr, re.M), name
-    for method in ("relinearize_rescale_hybrid", "multiply_relin_rescale_hybrid"):
-        assert callable(getattr(moai.Context, method)), method
 
 
 def test_header_comments_cite_reference_lines():
-    hdr = open(os.path.join(ROOT, "include", "moai_hip.h")).read()
     for name in NAMES:
-        at = hdr.index("int " + name + "(")
-        comment = hdr[hdr.rindex("/*", 0, at):at]
-        assert comment.rstrip().endswith("*/"), name  # the comment sits directly on the declaration
+        comment = header_comment(name)
         assert "SEAL/evaluator.cpp:2724-3020" in comment, name  # switch_key_inplace
         for cite in ("SEAL/evaluator.cpp:1682-1720", ":1402-1481", "SEAL/util/rns.cpp:830-901"):  # what moai_rescale's comment cites
             assert cite in comment, (name, cite)
