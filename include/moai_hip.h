@@ -1017,7 +1017,63 @@ int moai_relinearize_hybrid_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uin
 int moai_relinearize_rescale_hybrid_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uint64_t *const *outs /* [2][L-1][N] */,
                                          const uint64_t *key, size_t L, size_t alpha, size_t n, void *stream);
 
-/* ---- stream audit (debug) ----------------------------------------------------------------------------------------
+/* ---- hybrid rounding mode: the mod-down's overflow corrected in FP64 ----------------------------------------------------------------------
+ * Step 5 of every hybrid entry point, and the merged mod-down of the relinearize + rescale forms, is a FAST base conversion: it returns
+ * the rounded quotient less an overflow u in [0, n), n the number of source primes, which is where the (alpha - 1/2) and (alpha + 1/2)
+ * of the noise bounds above come from.  MOAI_HYBRID_ROUND_EXACT estimates that overflow in binary64 and takes it out.  The mode is an
+ * attribute of the context (an atomic; FAST when the context is created).  Every hybrid entry point reads it ONCE on entry, so a call
+ * with several mod-downs (moai_hybrid_bsgs_dot), its batch chunks and the separate calls of a fallback all round alike.  It is not a
+ * tuning knob: results depend on it, so it is not in MOAI_KNOBS and moai_reset_tuning leaves it alone.  With the default every entry
+ * point launches the kernels and gives the bits it gave before the mode existed.  The mod-ups (step 2) keep the fast form in both modes:
+ * their overflow is the approximation term of the key noise and part of the hoisted identity.
+ *
+ * The contract.  A mod-down from sources S (n = |S| primes m, in the order of the accumulator's rows: p_0 .. p_{alpha-1} for step 5,
+ * q_{L-1}, p_0 .. p_{alpha-1} for the merged form; W their product, H = floor(W / 2)) to the targets q_i is, in the fast mode,
+ *   y_m    = ((x_m + H mod m) mod m) [(W / m)^-1]_m  mod m
+ *   conv_i = (sum_m y_m ((W / m) mod q_i)  -  (H mod q_i)) mod q_i
+ * As integers sum_m y_m (W / m) = X' + v* W with X' = (x + H) mod W in [0, W) and v* = floor(sum_m y_m / m) in [0, n).  The exact mode:
+ *   r_m    = 1.0 / (double)m                 IEEE binary64, computed on the host (two roundings, reproducible in numpy)
+ *   f      = 0.0;  for m in S, in the source order:  f = f (+) ( (double)y_m (x) r_m )
+ *                                            (double)y_m round-to-nearest-even; (x) and (+) are single rounded operations, NOT fused
+ *   v      = min(max(floor(f), 0), n - 1)
+ *   conv_i = (sum_m y_m ((W / m) mod q_i)  -  v (W mod q_i)  -  (H mod q_i)) mod q_i
+ * Everything after the conversion (the forward transform and the last kernel) is the fast mode's.  The clamp is part of the contract:
+ * with n = 1 and y = m - 1 the product rounds to 1.0.  AT alpha = 1 BOTH MODES GIVE THE SAME BITS for step 5 (one source: v* = 0 = v),
+ * i.e. SEAL's; the merged form has two sources there and the modes differ.
+ *
+ * The property.  |f - sum_m y_m / m| <= eps with eps = 2^-40 promised here (csrc/hybrid_kernels.hip.h derives about 323 2^-53 for n <= 17
+ * and m < 2^61).  When floor(f) != v*, X' / W is within eps of 0 or of 1 and the neighbouring integer is still within 1/2 + eps of the
+ * real quotient.  So for EVERY coefficient and EVERY input, deterministically, with Z_p the lifted accumulator as an integer mod Q W (Q P
+ * for step 5) and out_p the integer the mod-down returns:
+ *   | out_p - Z_p / W |  <=  1/2 + 2^-40,
+ * and out_p = floor((Z_p + H) / W) exactly whenever X' / W is outside [0, 2^-40) and (1 - 2^-40, 1).  The results are bit for bit the
+ * integer-plus-numpy-float64 restatement tests/hybrid_exact_ref.py.
+ *
+ * The noise bounds in exact mode: every mod-down's (alpha - 1/2) or (alpha + 1/2) becomes (1/2 + 2^-40).
+ *   hybrid key switching (switch, relinearize, rotations, their list and hoisted forms):
+ *     |E| <= beta(L) N alpha 21 D_max / P + (1/2 + 2^-40)(1 + |s|_1)            -- the second term is SEAL's
+ *   moai_hybrid_rotate_pt_dot:
+ *     |E| <= (sum_{r : e_r != 1} |p_{g,r}|_1) beta(L) N alpha 21 D_max / P + (1/2 + 2^-40)(1 + |s|_1)
+ *   moai_hybrid_bsgs_dot (|rho_g| <= (1/2 + 2^-40) P):
+ *     |E| <= (1/2 + 2^-40)(1 + |s|_1) + sum_g [ l_g u + [E_g != 1] (u + (1/2 + 2^-40) |s|_1) ]
+ *   moai_relinearize_rescale_hybrid, moai_multiply_relin_rescale_hybrid and the list form: the centred value of
+ *     q_{L-1} (out_0 + out_1 s) - (c_0 + c_1 s + c_2 s^2) mod Q_L is at most beta(L) N alpha 21 D_max / P + q_{L-1} (1/2 + 2^-40)(1 + |s|_1);
+ *     u'_p = 0 outside the 2^-40 band, and each coefficient of (out - composition) mod Q_{L-1}, centred, lies in [-1, +1] instead of
+ *     [-(alpha + 1), +1].  It is still NOT the composition's bits: the merged form rounds once, the composition twice.
+ * In every bound the first term, the key noise with the mod-up's approximation, is unchanged.
+ *
+ * Neither call below launches or synchronises anything.  The exact mode adds no synchronisation and no launch to any call (the same
+ * conversion launch runs another instantiation of its kernel), uses the same scratch, works under HIP-graph stream capture wherever
+ * the fast mode does, and its constants are part of the per-(L, alpha) blocks whatever the mode, so setting it builds nothing.
+ * moai_op_trace counts are unchanged: a mode is not an operation.  A set while another thread is inside a hybrid call of the same
+ * context takes effect for the calls entered after it.
+ * Refusals: MOAI_EINVAL with a message for a null context, a null `mode` pointer, a mode that is neither of the two below. */
+#define MOAI_HYBRID_ROUND_FAST 0  /* the default: the fast conversion, the bits of every release before the mode existed */
+#define MOAI_HYBRID_ROUND_EXACT 1 /* the overflow of every mod-down estimated in binary64 and removed */
+int moai_hybrid_set_rounding(moai_ctx *ctx, int mode);
+int moai_hybrid_rounding(const moai_ctx *ctx, int *mode);
+
+/* ---- stream audit (debug)----------------------------------------------------------------------------------------
  * A caller that recycles device blocks in a stream-ordered cache (the seal:: shim's util::DevicePool: a released block may be
  * handed out again on the SAME stream without synchronising, which is only safe when everything that touches the block is
  * enqueued on that stream) can have that invariant checked.  With MOAI_STREAM_AUDIT=1 in the environment, or after

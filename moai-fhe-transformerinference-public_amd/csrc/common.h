@@ -197,6 +197,8 @@ struct moai_ctx
     std::map<const void *, KeyLayout> key_layouts;
     // constants of the hybrid key switch (hybrid.hip HyTable), one device block per (L, alpha), built on first use under op_mutex
     std::map<std::pair<size_t, size_t>, void *> hybrid_tables;
+    // how the hybrid mod-downs round (moai_hybrid_set_rounding): MOAI_HYBRID_ROUND_*; an entry point reads it once, on entry
+    std::atomic<int> hybrid_rounding{ 0 };
     void *mutex = nullptr;
     // serialises the enqueue of multi-kernel operations that share a stream's workspace arena: callers
     // on different host threads may target the same stream (MOAI's OpenMP loops do)

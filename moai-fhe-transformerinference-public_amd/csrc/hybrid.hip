@@ -30,6 +30,10 @@
 // single ciphertexts, each in its own block, into that same scratch (galois_gather_list) and run the chain above on it; the kernels
 // that read a member's key or touch a caller's block (hy_mac_kernel, moddown_finalize, hy_lift_last_row_kernel,
 // hy_rescale_finalize_kernel) have a LIST instantiation that takes those pointers from the pass's KsList record.
+// Rounding mode (moai_hybrid_set_rounding, an atomic of the context): every mod-down above is hy_mod_down -> hy_convert; in
+// MOAI_HYBRID_ROUND_EXACT that one launch takes hy_convert_kernel<.., true>, which removes the fast conversion's overflow with a
+// binary64 estimate (the header states the contract, the kernel derives the error bound).  An entry point reads the mode once
+// (hy_exact) and hands it down as `exact`; the mod-ups, the constants' cache and every other launch do not depend on it.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 //
@@ -66,6 +70,13 @@ static HyDims hy_dims(const moai_ctx *c, size_t L, size_t alpha)
 static size_t hy_budget()
 {
     return (size_t)std::max(1l, tuning(K_HYBRID_TMP_KB)) << 10;
+}
+
+// the context's rounding mode (moai_hybrid_set_rounding), read ONCE by every entry point before anything else: all the mod-downs of
+// a call, and the separate calls of a fallback, round alike whatever another thread sets meanwhile
+static bool hy_exact(const moai_ctx *c)
+{
+    return c && c->hybrid_rounding.load(std::memory_order_relaxed) == MOAI_HYBRID_ROUND_EXACT;
 }
 
 static uint64_t *hy_at(void *wsp, const HyPlan &p, HyRegion r)
@@ -110,7 +121,7 @@ static uint64_t hy_half_mod(uint64_t p_mod_m, uint64_t m)
 }
 
 // cv = the mod-down by W, the product of the context primes src[0 .. nsrc), to the data primes 0 .. ntgt-1, with the rounding terms
-// of floor(W / 2) (HyConv states the formulas)
+// of floor(W / 2) and the constants of the exact mode (HyConv states the formulas)
 static void hy_moddown_conv(const moai_ctx *c, HyConv &cv, const uint32_t *src, size_t nsrc, size_t ntgt)
 {
     cv.nsrc = (uint32_t)nsrc;
@@ -121,12 +132,14 @@ static void hy_moddown_conv(const moai_ctx *c, HyConv &cv, const uint32_t *src, 
         cv.src_prime[r] = src[r];
         cv.src_inv[r] = make_tw(hy_invmod(hy_prod_mod(c, src, nsrc, r, m), m), m);
         cv.src_pre[r] = hy_half_mod(0, m);
+        cv.src_rinv[r] = 1.0 / (double)m; // two roundings: the conversion, then the division
     }
     for (size_t i = 0; i < ntgt; ++i)
     {
-        const uint64_t q = c->primes[i];
+        const uint64_t q = c->primes[i], w_mod_q = hy_prod_mod(c, src, nsrc, nsrc, q);
         cv.tgt_prime[i] = (uint32_t)i;
-        cv.tgt_post[i] = hy_half_mod(hy_prod_mod(c, src, nsrc, nsrc, q), q);
+        cv.tgt_post[i] = hy_half_mod(w_mod_q, q);
+        cv.tgt_negw[i] = q - w_mod_q; // W and q are coprime: in (0, q)
         for (size_t r = 0; r < nsrc; ++r)
         {
             cv.w[i][r] = hy_prod_mod(c, src, nsrc, r, q);
@@ -219,8 +232,9 @@ static int hy_table(moai_ctx *c, size_t L, size_t alpha, const HyTable **out)
     });
 }
 
+// exact: the mod-down of MOAI_HYBRID_ROUND_EXACT, a separate instantiation; the mod-ups are always fast
 static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_t src_off, uint64_t *dst, const HyConv *cv, size_t nsrc,
-                      size_t polys, hipStream_t s)
+                      size_t polys, hipStream_t s, bool exact = false)
 {
     HyConvArgs a;
     a.src = src;
@@ -232,6 +246,11 @@ static int hy_convert(moai_ctx *c, const uint64_t *src, size_t src_stride, size_
     a.n2 = (uint32_t)(c->n >> 1);
     // the smallest instantiation that holds the digit: its registers are the unrolled source rows
     const int amax = nsrc <= 1 ? 1 : nsrc <= 2 ? 2 : nsrc <= 4 ? 4 : nsrc <= 8 ? 8 : 16;
+    if (exact)
+    {
+        return dispatch<1, 2, 4, 8, 16>("digit size ", amax,
+                                        [&](auto A) { return launch_rows(hy_convert_kernel<decltype(A)::value, true>, c, polys, s, a); });
+    }
     return dispatch<1, 2, 4, 8, 16>("digit size ", amax,
                                     [&](auto A) { return launch_rows(hy_convert_kernel<decltype(A)::value>, c, polys, s, a); });
 }
@@ -261,14 +280,14 @@ static int hy_decompose(moai_ctx *c, const HyTable *tab, const KsTarget &tg, siz
 
 // A mod-down up to its last kernel, for `polys` polynomials whose nsrc source rows -- the last nsrc of a switch's L + alpha -- are
 // rows off .. off + nsrc - 1 of every `stride` rows at src: x [polys][nsrc][N] = INTT(those rows), conv [polys][ntgt][N] = NTT(cv's
-// base conversion with the rounding terms), ntgt = L + alpha - nsrc
+// base conversion with the rounding terms, fast or exact as the call's rounding mode says), ntgt = L + alpha - nsrc
 static int hy_mod_down(moai_ctx *c, const HyConv *cv, const uint64_t *src, size_t stride, size_t off, size_t nsrc, size_t ntgt, size_t polys,
-                       uint64_t *x, uint64_t *conv, size_t L, size_t alpha, hipStream_t s)
+                       uint64_t *x, uint64_t *conv, size_t L, size_t alpha, bool exact, hipStream_t s)
 {
     RowMap rm{};
     hy_rowmap(c, L, alpha, 0, ntgt, &rm);
     MOAI_TRY(ntt_launch(c, x, polys, nsrc, rm, true, s, src, stride, off));
-    MOAI_TRY(hy_convert(c, x, nsrc, 0, conv, cv, nsrc, polys, s));
+    MOAI_TRY(hy_convert(c, x, nsrc, 0, conv, cv, nsrc, polys, s, exact));
     MOAI_TRY(make_rowmap(c, ntgt, nullptr, &rm));
     return ntt_launch(c, conv, polys, ntgt, rm, false, s);
 }
@@ -276,9 +295,9 @@ static int hy_mod_down(moai_ctx *c, const HyConv *cv, const uint64_t *src, size_
 // step 5 up to the last kernel, for the accumulators [B][2][L + alpha][N] of B switches: x [2B][alpha][N] = INTT(special rows),
 // conv [2B][L][N]
 static int hy_step5(moai_ctx *c, const HyTable *tab, const uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
-                    hipStream_t s)
+                    bool exact, hipStream_t s)
 {
-    return hy_mod_down(c, tab->conv + hy_beta(L, alpha), acc, L + alpha, L, alpha, L, 2 * B, x, conv, L, alpha, s);
+    return hy_mod_down(c, tab->conv + hy_beta(L, alpha), acc, L + alpha, L, alpha, L, 2 * B, x, conv, L, alpha, exact, s);
 }
 
 // the hy_mac_kernel / hy_hoisted_mac_kernel grid: blockIdx.x = ciphertext, .y covers a row, .z = row of L + alpha
@@ -322,7 +341,7 @@ static size_t hy_pass_size(size_t left)
 // common.h KsList) ciphertext b's key is lst->keys[b] and the last kernel writes lst->outs[b], adds lst->sums[b] and, for add.mode 1,
 // reads the addend from lst->ins[b]; key and out are not used
 static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
-                           size_t B, void *wsp, const HyPlan &w, const KsAddend &add, hipStream_t s)
+                           size_t B, void *wsp, const HyPlan &w, const KsAddend &add, bool exact, hipStream_t s)
 {
     uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
     // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
@@ -330,7 +349,7 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
     // 4. the inner products with the key
     MOAI_TRY(hy_mac(c, tg, ext, key, acc, L, alpha, B, s));
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
-    MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, w, HY_X), conv, L, alpha, B, s));
+    MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, w, HY_X), conv, L, alpha, B, exact, s));
     return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, tg.lst, s);
 }
 
@@ -376,8 +395,9 @@ enum
 //   HY_RELIN   in = ct3 [batch][3][L][N], io = out [batch][2][L][N]
 //   HY_GALOIS  in [batch][2][L][N], io = out [batch][2][L][N], which may be in itself; sum: null, or [batch][2][L][N] added by the last
 //              kernel (it may be io, never in)
+// exact: the rounding mode the entry point read (hy_exact)
 static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, const uint64_t *key, size_t L, size_t alpha, uint32_t elt,
-                    size_t batch, void *stream, const uint64_t *sum = nullptr)
+                    size_t batch, bool exact, void *stream, const uint64_t *sum = nullptr)
 {
     // every kind but HY_GALOIS comes with element 1; an even element is refused before the context is looked at
     MOAI_TRY(galois_elt_check(nullptr, elt));
@@ -424,11 +444,11 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
         case HY_SWITCH:
             // ct += switch(target)
             return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { in + b0 * L * n, L, 0 }, key, L, alpha, B, wsp, w,
-                                   { io + b0 * 2 * L * n, 2 * L, 1 }, s);
+                                   { io + b0 * 2 * L * n, 2 * L, 1 }, exact, s);
         case HY_RELIN:
             // out = (c0, c1) + switch(c2)      (evaluator.cpp:1383-1392)
             return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { in + b0 * 3 * L * n, 3 * L, 2 * L }, key, L, alpha, B, wsp, w,
-                                   { in + b0 * 3 * L * n, 3 * L, 1 }, s);
+                                   { in + b0 * 3 * L * n, 3 * L, 1 }, exact, s);
         default:
         {
             // out = (galois(in0), 0) + switch(galois(in1)) [+ sum]      (evaluator.cpp:2631-2654): both summands are added by the last
@@ -436,7 +456,7 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
             uint64_t *tmp = hy_at(wsp, w, HY_HEAD);
             MOAI_TRY(moai_galois_permute(c, in + b0 * 2 * L * n, tmp, B * 2, L, elt, stream));
             return hy_switch_chunk(c, tab, io + b0 * 2 * L * n, { tmp, 2 * L, L }, key, L, alpha, B, wsp, w,
-                                   { tmp, 2 * L, 2, sum ? sum + b0 * 2 * L * n : nullptr }, s);
+                                   { tmp, 2 * L, 2, sum ? sum + b0 * 2 * L * n : nullptr }, exact, s);
         }
         }
     });
@@ -533,7 +553,7 @@ static int hy_hoisted_mac(moai_ctx *c, const uint64_t *ext, const uint64_t *in, 
 // one chunk of B ciphertexts at `in` [B][2][L][N] on plan p; rotation r's result goes to rot.outs[r] + out_off.  *fallback is set
 // when INTT(c1) holds a zero coefficient: nothing but the scratch has been written then, and the caller makes the separate calls.
 static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyHoistRotations &rot, size_t L, size_t alpha, size_t B,
-                              const HyPlan &p, bool *fallback, hipStream_t s)
+                              const HyPlan &p, bool *fallback, bool exact, hipStream_t s)
 {
     const size_t n = c->n;
     return hy_hoisted_chunk(c, p, in, L, alpha, B, true, fallback, s, [&](const HyTable *tab, void *wsp) -> int {
@@ -550,7 +570,7 @@ static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, c
                 MOAI_TRY(galois_permute_c0(c, in, pc0 + r * B * L * n, B, L, rot.elts[r0 + r], s));
             }
             // steps 5 over (rotation, ciphertext) pairs
-            MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, p, HY_X), conv, L, alpha, g * B, s));
+            MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, p, HY_X), conv, L, alpha, g * B, exact, s));
             for (size_t r = 0; r < g; ++r)
             {
                 MOAI_TRY(moddown_finalize(c, acc + r * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + r * B * 2 * L * n,
@@ -696,7 +716,8 @@ static int hy_dot_inner(moai_ctx *c, const HyTable *tab, const uint64_t *in, con
 // holds a zero coefficient: the chunk then takes every rotation through the unhoisted steps 1-4 on the permuted input, to the same
 // bits.
 static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, const HyDotTerms &tm, const std::vector<size_t> &sw,
-                            const std::vector<size_t> &idn, size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, hipStream_t s)
+                            const std::vector<size_t> &idn, size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, bool exact,
+                            hipStream_t s)
 {
     const size_t n = c->n, ct_words = B * 2 * L * n;
     // steps 1-3 and the probe only where an output has a switched term
@@ -711,7 +732,7 @@ static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, con
             o.ng = (uint32_t)ng;
             MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs, ng, o, sc, L, alpha, B, *fallback, s));
             // step 5 once per output, over (output, ciphertext) pairs
-            MOAI_TRY(hy_step5(c, tab, S, hy_at(wsp, p, HY_X), conv, L, alpha, ng * B, s));
+            MOAI_TRY(hy_step5(c, tab, S, hy_at(wsp, p, HY_X), conv, L, alpha, ng * B, exact, s));
             for (size_t h = 0; h < ng; ++h)
             {
                 MOAI_TRY(moddown_finalize(c, S + h * B * 2 * (L + alpha) * n, (uint32_t)(L + alpha), conv + h * ct_words,
@@ -751,7 +772,7 @@ struct HyBsgsGiants
 // one chunk of B ciphertexts at `in` [B][2][L][N] into out [B][2][L][N] on plan p; tm holds the baby terms with one output per giant
 // step (tm.outs unused), p.G giant steps in flight.  *fallback as in hy_dot_chunk_run: the inner stage's zero probe.
 static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, const HyDotTerms &tm, const HyBsgsGiants &gi, bool any_switched,
-                             size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, hipStream_t s)
+                             size_t L, size_t alpha, size_t B, const HyPlan &p, bool *fallback, bool exact, hipStream_t s)
 {
     const size_t n = c->n, s_words = B * 2 * (L + alpha) * n;
     return hy_hoisted_chunk(c, p, in, L, alpha, B, any_switched, fallback, s, [&](const HyTable *tab, void *wsp) -> int {
@@ -808,7 +829,7 @@ static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, con
                 {
                     // step 5 of S_g[1] alone: the special rows of polynomial 1 of every (giant step, ciphertext) pair
                     MOAI_TRY(hy_mod_down(c, tab->conv + hy_beta(L, alpha), S, 2 * (L + alpha), (L + alpha) + L, alpha, L, n_md * B, x, conv,
-                                         L, alpha, s));
+                                         L, alpha, exact, s));
                 }
                 // tgt = perm_{E_g}(c1'_g), then steps 1-3 on all (giant step, ciphertext) pairs at once
                 HyC1Args a{};
@@ -836,7 +857,7 @@ static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, con
             return MOAI_OK;
         }));
         // the one final step 5, both polynomials, no addend
-        MOAI_TRY(hy_step5(c, tab, Z, hy_at(wsp, p, HY_ZX), zconv, L, alpha, B, s));
+        MOAI_TRY(hy_step5(c, tab, Z, hy_at(wsp, p, HY_ZX), zconv, L, alpha, B, exact, s));
         return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
     });
 }
@@ -868,7 +889,7 @@ static int hy_rescale_table(moai_ctx *c, size_t L, size_t alpha, const HyRescale
 // device record, common.h KsList) c2 [B][L][N] has been gathered to the plan's head, c0 and c1 are read from lst->ins[b], the key is
 // lst->keys[b] and the result goes to lst->outs[b]; ct3, key and out are not used
 static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescaleTable *rt, const uint64_t *ct3, const uint64_t *key,
-                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyPlan &w, hipStream_t s,
+                                uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyPlan &w, bool exact, hipStream_t s,
                                 const KsList *lst = nullptr)
 {
     uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
@@ -886,7 +907,7 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
         return launch_rows(hy_lift_last_row_kernel<decltype(LIST)::value>, c, 2 * B, s, args);
     }));
     // the merged mod-down: x = INTT(rows L-1 .. L+alpha-1 of acc, contiguous), conv = NTT(base conversion with W's rounding terms)
-    MOAI_TRY(hy_mod_down(c, &rt->conv, acc, L + alpha, L - 1, alpha + 1, L - 1, 2 * B, hy_at(wsp, w, HY_X), conv, L, alpha, s));
+    MOAI_TRY(hy_mod_down(c, &rt->conv, acc, L + alpha, L - 1, alpha + 1, L - 1, 2 * B, hy_at(wsp, w, HY_X), conv, L, alpha, exact, s));
     HyRescaleFinalArgs f;
     f.acc = acc;
     f.conv = conv;
@@ -920,6 +941,7 @@ static int hy_rescale_check(const moai_ctx *c, size_t alpha, size_t L)
 static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, bool product, const uint64_t *key, uint64_t *out, size_t L,
                             size_t alpha, size_t batch, void *stream)
 {
+    const bool exact = hy_exact(c);
     MOAI_TRY(hy_rescale_check(c, alpha, L));
     if (batch == 0)
     {
@@ -959,7 +981,7 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
             MOAI_TRY(launch_rows(hy_ct_product_kernel, c, B * L, s, g));
             ct3 = g.out;
         }
-        return hy_rescale_chunk_run(c, tab, rt, ct3, key, out + b0 * 2 * (L - 1) * n, L, alpha, B, wsp, w, s);
+        return hy_rescale_chunk_run(c, tab, rt, ct3, key, out + b0 * 2 * (L - 1) * n, L, alpha, B, wsp, w, exact, s);
     });
 }
 
@@ -984,7 +1006,7 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
                         const uint32_t *elts, const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n,
                         void *stream)
 {
-    const bool relin = kind != HY_LIST_GALOIS, rescale = kind == HY_LIST_RESCALE;
+    const bool relin = kind != HY_LIST_GALOIS, rescale = kind == HY_LIST_RESCALE, exact = hy_exact(c);
     if (n == 0)
     {
         return MOAI_OK;
@@ -1036,14 +1058,14 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
         case HY_LIST_GALOIS:
             // tmp [cnt][2][L][N] = galois(ins); out = (galois(in0), 0) + switch(galois(in1)) [+ sum]   (evaluator.cpp:2631-2654)
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, 2 * L, 0, s));
-            return hy_switch_chunk(c, tab, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, alpha, cnt, chunk, w, { tmp, 2 * L, 2 }, s);
+            return hy_switch_chunk(c, tab, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, alpha, cnt, chunk, w, { tmp, 2 * L, 2 }, exact, s);
         case HY_LIST_RELIN:
             // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch(c2)   (evaluator.cpp:1383-1392)
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
-            return hy_switch_chunk(c, tab, nullptr, { tmp, L, 0, dlist }, nullptr, L, alpha, cnt, chunk, w, { nullptr, 0, 1 }, s);
+            return hy_switch_chunk(c, tab, nullptr, { tmp, L, 0, dlist }, nullptr, L, alpha, cnt, chunk, w, { nullptr, 0, 1 }, exact, s);
         default:
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
-            return hy_rescale_chunk_run(c, tab, rt, nullptr, nullptr, nullptr, L, alpha, cnt, chunk, w, s, dlist);
+            return hy_rescale_chunk_run(c, tab, rt, nullptr, nullptr, nullptr, L, alpha, cnt, chunk, w, exact, s, dlist);
         }
     });
 }
@@ -1178,7 +1200,7 @@ extern "C" int moai_switch_key_hybrid(moai_ctx *c, uint64_t *ct, const uint64_t 
 {
     MOAI_AUDIT(stream, ct, target, key);
     trace_op("switch_key_hybrid", L, batch);
-    return hy_entry(c, HY_SWITCH, ct, target, key, L, alpha, 1, batch, stream);
+    return hy_entry(c, HY_SWITCH, ct, target, key, L, alpha, 1, batch, hy_exact(c), stream);
 }
 
 extern "C" int moai_relinearize_hybrid(moai_ctx *c, const uint64_t *ct3, const uint64_t *key, uint64_t *out, size_t L, size_t alpha,
@@ -1186,7 +1208,7 @@ extern "C" int moai_relinearize_hybrid(moai_ctx *c, const uint64_t *ct3, const u
 {
     MOAI_AUDIT(stream, ct3, key, out);
     trace_op("relinearize_hybrid", L, batch);
-    return hy_entry(c, HY_RELIN, out, ct3, key, L, alpha, 1, batch, stream);
+    return hy_entry(c, HY_RELIN, out, ct3, key, L, alpha, 1, batch, hy_exact(c), stream);
 }
 
 extern "C" int moai_apply_galois_hybrid(moai_ctx *c, uint64_t *ct, size_t L, size_t alpha, uint32_t galois_elt, const uint64_t *key,
@@ -1194,7 +1216,7 @@ extern "C" int moai_apply_galois_hybrid(moai_ctx *c, uint64_t *ct, size_t L, siz
 {
     MOAI_AUDIT(stream, ct, key);
     trace_op("apply_galois_hybrid", L, batch);
-    return hy_entry(c, HY_GALOIS, ct, ct, key, L, alpha, galois_elt, batch, stream);
+    return hy_entry(c, HY_GALOIS, ct, ct, key, L, alpha, galois_elt, batch, hy_exact(c), stream);
 }
 
 extern "C" int moai_apply_galois_hybrid_to(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L, size_t alpha, uint32_t galois_elt,
@@ -1202,7 +1224,7 @@ extern "C" int moai_apply_galois_hybrid_to(moai_ctx *c, const uint64_t *in, uint
 {
     MOAI_AUDIT(stream, in, out, key);
     trace_op("apply_galois_hybrid", L, batch);
-    return hy_entry(c, HY_GALOIS, out, in, key, L, alpha, galois_elt, batch, stream);
+    return hy_entry(c, HY_GALOIS, out, in, key, L, alpha, galois_elt, batch, hy_exact(c), stream);
 }
 
 extern "C" int moai_apply_galois_hybrid_acc(moai_ctx *c, const uint64_t *in, uint64_t *acc, size_t L, size_t alpha, uint32_t galois_elt,
@@ -1210,7 +1232,7 @@ extern "C" int moai_apply_galois_hybrid_acc(moai_ctx *c, const uint64_t *in, uin
 {
     MOAI_AUDIT(stream, in, acc, key);
     trace_op("apply_galois_hybrid", L, batch); // the same switch; the addition that follows it is what is saved
-    return hy_entry(c, HY_GALOIS, acc, in, key, L, alpha, galois_elt, batch, stream, acc);
+    return hy_entry(c, HY_GALOIS, acc, in, key, L, alpha, galois_elt, batch, hy_exact(c), stream, acc);
 }
 
 extern "C" int moai_apply_galois_hybrid_ptrs(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, size_t alpha,
@@ -1268,6 +1290,7 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
         *used_fallback = 0;
     }
     MOAI_TRY(hy_check(c, alpha, L, true));
+    const bool exact = hy_exact(c);
     if (batch == 0 || R == 0)
     {
         return MOAI_OK;
@@ -1294,13 +1317,13 @@ extern "C" int moai_apply_galois_hybrid_hoisted(moai_ctx *c, const uint64_t *in,
     const HyPlan p = hy_plan_hoisted(n, L, alpha, batch, R, hy_budget());
     return hy_batch_chunks(
         batch, p.cb, 2 * L * n, used_fallback,
-        [&](size_t off, size_t B, bool *fallback) { return hy_hoist_chunk_run(c, in + off, off, rot, L, alpha, B, p, fallback, s); },
+        [&](size_t off, size_t B, bool *fallback) { return hy_hoist_chunk_run(c, in + off, off, rot, L, alpha, B, p, fallback, exact, s); },
         [&](size_t off, size_t B) {
             // the separate rotations of this chunk, each on a copy of the input (they take the lock and the workspace themselves)
             for (size_t r = 0; r < R; ++r)
             {
                 MOAI_HIP_CHECK(hipMemcpyAsync(outs[r] + off, in + off, B * 2 * L * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-                MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, outs[r] + off, keys[r], L, alpha, galois_elts[r], B, stream));
+                MOAI_TRY(hy_entry(c, HY_GALOIS, outs[r] + off, outs[r] + off, keys[r], L, alpha, galois_elts[r], B, exact, stream));
             }
             return MOAI_OK;
         });
@@ -1322,6 +1345,7 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
     }
     MOAI_TRY(hy_odd_check(galois_elts, R));
     MOAI_TRY(hy_check(c, alpha, L, true));
+    const bool exact = hy_exact(c);
     if (batch == 0 || n_out == 0)
     {
         return MOAI_OK;
@@ -1362,7 +1386,7 @@ extern "C" int moai_hybrid_rotate_pt_dot(moai_ctx *c, const uint64_t *in, uint64
     const HyDotTerms tm = { R, n_out, galois_elts, tables.data(), keys, corrections, plains, outs };
     const HyPlan p = hy_plan_dot(n, L, alpha, batch, std::max<size_t>(sw.size(), 1), HY_DOT_MAX_NG, hy_budget());
     return hy_batch_chunks(batch, p.cb, 2 * L * n, used_fallback, [&](size_t off, size_t B, bool *fallback) {
-        return hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, p, fallback, s);
+        return hy_dot_chunk_run(c, in + off, off, tm, sw, idn, L, alpha, B, p, fallback, exact, s);
     });
 }
 
@@ -1380,6 +1404,7 @@ extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *o
     MOAI_TRY(hy_odd_check(baby_elts, R));
     MOAI_TRY(hy_odd_check(giant_elts, n_giant));
     MOAI_TRY(hy_check(c, alpha, L, true));
+    const bool exact = hy_exact(c);
     if (batch == 0)
     {
         return MOAI_OK;
@@ -1432,7 +1457,7 @@ extern "C" int moai_hybrid_bsgs_dot(moai_ctx *c, const uint64_t *in, uint64_t *o
     const HyBsgsGiants gi = { n_giant, giant_elts, giant_tables.data(), giant_keys, &switched };
     const HyPlan p = hy_plan_bsgs(n, L, alpha, batch, n_giant, HY_DOT_MAX_NG, hy_budget());
     return hy_batch_chunks(batch, p.cb, 2 * L * n, used_fallback, [&](size_t off, size_t B, bool *fallback) {
-        return hy_bsgs_chunk_run(c, in + off, out + off, tm, gi, any_switched, L, alpha, B, p, fallback, s);
+        return hy_bsgs_chunk_run(c, in + off, out + off, tm, gi, any_switched, L, alpha, B, p, fallback, exact, s);
     });
 }
 
@@ -1462,4 +1487,32 @@ extern "C" int moai_multiply_relin_rescale_hybrid(moai_ctx *c, const uint64_t *x
     MOAI_AUDIT(stream, x, y, key, out);
     trace_op("multiply_relin_rescale_hybrid", L, batch);
     return hy_rescale_entry(c, x, y, true, key, out, L, alpha, batch, stream);
+}
+
+extern "C" int moai_hybrid_set_rounding(moai_ctx *c, int mode)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (mode != MOAI_HYBRID_ROUND_FAST && mode != MOAI_HYBRID_ROUND_EXACT)
+    {
+        return set_error(MOAI_EINVAL, "rounding mode %d: MOAI_HYBRID_ROUND_FAST (0) or MOAI_HYBRID_ROUND_EXACT (1)", mode);
+    }
+    c->hybrid_rounding.store(mode, std::memory_order_relaxed);
+    return MOAI_OK;
+}
+
+extern "C" int moai_hybrid_rounding(const moai_ctx *c, int *mode)
+{
+    if (!c)
+    {
+        return set_error(MOAI_EINVAL, "null context");
+    }
+    if (!mode)
+    {
+        return set_error(MOAI_EINVAL, "null mode pointer");
+    }
+    *mode = c->hybrid_rounding.load(std::memory_order_relaxed);
+    return MOAI_OK;
 }

@@ -15,6 +15,9 @@ constexpr uint32_t HY_MAX_ALPHA = 16;
 //   y_r = ((x_r + src_pre[r]) mod s_r) * src_inv[r] mod s_r,   out_t = ((sum_r y_r w[t][r]) - tgt_post[t]) mod m_t
 // mod-up of digit j: src_pre = tgt_post = 0, src_inv = (D_j / q_r)^-1, w = (D_j / q_r) mod m_t
 // mod-down:          src_pre = floor(P / 2) mod p_t, tgt_post = floor(P / 2) mod q_i, src_inv = (P / p_t)^-1, w = (P / p_t) mod q_i
+// The exact mod-down (MOAI_HYBRID_ROUND_EXACT) also takes the overflow v of the sum out, out_t = ((sum_r y_r w[t][r]) + v tgt_negw[t]
+// - tgt_post[t]) mod m_t: src_rinv[r] = RN(1.0 / (double)s_r), tgt_negw[t] = m_t - (P mod m_t).  Both are filled for every mod-down
+// whatever the mode (zero in the mod-ups), so a cached block does not depend on it.
 struct alignas(16) HyConv
 {
     uint32_t nsrc, ntgt, pad[2];
@@ -24,6 +27,8 @@ struct alignas(16) HyConv
     uint64_t src_pre[HY_MAX_ALPHA];
     uint64_t tgt_post[MOAI_MAX_RNS];
     uint64_t w[MOAI_MAX_RNS][HY_MAX_ALPHA];
+    double src_rinv[HY_MAX_ALPHA];
+    uint64_t tgt_negw[MOAI_MAX_RNS];
 };
 
 // the constants of a switch at (L, alpha): conv[j], j < beta, are the mod-ups and conv[beta] is the mod-down; behind them lie the
@@ -60,9 +65,29 @@ struct HyConvArgs
 // blockIdx.y = polynomial.  A thread reads the nsrc <= AMAX source residues of its two coefficients once, scales them, and walks
 // the target rows: per target nsrc 128-bit multiply-adds (at most 16 products below 2^122) and one reduction.  The constants are
 // indexed by uniform values: scalar loads.
-template <int AMAX>
-__global__ __launch_bounds__(256) void hy_convert_kernel(HyConvArgs g)
+//
+// EXACT (a mod-down in MOAI_HYBRID_ROUND_EXACT; the fast instantiation's code is what it was).  As integers sum_r y_r (W / s_r) =
+// X' + v* W with X' in [0, W) and v* = floor(sum_r y_r / s_r) in [0, nsrc).  The kernel estimates that sum in binary64 as the header
+// states it -- f = 0; f = f (+) ((double)y_r (x) src_rinv[r]) in source order, every step one rounded operation (the file is compiled
+// with contraction off, and the pragma below says so again) -- takes v = min(max(floor(f), 0), nsrc - 1) and adds v (m_t - (W mod
+// m_t)) to the 128-bit sum: one more product, below 2^4 2^61, so the sum is 17 products below 2^122 < 2^127.
+// The bound on |f - sum_r y_r / s_r|, u = 2^-53, n = nsrc <= 17, s_r < 2^61, y_r < s_r:
+//   src_rinv[r] = (1 / s_r)(1 + d1), (double)y_r = y_r (1 + d2), the product (1 + d3), |d| <= u: each term t_r = (y_r / s_r)(1 + e_r)
+//   with |e_r| <= 3u + 3u^2 + u^3 < 3.01u, and y_r / s_r < 1, so |t_r - y_r / s_r| < 3.01u and t_r < 1 + 3.01u.
+//   The first addition (0 + t_0) is exact; every later partial sum is below 17 (1 + 3.01u) < 32, and so is its rounded value (32 is
+//   representable), so its rounding error is at most half an ulp of a value below 32, 2^4 u; n - 1 such additions.
+//   |f - sum_r y_r / s_r| <= 3.01 n u + 16 (n - 1) u <= (51.2 + 256) u < 323 2^-53 < 2^-44.
+// The header promises eps = 2^-40.  Hence floor(f) differs from v* only where X' / W is within eps of 0 or of 1, by one and to the near
+// side, and the clamp keeps v in [0, nsrc) where f rounds onto nsrc itself (nsrc = 1, y = s - 1: the product is 1.0).
+// Registers: the fast <16> takes 166 VGPRs, three waves per SIMD, and the target loop waits for its constants (behind the stores of
+// the previous target the compiler fetches them with vector loads of their uniform addresses, not with the scalar loads the note
+// above counts on), so the waves in flight are what hides that wait.  Left alone the exact <16> takes 178 and runs
+// two, 24 % slower per launch; asked to fit three it takes 166 with 20 bytes of spill per lane outside the target loop.  The
+// attribute's value for the fast instantiations is the default: their code is the same text.
+template <int AMAX, bool EXACT = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EXACT ? 3 : 1))) void hy_convert_kernel(HyConvArgs g)
 {
+#pragma clang fp contract(off)
     const HyConv &cv = *g.cv;
     const uint32_t ns = cv.nsrc, nt = cv.ntgt;
     const size_t n2 = g.n2;
@@ -84,11 +109,36 @@ __global__ __launch_bounds__(256) void hy_convert_kernel(HyConvArgs g)
                 y[r].y = csub(mul_shoup_lazy(csub(v.y + pre, q), inv.w, inv.wq, q), q);
             }
         }
+        // the overflow of the two coefficients: below nsrc <= 16, kept in 32 bits (the registers of this kernel are its occupancy)
+        [[maybe_unused]] uint32_t vx = 0, vy = 0;
+        if constexpr (EXACT)
+        {
+            double fx = 0.0, fy = 0.0;
+#pragma unroll
+            for (int r = 0; r < AMAX; ++r)
+            {
+                if ((uint32_t)r < ns)
+                {
+                    const double ri = cv.src_rinv[r];
+                    const double tx = __ull2double_rn(y[r].x) * ri, ty = __ull2double_rn(y[r].y) * ri;
+                    fx = fx + tx;
+                    fy = fy + ty;
+                }
+            }
+            // f >= 0 (a sum of non-negative terms), so the lower clamp is the conversion's own; the upper one is the contract's
+            const double top = (double)(ns - 1);
+            vx = (uint32_t)fmin(floor(fx), top);
+            vy = (uint32_t)fmin(floor(fy), top);
+        }
         for (uint32_t t = 0; t < nt; ++t)
         {
             const PrimeConst *pc = g.pc + cv.tgt_prime[t];
             const uint64_t m = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, post = cv.tgt_post[t];
             uint64_t lx = 0, hx = 0, ly = 0, hy = 0;
+            if constexpr (EXACT)
+            {
+                mac2(lx, hx, ly, hy, make_ulonglong2(vx, vy), cv.tgt_negw[t]);
+            }
 #pragma unroll
             for (int r = 0; r < AMAX; ++r)
             {

@@ -123,6 +123,8 @@ SYMBOLS = {
     "moai_apply_galois_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
     "moai_relinearize_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, sz, vp]),
     "moai_relinearize_rescale_hybrid_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, sz, vp]),
+    "moai_hybrid_set_rounding": (C.c_int, [vp, C.c_int]),
+    "moai_hybrid_rounding": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "moai_gather_blocks": (C.c_int, [vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_scatter_blocks": (C.c_int, [vp, vp, C.POINTER(vp), sz, sz, vp]),
     "moai_key_words": (sz, [vp, sz]),
@@ -147,6 +149,7 @@ SYMBOLS = {
 
 
 MOAI_EINVAL = -1  # include/moai_hip.h
+HYBRID_ROUND_FAST, HYBRID_ROUND_EXACT = 0, 1  # MOAI_HYBRID_ROUND_* of include/moai_hip.h
 # moai_arith_mode: the arithmetic modes and the operations it answers for (include/moai_hip.h)
 MODE_LAZY16, MODE_LAZY8, MODE_GUARD2, MODE_GUARD, MODE_NOGUARD, MODE_FPN, MODE_FPR = -3, -2, -1, 0, 1, 2, 3
 MODE_OF_KEY_SWITCH, MODE_OF_MOD_DOWN, MODE_OF_NTT_FORWARD, MODE_OF_NTT_INVERSE = 0, 1, 2, 3
@@ -401,6 +404,15 @@ class Context:
         if d == 0:
             _check(MOAI_EINVAL)
         return int(d)
+
+    # include/moai_hip.h, "hybrid rounding mode": HYBRID_ROUND_FAST (the default) or HYBRID_ROUND_EXACT, per context
+    def hybrid_set_rounding(self, mode):
+        _check(lib().moai_hybrid_set_rounding(self.h, int(mode)))
+
+    def hybrid_rounding(self):
+        mode = C.c_int(-1)
+        _check(lib().moai_hybrid_rounding(self.h, C.byref(mode)))
+        return mode.value
 
     def switch_key_hybrid(self, ct, target, key, L, alpha, batch, stream=None):
         _check(lib().moai_switch_key_hybrid(self.h, _ptr(ct), _ptr(target), _ptr(key), L, alpha, batch, stream))
