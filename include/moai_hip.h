@@ -572,15 +572,9 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_NTT_PIPE_MIN      32    chunks per side stream below which a transform stays on the caller's stream
  *   MOAI_NTT_PIPE_INNER    0     1: the transforms inside key switch, mod-down, encode and decode take the MOAI_NTT_PIPE schedule too
  *   MOAI_NTT_NAIVE         0     1: one launch per radix-2 stage over global memory (cross-check path)
- *   MOAI_NTT_COOP          0     1: the single-launch persistent transform (N >= 4096)
- *   MOAI_NTT_COOP_WPC      4     single-launch transform: workgroups per compute unit
- *   MOAI_NTT_COOP_DELAY    4     single-launch transform: rows a second pass stays behind the first
- *   MOAI_NTT_COOP_OCC      4     single-launch transform: occupancy the kernel is compiled for (3 or 4)
  *   MOAI_KS_FP_MIN_ROWS    16    batch * L from which the key switch uses the FP64 arithmetic modes
  *   MOAI_KS_TMP_MB         8192  MiB of key-switch digits in flight: sets how many output moduli share a launch
  *   MOAI_KS_P1_ITEMS       8     1: the key switch's strided pass at N = 2^16 runs one tile per workgroup instead of eight, pipelined
- *   MOAI_KS_P1_PRE         0     1: the M_FPN strided pass of the key switch takes its twiddles as plain doubles
- *   MOAI_KS_MAC_PF         1     key residues of the FP64 key-switch MAC: 0 loaded next to their use, 1 at its head, 2 at the digit's head
  *   MOAI_KS_HOIST_PAIR     4     rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one
  *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel

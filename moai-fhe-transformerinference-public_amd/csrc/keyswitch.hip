@@ -656,17 +656,12 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
     p1.L = (uint32_t)L;
     p1.G = (uint32_t)G;
     p1.total_work = (uint32_t)(batch * G * L * TPR);
-    p1.tw1 = c->fwd_twf1;
     // N = 2^16, FP64 modes, enough work to fill the chip that way: eight tiles per workgroup, software-pipelined
     // (fwd_strided_tiles; MOAI_KS_P1_ITEMS=1: one tile per workgroup)
     constexpr int P1_ITEMS = (LOGN == 16 && MODE >= M_FPN) ? 8 : 1;
     if (P1_ITEMS > 1 && p1.total_work >= 8u * 2048u && tuning(K_KS_P1_ITEMS) > 1)
     {
-        hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE, false, P1_ITEMS>), dim3(p1.total_work / P1_ITEMS), dim3(256), 0, s, p1);
-    }
-    else if (MODE == M_FPN && tuning(K_KS_P1_PRE))
-    {
-        hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE, MODE == M_FPN>), dim3(p1.total_work), dim3(256), 0, s, p1);
+        hipLaunchKernelGGL((ks_fwd_strided<LOGN, MODE, P1_ITEMS>), dim3(p1.total_work / P1_ITEMS), dim3(256), 0, s, p1);
     }
     else
     {
@@ -692,18 +687,10 @@ static int ks_fused_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const u
     p2.jchunk = (uint32_t)((L + splits - 1) / splits);
     p2.split_stride = batch * 2 * (L + 1) * c->n;
     p2.total_work = (uint32_t)(batch * G * TPR * 2 * splits); // 2048-coefficient tiles
-    // where the MAC fetches its key residues (keyswitch_kernels.hip.h): all eight loads at the head of the MAC by default --
-    // same box, same hour, l = 35 / 15, batch 64: 0.572 / 0.134 ms per ciphertext with the compiler's placement (0), 0.532 / 0.121
-    // with 1, 0.547 / 0.124 with 2 (profiles/r03_b_ks_kernel_variants_ab.txt)
-    // The integer modes have the PF = 0 kernels only; a value other than 1 or 2 is 0.
-    const long pf = MODE >= M_FPN ? tuning(K_KS_MAC_PF) : 0;
-    return dispatch<0, 1, 2>("key residue placement ", pf == 1 || pf == 2 ? (int)pf : 0, [&](auto PF) {
-        return plain_or_list<KsP2ListArgs>(p2, tg.lst, [&](const auto &args, auto LIST) {
-            hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, (MODE >= M_FPN ? decltype(PF)::value : 0), decltype(LIST)::value>),
-                               dim3(p2.total_work), dim3(256), 0, s, args);
-            MOAI_LAUNCH_CHECK();
-            return MOAI_OK;
-        });
+    return plain_or_list<KsP2ListArgs>(p2, tg.lst, [&](const auto &args, auto LIST) {
+        hipLaunchKernelGGL((ks_contig_mac8<LOGN, MODE, decltype(LIST)::value>), dim3(p2.total_work), dim3(256), 0, s, args);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
     });
 }
 
@@ -1349,7 +1336,6 @@ static int hoist_group(moai_ctx *c, const uint64_t *t, uint64_t *tmp, const uint
     p1.t = t;
     p1.tmp = tmp;
     p1.tw = twiddles(c, MODE, false).tw;
-    p1.tw1 = c->fwd_twf1;
     p1.pc = c->pc;
     p1.grp = grp;
     p1.L = (uint32_t)L;

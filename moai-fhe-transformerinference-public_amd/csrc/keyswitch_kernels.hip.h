@@ -27,7 +27,6 @@ struct KsP1Args
     const uint64_t *t;  // [B][L][N] digits in coefficient form
     uint64_t *tmp;      // [B][G][L][N] after the strided pass, lazy [0,4q)
     const Tw *tw;
-    const double *tw1;  // FP64 modes: the forward powers as plain doubles (PRE variant), or nullptr
     const PrimeConst *pc;
     KsGroup grp;
     uint32_t L;
@@ -43,7 +42,7 @@ struct KsP1Args
 //   M_FPN/FPR  prime below 2^51: FP64 butterflies (tw = the FP64 table), canonical integer into the MAC
 // ITEMS > 1 (FP64 modes): a workgroup takes ITEMS consecutive tiles of its row, software-pipelined (fwd_strided_tiles); the grid
 // is total_work / ITEMS
-template <int LOGN, int MODE, bool PRE = false, int ITEMS = 1>
+template <int LOGN, int MODE, int ITEMS = 1>
 __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -85,8 +84,7 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
             }
             else
             {
-                fwd_strided_tile<LOGN, LoadBarrettFp, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op,
-                                                                 PRE ? a.tw1 + ((size_t)prime << LOGN) : nullptr);
+                fwd_strided_tile<LOGN, LoadBarrettFp, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op);
             }
         }
         else
@@ -100,8 +98,7 @@ __global__ __launch_bounds__(256, 4) void ks_fwd_strided(KsP1Args a)
             }
             else
             {
-                fwd_strided_tile<LOGN, LoadFp52, MODE, PRE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op,
-                                                            PRE ? a.tw1 + ((size_t)prime << LOGN) : nullptr);
+                fwd_strided_tile<LOGN, LoadFp52, MODE>(in, out, tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds, threadIdx.x, op);
             }
         }
     }
@@ -169,11 +166,12 @@ __device__ __forceinline__ uint32_t phys8_b(uint32_t e)
     return e ^ (((e >> 5) & 3u) << 1);
 }
 
-// PF (FP64 modes): where the digit's sixteen key residues per thread (eight 16-byte loads) are issued.  0: next to the
-// products that use them, two loads per quarter of the MAC with a wait behind each pair -- what the compiler makes of the
-// straightforward loop (the periodic reduction's branch keeps it from moving them): four exposed L2 round trips per digit.
-// 1: all eight at the head of the MAC, one wait.  2: all eight at the head of the iteration, next to the digit's own loads,
-// so that they are in flight during the whole transform (32 more registers live across it).
+// FP64 modes: the digit's sixteen key residues per thread (eight 16-byte loads) are all issued at the head of the MAC, with one wait,
+// and one branch goes around the sixteen periodic reductions.  Measured in round 3 (profiles/r03_b_ks_kernel_variants_ab.txt;
+// l = 35, batch 64, per key switch): 0.529 ms this way; 0.572 ms with the loads next to the products that use them and a reduction
+// per quarter (the straightforward loop: the reduction's branch pins two loads per quarter with a wait behind each pair, four exposed
+// L2 round trips per digit); 0.547 ms with the loads at the head of the iteration, in flight during the whole transform (32 more
+// registers live across it).
 // (Measured in round 3 and not kept: the digit's VALUES prefetched one digit ahead without registers -- each wave copying the next
 // digit's 4 KiB into its own part of exchange buffer A with global_load_lds_dwordx4 as soon as it has read that buffer back, the
 // twiddles of stages 0..2 in LDS, no global load at the head of an iteration: bit-identical, 0.496 against 0.502 ms per key switch
@@ -182,7 +180,7 @@ __device__ __forceinline__ uint32_t phys8_b(uint32_t e)
 // LIST: every ciphertext of the batch has its own key and key layout (KsList).  The ciphertext index is uniform over the workgroup,
 // so the key's address and row count are two scalar loads at the head of the workgroup and live in SGPRs like the kernel
 // arguments they replace: the loop over the digits is the same code.
-template <int LOGN, int MODE, int PF = 0, bool LIST = false>
+template <int LOGN, int MODE, bool LIST = false>
 __global__ __launch_bounds__(256, 4) void ks_contig_mac8(std::conditional_t<LIST, KsP2ListArgs, KsP2Args> a)
 {
     constexpr int R1 = LOGN - 8;
@@ -283,16 +281,6 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(std::conditional_t<LIST
             reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 0) * key_k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
         const ulonglong2 *__restrict__ k1 =
             reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 1) * key_k + krow) << LOGN)) + ((size_t)tile << 10) + ch0;
-        ulonglong2 kpa[4], kpb[4];
-        if (mode_fp(MODE) && PF == 2)
-        {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-            {
-                kpa[c] = k0[c];
-                kpb[c] = k1[c];
-            }
-        }
         if (direct)
         {
             // digit under its own prime: canonical NTT-form values straight from the target row
@@ -411,22 +399,21 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(std::conditional_t<LIST
         // M_FPN (33 q < 2^52, context.hip build_prime) takes the digit as the butterflies left it, its products are below 2.5 q
         // (bounds below), and it adds sixteen
         const bool fold = MODE == M_FPR ? ((J - j0) % 3u == 2u) : (((J - j0) & 15u) == 15u);
-        if (mode_fp(MODE) && PF != 0)
+        if (mode_fp(MODE))
         {
-            // the same products and sums as below, in the same order per accumulator: the same bits.
+            // the MAC stays on the FP64 pipe as well (fp_mulmod_q with the key residue canonical, below 2^51): each product is
+            // reduced exactly like a butterfly's, and the running sums stay below 2^53.
             // The digit value enters the products as the butterflies left it in M_FPN (below 33q < 2^52: the quotient estimate of
             // fp_mulmod_q is then off by at most 2, the product below 2.5 q, h - c q = r - l still an integer below 2^50, and
             // sixteen of them on a folded sum stay below 40.5 q < 2^53 = 66 q at least) and folded to |v| <= q/2 in M_FPR
             // (2^53 is only 4q there).  A copied digit (canonical, below q) needs no folding in either mode.
             const double qd = u2d(bq1), qinv = u2d(bq2);
-            if (PF == 1)
-            {
+            ulonglong2 kpa[4], kpb[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
-                {
-                    kpa[c] = k0[c];
-                    kpb[c] = k1[c];
-                }
+            for (int c = 0; c < 4; ++c)
+            {
+                kpa[c] = k0[c];
+                kpb[c] = k1[c];
             }
             double sm[16];
 #pragma unroll
@@ -454,36 +441,6 @@ __global__ __launch_bounds__(256, 4) void ks_contig_mac8(std::conditional_t<LIST
                 lo0[2 * c + 1] = d2u(sm[4 * c + 1]);
                 lo1[2 * c] = d2u(sm[4 * c + 2]);
                 lo1[2 * c + 1] = d2u(sm[4 * c + 3]);
-            }
-        }
-        else if (mode_fp(MODE))
-        {
-            // FP64 modes: the MAC stays on the FP64 pipe as well (fp_mulmod_q with the key residue canonical, below 2^51; the
-            // digit folded to |v| <= q/2 first in M_FPR, as it comes in M_FPN -- bounds above), each product is reduced
-            // exactly like a butterfly's, and the running sums stay below 2^53.
-            const double qd = u2d(bq1), qinv = u2d(bq2);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-            {
-                const double vx = MODE == M_FPN ? u2d(x[2 * c]) : fp_red(u2d(x[2 * c]), qd, qinv);
-                const double vy = MODE == M_FPN ? u2d(x[2 * c + 1]) : fp_red(u2d(x[2 * c + 1]), qd, qinv);
-                const ulonglong2 ka = k0[c];
-                const ulonglong2 kb = k1[c];
-                double s0 = u2d(lo0[2 * c]) + fp_mulmod_q(vx, fp_from_u52(ka.x), qd, qinv);
-                double s1 = u2d(lo0[2 * c + 1]) + fp_mulmod_q(vy, fp_from_u52(ka.y), qd, qinv);
-                double s2 = u2d(lo1[2 * c]) + fp_mulmod_q(vx, fp_from_u52(kb.x), qd, qinv);
-                double s3 = u2d(lo1[2 * c + 1]) + fp_mulmod_q(vy, fp_from_u52(kb.y), qd, qinv);
-                if (fold)
-                {
-                    s0 = fp_red(s0, qd, qinv);
-                    s1 = fp_red(s1, qd, qinv);
-                    s2 = fp_red(s2, qd, qinv);
-                    s3 = fp_red(s3, qd, qinv);
-                }
-                lo0[2 * c] = d2u(s0);
-                lo0[2 * c + 1] = d2u(s1);
-                lo1[2 * c] = d2u(s2);
-                lo1[2 * c + 1] = d2u(s3);
             }
         }
         else

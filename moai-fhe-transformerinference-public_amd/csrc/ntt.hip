@@ -183,56 +183,6 @@ static int launch_inv(const moai_ctx *c, const NttArgs &base, hipStream_t s)
     return launch_classes<LOGN, true, M_GUARD, M_LAZY8, M_FPN, M_FPR, M_LAZY16>(c, base, s);
 }
 
-// single-launch transform (ntt_coop); its queue state lives in a per-stream arena
-static size_t coop_grid(const moai_ctx *c)
-{
-    const long wpc = tuning(K_NTT_COOP_WPC);
-    return (size_t)c->num_cu * (size_t)(wpc > 0 ? wpc : 4);
-}
-
-static uint32_t coop_delay()
-{
-    const long d = tuning(K_NTT_COOP_DELAY);
-    return (uint32_t)(d > 0 ? d : 1);
-}
-
-static size_t coop_steps_cap(const moai_ctx *c, size_t rows)
-{
-    return rows + coop_delay() + coop_grid(c) + 8;
-}
-
-static size_t coop_state_bytes(const moai_ctx *c, size_t rows)
-{
-    return sizeof(CoopState) + sizeof(uint32_t) * (rows + 8 * coop_steps_cap(c, rows));
-}
-
-static int launch_coop(moai_ctx *c, const NttArgs &base, bool inverse, void *state_mem, hipStream_t s)
-{
-    NttArgs a = base;
-    const uint32_t rows = a.n_poly * a.L;
-    const uint32_t grid = (uint32_t)coop_grid(c);
-    CoopArgs ca;
-    ca.rows = rows;
-    ca.delay = coop_delay();
-    ca.steps_cap = (uint32_t)coop_steps_cap(c, rows);
-    ca.st = static_cast<CoopState *>(state_mem);
-    ca.done = reinterpret_cast<uint32_t *>(static_cast<char *>(state_mem) + sizeof(CoopState));
-    ca.rowmap = ca.done + rows;
-    MOAI_HIP_CHECK(hipMemsetAsync(state_mem, 0, coop_state_bytes(c, rows), s));
-    a.total_work = grid;
-    MOAI_TRY(dispatch_logn(c->logn, [&](auto LG) {
-        return dispatch<3, 4>("ntt_coop occupancy ", tuning(K_NTT_COOP_OCC) == 3 ? 3 : 4, [&](auto OCC) {
-            return dispatch<0, 1>("direction ", inverse, [&](auto INV) {
-                hipLaunchKernelGGL((ntt_coop<decltype(LG)::value, decltype(INV)::value != 0, decltype(OCC)::value>), dim3(grid), dim3(256), 0,
-                                   s, a, ca);
-                return MOAI_OK;
-            });
-        });
-    }));
-    MOAI_LAUNCH_CHECK();
-    return MOAI_OK;
-}
-
 size_t ntt_pipe_plan(size_t n_poly, size_t L, size_t n, size_t chunk_bytes, long k, long min_chunks, size_t *chunk_polys, int *streams)
 {
     size_t chunk = n_poly, per_stream = 0;
@@ -290,10 +240,10 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
     }
     NttArgs a = ntt_args(c, data, n_poly, L, rows, inverse);
     const int logn = c->logn;
-    const bool naive = tuning(K_NTT_NAIVE) != 0, coop = tuning(K_NTT_COOP) != 0;
+    const bool naive = tuning(K_NTT_NAIVE) != 0;
     if (src)
     {
-        if (naive || logn <= 11 || coop)
+        if (naive || logn <= 11)
         {
             // the paths that transform in place: bring the slice over first
             const size_t row_bytes = c->n * sizeof(uint64_t);
@@ -340,16 +290,6 @@ int ntt_launch(moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, const RowMa
         }
         MOAI_LAUNCH_CHECK();
         return MOAI_OK;
-    }
-    if (coop)
-    {
-        // opt-in (MOAI_NTT_COOP=1): one persistent launch per transform, the two passes meeting in L2.
-        // Measured on MI355X (round 1): no faster than two launches -- L2 is write-through, so only the
-        // second-pass reads could be saved, and keeping enough rows in flight to avoid dependency stalls
-        // overflows the 4 MiB L2.
-        void *st = nullptr;
-        MOAI_TRY(reserve_for_stream(c, (void *)((uintptr_t)s ^ 1u), coop_state_bytes(c, n_poly * L), &st, false));
-        return launch_coop(c, a, inverse, st, s);
     }
     // The two passes of one transform exchange the whole polynomial through memory.  Launched per chunk of polynomials
     // (MOAI_NTT_CHUNK_MB [+ _KB], 0 = one chunk), the second pass can read from the 256 MiB Infinity Cache what the first one just

@@ -212,13 +212,13 @@ __device__ __forceinline__ void ct_bfly_stage(uint64_t &x, uint64_t &y, uint64_t
     }
 }
 
-// one tile of the strided pass: reads row `inp`, writes row `outp` (may be the same row)
-// PRE (FP64 modes, with tw1 = the forward powers as plain doubles): the per-thread twiddles of phase B -- fifteen at N = 2^16 --
-// are fetched as 8-byte doubles BEFORE the exchange instead of as 16-byte {w, w/q} pairs one or two at a time between the
-// butterflies that use them (ten exposed round trips to L2 per tile in the compiled loop); the butterflies then take their
-// quotient estimate from RN(y w) RN(1/q) like the contiguous key-switch pass (ct_bfly_fp1: growth below 2q per stage instead of
-// 0.75q; 46-bit primes still end all sixteen stages below 28q < 2^52).  Same residues.
 // the 16 values a thread takes from its tile of the input row (tile base = row + tile * G), not yet converted
+// Element e = j * 256 + tid of the tile sits in column e & (G - 1) of sub-transform e >> GB, sub-transforms 256 apart.  Every caller's
+// `tid` is a thread of a 256-thread workgroup, so the three fields of the index -- j, tid's sub-transform, tid's column -- share no
+// bit, and the index is written as their OR.  Written as the shifts and sums of e, the compiled addresses depended on whether the
+// compiler had traced `tid` back to the workgroup size at the point where it simplified this function -- one 32-bit offset off a scalar
+// base per access, or a 64-bit sum per access -- and that changed with the set of kernels that shared the function.  (Telling it with
+// __builtin_assume(tid < 256) picks the 64-bit sums at N = 2^14 and 2^15: 110-160 bytes more per kernel.)
 template <int LOGN>
 __device__ __forceinline__ void strided_load_raw(const uint64_t *__restrict__ irow, const uint32_t tid, uint64_t (&raw)[16])
 {
@@ -227,8 +227,9 @@ __device__ __forceinline__ void strided_load_raw(const uint64_t *__restrict__ ir
 #pragma unroll
     for (int j = 0; j < 16; ++j)
     {
-        uint32_t e = (uint32_t)j * 256u + tid;
-        raw[j] = irow[((e >> GB) << 8) + (e & (G - 1))];
+        // N = 2^12 (GB = 8: the index is j * 256 + tid) keeps the sum: its sixteen loads then share one 64-bit address and differ in
+        // their immediate offsets, sixteen offset registers fewer, which is what keeps those kernels at eight waves per SIMD
+        raw[j] = irow[GB == 8 ? (uint32_t)j * 256u + tid : ((uint32_t)j << (16 - GB)) | ((tid >> GB) << 8) | (tid & (G - 1))];
     }
 }
 
@@ -236,10 +237,9 @@ __device__ __forceinline__ void strided_load_raw(const uint64_t *__restrict__ ir
 // output row).  SYNC_FIRST: the workgroup has used `lds` for an earlier tile -- wait until everybody has read it.  The barriers
 // wait for LDS traffic only (lds_barrier), so global loads and stores of neighbouring tiles stay in flight across them.
 // LDSTW: phase B takes its twiddles (entries 16..255 of the table) from the workgroup's copy in LDS, `ldstw`
-template <int LOGN, int MODE, bool PRE, bool SYNC_FIRST, bool LDSTW = false>
+template <int LOGN, int MODE, bool SYNC_FIRST, bool LDSTW = false>
 __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__restrict__ row, const Tw *__restrict__ tw, uint64_t q,
-                                             uint64_t q2, uint64_t *lds, const uint32_t tid, const double *__restrict__ tw1,
-                                             const Tw *ldstw = nullptr)
+                                             uint64_t q2, uint64_t *lds, const uint32_t tid, const Tw *ldstw = nullptr)
 {
     // phase A's fifteen twiddles (entries 1..15 of the table) are the same for every thread: read through the constant address
     // space, so that they stay SCALAR loads also inside a loop over tiles -- behind the stores of an earlier iteration the compiler
@@ -252,12 +252,6 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
     constexpr int GB = 12 - R1;
     constexpr uint32_t G = 1u << GB;
     // phase A: top four bits of t live in the register index
-#ifdef MOAI_DIAG_NOCOMPUTE
-    const int diag_stages = (q == 0x7ff8dead0000beefull) ? 4 : 0; // diagnostic build: loads, exchange and stores only
-#define MOAI_DIAG_STAGE_OK(u) && ((u) < diag_stages)
-#else
-#define MOAI_DIAG_STAGE_OK(u)
-#endif
 #pragma unroll
     for (int u = 0; u < 4; ++u)
     {
@@ -265,7 +259,7 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
 #pragma unroll
         for (int j = 0; j < 16; ++j)
         {
-            if (!(j & half) MOAI_DIAG_STAGE_OK(u))
+            if (!(j & half))
             {
                 const uint32_t ti = (1u << u) + (uint32_t)(j >> (4 - u));
                 ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], twa[ti].w, twa[ti].wq, q, q2, LOGN - 1 - u);
@@ -274,21 +268,6 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
     }
     if (RB > 0)
     {
-        double twb[16];
-        if (PRE)
-        {
-            const uint32_t thp = tid >> GB;
-#pragma unroll
-            for (int s = 4; s < R1; ++s)
-            {
-                const int cnt = 16 >> (R1 - s); // distinct twiddles of this stage per thread
-#pragma unroll
-                for (int i = 0; i < cnt; ++i)
-                {
-                    twb[cnt - 1 + i] = tw1[(1u << s) + ((thp << (4 - (R1 - s))) | (uint32_t)i)];
-                }
-            }
-        }
         if (SYNC_FIRST)
         {
             lds_barrier();
@@ -314,18 +293,11 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
 #pragma unroll
             for (int j = 0; j < 16; ++j)
             {
-                if (!(j & half) MOAI_DIAG_STAGE_OK(s - 4))
+                if (!(j & half))
                 {
-                    if (PRE)
-                    {
-                        ct_bfly_fp1<MODE == M_FPR>(x[j], x[j + half], twb[(16 >> (R1 - s)) - 1 + (j >> (R1 - s))], u2d(q), u2d(q2));
-                    }
-                    else
-                    {
-                        uint32_t t_ = (th << 4) | (uint32_t)j;
-                        Tw t = LDSTW ? ldstw[(1u << s) + (t_ >> (R1 - s))] : tw[(1u << s) + (t_ >> (R1 - s))];
-                        ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], t.w, t.wq, q, q2, LOGN - 1 - s);
-                    }
+                    uint32_t t_ = (th << 4) | (uint32_t)j;
+                    Tw t = LDSTW ? ldstw[(1u << s) + (t_ >> (R1 - s))] : tw[(1u << s) + (t_ >> (R1 - s))];
+                    ct_bfly_stage<MODE, LOGN>(x[j], x[j + half], t.w, t.wq, q, q2, LOGN - 1 - s);
                 }
             }
         }
@@ -333,10 +305,7 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
         for (int j = 0; j < 16; ++j)
         {
             uint32_t t_ = (th << 4) | (uint32_t)j;
-#ifdef MOAI_DIAG_NOSTORE
-            if (x[j] == 0x7ff8dead0000beefull) // diagnostic build: the arithmetic stays, the stores (practically) never happen
-#endif
-            row[(t_ << 8) + g] = x[j]; // (non-temporal stores measured the same: 2080 against 2092 us in the key switch's pass)
+            row[(t_ << 8) | g] = x[j]; // (non-temporal stores measured the same: 2080 against 2092 us in the key switch's pass)
         }
     }
     else
@@ -350,12 +319,13 @@ __device__ __forceinline__ void strided_core(uint64_t (&x)[16], uint64_t *__rest
     }
 }
 
+// one tile of the strided pass: reads row `inp`, writes row `rowp` (may be the same row)
 // LDSTW (N = 2^16, `lds` with 512 more words): phase B's twiddles -- entries 16..255 of the table, the same for every tile -- are
 // copied into LDS, one 16-byte load per thread issued with the tile's own loads, and read from there behind the exchange
-template <int LOGN, class LoadOp = LoadIdentity, int MODE = M_GUARD, bool PRE = false, bool LDSTW = false>
+template <int LOGN, class LoadOp, int MODE, bool LDSTW = false>
 __device__ __forceinline__ void fwd_strided_tile(const uint64_t *__restrict__ inp, uint64_t *__restrict__ rowp, uint32_t tile,
                                                  const Tw *__restrict__ tw, uint64_t q, uint64_t q2, uint64_t *lds,
-                                                 const uint32_t tid, LoadOp op = LoadOp(), const double *__restrict__ tw1 = nullptr)
+                                                 const uint32_t tid, LoadOp op = LoadOp())
 {
     constexpr uint32_t G = 1u << (12 - (LOGN - 8));
     static_assert(!LDSTW || LOGN == 16, "the LDS copy holds the 256 entries phase B of N = 2^16 indexes");
@@ -371,13 +341,13 @@ __device__ __forceinline__ void fwd_strided_tile(const uint64_t *__restrict__ in
     {
         x[j] = op(x[j]);
     }
-    strided_core<LOGN, MODE, PRE, false, LDSTW>(x, rowp + tile * G, tw, q, q2, lds, tid, tw1, LDSTW ? ldstw : nullptr);
+    strided_core<LOGN, MODE, false, LDSTW>(x, rowp + tile * G, tw, q, q2, lds, tid, LDSTW ? ldstw : nullptr);
 }
 
 // ITEMS consecutive tiles of one row by one workgroup, software-pipelined: the loads of tile i + 1 are issued before the
 // butterflies of tile i, and the stores of tile i drain under the butterflies of tile i + 1.  A workgroup that loads, computes and
 // stores ONE tile keeps the memory system busy only through its neighbours on the CU, and 32 KiB of LDS plus ~96 VGPRs allow four
-// or five of them: measured on the key switch's strided pass (round 3, tools/diag), 2.37 ms per launch against 1.96 ms for its
+// or five of them: measured on the key switch's strided pass (round 3), 2.37 ms per launch against 1.96 ms for its
 // memory traffic alone and 1.62 ms for its arithmetic alone -- the two did not overlap.
 template <int LOGN, class LoadOp, int MODE, int ITEMS>
 __device__ __forceinline__ void fwd_strided_tiles(const uint64_t *inp, uint64_t *rowp, uint32_t tile0,
@@ -413,7 +383,7 @@ __device__ __forceinline__ void fwd_strided_tiles(const uint64_t *inp, uint64_t 
         {
             strided_load_raw<LOGN>(inp + (tile0 + it + 1u) * G, t, raw);
         }
-        strided_core<LOGN, MODE, false, true, true>(x, rowp + (tile0 + it) * G, tw, q, q2, lds, t, nullptr, ldstw);
+        strided_core<LOGN, MODE, true, true>(x, rowp + (tile0 + it) * G, tw, q, q2, lds, t, ldstw);
         if (more)
         {
 #pragma unroll
@@ -431,7 +401,7 @@ constexpr bool fwd_strided_occ4(int mode)
 {
     return mode == M_GUARD2 || mode_lazy(mode) || mode == M_FPR || mode == M_NOGUARD;
 }
-template <int LOGN, int MODE = M_GUARD>
+template <int LOGN, int MODE>
 __global__ __launch_bounds__(256, fwd_strided_occ4(MODE) ? 4 : 5) void ntt_fwd_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -454,11 +424,11 @@ __global__ __launch_bounds__(256, fwd_strided_occ4(MODE) ? 4 : 5) void ntt_fwd_s
         LoadFp op;
         op.qd = pc.qd;
         op.qinv = pc.qinv;
-        fwd_strided_tile<LOGN, LoadFp, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x, op);
+        fwd_strided_tile<LOGN, LoadFp, MODE, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x, op);
     }
     else
     {
-        fwd_strided_tile<LOGN, LoadIdentity, MODE, false, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x);
+        fwd_strided_tile<LOGN, LoadIdentity, MODE, LDSTW>(rowp, rowp, tile, a.tw + ((size_t)prime << LOGN), q, q2, lds, threadIdx.x);
     }
 }
 
@@ -490,7 +460,7 @@ struct StoreTile
 // TWL: -1 = `ldstw` decides at run time (the reads are then generic loads: every wait for one drains LDS and memory alike);
 // 0 = memory; 1 = LDS, known at compile time: the reads are ds_read_b128, and the copy's load is issued with the tile's own
 // sixteen and waited for only where it is written to LDS, instead of costing one round trip in front of every tile.
-template <int LOGN, int MODE = M_GUARD, class StoreOp = StoreTile, int TWL = -1>
+template <int LOGN, int MODE, class StoreOp, int TWL = -1>
 __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
                                                 const Tw *__restrict__ twb, uint64_t cr1, StoreOp store, Tw *ldstw = nullptr)
@@ -642,21 +612,10 @@ __device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uin
     }
 }
 
-template <int LOGN, int MODE = M_GUARD>
-__device__ __forceinline__ void fwd_contig_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
-                                                uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
-                                                const Tw *__restrict__ twb, uint64_t cr1 = 0, Tw *ldstw = nullptr)
-{
-    static_assert(!mode_lazy(MODE), "the lazy modes' final reduction needs mode_fin, not a default");
-    StoreTile st;
-    st.out = reinterpret_cast<ulonglong2 *>(rowp + ((size_t)tile << 12));
-    fwd_contig_tile<LOGN, MODE, StoreTile>(rowp, tile, tw, q, q2, lds2, tid, twb, cr1, st, ldstw);
-}
-
 // TWL (fwd_contig_tile): -1 = NttArgs::lds_twiddles decides at run time, 0 / 1 = compiled in (M_LAZY16)
 // (36.6 KiB of LDS admit four workgroups per CU, and every mode's body fits the 128 registers that go with them; said here so that
 // the allocator does not settle for 129 and three)
-template <int LOGN, int MODE = M_GUARD, int TWL = -1>
+template <int LOGN, int MODE, int TWL = -1>
 __global__ __launch_bounds__(256, 4) void ntt_fwd_contig(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -704,7 +663,7 @@ __device__ __forceinline__ void gs_bfly_tile(uint64_t (&x)[16], int j, int half,
     }
 }
 
-template <int LOGN, int MODE = M_GUARD>
+template <int LOGN, int MODE>
 __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                 uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
                                                 const Tw *__restrict__ twb, const uint64_t *srcp = nullptr, Tw *ldstw = nullptr)
@@ -818,7 +777,7 @@ __device__ __forceinline__ void inv_contig_tile(uint64_t *rowp, uint32_t tile, c
     }
 }
 
-template <int LOGN, int MODE = M_GUARD>
+template <int LOGN, int MODE>
 __global__ __launch_bounds__(256) void ntt_inv_contig(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -844,7 +803,7 @@ constexpr bool inv_strided_occ4(int mode)
 {
     return mode_lazy(mode);
 }
-template <int LOGN, int MODE = M_GUARD>
+template <int LOGN, int MODE>
 __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, uint32_t tile, const Tw *__restrict__ tw,
                                                  const PrimeConst *pc, uint64_t *lds, const uint32_t tid)
 {
@@ -877,7 +836,7 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
         for (int j = 0; j < 16; ++j)
         {
             uint32_t t_ = (th << 4) | (uint32_t)j;
-            x[j] = row[(t_ << 8) + g];
+            x[j] = row[(t_ << 8) | g];
         }
         if (LDSTW)
         {
@@ -964,7 +923,6 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
 #pragma unroll
     for (int j = 0; j < 16; ++j)
     {
-        uint32_t e = (uint32_t)j * 256u + tid;
         uint64_t v;
         if (mode_fp(MODE))
         {
@@ -981,11 +939,11 @@ __device__ __forceinline__ void inv_strided_tile(uint64_t *__restrict__ rowp, ui
         {
             v = csub(x[j], q); // below 2q
         }
-        row[((e >> GB) << 8) + (e & (G - 1))] = v;
+        row[((uint32_t)j << (16 - GB)) | ((tid >> GB) << 8) | (tid & (G - 1))] = v; // element j * 256 + tid, as in strided_load_raw
     }
 }
 
-template <int LOGN, int MODE = M_GUARD>
+template <int LOGN, int MODE>
 __global__ __launch_bounds__(256, inv_strided_occ4(MODE) ? 4 : 5) void ntt_inv_strided(NttArgs a)
 {
     constexpr uint32_t TPR = 1u << (LOGN - 12);
@@ -998,196 +956,6 @@ __global__ __launch_bounds__(256, inv_strided_occ4(MODE) ? 4 : 5) void ntt_inv_s
     const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[si]);
     inv_strided_tile<LOGN, MODE>(a.data + ((size_t)((srow / a.Lsel) * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN), a.pc + prime, lds,
                                threadIdx.x);
-}
-
-// =====================================================================================================
-// single-launch transform: both passes of a row meet in one XCD's L2
-// =====================================================================================================
-// The two passes exchange the whole row (N x 8 B) and no CU can hold a 512 KiB row, but an XCD's
-// 4 MiB L2 can.  This persistent kernel therefore keeps all work on one row inside one XCD: every
-// workgroup reads the id of the XCD it runs on (HW_REG_XCC_ID) and pulls (row, pass, tile) items from
-// that XCD's own queue with one fetch-add per item; rows are claimed from a global ticket by the
-// workgroup that draws tile 0 of a step.  Queue order per XCD, in steps of 2*TPR items:
-//     [first-pass tiles of step s][second-pass tiles of step s - DELAY]
-// so a row's second pass follows its first pass by DELAY rows: long enough that the first pass has
-// normally finished, short enough that the row is still in L2.  A first-pass tile publishes with
-// "s_waitcnt vmcnt(0); barrier; one lane bumps done[row]" (its stores have then reached L2); a
-// second-pass tile waits for done[row] == TPR, drops its CU's L1 (agent-scope acquire) and reads the
-// row from L2.  HBM then sees one read and one write per coefficient instead of two of each.
-//
-// Correctness does not depend on dispatch order or placement:
-//  * a row's items are only ever handed out by the queue of the XCD that claimed the row, so producer
-//    and consumer share an L2 by construction (not by an assumption about the dispatcher);
-//  * a workgroup blocks only on items that sit EARLIER in its own queue, i.e. on workgroups that are
-//    already running and never block themselves (first-pass tiles, the row claim), so there is no
-//    co-residency requirement and no deadlock for any grid size >= 1;
-//  * every spin is bounded; a timeout sets CoopState::error (checked by the host) instead of hanging.
-struct CoopState
-{
-    uint32_t next_row; // global row ticket
-    uint32_t error;    // non-zero after a spin timeout
-    uint32_t pad0[30];
-    struct
-    {
-        uint32_t head;
-        uint32_t pad[31];
-    } q[8];
-    // followed by: uint32_t done[rows]; uint32_t rowmap[8][steps_cap]
-};
-
-struct CoopArgs
-{
-    CoopState *st;
-    uint32_t *done;     // [rows] first-pass tiles completed
-    uint32_t *rowmap;   // [8][steps_cap]: 0 = unset, 1 = end of work, r + 2 = row r
-    uint32_t rows;      // n_poly * L
-    uint32_t steps_cap;
-    uint32_t delay;     // steps between a row's first and second pass in the queue
-};
-
-#define MOAI_SPIN_LIMIT (1u << 22)
-
-__device__ __forceinline__ uint32_t xcc_id()
-{
-    uint32_t v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(v));
-    return v & 7u;
-}
-
-__device__ __forceinline__ uint32_t ld_relaxed(uint32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int LOGN, bool INV, int WPS>
-__global__ __launch_bounds__(256, WPS) void ntt_coop(NttArgs a, CoopArgs c)
-{
-    constexpr uint32_t TPR = 1u << (LOGN - 12);
-    __shared__ ulonglong2 lds2[2048];
-    __shared__ uint32_t sh[2];
-    uint64_t *lds = reinterpret_cast<uint64_t *>(lds2);
-    const uint32_t tid0 = threadIdx.x;
-    const uint32_t xcc = xcc_id();
-    uint32_t *rowmap = c.rowmap + (size_t)xcc * c.steps_cap;
-
-    for (;;)
-    {
-        __syncthreads(); // LDS tile and sh[] of the previous item are dead
-        // opaque copy of the thread index: stops the compiler from hoisting the ~70 per-thread address
-        // computations of both tile bodies out of this loop and spilling them
-        uint32_t tid = tid0;
-        asm volatile("" : "+v"(tid));
-        if (tid == 0)
-        {
-            const uint32_t it = __hip_atomic_fetch_add(&c.st->q[xcc].head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t step = it / (2 * TPR);
-            const uint32_t rem = it % (2 * TPR);
-            const uint32_t pass = rem / TPR;
-            const uint32_t tile = rem % TPR;
-            uint32_t v = 0; // 0 = empty slot, 1 = end of work, r + 2 = row r
-            if (!(pass == 1 && step < c.delay))
-            {
-                const uint32_t sr = pass ? step - c.delay : step;
-                if (sr >= c.steps_cap)
-                {
-                    v = 1;
-                }
-                else if (pass == 0 && tile == 0)
-                {
-                    uint32_t r = __hip_atomic_fetch_add(&c.st->next_row, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    v = r < c.rows ? r + 2 : 1;
-                    __hip_atomic_store(&rowmap[sr], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                else
-                {
-                    uint32_t i = 0;
-                    while ((v = ld_relaxed(&rowmap[sr])) == 0 && ++i < MOAI_SPIN_LIMIT)
-                    {
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    if (v == 0)
-                    {
-                        __hip_atomic_store(&c.st->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        v = 1;
-                    }
-                }
-                if (v >= 2 && pass == 1)
-                {
-                    // wait for the TPR first-pass tiles of this row, then drop this CU's L1
-                    uint32_t *d = &c.done[v - 2];
-                    uint32_t i = 0;
-                    while (ld_relaxed(d) < TPR && ++i < MOAI_SPIN_LIMIT)
-                    {
-                        __builtin_amdgcn_s_sleep(8);
-                    }
-                    if (i >= MOAI_SPIN_LIMIT)
-                    {
-                        __hip_atomic_store(&c.st->error, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        v = 1;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            }
-            sh[0] = v;
-            sh[1] = (pass << 16) | tile;
-        }
-        __syncthreads();
-        // wave-uniform by construction: keep them in SGPRs so that row / twiddle bases stay scalar
-        const uint32_t v = __builtin_amdgcn_readfirstlane(sh[0]);
-        const uint32_t pt = __builtin_amdgcn_readfirstlane(sh[1]);
-        const uint32_t pass = pt >> 16;
-        const uint32_t tile = pt & 0xffffu;
-        if (v == 0)
-        {
-            continue;
-        }
-        if (v == 1)
-        {
-            if (pass == 1)
-            {
-                return; // the rows behind this point of the queue do not exist
-            }
-            continue;
-        }
-        // tickets run prime-major (polynomial index fastest) so that all XCDs work under the same prime
-        // at the same time and its twiddle tables stay resident in every L2
-        const uint32_t ticket = v - 2;
-        const uint32_t prow = (ticket % a.n_poly) * a.L + ticket / a.n_poly;
-        const uint32_t prime = a.rows.idx[prow % a.L];
-        const Tw *tw = a.tw + ((size_t)prime << LOGN);
-        const PrimeConst *pc = a.pc + prime;
-        uint64_t *rowp = a.data + ((size_t)prow << LOGN);
-        if (pass == 0)
-        {
-            if (INV)
-            {
-                inv_contig_tile<LOGN>(rowp, tile, tw, pc->q, pc->q2, lds2, tid, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256));
-            }
-            else
-            {
-                fwd_strided_tile<LOGN>(rowp, rowp, tile, tw, pc->q, pc->q2, lds, tid);
-            }
-            // publish: every wave's stores have reached L2, then one lane bumps the row counter
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0)
-            {
-                __hip_atomic_fetch_add(&c.done[ticket], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        else
-        {
-            if (INV)
-            {
-                inv_strided_tile<LOGN>(rowp, tile, tw, pc, lds, tid);
-            }
-            else
-            {
-                fwd_contig_tile<LOGN>(rowp, tile, tw, pc->q, pc->q2, lds2, tid, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256));
-            }
-        }
-    }
 }
 
 // =====================================================================================================

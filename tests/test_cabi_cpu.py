@@ -52,6 +52,10 @@ def test_tuning_knobs_are_checked_by_name(moai):
     assert b"MOAI_KS_TMP_MBS" in L.moai_last_error()
     assert L.moai_set_tuning(b"MOAI_KS_TMP_MB", 1) == 0
     assert L.moai_reset_tuning() == 0
+    # the knobs of the retired kernel variants are unknown names like any other
+    for retired in (b"MOAI_NTT_COOP", b"MOAI_NTT_COOP_WPC", b"MOAI_NTT_COOP_DELAY", b"MOAI_NTT_COOP_OCC", b"MOAI_KS_P1_PRE", b"MOAI_KS_MAC_PF"):
+        assert L.moai_set_tuning(retired, 1) == -1
+        assert retired in L.moai_last_error()
     with pytest.raises(moai.MoaiError, match="MOAI_NO_SUCH_KNOB"):
         moai.hip.set_tuning("MOAI_NO_SUCH_KNOB", 0)
     moai.hip.reset_tuning()

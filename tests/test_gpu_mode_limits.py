@@ -257,16 +257,13 @@ def test_key_switch_at_the_limits(moai, logn, order, arith):
 
 # N = 2^16: the launch variants of the fused kernels.  The strided pass of an FP64 group runs eight tiles per workgroup,
 # software-pipelined, from batch * members * L * 16 >= 16384 tiles on (csrc/keyswitch.hip ks_fused_group), where `members` counts
-# the output moduli of that mode in one launch: two per FP64 mode on this chain, so 64 ciphertexts.  "default" and the MAC_PF
-# variants are that kernel, MOAI_KS_P1_ITEMS=1 the one tile per workgroup that few ciphertexts take anyway, MOAI_KS_P1_PRE
-# applies to the latter only, and a scratch budget of one modulus per launch (G = 1) leaves too few tiles by design.
+# the output moduli of that mode in one launch: two per FP64 mode on this chain, so 64 ciphertexts.  "default" is that kernel,
+# MOAI_KS_P1_ITEMS=1 the one tile per workgroup that few ciphertexts take anyway, and a scratch budget of one modulus per launch
+# (G = 1) leaves too few tiles by design.
 # variant: (knobs, moduli of one mode per launch at most -- None: all of them --, pipelined strided pass expected)
 KS_VARIANTS = {
     "default": ({}, None, True),
     "p1_items_1": ({"MOAI_KS_P1_ITEMS": 1}, None, False),
-    "p1_pre": ({"MOAI_KS_P1_PRE": 1, "MOAI_KS_P1_ITEMS": 1}, None, False),
-    "mac_pf_0": ({"MOAI_KS_MAC_PF": 0}, None, True),
-    "mac_pf_2": ({"MOAI_KS_MAC_PF": 2}, None, True),
     "tmp_mb_g1": ({"MOAI_KS_TMP_MB": 1}, 1, False),
 }
 KS_VARIANT_BATCH = 64

@@ -720,30 +720,6 @@ def test_empty_and_degenerate_calls(moai, env12):
         moai.hip._check(moai.hip.lib().moai_set_tuning(None, 1))
 
 
-def test_coop_single_launch_ntt_agrees(moai):
-    """the opt-in single-launch transform (MOAI_NTT_COOP=1, per-XCD queues) against the oracle"""
-    import subprocess, sys
-    code = r'''
-import sys, numpy as np
-sys.path.insert(0, "tests"); sys.path.insert(0, ".")
-import oracle as O, __graft_entry__ as g
-m = g.load_package()
-for logn, bits in ((12, [60, 46]), (14, [58, 51, 46]), (16, [60, 51, 46, 58])):
-    n = 1 << logn
-    primes = O.coeff_modulus_create(n, bits)
-    octx, ctx = O.Context(logn, primes), m.Context(logn, primes)
-    x = O.uniform_rns(np.random.default_rng(logn), primes, (5,), n)
-    d = m.DeviceBuffer.from_numpy(x)
-    ctx.ntt_forward(d, 5, len(primes)); assert (d.to_numpy(x.shape) == octx.ntt(x, len(primes))).all()
-    ctx.ntt_inverse(d, 5, len(primes)); assert (d.to_numpy(x.shape) == x).all()
-print("ok")
-'''
-    env = dict(os.environ, MOAI_NTT_COOP="1")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
-
-
 @pytest.mark.parametrize("bits,rows,cols", [([51, 46, 46, 58], 70, 19), ([60, 61, 60], 33, 5), ([46, 51], 3, 16), ([51, 51, 47, 58], 48, 33)])
 def test_ct_pt_matmul_matches_multiply_plain_loop(moai, bits, rows, cols):
     """moai_ct_pt_matmul == the reference loop of multiply_plain(scalar plaintext) + add_inplace
