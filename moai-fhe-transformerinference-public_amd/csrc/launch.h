@@ -15,6 +15,7 @@ namespace moai {
     X(NTT_LAZY8, 1, "0: integer primes below 2^60 take the exact butterflies instead of the approximate Shoup quotient")       \
     X(NTT_LAZY16, 1, "0: those primes keep values below 8q with a guard in every stage instead of below 16q with fewer (M_LAZY8)") \
     X(NTT_LDSTW, 1, "0: the forward contiguous pass loads its first stages' twiddles from memory instead of through LDS")      \
+    X(NTT_PAIR, 1, "0: the contiguous passes of the 60-bit rows run one polynomial per workgroup instead of two that share their twiddles") \
     X(NTT_CHUNK_MB, 88, "> 0: launch the two passes of a transform per chunk of whole polynomials of at most this many MiB")    \
     X(NTT_CHUNK_KB, 0, "KiB added to MOAI_NTT_CHUNK_MB: chunks of rings whose polynomials are smaller than a MiB")             \
     X(NTT_PIPE, 2, "1..3: deal those chunks to this many side streams, so that a chunk's second pass runs beside the next one's first; 0: one stream") \

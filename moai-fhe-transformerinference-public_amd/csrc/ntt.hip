@@ -91,16 +91,15 @@ NttArgs ntt_args(const moai_ctx *c, uint64_t *data, size_t n_poly, size_t L, con
     return a;
 }
 
-// the forward pair of launches of one class; `a` selects its rows and carries its tables and grid size
-template <int LOGN, int MODE>
-static void launch_fwd_mode(const NttArgs &a, hipStream_t s)
+// the single contiguous pass of one class
+template <int LOGN, int MODE, bool INV>
+static void launch_contig_single(const NttArgs &a, hipStream_t s)
 {
-    // (the software-pipelined strided pass of the key switch, fwd_strided_tiles, does not pay here: measured in round 3 on 256 x 2
-    // polynomials, 11.25 against 11.37 ms with the bench's 60-bit primes and 7.77 against 7.40 ms -- slower -- with MOAI's FP64
-    // rows.  An in-place transform reads as much as it writes and has no cached operand; five resident workgroups of one tile
-    // each keep more of that traffic in flight than four pipelined ones.)
-    hipLaunchKernelGGL((ntt_fwd_strided<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
-    if constexpr (MODE == M_LAZY16)
+    if constexpr (INV)
+    {
+        hipLaunchKernelGGL((ntt_inv_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+    }
+    else if constexpr (MODE == M_LAZY16)
     {
         // where the first four stages' twiddles come from is compiled into this mode's contiguous pass
         if (a.lds_twiddles)
@@ -116,6 +115,59 @@ static void launch_fwd_mode(const NttArgs &a, hipStream_t s)
     {
         hipLaunchKernelGGL((ntt_fwd_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
     }
+}
+
+// The contiguous pass of one class.  pair (MOAI_NTT_PAIR) and a mode that has the paired kernels: one workgroup per tile of two
+// polynomials, which fetches the tile's twiddles once (ntt_kernels.hip.h fwd_contig_tile2); the last polynomial of an odd
+// count, or the only one, goes to the single kernel in a launch of its own.
+template <int LOGN, int MODE, bool INV>
+static void launch_contig(const NttArgs &a, bool pair, hipStream_t s)
+{
+    if constexpr (contig_pair_mode(MODE))
+    {
+        // (the forward paired kernel takes its first stages' twiddles through LDS: MOAI_NTT_LDSTW=0 keeps the single kernels)
+        if (pair && a.n_poly >= 2 && (INV || a.lds_twiddles))
+        {
+            constexpr uint32_t TPR = 1u << (LOGN - 12);
+            NttArgs p = a;
+            p.n_poly = a.n_poly & ~1u;
+            p.total_work = (p.n_poly >> 1) * a.Lsel * TPR;
+            if constexpr (INV)
+            {
+                hipLaunchKernelGGL((ntt_inv_contig2<LOGN, MODE>), dim3(p.total_work), dim3(256), 0, s, p);
+            }
+            else
+            {
+                hipLaunchKernelGGL((ntt_fwd_contig2<LOGN, MODE>), dim3(p.total_work), dim3(256), 0, s, p);
+            }
+            if (a.n_poly & 1u)
+            {
+                NttArgs r = a;
+                r.data = a.data + (((size_t)p.n_poly * a.L) << LOGN);
+                if (a.src)
+                {
+                    r.src = a.src + (((size_t)p.n_poly * a.src_stride) << LOGN);
+                }
+                r.n_poly = 1;
+                r.total_work = a.Lsel * TPR;
+                launch_contig_single<LOGN, MODE, INV>(r, s);
+            }
+            return;
+        }
+    }
+    launch_contig_single<LOGN, MODE, INV>(a, s);
+}
+
+// the forward pair of launches of one class; `a` selects its rows and carries its tables and grid size
+template <int LOGN, int MODE>
+static void launch_fwd_mode(const NttArgs &a, bool pair, hipStream_t s)
+{
+    // (the software-pipelined strided pass of the key switch, fwd_strided_tiles, does not pay here: measured in round 3 on 256 x 2
+    // polynomials, 11.25 against 11.37 ms with the bench's 60-bit primes and 7.77 against 7.40 ms -- slower -- with MOAI's FP64
+    // rows.  An in-place transform reads as much as it writes and has no cached operand; five resident workgroups of one tile
+    // each keep more of that traffic in flight than four pipelined ones.)
+    hipLaunchKernelGGL((ntt_fwd_strided<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+    launch_contig<LOGN, MODE, false>(a, pair, s);
 }
 
 // a.sel / a.selp / a.Lsel = the rows of `a` (and their primes) whose class -- fwd_class or inv_class -- is `mode`
@@ -150,16 +202,17 @@ static int launch_classes(const moai_ctx *c, const NttArgs &base, hipStream_t s)
         a.tw = t.tw;
         a.twb = t.twb;
         a.total_work = a.n_poly * a.Lsel * (1u << (LOGN - 12));
+        const bool pair = tuning(K_NTT_PAIR) != 0;
         MOAI_TRY((dispatch<MODES...>(INV ? "inverse transform mode " : "forward transform mode ", mode, [&](auto MD) {
             constexpr int MODE = decltype(MD)::value;
             if constexpr (INV)
             {
-                hipLaunchKernelGGL((ntt_inv_contig<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
+                launch_contig<LOGN, MODE, true>(a, pair, s);
                 hipLaunchKernelGGL((ntt_inv_strided<LOGN, MODE>), dim3(a.total_work), dim3(256), 0, s, a);
             }
             else
             {
-                launch_fwd_mode<LOGN, MODE>(a, s);
+                launch_fwd_mode<LOGN, MODE>(a, pair, s);
             }
             return MOAI_OK;
         })));

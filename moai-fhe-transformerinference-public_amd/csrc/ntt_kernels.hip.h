@@ -635,6 +635,221 @@ __global__ __launch_bounds__(256, 4) void ntt_fwd_contig(NttArgs a)
                                                 (TWL < 0 ? a.lds_twiddles != 0 : TWL == 1) ? reinterpret_cast<Tw *>(lds2 + 2048) : nullptr);
 }
 
+// Orders the LDS accesses of one wave in the program without waiting for any of them: a wave's LDS instructions execute in issue
+// order, so a slot that a lane reads may be overwritten by another lane of the same wave in a later instruction.
+__device__ __forceinline__ void lds_wave_order()
+{
+    asm volatile("" ::: "memory");
+}
+
+// The fifteen twiddles of four stages on sixteen registers are slots 2^u - 1 + k, k < 2^u, of stage u.  The paired tiles fetch
+// them PAIR_TW_AHEAD slots ahead of the butterflies that use them and close every butterfly pair with pair_fence: left alone the
+// compiler moves all fifteen loads (60 registers) to the head of the stages, beside 64 registers of data, and spills.
+// (The stage loops of the paired tiles run over the eight butterflies of a stage, not over sixteen registers of which every
+// second one is skipped: with twice the body, the skipped half counted, the loops went past the size up to which they are unrolled.)
+// Eight: the largest distance at which neither kernel spills (nine: 12 bytes in the inverse one), and on the bench's batch
+// 18.31 ms per step against 18.58 with four (profiles/ntt_pair_parent_vs_branch.txt).
+constexpr int PAIR_TW_AHEAD = 8;
+// No instruction: the four values are what the program holds from here on, and no memory access moves across.
+__device__ __forceinline__ void pair_fence(uint64_t &a0, uint64_t &a1, uint64_t &b0, uint64_t &b1)
+{
+    asm volatile("" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1)::"memory");
+}
+// the inverse stages run from the widest slot range down: slots 7..14, 3..6, 1..2, 0
+constexpr int inv_slot_of_order(int k)
+{
+    return k < 8 ? 7 + k : (k < 12 ? k - 5 : (k < 14 ? k - 11 : 0));
+}
+constexpr int inv_order_of_slot(int s)
+{
+    return s >= 7 ? s - 7 : (s >= 3 ? s + 5 : (s >= 1 ? s + 11 : 14));
+}
+constexpr int slot_stage(int s)
+{
+    return s >= 7 ? 3 : (s >= 3 ? 2 : (s >= 1 ? 1 : 0));
+}
+
+// the modes whose contiguous passes exist in the paired form (fwd_contig_tile2, inv_contig_tile2)
+constexpr bool contig_pair_mode(int mode)
+{
+    return mode == M_LAZY16;
+}
+
+// The same tile of TWO polynomials (rows rowA and rowB under one prime) by one workgroup.  The fifteen per-thread twiddles of the
+// last four stages depend on (prime, tile, thread) only -- 60 KiB per 32 KiB tile of data --, so does the LDS copy of the first
+// four stages' and all the index arithmetic: every twiddle is fetched once and applied to A's butterfly and to B's.  Both tiles'
+// loads are issued before the first butterfly.  The exchanges are wave-local; the tiles pass through the one 32 KiB buffer one
+// after the other, so LDS stays what fwd_contig_tile takes.  Plain stores (StoreTile) only; the first four stages' twiddles come
+// through LDS (fwd_contig_tile's TWL = 1).
+template <int LOGN, int MODE>
+__device__ __forceinline__ void fwd_contig_tile2(uint64_t *__restrict__ rowA, uint64_t *__restrict__ rowB, uint32_t tile,
+                                                 const Tw *__restrict__ tw, uint64_t q, uint64_t q2, ulonglong2 *lds2, const uint32_t tid,
+                                                 const Tw *__restrict__ twb, uint64_t cr1, Tw *ldstw)
+{
+    static_assert(contig_pair_mode(MODE) && mode_lazy(MODE), "the paired pass ends in the lazy modes' final reduction");
+    constexpr int R1 = LOGN - 8;
+    uint64_t *lds = reinterpret_cast<uint64_t *>(lds2);
+    uint64_t *__restrict__ baseA = rowA + ((size_t)tile << 12);
+    uint64_t *__restrict__ baseB = rowB + ((size_t)tile << 12);
+    const uint32_t b = tid >> 4;
+    const uint32_t tl = tid & 15u;
+    const Tw *__restrict__ twbt = twb + (size_t)tile * (15 * 256);
+
+    Tw fill;
+    uint32_t fill_slot = 0;
+    {
+        // as in fwd_contig_tile: lanes 60..63 repeat lane 59's load and store nothing
+        const uint32_t lane = tid & 63u;
+        const uint32_t l = lane < 59u ? lane : 59u;
+        const uint32_t bb = ((tid >> 6) << 2) + l / 15u, i = l % 15u;
+        const uint32_t u = i == 0 ? 0u : (i < 3 ? 1u : (i < 7 ? 2u : 3u)), k = i - ((1u << u) - 1u);
+        fill = tw[(1u << (R1 + u)) + (((tile << 4) + bb) << u) + k];
+        fill_slot = bb * 15u + i;
+    }
+    uint64_t xa[16], xb[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        xa[j] = baseA[(b << 8) | ((uint32_t)j << 4) | tl];
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        xb[j] = baseB[(b << 8) | ((uint32_t)j << 4) | tl];
+    }
+    if ((tid & 63u) < 60u)
+    {
+        ldstw[fill_slot] = fill;
+    }
+    lds_wave_sync();
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+    {
+        const int half = 8 >> u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+        {
+            const int j = ((i & ~(half - 1)) << 1) | (i & (half - 1)); // the i-th register index without the bit `half`
+            {
+                Tw t = ldstw[b * 15u + ((1u << u) - 1u) + (uint32_t)(j >> (4 - u))];
+                ct_bfly_stage<MODE, LOGN>(xa[j], xa[j + half], t.w, t.wq, q, q2, 7 - u);
+                ct_bfly_stage<MODE, LOGN>(xb[j], xb[j + half], t.w, t.wq, q, q2, 7 - u);
+            }
+        }
+    }
+    // the per-thread twiddles of the last four stages, slot s at twbt[s * 256 + tid]: the first ones arrive under the exchange
+    Tw tq[15];
+#pragma unroll
+    for (int s = 0; s < PAIR_TW_AHEAD; ++s)
+    {
+        tq[s] = twbt[((uint32_t)s << 8) + tid];
+    }
+    const uint32_t myrow = tid; // (b << 4) | th
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        lds[phys_contig((b << 8) | ((uint32_t)j << 4) | tl)] = xa[j];
+    }
+    lds_wave_sync();
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+    {
+        ulonglong2 v = lds2[(myrow << 3) | ((uint32_t)c ^ (myrow & 7u))];
+        xa[2 * c] = v.x;
+        xa[2 * c + 1] = v.y;
+    }
+    lds_wave_order(); // B's columns overwrite A's behind the reads of A's rows
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        lds[phys_contig((b << 8) | ((uint32_t)j << 4) | tl)] = xb[j];
+    }
+    lds_wave_sync();
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+    {
+        ulonglong2 v = lds2[(myrow << 3) | ((uint32_t)c ^ (myrow & 7u))];
+        xb[2 * c] = v.x;
+        xb[2 * c + 1] = v.y;
+    }
+#pragma unroll
+    for (int u = 4; u < 8; ++u)
+    {
+        const int half = 8 >> (u - 4);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+        {
+            const int j = ((i & ~(half - 1)) << 1) | (i & (half - 1)); // the i-th register index without the bit `half`
+            {
+                const int slot = (1 << (u - 4)) - 1 + (j >> (8 - u)); // used in ascending order
+                if ((j & ((1 << (8 - u)) - 1)) == 0)
+                {
+                    if (slot + PAIR_TW_AHEAD < 15)
+                    {
+                        tq[slot + PAIR_TW_AHEAD] = twbt[((uint32_t)(slot + PAIR_TW_AHEAD) << 8) + tid];
+                    }
+                }
+                const Tw t = tq[slot];
+                ct_bfly_stage<MODE, LOGN>(xa[j], xa[j + half], t.w, t.wq, q, q2, 7 - u);
+                ct_bfly_stage<MODE, LOGN>(xb[j], xb[j + half], t.w, t.wq, q, q2, 7 - u);
+                pair_fence(xa[j], xa[j + half], xb[j], xb[j + half]);
+            }
+        }
+    }
+    // per tile as in fwd_contig_tile: a thread's finished row to LDS, then every wave stores its own 8 KiB, 1 KiB per instruction.
+    // (An opaque copy of the thread index: the eight swizzled row slots are computed again here instead of staying in registers
+    // that the 64 values and the twiddles in flight need across the four stages above.)
+    uint32_t t2 = tid;
+    asm volatile("" : "+v"(t2));
+    const uint32_t wbase = (t2 >> 6) << 9, lane = t2 & 63u;
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+    {
+        if (p)
+        {
+            lds_wave_order(); // B's rows overwrite A's behind the reads of A's chunks
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+        {
+            ulonglong2 v;
+            v.x = lazy_final(p ? xb[2 * c] : xa[2 * c], q, cr1);
+            v.y = lazy_final(p ? xb[2 * c + 1] : xa[2 * c + 1], q, cr1);
+            lds2[(t2 << 3) | ((uint32_t)c ^ (t2 & 7u))] = v;
+        }
+        lds_wave_sync();
+        ulonglong2 *out = reinterpret_cast<ulonglong2 *>(p ? baseB : baseA);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+        {
+            const uint32_t ch = wbase + (uint32_t)i * 64u + lane;
+            const uint32_t rr = ch >> 3;
+            out[ch] = lds2[(rr << 3) | ((ch & 7u) ^ (rr & 7u))];
+        }
+    }
+}
+
+// polynomials 2p and 2p + 1 of the launch per workgroup; a.n_poly is even (the launcher gives an odd last polynomial to
+// ntt_fwd_contig), a.total_work = n_poly / 2 * Lsel * TPR.  The pair index runs fastest, as the polynomial does in ntt_fwd_contig.
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(256, 4) void ntt_fwd_contig2(NttArgs a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    __shared__ ulonglong2 lds2[2048 + 240];
+    const uint32_t pairs = a.n_poly >> 1;
+    const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t pol = (w % pairs) << 1;
+    const uint32_t rest = w / pairs;
+    const uint32_t tile = rest % TPR;
+    const uint32_t r = __builtin_amdgcn_readfirstlane(a.sel.idx[rest / TPR]);
+    const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[rest / TPR]);
+    const PrimeConst &pc = a.pc[prime];
+    uint64_t *rowA = a.data + (((size_t)pol * a.L + r) << LOGN);
+    fwd_contig_tile2<LOGN, MODE>(rowA, rowA + ((size_t)a.L << LOGN), tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc),
+                                      lds2, threadIdx.x, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), mode_fin<MODE>(pc),
+                                      reinterpret_cast<Tw *>(lds2 + 2048));
+}
+
 // =====================================================================================================
 // inverse, contiguous pass: stages LOGN-1 .. LOGN-8 (gap 1 .. 128); lazy [0,2q) out
 // =====================================================================================================
@@ -792,6 +1007,196 @@ __global__ __launch_bounds__(256) void ntt_inv_contig(NttArgs a)
     const uint64_t *srcp = a.src ? a.src + (((size_t)pol * a.src_stride + a.src_off + r) << LOGN) : nullptr;
     inv_contig_tile<LOGN, MODE>(a.data + (((size_t)pol * a.L + r) << LOGN), tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc),
                                 mode_q2<MODE>(pc), lds2, threadIdx.x, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), srcp);
+}
+
+// The same tile of two polynomials by one workgroup, every twiddle fetched once (fwd_contig_tile2 says why).  Both tiles' loads
+// are issued first and wait in registers; the fifteen per-thread twiddles are fetched behind the staging, where they are used
+// (inv_contig_tile holds all fifteen ahead of its tile, 60 registers, which do not fit beside 64 of data).  srcA / srcB (or
+// null): NttArgs::src's rows of the two polynomials.
+template <int LOGN, int MODE>
+__device__ __forceinline__ void inv_contig_tile2(uint64_t *rowA, uint64_t *rowB, uint32_t tile, const Tw *__restrict__ tw, uint64_t q,
+                                                 uint64_t q2, ulonglong2 *lds2, const uint32_t tid, const Tw *__restrict__ twb,
+                                                 const uint64_t *srcA, const uint64_t *srcB)
+{
+    static_assert(contig_pair_mode(MODE) && MODE == M_LAZY16, "the paired pass takes M_LAZY16's schedule");
+    constexpr int R1 = LOGN - 8;
+    uint64_t *lds = reinterpret_cast<uint64_t *>(lds2);
+    uint64_t *baseA = rowA + ((size_t)tile << 12);
+    uint64_t *baseB = rowB + ((size_t)tile << 12);
+    const uint32_t b = tid >> 4;
+    const uint32_t tl = tid & 15u;
+    const uint32_t blk = (tile << 4) + b;
+    const Tw *__restrict__ twbt = twb + (size_t)tile * (15 * 256);
+    constexpr Lazy16Inv z1 = lazy16_inv(4, 4, false), z2 = lazy16_inv(4, z1.out, false);
+    static_assert(z1.peak <= 16 && z2.peak <= 16, "a value of 16q or more");
+    static_assert(z2.out == lazy16_inv_handover(), "the strided pass starts from another bound");
+
+    const ulonglong2 *inA = reinterpret_cast<const ulonglong2 *>(srcA ? srcA + ((size_t)tile << 12) : baseA);
+    const ulonglong2 *inB = reinterpret_cast<const ulonglong2 *>(srcB ? srcB + ((size_t)tile << 12) : baseB);
+    const uint32_t wbase = (tid >> 6) << 9, lane = tid & 63u;
+    uint64_t ra[16], rb[16];
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+    {
+        const ulonglong2 v = inA[wbase + (uint32_t)it * 64u + lane];
+        ra[2 * it] = v.x;
+        ra[2 * it + 1] = v.y;
+    }
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+    {
+        const ulonglong2 v = inB[wbase + (uint32_t)it * 64u + lane];
+        rb[2 * it] = v.x;
+        rb[2 * it + 1] = v.y;
+    }
+    const uint32_t myrow = tid;
+    uint64_t xa[16], xb[16];
+    // every wave stages the 64 rows its own lanes transform, A's then B's
+    auto stage_in = [&](const uint64_t(&raw)[16], uint64_t(&x)[16]) {
+#pragma unroll
+        for (int it = 0; it < 8; ++it)
+        {
+            const uint32_t ch = wbase + (uint32_t)it * 64u + lane;
+            const uint32_t rr = ch >> 3;
+            ulonglong2 v;
+            v.x = raw[2 * it];
+            v.y = raw[2 * it + 1];
+            lds2[(rr << 3) | ((ch & 7u) ^ (rr & 7u))] = v;
+        }
+        lds_wave_sync();
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+        {
+            ulonglong2 v = lds2[(myrow << 3) | ((uint32_t)c ^ (myrow & 7u))];
+            x[2 * c] = v.x;
+            x[2 * c + 1] = v.y;
+        }
+    };
+    stage_in(ra, xa);
+    // the per-thread twiddles of the first four stages, slot s at twbt[s * 256 + tid]: the first ones arrive under B's staging
+    Tw tq[15];
+#pragma unroll
+    for (int k = 0; k < PAIR_TW_AHEAD; ++k)
+    {
+        tq[inv_slot_of_order(k)] = twbt[((uint32_t)inv_slot_of_order(k) << 8) + tid];
+    }
+    lds_wave_order(); // B's chunks overwrite A's behind the reads of A's rows
+    stage_in(rb, xb);
+#pragma unroll
+    for (int u = 7; u >= 4; --u)
+    {
+        const int half = 8 >> (u - 4);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+        {
+            const int j = ((i & ~(half - 1)) << 1) | (i & (half - 1)); // the i-th register index without the bit `half`
+            {
+                const int slot = (1 << (u - 4)) - 1 + (j >> (8 - u));
+                if ((j & ((1 << (8 - u)) - 1)) == 0)
+                {
+                    const int k = inv_order_of_slot(slot) + PAIR_TW_AHEAD;
+                    if (k < 15)
+                    {
+                        tq[inv_slot_of_order(k)] = twbt[((uint32_t)inv_slot_of_order(k) << 8) + tid];
+                    }
+                }
+                const Tw t = tq[slot];
+                gs_bfly_tile<MODE>(xa, j, half, t.w, t.wq, q, q2, false, z1.xk, 7 - u);
+                gs_bfly_tile<MODE>(xb, j, half, t.w, t.wq, q, q2, false, z1.xk, 7 - u);
+                pair_fence(xa[j], xa[j + half], xb[j], xb[j + half]);
+            }
+        }
+    }
+    // (an opaque copy of the thread index: the eight swizzled row slots are computed again instead of staying in registers
+    // across the four stages above)
+    uint32_t t2 = tid;
+    asm volatile("" : "+v"(t2));
+    // the last four stages' twiddles, shared by the sixteen threads of a block: slot s of stage u at tw[2^(R1+u) + blk * 2^u + k]
+    Tw ts[15];
+#pragma unroll
+    for (int k = 0; k < PAIR_TW_AHEAD; ++k)
+    {
+        const int sl = inv_slot_of_order(k), u = slot_stage(sl);
+        ts[sl] = tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(sl + 1 - (1 << u))];
+    }
+    // rows to columns, A's then B's (a row is private to its thread: nothing to wait for before it is written back)
+    auto transpose = [&](uint64_t(&x)[16]) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+        {
+            ulonglong2 v;
+            v.x = x[2 * c];
+            v.y = x[2 * c + 1];
+            lds2[(t2 << 3) | ((uint32_t)c ^ (t2 & 7u))] = v;
+        }
+        lds_wave_sync();
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+        {
+            x[j] = lds[phys_contig((b << 8) | ((uint32_t)j << 4) | tl)];
+        }
+    };
+    transpose(xa);
+    lds_wave_order(); // B's rows overwrite A's behind the reads of A's columns
+    transpose(xb);
+#pragma unroll
+    for (int u = 3; u >= 0; --u)
+    {
+        const int half = 8 >> u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+        {
+            const int j = ((i & ~(half - 1)) << 1) | (i & (half - 1)); // the i-th register index without the bit `half`
+            {
+                const int slot = (1 << u) - 1 + (j >> (4 - u));
+                if ((j & ((1 << (4 - u)) - 1)) == 0)
+                {
+                    const int k = inv_order_of_slot(slot) + PAIR_TW_AHEAD;
+                    if (k < 15)
+                    {
+                        const int sl = inv_slot_of_order(k), un = slot_stage(sl);
+                        ts[sl] = tw[(1u << (R1 + un)) + (blk << un) + (uint32_t)(sl + 1 - (1 << un))];
+                    }
+                }
+                const Tw t = ts[slot];
+                gs_bfly_tile<MODE>(xa, j, half, t.w, t.wq, q, q2, false, z2.xk, 3 - u);
+                gs_bfly_tile<MODE>(xb, j, half, t.w, t.wq, q, q2, false, z2.xk, 3 - u);
+                pair_fence(xa[j], xa[j + half], xb[j], xb[j + half]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        baseA[(b << 8) | ((uint32_t)j << 4) | tl] = xa[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+    {
+        baseB[(b << 8) | ((uint32_t)j << 4) | tl] = xb[j];
+    }
+}
+
+// polynomials 2p and 2p + 1 of the launch per workgroup; a.n_poly is even (the launcher gives an odd last polynomial to
+// ntt_inv_contig), a.total_work = n_poly / 2 * Lsel * TPR
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(256, 4) void ntt_inv_contig2(NttArgs a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    __shared__ ulonglong2 lds2[2048];
+    const uint32_t pairs = a.n_poly >> 1;
+    const uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t pol = (w % pairs) << 1;
+    const uint32_t rest = w / pairs;
+    const uint32_t tile = rest % TPR;
+    const uint32_t r = __builtin_amdgcn_readfirstlane(a.sel.idx[rest / TPR]);
+    const uint32_t prime = __builtin_amdgcn_readfirstlane(a.selp.idx[rest / TPR]);
+    const PrimeConst &pc = a.pc[prime];
+    const uint64_t *srcA = a.src ? a.src + (((size_t)pol * a.src_stride + a.src_off + r) << LOGN) : nullptr;
+    uint64_t *rowA = a.data + (((size_t)pol * a.L + r) << LOGN);
+    inv_contig_tile2<LOGN, MODE>(rowA, rowA + ((size_t)a.L << LOGN), tile, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc), lds2,
+                                 threadIdx.x, a.twb + (size_t)prime * ((size_t)TPR * 15 * 256), srcA,
+                                 srcA ? srcA + ((size_t)a.src_stride << LOGN) : nullptr);
 }
 
 // =====================================================================================================

@@ -2,8 +2,8 @@
 """Static instruction counts of the tiled NTT kernels (no GPU needed).
 
 Compiles csrc/ntt.hip to gfx950 assembly with the Makefile's flags and prints, for every
-ntt_{fwd,inv}_{strided,contig}<16, integer mode> kernel: vector-ALU instructions per thread and per butterfly (a thread
-does 64 butterflies per pass), v_mad_u64_u32 and how many of them multiply by a literal zero, v_mov_b32 (and how many copy
+ntt_{fwd,inv}_{strided,contig,contig2}<16, integer mode> kernel: vector-ALU instructions per thread and per butterfly (a thread
+does 64 butterflies per pass, 128 in the paired kernels ntt_*_contig2), global loads (instructions, and bytes per butterfly), v_mad_u64_u32 and how many of them multiply by a literal zero, v_mov_b32 (and how many copy
 one VGPR into another), VGPRs, scratch bytes and occupancy (waves per SIMD).  The kernels are straight-line code, so the
 static count is what a thread executes.
 
@@ -51,7 +51,7 @@ def parse(asm):
     for line in asm.split("\n"):
         m = re.match(r"^(\w+):", line)
         if m and m.group(1) in kernels:
-            cur = res[m.group(1)] = dict(valu=0, mad=0, mad0=0, mov=0, movvv=0, vgpr=None, scratch=None, occ=None)
+            cur = res[m.group(1)] = dict(valu=0, mad=0, mad0=0, mov=0, movvv=0, gload=0, gbytes=0, vgpr=None, scratch=None, occ=None)
             continue
         if cur is None:
             continue
@@ -63,6 +63,11 @@ def parse(asm):
             cur[{"NumVgprs": "vgpr", "ScratchSize": "scratch", "Occupancy": "occ"}[m.group(1)]] = int(m.group(2))
             if m.group(1) == "Occupancy":
                 cur = None
+            continue
+        m = re.match(r"global_load_(dwordx(\d)|dword|\w+)", s)
+        if m:
+            cur["gload"] += 1
+            cur["gbytes"] += 4 * int(m.group(2)) if m.group(2) else (4 if m.group(1) == "dword" else 0)
             continue
         if not s.startswith("v_"):
             continue
@@ -103,7 +108,7 @@ def main():
     names = demangle(sorted(res))
     rows = []
     for mangled, c in res.items():
-        m = re.search(r"moai::ntt_(fwd|inv)_(strided|contig)<16, (-?\d+)(?:, (-?\d+))?>", names[mangled])
+        m = re.search(r"moai::ntt_(fwd|inv)_(strided|contig2?)<16, (-?\d+)(?:, (-?\d+))?>", names[mangled])
         if not m or int(m.group(3)) not in MODES:
             continue
         mode = int(m.group(3))
@@ -112,11 +117,12 @@ def main():
     rows.sort(key=lambda r: r[:4])
     print("# static counts of the LOGN = 16 integer NTT kernels%s" % (" -- " + args.label if args.label else ""))
     print("# flags: " + " ".join(flags))
-    print("%-30s %-9s %6s %8s %5s %5s %5s %6s %5s %8s %4s" % ("kernel", "mode", "VALU", "per bfly", "mad64", "zero", "v_mov", "vgpr2v", "VGPR",
-                                                               "scratch", "occ"))
+    print("%-30s %-9s %6s %8s %5s %7s %5s %5s %5s %6s %5s %8s %4s" % ("kernel", "mode", "VALU", "per bfly", "gload", "B/bfly", "mad64", "zero", "v_mov",
+                                                                       "vgpr2v", "VGPR", "scratch", "occ"))
     for mode, _, _, name, c in rows:
-        print("%-30s %-9s %6d %8.2f %5d %5d %5d %6d %5d %8d %4d" % (name, MODES[mode], c["valu"], c["valu"] / BUTTERFLIES, c["mad"], c["mad0"],
-                                                                     c["mov"], c["movvv"], c["vgpr"], c["scratch"], c["occ"]))
+        bf = BUTTERFLIES * (2 if "contig2" in name else 1)
+        print("%-30s %-9s %6d %8.2f %5d %7.2f %5d %5d %5d %6d %5d %8d %4d" % (name, MODES[mode], c["valu"], c["valu"] / bf, c["gload"], c["gbytes"] / bf,
+                                                                               c["mad"], c["mad0"], c["mov"], c["movvv"], c["vgpr"], c["scratch"], c["occ"]))
     return 0
 
 
