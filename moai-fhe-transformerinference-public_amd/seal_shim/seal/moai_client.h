@@ -252,6 +252,94 @@ namespace seal
             return f;
         }
 
+        // The head of a seeded record: `count` polynomials of L rows, of which the stored half -- `words` 64-bit words, yet to be
+        // computed -- lies in a block of the record's own
+        inline wire::Record seeded_record_head(std::uint32_t kind, std::size_t count, std::size_t L, const parms_id_type &parms_id,
+                                               std::size_t words, const SEALContext &context)
+        {
+            wire::Record r;
+            r.kind = kind;
+            r.flags = wire::flag_ntt | wire::flag_seeded;
+            r.count = static_cast<std::uint32_t>(count);
+            r.L = static_cast<std::uint32_t>(L);
+            r.parms_id = parms_id;
+            r.block = std::make_shared<DeviceArray>(words, context.stream());
+            r.data = r.block->get();
+            return r;
+        }
+        // Takes `sequences` consecutive sequences of `rng` for the record and computes its stored half under the generator's seed
+        // kind.  ChaCha20: the record carries its first sequence and the public seed of that sequence, and seeded(seq) runs.
+        // SEAL's Blake2xb: the same sequences for the noise, one 64-byte SEAL seed per sequence for the uniform halves, and
+        // seal_seeded(seq, rejected) runs, with the device counters the record keeps until it is saved.
+        template <typename Seeded, typename SealSeeded>
+        inline void fill_seeded_record(wire::Record &r, DeviceRng &rng, std::size_t sequences, void *stream, Seeded seeded, SealSeeded seal_seeded)
+        {
+            const std::uint64_t seq = rng.take(sequences);
+            if (rng.get_seed_kind() == seed_kind::seal_blake2xb)
+            {
+                r.seal_seeds = seal_seeds(rng.key(), seq, sequences);
+                r.seal_flags = seal_flags(stream);
+                hip_check(seal_seeded(seq, reinterpret_cast<std::uint32_t *>(r.seal_flags->get())));
+                return;
+            }
+            r.seq = seq;
+            public_seed(rng.key(), r.seq, r.seed);
+            hip_check(seeded(seq));
+        }
+        // c0 of one symmetric encryption of `plain` (null: of zero) at L primes, seeded: a ciphertext, or the public key at the
+        // key level
+        inline wire::Record seeded_encryption(std::uint32_t kind, std::size_t L, const parms_id_type &parms_id, const std::uint64_t *sk_ntt,
+                                              const std::uint64_t *plain, DeviceRng &rng, const SEALContext &context)
+        {
+            wire::Record r = seeded_record_head(kind, 2, L, parms_id, L * context.n(), context);
+            std::uint64_t *c0 = r.block->get();
+            fill_seeded_record(
+                r, rng, 1, context.stream(),
+                [&](std::uint64_t seq) {
+                    return moai_encrypt_symmetric_seeded(context.device(), rng.key(), r.seed, seq, sk_ntt, plain, c0, 1, L, nullptr, context.stream());
+                },
+                [&](std::uint64_t seq, std::uint32_t *rejected) {
+                    return moai_encrypt_symmetric_seal_seeded(context.device(), rng.key(), r.seal_seeds.data(), seq, sk_ntt, plain, c0, 1, L, nullptr,
+                                                              rejected, context.stream());
+                });
+            return r;
+        }
+
+        // data primes of a key limited to chain index c, of k primes with the special one: c + 1, and the full k-1 from c = k-2 on
+        inline std::size_t levels_of(std::size_t chain_index, std::size_t k)
+        {
+            return chain_index >= k - 2 ? k - 1 : chain_index + 1;
+        }
+        // What a call generates: (slot, levels) per switching key; levels == k-1 is a whole key
+        using KeyPlan = std::vector<std::pair<std::uint64_t, std::size_t>>;
+        // The plan of a set of Galois keys at degree n: one entry per distinct element, in the order given; the first mention of
+        // an element counts.  chain_indices: null for whole keys, otherwise one entry per element or a single entry for all.
+        // Host arithmetic only: every element is checked here, before the first key is generated.
+        inline KeyPlan galois_key_plan(const std::vector<std::uint32_t> &galois_elts, const std::vector<std::size_t> *chain_indices, std::size_t n,
+                                       std::size_t k)
+        {
+            if (chain_indices && chain_indices->size() != 1 && chain_indices->size() != galois_elts.size())
+            {
+                throw std::invalid_argument("chain_indices must hold one entry, or one per Galois element");
+            }
+            KeyPlan plan;
+            for (std::size_t i = 0; i < galois_elts.size(); i++)
+            {
+                const std::uint32_t elt = galois_elts[i];
+                if (!(elt & 1) || elt >= 2 * n)
+                {
+                    throw std::invalid_argument("Galois element is not valid");
+                }
+                const std::uint64_t slot = (elt - 1) >> 1; // GaloisKeys::get_index
+                const bool seen = std::any_of(plan.begin(), plan.end(), [slot](const KeyPlan::value_type &p) { return p.first == slot; });
+                if (!seen)
+                {
+                    plan.emplace_back(slot, chain_indices ? levels_of((*chain_indices)[chain_indices->size() == 1 ? 0 : i], k) : k - 1);
+                }
+            }
+            return plan;
+        }
+
         // uniform residues [rows][N], row r under primes[r]
         inline void sample_uniform(const std::vector<std::uint64_t> &primes, std::size_t n, std::vector<std::uint64_t> &out)
         {
@@ -519,7 +607,7 @@ namespace seal
             // a full vector with one non-zero value at some slots and zero elsewhere -- MOAI's masked weights and biases
             // (Ct_pt_matrix_mul.hpp:124-146, single_att_block.hpp:33-42): recorded, not transformed (Plaintext::mask_).  Only when
             // the range check above cannot fail, so that every exception of the reference is still raised here and now.
-            if (!is_complex && conclusive && count == slots_ && masked_constants_enabled())
+            if (!is_complex && conclusive && count == slots_ && util::lazy_enabled())
             {
                 if (record_masked_constant(reinterpret_cast<const double *>(values), count, parms_id, scale, L, n, destination))
                 {
@@ -564,14 +652,6 @@ namespace seal
             destination.scale_ = scale;
         }
 
-        static bool masked_constants_enabled()
-        {
-            static const bool on = [] {
-                const char *e = std::getenv("MOAI_SHIM_LAZY");
-                return !(e && e[0] == '0');
-            }();
-            return on;
-        }
         // values = c * mask with mask in {0, 1}^slots and c != 0?  Then the plaintext records (mask, c, scale).  The mask's device
         // copy is shared by every plaintext with the same pattern this thread encodes in a row (MOAI encodes thousands per mask).
         bool record_masked_constant(const double *values, std::size_t count, parms_id_type parms_id, double scale, std::size_t L, std::size_t n,
@@ -782,12 +862,14 @@ namespace seal
         // relinearization key for s^2 (SEAL/keygenerator.cpp:129-168)
         void create_relin_keys(RelinKeys &destination)
         {
-            create_relin_keys_impl(destination, false);
+            generate_into(destination, relin_plan(k_ - 1), New::s_squared, Draw::host);
         }
-        // keys for the given Galois elements (SEAL/keygenerator.cpp:170-235)
+        // keys for the given Galois elements (SEAL/keygenerator.cpp:170-235), generated in the order given, an element
+        // mentioned again skipped.  Every element is checked before the first key is generated (util::galois_key_plan): a call
+        // that refuses one leaves the destination as it was and draws no randomness.
         void create_galois_keys(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination)
         {
-            create_galois_keys_impl(galois_elts, destination, false);
+            generate_into(destination, galois_plan(galois_elts, nullptr), New::rotated, Draw::host);
         }
 
         // ---- device key generation (opt-in, moai_fused::create_*; not part of the reference API) ------------------------
@@ -804,11 +886,11 @@ namespace seal
         }
         void create_relin_keys_device(RelinKeys &destination)
         {
-            create_relin_keys_impl(destination, true);
+            generate_into(destination, relin_plan(k_ - 1), New::s_squared, Draw::device);
         }
         void create_galois_keys_device(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination)
         {
-            create_galois_keys_impl(galois_elts, destination, true);
+            generate_into(destination, galois_plan(galois_elts, nullptr), New::rotated, Draw::device);
         }
         // ---- seeded keys for the wire (SEAL/keygenerator.h:92-118, 138-160, 190-300: the overloads without a destination) ----
         // c0 of every key digit from moai_kswitch_keygen_seeded and the public seed of the key; the uniform halves are drawn
@@ -817,49 +899,18 @@ namespace seal
         Serializable<PublicKey> create_public_key() const
         {
             wire::Object o = seeded_object(wire::kind_public_key);
-            o.head = seeded_record(wire::kind_public_key, nullptr);
+            o.head = util::seeded_encryption(wire::kind_public_key, k_, context_.key_parms_id(), sk_.ntt_->get(), nullptr, *rng_, context_);
             context_.sync();
             return Serializable<PublicKey>(std::move(o));
         }
         Serializable<RelinKeys> create_relin_keys()
         {
-            require_keyswitching();
-            util::DeviceArray s2(k_ * n_, context_.stream());
-            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
-                                            context_.stream()));
-            wire::Object o = seeded_object(wire::kind_relin_keys);
-            o.indices.push_back(0);
-            o.keys.push_back(seeded_record(wire::kind_kswitch_key, s2.get()));
-            o.head.count = 1;
-            context_.sync();
-            return Serializable<RelinKeys>(std::move(o));
+            return Serializable<RelinKeys>(generate_seeded(relin_plan(k_ - 1), New::s_squared, Seeds::either));
         }
+        // the keys in the order of their slots, as a saved set holds them
         Serializable<GaloisKeys> create_galois_keys(const std::vector<std::uint32_t> &galois_elts)
         {
-            require_keyswitching();
-            std::vector<std::uint64_t> idx;
-            for (std::uint32_t elt : galois_elts)
-            {
-                if (!(elt & 1) || elt >= 2 * n_)
-                {
-                    throw std::invalid_argument("Galois element is not valid");
-                }
-                idx.push_back(GaloisKeys::get_index(elt));
-            }
-            std::sort(idx.begin(), idx.end());
-            idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-            wire::Object o = seeded_object(wire::kind_galois_keys);
-            util::DeviceArray rotated(k_ * n_, context_.stream());
-            for (std::uint64_t i : idx)
-            {
-                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
-                                                    static_cast<std::uint32_t>(2 * i + 1), context_.stream()));
-                o.indices.push_back(i);
-                o.keys.push_back(seeded_record(wire::kind_kswitch_key, rotated.get()));
-            }
-            o.head.count = static_cast<std::uint32_t>(o.keys.size());
-            context_.sync();
-            return Serializable<GaloisKeys>(std::move(o));
+            return Serializable<GaloisKeys>(generate_seeded(by_slot(galois_plan(galois_elts, nullptr)), New::rotated, Seeds::either));
         }
         Serializable<GaloisKeys> create_galois_keys(const std::vector<int> &steps)
         {
@@ -877,63 +928,24 @@ namespace seal
         // have produced in full.  chain_indices: one entry per element, or a single entry for all.
         Serializable<RelinKeys> create_relin_keys_limited(std::size_t chain_index)
         {
-            require_keyswitching();
-            util::DeviceArray s2(k_ * n_, context_.stream());
-            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
-                                            context_.stream()));
-            wire::Object o = seeded_object(wire::kind_relin_keys);
-            o.indices.push_back(0);
-            o.keys.push_back(seeded_key_record(s2.get(), levels_of(chain_index)));
-            o.head.count = 1;
-            context_.sync();
-            return Serializable<RelinKeys>(std::move(o));
+            return Serializable<RelinKeys>(generate_seeded(relin_plan(util::levels_of(chain_index, k_)), New::s_squared, Seeds::chacha20_only));
         }
+        // the first mention of an element decides its levels; then the keys in the order of their slots, as create_galois_keys writes them
         Serializable<GaloisKeys> create_galois_keys_limited(const std::vector<std::uint32_t> &galois_elts,
                                                             const std::vector<std::size_t> &chain_indices)
         {
-            require_keyswitching();
-            // slot -> levels, in the order of the slots as create_galois_keys writes them; the first mention of an element counts
-            std::vector<std::pair<std::uint64_t, std::size_t>> slots = limited_slots(galois_elts, chain_indices);
-            std::stable_sort(slots.begin(), slots.end(), [](const std::pair<std::uint64_t, std::size_t> &a,
-                                                            const std::pair<std::uint64_t, std::size_t> &b) { return a.first < b.first; });
-            wire::Object o = seeded_object(wire::kind_galois_keys);
-            util::DeviceArray rotated(k_ * n_, context_.stream());
-            for (auto &sl : slots)
-            {
-                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
-                                                    static_cast<std::uint32_t>(2 * sl.first + 1), context_.stream()));
-                o.indices.push_back(sl.first);
-                o.keys.push_back(seeded_key_record(rotated.get(), sl.second));
-            }
-            o.head.count = static_cast<std::uint32_t>(o.keys.size());
-            context_.sync();
-            return Serializable<GaloisKeys>(std::move(o));
+            return Serializable<GaloisKeys>(generate_seeded(by_slot(galois_plan(galois_elts, &chain_indices)), New::rotated, Seeds::chacha20_only));
         }
-        // the same into a destination, drawn on the device like moai_fused::create_*_keys (a and e from the generator's one key)
+        // the same into a destination, drawn on the device like moai_fused::create_*_keys (a and e from the generator's one key),
+        // in the order given
         void create_relin_keys_limited_device(std::size_t chain_index, RelinKeys &destination)
         {
-            require_keyswitching();
-            util::DeviceArray s2(k_ * n_, context_.stream());
-            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
-                                            context_.stream()));
-            reset_set(destination, 1);
-            put_key_device(destination, 0, s2.get(), levels_of(chain_index));
-            context_.sync();
+            generate_into(destination, relin_plan(util::levels_of(chain_index, k_)), New::s_squared, Draw::device);
         }
         void create_galois_keys_limited_device(const std::vector<std::uint32_t> &galois_elts, const std::vector<std::size_t> &chain_indices,
                                                GaloisKeys &destination)
         {
-            require_keyswitching();
-            const std::vector<std::pair<std::uint64_t, std::size_t>> slots = limited_slots(galois_elts, chain_indices);
-            reset_set(destination, n_);
-            util::DeviceArray rotated(k_ * n_, context_.stream());
-            for (auto &sl : slots)
-            {
-                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_,
-                                                    static_cast<std::uint32_t>(2 * sl.first + 1), context_.stream()));
-                put_key_device(destination, sl.first, rotated.get(), sl.second);
-            }
-            context_.sync();
+            generate_into(destination, galois_plan(galois_elts, &chain_indices), New::rotated, Draw::device);
         }
         // the randomness of the device paths (a fresh OS-keyed one by default)
         void set_device_rng(std::shared_ptr<util::DeviceRng> rng)
@@ -1014,87 +1026,6 @@ namespace seal
                 throw std::logic_error("keyswitching is not supported by the context");
             }
         }
-        // data primes of a key limited to chain index c: c + 1, and the full k-1 from c = k-2 on
-        std::size_t levels_of(std::size_t chain_index) const
-        {
-            return chain_index >= k_ - 2 ? k_ - 1 : chain_index + 1;
-        }
-        // (slot, levels) per distinct Galois element, in the order given
-        std::vector<std::pair<std::uint64_t, std::size_t>> limited_slots(const std::vector<std::uint32_t> &galois_elts,
-                                                                         const std::vector<std::size_t> &chain_indices) const
-        {
-            if (chain_indices.size() != 1 && chain_indices.size() != galois_elts.size())
-            {
-                throw std::invalid_argument("chain_indices must hold one entry, or one per Galois element");
-            }
-            std::vector<std::pair<std::uint64_t, std::size_t>> slots;
-            for (std::size_t i = 0; i < galois_elts.size(); i++)
-            {
-                const std::uint32_t elt = galois_elts[i];
-                if (!(elt & 1) || elt >= 2 * n_)
-                {
-                    throw std::invalid_argument("Galois element is not valid");
-                }
-                const std::uint64_t slot = GaloisKeys::get_index(elt);
-                bool seen = false;
-                for (auto &s : slots)
-                {
-                    seen = seen || s.first == slot;
-                }
-                if (!seen)
-                {
-                    slots.emplace_back(slot, levels_of(chain_indices[chain_indices.size() == 1 ? 0 : i]));
-                }
-            }
-            return slots;
-        }
-        // c0 of a key's digits: the whole key (record kind 9) at levels == k-1, otherwise the limited one (kind 10)
-        wire::Record seeded_key_record(const std::uint64_t *new_key_ntt, std::size_t levels) const
-        {
-            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
-            {
-                throw std::logic_error("a key limited to a chain index has no form in SEAL's format: generate it under seed_kind::chacha20");
-            }
-            if (levels == k_ - 1)
-            {
-                return seeded_record(wire::kind_kswitch_key, new_key_ntt);
-            }
-            wire::Record r;
-            r.kind = wire::kind_kswitch_key_limited;
-            r.flags = wire::flag_ntt | wire::flag_seeded;
-            r.count = static_cast<std::uint32_t>(2 * levels);
-            r.L = static_cast<std::uint32_t>(levels + 1);
-            r.parms_id = context_.key_parms_id();
-            r.seq = rng_->take(k_ - 1);
-            util::public_seed(rng_->key(), r.seq, r.seed);
-            r.block = std::make_shared<util::DeviceArray>(levels * (levels + 1) * n_, context_.stream());
-            util::hip_check(moai_kswitch_keygen_limited_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), new_key_ntt,
-                                                               levels, r.block->get(), context_.stream()));
-            r.data = r.block->get();
-            return r;
-        }
-        // an empty set of `slots` slots with caches and residency of its own
-        void reset_set(KSwitchKeys &destination, std::size_t slots) const
-        {
-            destination.keys_.assign(slots, nullptr);
-            destination.hoist_ = std::make_shared<KSwitchKeys::HoistCache>();
-            destination.res_.reset();
-            destination.generation_ = KSwitchKeys::next_generation();
-            destination.parms_id_ = context_.key_parms_id();
-        }
-        void put_key_device(KSwitchKeys &destination, std::size_t slot, const std::uint64_t *new_key_ntt, std::size_t levels) const
-        {
-            if (levels == k_ - 1)
-            {
-                destination.keys_[slot] = make_kswitch_key_device(new_key_ntt);
-                return;
-            }
-            auto key = wire::limited_key_block(context_, levels);
-            util::hip_check(moai_kswitch_keygen_limited(context_.device(), rng_->key(), rng_->take(k_ - 1), sk_.ntt_->get(), new_key_ntt, levels,
-                                                        key->get(), context_.stream()));
-            destination.keys_[slot] = key;
-            destination.mark_born_limited(context_, slot, levels);
-        }
         wire::Object seeded_object(std::uint32_t kind) const
         {
             wire::Object o;
@@ -1107,106 +1038,119 @@ namespace seal
             o.head.parms_id = context_.key_parms_id();
             return o;
         }
-        // new_key_ntt == null: an encryption of zero at the key level (the public key); otherwise the k-1 digits of a switching key
-        wire::Record seeded_record(std::uint32_t kind, const std::uint64_t *new_key_ntt) const
+
+        // ---- switching keys: every create_*_keys member is a plan (what to generate, in which order), a new key per slot and
+        // a place for the finished key.  The order of a plan is the order in which its keys take their sequences of the device
+        // generator: k-1 per key, limited or not. ------------------------------------------------------------------------------
+        enum class New
         {
-            const std::size_t count = new_key_ntt ? k_ - 1 : 1;
-            wire::Record r;
-            r.kind = kind;
-            r.flags = wire::flag_ntt | wire::flag_seeded;
-            r.count = static_cast<std::uint32_t>(2 * count);
-            r.L = static_cast<std::uint32_t>(k_);
-            r.parms_id = context_.key_parms_id();
-            r.block = std::make_shared<util::DeviceArray>(count * k_ * n_, context_.stream());
-            r.data = r.block->get();
-            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
-            {
-                // the same sequences for the noise; a of digit J from the SEAL seed of sequence seq + J
-                const std::uint64_t seq = rng_->take(count);
-                r.seal_seeds = util::seal_seeds(rng_->key(), seq, count);
-                r.seal_flags = util::seal_flags(context_.stream());
-                std::uint32_t *rejected = reinterpret_cast<std::uint32_t *>(r.seal_flags->get());
-                if (new_key_ntt)
-                {
-                    util::hip_check(moai_kswitch_keygen_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq, sk_.ntt_->get(),
-                                                                    new_key_ntt, r.block->get(), rejected, context_.stream()));
-                }
-                else
-                {
-                    util::hip_check(moai_encrypt_symmetric_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq,
-                                                                       sk_.ntt_->get(), nullptr, r.block->get(), 1, k_, nullptr, rejected,
-                                                                       context_.stream()));
-                }
-                return r;
-            }
-            r.seq = rng_->take(count);
-            util::public_seed(rng_->key(), r.seq, r.seed);
-            if (new_key_ntt)
-            {
-                util::hip_check(moai_kswitch_keygen_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), new_key_ntt,
-                                                           r.block->get(), context_.stream()));
-            }
-            else
-            {
-                util::hip_check(moai_encrypt_symmetric_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_.ntt_->get(), nullptr,
-                                                              r.block->get(), 1, k_, nullptr, context_.stream()));
-            }
-            r.data = r.block->get();
-            return r;
+            s_squared, // the relinearization key: slot 0 switches from s^2
+            rotated    // Galois keys: slot i switches from s under the element 2 i + 1
+        };
+        enum class Draw
+        {
+            host,  // the reference's construction with host randomness (make_kswitch_key)
+            device // moai_kswitch_keygen / moai_kswitch_keygen_limited with util::DeviceRng randomness
+        };
+        enum class Seeds
+        {
+            either,       // whichever kind the device generator is set to
+            chacha20_only // the members that limit keys: SEAL's format has no limited key
+        };
+        util::KeyPlan relin_plan(std::size_t levels) const
+        {
+            require_keyswitching();
+            return util::KeyPlan{ { 0, levels } };
         }
-        void create_relin_keys_impl(RelinKeys &destination, bool device)
+        util::KeyPlan galois_plan(const std::vector<std::uint32_t> &galois_elts, const std::vector<std::size_t> *chain_indices) const
         {
-            if (!context_.using_keyswitching())
+            require_keyswitching();
+            return util::galois_key_plan(galois_elts, chain_indices, n_, k_);
+        }
+        static util::KeyPlan by_slot(util::KeyPlan plan)
+        {
+            std::stable_sort(plan.begin(), plan.end(),
+                             [](const util::KeyPlan::value_type &a, const util::KeyPlan::value_type &b) { return a.first < b.first; });
+            return plan;
+        }
+        // walks a plan: sink(slot, levels, new_key_ntt) with the new key [k][N] of each slot in turn
+        template <typename Sink>
+        void generate(const util::KeyPlan &plan, New what, Sink sink) const
+        {
+            util::DeviceArray new_key(k_ * n_, context_.stream());
+            if (what == New::s_squared)
             {
-                throw std::logic_error("keyswitching is not supported by the context");
+                util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), new_key.get(), 1, 1, k_,
+                                                context_.stream()));
             }
-            util::DeviceArray s2(k_ * n_, context_.stream());
-            util::hip_check(moai_dyadic_mul(context_.device(), sk_.ntt_->get(), sk_.ntt_->get(), s2.get(), 1, 1, k_,
-                                            context_.stream()));
-            destination.keys_.assign(1, nullptr);
-            destination.hoist_ = std::make_shared<KSwitchKeys::HoistCache>(); // constants derived from the keys this call replaces
-            destination.generation_ = KSwitchKeys::next_generation();
-            destination.keys_[0] = device ? make_kswitch_key_device(s2.get()) : make_kswitch_key(s2.get());
-            destination.parms_id_ = context_.key_parms_id();
+            for (const auto &p : plan)
+            {
+                if (what == New::rotated)
+                {
+                    util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), new_key.get(), 1, k_,
+                                                        static_cast<std::uint32_t>(2 * p.first + 1), context_.stream()));
+                }
+                sink(p.first, p.second, new_key.get());
+            }
             context_.sync();
         }
-        void create_galois_keys_impl(const std::vector<std::uint32_t> &galois_elts, GaloisKeys &destination, bool device)
+        // the plan's keys replace the set in `destination` (KSwitchKeys::reset: with it go the hoisting constants and the
+        // residency record of the keys it held)
+        void generate_into(KSwitchKeys &destination, const util::KeyPlan &plan, New what, Draw draw) const
         {
-            if (!context_.using_keyswitching())
-            {
-                throw std::logic_error("keyswitching is not supported by the context");
-            }
-            destination.keys_.assign(n_, nullptr);
-            // the hoisted-rotation constants are functions of the key (KSwitchKeys::hoist_correction): regenerating keys into an
-            // object that already served hoisted rotations must not leave the old keys' constants behind.  A copy made earlier
-            // keeps the old keys together with the old cache; copies made from now on share the new one.
-            destination.hoist_ = std::make_shared<KSwitchKeys::HoistCache>();
-            destination.generation_ = KSwitchKeys::next_generation();
-            util::DeviceArray rotated(k_ * n_, context_.stream());
-            for (std::uint32_t elt : galois_elts)
-            {
-                if (!(elt & 1) || elt >= 2 * n_)
+            destination.reset(what == New::s_squared ? 1 : n_, context_.key_parms_id());
+            generate(plan, what, [&](std::size_t slot, std::size_t levels, const std::uint64_t *new_key_ntt) {
+                if (draw == Draw::host)
                 {
-                    throw std::invalid_argument("Galois element is not valid");
+                    destination.keys_[slot] = make_kswitch_key(new_key_ntt);
+                    return;
                 }
-                if (destination.keys_[GaloisKeys::get_index(elt)])
+                // all digits in one chain of launches; a key limited below k-1 levels in the trimmed layout, with no full key behind it
+                const bool whole = levels == k_ - 1;
+                auto key = whole ? std::make_shared<util::DeviceArray>((k_ - 1) * 2 * k_ * n_, context_.stream()) : wire::limited_key_block(context_, levels);
+                const std::uint64_t seq = rng_->take(k_ - 1);
+                util::hip_check(whole ? moai_kswitch_keygen(context_.device(), rng_->key(), seq, sk_.ntt_->get(), new_key_ntt, key->get(), context_.stream())
+                                      : moai_kswitch_keygen_limited(context_.device(), rng_->key(), seq, sk_.ntt_->get(), new_key_ntt, levels,
+                                                                    key->get(), context_.stream()));
+                destination.keys_[slot] = key;
+                if (!whole)
                 {
-                    continue;
+                    destination.mark_born_limited(context_, slot, levels);
                 }
-                util::hip_check(moai_galois_permute(context_.device(), sk_.ntt_->get(), rotated.get(), 1, k_, elt,
-                                                    context_.stream()));
-                destination.keys_[GaloisKeys::get_index(elt)] = device ? make_kswitch_key_device(rotated.get()) : make_kswitch_key(rotated.get());
-            }
-            destination.parms_id_ = context_.key_parms_id();
-            context_.sync();
+            });
         }
-        // moai_kswitch_keygen: all k-1 digits in one chain of launches
-        std::shared_ptr<util::DeviceArray> make_kswitch_key_device(const std::uint64_t *new_key_ntt) const
+        // the plan's keys as a seeded set for the wire: c0 of every digit, the whole key (record kind 9) at levels == k-1, otherwise
+        // the limited one (kind 10)
+        wire::Object generate_seeded(const util::KeyPlan &plan, New what, Seeds seeds) const
         {
-            auto key = std::make_shared<util::DeviceArray>((k_ - 1) * 2 * k_ * n_, context_.stream());
-            util::hip_check(moai_kswitch_keygen(context_.device(), rng_->key(), rng_->take(k_ - 1), sk_.ntt_->get(), new_key_ntt,
-                                                key->get(), context_.stream()));
-            return key;
+            wire::Object o = seeded_object(what == New::s_squared ? wire::kind_relin_keys : wire::kind_galois_keys);
+            generate(plan, what, [&](std::size_t slot, std::size_t levels, const std::uint64_t *new_key_ntt) {
+                if (seeds == Seeds::chacha20_only && rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
+                {
+                    throw std::logic_error("a key limited to a chain index has no form in SEAL's format: generate it under seed_kind::chacha20");
+                }
+                const bool whole = levels == k_ - 1;
+                wire::Record r = util::seeded_record_head(whole ? wire::kind_kswitch_key : wire::kind_kswitch_key_limited, 2 * levels, levels + 1,
+                                                          context_.key_parms_id(), levels * (levels + 1) * n_, context_);
+                std::uint64_t *c0 = r.block->get();
+                util::fill_seeded_record(
+                    r, *rng_, k_ - 1, context_.stream(),
+                    [&](std::uint64_t seq) {
+                        return whole ? moai_kswitch_keygen_seeded(context_.device(), rng_->key(), r.seed, seq, sk_.ntt_->get(), new_key_ntt, c0,
+                                                                  context_.stream())
+                                     : moai_kswitch_keygen_limited_seeded(context_.device(), rng_->key(), r.seed, seq, sk_.ntt_->get(), new_key_ntt,
+                                                                          levels, c0, context_.stream());
+                    },
+                    // whole keys only: a of digit J from the SEAL seed of sequence seq + J
+                    [&](std::uint64_t seq, std::uint32_t *rejected) {
+                        return moai_kswitch_keygen_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq, sk_.ntt_->get(), new_key_ntt,
+                                                               c0, rejected, context_.stream());
+                    });
+                o.indices.push_back(slot);
+                o.keys.push_back(std::move(r));
+            });
+            o.head.count = static_cast<std::uint32_t>(o.keys.size());
+            return o;
         }
         void upload_ntt(const std::vector<std::uint64_t> &rns, util::DeviceArray &dst, std::size_t rows) const
         {
@@ -1322,18 +1266,12 @@ namespace seal
         // Encryptor::encrypt_symmetric (SEAL/encryptor.h:337-372, encryptor.cpp:88-120): one moai_encrypt_symmetric launch chain
         void encrypt_symmetric(const Plaintext &plain, Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
         {
-            auto cd = context_.get_context_data(plain.parms_id());
-            if (!cd || !plain.is_ntt_form())
-            {
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
-            const std::size_t L = cd->parms().coeff_modulus().size();
-            const std::uint64_t *p = plain.is_scalar() ? nullptr : plain.device_data();
-            encrypt_symmetric_device(plain.parms_id(), p, destination);
+            const std::size_t L = check_plain(plain);
+            // a vector plaintext goes into the encryption call; only constant rows are added afterwards
+            encrypt_symmetric_device(plain.parms_id(), plain.is_scalar() ? nullptr : plain.device_data(), destination);
             if (plain.is_scalar())
             {
-                util::hip_check(moai_add_scalar_rows(context_.device(), destination.device_data(), plain.scalar_rows().data(),
-                                                     destination.device_data(), 1, L, context_.stream()));
+                add_plain(destination.device_data(), plain, L);
             }
             destination.scale() = plain.scale();
             context_.sync();
@@ -1351,17 +1289,11 @@ namespace seal
         // c0 from moai_encrypt_symmetric_seeded and the public seed; c1 is drawn where the ciphertext is loaded
         Serializable<Ciphertext> encrypt_symmetric(const Plaintext &plain, MemoryPoolHandle = MemoryPoolHandle()) const
         {
-            auto cd = context_.get_context_data(plain.parms_id());
-            if (!cd || !plain.is_ntt_form())
-            {
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
-            const std::size_t L = cd->parms().coeff_modulus().size();
+            const std::size_t L = check_plain(plain);
             wire::Object o = seeded_ciphertext(plain.parms_id(), plain.is_scalar() ? nullptr : plain.device_data());
             if (plain.is_scalar())
             {
-                util::hip_check(moai_add_scalar_rows(context_.device(), o.head.block->get(), plain.scalar_rows().data(), o.head.block->get(),
-                                                     1, L, context_.stream()));
+                add_plain(o.head.block->get(), plain, L);
             }
             o.head.scale = plain.scale();
             context_.sync();
@@ -1409,41 +1341,22 @@ namespace seal
         // restricted to the plaintext's primes -- a fresh RLWE encryption either way)
         void encrypt(const Plaintext &plain, Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
         {
-            auto cd = context_.get_context_data(plain.parms_id());
-            if (!cd || !plain.is_ntt_form())
-            {
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
+            const std::size_t L = check_plain(plain);
             encrypt_zero(plain.parms_id(), destination);
-            const std::size_t L = cd->parms().coeff_modulus().size();
-            if (plain.is_scalar())
-            {
-                util::hip_check(moai_add_scalar_rows(context_.device(), destination.device_data(), plain.scalar_rows().data(),
-                                                     destination.device_data(), 1, L, context_.stream()));
-            }
-            else
-            {
-                util::hip_check(moai_add(context_.device(), destination.device_data(), plain.device_data(),
-                                         destination.device_data(), 1, L, context_.stream()));
-            }
+            add_plain(destination.device_data(), plain, L);
             destination.scale() = plain.scale();
         }
         void encrypt_zero(parms_id_type parms_id, Ciphertext &destination, MemoryPoolHandle = MemoryPoolHandle()) const
         {
-            auto cd = context_.get_context_data(parms_id);
-            if (!cd)
-            {
-                throw std::invalid_argument("parms_id is not valid for encryption parameters");
-            }
+            const std::size_t L = level_of(parms_id), n = context_.n();
             if (!pk_.size())
             {
                 throw std::logic_error("public key is not set");
             }
-            const auto &cm = cd->parms().coeff_modulus();
-            const std::size_t L = cm.size(), n = context_.n();
             const std::size_t k = context_.key_context_data()->parms().coeff_modulus().size();
+            const auto cd = context_.get_context_data(parms_id);
             std::vector<std::uint64_t> primes;
-            for (auto &m : cm)
+            for (auto &m : cd->parms().coeff_modulus())
             {
                 primes.push_back(m.value());
             }
@@ -1484,63 +1397,58 @@ namespace seal
         }
 
     private:
-        wire::Object seeded_ciphertext(parms_id_type parms_id, const std::uint64_t *plain) const
+        // the number of primes at parms_id
+        std::size_t level_of(const parms_id_type &parms_id) const
         {
             auto cd = context_.get_context_data(parms_id);
             if (!cd)
             {
                 throw std::invalid_argument("parms_id is not valid for encryption parameters");
             }
+            return cd->parms().coeff_modulus().size();
+        }
+        const std::uint64_t *require_secret_key() const
+        {
             if (!sk_)
             {
                 throw std::logic_error("secret key is not set");
             }
-            const std::size_t L = cd->parms().coeff_modulus().size();
+            return sk_->get();
+        }
+        // the number of primes of a plaintext that can be encrypted
+        std::size_t check_plain(const Plaintext &plain) const
+        {
+            auto cd = context_.get_context_data(plain.parms_id());
+            if (!cd || !plain.is_ntt_form())
+            {
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+            }
+            return cd->parms().coeff_modulus().size();
+        }
+        // dst [L][N] += plain: its constant rows, or its vector
+        void add_plain(std::uint64_t *dst, const Plaintext &plain, std::size_t L) const
+        {
+            util::hip_check(plain.is_scalar() ? moai_add_scalar_rows(context_.device(), dst, plain.scalar_rows().data(), dst, 1, L, context_.stream())
+                                              : moai_add(context_.device(), dst, plain.device_data(), dst, 1, L, context_.stream()));
+        }
+        wire::Object seeded_ciphertext(parms_id_type parms_id, const std::uint64_t *plain) const
+        {
+            const std::size_t L = level_of(parms_id);
             wire::Object o;
             o.dev = context_.device();
             o.stream = context_.stream();
-            wire::Record &r = o.head;
-            r.kind = wire::kind_ciphertext;
-            r.flags = wire::flag_ntt | wire::flag_seeded;
-            r.count = 2;
-            r.L = static_cast<std::uint32_t>(L);
-            r.parms_id = parms_id;
-            r.block = std::make_shared<util::DeviceArray>(L * context_.n(), context_.stream());
-            r.data = r.block->get();
-            if (rng_->get_seed_kind() == util::seed_kind::seal_blake2xb)
-            {
-                const std::uint64_t seq = rng_->take(1);
-                r.seal_seeds = util::seal_seeds(rng_->key(), seq, 1);
-                r.seal_flags = util::seal_flags(context_.stream());
-                util::hip_check(moai_encrypt_symmetric_seal_seeded(context_.device(), rng_->key(), r.seal_seeds.data(), seq, sk_->get(), plain,
-                                                                   r.block->get(), 1, L, nullptr,
-                                                                   reinterpret_cast<std::uint32_t *>(r.seal_flags->get()), context_.stream()));
-                return o;
-            }
-            r.seq = rng_->take(1);
-            util::public_seed(rng_->key(), r.seq, r.seed);
-            util::hip_check(moai_encrypt_symmetric_seeded(context_.device(), rng_->key(), r.seed, r.seq, sk_->get(), plain, r.block->get(),
-                                                          1, L, nullptr, context_.stream()));
-            r.data = r.block->get();
+            o.head = util::seeded_encryption(wire::kind_ciphertext, L, parms_id, require_secret_key(), plain, *rng_, context_);
             return o;
         }
         void encrypt_symmetric_device(parms_id_type parms_id, const std::uint64_t *plain, Ciphertext &destination) const
         {
-            auto cd = context_.get_context_data(parms_id);
-            if (!cd)
-            {
-                throw std::invalid_argument("parms_id is not valid for encryption parameters");
-            }
-            if (!sk_)
-            {
-                throw std::logic_error("secret key is not set");
-            }
-            const std::size_t L = cd->parms().coeff_modulus().size();
+            const std::size_t L = level_of(parms_id);
+            const std::uint64_t *sk = require_secret_key();
             destination.resize(context_, parms_id, 2);
             destination.is_ntt_form() = true;
             destination.scale() = 1.0;
-            util::hip_check(moai_encrypt_symmetric(context_.device(), rng_->key(), rng_->take(1), sk_->get(), plain,
-                                                   destination.device_data(), 1, L, nullptr, context_.stream()));
+            util::hip_check(moai_encrypt_symmetric(context_.device(), rng_->key(), rng_->take(1), sk, plain, destination.device_data(), 1, L, nullptr,
+                                                   context_.stream()));
         }
 
         SEALContext context_;

@@ -150,7 +150,7 @@ namespace seal
                 throw std::invalid_argument("encrypted1 and encrypted2 pack different numbers of ciphertexts");
             }
             const std::size_t L = encrypted1.coeff_modulus_size(), B = encrypted1.batch();
-            if (size1 == 2 && size2 == 2 && B == 1 && &encrypted1 != &encrypted2 && lazy_products())
+            if (size1 == 2 && size2 == 2 && B == 1 && &encrypted1 != &encrypted2 && util::lazy_enabled())
             {
                 // not computed now: the product is recorded as (block, block) and summed with the products add_inplace brings
                 // (Ciphertext::LazyTerm::src2; MOAI's ct x ct loops, Ct_ct_matrix_mul.hpp:32-41, 121-134); a square is always eager
@@ -534,7 +534,7 @@ namespace seal
                 throw std::invalid_argument("scale out of bounds");
             }
             const std::size_t L = encrypted.coeff_modulus_size();
-            if (&destination != &encrypted && plain.is_scalar() && encrypted.batch() == 1 && encrypted.size() == 2 && lazy_products())
+            if (&destination != &encrypted && plain.is_scalar() && encrypted.batch() == 1 && encrypted.size() == 2 && util::lazy_enabled())
             {
                 // not computed now: the destination records (block of the operand, the plaintext's constant rows); see
                 // Ciphertext::LazyTerm.  Everything that can throw has been checked above, as in the eager path.
@@ -555,7 +555,7 @@ namespace seal
                 return;
             }
             if (&destination != &encrypted && !plain.is_scalar() && plain.is_masked_constant() && encrypted.batch() == 1 && encrypted.size() == 2 &&
-                lazy_products())
+                util::lazy_enabled())
             {
                 // a masked-constant vector plaintext whose transform has not been made: the product is recorded with the
                 // plaintext's (mask, constant, scale); the transforms of a whole chain are made together (Ciphertext::materialize)
@@ -958,14 +958,6 @@ namespace seal
             }();
             (void)once;
         }
-        static bool lazy_products()
-        {
-            static const bool on = [] {
-                const char *e = std::getenv("MOAI_SHIM_LAZY");
-                return !(e && e[0] == '0');
-            }();
-            return on;
-        }
         void addsub(Ciphertext &e1, const Ciphertext &e2, bool sub) const
         {
             check_pair(e1, e2);
@@ -1163,7 +1155,7 @@ namespace seal
                 throw std::invalid_argument("CKKS encrypted must be in NTT form");
             }
             const std::size_t L = src.coeff_modulus_size();
-            if (lazy_products() && src.batch() == 1 && src.size() == 2 && galois_keys.generation() != 0)
+            if (util::lazy_enabled() && src.batch() == 1 && src.size() == 2 && galois_keys.generation() != 0)
             {
                 // not made now (util::RotState): recorded, and made when the result is read -- together with the other rotations of
                 // the same step this thread has asked for meanwhile.  Everything that can throw has been checked above.

@@ -924,6 +924,44 @@ namespace moai_fused
             }
             context.sync();
         }
+
+        // Cuts `plains` into runs of at most 64 NTT-form vector plaintexts at one level and scale, gathers each run into one
+        // device block [count][L][N] and calls f(first, count, L, gathered).  `what` names the caller in the refusal of a
+        // scalar-row plaintext.
+        template <typename F>
+        inline void for_plain_runs(const seal::SEALContext &context, const std::vector<seal::Plaintext> &plains, const char *what, F f)
+        {
+            using namespace seal;
+            for (std::size_t i = 0; i < plains.size();)
+            {
+                const Plaintext &p0 = plains[i];
+                auto cd = context.get_context_data(p0.parms_id());
+                if (!cd || !p0.is_ntt_form())
+                {
+                    throw std::invalid_argument("plain is not valid for encryption parameters");
+                }
+                if (p0.is_scalar())
+                {
+                    throw std::invalid_argument(std::string(what) + " takes vector plaintexts");
+                }
+                std::size_t j = i + 1;
+                while (j < plains.size() && j - i < 64 && plains[j].parms_id() == p0.parms_id() && plains[j].scale() == p0.scale() &&
+                       !plains[j].is_scalar() && plains[j].is_ntt_form())
+                {
+                    j++;
+                }
+                const std::size_t L = cd->parms().coeff_modulus().size();
+                util::DeviceArray gathered((j - i) * L * context.n(), context.stream());
+                const std::uint64_t *src[64];
+                for (std::size_t t = i; t < j; t++)
+                {
+                    src[t - i] = plains[t].device_data();
+                }
+                util::hip_check(moai_gather_blocks(context.device(), src, gathered.get(), j - i, L * context.n(), context.stream()));
+                f(i, j - i, L, gathered.get());
+                i = j;
+            }
+        }
     } // namespace detail
 
     // Encryptor::encrypt for many plaintexts (SEAL/encryptor.cpp:88-173 with the public key): batched device launches per run
@@ -931,40 +969,11 @@ namespace moai_fused
     // or encrypt them with Encryptor::encrypt.
     inline void encrypt(const seal::Encryptor &encryptor, const std::vector<seal::Plaintext> &plains, std::vector<seal::Ciphertext> &cts)
     {
-        using namespace seal;
-        const SEALContext &context = encryptor.context();
-        const std::size_t n = context.n();
-        void *st = context.stream();
         cts.resize(plains.size());
-        for (std::size_t i = 0; i < plains.size();)
-        {
-            const Plaintext &p0 = plains[i];
-            auto cd = context.get_context_data(p0.parms_id());
-            if (!cd || !p0.is_ntt_form())
-            {
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
-            if (p0.is_scalar())
-            {
-                throw std::invalid_argument("moai_fused::encrypt takes vector plaintexts");
-            }
-            std::size_t j = i + 1;
-            while (j < plains.size() && j - i < 64 && plains[j].parms_id() == p0.parms_id() && plains[j].scale() == p0.scale() &&
-                   !plains[j].is_scalar() && plains[j].is_ntt_form())
-            {
-                j++;
-            }
-            const std::size_t L = cd->parms().coeff_modulus().size();
-            util::DeviceArray packed((j - i) * L * n, st);
-            const std::uint64_t *src[64];
-            for (std::size_t t = i; t < j; t++)
-            {
-                src[t - i] = plains[t].device_data();
-            }
-            util::hip_check(moai_gather_blocks(context.device(), src, packed.get(), j - i, L * n, st));
-            detail::encrypt_packed(encryptor, p0.parms_id(), packed.get(), j - i, p0.scale(), cts, i);
-            i = j;
-        }
+        detail::for_plain_runs(encryptor.context(), plains, "moai_fused::encrypt",
+                               [&](std::size_t first, std::size_t count, std::size_t, const std::uint64_t *gathered) {
+                                   detail::encrypt_packed(encryptor, plains[first].parms_id(), gathered, count, plains[first].scale(), cts, first);
+                               });
     }
 
     // Encryptor::encrypt_symmetric(plain).save(stream) for many plaintexts (SEAL/encryptor.h:374-404 with save_seed): per run of up
@@ -997,44 +1006,19 @@ namespace moai_fused
             }
         } host;
         std::size_t host_bytes = 0;
-        for (std::size_t i = 0; i < plains.size();)
-        {
-            const Plaintext &p0 = plains[i];
-            auto cd = context.get_context_data(p0.parms_id());
-            if (!cd || !p0.is_ntt_form())
-            {
-                throw std::invalid_argument("plain is not valid for encryption parameters");
-            }
-            if (p0.is_scalar())
-            {
-                throw std::invalid_argument("moai_fused::encrypt_symmetric_save takes vector plaintexts");
-            }
-            std::size_t j = i + 1;
-            while (j < plains.size() && j - i < 64 && plains[j].parms_id() == p0.parms_id() && plains[j].scale() == p0.scale() &&
-                   !plains[j].is_scalar() && plains[j].is_ntt_form())
-            {
-                j++;
-            }
-            const std::size_t m = j - i, L = cd->parms().coeff_modulus().size(), pw = wire::packed_words(context.device(), L);
-            util::DeviceArray gathered(m * L * n, st), c0(m * L * n, st), packed(m * pw, st);
-            const std::uint64_t *src[64];
-            for (std::size_t t = i; t < j; t++)
-            {
-                src[t - i] = plains[t].device_data();
-            }
-            util::hip_check(moai_gather_blocks(context.device(), src, gathered.get(), m, L * n, st));
-            wire::Record r;
-            r.kind = wire::kind_ciphertext;
-            r.flags = wire::flag_ntt | wire::flag_seeded;
-            r.count = 2;
-            r.L = static_cast<std::uint32_t>(L);
-            r.scale = p0.scale();
-            r.parms_id = p0.parms_id();
+        detail::for_plain_runs(context, plains, "moai_fused::encrypt_symmetric_save",
+                               [&](std::size_t first, std::size_t m, std::size_t L, const std::uint64_t *gathered) {
+            const std::size_t pw = wire::packed_words(context.device(), L);
+            util::DeviceArray packed(m * pw, st);
+            // one record head for the run, its block the m c0 polynomials; always under the run's ChaCha20 seed, the only kind
+            // the wire format carries seeded
+            wire::Record r = util::seeded_record_head(wire::kind_ciphertext, 2, L, plains[first].parms_id(), m * L * n, context);
+            r.scale = plains[first].scale();
             const auto &rng = encryptor.device_rng();
             const std::uint64_t seq0 = rng->take(m);
             util::public_seed(rng->key(), seq0, r.seed);
-            util::hip_check(moai_encrypt_symmetric_seeded(context.device(), rng->key(), r.seed, seq0, sk, gathered.get(), c0.get(), m, L, nullptr, st));
-            util::hip_check(moai_pack_rows(context.device(), c0.get(), packed.get(), m, L, nullptr, st));
+            util::hip_check(moai_encrypt_symmetric_seeded(context.device(), rng->key(), r.seed, seq0, sk, gathered, r.block->get(), m, L, nullptr, st));
+            util::hip_check(moai_pack_rows(context.device(), r.block->get(), packed.get(), m, L, nullptr, st));
             if (host_bytes < m * pw * 8)
             {
                 if (host.p)
@@ -1055,8 +1039,7 @@ namespace moai_fused
                 sink.put(static_cast<const std::uint8_t *>(host.p) + b * pw * 8, pw * 8);
                 total += static_cast<std::streamoff>(sizeof(h) + pw * 8);
             }
-            i = j;
-        }
+        });
         return total;
     }
 

@@ -227,10 +227,8 @@ namespace seal
         {
             keys[o.indices[i]] = o.keys[i].block;
         }
+        reset(0, o.head.parms_id);
         keys_ = std::move(keys);
-        parms_id_ = o.head.parms_id;
-        hoist_ = std::make_shared<HoistCache>();
-        res_.reset();
         for (std::size_t i = 0; i < o.indices.size(); i++)
         {
             if (o.keys[i].kind == wire::kind_kswitch_key_limited)
@@ -238,7 +236,6 @@ namespace seal
                 mark_born_limited(context, o.indices[i], o.keys[i].L - 1);
             }
         }
-        generation_ = next_generation();
     }
     inline wire::Object KSwitchKeys::to_wire() const
     {

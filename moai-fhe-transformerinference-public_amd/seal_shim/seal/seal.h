@@ -826,6 +826,16 @@ namespace seal
             }();
             return on;
         }
+        // MOAI_SHIM_LAZY=0 (read once) computes eagerly: no deferred scalar products or rotations in the evaluator, and
+        // CKKSEncoder transforms masked constants instead of recording them.  The values are the same bits either way.
+        inline bool lazy_enabled()
+        {
+            static const bool on = [] {
+                const char *e = std::getenv("MOAI_SHIM_LAZY");
+                return !(e && e[0] == '0');
+            }();
+            return on;
+        }
         inline std::vector<std::weak_ptr<RotState>> &rot_registry()
         {
             static thread_local std::vector<std::weak_ptr<RotState>> r;
@@ -2112,6 +2122,19 @@ namespace seal
         // the object kind on the wire, and the number of key slots of an empty set (GaloisKeys: N, SEAL/galoiskeys.h:48)
         wire::Object set_to_wire(std::uint32_t kind) const;
         void set_from_wire(const SEALContext &context, wire::Object &&o, std::size_t min_slots);
+        // Replaces the set by `slots` empty slots: whoever writes new keys into this object (KeyGenerator::create_*_keys, load)
+        // starts here.  What was derived from the old keys goes with them: the hoisted-rotation constants are functions of the
+        // key (hoist_correction), and the residency record holds trimmed keys' full copies (device_key and key_block prefer them
+        // to keys_), so neither may be left behind.  A copy made earlier keeps the old keys together with the old cache and
+        // record; copies made from now on share the new ones.  The new generation keeps results cached WITH the old keys apart.
+        void reset(std::size_t slots, const parms_id_type &parms_id)
+        {
+            keys_.assign(slots, nullptr);
+            hoist_ = std::make_shared<HoistCache>();
+            res_.reset();
+            generation_ = next_generation();
+            parms_id_ = parms_id;
+        }
         // keys_[index] is a trimmed block of `levels` data primes with no full key behind it
         void mark_born_limited(const SEALContext &context, std::size_t index, std::size_t levels)
         {

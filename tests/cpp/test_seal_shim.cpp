@@ -824,6 +824,105 @@ static void trimmed_keys()
     evaluator.rotate_vector(c, 1, gk2, out);
 }
 
+// Keys regenerated into an object whose keys were trimmed and came back whole, or were born limited.  The residency record
+// (KSwitchKeys::Residency) holds the old keys' full copies, and device_key / key_block prefer them to the slots: it has to go
+// with the keys it describes.  The second generator has a secret key of its own, so a switch with a stale key does not decrypt.
+static void regenerated_keys_and_residency()
+{
+    EncryptionParameters parms(scheme_type::ckks);
+    const size_t N = 4096;
+    parms.set_poly_modulus_degree(N);
+    parms.set_coeff_modulus(CoeffModulus::Create(N, { 51, 46, 46, 46, 51, 58 }));
+    SEALContext context(parms, true, sec_level_type::none);
+    CKKSEncoder encoder(context);
+    Evaluator evaluator(context, encoder);
+    KeyGenerator A(context), B(context);
+    Encryptor encA(context, A.secret_key()), encB(context, B.secret_key());
+    Decryptor decA(context, A.secret_key()), decB(context, B.secret_key());
+    const size_t k = 6, slots = encoder.slot_count(), full_bytes = (k - 1) * 2 * k * N * 8;
+    const vector<int> steps = { 1, 3 };
+    vector<uint32_t> elts;
+    vector<size_t> present;
+    for (int s : steps)
+    {
+        elts.push_back(moai_galois_elt_from_step(context.device(), s));
+        present.push_back(GaloisKeys::get_index(elts.back()));
+    }
+    vector<double> v(slots), rotated(slots), squared(slots);
+    for (size_t i = 0; i < slots; i++) v[i] = 0.1 + 0.001 * (double)(i % 89);
+    for (size_t i = 0; i < slots; i++)
+    {
+        rotated[i] = v[(i + 3) % slots];
+        squared[i] = v[i] * v[i];
+    }
+    Plaintext p;
+    encoder.encode(v, pow(2.0, 40), p);
+    // rotate by 3 and square + relinearize at chain index 3 (four data primes), decoded under `dec`
+    auto program = [&](const Encryptor &enc, Decryptor &dec, const GaloisKeys &gk, const RelinKeys &rk) {
+        Ciphertext c, r, sq;
+        enc.encrypt_symmetric(p, c);
+        evaluator.mod_switch_to_next_inplace(c);
+        evaluator.rotate_vector(c, 3, gk, r);
+        evaluator.square(c, sq);
+        evaluator.relinearize_inplace(sq, rk);
+        vector<vector<double>> out(2);
+        Plaintext pr, ps;
+        dec.decrypt(r, pr);
+        encoder.decode(pr, out[0]);
+        dec.decrypt(sq, ps);
+        encoder.decode(ps, out[1]);
+        return out;
+    };
+    // A's keys, trimmed to chain index 1 and back whole after a switch at chain index 3
+    auto trimmed_and_regrown = [&](GaloisKeys &gk, RelinKeys &rk) {
+        A.create_galois_keys(steps, gk);
+        A.create_relin_keys(rk);
+        gk.limit_to_chain_index(context, 1);
+        rk.limit_to_chain_index(context, 1);
+        CHECK(gk.limited_levels(present[1]) == 2 && rk.limited_levels(0) == 2);
+        const auto out = program(encA, decA, gk, rk);
+        CHECK(max_err(out[0], rotated, slots) < 1e-4 && max_err(out[1], squared, slots) < 1e-4);
+        CHECK(gk.regrown_count() > 0 && rk.regrown_count() > 0);
+    };
+    auto whole_keys_of_B = [&](const GaloisKeys &gk, const RelinKeys &rk) {
+        CHECK(gk.regrown_count() == 0 && rk.regrown_count() == 0);
+        CHECK(gk.size() == 2 && rk.size() == 1);
+        for (size_t s : present)
+        {
+            CHECK(gk.limited_levels(s) == 0 && !gk.born_limited(s));
+        }
+        CHECK(rk.limited_levels(0) == 0 && !rk.born_limited(0));
+        CHECK(gk.device_bytes() == full_bytes * gk.size() && rk.device_bytes() == full_bytes * rk.size());
+        const auto under_B = program(encB, decB, gk, rk);
+        CHECK(max_err(under_B[0], rotated, slots) < 1e-4 && max_err(under_B[1], squared, slots) < 1e-4);
+        // A's secret key is another one: keys that still served it would show here
+        const auto under_A = program(encB, decA, gk, rk);
+        CHECK(max_err(under_A[0], rotated, slots) > 1e-2 && max_err(under_A[1], squared, slots) > 1e-2);
+    };
+    GaloisKeys gk;
+    RelinKeys rk;
+    trimmed_and_regrown(gk, rk);
+    B.create_galois_keys(steps, gk); // the reference API
+    B.create_relin_keys(rk);
+    whole_keys_of_B(gk, rk);
+    trimmed_and_regrown(gk, rk);
+    moai_fused::create_galois_keys(B, steps, gk); // drawn on the device
+    moai_fused::create_relin_keys(B, rk);
+    whole_keys_of_B(gk, rk);
+    // born limited, then whole: the marks go with the limited keys
+    moai_fused::create_galois_keys_limited(B, elts, { 1 }, gk);
+    moai_fused::create_relin_keys_limited(B, 1, rk);
+    CHECK(gk.born_limited(present[0]) && gk.limited_levels(present[1]) == 2 && rk.born_limited(0) && rk.limited_levels(0) == 2);
+    B.create_galois_keys(elts, gk);
+    B.create_relin_keys(rk);
+    whole_keys_of_B(gk, rk);
+    moai_fused::create_galois_keys_limited(B, elts, { 1 }, gk);
+    moai_fused::create_relin_keys_limited(B, 1, rk);
+    moai_fused::create_galois_keys(B, elts, gk);
+    moai_fused::create_relin_keys(B, rk);
+    whole_keys_of_B(gk, rk);
+}
+
 // Copies share their device block until one of them is written through (copy on write), and single-ciphertext rotations are
 // remembered by (source block, element, keys): both must be invisible -- every value is what the reference's deep copies and
 // from-scratch rotations give.
@@ -1153,6 +1252,7 @@ int main()
         packed_random_program();
         regenerated_keys_and_hoisting();
         trimmed_keys();
+        regenerated_keys_and_residency();
         shared_blocks_and_rotation_cache();
         deferred_scalar_products();
     }

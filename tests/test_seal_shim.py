@@ -133,3 +133,50 @@ int main() {
     assert lines[0] == ("76b8e0ada0f13d90405d6ae55386bd28bdd219b8a08ded1aa836efcc8b770dc7"
                         "da41597c5157488d7724e03fb8d84a376a43b8f41518a11cc387b669b2ee6586")
     assert lines[1] == "0"
+
+
+def test_key_plan_orders_slots_and_refuses_bad_elements(tmp_path):
+    """seal::util::galois_key_plan (moai_client.h): what KeyGenerator::create_*_keys generates and in which order, host
+    arithmetic without a context.  n = 8, k = 4: elements 1, 3 .. 15 are slots 0 .. 7, and levels_of saturates at chain index 2."""
+    src = tmp_path / "plan.cpp"
+    src.write_text(r'''
+#include "seal/seal.h"
+#include <cstdio>
+using namespace seal::util;
+static int bad = 0;
+static void check(bool ok, const char *what) { if (!ok) { std::printf("FAIL %s\n", what); bad++; } }
+template <class F> static std::string refusal(F f)
+{
+    try { f(); } catch (const std::invalid_argument &e) { return e.what(); } catch (...) { return "another exception"; }
+    return "no exception";
+}
+int main() {
+    const std::size_t n = 8, k = 4;
+    check(levels_of(0, k) == 1 && levels_of(1, k) == 2, "levels_of below the top: chain index + 1");
+    check(levels_of(k - 2, k) == k - 1 && levels_of(k, k) == k - 1 && levels_of(k - 2, k) == levels_of(k, k), "levels_of saturates at k-1");
+    // the given order, not the order of the slots; 11 again is dropped, with the levels of its first mention
+    const std::vector<std::uint32_t> elts = { 11, 3, 15, 11, 1 };
+    const std::vector<std::size_t> each = { 0, 1, 2, 1, 5 };
+    check(galois_key_plan(elts, &each, n, k) == KeyPlan{ { 5, 1 }, { 1, 2 }, { 7, 3 }, { 0, 3 } }, "per-element chain indices");
+    const std::vector<std::size_t> one = { 1 };
+    check(galois_key_plan(elts, &one, n, k) == KeyPlan{ { 5, 2 }, { 1, 2 }, { 7, 2 }, { 0, 2 } }, "one chain index for all elements");
+    check(galois_key_plan(elts, nullptr, n, k) == KeyPlan{ { 5, 3 }, { 1, 3 }, { 7, 3 }, { 0, 3 } }, "whole keys: k-1 levels");
+    check(galois_key_plan({}, nullptr, n, k).empty() && galois_key_plan({}, &one, n, k).empty(), "no elements, no keys");
+    const std::vector<std::size_t> four = { 0, 1, 2, 1 }, none = {};
+    const std::string count = "chain_indices must hold one entry, or one per Galois element", elt = "Galois element is not valid";
+    check(refusal([&] { galois_key_plan(elts, &four, n, k); }) == count, "four chain indices for five elements");
+    check(refusal([&] { galois_key_plan(elts, &none, n, k); }) == count, "no chain index for five elements");
+    check(refusal([&] { galois_key_plan({ 3, 4 }, nullptr, n, k); }) == elt, "an even element");
+    check(refusal([&] { galois_key_plan({ 3, 0 }, &one, n, k); }) == elt, "element 0");
+    check(refusal([&] { galois_key_plan({ 3, 2 * n }, nullptr, n, k); }) == elt, "element 2n");
+    check(refusal([&] { galois_key_plan({ 3, 2 * n + 1 }, nullptr, n, k); }) == elt, "element 2n + 1");
+    check(galois_key_plan({ 2 * n - 1 }, nullptr, n, k) == KeyPlan{ { n - 1, 3 } }, "element 2n - 1 is the last slot");
+    std::printf("bad %d\n", bad);
+    return bad ? 1 : 0;
+}
+''')
+    exe = tmp_path / "plan"
+    r = _gxx([str(src), "-o", str(exe), "-L" + PKG, "-lmoai_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "bad 0" in out.stdout, (out.stdout[-3000:], out.stderr[-2000:])
