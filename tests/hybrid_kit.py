@@ -1,7 +1,8 @@
 """What the tests of the hybrid key switch share (tests/test_gpu_hybrid_*.py, tests/test_hybrid_*_cpu.py,
 tests/test_cabi_hybrid_ptrs_cpu.py): the environment of one chain of primes (Env), the four shapes most of them run at (ENVS and
 the fixtures env_small1 .. env_tiled3), constants, the tuning-knob and op-trace context managers, and the checks of the C ABI that
-need no device.  Not collected: the tests themselves, their cases and their restatements stay in their own files."""
+need no device.  Not collected: the tests themselves and their restatements stay in their own files; the cases that several files
+run are in tests/hybrid_cases.py."""
 import contextlib
 import ctypes as C
 import os

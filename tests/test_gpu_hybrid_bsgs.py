@@ -23,69 +23,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import hybrid_bsgs_ref as HB
 import hybrid_ref as HR
 import mode_limits as ML
-import oracle as O
-from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, PATTERN, Env, cached, traced, tuned, unit_plain
+from hybrid_cases import BsgsCase as Case
+from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, Env, traced, tuned, unit_plain
 from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-BABY = [IDENT, 1, 3, -2, 64, 0]  # 0 = conjugation (Galois element 2N - 1)
-GIANT = [IDENT, 4, -8]
-
-
-def default_absent(baby, giant):
-    """giant step 1 lacks baby terms 1 and 3; the last giant step holds only the identity baby term"""
-    if len(giant) < 3 or IDENT not in baby:
-        return set()
-    return {(1, 1), (1, 3)} | {(len(giant) - 1, r) for r, s in enumerate(baby) if s != IDENT}
-
-
-class Case:
-    """one call: the operands on the device, and the restatement's output computed once (want=False: not at all)"""
-
-    def __init__(self, e, L, baby=BABY, giant=GIANT, B=None, seed=0, ct=None, plain=None, shared_key=False, want=True):
-        B = (3 if e.logn == 10 else 2) if B is None else B
-        self.e, self.L, self.B, self.R, self.ng = e, L, B, len(baby), len(giant)
-        rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed + 5)
-        self.baby, self.giant = e.elts(baby), e.elts(giant)
-        one_key = e.random_key(rng) if shared_key else None
-        self.bkeys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.baby]
-        self.gkeys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.giant]
-        dk = {}
-        self.dbkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.bkeys]
-        self.dgkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.gkeys]
-        self.ct = e.random_input(rng, L, B) if ct is None else ct(rng)
-        self.dct = e.up(self.ct)
-        dc = {}
-        self.corrs = [None if k is None else cached(dc, (id(k), elt), lambda: e.ctx.hybrid_hoist_correction(k, elt, L, e.alpha))
-                      for k, elt in zip(self.dbkeys, self.baby)]
-        absent = default_absent(baby, giant)
-        new_plain = plain or (lambda: O.uniform_rns(rng, e.rows(L), (), e.n))
-        self.plains = [[None if (g, r) in absent else new_plain() for r in range(self.R)] for g in range(self.ng)]
-        dp = {}
-        self.dplains = [[None if p is None else cached(dp, id(p), lambda: e.up(p)) for p in row] for row in self.plains]
-        self.shape = (B, 2, L, e.n)
-        if want:
-            self.want = np.stack([HB.bsgs_dot(e.octx, self.ct[b], L, e.alpha, self.baby, self.bkeys, self.giant, self.gkeys, self.plains)
-                                  for b in range(B)])
-
-    def run(self):
-        """(fallback flag, output [B][2][L][N]) from an output buffer filled with a pattern"""
-        out = self.e.filled(self.shape, PATTERN)
-        fb = self.e.ctx.hybrid_bsgs_dot(self.dct, out, self.L, self.e.alpha, self.baby, self.dbkeys, self.corrs, self.giant, self.dgkeys,
-                                        self.dplains, self.B)
-        got = out.to_numpy(self.shape)
-        assert (self.dct.to_numpy(self.ct.shape) == self.ct).all()  # the input is left alone
-        return fb, got
-
-    def check(self):
-        fb, got = self.run()
-        assert not fb
-        assert (got == self.want).all()
-
 
 @pytest.fixture(scope="module")
 def case_tiled3(env_tiled3):

@@ -15,7 +15,6 @@ tests/test_hybrid_exact_cpu.py), and every test leaves its context in MOAI_HYBRI
 9. The list forms in exact mode are the single calls in exact mode.
 10. At MOAI's parameters (N = 2^16, 35 + 12 primes, l = 35) fast - exact is one integer per coefficient in [-(alpha - 1), 0] ([-alpha, 0]
     for the merged rescale), the same in every row, and not zero everywhere."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -29,23 +28,13 @@ import hybrid_ref as HR
 import hybrid_rescale_ref as RR
 import mode_limits as ML
 import oracle as O
+from hybrid_cases import EXACT, FAST, check_boundaries, exact, run_rescale, run_switch
 from hybrid_kit import EINVAL, IDENT, MOAI_DATA_BITS, OK, PATTERN, Env, cached, exported, tuned
 from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-FAST, EXACT = 0, 1
 KEY = bytes(range(1, 33))
-
-
-@contextlib.contextmanager
-def exact(e):
-    """the block runs in MOAI_HYBRID_ROUND_EXACT; the context is back in the default afterwards, whatever happened"""
-    try:
-        e.ctx.hybrid_set_rounding(EXACT)
-        yield
-    finally:
-        e.ctx.hybrid_set_rounding(FAST)
 
 
 def key_of(e):
@@ -53,20 +42,6 @@ def key_of(e):
         k = O.uniform_rns(np.random.default_rng(e.logn * 100 + e.alpha + 7), e.primes, (e.digits, 2), e.n)
         return k, e.up(k)
     return cached(e.cache, "exact key", make)
-
-
-def run_switch(e, ct, target, dkey, L):
-    B = len(ct)
-    d = e.up(ct)
-    e.ctx.switch_key_hybrid(d, e.up(target), dkey, L, e.alpha, B)
-    return d.to_numpy((B, 2, L, e.n))
-
-
-def run_rescale(e, ct3, dkey, L):
-    B = len(ct3)
-    out = e.filled((B, 2, L - 1, e.n), PATTERN)
-    e.ctx.relinearize_rescale_hybrid(e.up(ct3), dkey, out, L, e.alpha, B)
-    return out.to_numpy((B, 2, L - 1, e.n))
 
 
 # ---- 1. the mode API ------------------------------------------------------------------------------------------------------------------
@@ -273,51 +248,6 @@ def test_sixteen_sources_on_61_bit_primes(moai, form, logn):
 
 
 # ---- 6. directed boundaries ---------------------------------------------------------------------------------------------------------
-def check_boundaries(e, rescale):
-    """The accumulator of a single-digit switch of the constant 1 is g (*) key digit 0, g the digit's converted constant under each row
-    (1 where the digit has one prime: it converts exactly).  So the key is built row by row as g^-1 times the residues of integers Z
-    whose X' are the targets, with c_0 = c_1 = 0; the restatement says what Z really was."""
-    L = 2 if rescale else 1
-    octx, n, alpha = e.octx, e.n, e.alpha
-    assert alpha >= 2 and HR.beta(L, alpha) == 1
-    rows = HH.rows_of(octx, L, alpha)
-    src, ntgt = HX.bases(octx, L, alpha, rescale)
-    W = HR._prod(e.primes[r] for r in src)
-    H, Qlo = W // 2, HR._prod(e.primes[:ntgt])
-    targets = [0, 1, 2, W - 2, W - 1, H - 1, H, H + 1]
-    ct3 = np.zeros((1, 3, L, n), dtype=np.uint64)
-    ct3[0, 2] = 1  # the constant 1 in NTT form
-    ones = np.ones((e.digits, 2, e.k, n), dtype=np.uint64)
-    g = RR.lifted(octx, ct3[0], ones, L, alpha)[0, :, 0]  # with the all-ones key the accumulator is g itself
-    rng = np.random.default_rng(600 + rescale)
-    key = np.zeros((e.digits, 2, e.k, n), dtype=np.uint64)
-    want = [targets[c % 8] for c in range(n)]
-    for p in range(2):
-        z = [int(rng.integers(0, 1 << 62)) % Qlo * W + (x - H) % W for x in want]
-        coef = np.stack([HR._u64(np.array([v % e.primes[r] for v in z], dtype=object)) for r in rows])
-        Zrows = octx.ntt(coef, len(rows), prime_index=rows)
-        for t, r in enumerate(rows):
-            m = e.primes[r]
-            key[0, p, r] = HR._u64(HR._obj(Zrows[t]) * pow(int(g[t]), -1, m) % m)
-    Z = RR.lifted(octx, ct3[0], key, L, alpha)
-    for p in range(2):
-        diag = {}
-        HX.mod_down_rows(octx, Z[p], L, alpha, rescale=rescale, diag=diag)
-        assert list(diag["X"]) == want, p  # the accumulator hit its targets
-        print("%s p %d: v - v* over the eight targets: %s" % ("rescale" if rescale else "switch", p,
-                                                               [int(diag["v"][c]) - int(diag["vstar"][c]) for c in range(8)]))
-    with exact(e):
-        if rescale:
-            got = run_rescale(e, ct3, e.up(key), L)[0]
-            assert (got == HX.relinearize_rescale(octx, ct3[0], key, L, alpha, Z=Z)).all()
-        else:
-            got = run_switch(e, ct3[:, :2], ct3[:, 2], e.up(key), L)[0]
-            assert (got == HX.switch_key(octx, ct3[0, :2], ct3[0, 2], key, L, alpha)).all()
-    for p in range(2):
-        err, _ = HX.quotient_error(octx, Z[p], got[p], L, alpha, rescale)
-        assert HX.within_half(err, W).all(), p
-
-
 @pytest.mark.parametrize("rescale", [False, True])
 def test_boundaries_alpha_2(env_small2, rescale):
     check_boundaries(env_small2, rescale)

@@ -25,10 +25,11 @@ import numpy as np
 import pytest
 
 import hybrid_hoist_ref as HH
-import hybrid_kit
 import hybrid_ref as HR
 import mode_limits as ML
 import oracle as O
+from hybrid_cases import LimitEnv as Env
+from hybrid_cases import Q_HALVES, assert_modes, switch_inputs
 from hybrid_kit import PATTERN, tuned
 
 pytestmark = pytest.mark.gpu
@@ -37,39 +38,6 @@ CHAINS = list(ML.HYBRID_CHAINS)
 KEYS = ["max", "rnd"]  # every row all m - 1; uniform
 STEPS = [1, 3, -2, 64, 0]  # 0 = conjugation (Galois element 2N - 1)
 SEAL_KEY = bytes(range(1, 33))
-Q_HALVES = ML.PATTERNS[3]
-
-
-class Env(hybrid_kit.Env):
-    """one chain at one degree: the oracle's and the device's context, the two keys on host and device"""
-
-    def __init__(self, moai, logn, which, alpha):
-        primes, self.names, alpha = ML.hybrid_chain(logn, which, alpha)
-        super().__init__(moai, logn, primes=primes, alpha=alpha)
-        self.which = which
-        self._keys, self._dkeys = {}, {}
-
-    def key(self, kind):
-        if kind not in self._keys:
-            if kind == "max":
-                key = np.empty((self.digits, 2, self.k, self.n), dtype=np.uint64)
-                for i, m in enumerate(self.primes):
-                    key[:, :, i, :] = m - 1
-            else:
-                key = O.uniform_rns(np.random.default_rng(7100 + self.logn), self.primes, (self.digits, 2), self.n)
-            key.setflags(write=False)
-            self._keys[kind] = key
-        return self._keys[kind]
-
-    def dkey(self, kind):
-        if kind not in self._dkeys:
-            self._dkeys[kind] = self.up(self.key(kind))
-        return self._dkeys[kind]
-
-    def close(self):
-        for b in self._dkeys.values():
-            b.free()
-        super().close()
 
 
 _envs = {}
@@ -90,27 +58,7 @@ def env(moai, logn, which, alpha=None):
     return _envs[(logn, which, alpha)]
 
 
-def code(moai, name):
-    return getattr(moai.hip, "MODE_" + name)
-
-
 # ---- a. modes ------------------------------------------------------------------------------------------------------------------
-def assert_modes(moai, e, fp=1, lazy16=1):
-    """every row of the chain is in its table class (tiled degrees; MOAI_NTT_LAZY16=0 moves the LAZY16 rows to LAZY8); returns the
-    (forward, inverse) class names of the special rows"""
-    if e.logn < 12:
-        return None
-    H = moai.hip
-    out = []
-    for i, name in enumerate(e.names):
-        want = [table[name.rstrip("-")][0 if fp else 1] for table in (ML.FWD_CLASS, ML.INV_CLASS)]
-        want = ["LAZY8" if w == "LAZY16" and not lazy16 else w for w in want]
-        got = [e.ctx.arith_mode(i, of) for of in (H.MODE_OF_NTT_FORWARD, H.MODE_OF_NTT_INVERSE)]
-        assert got == [code(moai, w) for w in want], (e.which, name, want, got)
-        out.append(tuple(want))
-    return out[e.lmax:]
-
-
 @pytest.mark.parametrize("which", CHAINS)
 def test_special_rows_take_the_intended_inverse_class(moai, which):
     """the mod-down inverts the special rows: exact integer and lazy butterflies on special_large, FP64 ones on special_small"""
@@ -120,25 +68,6 @@ def test_special_rows_take_the_intended_inverse_class(moai, which):
 
 
 # ---- the inputs and the restatement of a switch, computed once --------------------------------------------------------------------
-def switch_inputs(e, L):
-    """names, ct [B][2][L][N] (random addends) and tgt [B][L][N] (NTT form of the coefficient patterns).  2^10 and 2^12: worst_coeff
-    and every pattern of ML.PATTERNS; above: worst_coeff, q/2 and q/2+1, random."""
-    if ("in", L) not in e.cache:
-        rng = np.random.default_rng(7200 + 100 * e.logn + L)
-        pat = ML.pattern_rows(e.primes[:L], e.n, rng)
-        worst = ML.worst_coeff(e.primes, L, e.alpha, e.n)
-        if e.logn <= 12:
-            names, coeff = ("worst_coeff",) + ML.PATTERNS, [worst] + list(pat)
-        else:
-            names, coeff = ("worst_coeff", Q_HALVES, "random"), [worst, pat[3], pat[4]]
-        tgt = np.stack([e.octx.ntt(cf, L) for cf in coeff])
-        ct = O.uniform_rns(rng, e.primes[:L], (len(names), 2), e.n)
-        for a in (tgt, ct):
-            a.setflags(write=False)
-        e.cache[("in", L)] = (names, ct, tgt)
-    return e.cache[("in", L)]
-
-
 def switch_ref(e, L, kind, b):
     """HR.switch_key of ciphertext b of switch_inputs with key `kind`"""
     if ("sk", L, kind, b) not in e.cache:

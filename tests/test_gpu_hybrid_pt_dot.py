@@ -21,66 +21,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import hybrid_dot_ref as HD
 import hybrid_ref as HR
 import mode_limits as ML
-import oracle as O
-from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, PATTERN, Env, cached, traced, tuned, unit_plain
+from hybrid_cases import DotCase as Case
+from hybrid_kit import EINVAL, FILL, IDENT, MOAI_DATA_BITS, OK, Env, traced, tuned, unit_plain
 from hybrid_kit import env_small1, env_small2, env_tiled1, env_tiled3  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-STEPS = [1, 3, -2, 64, 0, IDENT]  # 0 = conjugation (Galois element 2N - 1)
-
-
-def default_absent(steps, n_out):
-    """output 1 lacks terms 1 and 3; the last output holds only the identity term"""
-    if n_out < 3 or IDENT not in steps:
-        return set()
-    return {(1, 1), (1, 3)} | {(n_out - 1, r) for r, s in enumerate(steps) if s != IDENT}
-
-
-class Case:
-    """one call: the operands on the device, and the restatement's outputs computed once (want=False: not at all)"""
-
-    def __init__(self, e, L, steps=STEPS, B=3, n_out=3, seed=0, ct=None, plain=None, shared_key=False, want=True):
-        self.e, self.L, self.B, self.R, self.n_out = e, L, B, len(steps), n_out
-        rng = np.random.default_rng(e.logn * 1000 + e.alpha * 100 + L * 10 + seed)
-        self.elts = e.elts(steps)
-        one_key = e.random_key(rng) if shared_key else None
-        self.keys = [None if elt == 1 else (one_key if shared_key else e.random_key(rng)) for elt in self.elts]
-        dk = {}
-        self.dkeys = [None if k is None else cached(dk, id(k), lambda: e.up(k)) for k in self.keys]
-        self.ct = e.random_input(rng, L, B) if ct is None else ct(rng)
-        self.dct = e.up(self.ct)
-        dc = {}
-        self.corrs = [None if k is None else cached(dc, (id(k), elt), lambda: e.ctx.hybrid_hoist_correction(k, elt, L, e.alpha))
-                      for k, elt in zip(self.dkeys, self.elts)]
-        absent = default_absent(steps, n_out)
-        new_plain = plain or (lambda: O.uniform_rns(rng, e.rows(L), (), e.n))
-        self.plains = [[None if (g, r) in absent else new_plain() for r in range(self.R)] for g in range(n_out)]
-        dp = {}
-        self.dplains = [[None if p is None else cached(dp, id(p), lambda: e.up(p)) for p in row] for row in self.plains]
-        self.shape = (n_out, B, 2, L, e.n)
-        if want:
-            self.want = np.empty(self.shape, dtype=np.uint64)
-            for b in range(B):
-                self.want[:, b] = HD.rotate_pt_dot(e.octx, self.ct[b], L, e.alpha, self.elts, self.keys, self.plains)
-
-    def run(self):
-        """(fallback flag, outputs [n_out][B][2][L][N]) from output buffers filled with a pattern"""
-        out = self.e.filled(self.shape, PATTERN)
-        fb = self.e.ctx.hybrid_rotate_pt_dot(self.dct, out, self.L, self.e.alpha, self.elts, self.dkeys, self.corrs, self.dplains, self.B)
-        got = out.to_numpy(self.shape)
-        assert (self.dct.to_numpy(self.ct.shape) == self.ct).all()  # the input is left alone
-        return fb, got
-
-    def check(self):
-        fb, got = self.run()
-        assert not fb
-        for g in range(self.n_out):
-            assert (got[g] == self.want[g]).all(), g
-
 
 @pytest.fixture(scope="module")
 def case_tiled3(env_tiled3):
