@@ -582,7 +582,8 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
  *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
  *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight
- *   MOAI_HYBRID_HOIST_NR   4     rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1 */
+ *   MOAI_HYBRID_HOIST_NR   4     rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1
+ *   MOAI_HYBRID_FUSED      0     1: hybrid switches at N >= 2^12 run mod-up, forward transform and key product as two fused passes */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
 /* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of
@@ -723,7 +724,22 @@ int moai_key_register(moai_ctx *ctx, const uint64_t *key, size_t levels);
  * ciphertext is beta (L + alpha) + 4L + 4 alpha rows of N words (2L more for apply_galois) from the stream's workspace; a batch
  * runs in chunks that fit MOAI_HYBRID_TMP_KB.  The first call at a new (L, alpha) builds that pair's constants with a blocking
  * copy, as the first use of a Galois element builds its table; otherwise no call synchronises.  moai_op_trace counts the calls
- * as "switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid" and "hybrid_keygen". */
+ * as "switch_key_hybrid", "relinearize_hybrid", "apply_galois_hybrid" and "hybrid_keygen".
+ * Fused form (MOAI_HYBRID_FUSED = 1, N >= 2^12; off by default, without effect below 2^12): the switch, relinearize and apply_galois
+ * calls of this section, their list forms and the merged relinearize + rescale calls below run steps 2-4 as two passes per group of
+ * output rows of one arithmetic mode -- the strided pass of the forward transform with the base conversion of step 2 on its loads,
+ * and the contiguous pass with the products of step 4 behind it -- after scaling INTT(c) once per ciphertext.  The converted rows
+ * then exist only between the two passes, beta rows per output row in flight.  Scratch per ciphertext: the head rows of the call
+ * (0, L, 2L or 3L as in the unfused form) + L + G beta + 2 (L + alpha) + 2 a + 2 t rows of N words, (a, t) = (alpha, L) for a switch
+ * and (alpha + 1, L - 1) for the merged rescale; cb is the largest count of ciphertexts that fits MOAI_HYBRID_TMP_KB with G = 1 (at
+ * least one, within the same limits as the unfused form) and G <= L + alpha the largest count of output rows that fits beside them
+ * (at least one).  The hoisted, pt-dot and BSGS calls keep the unfused steps.  Results depend on neither the knob, the budget nor
+ * the grouping: every accumulator is the same canonical residue either way, and moai_op_trace counts the same calls. */
+/* The number of output-row groups (pairs of launches) the fused form would take NOW for a chunk of a moai_switch_key_hybrid call
+ * of `batch` ciphertexts at (L, alpha): the rows of L + alpha ordered by arithmetic mode (MOAI_NTT_FP, MOAI_KS_FP_MIN_ROWS) and cut
+ * to G.  0 when the call would take the unfused steps -- MOAI_HYBRID_FUSED = 0, N < 2^12, batch = 0 -- or when (L, alpha) is
+ * refused, with the error set then.  Read-only: no launch, no stream. */
+size_t moai_hybrid_fused_groups(const moai_ctx *ctx, size_t L, size_t alpha, size_t batch);
 /* beta(L) = ceil(L / alpha), the digits SEAL/evaluator.cpp:2724-3020 would loop over at alpha = 1; 0 and the error set when refused */
 size_t moai_hybrid_digits(const moai_ctx *ctx, size_t alpha, size_t L);
 /* KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336, with digits of alpha primes and P for the special prime */

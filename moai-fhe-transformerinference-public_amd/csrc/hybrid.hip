@@ -34,12 +34,17 @@
 // MOAI_HYBRID_ROUND_EXACT that one launch takes hy_convert_kernel<.., true>, which removes the fast conversion's overflow with a
 // binary64 estimate (the header states the contract, the kernel derives the error bound).  An entry point reads the mode once
 // (hy_exact) and hands it down as `exact`; the mod-ups, the constants' cache and every other launch do not depend on it.
+// Fused steps 2-4 (MOAI_HYBRID_FUSED=1, N >= 2^12; off by default): the switch, relinearize, apply_galois, the merged rescale and
+// their list forms call steps 1-4 through hy_steps14, which then scales t in place (hy_scale_digits_kernel) and runs, per group of
+// output rows of one arithmetic mode, hy_fwd_strided (the base conversion on the strided pass's loads) and hy_contig_mac8 (the
+// contiguous pass with the key MAC behind it): no ext, no transformed digit in memory, the same canonical accumulators.  The hoisted,
+// pt-dot and BSGS families read the transformed digits from memory and keep the unfused steps.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 //
 // Files: the argument structs, the constant blocks and every kernel are in hybrid_kernels.hip.h; this file is the host code.  The
 // scratch of a chunk is planned by hybrid_scratch.h (host only, no context, no device): each call family (switch, hoisted, pt-dot,
-// bsgs, rescale) states its regions once -- a name, a row count, held per ciphertext or per (group, ciphertext) pair -- and from that
+// bsgs, rescale, fused) states its regions once -- a name, a row count, held per ciphertext or per (group, ciphertext) pair -- and from that
 // one statement a HyPlan takes the row totals that size a chunk under MOAI_HYBRID_TMP_KB, the 256-aligned offsets and the total.
 // Three sizing policies: ciphertexts only; ciphertexts, then groups beside them; groups first with the chunks evened out.
 #include <algorithm>
@@ -330,6 +335,174 @@ static int hy_mac(moai_ctx *c, const KsTarget &tg, const uint64_t *ext, const ui
     });
 }
 
+// ---- steps 2-4 fused into the forward transform's passes (MOAI_HYBRID_FUSED) -------------------------------------------------------
+// whether the switches take the fused passes now: the knob, and a ring the tiled kernels exist for
+static bool hy_fused(const moai_ctx *c)
+{
+    return tuning(K_HYBRID_FUSED) != 0 && c->logn >= 12;
+}
+
+// the scratch plan of a switch (rescale: of the merged relinearize + rescale), fused or not as hy_fused says; hy_steps14 takes the
+// path from the plan it is handed
+static HyPlan hy_switch_plan(const moai_ctx *c, size_t L, size_t alpha, size_t batch, size_t head_rows, bool rescale,
+                             size_t limit = HY_NO_LIMIT)
+{
+    const size_t n = c->n, budget = hy_budget();
+    if (!hy_fused(c))
+    {
+        return rescale ? hy_plan_rescale(n, L, alpha, batch, head_rows, budget, limit) : hy_plan_switch(n, L, alpha, batch, head_rows, budget, limit);
+    }
+    return rescale ? hy_plan_fused(n, L, alpha, batch, head_rows, alpha + 1, L - 1, budget, hy_rescale_grid_cap(L, alpha), limit)
+                   : hy_plan_fused(n, L, alpha, batch, head_rows, alpha, L, budget, hy_grid_cap(L, alpha), limit);
+}
+
+// which arithmetic the fused kernels use for an output row under `prime`: the one mode rule, with the integer no-guard form only
+// where the unreduced digit (below 33 q) may enter the MAC of beta digits: 36 q^2 beta < 2^128 (keyswitch.hip ks_mode, beta for L)
+static int hy_fused_mode(const moai_ctx *c, uint32_t prime, size_t beta, bool allow_fp)
+{
+    const int m = ntt_mode(c, prime, allow_fp);
+    if (m != M_NOGUARD)
+    {
+        return m;
+    }
+    const uint64_t q = c->primes[prime];
+    const unsigned __int128 lim = (unsigned __int128)q * q;
+    return lim < (~(unsigned __int128)0) / (36 * (unsigned __int128)beta) ? M_NOGUARD : M_GUARD;
+}
+
+// The launches of the fused steps 2-4 for B ciphertexts: the L + alpha output rows ordered by arithmetic mode and cut into groups of
+// at most G rows of one mode (G: the rows whose tmp fits the scratch, HyPlan::G), as ks_plan does it.  The FP64 modes from
+// MOAI_KS_FP_MIN_ROWS digit rows per call, as in the key switch: below that the extra launches cost more than they save.
+struct HyFusedPlanGroup
+{
+    HyFusedGroup grp;
+    size_t g; // members
+    int mode;
+};
+
+static std::vector<HyFusedPlanGroup> hy_fused_plan(const moai_ctx *c, size_t L, size_t alpha, size_t B, size_t G)
+{
+    const bool allow_fp = (long)(B * L) >= tuning(K_KS_FP_MIN_ROWS);
+    const size_t beta = hy_beta(L, alpha);
+    std::vector<uint32_t> order;
+    std::vector<int> order_mode;
+    for (int mode = M_FPR; mode >= M_GUARD; --mode)
+    {
+        for (size_t row = 0; row < L + alpha; ++row)
+        {
+            if (hy_fused_mode(c, (uint32_t)hy_row_prime(row, L, alpha, c->k), beta, allow_fp) == mode)
+            {
+                order.push_back((uint32_t)row);
+                order_mode.push_back(mode);
+            }
+        }
+    }
+    std::vector<HyFusedPlanGroup> plan;
+    for (size_t o0 = 0; o0 < order.size();)
+    {
+        HyFusedPlanGroup pg;
+        pg.mode = order_mode[o0];
+        pg.g = 0;
+        while (o0 + pg.g < order.size() && pg.g < G && order_mode[o0 + pg.g] == pg.mode)
+        {
+            ++pg.g;
+        }
+        for (size_t i = 0; i < MOAI_MAX_RNS; ++i)
+        {
+            const size_t row = order[o0 + (i < pg.g ? i : 0)];
+            pg.grp.row[i] = (uint32_t)row;
+            pg.grp.prime[i] = (uint32_t)hy_row_prime(row, L, alpha, c->k);
+        }
+        plan.push_back(pg);
+        o0 += pg.g;
+    }
+    return plan;
+}
+
+// one group: the strided pass with the conversions on its loads, then the contiguous pass with the MAC
+template <int LOGN, int MODE>
+static int hy_fused_group(moai_ctx *c, const HyTable *tab, const KsTarget &tg, const uint64_t *key, const uint64_t *y, uint64_t *tmp,
+                          uint64_t *acc, size_t L, size_t alpha, size_t B, const HyFusedPlanGroup &pg, hipStream_t s)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    const size_t beta = hy_beta(L, alpha);
+    if (B * pg.g * beta * TPR * 2 > 0x7fffffffull)
+    {
+        return set_error(MOAI_EINVAL, "batch too large for one launch");
+    }
+    HyP1Args p1;
+    p1.y = y;
+    p1.tmp = tmp;
+    p1.tw = twiddles(c, MODE, false).tw;
+    p1.pc = c->pc;
+    p1.cv = tab->conv; // device address arithmetic only
+    p1.grp = pg.grp;
+    p1.L = (uint32_t)L;
+    p1.alpha = (uint32_t)alpha;
+    p1.beta = (uint32_t)beta;
+    p1.G = (uint32_t)pg.g;
+    p1.total_work = (uint32_t)(B * beta * TPR * pg.g);
+    hipLaunchKernelGGL((hy_fwd_strided<LOGN, MODE>), dim3(p1.total_work), dim3(256), 0, s, p1);
+    MOAI_LAUNCH_CHECK();
+    HyP2Args p2;
+    p2.tmp = tmp;
+    p2.tgt = tg.ptr;
+    p2.tgt_stride = (uint32_t)tg.stride_rows;
+    p2.tgt_off = (uint32_t)tg.off_rows;
+    p2.key = key;
+    p2.acc = acc;
+    p2.tw = p1.tw;
+    p2.tw1 = c->fwd_twf1;
+    p2.pc = c->pc;
+    p2.grp = pg.grp;
+    p2.L = p1.L;
+    p2.alpha = p1.alpha;
+    p2.beta = p1.beta;
+    p2.G = p1.G;
+    p2.k = (uint32_t)c->k;
+    p2.B = (uint32_t)B;
+    p2.total_work = (uint32_t)(B * pg.g * TPR * 2); // 2048-coefficient tiles
+    return plain_or_list<HyP2ListArgs>(p2, tg.lst, [&](const auto &args, auto LIST) {
+        hipLaunchKernelGGL((hy_contig_mac8<LOGN, MODE, decltype(LIST)::value>), dim3(p2.total_work), dim3(256), 0, s, args);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
+}
+
+// Steps 1-4 for B ciphertexts on plan w, which says how: acc [B][2][L + alpha][N] = the inner products of the digits of the target
+// rows tg with `key` or, with tg.lst, member b's own.  A plan with ext (hy_plan_switch, hy_plan_rescale) takes the unfused chain; a
+// plan with tmp (hy_plan_fused) scales t once per ciphertext and runs the two fused passes per group of output rows.
+static int hy_steps14(moai_ctx *c, const HyTable *tab, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha, size_t B, void *wsp,
+                      const HyPlan &w, hipStream_t s)
+{
+    uint64_t *acc = hy_at(wsp, w, HY_ACC);
+    if (!w.rows[HY_TMP])
+    {
+        // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows; 4. the inner products
+        uint64_t *ext = hy_at(wsp, w, HY_EXT);
+        MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, hy_at(wsp, w, HY_T), ext, s));
+        return hy_mac(c, tg, ext, key, acc, L, alpha, B, s);
+    }
+    uint64_t *y = hy_at(wsp, w, HY_Y), *tmp = hy_at(wsp, w, HY_TMP);
+    RowMap rm;
+    MOAI_TRY(make_rowmap(c, L, nullptr, &rm));
+    MOAI_TRY(ntt_launch(c, y, B, L, rm, true, s, tg.ptr, tg.stride_rows, tg.off_rows));
+    HyScaleArgs sc;
+    sc.t = y;
+    sc.cv = tab->conv; // device address arithmetic only
+    sc.d = hy_dims(c, L, alpha);
+    MOAI_TRY(launch_rows(hy_scale_digits_kernel, c, B * L, s, sc));
+    for (const HyFusedPlanGroup &pg : hy_fused_plan(c, L, alpha, B, w.G))
+    {
+        MOAI_TRY(dispatch_logn(c->logn, [&](auto LG) {
+            return dispatch<M_GUARD, M_NOGUARD, M_FPN, M_FPR>("key-switch arithmetic mode ", pg.mode, [&](auto MD) {
+                return hy_fused_group<decltype(LG)::value, decltype(MD)::value>(c, tab, tg, key, y, tmp, acc, L, alpha, B, pg, s);
+            });
+        }));
+    }
+    return MOAI_OK;
+}
+
 // rotations of the next pass of a hoisted MAC over the digits when `left` are left: MOAI_HYBRID_HOIST_NR of them, 4, 2 or 1
 static size_t hy_pass_size(size_t left)
 {
@@ -343,11 +516,10 @@ static size_t hy_pass_size(size_t left)
 static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const KsTarget &tg, const uint64_t *key, size_t L, size_t alpha,
                            size_t B, void *wsp, const HyPlan &w, const KsAddend &add, bool exact, hipStream_t s)
 {
-    uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
-    // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows
-    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, hy_at(wsp, w, HY_T), ext, s));
-    // 4. the inner products with the key
-    MOAI_TRY(hy_mac(c, tg, ext, key, acc, L, alpha, B, s));
+    uint64_t *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
+    // 1. t = INTT(target); 2., 3. mod-up of every digit and the forward transform of the converted rows; 4. the inner products with
+    // the key -- unfused or fused, as the plan says
+    MOAI_TRY(hy_steps14(c, tab, tg, key, L, alpha, B, wsp, w, s));
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
     MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, w, HY_X), conv, L, alpha, B, exact, s));
     return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, tg.lst, s);
@@ -435,7 +607,7 @@ static int hy_entry(moai_ctx *c, int kind, uint64_t *io, const uint64_t *in, con
     const HyTable *tab;
     MOAI_TRY(hy_table(c, L, alpha, &tab));
     // 2 L rows in front: the permuted input of apply_galois
-    const HyPlan w = hy_plan_switch(n, L, alpha, batch, kind == HY_GALOIS ? 2 * L : 0, hy_budget());
+    const HyPlan w = hy_switch_plan(c, L, alpha, batch, kind == HY_GALOIS ? 2 * L : 0, false);
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
     return for_chunks(batch, w.cb, [&](size_t b0, size_t B) {
@@ -892,11 +1064,10 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
                                 uint64_t *out, size_t L, size_t alpha, size_t B, void *wsp, const HyPlan &w, bool exact, hipStream_t s,
                                 const KsList *lst = nullptr)
 {
-    uint64_t *ext = hy_at(wsp, w, HY_EXT), *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
+    uint64_t *acc = hy_at(wsp, w, HY_ACC), *conv = hy_at(wsp, w, HY_CONV);
     // steps 1-4 on c2, as every switch
     const KsTarget tg = lst ? KsTarget{ hy_at(wsp, w, HY_HEAD), L, 0, lst } : KsTarget{ ct3, 3 * L, 2 * L };
-    MOAI_TRY(hy_decompose(c, tab, tg, L, alpha, B, hy_at(wsp, w, HY_T), ext, s));
-    MOAI_TRY(hy_mac(c, tg, ext, key, acc, L, alpha, B, s));
+    MOAI_TRY(hy_steps14(c, tab, tg, key, L, alpha, B, wsp, w, s));
     // the lift of the one data row among the sources (the rows below it take theirs in the last kernel)
     HyLiftArgs lf;
     lf.acc = acc;
@@ -966,7 +1137,7 @@ static int hy_rescale_entry(moai_ctx *c, const uint64_t *x, const uint64_t *y, b
     MOAI_TRY(hy_table(c, L, alpha, &tab));
     MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
     // 3 L rows in front: the three-polynomial product
-    const HyPlan w = hy_plan_rescale(n, L, alpha, batch, product ? 3 * L : 0, hy_budget());
+    const HyPlan w = hy_switch_plan(c, L, alpha, batch, product ? 3 * L : 0, true);
     void *wsp;
     MOAI_TRY(workspace(c, w.total, s, &wsp));
     return for_chunks(batch, w.cb, [&](size_t b0, size_t B) {
@@ -1032,8 +1203,7 @@ static int hy_ptrs_impl(moai_ctx *c, int kind, const uint64_t *const *ins, uint6
         MOAI_TRY(hy_rescale_table(c, L, alpha, &rt));
     }
     const size_t gal_rows = relin ? L : 2 * L; // rows per member of the gathered target
-    const HyPlan w = rescale ? hy_plan_rescale(c->n, L, alpha, n, gal_rows, hy_budget(), KS_LIST_MAX)
-                             : hy_plan_switch(c->n, L, alpha, n, gal_rows, hy_budget(), KS_LIST_MAX);
+    const HyPlan w = hy_switch_plan(c, L, alpha, n, gal_rows, rescale, KS_LIST_MAX);
     const size_t sz_list = align256(sizeof(KsList));
     void *wsp;
     MOAI_TRY(workspace(c, sz_list + w.total, s, &wsp));
@@ -1165,6 +1335,16 @@ extern "C" size_t moai_hybrid_digits(const moai_ctx *c, size_t alpha, size_t L)
         return 0;
     }
     return hy_beta(L, alpha);
+}
+
+extern "C" size_t moai_hybrid_fused_groups(const moai_ctx *c, size_t L, size_t alpha, size_t batch)
+{
+    if (hy_check(c, alpha, L, true) || !hy_fused(c) || batch == 0)
+    {
+        return 0;
+    }
+    const HyPlan w = hy_switch_plan(c, L, alpha, batch, 0, false);
+    return hy_fused_plan(c, L, alpha, w.cb, w.G).size();
 }
 
 extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,

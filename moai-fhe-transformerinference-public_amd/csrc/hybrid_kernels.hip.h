@@ -5,6 +5,7 @@
 
 #include "launch.h"
 #include "modarith.hip.h"
+#include "ntt_kernels.hip.h"
 
 namespace moai {
 
@@ -864,6 +865,493 @@ __global__ __launch_bounds__(256) void hy_rescale_finalize_kernel(std::condition
         t.x = csub(mul_shoup_lazy(c.x, qi.w, qi.wq, q), q);
         t.y = csub(mul_shoup_lazy(c.y, qi.w, qi.wq, q), q);
         o[x] = add2(r, t, q);
+    }
+}
+
+// ---- the fused switch (MOAI_HYBRID_FUSED): steps 2-4 as two passes around the forward transform ------------------------------------
+// Steps 2-4 of the unfused chain move, per converted coefficient, 8 B out of the conversion, 32 B through the two transform passes
+// and 8 B back into the MAC.  Here the fast base conversion rides on the strided pass's loads (hy_fwd_strided) and the contiguous
+// pass multiplies every finished digit straight into the accumulators (hy_contig_mac8): a converted row exists only as the strided
+// pass's output, tmp [B][G][beta][N] for the G output rows of a launch, and a transformed digit never reaches memory.  What the
+// two kernels leave in acc [B][2][L + alpha][N] are the canonical residues hy_mac_kernel leaves -- the same sums modulo the same
+// primes -- so everything behind step 4 runs unchanged.  ks_fwd_strided / ks_contig_mac8 (keyswitch_kernels.hip.h) are the alpha = 1
+// shape of the same pair; these serve digits of up to HY_MAX_ALPHA primes and hybrid.hip's row order.
+
+// the output rows of one launch pair: rows of one arithmetic mode (32-bit entries: scalar loads, see RowMap).  The unused entries
+// repeat the first member.
+struct HyFusedGroup
+{
+    uint32_t prime[MOAI_MAX_RNS]; // context prime of member g
+    uint32_t row[MOAI_MAX_RNS];   // its row of L + alpha
+};
+
+struct HyScaleArgs
+{
+    uint64_t *t; // [B][L][N], coefficient form, canonical: scaled in place
+    const HyConv *cv;
+    HyDims d;
+};
+
+// step 2's scaled residues, once per ciphertext: y_r = c_r [(D_j / q_r)^-1]_{q_r} over the L rows of t = INTT(c), in place (nothing
+// else reads t: a digit's own rows come from the NTT-form target).  blockIdx.y = b * L + r.  The product hy_convert_kernel forms per
+// conversion (src_pre = 0 in a mod-up), here outside the loop over the L + alpha - |R_j| target rows.
+__global__ __launch_bounds__(256) void hy_scale_digits_kernel(HyScaleArgs g)
+{
+    const HyDims &d = g.d;
+    const uint32_t row = blockIdx.y % d.L, j = row / d.alpha;
+    const uint64_t q = d.pc[row].q;
+    const Tw inv = g.cv[j].src_inv[row - j * d.alpha];
+    ulonglong2 *t = reinterpret_cast<ulonglong2 *>(g.t) + (size_t)blockIdx.y * d.n2;
+    for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < d.n2; x += gridDim.x * 256u)
+    {
+        ulonglong2 v = t[x];
+        v.x = csub(mul_shoup_lazy(v.x, inv.w, inv.wq, q), q);
+        v.y = csub(mul_shoup_lazy(v.y, inv.w, inv.wq, q), q);
+        t[x] = v;
+    }
+}
+
+// strided_load_raw's index (ntt_kernels.hip.h: element j * 256 + tid of a tile, as the OR of its three fields) for one j, for a pass
+// that does not take all sixteen values at once
+template <int LOGN>
+__device__ __forceinline__ uint32_t strided_index(int j, uint32_t tid)
+{
+    constexpr int GB = 12 - (LOGN - 8);
+    constexpr uint32_t G = 1u << GB;
+    return GB == 8 ? (uint32_t)j * 256u + tid : ((uint32_t)j << (16 - GB)) | ((tid >> GB) << 8) | (tid & (G - 1));
+}
+
+struct HyP1Args
+{
+    const uint64_t *y; // [B][L][N]: the scaled residues (hy_scale_digits_kernel), coefficient form, canonical
+    uint64_t *tmp;     // [B][G][beta][N] after the strided pass, in the lazy range ks_fwd_strided leaves
+    const Tw *tw;
+    const PrimeConst *pc;
+    const HyConv *cv;  // [beta]: the mod-ups of HyTable
+    HyFusedGroup grp;
+    uint32_t L, alpha, beta;
+    uint32_t G;
+    uint32_t total_work; // B * beta * TPR * G
+};
+
+// The strided pass with the fast base conversion on its loads.  Work item = (ciphertext b, digit j, output row of the group, tile);
+// an item whose row is one of the digit's own primes has nothing to do (hy_contig_mac8 reads the target's NTT-form row there).
+// A thread holds its 16 coefficients as 16 128-bit sums and walks the digit's |R_j| <= 16 source rows in a loop whose trip count is
+// uniform over the workgroup: 16 loads with the tile's strided addressing, then 16 multiply-adds with w[row][r], one scalar load from
+// the digit's HyConv.  No template parameter on the digit size, so no instantiation that holds a whole digit in registers
+// (hy_convert_kernel<16>: 166 VGPRs).  The sixteen loads of a source row are issued as two halves of eight: with all sixteen in flight
+// beside the 64 registers of sums the kernel spilled 3-10 registers per lane at four waves per SIMD, one reload of them inside this
+// loop; in halves it takes 118-120 VGPRs and no scratch.  N = 2^12 (no exchange, no LDS, the sixteen stores off one address) takes
+// 142 and is bounded to three waves instead: at four it spilled 60-68 bytes per lane.
+// At most 16 products below 2^122: the sums stay below 2^126.  Then ONE reduction to the
+// canonical residue -- hy_mod128, since a source residue may be far above the target prime -- in the FP64 modes its conversion to the
+// balanced double (the residue is below q < 2^51: LoadFp52's operation), and strided_core as it is.
+// Order of the work ids, under xcd_remap: the group's output rows fastest, then the tile, the digit, the ciphertext.  The G
+// workgroups that share one (tile, digit, ciphertext) read the same |R_j| source tiles (alpha * 32 KiB) and are neighbours on one
+// XCD, so G - 1 of the G reads come from that XCD's L2.  With ks_fwd_strided's order (tile fastest) the neighbours share a row and
+// the re-use distance of a source tile is a whole digit, alpha * 512 KiB at N = 2^16 per output row, against 4 MiB of L2.  The other
+// order was not measured.
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(256, LOGN == 12 ? 3 : 4) void hy_fwd_strided(HyP1Args a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    constexpr uint32_t TG = 1u << (12 - (LOGN - 8)); // columns of a tile
+    __shared__ uint64_t lds[4096];
+    uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t g = w % a.G;
+    w /= a.G;
+    const uint32_t tile = w % TPR;
+    w /= TPR;
+    const uint32_t j = w % a.beta;
+    const uint32_t b = w / a.beta;
+    const uint32_t prime = __builtin_amdgcn_readfirstlane(a.grp.prime[g]);
+    const uint32_t row = __builtin_amdgcn_readfirstlane(a.grp.row[g]);
+    const uint32_t lo = j * a.alpha, hi = min(lo + a.alpha, a.L), ns = hi - lo;
+    if (row >= lo && row < hi)
+    {
+        return;
+    }
+    const uint32_t tg = row < lo ? row : row - ns; // the row's place among the conversion's targets
+    const HyConv &cv = a.cv[j];
+    const PrimeConst *pc = a.pc + prime;
+    const uint64_t *in = a.y + (((size_t)b * a.L + lo) << LOGN) + tile * TG;
+    uint64_t *out = a.tmp + ((((size_t)b * a.G + g) * a.beta + j) << LOGN);
+    uint64_t x[16], xh[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        x[i] = xh[i] = 0;
+    }
+    for (uint32_t r = 0; r < ns; ++r)
+    {
+        const uint64_t *__restrict__ irow = in + ((size_t)r << LOGN);
+        const uint64_t wr = cv.w[tg][r];
+        // the sixteen loads in two halves of eight: sixteen registers of loads in flight beside the 64 of the sums, not 32
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+        {
+            uint64_t raw[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+            {
+                raw[i] = irow[strided_index<LOGN>(h * 8 + i, threadIdx.x)];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+            {
+                mac128(x[h * 8 + i], xh[h * 8 + i], raw[i], wr);
+            }
+        }
+    }
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        x[i] = hy_mod128(x[i], xh[i], q, cr0, cr1);
+        if (mode_fp(MODE))
+        {
+            x[i] = d2u(fp_red(fp_from_u52(x[i]), u2d(pc->qd), u2d(pc->qinv)));
+        }
+    }
+    strided_core<LOGN, MODE, false>(x, out + tile * TG, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds,
+                                    threadIdx.x);
+}
+
+struct HyP2Args
+{
+    const uint64_t *tmp; // [B][G][beta][N]
+    const uint64_t *tgt; // the target in NTT form: ciphertext b's row r at tgt + ((b * tgt_stride + tgt_off + r) << LOGN)
+    uint32_t tgt_stride, tgt_off;
+    const uint64_t *key; // [beta(k - alpha)][2][k][N]
+    uint64_t *acc;       // [B][2][L + alpha][N], hy_mac_kernel's layout
+    const Tw *tw;
+    const double *tw1;   // FP64 modes: the forward powers as plain doubles
+    const PrimeConst *pc;
+    HyFusedGroup grp;
+    uint32_t L, alpha, beta;
+    uint32_t G;
+    uint32_t k;
+    uint32_t B;
+    uint32_t total_work; // B * 2 TPR * G: 2048-coefficient tiles
+};
+
+struct HyP2ListArgs : HyP2Args
+{
+    const KsList *lst; // ciphertext b's key is lst->keys[b], in the same whole layout (key unused)
+};
+
+// The contiguous pass plus the key MAC over the beta digits of one output row; ks_contig_mac8's structure (its comment has the
+// register layouts P1 / P2 / P3 and the swizzles): a workgroup owns a 2048-coefficient tile of (ciphertext, output row), runs
+// radix-8 / radix-8 / radix-4 with two LDS exchanges that stay inside a wave, and multiplies the eight finished coefficients into
+// the 2 x 8 accumulators from the registers that finish the transform; the FP64 modes keep the thirteen per-thread twiddles of stages
+// 3..7 in registers and the seven of stages 0..2 in LDS across the digit loop.  Where the output row is one of digit j's own primes
+// (row < L, row / alpha = j) the operand is the target's NTT-form row as it is, not tmp.  Key word: key[j][p][prime of the row],
+// k rows per polynomial.
+// Sums, beta <= 63 digits:
+//   M_GUARD    the digit is normalised to its canonical residue: at most 63 products below 2^122, one barrett128 (hy_mac_kernel's sum)
+//   M_NOGUARD  the unreduced digit (below 33 q) goes straight into the MAC; the host picks the mode only where 36 q^2 beta < 2^128
+//              (ks_mode's condition with beta in place of L)
+//   M_FPN      33 q < 2^52: products below 2.5 q as the butterflies left the digit, sixteen of them on a folded sum below 40.5 q < 2^53
+//   M_FPR      the digit folded to |v| <= q / 2, products below 0.88 q, three of them on a folded sum (2^53 / q > 4)
+// (the FP64 bounds are ks_contig_mac8's, which has their derivation: the periods do not depend on the number of digits).
+// LIST: member b's key from the pass's KsList record, as hy_mac_kernel<true>: a scalar load at the head of the workgroup.
+template <int LOGN, int MODE, bool LIST = false>
+__global__ __launch_bounds__(256, 4) void hy_contig_mac8(std::conditional_t<LIST, HyP2ListArgs, HyP2Args> a)
+{
+    constexpr int R1 = LOGN - 8;
+    constexpr uint32_t TPR8 = 1u << (LOGN - 11);
+    __shared__ ulonglong2 lds_a2[1024];
+    __shared__ ulonglong2 lds_b2[1024];
+    constexpr bool TW012 = mode_fp(MODE);
+    __shared__ double lds_tw[TW012 ? 64 : 1];
+    uint64_t *lds_a = reinterpret_cast<uint64_t *>(lds_a2);
+    uint64_t *lds_b = reinterpret_cast<uint64_t *>(lds_b2);
+
+    // ciphertext fastest: the workgroups that read the same key words and twiddles run together
+    uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t bq = w % a.B;
+    w /= a.B;
+    const uint32_t tile = w % TPR8;
+    const uint32_t g = w / TPR8;
+    const uint32_t prime = a.grp.prime[g];
+    const uint32_t row = a.grp.row[g];
+    const uint32_t own = row < a.L ? row / a.alpha : a.beta; // the digit this row belongs to; none for a special row
+    const PrimeConst *pc = a.pc + prime;
+    const uint64_t q = pc->q;
+    const uint64_t bq1 = mode_q<MODE>(*pc), bq2 = mode_q2<MODE>(*pc); // the butterflies' (q, q2) under MODE
+    const Tw *__restrict__ tw = a.tw + ((size_t)prime << LOGN);
+    const double *__restrict__ tw1 = a.tw1 + ((size_t)prime << LOGN);
+    const uint32_t tid0 = threadIdx.x;
+    const uint64_t *key = a.key;
+    if constexpr (LIST)
+    {
+        key = a.lst->keys[bq];
+    }
+
+    uint64_t lo0[8], hi0[8], lo1[8], hi1[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+    {
+        lo0[e] = hi0[e] = lo1[e] = hi1[e] = 0;
+    }
+    const uint64_t *__restrict__ dig = a.tmp + ((((size_t)bq * a.G + g) * a.beta) << LOGN) + ((size_t)tile << 11);
+
+    double twr[13];
+    if (mode_fp(MODE))
+    {
+        const uint32_t b = tid0 >> 5, r = tid0 & 31u, hi3 = r >> 2;
+        const uint32_t blk = (tile << 3) + b;
+        twr[0] = tw1[(1u << (R1 + 3)) + (blk << 3) + hi3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+        {
+            twr[1 + i] = tw1[(1u << (R1 + 4)) + (blk << 4) + ((hi3 << 1) | (uint32_t)i)];
+            twr[7 + i] = tw1[(1u << (R1 + 6)) + (blk << 6) + ((r << 1) | (uint32_t)i)];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+        {
+            twr[3 + i] = tw1[(1u << (R1 + 5)) + (blk << 5) + ((hi3 << 2) | (uint32_t)i)];
+            twr[9 + i] = tw1[(1u << (R1 + 7)) + (blk << 7) + ((r << 2) | (uint32_t)i)];
+        }
+    }
+    if (TW012)
+    {
+        if (tid0 < 64u && (tid0 & 7u) < 7u)
+        {
+            const uint32_t b_ = tid0 >> 3, i = tid0 & 7u;
+            const uint32_t u = i == 0 ? 0u : (i < 3 ? 1u : 2u);
+            lds_tw[tid0] = tw1[(1u << (R1 + u)) + ((((uint32_t)tile << 3) + b_) << u) + (i - ((1u << u) - 1u))];
+        }
+        lds_barrier(); // written by wave 0, read by all four
+    }
+    for (uint32_t J = 0; J < a.beta; ++J)
+    {
+        // opaque copy of the thread index: keeps the per-thread address arithmetic inside the loop instead of hoisted into (and
+        // spilled from) registers the accumulators need
+        uint32_t tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const uint32_t b = tid >> 5;
+        const uint32_t r = tid & 31u;
+        const uint32_t hi3 = r >> 2, lo2 = r & 3u;
+        const uint32_t blk = (tile << 3) + b;
+        // chunk (16 bytes = 2 coefficients) of this thread's 8 contiguous coefficients inside the tile
+        const uint32_t ch0 = (b << 7) | (r << 2);
+        const uint64_t *__restrict__ base = dig + ((size_t)J << LOGN);
+        uint64_t x[8];
+        const bool direct = (own == J); // workgroup-uniform
+        const ulonglong2 *__restrict__ k0 =
+            reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 0) * a.k + prime) << LOGN)) + ((size_t)tile << 10) + ch0;
+        const ulonglong2 *__restrict__ k1 =
+            reinterpret_cast<const ulonglong2 *>(key + (((size_t)(J * 2 + 1) * a.k + prime) << LOGN)) + ((size_t)tile << 10) + ch0;
+        if (direct)
+        {
+            // digit under one of its own primes: canonical NTT-form values straight from the target row
+            const ulonglong2 *__restrict__ trow =
+                reinterpret_cast<const ulonglong2 *>(a.tgt + (((size_t)bq * a.tgt_stride + a.tgt_off + row) << LOGN)) + ((size_t)tile << 10) + ch0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                ulonglong2 v = trow[c];
+                // FP64 modes: as doubles, like the values the butterflies leave (canonical below q: nothing to fold)
+                x[2 * c] = mode_fp(MODE) ? d2u(fp_from_u52(v.x)) : v.x;
+                x[2 * c + 1] = mode_fp(MODE) ? d2u(fp_from_u52(v.y)) : v.y;
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+            {
+                x[j] = base[(b << 8) | ((uint32_t)j << 5) | r];
+            }
+            // stages 0..2: layout P1
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+            {
+                const int half = 4 >> u;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                {
+                    if (!(j & half))
+                    {
+                        if (mode_fp(MODE))
+                        {
+                            ct_bfly_fp1_sel(x[j], x[j + half], lds_tw[(b << 3) + ((1u << u) - 1u) + (uint32_t)(j >> (3 - u))], u2d(bq1),
+                                            u2d(bq2), MODE == M_FPR && !(u & 1));
+                        }
+                        else
+                        {
+                            Tw t = tw[(1u << (R1 + u)) + (blk << u) + (uint32_t)(j >> (3 - u))];
+                            ct_bfly_t<MODE>(x[j], x[j + half], t.w, t.wq, bq1, bq2);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+            {
+                lds_a[phys8_a((b << 8) | ((uint32_t)j << 5) | r)] = x[j];
+            }
+            lds_wave_sync(); // block b's 32 threads are half a wave: both exchanges stay inside one wave
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+            {
+                x[j] = lds_a[phys8_a((b << 8) | (hi3 << 5) | ((uint32_t)j << 2) | lo2)];
+            }
+            // stages 3..5: layout P2
+#pragma unroll
+            for (int u = 3; u < 6; ++u)
+            {
+                const int half = 4 >> (u - 3);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                {
+                    if (!(j & half))
+                    {
+                        uint32_t t_ = (hi3 << 5) | ((uint32_t)j << 2) | lo2;
+                        if (mode_fp(MODE))
+                        {
+                            ct_bfly_fp1_sel(x[j], x[j + half], twr[(u == 3) ? 0 : (u == 4) ? 1 + (j >> 2) : 3 + (j >> 1)], u2d(bq1), u2d(bq2),
+                                            MODE == M_FPR && !(u & 1));
+                        }
+                        else
+                        {
+                            Tw t = tw[(1u << (R1 + u)) + (blk << u) + (t_ >> (8 - u))];
+                            ct_bfly_t<MODE>(x[j], x[j + half], t.w, t.wq, bq1, bq2);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+            {
+                lds_b[phys8_b((b << 8) | (hi3 << 5) | ((uint32_t)j << 2) | lo2)] = x[j];
+            }
+            lds_wave_sync();
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                // coefficients (r << 3) | 2c, 2c+1: chunk c of the row, stored at chunk c ^ ((r >> 2) & 3)
+                ulonglong2 v = lds_b2[((b << 8) | (r << 3)) / 2 + ((uint32_t)c ^ ((r >> 2) & 3u))];
+                x[2 * c] = v.x;
+                x[2 * c + 1] = v.y;
+            }
+            // stages 6..7: layout P3
+#pragma unroll
+            for (int u = 6; u < 8; ++u)
+            {
+                const int half = 2 >> (u - 6);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                {
+                    if (!(j & half))
+                    {
+                        uint32_t t_ = (r << 3) | (uint32_t)j;
+                        if (mode_fp(MODE))
+                        {
+                            ct_bfly_fp1_sel(x[j], x[j + half], twr[(u == 6) ? 7 + (j >> 2) : 9 + (j >> 1)], u2d(bq1), u2d(bq2),
+                                            MODE == M_FPR && !(u & 1));
+                        }
+                        else
+                        {
+                            Tw t = tw[(1u << (R1 + u)) + (blk << u) + (t_ >> (8 - u))];
+                            ct_bfly_t<MODE>(x[j], x[j + half], t.w, t.wq, bq1, bq2);
+                        }
+                    }
+                }
+            }
+        }
+        if (mode_fp(MODE))
+        {
+            // the MAC on the FP64 pipe (fp_mulmod_q, the key residue canonical below 2^51); the sixteen key residues are all issued at
+            // the head, with one wait, and one wave-uniform branch goes around the sixteen periodic reductions (ks_contig_mac8 measured
+            // that arrangement)
+            const bool fold = MODE == M_FPR ? (J % 3u == 2u) : ((J & 15u) == 15u);
+            const double qd = u2d(bq1), qinv = u2d(bq2);
+            ulonglong2 kpa[4], kpb[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                kpa[c] = k0[c];
+                kpb[c] = k1[c];
+            }
+            double sm[16];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                const double vx = MODE == M_FPN ? u2d(x[2 * c]) : fp_red(u2d(x[2 * c]), qd, qinv);
+                const double vy = MODE == M_FPN ? u2d(x[2 * c + 1]) : fp_red(u2d(x[2 * c + 1]), qd, qinv);
+                sm[4 * c + 0] = u2d(lo0[2 * c]) + fp_mulmod_q(vx, fp_from_u52(kpa[c].x), qd, qinv);
+                sm[4 * c + 1] = u2d(lo0[2 * c + 1]) + fp_mulmod_q(vy, fp_from_u52(kpa[c].y), qd, qinv);
+                sm[4 * c + 2] = u2d(lo1[2 * c]) + fp_mulmod_q(vx, fp_from_u52(kpb[c].x), qd, qinv);
+                sm[4 * c + 3] = u2d(lo1[2 * c + 1]) + fp_mulmod_q(vy, fp_from_u52(kpb[c].y), qd, qinv);
+            }
+            if (fold)
+            {
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                {
+                    sm[i] = fp_red(sm[i], qd, qinv);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                lo0[2 * c] = d2u(sm[4 * c + 0]);
+                lo0[2 * c + 1] = d2u(sm[4 * c + 1]);
+                lo1[2 * c] = d2u(sm[4 * c + 2]);
+                lo1[2 * c + 1] = d2u(sm[4 * c + 3]);
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+            {
+                uint64_t vx = x[2 * c], vy = x[2 * c + 1];
+                if (MODE == M_GUARD && !direct)
+                {
+                    vx = csub(csub(vx, bq2), q);
+                    vy = csub(csub(vy, bq2), q);
+                }
+                ulonglong2 ka = k0[c];
+                ulonglong2 kb = k1[c];
+                mac128(lo0[2 * c], hi0[2 * c], vx, ka.x);
+                mac128(lo0[2 * c + 1], hi0[2 * c + 1], vy, ka.y);
+                mac128(lo1[2 * c], hi1[2 * c], vx, kb.x);
+                mac128(lo1[2 * c + 1], hi1[2 * c + 1], vy, kb.y);
+            }
+        }
+        // no barrier here: the next digit writes buffer A, whose readers of this wave all passed the second wait above, and buffer B
+        // is written again only behind the next first wait
+    }
+    const uint32_t ch0 = ((tid0 >> 5) << 7) | ((tid0 & 31u) << 2);
+    const uint64_t cr0 = pc->cr0, cr1 = pc->cr1;
+    const size_t rows = a.L + a.alpha;
+    ulonglong2 *__restrict__ o0 = reinterpret_cast<ulonglong2 *>(a.acc + ((((size_t)bq * 2 + 0) * rows + row) << LOGN)) + ((size_t)tile << 10) + ch0;
+    ulonglong2 *__restrict__ o1 = reinterpret_cast<ulonglong2 *>(a.acc + ((((size_t)bq * 2 + 1) * rows + row) << LOGN)) + ((size_t)tile << 10) + ch0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+    {
+        ulonglong2 r0, r1;
+        if (mode_fp(MODE))
+        {
+            const double qd = u2d(bq1), qinv = u2d(bq2);
+            r0.x = fp_to_canonical(u2d(lo0[2 * c]), qd, qinv);
+            r0.y = fp_to_canonical(u2d(lo0[2 * c + 1]), qd, qinv);
+            r1.x = fp_to_canonical(u2d(lo1[2 * c]), qd, qinv);
+            r1.y = fp_to_canonical(u2d(lo1[2 * c + 1]), qd, qinv);
+        }
+        else
+        {
+            r0.x = barrett128(lo0[2 * c], hi0[2 * c], q, cr0, cr1);
+            r0.y = barrett128(lo0[2 * c + 1], hi0[2 * c + 1], q, cr0, cr1);
+            r1.x = barrett128(lo1[2 * c], hi1[2 * c], q, cr0, cr1);
+            r1.y = barrett128(lo1[2 * c + 1], hi1[2 * c + 1], q, cr0, cr1);
+        }
+        o0[c] = r0;
+        o1[c] = r1;
     }
 }
 

@@ -36,6 +36,8 @@ enum HyRegion
     HY_TGT,   // bsgs: the permuted c1' of a giant step, with its t and digits
     HY_T2,
     HY_EXT2,
+    HY_Y,     // fused: t scaled in place, the conversions' source rows
+    HY_TMP,   // fused: the strided pass's output for the output rows of a launch, per (output row in flight, ciphertext)
     HY_REGIONS
 };
 
@@ -117,6 +119,12 @@ inline size_t hy_grid_cap(size_t L, size_t alpha)
     return 65535 / (2 * (L + alpha));
 }
 
+// the merged relinearize + rescale: the widest grid runs over 3 * cb * L rows with the product, 2 * cb * (L + alpha) without
+inline size_t hy_rescale_grid_cap(size_t L, size_t alpha)
+{
+    return 65535 / std::max(2 * (L + alpha), 3 * L);
+}
+
 // ---- the three chunk policies ---------------------------------------------------------------------------------------------------
 // ciphertexts only: as many as the budget holds, at least one, at most grid_cap, limit and batch
 inline void hy_size_cts(HyPlan &p, size_t n, size_t batch, size_t budget, size_t grid_cap, size_t limit)
@@ -173,6 +181,25 @@ inline void hy_size_groups_first(HyPlan &p, size_t n, size_t L, size_t alpha, si
     const size_t chunks = (batch + cb - 1) / cb;
     p.cb = (batch + chunks - 1) / chunks;
     p.G = G;
+    p.place(n);
+}
+
+// ciphertexts, then output rows beside them (the fused switch): as many ciphertexts as fit with one output row in flight, at most
+// grid_cap, limit and batch; then as many output rows as fit beside them, at most `rows`; at least one of each.  The groups are cut
+// by the launches, not by a grid over (group, ciphertext) pairs, so no cap couples the two.
+inline void hy_size_cts_then_rows(HyPlan &p, size_t n, size_t batch, size_t rows, size_t budget, size_t grid_cap, size_t limit)
+{
+    const size_t row = n * sizeof(unsigned long long);
+    const size_t shared = p.shared_rows * row, grp = p.group_rows * row;
+    size_t cb = budget / (shared + grp);
+    cb = cb < 1 ? 1 : cb;
+    cb = cb > grid_cap ? grid_cap : cb;
+    cb = cb < batch ? cb : batch;
+    cb = cb < limit ? cb : limit;
+    size_t G = budget / cb > shared ? (budget / cb - shared) / grp : 0;
+    G = G < 1 ? 1 : G;
+    p.cb = cb;
+    p.G = G < rows ? G : rows;
     p.place(n);
 }
 
@@ -243,7 +270,24 @@ inline HyPlan hy_plan_rescale(size_t n, size_t L, size_t alpha, size_t batch, si
     hy_add_digits(p, L, alpha);
     hy_add_acc(p, HY_ACC, L, alpha);
     hy_add_mod_down(p, HY_X, HY_CONV, 2, alpha + 1, L - 1);
-    hy_size_cts(p, n, batch, budget, 65535 / std::max(2 * (L + alpha), 3 * L), limit);
+    hy_size_cts(p, n, batch, budget, hy_rescale_grid_cap(L, alpha), limit);
+    return p;
+}
+
+// The fused switch and the fused relinearize + rescale (MOAI_HYBRID_FUSED): y = t scaled in place takes the place of t, and the
+// converted rows of every digit exist only as tmp, beta rows per output row in flight (G of the L + alpha).  The mod-down behind
+// step 4 is the family's own: (alpha, L) sources and targets for the switch, (alpha + 1, L - 1) for the rescale; head_rows, limit
+// and grid_cap as in hy_plan_switch / hy_plan_rescale.
+inline HyPlan hy_plan_fused(size_t n, size_t L, size_t alpha, size_t batch, size_t head_rows, size_t md_src, size_t md_tgt, size_t budget,
+                            size_t grid_cap, size_t limit = HY_NO_LIMIT)
+{
+    HyPlan p;
+    p.add(HY_HEAD, head_rows);
+    p.add(HY_Y, L);
+    p.add(HY_TMP, hy_beta(L, alpha), true);
+    hy_add_acc(p, HY_ACC, L, alpha);
+    hy_add_mod_down(p, HY_X, HY_CONV, 2, md_src, md_tgt);
+    hy_size_cts_then_rows(p, n, batch, L + alpha, budget, grid_cap, limit);
     return p;
 }
 

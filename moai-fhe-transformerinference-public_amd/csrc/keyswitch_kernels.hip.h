@@ -155,17 +155,7 @@ struct KsP2ListArgs : KsP2Args
 //   P2  t = (r >> 2) << 5 | j << 2 | (r & 3)      stages 3..5 (t bits 4..2)
 //   P3  t = r << 3 | j                            stages 6..7 (t bits 1..0); 8 contiguous coefficients
 // LDS swizzles keep every exchange conflict free: exchange 1 stores t with bits 4..2 ^= bits 7..5, exchange 2
-// stores t with bits 2..1 ^= bits 6..5.
-__device__ __forceinline__ uint32_t phys8_a(uint32_t e)
-{
-    return e ^ (((e >> 5) & 7u) << 2);
-}
-
-__device__ __forceinline__ uint32_t phys8_b(uint32_t e)
-{
-    return e ^ (((e >> 5) & 3u) << 1);
-}
-
+// stores t with bits 2..1 ^= bits 6..5 (phys8_a, phys8_b: ntt_kernels.hip.h, shared with the hybrid switch's contiguous pass).
 // FP64 modes: the digit's sixteen key residues per thread (eight 16-byte loads) are all issued at the head of the MAC, with one wait,
 // and one branch goes around the sixteen periodic reductions.  Measured in round 3 (profiles/r03_b_ks_kernel_variants_ab.txt;
 // l = 35, batch 64, per key switch): 0.529 ms this way; 0.572 ms with the loads next to the products that use them and a reduction

@@ -1493,4 +1493,17 @@ __global__ __launch_bounds__(256) void ntt_stage_global(NttArgs a, int logn, int
     row[i1] = y;
 }
 
+// the two exchanges of the 8-coefficients-per-thread contiguous passes with the key MAC behind them (ks_contig_mac8,
+// hy_contig_mac8; keyswitch_kernels.hip.h states the register layouts): exchange 1 stores t with bits 4..2 ^= bits 7..5, exchange 2
+// stores t with bits 2..1 ^= bits 6..5
+__device__ __forceinline__ uint32_t phys8_a(uint32_t e)
+{
+    return e ^ (((e >> 5) & 7u) << 2);
+}
+
+__device__ __forceinline__ uint32_t phys8_b(uint32_t e)
+{
+    return e ^ (((e >> 5) & 3u) << 1);
+}
+
 } // namespace moai

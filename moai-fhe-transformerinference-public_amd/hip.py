@@ -108,6 +108,7 @@ SYMBOLS = {
     "moai_apply_galois_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
     "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
     "moai_hybrid_digits": (sz, [vp, sz, sz]),
+    "moai_hybrid_fused_groups": (sz, [vp, sz, sz, sz]),
     "moai_hybrid_keygen": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, vp, vp]),
     "moai_switch_key_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_relinearize_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
@@ -404,6 +405,14 @@ class Context:
         if d == 0:
             _check(MOAI_EINVAL)
         return int(d)
+
+    def hybrid_fused_groups(self, L, alpha, batch=1):
+        """output-row groups the fused hybrid switch (MOAI_HYBRID_FUSED) would launch now per chunk of `batch` ciphertexts; 0: the
+        call takes the unfused path (moai_hybrid_fused_groups; no launch).  A refused (L, alpha) raises."""
+        g = int(lib().moai_hybrid_fused_groups(self.h, L, alpha, batch))
+        if g == 0 and lib().moai_hybrid_digits(self.h, alpha, L) == 0:
+            _check(MOAI_EINVAL)
+        return g
 
     # include/moai_hip.h, "hybrid rounding mode": HYBRID_ROUND_FAST (the default) or HYBRID_ROUND_EXACT, per context
     def hybrid_set_rounding(self, mode):
