@@ -583,7 +583,8 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
  *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight
  *   MOAI_HYBRID_HOIST_NR   4     rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1
- *   MOAI_HYBRID_FUSED      0     1: hybrid switches at N >= 2^12 run mod-up, forward transform and key product as two fused passes */
+ *   MOAI_HYBRID_FUSED      0     1: hybrid switches at N >= 2^12 run mod-up, forward transform and key product as two fused passes
+ *   MOAI_HYBRID_FUSED_DOWN 0     1: hybrid mod-downs at N >= 2^12 run base conversion and division inside the forward transform's two passes */
 int moai_set_tuning(const char *name, long value);
 int moai_reset_tuning(void);
 /* The schedule moai_ntt_forward / moai_ntt_inverse would take for n_poly polynomials of L rows of n coefficients with chunks of
@@ -740,6 +741,20 @@ int moai_key_register(moai_ctx *ctx, const uint64_t *key, size_t levels);
  * to G.  0 when the call would take the unfused steps -- MOAI_HYBRID_FUSED = 0, N < 2^12, batch = 0 -- or when (L, alpha) is
  * refused, with the error set then.  Read-only: no launch, no stream. */
 size_t moai_hybrid_fused_groups(const moai_ctx *ctx, size_t L, size_t alpha, size_t batch);
+/* Fused mod-down (MOAI_HYBRID_FUSED_DOWN = 1, N >= 2^12; off by default, without effect below 2^12, independent of
+ * MOAI_HYBRID_FUSED): step 5 of every call of this section and of the sections below -- the switches and their list forms, the
+ * hoisted rotations, one per sum of moai_hybrid_rotate_pt_dot, the final one of moai_hybrid_bsgs_dot, the merged mod-down of the
+ * relinearize + rescale calls -- keeps its INTT of the source rows, scales them once per coefficient (and, in
+ * MOAI_HYBRID_ROUND_EXACT, forms the overflow v there, by the operations the contract states), and then runs, per arithmetic mode
+ * present among the output rows (MOAI_NTT_FP, MOAI_MD_FP_MIN_ROWS), the strided pass of the forward transform with the conversion's
+ * sums on its loads and the contiguous pass with the division and the addends on its stores.  The inner c1-only mod-down of
+ * moai_hybrid_bsgs_dot keeps the unfused stages.  No scratch is added: the scratch formulas of every call hold as stated.  Results do
+ * not depend on the knob: every output row is the same canonical residue, in both rounding modes.
+ * The query: the launch pairs (strided + contiguous) the fused mod-down of `polys` polynomials to L rows at (L, alpha) would take
+ * NOW, one per arithmetic mode present among the data primes i < L.  0 when the call would take the unfused stages --
+ * MOAI_HYBRID_FUSED_DOWN = 0, N < 2^12, polys = 0 -- or when (L, alpha) is refused, with the error set then.  Read-only: no launch,
+ * no stream. */
+size_t moai_hybrid_fused_down_launches(const moai_ctx *ctx, size_t L, size_t alpha, size_t polys);
 /* beta(L) = ceil(L / alpha), the digits SEAL/evaluator.cpp:2724-3020 would loop over at alpha = 1; 0 and the error set when refused */
 size_t moai_hybrid_digits(const moai_ctx *ctx, size_t alpha, size_t L);
 /* KeyGenerator::generate_one_kswitch_key, SEAL/keygenerator.cpp:303-336, with digits of alpha primes and P for the special prime */

@@ -39,6 +39,15 @@
 // output rows of one arithmetic mode, hy_fwd_strided (the base conversion on the strided pass's loads) and hy_contig_mac8 (the
 // contiguous pass with the key MAC behind it): no ext, no transformed digit in memory, the same canonical accumulators.  The hoisted,
 // pt-dot and BSGS families read the transformed digits from memory and keep the unfused steps.
+// Fused step 5 (MOAI_HYBRID_FUSED_DOWN=1, N >= 2^12; off by default, independent of MOAI_HYBRID_FUSED): wherever a family runs
+// { hy_mod_down, last kernel } -- hy_switch_chunk, hy_hoist_chunk_run, hy_dot_chunk_run, the final mod-down of hy_bsgs_chunk_run,
+// hy_rescale_chunk_run -- it calls hy_mod_down_fused instead (hy_step5_fused, or hy_step5_fused_groups where every rotation or sum
+// has an output and an addend of its own): the INTT of the source rows, unchanged; hy_down_scale_kernel, the conversion's per-source
+// work once per coefficient and, in exact mode, the overflow v written to the accumulator's first source row; then per arithmetic
+// mode present among the output rows (keyswitch.hip moddown's rule) hy_down_strided, the conversion's sums on the strided pass's
+// loads, and hy_down_contig or hy_rescale_contig, the division and the addends on the contiguous pass's stores.  The same scratch
+// regions (x, conv), the same canonical outputs in both rounding modes.  The inner c1-only mod-down of the BSGS sum scatters through a
+// permutation (hy_c1_moddown_permute_kernel) and keeps the unfused stages.
 // Every transform goes through ntt_launch with a RowMap.  The constants of one (L, alpha) live in one device block (HyTable)
 // that the context owns.
 //
@@ -503,6 +512,194 @@ static int hy_steps14(moai_ctx *c, const HyTable *tab, const KsTarget &tg, const
     return MOAI_OK;
 }
 
+// ---- step 5 fused into the forward transform's passes (MOAI_HYBRID_FUSED_DOWN) -----------------------------------------------------------
+// whether the mod-downs take the fused passes now: the knob, and a ring the tiled kernels exist for
+static bool hy_fused_down(const moai_ctx *c)
+{
+    return tuning(K_HYBRID_FUSED_DOWN) != 0 && c->logn >= 12;
+}
+
+// The output rows i < ntgt of a mod-down of `polys` polynomials that run in arithmetic `mode`; returns how many.  keyswitch.hip's
+// rule (moddown): ntt_mode, with the FP64 modes from MOAI_MD_FP_MIN_ROWS polynomials * rows.
+static uint32_t hy_down_rows(const moai_ctx *c, size_t polys, size_t ntgt, int mode, RowMap *sel)
+{
+    const bool allow_fp = (long)(polys * ntgt) >= tuning(K_MD_FP_MIN_ROWS);
+    uint32_t cnt = 0;
+    for (size_t i = 0; i < ntgt; ++i)
+    {
+        if (ntt_mode(c, (uint32_t)i, allow_fp) == mode)
+        {
+            sel->idx[cnt++] = (uint32_t)i;
+        }
+    }
+    return cnt;
+}
+
+// where the contiguous pass of a fused mod-down puts its quotients and what it adds to them
+struct HyDownTail
+{
+    uint64_t *out = nullptr;            // [polys][ntgt][N]; unused with lst
+    KsAddend add;                       // the plain mod-down's addends (moddown_finalize's)
+    const KsList *lst = nullptr;        // the list forms: outputs, sums and inputs per member
+    const HyRescaleTable *rt = nullptr; // set: the merged relinearize + rescale (hy_rescale_contig), c_p from ct3 or the list
+    const uint64_t *ct3 = nullptr;
+};
+
+// the source rows of a fused mod-down: x [polys][nsrc][N] = INTT(rows off .. off + nsrc - 1 of every `stride` rows at acc), scaled in
+// place; in exact mode the overflow row lands in the first source row of the accumulator (hy_down_scale_kernel says why it may)
+static int hy_down_sources(moai_ctx *c, const HyConv *cv, uint64_t *acc, size_t stride, size_t off, size_t nsrc, size_t ntgt, size_t polys,
+                           uint64_t *x, size_t L, size_t alpha, bool exact, hipStream_t s)
+{
+    RowMap rm{};
+    hy_rowmap(c, L, alpha, 0, ntgt, &rm);
+    MOAI_TRY(ntt_launch(c, x, polys, nsrc, rm, true, s, acc, stride, off));
+    HyDownScaleArgs g;
+    g.x = x;
+    g.v = acc + off * c->n;
+    g.cv = cv;
+    g.pc = c->pc;
+    g.v_stride = (uint32_t)stride;
+    g.n2 = (uint32_t)(c->n >> 1);
+    return exact ? launch_rows(hy_down_scale_kernel<true>, c, polys, s, g) : launch_rows(hy_down_scale_kernel<false>, c, polys, s, g);
+}
+
+// one pair of launches: the output rows `sel` of `polys` polynomials, all of arithmetic MODE
+template <int LOGN, int MODE>
+static int hy_down_pair(moai_ctx *c, const HyConv *cv, const Tw *inv, const uint64_t *acc, size_t stride, size_t off, size_t ntgt,
+                        size_t polys, const uint64_t *x, uint64_t *conv, const RowMap &sel, uint32_t Lsel, size_t L, size_t alpha, bool exact,
+                        const HyDownTail &t, hipStream_t s)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    if (polys * Lsel * TPR > 0x7fffffffull)
+    {
+        return set_error(MOAI_EINVAL, "batch too large for one launch");
+    }
+    const TwPair tw = twiddles(c, MODE, false);
+    HyDownP1Args p1;
+    p1.x = x;
+    p1.v = acc + off * c->n;
+    p1.conv = conv;
+    p1.tw = tw.tw;
+    p1.pc = c->pc;
+    p1.cv = cv;
+    p1.sel = sel;
+    p1.Lsel = Lsel;
+    p1.v_stride = (uint32_t)stride;
+    p1.exact = exact ? 1u : 0u;
+    p1.total_work = (uint32_t)(polys * TPR * Lsel);
+    hipLaunchKernelGGL((hy_down_strided<LOGN, MODE>), dim3(p1.total_work), dim3(256), 0, s, p1);
+    MOAI_LAUNCH_CHECK();
+    if (t.rt)
+    {
+        HyRescaleP2Args p2;
+        p2.conv = conv;
+        p2.acc = acc;
+        p2.ct3 = t.ct3;
+        p2.out = t.out;
+        p2.tw = tw.tw;
+        p2.twb = tw.twb;
+        p2.pc = c->pc;
+        p2.winv = t.rt->winv; // device address arithmetic only
+        p2.qinv = t.rt->qinv;
+        p2.L = (uint32_t)L;
+        p2.alpha = (uint32_t)alpha;
+        p2.P = (uint32_t)polys;
+        p2.total_work = p1.total_work;
+        p2.sel = sel;
+        p2.Lsel = Lsel;
+        return plain_or_list<HyRescaleP2ListArgs>(p2, t.lst, [&](const auto &args, auto LIST) {
+            hipLaunchKernelGGL((hy_rescale_contig<LOGN, MODE, decltype(LIST)::value>), dim3(p2.total_work), dim3(256), 0, s, args);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        });
+    }
+    HyDownP2Args p2;
+    p2.conv = conv;
+    p2.acc = acc;
+    p2.out = t.out;
+    p2.tw = tw.tw;
+    p2.twb = tw.twb;
+    p2.pc = c->pc;
+    p2.inv = inv;
+    p2.addend = t.add.ptr;
+    p2.addend2 = t.add.second;
+    p2.addend_bstride = (uint32_t)t.add.bstride;
+    p2.add_mode = t.add.mode;
+    p2.acc_stride = (uint32_t)stride;
+    p2.ntgt = (uint32_t)ntgt;
+    p2.P = (uint32_t)polys;
+    p2.total_work = p1.total_work;
+    p2.sel = sel;
+    p2.Lsel = Lsel;
+    return plain_or_list<HyDownP2ListArgs>(p2, t.lst, [&](const auto &args, auto LIST) {
+        hipLaunchKernelGGL((hy_down_contig<LOGN, MODE, decltype(LIST)::value>), dim3(p2.total_work), dim3(256), 0, s, args);
+        MOAI_LAUNCH_CHECK();
+        return MOAI_OK;
+    });
+}
+
+// the passes of a fused mod-down behind hy_down_sources, for `polys` polynomials at acc / x / conv: one strided + one contiguous launch
+// per arithmetic mode present among the output rows; fp_polys: the polynomials of the whole mod-down, which decide the modes
+static int hy_down_passes(moai_ctx *c, const HyConv *cv, const Tw *inv, const uint64_t *acc, size_t stride, size_t off, size_t ntgt,
+                          size_t polys, size_t fp_polys, const uint64_t *x, uint64_t *conv, size_t L, size_t alpha, bool exact,
+                          const HyDownTail &t, hipStream_t s)
+{
+    for (int mode = M_GUARD; mode <= M_FPR; ++mode)
+    {
+        RowMap sel{};
+        const uint32_t Lsel = hy_down_rows(c, fp_polys, ntgt, mode, &sel);
+        if (!Lsel)
+        {
+            continue;
+        }
+        MOAI_TRY(dispatch_logn(c->logn, [&](auto LG) {
+            return dispatch<M_GUARD, M_NOGUARD, M_FPN, M_FPR>("mod-down arithmetic mode ", mode, [&](auto MD) {
+                return hy_down_pair<decltype(LG)::value, decltype(MD)::value>(c, cv, inv, acc, stride, off, ntgt, polys, x, conv, sel, Lsel, L,
+                                                                              alpha, exact, t, s);
+            });
+        }));
+    }
+    return MOAI_OK;
+}
+
+// What replaces the pair { hy_mod_down, last kernel } under MOAI_HYBRID_FUSED_DOWN, hy_mod_down's arguments with the divisor's inverse
+// and the tail: the INTT of the source rows, unchanged; the scale kernel; the passes
+static int hy_mod_down_fused(moai_ctx *c, const HyConv *cv, const Tw *inv, uint64_t *acc, size_t stride, size_t off, size_t nsrc, size_t ntgt,
+                             size_t polys, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, bool exact, const HyDownTail &t, hipStream_t s)
+{
+    MOAI_TRY(hy_down_sources(c, cv, acc, stride, off, nsrc, ntgt, polys, x, L, alpha, exact, s));
+    return hy_down_passes(c, cv, inv, acc, stride, off, ntgt, polys, polys, x, conv, L, alpha, exact, t, s);
+}
+
+// the plain step 5 of B switches with its last kernel, fused: hy_step5 + moddown_finalize's arguments
+static int hy_step5_fused(moai_ctx *c, const HyTable *tab, uint64_t *acc, uint64_t *x, uint64_t *conv, uint64_t *out, size_t L, size_t alpha,
+                          size_t B, const KsAddend &add, const KsList *lst, bool exact, hipStream_t s)
+{
+    HyDownTail t;
+    t.out = out;
+    t.add = add;
+    t.lst = lst;
+    return hy_mod_down_fused(c, tab->conv + hy_beta(L, alpha), tab->pinv, acc, L + alpha, L, alpha, L, 2 * B, x, conv, L, alpha, exact, t, s);
+}
+
+// G groups (rotations, outputs) of B switches each, their accumulators B * 2 * (L + alpha) rows apart at acc: the sources of all of
+// them at once, as hy_step5 takes them, then the passes group by group -- a group's converted rows are read back while they are the
+// last thing written; tail(h) says where group h goes
+template <class Tail>
+static int hy_step5_fused_groups(moai_ctx *c, const HyTable *tab, uint64_t *acc, uint64_t *x, uint64_t *conv, size_t L, size_t alpha, size_t B,
+                                 size_t G, bool exact, hipStream_t s, Tail &&tail)
+{
+    const size_t n = c->n;
+    const HyConv *cv = tab->conv + hy_beta(L, alpha);
+    MOAI_TRY(hy_down_sources(c, cv, acc, L + alpha, L, alpha, L, G * 2 * B, x, L, alpha, exact, s));
+    for (size_t h = 0; h < G; ++h)
+    {
+        MOAI_TRY(hy_down_passes(c, cv, tab->pinv, acc + h * B * 2 * (L + alpha) * n, L + alpha, L, L, 2 * B, G * 2 * B,
+                                x + h * B * 2 * alpha * n, conv + h * B * 2 * L * n, L, alpha, exact, tail(h), s));
+    }
+    return MOAI_OK;
+}
+
 // rotations of the next pass of a hoisted MAC over the digits when `left` are left: MOAI_HYBRID_HOIST_NR of them, 4, 2 or 1
 static size_t hy_pass_size(size_t left)
 {
@@ -521,6 +718,10 @@ static int hy_switch_chunk(moai_ctx *c, const HyTable *tab, uint64_t *out, const
     // the key -- unfused or fused, as the plan says
     MOAI_TRY(hy_steps14(c, tab, tg, key, L, alpha, B, wsp, w, s));
     // 5. mod-down: x = INTT(special rows), conv = NTT(base conversion with the rounding terms), out = addend + (acc - conv) / P
+    if (hy_fused_down(c))
+    {
+        return hy_step5_fused(c, tab, acc, hy_at(wsp, w, HY_X), conv, out, L, alpha, B, add, tg.lst, exact, s);
+    }
     MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, w, HY_X), conv, L, alpha, B, exact, s));
     return moddown_finalize(c, acc, (uint32_t)(L + alpha), conv, out, 2 * B, L, tab->pinv, add, tg.lst, s);
 }
@@ -742,6 +943,15 @@ static int hy_hoist_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, c
                 MOAI_TRY(galois_permute_c0(c, in, pc0 + r * B * L * n, B, L, rot.elts[r0 + r], s));
             }
             // steps 5 over (rotation, ciphertext) pairs
+            if (hy_fused_down(c))
+            {
+                return hy_step5_fused_groups(c, tab, acc, hy_at(wsp, p, HY_X), conv, L, alpha, B, g, exact, s, [&](size_t r) {
+                    HyDownTail t;
+                    t.out = rot.outs[r0 + r] + out_off;
+                    t.add = { pc0 + r * B * L * n, L, 2 };
+                    return t;
+                });
+            }
             MOAI_TRY(hy_step5(c, tab, acc, hy_at(wsp, p, HY_X), conv, L, alpha, g * B, exact, s));
             for (size_t r = 0; r < g; ++r)
             {
@@ -904,6 +1114,15 @@ static int hy_dot_chunk_run(moai_ctx *c, const uint64_t *in, size_t out_off, con
             o.ng = (uint32_t)ng;
             MOAI_TRY(hy_dot_inner(c, tab, in, tm, gs, ng, o, sc, L, alpha, B, *fallback, s));
             // step 5 once per output, over (output, ciphertext) pairs
+            if (hy_fused_down(c))
+            {
+                return hy_step5_fused_groups(c, tab, S, hy_at(wsp, p, HY_X), conv, L, alpha, B, ng, exact, s, [&](size_t h) {
+                    HyDownTail t;
+                    t.out = tm.outs[gs[h]] + out_off;
+                    t.add = { add + h * ct_words, 2 * L, 1 };
+                    return t;
+                });
+            }
             MOAI_TRY(hy_step5(c, tab, S, hy_at(wsp, p, HY_X), conv, L, alpha, ng * B, exact, s));
             for (size_t h = 0; h < ng; ++h)
             {
@@ -1028,7 +1247,12 @@ static int hy_bsgs_chunk_run(moai_ctx *c, const uint64_t *in, uint64_t *out, con
             MOAI_LAUNCH_CHECK();
             return MOAI_OK;
         }));
-        // the one final step 5, both polynomials, no addend
+        // the one final step 5, both polynomials, no addend (the inner c1-only mod-down above scatters through a permutation and keeps
+        // the unfused stages whatever the knob says)
+        if (hy_fused_down(c))
+        {
+            return hy_step5_fused(c, tab, Z, hy_at(wsp, p, HY_ZX), zconv, out, L, alpha, B, {}, nullptr, exact, s);
+        }
         MOAI_TRY(hy_step5(c, tab, Z, hy_at(wsp, p, HY_ZX), zconv, L, alpha, B, exact, s));
         return moddown_finalize(c, Z, (uint32_t)(L + alpha), zconv, out, 2 * B, L, tab->pinv, {}, nullptr, s);
     });
@@ -1078,6 +1302,16 @@ static int hy_rescale_chunk_run(moai_ctx *c, const HyTable *tab, const HyRescale
         return launch_rows(hy_lift_last_row_kernel<decltype(LIST)::value>, c, 2 * B, s, args);
     }));
     // the merged mod-down: x = INTT(rows L-1 .. L+alpha-1 of acc, contiguous), conv = NTT(base conversion with W's rounding terms)
+    if (hy_fused_down(c))
+    {
+        HyDownTail t;
+        t.out = out;
+        t.lst = lst;
+        t.rt = rt;
+        t.ct3 = ct3;
+        return hy_mod_down_fused(c, &rt->conv, nullptr, acc, L + alpha, L - 1, alpha + 1, L - 1, 2 * B, hy_at(wsp, w, HY_X), conv, L, alpha,
+                                 exact, t, s);
+    }
     MOAI_TRY(hy_mod_down(c, &rt->conv, acc, L + alpha, L - 1, alpha + 1, L - 1, 2 * B, hy_at(wsp, w, HY_X), conv, L, alpha, exact, s));
     HyRescaleFinalArgs f;
     f.acc = acc;
@@ -1345,6 +1579,21 @@ extern "C" size_t moai_hybrid_fused_groups(const moai_ctx *c, size_t L, size_t a
     }
     const HyPlan w = hy_switch_plan(c, L, alpha, batch, 0, false);
     return hy_fused_plan(c, L, alpha, w.cb, w.G).size();
+}
+
+extern "C" size_t moai_hybrid_fused_down_launches(const moai_ctx *c, size_t L, size_t alpha, size_t polys)
+{
+    if (hy_check(c, alpha, L, true) || !hy_fused_down(c) || polys == 0)
+    {
+        return 0;
+    }
+    size_t pairs = 0;
+    for (int mode = M_GUARD; mode <= M_FPR; ++mode)
+    {
+        RowMap sel{};
+        pairs += hy_down_rows(c, polys, L, mode, &sel) ? 1 : 0;
+    }
+    return pairs;
 }
 
 extern "C" int moai_hybrid_keygen(moai_ctx *c, const uint8_t *key, uint64_t seq, const uint64_t *sk_ntt, const uint64_t *new_key_ntt,

@@ -1355,4 +1355,394 @@ __global__ __launch_bounds__(256, 4) void hy_contig_mac8(std::conditional_t<LIST
     }
 }
 
+// ---- the fused mod-down (MOAI_HYBRID_FUSED_DOWN): step 5 as a scale kernel and two passes around the forward transform -----------------
+// Behind the INTT of its nsrc source rows the unfused step 5 moves, per polynomial and in rows of N words: the conversion nsrc + ntgt
+// (hy_convert_kernel reads every source once and writes every target), the transform of the converted rows 4 ntgt (two passes, each a
+// read and a write), the last kernel 3 ntgt (accumulator, converted row, output; one or two more with addends).  A converted row
+// crosses memory six times, 8 ntgt rows in all.  Here the conversion's per-source work is done once per coefficient
+// (hy_down_scale_kernel, 2 nsrc rows, one more written in exact mode), its sums ride on the strided pass's loads (hy_down_strided:
+// nsrc source tiles read per output row, ntgt of them per source tile, all but the first from the XCD's L2 under the order below; ntgt
+// rows written) and the division on the contiguous pass's stores (hy_down_contig / hy_rescale_contig: the converted row and the
+// accumulator read, the output written, 3 ntgt).  A converted row crosses memory twice: 2 nsrc + 4 ntgt rows from HBM plus the re-read
+// source tiles, against 5 nsrc + 8 ntgt.  At L = 35, alpha = 12 with the INTT's 4 nsrc on both sides: 212 against 340.  Arithmetic on
+// the code; what the re-reads cost is a question for the measurement.
+// All three leave the canonical residues the unfused chain leaves -- the conversion's sum is reduced by the same hy_mod128 and
+// submod, the transform's output is canonical in every mode, the division is the same Shoup product -- so every output is bit for
+// bit what moddown_finalize_kernel / hy_rescale_finalize_kernel write, in both rounding modes.  moddown_strided / moddown_contig
+// (keyswitch_kernels.hip.h) are the one-source shape of the same pair.
+struct HyDownScaleArgs
+{
+    uint64_t *x; // [P][nsrc][N], coefficient form, canonical: scaled in place
+    uint64_t *v; // EXACT: polynomial p's overflow row, N words, at v + p * v_stride * N
+    const HyConv *cv;
+    const PrimeConst *pc;
+    uint32_t v_stride;
+    uint32_t n2;
+};
+
+// The mod-down's per-source work, once per coefficient instead of once per target row: in place on x,
+//   y_r = ((x_r + src_pre[r]) mod s_r) src_inv[r] mod s_r, canonical
+// (hy_convert_kernel's first loop; what hy_scale_digits_kernel does for the mod-ups).  blockIdx.y = polynomial.  A thread streams its
+// two coefficients through the nsrc rows in source order, the next row's load issued before this row's arithmetic; no register array.
+// EXACT (MOAI_HYBRID_ROUND_EXACT): the overflow estimate of hy_convert_kernel<.., true>, the same operations in the same order --
+// f = 0; f = f (+) ((double)y_r (x) src_rinv[r]), contraction off, v = min(floor(f), nsrc - 1); its comment has the error bound --
+// written as one more row of 64-bit words per polynomial, which hy_down_strided reads as a seventeenth source of weight tgt_negw[t].
+// Where that row lives: the polynomial's FIRST SOURCE ROW inside the accumulator (row `off` of its `stride` rows; the host passes v =
+// acc + off N and v_stride = stride).  The out-of-place INTT in front of this kernel was the last reader of the accumulator's source
+// rows: the contiguous passes read rows below the first source only (i < L of L + alpha for the plain mod-down, i < L - 1 for the
+// merged rescale, whose first source is the lifted row L - 1).  Checked for every caller: the switch, hoisted and rescale
+// accumulators (HY_ACC) are rewritten whole by the next chunk's MAC; the pt-dot sums (HY_S) are started from zero by the first pass
+// of the next group of outputs (HyDotOutputs::seeded = 0) and every output that takes a step 5 has a switched term; the BSGS sum
+// (HY_Z) takes its one final step 5 behind the last group and the next chunk starts it with zseeded = 0.  The inner c1-only mod-down
+// of the BSGS sum keeps the unfused stages and its S is read again by hy_bsgs_mac_kernel, special rows included: it is not routed
+// here.  No scratch region is added.
+template <bool EXACT>
+__global__ __launch_bounds__(256) void hy_down_scale_kernel(HyDownScaleArgs g)
+{
+#pragma clang fp contract(off)
+    const HyConv &cv = *g.cv;
+    const uint32_t ns = cv.nsrc;
+    const size_t n2 = g.n2;
+    ulonglong2 *x = reinterpret_cast<ulonglong2 *>(g.x) + (size_t)blockIdx.y * ns * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < g.n2; j += gridDim.x * 256u)
+    {
+        [[maybe_unused]] double fx = 0.0, fy = 0.0;
+        ulonglong2 next = x[j];
+        for (uint32_t r = 0; r < ns; ++r)
+        {
+            const uint64_t q = g.pc[cv.src_prime[r]].q, pre = cv.src_pre[r];
+            const Tw inv = cv.src_inv[r];
+            ulonglong2 y = next;
+            if (r + 1 < ns)
+            {
+                next = x[(size_t)(r + 1) * n2 + j];
+            }
+            y.x = csub(mul_shoup_lazy(csub(y.x + pre, q), inv.w, inv.wq, q), q);
+            y.y = csub(mul_shoup_lazy(csub(y.y + pre, q), inv.w, inv.wq, q), q);
+            x[(size_t)r * n2 + j] = y;
+            if constexpr (EXACT)
+            {
+                const double ri = cv.src_rinv[r];
+                const double tx = __ull2double_rn(y.x) * ri, ty = __ull2double_rn(y.y) * ri;
+                fx = fx + tx;
+                fy = fy + ty;
+            }
+        }
+        if constexpr (EXACT)
+        {
+            // f >= 0, so the lower clamp is the conversion's own; the upper one is the contract's (hy_convert_kernel)
+            const double top = (double)(ns - 1);
+            ulonglong2 *v = reinterpret_cast<ulonglong2 *>(g.v) + (size_t)blockIdx.y * g.v_stride * n2;
+            v[j] = make_ulonglong2((uint64_t)(uint32_t)fmin(floor(fx), top), (uint64_t)(uint32_t)fmin(floor(fy), top));
+        }
+    }
+}
+
+struct HyDownP1Args
+{
+    const uint64_t *x; // [P][nsrc][N]: the scaled residues (hy_down_scale_kernel), coefficient form, canonical
+    const uint64_t *v; // exact: the overflow rows, polynomial p's at v + p * v_stride * N (read only then)
+    uint64_t *conv;    // [P][ntgt][N] after the strided pass, in the lazy range hy_fwd_strided leaves
+    const Tw *tw;
+    const PrimeConst *pc;
+    const HyConv *cv;  // the mod-down's conversion
+    RowMap sel;        // the output rows (= targets = data primes) of this launch: one arithmetic mode per launch
+    uint32_t Lsel;
+    uint32_t v_stride;
+    uint32_t exact;      // 0 or 1: the extra trip over the overflow row
+    uint32_t total_work; // P * TPR * Lsel
+};
+
+// The strided pass with the mod-down's base conversion on its loads; hy_fwd_strided's structure.  Work item = (polynomial, tile,
+// output row of the launch).  A thread holds its 16 coefficients as 16 128-bit sums and walks the nsrc <= 16 source rows in a loop
+// whose trip count is uniform over the workgroup: sixteen loads with the tile's strided addressing, in two halves of eight, then
+// sixteen multiply-adds with w[t][r], one scalar load from the HyConv.  In exact mode the overflow row is one more trip of the same
+// loop -- another row pointer and the weight tgt_negw[t], both selected by a uniform condition -- so 17 products below 2^122 and a
+// sum below 2^127 (hy_convert_kernel's comment has the bound); no second instantiation.  Then ONE hy_mod128, the submod of
+// tgt_post[t] (the canonical residue hy_convert_kernel stores), in the FP64 modes its conversion to the balanced double (below
+// q < 2^51: LoadFp52's operation), and strided_core as it is.
+// Order of the work ids, under xcd_remap: output row fastest, then tile, then polynomial.  The Lsel workgroups that share one
+// (tile, polynomial) read the same nsrc source tiles (nsrc * 32 KiB) and are neighbours on one XCD; no digit index: all ntgt rows of
+// a polynomial share one set of sources.  The other order (tile fastest, moddown_strided's) was not measured.
+// Registers, scratch and waves: the table at hy_down_contig.  No scratch, four waves; N = 2^12 is bounded to three as hy_fwd_strided is.
+template <int LOGN, int MODE>
+__global__ __launch_bounds__(256, LOGN == 12 ? 3 : 4) void hy_down_strided(HyDownP1Args a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    constexpr uint32_t TG = 1u << (12 - (LOGN - 8)); // columns of a tile
+    __shared__ uint64_t lds[4096];
+    uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t g = w % a.Lsel;
+    w /= a.Lsel;
+    const uint32_t tile = w % TPR;
+    const uint32_t p = w / TPR;
+    const uint32_t t = __builtin_amdgcn_readfirstlane(a.sel.idx[g]);
+    const HyConv &cv = *a.cv;
+    const uint32_t ns = cv.nsrc, nt = cv.ntgt, trips = ns + a.exact;
+    const uint32_t prime = cv.tgt_prime[t];
+    const PrimeConst *pc = a.pc + prime;
+    const uint64_t *in = a.x + (((size_t)p * ns) << LOGN) + tile * TG;
+    const uint64_t *vrow = a.v + (((size_t)p * a.v_stride) << LOGN) + tile * TG;
+    uint64_t *out = a.conv + (((size_t)p * nt + t) << LOGN);
+    uint64_t x[16], xh[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        x[i] = xh[i] = 0;
+    }
+    for (uint32_t r = 0; r < trips; ++r)
+    {
+        const bool over = r == ns; // the exact mode's last trip: the overflow row
+        const uint64_t *__restrict__ irow = over ? vrow : in + ((size_t)r << LOGN);
+        const uint64_t wr = over ? cv.tgt_negw[t] : cv.w[t][r];
+        // the sixteen loads in two halves of eight, as in hy_fwd_strided
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+        {
+            uint64_t raw[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+            {
+                raw[i] = irow[strided_index<LOGN>(h * 8 + i, threadIdx.x)];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+            {
+                mac128(x[h * 8 + i], xh[h * 8 + i], raw[i], wr);
+            }
+        }
+    }
+    const uint64_t q = pc->q, cr0 = pc->cr0, cr1 = pc->cr1, post = cv.tgt_post[t];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        x[i] = submod(hy_mod128(x[i], xh[i], q, cr0, cr1), post, q);
+        if (mode_fp(MODE))
+        {
+            x[i] = d2u(fp_red(fp_from_u52(x[i]), u2d(pc->qd), u2d(pc->qinv)));
+        }
+    }
+    strided_core<LOGN, MODE, false>(x, out + tile * TG, a.tw + ((size_t)prime << LOGN), mode_q<MODE>(*pc), mode_q2<MODE>(*pc), lds,
+                                    threadIdx.x);
+}
+
+// what the contiguous pass of the plain mod-down does with a finished chunk u of NTT(conv): out = (acc - u) inv [+ add] [+ add2],
+// moddown_finalize_kernel's arithmetic.  StoreModDown's shape (the operands of four chunks fetched together, before the four calls
+// that finish them) without its partial sums and scalar product, and under names of its own -- one per LIST -- so that every kernel
+// here instantiates its own fwd_contig_tile and the existing kernels' instruction streams stay what they are (the note on
+// StoreModDownList).  A thread reads the chunks it adds before it writes the same chunks, so out may be add or add2.
+template <bool LIST>
+struct StoreHyDown
+{
+    const ulonglong2 *acc;  // tile base of the row being divided
+    ulonglong2 *out;        // tile base of the result row
+    const ulonglong2 *add;  // tile base of the row to add, or nullptr
+    const ulonglong2 *add2; // tile base of a second row to add, or nullptr
+    uint64_t q;
+    Tw inv;
+    ulonglong2 av[4], cv[4], dv[4];
+    __device__ __forceinline__ void fetch(const uint32_t (&chs)[4])
+    {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+        {
+            av[i] = acc[chs[i]];
+        }
+        if (add)
+        {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+            {
+                cv[i] = add[chs[i]];
+            }
+        }
+        if (add2)
+        {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+            {
+                dv[i] = add2[chs[i]];
+            }
+        }
+    }
+    __device__ __forceinline__ void operator()(int i, uint32_t ch, ulonglong2 u) const
+    {
+        ulonglong2 r;
+        r.x = csub(mul_shoup_lazy(av[i].x + q - u.x, inv.w, inv.wq, q), q);
+        r.y = csub(mul_shoup_lazy(av[i].y + q - u.y, inv.w, inv.wq, q), q);
+        if (add)
+        {
+            r = moai::add2(r, cv[i], q);
+        }
+        if (add2)
+        {
+            r = moai::add2(r, dv[i], q);
+        }
+        out[ch] = r;
+    }
+};
+
+struct HyDownP2Args
+{
+    uint64_t *conv;      // [P][ntgt][N]: the strided pass's output
+    const uint64_t *acc; // row (p, i) at acc + (p * acc_stride + i) * N
+    uint64_t *out;       // [P][ntgt][N]
+    const Tw *tw;
+    const Tw *twb;
+    const PrimeConst *pc;
+    const Tw *inv;       // the divisor's inverse mod q_i
+    const uint64_t *addend; // the addends as in ModDownArgs (KsAddend)
+    const uint64_t *addend2;
+    uint32_t addend_bstride;
+    int add_mode;
+    uint32_t acc_stride;
+    uint32_t ntgt;
+    uint32_t P;
+    uint32_t total_work; // P * TPR * Lsel
+    RowMap sel;
+    uint32_t Lsel;
+};
+
+struct HyDownP2ListArgs : HyDownP2Args
+{
+    const KsList *lst; // as moddown_contig: polynomials 2b and 2b + 1 go to lst->outs[b] plus lst->sums[b]; add_mode 1 reads lst->ins[b]
+};
+
+// The contiguous pass of the plain mod-down with the division on its stores: moddown_contig's structure -- polynomial fastest, one
+// 4096-coefficient tile per workgroup through fwd_contig_tile, every KsAddend mode and the LIST addressing -- on the hybrid
+// accumulator's rows (acc_stride = L + alpha, inv = P^-1).
+// Resources as the compiler reports them (gfx950, this file's flags; VGPRs, and the waves per SIMD they allow; no instantiation of
+// any of the kernels takes scratch, so nothing spills inside hy_down_strided's source loop; LIST and plain take the same):
+//                        M_GUARD    M_NOGUARD   M_FPN      M_FPR
+//   hy_down_strided      108, 4     108, 4      108, 4     108, 4     N = 2^13 .. 2^16 (110 at 2^15); 32 KiB of LDS
+//                        140, 3     140, 3      140, 3     140, 3     N = 2^12: no exchange, no LDS; bounded to three as hy_fwd_strided
+//   hy_down_contig        79, 5      79, 5       93, 5      85, 5     every N; 32 KiB of LDS, which also allow five workgroups a CU
+//   hy_rescale_contig    101, 4      99, 4      122, 4     100, 4     every N
+//   hy_down_scale_kernel 25 (fast), 33 (exact): eight waves
+// The overflow row costs the strided pass no register: kept in the pass's registers instead, the estimate would need the nsrc
+// scaled residues of all sixteen coefficients before the first sum, which is hy_convert_kernel<16>'s 166 VGPRs and three waves.
+template <int LOGN, int MODE, bool LIST = false>
+__global__ __launch_bounds__(256) void hy_down_contig(std::conditional_t<LIST, HyDownP2ListArgs, HyDownP2Args> a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    __shared__ ulonglong2 lds2[2048];
+    uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t p = w % a.P;
+    w /= a.P;
+    const uint32_t tile = w % TPR;
+    const uint32_t i = __builtin_amdgcn_readfirstlane(a.sel.idx[w / TPR]);
+    const PrimeConst &pc = a.pc[i];
+    const size_t orow = ((size_t)p * a.ntgt + i) << LOGN, toff = (size_t)tile << 11;
+    StoreHyDown<LIST> st;
+    st.acc = reinterpret_cast<const ulonglong2 *>(a.acc + (((size_t)p * a.acc_stride + i) << LOGN)) + toff;
+    st.out = reinterpret_cast<ulonglong2 *>(a.out + orow) + toff;
+    st.q = pc.q;
+    st.inv = a.inv[i];
+    st.add = nullptr;
+    if (a.add_mode == 1 || (a.add_mode == 2 && !(p & 1u)))
+    {
+        st.add = reinterpret_cast<const ulonglong2 *>(a.addend + (((size_t)(p >> 1) * a.addend_bstride + (size_t)(p & 1u) * a.ntgt + i) << LOGN)) + toff;
+    }
+    st.add2 = a.addend2 ? reinterpret_cast<const ulonglong2 *>(a.addend2 + orow) + toff : nullptr;
+    if constexpr (LIST)
+    {
+        const uint32_t b = p >> 1;
+        const size_t row = ((size_t)(p & 1u) * a.ntgt + i) << LOGN; // inside the member's [2][ntgt][N]
+        st.out = reinterpret_cast<ulonglong2 *>(a.lst->outs[b] + row) + toff;
+        const uint64_t *sum = a.lst->sums[b];
+        st.add2 = sum ? reinterpret_cast<const ulonglong2 *>(sum + row) + toff : nullptr;
+        if (a.add_mode == 1)
+        {
+            st.add = reinterpret_cast<const ulonglong2 *>(a.lst->ins[b] + row) + toff;
+        }
+    }
+    // the tile hands the store canonical integers in every mode
+    fwd_contig_tile<LOGN, MODE, StoreHyDown<LIST>>(a.conv + orow, tile, a.tw + ((size_t)i << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc), lds2,
+                                                   threadIdx.x, a.twb + (size_t)i * ((size_t)TPR * 15 * 256), pc.cr1, st);
+}
+
+// the merged relinearize + rescale's finish on a finished chunk u of NTT(conv): out = c_p [q_{L-1}^-1] + (acc - u) [W^-1],
+// hy_rescale_finalize_kernel's two Shoup products made canonical and one canonical add
+template <bool LIST>
+struct StoreHyRescale
+{
+    const ulonglong2 *acc; // tile base of the accumulator's row
+    const ulonglong2 *cp;  // tile base of c_p's row
+    ulonglong2 *out;       // tile base of the result row
+    uint64_t q;
+    Tw wi, qi;
+    ulonglong2 av[4], cv[4];
+    __device__ __forceinline__ void fetch(const uint32_t (&chs)[4])
+    {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+        {
+            av[i] = acc[chs[i]];
+            cv[i] = cp[chs[i]];
+        }
+    }
+    __device__ __forceinline__ void operator()(int i, uint32_t ch, ulonglong2 u) const
+    {
+        ulonglong2 r, t;
+        r.x = csub(mul_shoup_lazy(av[i].x + q - u.x, wi.w, wi.wq, q), q);
+        r.y = csub(mul_shoup_lazy(av[i].y + q - u.y, wi.w, wi.wq, q), q);
+        t.x = csub(mul_shoup_lazy(cv[i].x, qi.w, qi.wq, q), q);
+        t.y = csub(mul_shoup_lazy(cv[i].y, qi.w, qi.wq, q), q);
+        out[ch] = add2(r, t, q);
+    }
+};
+
+struct HyRescaleP2Args
+{
+    uint64_t *conv;      // [2B][L - 1][N]: the strided pass's output
+    const uint64_t *acc; // [B][2][L + alpha][N]
+    const uint64_t *ct3; // [B][3][L][N]: c_0 and c_1 read
+    uint64_t *out;       // [B][2][L - 1][N]
+    const Tw *tw;
+    const Tw *twb;
+    const PrimeConst *pc;
+    const Tw *winv, *qinv;
+    uint32_t L, alpha;
+    uint32_t P;          // 2B
+    uint32_t total_work; // P * TPR * Lsel
+    RowMap sel;
+    uint32_t Lsel;
+};
+
+struct HyRescaleP2ListArgs : HyRescaleP2Args
+{
+    const KsList *lst; // ciphertext b's [3][L][N] block is lst->ins[b] and its [2][L - 1][N] result lst->outs[b] (ct3 and out unused)
+};
+
+// The contiguous pass of the merged mod-down with hy_rescale_finalize_kernel's formula on its stores, rows i < L - 1, plain and LIST
+// addressing as there; the work order of hy_down_contig.
+template <int LOGN, int MODE, bool LIST = false>
+__global__ __launch_bounds__(256) void hy_rescale_contig(std::conditional_t<LIST, HyRescaleP2ListArgs, HyRescaleP2Args> a)
+{
+    constexpr uint32_t TPR = 1u << (LOGN - 12);
+    __shared__ ulonglong2 lds2[2048];
+    uint32_t w = xcd_remap(blockIdx.x, a.total_work);
+    const uint32_t poly = w % a.P;
+    w /= a.P;
+    const uint32_t tile = w % TPR;
+    const uint32_t i = __builtin_amdgcn_readfirstlane(a.sel.idx[w / TPR]);
+    const uint32_t lo = a.L - 1, b = poly >> 1, p = poly & 1u;
+    const PrimeConst &pc = a.pc[i];
+    const size_t orow = ((size_t)poly * lo + i) << LOGN, toff = (size_t)tile << 11;
+    StoreHyRescale<LIST> st;
+    st.acc = reinterpret_cast<const ulonglong2 *>(a.acc + (((size_t)poly * (a.L + a.alpha) + i) << LOGN)) + toff;
+    st.cp = reinterpret_cast<const ulonglong2 *>(a.ct3 + (((size_t)(b * 3 + p) * a.L + i) << LOGN)) + toff;
+    st.out = reinterpret_cast<ulonglong2 *>(a.out + orow) + toff;
+    if constexpr (LIST)
+    {
+        st.cp = reinterpret_cast<const ulonglong2 *>(a.lst->ins[b] + (((size_t)p * a.L + i) << LOGN)) + toff;
+        st.out = reinterpret_cast<ulonglong2 *>(a.lst->outs[b] + (((size_t)p * lo + i) << LOGN)) + toff;
+    }
+    st.q = pc.q;
+    st.wi = a.winv[i];
+    st.qi = a.qinv[i];
+    fwd_contig_tile<LOGN, MODE, StoreHyRescale<LIST>>(a.conv + orow, tile, a.tw + ((size_t)i << LOGN), mode_q<MODE>(pc), mode_q2<MODE>(pc),
+                                                      lds2, threadIdx.x, a.twb + (size_t)i * ((size_t)TPR * 15 * 256), pc.cr1, st);
+}
+
 } // namespace moai

@@ -32,7 +32,8 @@ namespace moai {
     X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller") \
     X(HYBRID_TMP_KB, 16777216, "KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight") \
     X(HYBRID_HOIST_NR, 4, "rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1")                         \
-    X(HYBRID_FUSED, 0, "1: hybrid switches at N >= 2^12 run mod-up, forward transform and key product as two fused passes")
+    X(HYBRID_FUSED, 0, "1: hybrid switches at N >= 2^12 run mod-up, forward transform and key product as two fused passes")    \
+    X(HYBRID_FUSED_DOWN, 0, "1: hybrid mod-downs at N >= 2^12 run base conversion and division inside the forward transform's two passes")
 
 enum Knob
 {

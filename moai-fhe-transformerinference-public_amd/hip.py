@@ -109,6 +109,7 @@ SYMBOLS = {
     "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
     "moai_hybrid_digits": (sz, [vp, sz, sz]),
     "moai_hybrid_fused_groups": (sz, [vp, sz, sz, sz]),
+    "moai_hybrid_fused_down_launches": (sz, [vp, sz, sz, sz]),
     "moai_hybrid_keygen": (C.c_int, [vp, C.c_char_p, C.c_uint64, vp, vp, sz, vp, vp]),
     "moai_switch_key_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_relinearize_hybrid": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
@@ -410,6 +411,14 @@ class Context:
         """output-row groups the fused hybrid switch (MOAI_HYBRID_FUSED) would launch now per chunk of `batch` ciphertexts; 0: the
         call takes the unfused path (moai_hybrid_fused_groups; no launch).  A refused (L, alpha) raises."""
         g = int(lib().moai_hybrid_fused_groups(self.h, L, alpha, batch))
+        if g == 0 and lib().moai_hybrid_digits(self.h, alpha, L) == 0:
+            _check(MOAI_EINVAL)
+        return g
+
+    def hybrid_fused_down_launches(self, L, alpha, polys=2):
+        """launch pairs the fused hybrid mod-down (MOAI_HYBRID_FUSED_DOWN) of `polys` polynomials to L rows would take now; 0: the
+        call takes the unfused stages (moai_hybrid_fused_down_launches; no launch).  A refused (L, alpha) raises."""
+        g = int(lib().moai_hybrid_fused_down_launches(self.h, L, alpha, polys))
         if g == 0 and lib().moai_hybrid_digits(self.h, alpha, L) == 0:
             _check(MOAI_EINVAL)
         return g
