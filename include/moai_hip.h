@@ -233,6 +233,18 @@ int moai_ct_pt_dot_rows(moai_ctx *ctx, const uint64_t *x, const uint64_t *p, con
  */
 int moai_ct_pt_matmul(moai_ctx *ctx, const uint64_t *x, const uint64_t *w, uint64_t *out, size_t rows, size_t cols,
                       size_t size, size_t L, void *stream);
+/* Which kernel that call would launch NOW, the tuning knobs included (read-only; no launch, no stream; the call and this query ask
+ * the same host function, after the same argument checks).  Every path computes the same canonical residues.
+ *   MOAI_MATMUL_PATH_INT   128-bit integer sums, any prime below 2^61
+ *   MOAI_MATMUL_PATH_FP64  exact FP64 sums: every prime of the level is below 2^51 and MOAI_MATMUL_FP is not 0
+ *   MOAI_MATMUL_PATH_MFMA  MOAI_MATMUL_MFMA is not 0 and N >= 16: residues split into signed byte limbs, the sums of limb products
+ *                          formed exactly by the int8 matrix instructions, one reduction mod q per output element and 8192 rows;
+ *                          any prime below 2^61, no workspace; wins over MOAI_MATMUL_FP
+ * MOAI_EINVAL for a null argument and for whatever moai_ct_pt_matmul refuses in (rows, cols, size, L). */
+#define MOAI_MATMUL_PATH_INT 0
+#define MOAI_MATMUL_PATH_FP64 1
+#define MOAI_MATMUL_PATH_MFMA 2
+int moai_ct_pt_matmul_path(moai_ctx *ctx, size_t rows, size_t cols, size_t size, size_t L, int *path);
 
 /* ---- level changes ---------------------------------------------------------------------------------
  * Evaluator::rescale_to_next SEAL/evaluator.cpp:1682-1720 -> mod_switch_scale_to_next :1402-1481 ->
@@ -579,6 +591,7 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_KS_HOIST_PAIR     4     rotations per pass of the hoisted MAC in the FP64 modes: 4, 2, or 0 for one
  *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
+ *   MOAI_MATMUL_MFMA       0     1: moai_ct_pt_matmul runs on the int8 matrix cores (byte limbs, exact) where N >= 16
  *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
  *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
  *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight

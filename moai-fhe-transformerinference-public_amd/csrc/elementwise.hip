@@ -825,6 +825,10 @@ __global__ __launch_bounds__(256) void ct_pt_matmul_kernel(MatmulArgs g)
     }
 }
 
+} // namespace moai
+#include "matmul_mfma.hip.h" // the same product on the int8 matrix cores (MOAI_MATMUL_MFMA)
+namespace moai {
+
 // ---- row moves: level drop, Galois gather ---------------------------------------------------------------------------
 // out row (p, i<Lout) = in row (p, i): blockIdx.y = p * Lout + i
 __global__ __launch_bounds__(256) void drop_rows_kernel(const uint64_t *in, uint64_t *out, uint32_t Lin, uint32_t Lout,
@@ -1487,6 +1491,42 @@ extern "C" int moai_ct_pt_dot_rows(moai_ctx *c, const uint64_t *x, const uint64_
     return MOAI_OK;
 }
 
+// The last argument check of moai_ct_pt_matmul and moai_ct_pt_matmul_path, and the kernel the call launches (MOAI_MATMUL_PATH_*):
+//   MFMA  MOAI_MATMUL_MFMA is not 0 and N >= 16 (a wave's strip is 16 coefficients): byte limbs on the int8 matrix cores,
+//         any prime; wins over MOAI_MATMUL_FP
+//   FP64  every prime of the level is below 2^51 and MOAI_MATMUL_FP is not 0: exact FP64 sums
+//   INT   otherwise: 128-bit integer sums
+constexpr int MATMUL_CG = 16; // output columns per pass of the integer and FP64 kernels
+static int matmul_path(const moai_ctx *c, size_t rows, size_t cols, size_t size, size_t L, int *path)
+{
+    if (size * L > 65535 || (cols + MATMUL_CG - 1) / MATMUL_CG > 65535)
+    {
+        return set_error(MOAI_EINVAL, "matrix too large for one launch");
+    }
+    if (tuning(K_MATMUL_MFMA) != 0 && c->n >= 16)
+    {
+        *path = MOAI_MATMUL_PATH_MFMA;
+        return MOAI_OK;
+    }
+    bool fp = tuning(K_MATMUL_FP) != 0;
+    for (size_t r = 0; r < L && fp; r++)
+    {
+        fp = c->primes[r] < (1ull << 51);
+    }
+    *path = fp ? MOAI_MATMUL_PATH_FP64 : MOAI_MATMUL_PATH_INT;
+    return MOAI_OK;
+}
+
+extern "C" int moai_ct_pt_matmul_path(moai_ctx *c, size_t rows, size_t cols, size_t size, size_t L, int *path)
+{
+    if (!path)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    MOAI_TRY(check_rows(c, (rows > cols ? rows : cols) * size, L));
+    return matmul_path(c, rows, cols, size, L, path);
+}
+
 extern "C" int moai_ct_pt_matmul(moai_ctx *c, const uint64_t *x, const uint64_t *w, uint64_t *out, size_t rows,
                                  size_t cols, size_t size, size_t L, void *stream)
 {
@@ -1501,11 +1541,9 @@ extern "C" int moai_ct_pt_matmul(moai_ctx *c, const uint64_t *x, const uint64_t 
     {
         return set_error(MOAI_EINVAL, "bad pointers");
     }
-    constexpr int CG = 16;
-    if (size * L > 65535 || (cols + CG - 1) / CG > 65535)
-    {
-        return set_error(MOAI_EINVAL, "matrix too large for one launch");
-    }
+    constexpr int CG = MATMUL_CG;
+    int path;
+    MOAI_TRY(matmul_path(c, rows, cols, size, L, &path));
     MatmulArgs g;
     g.x = x;
     g.w = w;
@@ -1517,13 +1555,14 @@ extern "C" int moai_ct_pt_matmul(moai_ctx *c, const uint64_t *x, const uint64_t 
     fill_rows(g, c, L);
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((g.n2 + 255u) / 256u, (uint32_t)(size * L), (uint32_t)((cols + CG - 1) / CG));
-    // exact FP64 sums when every prime of the level is below 2^51 (MOAI_MATMUL_FP=0: the integer kernel)
-    bool fp = tuning(K_MATMUL_FP) != 0;
-    for (size_t r = 0; r < L && fp; r++)
+    if (path == MOAI_MATMUL_PATH_MFMA)
     {
-        fp = c->primes[r] < (1ull << 51);
+        // 64 coefficients x MM_CT * 16 columns per workgroup; at most 2^10 x 2^16 workgroups in x
+        const uint32_t col_groups = (uint32_t)((cols + 16 * MM_CT - 1) / (16 * MM_CT));
+        const dim3 mgrid((uint32_t)((c->n + 63) / 64) * col_groups, (uint32_t)(size * L));
+        hipLaunchKernelGGL(ct_pt_matmul_mfma_kernel<MM_CT>, mgrid, dim3(256), 0, s, g, col_groups);
     }
-    if (fp)
+    else if (path == MOAI_MATMUL_PATH_FP64)
     {
         const size_t count = L * rows * cols;
         std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));

@@ -56,6 +56,7 @@ SYMBOLS = {
     "moai_ct_pt_dot_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_ct_pt_dot2": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, sz, vp]),
     "moai_ct_pt_matmul": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, sz, vp]),
+    "moai_ct_pt_matmul_path": (C.c_int, [vp, sz, sz, sz, sz, C.POINTER(C.c_int)]),
     "moai_rescale": (C.c_int, [vp, vp, vp, sz, sz, sz, vp]),
     "moai_mul_scalar_rescale": (C.c_int, [vp, vp, u64p, vp, sz, sz, sz, vp]),
     "moai_rescale_add": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, vp]),
@@ -155,6 +156,7 @@ HYBRID_ROUND_FAST, HYBRID_ROUND_EXACT = 0, 1  # MOAI_HYBRID_ROUND_* of include/m
 # moai_arith_mode: the arithmetic modes and the operations it answers for (include/moai_hip.h)
 MODE_LAZY16, MODE_LAZY8, MODE_GUARD2, MODE_GUARD, MODE_NOGUARD, MODE_FPN, MODE_FPR = -3, -2, -1, 0, 1, 2, 3
 MODE_OF_KEY_SWITCH, MODE_OF_MOD_DOWN, MODE_OF_NTT_FORWARD, MODE_OF_NTT_INVERSE = 0, 1, 2, 3
+MATMUL_PATH_INT, MATMUL_PATH_FP64, MATMUL_PATH_MFMA = 0, 1, 2  # moai_ct_pt_matmul_path
 
 
 class MoaiError(RuntimeError):
@@ -360,6 +362,12 @@ class Context:
 
     def ct_pt_matmul(self, x, w, out, rows, cols, size, L, stream=None):
         _check(lib().moai_ct_pt_matmul(self.h, _ptr(x), _ptr(w), _ptr(out), rows, cols, size, L, stream))
+
+    def ct_pt_matmul_path(self, rows, cols, size, L):
+        """MATMUL_PATH_INT, _FP64 or _MFMA: the kernel ct_pt_matmul would launch now (moai_ct_pt_matmul_path; no launch)"""
+        p = C.c_int(-1)
+        _check(lib().moai_ct_pt_matmul_path(self.h, rows, cols, size, L, C.byref(p)))
+        return p.value
 
     def rescale(self, src, out, size, L, batch, stream=None):
         _check(lib().moai_rescale(self.h, _ptr(src), _ptr(out), size, L, batch, stream))
