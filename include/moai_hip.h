@@ -199,6 +199,13 @@ int moai_ct_multiply_general(moai_ctx *ctx, const uint64_t *x, size_t size_x, co
  * sequence.  Primes of at most 61 bits (SEAL's own bound, util/defines.h:40). */
 int moai_ct_dot(moai_ctx *ctx, const uint64_t *x, const uint64_t *y, uint64_t *out, size_t count, size_t L,
                 void *stream);
+/* out[j][i] = sum over t < k of ckks_multiply(a[i][t], b[j][t])   (SEAL/evaluator.cpp:805-860, add_inplace :155-240):
+ * every (column, giant step) sum of Ct_ct_matrix_mul.hpp:116-137 in one call.
+ * a: [m][k][2][L][N]; b: [nb][k][2][L][N]; out: [nb][m][3][L][N], not an operand.  A short last giant step is
+ * zero-padded by the caller (a zero ciphertext adds zero).  Canonical residues: the bits of
+ * moai_ct_dot(a + i*k*2*L*N, b + j*k*2*L*N, out[j][i], k, L) for every (i, j).  1 <= k <= 4096. */
+int moai_ct_ct_matmul(moai_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t m, size_t nb, size_t k,
+                      size_t L, void *stream);
 /* out[poly] = sum over t < terms of multiply_plain(x[x_index[t]][poly], p[p_index[t]]) (evaluator.cpp:2336-2373)
  * accumulated with add_inplace: the inner loop of the baby-step / giant-step linear transforms of MOAI's
  * bootstrapping (include/source/bootstrapping/Bootstrapper.cpp:2028-2046, 2095-2113) for a whole batch.

@@ -827,6 +827,7 @@ __global__ __launch_bounds__(256) void ct_pt_matmul_kernel(MatmulArgs g)
 
 } // namespace moai
 #include "matmul_mfma.hip.h" // the same product on the int8 matrix cores (MOAI_MATMUL_MFMA)
+#include "ctct_mfma.hip.h"   // moai_ct_ct_matmul: every sum of ciphertext x ciphertext products of a matrix on the same cores
 namespace moai {
 
 // ---- row moves: level drop, Galois gather ---------------------------------------------------------------------------
@@ -1303,6 +1304,68 @@ extern "C" int moai_ct_dot(moai_ctx *c, const uint64_t *x, const uint64_t *y, ui
     g.count = (uint32_t)count;
     fill_rows(g, c, L);
     return launch_rows(ct_dot_kernel, c, L, stream, g);
+}
+
+// out[j][i] = the moai_ct_dot of row i of a and row j of b.  From N = 16 up one launch of ct_ct_matmul_mfma_kernel (ctct_mfma.hip.h);
+// a smaller ring has no strip of 16 coefficients and takes ct_dot_kernel per (i, j).
+extern "C" int moai_ct_ct_matmul(moai_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t m, size_t nb, size_t k,
+                                 size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, a, b, out);
+    trace_op("ct_ct_matmul", L, m * nb * k);
+    if (k == 0 || k > CC_KMAX)
+    {
+        return set_error(MOAI_EINVAL, "a sum of %zu products: 1 .. %u", k, CC_KMAX);
+    }
+    if (m > 0x7fffffffull || nb > 0x7fffffffull)
+    {
+        return set_error(MOAI_EINVAL, "matrix too large for one launch");
+    }
+    MOAI_TRY(check_rows(c, std::max(2 * k * std::max(m, nb), 3 * m * nb), L));
+    if (m == 0 || nb == 0 || L == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!a || !b || !out || out == a || out == b)
+    {
+        return set_error(MOAI_EINVAL, "bad pointers");
+    }
+    if (c->n < 16)
+    {
+        CtDotArgs d;
+        d.count = (uint32_t)k;
+        fill_rows(d, c, L);
+        for (size_t j = 0; j < nb; ++j)
+        {
+            for (size_t i = 0; i < m; ++i)
+            {
+                d.x = a + i * k * 2 * L * c->n;
+                d.y = b + j * k * 2 * L * c->n;
+                d.out = out + (j * m + i) * 3 * L * c->n;
+                MOAI_TRY(launch_rows(ct_dot_kernel, c, L, stream, d));
+            }
+        }
+        return MOAI_OK;
+    }
+    CtCtArgs g;
+    g.a = a;
+    g.b = b;
+    g.out = out;
+    g.m = (uint32_t)m;
+    g.nb = (uint32_t)nb;
+    g.k = (uint32_t)k;
+    g.mtiles = (uint32_t)((m + 7) / 8);
+    g.ngroups = (uint32_t)((nb + 8 * CC_NT - 1) / (8 * CC_NT));
+    fill_rows(g, c, L);
+    // 16 coefficients x one M tile x one N group per workgroup, the prime in y
+    const size_t blocks = (c->n / 16) * g.mtiles * g.ngroups;
+    if (blocks > 0x7fffffffull)
+    {
+        return set_error(MOAI_EINVAL, "matrix too large for one launch");
+    }
+    hipLaunchKernelGGL(ct_ct_matmul_mfma_kernel, dim3((uint32_t)blocks, (uint32_t)L), dim3(256), 0, (hipStream_t)stream, g);
+    MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
 }
 
 // ---- ciphertext x ciphertext ----------------------------------------------------------------------------------------

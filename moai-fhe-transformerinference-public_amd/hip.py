@@ -52,6 +52,7 @@ SYMBOLS = {
     "moai_ct_square": (C.c_int, [vp, vp, vp, sz, sz, vp]),
     "moai_ct_multiply_general": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, sz, vp]),
     "moai_ct_dot": (C.c_int, [vp, vp, vp, vp, sz, sz, vp]),
+    "moai_ct_ct_matmul": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, sz, vp]),
     "moai_ct_pt_dot": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, vp]),
     "moai_ct_pt_dot_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_ct_pt_dot2": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, sz, vp]),
@@ -343,6 +344,10 @@ class Context:
 
     def ct_dot(self, x, y, out, count, L, stream=None):
         _check(lib().moai_ct_dot(self.h, _ptr(x), _ptr(y), _ptr(out), count, L, stream))
+
+    def ct_ct_matmul(self, a, b, out, m, nb, k, L, stream=None):
+        """out[j][i] = the ct_dot of a[i] and b[j] over k terms; a [m][k][2][L][N], b [nb][k][2][L][N], out [nb][m][3][L][N]"""
+        _check(lib().moai_ct_ct_matmul(self.h, _ptr(a), _ptr(b), _ptr(out), m, nb, k, L, stream))
 
     def ct_pt_dot(self, x, p, out, x_index, p_index, n_poly, L, stream=None):
         xi = (C.c_uint32 * len(x_index))(*[int(v) for v in x_index])

@@ -812,16 +812,26 @@ namespace moai_fused
             }
         }
         // giant steps: out[i][j] = sum_k c_g[i][k] * rot_enc_X[j*g + k] (:116-141), all relinearized and rescaled together
+        // MOAI_SHIM_CT_CT_MATMUL=1: all of them in one moai_ct_ct_matmul (the zero ciphertexts behind a short last giant step add
+        // zero); otherwise one moai_ct_dot per (column, giant step).  The same bits either way.
+        static const bool one_call = [] {
+            const char *e = std::getenv("MOAI_SHIM_CT_CT_MATMUL");
+            return e && e[0] == '1';
+        }();
         util::DeviceArray d3(cols * Bg * 3 * L * n, st);
-        for (std::size_t i = 0; i < cols; i++)
+        if ((Bg - 1) * G >= nx)
+        {
+            throw std::logic_error("empty giant step");
+        }
+        if (one_call)
+        {
+            util::hip_check(moai_ct_ct_matmul(dev, cg.get(), rx.get(), d3.get(), cols, Bg, G, L, st));
+        }
+        for (std::size_t i = 0; i < cols && !one_call; i++)
         {
             for (std::size_t j = 0; j < Bg; j++)
             {
-                const std::size_t first = j * G, count = std::min(G, nx > first ? nx - first : 0);
-                if (!count)
-                {
-                    throw std::logic_error("empty giant step");
-                }
+                const std::size_t first = j * G, count = std::min(G, nx - first);
                 util::hip_check(moai_ct_dot(dev, cg.get() + i * G * ctw, rx.get() + first * ctw, d3.get() + (j * cols + i) * 3 * L * n,
                                             count, L, st));
             }
