@@ -221,6 +221,15 @@ int moai_ct_pt_dot(moai_ctx *ctx, const uint64_t *x, const uint64_t *p, uint64_t
 int moai_ct_pt_dot2(moai_ctx *ctx, const uint64_t *x, const uint64_t *p, uint64_t *out, uint64_t *out2,
                     const uint32_t *x_index, const uint32_t *p_index, const uint32_t *p_index2, size_t terms, size_t terms2,
                     size_t n_poly, size_t L, void *stream);
+/* Every giant-step sum of one transform (Bootstrapper.cpp:2024-2062, 2090-2128) in one pass over the baby-step ciphertexts:
+ * output j < n_out, at out + j * out_stride words, is the sum over t < terms[j] of x[x_index[o_j + t]] (.) p[p_index[o_j + t]]
+ * with o_j = terms[0] + .. + terms[j - 1] (the index lists of the outputs one after another; host arrays).  x, p and every
+ * output block as in moai_ct_pt_dot; out_stride >= n_poly * L * N; 1 <= terms[j] <= 64; the lists need not be sorted, nest or
+ * be free of repeats.  No output overlaps an operand, a plaintext or another output.  Every operand is read once per group
+ * of up to 12 outputs.  Canonical residues: the bits of n_out moai_ct_pt_dot calls, for any prime below 2^61. */
+int moai_ct_pt_dot_many(moai_ctx *ctx, const uint64_t *x, const uint64_t *p, uint64_t *out, size_t out_stride,
+                        const uint32_t *x_index, const uint32_t *p_index, const uint32_t *terms, size_t n_out, size_t n_poly,
+                        size_t L, void *stream);
 /* out = sum over ALL r < rows of multiply_plain(x[r], p[r]) accumulated with add_inplace: one output column of
  * ct_pt_matrix_mul_wo_pre_w_mask (include/source/matrix_mul/Ct_pt_matrix_mul.hpp:120-150, every weight a full plaintext),
  * any number of rows in one call; with p2 / out2 (both or neither) a second column over the same ciphertexts in the same

@@ -828,6 +828,7 @@ __global__ __launch_bounds__(256) void ct_pt_matmul_kernel(MatmulArgs g)
 } // namespace moai
 #include "matmul_mfma.hip.h" // the same product on the int8 matrix cores (MOAI_MATMUL_MFMA)
 #include "ctct_mfma.hip.h"   // moai_ct_ct_matmul: every sum of ciphertext x ciphertext products of a matrix on the same cores
+#include "ctpt_many.hip.h"   // moai_ct_pt_dot_many: every giant-step sum of a transform in one pass over its baby steps
 namespace moai {
 
 // ---- row moves: level drop, Galois gather ---------------------------------------------------------------------------
@@ -1506,6 +1507,131 @@ extern "C" int moai_ct_pt_dot2(moai_ctx *c, const uint64_t *x, const uint64_t *p
         return set_error(MOAI_EINVAL, "null argument");
     }
     return ct_pt_dot_common(c, x, p, out, out2, x_index, p_index, p_index2, terms, terms2, n_poly, L, stream);
+}
+
+// The term of output j (of the group in g) with operand ix and plaintext ip joins the first column of that operand in which
+// the output has no term yet, else a new column; false when the group has no column left.
+static bool ct_pt_many_add(CtPtManyArgs &g, uint32_t j, uint32_t ix, uint32_t ip)
+{
+    uint32_t c = 0;
+    while (c < g.cols && (g.xi[c] != ix || (g.mask[c] >> j & 1u)))
+    {
+        ++c;
+    }
+    if (c == g.cols)
+    {
+        if (g.cols == (uint32_t)CPM_COLS)
+        {
+            return false;
+        }
+        g.xi[c] = ix;
+        g.mask[c] = 0;
+        ++g.cols;
+    }
+    g.mask[c] = (uint16_t)(g.mask[c] | 1u << j);
+    g.pi[c][j] = (uint16_t)ip;
+    return true;
+}
+
+// out[j] = the moai_ct_pt_dot of the j-th index lists, j < n_out: ct_pt_dot_many_kernel (ctpt_many.hip.h) over groups of outputs.
+// The outputs are cut into the fewest groups of at most CPM_G, of equal size up to one; a group also ends where its lists need
+// more than CPM_COLS columns.  Every argument is checked before the first launch.
+extern "C" int moai_ct_pt_dot_many(moai_ctx *c, const uint64_t *x, const uint64_t *p, uint64_t *out, size_t out_stride,
+                                   const uint32_t *x_index, const uint32_t *p_index, const uint32_t *terms, size_t n_out,
+                                   size_t n_poly, size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, x, p, out);
+    MOAI_TRY(check_rows(c, n_poly, L));
+    if (n_out == 0 || n_out > 0xffffu || !terms)
+    {
+        return set_error(MOAI_EINVAL, "between 1 and 65535 outputs, each with its number of terms");
+    }
+    size_t total = 0;
+    for (size_t j = 0; j < n_out; ++j)
+    {
+        if (terms[j] == 0 || terms[j] > (uint32_t)CTPT_MAX_TERMS)
+        {
+            return set_error(MOAI_EINVAL, "output %zu: %u terms, between 1 and 64 per output", j, terms[j]);
+        }
+        total += terms[j];
+    }
+    trace_op("ct_pt_dot", L, n_poly * total); // the same products as n_out moai_ct_pt_dot calls
+    if (n_poly == 0 || L == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!x || !p || !out || !x_index || !p_index)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    uint32_t x_top = 0, p_top = 0;
+    for (size_t t = 0; t < total; ++t)
+    {
+        if (x_index[t] > 0xffffu || p_index[t] > 0xffffu)
+        {
+            return set_error(MOAI_EINVAL, "operand index out of range");
+        }
+        x_top = std::max(x_top, x_index[t]);
+        p_top = std::max(p_top, p_index[t]);
+    }
+    const size_t row = L * c->n, block = n_poly * row;
+    if (n_out > 1 && out_stride < block)
+    {
+        return set_error(MOAI_EINVAL, "outputs %zu words apart overlap: a block is %zu words", out_stride, block);
+    }
+    const uint64_t *out_end = out + (n_out - 1) * out_stride + block;
+    if ((out < x + ((size_t)x_top + 1) * block && x < out_end) || (out < p + ((size_t)p_top + 1) * row && p < out_end))
+    {
+        return set_error(MOAI_EINVAL, "an output overlaps an operand or a plaintext");
+    }
+    const size_t cap = (n_out + (n_out + CPM_G - 1) / CPM_G - 1) / ((n_out + CPM_G - 1) / CPM_G);
+    const size_t cblocks = (c->n + 255) / 256;
+    if (cblocks * n_poly > 0x7fffffffull)
+    {
+        return set_error(MOAI_EINVAL, "batch too large for one launch");
+    }
+    CtPtManyArgs g;
+    g.x = x;
+    g.p = p;
+    g.out_stride = out_stride;
+    g.n_poly = (uint32_t)n_poly;
+    fill_rows(g, c, L);
+    for (size_t j0 = 0, t0 = 0; j0 < n_out;)
+    {
+        g.out = out + j0 * out_stride;
+        g.cols = 0;
+        size_t j = j0, t = t0;
+        for (; j < n_out && j - j0 < cap; ++j)
+        {
+            const CtPtManyArgs before = g;
+            bool fits = true;
+            for (uint32_t e = 0; e < terms[j] && fits; ++e)
+            {
+                fits = ct_pt_many_add(g, (uint32_t)(j - j0), x_index[t + e], p_index[t + e]);
+            }
+            if (!fits) // never the first output of a group: its terms are at most CPM_COLS columns
+            {
+                g = before;
+                break;
+            }
+            t += terms[j];
+        }
+        g.gcount = (uint32_t)(j - j0);
+        // one polynomial per thread below three, else four for up to eight outputs and three for up to CPM_G
+        const uint32_t P = n_poly < 3 ? 1u : g.gcount <= 8u ? 4u : 3u;
+        g.pgroups = (uint32_t)((n_poly + P - 1) / P);
+        const dim3 grid((uint32_t)(cblocks * g.pgroups), (uint32_t)L);
+        void (*kernel)(CtPtManyArgs) = ct_pt_dot_many_kernel<CPM_G, 3>;
+        if (P != 3u)
+        {
+            kernel = P == 1u ? ct_pt_dot_many_kernel<CPM_G, 1> : ct_pt_dot_many_kernel<8, 4>;
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
+        MOAI_LAUNCH_CHECK();
+        j0 = j;
+        t0 = t;
+    }
+    return MOAI_OK;
 }
 
 extern "C" int moai_ct_pt_dot_rows(moai_ctx *c, const uint64_t *x, const uint64_t *p, const uint64_t *p2, uint64_t *out, uint64_t *out2,

@@ -56,6 +56,7 @@ SYMBOLS = {
     "moai_ct_pt_dot": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, vp]),
     "moai_ct_pt_dot_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "moai_ct_pt_dot2": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, sz, vp]),
+    "moai_ct_pt_dot_many": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, vp]),
     "moai_ct_pt_matmul": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, sz, vp]),
     "moai_ct_pt_matmul_path": (C.c_int, [vp, sz, sz, sz, sz, C.POINTER(C.c_int)]),
     "moai_rescale": (C.c_int, [vp, vp, vp, sz, sz, sz, vp]),
@@ -360,6 +361,15 @@ class Context:
         pi2 = (C.c_uint32 * max(1, len(p_index2)))(*[int(v) for v in p_index2])
         _check(lib().moai_ct_pt_dot2(self.h, _ptr(x), _ptr(p), _ptr(out), _ptr(out2), xi, pi, pi2, len(x_index), len(p_index2), n_poly, L,
                                      stream))
+
+    def ct_pt_dot_many(self, x, p, out, out_stride, x_index, p_index, n_poly, L, stream=None):
+        """out + j * out_stride words = the ct_pt_dot of the lists x_index[j], p_index[j], for every j, in one pass over the operands"""
+        flat_x = [int(v) for lst in x_index for v in lst]
+        flat_p = [int(v) for lst in p_index for v in lst]
+        xi = (C.c_uint32 * max(1, len(flat_x)))(*flat_x)
+        pi = (C.c_uint32 * max(1, len(flat_p)))(*flat_p)
+        terms = (C.c_uint32 * max(1, len(x_index)))(*[len(lst) for lst in x_index])
+        _check(lib().moai_ct_pt_dot_many(self.h, _ptr(x), _ptr(p), _ptr(out), out_stride, xi, pi, terms, len(x_index), n_poly, L, stream))
 
     def ct_pt_dot_rows(self, x, p, p2, out, out2, rows, n_poly, L, stream=None):
         _check(lib().moai_ct_pt_dot_rows(self.h, _ptr(x), _ptr(p), _ptr(p2) if p2 is not None else None, _ptr(out),
