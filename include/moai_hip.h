@@ -206,6 +206,26 @@ int moai_ct_dot(moai_ctx *ctx, const uint64_t *x, const uint64_t *y, uint64_t *o
  * moai_ct_dot(a + i*k*2*L*N, b + j*k*2*L*N, out[j][i], k, L) for every (i, j).  1 <= k <= 4096. */
 int moai_ct_ct_matmul(moai_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t m, size_t nb, size_t k,
                       size_t L, void *stream);
+/* The products and sums of out[i] = sum_j multiply(X[j], rotate(W[j], step_i)) -- the Q.K^T loop of ct_ct_matrix_mul_colpacking,
+ * include/source/matrix_mul/Ct_ct_matrix_mul.hpp:6-56 (ckks_multiply SEAL/evaluator.cpp:805-860, add_inplace :155-240) -- with
+ * the key switches of the rotations DEFERRED until after the sum.  The NTT-form automorphism pi of element e is a permutation
+ * (GaloisTool::apply_galois_ntt, SEAL/util/galois.cpp:192-218), and (pi(w0), pi(w1)) encrypts pi(m_W) under pi(s) as it
+ * stands, so  m_X pi(m_W) = x0 pi(w0) + x1 pi(w0) s + [x0 pi(w1) + x1 pi(w1) s] pi(s).  For every element elts[i]:
+ *   out[i] = (A0, A1, B0, B1),  A0 = sum_t x[t][0] (.) pi(w[t][0]),  A1 = sum_t x[t][1] (.) pi(w[t][0]),
+ *                               B0 = sum_t x[t][0] (.) pi(w[t][1]),  B1 = sum_t x[t][1] (.) pi(w[t][1]).
+ * moai_galois_fold brings (B0, B1) back under s with two key switches per output, whatever `terms` is.
+ *   x, w: [terms][2][L][N], NTT form;  out: [n_out][4][L][N], not an operand;  elts: HOST array of n_out elements, odd, < 2N.
+ * Canonical residues: the bits of moai_galois_permute of every w[t] by elts[i] followed by dyadic products and additions
+ * mod q, for any prime below 2^61.  Every x word is read once per group of up to 12 outputs; an element that is 1 modulo a
+ * power of two large enough to keep its permutation inside aligned blocks of 256 coefficients (MOAI's 5^(i num_batch)) reads
+ * w through LDS, any other one gathers it from memory: the same bits.
+ * 1 <= terms <= 65536: the 128-bit sums are folded every 32 terms, so their width does not limit the sum; 65536 is what
+ * the kernel's term counter and these checks are written for.  Nothing is enqueued when an argument is refused: MOAI_EINVAL
+ * for a null argument, an even element or one >= 2N, terms outside that range, or an output that overlaps an operand.
+ * n_out == 0 is MOAI_OK.  No scratch memory; the call does not synchronise.  moai_op_trace: n_out * terms units of
+ * "ct_dot_galois". */
+int moai_ct_dot_galois(moai_ctx *ctx, const uint64_t *x, const uint64_t *w, uint64_t *out, const uint32_t *elts, size_t n_out,
+                       size_t terms, size_t L, void *stream);
 /* out[poly] = sum over t < terms of multiply_plain(x[x_index[t]][poly], p[p_index[t]]) (evaluator.cpp:2336-2373)
  * accumulated with add_inplace: the inner loop of the baby-step / giant-step linear transforms of MOAI's
  * bootstrapping (include/source/bootstrapping/Bootstrapper.cpp:2028-2046, 2095-2113) for a whole batch.
@@ -347,6 +367,23 @@ int moai_apply_galois_ptrs(moai_ctx *ctx, const uint64_t *const *ins, uint64_t *
  * ("relinearize") as above. */
 int moai_relinearize_ptrs(moai_ctx *ctx, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *relin_key, size_t L,
                           size_t n, void *stream);
+/* The two key switches that end moai_ct_dot_galois, and the assembly of the size-3 ciphertext that the reference's
+ * relinearize receives at that point of ct_ct_matrix_mul_colpacking (include/source/matrix_mul/Ct_ct_matrix_mul.hpp:6-56;
+ * they stand for the `terms` switches of its rotate_vector calls, Evaluator::switch_key_inplace SEAL/evaluator.cpp:2724-3020):
+ *   out[i] = (A0 + u0, A1 + u1 + v0, v1),  (u0, u1) = moai_switch_key of target B0 into a zero ciphertext with keys[i],
+ *                                          (v0, v1) = the same of target B1  (it still carries the factor s),
+ * bit for bit, i < n_out.  acc: [n_out][4][L][N] as moai_ct_dot_galois writes it; out: [n_out][3][L][N], not acc;
+ * keys: HOST array of n_out device pointers, keys[i] the Galois key of elts[i] (the key that switches pi(s) to s) in
+ * moai_kswitch_keygen's layout, whole, moai_key_trim'med or born limited.  The 2 n_out switches run as one list, 64 per pass
+ * (moai_apply_galois_ptrs' machinery), and one small kernel per pass adds v0 and places v1.
+ * Noise.  The products and sums are exact.  With E the bound of one moai_switch_key at this level (the alpha = 1 case of
+ * the formula under "hybrid key switching" below), out[i] decrypts under (1, s, s^2) to sum_j m_X[j] pi(m_W[j]) with an
+ * error of at most E (1 + |s|_1) per coefficient (e + e' s for the two switches' errors e, e'), plus nothing else, and
+ * independent of `terms`; the conventional order multiplies every rotation's switch error by m_X[j].
+ * MOAI_EINVAL for a null argument or key or an output that overlaps acc, MOAI_ERANGE for a key limited below L; nothing is
+ * enqueued then.  n_out == 0 is MOAI_OK.  The call does not synchronise.  moai_op_trace: n_out units of "galois_fold". */
+int moai_galois_fold(moai_ctx *ctx, const uint64_t *acc, const uint64_t *const *keys, uint64_t *out, size_t n_out, size_t L,
+                     void *stream);
 
 /* ---- MOAI-owned integer kernel ---------------------------------------------------------------------------
  * Bootstrapper::modraise_inplace include/source/bootstrapping/Bootstrapper.cpp:2938-2992:

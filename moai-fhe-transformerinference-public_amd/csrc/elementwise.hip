@@ -829,6 +829,7 @@ __global__ __launch_bounds__(256) void ct_pt_matmul_kernel(MatmulArgs g)
 #include "matmul_mfma.hip.h" // the same product on the int8 matrix cores (MOAI_MATMUL_MFMA)
 #include "ctct_mfma.hip.h"   // moai_ct_ct_matmul: every sum of ciphertext x ciphertext products of a matrix on the same cores
 #include "ctpt_many.hip.h"   // moai_ct_pt_dot_many: every giant-step sum of a transform in one pass over its baby steps
+#include "ctdot_galois.hip.h" // moai_ct_dot_galois: sums of products with Galois-permuted operands, before any key switch
 namespace moai {
 
 // ---- row moves: level drop, Galois gather ---------------------------------------------------------------------------
@@ -1366,6 +1367,80 @@ extern "C" int moai_ct_ct_matmul(moai_ctx *c, const uint64_t *a, const uint64_t 
     }
     hipLaunchKernelGGL(ct_ct_matmul_mfma_kernel, dim3((uint32_t)blocks, (uint32_t)L), dim3(256), 0, (hipStream_t)stream, g);
     MOAI_LAUNCH_CHECK();
+    return MOAI_OK;
+}
+
+// out[i] = (A0, A1, B0, B1) of x and the image of w under elts[i]: ct_dot_galois_kernel (ctdot_galois.hip.h) over groups of at most
+// CDG_G (staged) or CDG_G_GATHER outputs.  An element whose permutation stays inside aligned blocks of CDG_BLOCK coefficients takes the staged form (w through
+// LDS), every other one the gather form; the outputs are grouped by form, in their order.  Everything is checked, and every
+// table built, before the first launch.  No scratch, so no op_mutex.
+extern "C" int moai_ct_dot_galois(moai_ctx *c, const uint64_t *x, const uint64_t *w, uint64_t *out, const uint32_t *elts, size_t n_out,
+                                  size_t terms, size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, x, w, out);
+    trace_op("ct_dot_galois", L, n_out * terms);
+    if (terms == 0 || terms > CDG_MAX_TERMS)
+    {
+        return set_error(MOAI_EINVAL, "a sum of %zu terms: 1 .. %zu", terms, CDG_MAX_TERMS);
+    }
+    if (n_out > 0x7fffffffull / 4)
+    {
+        return set_error(MOAI_EINVAL, "batch too large for one launch");
+    }
+    MOAI_TRY(check_rows(c, std::max(2 * terms, 4 * n_out), L));
+    if (n_out == 0 || L == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!x || !w || !out || !elts)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        MOAI_TRY(galois_elt_check(c, elts[i]));
+    }
+    const size_t n = c->n, in_bytes = terms * 2 * L * n * sizeof(uint64_t), out_bytes = n_out * 4 * L * n * sizeof(uint64_t);
+    if (overlap(out, out_bytes, x, in_bytes) || overlap(out, out_bytes, w, in_bytes))
+    {
+        return set_error(MOAI_EINVAL, "the output overlaps an operand");
+    }
+    // the two forms' outputs, each in the caller's order.  e = 1 mod 2^k keeps aligned blocks of N / 2^(k-1) coefficients
+    std::vector<uint32_t> form[2];
+    std::vector<const uint32_t *> tables(n_out);
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        const uint32_t e = elts[i];
+        const size_t closed = e == 1 ? 1 : n >> (__builtin_ctz(e - 1) - 1);
+        form[n >= CDG_BLOCK && closed <= CDG_BLOCK].push_back((uint32_t)i);
+        MOAI_TRY(galois_table(c, e, &tables[i]));
+    }
+    CtDotGaloisArgs g;
+    g.x = x;
+    g.w = w;
+    g.out = out;
+    g.terms = (uint32_t)terms;
+    fill_rows(g, c, L);
+    const dim3 grid((uint32_t)((n + CDG_BLOCK - 1) / CDG_BLOCK), (uint32_t)L);
+    for (int staged = 0; staged < 2; ++staged)
+    {
+        MOAI_TRY(for_chunks(form[staged].size(), staged ? CDG_G : CDG_G_GATHER, [&](size_t j0, size_t cnt) {
+            for (size_t j = 0; j < (size_t)CDG_G; ++j)
+            {
+                g.oi[j] = form[staged][j0 + (j < cnt ? j : 0)]; // the unused entries repeat the group's first output; never read
+                g.table[j] = tables[g.oi[j]];
+            }
+            g.gcount = (uint32_t)cnt;
+            void (*kernel)(CtDotGaloisArgs) = ct_dot_galois_kernel<CDG_G_GATHER, false>;
+            if (staged)
+            {
+                kernel = ct_dot_galois_kernel<CDG_G, true>;
+            }
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        }));
+    }
     return MOAI_OK;
 }
 

@@ -1154,23 +1154,56 @@ int ks_list_check_blocks(const moai_ctx *c, const uint64_t *const *ins, uint64_t
     return MOAI_OK;
 }
 
-// What the two list entry points share.  relin: member i is [3][L][N], its third polynomial is switched with `one_key` and the
-// first two are added (moai_relinearize); else member i is [2][L][N] and gets apply_galois by elts[i] with keys[i], plus sums[i].
+// The tail of a pass of moai_galois_fold.  Members 2b and 2b + 1 of the pass are output b's two switches: lst->outs[2b] is the
+// output [3][L][N], whose first two polynomials hold (A0 + u0, A1 + u1), and lst->outs[2b + 1] the pass's scratch pair (v0, v1).
+// Polynomial 1 += v0, polynomial 2 = v1.  blockIdx.y = (b * 2 + p) * L + prime; b and p are uniform over the workgroup.
+__global__ __launch_bounds__(256) void galois_fold_tail_kernel(const KsList *lst, const PrimeConst *pc, uint32_t L, uint32_t n2)
+{
+    const uint32_t prime = blockIdx.y % L, p = blockIdx.y / L & 1u, b = blockIdx.y / (2u * L);
+    const uint64_t q = pc[prime].q;
+    const ulonglong2 *v = reinterpret_cast<const ulonglong2 *>(lst->outs[2 * b + 1]) + ((size_t)p * L + prime) * n2;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(lst->outs[2 * b]) + ((size_t)(1 + p) * L + prime) * n2;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n2; j += gridDim.x * 256u)
+    {
+        o[j] = p ? v[j] : add2(o[j], v[j], q);
+    }
+}
+
+enum KsListForm
+{
+    KS_LIST_GALOIS,
+    KS_LIST_RELIN,
+    KS_LIST_FOLD
+};
+
+// What the list entry points share, in one of three forms.  KS_LIST_RELIN: member i is [3][L][N], its third polynomial is
+// switched with `one_key` and the first two are added (moai_relinearize).  KS_LIST_GALOIS: member i is [2][L][N] and gets
+// apply_galois by elts[i] with keys[i], plus sums[i].
+// KS_LIST_FOLD (moai_galois_fold, which has validated its own arguments and made the lists): member i is [3][L][N], its third
+// polynomial is switched with keys[i] and only sums[i] is added; members come in pairs, outs[2b] the output [3][L][N] and
+// outs[2b + 1] null: that switch goes to a scratch pair, and galois_fold_tail_kernel ends the pass.
 // Everything is validated before anything is enqueued; then at most KS_LIST_MAX members per pass: the list, one gather that
 // also permutes (galois_gather_kernel<true>) into the contiguous scratch, and the key switch with the LIST kernels.
 static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const *outs, size_t L, const uint32_t *elts,
-                        const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n, bool relin, void *stream)
+                        const uint64_t *const *keys, const uint64_t *one_key, const uint64_t *const *sums, size_t n, KsListForm form, void *stream)
 {
+    const bool relin = form == KS_LIST_RELIN, fold = form == KS_LIST_FOLD;
     if (n == 0)
     {
         return MOAI_OK;
     }
-    MOAI_TRY(ks_list_check_members(ins, outs, elts, keys, one_key, n, relin));
+    if (!fold)
+    {
+        MOAI_TRY(ks_list_check_members(ins, outs, elts, keys, one_key, n, relin));
+    }
     const size_t nb = n < KS_LIST_MAX ? n : KS_LIST_MAX; // members per pass
-    MOAI_TRY(check_level(c, L, nb * (relin ? 3 : 2)));
+    MOAI_TRY(check_level(c, L, nb * (relin || fold ? 3 : 2)));
     MOAI_TRY(check_switch_level(c, L));
     const size_t rn = L * c->n, in_bytes = (relin ? 3 : 2) * rn * sizeof(uint64_t), out_bytes = 2 * rn * sizeof(uint64_t);
-    MOAI_TRY(ks_list_check_blocks(c, ins, outs, elts, sums, n, in_bytes, out_bytes, relin));
+    if (!fold)
+    {
+        MOAI_TRY(ks_list_check_blocks(c, ins, outs, elts, sums, n, in_bytes, out_bytes, relin));
+    }
     std::vector<uint32_t> key_rows(n);
     if (relin)
     {
@@ -1179,44 +1212,54 @@ static int ks_ptrs_impl(moai_ctx *c, const uint64_t *const *ins, uint64_t *const
     }
     for (size_t i = 0; !relin && i < n; ++i)
     {
-        MOAI_TRY(key_rows_for(c, keys[i], L, &key_rows[i], (long)i));
+        MOAI_TRY(key_rows_for(c, keys[i], L, &key_rows[i], fold ? (long)(i / 2) : (long)i));
     }
     std::vector<const uint32_t *> tables(n);
     for (size_t i = 0; i < n; ++i)
     {
-        // relinearize: element 1, the identity permutation -- the gather then only collects the third polynomials
-        MOAI_TRY(galois_table(c, relin ? 1u : elts[i], &tables[i]));
+        // relinearize and fold: element 1, the identity permutation -- the gather then only collects the third polynomials
+        MOAI_TRY(galois_table(c, relin || fold ? 1u : elts[i], &tables[i]));
     }
     hipStream_t s = (hipStream_t)stream;
-    const size_t rows_tmp = relin ? L : 2 * L; // rows per member of the gathered target
+    const size_t rows_tmp = relin || fold ? L : 2 * L; // rows per member of the gathered target
     const size_t sz_list = align256(sizeof(KsList)), sz_tmp = align256(nb * rows_tmp * c->n * sizeof(uint64_t));
+    const size_t sz_pair = fold ? align256(nb * rn * sizeof(uint64_t)) : 0; // fold: (v0, v1) of every second member of a pass
     std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
     void *wsp;
-    MOAI_TRY(workspace(c, sz_list + sz_tmp + switch_key_ws_bytes(c, L, nb), s, &wsp));
+    MOAI_TRY(workspace(c, sz_list + sz_tmp + sz_pair + switch_key_ws_bytes(c, L, nb), s, &wsp));
     KsList *dlist = static_cast<KsList *>(wsp);
-    uint64_t *tmp = at_bytes(wsp, sz_list);
+    uint64_t *tmp = at_bytes(wsp, sz_list), *pair = at_bytes(wsp, sz_list + sz_tmp);
+    void *ks_ws = at_bytes(wsp, sz_list + sz_tmp + sz_pair);
     return for_chunks(n, KS_LIST_MAX, [&](size_t m0, size_t cnt) {
         KsList h;
         for (size_t e = 0; e < KS_LIST_MAX; ++e)
         {
             const size_t i = m0 + (e < cnt ? e : 0); // the unused entries repeat the pass's first member
             h.ins[e] = ins[i];
-            h.outs[e] = outs[i];
+            h.outs[e] = outs[i] ? outs[i] : pair + (e / 2) * 2 * rn;
             h.sums[e] = sums ? sums[i] : nullptr;
             h.keys[e] = relin ? one_key : keys[i];
             h.tables[e] = tables[i];
             h.key_rows[e] = key_rows[i];
         }
         MOAI_TRY(ks_list_write(h, dlist, s));
+        if (fold)
+        {
+            // tmp [cnt][L][N] = B0 or B1 of the members; outs = switch_key(tmp) + sums, then the pairs are joined
+            MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
+            MOAI_TRY(switch_key_impl(c, nullptr, { tmp, L, 0, dlist }, nullptr, L, cnt, ks_ws, s, { nullptr, 0, 0 }));
+            return launch_rows(galois_fold_tail_kernel, c, cnt * L, s, (const KsList *)dlist, (const PrimeConst *)c->pc, (uint32_t)L,
+                               (uint32_t)(c->n >> 1));
+        }
         if (relin)
         {
             // tmp [cnt][L][N] = the members' third polynomials; out = (c0, c1) + switch_key(c2)   (evaluator.cpp:1383-1392)
             MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, L, 2 * L, s));
-            return switch_key_impl(c, nullptr, { tmp, L, 0, dlist }, nullptr, L, cnt, at_bytes(wsp, sz_list + sz_tmp), s, { nullptr, 0, 1 });
+            return switch_key_impl(c, nullptr, { tmp, L, 0, dlist }, nullptr, L, cnt, ks_ws, s, { nullptr, 0, 1 });
         }
         // tmp [cnt][2][L][N] = galois(ins); out = (galois(in0), 0) + switch_key(galois(in1)) [+ sum]   (evaluator.cpp:2631-2654)
         MOAI_TRY(galois_gather_list(c, dlist, tmp, cnt, 2 * L, 0, s));
-        return switch_key_impl(c, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, cnt, at_bytes(wsp, sz_list + sz_tmp), s, { tmp, 2 * L, 2 });
+        return switch_key_impl(c, nullptr, { tmp, 2 * L, L, dlist }, nullptr, L, cnt, ks_ws, s, { tmp, 2 * L, 2 });
     });
 }
 
@@ -1230,7 +1273,7 @@ extern "C" int moai_apply_galois_ptrs(moai_ctx *c, const uint64_t *const *ins, u
         MOAI_AUDIT(stream, ins[i], outs[i], galois_keys[i], sums ? sums[i] : nullptr);
     }
     trace_op("apply_galois_to", L, n); // the calls it replaces
-    return ks_ptrs_impl(c, ins, outs, L, galois_elts, galois_keys, nullptr, sums, n, false, stream);
+    return ks_ptrs_impl(c, ins, outs, L, galois_elts, galois_keys, nullptr, sums, n, KS_LIST_GALOIS, stream);
 }
 
 extern "C" int moai_relinearize_ptrs(moai_ctx *c, const uint64_t *const *ct3s, uint64_t *const *outs, const uint64_t *relin_key, size_t L,
@@ -1242,7 +1285,51 @@ extern "C" int moai_relinearize_ptrs(moai_ctx *c, const uint64_t *const *ct3s, u
         MOAI_AUDIT(stream, ct3s[i], outs[i]);
     }
     trace_op("relinearize", L, n);
-    return ks_ptrs_impl(c, ct3s, outs, L, nullptr, nullptr, relin_key, nullptr, n, true, stream);
+    return ks_ptrs_impl(c, ct3s, outs, L, nullptr, nullptr, relin_key, nullptr, n, KS_LIST_RELIN, stream);
+}
+
+// Members 2i and 2i + 1 of one list are output i's two switches, both with keys[i]: (A0, A1, B0) switches B0 into out[i]'s first
+// two polynomials on top of (A0, A1); (A1, B0, B1) -- the same block one polynomial on -- switches B1 into the pass's scratch.
+extern "C" int moai_galois_fold(moai_ctx *c, const uint64_t *acc, const uint64_t *const *keys, uint64_t *out, size_t n_out, size_t L,
+                                void *stream)
+{
+    MOAI_AUDIT(stream, acc, out);
+    trace_op("galois_fold", L, n_out);
+    if (n_out > 0x7fffffffull / 4)
+    {
+        return set_error(MOAI_EINVAL, "batch too large for one launch");
+    }
+    MOAI_TRY(check_level(c, L, 4 * n_out));
+    if (n_out == 0)
+    {
+        return MOAI_OK;
+    }
+    if (!acc || !keys || !out)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        if (!keys[i])
+        {
+            return set_error(MOAI_EINVAL, "output %zu: null key", i);
+        }
+    }
+    const size_t rn = L * c->n;
+    if (overlap(out, n_out * 3 * rn * sizeof(uint64_t), acc, n_out * 4 * rn * sizeof(uint64_t)))
+    {
+        return set_error(MOAI_EINVAL, "the output overlaps the sums");
+    }
+    std::vector<const uint64_t *> ins(2 * n_out), sums(2 * n_out, nullptr), ks(2 * n_out);
+    std::vector<uint64_t *> outs(2 * n_out, nullptr);
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        ins[2 * i] = sums[2 * i] = acc + i * 4 * rn;
+        ins[2 * i + 1] = acc + i * 4 * rn + rn;
+        outs[2 * i] = out + i * 3 * rn;
+        ks[2 * i] = ks[2 * i + 1] = keys[i];
+    }
+    return ks_ptrs_impl(c, ins.data(), outs.data(), L, nullptr, ks.data(), nullptr, sums.data(), 2 * n_out, KS_LIST_FOLD, stream);
 }
 
 extern "C" int moai_modraise(moai_ctx *c, const uint64_t *in, uint64_t *out, size_t L_out, size_t batch, void *stream)

@@ -110,6 +110,8 @@ SYMBOLS = {
     "moai_ct_dot_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, vp, vp, sz, vp]),
     "moai_apply_galois_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
     "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
+    "moai_ct_dot_galois": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_uint32), sz, sz, sz, vp]),
+    "moai_galois_fold": (C.c_int, [vp, vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_hybrid_digits": (sz, [vp, sz, sz]),
     "moai_hybrid_fused_groups": (sz, [vp, sz, sz, sz]),
     "moai_hybrid_fused_down_launches": (sz, [vp, sz, sz, sz]),
@@ -606,6 +608,18 @@ class Context:
         ai = (vp * n)(*[_ptr(x) for x in ct3s])
         ao = (vp * n)(*[_ptr(x) for x in outs])
         _check(lib().moai_relinearize_ptrs(self.h, ai, ao, _ptr(key), L, n, stream))
+
+    def ct_dot_galois(self, x, w, out, elts, terms, L, stream=None):
+        """out[i] [4][L][N] = (A0, A1, B0, B1) of sum_t x[t] (.) pi_i(w[t]) for every Galois element elts[i], no key switch yet;
+        x, w [terms][2][L][N]"""
+        e = (C.c_uint32 * max(1, len(elts)))(*[int(v) for v in elts])
+        _check(lib().moai_ct_dot_galois(self.h, _ptr(x), _ptr(w), _ptr(out), e, len(elts), terms, L, stream))
+
+    def galois_fold(self, acc, keys, out, L, stream=None):
+        """out[i] [3][L][N] = acc[i]'s (A0, A1) plus the key switches of B0 and B1 with keys[i]: what ct_dot_galois leaves to do"""
+        n = len(keys)
+        ak = (vp * max(1, n))(*[_ptr(k) for k in keys])
+        _check(lib().moai_galois_fold(self.h, _ptr(acc), ak, _ptr(out), n, L, stream))
 
     def gather_blocks(self, blocks, packed, words, stream=None):
         """packed[i] = blocks[i] (`words` 64-bit words each) in one launch"""
