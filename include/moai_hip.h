@@ -222,10 +222,24 @@ int moai_ct_ct_matmul(moai_ctx *ctx, const uint64_t *a, const uint64_t *b, uint6
  * 1 <= terms <= 65536: the 128-bit sums are folded every 32 terms, so their width does not limit the sum; 65536 is what
  * the kernel's term counter and these checks are written for.  Nothing is enqueued when an argument is refused: MOAI_EINVAL
  * for a null argument, an even element or one >= 2N, terms outside that range, or an output that overlaps an operand.
- * n_out == 0 is MOAI_OK.  No scratch memory; the call does not synchronise.  moai_op_trace: n_out * terms units of
- * "ct_dot_galois". */
+ * n_out == 0 is MOAI_OK.  No scratch memory in those two forms; the call does not synchronise.  moai_op_trace: n_out * terms
+ * units of "ct_dot_galois".
+ * With MOAI_CTDOT_GALOIS_MFMA = v > 0 a third form takes the outputs whose permutation stays inside aligned blocks of 128
+ * coefficients, when N >= 128, terms <= 16383 and the call has at least v of them: per block, all their words are entries of one
+ * 256 x 256 x terms Gram matrix of x and w, formed exactly on the int8 matrix cores from signed byte limbs (as
+ * MOAI_MATMUL_PATH_MFMA) in one launch for all those outputs; the same bits.  It keeps 16 bytes per such output in the stream's
+ * arena (moai_ctx_reserve_stream). */
 int moai_ct_dot_galois(moai_ctx *ctx, const uint64_t *x, const uint64_t *w, uint64_t *out, const uint32_t *elts, size_t n_out,
                        size_t terms, size_t L, void *stream);
+/* How many outputs that call would send NOW to each form, the tuning knob included: counts[MOAI_CT_DOT_GALOIS_GATHER], [_STAGED]
+ * and [_GRAM] (read-only; no launch, no stream; the call and this query ask the same host function, after the same checks of
+ * (elts, n_out, terms, L)).  The automorphism is GaloisTool::apply_galois_ntt's (SEAL/util/galois.cpp:192-218); which aligned
+ * blocks it keeps follows from its index map (galois.cpp:18-51).  MOAI_EINVAL for a null argument and for whatever
+ * moai_ct_dot_galois refuses in those arguments; n_out == 0 is MOAI_OK with three zeros. */
+#define MOAI_CT_DOT_GALOIS_GATHER 0
+#define MOAI_CT_DOT_GALOIS_STAGED 1
+#define MOAI_CT_DOT_GALOIS_GRAM 2
+int moai_ct_dot_galois_forms(moai_ctx *ctx, const uint32_t *elts, size_t n_out, size_t terms, size_t L, uint32_t counts[3]);
 /* out[poly] = sum over t < terms of multiply_plain(x[x_index[t]][poly], p[p_index[t]]) (evaluator.cpp:2336-2373)
  * accumulated with add_inplace: the inner loop of the baby-step / giant-step linear transforms of MOAI's
  * bootstrapping (include/source/bootstrapping/Bootstrapper.cpp:2028-2046, 2095-2113) for a whole batch.
@@ -645,7 +659,8 @@ int moai_kswitch_keygen_seal_seeded(moai_ctx *ctx, const uint8_t *noise_key, con
  *   MOAI_MD_FP_MIN_ROWS    256   polynomials * L from which mod-down and rescale use the FP64 arithmetic modes
  *   MOAI_MATMUL_FP         1     0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel
  *   MOAI_MATMUL_MFMA       0     1: moai_ct_pt_matmul runs on the int8 matrix cores (byte limbs, exact) where N >= 16
- *   MOAI_DEC_TMP_MB        1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
+ *   MOAI_CTDOT_GALOIS_MFMA 0     v > 0: outputs of moai_ct_dot_galois that permute inside blocks of 128 coefficients take the Gram form on the int8 matrix cores when a call has at least v of them
+ *   MOAI_DEC_TMP_MB       1024  MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller
  *   MOAI_CLIENT_TMP_KB     1048576 KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller
  *   MOAI_HYBRID_TMP_KB     16777216 KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight
  *   MOAI_HYBRID_HOIST_NR   4     rotations per pass of the hybrid hoisted MAC over the digits: 4, 2 or 1

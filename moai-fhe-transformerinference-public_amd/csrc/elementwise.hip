@@ -830,6 +830,7 @@ __global__ __launch_bounds__(256) void ct_pt_matmul_kernel(MatmulArgs g)
 #include "ctct_mfma.hip.h"   // moai_ct_ct_matmul: every sum of ciphertext x ciphertext products of a matrix on the same cores
 #include "ctpt_many.hip.h"   // moai_ct_pt_dot_many: every giant-step sum of a transform in one pass over its baby steps
 #include "ctdot_galois.hip.h" // moai_ct_dot_galois: sums of products with Galois-permuted operands, before any key switch
+#include "ctdot_galois_mfma.hip.h" // the same sums as one Gram block per orbit on the int8 matrix cores (MOAI_CTDOT_GALOIS_MFMA)
 namespace moai {
 
 // ---- row moves: level drop, Galois gather ---------------------------------------------------------------------------
@@ -1370,15 +1371,18 @@ extern "C" int moai_ct_ct_matmul(moai_ctx *c, const uint64_t *a, const uint64_t 
     return MOAI_OK;
 }
 
-// out[i] = (A0, A1, B0, B1) of x and the image of w under elts[i]: ct_dot_galois_kernel (ctdot_galois.hip.h) over groups of at most
-// CDG_G (staged) or CDG_G_GATHER outputs.  An element whose permutation stays inside aligned blocks of CDG_BLOCK coefficients takes the staged form (w through
-// LDS), every other one the gather form; the outputs are grouped by form, in their order.  Everything is checked, and every
-// table built, before the first launch.  No scratch, so no op_mutex.
-extern "C" int moai_ct_dot_galois(moai_ctx *c, const uint64_t *x, const uint64_t *w, uint64_t *out, const uint32_t *elts, size_t n_out,
-                                  size_t terms, size_t L, void *stream)
+// out[i] = (A0, A1, B0, B1) of x and the image of w under elts[i], in one of three forms per output (MOAI_CT_DOT_GALOIS_*):
+//   GRAM    MOAI_CTDOT_GALOIS_MFMA = v > 0, N >= CDGM_BLOCK, at most CDGM_MAX_TERMS terms, and at least v outputs of the call whose
+//           permutation stays inside aligned blocks of CDGM_BLOCK coefficients: those outputs, in ONE launch of
+//           ct_dot_galois_mfma_kernel (ctdot_galois_mfma.hip.h), whatever their number
+//   STAGED  of the others, an element whose permutation stays inside aligned blocks of CDG_BLOCK coefficients: ct_dot_galois_kernel
+//           (ctdot_galois.hip.h) with w through LDS, groups of at most CDG_G outputs
+//   GATHER  every other one: the same kernel's gather form, groups of at most CDG_G_GATHER
+// each form's outputs in the caller's order.  cdg_sizes and cdg_forms are the checks and the sorting of the call and of
+// moai_ct_dot_galois_forms.  Everything is checked, every table built and the Gram form's records given their scratch before the
+// first launch.  Only the Gram form has scratch (its CdgmOut records), so only it takes op_mutex.
+static int cdg_sizes(const moai_ctx *c, size_t n_out, size_t terms, size_t L)
 {
-    MOAI_AUDIT(stream, x, w, out);
-    trace_op("ct_dot_galois", L, n_out * terms);
     if (terms == 0 || terms > CDG_MAX_TERMS)
     {
         return set_error(MOAI_EINVAL, "a sum of %zu terms: 1 .. %zu", terms, CDG_MAX_TERMS);
@@ -1387,7 +1391,64 @@ extern "C" int moai_ct_dot_galois(moai_ctx *c, const uint64_t *x, const uint64_t
     {
         return set_error(MOAI_EINVAL, "batch too large for one launch");
     }
-    MOAI_TRY(check_rows(c, std::max(2 * terms, 4 * n_out), L));
+    return check_rows(c, std::max(2 * terms, 4 * n_out), L);
+}
+
+// e = 1 mod 2^k keeps aligned blocks of N / 2^(k-1) coefficients
+static int cdg_forms(const moai_ctx *c, const uint32_t *elts, size_t n_out, size_t terms, std::vector<uint32_t> (&form)[3])
+{
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        MOAI_TRY(galois_elt_check(c, elts[i]));
+    }
+    const size_t n = c->n;
+    auto closed = [n](uint32_t e) { return e == 1 ? (size_t)1 : n >> (__builtin_ctz(e - 1) - 1); };
+    const long least = tuning(K_CTDOT_GALOIS_MFMA);
+    size_t eligible = 0;
+    for (size_t i = 0; i < n_out && least > 0 && n >= CDGM_BLOCK && terms <= CDGM_MAX_TERMS; ++i)
+    {
+        eligible += closed(elts[i]) <= CDGM_BLOCK;
+    }
+    const bool gram = eligible > 0 && eligible >= (size_t)least;
+    for (size_t i = 0; i < n_out; ++i)
+    {
+        const size_t cl = closed(elts[i]);
+        const int f = gram && cl <= CDGM_BLOCK ? MOAI_CT_DOT_GALOIS_GRAM
+                                               : n >= CDG_BLOCK && cl <= CDG_BLOCK ? MOAI_CT_DOT_GALOIS_STAGED : MOAI_CT_DOT_GALOIS_GATHER;
+        form[f].push_back((uint32_t)i);
+    }
+    return MOAI_OK;
+}
+
+extern "C" int moai_ct_dot_galois_forms(moai_ctx *c, const uint32_t *elts, size_t n_out, size_t terms, size_t L, uint32_t counts[3])
+{
+    if (!counts)
+    {
+        return set_error(MOAI_EINVAL, "null argument");
+    }
+    MOAI_TRY(cdg_sizes(c, n_out, terms, L));
+    std::vector<uint32_t> form[3];
+    if (n_out != 0 && L != 0)
+    {
+        if (!elts)
+        {
+            return set_error(MOAI_EINVAL, "null argument");
+        }
+        MOAI_TRY(cdg_forms(c, elts, n_out, terms, form));
+    }
+    for (int f = 0; f < 3; ++f)
+    {
+        counts[f] = (uint32_t)form[f].size();
+    }
+    return MOAI_OK;
+}
+
+extern "C" int moai_ct_dot_galois(moai_ctx *c, const uint64_t *x, const uint64_t *w, uint64_t *out, const uint32_t *elts, size_t n_out,
+                                  size_t terms, size_t L, void *stream)
+{
+    MOAI_AUDIT(stream, x, w, out);
+    trace_op("ct_dot_galois", L, n_out * terms);
+    MOAI_TRY(cdg_sizes(c, n_out, terms, L));
     if (n_out == 0 || L == 0)
     {
         return MOAI_OK;
@@ -1396,24 +1457,48 @@ extern "C" int moai_ct_dot_galois(moai_ctx *c, const uint64_t *x, const uint64_t
     {
         return set_error(MOAI_EINVAL, "null argument");
     }
-    for (size_t i = 0; i < n_out; ++i)
-    {
-        MOAI_TRY(galois_elt_check(c, elts[i]));
-    }
+    std::vector<uint32_t> form[3];
+    MOAI_TRY(cdg_forms(c, elts, n_out, terms, form));
     const size_t n = c->n, in_bytes = terms * 2 * L * n * sizeof(uint64_t), out_bytes = n_out * 4 * L * n * sizeof(uint64_t);
     if (overlap(out, out_bytes, x, in_bytes) || overlap(out, out_bytes, w, in_bytes))
     {
         return set_error(MOAI_EINVAL, "the output overlaps an operand");
     }
-    // the two forms' outputs, each in the caller's order.  e = 1 mod 2^k keeps aligned blocks of N / 2^(k-1) coefficients
-    std::vector<uint32_t> form[2];
     std::vector<const uint32_t *> tables(n_out);
     for (size_t i = 0; i < n_out; ++i)
     {
-        const uint32_t e = elts[i];
-        const size_t closed = e == 1 ? 1 : n >> (__builtin_ctz(e - 1) - 1);
-        form[n >= CDG_BLOCK && closed <= CDG_BLOCK].push_back((uint32_t)i);
-        MOAI_TRY(galois_table(c, e, &tables[i]));
+        MOAI_TRY(galois_table(c, elts[i], &tables[i]));
+    }
+    const std::vector<uint32_t> &gram = form[MOAI_CT_DOT_GALOIS_GRAM];
+    if (!gram.empty())
+    {
+        hipStream_t s = (hipStream_t)stream;
+        std::lock_guard<std::mutex> op_lock(*static_cast<std::mutex *>(c->op_mutex));
+        void *wsp;
+        MOAI_TRY(workspace(c, gram.size() * sizeof(CdgmOut), s, &wsp));
+        CdgmOut *outs = static_cast<CdgmOut *>(wsp);
+        MOAI_TRY(for_chunks(gram.size(), CDGM_WRITE, [&](size_t j0, size_t cnt) {
+            CdgmOutsArgs h;
+            for (size_t j = 0; j < (size_t)CDGM_WRITE; ++j)
+            {
+                const uint32_t oi = gram[j0 + (j < cnt ? j : 0)]; // the unused records repeat the chunk's first output; never written
+                h.e[j] = { tables[oi], oi, 0 };
+            }
+            hipLaunchKernelGGL(cdgm_outs_kernel, dim3(1), dim3(CDGM_WRITE), 0, s, h, outs + j0, (uint32_t)cnt);
+            MOAI_LAUNCH_CHECK();
+            return MOAI_OK;
+        }));
+        CdgmArgs m;
+        m.x = x;
+        m.w = w;
+        m.out = out;
+        m.terms = (uint32_t)terms;
+        m.count = (uint32_t)gram.size();
+        m.outs = outs;
+        fill_rows(m, c, L);
+        // one prime x one block of CDGM_BLOCK coefficients x one strip of 8 per workgroup: N / 8 <= 2^13 workgroups in x
+        hipLaunchKernelGGL(ct_dot_galois_mfma_kernel, dim3((uint32_t)(n / CDGM_BLOCK) * 16u, (uint32_t)L), dim3(256), 0, s, m);
+        MOAI_LAUNCH_CHECK();
     }
     CtDotGaloisArgs g;
     g.x = x;

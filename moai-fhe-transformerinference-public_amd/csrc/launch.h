@@ -29,6 +29,7 @@ namespace moai {
     X(MD_FP_MIN_ROWS, 256, "polynomials * L from which mod-down and rescale use the FP64 arithmetic modes")                    \
     X(MATMUL_FP, 1, "0: moai_ct_pt_matmul keeps primes below 2^51 on the integer kernel")                                      \
     X(MATMUL_MFMA, 0, "1: moai_ct_pt_matmul runs on the int8 matrix cores (byte limbs, exact) where N >= 16")                   \
+    X(CTDOT_GALOIS_MFMA, 0, "v > 0: outputs of moai_ct_dot_galois that permute inside blocks of 128 coefficients take the Gram form on the int8 matrix cores when a call has at least v of them") \
     X(DEC_TMP_MB, 1024, "MiB of scratch per chunk of moai_ckks_decode when the stream's arena is smaller")                     \
     X(CLIENT_TMP_KB, 1048576, "KiB of scratch per chunk of the encryption and key generation calls when the stream's arena is smaller") \
     X(HYBRID_TMP_KB, 16777216, "KiB of scratch per chunk of the hybrid key switch: sets how many ciphertexts of a batch are in flight") \

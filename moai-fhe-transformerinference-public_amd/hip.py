@@ -111,6 +111,7 @@ SYMBOLS = {
     "moai_apply_galois_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(vp), sz, vp]),
     "moai_relinearize_ptrs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, sz, vp]),
     "moai_ct_dot_galois": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_uint32), sz, sz, sz, vp]),
+    "moai_ct_dot_galois_forms": (C.c_int, [vp, C.POINTER(C.c_uint32), sz, sz, sz, C.POINTER(C.c_uint32)]),
     "moai_galois_fold": (C.c_int, [vp, vp, C.POINTER(vp), vp, sz, sz, vp]),
     "moai_hybrid_digits": (sz, [vp, sz, sz]),
     "moai_hybrid_fused_groups": (sz, [vp, sz, sz, sz]),
@@ -161,6 +162,7 @@ HYBRID_ROUND_FAST, HYBRID_ROUND_EXACT = 0, 1  # MOAI_HYBRID_ROUND_* of include/m
 MODE_LAZY16, MODE_LAZY8, MODE_GUARD2, MODE_GUARD, MODE_NOGUARD, MODE_FPN, MODE_FPR = -3, -2, -1, 0, 1, 2, 3
 MODE_OF_KEY_SWITCH, MODE_OF_MOD_DOWN, MODE_OF_NTT_FORWARD, MODE_OF_NTT_INVERSE = 0, 1, 2, 3
 MATMUL_PATH_INT, MATMUL_PATH_FP64, MATMUL_PATH_MFMA = 0, 1, 2  # moai_ct_pt_matmul_path
+CT_DOT_GALOIS_GATHER, CT_DOT_GALOIS_STAGED, CT_DOT_GALOIS_GRAM = 0, 1, 2  # moai_ct_dot_galois_forms
 
 
 class MoaiError(RuntimeError):
@@ -614,6 +616,13 @@ class Context:
         x, w [terms][2][L][N]"""
         e = (C.c_uint32 * max(1, len(elts)))(*[int(v) for v in elts])
         _check(lib().moai_ct_dot_galois(self.h, _ptr(x), _ptr(w), _ptr(out), e, len(elts), terms, L, stream))
+
+    def ct_dot_galois_forms(self, elts, terms, L):
+        """[gather, staged, Gram]: how many outputs ct_dot_galois would send to each form now (moai_ct_dot_galois_forms; no launch)"""
+        e = (C.c_uint32 * max(1, len(elts)))(*[int(v) for v in elts])
+        counts = (C.c_uint32 * 3)()
+        _check(lib().moai_ct_dot_galois_forms(self.h, e, len(elts), terms, L, counts))
+        return list(counts)
 
     def galois_fold(self, acc, keys, out, L, stream=None):
         """out[i] [3][L][N] = acc[i]'s (A0, A1) plus the key switches of B0 and B1 with keys[i]: what ct_dot_galois leaves to do"""

@@ -7,7 +7,9 @@ The operands are noise-free encryptions of messages below 2^10 under a ternary s
 before anything is timed three outputs of either order are decrypted under (1, s, s^2) on the device, the exact product
 sum_j m_X[j] pi(m_W[j]) is subtracted, and the centred error (the same integer in every row) is held against its bound: with E
 the bound of one moai_switch_key (include/moai_hip.h, the alpha = 1 case of the hybrid formula), E (1 + |s|_1) deferred and
-sum_j |m_X[j]|_1 E conventional."""
+sum_j |m_X[j]|_1 E conventional.
+With --sums only moai_ct_dot_galois is timed, on uniform residues and without keys: the integer forms against the Gram form on the
+int8 matrix cores (MOAI_CTDOT_GALOIS_MFMA), for 8 to 127 outputs (sums_only below)."""
 import os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -38,6 +40,45 @@ k, ctx = L + 1, m.Context(LOGN, primes)
 elts = [pow(5, 256 * i, 2 * N) for i in range(1, N_OUT + 1)]
 gen = torch.Generator(device=dev).manual_seed(11)
 q = torch.tensor(primes[:L], dtype=torch.int64, device=dev).view(L, 1)
+
+
+def sums_only():
+    """--sums: moai_ct_dot_galois alone on uniform residues, the integer forms (MOAI_CTDOT_GALOIS_MFMA=0) against the Gram form on
+    the int8 matrix cores (=1), alternating in one process after a warm-up call of each whose outputs must be equal words; the
+    first n_out of the 127 elements, to find the number of outputs from which the Gram form wins"""
+    knob, e0, e1 = "MOAI_CTDOT_GALOIS_MFMA", m.hip.Event(), m.hip.Event()
+    x, w = (torch.stack([torch.randint(0, p, (TERMS, 2, N), dtype=torch.int64, device=dev, generator=gen) for p in primes[:L]], dim=2).contiguous()
+            for _ in range(2))
+    print("\nmoai_ct_dot_galois alone, N = %d, terms = %d, %d data primes (51 + 14 x 46 bits); ms per call, median of %d windows of %d calls "
+          "(spread = (max - min) / median)" % (N, TERMS, L, REPS, CALLS))
+    print("%6s  %-22s %-22s %s" % ("n_out", "integer forms (knob 0)", "Gram form (knob 1)", "integer / Gram"))
+    for n_out in (8, 16, 32, 64, 96, 127):
+        out = [torch.empty((n_out, 4, L, N), dtype=torch.int64, device=dev) for _ in range(2)]
+        for v in (0, 1):
+            m.hip.set_tuning(knob, v)
+            assert ctx.ct_dot_galois_forms(elts[:n_out], TERMS, L) == ([0, 0, n_out] if v else [0, n_out, 0])
+            ctx.ct_dot_galois(x.data_ptr(), w.data_ptr(), out[v].data_ptr(), elts[:n_out], TERMS, L, stream=st)
+        torch.cuda.synchronize()
+        assert torch.equal(out[0], out[1]), "the two forms differ at n_out = %d" % n_out
+        t = ([], [])
+        for _ in range(REPS):
+            for v in (0, 1):
+                m.hip.set_tuning(knob, v)
+                e0.record(st)
+                for _ in range(CALLS):
+                    ctx.ct_dot_galois(x.data_ptr(), w.data_ptr(), out[v].data_ptr(), elts[:n_out], TERMS, L, stream=st)
+                e1.record(st)
+                torch.cuda.synchronize()
+                t[v].append(e1.elapsed_ms_since(e0) / CALLS)
+        med = [statistics.median(tv) for tv in t]
+        print("%6d  %-22s %-22s %.2f" % ((n_out,) + tuple("%.2f (%.1f %%)" % (md, 100 * (max(tv) - min(tv)) / md) for md, tv in zip(med, t)) + (med[0] / med[1],)))
+    m.hip.reset_tuning()
+    ctx.close()
+
+
+if "--sums" in sys.argv[1:]:
+    sums_only()
+    sys.exit(0)
 
 # the secret, one Galois key and one hoisting correction per element
 sk = ctx.sample_ternary(KEY, 3 << 40, 1, k)
